@@ -70,6 +70,24 @@ def cpu_baseline(pk_host, W, a, b, c, r, s, ped, log_n, gpu_proof_bytes):
             "proof_bytes_match": True, "proof_bytes_compared": len(cpu_bytes)}
 
 
+def dump_outputs(out_dir, proof, proof_bytes):
+    """--dump-outputs: what the caller of the timed path received from its last step, one float64 .npy file per array.
+    `proof_bytes` = the Proof.WriteTo bytes (one value 0..255 each).  Every other file holds BN254 field elements as rows of four
+    64-bit little-endian limbs, each limb split into its (low, high) 32-bit halves so that float64 holds it exactly: shape
+    (elements, 4, 2).  `proof_ar` = Ar (x, y), `proof_bs` = Bs (x.A0, x.A1, y.A0, y.A1), `proof_krs` = Krs (x, y); with a BSB22
+    commitment also `proof_commitment` (x, y) and `proof_pok` (x, y).  The proof is a few hundred bytes: nothing is sampled."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"proof_bytes": np.frombuffer(proof_bytes, dtype=np.uint8).astype(np.float64)}
+    for k in ("ar", "bs", "krs", "commitment", "pok"):
+        if k in proof:
+            limbs = np.asarray(proof[k], dtype=np.uint64).reshape(-1, 4)
+            arrays["proof_" + k] = np.stack([limbs & np.uint64(0xFFFFFFFF), limbs >> np.uint64(32)], axis=-1).astype(np.float64)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -109,8 +127,13 @@ def main():
                     help="multi-rank rehearsal on a 1-GPU box: every rank uses device 0, torch.distributed runs over gloo and the device group over its "
                          "host-staged transport (size the run to fit: e.g. --log-n 20 --sharded-msm-log-n 22 --sharded-prove-log-n 20)")
     ap.add_argument("--launch-check", action="store_true", help="only start the ranks, join them (gloo, no GPU) and print a one-line JSON summary: what the CPU test of the self-launch asserts")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned to its caller (the proof's points, the commitment and the "
+                         "proof bytes; rank 0) as DIR/<name>.npy in float64: the inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--sharded-helper", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.sharded_helper:
         return sharded_helper_main()
     if not args.launch_check:
@@ -253,13 +276,14 @@ def main():
         return B.proof_write(proof["raw"]) if not n_committed else B.proof_write(proof["raw"], cm.reshape(1, 8), proof["pok"])
 
     def one_step(with_c=False):
-        """the whole per-proof sequence of one caller (one goroutine of a prover service): Commit inside the solve, prove, WriteTo"""
+        """the whole per-proof sequence of one caller (one goroutine of a prover service): Commit inside the solve, prove, WriteTo.
+        Returns the proof bytes, the job's stats and the proof (with its commitment) as the caller holds it."""
         if not n_committed:
             proof, st = pool.wait(pool.submit(pkh, Wh, ah, bh, ch if with_c else None, rs[0], rs[1]))
-            return proof_bytes(proof, None), st
+            return proof_bytes(proof, None), st, proof
         cm = pool.commit(ped, values)
         proof, st = pool.wait(pool.submit_bsb22(pkh, Wh, ah, bh, ch if with_c else None, rs[0], rs[1], [(ped, values)], rs[2]))
-        return proof_bytes(proof, cm), st
+        return proof_bytes(proof, cm), st, dict(proof, commitment=cm)
 
     # untimed: size every context's workspaces (a pool job goes to whichever worker is free, so warm each one directly while
     # the workers are idle) and take the reference bytes from the plain entry points, one call at a time on context 0
@@ -287,7 +311,7 @@ def main():
     lat_host = lat_host_with_c = lat_commit = None
     for k in range(3):
         t1 = time.perf_counter()
-        bts, _ = one_step()
+        bts, _, _ = one_step()
         lat_host = (time.perf_counter() - t1) * 1e3
         if bts != serial_bytes:
             raise SystemExit("bench.py: the pool's host-input proof differs from the one-context reference proof of the same inputs")
@@ -296,7 +320,7 @@ def main():
     ch = c.download((n_constraints, 4))
     for k in range(2):
         t1 = time.perf_counter()
-        bts, _ = one_step(with_c=True)
+        bts, _, _ = one_step(with_c=True)
         lat_host_with_c = (time.perf_counter() - t1) * 1e3
         if bts != serial_bytes:
             raise SystemExit("bench.py: the host-input proof with c uploaded differs from the reference proof")
@@ -333,12 +357,14 @@ def main():
         dt = float(t.item())
     accum_ms, accum_pairs, accum_launches, accum_entries, last = 0.0, 0, 0, 0, None
     h2d = []
-    for bts, st in done:
+    for bts, st, _ in done:
         if bts != serial_bytes:   # every timed proof must be THE proof: same inputs, (r, s), committed values -> the reference bytes
             raise SystemExit("bench.py: a timed proof differs from the untimed reference proof of the same inputs")
         accum_ms += st["g1_accum_kernel_ms"]; accum_pairs += st["g1_accum_pairs"]; accum_launches += st["g1_accum_launches"]; accum_entries += st["g1_accum_entries"]; last = st
         h2d.append(st["h2d_ms"])
     h2d.sort()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, done[-1][2], done[-1][0])
 
     # second timed region: the same key with W, a, b, c ALREADY in HBM and no commitment (mi_prover_submit_dev, 164-byte proof body): the
     # GPU-side rate no caller of the reference can reach (its solver is CPU code) -- reported next to `value`, never as `value`

@@ -101,3 +101,73 @@ def test_clock_sampler_reads_rocm_smi_csv(monkeypatch):
     s._stop.set(); s._th.start()
     r = s.stop()
     assert r["samples"] == 2 and r["sclk_mhz_min"] == 2177 and r["sclk_mhz_max"] == 2201 and abs(r["package_power_w_mean"] - 1292.0) < 1e-9
+
+
+def _load_dump(d):
+    """bench.py --dump-outputs DIR back to integers: {name: uint64 limbs (elements, 4)}, plus the proof bytes"""
+    import numpy as np
+    got = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d) if f.endswith(".npy")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 << 20
+    out = {k: (a[..., 0].astype(np.uint64) | (a[..., 1].astype(np.uint64) << np.uint64(32))) for k, a in got.items() if k != "proof_bytes"}
+    return out, bytes(got["proof_bytes"].astype(np.uint8))
+
+
+def test_dump_outputs_hold_the_proof_exactly(tmp_path):
+    """--dump-outputs writes float64 files from which the caller's proof (points, commitment, PoK) and its bytes come back bit for bit:
+    the golden toy proof, alone (164 bytes) and with one BSB22 commitment (196 bytes), re-serialised by the oracle"""
+    import numpy as np
+    import cref
+    b = _bench_module()
+    z = np.load(os.path.join(ROOT, "tests", "golden", "prove_toy1000.npz"))
+    raw = np.concatenate([z["ar"], z["bs"], z["krs"]])
+    basis, sigma = cref.gen_g1(300, 5), cref.gen_g1(300, 6)
+    vals = cref.gen_scalars(300, 7, 1); ch = cref.gen_scalars(1, 8, 0)[0]
+    cm = cref.pedersen_msm(basis, vals)
+    pok = cref.pedersen_fold(cref.pedersen_msm(sigma, vals).reshape(1, 8), ch)
+    cases = (({"ar": z["ar"], "bs": z["bs"], "krs": z["krs"]}, cref.proof_write(raw), ["proof_ar", "proof_bs", "proof_krs", "proof_bytes"]),
+             ({"ar": z["ar"], "bs": z["bs"], "krs": z["krs"], "commitment": cm, "pok": pok}, cref.proof_write(raw, cm.reshape(1, 8), pok),
+              ["proof_ar", "proof_bs", "proof_krs", "proof_commitment", "proof_pok", "proof_bytes"]))
+    for i, (proof, pb, names) in enumerate(cases):
+        d = str(tmp_path / f"case{i}")
+        assert b.dump_outputs(d, proof, pb) == sorted(names)
+        got, got_bytes = _load_dump(d)
+        assert got_bytes == pb and len(pb) == (164 if i == 0 else 196)
+        assert got["proof_ar"].shape == (2, 4) and got["proof_bs"].shape == (4, 4) and got["proof_krs"].shape == (2, 4)
+        for k in proof:
+            assert np.array_equal(got["proof_" + k].reshape(-1), np.asarray(proof[k], dtype=np.uint64).reshape(-1)), k
+        back = np.concatenate([got["proof_ar"].reshape(-1), got["proof_bs"].reshape(-1), got["proof_krs"].reshape(-1)])
+        if i == 0:
+            assert cref.proof_write(back) == pb
+        else:
+            assert cref.proof_write(back, got["proof_commitment"].reshape(1, 8), got["proof_pok"].reshape(-1)) == pb
+
+
+def test_steps_below_one_are_refused():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--launch-check"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_timed_proof_and_repeat_from_run_to_run(tmp_path):
+    """bench.py --dump-outputs on a small key: the files hold the 196-byte proof of the last timed step (re-serialised through the
+    library's own WriteTo), and two runs with a different number of timed steps dump identical outputs (seeded inputs)"""
+    import numpy as np
+    from gpu_common import load_binding
+    B = load_binding()
+    small = ["--log-n", "14", "--warmup", "1", "--no-cpu-baseline", "--no-sensitivity", "--no-solo-legs", "--no-live-pmc", "--no-hbm-resident",
+             "--no-clock-samples", "--sharded-msm-log-n", "0", "--sharded-prove-log-n", "0"]
+    dumps = []
+    for steps in (2, 3):
+        d = str(tmp_path / f"steps{steps}")
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--dump-outputs", d] + small,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == steps and line["proofs_validated"].startswith(f"{steps} timed proofs") and line["proof_bytes"] == 196
+        dumps.append(_load_dump(d))
+    (got, pb), (got2, pb2) = dumps
+    assert len(pb) == 196 and pb == pb2 and got.keys() == got2.keys()
+    assert all(np.array_equal(got[k], got2[k]) for k in got)
+    raw = np.concatenate([got["proof_ar"].reshape(-1), got["proof_bs"].reshape(-1), got["proof_krs"].reshape(-1)])
+    assert B.proof_write(raw, got["proof_commitment"].reshape(1, 8), got["proof_pok"].reshape(-1)) == pb
