@@ -1,6 +1,7 @@
 // G2 instantiation of the MSM point kernels (see msm_curve_kernels.cuh, msm.hip) + the LDS-accumulator level-1 kernel.
 #include "msm_curve_kernels.cuh"
 #include "curve29_g2.cuh"
+#include "limb29_ops.cuh"
 
 // G2 level-1 accumulation with the XYZZ accumulator resident in LDS ([word][lane] image, 16 KiB per 64-lane
 // workgroup): only the operands of the current step live in VGPRs, so the kernel needs no scratch (the register
@@ -100,6 +101,25 @@ static __device__ __forceinline__ void g2x29_store_rp(const LdsAccG2_29 &A, bool
 #pragma unroll
         for (int q = 0; q < 4; q++) d4[4 * comp + q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
     }
+}
+// mi_debug_limb29_op_dev's G2 records (limb29_ops.cuh), one per lane, through the level kernels' own LDS accumulator image and store
+__global__ void __launch_bounds__(64) k_limb29_op_g2(int op, u32 *out, const u32 *in, size_t n) {
+    __shared__ u32 lds[72 * 64];
+    LdsAccG2_29 A{&lds[threadIdx.x]};
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32 *r = in + i * L29_IN_WORDS;
+    u32 *o = out + i * L29_OUT_WORDS;
+    for (int w = 0; w < L29_OUT_WORDS; w++) o[w] = 0;
+    if (op == L29_G2_STORE) {
+        for (int c = 0; c < 4; c++) A.st(c, F2_29{l29_get(r + 18 * c), l29_get(r + 18 * c + 9)});
+        g2x29_store_rp(A, (r[L29_FLAGS] & 1) != 0, reinterpret_cast<G2X *>(o));   // 64 words, 16-byte aligned (records are 320 bytes)
+        return;
+    }
+    (void)limb29_op_g2(op, A, r, o);
+}
+void launch_limb29_op_g2(hipStream_t st, unsigned grid, int op, u32 *out, const u32 *in, size_t n) {
+    hipLaunchKernelGGL(k_limb29_op_g2, dim3(grid), dim3(64), 0, st, op, out, in, n);
 }
 // WG = waves per workgroup (each wave has its own 18 KiB accumulator image)
 template <int WG>

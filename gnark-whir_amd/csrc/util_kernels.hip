@@ -3,6 +3,7 @@
 // two can be compared bit for bit), and VALU / modular-multiply throughput probes.
 #include "ctx.h"
 #include "curve.cuh"
+#include "limb29_ops.cuh"
 
 // ---------------------------------------------------------------- seeded PRNG (counter based)
 MI_HD u64 sm64(u64 z) {
@@ -183,6 +184,16 @@ __global__ void k_bench_valu(int kind, u32 iters, u64 *sink) {
     if (r == 0x123456789abcdefull) sink[0] = r;
 }
 
+// mi_debug_limb29_op_dev: one record of limb29_ops.cuh per lane (primitives and G1 steps here; the G2 steps in msm_g2.hip)
+__global__ void __launch_bounds__(64) k_limb29_op_g1(int op, u32 *out, const u32 *in, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 *o = out + i * L29_OUT_WORDS;
+    for (int w = 0; w < L29_OUT_WORDS; w++) o[w] = 0;
+    (void)limb29_op_g1(op, in + i * L29_IN_WORDS, o);
+}
+void launch_limb29_op_g2(hipStream_t st, unsigned grid, int op, u32 *out, const u32 *in, size_t n);   // msm_g2.hip
+
 static inline unsigned grid_for(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
 extern "C" {
@@ -209,6 +220,16 @@ int32_t mi_field_op_dev(mi_ctx *ctx, int field, int op, void *z, const void *x, 
     if (!n) return MI_OK;
     if (field == 0) hipLaunchKernelGGL(k_field_op<FrParams>, dim3(grid_for(n, 128)), dim3(128), 0, ctx->stream, op, (Fr *)z, (const Fr *)x, (const Fr *)y, n);
     else hipLaunchKernelGGL(k_field_op<FpParams>, dim3(grid_for(n, 128)), dim3(128), 0, ctx->stream, op, (Fp *)z, (const Fp *)x, (const Fp *)y, n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+int32_t mi_debug_limb29_op_dev(mi_ctx *ctx, int op, void *out_dev, const void *in_dev, size_t n) {
+    const bool g1 = (op >= 0 && op < L29_PRIM_END) || (op >= L29_G1_MADD && op <= L29_G1_STORE);
+    const bool g2 = op >= L29_G2_MADD && op < L29_OP_END;
+    if (!ctx || !(g1 || g2) || ((!out_dev || !in_dev) && n) || n > ((size_t)1 << 30)) return MI_EINVAL;
+    if (!n) return MI_OK;
+    if (g1) hipLaunchKernelGGL(k_limb29_op_g1, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, op, (u32 *)out_dev, (const u32 *)in_dev, n);
+    else launch_limb29_op_g2(ctx->stream, grid_for(n, 64), op, (u32 *)out_dev, (const u32 *)in_dev, n);
     MI_CHECK_HIP(ctx, hipGetLastError());
     return MI_OK;
 }

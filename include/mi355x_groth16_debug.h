@@ -29,6 +29,14 @@ int32_t mi_g1_add_dev(mi_ctx *ctx, mi_g1_affine *out_dev, const mi_g1_affine *a_
                       const mi_g1_affine *b_dev, size_t n);
 int32_t mi_g2_add_dev(mi_ctx *ctx, mi_g2_affine *out_dev, const mi_g2_affine *a_dev,
                       const mi_g2_affine *b_dev, size_t n);
+/* the 29-bit-limb arithmetic of the level-1 bucket accumulation (csrc/field29.cuh, curve29.cuh, curve29_g2.cuh), one record per lane:
+ * in_dev holds n records of MI_LIMB29_IN_WORDS u32, out_dev receives n of MI_LIMB29_OUT_WORDS (words an op does not write are zero).  op and
+ * layout are those of csrc/limb29_ops.cuh, which the host build of the tests runs too: 0..16 the primitives over Fp, 20..22 the G1 steps
+ * (mixed addition, full addition of a stored partial sum, store + load), 23..25 the G2 steps through the level kernels' LDS accumulator.
+ * Every input must meet the documented contract of its primitive.  MI_EINVAL for an unknown op, null buffers or n > 2^30. */
+#define MI_LIMB29_IN_WORDS 144
+#define MI_LIMB29_OUT_WORDS 80
+int32_t mi_debug_limb29_op_dev(mi_ctx *ctx, int op, void *out_dev, const void *in_dev, size_t n);
 /* random-gather throughput probe: n_threads lanes each chain `iters` dependent 64-byte gathers from a table of n_entries
  * (a power of two) 64-byte entries; scratch: 1 KiB.  The ceiling the level-1 bucket accumulation's point gathers run against. */
 int32_t mi_bench_gather_dev(mi_ctx *ctx, const void *table_dev, size_t n_entries, size_t n_threads, uint32_t iters,

@@ -159,31 +159,45 @@ extern "C" int emu_g2_rp_levels(void *out_aff, const void *pts_std, const unsign
     *(G2Aff *)out_aff = xyzz_to_affine(s);
     return 0;
 }
-// raw primitives of field29.cuh on limb vectors chosen by the test (9 x u32 each); field 1 = Fp, 0 = Fr
-extern "C" int emu_f29_prim(int field, int op, u32 *out, const u32 *a, const u32 *b, const u32 *c, const u32 *d) {
+// raw primitives of field29.cuh on limb vectors chosen by the test (9 x u32 each; e..h only for f29_mul4, may be null); field 1 = Fp, 0 = Fr.
+// The Fp ops are limb29_ops.cuh's (the numbering of mi_debug_limb29_op_dev); out gets nine words.
+#include "../../gnark-whir_amd/csrc/limb29_ops.cuh"
+extern "C" int emu_f29_prim(int field, int op, u32 *out, const u32 *a, const u32 *b, const u32 *c, const u32 *d, const u32 *efgh) {
+    if (field == 1) {
+        if (op < 0 || op >= L29_PRIM_END) return -1;
+        u32 in[L29_IN_WORDS] = {}, res[L29_OUT_WORDS] = {};
+        memcpy(in, a, 36); memcpy(in + 9, b, 36); memcpy(in + 18, c, 36); memcpy(in + 27, d, 36);
+        if (efgh) memcpy(in + 36, efgh, 144);
+        if (limb29_op_g1(op, in, res)) return -1;
+        memcpy(out, res, 36);
+        return 0;
+    }
     F29 A, B, C, D, R;
     memcpy(A.l, a, 36); memcpy(B.l, b, 36); memcpy(C.l, c, 36); memcpy(D.l, d, 36);
-    if (field == 1) {
-        switch (op) {
-        case 0: R = f29_mul<FpParams>(A, B); break;
-        case 1: R = f29_mul2<FpParams>(A, B, C, D); break;
-        case 2: R = f29_sub<FpParams>(A, B, P29<FpParams>::c8); break;
-        case 3: R = f29_sub<FpParams>(A, B, P29<FpParams>::c4); break;
-        case 4: R = f29_sub<FpParams>(A, B, P29<FpParams>::c2); break;
-        case 5: R = f29_wnorm(A); break;
-        case 6: R = f29_condsub(A, P29<FpParams>::p4); break;
-        case 7: R = f29_condsub(A, P29<FpParams>::p2); break;
-        case 8: R = f29_sqr<FpParams>(A); break;
-        default: return -1;
-        }
-    } else {
-        switch (op) {
-        case 0: R = f29_mul<FrParams>(A, B); break;
-        case 1: R = f29_mul2<FrParams>(A, B, C, D); break;
-        default: return -1;
-        }
+    switch (op) {
+    case 0: R = f29_mul<FrParams>(A, B); break;
+    case 1: R = f29_mul2<FrParams>(A, B, C, D); break;
+    default: return -1;
     }
     memcpy(out, R.l, 36);
+    return 0;
+}
+// records of limb29_ops.cuh, n of them: the host twin of mi_debug_limb29_op_dev (same op numbers, same layout)
+extern "C" int emu_limb29_op(int op, u32 *out, const u32 *in, size_t n) {
+    if (op < 0 || op >= L29_OP_END) return -1;
+    for (size_t i = 0; i < n; i++) {
+        const u32 *r = in + i * L29_IN_WORDS;
+        u32 *o = out + i * L29_OUT_WORDS;
+        memset(o, 0, L29_OUT_WORDS * 4);   // words an op does not write stay zero (the device does the same)
+        if (op == L29_G2_STORE) {   // what g2x29_store_rp (msm_g2.hip) writes: f2_29_pack per component, infinity = all zero
+            if (!(r[L29_FLAGS] & 1))
+                for (int c = 0; c < 4; c++) f2_29_pack(F2_29{l29_get(r + 18 * c), l29_get(r + 18 * c + 9)}, o + 16 * c);
+            continue;
+        }
+        RegAccG2_29 A{};
+        const int rc = op >= L29_G2_MADD ? limb29_op_g2(op, A, r, o) : limb29_op_g1(op, r, o);
+        if (rc) return rc;
+    }
     return 0;
 }
 extern "C" int emu_f29_roundtrip(void *out_std, const void *in_std, size_t n, int field) {   // std -> R' limbs -> std, and a product in both

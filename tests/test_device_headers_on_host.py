@@ -9,6 +9,7 @@ import pytest
 import pyref as P
 import cref
 from helpers import *
+import limb29_cases as L29
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -105,13 +106,11 @@ def test_limb29_primitives_at_their_documented_bounds(emu):
     values up to 8p x 8p), against Python big integers; the emu build traps on any 64-bit column overflow or limb underflow"""
     M29 = (1 << 29) - 1
     rng = np.random.default_rng(17)
-    def val(l):
-        return sum(int(x) << (29 * i) for i, x in enumerate(l))
-    def limbs_of(v):
-        return [(v >> (29 * i)) & M29 for i in range(8)] + [v >> 232]
-    def call(field, op, a, b=None, c=None, d=None):
+    from limb29_cases import val, limbs_of, words_of, words_val
+    def call(field, op, a, b=None, c=None, d=None, efgh=None):
         z = [0] * 9
         arrs = [np.array(x if x is not None else z, dtype=np.uint32) for x in (a, b, c, d)]
+        arrs.append(np.array(efgh if efgh is not None else z * 4, dtype=np.uint32))
         out = np.zeros(9, np.uint32)
         assert emu.emu_f29_prim(field, op, _p(out), *[_p(x) for x in arrs]) == 0
         return [int(x) for x in out]
@@ -151,6 +150,99 @@ def test_limb29_primitives_at_their_documented_bounds(emu):
                     got = call(1, op, limbs_of(v))
                     r = val(call(1, 5, got))
                     assert r % mod == v % mod and r <= max(v - K * mod, K * mod + (1 << 233)) and r >= 0 and r < K * mod + (1 << 234)
+    # the primitives without a caller-visible test of their own (the numbering is limb29_ops.cuh's, shared with mi_debug_limb29_op_dev)
+    mod = P.Q_MOD
+    W, N31 = (1 << 29) + 7, (1 << 31) - 1
+    Ri = pow(1 << 261, -1, mod)
+    def weak_max(V):   # limbs 0..7 at the weak cap 2^29 + 7, the top limb as large as V p allows
+        l = [W] * 8 + [0]
+        l[8] = (V * mod - val(l)) >> 232
+        assert val(l) < V * mod
+        return l
+    # f29_mul4: every operand weak (limbs 2^29 + 7), values up to 8p, on multiples of p, zero; value < (sum of VV / 128 + 1) p, normalised
+    ops8 = [weak_max(8), weak_max(8), limbs_of(8 * mod - 1), weak_max(8), weak_max(8), limbs_of(mod), limbs_of(7 * mod), weak_max(8)]
+    sets = [ops8, [weak_max(8)] * 8, [limbs_of(0)] * 8, [limbs_of(k * mod) for k in (1, 2, 3, 4, 5, 6, 7, 8)],
+            [weak_max(8), limbs_of(0)] * 4, [weak_max(2), weak_max(8), weak_max(5), weak_max(3), weak_max(8), weak_max(8), weak_max(1), weak_max(7)]]
+    for t in range(20):
+        sets.append([[int(v) for v in rng.integers(0, W + 1, 8)] + [int(rng.integers(0, 1 << 27))] for _ in range(8)])
+    for ops in sets:
+        vs = [val(o) for o in ops]
+        got = call(1, 9, *ops[:4], efgh=sum(ops[4:], []))
+        s_ = vs[0] * vs[1] + vs[2] * vs[3] + vs[4] * vs[5] + vs[6] * vs[7]
+        assert val(got) % mod == s_ * Ri % mod and all(g <= M29 for g in got[:8]) and val(got) < s_ // (1 << 261) + mod + 1, ops
+        vb = [-(-v // mod) for v in vs]
+        assert val(got) < (sum(vb[2 * k] * vb[2 * k + 1] for k in range(4)) / 128 + 1) * mod
+    # f29_norm: limbs up to 2^31 - 1 -> limbs 0..7 < 2^29, same value
+    for l in ([N31] * 8 + [0], [N31] * 8 + [1 << 20], [M29 + 1] * 8 + [5], limbs_of(0), weak_max(8)):
+        got = call(1, 10, l)
+        assert val(got) == val(l) and all(g <= M29 for g in got[:8]), l
+    # f29_unpack / f29_pack: 8 x u32 words <-> nine limbs, exact at 2^256 - 1, p, 0 and random words
+    for v in [(1 << 256) - 1, 0, mod, mod - 1, 5 * mod, (1 << 232) - 1, 1 << 232, (1 << 255)] + [int(rng.integers(0, 1 << 62)) << 190 | int(rng.integers(0, 1 << 62)) for _ in range(10)]:
+        w = words_of(v)
+        l = call(1, 11, w + [0])
+        assert l == limbs_of(v), v
+        assert call(1, 12, l)[:8] == w, v
+    # f29_to_std at the claimed V <= 128 (weak limbs, multiples of p) -> canonical standard form; f29_from_std back, < 1.01 p
+    for v_l in (weak_max(128), limbs_of(128 * mod - 1), limbs_of(0), limbs_of(mod), limbs_of(127 * mod), limbs_of(64 * mod + 12345), weak_max(1)):
+        v = val(v_l)
+        assert v < 128 * mod
+        got = call(1, 13, v_l)
+        plain = v * Ri % mod
+        assert words_val(got[:8]) == P.fp_to_mont(plain), v
+        back = call(1, 14, got[:8] + [0])
+        assert val(back) % mod == v % mod and all(g <= M29 for g in back[:8]) and val(back) < 1.01 * mod
+    # f29_below_2p on values below 6.1 p (weak limbs): same residue, "almost < 2p" (below 2p + 2^233), weak afterwards
+    for v_l in (limbs_of(0), limbs_of(2 * mod), limbs_of(2 * mod - 1), limbs_of(4 * mod - 1), limbs_of(4 * mod), limbs_of(6 * mod),
+                limbs_of(int(6.1 * mod) - 1), weak_max(6), limbs_of(2 * mod + (1 << 232)), limbs_of(4 * mod + (1 << 232) + 1), limbs_of(6 * mod + (1 << 240))):
+        v = val(v_l)
+        got = call(1, 15, v_l)
+        assert val(got) % mod == v % mod and val(got) < 2 * mod + (1 << 233) and all(g <= M29 + 8 for g in got[:8]), v
+    # f2_29_is_zero_mod_p: normalised components below 2.1 p; zero iff each is 0, p or 2p
+    zeros = [limbs_of(0), limbs_of(mod), limbs_of(2 * mod)]
+    nonzero = [limbs_of(1), limbs_of(mod + 1), limbs_of(2 * mod - 1), limbs_of(mod - 1), limbs_of(2 * mod + 1), limbs_of(int(2.09 * mod))]
+    for a in zeros + nonzero:
+        for b in zeros + nonzero:
+            want = int(val(a) % mod == 0 and val(b) % mod == 0)
+            assert call(1, 16, a, b)[0] == want, (val(a), val(b))
+
+
+def test_limb29_bounds_replay_covers_g1_and_g2():
+    """tools/f29_bounds.py: the worst-case replay of every step of both curves (products incl. f29_mul4, lazy subtractions, conditional
+    subtractions, the special-case tests, store / load of partial sums, to_std) holds, and its fixed points lie inside the invariants the
+    adversarial tests below start from"""
+    fb = L29.bounds()
+    res = fb.replay()
+    for key, inv in (("g1_madd", fb.G1_ACC), ("g1_add", fb.G1_ACC), ("g2_madd", fb.G2_ACC), ("g2_add", fb.G2_ACC)):
+        for b, (V, _) in zip(res[key], inv.values()):
+            for c in (b if isinstance(b, tuple) else (b,)):
+                assert c.V <= V, (key, c.name, c.V, V)
+    assert fb.G1_LOADED["X"][0] < fb.TWO256 and fb.G2_ACC["Y"][0] < fb.TWO256
+
+
+def test_limb29_group_steps_from_adversarial_states(emu):
+    """g1x29_madd / g1x29_add / g1x29_store_rp -> load_rp, g2x29_madd / g2x29_add / the G2 partial-sum store, started from explicit accumulator
+    states at the edges of the invariants tools/f29_bounds.py proves (a point scaled by l^2, l^3, every coordinate pushed up by multiples of
+    p; weak X limbs): generic additions, a negated operand, equal x (doubling), opposite points (cancellation), infinite operands and
+    accumulators -- against pyref in affine form, every result back inside the invariant.  Runs in a child process: a trap of the host build
+    (MI_CHECK_NOWRAP) fails the test with the case's name."""
+    cases = L29.group_cases(seed=5, per_kind=4)
+    outs = L29.run_group_cases(emu._name, cases)
+    bad = L29.check_group_outputs(cases, outs)
+    assert not bad, "\n".join(bad)
+
+
+def test_limb29_products_on_random_edge_operands(emu):
+    """f29_mul / f29_sqr / f29_mul2 / f29_mul4 on operands whose limbs and values sit on the contract's edges (weak limbs of 2^29 + 7,
+    limbs up to 2^31 - 1 against normalised ones, top limbs at the value bound 8p), in a child process: no trap, the value mod p and a
+    normalised result below (sum of products / 2^261 + p)"""
+    for op in (L29.MUL, L29.SQR, L29.MUL2, L29.MUL4):
+        recs = L29.product_records(op, 3000, 40 + op)
+        out, err = L29.run_emu(emu._name, op, recs)
+        assert err is None, err
+        for r, o in zip(recs, out):
+            want, s_ = L29.product_value(op, [int(x) for x in r])
+            v = L29.val([int(x) for x in o[:9]])
+            assert v % P.Q_MOD == want and all(int(x) <= L29.M29 for x in o[:8]) and v < s_ // (1 << 261) + P.Q_MOD + 1, (op, r)
 
 
 def test_limb29_mixed_addition_chain_matches_oracle(emu):
