@@ -82,3 +82,19 @@ def test_census_of_a_concrete_params_file():
     assert info["transcript_len"] == cfg["transcript_len"]
     txt = wc.report_config(cfg, None, 1)
     assert "ASSUMED" in txt and "--dist mix:" in txt
+
+
+def test_census_masks_are_the_midpoint_of_the_scenarios_membership():
+    """census_masks_permille(): the infinity masks of a key for this circuit, the midpoint of the L / R membership over the scenarios that pad
+    to 2^23 -- between the default scenario's 30 % / 71 % (profiles/r06_wire_census.txt) and the other end of the grid, and far from the
+    benchmark's 90 % / 50 %"""
+    S, _, _, _ = wc.census_range()
+    fa = [s["ab"][0] / s["ab"][2] for s in S]
+    fb = [s["ab"][1] / s["ab"][2] for s in S]
+    in_a, in_b = wc.census_masks_permille()
+    assert (in_a, in_b) == (round(500 * (min(fa) + max(fa))), round(500 * (min(fb) + max(fb))))
+    assert 1000 * min(fa) <= in_a <= 1000 * max(fa) and 1000 * min(fb) <= in_b <= 1000 * max(fb)
+    assert 300 <= in_a <= 480 and 550 <= in_b <= 710 and in_a < in_b
+    E, _ = wc.census(wc.Params())
+    ab = wc.totals(E, "lo")[4]
+    assert (round(100 * ab[0] / ab[2]), round(100 * ab[1] / ab[2])) == (30, 71)

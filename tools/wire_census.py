@@ -363,6 +363,18 @@ def census_mix_permille():
     return tuple(census_range()[3][k] for k in ("bit", "byte", "u64"))
 
 
+def census_masks_permille(target_log_n=23):
+    """(in_a, in_b) per-mille: the share of wires on an L side (pk.G1.A not infinity) and on an R side (pk.G1.B / G2.B not infinity), the
+    midpoint of the range over the scenarios that pad to 2^target_log_n, from the A / B membership totals() states -- the infinity masks
+    of a proving key for this circuit, as census_mix_permille() is its witness mix"""
+    S = census_range(target_log_n)[0]
+    out = []
+    for k in (0, 1):
+        f = [s["ab"][k] / s["ab"][2] for s in S]
+        out.append(int(round(500 * (min(f) + max(f)))))
+    return tuple(out)
+
+
 def report():
     L = []
     P = L.append
