@@ -66,6 +66,7 @@ struct mi_ctx {
     // (msm2_sort_enqueue) then skips its own count pass: h is read once less.  Disarmed again as soon as the launch is enqueued.
     // Behind the knob "z_count_fused" (on by default: throughput equal, a single proof slightly shorter).
     // (only slot MI_ZHOOK_SLOT -- prove's Z MSM -- ever looks at it, and the thread that arms it is the one that enqueues that slot)
+    std::atomic<uint64_t> generic_sorts_two_pass{0}, generic_sorts_one_pass{0};   // generic MSM sorts by kind (msm.hip msm_sort_enqueue)
     std::atomic<uint64_t> dense_item_sorts{0};   // accumulations whose item size the dense-sort rule chose (msm.hip; helper threads enqueue too)
     uint64_t z_count_fused_launches = 0;   // computeH last launches that carried the count (mi_debug_get_counter: the tests' proof that the path ran)
     struct ZCountHook { bool armed = false, done = false; int slot = -1; uint32_t n = 0, c = 0; alignas(8) unsigned char shape[64]; uint32_t *C1 = nullptr; const void *h = nullptr; /* the vector whose digits were counted */ } zhook;
@@ -85,6 +86,9 @@ static inline void mi_set_err(struct mi_ctx *ctx, const std::string &msg);
     do {                                                                                              \
         hipError_t e__ = mi_fault_hit() ? hipErrorUnknown : (call);                                   \
         if (e__ != hipSuccess) {                                                                      \
+            /* a failed allocation also leaves itself as the thread's last error: clear it, or the next   \
+               launch check (hipGetLastError) reports this out-of-memory as its own failure */            \
+            if (e__ == hipErrorOutOfMemory) (void)hipGetLastError();                                  \
             mi_set_err((ctx), std::string(#call) + ": " + hipGetErrorString(e__));                    \
             return e__ == hipErrorOutOfMemory ? MI_ENOMEM : MI_EHIP;                                  \
         }                                                                                             \

@@ -448,6 +448,8 @@ extern "C" int32_t mi_debug_get_counter(mi_ctx *ctx, const char *name, uint64_t 
     if (!ctx || !name || !out) return MI_EINVAL;
     if (!std::strcmp(name, "z_count_fused_launches")) { *out = ctx->z_count_fused_launches; return MI_OK; }
     if (!std::strcmp(name, "dense_item_sorts")) { *out = ctx->dense_item_sorts.load(); return MI_OK; }
+    if (!std::strcmp(name, "generic_sorts_two_pass")) { *out = ctx->generic_sorts_two_pass.load(); return MI_OK; }
+    if (!std::strcmp(name, "generic_sorts_one_pass")) { *out = ctx->generic_sorts_one_pass.load(); return MI_OK; }
     MI_FAIL(ctx, MI_EINVAL, std::string("unknown counter: ") + name);
 }
 extern "C" int32_t mi_debug_set_stream_plan(int32_t plan) {
@@ -680,7 +682,11 @@ static int32_t msm_sort_enqueue(mi_ctx *ctx, MsmSlot &sl, const Fr *scalars, u32
     // entry as a partial line of its own (PMC round 1: 4.1 GB written for 0.5 GB of entries at 2^23 pairs); the two-pass
     // sort stages runs through LDS and walks its chunks XCD by XCD (1.5x).  Same entries, same order inside a key up to the
     // order of LDS atomics -- which the sums do not depend on.
-    if (sl.c == 16 && !kn->one_pass_sort && n >= (1u << 18) && (u64)n * 16 < ((u64)1 << 31)) return msm2_sort_enqueue(ctx, sl, scalars, n, flags, 16, true, exact);
+    if (sl.c == 16 && !kn->one_pass_sort && n >= (1u << 18) && (u64)n * 16 < ((u64)1 << 31)) {
+        ctx->generic_sorts_two_pass++;
+        return msm2_sort_enqueue(ctx, sl, scalars, n, flags, 16, true, exact);
+    }
+    ctx->generic_sorts_one_pass++;
     sl.G = kn->G ? kn->G : (n / 8192 > 64 ? 64 : (n / 8192 ? n / 8192 : 1));
     const MsmShape s = slot_shape(sl);
     sl.nwin_keys = sl.nwin_digits = s.nwin;
@@ -977,7 +983,7 @@ int32_t mi_msm_enqueue(mi_ctx *ctx, int slot, int sort_slot, int curve, const vo
     if (slot < 0 || slot >= MI_MSM_SLOTS || sort_slot >= MI_MSM_SLOTS) return MI_EINVAL;
     static const char *const range_names[MI_MSM_SLOTS] = {"mi.msm.A.enqueue", "mi.msm.B1.enqueue", "mi.msm.B2.enqueue", "mi.msm.K.enqueue", "mi.msm.Z.enqueue", "mi.msm.PoK.enqueue"};
     const MiRange range(range_names[slot]);
-    if (n > ((size_t)1 << 27)) MI_FAIL(ctx, MI_EINVAL, "msm: n > 2^27 pairs per device not supported (shard the points)");
+    if (n > MI_MSM_MAX_PAIRS) MI_FAIL(ctx, MI_EINVAL, "msm: n > 2^27 pairs per device not supported (shard the points)");
     MsmSlot &sl = ctx->msm[slot];
     const std::function<hipEvent_t()> *gate_once = sl.accum_gate;   // valid for this call only, whatever path it takes
     sl.accum_gate = nullptr;

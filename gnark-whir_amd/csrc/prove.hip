@@ -44,6 +44,11 @@ int32_t mi_pk_load_range(mi_ctx *ctx, const mi_pk_desc *d, mi_pk **out, bool dev
     const u64 w_lo = sr ? sr->w_lo : 0, w_hi = sr ? sr->w_hi : d->nb_wires;
     const u64 z_lo = sr ? sr->z_lo : 0, z_hi = sr ? sr->z_hi : N - 1;
     if (w_lo > w_hi || w_hi > d->nb_wires || z_lo > z_hi || z_hi > N - 1) MI_FAIL(ctx, MI_EINVAL, "pk: bad shard range");
+    // one device runs every MSM of its part, and a single-device MSM takes at most 2^27 pairs (mi_msm_enqueue): A and K run over the
+    // part's wires, B over a subset of them, Z over its Z range.  Refused here, before anything is allocated or enqueued.
+    if (w_hi - w_lo > MI_MSM_MAX_PAIRS || z_hi - z_lo > MI_MSM_MAX_PAIRS)
+        MI_FAIL(ctx, MI_EINVAL, "pk: a per-device MSM would exceed 2^27 pairs (log_n = 28, or more than 2^27 wires on one device): "
+                                "load the key with mi_pk_load_sharded over enough devices");
     std::vector<u32> ia, ib, ik;
     u64 ci = 0, ca = 0, cb = 0, ck = 0, a0 = 0, b0 = 0, k0 = 0;
     for (u64 j = 0; j < d->nb_wires; j++) {

@@ -66,14 +66,21 @@ typedef struct mi_pk mi_pk;
                                natural in, bit-reversed out */
 
 /* ---- MSM flags ---- */
+#define MI_MSM_MAX_PAIRS (1ull << 27) /* pairs one device takes in one MSM (mi_msm_*, and every MSM of a
+                                         key that mi_pk_load[_dev] / each part of a sharded key holds) */
 #define MI_MSM_SCALARS_CANONICAL 1u /* scalars are plain integers < r (default: Montgomery) */
 
 /* Proving key as gnark keeps it in memory (groth16/bn254 ProvingKey, built by groth16.Setup at
  * mt.go:448).  All arrays are read during mi_pk_load only. */
 typedef struct mi_pk_desc {
-    uint32_t log_n;                 /* pk.Domain.Cardinality = 2^log_n, log_n <= 28          */
+    uint32_t log_n;                 /* pk.Domain.Cardinality = 2^log_n, log_n <= 28; one
+                                       device takes log_n <= 27 (its Z MSM has 2^log_n - 1
+                                       pairs, at most MI_MSM_MAX_PAIRS): log_n = 28 loads
+                                       with mi_pk_load_sharded only                           */
     uint32_t nb_public;             /* r1cs.GetNbPublicVariables(), includes the ONE wire     */
-    uint64_t nb_wires;              /* len(solution.W)                                        */
+    uint64_t nb_wires;              /* len(solution.W), < 2^31; one device takes at most
+                                       MI_MSM_MAX_PAIRS (the A and K MSMs run over every
+                                       wire): larger keys load with mi_pk_load_sharded        */
     const mi_g1_affine *g1_a;  uint64_t n_g1_a;   /* pk.G1.A, points at infinity filtered out */
     const mi_g1_affine *g1_b;  uint64_t n_g1_b;   /* pk.G1.B, idem                            */
     const mi_g1_affine *g1_k;  uint64_t n_g1_k;   /* pk.G1.K, private non-committed wires     */

@@ -29,6 +29,7 @@ ADD, SUB, MUL, INV = 0, 1, 2, 3
 ONE = fr_arr([1])[0]
 ZERO = np.zeros(4, np.uint64)
 EDGE_WIDTHS = (16, 17, 18, 19, 20, 22)
+CHUNK_BITS = 22
 G1 = g1_arr([P.G1_GEN])[0]
 G2 = g2_arr([P.G2_GEN])[0]
 
@@ -233,19 +234,50 @@ def constraint_values(n_constraints, dist, seed):
 
 
 # ---------------------------------------------------------------------------------------------------- the proof in the exponent
-def expected_proof_exps(exps, W, a, b, r, s):
-    """-> (ar, bs, krs) as canonical integers, by the formulas of the module docstring (c = a o b)"""
+def z_exps_bitrev(exps, chunk_bits=CHUNK_BITS):
+    """z_exps in the bit-reversed order pk.G1.Z is stored in, built chunk by chunk (no N-row index array, no second N-row copy): slot
+    h m + lo holds the exponent of i = bitrev_cb(lo) 2^(log_n - cb) + bitrev(h), i.e. (tau^(2^(log_n - cb)))^bitrev_cb(lo) tau^bitrev(h)"""
+    L = exps["log_n"]
+    cb = min(L, chunk_bits)
+    m, hi = 1 << cb, L - cb
+    tau = _int(exps["tau"])
+    zt = (pow(tau, 1 << L, P.R_MOD) - 1) * P.fr_inv(_int(exps["delta"])) % P.R_MOD
+    tab = powers(fr_arr([pow(tau, 1 << hi, P.R_MOD)])[0], m)[bitrev_index(cb)]
+    out = np.empty((1 << L, 4), np.uint64)
+    for h in range(1 << hi):
+        out[h * m:(h + 1) * m] = _op(MUL, tab, _bc(fr_arr([zt * pow(tau, P.bitrev(h, hi), P.R_MOD)])[0], m))
+    return out
+
+
+def _masked_dot(W, X, keep, chunk):
+    acc = ZERO.copy()
+    for lo in range(0, len(keep), chunk):
+        k = keep[lo:lo + chunk]
+        acc = _op(ADD, acc.reshape(1, 4), fr_dot(W[lo:lo + chunk][k], X[lo:lo + chunk][k]).reshape(1, 4))[0]
+    return acc
+
+
+def expected_proof_exps(exps, W, a, b, r, s, chunk=1 << CHUNK_BITS):
+    """-> (ar, bs, krs) as canonical integers, by the formulas of the module docstring (c = a o b).  Vector work runs `chunk` rows at a
+    time, so host memory beyond the inputs stays O(chunk) whatever N is."""
     N = 1 << exps["log_n"]
-    ia, ib = exps["infinity_a"] == 0, exps["infinity_b"] == 0
-    kr = k_rows(exps)
-    sa = fr_dot(W[ia], exps["A"][ia])
-    sb = fr_dot(W[ib], exps["B"][ib])
-    sk = fr_dot(W[kr], exps["K"][kr])
+    nw = exps["nb_wires"]
+    ia, ib = exps["infinity_a"][:nw] == 0, exps["infinity_b"][:nw] == 0
+    keep_k = np.zeros(nw, bool)
+    keep_k[k_rows(exps)] = True
+    sa = _masked_dot(W, exps["A"], ia, chunk)
+    sb = _masked_dot(W, exps["B"], ib, chunk)
+    sk = _masked_dot(W, exps["K"], keep_k, chunk)
     dom = P.Domain(N)
-    wp = powers(fr_arr([dom.gen])[0], N)
-    lw = _op(MUL, wp, batch_inv(_op(SUB, _bc(exps["tau"], N), wp)))          # w^i / (tau - w^i)
     nc = a.shape[0]
-    at, bt, ct = (_int(fr_dot(v, lw[:nc])) for v in (a, b, _op(MUL, a, b)))
+    at = bt = ct = 0
+    wtab = powers(fr_arr([dom.gen])[0], min(chunk, nc)) if nc else None
+    for lo in range(0, nc, chunk):
+        m = min(chunk, nc - lo)
+        wp = _op(MUL, wtab[:m], _bc(fr_arr([pow(dom.gen, lo, P.R_MOD)])[0], m))
+        lw = _op(MUL, wp, batch_inv(_op(SUB, _bc(exps["tau"], m), wp)))          # w^i / (tau - w^i)
+        ac, bc_ = a[lo:lo + m], b[lo:lo + m]
+        at += _int(fr_dot(ac, lw)); bt += _int(fr_dot(bc_, lw)); ct += _int(fr_dot(_op(MUL, ac, bc_), lw))
     tau, alpha, beta, delta = (_int(exps[k]) for k in ("tau", "alpha", "beta", "delta"))
     R = P.R_MOD
     lam = (pow(tau, N, R) - 1) * dom.card_inv % R                            # L_i(tau) = lam * w^i / (tau - w^i)
@@ -269,7 +301,7 @@ def check_proof(proof, want):
 def _key_scalars(exps):
     ia, ib = exps["infinity_a"] == 0, exps["infinity_b"] == 0
     N = 1 << exps["log_n"]
-    z = z_exps(exps)[bitrev_index(exps["log_n"])]
+    z = z_exps_bitrev(exps)
     return {"g1_a": exps["A"][ia], "g1_b": exps["B"][ib], "g1_k": exps["K"][k_rows(exps)], "g1_z": z, "g2_b": exps["B"][ib]}, N
 
 

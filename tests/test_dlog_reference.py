@@ -117,3 +117,17 @@ def test_oracle_prove_equals_the_exponent_reference(log_n, masks):
     assert not pk["g1_k"][np.searchsorted(D.k_rows(e), e["plants"]["unused"])].any(), "unused wires are (0, 0) in pk.G1.K"
     proof = cref.prove(pk, W, a, b, c, r, s)
     D.check_proof(proof, D.expected_proof_exps(e, W, a, b, r, s))
+
+
+def test_chunked_reference_equals_whole_vectors():
+    """the chunked forms (what the 2^27 proof uses) equal the whole-vector ones: Z in stored order, and the proof's exponents with
+    chunks that do not divide the wire or constraint counts"""
+    e = D.make_exps(10, 1000, 17, 32, (900, 500), True, 77)
+    for cb in (3, 7, 10, 22):
+        assert np.array_equal(D.z_exps_bitrev(e, chunk_bits=cb), D.z_exps(e)[D.bitrev_index(10)])
+    W = D.witness(e, 1, 78)
+    a, b, _ = D.constraint_values(900, 1, 79)
+    r, s = cref.gen_scalars(2, 80, 0)
+    want = D.expected_proof_exps(e, W, a, b, r, s, chunk=1 << 20)
+    assert D.expected_proof_exps(e, W, a, b, r, s, chunk=37) == want
+    assert D.expected_proof_exps(e, W, a, b, r, s, chunk=256) == want
