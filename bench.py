@@ -13,11 +13,15 @@ completes inside the timed region.  N > 1 GPUs: one independent pool per GPU (co
 value = proofs of all ranks / max-rank time.  `python bench.py --gpus N` launched PLAINLY starts its N rank processes itself
 (children, before any GPU call); under torch.distributed.run it uses the ranks it is given.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` for the dominant kernel (G1 level-1 bucket
-accumulate), `roofline_ntt`, `random_gather` / `valu` (the two ceilings that kernel runs against), `value_hbm_resident_inputs` (the
-GPU-side rate: the same key, inputs already in HBM, no commitment), the single-proof latencies, `sharded_msm` / `sharded_prove`
-(BASELINE configs[4] through the C-ABI's device group) and `cpu_baseline` (the oracle's C restatement on the host cores, rank 0,
-N = 1 only: the whole step of the benchmarked workload itself -- Commit, ProveKnowledge, fold, prove -- 196 bytes compared).
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up (key, witness, every pool context sized by one
+untimed proof, whose bytes every timed proof must equal), the W warm-up steps, the K timed steps, --dump-outputs, and the line: `value`,
+`ms_per_step`, the workload's config, the timed steps' phases, completion gaps and upload times.
+With --full it also runs every other leg and adds to the line: `roofline` for the dominant kernel (G1 level-1 bucket accumulate),
+`roofline_ntt`, `random_gather` / `valu` (the two ceilings that kernel runs against), `value_hbm_resident_inputs` (the GPU-side rate:
+the same key, inputs already in HBM, no commitment), the single-proof latencies, `sensitivity` (other witness mixes), the HBM ledger,
+`sharded_msm` / `sharded_prove` (BASELINE configs[4] through the C-ABI's device group) and `cpu_baseline` (the oracle's C restatement
+on the host cores, rank 0, N = 1 only: the whole step of the benchmarked workload itself -- Commit, ProveKnowledge, fold, prove -- 196
+bytes compared).  The --no-* switches below turn single legs of --full off again.
 """
 import argparse
 import json
@@ -121,11 +125,14 @@ def main():
     ap.add_argument("--bound-levels", action="store_true", help="tuning: mi_debug_set_msm_bound_levels(1): worst-case number of item levels per MSM instead of what the fullest bucket needs")
     ap.add_argument("--hold-accum", action="store_true", help="tuning: mi_debug_set_prove_schedule(1): the wire MSMs' bucket accumulations wait for computeH (measured: no gain)")
     ap.add_argument("--msm-chunk", type=int, default=0, help="tuning: mi_debug_set_msm_chunk on every context")
-    ap.add_argument("--sharded-msm-log-n", type=int, default=26, help="configs[4]: size of the point-sharded G1 MSM run after the proofs (0 = skip)")
-    ap.add_argument("--sharded-prove-log-n", type=int, default=26, help="configs[4]: FFT domain of the ONE proof point-sharded over the ranks, run after the proofs (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every leg the headline does not need: latencies, the HBM-resident region, sensitivity, solo "
+                         "kernels and probes, live counter passes, the sharded legs, the CPU baseline (a plain run: set-up, warm-up, timed steps, line)")
+    ap.add_argument("--sharded-msm-log-n", type=int, default=None, help="configs[4], --full: size of the point-sharded G1 MSM run after the proofs (default 26; 0 = skip)")
+    ap.add_argument("--sharded-prove-log-n", type=int, default=None, help="configs[4], --full: FFT domain of the ONE proof point-sharded over the ranks, run after the proofs (default 26; 0 = skip)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="multi-rank rehearsal on a 1-GPU box: every rank uses device 0, torch.distributed runs over gloo and the device group over its "
-                         "host-staged transport (size the run to fit: e.g. --log-n 20 --sharded-msm-log-n 22 --sharded-prove-log-n 20)")
+                         "host-staged transport (size the run to fit: e.g. --log-n 20, and with --full --sharded-msm-log-n 22 --sharded-prove-log-n 20)")
     ap.add_argument("--launch-check", action="store_true", help="only start the ranks, join them (gloo, no GPU) and print a one-line JSON summary: what the CPU test of the self-launch asserts")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="after the timed steps, write what the last timed step returned to its caller (the proof's points, the commitment and the "
@@ -134,6 +141,13 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    for name in ("sharded_msm_log_n", "sharded_prove_log_n"):
+        if getattr(args, name) is None:
+            setattr(args, name, 26 if args.full else 0)
+        elif getattr(args, name) and not args.full:
+            ap.error(f"--{name.replace('_', '-')} runs a leg of --full: add --full")
+    if not args.full:   # a plain run: set-up, warm-up, the K timed steps, --dump-outputs, the line -- every leg after them is --full's
+        args.no_cpu_baseline = args.no_sensitivity = args.no_solo_legs = args.no_live_pmc = args.no_hbm_resident = True
     if args.sharded_helper:
         return sharded_helper_main()
     if not args.launch_check:
@@ -291,7 +305,7 @@ def main():
     body_bytes = None
     for i in range(pool.in_flight):
         ci = pool.ctx(i)
-        for k in range(3 if i == 0 else 1):
+        for k in range(3 if i == 0 and args.full else 1):   # (--full: the single-proof latency is the third one on context 0)
             t1 = time.perf_counter()
             pr, _ = ci.prove(pkh, W.ptr, a.ptr, b.ptr, c.ptr, rs[0], rs[1], device=True, n_wires=nb_wires, n_constraints=n_constraints)
             if i == 0:
@@ -309,21 +323,22 @@ def main():
     # single-proof latency on the caller's path (host inputs, nothing else on the GPU): Commit + submit -> wait, c formed on the device /
     # c uploaded as well
     lat_host = lat_host_with_c = lat_commit = None
-    for k in range(3):
-        t1 = time.perf_counter()
-        bts, _, _ = one_step()
-        lat_host = (time.perf_counter() - t1) * 1e3
-        if bts != serial_bytes:
-            raise SystemExit("bench.py: the pool's host-input proof differs from the one-context reference proof of the same inputs")
-    if n_committed:
-        t1 = time.perf_counter(); pool.commit(ped, values); lat_commit = (time.perf_counter() - t1) * 1e3
-    ch = c.download((n_constraints, 4))
-    for k in range(2):
-        t1 = time.perf_counter()
-        bts, _, _ = one_step(with_c=True)
-        lat_host_with_c = (time.perf_counter() - t1) * 1e3
-        if bts != serial_bytes:
-            raise SystemExit("bench.py: the host-input proof with c uploaded differs from the reference proof")
+    if args.full:
+        for k in range(3):
+            t1 = time.perf_counter()
+            bts, _, _ = one_step()
+            lat_host = (time.perf_counter() - t1) * 1e3
+            if bts != serial_bytes:
+                raise SystemExit("bench.py: the pool's host-input proof differs from the one-context reference proof of the same inputs")
+        if n_committed:
+            t1 = time.perf_counter(); pool.commit(ped, values); lat_commit = (time.perf_counter() - t1) * 1e3
+        ch = c.download((n_constraints, 4))
+        for k in range(2):
+            t1 = time.perf_counter()
+            bts, _, _ = one_step(with_c=True)
+            lat_host_with_c = (time.perf_counter() - t1) * 1e3
+            if bts != serial_bytes:
+                raise SystemExit("bench.py: the host-input proof with c uploaded differs from the reference proof")
     if not want_cpu:
         ch = None
     from concurrent.futures import ThreadPoolExecutor
@@ -452,9 +467,9 @@ def main():
     # HBM ledger of the PROVE path, taken right after the timed regions: key + tables, every context's workspaces, the pool's input sets,
     # bench.py's own inputs -- before the solo-MSM / solo-computeH / probe legs below grow the (grow-only) workspaces of context 0 for
     # their own shapes (a generic 2^26-pair MSM alone adds ~22 GB at N = 2^26)
-    hbm_in_use_gb = (lambda fr_to: (fr_to[1] - fr_to[0]) / 1e9)(torch.cuda.mem_get_info())
+    hbm_in_use_gb = (lambda fr_to: (fr_to[1] - fr_to[0]) / 1e9)(torch.cuda.mem_get_info()) if args.full else None
     hbm_ledger = None
-    if rank == 0:
+    if rank == 0 and args.full:
         hbm_ledger = ctx.mem_ledger(pkh)   # the key + context 0; the other contexts of the pool add their own workspaces
         for i in range(1, pool.in_flight):
             for k, v in pool.ctx(i).mem_ledger().items():
@@ -511,7 +526,7 @@ def main():
             zsolo = {"error": str(e)}
     # computeH alone on the GPU (6 transforms of size N, the pointwise steps fused into the last one's edges): the NTT's own roofline line
     ntt_solo = None
-    if rank == 0:
+    if rank == 0 and args.full:
         hbuf = ctx.alloc(32 * N)
         ctx.compute_h_dev(log_n, a.ptr, b.ptr, c.ptr, n_constraints, hbuf.ptr)
         ms_h = min((ctx.compute_h_dev(log_n, a.ptr, b.ptr, c.ptr, n_constraints, hbuf.ptr), ctx.stats()["compute_h_ms"])[1] for _ in range(3))
@@ -519,7 +534,7 @@ def main():
         hbuf.free()
         ntt_solo = {"compute_h_ms": ms_h, "transforms": 6, "pass_launches": launches, "ms_per_transform": ms_h / 6.0}
     # VALU context for the roofline line: the chip's measured 256-bit Montgomery product rate (dependent chains, all CUs)
-    modmul_ms = min(ctx.bench_modmul(1, 256 * 4096, 256) for _ in range(3)) if rank == 0 else 0.0
+    modmul_ms = min(ctx.bench_modmul(1, 256 * 4096, 256) for _ in range(3)) if rank == 0 and args.full else 0.0
     # ... and the TRUE cycles of a v_mad_u64_u32 (the instruction 71 % of the dominant kernel's cycles go to): eight waves per SIMD of
     # independent multiply-accumulate chains for ~0.7 s under the clock sampler.  profiles/r02_probe_instr_rate.txt priced it at 5.28 cycles
     # ASSUMING 2.4 GHz; the chip clocks lower under such a load, so every cycle figure derived from that table is scaled by this ratio
@@ -544,7 +559,7 @@ def main():
     # ... and the memory system's ceiling for what that kernel asks of it: dependent random 64-byte gathers from a table far larger
     # than the 256 MB Infinity Cache (8.6 GB of scratch: the Z MSM's window tables are 7 GB at N = 2^23, A+K's 15 GB)
     gather_ms = 0.0
-    if rank == 0:
+    if rank == 0 and args.full:
         gtab = ctx.alloc(64 << 27)
         gather_ms = min(ctx.bench_gather(gtab.ptr, 1 << 27, 256 * 4 * 64 * 4, 128) for _ in range(3))
         gtab.free()
@@ -576,8 +591,36 @@ def main():
     sharded, sharded_prove = {"done": False}, {"done": False}
     if helper is not None:
         sharded, sharded_prove = run_sharded_legs(helper, B, torch, dist, rank, local_rank, world, args)
-    if rank == 0:
+    line = None
+    if rank == 0:   # the headline and what its timed steps showed
         proofs = args.steps * world
+        line = {
+            "metric": "Groth16 proofs/sec for WHIR-verifier circuit (2^20 poly); G1 MSM pts/sec",
+            "value": proofs / dt, "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u32x8 Montgomery (BN254 Fr/Fp, exact modular integers)", "data": "synthetic",
+            "config": {"workload": f"full Groth16 prove of the WHIR-verifier-shaped synthetic key/witness, FFT domain N=2^{log_n} "
+                                   f"(BASELINE {'configs[1]' if log_n == 23 else 'configs[2]' if log_n == 26 else 'non-baseline size'}; configs[3] = one such proof stream per GPU when n_gpus>1), "
+                                   f"with its ONE BSB22 commitment over {n_committed} private wires (Commit inside the step, ProveKnowledge beside the proof's MSMs, fold; {196 if n_committed else 164}-byte proof), "
+                                   "W, a, b handed over as HOST pointers (the cgo path; c = a o b formed on the device)",
+                       "nb_wires": nb_wires, "nb_public": nb_public, "n_constraints": n_constraints, "n_committed": n_committed, "scalar_dist": args.dist,
+                       "g1_msm_sizes": [na, nb, nk, N - 1], "g2_msm_size": nb, "pedersen_msm_sizes": [n_committed, n_committed], "proofs_in_flight_per_gpu": in_flight,
+                       "caller_threads": callers, "inputs": "host memory (PCIe inside the step)"},
+            "proof_bytes": len(serial_bytes), "rank0_numa_binding": numa,
+            # observed, not derived from the arguments: the ranks' PCI bus ids and how many are distinct (a run with fewer distinct devices than
+            # ranks is refused unless it is the declared one-GPU rehearsal); the device group's own view is in sharded_prove.observed
+            "devices_observed": dict(devices_observed, rehearsal_on_one_gpu=bool(args.rehearse_on_one_gpu)),
+            # the upload stage's wall time per job (W, a, b = 0.8 GB at N = 2^23 from pageable host memory): when its median nears
+            # ms_per_step the rate is bound by the PCIe / host-memory side of the box, not by the GPU
+            "host_inputs_upload_ms": {"median": h2d[len(h2d) // 2], "max": h2d[-1]},
+            "multi_gpu_note": "no scaling curve exists until an 8-GPU node runs this command with --gpus 2/4/8; nothing here extrapolates one",
+            "proofs_validated": f"{len(done)} timed proofs ({len(serial_bytes)} bytes each) + {0 if dev_rate is None else args.steps} HBM-resident-input proofs byte-equal to the untimed reference proofs",
+            "pk_load_s": t_load,
+            "phase_ms": {k: last[k] for k in ("compute_h_ms", "msm_a_ms", "msm_b1_ms", "msm_b2_ms", "msm_k_ms", "msm_z_ms", "assemble_ms", "total_ms")},
+            "step_completion_gaps": step_gaps,
+            "full": args.full,
+        }
+    if rank == 0 and args.full:   # what the legs after the timed steps measured
         # dominant kernel: G1 level-1 bucket accumulate; algorithmic bytes = 96 B per (point, scalar) pair
         per_launch_ms = accum_ms / max(accum_launches, 1)
         per_launch_bytes = 96.0 * accum_pairs / max(accum_launches, 1)
@@ -724,22 +767,7 @@ def main():
                              "note": "an instruction-count figure: multiply-accumulate-heavy kernels (level 1: 4.43 cycles per instruction by the ISA census) weigh more than the 3.84-cycle average"}
         except Exception:
             valu_util = None
-        line = {
-            "metric": "Groth16 proofs/sec for WHIR-verifier circuit (2^20 poly); G1 MSM pts/sec",
-            "value": proofs / dt, "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u32x8 Montgomery (BN254 Fr/Fp, exact modular integers)", "data": "synthetic",
-            "config": {"workload": f"full Groth16 prove of the WHIR-verifier-shaped synthetic key/witness, FFT domain N=2^{log_n} "
-                                   f"(BASELINE {'configs[1]' if log_n == 23 else 'configs[2]' if log_n == 26 else 'non-baseline size'}; configs[3] = one such proof stream per GPU when n_gpus>1), "
-                                   f"with its ONE BSB22 commitment over {n_committed} private wires (Commit inside the step, ProveKnowledge beside the proof's MSMs, fold; {196 if n_committed else 164}-byte proof), "
-                                   "W, a, b handed over as HOST pointers (the cgo path; c = a o b formed on the device)",
-                       "nb_wires": nb_wires, "nb_public": nb_public, "n_constraints": n_constraints, "n_committed": n_committed, "scalar_dist": args.dist,
-                       "g1_msm_sizes": [na, nb, nk, N - 1], "g2_msm_size": nb, "pedersen_msm_sizes": [n_committed, n_committed], "proofs_in_flight_per_gpu": in_flight,
-                       "caller_threads": callers, "inputs": "host memory (PCIe inside the step)"},
-            "proof_bytes": len(serial_bytes), "rank0_numa_binding": numa,
-            # observed, not derived from the arguments: the ranks' PCI bus ids and how many are distinct (a run with fewer distinct devices than
-            # ranks is refused unless it is the declared one-GPU rehearsal); the device group's own view is in sharded_prove.observed
-            "devices_observed": dict(devices_observed, rehearsal_on_one_gpu=bool(args.rehearse_on_one_gpu)),
+        line.update({
             # the GPU-side rate: the same key and witness with W, a, b, c already in HBM and no commitment (164-byte body) -- what rounds 1-3
             # reported as `value`; no caller of the reference can reach it (gnark's solver is CPU code)
             "value_hbm_resident_inputs": dev_rate, "ms_per_step_hbm_resident_inputs": dev_ms,
@@ -748,22 +776,14 @@ def main():
             # (inputs in HBM, plain mi_groth16_prove_dev, no commitment)
             "single_proof_latency_host_inputs_ms": lat_host, "single_proof_latency_host_inputs_with_c_uploaded_ms": lat_host_with_c,
             "single_proof_latency_ms": serial_ms, "pedersen_commit_latency_ms": lat_commit,
-            # the upload stage's wall time per job (W, a, b = 0.8 GB at N = 2^23 from pageable host memory): when its median nears
-            # ms_per_step the rate is bound by the PCIe / host-memory side of the box, not by the GPU
-            "host_inputs_upload_ms": {"median": h2d[len(h2d) // 2], "max": h2d[-1]},
             # BASELINE configs[4] (one MSM point-sharded over the ranks, strong scaling); n_gpus = 1: the same code path with one rank
             "sharded_msm": sharded,
             # BASELINE configs[4] as north_star states it: ONE proof point-sharded over the ranks (strong scaling)
             "sharded_prove": sharded_prove,
-            "multi_gpu_note": "no scaling curve exists until an 8-GPU node runs this command with --gpus 2/4/8; nothing here extrapolates one",
-            "proofs_validated": f"{len(done)} timed proofs ({len(serial_bytes)} bytes each) + {0 if dev_rate is None else args.steps} HBM-resident-input proofs byte-equal to the untimed reference proofs",
-            "pk_load_s": t_load,
             "hbm_in_use_gb": hbm_in_use_gb, "hbm_ledger_gb": hbm_ledger,
             # second half of BASELINE's metric: one G1 MSM of 2^23 uniform pairs alone on the GPU (standard MSM benchmark shape);
             # inside a proof the five MSMs overlap on five streams, so per-MSM spans there are not rates
             "g1_msm_pts_per_s": solo["msm_pts_per_s"], "g1_pairs_per_proof": g1_pairs_per_proof,
-            "phase_ms": {k: last[k] for k in ("compute_h_ms", "msm_a_ms", "msm_b1_ms", "msm_b2_ms", "msm_k_ms", "msm_z_ms", "assemble_ms", "total_ms")},
-            "step_completion_gaps": step_gaps,
             "clocks_under_load": clocks,
             "roofline": roofline,
             # second kernel: k_ntt_pass.  Algorithmic bytes 64 * N per size-N transform whatever the number of passes;
@@ -801,9 +821,10 @@ def main():
                      "kernel_alone_frac_of_issue_floor": None if issue_floor is None else solo["mixed_adds_per_s"] / issue_floor,
                      "z_shaped_launch_alone_frac_of_issue_floor": None if issue_floor is None or not zsolo or "mixed_adds_per_s" not in zsolo else zsolo["mixed_adds_per_s"] / issue_floor,
                      "job_utilisation": valu_util},
-        }
+        })
         if cpu_inputs is not None:
             line["cpu_baseline"] = cpu_baseline(*cpu_inputs, rs[0], rs[1], (ped_basis, ped_sigma, values, rs[2]) if n_committed else None, log_n, serial_bytes)
+    if line is not None:
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -148,6 +148,50 @@ def test_steps_below_one_are_refused():
     assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
 
 
+# what only a --full run measures and puts in the line
+FULL_ONLY_KEYS = ("value_hbm_resident_inputs", "single_proof_latency_ms", "single_proof_latency_host_inputs_ms", "sharded_msm", "sharded_prove",
+                  "hbm_ledger_gb", "g1_msm_solo", "g1_msm_z_shaped_solo", "roofline", "roofline_ntt", "random_gather", "valu", "sensitivity", "cpu_baseline")
+
+
+def test_sharded_legs_are_refused_in_a_plain_run():
+    """the sharded legs belong to --full: a plain run that asks for one is refused before anything starts, a --full run takes it"""
+    bench = os.path.join(ROOT, "bench.py")
+    for opt in ("--sharded-msm-log-n", "--sharded-prove-log-n"):
+        r = subprocess.run([sys.executable, bench, opt, "22", "--launch-check"], capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and f"{opt} runs a leg of --full" in r.stderr
+    env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29518")
+    for extra in (["--full", "--sharded-msm-log-n", "22"], ["--sharded-msm-log-n", "0", "--sharded-prove-log-n", "0"]):
+        r = subprocess.run([sys.executable, bench, "--gpus", "1", "--launch-check"] + extra, capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_plain_run_skips_and_full_run_runs_every_leg_on_a_small_key(rank_launcher):
+    """bench.py on a small key.  A plain run reports the timed steps and nothing of --full.  With --full every leg after the timed steps
+    runs and reports -- the HBM-resident region, the latencies, the sensitivity legs, the solo kernels, the counter passes, the sharded
+    legs (helper process) and the CPU baseline, whose 196 proof bytes must equal the GPU's.  (Both started by the rank launcher: a
+    process that never touched the GPU.)"""
+    argv = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--log-n", "14", "--steps", "2", "--warmup", "1"]
+    lines = []
+    for extra in ([], ["--full", "--sharded-msm-log-n", "16", "--sharded-prove-log-n", "16"]):
+        (r,) = rank_launcher.run(argv + extra, 1, timeout=900)
+        assert r["rc"] == 0, r["stderr"]
+        lines.append(json.loads([ln for ln in r["stdout"].splitlines() if ln.startswith("{")][-1]))
+    plain, line = lines
+    assert plain["full"] is False and plain["steps"] == 2 and plain["proof_bytes"] == 196 and plain["value"] > 0
+    assert not set(FULL_ONLY_KEYS) & set(plain), "a plain run ran legs of --full"
+    assert plain["proofs_validated"] == "2 timed proofs (196 bytes each) + 0 HBM-resident-input proofs byte-equal to the untimed reference proofs"
+    assert line["full"] is True and line["steps"] == 2 and line["proof_bytes"] == 196
+    missing = [k for k in FULL_ONLY_KEYS if k not in line]
+    assert not missing, missing
+    assert line["hbm_ledger_gb"] and line["g1_msm_solo"]["msm_pts_per_s"] > 0 and line["single_proof_latency_host_inputs_ms"] > 0
+    assert line["cpu_baseline"]["proof_bytes_match"] and line["cpu_baseline"]["proof_bytes_compared"] == 196
+    assert line["value_hbm_resident_inputs"] > 0 and line["proofs_validated"] == "2 timed proofs (196 bytes each) + 2 HBM-resident-input proofs byte-equal to the untimed reference proofs"
+    assert {"half_uniform", "uniform", "census"} <= set(line["sensitivity"]) and line["value_census_mix"] > 0
+    assert line["sharded_msm"].get("done") and line["sharded_prove"].get("done") and line["sharded_prove"]["equals_unsharded_prove"], (line["sharded_msm"], line["sharded_prove"])
+    assert line["roofline_ntt"]["compute_h_solo_ms"] > 0 and line["random_gather"]["ceiling_gathers_per_s"] > 0 and line["valu"]["modmul_ceiling_per_s"] > 0
+
+
 @pytest.mark.gpu
 def test_dump_outputs_are_the_timed_proof_and_repeat_from_run_to_run(tmp_path):
     """bench.py --dump-outputs on a small key: the files hold the 196-byte proof of the last timed step (re-serialised through the

@@ -53,7 +53,7 @@ if os.path.isdir(G + "r6_pmc_fetch") and os.path.isdir(G + "r6_pmc_write"):
         out[name] = {k: {"launches": len(v[0]), "kb_total": v[1], "kb_per_launch": v[1] / len(v[0])} for k, v in agg.items()}
     csrc = os.path.join(ROOT, "gnark-whir_amd", "csrc")
     out["_sources"] = {f: sha16(os.path.join(csrc, f)) for f in ("msm.hip", "msm_g1.hip", "msm_core.cuh", "msm2_core.cuh", "curve29.cuh", "field29.cuh", "ntt.hip", "ntt_tile.cuh", "ntt_wave.cuh", "field.cuh")}
-    out["_note"] = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `python3 bench.py --in-flight 1 --steps 2 --warmup 1 --no-cpu-baseline --no-hbm-resident "
+    out["_note"] = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `python3 bench.py --full --in-flight 1 --steps 2 --warmup 1 --no-cpu-baseline --no-hbm-resident "
                     "--sharded-msm-log-n 0 --sharded-prove-log-n 0 --no-sensitivity --no-solo-legs --n-committed 0` (no commitment: the per-launch averages are those of the proof's own MSMs), N=2^23, final round-5 code (_sources: sha256[:16] of the kernel sources the passes ran on; bench.py withholds "
                     "`traffic` when they differ); KB as rocprofv3 reports them, summed over the counter's dimensions; FETCH_SIZE raw (64-B gathers need no correction; 16-B-per-lane streams need x2)")
     if os.path.isdir(G + "r6_pmc_solo_fetch") and os.path.isdir(G + "r6_pmc_solo_write"):   # the solo Z-shaped launch (tools/solo_z_msm.py): the roofline line's basis
@@ -86,7 +86,7 @@ if os.path.exists(p):
             x = sens[key]
             rows.append(f"witness `{key}`".ljust(22) + f": value {x['value']:.2f} proofs/s, HBM-resident {x['value_hbm_resident_inputs']:.2f}, single proof {x['single_proof_latency_ms']:.2f} ms, "
                         f"G1 level-1 additions per proof {x['g1_level1_additions_per_proof'] / 1e6:.1f} M")
-        open("profiles/r06_scalar_mix.txt", "w").write("the `sensitivity` block of profiles/r06_bench_line_final.json (python bench.py, defaults: N = 2^23, three proofs in flight, the step = Commit + host-input prove "
+        open("profiles/r06_scalar_mix.txt", "w").write("the `sensitivity` block of profiles/r06_bench_line_final.json (python bench.py --full, defaults: N = 2^23, three proofs in flight, the step = Commit + host-input prove "
                                                         "with the PoK; same key, same box, same run; every proof compared with its leg's reference proof)\n" + "\n".join(rows) + "\n" +
                                                         "census = " + sens["census"].get("mix", "") + "\n")
         print("\n".join(rows))

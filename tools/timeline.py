@@ -1,5 +1,5 @@
 """Where the GPU's time goes while proofs overlap: reads the rocpd database of
-`rocprofv3 --kernel-trace -d DIR -o t -- python3 bench.py --no-cpu-baseline --no-hbm-resident --sharded-msm-log-n 0 --sharded-prove-log-n 0 --steps 30`
+`rocprofv3 --kernel-trace -d DIR -o t -- python3 bench.py --full --no-cpu-baseline --no-hbm-resident --sharded-msm-log-n 0 --sharded-prove-log-n 0 --steps 30`
 and sweeps the kernels' [start, end) intervals of the steady middle of the run (between the 25th and 75th percentile of the level-1 launches):
 for every instant, which CLASSES of kernel are resident -- issue-bound (level-1 accumulates, NTT passes), memory-bound (sorts, count / scatter),
 tails (upper levels, reduces, window sums, assembly) -- and prints the share of wall time per combination.
