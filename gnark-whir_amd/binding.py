@@ -37,6 +37,10 @@ EXPORTS = [
     "mi_whir_reverse", "mi_whir_prefix_decode_path", "mi_whir_limbs_to_fr", "mi_whir_interner_decode", "mi_whir_matrix_cells", "mi_whir_config_parse", "mi_whir_config_free",
 ]
 
+# include/mi355x_groth16_setup.h (groth16.Setup on the device); kept apart from EXPORTS, which lists the four older headers
+SETUP_EXPORTS = ["mi_groth16_setup", "mi_groth16_setup_exponents", "mi_groth16_setup_get_stats"]
+MAX_COMMITMENTS = 16   # MI_PK_RAW_MAX_COMMITMENTS
+
 
 class PkDesc(C.Structure):
     _fields_ = [
@@ -68,6 +72,75 @@ def pk_raw_inspect(blob: bytes):
     if load().mi_pk_raw_inspect(buf, C.c_size_t(len(blob)), C.byref(info)) != 0:
         raise MiError("mi_pk_raw_inspect: not a gnark v0.11.0 ProvingKey.WriteRawTo stream (as recalled)")
     return info
+
+
+class R1csMatrix(C.Structure):
+    _fields_ = [("row_ptr", C.c_void_p), ("col", C.c_void_p), ("coeff", C.c_void_p)]
+
+
+class R1csDesc(C.Structure):
+    _fields_ = [("n_constraints", C.c_uint64), ("nb_wires", C.c_uint64), ("nb_public", C.c_uint32),
+                ("A", R1csMatrix), ("B", R1csMatrix), ("C", R1csMatrix), ("coeffs", C.c_void_p), ("n_coeffs", C.c_uint64),
+                ("n_commitments", C.c_uint32), ("committed", C.POINTER(C.c_void_p)), ("n_committed", C.POINTER(C.c_uint64)),
+                ("commitment_wire", C.c_void_p)]
+
+
+class Trapdoor(C.Structure):
+    _fields_ = [(n, C.c_uint64 * 4) for n in ("tau", "alpha", "beta", "gamma", "delta")] + [("sigma", (C.c_uint64 * 4) * MAX_COMMITMENTS)]
+
+
+class VkOut(C.Structure):
+    _fields_ = [("alpha1", C.c_uint64 * 8), ("beta2", C.c_uint64 * 16), ("gamma2", C.c_uint64 * 16), ("delta2", C.c_uint64 * 16),
+                ("k", C.c_void_p), ("k_cap", C.c_uint64), ("n_k", C.c_uint64)]
+
+
+class SetupExponents(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("a", "b", "c", "k", "k_gamma", "z", "infinity_a", "infinity_b")]
+
+
+class SetupStats(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("upload_ms", "lagrange_ms", "sparse_ms", "elementwise_ms", "points_ms", "handover_ms", "total_ms",
+                                         "sparse_sort_ms", "sparse_sum_ms")] + [(n, C.c_uint64) for n in ("entries", "long_columns", "chunks")]
+
+
+def _r1cs_desc(r1cs: dict):
+    """r1cs: n_constraints, nb_wires, nb_public, A / B / C = (row_ptr uint64, col uint32, coeff uint32), coeffs (n, 4) uint64 Montgomery,
+    commitments = [(committed private wires uint32, commitment wire)] -> (R1csDesc, the arrays it points into)"""
+    d = R1csDesc(); keep = []
+    d.n_constraints, d.nb_wires, d.nb_public = int(r1cs["n_constraints"]), int(r1cs["nb_wires"]), int(r1cs["nb_public"])
+    for name in "ABC":
+        rp, col, cf = r1cs[name]
+        rp = None if rp is None else np.ascontiguousarray(rp, dtype=np.uint64)
+        col = None if col is None else np.ascontiguousarray(col, dtype=np.uint32)
+        cf = None if cf is None else np.ascontiguousarray(cf, dtype=np.uint32)
+        keep += [rp, col, cf]
+        m = getattr(d, name)
+        m.row_ptr, m.col, m.coeff = (None if x is None else x.ctypes.data for x in (rp, col, cf))
+    co = r1cs["coeffs"]
+    if co is not None:
+        co = _u64(co); keep.append(co)
+        d.coeffs = co.ctypes.data
+    d.n_coeffs = int(r1cs.get("n_coeffs", 0 if co is None else co.shape[0]))
+    com = r1cs.get("commitments") or []
+    d.n_commitments = int(r1cs.get("n_commitments", len(com)))
+    if com:
+        wires = [np.ascontiguousarray(w, dtype=np.uint32) for w, _ in com]
+        ptrs = (C.c_void_p * len(com))(*[w.ctypes.data for w in wires])
+        cnts = (C.c_uint64 * len(com))(*[w.shape[0] for w in wires])
+        cw = np.array([int(c) for _, c in com], dtype=np.uint32)
+        keep += [wires, ptrs, cnts, cw]
+        d.committed, d.n_committed, d.commitment_wire = C.cast(ptrs, C.POINTER(C.c_void_p)), C.cast(cnts, C.POINTER(C.c_uint64)), cw.ctypes.data
+    return d, keep
+
+
+def _trapdoor(td: dict):
+    """td: tau, alpha, beta, gamma, delta as (4,) uint64 Montgomery rows, sigma = list of such rows"""
+    t = Trapdoor()
+    for n in ("tau", "alpha", "beta", "gamma", "delta"):
+        setattr(t, n, (C.c_uint64 * 4)(*[int(v) for v in _u64(td[n]).reshape(4)]))
+    for k, sg in enumerate(td.get("sigma", [])):
+        t.sigma[k] = (C.c_uint64 * 4)(*[int(v) for v in _u64(sg).reshape(4)])
+    return t
 
 
 class Bsb22Input(C.Structure):
@@ -384,6 +457,34 @@ class Context:
         f = self.lib.mi_pedersen_prove_knowledge if knowledge else self.lib.mi_pedersen_commit
         self._ck(f(self.h, pk, _p(values), C.c_size_t(values.shape[0]), _p(out)))
         return out
+
+    # ---- groth16.Setup on the device (include/mi355x_groth16_setup.h)
+    def setup_exponents(self, r1cs: dict, td: dict, want=("a", "b", "c", "k", "k_gamma", "z", "infinity_a", "infinity_b")):
+        """mi_groth16_setup_exponents: the Fr half of Setup -> dict of host arrays ((n, 4) uint64 Montgomery; the masks uint8)"""
+        d, keep = _r1cs_desc(r1cs); t = _trapdoor(td)
+        nw = d.nb_wires; N = 1 << max(int(d.n_constraints) - 1, 0).bit_length()
+        out = {n: (np.zeros(nw, np.uint8) if n.startswith("inf") else np.zeros((N if n == "z" else nw, 4), np.uint64)) for n in want}
+        e = SetupExponents()
+        for n, arr in out.items():
+            setattr(e, n, arr.ctypes.data)
+        self._ck(self.lib.mi_groth16_setup_exponents(self.h, C.byref(d), C.byref(t), C.byref(e)))
+        return out
+
+    def setup(self, r1cs: dict, td: dict):
+        """mi_groth16_setup -> (key handle, [Pedersen key handles], vk dict: alpha1, beta2, gamma2, delta2, k (n, 8))"""
+        d, keep = _r1cs_desc(r1cs); t = _trapdoor(td)
+        cap = int(d.nb_public) + int(d.n_commitments)
+        vk_k = np.zeros((max(cap, 1), 8), np.uint64)
+        vk = VkOut(); vk.k = vk_k.ctypes.data; vk.k_cap = cap
+        h = C.c_void_p(); ped = (C.c_void_p * MAX_COMMITMENTS)()
+        self._ck(self.lib.mi_groth16_setup(self.h, C.byref(d), C.byref(t), C.byref(h), ped, C.byref(vk)))
+        vkd = {n: np.array(getattr(vk, n), dtype=np.uint64) for n in ("alpha1", "beta2", "gamma2", "delta2")}
+        vkd["k"] = vk_k[:int(vk.n_k)].copy()
+        return h, [C.c_void_p(ped[i]) for i in range(int(d.n_commitments))], vkd
+
+    def setup_stats(self):
+        st = SetupStats(); self._ck(self.lib.mi_groth16_setup_get_stats(self.h, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in SetupStats._fields_}
 
     def trim(self):
         """mi_ctx_trim: every grow-only workspace of this (idle) context goes back to the device"""

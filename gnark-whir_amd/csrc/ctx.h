@@ -11,6 +11,7 @@
 #include "../../include/mi355x_groth16_group.h"
 #include "../../include/mi355x_whir_ingest.h"
 #include "../../include/mi355x_groth16_debug.h"
+#include "../../include/mi355x_groth16_setup.h"
 
 struct DevBuf {             // growable device scratch owned by the ctx (no hipMalloc in the hot path
     void *p = nullptr;      // after warm-up: buffers only ever grow)
@@ -51,6 +52,7 @@ struct mi_ctx {
     std::string err;
     std::mutex err_m;          // a prove enqueues its MSM groups from helper threads (prove.hip): failures there report through mi_set_err
     mi_stats stats{};
+    mi_setup_stats setup_stats{};   // last mi_groth16_setup[_exponents] call (setup.hip)
     hipEvent_t ev[24]{};
     // scratch
     alignas(16) unsigned char ntt_state[384];  // NttState (ntt.hip): root tables + plan knobs

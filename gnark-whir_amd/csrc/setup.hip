@@ -1,0 +1,798 @@
+// groth16.Setup on the device (include/mi355x_groth16_setup.h): compiled R1CS + trapdoor -> device-resident proving key.
+// Replaces the gnark call at mt.go:448 of the reference that the reference pays on every run.
+//
+//   1  L_i(tau) = lam w^i / (tau - w^i), lam = (tau^N - 1) / N, i < n_constraints          k_lagrange: strided runs of 64 rows per
+//      thread, Montgomery's trick along the run, one Fermat inversion per run
+//   2  the transposed sparse product M_j = sum_i M[i][j] L_i for M = A, B, C.  The matrices arrive by row, the sums are by column,
+//      and there is no 256-bit atomic add.  Per matrix:
+//        count    32-bit histogram of the column indices; every entry keeps the rank the atomic gave it inside its column
+//        scan     exclusive prefix sum -> first slot of every column
+//        scatter  (row, coeff) of every entry to slot + rank (a counting sort by column; the order inside a column is whatever the
+//                 atomics gave: field addition is exact and commutative, so every order gives the same bits)
+//        sum      columns of <= SHORT entries: one thread each, 64 columns packed in a wave.  Longer ones are cut into pieces of CHUNK
+//                 entries; a wave sums one piece (lanes stride over it, the lanes' sums meet in a butterfly) into a partial, and a
+//                 second pass adds a column's partials the same way.  Column lengths are heavily skewed -- the constant wire sits in a
+//                 large share of all rows, most wires in one to three -- and a thread per column would leave one lane on millions of
+//                 entries.
+//      The count adds up a wave's entries of one column first (wave_claim): a hot column costs one atomic per wave instead of 64 on
+//      one address.
+//   3  element-wise: t_j = beta A_j + alpha B_j + C_j, t_j / delta, t_j / gamma, the zero tests; prefix sums compact the A_j / B_j / K_j
+//      that own a key point into dense arrays; the Z exponents directly in the stored bit-reversed order
+//   4  points: mi_batch_scalar_mul_g1/g2_dev (csrc/fixed_base.hip), then the arrays go to the key through the adopt path of
+//      mi_pk_load_range / mi_pedersen_pk_adopt.  Every exponent array is freed as soon as its points exist.
+// Only the R1CS goes up; the infinity masks, the counts and the verifying key come down.
+#include "prove_internal.h"
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+namespace {
+
+constexpr u32 SHORT = 16;      // a column of at most this many entries is summed by one thread
+constexpr u32 CHUNK = 512;     // entries of a longer column that one wave sums
+constexpr u32 LAG_RUN = 64;    // rows per thread of k_lagrange: one inversion per run
+constexpr u32 SCAN_ITEMS = 8, SCAN_BLOCK = 256, SCAN_TILE = SCAN_ITEMS * SCAN_BLOCK;
+
+MI_D Fr ld_fr(const Fr *p) {
+    const uint4 *q = reinterpret_cast<const uint4 *>(p);
+    const uint4 a = q[0], b = q[1];
+    Fr r;
+    r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w; r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
+    return r;
+}
+MI_D void st_fr(Fr *p, const Fr &v) {
+    uint4 *q = reinterpret_cast<uint4 *>(p);
+    q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
+    q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+}
+MI_D Fr fr_pow_u64(Fr b, u64 e) {
+    Fr acc = Fr::one();
+    while (e) {
+        if (e & 1) acc = acc * b;
+        b = fe_sqr(b);
+        e >>= 1;
+    }
+    return acc;
+}
+// the sum of v over the 64 lanes of a wave, in every lane (all lanes active)
+MI_D Fr wave_sum(Fr v) {
+#pragma unroll 1
+    for (int o = 32; o >= 1; o >>= 1) {
+        Fr t;
+#pragma unroll
+        for (int i = 0; i < 8; i++) t.l[i] = (u32)__shfl_xor((int)v.l[i], o);
+        v = v + t;
+    }
+    return v;
+}
+// cnt[key] += 1 for every active lane; returns the value this lane's increment saw.  Lanes of one wave that share a key are served by
+// ONE atomic: each round takes the first active lane's key, its lanes count themselves with a ballot, the lowest adds the count.
+MI_D u32 wave_claim(u32 *cnt, u32 key) {
+    const u32 lane = __lane_id();
+    u32 res = 0;
+    for (;;) {
+        const u32 k0 = (u32)__builtin_amdgcn_readfirstlane((int)key);
+        if (key == k0) {
+            const u64 m = __ballot(1);
+            const u32 rank = (u32)__popcll(m & (((u64)1 << lane) - 1));
+            u32 base = 0;
+            if (rank == 0) base = atomicAdd(&cnt[k0], (u32)__popcll(m));
+            base = (u32)__builtin_amdgcn_readfirstlane((int)base);
+            res = base + rank;
+            break;
+        }
+    }
+    return res;
+}
+
+// ---------------------------------------------------------------------------------------------------- 1: the Lagrange basis at tau
+// thread t owns the rows t, t + T, t + 2T, ... (< nc): coalesced, and the run's w^i follow from one power and repeated steps of w^T
+__global__ void __launch_bounds__(64) k_lagrange(Fr *L, u64 nc, u32 T, Fr w, Fr wT, Fr wTinv, Fr tau, Fr lam) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T || t >= nc) return;
+    Fr x = fr_pow_u64(w, t), p = Fr::one();
+    u32 cnt = 0;
+    for (u64 i = t; i < nc && cnt < LAG_RUN; i += T, cnt++) {   // L[i] <- product of the run's earlier denominators
+        st_fr(L + i, p);
+        p = p * (tau - x);
+        x = x * wT;
+    }
+    Fr inv = fe_inv(p);   // tau is not on the domain (refused on the host): no denominator is zero
+    for (u32 k = cnt; k-- > 0;) {
+        const u64 i = t + (u64)k * T;
+        x = x * wTinv;
+        const Fr dinv = inv * ld_fr(L + i);
+        inv = inv * (tau - x);
+        st_fr(L + i, (lam * x) * dinv);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- exclusive scan of u32 (in place)
+__device__ u32 block_exclusive_scan(u32 v, u32 *lds, u32 *total) {   // SCAN_BLOCK threads
+    const u32 t = threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+    for (u32 o = 1; o < SCAN_BLOCK; o <<= 1) {
+        const u32 add = t >= o ? lds[t - o] : 0;
+        __syncthreads();
+        lds[t] += add;
+        __syncthreads();
+    }
+    const u32 incl = lds[t];
+    *total = lds[SCAN_BLOCK - 1];
+    __syncthreads();
+    return incl - v;
+}
+__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_tiles(u32 *data, u64 n, u32 *tile_sums) {
+    __shared__ u32 lds[SCAN_BLOCK];
+    const u64 base = (u64)blockIdx.x * SCAN_TILE + (u64)threadIdx.x * SCAN_ITEMS;
+    u32 v[SCAN_ITEMS], s = 0;
+#pragma unroll
+    for (u32 k = 0; k < SCAN_ITEMS; k++) { v[k] = base + k < n ? data[base + k] : 0; s += v[k]; }
+    u32 total;
+    u32 run = block_exclusive_scan(s, lds, &total);
+#pragma unroll
+    for (u32 k = 0; k < SCAN_ITEMS; k++) { if (base + k < n) data[base + k] = run; run += v[k]; }
+    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
+}
+__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_sums(u32 *tile_sums, u32 n_tiles) {   // one block
+    __shared__ u32 lds[SCAN_BLOCK];
+    const u32 per = (n_tiles + SCAN_BLOCK - 1) / SCAN_BLOCK;
+    const u32 lo = min(threadIdx.x * per, n_tiles), hi = min(lo + per, n_tiles);
+    u32 s = 0;
+    for (u32 i = lo; i < hi; i++) s += tile_sums[i];
+    u32 total;
+    u32 run = block_exclusive_scan(s, lds, &total);
+    for (u32 i = lo; i < hi; i++) { const u32 v = tile_sums[i]; tile_sums[i] = run; run += v; }
+}
+__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_add(u32 *data, u64 n, const u32 *tile_sums) {
+    const u64 i = (u64)blockIdx.x * SCAN_BLOCK + threadIdx.x;
+    if (i < n) data[i] += tile_sums[i / SCAN_TILE];
+}
+
+// ---------------------------------------------------------------------------------------------------- 2: the transposed sparse product
+// rank[e] = how many entries of e's column were counted before it (any order: the atomics decide); cnt ends as the histogram
+__global__ void __launch_bounds__(256) k_col_count(const u32 *col, u32 nnz, u32 *cnt, u32 *rank) {
+    const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < nnz) rank[e] = wave_claim(cnt, col[e]);
+}
+// four consecutive entries per thread: one binary search of the row starts, then a walk
+__global__ void __launch_bounds__(256) k_col_scatter(const u32 *row_ptr, u32 n_rows, const u32 *col, const u32 *coeff, u32 nnz, const u32 *off,
+                                                     const u32 *rank, uint2 *sorted) {
+    const u64 e0 = ((u64)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (e0 >= nnz) return;
+    u32 lo = 0, hi = n_rows;   // row_ptr[lo] <= e0 < row_ptr[hi]
+    while (hi - lo > 1) {
+        const u32 mid = lo + (hi - lo) / 2;
+        if (row_ptr[mid] <= e0) lo = mid; else hi = mid;
+    }
+    u32 row = lo;
+    for (u32 k = 0; k < 4; k++) {
+        const u64 e = e0 + k;
+        if (e >= nnz) break;
+        while (row_ptr[row + 1] <= e) row++;   // empty rows in between
+        const u32 key = col[e];
+        const u32 pos = off[key] + rank[e];
+        sorted[pos] = make_uint2(row, coeff[e]);
+    }
+}
+struct LongCol { u32 col, first_piece, n_pieces, pad; };
+// ctr[0] = pieces, ctr[1] = long columns
+__global__ void __launch_bounds__(256) k_col_sum_short(Fr *out, u64 nb_wires, const u32 *off, const uint2 *sorted, const Fr *L, const Fr *coeffs,
+                                                       u32 *ctr, uint2 *pieces, LongCol *long_cols) {
+    const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nb_wires) return;
+    const u32 lo = off[j], len = off[j + 1] - lo;
+    if (len <= SHORT) {
+        Fr acc = Fr::zero();
+        for (u32 e = lo; e < lo + len; e++) {
+            const uint2 en = sorted[e];
+            acc = acc + ld_fr(coeffs + en.y) * ld_fr(L + en.x);
+        }
+        st_fr(out + j, acc);
+        return;
+    }
+    const u32 np = (len + CHUNK - 1) / CHUNK;
+    const u32 first = atomicAdd(&ctr[0], np);
+    long_cols[atomicAdd(&ctr[1], 1u)] = LongCol{(u32)j, first, np, 0};
+    for (u32 c = 0; c < np; c++) pieces[first + c] = make_uint2(lo + c * CHUNK, min(CHUNK, len - c * CHUNK));
+}
+// a wave per piece (grid-stride): partial[piece] = sum of its entries
+__global__ void __launch_bounds__(256) k_col_sum_pieces(Fr *partial, const u32 *ctr, const uint2 *pieces, const uint2 *sorted, const Fr *L, const Fr *coeffs) {
+    const u32 lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    const u32 n_pieces = ctr[0];
+    for (u32 it = wave; it < n_pieces; it += n_waves) {
+        const uint2 pc = pieces[it];
+        Fr acc = Fr::zero();
+        for (u32 k = lane; k < pc.y; k += 64) {
+            const uint2 en = sorted[pc.x + k];
+            acc = acc + ld_fr(coeffs + en.y) * ld_fr(L + en.x);
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) st_fr(partial + it, acc);
+    }
+}
+// a wave per long column (grid-stride): the sum of its partials
+__global__ void __launch_bounds__(256) k_col_sum_combine(Fr *out, const u32 *ctr, const LongCol *long_cols, const Fr *partial) {
+    const u32 lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
+    const u32 n_long = ctr[1];
+    for (u32 it = wave; it < n_long; it += n_waves) {
+        const LongCol lc = long_cols[it];
+        Fr acc = Fr::zero();
+        for (u32 k = lane; k < lc.n_pieces; k += 64) acc = acc + ld_fr(partial + lc.first_piece + k);
+        acc = wave_sum(acc);
+        if (lane == 0) st_fr(out + lc.col, acc);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- 3: element-wise
+// keep_* = 1 where the wire owns a point of pk.G1.A / pk.G1.B (+ pk.G2.B) / pk.G1.K (private; the committed and commitment wires are
+// cleared afterwards by k_clear_flags); all three are scanned into the compaction's slots
+__global__ void __launch_bounds__(256) k_elementwise(const Fr *A, const Fr *B, const Fr *C, Fr *Kd, Fr *Kg, uint8_t *inf_a, uint8_t *inf_b,
+                                                     u32 *keep_a, u32 *keep_b, u32 *keep_k, u64 nb_wires, u32 nb_public, Fr alpha, Fr beta,
+                                                     Fr delta_inv, Fr gamma_inv) {
+    const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nb_wires) return;
+    const Fr a = ld_fr(A + j), b = ld_fr(B + j), c = ld_fr(C + j);
+    const Fr t = beta * a + alpha * b + c;
+    st_fr(Kd + j, t * delta_inv);
+    st_fr(Kg + j, t * gamma_inv);
+    const bool za = a.is_zero(), zb = b.is_zero();
+    inf_a[j] = za; inf_b[j] = zb;
+    keep_a[j] = !za; keep_b[j] = !zb; keep_k[j] = j >= nb_public;
+}
+__global__ void k_clear_flags(u32 *flags, const u32 *idx, u32 n) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) flags[idx[i]] = 0;
+}
+// slot[j] = scanned flags (slot[j + 1] != slot[j] where the wire is kept)
+__global__ void __launch_bounds__(256) k_compact(Fr *dst, const Fr *src, const u32 *slot, u64 n) {
+    const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const u32 s = slot[j];
+    if (slot[j + 1] != s) st_fr(dst + s, ld_fr(src + j));
+}
+__global__ void __launch_bounds__(256) k_gather_scale(Fr *dst, const Fr *src, const u32 *idx, u64 n, Fr factor) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) st_fr(dst + i, ld_fr(src + idx[i]) * factor);
+}
+struct TauPowers { Fr p[MI_SETUP_MAX_LOG_N + 1]; };   // tau^(2^k)
+// slot s of the stored order holds tau^bitrev(s) (tau^N - 1) / delta
+__global__ void __launch_bounds__(256) k_z_exps(Fr *Z, u32 log_n, Fr zt, TauPowers tp) {
+    const u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >> log_n) return;
+    const u32 i = log_n ? __brev((u32)s) >> (32 - log_n) : 0;
+    Fr acc = zt;
+    for (u32 k = 0; k < log_n; k++)
+        if ((i >> k) & 1) acc = acc * tp.p[k];
+    st_fr(Z + s, acc);
+}
+
+// ---------------------------------------------------------------------------------------------------- host side
+Fr fr_of(const mi_fr &x) { Fr r; std::memcpy(&r, &x, 32); return r; }
+Fr host_fr_u64x4(u64 a, u64 b, u64 c, u64 d) {
+    Fr t;
+    t.l[0] = (u32)a; t.l[1] = (u32)(a >> 32); t.l[2] = (u32)b; t.l[3] = (u32)(b >> 32);
+    t.l[4] = (u32)c; t.l[5] = (u32)(c >> 32); t.l[6] = (u32)d; t.l[7] = (u32)(d >> 32);
+    return fe_to_mont(t);
+}
+Fp host_fp_u64x4(u64 a, u64 b, u64 c, u64 d) {
+    Fp t;
+    t.l[0] = (u32)a; t.l[1] = (u32)(a >> 32); t.l[2] = (u32)b; t.l[3] = (u32)(b >> 32);
+    t.l[4] = (u32)c; t.l[5] = (u32)(c >> 32); t.l[6] = (u32)d; t.l[7] = (u32)(d >> 32);
+    return fe_to_mont(t);
+}
+Fr setup_domain_generator(u32 log_n) {   // fft.NewDomain: Generator = root^(2^(28 - log_n)), as csrc/ntt.hip
+    Fr g = host_fr_u64x4(0x9bd61b6e725b19f0ull, 0x402d111e41112ed4ull, 0x00e0a7eb8ef62abcull, 0x2a3c09f0a58a7e85ull);
+    for (u32 k = log_n; k < 28; k++) g = fe_sqr(g);
+    return g;
+}
+// the generators gnark-crypto's bn254 package fixes (g1 = (1, 2); g2 as in EIP-197)
+mi_g1_affine g1_generator() {
+    G1Aff g{Fp::one(), fe_from_u32<FpParams>(2)};
+    mi_g1_affine o; std::memcpy(&o, &g, 64); return o;
+}
+mi_g2_affine g2_generator() {
+    G2Aff g;
+    g.x.a0 = host_fp_u64x4(0x46debd5cd992f6edull, 0x674322d4f75edaddull, 0x426a00665e5c4479ull, 0x1800deef121f1e76ull);
+    g.x.a1 = host_fp_u64x4(0x97e485b7aef312c2ull, 0xf1aa493335a9e712ull, 0x7260bfb731fb5d25ull, 0x198e9393920d483aull);
+    g.y.a0 = host_fp_u64x4(0x4ce6cc0166fa7daaull, 0xe3d1e7690c43d37bull, 0x4aab71808dcb408full, 0x12c85ea5db8c6debull);
+    g.y.a1 = host_fp_u64x4(0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull);
+    mi_g2_affine o; std::memcpy(&o, &g, 128); return o;
+}
+
+// what the host derives from the inputs before any device work
+struct Plan {
+    u32 log_n = 0;
+    u64 N = 0, nc = 0, nb_wires = 0;
+    u32 nb_public = 0, n_commitments = 0;
+    std::vector<u32> row_ptr[3];     // the row starts in 32 bits (nnz < 2^32)
+    u32 nnz[3] = {0, 0, 0};
+    std::vector<u32> removed;        // committed + commitment wires, ascending: the private wires without a pk.G1.K point
+    std::vector<u32> vk_wires;       // public wires, then the commitment wires ascending
+    Fr tau, alpha, beta, delta_inv, gamma_inv, lam, zt, w;
+    TauPowers tp;
+};
+
+int32_t check_matrix(mi_ctx *ctx, const char *name, const mi_r1cs_matrix &m, const mi_r1cs_desc *d, Plan &pl, int k) {
+    const std::string nm(name);
+    if (!m.row_ptr) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".row_ptr is null");
+    if (m.row_ptr[0] != 0) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".row_ptr[0] is not 0");
+    const u64 n = d->n_constraints;
+    for (u64 i = 0; i < n; i++)
+        if (m.row_ptr[i + 1] < m.row_ptr[i]) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".row_ptr decreases at row " + std::to_string(i));
+    const u64 nnz = m.row_ptr[n];
+    if (nnz >> 32) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".row_ptr[n_constraints]: 2^32 entries or more");
+    if (nnz && (!m.col || !m.coeff)) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".col / " + nm + ".coeff is null");
+    // every index, on a few threads: the device never sees an index out of range
+    const unsigned T = nnz > (1u << 20) ? 8 : 1;
+    std::vector<u64> bad_col(T, ~0ull), bad_coeff(T, ~0ull);
+    auto scan = [&](unsigned t) {
+        const u64 lo = nnz * t / T, hi = nnz * (t + 1) / T;
+        for (u64 e = lo; e < hi; e++) {
+            if (m.col[e] >= d->nb_wires && bad_col[t] == ~0ull) bad_col[t] = e;
+            if (m.coeff[e] >= d->n_coeffs && bad_coeff[t] == ~0ull) bad_coeff[t] = e;
+        }
+    };
+    if (T == 1) scan(0);
+    else {
+        std::vector<std::thread> th;
+        for (unsigned t = 0; t < T; t++) th.emplace_back(scan, t);
+        for (auto &x : th) x.join();
+    }
+    for (unsigned t = 0; t < T; t++) {
+        if (bad_col[t] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".col[" + std::to_string(bad_col[t]) + "] is not below nb_wires");
+        if (bad_coeff[t] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".coeff[" + std::to_string(bad_coeff[t]) + "] is not below n_coeffs");
+    }
+    pl.nnz[k] = (u32)nnz;
+    pl.row_ptr[k].resize(n + 1);
+    for (u64 i = 0; i <= n; i++) pl.row_ptr[k][i] = (u32)m.row_ptr[i];
+    return MI_OK;
+}
+
+int32_t make_plan(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_trapdoor *td, Plan &pl) {
+    if (!d) MI_FAIL(ctx, MI_EINVAL, "setup: r1cs is null");
+    if (!td) MI_FAIL(ctx, MI_EINVAL, "setup: trapdoor is null");
+    if (d->n_constraints > ((u64)1 << MI_SETUP_MAX_LOG_N)) MI_FAIL(ctx, MI_EINVAL, "setup: n_constraints: log_n above 27");
+    u32 log_n = 0;
+    while (((u64)1 << log_n) < d->n_constraints) log_n++;
+    pl.log_n = log_n; pl.N = (u64)1 << log_n; pl.nc = d->n_constraints;
+    if (d->nb_wires == 0 || d->nb_wires > MI_MSM_MAX_PAIRS) MI_FAIL(ctx, MI_EINVAL, "setup: nb_wires is 0 or above 2^27");
+    if (d->nb_public == 0 || d->nb_public > d->nb_wires) MI_FAIL(ctx, MI_EINVAL, "setup: nb_public is 0 or above nb_wires");
+    pl.nb_wires = d->nb_wires; pl.nb_public = d->nb_public;
+    if (!d->coeffs && d->n_coeffs) MI_FAIL(ctx, MI_EINVAL, "setup: coeffs is null");
+    if (d->n_coeffs >> 32) MI_FAIL(ctx, MI_EINVAL, "setup: n_coeffs: 2^32 entries or more");
+    MI_TRY(check_matrix(ctx, "A", d->A, d, pl, 0));
+    MI_TRY(check_matrix(ctx, "B", d->B, d, pl, 1));
+    MI_TRY(check_matrix(ctx, "C", d->C, d, pl, 2));
+    // commitments
+    if (d->n_commitments > MI_PK_RAW_MAX_COMMITMENTS) MI_FAIL(ctx, MI_EINVAL, "setup: n_commitments above MI_PK_RAW_MAX_COMMITMENTS");
+    pl.n_commitments = d->n_commitments;
+    if (d->n_commitments && (!d->committed || !d->n_committed || !d->commitment_wire)) MI_FAIL(ctx, MI_EINVAL, "setup: committed / n_committed / commitment_wire is null");
+    std::vector<u32> cw;
+    for (u32 k = 0; k < d->n_commitments; k++) {
+        if (d->n_committed[k] && !d->committed[k]) MI_FAIL(ctx, MI_EINVAL, "setup: committed[" + std::to_string(k) + "] is null");
+        for (u64 i = 0; i < d->n_committed[k]; i++) {
+            const u32 j = d->committed[k][i];
+            if (j < d->nb_public || j >= d->nb_wires) MI_FAIL(ctx, MI_EINVAL, "setup: committed[" + std::to_string(k) + "][" + std::to_string(i) + "] is not a private wire");
+            pl.removed.push_back(j);
+        }
+        const u32 j = d->commitment_wire[k];
+        if (j < d->nb_public || j >= d->nb_wires) MI_FAIL(ctx, MI_EINVAL, "setup: commitment_wire[" + std::to_string(k) + "] is not a private wire");
+        pl.removed.push_back(j);
+        cw.push_back(j);
+    }
+    std::sort(pl.removed.begin(), pl.removed.end());
+    if (std::adjacent_find(pl.removed.begin(), pl.removed.end()) != pl.removed.end())
+        MI_FAIL(ctx, MI_EINVAL, "setup: committed / commitment_wire: a wire is listed twice");
+    std::sort(cw.begin(), cw.end());
+    for (u32 j = 0; j < d->nb_public; j++) pl.vk_wires.push_back(j);
+    pl.vk_wires.insert(pl.vk_wires.end(), cw.begin(), cw.end());
+    // the trapdoor
+    const Fr delta = fr_of(td->delta), gamma = fr_of(td->gamma);
+    pl.tau = fr_of(td->tau); pl.alpha = fr_of(td->alpha); pl.beta = fr_of(td->beta);
+    if (delta.is_zero()) MI_FAIL(ctx, MI_EINVAL, "setup: trapdoor.delta is 0");
+    if (gamma.is_zero()) MI_FAIL(ctx, MI_EINVAL, "setup: trapdoor.gamma is 0");
+    for (u32 k = 0; k < d->n_commitments; k++)
+        if (fr_of(td->sigma[k]).is_zero()) MI_FAIL(ctx, MI_EINVAL, "setup: trapdoor.sigma[" + std::to_string(k) + "] is 0");
+    Fr tn = pl.tau;
+    for (u32 k = 0; k <= log_n; k++) { pl.tp.p[k] = tn; if (k < log_n) tn = fe_sqr(tn); }
+    if (tn == Fr::one()) MI_FAIL(ctx, MI_EINVAL, "setup: trapdoor.tau lies on the domain (tau^N = 1)");
+    pl.delta_inv = fe_inv(delta); pl.gamma_inv = fe_inv(gamma);
+    const Fr zn = tn - Fr::one();
+    pl.lam = zn * fe_inv(fe_from_u32<FrParams>((u32)pl.N));
+    pl.zt = zn * pl.delta_inv;
+    pl.w = setup_domain_generator(log_n);
+    return MI_OK;
+}
+
+// device allocations of one call, freed when it returns (the key takes what it adopts out of the list)
+struct Arena {
+    std::vector<void *> live;
+    ~Arena() { for (void *p : live) if (p) (void)hipFree(p); }
+    int32_t alloc(mi_ctx *ctx, void **out, size_t bytes) {
+        *out = nullptr;
+        MI_CHECK_HIP(ctx, hipMalloc(out, bytes ? bytes : 64));
+        live.push_back(*out);
+        return MI_OK;
+    }
+    template <class T> int32_t alloc(mi_ctx *ctx, T **out, size_t count) { return alloc(ctx, (void **)out, count * sizeof(T)); }
+    void release(void *p) {   // free now
+        if (!p) return;
+        for (void *&q : live) if (q == p) { q = nullptr; (void)hipFree(p); return; }
+    }
+    void disown(void *p) { for (void *&q : live) if (q == p) q = nullptr; }
+};
+
+int32_t scan_u32(mi_ctx *ctx, u32 *data, u64 n, u32 *tile_sums) {
+    const u32 tiles = (u32)((n + SCAN_TILE - 1) / SCAN_TILE);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(SCAN_BLOCK), 0, ctx->stream, data, n, tile_sums);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_BLOCK), 0, ctx->stream, tile_sums, tiles);
+    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)((n + SCAN_BLOCK - 1) / SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, ctx->stream, data, n, (const u32 *)tile_sums);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+unsigned blocks_of(u64 n, u32 per) { return (unsigned)((n + per - 1) / per); }
+
+struct Timer {   // HIP events on the context's stream, one per phase boundary
+    enum { UP0, UP1, LAG, SUM, ELEM, POINTS, DONE, COUNT };
+    hipEvent_t ev[COUNT]{};
+    bool have[COUNT]{};
+    ~Timer() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+    int32_t init(mi_ctx *ctx) { for (auto &e : ev) MI_CHECK_HIP(ctx, hipEventCreate(&e)); return MI_OK; }
+    int32_t mark(mi_ctx *ctx, int k) { MI_CHECK_HIP(ctx, hipEventRecord(ev[k], ctx->stream)); have[k] = true; return MI_OK; }
+    float span(int a, int b) { float ms = 0; if (have[a] && have[b] && hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess) { (void)hipGetLastError(); ms = 0; } return ms; }
+};
+
+// the Fr half on the device: everything both entry points share
+struct FrHalf {
+    Fr *A = nullptr, *B = nullptr, *C = nullptr, *Kd = nullptr, *Kg = nullptr;
+    uint8_t *inf_a = nullptr, *inf_b = nullptr;
+    u32 *slot_a = nullptr, *slot_b = nullptr, *slot_k = nullptr;   // nb_wires + 1 each: compaction slots, [nb_wires] = the count
+    u32 *tile_sums = nullptr;
+    float sort_ms = 0, sum_ms = 0;
+    u64 long_columns = 0, chunks = 0;
+};
+
+int32_t run_fr_half(mi_ctx *ctx, const mi_r1cs_desc *d, const Plan &pl, Arena &ar, Timer &tm, FrHalf &f) {
+    const u64 nw = pl.nb_wires;
+    hipStream_t st = ctx->stream;
+    const u32 max_nnz = std::max(pl.nnz[0], std::max(pl.nnz[1], pl.nnz[2]));
+    // ---- upload
+    MI_TRY(tm.mark(ctx, Timer::UP0));
+    Fr *coeffs = nullptr, *L = nullptr;
+    u32 *row_ptr = nullptr, *col = nullptr, *cf = nullptr;
+    MI_TRY(ar.alloc(ctx, &coeffs, (size_t)d->n_coeffs));
+    if (d->n_coeffs) MI_CHECK_HIP(ctx, hipMemcpyAsync(coeffs, d->coeffs, d->n_coeffs * 32, hipMemcpyHostToDevice, st));
+    MI_TRY(ar.alloc(ctx, &row_ptr, (size_t)pl.nc + 1));
+    MI_TRY(ar.alloc(ctx, &col, (size_t)max_nnz));
+    MI_TRY(ar.alloc(ctx, &cf, (size_t)max_nnz));
+    MI_TRY(tm.mark(ctx, Timer::UP1));
+    // ---- 1: Lagrange
+    MI_TRY(ar.alloc(ctx, &L, (size_t)pl.nc));
+    if (pl.nc) {
+        u64 T = (pl.nc + LAG_RUN - 1) / LAG_RUN;
+        T = (T + 63) / 64 * 64;
+        Fr wT = Fr::one(), b = pl.w;
+        for (u64 e = T; e; e >>= 1) { if (e & 1) wT = wT * b; b = fe_sqr(b); }
+        hipLaunchKernelGGL(k_lagrange, dim3((unsigned)(T / 64)), dim3(64), 0, st, L, pl.nc, (u32)T, pl.w, wT, fe_inv(wT), pl.tau, pl.lam);
+        MI_CHECK_HIP(ctx, hipGetLastError());
+    }
+    MI_TRY(tm.mark(ctx, Timer::LAG));
+    // ---- 2: the three transposed products, one after the other over the same scratch
+    u32 *cnt = nullptr, *off = nullptr, *ctr = nullptr, *rank = nullptr;
+    uint2 *sorted = nullptr, *pieces = nullptr;
+    LongCol *long_cols = nullptr;
+    Fr *partial = nullptr;
+    const size_t cap_long = (size_t)max_nnz / SHORT + 1;   // a long column has more than SHORT entries and at most len / SHORT pieces
+    MI_TRY(ar.alloc(ctx, &cnt, (size_t)nw + 1));
+    MI_TRY(ar.alloc(ctx, &off, (size_t)nw + 1));
+    MI_TRY(ar.alloc(ctx, &f.tile_sums, (size_t)((nw + 1 + SCAN_TILE - 1) / SCAN_TILE) + 1));
+    MI_TRY(ar.alloc(ctx, &rank, (size_t)max_nnz));
+    MI_TRY(ar.alloc(ctx, &sorted, (size_t)max_nnz));
+    MI_TRY(ar.alloc(ctx, &pieces, cap_long));
+    MI_TRY(ar.alloc(ctx, &long_cols, cap_long));
+    MI_TRY(ar.alloc(ctx, &partial, cap_long));
+    MI_TRY(ar.alloc(ctx, &ctr, (size_t)8));
+    MI_TRY(ar.alloc(ctx, &f.A, (size_t)nw));
+    MI_TRY(ar.alloc(ctx, &f.B, (size_t)nw));
+    MI_TRY(ar.alloc(ctx, &f.C, (size_t)nw));
+    MI_CHECK_HIP(ctx, hipMemsetAsync(ctr, 0, 32, st));
+    const mi_r1cs_matrix *mats[3] = {&d->A, &d->B, &d->C};
+    Fr *outs[3] = {f.A, f.B, f.C};
+    // per matrix: e[0] upload e[1] sort e[2] sum e[3]
+    struct Events { hipEvent_t e[4]{}; ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } evs;
+    for (auto &x : evs.e) MI_CHECK_HIP(ctx, hipEventCreate(&x));
+    hipEvent_t e0 = evs.e[0], e1 = evs.e[1], e2 = evs.e[2], e3 = evs.e[3];
+    const unsigned wave_grid = (unsigned)ctx->cu_count * 8;   // blocks of 4 waves for the grid-stride passes
+    for (int k = 0; k < 3; k++) {
+        const u32 nnz = pl.nnz[k];
+        MI_CHECK_HIP(ctx, hipEventRecord(e0, st));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(row_ptr, pl.row_ptr[k].data(), (pl.nc + 1) * 4, hipMemcpyHostToDevice, st));
+        if (nnz) {
+            MI_CHECK_HIP(ctx, hipMemcpyAsync(col, mats[k]->col, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+            MI_CHECK_HIP(ctx, hipMemcpyAsync(cf, mats[k]->coeff, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+        }
+        MI_CHECK_HIP(ctx, hipEventRecord(e1, st));
+        MI_CHECK_HIP(ctx, hipMemsetAsync(cnt, 0, (nw + 1) * 4, st));
+        if (nnz) hipLaunchKernelGGL(k_col_count, dim3(blocks_of(nnz, 256)), dim3(256), 0, st, (const u32 *)col, nnz, cnt, rank);
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(off, cnt, (nw + 1) * 4, hipMemcpyDeviceToDevice, st));
+        MI_TRY(scan_u32(ctx, off, nw + 1, f.tile_sums));
+        if (nnz) hipLaunchKernelGGL(k_col_scatter, dim3(blocks_of(((u64)nnz + 3) / 4, 256)), dim3(256), 0, st, (const u32 *)row_ptr, (u32)pl.nc,
+                                    (const u32 *)col, (const u32 *)cf, nnz, (const u32 *)off, (const u32 *)rank, sorted);
+        MI_CHECK_HIP(ctx, hipEventRecord(e2, st));
+        MI_CHECK_HIP(ctx, hipMemsetAsync(ctr, 0, 8, st));
+        hipLaunchKernelGGL(k_col_sum_short, dim3(blocks_of(nw, 256)), dim3(256), 0, st, outs[k], nw, (const u32 *)off, (const uint2 *)sorted,
+                           (const Fr *)L, (const Fr *)coeffs, ctr, pieces, long_cols);
+        hipLaunchKernelGGL(k_col_sum_pieces, dim3(wave_grid), dim3(256), 0, st, partial, (const u32 *)ctr, (const uint2 *)pieces, (const uint2 *)sorted,
+                           (const Fr *)L, (const Fr *)coeffs);
+        hipLaunchKernelGGL(k_col_sum_combine, dim3(wave_grid), dim3(256), 0, st, outs[k], (const u32 *)ctr, (const LongCol *)long_cols, (const Fr *)partial);
+        MI_CHECK_HIP(ctx, hipGetLastError());
+        u32 ctr_h[2] = {0, 0};
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ctr_h, ctr, 8, hipMemcpyDeviceToHost, st));
+        MI_CHECK_HIP(ctx, hipEventRecord(e3, st));
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));   // the host arrays of this matrix are not read after this point
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, e1, e2) == hipSuccess) f.sort_ms += ms;
+        if (hipEventElapsedTime(&ms, e2, e3) == hipSuccess) f.sum_ms += ms;
+        if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ctx->setup_stats.upload_ms += ms;
+        f.chunks += ctr_h[0]; f.long_columns += ctr_h[1];
+    }
+    MI_TRY(tm.mark(ctx, Timer::SUM));
+    for (void *p : {(void *)row_ptr, (void *)col, (void *)cf, (void *)cnt, (void *)off, (void *)rank, (void *)sorted, (void *)pieces, (void *)long_cols, (void *)partial, (void *)L, (void *)coeffs, (void *)ctr})
+        ar.release(p);
+    // ---- 3: element-wise and the compaction slots
+    MI_TRY(ar.alloc(ctx, &f.Kd, (size_t)nw));
+    MI_TRY(ar.alloc(ctx, &f.Kg, (size_t)nw));
+    MI_TRY(ar.alloc(ctx, &f.inf_a, (size_t)nw));
+    MI_TRY(ar.alloc(ctx, &f.inf_b, (size_t)nw));
+    MI_TRY(ar.alloc(ctx, &f.slot_a, (size_t)nw + 1));
+    MI_TRY(ar.alloc(ctx, &f.slot_b, (size_t)nw + 1));
+    MI_TRY(ar.alloc(ctx, &f.slot_k, (size_t)nw + 1));
+    for (u32 *s : {f.slot_a, f.slot_b, f.slot_k}) MI_CHECK_HIP(ctx, hipMemsetAsync(s + nw, 0, 4, st));
+    hipLaunchKernelGGL(k_elementwise, dim3(blocks_of(nw, 256)), dim3(256), 0, st, (const Fr *)f.A, (const Fr *)f.B, (const Fr *)f.C, f.Kd, f.Kg, f.inf_a, f.inf_b,
+                       f.slot_a, f.slot_b, f.slot_k, nw, pl.nb_public, pl.alpha, pl.beta, pl.delta_inv, pl.gamma_inv);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    if (!pl.removed.empty()) {
+        u32 *rem = nullptr;
+        MI_TRY(ar.alloc(ctx, &rem, pl.removed.size()));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(rem, pl.removed.data(), pl.removed.size() * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_clear_flags, dim3(blocks_of(pl.removed.size(), 256)), dim3(256), 0, st, f.slot_k, (const u32 *)rem, (u32)pl.removed.size());
+        MI_CHECK_HIP(ctx, hipGetLastError());
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+        ar.release(rem);
+    }
+    for (u32 *s : {f.slot_a, f.slot_b, f.slot_k}) MI_TRY(scan_u32(ctx, s, nw + 1, f.tile_sums));
+    MI_TRY(tm.mark(ctx, Timer::ELEM));
+    return MI_OK;
+}
+
+int32_t z_exps_dev(mi_ctx *ctx, const Plan &pl, Fr *Z) {
+    hipLaunchKernelGGL(k_z_exps, dim3(blocks_of(pl.N, 256)), dim3(256), 0, ctx->stream, Z, pl.log_n, pl.zt, pl.tp);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+
+void fill_stats(mi_ctx *ctx, const Plan &pl, Timer &tm, const FrHalf &f, double total_ms) {
+    mi_setup_stats &s = ctx->setup_stats;
+    s.upload_ms += tm.span(Timer::UP0, Timer::UP1);
+    s.lagrange_ms = tm.span(Timer::UP1, Timer::LAG);
+    s.sparse_sort_ms = f.sort_ms; s.sparse_sum_ms = f.sum_ms; s.sparse_ms = f.sort_ms + f.sum_ms;
+    s.elementwise_ms = tm.span(Timer::SUM, Timer::ELEM);
+    s.points_ms = tm.span(Timer::ELEM, Timer::POINTS);
+    s.handover_ms = tm.span(Timer::POINTS, Timer::DONE);
+    s.total_ms = (float)total_ms;
+    s.entries = (u64)pl.nnz[0] + pl.nnz[1] + pl.nnz[2];
+    s.long_columns = f.long_columns; s.chunks = f.chunks;
+}
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+}  // namespace
+
+extern "C" {
+
+int32_t mi_groth16_setup_get_stats(mi_ctx *ctx, mi_setup_stats *out) {
+    if (!ctx || !out) return MI_EINVAL;
+    *out = ctx->setup_stats;
+    return MI_OK;
+}
+
+int32_t mi_groth16_setup_exponents(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, mi_setup_exponents *out) {
+    if (!ctx) return MI_EINVAL;
+    if (!out) MI_FAIL(ctx, MI_EINVAL, "setup: out is null");
+    Plan pl;
+    MI_TRY(make_plan(ctx, r1cs, trapdoor, pl));
+    const double t0 = now_ms();
+    ctx->setup_stats = mi_setup_stats{};
+    Arena ar;
+    Timer tm;
+    FrHalf f;
+    MI_TRY(tm.init(ctx));
+    MI_TRY(run_fr_half(ctx, r1cs, pl, ar, tm, f));
+    hipStream_t st = ctx->stream;
+    const u64 nw = pl.nb_wires;
+    const std::pair<void *, const void *> fetch[] = {{out->a, f.A}, {out->b, f.B}, {out->c, f.C}, {out->k, f.Kd}, {out->k_gamma, f.Kg}};
+    for (const auto &p : fetch)
+        if (p.first) MI_CHECK_HIP(ctx, hipMemcpyAsync(p.first, p.second, nw * 32, hipMemcpyDeviceToHost, st));
+    if (out->infinity_a) MI_CHECK_HIP(ctx, hipMemcpyAsync(out->infinity_a, f.inf_a, nw, hipMemcpyDeviceToHost, st));
+    if (out->infinity_b) MI_CHECK_HIP(ctx, hipMemcpyAsync(out->infinity_b, f.inf_b, nw, hipMemcpyDeviceToHost, st));
+    if (out->z) {
+        Fr *Z = nullptr;
+        MI_TRY(ar.alloc(ctx, &Z, (size_t)pl.N));
+        MI_TRY(z_exps_dev(ctx, pl, Z));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(out->z, Z, pl.N * 32, hipMemcpyDeviceToHost, st));
+    }
+    MI_TRY(tm.mark(ctx, Timer::DONE));
+    MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+    fill_stats(ctx, pl, tm, f, now_ms() - t0);
+    return MI_OK;
+}
+
+int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, mi_pk **pk_out, mi_pedersen_pk **ped_out, mi_vk_out *vk_out) {
+    if (!ctx) return MI_EINVAL;
+    if (!pk_out) MI_FAIL(ctx, MI_EINVAL, "setup: pk_out is null");
+    *pk_out = nullptr;
+    if (!vk_out) MI_FAIL(ctx, MI_EINVAL, "setup: vk_out is null");
+    Plan pl;
+    MI_TRY(make_plan(ctx, r1cs, trapdoor, pl));
+    if (pl.n_commitments && !ped_out) MI_FAIL(ctx, MI_EINVAL, "setup: ped_out is null");
+    if (!vk_out->k || vk_out->k_cap < pl.vk_wires.size()) MI_FAIL(ctx, MI_EINVAL, "setup: vk_out.k / k_cap: room for nb_public + n_commitments points is needed");
+    for (u32 k = 0; k < pl.n_commitments; k++) ped_out[k] = nullptr;
+    const double t0 = now_ms();
+    ctx->setup_stats = mi_setup_stats{};
+    const mi_g1_affine g1 = g1_generator();
+    const mi_g2_affine g2 = g2_generator();
+    hipStream_t st = ctx->stream;
+    const u64 nw = pl.nb_wires;
+    u32 n_ped = 0;
+    auto body = [&]() -> int32_t {
+        Arena ar;
+        Timer tm;
+        FrHalf f;
+        MI_TRY(tm.init(ctx));
+        MI_TRY(run_fr_half(ctx, r1cs, pl, ar, tm, f));
+        // masks and counts to the host
+        std::vector<uint8_t> ia(nw), ib(nw);
+        u32 n_a = 0, n_b = 0, n_k = 0;
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ia.data(), f.inf_a, nw, hipMemcpyDeviceToHost, st));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ib.data(), f.inf_b, nw, hipMemcpyDeviceToHost, st));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(&n_a, f.slot_a + nw, 4, hipMemcpyDeviceToHost, st));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(&n_b, f.slot_b + nw, 4, hipMemcpyDeviceToHost, st));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(&n_k, f.slot_k + nw, 4, hipMemcpyDeviceToHost, st));
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+        ar.release(f.inf_a); ar.release(f.inf_b);
+        // dense scalar arrays; each per-wire array goes as soon as it has been read
+        Fr *sa = nullptr, *sb = nullptr, *sk = nullptr;
+        auto compact = [&](Fr **dst, Fr *src, u32 *slot, u32 n) -> int32_t {
+            MI_TRY(ar.alloc(ctx, dst, (size_t)n));
+            hipLaunchKernelGGL(k_compact, dim3(blocks_of(nw, 256)), dim3(256), 0, st, *dst, (const Fr *)src, (const u32 *)slot, nw);
+            MI_CHECK_HIP(ctx, hipGetLastError());
+            MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+            ar.release(src); ar.release(slot);
+            return MI_OK;
+        };
+        MI_TRY(compact(&sa, f.A, f.slot_a, n_a));
+        MI_TRY(compact(&sb, f.B, f.slot_b, n_b));
+        ar.release(f.C);
+        MI_TRY(compact(&sk, f.Kd, f.slot_k, n_k));
+        ar.release(f.tile_sums);
+        // a batch of points from device scalars into a fresh array
+        auto mul_g1 = [&](void **dst, const Fr *sc, size_t n) -> int32_t {
+            MI_TRY(ar.alloc(ctx, dst, n * 64));
+            return mi_batch_scalar_mul_g1_dev(ctx, &g1, (const mi_fr *)sc, n, (mi_g1_affine *)*dst);
+        };
+        auto gather = [&](Fr **dst, const u32 *wires, size_t n, const Fr &factor) -> int32_t {
+            u32 *idx = nullptr;
+            MI_TRY(ar.alloc(ctx, &idx, n));
+            MI_TRY(ar.alloc(ctx, dst, n));
+            if (n) {
+                MI_CHECK_HIP(ctx, hipMemcpyAsync(idx, wires, n * 4, hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(k_gather_scale, dim3(blocks_of(n, 256)), dim3(256), 0, st, *dst, (const Fr *)f.Kg, (const u32 *)idx, (u64)n, factor);
+                MI_CHECK_HIP(ctx, hipGetLastError());
+            }
+            MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+            ar.release(idx);
+            return MI_OK;
+        };
+        // ---- 4: points.  vk.G1.K and the Pedersen bases first: they read t / gamma, which can go afterwards
+        {
+            Fr *sv = nullptr;
+            void *pv = nullptr;
+            const size_t n = pl.vk_wires.size();
+            MI_TRY(gather(&sv, pl.vk_wires.data(), n, Fr::one()));
+            MI_TRY(mul_g1(&pv, sv, n));
+            MI_CHECK_HIP(ctx, hipMemcpyAsync(vk_out->k, pv, n * 64, hipMemcpyDeviceToHost, st));
+            MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+            vk_out->n_k = n;
+            ar.release(sv); ar.release(pv);
+        }
+        for (u32 k = 0; k < pl.n_commitments; k++) {
+            Fr *s0 = nullptr, *s1 = nullptr;
+            void *basis = nullptr, *bes = nullptr;
+            const size_t n = (size_t)r1cs->n_committed[k];
+            MI_TRY(gather(&s0, r1cs->committed[k], n, Fr::one()));
+            MI_TRY(gather(&s1, r1cs->committed[k], n, fr_of(trapdoor->sigma[k])));
+            MI_TRY(mul_g1(&basis, s0, n));
+            MI_TRY(mul_g1(&bes, s1, n));
+            MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+            ar.release(s0); ar.release(s1);
+            MI_TRY(mi_pedersen_pk_adopt(ctx, basis, bes, n, &ped_out[k]));
+            ar.disown(basis); ar.disown(bes);
+            n_ped = k + 1;
+        }
+        ar.release(f.Kg);
+        // alpha, beta, delta on G1; beta, delta, gamma on G2
+        G1Aff small1[3];
+        G2Aff small2[3];
+        {
+            const Fr sc[4] = {pl.alpha, pl.beta, fr_of(trapdoor->delta), fr_of(trapdoor->gamma)};
+            Fr *ds = nullptr;
+            void *p1 = nullptr, *p2 = nullptr;
+            MI_TRY(ar.alloc(ctx, &ds, (size_t)4));
+            MI_CHECK_HIP(ctx, hipMemcpyAsync(ds, sc, sizeof(sc), hipMemcpyHostToDevice, st));
+            MI_TRY(mul_g1(&p1, ds, 3));
+            MI_TRY(ar.alloc(ctx, &p2, (size_t)3 * 128));
+            MI_TRY(mi_batch_scalar_mul_g2_dev(ctx, &g2, (const mi_fr *)(ds + 1), 3, (mi_g2_affine *)p2));
+            MI_CHECK_HIP(ctx, hipMemcpyAsync(small1, p1, sizeof(small1), hipMemcpyDeviceToHost, st));
+            MI_CHECK_HIP(ctx, hipMemcpyAsync(small2, p2, sizeof(small2), hipMemcpyDeviceToHost, st));
+            MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+            ar.release(ds); ar.release(p1); ar.release(p2);
+        }
+        std::memcpy(&vk_out->alpha1, &small1[0], 64);
+        std::memcpy(&vk_out->beta2, &small2[0], 128); std::memcpy(&vk_out->delta2, &small2[1], 128); std::memcpy(&vk_out->gamma2, &small2[2], 128);
+        // the five arrays of the key
+        void *arrays[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        MI_TRY(mul_g1(&arrays[0], sa, n_a));
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+        ar.release(sa);
+        MI_TRY(mul_g1(&arrays[1], sb, n_b));
+        MI_TRY(ar.alloc(ctx, &arrays[4], (size_t)n_b * 128));
+        MI_TRY(mi_batch_scalar_mul_g2_dev(ctx, &g2, (const mi_fr *)sb, n_b, (mi_g2_affine *)arrays[4]));
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+        ar.release(sb);
+        MI_TRY(mul_g1(&arrays[2], sk, n_k));
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+        ar.release(sk);
+        {
+            Fr *Z = nullptr;
+            MI_TRY(ar.alloc(ctx, &Z, (size_t)pl.N));
+            MI_TRY(z_exps_dev(ctx, pl, Z));
+            MI_TRY(mul_g1(&arrays[3], Z, pl.N));
+            MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+            ar.release(Z);
+        }
+        MI_TRY(tm.mark(ctx, Timer::POINTS));
+        // ---- the key takes the arrays
+        mi_pk_desc d;
+        std::memset(&d, 0, sizeof(d));
+        d.log_n = pl.log_n; d.nb_public = pl.nb_public; d.nb_wires = nw;
+        d.g1_a = (const mi_g1_affine *)arrays[0]; d.n_g1_a = n_a;
+        d.g1_b = (const mi_g1_affine *)arrays[1]; d.n_g1_b = n_b;
+        d.g1_k = (const mi_g1_affine *)arrays[2]; d.n_g1_k = n_k;
+        d.g1_z = (const mi_g1_affine *)arrays[3]; d.n_g1_z = pl.N;
+        d.g2_b = (const mi_g2_affine *)arrays[4]; d.n_g2_b = n_b;
+        std::memcpy(&d.alpha1, &small1[0], 64); std::memcpy(&d.beta1, &small1[1], 64); std::memcpy(&d.delta1, &small1[2], 64);
+        std::memcpy(&d.beta2, &small2[0], 128); std::memcpy(&d.delta2, &small2[1], 128);
+        d.infinity_a = ia.data(); d.infinity_b = ib.data();
+        d.committed_wires = pl.removed.empty() ? nullptr : pl.removed.data(); d.n_committed = pl.removed.size();
+        bool took = false;
+        const int32_t lr = mi_pk_load_range(ctx, &d, pk_out, true, nullptr, /*adopt=*/true, &took);
+        if (took) for (void *a : arrays) ar.disown(a);   // the key's now (it has released them itself if it failed after taking them)
+        MI_TRY(lr);
+        MI_TRY(tm.mark(ctx, Timer::DONE));
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+        fill_stats(ctx, pl, tm, f, now_ms() - t0);
+        return MI_OK;
+    };
+    const int32_t rc = body();
+    if (rc != MI_OK) {
+        (void)hipStreamSynchronize(st);
+        if (*pk_out) { mi_pk_free(ctx, *pk_out); *pk_out = nullptr; }
+        for (u32 k = 0; k < n_ped; k++) { mi_pedersen_pk_free(ctx, ped_out[k]); ped_out[k] = nullptr; }
+    }
+    return rc;
+}
+
+}  // extern "C"
