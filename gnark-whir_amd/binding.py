@@ -40,6 +40,11 @@ EXPORTS = [
 # include/mi355x_groth16_setup.h (groth16.Setup on the device); kept apart from EXPORTS, which lists the four older headers
 SETUP_EXPORTS = ["mi_groth16_setup", "mi_groth16_setup_exponents", "mi_groth16_setup_get_stats"]
 MAX_COMMITMENTS = 16   # MI_PK_RAW_MAX_COMMITMENTS
+# include/mi355x_groth16_r1cs.h (the device-resident R1CS and the entry points that prove from W alone)
+R1CS_EXPORTS = ["mi_r1cs_load", "mi_r1cs_free", "mi_r1cs_bytes", "mi_r1cs_eval", "mi_r1cs_eval_dev", "mi_r1cs_check_dev", "mi_r1cs_get_stats",
+                "mi_groth16_prove_w", "mi_groth16_prove_w_dev", "mi_prover_submit_w", "mi_prover_submit_w_dev", "mi_prover_submit_w_bsb22"]
+R1CS_A, R1CS_B, R1CS_C = 1, 2, 4
+PROVE_W_EVAL_C = 1
 
 
 class PkDesc(C.Structure):
@@ -101,6 +106,10 @@ class SetupExponents(C.Structure):
 class SetupStats(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("upload_ms", "lagrange_ms", "sparse_ms", "elementwise_ms", "points_ms", "handover_ms", "total_ms",
                                          "sparse_sort_ms", "sparse_sum_ms")] + [(n, C.c_uint64) for n in ("entries", "long_columns", "chunks")]
+
+
+class R1csStats(C.Structure):
+    _fields_ = [("eval_ms", C.c_float), ("matrices", C.c_uint32)] + [(n, C.c_uint64) for n in ("entries", "long_rows", "pieces")]
 
 
 def _r1cs_desc(r1cs: dict):
@@ -486,6 +495,61 @@ class Context:
         st = SetupStats(); self._ck(self.lib.mi_groth16_setup_get_stats(self.h, C.byref(st)))
         return {n: getattr(st, n) for n, _ in SetupStats._fields_}
 
+    # ---- the device-resident R1CS (include/mi355x_groth16_r1cs.h)
+    def r1cs_load(self, r1cs: dict):
+        """mi_r1cs_load: the dict setup() takes -> handle of the resident R1CS (shared by every context of this device)"""
+        d, keep = _r1cs_desc(r1cs); h = C.c_void_p()
+        self._ck(self.lib.mi_r1cs_load(self.h, C.byref(d), C.byref(h)))
+        return h
+
+    def r1cs_free(self, rh):
+        self._ck(self.lib.mi_r1cs_free(self.h, rh))
+
+    def r1cs_bytes(self, rh):
+        v = C.c_uint64(); self._ck(self.lib.mi_r1cs_bytes(rh, C.byref(v))); return int(v.value)
+
+    def r1cs_eval(self, rh, W, n_constraints, which=R1CS_A | R1CS_B | R1CS_C, device=False):
+        """(A W, B W, C W), None for a matrix not in `which`; W: (nb_wires, 4) host array, or a device pointer with device=True (the
+        outputs then go through device buffers of the call's own: mi_r1cs_eval_dev)"""
+        outs = [np.zeros((n_constraints, 4), np.uint64) if which & (1 << k) else None for k in range(3)]
+        if not device:
+            self._ck(self.lib.mi_r1cs_eval(self.h, rh, _p(_u64(W)), C.c_uint32(which), *[_p(o) for o in outs]))
+            return tuple(outs)
+        bufs = [self.alloc(32 * n_constraints + 32) if o is not None else None for o in outs]
+        try:
+            self._ck(self.lib.mi_r1cs_eval_dev(self.h, rh, _p(W), C.c_uint32(which), *[_p(b.ptr if b else None) for b in bufs]))
+            self.sync()
+            return tuple(None if b is None else b.download((n_constraints, 4)) for b in bufs)
+        finally:
+            for b in bufs:
+                if b: b.free()
+
+    def r1cs_check(self, rh, W, device=False):
+        """mi_r1cs_check_dev -> (rows with (A W)(B W) != C W, the lowest of them or 2^64 - 1); W as in r1cs_eval"""
+        n_bad, first = C.c_uint64(), C.c_uint64()
+        d = None if device else self.to_dev(_u64(W))
+        try:
+            self._ck(self.lib.mi_r1cs_check_dev(self.h, rh, _p(W if device else d.ptr), C.byref(n_bad), C.byref(first)))
+        finally:
+            if d: d.free()
+        return int(n_bad.value), int(first.value)
+
+    def r1cs_stats(self):
+        st = R1csStats(); self._ck(self.lib.mi_r1cs_get_stats(self.h, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in R1csStats._fields_}
+
+    def prove_w(self, pkh, rh, W, r, s, flags=0, device=False, n_wires=None):
+        """mi_groth16_prove_w[_dev]: the proof from the wire vector alone"""
+        out = np.zeros(32, np.uint64); st = Stats()
+        r, s = _u64(r), _u64(s)
+        if device:
+            self._ck(self.lib.mi_groth16_prove_w_dev(self.h, pkh, rh, _p(W), C.c_size_t(n_wires), C.c_uint32(flags), _p(r), _p(s), _p(out), C.byref(st)))
+        else:
+            W = _u64(W)
+            self._ck(self.lib.mi_groth16_prove_w(self.h, pkh, rh, _p(W), C.c_size_t(W.shape[0] if n_wires is None else n_wires), C.c_uint32(flags),
+                                                 _p(r), _p(s), _p(out), C.byref(st)))
+        return {"ar": out[:8].copy(), "bs": out[8:24].copy(), "krs": out[24:].copy(), "raw": out}, st.as_dict()
+
     def trim(self):
         """mi_ctx_trim: every grow-only workspace of this (idle) context goes back to the device"""
         self._ck(self.lib.mi_ctx_trim(self.h))
@@ -576,6 +640,37 @@ class Prover:
         if rc != 0:
             raise MiError(f"mi_prover_submit_bsb22: rc={rc}")
         self._pending[t.value] = (out, st, {"keep": (W, a, b, c, vals, arr, challenge), "pok": pok})
+        return t.value
+
+    # ---- from W alone (include/mi355x_groth16_r1cs.h)
+    def submit_w(self, pkh, rh, W, r, s, flags=0, device=False, n_wires=None) -> int:
+        out = np.zeros(32, np.uint64); st = Stats(); t = C.c_uint64()
+        r, s = _u64(r), _u64(s)
+        if device:
+            keep = ()
+            rc = self.lib.mi_prover_submit_w_dev(self.h, pkh, rh, _p(W), C.c_size_t(n_wires), C.c_uint32(flags), _p(r), _p(s), _p(out), C.byref(st), C.byref(t))
+        else:
+            W = _u64(W); keep = (W,)
+            rc = self.lib.mi_prover_submit_w(self.h, pkh, rh, _p(W), C.c_size_t(W.shape[0] if n_wires is None else n_wires), C.c_uint32(flags),
+                                             _p(r), _p(s), _p(out), C.byref(st), C.byref(t))
+        if rc != 0:
+            raise MiError(f"mi_prover_submit_w: rc={rc}")
+        self._pending[t.value] = (out, st, keep)
+        return t.value
+
+    def submit_w_bsb22(self, pkh, rh, W, r, s, commitments, challenge, flags=0) -> int:
+        """submit_bsb22 without a, b, c"""
+        out = np.zeros(32, np.uint64); st = Stats(); t = C.c_uint64(); pok = np.zeros(8, np.uint64)
+        r, s, challenge, W = _u64(r), _u64(s), _u64(challenge), _u64(W)
+        vals = [_u64(v) for _, v in commitments]
+        arr = (Bsb22Input * len(commitments))()
+        for i, ((key, _), v) in enumerate(zip(commitments, vals)):
+            arr[i].key = key if isinstance(key, int) else key.value; arr[i].values = v.ctypes.data; arr[i].n = v.shape[0]
+        rc = self.lib.mi_prover_submit_w_bsb22(self.h, pkh, rh, _p(W), C.c_size_t(W.shape[0]), C.c_uint32(flags), _p(r), _p(s), arr,
+                                               C.c_uint32(len(commitments)), _p(challenge), _p(out), _p(pok), C.byref(st), C.byref(t))
+        if rc != 0:
+            raise MiError(f"mi_prover_submit_w_bsb22: rc={rc}")
+        self._pending[t.value] = (out, st, {"keep": (W, vals, arr, challenge), "pok": pok})
         return t.value
 
     def trim(self):

@@ -12,6 +12,7 @@
 #include "../../include/mi355x_whir_ingest.h"
 #include "../../include/mi355x_groth16_debug.h"
 #include "../../include/mi355x_groth16_setup.h"
+#include "../../include/mi355x_groth16_r1cs.h"
 
 struct DevBuf {             // growable device scratch owned by the ctx (no hipMalloc in the hot path
     void *p = nullptr;      // after warm-up: buffers only ever grow)
@@ -53,6 +54,8 @@ struct mi_ctx {
     std::mutex err_m;          // a prove enqueues its MSM groups from helper threads (prove.hip): failures there report through mi_set_err
     mi_stats stats{};
     mi_setup_stats setup_stats{};   // last mi_groth16_setup[_exponents] call (setup.hip)
+    mi_r1cs_stats r1cs_stats{};     // last evaluation of a resident R1CS on this context (r1cs.hip); eval_ms is read from ev[12], ev[13] on request
+    bool r1cs_timed = false;
     hipEvent_t ev[24]{};
     // scratch
     alignas(16) unsigned char ntt_state[384];  // NttState (ntt.hip): root tables + plan knobs

@@ -17,6 +17,7 @@
 // 13 % of the throughput; on the uploader it overlaps the previous proofs' kernels.
 #include <hip/hip_runtime.h>
 #include "prove_internal.h"
+#include "r1cs_internal.h"
 #include <chrono>
 #include <cstdlib>
 #include <condition_variable>
@@ -47,6 +48,9 @@ struct Job {
     std::vector<mi_bsb22_input> bsb;
     mi_fr challenge{};
     mi_g1_affine *pok_out = nullptr;
+    // mi_prover_submit_w*: a, b (and c with MI_PROVE_W_EVAL_C) are evaluated by the worker from W and this resident R1CS; a, b, c above stay null
+    const mi_r1cs *r1cs = nullptr;
+    uint32_t w_flags = 0;
 };
 struct InputSet {          // W | a | b | c of one staged host job
     void *p = nullptr;
@@ -131,7 +135,9 @@ static void worker_main(mi_prover *p, mi_ctx *ctx) {
             };
             try { f_pok = std::async(std::launch::async, enq); } catch (...) { rc_pok = enq(); pok_pending = rc_pok == MI_OK; if (rc_pok != MI_OK) pok_err = pok_enq_err; }
         }
-        if (j->gated) {
+        if (j->r1cs) {   // W is resident (a host job's W was staged by the uploader, which hands such a job over complete)
+            rc = mi_groth16_prove_w_dev(ctx, j->pk, j->r1cs, j->W, j->n_wires, j->w_flags, &j->r, &j->s, j->out, j->stats);
+        } else if (j->gated) {
             InputSet &set = p->sets[j->set];
             const std::function<bool(int)> abc = [&](int k) -> bool {   // blocks until k of a, b, c are resident (or their upload has failed)
                 std::unique_lock<std::mutex> lk(p->m);
@@ -199,6 +205,7 @@ static void uploader_main(mi_prover *p) {
         }
         InputSet &set = p->sets[si];
         const MiRange range_up("mi.pool.upload");
+        // (a job that proves from W alone has n_constraints = 0 here: W is all it stages)
         const size_t wb = j->n_wires * sizeof(mi_fr), cb = j->n_constraints * sizeof(mi_fr), need = wb + 3 * cb + 128;
         hipError_t e = hipSuccess;
         const char *what = "";
@@ -218,7 +225,7 @@ static void uploader_main(mi_prover *p) {
             // (no events on this stream: a marker between two pageable copies slowed the copies behind it -- the hand-overs are ordered
             //  by synchronising the stream on this thread instead)
             if (wb) e = hipMemcpyAsync(base, j->W, wb, hipMemcpyHostToDevice, p->copy_stream);
-            if (e == hipSuccess && p->early_handover) e = hipStreamSynchronize(p->copy_stream);
+            if (e == hipSuccess && (p->early_handover || j->r1cs)) e = hipStreamSynchronize(p->copy_stream);
         }
         if (e != hipSuccess) {
             (void)hipGetLastError();
@@ -227,6 +234,18 @@ static void uploader_main(mi_prover *p) {
                 p->uploading = false;
             }
             finish_job(p, j, e == hipErrorOutOfMemory ? MI_ENOMEM : MI_EHIP, what);   // (a literal: nothing on this thread may throw)
+            p->cv_work.notify_all();
+            continue;
+        }
+        if (j->r1cs) {   // W only: it is resident, the job is complete; the worker evaluates a and b from it
+            {
+                std::lock_guard<std::mutex> lk(p->m);
+                j->h2d_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+                set.abc_state = 3;
+                p->uploading = false;
+                j->W = (const mi_fr *)base;
+                p->queue.push_back(j);
+            }
             p->cv_work.notify_all();
             continue;
         }
@@ -361,7 +380,8 @@ const char *mi_prover_last_error(mi_prover *p) {
 
 static int32_t submit(mi_prover *p, bool host, mi_pk *pk, const mi_fr *W, size_t n_wires, const mi_fr *a, const mi_fr *b, const mi_fr *c,
                       size_t n_constraints, const mi_fr *r, const mi_fr *s, mi_proof_out *out, mi_stats *stats, uint64_t *ticket,
-                      const mi_bsb22_input *bsb = nullptr, uint32_t n_bsb = 0, const mi_fr *challenge = nullptr, mi_g1_affine *pok_out = nullptr) {
+                      const mi_bsb22_input *bsb = nullptr, uint32_t n_bsb = 0, const mi_fr *challenge = nullptr, mi_g1_affine *pok_out = nullptr,
+                      const mi_r1cs *r1cs = nullptr, uint32_t w_flags = 0) {
     if (!p || !pk || !r || !s || !out || !ticket || (!W && n_wires) || ((!a || !b) && n_constraints)) return MI_EINVAL;   // c == null: c = a o b
     if (n_bsb && (!bsb || !challenge || !pok_out || n_bsb > MI_PK_RAW_MAX_COMMITMENTS)) return MI_EINVAL;
     for (uint32_t i = 0; i < n_bsb; i++) if (!bsb[i].key || (!bsb[i].values && bsb[i].n)) return MI_EINVAL;
@@ -373,6 +393,7 @@ static int32_t submit(mi_prover *p, bool host, mi_pk *pk, const mi_fr *W, size_t
     j->n_wires = n_wires; j->n_constraints = n_constraints;
     j->r = *r; j->s = *s;   // copied: the caller's r, s need not outlive the call
     j->out = out; j->stats = stats;
+    j->r1cs = r1cs; j->w_flags = w_flags;
     {
         std::lock_guard<std::mutex> lk(p->m);
         if (p->stop) { delete j; return MI_EINVAL; }
@@ -399,6 +420,27 @@ int32_t mi_prover_submit_bsb22(mi_prover *p, mi_pk *pk, const mi_fr *W, size_t n
                                size_t n_constraints, const mi_fr *r, const mi_fr *s, const mi_bsb22_input *commitments, uint32_t n_commitments,
                                const mi_fr *challenge, mi_proof_out *out, mi_g1_affine *pok_out, mi_stats *stats, uint64_t *ticket) {
     return submit(p, true, pk, W, n_wires, a, b, c, n_constraints, r, s, out, stats, ticket, commitments, n_commitments, challenge, pok_out);
+}
+// From W alone (include/mi355x_groth16_r1cs.h).  Sizes and flags are checked by the job (mi_groth16_prove_w_dev) and reported through
+// mi_prover_wait like every other failure of a proof; what would make the upload stage read out of bounds is refused here.
+static int32_t submit_w(mi_prover *p, bool host, mi_pk *pk, const mi_r1cs *r1cs, const mi_fr *W, size_t n_wires, uint32_t flags, const mi_fr *r, const mi_fr *s,
+                        mi_proof_out *out, mi_stats *stats, uint64_t *ticket, const mi_bsb22_input *bsb = nullptr, uint32_t n_bsb = 0,
+                        const mi_fr *challenge = nullptr, mi_g1_affine *pok_out = nullptr) {
+    if (!r1cs || !W || !pk || n_wires != pk->nb_wires || n_wires != r1cs->nb_wires) return MI_EINVAL;
+    return submit(p, host, pk, W, n_wires, nullptr, nullptr, nullptr, 0, r, s, out, stats, ticket, bsb, n_bsb, challenge, pok_out, r1cs, flags);
+}
+int32_t mi_prover_submit_w(mi_prover *p, mi_pk *pk, const mi_r1cs *r1cs, const mi_fr *W, size_t n_wires, uint32_t flags,
+                           const mi_fr *r, const mi_fr *s, mi_proof_out *out, mi_stats *stats, uint64_t *ticket) {
+    return submit_w(p, true, pk, r1cs, W, n_wires, flags, r, s, out, stats, ticket);
+}
+int32_t mi_prover_submit_w_dev(mi_prover *p, mi_pk *pk, const mi_r1cs *r1cs, const mi_fr *W_dev, size_t n_wires, uint32_t flags,
+                               const mi_fr *r, const mi_fr *s, mi_proof_out *out, mi_stats *stats, uint64_t *ticket) {
+    return submit_w(p, false, pk, r1cs, W_dev, n_wires, flags, r, s, out, stats, ticket);
+}
+int32_t mi_prover_submit_w_bsb22(mi_prover *p, mi_pk *pk, const mi_r1cs *r1cs, const mi_fr *W, size_t n_wires, uint32_t flags,
+                                 const mi_fr *r, const mi_fr *s, const mi_bsb22_input *commitments, uint32_t n_commitments,
+                                 const mi_fr *challenge, mi_proof_out *out, mi_g1_affine *pok_out, mi_stats *stats, uint64_t *ticket) {
+    return submit_w(p, true, pk, r1cs, W, n_wires, flags, r, s, out, stats, ticket, commitments, n_commitments, challenge, pok_out);
 }
 // Pedersen Commit inside the solve (gnark's BSB22 hint override): synchronous, from any thread; one commitment at a time on a context of
 // its own whose streams rank with the pool's first context, so that a blocked solver waits for one small MSM, not for a proof

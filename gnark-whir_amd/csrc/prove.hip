@@ -7,6 +7,7 @@
 //   prove        computeH on the device -> three gathers of W -> five MSMs -> O(1)-point blinding and
 //                assembly on the host (Ar, Bs1, Krs, Bs exactly as prove.go composes them).
 #include "prove_internal.h"
+#include "r1cs_internal.h"
 #include <cstring>
 #include <vector>
 #include <chrono>
@@ -483,18 +484,22 @@ struct HostInputs { const mi_fr *W, *a, *b, *c; };
 // Device inputs that are still ARRIVING (the prover pool's upload stage, pool.hip): W is resident when the call is made; abc() blocks
 // the host until a, b, c are resident too and returns true (false: their upload failed).  Host-side waits on purpose: events recorded
 // on the pool's copy stream between its pageable copies slowed those copies down (round 3: uploads of 50-70 ms instead of 19).
+// Proving from W alone (mi_groth16_prove_w*): a = A W and b = B W (and c = C W with eval_c) come from the resident R1CS, evaluated into
+// context workspace on the context's stream; a, b, c of prove_common are ignored.
+struct WEval { const mi_r1cs *r1cs; bool eval_c; };
 struct AbcGate { const std::function<bool(int)> *abc; /* abc(k): blocks until k of a, b, c are resident */ bool abc_arrived; /* they all were when the job was picked up */ };
 
 // W, a, b, c: device buffers (for host inputs: staging areas the uploads below fill).
 static int32_t prove_common(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wires, const mi_fr *a, const mi_fr *b, const mi_fr *c,
                             size_t n_constraints, const mi_fr *r_m, const mi_fr *s_m, mi_proof_out *out, mi_stats *stats, const HostInputs *host,
-                            const AbcGate *gate = nullptr) {
+                            const AbcGate *gate = nullptr, const WEval *weval = nullptr) {
     if (!ctx || !pk || !r_m || !s_m || !out) return MI_EINVAL;
     const MiRange range_all("mi.prove");
+    if (weval) n_constraints = weval->r1cs->nc;   // a, b, c are not given: the evaluation below produces them
     // null W / a / b only where the matching count is 0 (the header's rule, as the pool's submit applies it); c == null: c = a o b on the device
-    if ((!W && n_wires) || ((!a || !b) && n_constraints)) MI_FAIL(ctx, MI_EINVAL, "prove: null W, a or b with a non-zero count");
-    if (host && ((!host->W && n_wires) || ((!host->a || !host->b) && n_constraints))) MI_FAIL(ctx, MI_EINVAL, "prove: null host W, a or b with a non-zero count");
-    const bool derive_c = host ? !host->c : !c;
+    if ((!W && n_wires) || (!weval && (!a || !b) && n_constraints)) MI_FAIL(ctx, MI_EINVAL, "prove: null W, a or b with a non-zero count");
+    if (host && ((!host->W && n_wires) || (!weval && (!host->a || !host->b) && n_constraints))) MI_FAIL(ctx, MI_EINVAL, "prove: null host W, a or b with a non-zero count");
+    const bool derive_c = weval ? !weval->eval_c : host ? !host->c : !c;
     const size_t N = (size_t)1 << pk->log_n;
     if (pk->wire_lo || pk->n_z_msm != N - 1) MI_FAIL(ctx, MI_EINVAL, "prove: this key is one part of a sharded key (use mi_groth16_prove_sharded)");
     if (n_wires != pk->nb_wires || n_constraints > N) MI_FAIL(ctx, MI_EINVAL, "prove: witness size does not match the proving key");
@@ -557,6 +562,37 @@ static int32_t prove_common(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wir
         }
     };
     auto main_part = [&]() -> int32_t {
+        if (weval) {
+            // W alone: upload it (host inputs) and start the wire MSMs exactly as below; a and b are then evaluated on the context's
+            // stream and computeH runs behind them part by part.  Nothing else crosses the bus, so nothing holds this thread.
+            if (host) {
+                const auto t_up = std::chrono::steady_clock::now();
+                hipStream_t cps = nullptr;
+                MI_TRY(mi_copy_stream(ctx, &cps));
+                MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the staging area may still be read by an earlier call's kernels
+                MI_CHECK_HIP(ctx, hipEventRecord(ev[11], ctx->stream));
+                {
+                    const MiRange range("mi.prove.upload");
+                    if (n_wires) MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)W, host->W, n_wires * sizeof(mi_fr), hipMemcpyHostToDevice, cps));
+                    MI_CHECK_HIP(ctx, hipStreamSynchronize(cps));
+                }
+                ctx->stats.h2d_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
+                start_wires(nullptr);   // W is resident: nothing to wait for
+            } else {
+                MI_CHECK_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
+                start_wires(ev[2]);
+            }
+            const mi_fr *ea = nullptr, *eb = nullptr, *ec = nullptr;
+            MI_TRY(mi_r1cs_eval_ws(ctx, weval->r1cs, W, weval->eval_c, &ea, &eb, &ec));
+            MI_TRY(mi_compute_h_part(ctx, pk->log_n, 0, ea, n_constraints, (mi_fr *)h));
+            MI_TRY(mi_compute_h_part(ctx, pk->log_n, 1, eb, n_constraints, (mi_fr *)h));
+            if (derive_c) MI_TRY(mi_compute_h_part(ctx, pk->log_n, 2, ea, n_constraints, (mi_fr *)h, eb));
+            else MI_TRY(mi_compute_h_part(ctx, pk->log_n, 2, ec, n_constraints, (mi_fr *)h));
+            MI_TRY(last_part_of_h());
+            MI_CHECK_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
+            h_recorded.set_value(ev[3]); h_promised = true;
+            return mi_prove_enqueue_z_msm(ctx, pk, (const mi_fr *)h, ev[3]);
+        }
         if (gate) {
             // inputs on their way into HBM (pool upload stage): the wire MSMs start as soon as W is there; a, b, c (3/4 of the bytes)
             // finish arriving behind them, and computeH waits for exactly that
@@ -681,7 +717,36 @@ int32_t mi_groth16_prove_dev_gated(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_
     return prove_common(ctx, pk, W, n_wires, a, b, c, n_constraints, r, s, out, stats, nullptr, &gate);
 }
 
+// what both W-only entry points refuse before anything is enqueued
+static int32_t check_w_inputs(mi_ctx *ctx, const mi_pk *pk, const mi_r1cs *r1cs, const mi_fr *W, size_t n_wires, uint32_t flags) {
+    if (!r1cs) MI_FAIL(ctx, MI_EINVAL, "prove_w: r1cs is null");
+    if (!W) MI_FAIL(ctx, MI_EINVAL, "prove_w: W is null");
+    if (flags & ~MI_PROVE_W_EVAL_C) MI_FAIL(ctx, MI_EINVAL, "prove_w: unknown flag");
+    if (r1cs->dev != ctx->dev) MI_FAIL(ctx, MI_EINVAL, "prove_w: the r1cs was loaded on another device");
+    if (pk->wire_lo || pk->n_z_msm != ((u64)1 << pk->log_n) - 1) MI_FAIL(ctx, MI_EINVAL, "prove_w: this key is one part of a sharded key");
+    if (n_wires != pk->nb_wires) MI_FAIL(ctx, MI_EINVAL, "prove_w: n_wires does not match the proving key");
+    if (n_wires != r1cs->nb_wires) MI_FAIL(ctx, MI_EINVAL, "prove_w: n_wires does not match the r1cs");
+    if (pk->log_n != r1cs->log_n) MI_FAIL(ctx, MI_EINVAL, "prove_w: the key's log_n is not the domain of the r1cs's n_constraints");
+    return MI_OK;
+}
+
 extern "C" {
+int32_t mi_groth16_prove_w_dev(mi_ctx *ctx, mi_pk *pk, const mi_r1cs *r1cs, const mi_fr *W_dev, size_t n_wires, uint32_t flags,
+                               const mi_fr *r, const mi_fr *s, mi_proof_out *out, mi_stats *stats) {
+    if (!ctx || !pk || !r || !s || !out) return MI_EINVAL;
+    MI_TRY(check_w_inputs(ctx, pk, r1cs, W_dev, n_wires, flags));
+    const WEval we{r1cs, (flags & MI_PROVE_W_EVAL_C) != 0};
+    return prove_common(ctx, pk, W_dev, n_wires, nullptr, nullptr, nullptr, 0, r, s, out, stats, nullptr, nullptr, &we);
+}
+int32_t mi_groth16_prove_w(mi_ctx *ctx, mi_pk *pk, const mi_r1cs *r1cs, const mi_fr *W, size_t n_wires, uint32_t flags,
+                           const mi_fr *r, const mi_fr *s, mi_proof_out *out, mi_stats *stats) {
+    if (!ctx || !pk || !r || !s || !out) return MI_EINVAL;
+    MI_TRY(check_w_inputs(ctx, pk, r1cs, W, n_wires, flags));
+    MI_TRY(mi_reserve(ctx, ctx->ws[16], n_wires * 32 + 128));
+    const HostInputs host{W, nullptr, nullptr, nullptr};
+    const WEval we{r1cs, (flags & MI_PROVE_W_EVAL_C) != 0};
+    return prove_common(ctx, pk, (mi_fr *)ctx->ws[16].p, n_wires, nullptr, nullptr, nullptr, 0, r, s, out, stats, &host, nullptr, &we);
+}
 int32_t mi_groth16_prove_dev(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wires, const mi_fr *a, const mi_fr *b, const mi_fr *c,
                              size_t n_constraints, const mi_fr *r, const mi_fr *s, mi_proof_out *out, mi_stats *stats) {
     return prove_common(ctx, pk, W, n_wires, a, b, c, n_constraints, r, s, out, stats, nullptr);

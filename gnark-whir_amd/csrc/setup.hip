@@ -22,6 +22,8 @@
 //      mi_pk_load_range / mi_pedersen_pk_adopt.  Every exponent array is freed as soon as its points exist.
 // Only the R1CS goes up; the infinity masks, the counts and the verifying key come down.
 #include "prove_internal.h"
+#include "r1cs_internal.h"
+#include "sparse_fr.cuh"
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -30,23 +32,11 @@
 
 namespace {
 
-constexpr u32 SHORT = 16;      // a column of at most this many entries is summed by one thread
-constexpr u32 CHUNK = 512;     // entries of a longer column that one wave sums
+constexpr u32 SHORT = SPARSE_SHORT;   // a column of at most this many entries is summed by one thread (sparse_fr.cuh: 16)
+constexpr u32 CHUNK = SPARSE_CHUNK;   // entries of a longer column that one wave sums (512)
 constexpr u32 LAG_RUN = 64;    // rows per thread of k_lagrange: one inversion per run
 constexpr u32 SCAN_ITEMS = 8, SCAN_BLOCK = 256, SCAN_TILE = SCAN_ITEMS * SCAN_BLOCK;
 
-MI_D Fr ld_fr(const Fr *p) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    const uint4 a = q[0], b = q[1];
-    Fr r;
-    r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w; r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-    return r;
-}
-MI_D void st_fr(Fr *p, const Fr &v) {
-    uint4 *q = reinterpret_cast<uint4 *>(p);
-    q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-    q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
 MI_D Fr fr_pow_u64(Fr b, u64 e) {
     Fr acc = Fr::one();
     while (e) {
@@ -55,17 +45,6 @@ MI_D Fr fr_pow_u64(Fr b, u64 e) {
         e >>= 1;
     }
     return acc;
-}
-// the sum of v over the 64 lanes of a wave, in every lane (all lanes active)
-MI_D Fr wave_sum(Fr v) {
-#pragma unroll 1
-    for (int o = 32; o >= 1; o >>= 1) {
-        Fr t;
-#pragma unroll
-        for (int i = 0; i < 8; i++) t.l[i] = (u32)__shfl_xor((int)v.l[i], o);
-        v = v + t;
-    }
-    return v;
 }
 // cnt[key] += 1 for every active lane; returns the value this lane's increment saw.  Lanes of one wave that share a key are served by
 // ONE atomic: each round takes the first active lane's key, its lanes count themselves with a ballot, the lowest adds the count.
@@ -303,93 +282,18 @@ mi_g2_affine g2_generator() {
     mi_g2_affine o; std::memcpy(&o, &g, 128); return o;
 }
 
-// what the host derives from the inputs before any device work
-struct Plan {
-    u32 log_n = 0;
-    u64 N = 0, nc = 0, nb_wires = 0;
-    u32 nb_public = 0, n_commitments = 0;
-    std::vector<u32> row_ptr[3];     // the row starts in 32 bits (nnz < 2^32)
-    u32 nnz[3] = {0, 0, 0};
-    std::vector<u32> removed;        // committed + commitment wires, ascending: the private wires without a pk.G1.K point
-    std::vector<u32> vk_wires;       // public wires, then the commitment wires ascending
+// what the host derives from the inputs before any device work: the R1CS's shape (r1cs_internal.h, shared with the resident handle
+// of r1cs.hip) and the trapdoor's part
+struct Plan : R1csShape {
     Fr tau, alpha, beta, delta_inv, gamma_inv, lam, zt, w;
     TauPowers tp;
 };
 
-int32_t check_matrix(mi_ctx *ctx, const char *name, const mi_r1cs_matrix &m, const mi_r1cs_desc *d, Plan &pl, int k) {
-    const std::string nm(name);
-    if (!m.row_ptr) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".row_ptr is null");
-    if (m.row_ptr[0] != 0) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".row_ptr[0] is not 0");
-    const u64 n = d->n_constraints;
-    for (u64 i = 0; i < n; i++)
-        if (m.row_ptr[i + 1] < m.row_ptr[i]) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".row_ptr decreases at row " + std::to_string(i));
-    const u64 nnz = m.row_ptr[n];
-    if (nnz >> 32) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".row_ptr[n_constraints]: 2^32 entries or more");
-    if (nnz && (!m.col || !m.coeff)) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".col / " + nm + ".coeff is null");
-    // every index, on a few threads: the device never sees an index out of range
-    const unsigned T = nnz > (1u << 20) ? 8 : 1;
-    std::vector<u64> bad_col(T, ~0ull), bad_coeff(T, ~0ull);
-    auto scan = [&](unsigned t) {
-        const u64 lo = nnz * t / T, hi = nnz * (t + 1) / T;
-        for (u64 e = lo; e < hi; e++) {
-            if (m.col[e] >= d->nb_wires && bad_col[t] == ~0ull) bad_col[t] = e;
-            if (m.coeff[e] >= d->n_coeffs && bad_coeff[t] == ~0ull) bad_coeff[t] = e;
-        }
-    };
-    if (T == 1) scan(0);
-    else {
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < T; t++) th.emplace_back(scan, t);
-        for (auto &x : th) x.join();
-    }
-    for (unsigned t = 0; t < T; t++) {
-        if (bad_col[t] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".col[" + std::to_string(bad_col[t]) + "] is not below nb_wires");
-        if (bad_coeff[t] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "setup: " + nm + ".coeff[" + std::to_string(bad_coeff[t]) + "] is not below n_coeffs");
-    }
-    pl.nnz[k] = (u32)nnz;
-    pl.row_ptr[k].resize(n + 1);
-    for (u64 i = 0; i <= n; i++) pl.row_ptr[k][i] = (u32)m.row_ptr[i];
-    return MI_OK;
-}
-
 int32_t make_plan(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_trapdoor *td, Plan &pl) {
     if (!d) MI_FAIL(ctx, MI_EINVAL, "setup: r1cs is null");
     if (!td) MI_FAIL(ctx, MI_EINVAL, "setup: trapdoor is null");
-    if (d->n_constraints > ((u64)1 << MI_SETUP_MAX_LOG_N)) MI_FAIL(ctx, MI_EINVAL, "setup: n_constraints: log_n above 27");
-    u32 log_n = 0;
-    while (((u64)1 << log_n) < d->n_constraints) log_n++;
-    pl.log_n = log_n; pl.N = (u64)1 << log_n; pl.nc = d->n_constraints;
-    if (d->nb_wires == 0 || d->nb_wires > MI_MSM_MAX_PAIRS) MI_FAIL(ctx, MI_EINVAL, "setup: nb_wires is 0 or above 2^27");
-    if (d->nb_public == 0 || d->nb_public > d->nb_wires) MI_FAIL(ctx, MI_EINVAL, "setup: nb_public is 0 or above nb_wires");
-    pl.nb_wires = d->nb_wires; pl.nb_public = d->nb_public;
-    if (!d->coeffs && d->n_coeffs) MI_FAIL(ctx, MI_EINVAL, "setup: coeffs is null");
-    if (d->n_coeffs >> 32) MI_FAIL(ctx, MI_EINVAL, "setup: n_coeffs: 2^32 entries or more");
-    MI_TRY(check_matrix(ctx, "A", d->A, d, pl, 0));
-    MI_TRY(check_matrix(ctx, "B", d->B, d, pl, 1));
-    MI_TRY(check_matrix(ctx, "C", d->C, d, pl, 2));
-    // commitments
-    if (d->n_commitments > MI_PK_RAW_MAX_COMMITMENTS) MI_FAIL(ctx, MI_EINVAL, "setup: n_commitments above MI_PK_RAW_MAX_COMMITMENTS");
-    pl.n_commitments = d->n_commitments;
-    if (d->n_commitments && (!d->committed || !d->n_committed || !d->commitment_wire)) MI_FAIL(ctx, MI_EINVAL, "setup: committed / n_committed / commitment_wire is null");
-    std::vector<u32> cw;
-    for (u32 k = 0; k < d->n_commitments; k++) {
-        if (d->n_committed[k] && !d->committed[k]) MI_FAIL(ctx, MI_EINVAL, "setup: committed[" + std::to_string(k) + "] is null");
-        for (u64 i = 0; i < d->n_committed[k]; i++) {
-            const u32 j = d->committed[k][i];
-            if (j < d->nb_public || j >= d->nb_wires) MI_FAIL(ctx, MI_EINVAL, "setup: committed[" + std::to_string(k) + "][" + std::to_string(i) + "] is not a private wire");
-            pl.removed.push_back(j);
-        }
-        const u32 j = d->commitment_wire[k];
-        if (j < d->nb_public || j >= d->nb_wires) MI_FAIL(ctx, MI_EINVAL, "setup: commitment_wire[" + std::to_string(k) + "] is not a private wire");
-        pl.removed.push_back(j);
-        cw.push_back(j);
-    }
-    std::sort(pl.removed.begin(), pl.removed.end());
-    if (std::adjacent_find(pl.removed.begin(), pl.removed.end()) != pl.removed.end())
-        MI_FAIL(ctx, MI_EINVAL, "setup: committed / commitment_wire: a wire is listed twice");
-    std::sort(cw.begin(), cw.end());
-    for (u32 j = 0; j < d->nb_public; j++) pl.vk_wires.push_back(j);
-    pl.vk_wires.insert(pl.vk_wires.end(), cw.begin(), cw.end());
+    MI_TRY(mi_r1cs_validate(ctx, "setup", d, pl));
+    const u32 log_n = pl.log_n;
     // the trapdoor
     const Fr delta = fr_of(td->delta), gamma = fr_of(td->gamma);
     pl.tau = fr_of(td->tau); pl.alpha = fr_of(td->alpha); pl.beta = fr_of(td->beta);

@@ -19,6 +19,7 @@
 #include <vector>
 #include "../../include/mi355x_groth16.h"
 #include "../../include/mi355x_groth16_group.h"
+#include "../../include/mi355x_groth16_r1cs.h"
 #include "../../include/mi355x_groth16_debug.h"   // (this mirror is the TEST side: generators and knobs)
 
 namespace groth16 {
@@ -174,6 +175,36 @@ inline mi_g2_jac MultiExpG2(const Context &ctx, const std::vector<mi_g2_affine> 
     mi_g2_jac out{};
     ctx.check(mi_msm_g2(ctx.get(), points.data(), scalars.data(), points.size(), 0, &out));
     return out;
+}
+// The compiled constraint system kept on the device (include/mi355x_groth16_r1cs.h): what lets Prove take the solved wire vector alone.
+class ResidentR1CS {
+  public:
+    ResidentR1CS(const Context &ctx, const mi_r1cs_desc &desc) : ctx_(ctx) { ctx_.check(mi_r1cs_load(ctx_.get(), &desc, &r_)); }
+    ~ResidentR1CS() { if (r_) mi_r1cs_free(ctx_.get(), r_); }
+    ResidentR1CS(const ResidentR1CS &) = delete;
+    ResidentR1CS &operator=(const ResidentR1CS &) = delete;
+    mi_r1cs *get() const { return r_; }
+    uint64_t Bytes() const { uint64_t b = 0; ctx_.check(mi_r1cs_bytes(r_, &b)); return b; }
+    // cs.IsSolved for a wire vector in device memory: rows with (A W)(B W) != C W, and the first of them
+    uint64_t Unsatisfied(const mi_fr *W_dev, uint64_t *first_bad = nullptr) const {
+        uint64_t n = 0, first = 0;
+        ctx_.check(mi_r1cs_check_dev(ctx_.get(), r_, W_dev, &n, &first));
+        if (first_bad) *first_bad = first;
+        return n;
+    }
+
+  private:
+    const Context &ctx_;
+    mi_r1cs *r_ = nullptr;
+};
+// groth16.Prove from the solved wire vector alone (host memory): a = A W and b = B W are evaluated on the device
+inline Proof ProveW(const Context &ctx, const ProvingKey &pk, const ResidentR1CS &r1cs, const std::vector<mi_fr> &W, const mi_fr &r, const mi_fr &s,
+                    uint32_t flags = 0, mi_stats *stats = nullptr) {
+    mi_proof_out out{};
+    ctx.check(mi_groth16_prove_w(ctx.get(), pk.get(), r1cs.get(), W.data(), W.size(), flags, &r, &s, &out, stats));
+    Proof p;
+    p.Ar = out.ar; p.Bs = out.bs; p.Krs = out.krs;
+    return p;
 }
 // fft.Domain: FFT / FFTInverse with fft.DIF / fft.DIT and fft.OnCoset()
 enum Decimation { DIF = 0, DIT = 1 };
