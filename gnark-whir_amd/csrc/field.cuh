@@ -417,8 +417,11 @@ MI_HD Fe<P> operator*(const Fe<P> &x, const Fe<P> &y) {
     r.l[7] = (u32)acc;   // column 15 is empty for 8-limb operands; p < 2^254 keeps the result < 2p < 2^256
     return fe_reduce_once(r);
 }
-// the same product without its final conditional subtraction: x < 4p (any limbs), y < p (a table constant: top limb < 2^30, what
-// the carry-less first products of columns >= 8 need) -> a representative below x y / R + p < 2p
+// the same product without its final conditional subtraction: the exact integer (x y + m p) / R with m = -x y / p mod R, a representative
+// below x y / R + p.  Contract: x y < 4 p^2 and y < 2p -- x < 4p (any limbs) by a table constant y < p (the butterflies, the edge factors), or
+// both factors below 2p (ntt_mul_lazy2: the second factor is data) -- so the result is below (4p / R + 1) p < 1.76 p < 2p, and the top limb of
+// y is below 2^31, what the carry-less first products x_(k-7) y_7 of columns >= 8 need (mac96_first; a factor y in [2p, 4p) could break it).
+// The host build of the tests traps on either violation (MI_CHECK_NOWRAP).
 template <class P>
 MI_HD Fe<P> fe_mul_lazy(const Fe<P> &x, const Fe<P> &y) {
     u64 acc = 0;
@@ -466,6 +469,9 @@ MI_HD Fe<P> fe_mul_lazy(const Fe<P> &x, const Fe<P> &y) {   // the product befor
     r.l[7] = (u32)acc;
 #if defined(MI_CHECK_NOWRAP)
     if (acc >> 32) __builtin_trap();   // the result must fit 256 bits (x y / R + p < 2^256)
+    if (y.l[7] >> 31) __builtin_trap();   // the contract of the device form: y < 2p ...
+    Fe<P> over;
+    if (!fe_sub_raw(over, r, fe_twice_modulus<P>())) __builtin_trap();   // ... and x y < 4 p^2, so that the result stays below 2p
 #endif
     return r;
 }

@@ -4,6 +4,7 @@
 #include "ctx.h"
 #include "curve.cuh"
 #include "limb29_ops.cuh"
+#include "lazy_ops.cuh"
 
 // ---------------------------------------------------------------- seeded PRNG (counter based)
 MI_HD u64 sm64(u64 z) {
@@ -193,6 +194,14 @@ __global__ void __launch_bounds__(64) k_limb29_op_g1(int op, u32 *out, const u32
     (void)limb29_op_g1(op, in + i * L29_IN_WORDS, o);
 }
 void launch_limb29_op_g2(hipStream_t st, unsigned grid, int op, u32 *out, const u32 *in, size_t n);   // msm_g2.hip
+// mi_debug_lazy_op_dev: one record of lazy_ops.cuh per lane
+__global__ void __launch_bounds__(64) k_lazy_op(int op, u32 *out, const u32 *in, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    u32 *o = out + i * LZ_OUT_WORDS;
+    for (int w = 0; w < LZ_OUT_WORDS; w++) o[w] = 0;
+    (void)lazy_op(op, in + i * LZ_IN_WORDS, o);
+}
 
 static inline unsigned grid_for(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
@@ -230,6 +239,13 @@ int32_t mi_debug_limb29_op_dev(mi_ctx *ctx, int op, void *out_dev, const void *i
     if (!n) return MI_OK;
     if (g1) hipLaunchKernelGGL(k_limb29_op_g1, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, op, (u32 *)out_dev, (const u32 *)in_dev, n);
     else launch_limb29_op_g2(ctx->stream, grid_for(n, 64), op, (u32 *)out_dev, (const u32 *)in_dev, n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+int32_t mi_debug_lazy_op_dev(mi_ctx *ctx, int op, void *out_dev, const void *in_dev, size_t n) {
+    if (!ctx || op < 0 || op >= LZ_OP_END || ((!out_dev || !in_dev) && n) || n > ((size_t)1 << 30)) return MI_EINVAL;
+    if (!n) return MI_OK;
+    hipLaunchKernelGGL(k_lazy_op, dim3(grid_for(n, 64)), dim3(64), 0, ctx->stream, op, (u32 *)out_dev, (const u32 *)in_dev, n);
     MI_CHECK_HIP(ctx, hipGetLastError());
     return MI_OK;
 }

@@ -37,6 +37,15 @@ int32_t mi_g2_add_dev(mi_ctx *ctx, mi_g2_affine *out_dev, const mi_g2_affine *a_
 #define MI_LIMB29_IN_WORDS 144
 #define MI_LIMB29_OUT_WORDS 80
 int32_t mi_debug_limb29_op_dev(mi_ctx *ctx, int op, void *out_dev, const void *in_dev, size_t n);
+/* the lazy 8 x 32-bit arithmetic under every NTT stage (csrc/field.cuh fe_add_nored / fe_sub_plus2p / fe_condsub_2p / fe_canon / fe_mul_lazy,
+ * csrc/ntt_tile.cuh ntt_bfly_dif / ntt_bfly_dit / ntt_mul_lazy2 and the store_sub expression), over Fr, one record per lane: in_dev holds n
+ * records of MI_LAZY_IN_WORDS u32 (x | y | w, eight limbs each), out_dev receives n of MI_LAZY_OUT_WORDS (two results of eight limbs; words an
+ * op does not write are zero).  op and layout are those of csrc/lazy_ops.cuh, which the host build of the tests runs too: 0 add_nored,
+ * 1 sub_plus2p, 2 condsub_2p, 3 canon, 4 mul_lazy, 5 mul_lazy2, 6 / 7 the DIF butterfly with / without a twiddle, 8 / 9 the DIT butterfly,
+ * 10 store_sub.  Every input must meet the documented contract of its primitive.  MI_EINVAL for an unknown op, null buffers or n > 2^30. */
+#define MI_LAZY_IN_WORDS 24
+#define MI_LAZY_OUT_WORDS 16
+int32_t mi_debug_lazy_op_dev(mi_ctx *ctx, int op, void *out_dev, const void *in_dev, size_t n);
 /* random-gather throughput probe: n_threads lanes each chain `iters` dependent 64-byte gathers from a table of n_entries
  * (a power of two) 64-byte entries; scratch: 1 KiB.  The ceiling the level-1 bucket accumulation's point gathers run against. */
 int32_t mi_bench_gather_dev(mi_ctx *ctx, const void *table_dev, size_t n_entries, size_t n_threads, uint32_t iters,

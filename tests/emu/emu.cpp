@@ -287,6 +287,18 @@ extern "C" int emu_ntt(void *data_v, uint32_t log_n, uint32_t flags, uint32_t lo
                        uint32_t nthr, uint32_t n_valid) {
     return emu_ntt_fused(data_v, log_n, flags, log_e, max_contig, max_strided, nthr, n_valid, nullptr, nullptr);
 }
+// records of lazy_ops.cuh, n of them: the host twin of mi_debug_lazy_op_dev (same op numbers, same layout; every bound the lazy arithmetic
+// relies on traps)
+#include "../../gnark-whir_amd/csrc/lazy_ops.cuh"
+extern "C" int emu_lazy_op(int op, u32 *out, const u32 *in, size_t n) {
+    if (op < 0 || op >= LZ_OP_END) return -1;
+    for (size_t i = 0; i < n; i++) {
+        u32 *o = out + i * LZ_OUT_WORDS;
+        memset(o, 0, LZ_OUT_WORDS * 4);   // words an op does not write stay zero (the device does the same)
+        if (lazy_op(op, in + i * LZ_IN_WORDS, o)) return -1;
+    }
+    return 0;
+}
 
 // ---------------------------------------------------------------- MSM pipeline emulation (msm_core.cuh on the host)
 #include "../../gnark-whir_amd/csrc/msm_core.cuh"
