@@ -19,6 +19,34 @@ struct DevBuf {             // growable device scratch owned by the ctx (no hipM
     size_t cap = 0;
 };
 
+// mi_ctx::ws[]: every workspace slot in use, its owner and the stream its work runs on ("main" = ctx->stream).  A new user takes a
+// free number here; two phases that can be in flight together never share a slot.
+enum {
+    WS_H_B = 0,            // ntt.hip computeH: b's transform                                            main
+    WS_H_C = 1,            // ntt.hip computeH: c's transform                                            main
+    WS_HOST_IO0 = 2,       // host entry points of ntt.hip / msm.hip / group.hip: vector or points       main
+    WS_HOST_IO1 = 3,       // the same: computeH's a, b, c / the MSM's scalars                           main
+    WS_FB_SUMS = 4,        // fixed_base.hip: the XYZZ sums before their conversion                      main
+    WS_FB_INV = 5,         // fixed_base.hip: running products of the batched inversion                  main
+    WS_R1CS_A = 6,         // r1cs.hip: A W of an evaluation into workspace                              main
+    WS_R1CS_B = 7,         // r1cs.hip: B W                                                              main
+    WS_R1CS_C = 8,         // r1cs.hip: C W                                                              main
+    WS_R1CS_PARTIAL = 9,   // r1cs.hip: partials of the long rows' pieces                                main
+    WS_R1CS_CHECK = 10,    // r1cs.hip check: the counters, then one sum per long row                    main
+    WS_R1CS_W = 11,        // r1cs.hip: W of the host entry point                                        main
+    WS_SCAN = 12,          // setup.hip: block sums of the shared u32 scan (scan_u32.cuh)                main
+    WS_H = 14,             // prove.hip / group.hip: h, computeH's result and the Z MSM's scalars        main, read by msm[4].stream
+    WS_PROVE_IN = 16,      // prove.hip / group.hip: W (+ a, b, c) of a prove over host inputs           filled on copy_stream
+    WS_B_WIRES = 17,       // prove.hip: W gathered to the wires that own a pk.G1.B point                msm[1].stream
+    WS_POK_VALUES = 19,    // prove.hip ProveKnowledge: the committed values                             msm[5].stream
+    WS_FB_TABLE = 20,      // fixed_base.hip: the window table of the base                               main
+    WS_FB_SCALARS = 21,    // fixed_base.hip host entry point: the scalars                               main
+    WS_FB_OUT = 22,        // fixed_base.hip host entry point: the points                                main
+    WS_RPRIME = 23,        // msm.hip device entry point: the points in the R' packed form               main
+    WS_COUNT = 24          // 13, 15 and 18 are free
+};
+enum { EV_R1CS_BEGIN = 12, EV_R1CS_END = 13 };   // mi_ctx::ev[]: around the launches of the last R1CS evaluation (r1cs.hip)
+
 #define MI_MSM_SLOTS 6
 #define MI_ZHOOK_SLOT 4    // the slot whose sort may take its count from computeH's last launch (mi_ctx::zhook)
 struct MsmSlot {            // one in-flight MSM (msm.hip): own stream, events, workspaces, pinned result
@@ -54,13 +82,13 @@ struct mi_ctx {
     std::mutex err_m;          // a prove enqueues its MSM groups from helper threads (prove.hip): failures there report through mi_set_err
     mi_stats stats{};
     mi_setup_stats setup_stats{};   // last mi_groth16_setup[_exponents] call (setup.hip)
-    mi_r1cs_stats r1cs_stats{};     // last evaluation of a resident R1CS on this context (r1cs.hip); eval_ms is read from ev[12], ev[13] on request
+    mi_r1cs_stats r1cs_stats{};     // last evaluation of a resident R1CS on this context (r1cs.hip); eval_ms is read from ev[EV_R1CS_BEGIN], ev[EV_R1CS_END] on request
     bool r1cs_timed = false;
     hipEvent_t ev[24]{};
     // scratch
     alignas(16) unsigned char ntt_state[384];  // NttState (ntt.hip): root tables + plan knobs
     alignas(16) unsigned char msm_knobs[128];   // MsmKnobs (msm.hip)
-    DevBuf ws[24];
+    DevBuf ws[WS_COUNT];
     MsmSlot msm[MI_MSM_SLOTS];          // MSM / prove workspaces, see msm.hip / prove.hip
     int cu_count = 256;
     int prio_scheme = 0;      // MI_PRIO_*: how the context's streams rank (api.hip, msm.hip)
@@ -77,6 +105,9 @@ struct mi_ctx {
     struct ZCountHook { bool armed = false, done = false; int slot = -1; uint32_t n = 0, c = 0; alignas(8) unsigned char shape[64]; uint32_t *C1 = nullptr; const void *h = nullptr; /* the vector whose digits were counted */ } zhook;
     uint32_t hold_accum = 0;             // prove: 1 = the wire MSMs' bucket accumulations wait for computeH (mi_debug_set_prove_schedule; measured: no gain)
 };
+
+static_assert(sizeof(mi_ctx::ws) == WS_COUNT * sizeof(DevBuf) && WS_RPRIME == WS_COUNT - 1, "WS_* names every slot of mi_ctx::ws up to its end");
+static_assert(EV_R1CS_END < sizeof(mi_ctx::ev) / sizeof(hipEvent_t), "EV_* index mi_ctx::ev");
 
 // Fault injection for the error-path tests (mi_debug_inject_hip_failure, api.hip): the n-th MI_CHECK_HIP from now reports
 // hipErrorUnknown INSTEAD of running its call.  Disabled (<= 0) it costs one relaxed atomic load per checked call.
@@ -150,6 +181,8 @@ static inline bool mi_try_reserve(DevBuf &b, size_t bytes) {
     b.cap = want;
     return true;
 }
+
+static inline unsigned mi_blocks_of(uint64_t n, uint32_t per) { return (unsigned)((n + per - 1) / per); }   // workgroups of `per` items over n
 
 // ctx->copy_stream, created on first use (api.hip)
 int32_t mi_copy_stream(mi_ctx *ctx, hipStream_t *out);

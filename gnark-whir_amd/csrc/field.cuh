@@ -595,6 +595,21 @@ MI_HD Fe<P> fe_from_u32(u32 v) {
 typedef Fe<FrParams> Fr;
 typedef Fe<FpParams> Fp;
 
+// host: a plain integer below the modulus as four 64-bit limbs, least significant first -> Montgomery form
+template <class P>
+inline Fe<P> fe_from_u64x4(u64 a, u64 b, u64 c, u64 d) {
+    Fe<P> t;
+    t.l[0] = (u32)a; t.l[1] = (u32)(a >> 32); t.l[2] = (u32)b; t.l[3] = (u32)(b >> 32);
+    t.l[4] = (u32)c; t.l[5] = (u32)(c >> 32); t.l[6] = (u32)d; t.l[7] = (u32)(d >> 32);
+    return fe_to_mont(t);
+}
+// host: fft.NewDomain's Generator of the size-2^log_n domain = root^(2^(28 - log_n)), root = gnark-crypto's 2^28-th root of unity
+inline Fr fr_domain_generator(u32 log_n) {
+    Fr g = fe_from_u64x4<FrParams>(0x9bd61b6e725b19f0ull, 0x402d111e41112ed4ull, 0x00e0a7eb8ef62abcull, 0x2a3c09f0a58a7e85ull);
+    for (u32 k = log_n; k < 28; k++) g = fe_sqr(g);
+    return g;
+}
+
 // ---------------------------------------------------------------- Fp2 = Fp[u]/(u^2+1)  (fptower.E2)
 struct Fp2 {
     Fp a0, a1;

@@ -64,13 +64,13 @@ template <class F, class AffT>
 static int32_t fb_run_dev(mi_ctx *ctx, const AffT *base, const mi_fr *scalars_dev, size_t n, AffT *out_dev) {
     if (!ctx || !base || ((!scalars_dev || !out_dev) && n)) return MI_EINVAL;
     if (n == 0) return MI_OK;
-    MI_TRY(mi_reserve(ctx, ctx->ws[20], 32 * 256 * sizeof(Affine<F>)));
-    MI_TRY(mi_reserve(ctx, ctx->ws[4], n * sizeof(XYZZ<F>)));   // the sums before their conversion
-    MI_TRY(mi_reserve(ctx, ctx->ws[5], n * sizeof(F)));         // running products of the batched inversion
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_FB_TABLE], 32 * 256 * sizeof(Affine<F>)));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_FB_SUMS], n * sizeof(XYZZ<F>)));   // the sums before their conversion
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_FB_INV], n * sizeof(F)));         // running products of the batched inversion
     Affine<F> b;
     std::memcpy(&b, base, sizeof(b));
-    Affine<F> *table = (Affine<F> *)ctx->ws[20].p;
-    XYZZ<F> *sums = (XYZZ<F> *)ctx->ws[4].p;
+    Affine<F> *table = (Affine<F> *)ctx->ws[WS_FB_TABLE].p;
+    XYZZ<F> *sums = (XYZZ<F> *)ctx->ws[WS_FB_SUMS].p;
     const unsigned blocks = (unsigned)((n + 63) / 64);
     hipLaunchKernelGGL(k_fb_table<F>, dim3(32 * 256 / 64), dim3(64), 0, ctx->stream, table, b);
     if constexpr (FbG1<F>::value) {
@@ -81,18 +81,18 @@ static int32_t fb_run_dev(mi_ctx *ctx, const AffT *base, const mi_fr *scalars_de
     }
     constexpr int K = 16;
     hipLaunchKernelGGL((k_xyzz_batch_to_affine<F, K>), dim3((unsigned)(((n + K - 1) / K + 63) / 64)), dim3(64), 0, ctx->stream, (const XYZZ<F> *)sums,
-                       (Affine<F> *)out_dev, (F *)ctx->ws[5].p, n);
+                       (Affine<F> *)out_dev, (F *)ctx->ws[WS_FB_INV].p, n);
     MI_CHECK_HIP(ctx, hipGetLastError());
     return MI_OK;
 }
 template <class F, class AffT>
 static int32_t fb_run_host(mi_ctx *ctx, const AffT *base, const mi_fr *scalars, size_t n, AffT *out) {
     if (!ctx || !base || ((!scalars || !out) && n)) return MI_EINVAL;
-    MI_TRY(mi_reserve(ctx, ctx->ws[21], n * sizeof(mi_fr) + 64));
-    MI_TRY(mi_reserve(ctx, ctx->ws[22], n * sizeof(AffT) + 64));
-    if (n) MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[21].p, scalars, n * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->stream));
-    MI_TRY((fb_run_dev<F, AffT>(ctx, base, (const mi_fr *)ctx->ws[21].p, n, (AffT *)ctx->ws[22].p)));
-    if (n) MI_CHECK_HIP(ctx, hipMemcpyAsync(out, ctx->ws[22].p, n * sizeof(AffT), hipMemcpyDeviceToHost, ctx->stream));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_FB_SCALARS], n * sizeof(mi_fr) + 64));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_FB_OUT], n * sizeof(AffT) + 64));
+    if (n) MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[WS_FB_SCALARS].p, scalars, n * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->stream));
+    MI_TRY((fb_run_dev<F, AffT>(ctx, base, (const mi_fr *)ctx->ws[WS_FB_SCALARS].p, n, (AffT *)ctx->ws[WS_FB_OUT].p)));
+    if (n) MI_CHECK_HIP(ctx, hipMemcpyAsync(out, ctx->ws[WS_FB_OUT].p, n * sizeof(AffT), hipMemcpyDeviceToHost, ctx->stream));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MI_OK;
 }

@@ -940,13 +940,13 @@ static int32_t msm_sharded_host(mi_group *g, int curve, const AffT *pts, const m
         range_of(n, g->world, i, lo, hi);
         (void)hipSetDevice(g->dev[i]);
         mi_ctx *ctx = g->ctx[i];
-        G_CTX(g, i, mi_reserve(ctx, ctx->ws[2], (hi - lo) * sizeof(AffT) + 64));
-        G_CTX(g, i, mi_reserve(ctx, ctx->ws[3], (hi - lo) * sizeof(mi_fr) + 64));
+        G_CTX(g, i, mi_reserve(ctx, ctx->ws[WS_HOST_IO0], (hi - lo) * sizeof(AffT) + 64));
+        G_CTX(g, i, mi_reserve(ctx, ctx->ws[WS_HOST_IO1], (hi - lo) * sizeof(mi_fr) + 64));
         if (hi > lo) {
-            G_HIP(g, hipMemcpyAsync(ctx->ws[2].p, pts + lo, (hi - lo) * sizeof(AffT), hipMemcpyHostToDevice, ctx->stream));
-            G_HIP(g, hipMemcpyAsync(ctx->ws[3].p, scalars + lo, (hi - lo) * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->stream));
+            G_HIP(g, hipMemcpyAsync(ctx->ws[WS_HOST_IO0].p, pts + lo, (hi - lo) * sizeof(AffT), hipMemcpyHostToDevice, ctx->stream));
+            G_HIP(g, hipMemcpyAsync(ctx->ws[WS_HOST_IO1].p, scalars + lo, (hi - lo) * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->stream));
         }
-        pp[i] = ctx->ws[2].p; ss[i] = ctx->ws[3].p; nn[i] = hi - lo;
+        pp[i] = ctx->ws[WS_HOST_IO0].p; ss[i] = ctx->ws[WS_HOST_IO1].p; nn[i] = hi - lo;
     }
     return msm_sharded_dev<F>(g, curve, pp.data(), ss.data(), nn.data(), n, flags, mode, out);
 }
@@ -1344,8 +1344,8 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
         const bool lead = g->rank0 + i == 0;
         std::memset(&ctx->stats, 0, sizeof(ctx->stats));
         int32_t rc = MI_OK;
-        if (host) rc = mi_reserve(ctx, ctx->ws[16], pk->nb_wires * sizeof(mi_fr) + (lead && !use_sh ? 3 * cb : 0) + 128);
-        if (rc == MI_OK && !use_sh) rc = mi_reserve(ctx, ctx->ws[14], (lead ? N : pk->n_z_msm + 1) * sizeof(Fr));
+        if (host) rc = mi_reserve(ctx, ctx->ws[WS_PROVE_IN], pk->nb_wires * sizeof(mi_fr) + (lead && !use_sh ? 3 * cb : 0) + 128);
+        if (rc == MI_OK && !use_sh) rc = mi_reserve(ctx, ctx->ws[WS_H], (lead ? N : pk->n_z_msm + 1) * sizeof(Fr));
         note(rc, mi_last_error(ctx));
     }
     // every local rank: its slice of W, its wire MSMs; the lead also a, b, c, computeH and its own Z MSM.  One host thread per rank:
@@ -1356,7 +1356,7 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
         hipEvent_t *ev = ctx->ev;
         const bool lead = g->rank0 + i == 0;
         const size_t wb = pk->nb_wires * sizeof(mi_fr);
-        const mi_fr *Wd = host ? (const mi_fr *)ctx->ws[16].p : W_dev[i];
+        const mi_fr *Wd = host ? (const mi_fr *)ctx->ws[WS_PROVE_IN].p : W_dev[i];
         if (!Wd && wb) MI_FAIL(ctx, MI_EINVAL, "prove: null wire slice");
         // host inputs: pageable copies on the context's copy stream (which carries nothing else), ordered by synchronising it on this
         // thread -- no event between two of them (prove.hip, pool.hip: a marker slows every copy behind it)
@@ -1385,7 +1385,7 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
         // lead: a, b, c arrive while the wire MSMs run; computeH; its own slice of h feeds its Z MSM straight away
         const mi_fr *da = a, *db = b, *dc = c;
         if (host) {
-            char *base = (char *)ctx->ws[16].p;
+            char *base = (char *)ctx->ws[WS_PROVE_IN].p;
             da = (mi_fr *)(base + wb); db = (mi_fr *)(base + wb + cb); dc = c ? (mi_fr *)(base + wb + 2 * cb) : nullptr;
             if (cb) {
                 MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)da, a, cb, hipMemcpyHostToDevice, cps));
@@ -1396,7 +1396,7 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
             ctx->stats.h2d_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
         }
         MI_CHECK_HIP(ctx, hipEventRecord(ev[11], ctx->stream));
-        Fr *h = (Fr *)ctx->ws[14].p;
+        Fr *h = (Fr *)ctx->ws[WS_H].p;
         MI_TRY(mi_compute_h_dev_impl(ctx, pk->log_n, da, db, dc, n_constraints, (mi_fr *)h));
         MI_CHECK_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
         return mi_prove_enqueue_z_msm(ctx, pk, (const mi_fr *)(h + pk->z_lo), ev[3], defer);
@@ -1432,8 +1432,8 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
             u64 zlo, zhi;
             range_of(N - 1, W, j, zlo, zhi);
             Xfer x{0, j, nullptr, nullptr, (size_t)(zhi - zlo) * sizeof(Fr)};
-            if (g->local(0)) x.sp = (const char *)g->ctx[0 - g->rank0]->ws[14].p + zlo * sizeof(Fr);
-            if (g->local(j)) x.dp = g->ctx[j - g->rank0]->ws[14].p;
+            if (g->local(0)) x.sp = (const char *)g->ctx[0 - g->rank0]->ws[WS_H].p + zlo * sizeof(Fr);
+            if (g->local(j)) x.dp = g->ctx[j - g->rank0]->ws[WS_H].p;
             list.push_back(x);
         }
         if (lead_here) {
@@ -1449,7 +1449,7 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
                 if (g->rank0 + i == 0) return MI_OK;
                 mi_ctx *ctx = g->ctx[i];
                 MI_CHECK_HIP(ctx, hipEventRecord(g->ev_h[i], g->xs[i]));
-                return mi_prove_enqueue_z_msm(ctx, spk->part[i], (const mi_fr *)ctx->ws[14].p, g->ev_h[i], defer);
+                return mi_prove_enqueue_z_msm(ctx, spk->part[i], (const mi_fr *)ctx->ws[WS_H].p, g->ev_h[i], defer);
             }), e);
         }
     }

@@ -15,6 +15,7 @@
 // figure reported for it is the algorithmic 96 B (160 B) per pair of SURVEY 8d over its duration.
 #include "ctx.h"
 #include "msm2_core.cuh"
+#include "scan_u32.cuh"
 #include "msm_curve_ops.h"
 #include <cstring>
 #include <cstdlib>
@@ -248,82 +249,7 @@ __global__ void __launch_bounds__(1024) k_msm2_scatter2_staged(Msm2Shape s, cons
     msm2_stage2_copy(cursor, loc, st_lo, st_val, e - b, sorted, threadIdx.x, blockDim.x);
 }
 
-// ---------------------------------------------------------------- exclusive scan of u32 (out has m+1 entries, out[m] = total)
-// Every kernel of this family is a grid of SINGLE-WAVE workgroups (64 threads, scans by wave shuffles, no LDS, no barrier).  These launches
-// sit between the heavy kernels of an MSM's chain, and beside them run the level-1 accumulations of the other MSMs, whose one-wave
-// workgroups keep every SIMD's register file full: a four-wave workgroup needs a free slot on all four SIMDs of one CU at the same
-// moment (rocprofv3: k_scan_block_sums 3.7 ms inside a proof, 12 us alone), one wave takes any slot.  Measured on the job and on the
-// single proof: no difference either way (the freed slots go to the accumulations' next workgroups first); kept for the simpler kernels.
-static constexpr u32 SCAN_PER_THREAD = 16, SCAN_THREADS = 64, SCAN_BLOCK = SCAN_PER_THREAD * SCAN_THREADS;
-static constexpr u32 SCAN_MAX_INLINE_BLOCKS = 8 * SCAN_THREADS;   // mode 2 of k_scan_final: every workgroup scans the block sums itself, eight per lane
-__device__ __forceinline__ u32 wave_inclusive_scan(u32 v) {
-    for (int off = 1; off < 64; off <<= 1) { const u32 o = (u32)__shfl_up((int)v, off); if ((int)(threadIdx.x & 63) >= off) v += o; }
-    return v;
-}
-__device__ __forceinline__ u32 wave_exclusive_scan(u32 v, u32 *total) {
-    const u32 incl = wave_inclusive_scan(v);
-    *total = (u32)__shfl((int)incl, 63);
-    return incl - v;
-}
-__global__ void __launch_bounds__(64) k_scan_block_sums(const u32 *in, size_t m, u32 *block_sums) {
-    size_t base = (size_t)blockIdx.x * SCAN_BLOCK + (size_t)threadIdx.x * SCAN_PER_THREAD;
-    u32 s = 0;
-    for (u32 k = 0; k < SCAN_PER_THREAD; k++) if (base + k < m) s += in[base + k];
-    u32 total;
-    wave_exclusive_scan(s, &total);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-__global__ void __launch_bounds__(64) k_scan_of_sums(u32 *block_sums, u32 nblocks) {  // single workgroup, in place; eight sums per lane per trip
-    u32 carry = 0;
-    for (u32 base = 0; base < nblocks; base += 8 * 64) {
-        const u32 i0 = base + threadIdx.x * 8;
-        u32 v[8], mine = 0;
-        for (u32 k = 0; k < 8; k++) { v[k] = i0 + k < nblocks ? block_sums[i0 + k] : 0; mine += v[k]; }
-        u32 total;
-        u32 ex = carry + wave_exclusive_scan(mine, &total);
-        for (u32 k = 0; k < 8; k++) { if (i0 + k < nblocks) block_sums[i0 + k] = ex; ex += v[k]; }
-        carry += total;
-    }
-    if (threadIdx.x == 0) block_sums[nblocks] = carry;
-}
-// mode 0: block_sums holds the exclusive scan of the block sums (+ the total at [gridDim.x]) -- after k_scan_of_sums
-// mode 1: a single block: no block sums at all
-// mode 2: block_sums holds the raw sums of <= SCAN_MAX_INLINE_BLOCKS blocks: every workgroup scans them itself (saves the k_scan_of_sums launch)
-// The block that writes out[m] can also leave words in PINNED HOST memory (device-visible: hipHostMalloc) for the enqueueing thread: the
-// total (total_host) and one more word (copy_src -> copy_host: the sort's fullest bucket).  A hipMemcpyAsync of four bytes is a blit KERNEL
-// (__amd_rocclr_copyBuffer: 22 per proof, ~60 us each inside the job, every one on an MSM's chain); a store from a kernel that runs anyway is not.
-__global__ void __launch_bounds__(64) k_scan_final(const u32 *in, size_t m, const u32 *block_sums, u32 *out, int mode,
-                                                   u32 *total_host = nullptr, const u32 *copy_src = nullptr, u32 *copy_host = nullptr) {
-    u32 offset = 0, grand = 0;
-    if (mode == 0) { offset = block_sums[blockIdx.x]; grand = block_sums[gridDim.x]; }
-    if (mode == 2) {   // lane t holds the sums of blocks 8 t .. 8 t + 7; this block's offset = sums of the blocks before it
-        const u32 i0 = threadIdx.x * 8;
-        u32 mine = 0, before_in_lane = 0;
-        for (u32 k = 0; k < 8; k++) {
-            const u32 v = i0 + k < gridDim.x ? block_sums[i0 + k] : 0;
-            if (i0 + k < blockIdx.x) before_in_lane += v;
-            mine += v;
-        }
-        const u32 ex = wave_exclusive_scan(mine, &grand);
-        const u32 owner = blockIdx.x >> 3;   // the lane that holds this block's sum
-        offset = (u32)__shfl((int)(ex + before_in_lane), (int)owner);
-    }
-    size_t base = (size_t)blockIdx.x * SCAN_BLOCK + (size_t)threadIdx.x * SCAN_PER_THREAD;
-    u32 v[SCAN_PER_THREAD], s = 0;
-    for (u32 k = 0; k < SCAN_PER_THREAD; k++) { v[k] = base + k < m ? in[base + k] : 0; s += v[k]; }
-    u32 total;
-    u32 ex = wave_exclusive_scan(s, &total) + offset;
-    for (u32 k = 0; k < SCAN_PER_THREAD; k++) {
-        if (base + k < m) out[base + k] = ex;
-        ex += v[k];
-    }
-    if (mode == 1) grand = total;
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        out[m] = grand;
-        if (total_host) *total_host = grand;
-        if (copy_host) *copy_host = *copy_src;
-    }
-}
+// (the exclusive scan of u32 these kernels feed and finish lives in scan_u32.cuh)
 // The chunk counts of the groups (msm2_chunk_count_body) and the scan of them as ONE single-wave launch (ngroups <= 4096: lane t takes the groups [t*per, (t+1)*per)):
 // gstart, nchunks, cstart = exclusive scan of nchunks (+ the total at [ngroups]).  Also zeroes the two things kernels further down this
 // stream add into: the fullest-bucket word (k_msm2_colsum's atomicMax) and the `nzero` block sums of the key scan (k_msm2_colsum's atomicAdd).
@@ -392,27 +318,6 @@ __global__ void __launch_bounds__(64) k_msm_finish_list(u32 nkeys, const u32 *it
     if (small) list_small[base_s + (u32)__popcll(ms & below)] = key;
     if (big) list_big[base_b + (u32)__popcll(mb & below)] = key;
 }
-// total_host / copy_src -> copy_host: words the last kernel also leaves in pinned host memory (k_scan_final), or null
-static int32_t exclusive_scan(mi_ctx *ctx, hipStream_t st, const u32 *in, size_t m, u32 *out, DevBuf &tmp,
-                              u32 *total_host = nullptr, const u32 *copy_src = nullptr, u32 *copy_host = nullptr) {
-    u32 nblocks = (u32)((m + SCAN_BLOCK - 1) / SCAN_BLOCK);
-    if (nblocks == 0) nblocks = 1;
-    MI_TRY(mi_reserve(ctx, tmp, (size_t)(nblocks + 1) * 4));
-    u32 *bs = (u32 *)tmp.p;
-    if (nblocks == 1) {
-        hipLaunchKernelGGL(k_scan_final, dim3(1), dim3(SCAN_THREADS), 0, st, in, m, bs, out, 1, total_host, copy_src, copy_host);
-    } else if (nblocks <= SCAN_MAX_INLINE_BLOCKS) {
-        hipLaunchKernelGGL(k_scan_block_sums, dim3(nblocks), dim3(SCAN_THREADS), 0, st, in, m, bs);
-        hipLaunchKernelGGL(k_scan_final, dim3(nblocks), dim3(SCAN_THREADS), 0, st, in, m, bs, out, 2, total_host, copy_src, copy_host);
-    } else {
-        hipLaunchKernelGGL(k_scan_block_sums, dim3(nblocks), dim3(SCAN_THREADS), 0, st, in, m, bs);
-        hipLaunchKernelGGL(k_scan_of_sums, dim3(1), dim3(SCAN_THREADS), 0, st, bs, nblocks);
-        hipLaunchKernelGGL(k_scan_final, dim3(nblocks), dim3(SCAN_THREADS), 0, st, in, m, bs, out, 0, total_host, copy_src, copy_host);
-    }
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    return MI_OK;
-}
-
 // ---------------------------------------------------------------- orchestration
 // An MSM is enqueued asynchronously on the stream of a *slot* (ctx->msm[i]): sort stage, accumulate
 // stage, async copy of the <= 128 window sums into pinned host memory.  Nothing blocks the host until
@@ -1073,10 +978,10 @@ static int32_t msm_dev_entry(mi_ctx *ctx, int curve, const void *pts_dev, const 
     uint32_t rp = 0;
     if (n >= ((size_t)1 << (curve == 1 ? 16 : 14)) && !knobs_of(ctx)->no_rprime) {
         const MsmCurveOps &o = curve == 1 ? msm_g1_ops() : msm_g2_ops();
-        MI_TRY(mi_reserve(ctx, ctx->ws[23], n * (curve == 1 ? 64 : 128) + 64));
-        o.to_rprime(ctx->stream, ctx->ws[23].p, pts_dev, n);
+        MI_TRY(mi_reserve(ctx, ctx->ws[WS_RPRIME], n * (curve == 1 ? 64 : 128) + 64));
+        o.to_rprime(ctx->stream, ctx->ws[WS_RPRIME].p, pts_dev, n);
         MI_CHECK_HIP(ctx, hipGetLastError());
-        pts_dev = ctx->ws[23].p;
+        pts_dev = ctx->ws[WS_RPRIME].p;
         rp = MI_MSM_PTS_RPRIME;
     }
     MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
@@ -1091,13 +996,13 @@ static int32_t msm_dev_entry(mi_ctx *ctx, int curve, const void *pts_dev, const 
 template <class F, class AffT, class JacT>
 static int32_t msm_host_entry(mi_ctx *ctx, int curve, const AffT *pts, const mi_fr *scalars, size_t n, uint32_t flags, JacT *out) {
     if (!ctx || !out || ((!pts || !scalars) && n) || (flags & ~1u)) return MI_EINVAL;
-    MI_TRY(mi_reserve(ctx, ctx->ws[2], n * sizeof(AffT) + 64));
-    MI_TRY(mi_reserve(ctx, ctx->ws[3], n * sizeof(mi_fr) + 64));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_HOST_IO0], n * sizeof(AffT) + 64));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_HOST_IO1], n * sizeof(mi_fr) + 64));
     if (n) {
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[2].p, pts, n * sizeof(AffT), hipMemcpyHostToDevice, ctx->stream));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[3].p, scalars, n * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[WS_HOST_IO0].p, pts, n * sizeof(AffT), hipMemcpyHostToDevice, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[WS_HOST_IO1].p, scalars, n * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->stream));
     }
-    return msm_dev_entry<F>(ctx, curve, ctx->ws[2].p, ctx->ws[3].p, n, flags, out);
+    return msm_dev_entry<F>(ctx, curve, ctx->ws[WS_HOST_IO0].p, ctx->ws[WS_HOST_IO1].p, n, flags, out);
 }
 
 template <class F, class JacT>

@@ -412,18 +412,6 @@ __global__ void k_sc_layout(Fr *out, u32 log_n, Fr base, Fr c) {     // out[i] =
     out[i] = acc;
 }
 
-static Fr host_fr_from_u64x4(u64 a, u64 b, u64 c, u64 d) {
-    Fr t;
-    t.l[0] = (u32)a; t.l[1] = (u32)(a >> 32); t.l[2] = (u32)b; t.l[3] = (u32)(b >> 32);
-    t.l[4] = (u32)c; t.l[5] = (u32)(c >> 32); t.l[6] = (u32)d; t.l[7] = (u32)(d >> 32);
-    return fe_to_mont(t);
-}
-static Fr domain_generator(u32 log_n) {  // fft.NewDomain: Generator = root^(2^(28-log_n))
-    Fr g = host_fr_from_u64x4(0x9bd61b6e725b19f0ull, 0x402d111e41112ed4ull, 0x00e0a7eb8ef62abcull, 0x2a3c09f0a58a7e85ull);
-    for (u32 k = log_n; k < 28; k++) g = fe_sqr(g);
-    return g;
-}
-
 static int32_t build_table(mi_ctx *ctx, Fr **slot, u32 count, const Fr &base, const Fr &c, u32 shift) {
     if (*slot) { MI_CHECK_HIP(ctx, hipFree(*slot)); *slot = nullptr; }
     MI_CHECK_HIP(ctx, hipMalloc((void **)slot, sizeof(Fr) * (count ? count : 1)));
@@ -435,15 +423,15 @@ static int32_t build_table(mi_ctx *ctx, Fr **slot, u32 count, const Fr &base, co
 static int32_t ensure_tables(mi_ctx *ctx, u32 log_n) {
     NttState *st = state_of(ctx);
     if (!st->small_f) {
-        Fr w4096 = domain_generator(12);
+        Fr w4096 = fr_domain_generator(12);
         MI_TRY(build_table(ctx, &st->small_f, 2048, w4096, Fr::one(), 0));
         MI_TRY(build_table(ctx, &st->small_i, 2048, fe_inv(w4096), Fr::one(), 0));
-        Fr w64k = domain_generator(16);
+        Fr w64k = fr_domain_generator(16);
         MI_TRY(build_table(ctx, &st->tw64k_f, 65536, w64k, Fr::one(), 0));
         MI_TRY(build_table(ctx, &st->tw64k_i, 65536, fe_inv(w64k), Fr::one(), 0));
     }
     if (st->log_n == log_n) return MI_OK;
-    Fr w = domain_generator(log_n), wi = fe_inv(w);
+    Fr w = fr_domain_generator(log_n), wi = fe_inv(w);
     Fr g = fe_from_u32<FrParams>(5), gi = fe_inv(g);
     Fr nn = Fr::zero();
     nn.l[0] = (u32)(1u << log_n);  // log_n <= 28
@@ -490,7 +478,7 @@ static int32_t ensure_direct(mi_ctx *ctx, u32 log_n) {
             for (Fr **q : four) if (*q) { (void)hipFree(*q); *q = nullptr; }
             return MI_OK;
         }
-    const Fr w = domain_generator(log_n), wi = fe_inv(w), g = fe_from_u32<FrParams>(5), gi = fe_inv(g);
+    const Fr w = fr_domain_generator(log_n), wi = fe_inv(w), g = fe_from_u32<FrParams>(5), gi = fe_inv(g);
     Fr nn = Fr::zero();
     nn.l[0] = (u32)(1u << log_n);
     const Fr ninv = fe_inv(fe_to_mont(nn));
@@ -597,8 +585,8 @@ int32_t mi_ntt_dev_impl(mi_ctx *ctx, mi_fr *inout_dev, uint32_t log_n, uint32_t 
 // computeH in four parts on ctx->stream, so that a caller whose inputs arrive one vector at a time (the host-pointer prove: a, b, c cross
 // PCIe one after the other) can start a's transforms while b is still on the bus:
 //   part 0 (src = a), part 1 (src = b)   N FFTInverse(., DIF) and the coset FFT up to (not including) its last pass when that pass runs in
-//                                        the strided triple, else all of it; a lives in h_out, b in ws[0]
-//   part 2 (src = c)                     den FFTInverse(c, DIF) into ws[1]; src2 != null: c is not given and is formed as src o src2 (the ORIGINAL a and b,
+//                                        the strided triple, else all of it; a lives in h_out, b in ws[WS_H_B]
+//   part 2 (src = c)                     den FFTInverse(c, DIF) into ws[WS_H_C]; src2 != null: c is not given and is formed as src o src2 (the ORIGINAL a and b,
 //                                        row by row) on the way into the first pass -- what c is for every witness gnark's solver accepts
 //   part 3                               the strided triple (or the coset FFTs' last passes) and the last transform -> h_out
 // The same launches as the one-call form, in an order that differs only between independent vectors: identical h.
@@ -644,9 +632,9 @@ int32_t mi_compute_h_part(mi_ctx *ctx, uint32_t log_n, int part, const mi_fr *sr
     //     h = cosetFFTInverse((ca cb - cc) den) = den cosetFFTInverse(ca cb) - den FFTInverse(c),
     // so the coset FFT of c is never computed -- SIX transforms, the same field elements (exact arithmetic), for ANY a, b, c.
     MI_TRY(ensure_direct(ctx, log_n));
-    MI_TRY(mi_reserve(ctx, ctx->ws[0], n * sizeof(Fr)));
-    MI_TRY(mi_reserve(ctx, ctx->ws[1], n * sizeof(Fr)));
-    Fr *A = (Fr *)h_out, *B = (Fr *)ctx->ws[0].p, *C = (Fr *)ctx->ws[1].p;
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_H_B], n * sizeof(Fr)));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_H_C], n * sizeof(Fr)));
+    Fr *A = (Fr *)h_out, *B = (Fr *)ctx->ws[WS_H_B].p, *C = (Fr *)ctx->ws[WS_H_C].p;
     ComputeHPlan cp;
     MI_TRY(compute_h_plan(ctx, log_n, A, cp));
     const u32 first_skip = cp.pair ? 1u : 0u;
@@ -785,10 +773,10 @@ int32_t mi_ntt_dev(mi_ctx *ctx, mi_fr *inout_dev, uint32_t log_n, uint32_t flags
 int32_t mi_ntt(mi_ctx *ctx, mi_fr *inout, uint32_t log_n, uint32_t flags) {
     if (!ctx || !inout || log_n > 28 || (flags & ~7u)) return MI_EINVAL;
     size_t bytes = sizeof(Fr) << log_n;
-    MI_TRY(mi_reserve(ctx, ctx->ws[2], bytes));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[2].p, inout, bytes, hipMemcpyHostToDevice, ctx->stream));
-    MI_TRY(mi_ntt_dev(ctx, (mi_fr *)ctx->ws[2].p, log_n, flags));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(inout, ctx->ws[2].p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_HOST_IO0], bytes));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[WS_HOST_IO0].p, inout, bytes, hipMemcpyHostToDevice, ctx->stream));
+    MI_TRY(mi_ntt_dev(ctx, (mi_fr *)ctx->ws[WS_HOST_IO0].p, log_n, flags));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(inout, ctx->ws[WS_HOST_IO0].p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MI_OK;
 }
@@ -808,14 +796,14 @@ int32_t mi_compute_h(mi_ctx *ctx, uint32_t log_n, const mi_fr *a, const mi_fr *b
                      size_t n_constraints, mi_fr *h_out) {
     if (!ctx || !a || !b || !h_out || log_n > 28 || n_constraints > ((size_t)1 << log_n)) return MI_EINVAL;   // c may be null: c = a o b
     size_t nb = n_constraints * sizeof(Fr), full = sizeof(Fr) << log_n;
-    MI_TRY(mi_reserve(ctx, ctx->ws[2], full));
-    MI_TRY(mi_reserve(ctx, ctx->ws[3], nb * 3 + 96));
-    char *in = (char *)ctx->ws[3].p;
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_HOST_IO0], full));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_HOST_IO1], nb * 3 + 96));
+    char *in = (char *)ctx->ws[WS_HOST_IO1].p;
     MI_CHECK_HIP(ctx, hipMemcpyAsync(in, a, nb, hipMemcpyHostToDevice, ctx->stream));
     MI_CHECK_HIP(ctx, hipMemcpyAsync(in + nb, b, nb, hipMemcpyHostToDevice, ctx->stream));
     if (c) MI_CHECK_HIP(ctx, hipMemcpyAsync(in + 2 * nb, c, nb, hipMemcpyHostToDevice, ctx->stream));
-    MI_TRY(mi_compute_h_dev(ctx, log_n, (mi_fr *)in, (mi_fr *)(in + nb), c ? (mi_fr *)(in + 2 * nb) : nullptr, n_constraints, (mi_fr *)ctx->ws[2].p));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(h_out, ctx->ws[2].p, full, hipMemcpyDeviceToHost, ctx->stream));
+    MI_TRY(mi_compute_h_dev(ctx, log_n, (mi_fr *)in, (mi_fr *)(in + nb), c ? (mi_fr *)(in + 2 * nb) : nullptr, n_constraints, (mi_fr *)ctx->ws[WS_HOST_IO0].p));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(h_out, ctx->ws[WS_HOST_IO0].p, full, hipMemcpyDeviceToHost, ctx->stream));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MI_OK;
 }

@@ -135,14 +135,6 @@ static Fr host_pow(Fr b, u64 e) {
     while (e) { if (e & 1) acc = acc * b; b = fe_sqr(b); e >>= 1; }
     return acc;
 }
-static Fr cross_domain_generator(u32 log_n) {   // fft.NewDomain: Generator = root^(2^(28 - log_n)), as csrc/ntt.hip
-    Fr t;
-    const u64 lim[4] = {0x9bd61b6e725b19f0ull, 0x402d111e41112ed4ull, 0x00e0a7eb8ef62abcull, 0x2a3c09f0a58a7e85ull};
-    for (int i = 0; i < 4; i++) { t.l[2 * i] = (u32)lim[i]; t.l[2 * i + 1] = (u32)(lim[i] >> 32); }
-    Fr g = fe_to_mont(t);
-    for (u32 k = log_n; k < 28; k++) g = fe_sqr(g);
-    return g;
-}
 
 void mi_cross_tables_free(CrossNttTables *t) {
     for (void **p : {&t->tw_inv, &t->tw_fwd, &t->s_fwd, &t->s_inv}) if (*p) { (void)hipFree(*p); *p = nullptr; }
@@ -159,7 +151,7 @@ int32_t mi_cross_tables_build(mi_ctx *ctx, u32 log_n, u32 log_w, u32 rank, Cross
     MI_CHECK_HIP(ctx, hipMalloc(&t->tw_fwd, sizeof(Fr) * cnt));
     MI_CHECK_HIP(ctx, hipMalloc(&t->s_fwd, sizeof(Fr) * M));
     MI_CHECK_HIP(ctx, hipMalloc(&t->s_inv, sizeof(Fr) * M));
-    const Fr w = cross_domain_generator(log_n), wi = fe_inv(w), g = fe_from_u32<FrParams>(5), gi = fe_inv(g);
+    const Fr w = fr_domain_generator(log_n), wi = fe_inv(w), g = fe_from_u32<FrParams>(5), gi = fe_inv(g);
     Fr gn = g;
     for (u32 k = 0; k < log_n; k++) gn = fe_sqr(gn);
     const Fr den = fe_inv(gn - Fr::one());
@@ -181,7 +173,7 @@ int32_t mi_cross_tables_build(mi_ctx *ctx, u32 log_n, u32 log_w, u32 rank, Cross
 }
 static void cross_args(const CrossNttTables &t, int mode, bool den_scale, CrossArgs *a) {
     const u32 W = 1u << t.log_w;
-    const Fr ww = cross_domain_generator(t.log_w), base = mode == 0 ? fe_inv(ww) : ww;
+    const Fr ww = fr_domain_generator(t.log_w), base = mode == 0 ? fe_inv(ww) : ww;
     Fr p = Fr::one();
     for (u32 e = 0; e < 8; e++) { a->wp[e] = p; if (e + 1 < W / 2) p = p * base; }
     a->scale = mode == 0 ? (den_scale ? t.w_inv_scale * t.den : t.w_inv_scale) : Fr::one();

@@ -118,7 +118,7 @@ static void worker_main(mi_prover *p, mi_ctx *ctx) {
         std::string pok_err;
         for (size_t i = 0; i + 1 < nb && rc_pok == MI_OK; i++) rc_pok = mi_pedersen_prove_knowledge(ctx, j->bsb[i].key, j->bsb[i].values, j->bsb[i].n, &poks[i]);
         // (enqueued from a helper thread while this one enqueues the proof: the PoK's sort waits once on the host for its count pass, and
-        //  the values' pageable copy holds its thread -- neither should delay the proof's own kernels; slot 5 and ws[19] are the PoK's alone)
+        //  the values' pageable copy holds its thread -- neither should delay the proof's own kernels; slot 5 and ws[WS_POK_VALUES] are the PoK's alone)
         bool pok_pending = false;
         std::future<int32_t> f_pok;
         std::string pok_enq_err;   // the helper's own error sink (ctx.h mi_err_sink): it works on ctx while this thread proves on it

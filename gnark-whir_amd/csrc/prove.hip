@@ -235,11 +235,11 @@ static void pedersen_build_tables(mi_ctx *ctx, mi_pedersen_pk *pk) {
 static int32_t pedersen_enqueue(mi_ctx *ctx, const void *bases_dev, const void *tables_dev, u32 c_tab, size_t key_n, const mi_fr *values, size_t n) {
     if (!ctx || (!values && n)) return MI_EINVAL;
     if (n > key_n) MI_FAIL(ctx, MI_EINVAL, "pedersen: more values than basis points");   // gnark: "must have as many values as basis elements"
-    MI_TRY(mi_reserve(ctx, ctx->ws[19], n * sizeof(mi_fr) + 64));
-    if (n) MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[19].p, values, n * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->msm[5].stream));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_POK_VALUES], n * sizeof(mi_fr) + 64));
+    if (n) MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[WS_POK_VALUES].p, values, n * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->msm[5].stream));
     // the tables are laid out [window][key_n]: they serve exactly the full-length call (gnark's: as many values as basis elements)
-    if (tables_dev && n == key_n) return mi_msm_enqueue(ctx, 5, -1, 1, tables_dev, ctx->ws[19].p, n, MI_MSM_PTS_RPRIME, nullptr, false, c_tab);
-    return mi_msm_enqueue(ctx, 5, -1, 1, bases_dev, ctx->ws[19].p, n, 0, nullptr, false);
+    if (tables_dev && n == key_n) return mi_msm_enqueue(ctx, 5, -1, 1, tables_dev, ctx->ws[WS_POK_VALUES].p, n, MI_MSM_PTS_RPRIME, nullptr, false, c_tab);
+    return mi_msm_enqueue(ctx, 5, -1, 1, bases_dev, ctx->ws[WS_POK_VALUES].p, n, 0, nullptr, false);
 }
 static int32_t pedersen_collect(mi_ctx *ctx, mi_g1_affine *out) {
     G1X r;
@@ -331,9 +331,9 @@ int32_t mi_get_mem_ledger(mi_ctx *ctx, const mi_pk *pk, mi_mem_ledger *out) {
         out->key_indices = (pk->n_a + pk->n_b + pk->n_k) * 4;
     }
     out->ctx_ntt_tables = mi_ntt_table_bytes(ctx);
-    for (int i = 0; i < 24; i++) {
+    for (int i = 0; i < WS_COUNT; i++) {
         const size_t cap = ctx->ws[i].cap;
-        if (i == 0 || i == 1 || i == 14) out->ctx_ntt_vectors += cap; else out->ctx_other += cap;
+        if (i == WS_H_B || i == WS_H_C || i == WS_H) out->ctx_ntt_vectors += cap; else out->ctx_other += cap;
     }
     for (const auto &sl : ctx->msm) for (const auto &b : sl.buf) out->ctx_msm += b.cap;
     return MI_OK;
@@ -373,21 +373,21 @@ int32_t mi_prove_enqueue_b_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, hipEvent
     const uint32_t df = (defer ? MI_MSM_DEFER_REDUCE : 0) | MI_MSM_EXACT_SIZE;
     const uint32_t rp = pk->rprime ? MI_MSM_PTS_RPRIME : 0;
     // wireValuesB by the static gather indices, on its MSM's stream; B2 (G2) shares B1's sort (same scalars)
-    MI_TRY(mi_reserve(ctx, ctx->ws[17], (pk->n_b + 1) * sizeof(Fr)));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_B_WIRES], (pk->n_b + 1) * sizeof(Fr)));
     hipStream_t st = ctx->msm[1].stream;
     if (ev_w) MI_CHECK_HIP(ctx, hipStreamWaitEvent(st, ev_w, 0));
-    if (pk->n_b) hipLaunchKernelGGL(k_gather_fr, dim3((unsigned)((pk->n_b + 255) / 256)), dim3(256), 0, st, (Fr *)ctx->ws[17].p, (const Fr *)W, pk->idx_b, pk->n_b);
+    if (pk->n_b) hipLaunchKernelGGL(k_gather_fr, dim3((unsigned)((pk->n_b + 255) / 256)), dim3(256), 0, st, (Fr *)ctx->ws[WS_B_WIRES].p, (const Fr *)W, pk->idx_b, pk->n_b);
     MI_CHECK_HIP(ctx, hipGetLastError());
     if (pk->pre_b1) {
         gates.arm(1);
         // (B1 and K are not timed: their chains interleave on one stream, so the event pair around one's level-1 launch may bracket kernels
         //  of the other; mi_stats.g1_accum_* then cover A and Z, the two launches with a stream of their own)
-        MI_TRY(mi_msm_enqueue(ctx, 1, -1, 1, pk->pre_b1, ctx->ws[17].p, pk->n_b, df | rp, nullptr, false, pk->c_b));
+        MI_TRY(mi_msm_enqueue(ctx, 1, -1, 1, pk->pre_b1, ctx->ws[WS_B_WIRES].p, pk->n_b, df | rp, nullptr, false, pk->c_b));
         gates.arm(2);
         return mi_msm_enqueue(ctx, 2, 1, 2, pk->pre_b2, nullptr, pk->n_b, df | rp, nullptr, false, pk->c_b);
     }
     gates.arm(1);
-    MI_TRY(mi_msm_enqueue(ctx, 1, -1, 1, pk->g1_b, ctx->ws[17].p, pk->n_b, df | rp, nullptr, false, 0, 0, pk->gen_c_b));
+    MI_TRY(mi_msm_enqueue(ctx, 1, -1, 1, pk->g1_b, ctx->ws[WS_B_WIRES].p, pk->n_b, df | rp, nullptr, false, 0, 0, pk->gen_c_b));
     gates.arm(2);
     return mi_msm_enqueue(ctx, 2, 1, 2, pk->g2_b, nullptr, pk->n_b, df | rp, nullptr, false);
 }
@@ -509,8 +509,8 @@ static int32_t prove_common(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wir
     // Stream plan: computeH on the caller's stream; MSM A, B1, B2, K, Z on slots 0..4 (own streams).  A, B and
     // K depend only on W and start at once; B2 (G2) reuses B1's sort; Z waits for h.  The latency-bound tails
     // (levels >= 2, bucket reduce, scans) of one MSM overlap the throughput-bound accumulation of the others.
-    MI_TRY(mi_reserve(ctx, ctx->ws[14], N * sizeof(Fr)));
-    Fr *h = (Fr *)ctx->ws[14].p;
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_H], N * sizeof(Fr)));
+    Fr *h = (Fr *)ctx->ws[WS_H].p;
     // step 4: h = computeH(a, b, c)  (bit-reversed, like gnark leaves it), then the Z MSM over h[:N-1] against the bit-reversed pk.G1.Z
     // "computeH is enqueued and its end event recorded": what the wire MSMs' accumulations wait for (hold, below).  Always fulfilled
     // before the helper threads are joined -- with a null event on a failure path, which releases them without a wait.
@@ -742,10 +742,10 @@ int32_t mi_groth16_prove_w(mi_ctx *ctx, mi_pk *pk, const mi_r1cs *r1cs, const mi
                            const mi_fr *r, const mi_fr *s, mi_proof_out *out, mi_stats *stats) {
     if (!ctx || !pk || !r || !s || !out) return MI_EINVAL;
     MI_TRY(check_w_inputs(ctx, pk, r1cs, W, n_wires, flags));
-    MI_TRY(mi_reserve(ctx, ctx->ws[16], n_wires * 32 + 128));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_PROVE_IN], n_wires * 32 + 128));
     const HostInputs host{W, nullptr, nullptr, nullptr};
     const WEval we{r1cs, (flags & MI_PROVE_W_EVAL_C) != 0};
-    return prove_common(ctx, pk, (mi_fr *)ctx->ws[16].p, n_wires, nullptr, nullptr, nullptr, 0, r, s, out, stats, &host, nullptr, &we);
+    return prove_common(ctx, pk, (mi_fr *)ctx->ws[WS_PROVE_IN].p, n_wires, nullptr, nullptr, nullptr, 0, r, s, out, stats, &host, nullptr, &we);
 }
 int32_t mi_groth16_prove_dev(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wires, const mi_fr *a, const mi_fr *b, const mi_fr *c,
                              size_t n_constraints, const mi_fr *r, const mi_fr *s, mi_proof_out *out, mi_stats *stats) {
@@ -755,8 +755,8 @@ int32_t mi_groth16_prove(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wires,
                          size_t n_constraints, const mi_fr *r, const mi_fr *s, mi_proof_out *out, mi_stats *stats) {
     if (!ctx || !pk || !r || !s || !out) return MI_EINVAL;   // W, a, b: checked against their counts in prove_common; c == null: c = a o b
     const size_t wb = n_wires * 32, cb = n_constraints * 32;
-    MI_TRY(mi_reserve(ctx, ctx->ws[16], wb + 3 * cb + 128));
-    char *base = (char *)ctx->ws[16].p;
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_PROVE_IN], wb + 3 * cb + 128));
+    char *base = (char *)ctx->ws[WS_PROVE_IN].p;
     const HostInputs host{W, a, b, c};
     return prove_common(ctx, pk, (mi_fr *)base, n_wires, (mi_fr *)(base + wb), (mi_fr *)(base + wb + cb), (mi_fr *)(base + wb + 2 * cb),
                         n_constraints, r, s, out, stats, &host);

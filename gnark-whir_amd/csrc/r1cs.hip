@@ -8,12 +8,9 @@
 //          bits of the entry's wire word (wires are below 2^27), so that an entry with coefficient +-1 adds or subtracts W[wire] without
 //          a multiplication and without touching the table, and one with coefficient 0 is skipped: those are the bulk of a real gnark
 //          table; and the row-length plan below
-//   sum    the split Setup's column sum uses (setup.hip step 2 "sum", constants in sparse_fr.cuh), by row instead of by column and
-//          planned on the host at load time instead of on the device per call: row lengths are as skewed as column lengths are -- most
-//          rows hold one to four entries, a few linear combinations thousands.  A row of at most SPARSE_SHORT entries goes to one lane,
-//          64 rows packed in a wave (k_rows_short).  A longer row is cut into pieces of SPARSE_CHUNK entries; a wave sums one piece with
-//          its lanes striding over it and a butterfly of field additions (k_row_pieces), and a last pass adds a row's partials the same
-//          way (k_row_combine).  Field addition is exact and commutative: every order gives the same bits.
+//   sum    the split sum of sparse_fr.cuh, by row: row lengths are as skewed as Setup's column lengths -- most rows hold one to four
+//          entries, a few linear combinations thousands.  Planned on the host at load time (sparse_cut), not per call: short rows
+//          by k_rows_short, the pieces of the long ones by k_row_pieces, their partials by k_row_combine.
 // The matrices one call asks for (A and B on the prove path) share each launch (blockIdx.y picks the matrix): three launches per call
 // on the context's stream.  The partials live in context workspace (mi_reserve: grow-only, freed by mi_ctx_trim); nothing is allocated
 // in steady state.  The handle is read-only after load and shared by every context of its device.
@@ -31,15 +28,11 @@ namespace {
 constexpr u32 CLS_SHIFT = 30, COL_MASK = (1u << CLS_SHIFT) - 1;   // MI_MSM_MAX_PAIRS = 2^27 wires at most: bits 30, 31 are spare
 enum : u32 { CLS_ANY = 0, CLS_ONE = 1, CLS_MINUS_ONE = 2, CLS_ZERO = 3 };
 static_assert(MI_MSM_MAX_PAIRS <= (1ull << CLS_SHIFT), "the class bits need the top of the wire word");
-// workspaces of the context (ctx.h ws[]): the three outputs of an evaluation into workspace, partials of the long rows, the
-// check's counters, W of the host entry point
-enum { WS_A = 6, WS_B = 7, WS_C = 8, WS_PARTIAL = 9, WS_COUNTERS = 10, WS_W = 11 };
-enum { EV_BEGIN = 12, EV_END = 13 };   // ctx->ev[]: around the launches of the last evaluation
 
 struct MatArg {
     const u32 *row_off;
     const uint2 *entries;
-    const uint4 *long_rows;
+    const SparseLong *long_rows;
     const uint2 *pieces;
     Fr *out;        // n_constraints rows; the check: one value per LONG row, in long_rows' order
     Fr *partial;    // one per piece
@@ -47,71 +40,54 @@ struct MatArg {
 };
 struct EvalArgs { MatArg m[3]; };
 
-MI_D void add_entry(Fr &acc, const uint2 en, const Fr *W, const Fr *coeffs) {
-    const u32 cls = en.x >> CLS_SHIFT;
-    if (cls == CLS_ZERO) return;
-    const Fr w = ld_fr(W + (en.x & COL_MASK));
-    if (cls == CLS_ONE) acc = acc + w;
-    else if (cls == CLS_MINUS_ONE) acc = acc - w;
-    else acc = acc + ld_fr(coeffs + en.y) * w;
-}
-MI_D Fr sum_short_row(const uint2 *entries, u32 lo, u32 len, const Fr *W, const Fr *coeffs) {
-    Fr acc = Fr::zero();
-    for (u32 e = lo; e < lo + len; e++) add_entry(acc, entries[e], W, coeffs);
-    return acc;
-}
+// the term of an entry (wire | class << 30, coefficient): nothing, +-W[wire] without a product, or coeffs[coefficient] * W[wire]
+struct RowTerm {
+    const Fr *W, *coeffs;
+    MI_D void operator()(Fr &acc, const uint2 en) const {
+        const u32 cls = en.x >> CLS_SHIFT;
+        if (cls == CLS_ZERO) return;
+        const Fr w = ld_fr(W + (en.x & COL_MASK));
+        if (cls == CLS_ONE) acc = acc + w;
+        else if (cls == CLS_MINUS_ONE) acc = acc - w;
+        else acc = acc + ld_fr(coeffs + en.y) * w;
+    }
+};
 
-// one lane per row, 64 rows in a wave; blockIdx.y = the matrix
-__global__ void __launch_bounds__(256) k_rows_short(EvalArgs args, u64 nc, const Fr *W, const Fr *coeffs) {
+// the wrappers of sparse_fr.cuh's bodies; blockIdx.y = the matrix.  One lane per row, 64 rows in a wave:
+__global__ void __launch_bounds__(256) k_rows_short(EvalArgs args, u64 nc, RowTerm term) {
     const u64 row = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= nc) return;
     const MatArg &m = args.m[blockIdx.y];
     const u32 lo = m.row_off[row], len = m.row_off[row + 1] - lo;
     if (len > SPARSE_SHORT) return;   // k_row_combine writes it
-    st_fr(m.out + row, sum_short_row(m.entries, lo, len, W, coeffs));
+    st_fr(m.out + row, sparse_sum_short(m.entries, lo, len, term));
 }
-// a wave per piece (grid-stride): partial[piece] = the sum of its entries
-__global__ void __launch_bounds__(256) k_row_pieces(EvalArgs args, const Fr *W, const Fr *coeffs) {
+__global__ void __launch_bounds__(256) k_row_pieces(EvalArgs args, RowTerm term) {
     const MatArg &m = args.m[blockIdx.y];
-    const u32 lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    for (u32 it = wave; it < m.n_pieces; it += n_waves) {
-        const uint2 pc = m.pieces[it];
-        Fr acc = Fr::zero();
-        for (u32 k = lane; k < pc.y; k += 64) add_entry(acc, m.entries[pc.x + k], W, coeffs);
-        acc = wave_sum(acc);
-        if (lane == 0) st_fr(m.partial + it, acc);
-    }
+    sparse_sum_pieces(m.partial, m.pieces, m.n_pieces, m.entries, term);
 }
-// a wave per long row (grid-stride): the sum of its partials, to the row's slot (compact: to the long row's own index)
+// compact (the check): a long row's sum goes to out[its place among the long rows], not to out[row]
 __global__ void __launch_bounds__(256) k_row_combine(EvalArgs args, bool compact) {
     const MatArg &m = args.m[blockIdx.y];
-    const u32 lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    for (u32 it = wave; it < m.n_long; it += n_waves) {
-        const uint4 lr = m.long_rows[it];   // (row, first piece, pieces, 0)
-        Fr acc = Fr::zero();
-        for (u32 k = lane; k < lr.z; k += 64) acc = acc + ld_fr(m.partial + lr.y + k);
-        acc = wave_sum(acc);
-        if (lane == 0) st_fr(m.out + (compact ? it : lr.x), acc);
-    }
+    sparse_combine(m.out, m.long_rows, m.n_long, m.partial, compact);
 }
 // (M W)[row] inside the check: a short row is summed here, a long one was summed by the two kernels above into out[its index]
-MI_D Fr row_value(const MatArg &m, u32 row, const Fr *W, const Fr *coeffs) {
+MI_D Fr row_value(const MatArg &m, u32 row, const RowTerm &term) {
     const u32 lo = m.row_off[row], len = m.row_off[row + 1] - lo;
-    if (len <= SPARSE_SHORT) return sum_short_row(m.entries, lo, len, W, coeffs);
+    if (len <= SPARSE_SHORT) return sparse_sum_short(m.entries, lo, len, term);
     u32 a = 0, b = m.n_long;   // long_rows is ascending by row and holds this one
     while (b - a > 1) {
         const u32 mid = a + (b - a) / 2;
-        if (m.long_rows[mid].x <= row) a = mid; else b = mid;
+        if (m.long_rows[mid].index <= row) a = mid; else b = mid;
     }
     return ld_fr(m.out + a);
 }
 // ctr[0] = rows with (A W)(B W) != C W, ctr[1] = the lowest of them: a wave counts its rows with a ballot, one lane adds
-__global__ void __launch_bounds__(256) k_check(EvalArgs args, u64 nc, const Fr *W, const Fr *coeffs, unsigned long long *ctr) {
+__global__ void __launch_bounds__(256) k_check(EvalArgs args, u64 nc, RowTerm term, unsigned long long *ctr) {
     const u64 row = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     bool bad = false;
     if (row < nc) {
-        const Fr a = row_value(args.m[0], (u32)row, W, coeffs), b = row_value(args.m[1], (u32)row, W, coeffs);
-        const Fr c = row_value(args.m[2], (u32)row, W, coeffs);
+        const Fr a = row_value(args.m[0], (u32)row, term), b = row_value(args.m[1], (u32)row, term), c = row_value(args.m[2], (u32)row, term);
         bad = !(a * b == c);
     }
     const u64 mask = __ballot(bad);
@@ -120,8 +96,6 @@ __global__ void __launch_bounds__(256) k_check(EvalArgs args, u64 nc, const Fr *
         atomicMin(&ctr[1], (unsigned long long)row);
     }
 }
-
-unsigned blocks_of(u64 n, u32 per) { return (unsigned)((n + per - 1) / per); }
 
 // fn(t, lo, hi) over [0, n) on a few host threads when n is large
 template <class Fn>
@@ -190,8 +164,8 @@ int32_t enqueue_eval(mi_ctx *ctx, const mi_r1cs *r, const Fr *W, u32 which, Fr *
     u32 nm = 0;
     u64 n_pieces = 0, n_long = 0, entries = 0;
     for (int k = 0; k < 3; k++) if (which & (1u << k)) { n_pieces += r->m[k].n_pieces; n_long += r->m[k].n_long; entries += r->m[k].nnz; }
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_PARTIAL], (n_pieces + 1) * sizeof(Fr)));
-    Fr *partial = (Fr *)ctx->ws[WS_PARTIAL].p;
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_R1CS_PARTIAL], (n_pieces + 1) * sizeof(Fr)));
+    Fr *partial = (Fr *)ctx->ws[WS_R1CS_PARTIAL].p;
     u32 max_pieces = 0, max_long = 0;
     for (int k = 0; k < 3; k++) {
         if (!(which & (1u << k))) continue;
@@ -200,16 +174,16 @@ int32_t enqueue_eval(mi_ctx *ctx, const mi_r1cs *r, const Fr *W, u32 which, Fr *
         partial += m.n_pieces;
         max_pieces = std::max(max_pieces, m.n_pieces); max_long = std::max(max_long, m.n_long);
     }
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_BEGIN], st));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_R1CS_BEGIN], st));
     if (nm && r->nc) {
-        const Fr *coeffs = (const Fr *)r->coeffs;
+        const RowTerm term{W, (const Fr *)r->coeffs};
         const unsigned wave_cap = (unsigned)ctx->cu_count * 8;   // blocks of 4 waves for the grid-stride passes
-        if (!compact) hipLaunchKernelGGL(k_rows_short, dim3(blocks_of(r->nc, 256), nm), dim3(256), 0, st, args, r->nc, W, coeffs);
-        if (max_pieces) hipLaunchKernelGGL(k_row_pieces, dim3(std::min(wave_cap, blocks_of(max_pieces, 4)), nm), dim3(256), 0, st, args, W, coeffs);
-        if (max_long) hipLaunchKernelGGL(k_row_combine, dim3(std::min(wave_cap, blocks_of(max_long, 4)), nm), dim3(256), 0, st, args, compact);
+        if (!compact) hipLaunchKernelGGL(k_rows_short, dim3(mi_blocks_of(r->nc, 256), nm), dim3(256), 0, st, args, r->nc, term);
+        if (max_pieces) hipLaunchKernelGGL(k_row_pieces, dim3(std::min(wave_cap, mi_blocks_of(max_pieces, 4)), nm), dim3(256), 0, st, args, term);
+        if (max_long) hipLaunchKernelGGL(k_row_combine, dim3(std::min(wave_cap, mi_blocks_of(max_long, 4)), nm), dim3(256), 0, st, args, compact);
         MI_CHECK_HIP(ctx, hipGetLastError());
     }
-    if (!compact) MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_END], st));
+    if (!compact) MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_R1CS_END], st));
     ctx->r1cs_stats = mi_r1cs_stats{0.f, nm, entries, n_long, n_pieces};
     ctx->r1cs_timed = true;
     return MI_OK;
@@ -266,10 +240,10 @@ int32_t mi_r1cs_validate(mi_ctx *ctx, const char *who_c, const mi_r1cs_desc *d, 
 
 int32_t mi_r1cs_eval_ws(mi_ctx *ctx, const mi_r1cs *r, const mi_fr *W_dev, bool eval_c, const mi_fr **a, const mi_fr **b, const mi_fr **c) {
     const size_t bytes = (size_t)r->nc * sizeof(Fr) + 64;
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_A], bytes));
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_B], bytes));
-    if (eval_c) MI_TRY(mi_reserve(ctx, ctx->ws[WS_C], bytes));
-    Fr *const outs[3] = {(Fr *)ctx->ws[WS_A].p, (Fr *)ctx->ws[WS_B].p, eval_c ? (Fr *)ctx->ws[WS_C].p : nullptr};
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_R1CS_A], bytes));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_R1CS_B], bytes));
+    if (eval_c) MI_TRY(mi_reserve(ctx, ctx->ws[WS_R1CS_C], bytes));
+    Fr *const outs[3] = {(Fr *)ctx->ws[WS_R1CS_A].p, (Fr *)ctx->ws[WS_R1CS_B].p, eval_c ? (Fr *)ctx->ws[WS_R1CS_C].p : nullptr};
     MI_TRY(enqueue_eval(ctx, r, (const Fr *)W_dev, MI_R1CS_A | MI_R1CS_B | (eval_c ? MI_R1CS_C : 0u), outs, false));
     *a = (const mi_fr *)outs[0]; *b = (const mi_fr *)outs[1]; *c = (const mi_fr *)outs[2];
     return MI_OK;
@@ -300,7 +274,7 @@ int32_t mi_r1cs_load(mi_ctx *ctx, const mi_r1cs_desc *d, mi_r1cs **out) {
         MI_TRY(to_device(ctx, r, &r->coeffs, d->coeffs, (size_t)d->n_coeffs * 32));
         const mi_r1cs_matrix *mats[3] = {&d->A, &d->B, &d->C};
         std::vector<uint2> packed;
-        std::vector<uint4> long_rows;
+        std::vector<SparseLong> long_rows;
         std::vector<uint2> pieces;
         for (int k = 0; k < 3; k++) {
             const mi_r1cs_matrix &m = *mats[k];
@@ -314,15 +288,16 @@ int32_t mi_r1cs_load(mi_ctx *ctx, const mi_r1cs_desc *d, mi_r1cs **out) {
             for (u64 i = 0; i < sh.nc; i++) {
                 const u32 lo = rp[i], len = rp[i + 1] - lo;
                 if (len <= SPARSE_SHORT) continue;
-                const u32 np = (len + SPARSE_CHUNK - 1) / SPARSE_CHUNK;
-                long_rows.push_back(make_uint4((u32)i, (u32)pieces.size(), np, 0));
-                for (u32 c = 0; c < np; c++) pieces.push_back(make_uint2(lo + c * SPARSE_CHUNK, std::min(SPARSE_CHUNK, len - c * SPARSE_CHUNK)));
+                const size_t first = pieces.size();
+                long_rows.push_back(SparseLong{(u32)i, (u32)first, sparse_cut(lo, len, nullptr), 0});
+                pieces.resize(first + long_rows.back().n_pieces);
+                sparse_cut(lo, len, pieces.data() + first);
             }
             R1csMatrixDev &dm = r->m[k];
             dm.nnz = nnz; dm.n_long = (u32)long_rows.size(); dm.n_pieces = (u32)pieces.size();
             MI_TRY(to_device(ctx, r, (void **)&dm.row_off, rp.data(), rp.size() * 4));
             MI_TRY(to_device(ctx, r, (void **)&dm.entries, packed.data(), (size_t)nnz * 8));
-            MI_TRY(to_device(ctx, r, (void **)&dm.long_rows, long_rows.data(), long_rows.size() * 16));
+            MI_TRY(to_device(ctx, r, (void **)&dm.long_rows, long_rows.data(), long_rows.size() * sizeof(SparseLong)));
             MI_TRY(to_device(ctx, r, (void **)&dm.pieces, pieces.data(), pieces.size() * 8));
         }
         return MI_OK;
@@ -352,7 +327,7 @@ int32_t mi_r1cs_get_stats(mi_ctx *ctx, mi_r1cs_stats *out) {
     if (!ctx || !out) return MI_EINVAL;
     if (ctx->r1cs_timed) {   // the device time is read here, not in the call: a prove never waits for its evaluation on the host
         float ms = 0;
-        if (hipEventSynchronize(ctx->ev[EV_END]) != hipSuccess || hipEventElapsedTime(&ms, ctx->ev[EV_BEGIN], ctx->ev[EV_END]) != hipSuccess) { (void)hipGetLastError(); ms = 0; }
+        if (hipEventSynchronize(ctx->ev[EV_R1CS_END]) != hipSuccess || hipEventElapsedTime(&ms, ctx->ev[EV_R1CS_BEGIN], ctx->ev[EV_R1CS_END]) != hipSuccess) { (void)hipGetLastError(); ms = 0; }
         ctx->r1cs_stats.eval_ms = ms;
         ctx->r1cs_timed = false;
     }
@@ -376,17 +351,17 @@ int32_t mi_r1cs_eval(mi_ctx *ctx, const mi_r1cs *r, const mi_fr *W, uint32_t whi
     MI_TRY(check_which(ctx, which, a, b, c, "r1cs eval"));
     hipStream_t st = ctx->stream;
     const size_t rows = (size_t)r->nc * sizeof(Fr);
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_W], (size_t)r->nb_wires * sizeof(Fr)));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_R1CS_W], (size_t)r->nb_wires * sizeof(Fr)));
     mi_fr *host[3] = {a, b, c};
     Fr *outs[3] = {nullptr, nullptr, nullptr};
-    const int ws_of[3] = {WS_A, WS_B, WS_C};
+    const int ws_of[3] = {WS_R1CS_A, WS_R1CS_B, WS_R1CS_C};
     for (int k = 0; k < 3; k++) {
         if (!(which & (1u << k))) continue;
         MI_TRY(mi_reserve(ctx, ctx->ws[ws_of[k]], rows + 64));
         outs[k] = (Fr *)ctx->ws[ws_of[k]].p;
     }
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[WS_W].p, W, (size_t)r->nb_wires * sizeof(Fr), hipMemcpyHostToDevice, st));
-    MI_TRY(enqueue_eval(ctx, r, (const Fr *)ctx->ws[WS_W].p, which, outs, false));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[WS_R1CS_W].p, W, (size_t)r->nb_wires * sizeof(Fr), hipMemcpyHostToDevice, st));
+    MI_TRY(enqueue_eval(ctx, r, (const Fr *)ctx->ws[WS_R1CS_W].p, which, outs, false));
     for (int k = 0; k < 3; k++)
         if (outs[k] && rows) MI_CHECK_HIP(ctx, hipMemcpyAsync(host[k], outs[k], rows, hipMemcpyDeviceToHost, st));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
@@ -400,9 +375,9 @@ int32_t mi_r1cs_check_dev(mi_ctx *ctx, const mi_r1cs *r, const mi_fr *W_dev, uin
     hipStream_t st = ctx->stream;
     // the long rows' sums, one per long row, behind the counters
     const u64 n_long = (u64)r->m[0].n_long + r->m[1].n_long + r->m[2].n_long;
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_COUNTERS], 64 + (n_long + 1) * sizeof(Fr)));
-    unsigned long long *ctr = (unsigned long long *)ctx->ws[WS_COUNTERS].p;
-    Fr *lv = (Fr *)((char *)ctx->ws[WS_COUNTERS].p + 64);
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_R1CS_CHECK], 64 + (n_long + 1) * sizeof(Fr)));
+    unsigned long long *ctr = (unsigned long long *)ctx->ws[WS_R1CS_CHECK].p;
+    Fr *lv = (Fr *)((char *)ctx->ws[WS_R1CS_CHECK].p + 64);
     Fr *const outs[3] = {lv, lv + r->m[0].n_long, lv + r->m[0].n_long + r->m[1].n_long};
     MI_CHECK_HIP(ctx, hipMemsetAsync(ctr, 0, 8, st));
     MI_CHECK_HIP(ctx, hipMemsetAsync(ctr + 1, 0xff, 8, st));
@@ -410,10 +385,10 @@ int32_t mi_r1cs_check_dev(mi_ctx *ctx, const mi_r1cs *r, const mi_fr *W_dev, uin
     if (r->nc) {
         EvalArgs args{};
         for (int k = 0; k < 3; k++) args.m[k] = MatArg{r->m[k].row_off, r->m[k].entries, r->m[k].long_rows, r->m[k].pieces, outs[k], nullptr, r->m[k].n_long, r->m[k].n_pieces};
-        hipLaunchKernelGGL(k_check, dim3(blocks_of(r->nc, 256)), dim3(256), 0, st, args, r->nc, (const Fr *)W_dev, (const Fr *)r->coeffs, ctr);
+        hipLaunchKernelGGL(k_check, dim3(mi_blocks_of(r->nc, 256)), dim3(256), 0, st, args, r->nc, RowTerm{(const Fr *)W_dev, (const Fr *)r->coeffs}, ctr);
         MI_CHECK_HIP(ctx, hipGetLastError());
     }
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_END], st));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_R1CS_END], st));
     unsigned long long res[2] = {0, 0};
     MI_CHECK_HIP(ctx, hipMemcpyAsync(res, ctr, 16, hipMemcpyDeviceToHost, st));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(st));

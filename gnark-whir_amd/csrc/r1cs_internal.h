@@ -18,10 +18,11 @@ struct R1csShape {
 // mi_last_error = "<who>: <field> ...".  d itself is checked by the caller (Setup reports a null trapdoor before the first field).
 int32_t mi_r1cs_validate(mi_ctx *ctx, const char *who, const mi_r1cs_desc *d, R1csShape &sh);
 
+struct SparseLong;   // sparse_fr.cuh
 struct R1csMatrixDev {
     uint32_t *row_off = nullptr;        // nc + 1
     uint2 *entries = nullptr;           // nnz x (col | class << 30, coefficient index)
-    uint4 *long_rows = nullptr;         // per row of more than SPARSE_SHORT entries, ascending: (row, first piece, pieces, 0)
+    SparseLong *long_rows = nullptr;    // per row of more than SPARSE_SHORT entries, ascending by row (index = the row)
     uint2 *pieces = nullptr;            // (first entry, entries)
     uint32_t nnz = 0, n_long = 0, n_pieces = 0;
 };

@@ -6,14 +6,12 @@
 //   2  the transposed sparse product M_j = sum_i M[i][j] L_i for M = A, B, C.  The matrices arrive by row, the sums are by column,
 //      and there is no 256-bit atomic add.  Per matrix:
 //        count    32-bit histogram of the column indices; every entry keeps the rank the atomic gave it inside its column
-//        scan     exclusive prefix sum -> first slot of every column
+//        scan     exclusive prefix sum -> first slot of every column (scan_u32.cuh, the MSM's scan)
 //        scatter  (row, coeff) of every entry to slot + rank (a counting sort by column; the order inside a column is whatever the
 //                 atomics gave: field addition is exact and commutative, so every order gives the same bits)
-//        sum      columns of <= SHORT entries: one thread each, 64 columns packed in a wave.  Longer ones are cut into pieces of CHUNK
-//                 entries; a wave sums one piece (lanes stride over it, the lanes' sums meet in a butterfly) into a partial, and a
-//                 second pass adds a column's partials the same way.  Column lengths are heavily skewed -- the constant wire sits in a
-//                 large share of all rows, most wires in one to three -- and a thread per column would leave one lane on millions of
-//                 entries.
+//        sum      the split sum of sparse_fr.cuh (short columns by one lane, long ones cut into pieces, a wave per piece, a combine
+//                 pass), planned here on the device because a column's length exists only after the histogram: k_col_sum_short
+//                 sums the short columns and cuts the long ones, its counts stay in device memory (ctr) for the two wave passes
 //      The count adds up a wave's entries of one column first (wave_claim): a hot column costs one atomic per wave instead of 64 on
 //      one address.
 //   3  element-wise: t_j = beta A_j + alpha B_j + C_j, t_j / delta, t_j / gamma, the zero tests; prefix sums compact the A_j / B_j / K_j
@@ -23,6 +21,7 @@
 // Only the R1CS goes up; the infinity masks, the counts and the verifying key come down.
 #include "prove_internal.h"
 #include "r1cs_internal.h"
+#include "scan_u32.cuh"
 #include "sparse_fr.cuh"
 #include <algorithm>
 #include <chrono>
@@ -32,10 +31,7 @@
 
 namespace {
 
-constexpr u32 SHORT = SPARSE_SHORT;   // a column of at most this many entries is summed by one thread (sparse_fr.cuh: 16)
-constexpr u32 CHUNK = SPARSE_CHUNK;   // entries of a longer column that one wave sums (512)
 constexpr u32 LAG_RUN = 64;    // rows per thread of k_lagrange: one inversion per run
-constexpr u32 SCAN_ITEMS = 8, SCAN_BLOCK = 256, SCAN_TILE = SCAN_ITEMS * SCAN_BLOCK;
 
 MI_D Fr fr_pow_u64(Fr b, u64 e) {
     Fr acc = Fr::one();
@@ -88,49 +84,6 @@ __global__ void __launch_bounds__(64) k_lagrange(Fr *L, u64 nc, u32 T, Fr w, Fr 
     }
 }
 
-// ---------------------------------------------------------------------------------------------------- exclusive scan of u32 (in place)
-__device__ u32 block_exclusive_scan(u32 v, u32 *lds, u32 *total) {   // SCAN_BLOCK threads
-    const u32 t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (u32 o = 1; o < SCAN_BLOCK; o <<= 1) {
-        const u32 add = t >= o ? lds[t - o] : 0;
-        __syncthreads();
-        lds[t] += add;
-        __syncthreads();
-    }
-    const u32 incl = lds[t];
-    *total = lds[SCAN_BLOCK - 1];
-    __syncthreads();
-    return incl - v;
-}
-__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_tiles(u32 *data, u64 n, u32 *tile_sums) {
-    __shared__ u32 lds[SCAN_BLOCK];
-    const u64 base = (u64)blockIdx.x * SCAN_TILE + (u64)threadIdx.x * SCAN_ITEMS;
-    u32 v[SCAN_ITEMS], s = 0;
-#pragma unroll
-    for (u32 k = 0; k < SCAN_ITEMS; k++) { v[k] = base + k < n ? data[base + k] : 0; s += v[k]; }
-    u32 total;
-    u32 run = block_exclusive_scan(s, lds, &total);
-#pragma unroll
-    for (u32 k = 0; k < SCAN_ITEMS; k++) { if (base + k < n) data[base + k] = run; run += v[k]; }
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_sums(u32 *tile_sums, u32 n_tiles) {   // one block
-    __shared__ u32 lds[SCAN_BLOCK];
-    const u32 per = (n_tiles + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    const u32 lo = min(threadIdx.x * per, n_tiles), hi = min(lo + per, n_tiles);
-    u32 s = 0;
-    for (u32 i = lo; i < hi; i++) s += tile_sums[i];
-    u32 total;
-    u32 run = block_exclusive_scan(s, lds, &total);
-    for (u32 i = lo; i < hi; i++) { const u32 v = tile_sums[i]; tile_sums[i] = run; run += v; }
-}
-__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_add(u32 *data, u64 n, const u32 *tile_sums) {
-    const u64 i = (u64)blockIdx.x * SCAN_BLOCK + threadIdx.x;
-    if (i < n) data[i] += tile_sums[i / SCAN_TILE];
-}
-
 // ---------------------------------------------------------------------------------------------------- 2: the transposed sparse product
 // rank[e] = how many entries of e's column were counted before it (any order: the atomics decide); cnt ends as the histogram
 __global__ void __launch_bounds__(256) k_col_count(const u32 *col, u32 nnz, u32 *cnt, u32 *rank) {
@@ -157,53 +110,27 @@ __global__ void __launch_bounds__(256) k_col_scatter(const u32 *row_ptr, u32 n_r
         sorted[pos] = make_uint2(row, coeff[e]);
     }
 }
-struct LongCol { u32 col, first_piece, n_pieces, pad; };
-// ctr[0] = pieces, ctr[1] = long columns
-__global__ void __launch_bounds__(256) k_col_sum_short(Fr *out, u64 nb_wires, const u32 *off, const uint2 *sorted, const Fr *L, const Fr *coeffs,
-                                                       u32 *ctr, uint2 *pieces, LongCol *long_cols) {
+// the term of an entry (row, coefficient) of a sorted column: coeffs[coefficient] * L[row]
+struct ColTerm {
+    const Fr *L, *coeffs;
+    MI_D void operator()(Fr &acc, const uint2 en) const { acc = acc + ld_fr(coeffs + en.y) * ld_fr(L + en.x); }
+};
+// a short column is summed here; a long one claims its pieces: ctr[0] = pieces, ctr[1] = long columns
+__global__ void __launch_bounds__(256) k_col_sum_short(Fr *out, u64 nb_wires, const u32 *off, const uint2 *sorted, ColTerm term, u32 *ctr, uint2 *pieces,
+                                                       SparseLong *long_cols) {
     const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= nb_wires) return;
     const u32 lo = off[j], len = off[j + 1] - lo;
-    if (len <= SHORT) {
-        Fr acc = Fr::zero();
-        for (u32 e = lo; e < lo + len; e++) {
-            const uint2 en = sorted[e];
-            acc = acc + ld_fr(coeffs + en.y) * ld_fr(L + en.x);
-        }
-        st_fr(out + j, acc);
-        return;
-    }
-    const u32 np = (len + CHUNK - 1) / CHUNK;
-    const u32 first = atomicAdd(&ctr[0], np);
-    long_cols[atomicAdd(&ctr[1], 1u)] = LongCol{(u32)j, first, np, 0};
-    for (u32 c = 0; c < np; c++) pieces[first + c] = make_uint2(lo + c * CHUNK, min(CHUNK, len - c * CHUNK));
+    if (len <= SPARSE_SHORT) { st_fr(out + j, sparse_sum_short(sorted, lo, len, term)); return; }
+    const u32 np = sparse_cut(lo, len, nullptr), first = atomicAdd(&ctr[0], np);
+    long_cols[atomicAdd(&ctr[1], 1u)] = SparseLong{(u32)j, first, np, 0};
+    sparse_cut(lo, len, pieces + first);
 }
-// a wave per piece (grid-stride): partial[piece] = sum of its entries
-__global__ void __launch_bounds__(256) k_col_sum_pieces(Fr *partial, const u32 *ctr, const uint2 *pieces, const uint2 *sorted, const Fr *L, const Fr *coeffs) {
-    const u32 lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    const u32 n_pieces = ctr[0];
-    for (u32 it = wave; it < n_pieces; it += n_waves) {
-        const uint2 pc = pieces[it];
-        Fr acc = Fr::zero();
-        for (u32 k = lane; k < pc.y; k += 64) {
-            const uint2 en = sorted[pc.x + k];
-            acc = acc + ld_fr(coeffs + en.y) * ld_fr(L + en.x);
-        }
-        acc = wave_sum(acc);
-        if (lane == 0) st_fr(partial + it, acc);
-    }
+__global__ void __launch_bounds__(256) k_col_sum_pieces(Fr *partial, const u32 *ctr, const uint2 *pieces, const uint2 *sorted, ColTerm term) {
+    sparse_sum_pieces(partial, pieces, ctr[0], sorted, term);
 }
-// a wave per long column (grid-stride): the sum of its partials
-__global__ void __launch_bounds__(256) k_col_sum_combine(Fr *out, const u32 *ctr, const LongCol *long_cols, const Fr *partial) {
-    const u32 lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    const u32 n_long = ctr[1];
-    for (u32 it = wave; it < n_long; it += n_waves) {
-        const LongCol lc = long_cols[it];
-        Fr acc = Fr::zero();
-        for (u32 k = lane; k < lc.n_pieces; k += 64) acc = acc + ld_fr(partial + lc.first_piece + k);
-        acc = wave_sum(acc);
-        if (lane == 0) st_fr(out + lc.col, acc);
-    }
+__global__ void __launch_bounds__(256) k_col_sum_combine(Fr *out, const u32 *ctr, const SparseLong *long_cols, const Fr *partial) {
+    sparse_combine(out, long_cols, ctr[1], partial, false);
 }
 
 // ---------------------------------------------------------------------------------------------------- 3: element-wise
@@ -251,23 +178,6 @@ __global__ void __launch_bounds__(256) k_z_exps(Fr *Z, u32 log_n, Fr zt, TauPowe
 
 // ---------------------------------------------------------------------------------------------------- host side
 Fr fr_of(const mi_fr &x) { Fr r; std::memcpy(&r, &x, 32); return r; }
-Fr host_fr_u64x4(u64 a, u64 b, u64 c, u64 d) {
-    Fr t;
-    t.l[0] = (u32)a; t.l[1] = (u32)(a >> 32); t.l[2] = (u32)b; t.l[3] = (u32)(b >> 32);
-    t.l[4] = (u32)c; t.l[5] = (u32)(c >> 32); t.l[6] = (u32)d; t.l[7] = (u32)(d >> 32);
-    return fe_to_mont(t);
-}
-Fp host_fp_u64x4(u64 a, u64 b, u64 c, u64 d) {
-    Fp t;
-    t.l[0] = (u32)a; t.l[1] = (u32)(a >> 32); t.l[2] = (u32)b; t.l[3] = (u32)(b >> 32);
-    t.l[4] = (u32)c; t.l[5] = (u32)(c >> 32); t.l[6] = (u32)d; t.l[7] = (u32)(d >> 32);
-    return fe_to_mont(t);
-}
-Fr setup_domain_generator(u32 log_n) {   // fft.NewDomain: Generator = root^(2^(28 - log_n)), as csrc/ntt.hip
-    Fr g = host_fr_u64x4(0x9bd61b6e725b19f0ull, 0x402d111e41112ed4ull, 0x00e0a7eb8ef62abcull, 0x2a3c09f0a58a7e85ull);
-    for (u32 k = log_n; k < 28; k++) g = fe_sqr(g);
-    return g;
-}
 // the generators gnark-crypto's bn254 package fixes (g1 = (1, 2); g2 as in EIP-197)
 mi_g1_affine g1_generator() {
     G1Aff g{Fp::one(), fe_from_u32<FpParams>(2)};
@@ -275,10 +185,10 @@ mi_g1_affine g1_generator() {
 }
 mi_g2_affine g2_generator() {
     G2Aff g;
-    g.x.a0 = host_fp_u64x4(0x46debd5cd992f6edull, 0x674322d4f75edaddull, 0x426a00665e5c4479ull, 0x1800deef121f1e76ull);
-    g.x.a1 = host_fp_u64x4(0x97e485b7aef312c2ull, 0xf1aa493335a9e712ull, 0x7260bfb731fb5d25ull, 0x198e9393920d483aull);
-    g.y.a0 = host_fp_u64x4(0x4ce6cc0166fa7daaull, 0xe3d1e7690c43d37bull, 0x4aab71808dcb408full, 0x12c85ea5db8c6debull);
-    g.y.a1 = host_fp_u64x4(0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull);
+    g.x.a0 = fe_from_u64x4<FpParams>(0x46debd5cd992f6edull, 0x674322d4f75edaddull, 0x426a00665e5c4479ull, 0x1800deef121f1e76ull);
+    g.x.a1 = fe_from_u64x4<FpParams>(0x97e485b7aef312c2ull, 0xf1aa493335a9e712ull, 0x7260bfb731fb5d25ull, 0x198e9393920d483aull);
+    g.y.a0 = fe_from_u64x4<FpParams>(0x4ce6cc0166fa7daaull, 0xe3d1e7690c43d37bull, 0x4aab71808dcb408full, 0x12c85ea5db8c6debull);
+    g.y.a1 = fe_from_u64x4<FpParams>(0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull);
     mi_g2_affine o; std::memcpy(&o, &g, 128); return o;
 }
 
@@ -308,7 +218,7 @@ int32_t make_plan(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_trapdoor *td, Pla
     const Fr zn = tn - Fr::one();
     pl.lam = zn * fe_inv(fe_from_u32<FrParams>((u32)pl.N));
     pl.zt = zn * pl.delta_inv;
-    pl.w = setup_domain_generator(log_n);
+    pl.w = fr_domain_generator(log_n);
     return MI_OK;
 }
 
@@ -330,16 +240,6 @@ struct Arena {
     void disown(void *p) { for (void *&q : live) if (q == p) q = nullptr; }
 };
 
-int32_t scan_u32(mi_ctx *ctx, u32 *data, u64 n, u32 *tile_sums) {
-    const u32 tiles = (u32)((n + SCAN_TILE - 1) / SCAN_TILE);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(SCAN_BLOCK), 0, ctx->stream, data, n, tile_sums);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_BLOCK), 0, ctx->stream, tile_sums, tiles);
-    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)((n + SCAN_BLOCK - 1) / SCAN_BLOCK)), dim3(SCAN_BLOCK), 0, ctx->stream, data, n, (const u32 *)tile_sums);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    return MI_OK;
-}
-unsigned blocks_of(u64 n, u32 per) { return (unsigned)((n + per - 1) / per); }
-
 struct Timer {   // HIP events on the context's stream, one per phase boundary
     enum { UP0, UP1, LAG, SUM, ELEM, POINTS, DONE, COUNT };
     hipEvent_t ev[COUNT]{};
@@ -355,7 +255,6 @@ struct FrHalf {
     Fr *A = nullptr, *B = nullptr, *C = nullptr, *Kd = nullptr, *Kg = nullptr;
     uint8_t *inf_a = nullptr, *inf_b = nullptr;
     u32 *slot_a = nullptr, *slot_b = nullptr, *slot_k = nullptr;   // nb_wires + 1 each: compaction slots, [nb_wires] = the count
-    u32 *tile_sums = nullptr;
     float sort_ms = 0, sum_ms = 0;
     u64 long_columns = 0, chunks = 0;
 };
@@ -388,12 +287,11 @@ int32_t run_fr_half(mi_ctx *ctx, const mi_r1cs_desc *d, const Plan &pl, Arena &a
     // ---- 2: the three transposed products, one after the other over the same scratch
     u32 *cnt = nullptr, *off = nullptr, *ctr = nullptr, *rank = nullptr;
     uint2 *sorted = nullptr, *pieces = nullptr;
-    LongCol *long_cols = nullptr;
+    SparseLong *long_cols = nullptr;
     Fr *partial = nullptr;
-    const size_t cap_long = (size_t)max_nnz / SHORT + 1;   // a long column has more than SHORT entries and at most len / SHORT pieces
-    MI_TRY(ar.alloc(ctx, &cnt, (size_t)nw + 1));
+    const size_t cap_long = (size_t)max_nnz / SPARSE_SHORT + 1;   // a long column has more than SPARSE_SHORT entries and at most len / SPARSE_SHORT pieces
+    MI_TRY(ar.alloc(ctx, &cnt, (size_t)nw));
     MI_TRY(ar.alloc(ctx, &off, (size_t)nw + 1));
-    MI_TRY(ar.alloc(ctx, &f.tile_sums, (size_t)((nw + 1 + SCAN_TILE - 1) / SCAN_TILE) + 1));
     MI_TRY(ar.alloc(ctx, &rank, (size_t)max_nnz));
     MI_TRY(ar.alloc(ctx, &sorted, (size_t)max_nnz));
     MI_TRY(ar.alloc(ctx, &pieces, cap_long));
@@ -420,19 +318,17 @@ int32_t run_fr_half(mi_ctx *ctx, const mi_r1cs_desc *d, const Plan &pl, Arena &a
             MI_CHECK_HIP(ctx, hipMemcpyAsync(cf, mats[k]->coeff, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
         }
         MI_CHECK_HIP(ctx, hipEventRecord(e1, st));
-        MI_CHECK_HIP(ctx, hipMemsetAsync(cnt, 0, (nw + 1) * 4, st));
-        if (nnz) hipLaunchKernelGGL(k_col_count, dim3(blocks_of(nnz, 256)), dim3(256), 0, st, (const u32 *)col, nnz, cnt, rank);
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(off, cnt, (nw + 1) * 4, hipMemcpyDeviceToDevice, st));
-        MI_TRY(scan_u32(ctx, off, nw + 1, f.tile_sums));
-        if (nnz) hipLaunchKernelGGL(k_col_scatter, dim3(blocks_of(((u64)nnz + 3) / 4, 256)), dim3(256), 0, st, (const u32 *)row_ptr, (u32)pl.nc,
+        MI_CHECK_HIP(ctx, hipMemsetAsync(cnt, 0, nw * 4, st));
+        if (nnz) hipLaunchKernelGGL(k_col_count, dim3(mi_blocks_of(nnz, 256)), dim3(256), 0, st, (const u32 *)col, nnz, cnt, rank);
+        MI_TRY(exclusive_scan(ctx, st, cnt, nw, off, ctx->ws[WS_SCAN]));   // off[nw] = the number of entries
+        if (nnz) hipLaunchKernelGGL(k_col_scatter, dim3(mi_blocks_of(((u64)nnz + 3) / 4, 256)), dim3(256), 0, st, (const u32 *)row_ptr, (u32)pl.nc,
                                     (const u32 *)col, (const u32 *)cf, nnz, (const u32 *)off, (const u32 *)rank, sorted);
         MI_CHECK_HIP(ctx, hipEventRecord(e2, st));
         MI_CHECK_HIP(ctx, hipMemsetAsync(ctr, 0, 8, st));
-        hipLaunchKernelGGL(k_col_sum_short, dim3(blocks_of(nw, 256)), dim3(256), 0, st, outs[k], nw, (const u32 *)off, (const uint2 *)sorted,
-                           (const Fr *)L, (const Fr *)coeffs, ctr, pieces, long_cols);
-        hipLaunchKernelGGL(k_col_sum_pieces, dim3(wave_grid), dim3(256), 0, st, partial, (const u32 *)ctr, (const uint2 *)pieces, (const uint2 *)sorted,
-                           (const Fr *)L, (const Fr *)coeffs);
-        hipLaunchKernelGGL(k_col_sum_combine, dim3(wave_grid), dim3(256), 0, st, outs[k], (const u32 *)ctr, (const LongCol *)long_cols, (const Fr *)partial);
+        const ColTerm term{L, coeffs};
+        hipLaunchKernelGGL(k_col_sum_short, dim3(mi_blocks_of(nw, 256)), dim3(256), 0, st, outs[k], nw, (const u32 *)off, (const uint2 *)sorted, term, ctr, pieces, long_cols);
+        hipLaunchKernelGGL(k_col_sum_pieces, dim3(wave_grid), dim3(256), 0, st, partial, (const u32 *)ctr, (const uint2 *)pieces, (const uint2 *)sorted, term);
+        hipLaunchKernelGGL(k_col_sum_combine, dim3(wave_grid), dim3(256), 0, st, outs[k], (const u32 *)ctr, (const SparseLong *)long_cols, (const Fr *)partial);
         MI_CHECK_HIP(ctx, hipGetLastError());
         u32 ctr_h[2] = {0, 0};
         MI_CHECK_HIP(ctx, hipMemcpyAsync(ctr_h, ctr, 8, hipMemcpyDeviceToHost, st));
@@ -455,26 +351,27 @@ int32_t run_fr_half(mi_ctx *ctx, const mi_r1cs_desc *d, const Plan &pl, Arena &a
     MI_TRY(ar.alloc(ctx, &f.slot_a, (size_t)nw + 1));
     MI_TRY(ar.alloc(ctx, &f.slot_b, (size_t)nw + 1));
     MI_TRY(ar.alloc(ctx, &f.slot_k, (size_t)nw + 1));
-    for (u32 *s : {f.slot_a, f.slot_b, f.slot_k}) MI_CHECK_HIP(ctx, hipMemsetAsync(s + nw, 0, 4, st));
-    hipLaunchKernelGGL(k_elementwise, dim3(blocks_of(nw, 256)), dim3(256), 0, st, (const Fr *)f.A, (const Fr *)f.B, (const Fr *)f.C, f.Kd, f.Kg, f.inf_a, f.inf_b,
+    hipLaunchKernelGGL(k_elementwise, dim3(mi_blocks_of(nw, 256)), dim3(256), 0, st, (const Fr *)f.A, (const Fr *)f.B, (const Fr *)f.C, f.Kd, f.Kg, f.inf_a, f.inf_b,
                        f.slot_a, f.slot_b, f.slot_k, nw, pl.nb_public, pl.alpha, pl.beta, pl.delta_inv, pl.gamma_inv);
     MI_CHECK_HIP(ctx, hipGetLastError());
     if (!pl.removed.empty()) {
         u32 *rem = nullptr;
         MI_TRY(ar.alloc(ctx, &rem, pl.removed.size()));
         MI_CHECK_HIP(ctx, hipMemcpyAsync(rem, pl.removed.data(), pl.removed.size() * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_clear_flags, dim3(blocks_of(pl.removed.size(), 256)), dim3(256), 0, st, f.slot_k, (const u32 *)rem, (u32)pl.removed.size());
+        hipLaunchKernelGGL(k_clear_flags, dim3(mi_blocks_of(pl.removed.size(), 256)), dim3(256), 0, st, f.slot_k, (const u32 *)rem, (u32)pl.removed.size());
         MI_CHECK_HIP(ctx, hipGetLastError());
         MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
         ar.release(rem);
     }
-    for (u32 *s : {f.slot_a, f.slot_b, f.slot_k}) MI_TRY(scan_u32(ctx, s, nw + 1, f.tile_sums));
+    // in == out: k_scan_final holds a block's values in registers before it stores the first of them, no block reads another's, and
+    // the block sums come from an earlier launch.  The count of kept wires arrives in slot[nw].
+    for (u32 *s : {f.slot_a, f.slot_b, f.slot_k}) MI_TRY(exclusive_scan(ctx, st, s, nw, s, ctx->ws[WS_SCAN]));
     MI_TRY(tm.mark(ctx, Timer::ELEM));
     return MI_OK;
 }
 
 int32_t z_exps_dev(mi_ctx *ctx, const Plan &pl, Fr *Z) {
-    hipLaunchKernelGGL(k_z_exps, dim3(blocks_of(pl.N, 256)), dim3(256), 0, ctx->stream, Z, pl.log_n, pl.zt, pl.tp);
+    hipLaunchKernelGGL(k_z_exps, dim3(mi_blocks_of(pl.N, 256)), dim3(256), 0, ctx->stream, Z, pl.log_n, pl.zt, pl.tp);
     MI_CHECK_HIP(ctx, hipGetLastError());
     return MI_OK;
 }
@@ -571,7 +468,7 @@ int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
         Fr *sa = nullptr, *sb = nullptr, *sk = nullptr;
         auto compact = [&](Fr **dst, Fr *src, u32 *slot, u32 n) -> int32_t {
             MI_TRY(ar.alloc(ctx, dst, (size_t)n));
-            hipLaunchKernelGGL(k_compact, dim3(blocks_of(nw, 256)), dim3(256), 0, st, *dst, (const Fr *)src, (const u32 *)slot, nw);
+            hipLaunchKernelGGL(k_compact, dim3(mi_blocks_of(nw, 256)), dim3(256), 0, st, *dst, (const Fr *)src, (const u32 *)slot, nw);
             MI_CHECK_HIP(ctx, hipGetLastError());
             MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
             ar.release(src); ar.release(slot);
@@ -581,7 +478,6 @@ int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
         MI_TRY(compact(&sb, f.B, f.slot_b, n_b));
         ar.release(f.C);
         MI_TRY(compact(&sk, f.Kd, f.slot_k, n_k));
-        ar.release(f.tile_sums);
         // a batch of points from device scalars into a fresh array
         auto mul_g1 = [&](void **dst, const Fr *sc, size_t n) -> int32_t {
             MI_TRY(ar.alloc(ctx, dst, n * 64));
@@ -593,7 +489,7 @@ int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
             MI_TRY(ar.alloc(ctx, dst, n));
             if (n) {
                 MI_CHECK_HIP(ctx, hipMemcpyAsync(idx, wires, n * 4, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_gather_scale, dim3(blocks_of(n, 256)), dim3(256), 0, st, *dst, (const Fr *)f.Kg, (const u32 *)idx, (u64)n, factor);
+                hipLaunchKernelGGL(k_gather_scale, dim3(mi_blocks_of(n, 256)), dim3(256), 0, st, *dst, (const Fr *)f.Kg, (const u32 *)idx, (u64)n, factor);
                 MI_CHECK_HIP(ctx, hipGetLastError());
             }
             MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
