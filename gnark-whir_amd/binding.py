@@ -19,7 +19,7 @@ EXPORTS = [
     "mi_ntt", "mi_ntt_dev", "mi_compute_h", "mi_compute_h_dev", "mi_msm_g1", "mi_msm_g1_dev", "mi_msm_g2",
     "mi_msm_g2_dev", "mi_groth16_prove", "mi_groth16_prove_dev", "mi_get_stats", "mi_g1_compress",
     "mi_g2_compress", "mi_proof_write", "mi_g1_sum", "mi_g2_sum", "mi_gen_scalars_dev", "mi_gen_g1_dev",
-    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
+    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
     "mi_dev_alloc", "mi_dev_free", "mi_dev_upload", "mi_dev_download", "mi_dev_sync",
     "mi_msm_precompute_g1_dev", "mi_msm_precompute_g2_dev", "mi_msm_g1_fixed_dev", "mi_msm_g2_fixed_dev", "mi_msm_table_to_rprime_g1_dev", "mi_msm_table_to_rprime_g2_dev", "mi_pk_table_plan",
     "mi_batch_scalar_mul_g1", "mi_batch_scalar_mul_g1_dev", "mi_batch_scalar_mul_g2", "mi_batch_scalar_mul_g2_dev",
@@ -45,6 +45,10 @@ R1CS_EXPORTS = ["mi_r1cs_load", "mi_r1cs_free", "mi_r1cs_bytes", "mi_r1cs_eval",
                 "mi_groth16_prove_w", "mi_groth16_prove_w_dev", "mi_prover_submit_w", "mi_prover_submit_w_dev", "mi_prover_submit_w_bsb22"]
 R1CS_A, R1CS_B, R1CS_C = 1, 2, 4
 PROVE_W_EVAL_C = 1
+# include/mi355x_groth16_verify.h (groth16.Verify on the device)
+VERIFY_EXPORTS = ["mi_vk_load", "mi_vk_free", "mi_pedersen_vk_make", "mi_groth16_verify", "mi_groth16_verify_batch"]
+VERIFY_OK, VERIFY_PAIRING, VERIFY_PEDERSEN, VERIFY_MALFORMED = 0, 1, 2, 3
+PAIRING_FINAL_EXP = 1
 
 
 class PkDesc(C.Structure):
@@ -150,6 +154,20 @@ def _trapdoor(td: dict):
     for k, sg in enumerate(td.get("sigma", [])):
         t.sigma[k] = (C.c_uint64 * 4)(*[int(v) for v in _u64(sg).reshape(4)])
     return t
+
+
+class PedersenVk(C.Structure):
+    _fields_ = [("g", C.c_uint64 * 16), ("g_sigma_neg", C.c_uint64 * 16)]
+
+
+class VkDesc(C.Structure):
+    _fields_ = [("alpha1", C.c_uint64 * 8), ("beta2", C.c_uint64 * 16), ("gamma2", C.c_uint64 * 16), ("delta2", C.c_uint64 * 16),
+                ("k", C.c_void_p), ("n_k", C.c_uint64), ("nb_public", C.c_uint32), ("n_commitments", C.c_uint32), ("ped", C.c_void_p)]
+
+
+class VerifyInput(C.Structure):
+    _fields_ = [("proof", C.c_uint64 * 32), ("commitments", C.c_void_p), ("pok", C.c_void_p), ("public_inputs", C.c_void_p),
+                ("commitment_values", C.c_void_p), ("fold_challenge", C.c_void_p)]
 
 
 class Bsb22Input(C.Structure):
@@ -559,6 +577,42 @@ class Context:
                                                  _p(r), _p(s), _p(out), C.byref(st)))
         return {"ar": out[:8].copy(), "bs": out[8:24].copy(), "krs": out[24:].copy(), "raw": out}, st.as_dict()
 
+    # ---- groth16.Verify on the device (include/mi355x_groth16_verify.h)
+    def pedersen_vk_make(self, sigmas):
+        """mi_pedersen_vk_make: (n, 4) Montgomery sigma rows -> (n, 2, 16) uint64: G and GSigmaNeg of each commitment"""
+        sg = _u64(sigmas).reshape(-1, 4); n = sg.shape[0]
+        out = np.zeros((n, 2, 16), np.uint64)
+        self._ck(self.lib.mi_pedersen_vk_make(self.h, _p(sg), C.c_uint32(n), _p(out)))
+        return out
+
+    def vk_load(self, vk: dict, nb_public, ped=None, n_k=None):
+        """mi_vk_load: the vk dict setup() returns (alpha1, beta2, gamma2, delta2, k), nb_public (with the ONE wire) and the Pedersen
+        verifying keys ((n_commitments, 2, 16), as pedersen_vk_make) -> VerifyingKey"""
+        return VerifyingKey(self, vk, nb_public, ped, n_k)
+
+    def pairing(self, p, q, final_exp=True):
+        """mi_debug_pairing_dev over host arrays: (n, 8) G1 and (n, 16) G2 points -> (n, 48) uint64, 12 x mi_fp per pair"""
+        p, q = _u64(p).reshape(-1, 8), _u64(q).reshape(-1, 16); n = p.shape[0]
+        dp, dq = self.to_dev(p), self.to_dev(q); do = self.alloc(max(384 * n, 32))
+        try:
+            self._ck(self.lib.mi_debug_pairing_dev(self.h, _p(dp.ptr), _p(dq.ptr), C.c_size_t(n), _p(do.ptr), C.c_uint32(PAIRING_FINAL_EXP if final_exp else 0)))
+            self.sync()
+            return do.download((n, 48)) if n else np.zeros((0, 48), np.uint64)
+        finally:
+            for b in (dp, dq, do): b.free()
+
+    def fp12_op(self, op, x, y=None):
+        """mi_debug_fp12_op_dev over host arrays of (n, 48) uint64 records (csrc/pairing_ops.cuh)"""
+        x = _u64(x).reshape(-1, 48); n = x.shape[0]
+        dx = self.to_dev(x); dy = self.to_dev(_u64(y).reshape(-1, 48)) if y is not None else None; dz = self.alloc(max(384 * n, 32))
+        try:
+            self._ck(self.lib.mi_debug_fp12_op_dev(self.h, C.c_int(op), _p(dz.ptr), _p(dx.ptr), _p(dy.ptr if dy else None), C.c_size_t(n)))
+            self.sync()
+            return dz.download((n, 48)) if n else np.zeros((0, 48), np.uint64)
+        finally:
+            for b in (dx, dy, dz):
+                if b: b.free()
+
     def trim(self):
         """mi_ctx_trim: every grow-only workspace of this (idle) context goes back to the device"""
         self._ck(self.lib.mi_ctx_trim(self.h))
@@ -570,6 +624,53 @@ class Context:
         """device memory held by the key `pkh` and by this context, in GB (mi_get_mem_ledger)"""
         m = MemLedger(); self._ck(self.lib.mi_get_mem_ledger(self.h, pkh, C.byref(m)))
         return {n: getattr(m, n) / 1e9 for n, _ in MemLedger._fields_}
+
+
+class VerifyingKey:
+    """A device-resident verifying key (mi_vk).  verify / verify_batch take proofs as dicts: raw ((32,) uint64: Ar | Bs | Krs, as
+    prove()'s "raw"), public_inputs ((nb_public - 1, 4) Montgomery), and with commitments: commitments (n, 8), pok (8,),
+    commitment_values (n, 4), fold_challenge (4,) (optional with one commitment).  The verdict is one of VERIFY_*."""
+
+    def __init__(self, ctx, vk, nb_public, ped=None, n_k=None):
+        self.ctx = ctx
+        d = VkDesc()
+        for n, w in (("alpha1", 8), ("beta2", 16), ("gamma2", 16), ("delta2", 16)):
+            setattr(d, n, (C.c_uint64 * w)(*[int(v) for v in _u64(vk[n]).reshape(w)]))
+        k = _u64(vk["k"]).reshape(-1, 8)
+        ped = None if ped is None else _u64(ped).reshape(-1, 2, 16)
+        d.k, d.n_k, d.nb_public = k.ctypes.data, int(k.shape[0] if n_k is None else n_k), int(nb_public)
+        d.n_commitments = 0 if ped is None else int(ped.shape[0])
+        d.ped = None if ped is None else ped.ctypes.data
+        self.nb_public, self.n_commitments = int(nb_public), int(d.n_commitments)
+        h = C.c_void_p()
+        ctx._ck(ctx.lib.mi_vk_load(ctx.h, C.byref(d), C.byref(h)))
+        self.h = h
+
+    def _inputs(self, proofs):
+        arr = (VerifyInput * len(proofs))(); keep = []
+        for i, pr in enumerate(proofs):
+            arr[i].proof = (C.c_uint64 * 32)(*[int(v) for v in _u64(pr["raw"]).reshape(32)])
+            for name in ("commitments", "pok", "public_inputs", "commitment_values", "fold_challenge"):
+                v = pr.get(name)
+                if v is not None:
+                    v = _u64(v); keep.append(v)
+                    setattr(arr[i], name, v.ctypes.data)
+        return arr, keep
+
+    def verify(self, proof: dict) -> int:
+        arr, keep = self._inputs([proof]); v = C.c_uint8(255)
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify(self.ctx.h, self.h, C.byref(arr[0]), C.byref(v)))
+        return int(v.value)
+
+    def verify_batch(self, proofs):
+        arr, keep = self._inputs(list(proofs)); out = np.full(len(arr), 255, np.uint8)
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_batch(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), _p(out)))
+        return out
+
+    def free(self):
+        if self.h:
+            self.ctx._ck(self.ctx.lib.mi_vk_free(self.ctx.h, self.h))
+            self.h = None
 
 
 # ---- host-only helpers (no ctx)

@@ -35,6 +35,7 @@ enum {
     WS_R1CS_CHECK = 10,    // r1cs.hip check: the counters, then one sum per long row                    main
     WS_R1CS_W = 11,        // r1cs.hip: W of the host entry point                                        main
     WS_SCAN = 12,          // setup.hip: block sums of the shared u32 scan (scan_u32.cuh)                main
+    WS_VERIFY = 13,        // verify.hip: scalars, pairs, Miller values, flags and verdicts of a batch           main
     WS_H = 14,             // prove.hip / group.hip: h, computeH's result and the Z MSM's scalars        main, read by msm[4].stream
     WS_PROVE_IN = 16,      // prove.hip / group.hip: W (+ a, b, c) of a prove over host inputs           filled on copy_stream
     WS_B_WIRES = 17,       // prove.hip: W gathered to the wires that own a pk.G1.B point                msm[1].stream
@@ -43,7 +44,7 @@ enum {
     WS_FB_SCALARS = 21,    // fixed_base.hip host entry point: the scalars                               main
     WS_FB_OUT = 22,        // fixed_base.hip host entry point: the points                                main
     WS_RPRIME = 23,        // msm.hip device entry point: the points in the R' packed form               main
-    WS_COUNT = 24          // 13, 15 and 18 are free
+    WS_COUNT = 24          // 15 and 18 are free
 };
 enum { EV_R1CS_BEGIN = 12, EV_R1CS_END = 13 };   // mi_ctx::ev[]: around the launches of the last R1CS evaluation (r1cs.hip)
 

@@ -1,0 +1,276 @@
+// groth16.Verify on the device (include/mi355x_groth16_verify.h; mt.go:497 of the reference): the BN254 pairing check behind a
+// device-resident verifying key, and the two debug entry points over the same arithmetic (fp12.cuh, pairing.cuh, pairing_ops.cuh).
+//
+// One batch, every launch on ctx->stream:
+//   host      the curve checks of the G1 points, the scalars of kSum; per proof one G1 MSM over the key's resident K[1..] (msm.hip), then
+//             kSum = K[0] + that + sum C_k and the folded commitments c^k C_k; the pairs of every proof laid out as pairing_ops.cuh says
+//   k_verify_g2_check   one lane per proof: Bs on the twist and in its r-torsion -> the malformed flag
+//   k_pairing_miller    one lane per (proof, pair): a Miller loop, 384 B out
+//   k_verify_judge      one lane per proof: the products of its Miller values, the final exponentiations, the comparisons -> a verdict byte
+// Everything of a batch lives in ONE grow-only workspace (WS_VERIFY): nothing is allocated in steady state.
+#include "ctx.h"
+#include "../../include/mi355x_groth16_verify.h"
+#include "pairing_ops.cuh"
+#include <cstring>
+#include <vector>
+
+struct mi_vk {
+    G1Aff alpha1;
+    G2Aff beta2, gamma2, delta2;
+    std::vector<G1Aff> k;              // host copy: K[0] and the counts
+    G1Aff *k_dev = nullptr;            // K[1 .. n_k): the bases of kSum's MSM, uploaded once
+    Fp12 *e_alpha_beta_dev = nullptr;  // e(alpha, beta)^s, computed once
+    uint32_t nb_public = 0, n_commitments = 0;
+    std::vector<mi_pedersen_vk> ped;
+};
+
+namespace {
+
+// Fp12 values live in scratch memory here by design (fp12.cuh): one wave per SIMD is all these kernels ask for
+__global__ void __launch_bounds__(64, 1) k_pairing_miller(const G1Aff *p, const G2Aff *q, Fp12 *out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const G1Aff pp = p[i];
+    const G2Aff qq = q[i];
+    Fp12 f;
+    pairing_miller_loop(&f, &pp, &qq);
+    out[i] = f;
+}
+__global__ void __launch_bounds__(64, 1) k_pairing_final_exp(Fp12 *io, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fp12 f = io[i];
+    pairing_final_exp(&f, &f);
+    io[i] = f;
+}
+__global__ void __launch_bounds__(64, 1) k_fp12_op(int op, Fp12 *z, const Fp12 *x, const Fp12 *y, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Fp12 xx = x[i], yy = y ? y[i] : x[i];
+    Fp12 r = Fp12{Fp6::zero(), Fp6::zero()};
+    (void)fp12_op(op, &r, &xx, &yy);
+    z[i] = r;
+}
+// flags[i] |= Bs of proof i (the Q of its first pair) is not a point of the r-torsion of the twist
+__global__ void __launch_bounds__(64, 1) k_verify_g2_check(const G2Aff *q, u32 pairs_per_proof, uint8_t *flags, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const G2Aff bs = q[i * pairs_per_proof];
+    if (!g2_in_subgroup(&bs)) flags[i] = 1;
+}
+__global__ void __launch_bounds__(64, 1) k_verify_judge(const Fp12 *ml, u32 pairs_per_proof, const Fp12 *e_alpha_beta, const uint8_t *flags,
+                                                        uint8_t *verdicts, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Fp12 eab = *e_alpha_beta;
+    verdicts[i] = verify_judge(ml + i * pairs_per_proof, pairs_per_proof - MI_VERIFY_GROTH_PAIRS, &eab, flags[i] != 0);
+}
+
+inline unsigned grid64(size_t n) { return (unsigned)((n + 63) / 64); }
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+G1Aff g1_of(const mi_g1_affine &p) { G1Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
+G2Aff g2_of(const mi_g2_affine &p) { G2Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
+G1Aff g1_neg(const G1Aff &p) { return G1Aff{p.x, fe_neg(p.y)}; }
+
+// Miller values of n pairs already on the device, then (final) f^d' in place
+int32_t pairing_enqueue(mi_ctx *ctx, const G1Aff *p_dev, const G2Aff *q_dev, size_t n, Fp12 *gt_dev, bool final_exp) {
+    hipLaunchKernelGGL(k_pairing_miller, dim3(grid64(n)), dim3(64), 0, ctx->stream, p_dev, q_dev, gt_dev, n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    if (final_exp) {
+        hipLaunchKernelGGL(k_pairing_final_exp, dim3(grid64(n)), dim3(64), 0, ctx->stream, gt_dev, n);
+        MI_CHECK_HIP(ctx, hipGetLastError());
+    }
+    return MI_OK;
+}
+
+int32_t verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts) {
+    if (!ctx) return MI_EINVAL;
+    if (!vk || (!in && n) || (!verdicts && n)) MI_FAIL(ctx, MI_EINVAL, "verify: null vk, input or verdict pointer");
+    if (n > ((size_t)1 << 24)) MI_FAIL(ctx, MI_EINVAL, "verify: more than 2^24 proofs in one batch");
+    const u32 nc = vk->n_commitments, n_pub = vk->nb_public - 1, ns = n_pub + nc;
+    const u32 n_ped = nc ? nc + 1 : 0, np = MI_VERIFY_GROTH_PAIRS + n_ped;
+    for (size_t i = 0; i < n; i++) {
+        if (n_pub && !in[i].public_inputs) MI_FAIL(ctx, MI_EINVAL, "verify: public_inputs is null");
+        if (nc && (!in[i].commitments || !in[i].pok || !in[i].commitment_values)) MI_FAIL(ctx, MI_EINVAL, "verify: commitments, pok or commitment_values is null");
+        if (nc > 1 && !in[i].fold_challenge) MI_FAIL(ctx, MI_EINVAL, "verify: fold_challenge is null with more than one commitment");
+    }
+    if (!n) return MI_OK;
+
+    // ---- host: flags, scalars
+    std::vector<uint8_t> flags(n, 0);
+    std::vector<mi_fr> scal((size_t)n * ns);
+    for (size_t i = 0; i < n; i++) {
+        bool ok = g1_on_curve(g1_of(in[i].proof.ar)) && g1_on_curve(g1_of(in[i].proof.krs));
+        if (nc) ok = ok && g1_on_curve(g1_of(*in[i].pok));
+        for (u32 k = 0; k < nc; k++) ok = ok && g1_on_curve(g1_of(in[i].commitments[k]));
+        flags[i] = ok ? 0 : 1;
+        if (n_pub) std::memcpy(&scal[i * ns], in[i].public_inputs, (size_t)n_pub * sizeof(mi_fr));
+        if (nc) std::memcpy(&scal[i * ns + n_pub], in[i].commitment_values, (size_t)nc * sizeof(mi_fr));
+    }
+    // ---- workspace: scalars | P | Q | Miller values | flags | verdicts
+    const size_t off_p = up256((size_t)n * ns * sizeof(mi_fr)), off_q = off_p + up256(n * np * sizeof(G1Aff));
+    const size_t off_ml = off_q + up256(n * np * sizeof(G2Aff)), off_fl = off_ml + up256(n * np * sizeof(Fp12));
+    const size_t off_vd = off_fl + up256(n), total = off_vd + up256(n);
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], total));
+    char *ws = (char *)ctx->ws[WS_VERIFY].p;
+    // ---- kSum: the scalar part through the G1 MSM over the resident K[1..], the rest on the host
+    std::vector<G1Aff> P(n * np);
+    std::vector<G2Aff> Q(n * np);
+    if (ns) MI_CHECK_HIP(ctx, hipMemcpyAsync(ws, scal.data(), scal.size() * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->stream));
+    for (size_t i = 0; i < n; i++) {
+        G1X acc = G1X::from_affine(vk->k[0]);
+        if (ns) {
+            mi_g1_jac j;
+            MI_TRY(mi_msm_g1_dev(ctx, (const mi_g1_affine *)vk->k_dev, (const mi_fr *)ws + i * ns, ns, 0, &j));
+            Fp jz;
+            std::memcpy(&jz, &j.z, sizeof(jz));
+            if (!jz.is_zero()) {   // normalised: Z = 1
+                G1Aff a;
+                std::memcpy(&a, &j, sizeof(a));
+                xyzz_madd(acc, a, false);
+            }
+        }
+        for (u32 k = 0; k < nc; k++) xyzz_madd(acc, g1_of(in[i].commitments[k]), false);
+        G1Aff *p = &P[i * np];
+        G2Aff *q = &Q[i * np];
+        p[0] = g1_of(in[i].proof.ar);              q[0] = g2_of(in[i].proof.bs);
+        p[1] = g1_neg(xyzz_to_affine(acc));        q[1] = vk->gamma2;
+        p[2] = g1_neg(g1_of(in[i].proof.krs));     q[2] = vk->delta2;
+        if (nc) {
+            p[3] = g1_of(*in[i].pok);              q[3] = g2_of(vk->ped[0].g);
+            Fr ch = Fr::one(), pw = Fr::one();
+            if (nc > 1) std::memcpy(&ch, in[i].fold_challenge, sizeof(ch));
+            for (u32 k = 0; k < nc; k++) {
+                const G1Aff c = g1_of(in[i].commitments[k]);
+                p[4 + k] = k ? xyzz_to_affine(xyzz_mul_256(G1X::from_affine(c), fe_from_mont(pw).l)) : c;   // c^0 = 1
+                q[4 + k] = g2_of(vk->ped[k].g_sigma_neg);
+                pw = pw * ch;
+            }
+        }
+    }
+    // ---- device: Bs check, Miller loops, judgement
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_p, P.data(), P.size() * sizeof(G1Aff), hipMemcpyHostToDevice, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_q, Q.data(), Q.size() * sizeof(G2Aff), hipMemcpyHostToDevice, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_verify_g2_check, dim3(grid64(n)), dim3(64), 0, ctx->stream, (const G2Aff *)(ws + off_q), np, (uint8_t *)(ws + off_fl), n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    MI_TRY(pairing_enqueue(ctx, (const G1Aff *)(ws + off_p), (const G2Aff *)(ws + off_q), n * np, (Fp12 *)(ws + off_ml), false));
+    hipLaunchKernelGGL(k_verify_judge, dim3(grid64(n)), dim3(64), 0, ctx->stream, (const Fp12 *)(ws + off_ml), np, vk->e_alpha_beta_dev,
+                       (const uint8_t *)(ws + off_fl), (uint8_t *)(ws + off_vd), n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(verdicts, ws + off_vd, n, hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MI_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+int32_t mi_vk_load(mi_ctx *ctx, const mi_vk_desc *d, mi_vk **out) {
+    if (!ctx) return MI_EINVAL;
+    if (!d || !out) MI_FAIL(ctx, MI_EINVAL, "vk load: null descriptor or output pointer");
+    *out = nullptr;
+    if (!d->k) MI_FAIL(ctx, MI_EINVAL, "vk load: k is null");
+    if (d->nb_public == 0) MI_FAIL(ctx, MI_EINVAL, "vk load: nb_public is 0 (it counts the ONE wire)");
+    if (d->n_commitments > MI_PK_RAW_MAX_COMMITMENTS) MI_FAIL(ctx, MI_EINVAL, "vk load: n_commitments above MI_PK_RAW_MAX_COMMITMENTS");
+    if (d->n_k != (uint64_t)d->nb_public + d->n_commitments) MI_FAIL(ctx, MI_EINVAL, "vk load: n_k is not nb_public + n_commitments");
+    if (d->n_commitments && !d->ped) MI_FAIL(ctx, MI_EINVAL, "vk load: ped is null");
+    const G1Aff alpha = g1_of(d->alpha1);
+    const G2Aff beta = g2_of(d->beta2), gamma = g2_of(d->gamma2), delta = g2_of(d->delta2);
+    if (!g1_on_curve(alpha)) MI_FAIL(ctx, MI_EINVAL, "vk load: alpha1 is not on the curve");
+    if (!g2_in_subgroup(&beta)) MI_FAIL(ctx, MI_EINVAL, "vk load: beta2 is not in the r-torsion of the twist");
+    if (gamma.is_inf() || !g2_in_subgroup(&gamma)) MI_FAIL(ctx, MI_EINVAL, "vk load: gamma2 is infinity or not in the r-torsion of the twist");
+    if (delta.is_inf() || !g2_in_subgroup(&delta)) MI_FAIL(ctx, MI_EINVAL, "vk load: delta2 is infinity or not in the r-torsion of the twist");
+    for (uint64_t i = 0; i < d->n_k; i++)
+        if (!g1_on_curve(g1_of(d->k[i]))) MI_FAIL(ctx, MI_EINVAL, "vk load: k[" + std::to_string(i) + "] is not on the curve");
+    for (uint32_t k = 0; k < d->n_commitments; k++) {
+        const G2Aff g = g2_of(d->ped[k].g), gs = g2_of(d->ped[k].g_sigma_neg);
+        if (std::memcmp(&d->ped[k].g, &d->ped[0].g, sizeof(mi_g2_affine)) != 0) MI_FAIL(ctx, MI_EINVAL, "vk load: the Pedersen keys do not share one G");
+        if (g.is_inf() || !g2_in_subgroup(&g) || !g2_in_subgroup(&gs))
+            MI_FAIL(ctx, MI_EINVAL, "vk load: ped[" + std::to_string(k) + "] is not in the r-torsion of the twist");
+    }
+    mi_vk *vk = new (std::nothrow) mi_vk;
+    if (!vk) MI_FAIL(ctx, MI_ENOMEM, "vk load: out of host memory");
+    vk->alpha1 = alpha; vk->beta2 = beta; vk->gamma2 = gamma; vk->delta2 = delta;
+    vk->nb_public = d->nb_public; vk->n_commitments = d->n_commitments;
+    vk->k.resize(d->n_k);
+    std::memcpy(vk->k.data(), d->k, d->n_k * sizeof(G1Aff));
+    if (d->n_commitments) vk->ped.assign(d->ped, d->ped + d->n_commitments);
+    auto body = [&]() -> int32_t {
+        const size_t nb = (d->n_k - 1) * sizeof(G1Aff);
+        MI_CHECK_HIP(ctx, hipMalloc((void **)&vk->k_dev, nb + 64));
+        MI_CHECK_HIP(ctx, hipMalloc((void **)&vk->e_alpha_beta_dev, sizeof(Fp12)));
+        if (nb) MI_CHECK_HIP(ctx, hipMemcpyAsync(vk->k_dev, vk->k.data() + 1, nb, hipMemcpyHostToDevice, ctx->stream));
+        MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], 512));
+        char *ws = (char *)ctx->ws[WS_VERIFY].p;
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ws, &alpha, sizeof(alpha), hipMemcpyHostToDevice, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + 256, &beta, sizeof(beta), hipMemcpyHostToDevice, ctx->stream));
+        MI_TRY(pairing_enqueue(ctx, (const G1Aff *)ws, (const G2Aff *)(ws + 256), 1, vk->e_alpha_beta_dev, true));
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return MI_OK;
+    };
+    const int32_t rc = body();
+    if (rc != MI_OK) {
+        if (vk->k_dev) (void)hipFree(vk->k_dev);
+        if (vk->e_alpha_beta_dev) (void)hipFree(vk->e_alpha_beta_dev);
+        delete vk;
+        return rc;
+    }
+    *out = vk;
+    return MI_OK;
+}
+
+int32_t mi_vk_free(mi_ctx *ctx, mi_vk *vk) {
+    if (!ctx) return MI_EINVAL;
+    if (!vk) return MI_OK;
+    hipError_t e1 = vk->k_dev ? hipFree(vk->k_dev) : hipSuccess, e2 = vk->e_alpha_beta_dev ? hipFree(vk->e_alpha_beta_dev) : hipSuccess;
+    delete vk;
+    MI_CHECK_HIP(ctx, e1);
+    MI_CHECK_HIP(ctx, e2);
+    return MI_OK;
+}
+
+int32_t mi_pedersen_vk_make(mi_ctx *ctx, const mi_fr *sigma, uint32_t n, mi_pedersen_vk *out) {
+    if (!ctx) return MI_EINVAL;
+    if ((!sigma || !out) && n) MI_FAIL(ctx, MI_EINVAL, "pedersen vk: null sigma or output pointer");
+    if (!n) return MI_OK;
+    const G2Aff gen{fp12c_g2gen_x(), fp12c_g2gen_y()};
+    mi_g2_affine g;
+    std::memcpy(&g, &gen, sizeof(g));
+    std::vector<mi_fr> neg(n);
+    std::vector<mi_g2_affine> pts(n);
+    for (uint32_t k = 0; k < n; k++) {
+        Fr s;
+        std::memcpy(&s, &sigma[k], sizeof(s));
+        s = fe_neg(s);
+        std::memcpy(&neg[k], &s, sizeof(s));
+    }
+    MI_TRY(mi_batch_scalar_mul_g2(ctx, &g, neg.data(), n, pts.data()));
+    for (uint32_t k = 0; k < n; k++) { out[k].g = g; out[k].g_sigma_neg = pts[k]; }
+    return MI_OK;
+}
+
+int32_t mi_groth16_verify(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, uint8_t *verdict) {
+    if (ctx && (!in || !verdict)) MI_FAIL(ctx, MI_EINVAL, "verify: null input or verdict pointer");
+    return verify_run(ctx, vk, in, 1, verdict);
+}
+int32_t mi_groth16_verify_batch(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts) {
+    return verify_run(ctx, vk, in, n, verdicts);
+}
+
+// ---------------------------------------------------------------- debug surface (include/mi355x_groth16_debug.h)
+int32_t mi_debug_pairing_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, const mi_g2_affine *q_dev, size_t n, mi_fp *gt_dev, uint32_t flags) {
+    if (!ctx || (flags & ~MI_PAIRING_FINAL_EXP) || ((!p_dev || !q_dev || !gt_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
+    if (!n) return MI_OK;
+    return pairing_enqueue(ctx, (const G1Aff *)p_dev, (const G2Aff *)q_dev, n, (Fp12 *)gt_dev, (flags & MI_PAIRING_FINAL_EXP) != 0);
+}
+int32_t mi_debug_fp12_op_dev(mi_ctx *ctx, int op, mi_fp *z_dev, const mi_fp *x_dev, const mi_fp *y_dev, size_t n) {
+    if (!ctx || op < 0 || op >= F12_OP_END || ((!z_dev || !x_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
+    if (!n) return MI_OK;
+    hipLaunchKernelGGL(k_fp12_op, dim3(grid64(n)), dim3(64), 0, ctx->stream, op, (Fp12 *)z_dev, (const Fp12 *)x_dev, (const Fp12 *)y_dev, n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+}

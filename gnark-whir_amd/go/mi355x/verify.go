@@ -1,0 +1,159 @@
+//go:build mi355x
+
+// groth16.Verify (reilabs/gnark-whir mt.go:497) on the device: include/mi355x_groth16_verify.h.
+//
+// STATUS: SOURCE ONLY, like the rest of the shim (mi355x.go): never compiled here.  The library is hash-free; this file computes what
+// gnark's verify.go computes on the host -- the hash-to-field of every commitment (with the public committed values) and the fold
+// challenge -- and hands the rest to mi_groth16_verify.
+package mi355x
+
+/*
+#include <stdlib.h>
+#include "mi355x_groth16_verify.h"
+*/
+import "C"
+
+import (
+	"errors"
+	"fmt"
+	"runtime"
+	"unsafe"
+
+	"github.com/consensys/gnark-crypto/ecc/bn254"
+	"github.com/consensys/gnark-crypto/ecc/bn254/fr"
+	"github.com/consensys/gnark-crypto/ecc/bn254/fr/hash_to_field"
+	groth16_bn254 "github.com/consensys/gnark/backend/groth16/bn254"
+	"github.com/consensys/gnark/constraint"
+)
+
+// VerifyingKey is gnark's key plus its device-resident handle (mi_vk).
+type VerifyingKey struct {
+	groth16_bn254.VerifyingKey
+	ctx *C.mi_ctx
+	dev *C.mi_vk
+}
+
+// ErrRejected carries the verdict of a rejected proof: MI_VERIFY_PAIRING, MI_VERIFY_PEDERSEN or MI_VERIFY_MALFORMED.
+type ErrRejected struct{ Verdict int }
+
+func (e ErrRejected) Error() string { return fmt.Sprintf("mi355x: proof rejected (verdict %d)", e.Verdict) }
+
+// LoadVerifyingKey uploads vk once (mi_vk_load): every point is validated and e(alpha, beta) is computed there.
+func LoadVerifyingKey(vk *groth16_bn254.VerifyingKey, device int) (*VerifyingKey, error) {
+	out := &VerifyingKey{VerifyingKey: *vk}
+	if rc := C.mi_init(C.int(device), &out.ctx); rc != C.MI_OK {
+		return nil, fmt.Errorf("mi355x: mi_init rc=%d", int(rc))
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	nc := len(vk.PublicAndCommitmentCommitted)
+	ped := make([]C.mi_pedersen_vk, nc)
+	for i := 0; i < nc; i++ {
+		ped[i].g = *(*C.mi_g2_affine)(unsafe.Pointer(&vk.CommitmentKeys[i].G))
+		ped[i].g_sigma_neg = *(*C.mi_g2_affine)(unsafe.Pointer(&vk.CommitmentKeys[i].GSigmaNeg))
+	}
+	var d C.mi_vk_desc
+	d.alpha1 = *(*C.mi_g1_affine)(unsafe.Pointer(&vk.G1.Alpha))
+	d.beta2 = *(*C.mi_g2_affine)(unsafe.Pointer(&vk.G2.Beta))
+	d.gamma2 = *(*C.mi_g2_affine)(unsafe.Pointer(&vk.G2.Gamma))
+	d.delta2 = *(*C.mi_g2_affine)(unsafe.Pointer(&vk.G2.Delta))
+	d.k = g1(&pin, vk.G1.K)
+	d.n_k = C.uint64_t(len(vk.G1.K))
+	d.nb_public = C.uint32_t(len(vk.G1.K) - nc)
+	d.n_commitments = C.uint32_t(nc)
+	if nc > 0 {
+		pin.Pin(&ped[0])
+		d.ped = &ped[0]
+	}
+	if err := status(out.ctx, C.mi_vk_load(out.ctx, &d, &out.dev)); err != nil {
+		C.mi_shutdown(out.ctx)
+		return nil, err
+	}
+	return out, nil
+}
+
+// Close frees the device-resident key and its context.
+func (vk *VerifyingKey) Close() {
+	if vk.dev != nil {
+		C.mi_vk_free(vk.ctx, vk.dev)
+		vk.dev = nil
+	}
+	if vk.ctx != nil {
+		C.mi_shutdown(vk.ctx)
+		vk.ctx = nil
+	}
+}
+
+// Verify replaces groth16.Verify(proof, vk, publicWitness).  publicWitness holds the public inputs without the ONE wire, as
+// witness.Vector() of the public witness does.
+func Verify(vk *VerifyingKey, proof *groth16_bn254.Proof, publicWitness fr.Vector) error {
+	nc := len(vk.PublicAndCommitmentCommitted)
+	if len(proof.Commitments) != nc {
+		return errors.New("mi355x: the proof's commitments do not match the key")
+	}
+	if len(publicWitness) != len(vk.G1.K)-nc-1 {
+		return errors.New("mi355x: wrong number of public inputs")
+	}
+	// verify.go: commitment i is hashed with the public committed values before it (later commitments may commit to earlier ones)
+	values := make([]fr.Element, nc)
+	full := append(fr.Vector{}, publicWitness...)
+	h2f := hash_to_field.New([]byte(constraint.CommitmentDst))
+	maxNb := 0
+	for _, s := range vk.PublicAndCommitmentCommitted {
+		if len(s) > maxNb {
+			maxNb = len(s)
+		}
+	}
+	buf := make([]byte, 0, fr.Bytes*maxNb+bn254.SizeOfG1AffineUncompressed)
+	for i := 0; i < nc; i++ {
+		buf = append(buf[:0], proof.Commitments[i].Marshal()...)
+		for _, j := range vk.PublicAndCommitmentCommitted[i] {
+			b := full[j-1].Bytes()
+			buf = append(buf, b[:]...)
+		}
+		h2f.Write(buf)
+		values[i].SetBytes(h2f.Sum(nil))
+		h2f.Reset()
+		full = append(full, values[i])
+	}
+	var challenge fr.Element
+	if nc > 0 {
+		ser := make([]byte, fr.Bytes*nc)
+		for i := range values {
+			copy(ser[fr.Bytes*i:], values[i].Marshal())
+		}
+		ch, err := fr.Hash(ser, []byte("G16-BSB22"), 1)
+		if err != nil {
+			return err
+		}
+		challenge = ch[0]
+	}
+
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	var in C.mi_verify_input
+	in.proof.ar = *(*C.mi_g1_affine)(unsafe.Pointer(&proof.Ar))
+	in.proof.bs = *(*C.mi_g2_affine)(unsafe.Pointer(&proof.Bs))
+	in.proof.krs = *(*C.mi_g1_affine)(unsafe.Pointer(&proof.Krs))
+	if len(publicWitness) > 0 {
+		pin.Pin(&publicWitness[0])
+		in.public_inputs = (*C.mi_fr)(unsafe.Pointer(&publicWitness[0]))
+	}
+	if nc > 0 {
+		in.commitments = g1(&pin, proof.Commitments)
+		pin.Pin(&proof.CommitmentPok)
+		in.pok = (*C.mi_g1_affine)(unsafe.Pointer(&proof.CommitmentPok))
+		pin.Pin(&values[0])
+		in.commitment_values = (*C.mi_fr)(unsafe.Pointer(&values[0]))
+		pin.Pin(&challenge)
+		in.fold_challenge = (*C.mi_fr)(unsafe.Pointer(&challenge))
+	}
+	var verdict C.uint8_t
+	if err := status(vk.ctx, C.mi_groth16_verify(vk.ctx, vk.dev, &in, &verdict)); err != nil {
+		return err
+	}
+	if verdict != C.MI_VERIFY_OK {
+		return ErrRejected{Verdict: int(verdict)}
+	}
+	return nil
+}

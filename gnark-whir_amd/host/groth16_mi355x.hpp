@@ -20,6 +20,7 @@
 #include "../../include/mi355x_groth16.h"
 #include "../../include/mi355x_groth16_group.h"
 #include "../../include/mi355x_groth16_r1cs.h"
+#include "../../include/mi355x_groth16_verify.h"
 #include "../../include/mi355x_groth16_debug.h"   // (this mirror is the TEST side: generators and knobs)
 
 namespace groth16 {
@@ -205,6 +206,34 @@ inline Proof ProveW(const Context &ctx, const ProvingKey &pk, const ResidentR1CS
     Proof p;
     p.Ar = out.ar; p.Bs = out.bs; p.Krs = out.krs;
     return p;
+}
+// Device-resident verifying key (include/mi355x_groth16_verify.h): validated and e(alpha, beta) computed once, at load.
+class VerifyingKey {
+  public:
+    VerifyingKey(const Context &ctx, const mi_vk_desc &desc) : ctx_(ctx) { ctx_.check(mi_vk_load(ctx_.get(), &desc, &vk_)); }
+    ~VerifyingKey() { if (vk_) mi_vk_free(ctx_.get(), vk_); }
+    VerifyingKey(const VerifyingKey &) = delete;
+    VerifyingKey &operator=(const VerifyingKey &) = delete;
+    mi_vk *get() const { return vk_; }
+
+  private:
+    const Context &ctx_;
+    mi_vk *vk_ = nullptr;
+};
+// groth16.Verify: the verdict (MI_VERIFY_OK, _PAIRING, _PEDERSEN, _MALFORMED); a rejected proof is a verdict, not an exception.
+// publicInputs: without the ONE wire; commitmentValues (the hash-to-field of each commitment) and foldChallenge come from the caller.
+inline uint8_t Verify(const Context &ctx, const VerifyingKey &vk, const Proof &proof, const std::vector<mi_fr> &publicInputs,
+                      const std::vector<mi_fr> &commitmentValues = {}, const mi_fr *foldChallenge = nullptr) {
+    mi_verify_input in{};
+    in.proof = mi_proof_out{proof.Ar, proof.Bs, proof.Krs};
+    in.commitments = proof.Commitments.empty() ? nullptr : proof.Commitments.data();
+    in.pok = &proof.CommitmentPok;
+    in.public_inputs = publicInputs.empty() ? nullptr : publicInputs.data();
+    in.commitment_values = commitmentValues.empty() ? nullptr : commitmentValues.data();
+    in.fold_challenge = foldChallenge;
+    uint8_t verdict = MI_VERIFY_MALFORMED;
+    ctx.check(mi_groth16_verify(ctx.get(), vk.get(), &in, &verdict));
+    return verdict;
 }
 // fft.Domain: FFT / FFTInverse with fft.DIF / fft.DIT and fft.OnCoset()
 enum Decimation { DIF = 0, DIT = 1 };

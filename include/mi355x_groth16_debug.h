@@ -46,6 +46,20 @@ int32_t mi_debug_limb29_op_dev(mi_ctx *ctx, int op, void *out_dev, const void *i
 #define MI_LAZY_IN_WORDS 24
 #define MI_LAZY_OUT_WORDS 16
 int32_t mi_debug_lazy_op_dev(mi_ctx *ctx, int op, void *out_dev, const void *in_dev, size_t n);
+/* the pairing behind mi355x_groth16_verify.h (csrc/fp12.cuh, pairing.cuh), one record per lane; the host build of the tests
+ * (tests/emu/emu_pairing.cpp) runs the same bodies.  An Fp12 / GT record is 12 x mi_fp in the tower order C0.B0.A0, C0.B0.A1, C0.B1.A0,
+ * ... C1.B2.A1 (Fp2 = Fp[u]/(u^2+1), Fp6 = Fp2[v]/(v^3 - (9+u)), Fp12 = Fp6[w]/(w^2 - v)).
+ * mi_debug_pairing_dev: gt_dev[i] = the Miller value of (p_dev[i], q_dev[i]) (flags = 0) or the pairing value f^d' (MI_PAIRING_FINAL_EXP),
+ * d' = s (p^12 - 1) / r with s = 2 x0 (6 x0^2 + 3 x0 + 1) as csrc/pairing.cuh states it; 1 when either point is infinity.  The points must
+ * lie on their curves, q in the r-torsion (not checked here).
+ * mi_debug_fp12_op_dev: z[i] = op(x[i], y[i]); op as in csrc/pairing_ops.cuh: 0 mul, 1 sqr, 2 inv, 3 / 4 / 5 Frobenius p / p^2 / p^3,
+ * 6 cyclotomic square, 7 conjugate, 8 easy part, 9 final exponentiation, 10 product by the sparse line (y.C0.B0, y.C1.B0, y.C1.B1),
+ * 11 add, 12 sub, 13 / 14 / 15 the Fp6 product / square / inverse on both halves.  y_dev may be NULL for the one-operand ops.
+ * MI_EINVAL for an unknown op or flag, null buffers or n > 2^24. */
+#define MI_PAIRING_FINAL_EXP 1u
+#define MI_FP12_WORDS 96
+int32_t mi_debug_pairing_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, const mi_g2_affine *q_dev, size_t n, mi_fp *gt_dev, uint32_t flags);
+int32_t mi_debug_fp12_op_dev(mi_ctx *ctx, int op, mi_fp *z_dev, const mi_fp *x_dev, const mi_fp *y_dev, size_t n);
 /* random-gather throughput probe: n_threads lanes each chain `iters` dependent 64-byte gathers from a table of n_entries
  * (a power of two) 64-byte entries; scratch: 1 KiB.  The ceiling the level-1 bucket accumulation's point gathers run against. */
 int32_t mi_bench_gather_dev(mi_ctx *ctx, const void *table_dev, size_t n_entries, size_t n_threads, uint32_t iters,

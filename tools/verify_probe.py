@@ -1,0 +1,87 @@
+"""Times groth16.Verify on the device (mi_groth16_verify[_batch], csrc/verify.hip).
+
+    python tools/verify_probe.py [--write profiles/verify.txt] [--batches 64,1024,16384] [--runs 5]
+
+A solvable circuit of 1000 constraints (domain 2^10, 4 public inputs, one BSB22 commitment; tests/r1cs_cases.py), its key from
+mi_groth16_setup, one proof through the prover pool.  After a warm-up call, the median wall time of `--runs` calls of one verification
+and of batches of the given sizes (the same proof repeated: the arithmetic does not depend on the data).  The times are those of the
+whole call, host part included (the G1 checks, one synchronous MSM per proof for kSum, the folds): the library has no per-phase device
+timers for Verify yet.  There is no baseline: no CPU pairing exists in this repository and gnark cannot be built here, so no rate is
+claimed -- the figures are recorded, nothing more."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+import numpy as np  # noqa: E402
+import cref  # noqa: E402
+import dlog_keys as D  # noqa: E402
+import setup_cases as S  # noqa: E402
+import r1cs_cases as RC  # noqa: E402
+from gpu_common import load_binding  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--write")
+    ap.add_argument("--batches", default="64,1024,16384")
+    ap.add_argument("--runs", type=int, default=5)
+    args = ap.parse_args()
+    B = load_binding()
+    ctx = B.Context(0)
+    n, nab, nb_public = 1000, 400, 5
+    r1cs = RC.skewed_r1cs(n, nab, nb_public, 11, long_lens=(16, 17, 64), commitments=1, n_committed=32)
+    r1cs["nb_wires"] = nab + n
+    r1cs["C"] = (np.arange(n + 1, dtype=np.uint64), (nab + np.arange(n)).astype(np.uint32), np.ones(n, np.uint32))
+    W = np.zeros((r1cs["nb_wires"], 4), np.uint64)
+    W[:nab] = RC.witness(nab, 12)
+    a, b = RC.eval_rows(r1cs, "A", W), RC.eval_rows(r1cs, "B", W)
+    W[nab:] = D._op(2, a, b)
+    td = S.synth_trapdoor(13, n_sigma=1)
+    r, s = cref.gen_scalars(2, 14, 0)
+    ch = cref.gen_scalars(1, 15, 0)[0]
+    pkh, peds, vk = ctx.setup(r1cs, td)
+    vals = np.ascontiguousarray(W[r1cs["commitments"][0][0]])
+    pool = B.Prover(0, 1)
+    try:
+        cm = pool.commit(peds[0], vals).reshape(1, 8)
+        proof, _ = pool.wait(pool.submit_bsb22(pkh, W, a, b, None, r, s, [(peds[0], vals)], ch))
+    finally:
+        pool.close()
+    vkh = ctx.vk_load(vk, nb_public, ctx.pedersen_vk_make(np.stack(td["sigma"])))
+    inp = {"raw": proof["raw"], "public_inputs": np.ascontiguousarray(W[1:nb_public]), "commitments": cm,
+           "pok": np.ascontiguousarray(proof["pok"]).reshape(8), "fold_challenge": ch,
+           "commitment_values": np.ascontiguousarray(W[[r1cs["commitments"][0][1]]])}
+    assert vkh.verify(inp) == B.VERIFY_OK
+    lines = [f"groth16.Verify on the device: 1000 constraints (domain 2^10), {nb_public - 1} public inputs, 1 commitment (5 pairs per proof)",
+             f"median wall time of {args.runs} calls after one warm-up call, host part included; no baseline exists, no rate is claimed"]
+
+    def timed(fn):
+        fn()
+        ts = []
+        for _ in range(args.runs):
+            t = time.perf_counter(); fn(); ts.append((time.perf_counter() - t) * 1e3)
+        return statistics.median(ts)
+
+    lines.append(f"one verification      {timed(lambda: vkh.verify(inp)):10.3f} ms")
+    for nb in [int(x) for x in args.batches.split(",") if x]:
+        arr, keep = vkh._inputs([inp] * nb)
+        out = np.zeros(nb, np.uint8)
+        call = lambda: ctx._ck(ctx.lib.mi_groth16_verify_batch(ctx.h, vkh.h, arr, nb, out.ctypes.data_as(B.C.c_void_p)))
+        ms = timed(call)
+        assert not out.any()
+        lines.append(f"batch of {nb:6d}       {ms:10.3f} ms   {ms / nb:8.4f} ms per proof")
+    print("\n".join(lines))
+    if args.write:
+        with open(args.write, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    vkh.free(); ctx.pedersen_pk_free(peds[0]); ctx.pk_free(pkh); ctx.close()
+
+
+if __name__ == "__main__":
+    main()
