@@ -124,11 +124,24 @@ MI_OOL void pairing_final_exp(Fp12 *z, const Fp12 *f) {
 }
 
 // ---------------------------------------------------------------- the checks a verifier makes on points it did not compute
+// The eight words of x, read as one 256-bit integer, are below the modulus.  Every comparison in this library is one of words, and the
+// arithmetic maps x and x + p (2p < 2^256) to the same result: a caller's value that is not reduced would be a SECOND encoding of the
+// same element (and (p, p) a second infinity).  A verifier accepts exactly one encoding, so it asks this of every word it is given.
+template <class P>
+MI_HD bool fe_is_reduced(const Fe<P> &x) {
+    Fe<P> t;
+    return fe_sub_raw(t, x, Fe<P>::modulus()) != 0;   // x - p borrows
+}
+MI_HD bool g1_reduced(const G1Aff &p) { return fe_is_reduced(p.x) && fe_is_reduced(p.y); }
+MI_HD bool g2_reduced(const G2Aff &q) { return fe_is_reduced(q.x.a0) && fe_is_reduced(q.x.a1) && fe_is_reduced(q.y.a0) && fe_is_reduced(q.y.a1); }
+// host callers only (verify.hip, the host build of the tests).  Coordinates that are not reduced are no point of the curve: decided
+// before any arithmetic touches them
 MI_HD bool g1_on_curve(const G1Aff &p) {   // infinity counts as a point of the curve
+    if (!g1_reduced(p)) return false;
     if (p.is_inf()) return true;
     return fe_sqr(p.y) == fe_sqr(p.x) * p.x + curve_b((const Fp *)0);
 }
-MI_HD bool g2_on_twist(const G2Aff &q) {
+MI_HD bool g2_on_twist(const G2Aff &q) {   // of REDUCED coordinates (the device runs this one; the host asks g2_reduced first)
     if (q.is_inf()) return true;
     return fe_sqr(q.y) == fe_sqr(q.x) * q.x + fp12c_twist_b();
 }

@@ -1,5 +1,6 @@
 // What the verifier's kernels (verify.hip) and the host build of the tests (tests/emu/emu_pairing.cpp, overflow traps on) both run, one
-// record per lane / per call: the Fp12 operations of mi_debug_fp12_op_dev, and the judgement of one proof from its Miller values.
+// record per lane / per call: the Fp12 operations of mi_debug_fp12_op_dev, the judgement of one proof from its Miller values, and the
+// host half of one proof (its range and curve checks, kSum, the folds, the layout of its pairs), which verify.hip's host code runs.
 #pragma once
 #include "pairing.cuh"
 
@@ -54,6 +55,66 @@ MI_HD int fp12_op(int op, Fp12 *z, const Fp12 *x, const Fp12 *y) {
 // prod ml[0..3)^d' == e(alpha, beta)^s (1 when it fails), then the Pedersen one prod ml[3..)^d' == 1 (2), else 0.  n_ped = 0 or
 // n_commitments + 1; it is the same for every proof of a key, so a wave does not diverge here.
 #define MI_VERIFY_GROTH_PAIRS 3
+
+// ---------------------------------------------------------------- the host half of one proof (verify.hip's verify_run; the host build
+// of the tests runs the same two functions).  The layouts are those of include/mi355x_groth16_verify.h: G1Aff = mi_g1_affine,
+// G2Aff = mi_g2_affine, Fr = mi_fr, two G2Aff per mi_pedersen_vk.
+struct VerifyKeyRef {
+    const G1Aff *k0;                 // K[0]; K[1..] are the bases of the MSM, which the caller runs
+    const G2Aff *gamma2, *delta2;
+    const G2Aff *ped;                // 2 n_commitments points: G, GSigmaNeg of each commitment
+    u32 n_pub, n_commitments;        // n_pub = nb_public - 1: without the ONE wire
+};
+struct VerifyProofRef {
+    const G1Aff *ar;
+    const G2Aff *bs;
+    const G1Aff *krs, *commitments, *pok;
+    const Fr *public_inputs, *commitment_values, *fold_challenge;
+};
+MI_HD u32 verify_pairs_per_proof(u32 n_commitments) { return MI_VERIFY_GROTH_PAIRS + (n_commitments ? n_commitments + 1 : 0); }
+MI_HD G1Aff g1_aff_neg(const G1Aff &p) { return G1Aff{p.x, fe_neg(p.y)}; }
+
+// What the host can say about a proof before any arithmetic: every coordinate below p, every scalar below r (fe_is_reduced), every G1
+// point on the curve.  (Bs on the twist and in its r-torsion is the device's question, k_verify_g2_check.)  fold_challenge is read, and
+// therefore checked, with more than one commitment only.  A proof that fails here is MI_VERIFY_MALFORMED and none of its words reaches
+// the MSM, the group law or a Miller loop.
+inline bool verify_well_formed(const VerifyKeyRef &vk, const VerifyProofRef &in) {
+    const u32 nc = vk.n_commitments;
+    bool ok = g1_on_curve(*in.ar) && g1_on_curve(*in.krs) && g2_reduced(*in.bs);
+    if (nc) ok = ok && g1_on_curve(*in.pok);
+    for (u32 k = 0; k < nc; k++) ok = ok && g1_on_curve(in.commitments[k]) && fe_is_reduced(in.commitment_values[k]);
+    for (u32 i = 0; i < vk.n_pub; i++) ok = ok && fe_is_reduced(in.public_inputs[i]);
+    if (nc > 1) ok = ok && fe_is_reduced(*in.fold_challenge);
+    return ok;
+}
+// The pairs of one proof, p[] and q[] of verify_pairs_per_proof entries in the order below.  msm = sum_i public_inputs[i] K[1 + i] +
+// sum_k commitment_values[k] K[nb_public + k], affine ((0, 0) = infinity, also when there is no scalar at all).  A proof that is not
+// well formed gets pairs of infinities: its verdict is decided, and its words stay out of the arithmetic.
+inline void verify_assemble(const VerifyKeyRef &vk, const VerifyProofRef &in, bool well_formed, const G1Aff &msm, G1Aff *p, G2Aff *q) {
+    const u32 nc = vk.n_commitments, np = verify_pairs_per_proof(nc);
+    if (!well_formed) {
+        for (u32 j = 0; j < np; j++) { p[j] = G1Aff{Fp::zero(), Fp::zero()}; q[j] = G2Aff{Fp2::zero(), Fp2::zero()}; }
+        return;
+    }
+    G1X acc = G1X::from_affine(*vk.k0);
+    xyzz_madd(acc, msm, false);
+    for (u32 k = 0; k < nc; k++) xyzz_madd(acc, in.commitments[k], false);
+    p[0] = *in.ar;                            q[0] = *in.bs;
+    p[1] = g1_aff_neg(xyzz_to_affine(acc));   q[1] = *vk.gamma2;
+    p[2] = g1_aff_neg(*in.krs);               q[2] = *vk.delta2;
+    if (nc) {
+        p[3] = *in.pok;                       q[3] = vk.ped[0];
+        Fr ch = Fr::one(), pw = Fr::one();
+        if (nc > 1) ch = *in.fold_challenge;
+        for (u32 k = 0; k < nc; k++) {
+            const G1Aff c = in.commitments[k];
+            p[4 + k] = k ? xyzz_to_affine(xyzz_mul_256(G1X::from_affine(c), fe_from_mont(pw).l)) : c;   // c^0 = 1
+            q[4 + k] = vk.ped[2 * k + 1];
+            pw = pw * ch;
+        }
+    }
+}
+
 MI_OOL uint8_t verify_judge(const Fp12 *ml, u32 n_ped, const Fp12 *e_alpha_beta, bool malformed) {
     Fp12 f;
     fp12_mul(&f, &ml[0], &ml[1]);

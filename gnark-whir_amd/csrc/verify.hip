@@ -2,8 +2,10 @@
 // device-resident verifying key, and the two debug entry points over the same arithmetic (fp12.cuh, pairing.cuh, pairing_ops.cuh).
 //
 // One batch, every launch on ctx->stream:
-//   host      the curve checks of the G1 points, the scalars of kSum; per proof one G1 MSM over the key's resident K[1..] (msm.hip), then
-//             kSum = K[0] + that + sum C_k and the folded commitments c^k C_k; the pairs of every proof laid out as pairing_ops.cuh says
+//   host      the range checks of every word and the curve checks of the G1 points (verify_well_formed: a proof that fails them is
+//             malformed and goes no further), the scalars of kSum; per proof one G1 MSM over the key's resident K[1..] (msm.hip), then
+//             kSum = K[0] + that + sum C_k, the folded commitments c^k C_k and the layout of the pairs (verify_assemble); both functions
+//             live in pairing_ops.cuh, where the host build of the tests runs them too
 //   k_verify_g2_check   one lane per proof: Bs on the twist and in its r-torsion -> the malformed flag
 //   k_pairing_miller    one lane per (proof, pair): a Miller loop, 384 B out
 //   k_verify_judge      one lane per proof: the products of its Miller values, the final exponentiations, the comparisons -> a verdict byte
@@ -12,6 +14,7 @@
 #include "../../include/mi355x_groth16_verify.h"
 #include "pairing_ops.cuh"
 #include <cstring>
+#include <string>
 #include <vector>
 
 struct mi_vk {
@@ -71,7 +74,8 @@ inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 G1Aff g1_of(const mi_g1_affine &p) { G1Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
 G2Aff g2_of(const mi_g2_affine &p) { G2Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
-G1Aff g1_neg(const G1Aff &p) { return G1Aff{p.x, fe_neg(p.y)}; }
+static_assert(sizeof(mi_pedersen_vk) == 2 * sizeof(G2Aff) && sizeof(mi_g1_affine) == sizeof(G1Aff) && sizeof(mi_fr) == sizeof(Fr),
+              "pairing_ops.cuh reads the header's records as G1Aff / G2Aff / Fr");
 
 // Miller values of n pairs already on the device, then (final) f^d' in place
 int32_t pairing_enqueue(mi_ctx *ctx, const G1Aff *p_dev, const G2Aff *q_dev, size_t n, Fp12 *gt_dev, bool final_exp) {
@@ -89,7 +93,7 @@ int32_t verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size
     if (!vk || (!in && n) || (!verdicts && n)) MI_FAIL(ctx, MI_EINVAL, "verify: null vk, input or verdict pointer");
     if (n > ((size_t)1 << 24)) MI_FAIL(ctx, MI_EINVAL, "verify: more than 2^24 proofs in one batch");
     const u32 nc = vk->n_commitments, n_pub = vk->nb_public - 1, ns = n_pub + nc;
-    const u32 n_ped = nc ? nc + 1 : 0, np = MI_VERIFY_GROTH_PAIRS + n_ped;
+    const u32 np = verify_pairs_per_proof(nc);
     for (size_t i = 0; i < n; i++) {
         if (n_pub && !in[i].public_inputs) MI_FAIL(ctx, MI_EINVAL, "verify: public_inputs is null");
         if (nc && (!in[i].commitments || !in[i].pok || !in[i].commitment_values)) MI_FAIL(ctx, MI_EINVAL, "verify: commitments, pok or commitment_values is null");
@@ -97,14 +101,18 @@ int32_t verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size
     }
     if (!n) return MI_OK;
 
-    // ---- host: flags, scalars
+    // ---- host: flags (range and curve checks, pairing_ops.cuh), scalars
+    const VerifyKeyRef kref{&vk->k[0], &vk->gamma2, &vk->delta2, (const G2Aff *)vk->ped.data(), n_pub, nc};
+    auto proof_ref = [&](size_t i) {
+        return VerifyProofRef{(const G1Aff *)&in[i].proof.ar, (const G2Aff *)&in[i].proof.bs, (const G1Aff *)&in[i].proof.krs,
+                              (const G1Aff *)in[i].commitments, (const G1Aff *)in[i].pok, (const Fr *)in[i].public_inputs,
+                              (const Fr *)in[i].commitment_values, (const Fr *)in[i].fold_challenge};
+    };
     std::vector<uint8_t> flags(n, 0);
     std::vector<mi_fr> scal((size_t)n * ns);
     for (size_t i = 0; i < n; i++) {
-        bool ok = g1_on_curve(g1_of(in[i].proof.ar)) && g1_on_curve(g1_of(in[i].proof.krs));
-        if (nc) ok = ok && g1_on_curve(g1_of(*in[i].pok));
-        for (u32 k = 0; k < nc; k++) ok = ok && g1_on_curve(g1_of(in[i].commitments[k]));
-        flags[i] = ok ? 0 : 1;
+        flags[i] = verify_well_formed(kref, proof_ref(i)) ? 0 : 1;
+        if (flags[i]) continue;   // its scalars stay zero and are never read: no MSM runs for a malformed proof
         if (n_pub) std::memcpy(&scal[i * ns], in[i].public_inputs, (size_t)n_pub * sizeof(mi_fr));
         if (nc) std::memcpy(&scal[i * ns + n_pub], in[i].commitment_values, (size_t)nc * sizeof(mi_fr));
     }
@@ -119,35 +127,15 @@ int32_t verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size
     std::vector<G2Aff> Q(n * np);
     if (ns) MI_CHECK_HIP(ctx, hipMemcpyAsync(ws, scal.data(), scal.size() * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->stream));
     for (size_t i = 0; i < n; i++) {
-        G1X acc = G1X::from_affine(vk->k[0]);
-        if (ns) {
+        G1Aff msm{Fp::zero(), Fp::zero()};
+        if (ns && !flags[i]) {
             mi_g1_jac j;
             MI_TRY(mi_msm_g1_dev(ctx, (const mi_g1_affine *)vk->k_dev, (const mi_fr *)ws + i * ns, ns, 0, &j));
             Fp jz;
             std::memcpy(&jz, &j.z, sizeof(jz));
-            if (!jz.is_zero()) {   // normalised: Z = 1
-                G1Aff a;
-                std::memcpy(&a, &j, sizeof(a));
-                xyzz_madd(acc, a, false);
-            }
+            if (!jz.is_zero()) std::memcpy(&msm, &j, sizeof(msm));   // normalised: Z = 1
         }
-        for (u32 k = 0; k < nc; k++) xyzz_madd(acc, g1_of(in[i].commitments[k]), false);
-        G1Aff *p = &P[i * np];
-        G2Aff *q = &Q[i * np];
-        p[0] = g1_of(in[i].proof.ar);              q[0] = g2_of(in[i].proof.bs);
-        p[1] = g1_neg(xyzz_to_affine(acc));        q[1] = vk->gamma2;
-        p[2] = g1_neg(g1_of(in[i].proof.krs));     q[2] = vk->delta2;
-        if (nc) {
-            p[3] = g1_of(*in[i].pok);              q[3] = g2_of(vk->ped[0].g);
-            Fr ch = Fr::one(), pw = Fr::one();
-            if (nc > 1) std::memcpy(&ch, in[i].fold_challenge, sizeof(ch));
-            for (u32 k = 0; k < nc; k++) {
-                const G1Aff c = g1_of(in[i].commitments[k]);
-                p[4 + k] = k ? xyzz_to_affine(xyzz_mul_256(G1X::from_affine(c), fe_from_mont(pw).l)) : c;   // c^0 = 1
-                q[4 + k] = g2_of(vk->ped[k].g_sigma_neg);
-                pw = pw * ch;
-            }
-        }
+        verify_assemble(kref, proof_ref(i), !flags[i], msm, &P[i * np], &Q[i * np]);
     }
     // ---- device: Bs check, Miller loops, judgement
     MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_p, P.data(), P.size() * sizeof(G1Aff), hipMemcpyHostToDevice, ctx->stream));
@@ -179,6 +167,18 @@ int32_t mi_vk_load(mi_ctx *ctx, const mi_vk_desc *d, mi_vk **out) {
     if (d->n_commitments && !d->ped) MI_FAIL(ctx, MI_EINVAL, "vk load: ped is null");
     const G1Aff alpha = g1_of(d->alpha1);
     const G2Aff beta = g2_of(d->beta2), gamma = g2_of(d->gamma2), delta = g2_of(d->delta2);
+    // every coordinate below p, before any arithmetic sees it: one encoding per element (pairing.cuh, fe_is_reduced)
+    const std::string not_reduced = " has a coordinate that is not below p";
+    if (!g1_reduced(alpha)) MI_FAIL(ctx, MI_EINVAL, "vk load: alpha1" + not_reduced);
+    if (!g2_reduced(beta)) MI_FAIL(ctx, MI_EINVAL, "vk load: beta2" + not_reduced);
+    if (!g2_reduced(gamma)) MI_FAIL(ctx, MI_EINVAL, "vk load: gamma2" + not_reduced);
+    if (!g2_reduced(delta)) MI_FAIL(ctx, MI_EINVAL, "vk load: delta2" + not_reduced);
+    for (uint64_t i = 0; i < d->n_k; i++)
+        if (!g1_reduced(g1_of(d->k[i]))) MI_FAIL(ctx, MI_EINVAL, "vk load: k[" + std::to_string(i) + "]" + not_reduced);
+    for (uint32_t k = 0; k < d->n_commitments; k++) {
+        if (!g2_reduced(g2_of(d->ped[k].g))) MI_FAIL(ctx, MI_EINVAL, "vk load: ped[" + std::to_string(k) + "].g" + not_reduced);
+        if (!g2_reduced(g2_of(d->ped[k].g_sigma_neg))) MI_FAIL(ctx, MI_EINVAL, "vk load: ped[" + std::to_string(k) + "].g_sigma_neg" + not_reduced);
+    }
     if (!g1_on_curve(alpha)) MI_FAIL(ctx, MI_EINVAL, "vk load: alpha1 is not on the curve");
     if (!g2_in_subgroup(&beta)) MI_FAIL(ctx, MI_EINVAL, "vk load: beta2 is not in the r-torsion of the twist");
     if (gamma.is_inf() || !g2_in_subgroup(&gamma)) MI_FAIL(ctx, MI_EINVAL, "vk load: gamma2 is infinity or not in the r-torsion of the twist");

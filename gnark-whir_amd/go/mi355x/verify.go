@@ -34,6 +34,9 @@ type VerifyingKey struct {
 }
 
 // ErrRejected carries the verdict of a rejected proof: MI_VERIFY_PAIRING, MI_VERIFY_PEDERSEN or MI_VERIFY_MALFORMED.
+// MI_VERIFY_MALFORMED covers words that are not reduced as well (a coordinate not below p, a scalar not below r: ONE ENCODING in the
+// header).  gnark-crypto's fp.Element / fr.Element are always reduced, so values that went through its decoders cannot trigger it;
+// words written into an Element from outside can.  mi_vk_load refuses such a coordinate in the key with MI_EINVAL.
 type ErrRejected struct{ Verdict int }
 
 func (e ErrRejected) Error() string { return fmt.Sprintf("mi355x: proof rejected (verdict %d)", e.Verdict) }

@@ -222,6 +222,8 @@ class VerifyingKey {
 };
 // groth16.Verify: the verdict (MI_VERIFY_OK, _PAIRING, _PEDERSEN, _MALFORMED); a rejected proof is a verdict, not an exception.
 // publicInputs: without the ONE wire; commitmentValues (the hash-to-field of each commitment) and foldChallenge come from the caller.
+// Every coordinate and scalar must be reduced (its words below p, resp. r): one that is not makes the verdict MI_VERIFY_MALFORMED, and
+// the VerifyingKey constructor throws MI_EINVAL for such a coordinate in the descriptor (ONE ENCODING in the header).
 inline uint8_t Verify(const Context &ctx, const VerifyingKey &vk, const Proof &proof, const std::vector<mi_fr> &publicInputs,
                       const std::vector<mi_fr> &commitmentValues = {}, const mi_fr *foldChallenge = nullptr) {
     mi_verify_input in{};

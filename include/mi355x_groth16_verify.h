@@ -45,9 +45,10 @@ typedef struct mi_vk_desc {
 } mi_vk_desc;
 
 /* Uploads the key and computes e(alpha, beta) once.  MI_EINVAL, decided on the host before any allocation: a null pointer, nb_public
- * of 0, n_k != nb_public + n_commitments, n_commitments above MI_PK_RAW_MAX_COMMITMENTS, a point off its curve, a G2 point outside the
- * r-torsion of the twist, gamma2 or delta2 at infinity, or Pedersen keys that do not all share one G (gnark's BatchVerifyMultiVk
- * condition: one pairing with G serves every commitment).  mi_last_error names the field. */
+ * of 0, n_k != nb_public + n_commitments, n_commitments above MI_PK_RAW_MAX_COMMITMENTS, a coordinate that is not reduced (see ONE
+ * ENCODING below), a point off its curve, a G2 point outside the r-torsion of the twist, gamma2 or delta2 at infinity, or Pedersen keys
+ * that do not all share one G (gnark's BatchVerifyMultiVk condition: one pairing with G serves every commitment).  mi_last_error names
+ * the field.  K[i] at infinity is a valid key (gnark emits it for a public wire no constraint uses). */
 int32_t mi_vk_load(mi_ctx *ctx, const mi_vk_desc *desc, mi_vk **out);
 int32_t mi_vk_free(mi_ctx *ctx, mi_vk *vk);
 
@@ -67,11 +68,21 @@ typedef struct mi_verify_input {
     const mi_fr *fold_challenge;            /* as the challenge of mi_prover_submit_bsb22; may be NULL when n_commitments <= 1 */
 } mi_verify_input;
 
+/* ONE ENCODING.  An mi_fp / mi_fr is four Montgomery words; read as one 256-bit integer they must lie BELOW the modulus (p for a
+ * coordinate, r for a scalar).  The arithmetic would take x + p for x (2p < 2^256), so a word string that is not reduced would be a
+ * second encoding of the same proof -- for public_inputs it is the public-input aliasing of pairing verifiers, and (p, p) would be a
+ * second infinity.  The verifier refuses them:
+ *   - mi_groth16_verify[_batch]: any coordinate of proof, commitments or pok not below p, or any of public_inputs, commitment_values,
+ *     fold_challenge not below r, makes the verdict MI_VERIFY_MALFORMED.  (fold_challenge is read, and checked, only with more than one
+ *     commitment.)  This is decided on the host, before anything of that proof reaches the MSM or a pairing.
+ *   - mi_vk_load: MI_EINVAL for any such coordinate of the descriptor; mi_last_error names the field. */
+
 /* verdicts; the checks run in the order 3, 1, 2 and the first that fails names the verdict */
 #define MI_VERIFY_OK 0          /* both equations hold */
 #define MI_VERIFY_PAIRING 1     /* e(Ar, Bs) != e(alpha, beta) e(kSum, gamma) e(Krs, delta) */
 #define MI_VERIFY_PEDERSEN 2    /* prod_k e(c^k C_k, GSigmaNeg_k) e(pok, G) != 1 */
-#define MI_VERIFY_MALFORMED 3   /* Ar, Krs, pok or a commitment off the curve, or Bs off the twist or outside its r-torsion */
+#define MI_VERIFY_MALFORMED 3   /* a coordinate or scalar that is not reduced (ONE ENCODING); Ar, Krs, pok or a commitment off the
+                                   curve; Bs off the twist or outside its r-torsion */
 
 /* Both return MI_OK whenever a verdict was reached: a rejected proof is a verdict, not an error.  MI_EINVAL (null pointers, a missing
  * array the key's counts call for) is decided on the host before any device work.  A batch judges every proof on its own -- no random

@@ -1,7 +1,8 @@
 """GPU suite: groth16.Verify on the device (include/mi355x_groth16_verify.h) -- the pairing and the tower through the two debug entry
 points against the host build of the same code (tests/emu/emu_pairing.cpp) and the definitional reference (tests/pairing_ref.py), whole
-proofs from mi_groth16_setup keys under a random trapdoor and from toy keys with known discrete logs, one tamper per verdict code, and
-batches against the per-proof calls."""
+proofs from mi_groth16_setup keys under a random trapdoor and from toy keys with known discrete logs, one tamper per verdict code,
+batches against the per-proof calls, and the forged, edge and non-reduced inputs of tests/verify_forge.py, alone and in batches of
+distinct proofs, against the verdict computed in the exponent."""
 import ctypes as C
 import numpy as np
 import pytest
@@ -9,6 +10,7 @@ import pyref as P
 import cref
 import pairing_ref as R
 import verify_cases as V
+import verify_forge as F
 import setup_cases as S
 import r1cs_cases as RC
 import dlog_keys as D
@@ -234,3 +236,89 @@ def test_batches_equal_the_per_proof_calls(ctx, made):
         got = vkh.verify_batch(proofs)
         assert list(got) == [single[id(pr)] for pr in proofs], n
     assert len(vkh.verify_batch([])) == 0
+
+
+# ---------------------------------------------------------------------------------------------------- forged, edge and non-reduced inputs
+@pytest.fixture(scope="module")
+def forged_vk(ctx):
+    """key of tests/verify_forge.py -> its mi_vk, loaded once"""
+    loaded = {}
+
+    def get(key):
+        if key["id"] not in loaded:
+            d, nbp, ped = V.vk_arrays(key["vk"])
+            loaded[key["id"]] = ctx.vk_load(d, nbp, ped)
+        return loaded[key["id"]]
+    yield get
+    for h in loaded.values():
+        h.free()
+
+
+@pytest.mark.parametrize("key_id", F.CASE_KEY_IDS)
+def test_forged_cases_get_the_verdict_of_the_exponent(forged_vk, key_id):
+    """every case of verify_forge.cases() for this key: accepted edge proofs (kSum at infinity, the doubling and the cancelling branch of
+    the group law, infinite K, Krs, C_k and pok, every fold power), each with one exponent off, forged rejections, the precedence of the
+    verdicts, and second encodings (a word + its modulus), which are malformed"""
+    mine = [c for c in F.cases() if c["key"]["id"] == key_id]
+    assert mine
+    vkh = forged_vk(mine[0]["key"])
+    bad = []
+    for c in mine:
+        want = F.verdict_in_exponent(c["key"], c)
+        assert want == c["want"], c["name"]
+        got = vkh.verify(F.verify_input(c))
+        if got != want:
+            bad.append((c["name"], got, want))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("shape", [(3, 1), (3, 3)])
+def test_batch_of_distinct_forged_proofs(forged_vk, shape):
+    """70 proofs with their own public inputs, commitment values and a: entry i must be judged on ITS scalars, pairs and Bs.  Rejections
+    of the three kinds at 0, 63, 64, 69; entry 31 is the proof of entry 30 under other public inputs.  Then batches of 1 and 3 in the
+    workspace the 70 left behind."""
+    B = load_binding()
+    key = F.forge_key(*shape)
+    vkh = forged_vk(key)
+    batch = F.distinct_batch(key, 70, 500 + shape[1])
+    want = [F.verdict_in_exponent(key, c) for c in batch]
+    assert [want[i] for i in (0, 31, 63, 64, 69)] == [B.VERIFY_MALFORMED, B.VERIFY_PAIRING, B.VERIFY_MALFORMED, B.VERIFY_PEDERSEN, B.VERIFY_MALFORMED]
+    assert want.count(B.VERIFY_OK) == 65
+    inputs = [F.verify_input(c) for c in batch]
+    assert len({x["public_inputs"].tobytes() for x in inputs}) == 70 and len({x["commitment_values"].tobytes() for x in inputs}) == 69
+    assert np.array_equal(inputs[30]["raw"], inputs[31]["raw"])
+    assert list(vkh.verify_batch(inputs)) == want
+    assert [vkh.verify(x) for x in inputs] == want
+    for n in (1, 3):
+        assert list(vkh.verify_batch(inputs[62:62 + n])) == want[62:62 + n], n
+        assert list(vkh.verify_batch(inputs[70 - n:])) == want[70 - n:], n
+
+
+def test_vk_load_asks_for_reduced_words_and_takes_infinite_k(ctx):
+    B = load_binding()
+    key = F.forge_key(3, 1)
+    d, nbp, ped = V.vk_arrays(key["vk"])
+
+    def plus_p(arr, row):
+        a = np.array(arr, np.uint64, copy=True); rows = a.reshape(-1, 4)
+        v = cref.limbs_to_int(rows[row]) + R.p
+        assert R.p <= v < 1 << 256
+        rows[row] = cref.int_to_limbs(v)
+        return a
+
+    # rows of 4 words: alpha1 = x, y; gamma2 = x.a0, x.a1, y.a0, y.a1; k = 2 per point; ped[0] = g (4 rows), g_sigma_neg (4 rows)
+    for what, vk, pd in ((r"alpha1 has", dict(d, alpha1=plus_p(d["alpha1"], 0)), ped), (r"gamma2 has", dict(d, gamma2=plus_p(d["gamma2"], 2)), ped),
+                         (r"k\[1\] has", dict(d, k=plus_p(d["k"], 3)), ped), (r"ped\[0\]\.g_sigma_neg has", d, plus_p(ped, 5))):
+        with pytest.raises(B.MiError, match=what):
+            ctx.vk_load(vk, nbp, pd)
+    ctx.vk_load(d, nbp, ped).free()
+    for shape, zero_k in (((2, 0), (1,)), ((3, 1), (0,))):
+        k = F.forge_key(*shape, zero_k=zero_k)
+        assert k["vk"]["k"][zero_k[0]] is None
+        dd, n, pp = V.vk_arrays(k["vk"])
+        ctx.vk_load(dd, n, pp).free()
+
+
+def test_pedersen_vk_make_at_the_largest_count(ctx):
+    key = F.forge_key(2, 16)
+    assert np.array_equal(ctx.pedersen_vk_make(fr_arr(key["exps"]["sigma"])), V.vk_arrays(key["vk"])[2])
