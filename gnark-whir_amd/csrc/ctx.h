@@ -36,25 +36,56 @@ enum {
     WS_R1CS_W = 11,        // r1cs.hip: W of the host entry point                                        main
     WS_SCAN = 12,          // setup.hip: block sums of the shared u32 scan (scan_u32.cuh)                main
     WS_VERIFY = 13,        // verify.hip: scalars, pairs, Miller values, flags and verdicts of a batch           main
-    WS_H = 14,             // prove.hip / group.hip: h, computeH's result and the Z MSM's scalars        main, read by msm[4].stream
+    WS_H = 14,             // prove.hip / group.hip: h, computeH's result and the Z MSM's scalars        main, read by msm[MSM_SLOT_Z].stream
     WS_PROVE_IN = 16,      // prove.hip / group.hip: W (+ a, b, c) of a prove over host inputs           filled on copy_stream
-    WS_B_WIRES = 17,       // prove.hip: W gathered to the wires that own a pk.G1.B point                msm[1].stream
-    WS_POK_VALUES = 19,    // prove.hip ProveKnowledge: the committed values                             msm[5].stream
+    WS_B_WIRES = 17,       // prove.hip: W gathered to the wires that own a pk.G1.B point                msm[MSM_SLOT_B1].stream
+    WS_POK_VALUES = 19,    // prove.hip ProveKnowledge: the committed values                             msm[MSM_SLOT_POK].stream
     WS_FB_TABLE = 20,      // fixed_base.hip: the window table of the base                               main
     WS_FB_SCALARS = 21,    // fixed_base.hip host entry point: the scalars                               main
     WS_FB_OUT = 22,        // fixed_base.hip host entry point: the points                                main
     WS_RPRIME = 23,        // msm.hip device entry point: the points in the R' packed form               main
     WS_COUNT = 24          // 15 and 18 are free
 };
-enum { EV_R1CS_BEGIN = 12, EV_R1CS_END = 13 };   // mi_ctx::ev[]: around the launches of the last R1CS evaluation (r1cs.hip)
+// mi_ctx::ev[]: every event of the context in use, what it marks and the stream that records it ("main" = ctx->stream).
+enum {
+    EV_T0 = 0,             // timing pair of the NTT, utility and MSM entry points: before the work (the MSM's wait event)     main
+    EV_T1 = 1,             // the same: after it                                                             main, msm[MSM_SLOT_A].stream
+    EV_W_READY = 2,        // group.hip: this rank's slice of W is on the device -- what its wire MSMs wait for                  main
+    EV_H_READY = 3,        // prove: h is ready -- what the Z MSM and the held wire accumulations wait for; compute_h_ms ends   main
+    EV_PROVE_BEGIN = 11,   // prove.hip: the head of the proof, and "W is ready" where W is a device input; group.hip: before the
+                           // lead's computeH / the slices of computeH over the ranks.  compute_h_ms begins                    main
+    EV_R1CS_BEGIN = 12,    // r1cs.hip: before the launches of the last R1CS evaluation                                         main
+    EV_R1CS_END = 13,      // r1cs.hip: after them                                                                              main
+    EV_COUNT = 24          // the others are free
+};
 
-#define MI_MSM_SLOTS 6
-#define MI_ZHOOK_SLOT 4    // the slot whose sort may take its count from computeH's last launch (mi_ctx::zhook)
+// mi_ctx::msm[]: who runs on which slot.  The values are fixed: the stream plan (msm.hip: K borrows B1's stream, Z has its own
+// priority) and the per-slot statistics depend on them.
+enum {
+    MSM_SLOT_A = 0,        // prove: pk.G1.A over W; its sort serves K.  Also the one slot of the plain MSM entry points
+    MSM_SLOT_B1 = 1,       // prove: pk.G1.B over the gathered wires; its sort serves B2
+    MSM_SLOT_B2 = 2,       // prove: pk.G2.B (G2)
+    MSM_SLOT_K = 3,        // prove: pk.G1.K over W, on B1's stream
+    MSM_SLOT_Z = 4,        // prove: pk.G1.Z over h; the one slot whose sort may take its count from computeH's last launch (mi_ctx::zhook)
+    MSM_SLOT_POK = 5,      // pool.hip / prove.hip: ProveKnowledge of a BSB22 commitment, beside a proof's five
+    MI_MSM_SLOTS = 6
+};
+#define MI_ZHOOK_SLOT MSM_SLOT_Z
+// MsmSlot::ev[]: all recorded on the slot's stream by msm.hip
+enum {
+    MSM_EV_SORT_DONE = 0,  // the sort stage is enqueued: what an MSM that borrows this slot's sort waits for
+    MSM_EV_L1_BEGIN = 1,   // before the level-1 accumulate launch (timed slots)
+    MSM_EV_L1_END = 2,     // after it
+    MSM_EV_JOB_BEGIN = 3,  // before the whole job
+    MSM_EV_JOB_END = 4,    // after it (the result is in pinned host memory)
+    MSM_EV_BUCKETS = 5,    // the bucket sums are ready (deferred reduce, group.hip's exchange)
+    MSM_EV_MAX_LANDED = 6, // the fullest bucket's size has landed in host memory (exact level count, msm.hip)
+    MSM_EV_COUNT = 7
+};
 struct MsmSlot {            // one in-flight MSM (msm.hip): own stream, events, workspaces, pinned result
     hipStream_t stream = nullptr;
-    hipEvent_t ev[7]{};     // 0: sort done, 1/2: around the level-1 accumulate launch, 3/4: whole job, 5: bucket sums ready (deferred reduce),
-                            // 6: the largest bucket's size has landed in host memory (exact level count, msm.hip)
-    bool max_pending = false;       // this slot's sort has a "largest bucket" word on its way to the host (ev[6])
+    hipEvent_t ev[MSM_EV_COUNT]{};
+    bool max_pending = false;       // this slot's sort has a "largest bucket" word on its way to the host (ev[MSM_EV_MAX_LANDED])
     uint32_t max_key_count = 0;     // entries of the fullest bucket of this slot's sort, once fetched
     DevBuf buf[18];
     void *host_wsum = nullptr;
@@ -85,7 +116,7 @@ struct mi_ctx {
     mi_setup_stats setup_stats{};   // last mi_groth16_setup[_exponents] call (setup.hip)
     mi_r1cs_stats r1cs_stats{};     // last evaluation of a resident R1CS on this context (r1cs.hip); eval_ms is read from ev[EV_R1CS_BEGIN], ev[EV_R1CS_END] on request
     bool r1cs_timed = false;
-    hipEvent_t ev[24]{};
+    hipEvent_t ev[EV_COUNT]{};
     // scratch
     alignas(16) unsigned char ntt_state[384];  // NttState (ntt.hip): root tables + plan knobs
     alignas(16) unsigned char msm_knobs[128];   // MsmKnobs (msm.hip)
@@ -99,7 +130,7 @@ struct mi_ctx {
     // kernel counts every h coefficient it stores -- its contiguous tile IS a slice (or two) of the sort -- and sets `done`; the Z sort
     // (msm2_sort_enqueue) then skips its own count pass: h is read once less.  Disarmed again as soon as the launch is enqueued.
     // Behind the knob "z_count_fused" (on by default: throughput equal, a single proof slightly shorter).
-    // (only slot MI_ZHOOK_SLOT -- prove's Z MSM -- ever looks at it, and the thread that arms it is the one that enqueues that slot)
+    // (only slot MSM_SLOT_Z -- prove's Z MSM -- ever looks at it, and the thread that arms it is the one that enqueues that slot)
     std::atomic<uint64_t> generic_sorts_two_pass{0}, generic_sorts_one_pass{0};   // generic MSM sorts by kind (msm.hip msm_sort_enqueue)
     std::atomic<uint64_t> dense_item_sorts{0};   // accumulations whose item size the dense-sort rule chose (msm.hip; helper threads enqueue too)
     uint64_t z_count_fused_launches = 0;   // computeH last launches that carried the count (mi_debug_get_counter: the tests' proof that the path ran)
@@ -108,7 +139,9 @@ struct mi_ctx {
 };
 
 static_assert(sizeof(mi_ctx::ws) == WS_COUNT * sizeof(DevBuf) && WS_RPRIME == WS_COUNT - 1, "WS_* names every slot of mi_ctx::ws up to its end");
-static_assert(EV_R1CS_END < sizeof(mi_ctx::ev) / sizeof(hipEvent_t), "EV_* index mi_ctx::ev");
+static_assert(EV_R1CS_END < EV_COUNT && sizeof(mi_ctx::ev) == EV_COUNT * sizeof(hipEvent_t), "EV_* index mi_ctx::ev");
+static_assert(MSM_SLOT_POK == MI_MSM_SLOTS - 1 && sizeof(mi_ctx::msm) == MI_MSM_SLOTS * sizeof(MsmSlot) && MSM_EV_MAX_LANDED == MSM_EV_COUNT - 1,
+              "MSM_SLOT_* name every slot of mi_ctx::msm, MSM_EV_* every event of a slot");
 
 // Fault injection for the error-path tests (mi_debug_inject_hip_failure, api.hip): the n-th MI_CHECK_HIP from now reports
 // hipErrorUnknown INSTEAD of running its call.  Disabled (<= 0) it costs one relaxed atomic load per checked call.

@@ -886,13 +886,13 @@ static int32_t msm_sharded_dev(mi_group *g, int curve, const void *const *pts_de
     const u32 c = mi_msm_auto_c((n_total + g->world - 1) / g->world);
     const uint32_t df = mode == 1 ? MI_MSM_DEFER_REDUCE : 0;
     const auto t0 = std::chrono::steady_clock::now();
-    const int slots[1] = {0}, curves[1] = {curve};
+    const int slots[1] = {MSM_SLOT_A}, curves[1] = {curve};
     std::string lerr;
     int32_t lrc = for_each_local_rank(g, &lerr, [&](int i) -> int32_t {
         mi_ctx *ctx = g->ctx[i];
         std::memset(&ctx->stats, 0, sizeof(ctx->stats));
-        MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-        return mi_msm_enqueue(ctx, 0, -1, curve, pts_dev[i], sc_dev[i], n_local[i], flags | df, ctx->ev[0], curve == 1, 0, 0, c);
+        MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T0], ctx->stream));
+        return mi_msm_enqueue(ctx, MSM_SLOT_A, -1, curve, pts_dev[i], sc_dev[i], n_local[i], flags | df, ctx->ev[EV_T0], curve == 1, 0, 0, c);
     });
     BucketExchange bx;
     std::vector<uint64_t> check{(uint64_t)n_total, (uint64_t)mode, (uint64_t)flags};
@@ -906,7 +906,7 @@ static int32_t msm_sharded_dev(mi_group *g, int curve, const void *const *pts_de
         for (int i = 0; i < nl; i++) {
             (void)hipSetDevice(g->dev[i]);
             std::memset(&mine[i], 0, sizeof(Part));
-            const int32_t r = lrc != MI_OK ? lrc : mi_msm_finish(g->ctx[i], 0, curve, &mine[i].p);
+            const int32_t r = lrc != MI_OK ? lrc : mi_msm_finish(g->ctx[i], MSM_SLOT_A, curve, &mine[i].p);
             if (r != MI_OK && lrc == MI_OK) { lrc = r; lerr = mi_last_error(g->ctx[i]); }
             mine[i].rc = lrc;
         }
@@ -1312,7 +1312,7 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
     if (!g || !spk || !out) return MI_EINVAL;
     const int nl = g->n_local(), W = g->world;
     if ((nl != W && nl != 1) || (int)spk->part.size() != nl) G_FAIL(g, MI_EINVAL, "group: a process holds either all ranks or exactly one");
-    static const int slots[5] = {0, 1, 2, 3, 4}, curves[5] = {1, 1, 2, 1, 1};   // A, B1, B2, K, Z: the same order on every rank
+    static const int slots[5] = {MSM_SLOT_A, MSM_SLOT_B1, MSM_SLOT_B2, MSM_SLOT_K, MSM_SLOT_Z}, curves[5] = {1, 1, 2, 1, 1};   // the same order on every rank
     const bool lead_here = g->rank0 == 0;   // global rank 0 runs computeH and owns a, b, c
     const size_t N = (size_t)1 << spk->log_n;
     const auto t_begin = std::chrono::steady_clock::now();
@@ -1367,11 +1367,11 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
             MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)Wd, W_host + pk->wire_lo, wb, hipMemcpyHostToDevice, cps));
             MI_CHECK_HIP(ctx, hipStreamSynchronize(cps));
         }
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
-        MI_TRY(mi_prove_enqueue_wire_msms(ctx, pk, Wd, ev[2], defer));
+        MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_W_READY], ctx->stream));
+        MI_TRY(mi_prove_enqueue_wire_msms(ctx, pk, Wd, ev[EV_W_READY], defer));
         if (use_sh) {   // this rank's rows of a, b (, c) into the group's slice vectors; computeH itself is a collective and follows the agreement
             const u32 log_m = pk->log_n - log_w;
-            MI_CHECK_HIP(ctx, hipEventRecord(ev[11], ctx->stream));
+            MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_PROVE_BEGIN], ctx->stream));
             for (int which = 0; which < 3; which++) {
                 const mi_fr *src = abc_sl ? (abc_sl[which] ? abc_sl[which][i] : nullptr) : (which == 0 ? a : which == 1 ? b : c);
                 const bool given = abc_sl ? abc_sl[which] != nullptr : src != nullptr;
@@ -1395,11 +1395,11 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
             }
             ctx->stats.h2d_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
         }
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[11], ctx->stream));
+        MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_PROVE_BEGIN], ctx->stream));
         Fr *h = (Fr *)ctx->ws[WS_H].p;
         MI_TRY(mi_compute_h_dev_impl(ctx, pk->log_n, da, db, dc, n_constraints, (mi_fr *)h));
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
-        return mi_prove_enqueue_z_msm(ctx, pk, (const mi_fr *)(h + pk->z_lo), ev[3], defer);
+        MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_H_READY], ctx->stream));
+        return mi_prove_enqueue_z_msm(ctx, pk, (const mi_fr *)(h + pk->z_lo), ev[EV_H_READY], defer);
     };
     if (lrc == MI_OK) { std::string e; note(for_each_local_rank(g, &e, rank_main), e); }
     auto fail = [&](int32_t rc) { const std::string keep = g->err; drain_slots(g, slots, curves, 5); g->err = keep; return rc; };
@@ -1421,9 +1421,9 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
             std::string e;
             note(for_each_local_rank(g, &e, [&](int i) -> int32_t {
                 mi_ctx *ctx = g->ctx[i];
-                MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+                MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_H_READY], ctx->stream));
                 const Fr *hz = (const Fr *)g->hh[i].p + (g->rank0 + i == 0 ? 1 : 0);
-                return mi_prove_enqueue_z_msm(ctx, spk->part[i], (const mi_fr *)hz, ctx->ev[3], defer);
+                return mi_prove_enqueue_z_msm(ctx, spk->part[i], (const mi_fr *)hz, ctx->ev[EV_H_READY], defer);
             }), e);
         }
     } else if (W > 1) {
@@ -1438,7 +1438,7 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
         }
         if (lead_here) {
             (void)hipSetDevice(g->dev[0]);
-            const hipError_t e = hipStreamWaitEvent(g->xs[0], g->ctx[0]->ev[3], 0);
+            const hipError_t e = hipStreamWaitEvent(g->xs[0], g->ctx[0]->ev[EV_H_READY], 0);
             if (e != hipSuccess) note(MI_EHIP, std::string("hipStreamWaitEvent (h ready): ") + hipGetErrorString(e));   // (still takes part in the batch)
         }
         const int32_t rc = run_xfers(g, list, g->xs);
@@ -1480,11 +1480,11 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
         std::memset(&mine[i], 0, sizeof(Part));
         if (lrc == MI_OK) {
             mi_ctx *ctx = g->ctx[i];
-            int32_t rc = mi_msm_finish(ctx, 0, 1, &mine[i].a);
-            if (rc == MI_OK) rc = mi_msm_finish(ctx, 1, 1, &mine[i].b1);
-            if (rc == MI_OK) rc = mi_msm_finish(ctx, 3, 1, &mine[i].k);
-            if (rc == MI_OK) rc = mi_msm_finish(ctx, 2, 2, &mine[i].b2);
-            if (rc == MI_OK) rc = mi_msm_finish(ctx, 4, 1, &mine[i].z);
+            int32_t rc = mi_msm_finish(ctx, MSM_SLOT_A, 1, &mine[i].a);
+            if (rc == MI_OK) rc = mi_msm_finish(ctx, MSM_SLOT_B1, 1, &mine[i].b1);
+            if (rc == MI_OK) rc = mi_msm_finish(ctx, MSM_SLOT_K, 1, &mine[i].k);
+            if (rc == MI_OK) rc = mi_msm_finish(ctx, MSM_SLOT_B2, 2, &mine[i].b2);
+            if (rc == MI_OK) rc = mi_msm_finish(ctx, MSM_SLOT_Z, 1, &mine[i].z);
             if (rc == MI_OK && (hipStreamSynchronize(ctx->stream) != hipSuccess || hipStreamSynchronize(g->xs[i]) != hipSuccess)) { mi_set_err(ctx, "prove: stream synchronisation failed"); rc = MI_EHIP; }
             note(rc, mi_last_error(ctx));
         }
@@ -1511,7 +1511,7 @@ static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, co
     mi_stats &st = g->ctx[0]->stats;
     auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<float, std::milli>(y - x).count(); };
     // (statistics are best effort: past the last all-gather nothing may fail on one rank alone)
-    if ((lead_here || use_sh) && hipEventElapsedTime(&st.compute_h_ms, g->ctx[0]->ev[11], g->ctx[0]->ev[3]) != hipSuccess) { (void)hipGetLastError(); st.compute_h_ms = 0; }
+    if ((lead_here || use_sh) && hipEventElapsedTime(&st.compute_h_ms, g->ctx[0]->ev[EV_PROVE_BEGIN], g->ctx[0]->ev[EV_H_READY]) != hipSuccess) { (void)hipGetLastError(); st.compute_h_ms = 0; }
     st.assemble_ms = ms(t_gpu_done, t_end);
     st.total_ms = ms(t_begin, t_end);
     if (stats) *stats = st;

@@ -345,8 +345,8 @@ static MsmShape key_shape(const MsmSlot &sl) {
 
 // Process-wide, read by mi_msm_state_init (experiments on which chains share a hardware queue: the runtime gives a new stream the
 // least-loaded of its priority class's four queues, ties to the newest -- tools/probes/stream_queue_probe.py):
-//   0  slot 3 (K) created, then destroyed and pointed at slot 1's stream (rounds 4-5)          1  slot 3 never created
-//   2  as 1, and slot 1 (B1 + K) on slot 0's stream (A): three wire chains instead of four
+//   0  MSM_SLOT_K created, then destroyed and pointed at MSM_SLOT_B1's stream (rounds 4-5)     1  MSM_SLOT_K never created
+//   2  as 1, and MSM_SLOT_B1 (B1 + K) on MSM_SLOT_A's stream: three wire chains instead of four
 static std::atomic<int> g_stream_plan{1};
 // counters the tests read to prove that an optional path really ran (names in the header)
 extern "C" int32_t mi_debug_get_counter(mi_ctx *ctx, const char *name, uint64_t *out) {
@@ -355,6 +355,7 @@ extern "C" int32_t mi_debug_get_counter(mi_ctx *ctx, const char *name, uint64_t 
     if (!std::strcmp(name, "dense_item_sorts")) { *out = ctx->dense_item_sorts.load(); return MI_OK; }
     if (!std::strcmp(name, "generic_sorts_two_pass")) { *out = ctx->generic_sorts_two_pass.load(); return MI_OK; }
     if (!std::strcmp(name, "generic_sorts_one_pass")) { *out = ctx->generic_sorts_one_pass.load(); return MI_OK; }
+    if (!std::strcmp(name, "hip_failure_countdown")) { const int v = mi_fault_countdown.load(); *out = v > 0 ? (uint64_t)v : 0; return MI_OK; }
     MI_FAIL(ctx, MI_EINVAL, std::string("unknown counter: ") + name);
 }
 extern "C" int32_t mi_debug_set_stream_plan(int32_t plan) {
@@ -373,7 +374,7 @@ int32_t mi_msm_state_init(mi_ctx *ctx) {
 #undef MI_PART_LDS
     (void)hipFuncSetAttribute((const void *)k_msm2_scatter2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void *)k_msm2_scatter2_staged, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    // Stream priorities (3 levels on this device).  prove.hip runs A, B1, B2, K on slots 0..3 and Z on slot 4; computeH runs on
+    // Stream priorities (3 levels on this device).  prove.hip runs A, B1, B2, K, Z on the slots of their names (MSM_SLOT_*); computeH runs on
     // the context's own stream (high, api.hip).  With equal priorities the hardware shares the CUs evenly, all five MSMs crawl
     // along together and their latency-bound tails pile up at the end of the proof.  Z's stream at LOW priority lets the four
     // wire MSMs finish first -- their tails hide under Z's bulk -- and, with several proofs in flight, lets the next proof's
@@ -383,29 +384,29 @@ int32_t mi_msm_state_init(mi_ctx *ctx) {
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
     // The runtime maps streams onto a few hardware queues in creation order, and two streams on one queue run one after the other: the
     // order in which the slots' streams are created decides WHICH two MSMs of a proof share a queue (rocprofv3: with the natural order
-    // K (slot 3) queued behind B2's whole G2 chain (slot 2) and ended a single proof; every other order measured within 0.3 ms of
+    // K queued behind B2's whole G2 chain and ended a single proof; every other order measured within 0.3 ms of
     // this one or worse).
     const int plan = g_stream_plan.load();
     for (int idx = 0; idx < MI_MSM_SLOTS; idx++) {
-        if (plan >= 1 && idx == 3) continue;   // K's slot borrows a stream below
-        if (plan >= 2 && idx == 1) continue;
+        if (plan >= 1 && idx == MSM_SLOT_K) continue;   // K's slot borrows a stream below
+        if (plan >= 2 && idx == MSM_SLOT_B1) continue;
         MsmSlot &sl = ctx->msm[idx];
         int pw = 0, pz = prio_lo;   // wires, Z: MI_PRIO_SOLO, MI_PRIO_POOL_SECOND
         if (ctx->prio_scheme == MI_PRIO_POOL_FIRST) { pw = prio_hi; pz = 0; }
         if (ctx->prio_scheme == MI_PRIO_POOL_REST) pw = pz = prio_lo;
         // every failure is reported: a null stream / event / host_wsum would otherwise surface much later as a memcpy into
         // null (msm_accum_enqueue).  The caller (mi_init_prio) unwinds through mi_shutdown, which frees what was created.
-        MI_CHECK_HIP(ctx, hipStreamCreateWithPriority(&sl.stream, hipStreamNonBlocking, idx == 4 ? pz : pw));
+        MI_CHECK_HIP(ctx, hipStreamCreateWithPriority(&sl.stream, hipStreamNonBlocking, idx == MSM_SLOT_Z ? pz : pw));
     }
-    // K (slot 3) runs on B1's stream (slot 1).  With a stream of its own it landed on the hardware queue of B2's stream, behind the whole
+    // K (MSM_SLOT_K) runs on B1's stream (MSM_SLOT_B1).  With a stream of its own it landed on the hardware queue of B2's stream, behind the whole
     // G2 chain, and a single proof ended with K's accumulation alone on the GPU: rocprofv3 timeline, K's level 1 starting at 27 of 31 ms.
     // Behind B1 -- the shortest of the five MSMs -- one proof is 1.0 ms shorter (30.8 against 31.9 ms) and the job unchanged; behind A
-    // (whose sort K shares) 0.8 ms.  The two chains are enqueued from two host threads (mi_prove_enqueue_b_msms / _ak_msms) and so
+    // (whose sort K shares) 0.8 ms.  The two chains are enqueued from two host threads (WireMsms, prove.hip) and so
     // interleave on the one stream: their buffers are disjoint, every wait one of them inserts also holds the other, and the event
-    // pair around K's level-1 launch may bracket a kernel of B1's chain (the stats of slot 3 are then an upper bound).
-    if (ctx->msm[3].stream) (void)hipStreamDestroy(ctx->msm[3].stream);
-    if (plan >= 2) ctx->msm[1].stream = ctx->msm[0].stream;
-    ctx->msm[3].stream = ctx->msm[1].stream;
+    // pair around K's level-1 launch may bracket a kernel of B1's chain (the stats of MSM_SLOT_K are then an upper bound).
+    if (ctx->msm[MSM_SLOT_K].stream) (void)hipStreamDestroy(ctx->msm[MSM_SLOT_K].stream);
+    if (plan >= 2) ctx->msm[MSM_SLOT_B1].stream = ctx->msm[MSM_SLOT_A].stream;
+    ctx->msm[MSM_SLOT_K].stream = ctx->msm[MSM_SLOT_B1].stream;
     for (auto &sl : ctx->msm) {
         for (auto &e : sl.ev) MI_CHECK_HIP(ctx, hipEventCreate(&e));
         MI_CHECK_HIP(ctx, hipHostMalloc(&sl.host_wsum, 128 * 256 + 64));
@@ -426,7 +427,7 @@ void mi_msm_state_free(mi_ctx *ctx) {
 enum { B_DIGITS, B_H, B_S, B_SORTED, B_LEVELS, B_PART0, B_PART1, B_BUCKET, B_SCAN, B_WIN, B_PVAL, B_C1, B_CHUNKS, B_ITEMTAB, B_MAX, B_BA_NODES, B_BA_PREFIX, B_BA_TOT, B_COUNT_ };
 static_assert(B_COUNT_ <= sizeof(MsmSlot::buf) / sizeof(DevBuf), "MsmSlot::buf is too small");
 
-// The fullest bucket of a sort: per-key totals -> one word (atomicMax), copied to pinned host memory behind the slot's ev[6].  The item
+// The fullest bucket of a sort: per-key totals -> one word (atomicMax), copied to pinned host memory behind the slot's ev[MSM_EV_MAX_LANDED].  The item
 // machinery needs ceil(log_L(fullest bucket)) levels; the worst case (every entry in one bucket) says 9 at N = 2^23 where uniform
 // scalars need 3 and the WHIR mix 7, and every unneeded level is three launches of empty kernels on the MSM's tail.  The host waits for
 // the word on the thread that enqueues the accumulation (a helper thread for the wire MSMs) while the rest of the sort still runs.
@@ -438,7 +439,7 @@ __global__ void __launch_bounds__(256) k_max_u32(const u32 *v, u32 n, u32 *out) 
 }
 // totals == nullptr: the word at sl.buf[B_MAX] has been computed already (k_msm2_colsum); only the copy and the event are enqueued
 // Then the scan of the per-key totals -> keystart, whose last kernel ALSO leaves that word (host_wsum + 128*256 + 32) and the number of
-// sorted entries (host_wsum + 128*256) in the slot's pinned host memory: no copy launches (k_scan_final); ev[6] follows the scan.
+// sorted entries (host_wsum + 128*256) in the slot's pinned host memory: no copy launches (k_scan_final); ev[MSM_EV_MAX_LANDED] follows the scan.
 // sums_ready: the scan's block sums are in sl.buf[B_SCAN] already (k_msm2_colsum added them up): only the scan's last kernel is launched.
 static int32_t fetch_max_and_scan_keys(mi_ctx *ctx, MsmSlot &sl, const u32 *totals, u32 nkeys, u32 *keystart, bool compute_max, bool sums_ready = false) {
     MI_TRY(mi_reserve(ctx, sl.buf[B_MAX], 64));
@@ -460,7 +461,7 @@ static int32_t fetch_max_and_scan_keys(mi_ctx *ctx, MsmSlot &sl, const u32 *tota
     } else {
         MI_TRY(exclusive_scan(ctx, st, totals, nkeys, keystart, sl.buf[B_SCAN], (u32 *)host, dmax, (u32 *)(host + 32)));
     }
-    MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[6], st));
+    MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_MAX_LANDED], st));
     sl.max_pending = true;
     return MI_OK;
 }
@@ -504,7 +505,7 @@ static int32_t run_levels(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &sl, u32 
         // the timed span (mi_stats.g1_accum_kernel_ms) brackets the accumulate kernel alone: on the 29-bit path the launcher records the
         // opening event AFTER its item-table kernel (0.1 ms alone, up to 0.5 ms waiting for CUs with three proofs in flight)
         const bool rp_path = level == 0 && pts && rprime && ops.accum_affine_rp;
-        if (time_first && level == 0 && !rp_path) MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[1], st));
+        if (time_first && level == 0 && !rp_path) MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_L1_BEGIN], st));
         const u32 ba_rounds = knobs_of(ctx)->ba_rounds;
         // batch-affine rounds (msm_ba_g1.cuh) where the buckets hold a few items each (>= 32 entries on average) and the scratch fits
         const u32 ba_waves = (u32)ctx->cu_count * 16;
@@ -516,24 +517,24 @@ static int32_t run_levels(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &sl, u32 
             MI_TRY(mi_reserve(ctx, sl.buf[B_ITEMTAB], (items_bound + 1) * 16));
             ops.accum_affine_ba(st, (u32)ctx->cu_count * 64, pts, sorted, cur.start, cur.cnt, cur.items, cur.item_start, nkeys, final_out, pout, sl.buf[B_ITEMTAB].p,
                                 rp_partials ? 1u : 0u, ba_rounds, items_bound + 1, ba_waves, sl.buf[B_BA_NODES].p, sl.buf[B_BA_PREFIX].p, sl.buf[B_BA_TOT].p,
-                                (char *)sl.buf[B_BA_TOT].p + ba_tot, time_first ? sl.ev[1] : nullptr);
+                                (char *)sl.buf[B_BA_TOT].p + ba_tot, time_first ? sl.ev[MSM_EV_L1_BEGIN] : nullptr);
         } else if (rp_path) {
             MI_TRY(mi_reserve(ctx, sl.buf[B_ITEMTAB], (items_bound + 1) * 16));
             // which build of the G1 level-1 kernel: three waves per SIMD (168 VGPRs: a SIMD's register file is full, and a freed wave slot
             // is too small for any 256-VGPR G2 workgroup, which then waits for the END of this launch) or two (196: one freed slot admits one)
             const MsmKnobs *kn = knobs_of(ctx);
             const bool g2 = ops.xyzz_bytes == 256;
-            const bool two = !g2 && (kn->l1_waves == 2 || (kn->z_waves == 2 && &sl == &ctx->msm[4]));
+            const bool two = !g2 && (kn->l1_waves == 2 || (kn->z_waves == 2 && &sl == &ctx->msm[MSM_SLOT_Z]));
             const u32 wg = g2 ? kn->g2_wg : kn->l1_wg, wg_log = wg == 4 ? 2u : wg == 2 ? 1u : 0u;   // waves per workgroup
             // (the level-1 launches on lowest-priority streams of their own -- "the accumulation is what fills the GPU, everything else is
             //  dispatched ahead of it" -- measured -6 % proofs/s, profiles/r05_ab_evidence.txt: removed)
             ops.accum_affine_rp(st, grid, pts, sorted, cur.start, cur.cnt, cur.items, cur.item_start, nkeys, L, final_out, pout, sl.buf[B_ITEMTAB].p,
-                                (rp_partials ? 1u : 0u) | (two ? 2u : 0u) | (wg_log << 2), time_first ? sl.ev[1] : nullptr);
+                                (rp_partials ? 1u : 0u) | (two ? 2u : 0u) | (wg_log << 2), time_first ? sl.ev[MSM_EV_L1_BEGIN] : nullptr);
         } else if (level == 0 && pts) ops.accum_affine(st, grid, pts, sorted, cur.start, cur.cnt, cur.items, cur.item_start, nkeys, L, final_out, pout);
         else if (rp_partials) ops.accum_xyzz_rp(st, grid, pin, cur.start, cur.cnt, cur.items, cur.item_start, nkeys, L, final_out, pout);
         else ops.accum_xyzz(st, grid, pin, cur.start, cur.cnt, cur.items, cur.item_start, nkeys, L, final_out, pout);
         MI_CHECK_HIP(ctx, hipGetLastError());
-        if (time_first && level == 0) MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[2], st));
+        if (time_first && level == 0) MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_L1_END], st));
         u64 m_next = (m + L - 1) / L;  // entries of the largest key at the next level
         if (m_next <= 1) break;
         // the finisher: no key holds more than finish_max partial sums -> one list launch + one launch end the machinery (the lists live in
@@ -576,7 +577,7 @@ static int32_t run_levels(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &sl, u32 
     return MI_OK;
 }
 
-// sort stage on slot sl: digits + counting sort of (key -> point index | sign).  Records sl.ev[0].
+// sort stage on slot sl: digits + counting sort of (key -> point index | sign).  Records sl.ev[MSM_EV_SORT_DONE].
 static int32_t msm2_sort_enqueue(mi_ctx *ctx, MsmSlot &sl, const Fr *scalars, u32 n, u32 flags, u32 c, bool wkeys = false, bool exact = false);
 static int32_t msm_sort_enqueue(mi_ctx *ctx, MsmSlot &sl, const Fr *scalars, u32 n, u32 flags, u32 generic_c, bool exact) {
     MsmKnobs *kn = knobs_of(ctx);
@@ -614,11 +615,11 @@ static int32_t msm_sort_enqueue(mi_ctx *ctx, MsmSlot &sl, const Fr *scalars, u32
     MI_TRY(fetch_max_and_scan_keys(ctx, sl, total, s.nkeys, keystart, true));
     hipLaunchKernelGGL(k_msm_scatter, dim3(s.nslices, s.nwin), dim3(1024), lds_bytes, st, s, digits, keystart, H, sorted);
     MI_CHECK_HIP(ctx, hipGetLastError());
-    MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[0], st));
+    MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_SORT_DONE], st));
     return MI_OK;
 }
 
-// fixed-base sort stage: entries of ALL windows keyed by one bucket set of 2^(c-1), two-pass sort.  Records sl.ev[0].
+// fixed-base sort stage: entries of ALL windows keyed by one bucket set of 2^(c-1), two-pass sort.  Records sl.ev[MSM_EV_SORT_DONE].
 // the shape of the fixed-base sort of n scalars with c-bit windows under the context's knobs (one place: the sort and the count hook must agree)
 static Msm2Shape msm2_plan_shape(const MsmKnobs *kn, u32 n, u32 c, bool wkeys) {
     const u32 G = n ? (n + MSM2_SLICE - 1) / MSM2_SLICE : 1;   // pass-1 slices
@@ -633,7 +634,7 @@ int32_t mi_msm_z_count_arm(mi_ctx *ctx, int slot, size_t n, uint32_t c) {
     static_assert(sizeof(Msm2Shape) <= sizeof(ctx->zhook.shape), "Msm2Shape travels in ctx->zhook.shape");
     ctx->zhook.armed = ctx->zhook.done = false; ctx->zhook.h = nullptr;
     const MsmKnobs *kn = knobs_of(ctx);
-    if (!kn->z_count_fused || slot != MI_ZHOOK_SLOT || c < 17 || c > 22 || n < MSM2_SLICE || n > ((size_t)1 << 27)) return MI_OK;
+    if (!kn->z_count_fused || slot != MSM_SLOT_Z || c < 17 || c > 22 || n < MSM2_SLICE || n > ((size_t)1 << 27)) return MI_OK;
     const Msm2Shape s = msm2_plan_shape(kn, (u32)n, c, false);
     if ((u64)s.nwin * n >= ((u64)1 << 31) || (n + s.nslices - 1) / s.nslices != MSM2_SLICE) return MI_OK;
     MsmSlot &sl = ctx->msm[slot];
@@ -663,8 +664,8 @@ static int32_t msm2_sort_enqueue(mi_ctx *ctx, MsmSlot &sl, const Fr *scalars, u3
     while (per > 1 && per * s.ngroups > 8192) per >>= 1;
     // computeH's last launch may have counted these very scalars already (ctx->zhook, armed by prove.hip for this slot, shape and matrix)
     bool counted = false;
-    if (&sl == &ctx->msm[MI_ZHOOK_SLOT]) {   // (the other slots' sorts run on helper threads and never touch the hook)
-        counted = ctx->zhook.done && ctx->zhook.slot == MI_ZHOOK_SLOT && ctx->zhook.n == n && ctx->zhook.c == c && ctx->zhook.C1 == C1 && ctx->zhook.h == (const void *)scalars && mont && !wkeys;
+    if (&sl == &ctx->msm[MSM_SLOT_Z]) {   // (the other slots' sorts run on helper threads and never touch the hook)
+        counted = ctx->zhook.done && ctx->zhook.slot == MSM_SLOT_Z && ctx->zhook.n == n && ctx->zhook.c == c && ctx->zhook.C1 == C1 && ctx->zhook.h == (const void *)scalars && mont && !wkeys;
         ctx->zhook.done = false;
     }
     if (!counted) {
@@ -722,7 +723,7 @@ static int32_t msm2_sort_enqueue(mi_ctx *ctx, MsmSlot &sl, const Fr *scalars, u3
     else
         hipLaunchKernelGGL(k_msm2_scatter2, dim3(chunks_bound + 8), dim3(1024), s.gsize * 4, st, s, gstart, cstart, keystart, H2, part_lo, part_val, sorted);
     MI_CHECK_HIP(ctx, hipGetLastError());
-    MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[0], st));
+    MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_SORT_DONE], st));
     return MI_OK;
 }
 
@@ -741,7 +742,7 @@ static int32_t msm_accum_enqueue(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &s
     const u32 seg = kn->seg ? kn->seg : msm_auto_seg(s.nbuckets);
     const u64 T_bound = srt.entries_cap;   // nwin * n, or the counted number of entries (msm2_sort_enqueue, exact)
     hipStream_t st = acc.stream;
-    if (&srt != &acc) MI_CHECK_HIP(ctx, hipStreamWaitEvent(st, srt.ev[0], 0));
+    if (&srt != &acc) MI_CHECK_HIP(ctx, hipStreamWaitEvent(st, srt.ev[MSM_EV_SORT_DONE], 0));
     MI_TRY(mi_reserve(ctx, acc.buf[B_LEVELS], ((size_t)s.nkeys + 1) * 4 * 8));
     MI_TRY(mi_reserve(ctx, acc.buf[B_BUCKET], (size_t)s.nkeys * ops.xyzz_bytes + 64));   // + the finisher's two list counters
     const u32 *S = (const u32 *)srt.buf[B_S].p, *sorted = (const u32 *)srt.buf[B_SORTED].p;
@@ -753,7 +754,7 @@ static int32_t msm_accum_enqueue(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &s
     // fullest bucket there is (k_max_u32 above: the wait is on the enqueueing thread and ends before the sort does)
     u64 max_count = (u64)(srt.nwin_digits / srt.nwin_keys) * n;
     if (srt.max_pending) {
-        MI_CHECK_HIP(ctx, hipEventSynchronize(srt.ev[6]));
+        MI_CHECK_HIP(ctx, hipEventSynchronize(srt.ev[MSM_EV_MAX_LANDED]));
         srt.max_key_count = *(const u32 *)((const char *)srt.host_wsum + 128 * 256 + 32);
         srt.max_pending = false;
     }
@@ -809,7 +810,7 @@ static int32_t msm_accum_enqueue(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &s
     acc.timed = timed;
     acc.deferred = defer_reduce;
     if (defer_reduce) {
-        MI_CHECK_HIP(ctx, hipEventRecord(acc.ev[5], st));
+        MI_CHECK_HIP(ctx, hipEventRecord(acc.ev[MSM_EV_BUCKETS], st));
         return MI_OK;
     }
     return msm_tail_enqueue(ctx, ops, acc);
@@ -839,7 +840,7 @@ static int32_t msm_tail_enqueue(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &ac
     }
     MI_CHECK_HIP(ctx, hipGetLastError());
     if (!on_host) MI_CHECK_HIP(ctx, hipMemcpyAsync(acc.host_wsum, P, ops.xyzz_bytes * s.nwin, hipMemcpyDeviceToHost, st));   // tb == 1: no tree ran
-    MI_CHECK_HIP(ctx, hipEventRecord(acc.ev[4], st));
+    MI_CHECK_HIP(ctx, hipEventRecord(acc.ev[MSM_EV_JOB_END], st));
     acc.deferred = false;
     acc.active = true;
     return MI_OK;
@@ -853,7 +854,7 @@ static int32_t msm_finish(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &sl, void
     ops.combine_windows(sl.host_wsum, s.nwin, s.c, out);   // Horner on the host, <= 128 points
     if (sl.timed) {
         float ms = 0;
-        MI_CHECK_HIP(ctx, hipEventElapsedTime(&ms, sl.ev[1], sl.ev[2]));
+        MI_CHECK_HIP(ctx, hipEventElapsedTime(&ms, sl.ev[MSM_EV_L1_BEGIN], sl.ev[MSM_EV_L1_END]));
         ctx->stats.g1_accum_kernel_ms += ms;
         ctx->stats.g1_accum_pairs += sl.stat_pairs;
         ctx->stats.g1_accum_launches += 1;
@@ -883,11 +884,15 @@ int32_t mi_msm_precompute(mi_ctx *ctx, int curve, const void *base_dev, void *pr
     MI_CHECK_HIP(ctx, e);
     return MI_OK;
 }
+// roctx range names of a slot's enqueue and collect, one row per MSM_SLOT_* in the enum's order
+static const char *const msm_range_names[MI_MSM_SLOTS][2] = {
+    /* MSM_SLOT_A   */ {"mi.msm.A.enqueue", "mi.msm.A.collect"},   /* MSM_SLOT_B1  */ {"mi.msm.B1.enqueue", "mi.msm.B1.collect"},
+    /* MSM_SLOT_B2  */ {"mi.msm.B2.enqueue", "mi.msm.B2.collect"}, /* MSM_SLOT_K   */ {"mi.msm.K.enqueue", "mi.msm.K.collect"},
+    /* MSM_SLOT_Z   */ {"mi.msm.Z.enqueue", "mi.msm.Z.collect"},   /* MSM_SLOT_POK */ {"mi.msm.PoK.enqueue", "mi.msm.PoK.collect"}};
 int32_t mi_msm_enqueue(mi_ctx *ctx, int slot, int sort_slot, int curve, const void *pts_dev, const void *scalars_dev, size_t n,
                        uint32_t flags, hipEvent_t wait_ev, bool timed, uint32_t precomp_c, size_t stat_pairs, uint32_t generic_c) {
     if (slot < 0 || slot >= MI_MSM_SLOTS || sort_slot >= MI_MSM_SLOTS) return MI_EINVAL;
-    static const char *const range_names[MI_MSM_SLOTS] = {"mi.msm.A.enqueue", "mi.msm.B1.enqueue", "mi.msm.B2.enqueue", "mi.msm.K.enqueue", "mi.msm.Z.enqueue", "mi.msm.PoK.enqueue"};
-    const MiRange range(range_names[slot]);
+    const MiRange range(msm_range_names[slot][0]);
     if (n > MI_MSM_MAX_PAIRS) MI_FAIL(ctx, MI_EINVAL, "msm: n > 2^27 pairs per device not supported (shard the points)");
     MsmSlot &sl = ctx->msm[slot];
     const std::function<hipEvent_t()> *gate_once = sl.accum_gate;   // valid for this call only, whatever path it takes
@@ -916,18 +921,18 @@ int32_t mi_msm_enqueue(mi_ctx *ctx, int slot, int sort_slot, int curve, const vo
         const MsmShape s = key_shape(sl);
         MI_TRY(mi_reserve(ctx, sl.buf[B_BUCKET], (size_t)s.nkeys * ops.xyzz_bytes + 64));
         if (wait_ev) MI_CHECK_HIP(ctx, hipStreamWaitEvent(sl.stream, wait_ev, 0));
-        MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[3], sl.stream));
+        MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_JOB_BEGIN], sl.stream));
         MI_CHECK_HIP(ctx, hipMemsetAsync(sl.buf[B_BUCKET].p, 0, (size_t)s.nkeys * ops.xyzz_bytes + 64, sl.stream));
         sl.tail_seg = knobs_of(ctx)->seg ? knobs_of(ctx)->seg : msm_auto_seg(s.nbuckets);
         static const u32 no_entries = 0;
         sl.entries_src = &no_entries;   // (a host word, like every slot's)
         sl.timed = false;
         sl.deferred = true;
-        MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[5], sl.stream));
+        MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_BUCKETS], sl.stream));
         return MI_OK;
     }
     if (wait_ev) MI_CHECK_HIP(ctx, hipStreamWaitEvent(sl.stream, wait_ev, 0));
-    MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[3], sl.stream));
+    MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_JOB_BEGIN], sl.stream));
     MsmSlot &srt = sort_slot >= 0 ? ctx->msm[sort_slot] : sl;
     if (sort_slot < 0 && precomp_c) MI_TRY(msm2_sort_enqueue(ctx, sl, (const Fr *)scalars_dev, (u32)n, flags, precomp_c, false, exact));
     else if (sort_slot < 0) MI_TRY(msm_sort_enqueue(ctx, sl, (const Fr *)scalars_dev, (u32)n, flags, generic_c, exact));
@@ -952,13 +957,12 @@ int32_t mi_msm_bucket_view(mi_ctx *ctx, int slot, int curve, MsmBucketView *v) {
     if (!sl.deferred) return MI_OK;
     const MsmShape s = key_shape(sl);
     v->bucket = sl.buf[B_BUCKET].p; v->nkeys = s.nkeys; v->xyzz_bytes = ops.xyzz_bytes; v->seg = sl.tail_seg;
-    v->stream = sl.stream; v->ready = sl.ev[5]; v->c = s.c; v->nwin = s.nwin;
+    v->stream = sl.stream; v->ready = sl.ev[MSM_EV_BUCKETS]; v->c = s.c; v->nwin = s.nwin;
     return MI_OK;
 }
 int32_t mi_msm_finish(mi_ctx *ctx, int slot, int curve, void *out_xyzz_host) {
     if (slot < 0 || slot >= MI_MSM_SLOTS) return MI_EINVAL;
-    static const char *const range_names[MI_MSM_SLOTS] = {"mi.msm.A.collect", "mi.msm.B1.collect", "mi.msm.B2.collect", "mi.msm.K.collect", "mi.msm.Z.collect", "mi.msm.PoK.collect"};
-    const MiRange range(range_names[slot]);
+    const MiRange range(msm_range_names[slot][1]);
     return msm_finish(ctx, curve == 1 ? msm_g1_ops() : msm_g2_ops(), ctx->msm[slot], out_xyzz_host);
 }
 
@@ -969,7 +973,7 @@ static void xyzz_to_jac_out(const XYZZ<F> &r, JacT *out) {
     else { Affine<F> a = xyzz_to_affine(r); j = Jac<F>{a.x, a.y, F::one()}; }
     std::memcpy(out, &j, sizeof(j));
 }
-// one MSM through slot 0, ordered after everything already queued on ctx->stream
+// one MSM through MSM_SLOT_A, ordered after everything already queued on ctx->stream
 template <class F, class JacT>
 static int32_t msm_dev_entry(mi_ctx *ctx, int curve, const void *pts_dev, const void *scalars_dev, size_t n, uint32_t flags, JacT *out) {
     std::memset(&ctx->stats, 0, sizeof(ctx->stats));
@@ -984,12 +988,12 @@ static int32_t msm_dev_entry(mi_ctx *ctx, int curve, const void *pts_dev, const 
         pts_dev = ctx->ws[WS_RPRIME].p;
         rp = MI_MSM_PTS_RPRIME;
     }
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    MI_TRY(mi_msm_enqueue(ctx, 0, -1, curve, pts_dev, scalars_dev, n, flags | MI_MSM_EXACT_SIZE | rp, ctx->ev[0], curve == 1));
-    if (n) MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->msm[0].stream));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T0], ctx->stream));
+    MI_TRY(mi_msm_enqueue(ctx, MSM_SLOT_A, -1, curve, pts_dev, scalars_dev, n, flags | MI_MSM_EXACT_SIZE | rp, ctx->ev[EV_T0], curve == 1));
+    if (n) MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T1], ctx->msm[MSM_SLOT_A].stream));
     XYZZ<F> r;
-    MI_TRY(mi_msm_finish(ctx, 0, curve, &r));
-    if (n) MI_CHECK_HIP(ctx, hipEventElapsedTime(&ctx->stats.total_ms, ctx->ev[0], ctx->ev[1]));
+    MI_TRY(mi_msm_finish(ctx, MSM_SLOT_A, curve, &r));
+    if (n) MI_CHECK_HIP(ctx, hipEventElapsedTime(&ctx->stats.total_ms, ctx->ev[EV_T0], ctx->ev[EV_T1]));
     xyzz_to_jac_out<F>(r, out);
     return MI_OK;
 }
@@ -1010,12 +1014,12 @@ static int32_t msm_fixed_dev_entry(mi_ctx *ctx, int curve, const void *pre_dev, 
     std::memset(&ctx->stats, 0, sizeof(ctx->stats));
     const uint32_t rp = (flags & MI_MSM_TABLE_RPRIME) ? MI_MSM_PTS_RPRIME : 0;   // the table was converted by mi_msm_table_to_rprime_*: level 1 in 29-bit limbs
     flags &= ~MI_MSM_TABLE_RPRIME;
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    MI_TRY(mi_msm_enqueue(ctx, 0, -1, curve, pre_dev, scalars_dev, n, flags | MI_MSM_EXACT_SIZE | rp, ctx->ev[0], curve == 1, c));
-    if (n) MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->msm[0].stream));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T0], ctx->stream));
+    MI_TRY(mi_msm_enqueue(ctx, MSM_SLOT_A, -1, curve, pre_dev, scalars_dev, n, flags | MI_MSM_EXACT_SIZE | rp, ctx->ev[EV_T0], curve == 1, c));
+    if (n) MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T1], ctx->msm[MSM_SLOT_A].stream));
     XYZZ<F> r;
-    MI_TRY(mi_msm_finish(ctx, 0, curve, &r));
-    if (n) MI_CHECK_HIP(ctx, hipEventElapsedTime(&ctx->stats.total_ms, ctx->ev[0], ctx->ev[1]));
+    MI_TRY(mi_msm_finish(ctx, MSM_SLOT_A, curve, &r));
+    if (n) MI_CHECK_HIP(ctx, hipEventElapsedTime(&ctx->stats.total_ms, ctx->ev[EV_T0], ctx->ev[EV_T1]));
     xyzz_to_jac_out<F>(r, out);
     return MI_OK;
 }

@@ -763,11 +763,11 @@ int32_t mi_debug_set_ntt_threads(mi_ctx *ctx, uint32_t threads) {
 int32_t mi_ntt_dev(mi_ctx *ctx, mi_fr *inout_dev, uint32_t log_n, uint32_t flags) {
     if (!ctx || !inout_dev || log_n > 28 || (flags & ~7u)) return MI_EINVAL;
     stats_begin(ctx);
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T0], ctx->stream));
     MI_TRY(mi_ntt_dev_impl(ctx, inout_dev, log_n, flags));
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    MI_CHECK_HIP(ctx, hipEventSynchronize(ctx->ev[1]));
-    MI_CHECK_HIP(ctx, hipEventElapsedTime(&ctx->stats.ntt_kernel_ms, ctx->ev[0], ctx->ev[1]));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T1], ctx->stream));
+    MI_CHECK_HIP(ctx, hipEventSynchronize(ctx->ev[EV_T1]));
+    MI_CHECK_HIP(ctx, hipEventElapsedTime(&ctx->stats.ntt_kernel_ms, ctx->ev[EV_T0], ctx->ev[EV_T1]));
     return MI_OK;
 }
 int32_t mi_ntt(mi_ctx *ctx, mi_fr *inout, uint32_t log_n, uint32_t flags) {
@@ -784,11 +784,11 @@ int32_t mi_compute_h_dev(mi_ctx *ctx, uint32_t log_n, const mi_fr *a, const mi_f
                          size_t n_constraints, mi_fr *h_out) {
     if (!ctx || !a || !b || !h_out || log_n > 28 || n_constraints > ((size_t)1 << log_n)) return MI_EINVAL;   // c may be null: c = a o b
     stats_begin(ctx);
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T0], ctx->stream));
     MI_TRY(mi_compute_h_dev_impl(ctx, log_n, a, b, c, n_constraints, h_out));
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    MI_CHECK_HIP(ctx, hipEventSynchronize(ctx->ev[1]));
-    MI_CHECK_HIP(ctx, hipEventElapsedTime(&ctx->stats.compute_h_ms, ctx->ev[0], ctx->ev[1]));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T1], ctx->stream));
+    MI_CHECK_HIP(ctx, hipEventSynchronize(ctx->ev[EV_T1]));
+    MI_CHECK_HIP(ctx, hipEventElapsedTime(&ctx->stats.compute_h_ms, ctx->ev[EV_T0], ctx->ev[EV_T1]));
     ctx->stats.ntt_kernel_ms = ctx->stats.compute_h_ms;
     return MI_OK;
 }

@@ -111,14 +111,14 @@ static void worker_main(mi_prover *p, mi_ctx *ctx) {
         int32_t rc = MI_ENOMEM, rc_pok = MI_OK;
         std::string prove_err;
         try {   // (nothing may leave a worker thread: an allocation failure in the bookkeeping below is this job's MI_ENOMEM, not std::terminate)
-        // BSB22: ProveKnowledge of every commitment but the last runs before the proof, the last one rides on slot 5 BESIDE the proof's
+        // BSB22: ProveKnowledge of every commitment but the last runs before the proof, the last one rides on MSM_SLOT_POK BESIDE the proof's
         // five MSMs and is collected after it (prove.go computes the PoK between the solve and computeH: same values, same points)
         const size_t nb = j->bsb.size();
         std::vector<mi_g1_affine> poks(nb);
         std::string pok_err;
         for (size_t i = 0; i + 1 < nb && rc_pok == MI_OK; i++) rc_pok = mi_pedersen_prove_knowledge(ctx, j->bsb[i].key, j->bsb[i].values, j->bsb[i].n, &poks[i]);
         // (enqueued from a helper thread while this one enqueues the proof: the PoK's sort waits once on the host for its count pass, and
-        //  the values' pageable copy holds its thread -- neither should delay the proof's own kernels; slot 5 and ws[WS_POK_VALUES] are the PoK's alone)
+        //  the values' pageable copy holds its thread -- neither should delay the proof's own kernels; MSM_SLOT_POK and ws[WS_POK_VALUES] are the PoK's alone)
         bool pok_pending = false;
         std::future<int32_t> f_pok;
         std::string pok_enq_err;   // the helper's own error sink (ctx.h mi_err_sink): it works on ctx while this thread proves on it
@@ -159,7 +159,7 @@ static void worker_main(mi_prover *p, mi_ctx *ctx) {
         }
         prove_err = rc != MI_OK ? mi_last_error(ctx) : "";
         if (f_pok.valid()) { rc_pok = f_pok.get(); pok_pending = rc_pok == MI_OK; if (rc_pok != MI_OK) pok_err = "prover: enqueueing the ProveKnowledge MSM failed: " + pok_enq_err; }
-        if (pok_pending) {   // collected whatever the proof did: slot 5 must be idle for the next job
+        if (pok_pending) {   // collected whatever the proof did: MSM_SLOT_POK must be idle for the next job
             const int32_t r2 = mi_pedersen_pok_collect(ctx, &poks[nb - 1]);
             if (r2 != MI_OK && rc_pok == MI_OK) { rc_pok = r2; pok_err = mi_last_error(ctx); }
         }

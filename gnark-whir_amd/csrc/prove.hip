@@ -230,20 +230,20 @@ static void pedersen_build_tables(mi_ctx *ctx, mi_pedersen_pk *pk) {
     if (!ok) { (void)hipGetLastError(); for (void *q : t) if (q) (void)hipFree(q); return; }
     pk->pre_basis = t[0]; pk->pre_sigma = t[1]; pk->c_tab = c;
 }
-// One Pedersen MSM on slot 5 of ctx (its own stream: it runs beside the five MSMs of a proof), in two halves so that a prover-pool job
+// One Pedersen MSM on MSM_SLOT_POK of ctx (its own stream: it runs beside the five MSMs of a proof), in two halves so that a prover-pool job
 // can enqueue its proof's ProveKnowledge MSM, prove, and collect (pool.hip); host values in, affine point out.
 static int32_t pedersen_enqueue(mi_ctx *ctx, const void *bases_dev, const void *tables_dev, u32 c_tab, size_t key_n, const mi_fr *values, size_t n) {
     if (!ctx || (!values && n)) return MI_EINVAL;
     if (n > key_n) MI_FAIL(ctx, MI_EINVAL, "pedersen: more values than basis points");   // gnark: "must have as many values as basis elements"
     MI_TRY(mi_reserve(ctx, ctx->ws[WS_POK_VALUES], n * sizeof(mi_fr) + 64));
-    if (n) MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[WS_POK_VALUES].p, values, n * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->msm[5].stream));
+    if (n) MI_CHECK_HIP(ctx, hipMemcpyAsync(ctx->ws[WS_POK_VALUES].p, values, n * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->msm[MSM_SLOT_POK].stream));
     // the tables are laid out [window][key_n]: they serve exactly the full-length call (gnark's: as many values as basis elements)
-    if (tables_dev && n == key_n) return mi_msm_enqueue(ctx, 5, -1, 1, tables_dev, ctx->ws[WS_POK_VALUES].p, n, MI_MSM_PTS_RPRIME, nullptr, false, c_tab);
-    return mi_msm_enqueue(ctx, 5, -1, 1, bases_dev, ctx->ws[WS_POK_VALUES].p, n, 0, nullptr, false);
+    if (tables_dev && n == key_n) return mi_msm_enqueue(ctx, MSM_SLOT_POK, -1, 1, tables_dev, ctx->ws[WS_POK_VALUES].p, n, MI_MSM_PTS_RPRIME, nullptr, false, c_tab);
+    return mi_msm_enqueue(ctx, MSM_SLOT_POK, -1, 1, bases_dev, ctx->ws[WS_POK_VALUES].p, n, 0, nullptr, false);
 }
 static int32_t pedersen_collect(mi_ctx *ctx, mi_g1_affine *out) {
     G1X r;
-    MI_TRY(mi_msm_finish(ctx, 5, 1, &r));
+    MI_TRY(mi_msm_finish(ctx, MSM_SLOT_POK, 1, &r));
     G1Aff a = xyzz_to_affine(r);
     if (out) std::memcpy(out, &a, sizeof(a));
     return MI_OK;
@@ -362,71 +362,72 @@ int32_t mi_pk_free(mi_ctx *ctx, mi_pk *pk) {
 
 // ---------------------------------------------------------------- the pieces of a proof (shared with group.hip)
 // step 5 + the wire MSMs: they depend on W only (ev_w = "W is on the device").  Two independent groups, each with ONE sort:
-// B1 + B2 (slots 1, 2) and A + K (slots 0, 3).  Enqueueing a group waits once, on the host, for the count pass of its sort (msm.hip,
+// B1 + B2 and A + K.  Enqueueing a group waits once, on the host, for the count pass of its sort (msm.hip,
 // MI_MSM_EXACT_SIZE), so a proof enqueues the two groups from two helper threads while its own thread enqueues computeH and the Z MSM
 // (prove_common): measured on one proof alone, the A + K sort used to start 10 ms into the proof because the host was still busy
 // enqueueing Z's and B's ~130 launches, and the memory-bound sorts then ran beside the bucket accumulations instead of beside the NTT.
-int32_t mi_prove_enqueue_b_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, hipEvent_t ev_w, bool defer, const std::function<hipEvent_t()> *accum_gate) {
+static void arm_accum_gate(mi_ctx *ctx, int slot, const std::function<hipEvent_t()> *accum_gate) { ctx->msm[slot].accum_gate = accum_gate; }
+static int32_t enqueue_b_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, hipEvent_t ev_w, bool defer, const std::function<hipEvent_t()> *accum_gate) {
     (void)hipSetDevice(ctx->dev);   // the current device is per host thread
-    struct Gates { mi_ctx *c; const std::function<hipEvent_t()> *g; void arm(int slot) const { c->msm[slot].accum_gate = g; } } gates{ctx, accum_gate};
     // wire values are skewed (45 % of them 0 or 1): their sorts are sized by the counted entries, not by windows * n (msm.hip)
-    const uint32_t df = (defer ? MI_MSM_DEFER_REDUCE : 0) | MI_MSM_EXACT_SIZE;
-    const uint32_t rp = pk->rprime ? MI_MSM_PTS_RPRIME : 0;
+    const uint32_t fl = (defer ? MI_MSM_DEFER_REDUCE : 0) | MI_MSM_EXACT_SIZE | (pk->rprime ? MI_MSM_PTS_RPRIME : 0);
     // wireValuesB by the static gather indices, on its MSM's stream; B2 (G2) shares B1's sort (same scalars)
     MI_TRY(mi_reserve(ctx, ctx->ws[WS_B_WIRES], (pk->n_b + 1) * sizeof(Fr)));
-    hipStream_t st = ctx->msm[1].stream;
+    hipStream_t st = ctx->msm[MSM_SLOT_B1].stream;
     if (ev_w) MI_CHECK_HIP(ctx, hipStreamWaitEvent(st, ev_w, 0));
     if (pk->n_b) hipLaunchKernelGGL(k_gather_fr, dim3((unsigned)((pk->n_b + 255) / 256)), dim3(256), 0, st, (Fr *)ctx->ws[WS_B_WIRES].p, (const Fr *)W, pk->idx_b, pk->n_b);
     MI_CHECK_HIP(ctx, hipGetLastError());
-    if (pk->pre_b1) {
-        gates.arm(1);
-        // (B1 and K are not timed: their chains interleave on one stream, so the event pair around one's level-1 launch may bracket kernels
-        //  of the other; mi_stats.g1_accum_* then cover A and Z, the two launches with a stream of their own)
-        MI_TRY(mi_msm_enqueue(ctx, 1, -1, 1, pk->pre_b1, ctx->ws[WS_B_WIRES].p, pk->n_b, df | rp, nullptr, false, pk->c_b));
-        gates.arm(2);
-        return mi_msm_enqueue(ctx, 2, 1, 2, pk->pre_b2, nullptr, pk->n_b, df | rp, nullptr, false, pk->c_b);
-    }
-    gates.arm(1);
-    MI_TRY(mi_msm_enqueue(ctx, 1, -1, 1, pk->g1_b, ctx->ws[WS_B_WIRES].p, pk->n_b, df | rp, nullptr, false, 0, 0, pk->gen_c_b));
-    gates.arm(2);
-    return mi_msm_enqueue(ctx, 2, 1, 2, pk->g2_b, nullptr, pk->n_b, df | rp, nullptr, false);
+    // fixed-base tables, or the plain bases on the generic path (with the window bits the parts of a sharded key agree on)
+    const bool tables = pk->pre_b1 != nullptr;
+    const uint32_t precomp_c = tables ? pk->c_b : 0;
+    arm_accum_gate(ctx, MSM_SLOT_B1, accum_gate);
+    // (B1 and K are not timed: their chains interleave on one stream, so the event pair around one's level-1 launch may bracket kernels
+    //  of the other; mi_stats.g1_accum_* then cover A and Z, the two launches with a stream of their own)
+    MI_TRY(mi_msm_enqueue(ctx, MSM_SLOT_B1, -1, 1, tables ? pk->pre_b1 : pk->g1_b, ctx->ws[WS_B_WIRES].p, pk->n_b, fl, nullptr, false, precomp_c, 0, tables ? 0 : pk->gen_c_b));
+    arm_accum_gate(ctx, MSM_SLOT_B2, accum_gate);
+    return mi_msm_enqueue(ctx, MSM_SLOT_B2, MSM_SLOT_B1, 2, tables ? pk->pre_b2 : pk->g2_b, nullptr, pk->n_b, fl, nullptr, false, precomp_c);
 }
-int32_t mi_prove_enqueue_ak_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, hipEvent_t ev_w, bool defer, const std::function<hipEvent_t()> *accum_gate) {
+static int32_t enqueue_ak_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, hipEvent_t ev_w, bool defer, const std::function<hipEvent_t()> *accum_gate) {
     (void)hipSetDevice(ctx->dev);
-    struct Gates { mi_ctx *c; const std::function<hipEvent_t()> *g; void arm(int slot) const { c->msm[slot].accum_gate = g; } } gates{ctx, accum_gate};
-    const uint32_t df = (defer ? MI_MSM_DEFER_REDUCE : 0) | MI_MSM_EXACT_SIZE;
-    const uint32_t rp = pk->rprime ? MI_MSM_PTS_RPRIME : 0;
-    // A and K are both multiplied by W itself: one sort of all wires (slot 0) serves both, against the per-wire expanded
+    const uint32_t fl = (defer ? MI_MSM_DEFER_REDUCE : 0) | MI_MSM_EXACT_SIZE | (pk->rprime ? MI_MSM_PTS_RPRIME : 0);
+    // A and K are both multiplied by W itself: one sort of all wires (A's slot) serves both, against the per-wire expanded
     // point arrays (a wire without a point reads (0,0) = infinity and is skipped); no gather, one sort less
-    if (pk->pre_a) {
-        gates.arm(0);
-        MI_TRY(mi_msm_enqueue(ctx, 0, -1, 1, pk->pre_a, W, pk->nb_wires, df | rp, ev_w, true, pk->c_ak, pk->n_a));
-        gates.arm(3);
-        return mi_msm_enqueue(ctx, 3, 0, 1, pk->pre_k, nullptr, pk->nb_wires, df | rp, nullptr, false, pk->c_ak, pk->n_k);   // (not timed: K and B1 share a stream, msm.hip)
-    }
-    gates.arm(0);
-    MI_TRY(mi_msm_enqueue(ctx, 0, -1, 1, pk->a_full, W, pk->nb_wires, df | rp, ev_w, true, 0, pk->n_a, pk->gen_c_ak));
-    gates.arm(3);
-    return mi_msm_enqueue(ctx, 3, 0, 1, pk->k_full, nullptr, pk->nb_wires, df | rp, nullptr, false, 0, pk->n_k);
+    const bool tables = pk->pre_a != nullptr;
+    const uint32_t precomp_c = tables ? pk->c_ak : 0;
+    arm_accum_gate(ctx, MSM_SLOT_A, accum_gate);
+    MI_TRY(mi_msm_enqueue(ctx, MSM_SLOT_A, -1, 1, tables ? pk->pre_a : (const void *)pk->a_full, W, pk->nb_wires, fl, ev_w, true, precomp_c, pk->n_a, tables ? 0 : pk->gen_c_ak));
+    arm_accum_gate(ctx, MSM_SLOT_K, accum_gate);
+    return mi_msm_enqueue(ctx, MSM_SLOT_K, MSM_SLOT_A, 1, tables ? pk->pre_k : (const void *)pk->k_full, nullptr, pk->nb_wires, fl, nullptr, false, precomp_c, pk->n_k);   // (not timed: K and B1 share a stream, msm.hip)
 }
-// both groups from two helper threads; returns when everything is enqueued
+void WireMsms::start(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, hipEvent_t ev_w, bool defer, const std::function<hipEvent_t()> *accum_gate) {
+    auto group = [&](std::future<int32_t> &f, int32_t (*enqueue)(mi_ctx *, mi_pk *, const mi_fr *, hipEvent_t, bool, const std::function<hipEvent_t()> *)) {
+        try {
+            f = std::async(std::launch::async, [=]() -> int32_t { try { return enqueue(ctx, pk, W, ev_w, defer, accum_gate); } catch (...) { return MI_ENOMEM; } });
+        } catch (...) {   // no thread to be had: this thread does it (without the gate: it would wait for itself); no exception crosses the C-ABI
+            int32_t r = MI_ENOMEM;
+            try { r = enqueue(ctx, pk, W, ev_w, defer, nullptr); } catch (...) {}
+            if (rc_inline == MI_OK) rc_inline = r;
+        }
+    };
+    group(f_b, enqueue_b_msms);
+    group(f_ak, enqueue_ak_msms);
+}
+int32_t WireMsms::join() {
+    int32_t rc = rc_inline;
+    for (std::future<int32_t> *f : {&f_b, &f_ak})
+        if (f->valid()) { const int32_t r = f->get(); if (rc == MI_OK) rc = r; }
+    return rc;
+}
 int32_t mi_prove_enqueue_wire_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, hipEvent_t ev_w, bool defer) {
-    std::future<int32_t> fb;
-    int32_t rb = MI_OK;
-    try {
-        fb = std::async(std::launch::async, [=]() -> int32_t { try { return mi_prove_enqueue_b_msms(ctx, pk, W, ev_w, defer, nullptr); } catch (...) { return MI_ENOMEM; } });
-    } catch (...) {
-        rb = mi_prove_enqueue_b_msms(ctx, pk, W, ev_w, defer, nullptr);
-    }
-    const int32_t ra = mi_prove_enqueue_ak_msms(ctx, pk, W, ev_w, defer, nullptr);
-    if (fb.valid()) rb = fb.get();
-    return ra != MI_OK ? ra : rb;
+    WireMsms wires;
+    wires.start(ctx, pk, W, ev_w, defer, nullptr);
+    return wires.join();
 }
 // the Z MSM over this key's h coefficients against the bit-reversed pk.G1.Z (ev_h = "h is ready")
 int32_t mi_prove_enqueue_z_msm(mi_ctx *ctx, mi_pk *pk, const mi_fr *h, hipEvent_t ev_h, bool defer) {
-    const uint32_t df = (defer ? MI_MSM_DEFER_REDUCE : 0) | (pk->rprime ? MI_MSM_PTS_RPRIME : 0);
-    if (pk->pre_z) return mi_msm_enqueue(ctx, 4, -1, 1, pk->pre_z, h, pk->n_z_msm, df, ev_h, true, pk->c_z);
-    return mi_msm_enqueue(ctx, 4, -1, 1, pk->g1_z, h, pk->n_z_msm, df, ev_h, true, 0, 0, pk->gen_c_z);
+    const uint32_t fl = (defer ? MI_MSM_DEFER_REDUCE : 0) | (pk->rprime ? MI_MSM_PTS_RPRIME : 0);
+    const bool tables = pk->pre_z != nullptr;
+    return mi_msm_enqueue(ctx, MSM_SLOT_Z, -1, 1, tables ? pk->pre_z : pk->g1_z, h, pk->n_z_msm, fl, ev_h, true, tables ? pk->c_z : 0, 0, tables ? 0 : pk->gen_c_z);
 }
 
 // a host helper thread for one independent scalar multiplication; without a thread to be had the work runs here (no exception may
@@ -489,6 +490,13 @@ struct HostInputs { const mi_fr *W, *a, *b, *c; };
 struct WEval { const mi_r1cs *r1cs; bool eval_c; };
 struct AbcGate { const std::function<bool(int)> *abc; /* abc(k): blocks until k of a, b, c are resident */ bool abc_arrived; /* they all were when the job was picked up */ };
 
+// what every prove entry point refuses about the key before anything is enqueued
+static int32_t check_key_fits(mi_ctx *ctx, const mi_pk *pk, size_t n_wires) {
+    if (pk->wire_lo || pk->n_z_msm != ((u64)1 << pk->log_n) - 1) MI_FAIL(ctx, MI_EINVAL, "prove: this key is one part of a sharded key (use mi_groth16_prove_sharded)");
+    if (n_wires != pk->nb_wires) MI_FAIL(ctx, MI_EINVAL, "prove: witness size (n_wires) does not match the proving key");
+    return MI_OK;
+}
+
 // W, a, b, c: device buffers (for host inputs: staging areas the uploads below fill).
 static int32_t prove_common(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wires, const mi_fr *a, const mi_fr *b, const mi_fr *c,
                             size_t n_constraints, const mi_fr *r_m, const mi_fr *s_m, mi_proof_out *out, mi_stats *stats, const HostInputs *host,
@@ -501,16 +509,16 @@ static int32_t prove_common(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wir
     if (host && ((!host->W && n_wires) || (!weval && (!host->a || !host->b) && n_constraints))) MI_FAIL(ctx, MI_EINVAL, "prove: null host W, a or b with a non-zero count");
     const bool derive_c = weval ? !weval->eval_c : host ? !host->c : !c;
     const size_t N = (size_t)1 << pk->log_n;
-    if (pk->wire_lo || pk->n_z_msm != N - 1) MI_FAIL(ctx, MI_EINVAL, "prove: this key is one part of a sharded key (use mi_groth16_prove_sharded)");
-    if (n_wires != pk->nb_wires || n_constraints > N) MI_FAIL(ctx, MI_EINVAL, "prove: witness size does not match the proving key");
+    MI_TRY(check_key_fits(ctx, pk, n_wires));   // (the W-only entry points have asked already, ahead of their own refusals: asked of every arrival here)
+    if (n_constraints > N) MI_FAIL(ctx, MI_EINVAL, "prove: witness size does not match the proving key");
     std::memset(&ctx->stats, 0, sizeof(ctx->stats));
     const auto t_begin = std::chrono::steady_clock::now();
     hipEvent_t *ev = ctx->ev;
-    // Stream plan: computeH on the caller's stream; MSM A, B1, B2, K, Z on slots 0..4 (own streams).  A, B and
+    // Stream plan: computeH on the caller's stream; MSM A, B1, B2, K, Z on their slots (MSM_SLOT_*, own streams).  A, B and
     // K depend only on W and start at once; B2 (G2) reuses B1's sort; Z waits for h.  The latency-bound tails
     // (levels >= 2, bucket reduce, scans) of one MSM overlap the throughput-bound accumulation of the others.
     MI_TRY(mi_reserve(ctx, ctx->ws[WS_H], N * sizeof(Fr)));
-    Fr *h = (Fr *)ctx->ws[WS_H].p;
+    mi_fr *h = (mi_fr *)ctx->ws[WS_H].p;
     // step 4: h = computeH(a, b, c)  (bit-reversed, like gnark leaves it), then the Z MSM over h[:N-1] against the bit-reversed pk.G1.Z
     // "computeH is enqueued and its end event recorded": what the wire MSMs' accumulations wait for (hold, below).  Always fulfilled
     // before the helper threads are joined -- with a null event on a failure path, which releases them without a wait.
@@ -518,23 +526,6 @@ static int32_t prove_common(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wir
     bool h_promised = false;
     const std::shared_future<hipEvent_t> h_fut = h_recorded.get_future().share();
     const std::function<hipEvent_t()> h_gate = [h_fut] { return h_fut.get(); };
-    // the Z MSM's digit count rides in computeH's last launch (mi_ctx::zhook): armed for exactly that launch
-    auto arm_z_count = [&]() -> int32_t { return pk->pre_z ? mi_msm_z_count_arm(ctx, MI_ZHOOK_SLOT, pk->n_z_msm, pk->c_z) : MI_OK; };
-    auto last_part_of_h = [&]() -> int32_t {
-        MI_TRY(arm_z_count());
-        const int32_t rc_h = mi_compute_h_part(ctx, pk->log_n, 3, nullptr, n_constraints, (mi_fr *)h);
-        ctx->zhook.armed = false;
-        return rc_h;
-    };
-    auto enqueue_h_and_z = [&]() -> int32_t {
-        MI_TRY(arm_z_count());
-        const int32_t rc_h = mi_compute_h_dev_impl(ctx, pk->log_n, a, b, derive_c ? nullptr : c, n_constraints, (mi_fr *)h);
-        ctx->zhook.armed = false;
-        MI_TRY(rc_h);
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
-        h_recorded.set_value(ev[3]); h_promised = true;
-        return mi_prove_enqueue_z_msm(ctx, pk, (const mi_fr *)h, ev[3]);
-    };
     // The two wire-MSM groups are enqueued by two helper threads (each waits once for its sort's count pass) while this thread
     // enqueues computeH and the Z MSM -- or is held by the uploads of a, b, c: all sorts start at the head of the proof, beside the NTT.
     // Whatever fails, the helpers are joined and every slot is collected before the error is returned (nothing of this proof may stay
@@ -545,79 +536,16 @@ static int32_t prove_common(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wir
     // accumulations and the GPU idled for 3 ms before the Z accumulation.  Not for host inputs whose a, b, c are still on the PCIe
     // bus: there the accumulations are what fills the GPU meanwhile.
     const bool hold = ctx->hold_accum && !host && (!gate || gate->abc_arrived);
-    std::future<int32_t> f_b, f_ak;
-    int32_t rc_inline = MI_OK;
-    auto start_wires = [&](hipEvent_t ev_w) {   // ev_w: "W is resident" on some stream, or null when the host already knows it is
-        const std::function<hipEvent_t()> *g = hold ? &h_gate : nullptr;
-        try {
-            f_b = std::async(std::launch::async, [=]() -> int32_t { try { return mi_prove_enqueue_b_msms(ctx, pk, W, ev_w, false, g); } catch (...) { return MI_ENOMEM; } });
-        } catch (...) {   // no thread to be had: this thread does it (without the hold: it would wait for itself); no exception crosses the C-ABI
-            rc_inline = mi_prove_enqueue_b_msms(ctx, pk, W, ev_w, false, nullptr);
-        }
-        try {
-            f_ak = std::async(std::launch::async, [=]() -> int32_t { try { return mi_prove_enqueue_ak_msms(ctx, pk, W, ev_w, false, g); } catch (...) { return MI_ENOMEM; } });
-        } catch (...) {
-            const int32_t r = mi_prove_enqueue_ak_msms(ctx, pk, W, ev_w, false, nullptr);
-            if (rc_inline == MI_OK) rc_inline = r;
-        }
-    };
-    auto main_part = [&]() -> int32_t {
-        if (weval) {
-            // W alone: upload it (host inputs) and start the wire MSMs exactly as below; a and b are then evaluated on the context's
-            // stream and computeH runs behind them part by part.  Nothing else crosses the bus, so nothing holds this thread.
-            if (host) {
-                const auto t_up = std::chrono::steady_clock::now();
-                hipStream_t cps = nullptr;
-                MI_TRY(mi_copy_stream(ctx, &cps));
-                MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the staging area may still be read by an earlier call's kernels
-                MI_CHECK_HIP(ctx, hipEventRecord(ev[11], ctx->stream));
-                {
-                    const MiRange range("mi.prove.upload");
-                    if (n_wires) MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)W, host->W, n_wires * sizeof(mi_fr), hipMemcpyHostToDevice, cps));
-                    MI_CHECK_HIP(ctx, hipStreamSynchronize(cps));
-                }
-                ctx->stats.h2d_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
-                start_wires(nullptr);   // W is resident: nothing to wait for
-            } else {
-                MI_CHECK_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
-                start_wires(ev[2]);
-            }
-            const mi_fr *ea = nullptr, *eb = nullptr, *ec = nullptr;
-            MI_TRY(mi_r1cs_eval_ws(ctx, weval->r1cs, W, weval->eval_c, &ea, &eb, &ec));
-            MI_TRY(mi_compute_h_part(ctx, pk->log_n, 0, ea, n_constraints, (mi_fr *)h));
-            MI_TRY(mi_compute_h_part(ctx, pk->log_n, 1, eb, n_constraints, (mi_fr *)h));
-            if (derive_c) MI_TRY(mi_compute_h_part(ctx, pk->log_n, 2, ea, n_constraints, (mi_fr *)h, eb));
-            else MI_TRY(mi_compute_h_part(ctx, pk->log_n, 2, ec, n_constraints, (mi_fr *)h));
-            MI_TRY(last_part_of_h());
-            MI_CHECK_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
-            h_recorded.set_value(ev[3]); h_promised = true;
-            return mi_prove_enqueue_z_msm(ctx, pk, (const mi_fr *)h, ev[3]);
-        }
-        if (gate) {
-            // inputs on their way into HBM (pool upload stage): the wire MSMs start as soon as W is there; a, b, c (3/4 of the bytes)
-            // finish arriving behind them, and computeH waits for exactly that
-            start_wires(nullptr);   // W is resident (the pool synchronised its copy stream before handing the job over)
-            MI_CHECK_HIP(ctx, hipEventRecord(ev[11], ctx->stream));
-            // computeH one vector at a time, as the vectors arrive (the direct host-pointer path below does the same): a's transforms
-            // run while b is on the bus; h is ready ~2.5 ms after the last vector instead of a whole computeH later
-            const auto need = [&](int k) -> int32_t { if (!(*gate->abc)(k)) MI_FAIL(ctx, MI_EHIP, "prove: the upload of a, b, c failed"); return MI_OK; };
-            MI_TRY(need(1));
-            MI_TRY(mi_compute_h_part(ctx, pk->log_n, 0, a, n_constraints, (mi_fr *)h));
-            MI_TRY(need(2));
-            MI_TRY(mi_compute_h_part(ctx, pk->log_n, 1, b, n_constraints, (mi_fr *)h));
-            if (derive_c) MI_TRY(mi_compute_h_part(ctx, pk->log_n, 2, a, n_constraints, (mi_fr *)h, b));
-            else { MI_TRY(need(3)); MI_TRY(mi_compute_h_part(ctx, pk->log_n, 2, c, n_constraints, (mi_fr *)h)); }
-            MI_TRY(last_part_of_h());
-            MI_CHECK_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
-            h_recorded.set_value(ev[3]); h_promised = true;
-            return mi_prove_enqueue_z_msm(ctx, pk, (const mi_fr *)h, ev[3]);
-        }
-        if (!host) {
-            // inputs already in HBM
-            MI_CHECK_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
-            start_wires(ev[2]);
-            return enqueue_h_and_z();
-        }
+    WireMsms wires;
+
+    // How the inputs arrive.  The schedule below is the same for all of them; they differ in what "make it resident" means:
+    //   w_resident(&ev_w)  makes W resident; ev_w = the event the wire MSMs must wait for, null when the host already knows W is there
+    //   make_abc(k)        k = 0, 1, 2: makes a, b, c resident at abc[k]
+    struct { std::function<int32_t(hipEvent_t *)> w_resident; std::function<int32_t(int)> make_abc; } arrival;
+    const mi_fr *abc[3] = {a, b, c};
+    std::chrono::steady_clock::time_point t_up;
+    hipStream_t cps = nullptr;
+    if (host) {
         // inputs in host memory (the cgo path): upload W, start the wire MSMs, and upload a, b, c WHILE they run; the
         // PCIe time of a, b, c (3/4 of the bytes) disappears behind the MSMs instead of preceding the whole proof.  The copies run on
         // the context's copy stream, which carries nothing else, and are ordered by synchronising it on this thread (a pageable copy
@@ -626,47 +554,69 @@ static int32_t prove_common(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wir
         // MSM), so a's inverse and coset transforms start as soon as a is resident (mi_compute_h_part), b's behind b, and what needs
         // all three behind c: h is ready ~2.5 ms after c has crossed instead of a whole computeH later.  (a first: measured 2 ms worse
         // -- the wire MSMs' 14 ms of work then start 5 ms later and nothing else can fill the bus time.)
-        const size_t wb = n_wires * sizeof(mi_fr), cb = n_constraints * sizeof(mi_fr);
-        const auto t_up = std::chrono::steady_clock::now();
-        hipStream_t cps = nullptr;
-        MI_TRY(mi_copy_stream(ctx, &cps));
-        auto upload = [&](const mi_fr *dst, const mi_fr *src, size_t bytes) -> int32_t {
+        // h2d_ms: wall clock from before the first upload to after the last one -- they overlap the wire MSMs.
+        auto upload = [&, ctx](const mi_fr *dst, const mi_fr *src, size_t bytes) -> int32_t {
             const MiRange range("mi.prove.upload");
             if (bytes) MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)dst, src, bytes, hipMemcpyHostToDevice, cps));
             MI_CHECK_HIP(ctx, hipStreamSynchronize(cps));
+            ctx->stats.h2d_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
             return MI_OK;
         };
-        MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the staging area may still be read by an earlier call's kernels
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[11], ctx->stream));
-        MI_TRY(upload(W, host->W, wb));
-        start_wires(nullptr);   // W is resident: nothing to wait for
-        MI_TRY(upload(a, host->a, cb));
-        MI_TRY(mi_compute_h_part(ctx, pk->log_n, 0, a, n_constraints, (mi_fr *)h));
-        MI_TRY(upload(b, host->b, cb));
-        MI_TRY(mi_compute_h_part(ctx, pk->log_n, 1, b, n_constraints, (mi_fr *)h));
-        if (!derive_c) MI_TRY(upload(c, host->c, cb));   // (derive_c: a quarter of the proof's PCIe bytes never crosses)
-        ctx->stats.h2d_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
-        if (derive_c) MI_TRY(mi_compute_h_part(ctx, pk->log_n, 2, a, n_constraints, (mi_fr *)h, b));
-        else MI_TRY(mi_compute_h_part(ctx, pk->log_n, 2, c, n_constraints, (mi_fr *)h));
-        MI_TRY(last_part_of_h());
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
-        h_recorded.set_value(ev[3]); h_promised = true;
-        return mi_prove_enqueue_z_msm(ctx, pk, (const mi_fr *)h, ev[3]);
+        arrival.w_resident = [&, upload](hipEvent_t *ev_w) -> int32_t {
+            t_up = std::chrono::steady_clock::now();
+            MI_TRY(mi_copy_stream(ctx, &cps));
+            MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the staging area may still be read by an earlier call's kernels
+            *ev_w = nullptr;   // once the upload has returned W is resident: nothing to wait for
+            return upload(W, host->W, n_wires * sizeof(mi_fr));
+        };
+        arrival.make_abc = [&, upload](int k) -> int32_t { return upload(abc[k], k == 0 ? host->a : k == 1 ? host->b : host->c, n_constraints * sizeof(mi_fr)); };
+    } else if (gate) {
+        // inputs on their way into HBM (pool upload stage): the wire MSMs start as soon as W is there; a, b, c (3/4 of the bytes)
+        // finish arriving behind them, and computeH waits for exactly that, one vector at a time: a's transforms run while b is on
+        // the bus; h is ready ~2.5 ms after the last vector instead of a whole computeH later
+        arrival.w_resident = [](hipEvent_t *ev_w) -> int32_t { *ev_w = nullptr; return MI_OK; };   // W is resident (the pool synchronised its copy stream before handing the job over)
+        arrival.make_abc = [&](int k) -> int32_t { if (!(*gate->abc)(k + 1)) MI_FAIL(ctx, MI_EHIP, "prove: the upload of a, b, c failed"); return MI_OK; };
+    } else {
+        // inputs already in HBM: the begin event orders the wire MSMs behind whatever wrote W on the context's stream
+        arrival.w_resident = [&](hipEvent_t *ev_w) -> int32_t { *ev_w = ev[EV_PROVE_BEGIN]; return MI_OK; };
+        arrival.make_abc = [](int) -> int32_t { return MI_OK; };
+    }
+    // W alone, from host or device memory: a and b (and c) are evaluated on the context's stream, behind the start of the wire MSMs,
+    // and computeH runs behind them part by part.  Nothing but W crosses the bus, so nothing holds this thread.
+    if (weval) arrival.make_abc = [&](int k) -> int32_t { return k ? MI_OK : mi_r1cs_eval_ws(ctx, weval->r1cs, W, weval->eval_c, &abc[0], &abc[1], &abc[2]); };
+
+    auto main_part = [&]() -> int32_t {
+        MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_PROVE_BEGIN], ctx->stream));
+        hipEvent_t ev_w = nullptr;
+        MI_TRY(arrival.w_resident(&ev_w));
+        wires.start(ctx, pk, W, ev_w, false, hold ? &h_gate : nullptr);
+        MI_TRY(arrival.make_abc(0));
+        MI_TRY(mi_compute_h_part(ctx, pk->log_n, 0, abc[0], n_constraints, h));
+        MI_TRY(arrival.make_abc(1));
+        MI_TRY(mi_compute_h_part(ctx, pk->log_n, 1, abc[1], n_constraints, h));
+        if (derive_c) MI_TRY(mi_compute_h_part(ctx, pk->log_n, 2, abc[0], n_constraints, h, abc[1]));   // c = a o b on the device: c is never asked for (a quarter of a host proof's PCIe bytes never crosses)
+        else { MI_TRY(arrival.make_abc(2)); MI_TRY(mi_compute_h_part(ctx, pk->log_n, 2, abc[2], n_constraints, h)); }
+        // the Z MSM's digit count rides in computeH's last launch (mi_ctx::zhook): armed for exactly that launch
+        if (pk->pre_z) MI_TRY(mi_msm_z_count_arm(ctx, MSM_SLOT_Z, pk->n_z_msm, pk->c_z));
+        const int32_t rc_h = mi_compute_h_part(ctx, pk->log_n, 3, nullptr, n_constraints, h);
+        ctx->zhook.armed = false;
+        MI_TRY(rc_h);
+        MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_H_READY], ctx->stream));
+        h_recorded.set_value(ev[EV_H_READY]); h_promised = true;
+        return mi_prove_enqueue_z_msm(ctx, pk, h, ev[EV_H_READY]);
     };
     {
         int32_t rc = main_part();
-        if (rc == MI_OK) rc = rc_inline;
         if (!h_promised) h_recorded.set_value(nullptr);   // a failure before computeH's event: release the helpers
-        if (f_b.valid()) { const int32_t r = f_b.get(); if (rc == MI_OK) rc = r; }
-        if (f_ak.valid()) { const int32_t r = f_ak.get(); if (rc == MI_OK) rc = r; }
+        { const int32_t r = wires.join(); if (rc == MI_OK) rc = r; }
         // a digit count computeH's last launch produced for a Z sort that never came must not meet a later sort of the same shape
         // (the sort also compares the counted vector's address)
-        if (rc != MI_OK) ctx->zhook.armed = ctx->zhook.done = false;
         if (rc != MI_OK) {
+            ctx->zhook.armed = ctx->zhook.done = false;
             const std::string keep = ctx->err;   // the collection below may overwrite it
             G1X t1; G2X t2;
-            for (int sl : {0, 1, 3, 4}) (void)mi_msm_finish(ctx, sl, 1, &t1);
-            (void)mi_msm_finish(ctx, 2, 2, &t2);
+            for (int sl : {MSM_SLOT_A, MSM_SLOT_B1, MSM_SLOT_K, MSM_SLOT_Z}) (void)mi_msm_finish(ctx, sl, 1, &t1);
+            (void)mi_msm_finish(ctx, MSM_SLOT_B2, 2, &t2);
             (void)hipStreamSynchronize(ctx->stream);
             mi_set_err(ctx, keep);
             return rc;
@@ -678,13 +628,13 @@ static int32_t prove_common(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wir
     // step 7: collect the five MSMs
     G1X msm_a, msm_b1, msm_k, msm_z;
     G2X msm_b2;
-    MI_TRY(mi_msm_finish(ctx, 0, 1, &msm_a));
-    MI_TRY(mi_msm_finish(ctx, 1, 1, &msm_b1));
+    MI_TRY(mi_msm_finish(ctx, MSM_SLOT_A, 1, &msm_a));
+    MI_TRY(mi_msm_finish(ctx, MSM_SLOT_B1, 1, &msm_b1));
     const auto t_asm0 = std::chrono::steady_clock::now();
     as.have_a_b1(msm_a, msm_b1);
-    MI_TRY(mi_msm_finish(ctx, 3, 1, &msm_k));
-    MI_TRY(mi_msm_finish(ctx, 2, 2, &msm_b2));
-    MI_TRY(mi_msm_finish(ctx, 4, 1, &msm_z));
+    MI_TRY(mi_msm_finish(ctx, MSM_SLOT_K, 1, &msm_k));
+    MI_TRY(mi_msm_finish(ctx, MSM_SLOT_B2, 2, &msm_b2));
+    MI_TRY(mi_msm_finish(ctx, MSM_SLOT_Z, 1, &msm_z));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const auto t_gpu_done = std::chrono::steady_clock::now();
     { const MiRange range("mi.prove.assemble"); as.finish(msm_k, msm_b2, msm_z, out); }
@@ -694,16 +644,15 @@ static int32_t prove_common(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wir
         return std::chrono::duration<float, std::milli>(y - x).count();
     };
     auto slot_ms = [&](int slot, float *dst) -> int32_t {
-        MI_CHECK_HIP(ctx, hipEventElapsedTime(dst, ctx->msm[slot].ev[3], ctx->msm[slot].ev[4]));
+        MI_CHECK_HIP(ctx, hipEventElapsedTime(dst, ctx->msm[slot].ev[MSM_EV_JOB_BEGIN], ctx->msm[slot].ev[MSM_EV_JOB_END]));
         return MI_OK;
     };
     // per-phase spans overlap (five streams): they do not add up to total_ms
-    MI_CHECK_HIP(ctx, hipEventElapsedTime(&st.compute_h_ms, (host || gate) ? ev[11] : ev[2], ev[3]));
-    // (h2d_ms of the host-pointer path: wall clock of the uploads, set above -- they overlap the wire MSMs)
-    if (pk->nb_wires) MI_TRY(slot_ms(0, &st.msm_a_ms));
-    if (pk->n_b) { MI_TRY(slot_ms(1, &st.msm_b1_ms)); MI_TRY(slot_ms(2, &st.msm_b2_ms)); }
-    if (pk->nb_wires) MI_TRY(slot_ms(3, &st.msm_k_ms));
-    if (N > 1) MI_TRY(slot_ms(4, &st.msm_z_ms));
+    MI_CHECK_HIP(ctx, hipEventElapsedTime(&st.compute_h_ms, ev[EV_PROVE_BEGIN], ev[EV_H_READY]));
+    if (pk->nb_wires) MI_TRY(slot_ms(MSM_SLOT_A, &st.msm_a_ms));
+    if (pk->n_b) { MI_TRY(slot_ms(MSM_SLOT_B1, &st.msm_b1_ms)); MI_TRY(slot_ms(MSM_SLOT_B2, &st.msm_b2_ms)); }
+    if (pk->nb_wires) MI_TRY(slot_ms(MSM_SLOT_K, &st.msm_k_ms));
+    if (N > 1) MI_TRY(slot_ms(MSM_SLOT_Z, &st.msm_z_ms));
     st.assemble_ms = ms(t_gpu_done, t_end);     // host work left after the last MSM landed
     st.filter_ms = ms(t_asm0, t_gpu_done);      // host blinding work hidden under the GPU
     st.total_ms = ms(t_begin, t_end);
@@ -723,8 +672,7 @@ static int32_t check_w_inputs(mi_ctx *ctx, const mi_pk *pk, const mi_r1cs *r1cs,
     if (!W) MI_FAIL(ctx, MI_EINVAL, "prove_w: W is null");
     if (flags & ~MI_PROVE_W_EVAL_C) MI_FAIL(ctx, MI_EINVAL, "prove_w: unknown flag");
     if (r1cs->dev != ctx->dev) MI_FAIL(ctx, MI_EINVAL, "prove_w: the r1cs was loaded on another device");
-    if (pk->wire_lo || pk->n_z_msm != ((u64)1 << pk->log_n) - 1) MI_FAIL(ctx, MI_EINVAL, "prove_w: this key is one part of a sharded key");
-    if (n_wires != pk->nb_wires) MI_FAIL(ctx, MI_EINVAL, "prove_w: n_wires does not match the proving key");
+    MI_TRY(check_key_fits(ctx, pk, n_wires));
     if (n_wires != r1cs->nb_wires) MI_FAIL(ctx, MI_EINVAL, "prove_w: n_wires does not match the r1cs");
     if (pk->log_n != r1cs->log_n) MI_FAIL(ctx, MI_EINVAL, "prove_w: the key's log_n is not the domain of the r1cs's n_constraints");
     return MI_OK;

@@ -43,25 +43,33 @@ struct ShardRange { u64 w_lo, w_hi, z_lo, z_hi; };   // wires [w_lo, w_hi), Z pa
 int32_t mi_pk_load_range(mi_ctx *ctx, const mi_pk_desc *d, mi_pk **out, bool device_points, const ShardRange *sr, bool adopt = false, bool *took_arrays = nullptr);
 // a Pedersen key over device arrays the key takes ownership of (mi_pk_load_raw)
 extern "C" int32_t mi_pedersen_pk_adopt(mi_ctx *ctx, void *basis_dev, void *basis_exp_sigma_dev, size_t n, mi_pedersen_pk **out);
-// ProveKnowledge of one BSB22 commitment in two halves on slot 5 of ctx (beside a proof's five MSMs): host values in, affine point out
+// ProveKnowledge of one BSB22 commitment in two halves on MSM_SLOT_POK of ctx (beside a proof's five MSMs): host values in, affine point out
 int32_t mi_pedersen_pok_enqueue(mi_ctx *ctx, mi_pedersen_pk *pk, const mi_fr *values, size_t n);
 int32_t mi_pedersen_pok_collect(mi_ctx *ctx, mi_g1_affine *pok_or_null);
-// The wire MSMs (A, B1, B2, K on slots 0..3) over W_dev = this key's wire range, ordered after ev_w; the Z MSM (slot 4) over
+// The wire MSMs (MSM_SLOT_A, _B1, _B2, _K) over W_dev = this key's wire range, ordered after ev_w; the Z MSM (MSM_SLOT_Z) over
 // h_dev = this key's first h coefficient, ordered after ev_h.  defer_reduce: stop each MSM at its bucket sums (group.hip
 // exchanges them between devices before the reduce, SURVEY 8e option ii).
-int32_t mi_prove_enqueue_wire_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W_dev, hipEvent_t ev_w, bool defer_reduce = false);
-// its two halves, each with one sort and one host-side wait for that sort's count pass: B1 + B2 (slots 1, 2), A + K (slots 0, 3).
-// Independent of each other (own slots, own buffers): safe to call from two threads at once.
-// accum_gate (may be null): MsmSlot::accum_gate for the group's two slots -- the sorts are enqueued at once, the bucket accumulations
+// The wire MSMs are two independent groups, each with one sort and one host-side wait for that sort's count pass: B1 + B2 and A + K
+// (own slots, own buffers: safe to enqueue from two threads at once).  start() hands each group to a helper thread and returns at
+// once; join() waits for both and returns the first failure.  A group for which no thread can be had is enqueued by start() on the
+// calling thread, without the gate (the caller would wait for itself); no exception crosses either call.
+// accum_gate (may be null): MsmSlot::accum_gate for the four slots -- the sorts are enqueued at once, the bucket accumulations
 // behind the event it returns.
-int32_t mi_prove_enqueue_b_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W_dev, hipEvent_t ev_w, bool defer_reduce = false, const std::function<hipEvent_t()> *accum_gate = nullptr);
-int32_t mi_prove_enqueue_ak_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W_dev, hipEvent_t ev_w, bool defer_reduce = false, const std::function<hipEvent_t()> *accum_gate = nullptr);
+struct WireMsms {
+    std::future<int32_t> f_b, f_ak;
+    int32_t rc_inline = MI_OK;
+    void start(mi_ctx *ctx, mi_pk *pk, const mi_fr *W_dev, hipEvent_t ev_w, bool defer_reduce, const std::function<hipEvent_t()> *accum_gate);
+    int32_t join();
+};
+// start() and join() in one call
+int32_t mi_prove_enqueue_wire_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W_dev, hipEvent_t ev_w, bool defer_reduce = false);
 int32_t mi_prove_enqueue_z_msm(mi_ctx *ctx, mi_pk *pk, const mi_fr *h_dev, hipEvent_t ev_h, bool defer_reduce = false);
 
-// mi_groth16_prove_dev over inputs that are still arriving in HBM (the prover pool's upload stage): W is resident; the wire MSMs are
-// enqueued at once; abc_ready(k) must block until k of a, b, c (in that order) are resident (false = their upload failed): computeH is
-// enqueued one vector at a time behind them (k = 3 is never asked for when c is null).  abc_arrived: they all were when the job was
-// picked up (the steady state).  Same proof bytes.
+// mi_groth16_prove_dev over inputs that are still arriving in HBM (the prover pool's upload stage): the one schedule of prove_common
+// (prove.hip) with W resident when the call is made -- the wire MSMs are enqueued at once, with nothing to wait for -- and
+// abc_ready(k), k = 1, 2, 3, asked right before computeH's part for a, b, c is enqueued: it must block until k of a, b, c (in that
+// order) are resident (false = their upload failed; k = 3 is never asked for when c is null).  abc_arrived: they all were when the job
+// was picked up (the steady state): only then may the wire MSMs' accumulations be held back for computeH.  Same proof bytes.
 int32_t mi_groth16_prove_dev_gated(mi_ctx *ctx, mi_pk *pk, const mi_fr *W_dev, size_t n_wires, const mi_fr *a_dev, const mi_fr *b_dev, const mi_fr *c_dev,
                                    size_t n_constraints, const mi_fr *r, const mi_fr *s, mi_proof_out *out, mi_stats *stats,
                                    const std::function<bool(int)> &abc_ready, bool abc_arrived);

@@ -263,32 +263,32 @@ int32_t mi_g2_add_dev(mi_ctx *ctx, mi_g2_affine *out, const mi_g2_affine *a, con
 }
 int32_t mi_bench_modmul_dev(mi_ctx *ctx, int field, size_t n_threads, uint32_t iters, void *scratch_dev, float *ms_out) {
     if (!ctx || !scratch_dev || !ms_out || n_threads % 256) return MI_EINVAL;
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T0], ctx->stream));
     if (field == 0) hipLaunchKernelGGL(k_bench_modmul<FrParams>, dim3((unsigned)(n_threads / 256)), dim3(256), 0, ctx->stream, (Fr *)scratch_dev, iters);
     else hipLaunchKernelGGL(k_bench_modmul<FpParams>, dim3((unsigned)(n_threads / 256)), dim3(256), 0, ctx->stream, (Fp *)scratch_dev, iters);
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    MI_CHECK_HIP(ctx, hipEventSynchronize(ctx->ev[1]));
-    MI_CHECK_HIP(ctx, hipEventElapsedTime(ms_out, ctx->ev[0], ctx->ev[1]));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T1], ctx->stream));
+    MI_CHECK_HIP(ctx, hipEventSynchronize(ctx->ev[EV_T1]));
+    MI_CHECK_HIP(ctx, hipEventElapsedTime(ms_out, ctx->ev[EV_T0], ctx->ev[EV_T1]));
     return MI_OK;
 }
 // random 64-byte gathers from a table of n_entries 64-B entries (no arithmetic): the memory system's ceiling for the MSM's
 // level-1 accumulation, which gathers one 64-B point per mixed addition from tables far larger than the 256 MB Infinity Cache
 int32_t mi_bench_gather_dev(mi_ctx *ctx, const void *table_dev, size_t n_entries, size_t n_threads, uint32_t iters, void *scratch_dev, float *ms_out) {
     if (!ctx || !table_dev || !scratch_dev || !ms_out || n_threads % 64 || n_entries < 2 || (n_entries & (n_entries - 1))) return MI_EINVAL;
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T0], ctx->stream));
     hipLaunchKernelGGL(k_bench_gather, dim3((unsigned)(n_threads / 64)), dim3(64), 0, ctx->stream, (const uint4 *)table_dev, (u64)(n_entries - 1), iters, (uint4 *)scratch_dev);
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    MI_CHECK_HIP(ctx, hipEventSynchronize(ctx->ev[1]));
-    MI_CHECK_HIP(ctx, hipEventElapsedTime(ms_out, ctx->ev[0], ctx->ev[1]));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T1], ctx->stream));
+    MI_CHECK_HIP(ctx, hipEventSynchronize(ctx->ev[EV_T1]));
+    MI_CHECK_HIP(ctx, hipEventElapsedTime(ms_out, ctx->ev[EV_T0], ctx->ev[EV_T1]));
     return MI_OK;
 }
 int32_t mi_bench_valu_dev(mi_ctx *ctx, int kind, size_t n_threads, uint32_t iters, void *scratch_dev, float *ms_out) {
     if (!ctx || !scratch_dev || !ms_out || n_threads % 256) return MI_EINVAL;
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T0], ctx->stream));
     hipLaunchKernelGGL(k_bench_valu, dim3((unsigned)(n_threads / 256)), dim3(256), 0, ctx->stream, kind, iters, (u64 *)scratch_dev);
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    MI_CHECK_HIP(ctx, hipEventSynchronize(ctx->ev[1]));
-    MI_CHECK_HIP(ctx, hipEventElapsedTime(ms_out, ctx->ev[0], ctx->ev[1]));
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T1], ctx->stream));
+    MI_CHECK_HIP(ctx, hipEventSynchronize(ctx->ev[EV_T1]));
+    MI_CHECK_HIP(ctx, hipEventElapsedTime(ms_out, ctx->ev[EV_T0], ctx->ev[EV_T1]));
     return MI_OK;
 }
 }

@@ -150,7 +150,8 @@ int32_t mi_debug_set_knob(mi_ctx *ctx, const char *name, int64_t value);
 /* Counters the tests read to prove that an optional path really ran: "z_count_fused_launches" = computeH last launches of this context that
  * carried the Z MSM's digit count (knob "z_count_fused"); "dense_item_sorts" = bucket accumulations whose level-1 item size the dense-sort rule
  * chose (knob "dense_item_l1"); "generic_sorts_two_pass" / "generic_sorts_one_pass" = generic (no-table) MSM sorts that took the LDS-staged
- * two-pass sort (c = 16, 2^18 <= n, 16 n < 2^31) / the one-pass counting sort.  MI_EINVAL for an unknown name. */
+ * two-pass sort (c = 16, 2^18 <= n, 16 n < 2^31) / the one-pass counting sort; "hip_failure_countdown" = checked calls still to pass before
+ * the failure armed by mi_debug_inject_hip_failure (process-wide; 0 = disarmed or spent).  MI_EINVAL for an unknown name. */
 int32_t mi_debug_get_counter(mi_ctx *ctx, const char *name, uint64_t *out);
 /* Process-wide, for contexts created afterwards: how the MSM slots of a context share streams (0: K's stream created, destroyed and
  * pointed at B1's, as rounds 4-5 did; 1, the default: never created; 2: A, B1 and K on one stream).  Same results; an experiment on which
