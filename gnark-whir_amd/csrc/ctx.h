@@ -82,13 +82,23 @@ enum {
     MSM_EV_MAX_LANDED = 6, // the fullest bucket's size has landed in host memory (exact level count, msm.hip)
     MSM_EV_COUNT = 7
 };
+enum { B_DIGITS, B_H, B_S, B_SORTED, B_LEVELS, B_PART0, B_PART1, B_BUCKET, B_SCAN, B_WIN, B_PVAL, B_C1, B_CHUNKS, B_ITEMTAB, B_MAX, B_BA_NODES, B_BA_PREFIX, B_BA_TOT, B_COUNT_ };   // MsmSlot::buf[]: the slot's device workspaces (msm.hip)
+// MsmSlot::host_wsum, pinned host memory: the window sums the last sum tree (or a copy) stores, then words that kernels of the slot's SORT store (k_scan_final)
+struct MsmHostWords {
+    unsigned char wsum[128][256];             // <= 128 XYZZ window sums, packed from byte 0: 128 B each (G1) or 256 B (G2)
+    uint32_t entries, pad0_[3];               // sorted entries = non-zero digits (the key scan's total)
+    uint32_t exact_total, pad1_[3];           // the count pass's total, fetched before the workspaces are sized (MI_MSM_EXACT_SIZE)
+    uint32_t max_bucket, pad2_[7];            // entries of the fullest bucket; lands with ev[MSM_EV_MAX_LANDED]
+};
+static_assert(offsetof(MsmHostWords, entries) == sizeof(MsmHostWords::wsum) && offsetof(MsmHostWords, exact_total) == offsetof(MsmHostWords, entries) + 16 &&
+              offsetof(MsmHostWords, max_bucket) == offsetof(MsmHostWords, entries) + 32 && sizeof(MsmHostWords) == 128 * 256 + 64, "the words lie where the kernels store them");
 struct MsmSlot {            // one in-flight MSM (msm.hip): own stream, events, workspaces, pinned result
     hipStream_t stream = nullptr;
     hipEvent_t ev[MSM_EV_COUNT]{};
     bool max_pending = false;       // this slot's sort has a "largest bucket" word on its way to the host (ev[MSM_EV_MAX_LANDED])
     uint32_t max_key_count = 0;     // entries of the fullest bucket of this slot's sort, once fetched
-    DevBuf buf[18];
-    void *host_wsum = nullptr;
+    DevBuf buf[B_COUNT_];
+    MsmHostWords *host_wsum = nullptr;
     uint32_t n = 0, c = 0, G = 0;
     uint64_t entries_cap = 0;   // entries the sort of this slot is sized for: windows * n, or the counted number (MI_MSM_EXACT_SIZE)
     uint64_t stat_pairs = 0;    // (point, scalar) pairs this MSM really has (A and K run over per-wire expanded arrays with holes)
@@ -140,8 +150,8 @@ struct mi_ctx {
 
 static_assert(sizeof(mi_ctx::ws) == WS_COUNT * sizeof(DevBuf) && WS_RPRIME == WS_COUNT - 1, "WS_* names every slot of mi_ctx::ws up to its end");
 static_assert(EV_R1CS_END < EV_COUNT && sizeof(mi_ctx::ev) == EV_COUNT * sizeof(hipEvent_t), "EV_* index mi_ctx::ev");
-static_assert(MSM_SLOT_POK == MI_MSM_SLOTS - 1 && sizeof(mi_ctx::msm) == MI_MSM_SLOTS * sizeof(MsmSlot) && MSM_EV_MAX_LANDED == MSM_EV_COUNT - 1,
-              "MSM_SLOT_* name every slot of mi_ctx::msm, MSM_EV_* every event of a slot");
+static_assert(MSM_SLOT_POK == MI_MSM_SLOTS - 1 && sizeof(mi_ctx::msm) == MI_MSM_SLOTS * sizeof(MsmSlot) && MSM_EV_MAX_LANDED == MSM_EV_COUNT - 1 &&
+              sizeof(MsmSlot::buf) == B_COUNT_ * sizeof(DevBuf), "MSM_SLOT_* name every slot of mi_ctx::msm, MSM_EV_* every event of a slot, B_* every workspace");
 
 // Fault injection for the error-path tests (mi_debug_inject_hip_failure, api.hip): the n-th MI_CHECK_HIP from now reports
 // hipErrorUnknown INSTEAD of running its call.  Disabled (<= 0) it costs one relaxed atomic load per checked call.

@@ -17,6 +17,7 @@
 #include "msm2_core.cuh"
 #include "scan_u32.cuh"
 #include "msm_curve_ops.h"
+#include <algorithm>
 #include <cstring>
 #include <cstdlib>
 #include <new>
@@ -324,8 +325,6 @@ __global__ void __launch_bounds__(64) k_msm_finish_list(u32 nkeys, const u32 *it
 // mi_msm_finish.  Several slots run concurrently (prove.hip puts the five MSMs on five streams so the
 // latency-bound tails of one overlap the throughput-bound accumulation of another), and an accumulate
 // stage may reuse another slot's sort (pk.G1.B and pk.G2.B are multiplied by the same scalars).
-struct LevelArrays { u32 *start, *cnt, *items, *item_start; };
-
 static u32 auto_c(u32 n) {
     u32 lg = 0;
     while ((2u << lg) <= n) lg++;          // floor(log2 n) for n >= 1
@@ -409,7 +408,7 @@ int32_t mi_msm_state_init(mi_ctx *ctx) {
     ctx->msm[MSM_SLOT_K].stream = ctx->msm[MSM_SLOT_B1].stream;
     for (auto &sl : ctx->msm) {
         for (auto &e : sl.ev) MI_CHECK_HIP(ctx, hipEventCreate(&e));
-        MI_CHECK_HIP(ctx, hipHostMalloc(&sl.host_wsum, 128 * 256 + 64));
+        MI_CHECK_HIP(ctx, hipHostMalloc(&sl.host_wsum, sizeof(MsmHostWords)));
     }
     return MI_OK;
 }
@@ -423,10 +422,6 @@ void mi_msm_state_free(mi_ctx *ctx) {
     }
 }
 
-// slot buffers
-enum { B_DIGITS, B_H, B_S, B_SORTED, B_LEVELS, B_PART0, B_PART1, B_BUCKET, B_SCAN, B_WIN, B_PVAL, B_C1, B_CHUNKS, B_ITEMTAB, B_MAX, B_BA_NODES, B_BA_PREFIX, B_BA_TOT, B_COUNT_ };
-static_assert(B_COUNT_ <= sizeof(MsmSlot::buf) / sizeof(DevBuf), "MsmSlot::buf is too small");
-
 // The fullest bucket of a sort: per-key totals -> one word (atomicMax), copied to pinned host memory behind the slot's ev[MSM_EV_MAX_LANDED].  The item
 // machinery needs ceil(log_L(fullest bucket)) levels; the worst case (every entry in one bucket) says 9 at N = 2^23 where uniform
 // scalars need 3 and the WHIR mix 7, and every unneeded level is three launches of empty kernels on the MSM's tail.  The host waits for
@@ -438,8 +433,8 @@ __global__ void __launch_bounds__(256) k_max_u32(const u32 *v, u32 n, u32 *out) 
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
 // totals == nullptr: the word at sl.buf[B_MAX] has been computed already (k_msm2_colsum); only the copy and the event are enqueued
-// Then the scan of the per-key totals -> keystart, whose last kernel ALSO leaves that word (host_wsum + 128*256 + 32) and the number of
-// sorted entries (host_wsum + 128*256) in the slot's pinned host memory: no copy launches (k_scan_final); ev[MSM_EV_MAX_LANDED] follows the scan.
+// Then the scan of the per-key totals -> keystart, whose last kernel ALSO leaves that word (host_wsum->max_bucket) and the number of
+// sorted entries (host_wsum->entries) in the slot's pinned host memory: no copy launches (k_scan_final); ev[MSM_EV_MAX_LANDED] follows the scan.
 // sums_ready: the scan's block sums are in sl.buf[B_SCAN] already (k_msm2_colsum added them up): only the scan's last kernel is launched.
 static int32_t fetch_max_and_scan_keys(mi_ctx *ctx, MsmSlot &sl, const u32 *totals, u32 nkeys, u32 *keystart, bool compute_max, bool sums_ready = false) {
     MI_TRY(mi_reserve(ctx, sl.buf[B_MAX], 64));
@@ -447,131 +442,113 @@ static int32_t fetch_max_and_scan_keys(mi_ctx *ctx, MsmSlot &sl, const u32 *tota
     hipStream_t st = sl.stream;
     if (compute_max) {
         MI_CHECK_HIP(ctx, hipMemsetAsync(dmax, 0, 4, st));
-        unsigned grid = (nkeys + 255) / 256;
-        if (grid > 1024) grid = 1024;
-        hipLaunchKernelGGL(k_max_u32, dim3(grid), dim3(256), 0, st, totals, nkeys, dmax);
+        hipLaunchKernelGGL(k_max_u32, dim3(std::min((nkeys + 255) / 256, 1024u)), dim3(256), 0, st, totals, nkeys, dmax);
         MI_CHECK_HIP(ctx, hipGetLastError());
     }
-    char *host = (char *)sl.host_wsum + 128 * 256;
-    if (sums_ready) {
-        const u32 nblocks = (nkeys + SCAN_BLOCK - 1) / SCAN_BLOCK;
-        hipLaunchKernelGGL(k_scan_final, dim3(nblocks), dim3(SCAN_THREADS), 0, st, totals, (size_t)nkeys, (const u32 *)sl.buf[B_SCAN].p, keystart, 2, (u32 *)host, (const u32 *)dmax,
-                           (u32 *)(host + 32));
-        MI_CHECK_HIP(ctx, hipGetLastError());
-    } else {
-        MI_TRY(exclusive_scan(ctx, st, totals, nkeys, keystart, sl.buf[B_SCAN], (u32 *)host, dmax, (u32 *)(host + 32)));
-    }
+    MI_TRY(exclusive_scan(ctx, st, totals, nkeys, keystart, sl.buf[B_SCAN], &sl.host_wsum->entries, dmax, &sl.host_wsum->max_bucket, sums_ready));
     MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_MAX_LANDED], st));
     sl.max_pending = true;
     return MI_OK;
 }
 
-// Runs levels of the item machinery over `nkeys` keys whose level-0 decomposition (start/cnt/items) is
-// already in cur.  Level 0 reads (pts, sorted) when pts != null, else partial_first.
-static int32_t run_levels(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &sl, u32 nkeys, LevelArrays cur, LevelArrays nxt, u64 first_items_bound,
-                          u64 max_count, u32 L_first, u32 L_next, const void *pts, const u32 *sorted, const void *partial_first,
-                          void *final_out, bool time_first, bool rprime = false, bool first_sums_ready = false) {
+struct LevelPlan {   // what msm_accum_enqueue decides for run_levels
+    u32 L_first, L_next;                  // entries per level-1 item, partial sums per item of the levels above
+    u64 first_items_bound, max_count;     // bounds on the items of level 1 and on the entries of the fullest key
+    const void *pts; const u32 *sorted;   // level 1's input
+    void *final_out;                      // the bucket sums (+ the finisher's counters behind them)
+    bool time_first, rprime, first_sums_ready;   // ev[MSM_EV_L1_*] around level 1; points in the R' form; k_msm_prep1_sums left level 1's block sums in B_SCAN
+};
+// How level 1 runs on this slot (launcher, form, grid cap: from the knobs, the curve and the slot), its scratch reserved.  Asked once per accumulate stage.
+struct Level1Choice {
+    bool rp_path, use_ba;   // the 29-bit kernels (accum_affine_rp) / their batch-affine variant (accum_affine_ba)
+    MsmLevel1Form form;
+    u32 grid_cap, ba_waves;
+    MsmBaScratch ba;
+};
+static int32_t choose_level1(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &sl, u32 nkeys, const LevelPlan &p, Level1Choice &c) {
+    const MsmKnobs *kn = knobs_of(ctx);
+    const bool g2 = ops.curve == 2;
+    const u64 items = p.first_items_bound + 1;
+    c.rp_path = p.rprime && ops.accum_affine_rp;
+    // partial sums between the levels in the packed R' form (curve29.cuh) when level 1 runs in 29-bit limbs and the curve has the upper-level kernel
+    c.form.rp_partials = c.rp_path && ops.accum_xyzz_rp && !kn->std_partials;
+    // which build of the G1 level-1 kernel: three waves per SIMD (168 VGPRs: a SIMD's register file is full, and a freed wave slot
+    // is too small for any 256-VGPR G2 workgroup, which then waits for the END of this launch) or two (196: one freed slot admits one)
+    c.form.waves_per_simd = !g2 && (kn->l1_waves == 2 || (kn->z_waves == 2 && &sl == &ctx->msm[MSM_SLOT_Z])) ? 2u : 3u;
+    c.form.wg_waves = g2 ? kn->g2_wg : kn->l1_wg;
+    // (level-1 launches on lowest-priority streams of their own measured -6 % proofs/s, profiles/r05_ab_evidence.txt: removed)
+    const u32 capx = g2 ? kn->g2_grid_per_cu : kn->g1_grid_per_cu;   // knobs: resident-grid cap per CU of the level-1 kernels (0 = every level's 128)
+    c.grid_cap = (u32)ctx->cu_count * (capx ? capx : 128u);
+    // batch-affine rounds (msm_ba_g1.cuh) where the buckets hold a few items each (>= 32 entries on average) and the scratch fits
+    c.ba_waves = (u32)ctx->cu_count * 16;
+    const size_t ba_tot = msm_ba_scratch_bytes(items, c.ba_waves);
+    c.use_ba = c.rp_path && kn->ba_rounds && ops.accum_affine_ba && p.L_first == 16 && p.first_items_bound >= (u64)nkeys * 3 &&
+               mi_try_reserve(sl.buf[B_BA_NODES], items * 512) && mi_try_reserve(sl.buf[B_BA_PREFIX], items * 256) && mi_try_reserve(sl.buf[B_BA_TOT], 2 * ba_tot);
+    c.ba = MsmBaScratch{sl.buf[B_BA_NODES].p, sl.buf[B_BA_PREFIX].p, sl.buf[B_BA_TOT].p, (char *)sl.buf[B_BA_TOT].p + ba_tot};
+    if (c.rp_path) MI_TRY(mi_reserve(ctx, sl.buf[B_ITEMTAB], items * 16));
+    return MI_OK;
+}
+
+// Runs levels of the item machinery over `nkeys` keys whose level-1 decomposition (start/cnt/items) is in cur: reserve the output, launch the level, then the finisher or the next level
+static int32_t run_levels(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &sl, u32 nkeys, LevelArrays cur, LevelArrays nxt, const LevelPlan &p) {
     hipStream_t st = sl.stream;
-    const void *pin = partial_first;
-    u64 items_bound = first_items_bound;
-    u64 m = max_count;  // bound on entries of the largest key at this level
-    u32 L = L_first;
+    u64 items_bound = p.first_items_bound, m = p.max_count;  // bounds on the items and on the entries of the largest key at this level
     const u32 scan_blocks = (nkeys + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    // partial sums between the levels in the packed R' form (curve29.cuh) when level 1 runs in 29-bit limbs and the curve has the
-    // matching upper-level kernel
-    const bool rp_partials = pts && rprime && ops.accum_affine_rp && ops.accum_xyzz_rp && !knobs_of(ctx)->std_partials;
-    if (first_sums_ready) {   // (k_msm_prep1_sums left the block sums of cur.items in B_SCAN)
-        hipLaunchKernelGGL(k_scan_final, dim3(scan_blocks), dim3(SCAN_THREADS), 0, st, cur.items, (size_t)nkeys, (const u32 *)sl.buf[B_SCAN].p, cur.item_start, 2, nullptr, nullptr, nullptr);
-        MI_CHECK_HIP(ctx, hipGetLastError());
-    } else {
-        MI_TRY(exclusive_scan(ctx, st, cur.items, nkeys, cur.item_start, sl.buf[B_SCAN]));
-    }
+    Level1Choice l1;
+    MI_TRY(choose_level1(ctx, ops, sl, nkeys, p, l1));
+    MI_TRY(exclusive_scan(ctx, st, cur.items, nkeys, cur.item_start, sl.buf[B_SCAN], nullptr, nullptr, nullptr, p.first_sums_ready));
+    MsmLevelLaunch a{};   // (grid, lv, partial_out and -- above level 1 -- L, partial_in are set per level)
+    a.st = st; a.nkeys = nkeys; a.L = p.L_first; a.bucket = p.final_out; a.pts = p.pts; a.sorted = p.sorted; a.item_table = sl.buf[B_ITEMTAB].p; a.ev_before = p.time_first ? sl.ev[MSM_EV_L1_BEGIN] : nullptr;
     for (u32 level = 0;; level++) {
         DevBuf &pout_buf = sl.buf[(level & 1) ? B_PART1 : B_PART0];
         MI_TRY(mi_reserve(ctx, pout_buf, (items_bound + 1) * ops.xyzz_bytes));
-        void *pout = pout_buf.p;
+        a.lv = cur; a.partial_out = pout_buf.p;
         // bounded grid, grid-stride inside: at most 128 single-wave workgroups per CU, i.e. a wave of the level-1 kernel lives for a few
         // items (~0.5 ms), not for the whole launch.  A fully persistent grid (32 per CU = every wave slot) made the small kernels of the
         // other MSM streams wait for the end of the launch: 128..4096 per CU measured +1.5 % proofs/s and -1 ms latency over 32.
         // Levels that turn out to be (nearly) empty -- the bound is a worst case -- still cost microseconds, not a full dispatch.
-        u32 grid = (u32)((items_bound + 63) / 64);
-        u32 grid_cap = (u32)ctx->cu_count * 128;
-        {   // knobs g1_grid_per_cu / g2_grid_per_cu: resident-grid caps per CU for the level-1 kernels
-            const u32 capx = ops.xyzz_bytes == 256 ? knobs_of(ctx)->g2_grid_per_cu : knobs_of(ctx)->g1_grid_per_cu;
-            if (level == 0 && capx > 0) grid_cap = (u32)ctx->cu_count * capx;
-        }
-        if (grid > grid_cap) grid = grid_cap;
-        if (grid == 0) grid = 1;
+        const u64 waves = (items_bound + 63) / 64, grid_cap = level == 0 ? l1.grid_cap : (u32)ctx->cu_count * 128;
+        a.grid = (unsigned)(waves > grid_cap ? grid_cap : waves ? waves : 1);
         // the timed span (mi_stats.g1_accum_kernel_ms) brackets the accumulate kernel alone: on the 29-bit path the launcher records the
         // opening event AFTER its item-table kernel (0.1 ms alone, up to 0.5 ms waiting for CUs with three proofs in flight)
-        const bool rp_path = level == 0 && pts && rprime && ops.accum_affine_rp;
-        if (time_first && level == 0 && !rp_path) MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_L1_BEGIN], st));
-        const u32 ba_rounds = knobs_of(ctx)->ba_rounds;
-        // batch-affine rounds (msm_ba_g1.cuh) where the buckets hold a few items each (>= 32 entries on average) and the scratch fits
-        const u32 ba_waves = (u32)ctx->cu_count * 16;
-        const size_t ba_tot = msm_ba_scratch_bytes(items_bound + 1, ba_waves);
-        const bool use_ba = rp_path && ba_rounds && ops.accum_affine_ba && L == 16 && first_items_bound >= (u64)nkeys * 3 &&
-                            mi_try_reserve(sl.buf[B_BA_NODES], (items_bound + 1) * 512) && mi_try_reserve(sl.buf[B_BA_PREFIX], (items_bound + 1) * 256) &&
-                            mi_try_reserve(sl.buf[B_BA_TOT], 2 * ba_tot);
-        if (use_ba) {
-            MI_TRY(mi_reserve(ctx, sl.buf[B_ITEMTAB], (items_bound + 1) * 16));
-            ops.accum_affine_ba(st, (u32)ctx->cu_count * 64, pts, sorted, cur.start, cur.cnt, cur.items, cur.item_start, nkeys, final_out, pout, sl.buf[B_ITEMTAB].p,
-                                rp_partials ? 1u : 0u, ba_rounds, items_bound + 1, ba_waves, sl.buf[B_BA_NODES].p, sl.buf[B_BA_PREFIX].p, sl.buf[B_BA_TOT].p,
-                                (char *)sl.buf[B_BA_TOT].p + ba_tot, time_first ? sl.ev[MSM_EV_L1_BEGIN] : nullptr);
-        } else if (rp_path) {
-            MI_TRY(mi_reserve(ctx, sl.buf[B_ITEMTAB], (items_bound + 1) * 16));
-            // which build of the G1 level-1 kernel: three waves per SIMD (168 VGPRs: a SIMD's register file is full, and a freed wave slot
-            // is too small for any 256-VGPR G2 workgroup, which then waits for the END of this launch) or two (196: one freed slot admits one)
-            const MsmKnobs *kn = knobs_of(ctx);
-            const bool g2 = ops.xyzz_bytes == 256;
-            const bool two = !g2 && (kn->l1_waves == 2 || (kn->z_waves == 2 && &sl == &ctx->msm[MSM_SLOT_Z]));
-            const u32 wg = g2 ? kn->g2_wg : kn->l1_wg, wg_log = wg == 4 ? 2u : wg == 2 ? 1u : 0u;   // waves per workgroup
-            // (the level-1 launches on lowest-priority streams of their own -- "the accumulation is what fills the GPU, everything else is
-            //  dispatched ahead of it" -- measured -6 % proofs/s, profiles/r05_ab_evidence.txt: removed)
-            ops.accum_affine_rp(st, grid, pts, sorted, cur.start, cur.cnt, cur.items, cur.item_start, nkeys, L, final_out, pout, sl.buf[B_ITEMTAB].p,
-                                (rp_partials ? 1u : 0u) | (two ? 2u : 0u) | (wg_log << 2), time_first ? sl.ev[MSM_EV_L1_BEGIN] : nullptr);
-        } else if (level == 0 && pts) ops.accum_affine(st, grid, pts, sorted, cur.start, cur.cnt, cur.items, cur.item_start, nkeys, L, final_out, pout);
-        else if (rp_partials) ops.accum_xyzz_rp(st, grid, pin, cur.start, cur.cnt, cur.items, cur.item_start, nkeys, L, final_out, pout);
-        else ops.accum_xyzz(st, grid, pin, cur.start, cur.cnt, cur.items, cur.item_start, nkeys, L, final_out, pout);
+        if (level > 0) (l1.form.rp_partials ? ops.accum_xyzz_rp : ops.accum_xyzz)(a);
+        else if (!l1.rp_path) {
+            if (p.time_first) MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_L1_BEGIN], st));
+            ops.accum_affine(a);
+        } else if (!l1.use_ba) ops.accum_affine_rp(a, l1.form);
+        else {
+            a.grid = (u32)ctx->cu_count * 64;   // (here: the cap of each of its launches)
+            ops.accum_affine_ba(a, l1.form, knobs_of(ctx)->ba_rounds, items_bound + 1, l1.ba_waves, l1.ba);
+        }
         MI_CHECK_HIP(ctx, hipGetLastError());
-        if (time_first && level == 0) MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_L1_END], st));
-        u64 m_next = (m + L - 1) / L;  // entries of the largest key at the next level
+        if (p.time_first && level == 0) MI_CHECK_HIP(ctx, hipEventRecord(sl.ev[MSM_EV_L1_END], st));
+        const u64 m_next = (m + a.L - 1) / a.L;  // entries of the largest key at the next level
         if (m_next <= 1) break;
         // the finisher: no key holds more than finish_max partial sums -> one list launch + one launch end the machinery (the lists live in
         // the next level's start / cnt arrays, free from here on; the counters behind the bucket array, zeroed with it)
-        {
-            const MsmKnobs *kn = knobs_of(ctx);
-            const u64 fin_max = kn->finisher_max ? kn->finisher_max : ops.finish_max;
-            if (kn->finisher && ops.finish_keys && m_next <= fin_max && level >= kn->finisher_min_level) {
-                u32 *counters = (u32 *)((char *)final_out + (size_t)nkeys * ops.xyzz_bytes);
-                hipLaunchKernelGGL(k_msm_finish_list, dim3((nkeys + 63) / 64), dim3(64), 0, st, nkeys, cur.items, MSM_FIN_SMALL, nxt.start, nxt.cnt, counters);
-                const u32 T = ops.finish_T;
-                u32 nb_small = (nkeys + T - 1) / T, nb_big = nkeys;
-                const u32 cap_small = (u32)ctx->cu_count * 8, cap_big = (u32)ctx->cu_count * 4;
-                if (nb_small > cap_small) nb_small = cap_small;
-                if (nb_big > cap_big) nb_big = cap_big;
-                ops.finish_keys(st, nb_small, nb_big, pout, nxt.start, nxt.cnt, counters, cur.item_start, cur.items, final_out, rp_partials ? 1u : 0u);
-                MI_CHECK_HIP(ctx, hipGetLastError());
-                break;
-            }
+        const MsmKnobs *kn = knobs_of(ctx);
+        if (kn->finisher && ops.finish_keys && m_next <= (kn->finisher_max ? kn->finisher_max : ops.finish_max) && level >= kn->finisher_min_level) {
+            u32 *counters = (u32 *)((char *)p.final_out + (size_t)nkeys * ops.xyzz_bytes);
+            hipLaunchKernelGGL(k_msm_finish_list, dim3((nkeys + 63) / 64), dim3(64), 0, st, nkeys, cur.items, MSM_FIN_SMALL, nxt.start, nxt.cnt, counters);
+            const u32 nb_small = std::min((nkeys + ops.finish_T - 1) / ops.finish_T, (u32)ctx->cu_count * 8), nb_big = std::min(nkeys, (u32)ctx->cu_count * 4);
+            ops.finish_keys(st, nb_small, nb_big, a.partial_out, nxt.start, nxt.cnt, counters, cur.item_start, cur.items, p.final_out, l1.form.rp_partials ? 1u : 0u);
+            MI_CHECK_HIP(ctx, hipGetLastError());
+            break;
         }
         // next level: (start, cnt, items) of the keys that go on, and the exclusive scan of their items
-        if (scan_blocks <= SCAN_MAX_INLINE_BLOCKS) {   // prep fused with the block sums, the scan of the sums fused with the final pass: two launches
+        const bool fused = scan_blocks <= SCAN_MAX_INLINE_BLOCKS;   // prep fused with the block sums, the scan of the sums fused with the final pass: two launches
+        if (fused) {
             MI_TRY(mi_reserve(ctx, sl.buf[B_SCAN], (size_t)(scan_blocks + 1) * 4));
-            u32 *bs = (u32 *)sl.buf[B_SCAN].p;
-            hipLaunchKernelGGL(k_msm_prep_next_sums, dim3(scan_blocks), dim3(SCAN_THREADS), 0, st, nkeys, cur.items, cur.item_start, L_next, nxt.start, nxt.cnt,
-                               nxt.items, bs);
-            hipLaunchKernelGGL(k_scan_final, dim3(scan_blocks), dim3(SCAN_THREADS), 0, st, nxt.items, (size_t)nkeys, bs, nxt.item_start, 2, nullptr, nullptr, nullptr);
-            MI_CHECK_HIP(ctx, hipGetLastError());
+            hipLaunchKernelGGL(k_msm_prep_next_sums, dim3(scan_blocks), dim3(SCAN_THREADS), 0, st, nkeys, cur.items, cur.item_start, p.L_next, nxt.start, nxt.cnt, nxt.items, (u32 *)sl.buf[B_SCAN].p);
         } else {
-            hipLaunchKernelGGL(k_msm_prep_next, dim3((nkeys + 63) / 64), dim3(64), 0, st, nkeys, cur.items, cur.item_start, L_next, nxt.start, nxt.cnt, nxt.items);
+            hipLaunchKernelGGL(k_msm_prep_next, dim3((nkeys + 63) / 64), dim3(64), 0, st, nkeys, cur.items, cur.item_start, p.L_next, nxt.start, nxt.cnt, nxt.items);
             MI_CHECK_HIP(ctx, hipGetLastError());
-            MI_TRY(exclusive_scan(ctx, st, nxt.items, nkeys, nxt.item_start, sl.buf[B_SCAN]));
         }
+        MI_TRY(exclusive_scan(ctx, st, nxt.items, nkeys, nxt.item_start, sl.buf[B_SCAN], nullptr, nullptr, nullptr, fused));
         // items at the next level: every continuing key has >= 2 entries, so items <= entries/L + keys
-        u64 nb = items_bound / L_next + (items_bound < nkeys ? items_bound : nkeys) + 1;
+        u64 nb = items_bound / p.L_next + (items_bound < nkeys ? items_bound : nkeys) + 1;
         items_bound = nb < items_bound ? nb : items_bound;
-        m = m_next; L = L_next; pin = pout;
+        m = m_next; a.L = p.L_next; a.partial_in = a.partial_out;
         LevelArrays t = cur; cur = nxt; nxt = t;
     }
     return MI_OK;
@@ -674,7 +651,7 @@ static int32_t msm2_sort_enqueue(mi_ctx *ctx, MsmSlot &sl, const Fr *scalars, u3
 #undef MI_LAUNCH_COUNT
     }
     MI_CHECK_HIP(ctx, hipGetLastError());
-    u32 *host_total = (u32 *)((char *)sl.host_wsum + 128 * 256 + 16);
+    u32 *host_total = &sl.host_wsum->exact_total;
     MI_TRY(exclusive_scan(ctx, st, C1, (size_t)s.ngroups * G, S1, sl.buf[B_SCAN], exact ? host_total : nullptr));
     // Entry-indexed workspaces (two partition arrays, chunk histograms, sorted entries; later the per-item partial sums) take
     // ~19 B per entry.  The bound nwin * n is tight for uniform scalars (the h coefficients of the Z MSM) but 3x too large
@@ -755,7 +732,7 @@ static int32_t msm_accum_enqueue(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &s
     u64 max_count = (u64)(srt.nwin_digits / srt.nwin_keys) * n;
     if (srt.max_pending) {
         MI_CHECK_HIP(ctx, hipEventSynchronize(srt.ev[MSM_EV_MAX_LANDED]));
-        srt.max_key_count = *(const u32 *)((const char *)srt.host_wsum + 128 * 256 + 32);
+        srt.max_key_count = srt.host_wsum->max_bucket;
         srt.max_pending = false;
     }
     if (!kn->bound_levels && srt.max_key_count && srt.max_key_count < max_count) max_count = srt.max_key_count;
@@ -765,7 +742,7 @@ static int32_t msm_accum_enqueue(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &s
     // +0.7 %, 11 and 12 of 12 rounds).  The fullest bucket and the entry count are in host memory by now (the key scan stored them).
     bool flat = false;
     if (kn->flat_L1 != 1 && pts && srt.max_key_count) {   // (a flat sort's own size wins over the plan's L1)
-        const u64 entries = *(const u32 *)((const char *)srt.host_wsum + 128 * 256);
+        const u64 entries = srt.host_wsum->entries;
         const u64 avg = entries / (s.nkeys ? s.nkeys : 1);
         if (avg >= 64 && (u64)srt.max_key_count <= 2 * avg) {
             if (kn->flat_L1 >= 4) { L1 = kn->flat_L1; flat = true; }
@@ -781,7 +758,7 @@ static int32_t msm_accum_enqueue(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &s
     // entries.  Items of 32 halve the partial sums the dearer upper levels add up; it triggers only where it pays (same-process A/B of the rule: census mix +0.6 % / +1.5 %, uniform +0.2 % / +0.8 %,
     // 13 of 14 rounds; BASELINE mix, ~0.3 of the digits non-zero: items of 32 measured -0.5 % in r5, the rule leaves it at 16).  The count is the sort's own, per call.
     if (!flat && !kn->L1 && kn->dense_L1 != 1 && pts && srt.max_key_count && srt.nwin_keys == 1) {
-        const u64 entries = *(const u32 *)((const char *)srt.host_wsum + 128 * 256);
+        const u64 entries = srt.host_wsum->entries;
         if (entries >= ((u64)1 << 20) && 2 * entries >= (u64)n * srt.nwin_digits) { L1 = kn->dense_L1 >= 4 ? kn->dense_L1 : 32; ctx->dense_item_sorts++; }
     }
     // level-1 decomposition of every key (also: empty keys' buckets = infinity, finisher counters = 0) -- with the block sums of the item
@@ -802,11 +779,14 @@ static int32_t msm_accum_enqueue(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &s
         acc.accum_gate = nullptr;
         if (g) MI_CHECK_HIP(ctx, hipStreamWaitEvent(st, g, 0));
     }
-    MI_TRY(run_levels(ctx, ops, acc, s.nkeys, A, B, T_bound / L1 + s.nkeys + 1, max_count, L1, L2, pts, sorted, nullptr, bucket, timed, rprime, prep_sums));
+    LevelPlan plan{};
+    plan.L_first = L1; plan.L_next = L2; plan.first_items_bound = T_bound / L1 + s.nkeys + 1; plan.max_count = max_count;
+    plan.pts = pts; plan.sorted = sorted; plan.final_out = bucket; plan.time_first = timed; plan.rprime = rprime; plan.first_sums_ready = prep_sums;
+    MI_TRY(run_levels(ctx, ops, acc, s.nkeys, A, B, plan));
     // everything below reads the bucket sums only: a point-sharded MSM (group.hip, SURVEY 8e option ii) stops here, exchanges
     // bucket slices between the devices and calls mi_msm_reduce_enqueue afterwards
     acc.tail_seg = seg;
-    acc.entries_src = (const u32 *)((const char *)srt.host_wsum + 128 * 256);   // HOST word: the sort's key scan left the number of sorted entries there (fetch_max_and_scan_keys)
+    acc.entries_src = &srt.host_wsum->entries;   // HOST word: the sort's key scan left the number of sorted entries there (fetch_max_and_scan_keys)
     acc.timed = timed;
     acc.deferred = defer_reduce;
     if (defer_reduce) {
@@ -834,12 +814,12 @@ static int32_t msm_tail_enqueue(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &ac
     bool on_host = false;
     for (u32 k = tb; k > 1;) {
         const u32 nout = (k + ops.sum_T - 1) / ops.sum_T;
-        ops.sum_tree(st, nout, s.nwin, cur, k, nout == 1 ? (char *)acc.host_wsum : next);
+        ops.sum_tree(st, nout, s.nwin, cur, k, nout == 1 ? (char *)acc.host_wsum->wsum : next);
         on_host = nout == 1;
         cur = next; next += (size_t)s.nwin * nout * ops.xyzz_bytes; k = nout;
     }
     MI_CHECK_HIP(ctx, hipGetLastError());
-    if (!on_host) MI_CHECK_HIP(ctx, hipMemcpyAsync(acc.host_wsum, P, ops.xyzz_bytes * s.nwin, hipMemcpyDeviceToHost, st));   // tb == 1: no tree ran
+    if (!on_host) MI_CHECK_HIP(ctx, hipMemcpyAsync(acc.host_wsum->wsum, P, ops.xyzz_bytes * s.nwin, hipMemcpyDeviceToHost, st));   // tb == 1: no tree ran
     MI_CHECK_HIP(ctx, hipEventRecord(acc.ev[MSM_EV_JOB_END], st));
     acc.deferred = false;
     acc.active = true;
@@ -851,7 +831,7 @@ static int32_t msm_finish(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &sl, void
     if (!sl.active) { ops.combine_windows(nullptr, 0, 0, out); return MI_OK; }   // zero windows -> infinity
     MI_CHECK_HIP(ctx, hipStreamSynchronize(sl.stream));
     const MsmShape s = key_shape(sl);
-    ops.combine_windows(sl.host_wsum, s.nwin, s.c, out);   // Horner on the host, <= 128 points
+    ops.combine_windows(sl.host_wsum->wsum, s.nwin, s.c, out);   // Horner on the host, <= 128 points
     if (sl.timed) {
         float ms = 0;
         MI_CHECK_HIP(ctx, hipEventElapsedTime(&ms, sl.ev[MSM_EV_L1_BEGIN], sl.ev[MSM_EV_L1_END]));
@@ -860,7 +840,7 @@ static int32_t msm_finish(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &sl, void
         ctx->stats.g1_accum_launches += 1;
         ctx->stats.g1_accum_entries += *sl.entries_src;
     }
-    if (ops.xyzz_bytes == 128) ctx->stats.g1_level1_additions += *sl.entries_src;   // every G1 MSM, timed or not (a host word: the owning sort's key scan stored it)
+    if (ops.curve == 1) ctx->stats.g1_level1_additions += *sl.entries_src;   // every G1 MSM, timed or not (a host word: the owning sort's key scan stored it)
     sl.active = false;
     return MI_OK;
 }
@@ -868,7 +848,7 @@ static int32_t msm_finish(mi_ctx *ctx, const MsmCurveOps &ops, MsmSlot &sl, void
 // internal entry points used by prove.hip (curve: 1 = G1, 2 = G2)
 int32_t mi_msm_precompute(mi_ctx *ctx, int curve, const void *base_dev, void *pre_dev, size_t n, uint32_t c) {
     if (!ctx || !base_dev || !pre_dev || c < 17 || c > 22 || n >= ((size_t)1 << 31)) return MI_EINVAL;
-    const MsmCurveOps &ops = curve == 1 ? msm_g1_ops() : msm_g2_ops();
+    const MsmCurveOps &ops = mi_msm_ops(curve);
     if (!n) return MI_OK;
     // batched conversions (one inversion per 16 points per window instead of one per point: ~2.7x less work) need n XYZZ + n coordinates
     // of scratch for the duration of the build; without room for them the one-kernel form runs
@@ -906,7 +886,7 @@ int32_t mi_msm_enqueue(mi_ctx *ctx, int slot, int sort_slot, int curve, const vo
         if (!defer) return MI_OK;
         // An EMPTY deferred MSM (a rank of a point-sharded MSM without pairs: group.hip) still leaves a bucket array of the plan's shape
         // -- all infinity -- so that the bucket exchange and the reduce treat this rank like every other.
-        const MsmCurveOps &ops = curve == 1 ? msm_g1_ops() : msm_g2_ops();
+        const MsmCurveOps &ops = mi_msm_ops(curve);
         sl.n = 0; sl.G = 1;
         if (sort_slot >= 0) {   // the shape of the (equally empty) sort it would have shared
             const MsmSlot &srt = ctx->msm[sort_slot];
@@ -938,21 +918,21 @@ int32_t mi_msm_enqueue(mi_ctx *ctx, int slot, int sort_slot, int curve, const vo
     else if (sort_slot < 0) MI_TRY(msm_sort_enqueue(ctx, sl, (const Fr *)scalars_dev, (u32)n, flags, generic_c, exact));
     else if (srt.n != n) MI_FAIL(ctx, MI_EINVAL, "msm: shared sort has a different length");
     sl.accum_gate = gate_once;
-    return msm_accum_enqueue(ctx, curve == 1 ? msm_g1_ops() : msm_g2_ops(), srt, sl, pts_dev, timed, defer, rprime);
+    return msm_accum_enqueue(ctx, mi_msm_ops(curve), srt, sl, pts_dev, timed, defer, rprime);
 }
 bool mi_msm_limb29_enabled(mi_ctx *ctx) { return !knobs_of(ctx)->no_rprime; }
 uint32_t mi_msm_auto_c(size_t n) { return auto_c(n ? (u32)n : 1u); }
-const MsmCurveOps &mi_msm_ops(int curve) { return curve == 1 ? msm_g1_ops() : msm_g2_ops(); }
+const MsmCurveOps &mi_msm_ops(int curve) { return curve != 1 ? msm_g2_ops() : msm_g1_ops(); }
 int32_t mi_msm_reduce_enqueue(mi_ctx *ctx, int slot, int curve) {
     if (slot < 0 || slot >= MI_MSM_SLOTS) return MI_EINVAL;
     MsmSlot &sl = ctx->msm[slot];
     if (!sl.deferred) return MI_OK;   // an empty MSM (n == 0) never got as far as its buckets
-    return msm_tail_enqueue(ctx, curve == 1 ? msm_g1_ops() : msm_g2_ops(), sl);
+    return msm_tail_enqueue(ctx, mi_msm_ops(curve), sl);
 }
 int32_t mi_msm_bucket_view(mi_ctx *ctx, int slot, int curve, MsmBucketView *v) {
     if (slot < 0 || slot >= MI_MSM_SLOTS || !v) return MI_EINVAL;
     MsmSlot &sl = ctx->msm[slot];
-    const MsmCurveOps &ops = curve == 1 ? msm_g1_ops() : msm_g2_ops();
+    const MsmCurveOps &ops = mi_msm_ops(curve);
     *v = MsmBucketView{};
     if (!sl.deferred) return MI_OK;
     const MsmShape s = key_shape(sl);
@@ -963,7 +943,7 @@ int32_t mi_msm_bucket_view(mi_ctx *ctx, int slot, int curve, MsmBucketView *v) {
 int32_t mi_msm_finish(mi_ctx *ctx, int slot, int curve, void *out_xyzz_host) {
     if (slot < 0 || slot >= MI_MSM_SLOTS) return MI_EINVAL;
     const MiRange range(msm_range_names[slot][1]);
-    return msm_finish(ctx, curve == 1 ? msm_g1_ops() : msm_g2_ops(), ctx->msm[slot], out_xyzz_host);
+    return msm_finish(ctx, mi_msm_ops(curve), ctx->msm[slot], out_xyzz_host);
 }
 
 template <class F, class JacT>
@@ -973,7 +953,18 @@ static void xyzz_to_jac_out(const XYZZ<F> &r, JacT *out) {
     else { Affine<F> a = xyzz_to_affine(r); j = Jac<F>{a.x, a.y, F::one()}; }
     std::memcpy(out, &j, sizeof(j));
 }
-// one MSM through MSM_SLOT_A, ordered after everything already queued on ctx->stream
+// one MSM through MSM_SLOT_A, ordered after everything already queued on ctx->stream (precomp_c != 0: over fixed-base window tables); total_ms
+template <class F, class JacT>
+static int32_t msm_timed_on_slot_a(mi_ctx *ctx, int curve, const void *pts_dev, const void *scalars_dev, size_t n, uint32_t flags, uint32_t precomp_c, JacT *out) {
+    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T0], ctx->stream));
+    MI_TRY(mi_msm_enqueue(ctx, MSM_SLOT_A, -1, curve, pts_dev, scalars_dev, n, flags | MI_MSM_EXACT_SIZE, ctx->ev[EV_T0], curve == 1, precomp_c));
+    if (n) MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T1], ctx->msm[MSM_SLOT_A].stream));
+    XYZZ<F> r;
+    MI_TRY(mi_msm_finish(ctx, MSM_SLOT_A, curve, &r));
+    if (n) MI_CHECK_HIP(ctx, hipEventElapsedTime(&ctx->stats.total_ms, ctx->ev[EV_T0], ctx->ev[EV_T1]));
+    xyzz_to_jac_out<F>(r, out);
+    return MI_OK;
+}
 template <class F, class JacT>
 static int32_t msm_dev_entry(mi_ctx *ctx, int curve, const void *pts_dev, const void *scalars_dev, size_t n, uint32_t flags, JacT *out) {
     std::memset(&ctx->stats, 0, sizeof(ctx->stats));
@@ -981,21 +972,14 @@ static int32_t msm_dev_entry(mi_ctx *ctx, int curve, const void *pts_dev, const 
     // reads (64 B in, 64 B out per point: 0.2 ms per 2^23 points against ~15 ms of MSM)
     uint32_t rp = 0;
     if (n >= ((size_t)1 << (curve == 1 ? 16 : 14)) && !knobs_of(ctx)->no_rprime) {
-        const MsmCurveOps &o = curve == 1 ? msm_g1_ops() : msm_g2_ops();
+        const MsmCurveOps &o = mi_msm_ops(curve);
         MI_TRY(mi_reserve(ctx, ctx->ws[WS_RPRIME], n * (curve == 1 ? 64 : 128) + 64));
         o.to_rprime(ctx->stream, ctx->ws[WS_RPRIME].p, pts_dev, n);
         MI_CHECK_HIP(ctx, hipGetLastError());
         pts_dev = ctx->ws[WS_RPRIME].p;
         rp = MI_MSM_PTS_RPRIME;
     }
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T0], ctx->stream));
-    MI_TRY(mi_msm_enqueue(ctx, MSM_SLOT_A, -1, curve, pts_dev, scalars_dev, n, flags | MI_MSM_EXACT_SIZE | rp, ctx->ev[EV_T0], curve == 1));
-    if (n) MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T1], ctx->msm[MSM_SLOT_A].stream));
-    XYZZ<F> r;
-    MI_TRY(mi_msm_finish(ctx, MSM_SLOT_A, curve, &r));
-    if (n) MI_CHECK_HIP(ctx, hipEventElapsedTime(&ctx->stats.total_ms, ctx->ev[EV_T0], ctx->ev[EV_T1]));
-    xyzz_to_jac_out<F>(r, out);
-    return MI_OK;
+    return msm_timed_on_slot_a<F>(ctx, curve, pts_dev, scalars_dev, n, flags | rp, 0, out);
 }
 template <class F, class AffT, class JacT>
 static int32_t msm_host_entry(mi_ctx *ctx, int curve, const AffT *pts, const mi_fr *scalars, size_t n, uint32_t flags, JacT *out) {
@@ -1014,14 +998,7 @@ static int32_t msm_fixed_dev_entry(mi_ctx *ctx, int curve, const void *pre_dev, 
     std::memset(&ctx->stats, 0, sizeof(ctx->stats));
     const uint32_t rp = (flags & MI_MSM_TABLE_RPRIME) ? MI_MSM_PTS_RPRIME : 0;   // the table was converted by mi_msm_table_to_rprime_*: level 1 in 29-bit limbs
     flags &= ~MI_MSM_TABLE_RPRIME;
-    MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T0], ctx->stream));
-    MI_TRY(mi_msm_enqueue(ctx, MSM_SLOT_A, -1, curve, pre_dev, scalars_dev, n, flags | MI_MSM_EXACT_SIZE | rp, ctx->ev[EV_T0], curve == 1, c));
-    if (n) MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T1], ctx->msm[MSM_SLOT_A].stream));
-    XYZZ<F> r;
-    MI_TRY(mi_msm_finish(ctx, MSM_SLOT_A, curve, &r));
-    if (n) MI_CHECK_HIP(ctx, hipEventElapsedTime(&ctx->stats.total_ms, ctx->ev[EV_T0], ctx->ev[EV_T1]));
-    xyzz_to_jac_out<F>(r, out);
-    return MI_OK;
+    return msm_timed_on_slot_a<F>(ctx, curve, pre_dev, scalars_dev, n, flags | rp, c, out);
 }
 static int32_t table_to_rprime(mi_ctx *ctx, int curve, void *pre_dev, size_t n_points) {
     if (!ctx || (!pre_dev && n_points)) return MI_EINVAL;

@@ -37,16 +37,12 @@ __global__ void __launch_bounds__(64, ReduceWaves<F>::value) k_msm_bucket_reduce
 
 
 template <class F>
-static void launch_accum_affine(hipStream_t st, unsigned grid, const void *pts, const u32 *sorted, const u32 *start, const u32 *cnt, const u32 *items,
-                                const u32 *item_start, u32 nkeys, u32 L, void *bucket, void *pout) {
-    hipLaunchKernelGGL(k_msm_accum_affine<F>, dim3(grid), dim3(64), 0, st, (const Affine<F> *)pts, sorted, start, cnt, items, item_start, nkeys, L,
-                       (XYZZ<F> *)bucket, (XYZZ<F> *)pout);
+static void launch_accum_affine(const MsmLevelLaunch &a) {
+    hipLaunchKernelGGL(k_msm_accum_affine<F>, dim3(a.grid), dim3(64), 0, a.st, (const Affine<F> *)a.pts, a.sorted, a.lv.start, a.lv.cnt, a.lv.items, a.lv.item_start, a.nkeys, a.L, (XYZZ<F> *)a.bucket, (XYZZ<F> *)a.partial_out);
 }
 template <class F>
-static void launch_accum_xyzz(hipStream_t st, unsigned grid, const void *pin, const u32 *start, const u32 *cnt, const u32 *items, const u32 *item_start,
-                              u32 nkeys, u32 L, void *bucket, void *pout) {
-    hipLaunchKernelGGL(k_msm_accum_xyzz<F>, dim3(grid), dim3(64), 0, st, (const XYZZ<F> *)pin, start, cnt, items, item_start, nkeys, L,
-                       (XYZZ<F> *)bucket, (XYZZ<F> *)pout);
+static void launch_accum_xyzz(const MsmLevelLaunch &a) {
+    hipLaunchKernelGGL(k_msm_accum_xyzz<F>, dim3(a.grid), dim3(64), 0, a.st, (const XYZZ<F> *)a.partial_in, a.lv.start, a.lv.cnt, a.lv.items, a.lv.item_start, a.nkeys, a.L, (XYZZ<F> *)a.bucket, (XYZZ<F> *)a.partial_out);
 }
 template <class F>
 static void launch_bucket_reduce(hipStream_t st, unsigned grid_x, unsigned nwin, const void *bucket, u32 nbuckets, u32 seg, u32 tb, void *out) {
@@ -175,4 +171,21 @@ static void launch_precompute(hipStream_t st, const void *base, void *pre, u32 n
 template <class F>
 static void host_combine_windows(const void *wsum, u32 nwin, u32 c, void *out) {
     *(XYZZ<F> *)out = nwin ? msm_combine_windows<F>((const XYZZ<F> *)wsum, nwin, c) : XYZZ<F>::inf();
+}
+// the MsmCurveOps entries that are the same templates for both curves; msm_g1.hip / msm_g2.hip add their level-1, R' and finisher kernels
+template <class F>
+static MsmCurveOps msm_generic_ops(int curve) {
+    MsmCurveOps o{};
+    o.curve = curve;
+    o.xyzz_bytes = sizeof(XYZZ<F>);
+    o.coord_bytes = sizeof(F);
+    o.accum_xyzz = launch_accum_xyzz<F>;
+    o.bucket_reduce = launch_bucket_reduce<F>;
+    o.sum_T = SumT<F>::value;
+    o.sum_tree = launch_sum_tree<F>;
+    o.combine_windows = host_combine_windows<F>;
+    o.sum_slices = launch_sum_slices<F>;
+    o.precompute = launch_precompute<F>;
+    o.precompute_batched = launch_precompute_batched<F>;
+    return o;
 }

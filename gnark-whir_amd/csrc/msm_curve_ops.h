@@ -7,12 +7,31 @@
 #include <stdint.h>
 
 static constexpr uint32_t MSM_FIN_SMALL = 16;   // the finisher: keys with <= this many partial sums are summed by one thread each
+// the per-key arrays of one item level: first input, number of inputs, items, exclusive scan of the items (the total at [nkeys])
+struct LevelArrays { uint32_t *start, *cnt, *items, *item_start; };
+// What the launcher of one item level needs; run_levels (msm.hip) fills one per level.  An item sums up to L consecutive inputs of its key.
+struct MsmLevelLaunch {
+    hipStream_t st;
+    unsigned grid;                 // in waves of 64 items, grid-stride inside (a launcher of multi-wave workgroups divides by their size)
+    uint32_t nkeys, L;
+    LevelArrays lv;
+    void *bucket, *partial_out;    // a key's only item stores bucket[key] (standard XYZZ), every other item partial_out[item]
+    const void *pts; const uint32_t *sorted;   // level 1: the points and the sorted entries (point index | sign << 31)
+    const void *partial_in;        // the levels above: the partial sums the level before left
+    void *item_table;              // 29-bit level 1: 16 B per item of scratch
+    hipEvent_t ev_before;          // 29-bit level 1: recorded on st between the item-table kernel and the accumulate kernel when non-null (stats)
+};
+struct MsmLevel1Form {         // the form of a 29-bit level 1: a wrong choice still gives right sums, from another kernel build -- so each has a name
+    bool rp_partials;          // partial sums leave in the packed R' form (the levels above are then accum_xyzz_rp and the finisher's rp form)
+    uint32_t waves_per_simd;   // G1 only: the build for 3 or 2 waves per SIMD (msm_g1.hip)
+    uint32_t wg_waves;         // waves per workgroup: 1, 2 or 4
+};
+struct MsmBaScratch { void *nodes, *prefix, *totals, *invs; };   // 512 B per item, 256 B per item, msm_ba_scratch_bytes each
 struct MsmCurveOps {
+    int curve;           // 1 = G1, 2 = G2
     size_t xyzz_bytes;   // sizeof(XYZZ<F>): 128 (G1) / 256 (G2)
-    void (*accum_affine)(hipStream_t st, unsigned grid, const void *pts, const uint32_t *sorted, const uint32_t *start, const uint32_t *cnt,
-                         const uint32_t *items, const uint32_t *item_start, uint32_t nkeys, uint32_t L, void *bucket, void *partial_out);
-    void (*accum_xyzz)(hipStream_t st, unsigned grid, const void *partial_in, const uint32_t *start, const uint32_t *cnt, const uint32_t *items,
-                       const uint32_t *item_start, uint32_t nkeys, uint32_t L, void *bucket, void *partial_out);
+    void (*accum_affine)(const MsmLevelLaunch &);   // level 1 over points in the standard Montgomery form
+    void (*accum_xyzz)(const MsmLevelLaunch &);     // the levels above over standard XYZZ partial sums
     void (*bucket_reduce)(hipStream_t st, unsigned grid_x, unsigned nwin, const void *bucket, uint32_t nbuckets, uint32_t seg, uint32_t tb, void *out);
     // tree sum: block (bx, w) adds in[w*n + bx*sum_T .. + sum_T) in LDS and writes out[w*nout + bx]
     uint32_t sum_T;
@@ -25,24 +44,14 @@ struct MsmCurveOps {
     void (*combine_windows)(const void *host_wsum, uint32_t nwin, uint32_t c, void *out_xyzz);
     // own[i] += sum_p recv[p * own_len + i]  (XYZZ; bucket slices received from the other devices of a sharded MSM)
     void (*sum_slices)(hipStream_t st, void *own, const void *recv, uint32_t n_peers, uint32_t own_len);
-    // Level-1 accumulation over points kept in the R' = 2^261 packed form (curve29.cuh: nine 29-bit limbs, lazy arithmetic);
-    // same arguments and results as accum_affine.
-    void (*accum_affine_rp)(hipStream_t st, unsigned grid, const void *pts_rp, const uint32_t *sorted, const uint32_t *start, const uint32_t *cnt,
-                            const uint32_t *items, const uint32_t *item_start, uint32_t nkeys, uint32_t L, void *bucket, void *partial_out,
-                            void *item_table /* 16 B per item of scratch */, uint32_t rp_partials /* bit 0; bit 1: the G1 kernel's two-wave build */,
-                            hipEvent_t ev_before /* recorded on st between the item-table kernel and the accumulate kernel when non-null (stats) */);
-    // Levels >= 2 over partial sums the level before left in the packed R' form (accum_affine_rp with rp_partials = 1, or this
-    // kernel): same arguments as accum_xyzz; bucket sums leave in the standard form, partial sums in the R' form.  Null = the
-    // curve keeps its partial sums in the standard form, and rp_partials must be 0.  (G1: k_msm_accum_xyzz29, G2: k_msm_accum_xyzz_g2_29.)
-    void (*accum_xyzz_rp)(hipStream_t st, unsigned grid, const void *partial_in, const uint32_t *start, const uint32_t *cnt, const uint32_t *items,
-                          const uint32_t *item_start, uint32_t nkeys, uint32_t L, void *bucket, void *partial_out);
-    // Level-1 accumulation by batch-affine rounds (msm_ba_g1.cuh): same inputs and outputs as accum_affine_rp for items of <= 16
-    // entries.  rounds = 1..4; scratch: nodes (512 B per item), prefix (256 B per item), totals / invs (msm_ba_scratch_bytes each).
-    // Null where no such kernels exist (G2).
-    void (*accum_affine_ba)(hipStream_t st, unsigned grid_cap, const void *pts_rp, const uint32_t *sorted, const uint32_t *start, const uint32_t *cnt,
-                            const uint32_t *items, const uint32_t *item_start, uint32_t nkeys, void *bucket, void *partial_out, void *item_table,
-                            uint32_t rp_partials, uint32_t rounds, uint64_t items_bound, uint32_t target_waves, void *nodes, void *prefix, void *totals,
-                            void *invs, hipEvent_t ev_before);
+    // Level-1 accumulation over points kept in the R' = 2^261 packed form (curve29.cuh: nine 29-bit limbs, lazy arithmetic); results as accum_affine.
+    void (*accum_affine_rp)(const MsmLevelLaunch &, const MsmLevel1Form &);
+    // Levels >= 2 over partial sums the level before left in the packed R' form (form.rp_partials): bucket sums leave in the standard form, partial
+    // sums in the R' form.  Null = the curve keeps its partial sums in the standard form, and rp_partials must be false.
+    void (*accum_xyzz_rp)(const MsmLevelLaunch &);
+    // Level-1 accumulation by batch-affine rounds (msm_ba_g1.cuh): same inputs and outputs as accum_affine_rp for items of <= 16 entries; a.grid caps
+    // every launch.  rounds = 1..4 over at most items_bound items, chunks sized for target_waves waves.  Null where no such kernels exist (G2).
+    void (*accum_affine_ba)(const MsmLevelLaunch &a, const MsmLevel1Form &, uint32_t rounds, uint64_t items_bound, uint32_t target_waves, const MsmBaScratch &);
     // The finisher (msm_curve_kernels.cuh k_msm_finish_keys): every key on the two lists (k_msm_finish_list) has its partial sums
     // partials[item_start[key] .. + items[key]) -- standard XYZZ, or the packed R' form when rp -- summed into bucket[key] (standard).
     // Workgroups of finish_T threads; a key on the big list may hold at most finish_max partial sums (the chain of its one workgroup).

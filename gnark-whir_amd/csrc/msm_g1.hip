@@ -10,7 +10,7 @@
 // (tools/bench_limb29/madd29.hip: 13.1 against 11.3 G/s on L2-resident points, conversions included).
 // Built twice.  Three waves per SIMD (168 VGPRs: 504 of a SIMD's 512 registers) is the default: alone on the GPU it is the faster
 // build (14.0 against 13.5 G additions/s; N = 2^26, one proof filling the GPU: 3.86 against 3.76 proofs/s) and its launches are the
-// short ones the roofline line is quoted on.  Two waves (196 VGPRs, no scratch; flag bit 1, mi_debug_set_msm_l1_waves) leaves room for
+// short ones the roofline line is quoted on.  Two waves (196 VGPRs, no scratch; MsmLevel1Form::waves_per_simd, mi_debug_set_msm_l1_waves) leaves room for
 // a wave of the NTT passes (86 VGPRs) on the same SIMD, which fills the gaps the gathers leave: with three proofs in flight at
 // N = 2^23 the JOB is 1.7 % faster and the single-proof latency 1 ms shorter (same-box A/B 32.9-33.0 against 32.0-32.6 proofs/s) while
 // every launch of this kernel takes 8.8 instead of 5.5 ms.  Four waves would spill (332 B of scratch: 28.5 proofs/s).
@@ -66,59 +66,40 @@ __global__ void __launch_bounds__(64, 3) k_msm_accum_xyzz29(const G1X *partial_i
         else g1x29_store_rp(acc, reinterpret_cast<u32 *>(partial_out + item));
     }
 }
-static void launch_accum_xyzz29(hipStream_t st, unsigned grid, const void *pin, const u32 *start, const u32 *cnt, const u32 *items, const u32 *item_start,
-                                u32 nkeys, u32 L, void *bucket, void *pout) {
-    hipLaunchKernelGGL(k_msm_accum_xyzz29, dim3(grid), dim3(64), 0, st, (const G1X *)pin, start, cnt, items, item_start, nkeys, (G1X *)bucket, (G1X *)pout);
+static void launch_accum_xyzz29(const MsmLevelLaunch &a) {
+    hipLaunchKernelGGL(k_msm_accum_xyzz29, dim3(a.grid), dim3(64), 0, a.st, (const G1X *)a.partial_in, a.lv.start, a.lv.cnt, a.lv.items, a.lv.item_start, a.nkeys, (G1X *)a.bucket, (G1X *)a.partial_out);
 }
-static void launch_accum_affine29(hipStream_t st, unsigned grid, const void *pts, const u32 *sorted, const u32 *start, const u32 *cnt, const u32 *items,
-                                  const u32 *item_start, u32 nkeys, u32 L, void *bucket, void *pout, void *item_tab, u32 rp_partials, hipEvent_t ev_before) {
-    hipLaunchKernelGGL(k_msm_item_table<Fp>, dim3(grid < 32768 ? grid : 32768), dim3(64), 0, st, start, cnt, items, item_start, nkeys, (uint4 *)item_tab);
-    if (ev_before) (void)hipEventRecord(ev_before, st);
-    // rp_partials: bit 0 = partial sums stay in the R' form, bit 1 = the two-waves-per-SIMD build, bits 2..3 = log2 of the waves per workgroup
-    const u32 wg_log = (rp_partials >> 2) & 3u, wg = 1u << wg_log;
-    const unsigned g = (grid + wg - 1) / wg;   // `grid` counts waves
-#define MI_L1(WG, WPS) hipLaunchKernelGGL((k_msm_accum_affine29<WG, WPS>), dim3(g), dim3(64 * WG), 0, st, (const G1Aff *)pts, sorted, (const uint4 *)item_tab, \
-                                          item_start, nkeys, (G1X *)bucket, (G1X *)pout, rp_partials & 1u)
-    if (rp_partials & 2) { if (wg == 4) MI_L1(4, 2); else if (wg == 2) MI_L1(2, 2); else MI_L1(1, 2); }
+static void launch_accum_affine29(const MsmLevelLaunch &a, const MsmLevel1Form &f) {
+    hipLaunchKernelGGL(k_msm_item_table<Fp>, dim3(a.grid < 32768 ? a.grid : 32768), dim3(64), 0, a.st, a.lv.start, a.lv.cnt, a.lv.items, a.lv.item_start, a.nkeys, (uint4 *)a.item_table);
+    if (a.ev_before) (void)hipEventRecord(a.ev_before, a.st);
+    const u32 wg = f.wg_waves, g = (a.grid + wg - 1) / wg;   // a.grid counts waves
+#define MI_L1(WG, WPS) hipLaunchKernelGGL((k_msm_accum_affine29<WG, WPS>), dim3(g), dim3(64 * WG), 0, a.st, (const G1Aff *)a.pts, a.sorted, (const uint4 *)a.item_table, \
+                                          a.lv.item_start, a.nkeys, (G1X *)a.bucket, (G1X *)a.partial_out, f.rp_partials ? 1u : 0u)
+    if (f.waves_per_simd == 2) { if (wg == 4) MI_L1(4, 2); else if (wg == 2) MI_L1(2, 2); else MI_L1(1, 2); }
     else { if (wg == 4) MI_L1(4, 3); else if (wg == 2) MI_L1(2, 3); else MI_L1(1, 3); }
 #undef MI_L1
 }
-// one batch-affine round (msm_ba_g1.cuh)
+// one batch-affine round (msm_ba_g1.cuh); behind the last one, the kernel that writes every item's sum.  a.grid caps every launch.
 template <int R>
-static void ba_round(hipStream_t st, unsigned grid_cap, const G1Aff *pts, const u32 *sorted, const uint4 *tab, const u32 *item_start, u32 nkeys, uint64_t items_bound,
-                     u32 target_waves, uint4 *nodes, uint4 *prefix, uint4 *totals, uint4 *invs) {
-    const uint64_t slots = items_bound << (BA_LOG_L - R);
+static void ba_round(const MsmLevelLaunch &a, const MsmLevel1Form &f, uint64_t items_bound, u32 target_waves, const MsmBaScratch &sc, bool last) {
+    const G1Aff *pts = (const G1Aff *)a.pts;
+    const uint4 *tab = (const uint4 *)a.item_table, *nodes = (const uint4 *)sc.nodes;
+    const uint64_t slots = items_bound << (BA_LOG_L - R), chunks = msm_ba_chunks(slots, target_waves), waves = (items_bound + 63) / 64;
     const u32 K = msm_ba_K(slots, target_waves);
-    const uint64_t chunks = msm_ba_chunks(slots, target_waves);
-    const unsigned grid = (unsigned)(chunks < grid_cap ? (chunks ? chunks : 1) : grid_cap);
-    hipLaunchKernelGGL(k_ba_fwd<R>, dim3(grid), dim3(64), 0, st, pts, sorted, tab, item_start, nkeys, (const uint4 *)nodes, prefix, totals, K);
-    hipLaunchKernelGGL(k_ba_inv, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, st, item_start, nkeys, BA_LOG_L - R, K, (const u32 *)totals, (u32 *)invs);
-    hipLaunchKernelGGL(k_ba_bwd<R>, dim3(grid), dim3(64), 0, st, pts, sorted, tab, item_start, nkeys, nodes, (const uint4 *)prefix, (const uint4 *)invs, K);
+    const unsigned grid = (unsigned)(chunks < a.grid ? (chunks ? chunks : 1) : a.grid), fgrid = (unsigned)(waves < a.grid ? (waves ? waves : 1) : a.grid);
+    hipLaunchKernelGGL(k_ba_fwd<R>, dim3(grid), dim3(64), 0, a.st, pts, a.sorted, tab, a.lv.item_start, a.nkeys, nodes, (uint4 *)sc.prefix, (uint4 *)sc.totals, K);
+    hipLaunchKernelGGL(k_ba_inv, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, a.st, a.lv.item_start, a.nkeys, BA_LOG_L - R, K, (const u32 *)sc.totals, (u32 *)sc.invs);
+    hipLaunchKernelGGL(k_ba_bwd<R>, dim3(grid), dim3(64), 0, a.st, pts, a.sorted, tab, a.lv.item_start, a.nkeys, (uint4 *)sc.nodes, (const uint4 *)sc.prefix, (const uint4 *)sc.invs, K);
+    if (last) hipLaunchKernelGGL(k_ba_finish<R>, dim3(fgrid), dim3(64), 0, a.st, pts, a.sorted, tab, a.lv.item_start, a.nkeys, nodes, (G1X *)a.bucket, (G1X *)a.partial_out, f.rp_partials ? 1u : 0u);
 }
-static void launch_accum_affine_ba(hipStream_t st, unsigned grid_cap, const void *pts_, const u32 *sorted, const u32 *start, const u32 *cnt, const u32 *items,
-                                   const u32 *item_start, u32 nkeys, void *bucket, void *pout, void *item_tab, u32 rp_partials, u32 rounds, uint64_t items_bound,
-                                   u32 target_waves, void *nodes_, void *prefix_, void *totals_, void *invs_, hipEvent_t ev_before) {
-    const G1Aff *pts = (const G1Aff *)pts_;
-    const uint4 *tab = (const uint4 *)item_tab;
-    uint4 *nodes = (uint4 *)nodes_, *prefix = (uint4 *)prefix_, *totals = (uint4 *)totals_, *invs = (uint4 *)invs_;
-    unsigned tgrid = (unsigned)((items_bound + 255) / 256);
-    hipLaunchKernelGGL(k_msm_item_table<Fp>, dim3(tgrid < 8192 ? (tgrid ? tgrid : 1) : 8192), dim3(256), 0, st, start, cnt, items, item_start, nkeys, (uint4 *)item_tab);
-    if (ev_before) (void)hipEventRecord(ev_before, st);
-    if (rounds >= 1) ba_round<1>(st, grid_cap, pts, sorted, tab, item_start, nkeys, items_bound, target_waves, nodes, prefix, totals, invs);
-    if (rounds >= 2) ba_round<2>(st, grid_cap, pts, sorted, tab, item_start, nkeys, items_bound, target_waves, nodes, prefix, totals, invs);
-    if (rounds >= 3) ba_round<3>(st, grid_cap, pts, sorted, tab, item_start, nkeys, items_bound, target_waves, nodes, prefix, totals, invs);
-    if (rounds >= 4) ba_round<4>(st, grid_cap, pts, sorted, tab, item_start, nkeys, items_bound, target_waves, nodes, prefix, totals, invs);
-    unsigned fgrid = (unsigned)((items_bound + 63) / 64);
-    if (fgrid > grid_cap) fgrid = grid_cap;
-    if (!fgrid) fgrid = 1;
-    G1X *bk = (G1X *)bucket, *po = (G1X *)pout;
-    const u32 rpp = rp_partials & 1u;
-    switch (rounds) {
-    case 1: hipLaunchKernelGGL(k_ba_finish<1>, dim3(fgrid), dim3(64), 0, st, pts, sorted, tab, item_start, nkeys, (const uint4 *)nodes, bk, po, rpp); break;
-    case 2: hipLaunchKernelGGL(k_ba_finish<2>, dim3(fgrid), dim3(64), 0, st, pts, sorted, tab, item_start, nkeys, (const uint4 *)nodes, bk, po, rpp); break;
-    case 3: hipLaunchKernelGGL(k_ba_finish<3>, dim3(fgrid), dim3(64), 0, st, pts, sorted, tab, item_start, nkeys, (const uint4 *)nodes, bk, po, rpp); break;
-    default: hipLaunchKernelGGL(k_ba_finish<4>, dim3(fgrid), dim3(64), 0, st, pts, sorted, tab, item_start, nkeys, (const uint4 *)nodes, bk, po, rpp); break;
-    }
+static void launch_accum_affine_ba(const MsmLevelLaunch &a, const MsmLevel1Form &f, u32 rounds, uint64_t items_bound, u32 target_waves, const MsmBaScratch &sc) {
+    const unsigned tgrid = (unsigned)((items_bound + 255) / 256);
+    hipLaunchKernelGGL(k_msm_item_table<Fp>, dim3(tgrid < 8192 ? (tgrid ? tgrid : 1) : 8192), dim3(256), 0, a.st, a.lv.start, a.lv.cnt, a.lv.items, a.lv.item_start, a.nkeys, (uint4 *)a.item_table);
+    if (a.ev_before) (void)hipEventRecord(a.ev_before, a.st);
+    if (rounds >= 1) ba_round<1>(a, f, items_bound, target_waves, sc, rounds == 1);
+    if (rounds >= 2) ba_round<2>(a, f, items_bound, target_waves, sc, rounds == 2);
+    if (rounds >= 3) ba_round<3>(a, f, items_bound, target_waves, sc, rounds == 3);
+    if (rounds >= 4) ba_round<4>(a, f, items_bound, target_waves, sc, true);
 }
 // the finisher over partial sums in the packed R' form (k_msm_accum_xyzz29's additions)
 struct FinG1rp {
@@ -149,6 +130,17 @@ static void launch_to_rprime(hipStream_t st, void *dst, const void *src, size_t 
 }
 
 const MsmCurveOps &msm_g1_ops() {
-    static const MsmCurveOps ops = {sizeof(G1X), launch_accum_affine<Fp>, launch_accum_xyzz<Fp>, launch_bucket_reduce<Fp>, SumT<Fp>::value, launch_sum_tree<Fp>, launch_precompute<Fp>, launch_precompute_batched<Fp>, sizeof(Fp), host_combine_windows<Fp>, launch_sum_slices<Fp>, launch_accum_affine29, launch_accum_xyzz29, launch_accum_affine_ba, launch_finish_g1, 256, 4096, launch_to_rprime};
+    static const MsmCurveOps ops = [] {
+        MsmCurveOps o = msm_generic_ops<Fp>(1);
+        o.accum_affine = launch_accum_affine<Fp>;
+        o.accum_affine_rp = launch_accum_affine29;
+        o.accum_xyzz_rp = launch_accum_xyzz29;
+        o.accum_affine_ba = launch_accum_affine_ba;
+        o.finish_keys = launch_finish_g1;
+        o.finish_T = 256;
+        o.finish_max = 4096;
+        o.to_rprime = launch_to_rprime;
+        return o;
+    }();
     return ops;
 }

@@ -66,10 +66,8 @@ __global__ void __launch_bounds__(64, 2) k_msm_accum_affine_g2_lds(const G2Aff *
     }
 }
 
-static void launch_accum_affine_g2(hipStream_t st, unsigned grid, const void *pts, const u32 *sorted, const u32 *start, const u32 *cnt, const u32 *items,
-                                   const u32 *item_start, u32 nkeys, u32 L, void *bucket, void *pout) {
-    hipLaunchKernelGGL(k_msm_accum_affine_g2_lds, dim3(grid), dim3(64), 0, st, (const G2Aff *)pts, sorted, start, cnt, items, item_start, nkeys, L,
-                       (G2X *)bucket, (G2X *)pout);
+static void launch_accum_affine_g2(const MsmLevelLaunch &a) {
+    hipLaunchKernelGGL(k_msm_accum_affine_g2_lds, dim3(a.grid), dim3(64), 0, a.st, (const G2Aff *)a.pts, a.sorted, a.lv.start, a.lv.cnt, a.lv.items, a.lv.item_start, a.nkeys, a.L, (G2X *)a.bucket, (G2X *)a.partial_out);
 }
 // The same level-1 accumulation in the 9 x 29-bit representation (curve29_g2.cuh): accumulator image [word][lane] of 4 x 18 words
 // (18 KiB per 64-lane workgroup), points read in the R' packed form, an item's sum converted back to the standard XYZZ once.
@@ -174,20 +172,15 @@ __global__ void __launch_bounds__(64, 2) k_msm_accum_xyzz_g2_29(const G2X *parti
         bucket[key] = out;
     }
 }
-static void launch_accum_xyzz_g2_29(hipStream_t st, unsigned grid, const void *pin, const u32 *start, const u32 *cnt, const u32 *items, const u32 *item_start,
-                                    u32 nkeys, u32 L, void *bucket, void *pout) {
-    hipLaunchKernelGGL(k_msm_accum_xyzz_g2_29, dim3(grid), dim3(64), 0, st, (const G2X *)pin, start, cnt, items, item_start, nkeys, (G2X *)bucket, (G2X *)pout);
+static void launch_accum_xyzz_g2_29(const MsmLevelLaunch &a) {
+    hipLaunchKernelGGL(k_msm_accum_xyzz_g2_29, dim3(a.grid), dim3(64), 0, a.st, (const G2X *)a.partial_in, a.lv.start, a.lv.cnt, a.lv.items, a.lv.item_start, a.nkeys, (G2X *)a.bucket, (G2X *)a.partial_out);
 }
-static void launch_accum_affine_g2_29(hipStream_t st, unsigned grid, const void *pts, const u32 *sorted, const u32 *start, const u32 *cnt, const u32 *items,
-                                      const u32 *item_start, u32 nkeys, u32 L, void *bucket, void *pout, void *item_tab, u32 rp_partials,
-                                      hipEvent_t ev_before) {
-    hipLaunchKernelGGL(k_msm_item_table<Fp2>, dim3(grid < 32768 ? grid : 32768), dim3(64), 0, st, start, cnt, items, item_start, nkeys, (uint4 *)item_tab);
-    if (ev_before) (void)hipEventRecord(ev_before, st);
-    // rp_partials: bit 0 = partial sums stay in the R' form, bits 2..3 = log2 of the waves per workgroup (`grid` counts waves)
-    const u32 wg = 1u << ((rp_partials >> 2) & 3u);
-    const unsigned g = (grid + wg - 1) / wg;
-#define MI_L1G2(WG) hipLaunchKernelGGL(k_msm_accum_affine_g2_29<WG>, dim3(g), dim3(64 * WG), 0, st, (const G2Aff *)pts, sorted, (const uint4 *)item_tab, item_start, nkeys, \
-                                       (G2X *)bucket, (G2X *)pout, rp_partials & 1u)
+static void launch_accum_affine_g2_29(const MsmLevelLaunch &a, const MsmLevel1Form &f) {   // (one build: f.waves_per_simd is not read)
+    hipLaunchKernelGGL(k_msm_item_table<Fp2>, dim3(a.grid < 32768 ? a.grid : 32768), dim3(64), 0, a.st, a.lv.start, a.lv.cnt, a.lv.items, a.lv.item_start, a.nkeys, (uint4 *)a.item_table);
+    if (a.ev_before) (void)hipEventRecord(a.ev_before, a.st);
+    const u32 wg = f.wg_waves, g = (a.grid + wg - 1) / wg;   // a.grid counts waves
+#define MI_L1G2(WG) hipLaunchKernelGGL(k_msm_accum_affine_g2_29<WG>, dim3(g), dim3(64 * WG), 0, a.st, (const G2Aff *)a.pts, a.sorted, (const uint4 *)a.item_table, \
+                                       a.lv.item_start, a.nkeys, (G2X *)a.bucket, (G2X *)a.partial_out, f.rp_partials ? 1u : 0u)
     if (wg == 4) MI_L1G2(4); else if (wg == 2) MI_L1G2(2); else MI_L1G2(1);
 #undef MI_L1G2
 }
@@ -229,6 +222,16 @@ static void launch_g2_to_rprime(hipStream_t st, void *dst, const void *src, size
 }
 
 const MsmCurveOps &msm_g2_ops() {
-    static const MsmCurveOps ops = {sizeof(G2X), launch_accum_affine_g2, launch_accum_xyzz<Fp2>, launch_bucket_reduce<Fp2>, SumT<Fp2>::value, launch_sum_tree<Fp2>, launch_precompute<Fp2>, launch_precompute_batched<Fp2>, sizeof(Fp2), host_combine_windows<Fp2>, launch_sum_slices<Fp2>, launch_accum_affine_g2_29, launch_accum_xyzz_g2_29, nullptr, launch_finish_g2, 64, 1024, launch_g2_to_rprime};
+    static const MsmCurveOps ops = [] {
+        MsmCurveOps o = msm_generic_ops<Fp2>(2);   // (accum_affine_ba stays null: no batch-affine kernels for G2)
+        o.accum_affine = launch_accum_affine_g2;   // (the accumulator in LDS: k_msm_accum_affine<Fp2> is not built)
+        o.accum_affine_rp = launch_accum_affine_g2_29;
+        o.accum_xyzz_rp = launch_accum_xyzz_g2_29;
+        o.finish_keys = launch_finish_g2;
+        o.finish_T = 64;
+        o.finish_max = 1024;
+        o.to_rprime = launch_g2_to_rprime;
+        return o;
+    }();
     return ops;
 }

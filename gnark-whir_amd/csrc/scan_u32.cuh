@@ -1,5 +1,5 @@
 // The library's one global exclusive scan of u32: the single-wave kernels, the wave scans they are made of and the host driver.  Shared
-// by msm.hip (whose fused kernels compute or consume the block sums themselves and launch k_scan_final directly) and setup.hip.
+// by msm.hip (whose fused kernels add up the block sums themselves: sums_ready) and setup.hip.
 // The kernels are static: every translation unit that includes this header carries its own copy of the ones it launches.
 #pragma once
 #include "ctx.h"
@@ -82,22 +82,17 @@ static __global__ void __launch_bounds__(64) k_scan_final(const u32 *in, size_t 
     }
 }
 // total_host / copy_src -> copy_host: words the last kernel also leaves in pinned host memory (k_scan_final), or null
+// sums_ready: a kernel of the caller's has left the raw sums of the (<= SCAN_MAX_INLINE_BLOCKS) blocks in tmp: only the last kernel is launched
 static int32_t exclusive_scan(mi_ctx *ctx, hipStream_t st, const u32 *in, size_t m, u32 *out, DevBuf &tmp,
-                              u32 *total_host = nullptr, const u32 *copy_src = nullptr, u32 *copy_host = nullptr) {
+                              u32 *total_host = nullptr, const u32 *copy_src = nullptr, u32 *copy_host = nullptr, bool sums_ready = false) {
     u32 nblocks = (u32)((m + SCAN_BLOCK - 1) / SCAN_BLOCK);
     if (nblocks == 0) nblocks = 1;
     MI_TRY(mi_reserve(ctx, tmp, (size_t)(nblocks + 1) * 4));
     u32 *bs = (u32 *)tmp.p;
-    if (nblocks == 1) {
-        hipLaunchKernelGGL(k_scan_final, dim3(1), dim3(SCAN_THREADS), 0, st, in, m, bs, out, 1, total_host, copy_src, copy_host);
-    } else if (nblocks <= SCAN_MAX_INLINE_BLOCKS) {
-        hipLaunchKernelGGL(k_scan_block_sums, dim3(nblocks), dim3(SCAN_THREADS), 0, st, in, m, bs);
-        hipLaunchKernelGGL(k_scan_final, dim3(nblocks), dim3(SCAN_THREADS), 0, st, in, m, bs, out, 2, total_host, copy_src, copy_host);
-    } else {
-        hipLaunchKernelGGL(k_scan_block_sums, dim3(nblocks), dim3(SCAN_THREADS), 0, st, in, m, bs);
-        hipLaunchKernelGGL(k_scan_of_sums, dim3(1), dim3(SCAN_THREADS), 0, st, bs, nblocks);
-        hipLaunchKernelGGL(k_scan_final, dim3(nblocks), dim3(SCAN_THREADS), 0, st, in, m, bs, out, 0, total_host, copy_src, copy_host);
-    }
+    const int mode = nblocks == 1 && !sums_ready ? 1 : nblocks <= SCAN_MAX_INLINE_BLOCKS ? 2 : 0;   // (k_scan_final's modes)
+    if (mode != 1 && !sums_ready) hipLaunchKernelGGL(k_scan_block_sums, dim3(nblocks), dim3(SCAN_THREADS), 0, st, in, m, bs);
+    if (mode == 0) hipLaunchKernelGGL(k_scan_of_sums, dim3(1), dim3(SCAN_THREADS), 0, st, bs, nblocks);
+    hipLaunchKernelGGL(k_scan_final, dim3(nblocks), dim3(SCAN_THREADS), 0, st, in, m, bs, out, mode, total_host, copy_src, copy_host);
     MI_CHECK_HIP(ctx, hipGetLastError());
     return MI_OK;
 }
