@@ -19,7 +19,7 @@ EXPORTS = [
     "mi_ntt", "mi_ntt_dev", "mi_compute_h", "mi_compute_h_dev", "mi_msm_g1", "mi_msm_g1_dev", "mi_msm_g2",
     "mi_msm_g2_dev", "mi_groth16_prove", "mi_groth16_prove_dev", "mi_get_stats", "mi_g1_compress",
     "mi_g2_compress", "mi_proof_write", "mi_g1_sum", "mi_g2_sum", "mi_gen_scalars_dev", "mi_gen_g1_dev",
-    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
+    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_debug_decode_g1_dev", "mi_debug_decode_g2_dev", "mi_debug_hash_to_field_dev", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
     "mi_dev_alloc", "mi_dev_free", "mi_dev_upload", "mi_dev_download", "mi_dev_sync",
     "mi_msm_precompute_g1_dev", "mi_msm_precompute_g2_dev", "mi_msm_g1_fixed_dev", "mi_msm_g2_fixed_dev", "mi_msm_table_to_rprime_g1_dev", "mi_msm_table_to_rprime_g2_dev", "mi_pk_table_plan",
     "mi_batch_scalar_mul_g1", "mi_batch_scalar_mul_g1_dev", "mi_batch_scalar_mul_g2", "mi_batch_scalar_mul_g2_dev",
@@ -49,6 +49,8 @@ PROVE_W_EVAL_C = 1
 VERIFY_EXPORTS = ["mi_vk_load", "mi_vk_free", "mi_pedersen_vk_make", "mi_groth16_verify", "mi_groth16_verify_batch"]
 VERIFY_OK, VERIFY_PAIRING, VERIFY_PEDERSEN, VERIFY_MALFORMED = 0, 1, 2, 3
 PAIRING_FINAL_EXP = 1
+# include/mi355x_groth16_verify_bytes.h (groth16.Verify from a proof's bytes: decode and hash on the device)
+VERIFY_BYTES_EXPORTS = ["mi_vk_set_public_committed", "mi_groth16_verify_bytes", "mi_groth16_verify_bytes_batch", "mi_proof_read", "mi_hash_to_field"]
 
 
 class PkDesc(C.Structure):
@@ -168,6 +170,10 @@ class VkDesc(C.Structure):
 class VerifyInput(C.Structure):
     _fields_ = [("proof", C.c_uint64 * 32), ("commitments", C.c_void_p), ("pok", C.c_void_p), ("public_inputs", C.c_void_p),
                 ("commitment_values", C.c_void_p), ("fold_challenge", C.c_void_p)]
+
+
+class VerifyBytesInput(C.Structure):
+    _fields_ = [("proof", C.c_void_p), ("proof_len", C.c_size_t), ("public_inputs", C.c_void_p)]
 
 
 class Bsb22Input(C.Structure):
@@ -613,6 +619,34 @@ class Context:
             for b in (dx, dy, dz):
                 if b: b.free()
 
+    def decode_points(self, enc: bytes, g2=False):
+        """mi_debug_decode_g1_dev / _g2_dev over host bytes: n encodings of 32 (64) bytes -> ((n, 8) or (n, 16) uint64, (n,) uint8 malformed)"""
+        w = 64 if g2 else 32
+        assert len(enc) % w == 0
+        n = len(enc) // w
+        if not n:
+            return np.zeros((0, w // 4), np.uint64), np.zeros(0, np.uint8)
+        de = self.to_dev(np.frombuffer(enc, np.uint8)); do = self.alloc(n * w * 2); db = self.alloc(max(n, 32))
+        try:
+            fn = self.lib.mi_debug_decode_g2_dev if g2 else self.lib.mi_debug_decode_g1_dev
+            self._ck(fn(self.h, _p(de.ptr), C.c_size_t(n), _p(do.ptr), _p(db.ptr)))
+            self.sync()
+            return do.download((n, w // 4)), db.download((n,), np.uint8)
+        finally:
+            for b in (de, do, db): b.free()
+
+    def hash_to_field_dev(self, dst: bytes, msgs):
+        """mi_debug_hash_to_field_dev: messages of one length and one dst -> (n, 4) uint64 Montgomery"""
+        n = len(msgs); ln = len(msgs[0]) if n else 0
+        assert all(len(m) == ln for m in msgs) and n
+        dd = self.to_dev(np.frombuffer(dst, np.uint8)); dm = self.to_dev(np.frombuffer(b"".join(msgs) + b"\0", np.uint8)); do = self.alloc(32 * n)
+        try:
+            self._ck(self.lib.mi_debug_hash_to_field_dev(self.h, _p(dd.ptr), C.c_uint32(len(dst)), _p(dm.ptr), C.c_size_t(ln), C.c_size_t(n), _p(do.ptr)))
+            self.sync()
+            return do.download((n, 4))
+        finally:
+            for b in (dd, dm, do): b.free()
+
     def trim(self):
         """mi_ctx_trim: every grow-only workspace of this (idle) context goes back to the device"""
         self._ck(self.lib.mi_ctx_trim(self.h))
@@ -665,6 +699,31 @@ class VerifyingKey:
     def verify_batch(self, proofs):
         arr, keep = self._inputs(list(proofs)); out = np.full(len(arr), 255, np.uint8)
         self.ctx._ck(self.ctx.lib.mi_groth16_verify_batch(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), _p(out)))
+        return out
+
+    # ---- from a proof's bytes (include/mi355x_groth16_verify_bytes.h)
+    def set_public_committed(self, lists):
+        """mi_vk_set_public_committed: gnark's PublicAndCommitmentCommitted, one list of 1-based indices per commitment"""
+        off = np.cumsum([0] + [len(l) for l in lists]).astype(np.uint32)
+        idx = np.array([j for l in lists for j in l], np.uint32)
+        assert len(lists) == self.n_commitments
+        self.ctx._ck(self.ctx.lib.mi_vk_set_public_committed(self.ctx.h, self.h, _p(off), _p(idx) if len(idx) else None))
+
+    def verify_bytes(self, proof: bytes, public_inputs=None) -> int:
+        v = C.c_uint8(255); pub = None if public_inputs is None else _u64(public_inputs)
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_bytes(self.ctx.h, self.h, proof, C.c_size_t(len(proof)), _p(pub), C.byref(v)))
+        return int(v.value)
+
+    def verify_bytes_batch(self, proofs):
+        """proofs: [(bytes, public_inputs (nb_public - 1, 4) or None)]"""
+        proofs = list(proofs); arr = (VerifyBytesInput * len(proofs))(); keep = []
+        for i, (b, pub) in enumerate(proofs):
+            buf = C.create_string_buffer(b, len(b)); keep.append(buf)
+            arr[i].proof, arr[i].proof_len = C.addressof(buf), len(b)
+            if pub is not None:
+                pub = _u64(pub); keep.append(pub); arr[i].public_inputs = pub.ctypes.data
+        out = np.full(len(proofs), 255, np.uint8)
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_bytes_batch(self.ctx.h, self.h, arr, C.c_size_t(len(proofs)), _p(out)))
         return out
 
     def free(self):
@@ -986,6 +1045,22 @@ def proof_write(raw, commitments=None, pok=None):
     buf = np.zeros(164 + 32 * n, np.uint8)
     ln = load().mi_proof_write(_p(_u64(raw)), _p(commitments), C.c_uint32(n), _p(pok), _p(buf))
     return bytes(buf[:ln])
+
+
+def proof_read(data: bytes, n_commitments):
+    """mi_proof_read: Proof.WriteTo's bytes -> (raw (32,) uint64, commitments (n, 8), pok (8,)), or None when the library refuses them"""
+    raw = np.zeros(32, np.uint64); cm = np.zeros((n_commitments, 8), np.uint64); pok = np.zeros(8, np.uint64)
+    rc = load().mi_proof_read(data, C.c_size_t(len(data)), C.c_uint32(n_commitments), _p(raw), _p(cm) if n_commitments else None, _p(pok))
+    return (raw, cm, pok) if rc == 0 else None
+
+
+def hash_to_field(dst: bytes, msg: bytes):
+    """mi_hash_to_field -> (4,) uint64 Montgomery"""
+    out = np.zeros(4, np.uint64)
+    rc = load().mi_hash_to_field(dst, C.c_size_t(len(dst)), msg, C.c_size_t(len(msg)), _p(out))
+    if rc != 0:
+        raise MiError(f"mi_hash_to_field rc={rc}")
+    return out
 
 
 def g1_compress(p):

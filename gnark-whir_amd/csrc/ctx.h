@@ -37,6 +37,7 @@ enum {
     WS_SCAN = 12,          // setup.hip: block sums of the shared u32 scan (scan_u32.cuh)                main
     WS_VERIFY = 13,        // verify.hip: scalars, pairs, Miller values, flags and verdicts of a batch           main
     WS_H = 14,             // prove.hip / group.hip: h, computeH's result and the Z MSM's scalars        main, read by msm[MSM_SLOT_Z].stream
+    WS_VERIFY_BYTES = 15,  // verify_bytes.hip: proof bytes, lists, decoded points, flags, hashes of a batch           main
     WS_PROVE_IN = 16,      // prove.hip / group.hip: W (+ a, b, c) of a prove over host inputs           filled on copy_stream
     WS_B_WIRES = 17,       // prove.hip: W gathered to the wires that own a pk.G1.B point                msm[MSM_SLOT_B1].stream
     WS_POK_VALUES = 19,    // prove.hip ProveKnowledge: the committed values                             msm[MSM_SLOT_POK].stream
@@ -44,7 +45,7 @@ enum {
     WS_FB_SCALARS = 21,    // fixed_base.hip host entry point: the scalars                               main
     WS_FB_OUT = 22,        // fixed_base.hip host entry point: the points                                main
     WS_RPRIME = 23,        // msm.hip device entry point: the points in the R' packed form               main
-    WS_COUNT = 24          // 15 and 18 are free
+    WS_COUNT = 24          // 18 is free
 };
 // mi_ctx::ev[]: every event of the context in use, what it marks and the stream that records it ("main" = ctx->stream).
 enum {

@@ -10,22 +10,11 @@
 //   k_pairing_miller    one lane per (proof, pair): a Miller loop, 384 B out
 //   k_verify_judge      one lane per proof: the products of its Miller values, the final exponentiations, the comparisons -> a verdict byte
 // Everything of a batch lives in ONE grow-only workspace (WS_VERIFY): nothing is allocated in steady state.
-#include "ctx.h"
-#include "../../include/mi355x_groth16_verify.h"
-#include "pairing_ops.cuh"
+// mi_verify_run is that batch; verify_bytes.hip calls it too, with the proofs it decoded (verify_internal.h holds mi_vk for both).
+#include "verify_internal.h"
 #include <cstring>
 #include <string>
 #include <vector>
-
-struct mi_vk {
-    G1Aff alpha1;
-    G2Aff beta2, gamma2, delta2;
-    std::vector<G1Aff> k;              // host copy: K[0] and the counts
-    G1Aff *k_dev = nullptr;            // K[1 .. n_k): the bases of kSum's MSM, uploaded once
-    Fp12 *e_alpha_beta_dev = nullptr;  // e(alpha, beta)^s, computed once
-    uint32_t nb_public = 0, n_commitments = 0;
-    std::vector<mi_pedersen_vk> ped;
-};
 
 namespace {
 
@@ -69,9 +58,6 @@ __global__ void __launch_bounds__(64, 1) k_verify_judge(const Fp12 *ml, u32 pair
     verdicts[i] = verify_judge(ml + i * pairs_per_proof, pairs_per_proof - MI_VERIFY_GROTH_PAIRS, &eab, flags[i] != 0);
 }
 
-inline unsigned grid64(size_t n) { return (unsigned)((n + 63) / 64); }
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 G1Aff g1_of(const mi_g1_affine &p) { G1Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
 G2Aff g2_of(const mi_g2_affine &p) { G2Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
 static_assert(sizeof(mi_pedersen_vk) == 2 * sizeof(G2Aff) && sizeof(mi_g1_affine) == sizeof(G1Aff) && sizeof(mi_fr) == sizeof(Fr),
@@ -88,7 +74,9 @@ int32_t pairing_enqueue(mi_ctx *ctx, const G1Aff *p_dev, const G2Aff *q_dev, siz
     return MI_OK;
 }
 
-int32_t verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts) {
+}   // namespace
+
+int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts, const uint8_t *decode_malformed) {
     if (!ctx) return MI_EINVAL;
     if (!vk || (!in && n) || (!verdicts && n)) MI_FAIL(ctx, MI_EINVAL, "verify: null vk, input or verdict pointer");
     if (n > ((size_t)1 << 24)) MI_FAIL(ctx, MI_EINVAL, "verify: more than 2^24 proofs in one batch");
@@ -111,7 +99,7 @@ int32_t verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size
     std::vector<uint8_t> flags(n, 0);
     std::vector<mi_fr> scal((size_t)n * ns);
     for (size_t i = 0; i < n; i++) {
-        flags[i] = verify_well_formed(kref, proof_ref(i)) ? 0 : 1;
+        flags[i] = (decode_malformed && decode_malformed[i]) || !verify_well_formed(kref, proof_ref(i)) ? 1 : 0;
         if (flags[i]) continue;   // its scalars stay zero and are never read: no MSM runs for a malformed proof
         if (n_pub) std::memcpy(&scal[i * ns], in[i].public_inputs, (size_t)n_pub * sizeof(mi_fr));
         if (nc) std::memcpy(&scal[i * ns + n_pub], in[i].commitment_values, (size_t)nc * sizeof(mi_fr));
@@ -151,8 +139,6 @@ int32_t verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MI_OK;
 }
-
-}   // namespace
 
 extern "C" {
 
@@ -195,6 +181,7 @@ int32_t mi_vk_load(mi_ctx *ctx, const mi_vk_desc *d, mi_vk **out) {
     if (!vk) MI_FAIL(ctx, MI_ENOMEM, "vk load: out of host memory");
     vk->alpha1 = alpha; vk->beta2 = beta; vk->gamma2 = gamma; vk->delta2 = delta;
     vk->nb_public = d->nb_public; vk->n_commitments = d->n_commitments;
+    vk->pc_off.assign((size_t)d->n_commitments + 1, 0);
     vk->k.resize(d->n_k);
     std::memcpy(vk->k.data(), d->k, d->n_k * sizeof(G1Aff));
     if (d->n_commitments) vk->ped.assign(d->ped, d->ped + d->n_commitments);
@@ -254,10 +241,10 @@ int32_t mi_pedersen_vk_make(mi_ctx *ctx, const mi_fr *sigma, uint32_t n, mi_pede
 
 int32_t mi_groth16_verify(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, uint8_t *verdict) {
     if (ctx && (!in || !verdict)) MI_FAIL(ctx, MI_EINVAL, "verify: null input or verdict pointer");
-    return verify_run(ctx, vk, in, 1, verdict);
+    return mi_verify_run(ctx, vk, in, 1, verdict, nullptr);
 }
 int32_t mi_groth16_verify_batch(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts) {
-    return verify_run(ctx, vk, in, n, verdicts);
+    return mi_verify_run(ctx, vk, in, n, verdicts, nullptr);
 }
 
 // ---------------------------------------------------------------- debug surface (include/mi355x_groth16_debug.h)

@@ -1,0 +1,191 @@
+// groth16.Verify from the bytes of a proof (include/mi355x_groth16_verify_bytes.h): decode and hash on the device, then the batch body
+// of verify.hip (mi_verify_run) over the decoded records, and the three debug entry points over the same arithmetic.
+//
+// One batch, every launch on ctx->stream:
+//   host      the framing (proof_len, null pointers: MI_EINVAL), the count inside each proof against the key's (-> malformed)
+//   k_decode_g1    one lane per (proof, G1 point): Ar, Krs, the commitments, pok -> a G1Aff and a malformed byte   (decode_ops.cuh)
+//   k_decode_g2    one lane per proof: Bs -> a G2Aff and a malformed byte (an Fp2 square root: four fixed exponentiations)
+//   k_verify_hash  one lane per proof: commitment_values and fold_challenge from the decoded commitments, the public inputs and the
+//                  key's committed lists (sha256_h2f.cuh); a proof that did not decode is skipped
+//   host      the decoded records come back and go through mi_verify_run, the body of mi_groth16_verify_batch, which assembles on the
+//             host as it always did; a proof that did not decode enters it as malformed and none of its words is read
+// Two decode kernels rather than one: a G2 lane does four times the work of a G1 lane, and in one wave the G1 lanes would wait for it.
+// Everything of a batch lives in ONE grow-only workspace (WS_VERIFY_BYTES): nothing is allocated in steady state.
+#include "verify_internal.h"
+#include "../../include/mi355x_groth16_verify_bytes.h"
+#include "sha256_h2f.cuh"
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace {
+
+// enc: n_lanes encodings of 32 bytes.  per_proof == 0: back to back.  Otherwise lane = proof * per_proof + slot and the encoding is
+// slot `slot` of that proof's bytes (proof_g1_slot_offset), proofs proof_len apart.
+__global__ void __launch_bounds__(64, 1) k_decode_g1(const uint8_t *enc, size_t proof_len, u32 per_proof, G1Aff *out, uint8_t *bad, size_t n_lanes) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_lanes) return;
+    const uint8_t *src = per_proof ? enc + (i / per_proof) * proof_len + proof_g1_slot_offset((u32)(i % per_proof)) : enc + 32 * i;
+    uint8_t b[32];
+    for (int k = 0; k < 32; k++) b[k] = src[k];
+    G1Aff p;
+    const bool ok = g1_decode(&p, b);
+    out[i] = p;
+    bad[i] = ok ? 0 : 1;
+}
+// enc: n encodings of 64 bytes, stride apart
+__global__ void __launch_bounds__(64, 1) k_decode_g2(const uint8_t *enc, size_t stride, G2Aff *out, uint8_t *bad, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t *src = enc + i * stride;
+    uint8_t b[64];
+    for (int k = 0; k < 64; k++) b[k] = src[k];
+    G2Aff q;
+    const bool ok = g2_decode(&q, b);
+    out[i] = q;
+    bad[i] = ok ? 0 : 1;
+}
+// g1: per proof its 3 + nc decoded points in slot order (commitments from slot 2); bad1 / bad2 / bad_count -> bad[i] for the host
+__global__ void __launch_bounds__(64, 1) k_verify_hash(const G1Aff *g1, const uint8_t *bad1, const uint8_t *bad2, u32 nc, const Fr *public_inputs, u32 n_pub,
+                                                       const u32 *pc_off, const u32 *pc_idx, Fr *values, Fr *folds, uint8_t *bad, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32 slots = proof_g1_slots(nc);
+    u32 b = bad[i] | bad2[i];   // bad[i] arrives holding the host's count check
+    for (u32 s = 0; s < slots; s++) b |= bad1[i * slots + s];
+    bad[i] = b ? 1 : 0;
+    Fr fold = Fr::zero();
+    for (u32 k = 0; k < nc; k++) values[i * nc + k] = Fr::zero();
+    if (!b && nc) bsb22_hashes(g1 + i * slots + 2, nc, public_inputs + i * n_pub, n_pub, pc_off, pc_idx, values + i * nc, &fold);
+    folds[i] = fold;
+}
+__global__ void __launch_bounds__(64, 1) k_hash_to_field(const uint8_t *msgs, size_t msg_len, const uint8_t *dst, u32 dst_len, Fr *out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint8_t d[255];
+    for (u32 k = 0; k < dst_len; k++) d[k] = dst[k];
+    out[i] = hash_to_field(d, dst_len, msgs + i * msg_len, msg_len);
+}
+
+int32_t verify_bytes_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, uint8_t *verdicts) {
+    if (!ctx) return MI_EINVAL;
+    if (!vk || (!in && n) || (!verdicts && n)) MI_FAIL(ctx, MI_EINVAL, "verify bytes: null vk, input or verdict pointer");
+    if (n > ((size_t)1 << 24)) MI_FAIL(ctx, MI_EINVAL, "verify bytes: more than 2^24 proofs in one batch");
+    const u32 nc = vk->n_commitments, n_pub = vk->nb_public - 1, slots = proof_g1_slots(nc);
+    const size_t plen = proof_bytes_len(nc);
+    for (size_t i = 0; i < n; i++) {
+        if (!in[i].proof) MI_FAIL(ctx, MI_EINVAL, "verify bytes: proof is null");
+        if (in[i].proof_len != plen)
+            MI_FAIL(ctx, MI_EINVAL, "verify bytes: proof_len is " + std::to_string(in[i].proof_len) + ", the key's proofs have " + std::to_string(plen) + " bytes");
+        if (n_pub && !in[i].public_inputs) MI_FAIL(ctx, MI_EINVAL, "verify bytes: public_inputs is null");
+    }
+    if (!n) return MI_OK;
+    // ---- workspace: bytes | public inputs | committed offsets | committed indices | G1 | G2 | bad G1 | bad G2 | bad | values | folds
+    const size_t n_idx = vk->pc_idx.size();
+    const size_t off_pub = up256(n * plen), off_po = off_pub + up256(n * n_pub * sizeof(Fr)), off_pi = off_po + up256((nc + 1) * sizeof(u32));
+    const size_t off_g1 = off_pi + up256(n_idx * sizeof(u32)), off_g2 = off_g1 + up256(n * slots * sizeof(G1Aff)), off_b1 = off_g2 + up256(n * sizeof(G2Aff));
+    const size_t off_b2 = off_b1 + up256(n * slots), off_bad = off_b2 + up256(n), off_val = off_bad + up256(n), off_fold = off_val + up256(n * nc * sizeof(Fr));
+    const size_t total = off_fold + up256(n * sizeof(Fr));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY_BYTES], total));
+    char *ws = (char *)ctx->ws[WS_VERIFY_BYTES].p;
+    // ---- host: one staging image of the first four regions and the count check
+    std::vector<uint8_t> stage(off_g1, 0), bad(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        std::memcpy(&stage[i * plen], in[i].proof, plen);
+        if (n_pub) std::memcpy(&stage[off_pub + i * n_pub * sizeof(Fr)], in[i].public_inputs, (size_t)n_pub * sizeof(Fr));
+        bad[i] = proof_bytes_count(in[i].proof) != nc;
+    }
+    std::memcpy(&stage[off_po], vk->pc_off.data(), (nc + 1) * sizeof(u32));
+    if (n_idx) std::memcpy(&stage[off_pi], vk->pc_idx.data(), n_idx * sizeof(u32));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws, stage.data(), off_g1, hipMemcpyHostToDevice, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_bad, bad.data(), n, hipMemcpyHostToDevice, ctx->stream));
+    // ---- device: decode, hash
+    hipLaunchKernelGGL(k_decode_g1, dim3(grid64(n * slots)), dim3(64), 0, ctx->stream, (const uint8_t *)ws, plen, slots, (G1Aff *)(ws + off_g1),
+                       (uint8_t *)(ws + off_b1), n * slots);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_decode_g2, dim3(grid64(n)), dim3(64), 0, ctx->stream, (const uint8_t *)ws + MI_PROOF_OFF_BS, plen, (G2Aff *)(ws + off_g2),
+                       (uint8_t *)(ws + off_b2), n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_verify_hash, dim3(grid64(n)), dim3(64), 0, ctx->stream, (const G1Aff *)(ws + off_g1), (const uint8_t *)(ws + off_b1),
+                       (const uint8_t *)(ws + off_b2), nc, (const Fr *)(ws + off_pub), n_pub, (const u32 *)(ws + off_po), (const u32 *)(ws + off_pi),
+                       (Fr *)(ws + off_val), (Fr *)(ws + off_fold), (uint8_t *)(ws + off_bad), n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    // ---- host: the decoded records as mi_verify_input, then the body of mi_groth16_verify_batch
+    std::vector<G1Aff> g1(n * slots);
+    std::vector<G2Aff> g2(n);
+    std::vector<Fr> values((size_t)n * nc), folds(n);
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(g1.data(), ws + off_g1, g1.size() * sizeof(G1Aff), hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(g2.data(), ws + off_g2, g2.size() * sizeof(G2Aff), hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(bad.data(), ws + off_bad, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (nc) MI_CHECK_HIP(ctx, hipMemcpyAsync(values.data(), ws + off_val, values.size() * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(folds.data(), ws + off_fold, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<mi_verify_input> dec(n);
+    for (size_t i = 0; i < n; i++) {
+        const G1Aff *p = &g1[i * slots];
+        std::memcpy(&dec[i].proof.ar, &p[0], sizeof(G1Aff));
+        std::memcpy(&dec[i].proof.bs, &g2[i], sizeof(G2Aff));
+        std::memcpy(&dec[i].proof.krs, &p[1], sizeof(G1Aff));
+        dec[i].commitments = (const mi_g1_affine *)(p + 2);
+        dec[i].pok = (const mi_g1_affine *)(p + 2 + nc);
+        dec[i].public_inputs = in[i].public_inputs;
+        dec[i].commitment_values = nc ? (const mi_fr *)&values[i * nc] : nullptr;
+        dec[i].fold_challenge = (const mi_fr *)&folds[i];
+    }
+    return mi_verify_run(ctx, vk, dec.data(), n, verdicts, bad.data());
+}
+
+}   // namespace
+
+extern "C" {
+
+int32_t mi_vk_set_public_committed(mi_ctx *ctx, mi_vk *vk, const uint32_t *offsets, const uint32_t *indices) {
+    if (!ctx) return MI_EINVAL;
+    if (!vk || !offsets) MI_FAIL(ctx, MI_EINVAL, "public committed: null vk or offsets");
+    const u32 nc = vk->n_commitments;
+    if (offsets[0] != 0) MI_FAIL(ctx, MI_EINVAL, "public committed: offsets[0] is not 0");
+    for (u32 i = 0; i < nc; i++)
+        if (offsets[i + 1] < offsets[i]) MI_FAIL(ctx, MI_EINVAL, "public committed: offsets[" + std::to_string(i + 1) + "] is below offsets[" + std::to_string(i) + "]");
+    if (offsets[nc] && !indices) MI_FAIL(ctx, MI_EINVAL, "public committed: indices is null");
+    for (u32 i = 0; i < nc; i++)
+        for (u32 t = offsets[i]; t < offsets[i + 1]; t++)
+            if (indices[t] < 1 || indices[t] > vk->nb_public - 1 + i)
+                MI_FAIL(ctx, MI_EINVAL, "public committed: indices[" + std::to_string(t) + "] = " + std::to_string(indices[t]) + " of commitment " + std::to_string(i) +
+                                            " is outside 1 .. " + std::to_string(vk->nb_public - 1 + i));
+    vk->pc_off.assign(offsets, offsets + nc + 1);
+    vk->pc_idx.assign(indices, indices + offsets[nc]);
+    return MI_OK;
+}
+
+int32_t mi_groth16_verify_bytes(mi_ctx *ctx, const mi_vk *vk, const uint8_t *proof, size_t proof_len, const mi_fr *public_inputs, uint8_t *verdict) {
+    if (ctx && !verdict) MI_FAIL(ctx, MI_EINVAL, "verify bytes: null verdict pointer");
+    const mi_verify_bytes_input in{proof, proof_len, public_inputs};
+    return verify_bytes_run(ctx, vk, &in, 1, verdict);
+}
+int32_t mi_groth16_verify_bytes_batch(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, uint8_t *verdicts) {
+    return verify_bytes_run(ctx, vk, in, n, verdicts);
+}
+
+// ---------------------------------------------------------------- debug surface (include/mi355x_groth16_debug.h)
+int32_t mi_debug_decode_g1_dev(mi_ctx *ctx, const uint8_t *enc_dev, size_t n, mi_g1_affine *out_dev, uint8_t *bad_dev) {
+    if (!ctx || ((!enc_dev || !out_dev || !bad_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
+    if (!n) return MI_OK;
+    hipLaunchKernelGGL(k_decode_g1, dim3(grid64(n)), dim3(64), 0, ctx->stream, enc_dev, (size_t)0, 0u, (G1Aff *)out_dev, bad_dev, n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+int32_t mi_debug_decode_g2_dev(mi_ctx *ctx, const uint8_t *enc_dev, size_t n, mi_g2_affine *out_dev, uint8_t *bad_dev) {
+    if (!ctx || ((!enc_dev || !out_dev || !bad_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
+    if (!n) return MI_OK;
+    hipLaunchKernelGGL(k_decode_g2, dim3(grid64(n)), dim3(64), 0, ctx->stream, enc_dev, (size_t)64, (G2Aff *)out_dev, bad_dev, n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+int32_t mi_debug_hash_to_field_dev(mi_ctx *ctx, const uint8_t *dst_dev, uint32_t dst_len, const uint8_t *msgs_dev, size_t msg_len, size_t n, mi_fr *out_dev) {
+    if (!ctx || !dst_dev || dst_len == 0 || dst_len > 255 || ((!out_dev || (!msgs_dev && msg_len)) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
+    if (!n) return MI_OK;
+    hipLaunchKernelGGL(k_hash_to_field, dim3(grid64(n)), dim3(64), 0, ctx->stream, msgs_dev, msg_len, dst_dev, dst_len, (Fr *)out_dev, n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+}

@@ -2,14 +2,15 @@
 
 // groth16.Verify (reilabs/gnark-whir mt.go:497) on the device: include/mi355x_groth16_verify.h.
 //
-// STATUS: SOURCE ONLY, like the rest of the shim (mi355x.go): never compiled here.  The library is hash-free; this file computes what
-// gnark's verify.go computes on the host -- the hash-to-field of every commitment (with the public committed values) and the fold
-// challenge -- and hands the rest to mi_groth16_verify.
+// STATUS: SOURCE ONLY, like the rest of the shim (mi355x.go): never compiled here.  Verify computes what gnark's verify.go computes on
+// the host -- the hash-to-field of every commitment (with the public committed values) and the fold challenge -- and hands the rest to
+// mi_groth16_verify.  VerifyBytes takes Proof.WriteTo's bytes and leaves decoding and hashing to the device (mi_groth16_verify_bytes).
 package mi355x
 
 /*
 #include <stdlib.h>
 #include "mi355x_groth16_verify.h"
+#include "mi355x_groth16_verify_bytes.h"
 */
 import "C"
 
@@ -70,6 +71,23 @@ func LoadVerifyingKey(vk *groth16_bn254.VerifyingKey, device int) (*VerifyingKey
 	}
 	if err := status(out.ctx, C.mi_vk_load(out.ctx, &d, &out.dev)); err != nil {
 		C.mi_shutdown(out.ctx)
+		return nil, err
+	}
+	// PublicAndCommitmentCommitted in CSR form, for VerifyBytes: the device hashes each commitment with these values
+	offsets := make([]C.uint32_t, nc+1)
+	var indices []C.uint32_t
+	for i, s := range vk.PublicAndCommitmentCommitted {
+		for _, j := range s {
+			indices = append(indices, C.uint32_t(j))
+		}
+		offsets[i+1] = C.uint32_t(len(indices))
+	}
+	var idx *C.uint32_t
+	if len(indices) > 0 {
+		idx = &indices[0]
+	}
+	if err := status(out.ctx, C.mi_vk_set_public_committed(out.ctx, out.dev, &offsets[0], idx)); err != nil {
+		out.Close()
 		return nil, err
 	}
 	return out, nil
@@ -153,6 +171,35 @@ func Verify(vk *VerifyingKey, proof *groth16_bn254.Proof, publicWitness fr.Vecto
 	}
 	var verdict C.uint8_t
 	if err := status(vk.ctx, C.mi_groth16_verify(vk.ctx, vk.dev, &in, &verdict)); err != nil {
+		return err
+	}
+	if verdict != C.MI_VERIFY_OK {
+		return ErrRejected{Verdict: int(verdict)}
+	}
+	return nil
+}
+
+// VerifyBytes replaces groth16.Verify for a proof that arrives as Proof.WriteTo's bytes (164 + 32 * commitments): the points are
+// decompressed and the BSB22 hashes computed on the device.  No host hashing, no gnark-crypto decoding.
+func VerifyBytes(vk *VerifyingKey, proof []byte, publicWitness fr.Vector) error {
+	nc := len(vk.PublicAndCommitmentCommitted)
+	if len(publicWitness) != len(vk.G1.K)-nc-1 {
+		return errors.New("mi355x: wrong number of public inputs")
+	}
+	if len(proof) == 0 {
+		return errors.New("mi355x: empty proof")
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&proof[0])
+	var pub *C.mi_fr
+	if len(publicWitness) > 0 {
+		pin.Pin(&publicWitness[0])
+		pub = (*C.mi_fr)(unsafe.Pointer(&publicWitness[0]))
+	}
+	var verdict C.uint8_t
+	rc := C.mi_groth16_verify_bytes(vk.ctx, vk.dev, (*C.uint8_t)(unsafe.Pointer(&proof[0])), C.size_t(len(proof)), pub, &verdict)
+	if err := status(vk.ctx, rc); err != nil {
 		return err
 	}
 	if verdict != C.MI_VERIFY_OK {

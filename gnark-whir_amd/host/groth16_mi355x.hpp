@@ -21,6 +21,7 @@
 #include "../../include/mi355x_groth16_group.h"
 #include "../../include/mi355x_groth16_r1cs.h"
 #include "../../include/mi355x_groth16_verify.h"
+#include "../../include/mi355x_groth16_verify_bytes.h"
 #include "../../include/mi355x_groth16_debug.h"   // (this mirror is the TEST side: generators and knobs)
 
 namespace groth16 {
@@ -215,6 +216,12 @@ class VerifyingKey {
     VerifyingKey(const VerifyingKey &) = delete;
     VerifyingKey &operator=(const VerifyingKey &) = delete;
     mi_vk *get() const { return vk_; }
+    // gnark's PublicAndCommitmentCommitted, one list of 1-based indices per commitment: what VerifyBytes hashes beside each commitment
+    void SetPublicCommitted(const std::vector<std::vector<uint32_t>> &lists) {
+        std::vector<uint32_t> off{0}, idx;
+        for (const auto &l : lists) { idx.insert(idx.end(), l.begin(), l.end()); off.push_back((uint32_t)idx.size()); }
+        ctx_.check(mi_vk_set_public_committed(ctx_.get(), vk_, off.data(), idx.empty() ? nullptr : idx.data()));
+    }
 
   private:
     const Context &ctx_;
@@ -236,6 +243,27 @@ inline uint8_t Verify(const Context &ctx, const VerifyingKey &vk, const Proof &p
     uint8_t verdict = MI_VERIFY_MALFORMED;
     ctx.check(mi_groth16_verify(ctx.get(), vk.get(), &in, &verdict));
     return verdict;
+}
+// groth16.Verify from Proof.WriteTo's bytes (include/mi355x_groth16_verify_bytes.h): the points are decompressed and the BSB22 hashes
+// computed on the device.  Throws MI_EINVAL when bytes.size() is not 164 + 32 * the key's commitments; anything else is a verdict.
+inline uint8_t VerifyBytes(const Context &ctx, const VerifyingKey &vk, const std::vector<uint8_t> &bytes, const std::vector<mi_fr> &publicInputs) {
+    uint8_t verdict = MI_VERIFY_MALFORMED;
+    ctx.check(mi_groth16_verify_bytes(ctx.get(), vk.get(), bytes.data(), bytes.size(), publicInputs.empty() ? nullptr : publicInputs.data(), &verdict));
+    return verdict;
+}
+// The inverse of Proof::WriteTo (mi_proof_read): false when the bytes are not one well-formed proof with nCommitments commitments
+inline bool ReadProof(const std::vector<uint8_t> &bytes, uint32_t nCommitments, Proof &out) {
+    mi_proof_out p;
+    out.Commitments.resize(nCommitments);
+    if (mi_proof_read(bytes.data(), bytes.size(), nCommitments, &p, nCommitments ? out.Commitments.data() : nullptr, &out.CommitmentPok) != MI_OK) return false;
+    out.Ar = p.ar; out.Bs = p.bs; out.Krs = p.krs;
+    return true;
+}
+// fr.Hash(msg, dst, 1)[0] (mi_hash_to_field): the BSB22 commitment values and fold challenge are such hashes
+inline mi_fr HashToField(const std::string &dst, const std::vector<uint8_t> &msg) {
+    mi_fr out;
+    if (mi_hash_to_field((const uint8_t *)dst.data(), dst.size(), msg.data(), msg.size(), &out) != MI_OK) throw Error(MI_EINVAL, "HashToField: dst must have 1 .. 255 bytes");
+    return out;
 }
 // fft.Domain: FFT / FFTInverse with fft.DIF / fft.DIT and fft.OnCoset()
 enum Decimation { DIF = 0, DIT = 1 };

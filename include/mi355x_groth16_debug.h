@@ -60,6 +60,16 @@ int32_t mi_debug_lazy_op_dev(mi_ctx *ctx, int op, void *out_dev, const void *in_
 #define MI_FP12_WORDS 96
 int32_t mi_debug_pairing_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, const mi_g2_affine *q_dev, size_t n, mi_fp *gt_dev, uint32_t flags);
 int32_t mi_debug_fp12_op_dev(mi_ctx *ctx, int op, mi_fp *z_dev, const mi_fp *x_dev, const mi_fp *y_dev, size_t n);
+/* the decoders and the hash behind mi355x_groth16_verify_bytes.h (csrc/decode_ops.cuh, sha256_h2f.cuh), one record per lane; the host
+ * build of the tests (tests/emu/emu_decode.cpp) runs the same bodies.  All pointers are DEVICE pointers; the launches go to the context's
+ * stream (mi_dev_sync before reading).
+ * mi_debug_decode_g1_dev / _g2_dev: n compressed encodings of 32 / 64 bytes back to back -> n points and n bytes, 1 = malformed (the point
+ * is then (0, 0)).
+ * mi_debug_hash_to_field_dev: n messages of msg_len bytes back to back and ONE dst of dst_len bytes (1 .. 255) -> n Montgomery mi_fr.
+ * MI_EINVAL for null buffers, a dst_len out of range or n > 2^24. */
+int32_t mi_debug_decode_g1_dev(mi_ctx *ctx, const uint8_t *enc_dev, size_t n, mi_g1_affine *out_dev, uint8_t *bad_dev);
+int32_t mi_debug_decode_g2_dev(mi_ctx *ctx, const uint8_t *enc_dev, size_t n, mi_g2_affine *out_dev, uint8_t *bad_dev);
+int32_t mi_debug_hash_to_field_dev(mi_ctx *ctx, const uint8_t *dst_dev, uint32_t dst_len, const uint8_t *msgs_dev, size_t msg_len, size_t n, mi_fr *out_dev);
 /* random-gather throughput probe: n_threads lanes each chain `iters` dependent 64-byte gathers from a table of n_entries
  * (a power of two) 64-byte entries; scratch: 1 KiB.  The ceiling the level-1 bucket accumulation's point gathers run against. */
 int32_t mi_bench_gather_dev(mi_ctx *ctx, const void *table_dev, size_t n_entries, size_t n_threads, uint32_t iters,

@@ -13,8 +13,9 @@
  * Same library and conventions as mi355x_groth16.h / mi355x_groth16_setup.h: int32 status codes, Montgomery mi_fr / mi_fp, HOST
  * pointers, mi_last_error; the library keeps no caller pointer after return.  The workspace belongs to the context and only grows.
  *
- * THE LIBRARY STAYS HASH-FREE, as on the prover side: commitment_values[k] -- gnark's SHA-256 hash-to-field of commitment k (and of
- * the public committed values) -- and fold_challenge are computed by the caller and passed in.
+ * THESE ENTRY POINTS TAKE THE HASHES AS INPUTS: commitment_values[k] -- gnark's SHA-256 hash-to-field of commitment k (and of the
+ * public committed values) -- and fold_challenge are passed in.  mi355x_groth16_verify_bytes.h computes them (and decodes the proof's
+ * bytes) on the device and lands here; mi_hash_to_field of that header is the same hash on the host for a caller of this one.
  *
  * NOT PINNED TO gnark's SOURCE, like the Pedersen bases of mi_groth16_setup: the verifier is defined by the two equations above and by
  * mi_pedersen_vk_make below, which match the keys mi_groth16_setup makes.  Before relying on it against keys or proofs from gnark itself,

@@ -1,4 +1,5 @@
-"""Times groth16.Verify on the device (mi_groth16_verify[_batch], csrc/verify.hip).
+"""Times groth16.Verify on the device (mi_groth16_verify[_batch], csrc/verify.hip) and, beside each of its legs, the same proofs from
+their bytes (mi_groth16_verify_bytes[_batch], csrc/verify_bytes.hip): the difference of the two is the cost of decoding and hashing.
 
     python tools/verify_probe.py [--write profiles/verify.txt] [--batches 64,1024,16384] [--runs 5]
 
@@ -23,6 +24,8 @@ import cref  # noqa: E402
 import dlog_keys as D  # noqa: E402
 import setup_cases as S  # noqa: E402
 import r1cs_cases as RC  # noqa: E402
+import bytes_cases as BC  # noqa: E402
+from helpers import fr_arr, fr_vals, g1_pts  # noqa: E402
 from gpu_common import load_binding  # noqa: E402
 
 
@@ -44,12 +47,18 @@ def main():
     W[nab:] = D._op(2, a, b)
     td = S.synth_trapdoor(13, n_sigma=1)
     r, s = cref.gen_scalars(2, 14, 0)
-    ch = cref.gen_scalars(1, 15, 0)[0]
     pkh, peds, vk = ctx.setup(r1cs, td)
     vals = np.ascontiguousarray(W[r1cs["commitments"][0][0]])
     pool = B.Prover(0, 1)
     try:
         cm = pool.commit(peds[0], vals).reshape(1, 8)
+        # the bytes leg hashes: the commitment wire's value IS the hash of the commitment, the challenge the hash of that value
+        # (tests/bytes_cases.py states both in Python), written into W before the rest of the witness is solved
+        values, fold = BC.bsb22_hashes(g1_pts(cm), fr_vals(W[1:nb_public]))
+        W[r1cs["commitments"][0][1]] = fr_arr(values)[0]
+        ch = fr_arr([fold])[0]
+        a, b = RC.eval_rows(r1cs, "A", W), RC.eval_rows(r1cs, "B", W)
+        W[nab:] = D._op(2, a, b)
         proof, _ = pool.wait(pool.submit_bsb22(pkh, W, a, b, None, r, s, [(peds[0], vals)], ch))
     finally:
         pool.close()
@@ -58,6 +67,8 @@ def main():
            "pok": np.ascontiguousarray(proof["pok"]).reshape(8), "fold_challenge": ch,
            "commitment_values": np.ascontiguousarray(W[[r1cs["commitments"][0][1]]])}
     assert vkh.verify(inp) == B.VERIFY_OK
+    data = B.proof_write(inp["raw"], commitments=cm, pok=inp["pok"])
+    assert vkh.verify_bytes(data, inp["public_inputs"]) == B.VERIFY_OK
     lines = [f"groth16.Verify on the device: 1000 constraints (domain 2^10), {nb_public - 1} public inputs, 1 commitment (5 pairs per proof)",
              f"median wall time of {args.runs} calls after one warm-up call, host part included; no baseline exists, no rate is claimed"]
 
@@ -68,14 +79,22 @@ def main():
             t = time.perf_counter(); fn(); ts.append((time.perf_counter() - t) * 1e3)
         return statistics.median(ts)
 
-    lines.append(f"one verification      {timed(lambda: vkh.verify(inp)):10.3f} ms")
+    one, one_b = timed(lambda: vkh.verify(inp)), timed(lambda: vkh.verify_bytes(data, inp["public_inputs"]))
+    lines.append(f"one verification      {one:10.3f} ms   from bytes {one_b:10.3f} ms   decode + hash {one_b - one:9.3f} ms")
     for nb in [int(x) for x in args.batches.split(",") if x]:
         arr, keep = vkh._inputs([inp] * nb)
         out = np.zeros(nb, np.uint8)
         call = lambda: ctx._ck(ctx.lib.mi_groth16_verify_batch(ctx.h, vkh.h, arr, nb, out.ctypes.data_as(B.C.c_void_p)))
         ms = timed(call)
         assert not out.any()
-        lines.append(f"batch of {nb:6d}       {ms:10.3f} ms   {ms / nb:8.4f} ms per proof")
+        barr = (B.VerifyBytesInput * nb)()
+        buf = B.C.create_string_buffer(data, len(data)); pub = np.ascontiguousarray(inp["public_inputs"], np.uint64)
+        for i in range(nb):
+            barr[i].proof, barr[i].proof_len, barr[i].public_inputs = B.C.addressof(buf), len(data), pub.ctypes.data
+        bcall = lambda: ctx._ck(ctx.lib.mi_groth16_verify_bytes_batch(ctx.h, vkh.h, barr, B.C.c_size_t(nb), out.ctypes.data_as(B.C.c_void_p)))
+        bms = timed(bcall)
+        assert not out.any()
+        lines.append(f"batch of {nb:6d}       {ms:10.3f} ms   {ms / nb:8.4f} ms per proof   from bytes {bms:10.3f} ms   decode + hash {(bms - ms) / nb:8.4f} ms per proof")
     print("\n".join(lines))
     if args.write:
         with open(args.write, "w") as f:
