@@ -19,7 +19,7 @@ EXPORTS = [
     "mi_ntt", "mi_ntt_dev", "mi_compute_h", "mi_compute_h_dev", "mi_msm_g1", "mi_msm_g1_dev", "mi_msm_g2",
     "mi_msm_g2_dev", "mi_groth16_prove", "mi_groth16_prove_dev", "mi_get_stats", "mi_g1_compress",
     "mi_g2_compress", "mi_proof_write", "mi_g1_sum", "mi_g2_sum", "mi_gen_scalars_dev", "mi_gen_g1_dev",
-    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_debug_decode_g1_dev", "mi_debug_decode_g2_dev", "mi_debug_hash_to_field_dev", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
+    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_debug_decode_g1_dev", "mi_debug_decode_g2_dev", "mi_debug_hash_to_field_dev", "mi_debug_fp12_product_dev", "mi_debug_g1_scale128_dev", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
     "mi_dev_alloc", "mi_dev_free", "mi_dev_upload", "mi_dev_download", "mi_dev_sync",
     "mi_msm_precompute_g1_dev", "mi_msm_precompute_g2_dev", "mi_msm_g1_fixed_dev", "mi_msm_g2_fixed_dev", "mi_msm_table_to_rprime_g1_dev", "mi_msm_table_to_rprime_g2_dev", "mi_pk_table_plan",
     "mi_batch_scalar_mul_g1", "mi_batch_scalar_mul_g1_dev", "mi_batch_scalar_mul_g2", "mi_batch_scalar_mul_g2_dev",
@@ -51,6 +51,8 @@ VERIFY_OK, VERIFY_PAIRING, VERIFY_PEDERSEN, VERIFY_MALFORMED = 0, 1, 2, 3
 PAIRING_FINAL_EXP = 1
 # include/mi355x_groth16_verify_bytes.h (groth16.Verify from a proof's bytes: decode and hash on the device)
 VERIFY_BYTES_EXPORTS = ["mi_vk_set_public_committed", "mi_groth16_verify_bytes", "mi_groth16_verify_bytes_batch", "mi_proof_read", "mi_hash_to_field"]
+# include/mi355x_groth16_verify_combined.h (one verdict for a batch: the random linear combination of the proofs' equations)
+VERIFY_COMBINED_EXPORTS = ["mi_groth16_verify_combined", "mi_groth16_verify_bytes_combined"]
 
 
 class PkDesc(C.Structure):
@@ -619,6 +621,30 @@ class Context:
             for b in (dx, dy, dz):
                 if b: b.free()
 
+    def fp12_product(self, x):
+        """mi_debug_fp12_product_dev over a host array of (n, 48) uint64 records -> (48,): their product"""
+        x = _u64(x).reshape(-1, 48); n = x.shape[0]
+        dx = self.to_dev(x); do = self.alloc(384)
+        try:
+            self._ck(self.lib.mi_debug_fp12_product_dev(self.h, _p(dx.ptr), C.c_size_t(n), _p(do.ptr)))
+            self.sync()
+            return do.download((48,))
+        finally:
+            for b in (dx, do): b.free()
+
+    def g1_scale128(self, pts, ks):
+        """mi_debug_g1_scale128_dev: (n, 8) G1 points and n plain integers below 2^128 -> (n, 8): ks[i] * pts[i], affine"""
+        pts = _u64(pts).reshape(-1, 8); n = pts.shape[0]
+        assert len(ks) == n and n and all(0 <= int(k) < 1 << 128 for k in ks)
+        kk = np.array([[int(k) & (1 << 64) - 1, int(k) >> 64] for k in ks], np.uint64)
+        dp, dk = self.to_dev(pts), self.to_dev(kk); do = self.alloc(64 * n)
+        try:
+            self._ck(self.lib.mi_debug_g1_scale128_dev(self.h, _p(dp.ptr), _p(dk.ptr), C.c_size_t(n), _p(do.ptr)))
+            self.sync()
+            return do.download((n, 8))
+        finally:
+            for b in (dp, dk, do): b.free()
+
     def decode_points(self, enc: bytes, g2=False):
         """mi_debug_decode_g1_dev / _g2_dev over host bytes: n encodings of 32 (64) bytes -> ((n, 8) or (n, 16) uint64, (n,) uint8 malformed)"""
         w = 64 if g2 else 32
@@ -701,6 +727,22 @@ class VerifyingKey:
         self.ctx._ck(self.ctx.lib.mi_groth16_verify_batch(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), _p(out)))
         return out
 
+    # ---- one verdict for the batch (include/mi355x_groth16_verify_combined.h)
+    def verify_combined(self, proofs, seed=None):
+        """mi_groth16_verify_combined: proofs as verify_batch takes them, seed = 32 bytes or None (the library draws it from the
+        operating system) -> (verdict, first_malformed)"""
+        assert seed is None or len(seed) == 32
+        arr, keep = self._inputs(list(proofs)); v = C.c_uint8(255); first = C.c_uint64(1 << 63)
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_combined(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), seed, C.byref(v), C.byref(first)))
+        return int(v.value), int(first.value)
+
+    def verify_bytes_combined(self, proofs, seed=None):
+        """mi_groth16_verify_bytes_combined: proofs as verify_bytes_batch takes them -> (verdict, first_malformed)"""
+        assert seed is None or len(seed) == 32
+        arr, keep = self._bytes_inputs(proofs); v = C.c_uint8(255); first = C.c_uint64(1 << 63)
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_bytes_combined(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), seed, C.byref(v), C.byref(first)))
+        return int(v.value), int(first.value)
+
     # ---- from a proof's bytes (include/mi355x_groth16_verify_bytes.h)
     def set_public_committed(self, lists):
         """mi_vk_set_public_committed: gnark's PublicAndCommitmentCommitted, one list of 1-based indices per commitment"""
@@ -716,15 +758,19 @@ class VerifyingKey:
 
     def verify_bytes_batch(self, proofs):
         """proofs: [(bytes, public_inputs (nb_public - 1, 4) or None)]"""
+        arr, keep = self._bytes_inputs(proofs)
+        out = np.full(len(arr), 255, np.uint8)
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_bytes_batch(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), _p(out)))
+        return out
+
+    def _bytes_inputs(self, proofs):
         proofs = list(proofs); arr = (VerifyBytesInput * len(proofs))(); keep = []
         for i, (b, pub) in enumerate(proofs):
             buf = C.create_string_buffer(b, len(b)); keep.append(buf)
             arr[i].proof, arr[i].proof_len = C.addressof(buf), len(b)
             if pub is not None:
                 pub = _u64(pub); keep.append(pub); arr[i].public_inputs = pub.ctypes.data
-        out = np.full(len(proofs), 255, np.uint8)
-        self.ctx._ck(self.ctx.lib.mi_groth16_verify_bytes_batch(self.ctx.h, self.h, arr, C.c_size_t(len(proofs)), _p(out)))
-        return out
+        return arr, keep
 
     def free(self):
         if self.h:

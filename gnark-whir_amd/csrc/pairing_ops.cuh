@@ -129,3 +129,71 @@ MI_OOL uint8_t verify_judge(const Fp12 *ml, u32 n_ped, const Fp12 *e_alpha_beta,
     }
     return malformed ? 3 : verdict;
 }
+
+// ---------------------------------------------------------------- one verdict for a batch (include/mi355x_groth16_verify_combined.h;
+// csrc/verify_combined.hip and tests/emu/emu_verify_combined.cpp both run this text).  With coefficients r_i < 2^128 and S = sum r_i:
+//     prod_i e(r_i Ar_i, Bs_i) e(-S alpha, beta) e(-(S K[0] + sum_j (sum_i r_i s_ij) K[1 + j] + sum_i r_i sum_k C_ik), gamma)
+//            e(-sum_i r_i Krs_i, delta) = 1                                                                      else 1
+//     e(sum_i r_i pok_i, G) prod_k e(sum_i (r_i c_i^k) C_ik, GSigmaNeg_k) = 1                                    else 2
+// The n pairs (r_i Ar_i, Bs_i) come first, then the tail in the order of the single proof's pairs:
+//     n: (-S alpha, beta)   n + 1: (-kSum, gamma)   n + 2: (-sum r_i Krs_i, delta)   then, with commitments:   n + 3: (sum r_i pok_i, G)
+//     n + 4 + k: (sum_i r_i c_i^k C_ik, GSigmaNeg_k)
+
+// a coefficient: four little-endian words of a plain integer below 2^128 -> the Montgomery scalar
+MI_HD Fr fr_from_u128(const u32 k[4]) {
+    Fr x = Fr::zero();
+    for (int i = 0; i < 4; i++) x.l[i] = k[i];
+    return fe_to_mont(x);
+}
+// k p for a plain integer k < 2^128: double-and-add (mixed additions of p) from the top bit in XYZZ, one inversion on the way back to affine.  (0, 0) = infinity
+// in and out; k = 0 gives infinity.
+MI_OOL G1Aff g1_scale128(const G1Aff &p, const u32 k[4]) {
+    G1X acc = G1X::inf();
+    for (int i = 127; i >= 0; i--) {
+        acc = xyzz_dbl(acc);
+        if ((k[i >> 5] >> (i & 31)) & 1) xyzz_madd(acc, p, false);
+    }
+    return xyzz_to_affine(acc);   // p = infinity: every mixed addition left acc at infinity
+}
+// x[0] x[1] ... x[cnt - 1] from the left, cnt >= 1.  Fp elements are fully reduced, so any grouping gives the same words.
+MI_OOL void fp12_product_run(Fp12 *z, const Fp12 *x, size_t cnt) {
+    Fp12 f = x[0];
+    for (size_t i = 1; i < cnt; i++) {
+        const Fp12 y = x[i];
+        fp12_mul(&f, &f, &y);
+    }
+    *z = f;
+}
+#define MI_FP12_PRODUCT_FAN_IN 8   // values one lane of k_fp12_product multiplies; a level of m values leaves ceil(m / 8)
+
+// What the MSMs of a batch give (affine, (0, 0) = infinity) and the sum of the coefficients
+struct VerifyCombinedSums {
+    Fr s;                   // S = sum r_i, Montgomery
+    G1Aff k;                // sum_j (sum_i r_i s_ij) K[1 + j]
+    G1Aff krs;              // sum_i r_i Krs_i
+    G1Aff c;                // sum_i r_i sum_k C_ik
+    G1Aff pok;              // sum_i r_i pok_i
+    const G1Aff *ck;        // n_commitments points: sum_i (r_i c_i^k) C_ik
+};
+MI_HD u32 verify_combined_tail_pairs(u32 n_commitments) { return verify_pairs_per_proof(n_commitments); }
+// The tail pairs, p[] and q[] of verify_combined_tail_pairs entries.  S K[0] and S alpha are single scalar multiplications.
+inline void verify_combined_assemble(const VerifyKeyRef &vk, const G1Aff &alpha1, const G2Aff &beta2, const VerifyCombinedSums &m, G1Aff *p, G2Aff *q) {
+    const u32 nc = vk.n_commitments;
+    const Fr s = fe_from_mont(m.s);
+    G1X acc = xyzz_mul_256(G1X::from_affine(*vk.k0), s.l);
+    xyzz_madd(acc, m.k, false);
+    xyzz_madd(acc, m.c, false);
+    p[0] = g1_aff_neg(xyzz_to_affine(xyzz_mul_256(G1X::from_affine(alpha1), s.l)));   q[0] = beta2;
+    p[1] = g1_aff_neg(xyzz_to_affine(acc));                                           q[1] = *vk.gamma2;
+    p[2] = g1_aff_neg(m.krs);                                                         q[2] = *vk.delta2;
+    if (nc) {
+        p[3] = m.pok;                                                                 q[3] = vk.ped[0];
+        for (u32 k = 0; k < nc; k++) { p[4 + k] = m.ck[k]; q[4 + k] = vk.ped[2 * k + 1]; }
+    }
+}
+// The verdict from the two products after their final exponentiations (ped = null without commitments): 1, 2 or 0
+MI_HD uint8_t verify_combined_judge(const Fp12 *groth, const Fp12 *ped) {
+    if (!(*groth == Fp12::one())) return 1;
+    if (ped && !(*ped == Fp12::one())) return 2;
+    return 0;
+}

@@ -11,6 +11,8 @@
 //   k_verify_judge      one lane per proof: the products of its Miller values, the final exponentiations, the comparisons -> a verdict byte
 // Everything of a batch lives in ONE grow-only workspace (WS_VERIFY): nothing is allocated in steady state.
 // mi_verify_run is that batch; verify_bytes.hip calls it too, with the proofs it decoded (verify_internal.h holds mi_vk for both).
+// verify_combined.hip judges a batch with ONE verdict instead and reuses k_verify_g2_check, k_pairing_miller and k_pairing_final_exp
+// through mi_verify_g2_check_enqueue / mi_pairing_enqueue.
 #include "verify_internal.h"
 #include <cstring>
 #include <string>
@@ -63,18 +65,25 @@ G2Aff g2_of(const mi_g2_affine &p) { G2Aff a; std::memcpy(&a, &p, sizeof(a)); re
 static_assert(sizeof(mi_pedersen_vk) == 2 * sizeof(G2Aff) && sizeof(mi_g1_affine) == sizeof(G1Aff) && sizeof(mi_fr) == sizeof(Fr),
               "pairing_ops.cuh reads the header's records as G1Aff / G2Aff / Fr");
 
-// Miller values of n pairs already on the device, then (final) f^d' in place
-int32_t pairing_enqueue(mi_ctx *ctx, const G1Aff *p_dev, const G2Aff *q_dev, size_t n, Fp12 *gt_dev, bool final_exp) {
-    hipLaunchKernelGGL(k_pairing_miller, dim3(grid64(n)), dim3(64), 0, ctx->stream, p_dev, q_dev, gt_dev, n);
+}   // namespace
+
+int32_t mi_final_exp_enqueue(mi_ctx *ctx, Fp12 *io_dev, size_t n) {
+    hipLaunchKernelGGL(k_pairing_final_exp, dim3(grid64(n)), dim3(64), 0, ctx->stream, io_dev, n);
     MI_CHECK_HIP(ctx, hipGetLastError());
-    if (final_exp) {
-        hipLaunchKernelGGL(k_pairing_final_exp, dim3(grid64(n)), dim3(64), 0, ctx->stream, gt_dev, n);
-        MI_CHECK_HIP(ctx, hipGetLastError());
-    }
     return MI_OK;
 }
-
-}   // namespace
+// Miller values of n pairs already on the device, then (final) f^d' in place
+int32_t mi_pairing_enqueue(mi_ctx *ctx, const G1Aff *p_dev, const G2Aff *q_dev, size_t n, Fp12 *gt_dev, bool final_exp) {
+    hipLaunchKernelGGL(k_pairing_miller, dim3(grid64(n)), dim3(64), 0, ctx->stream, p_dev, q_dev, gt_dev, n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    if (final_exp) MI_TRY(mi_final_exp_enqueue(ctx, gt_dev, n));
+    return MI_OK;
+}
+int32_t mi_verify_g2_check_enqueue(mi_ctx *ctx, const G2Aff *q_dev, u32 stride, uint8_t *flags_dev, size_t n) {
+    hipLaunchKernelGGL(k_verify_g2_check, dim3(grid64(n)), dim3(64), 0, ctx->stream, q_dev, stride, flags_dev, n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
 
 int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts, const uint8_t *decode_malformed) {
     if (!ctx) return MI_EINVAL;
@@ -129,9 +138,8 @@ int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, s
     MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_p, P.data(), P.size() * sizeof(G1Aff), hipMemcpyHostToDevice, ctx->stream));
     MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_q, Q.data(), Q.size() * sizeof(G2Aff), hipMemcpyHostToDevice, ctx->stream));
     MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_verify_g2_check, dim3(grid64(n)), dim3(64), 0, ctx->stream, (const G2Aff *)(ws + off_q), np, (uint8_t *)(ws + off_fl), n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    MI_TRY(pairing_enqueue(ctx, (const G1Aff *)(ws + off_p), (const G2Aff *)(ws + off_q), n * np, (Fp12 *)(ws + off_ml), false));
+    MI_TRY(mi_verify_g2_check_enqueue(ctx, (const G2Aff *)(ws + off_q), np, (uint8_t *)(ws + off_fl), n));
+    MI_TRY(mi_pairing_enqueue(ctx, (const G1Aff *)(ws + off_p), (const G2Aff *)(ws + off_q), n * np, (Fp12 *)(ws + off_ml), false));
     hipLaunchKernelGGL(k_verify_judge, dim3(grid64(n)), dim3(64), 0, ctx->stream, (const Fp12 *)(ws + off_ml), np, vk->e_alpha_beta_dev,
                        (const uint8_t *)(ws + off_fl), (uint8_t *)(ws + off_vd), n);
     MI_CHECK_HIP(ctx, hipGetLastError());
@@ -194,7 +202,7 @@ int32_t mi_vk_load(mi_ctx *ctx, const mi_vk_desc *d, mi_vk **out) {
         char *ws = (char *)ctx->ws[WS_VERIFY].p;
         MI_CHECK_HIP(ctx, hipMemcpyAsync(ws, &alpha, sizeof(alpha), hipMemcpyHostToDevice, ctx->stream));
         MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + 256, &beta, sizeof(beta), hipMemcpyHostToDevice, ctx->stream));
-        MI_TRY(pairing_enqueue(ctx, (const G1Aff *)ws, (const G2Aff *)(ws + 256), 1, vk->e_alpha_beta_dev, true));
+        MI_TRY(mi_pairing_enqueue(ctx, (const G1Aff *)ws, (const G2Aff *)(ws + 256), 1, vk->e_alpha_beta_dev, true));
         MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return MI_OK;
     };
@@ -251,7 +259,7 @@ int32_t mi_groth16_verify_batch(mi_ctx *ctx, const mi_vk *vk, const mi_verify_in
 int32_t mi_debug_pairing_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, const mi_g2_affine *q_dev, size_t n, mi_fp *gt_dev, uint32_t flags) {
     if (!ctx || (flags & ~MI_PAIRING_FINAL_EXP) || ((!p_dev || !q_dev || !gt_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
     if (!n) return MI_OK;
-    return pairing_enqueue(ctx, (const G1Aff *)p_dev, (const G2Aff *)q_dev, n, (Fp12 *)gt_dev, (flags & MI_PAIRING_FINAL_EXP) != 0);
+    return mi_pairing_enqueue(ctx, (const G1Aff *)p_dev, (const G2Aff *)q_dev, n, (Fp12 *)gt_dev, (flags & MI_PAIRING_FINAL_EXP) != 0);
 }
 int32_t mi_debug_fp12_op_dev(mi_ctx *ctx, int op, mi_fp *z_dev, const mi_fp *x_dev, const mi_fp *y_dev, size_t n) {
     if (!ctx || op < 0 || op >= F12_OP_END || ((!z_dev || !x_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;

@@ -8,7 +8,8 @@
 //   k_verify_hash  one lane per proof: commitment_values and fold_challenge from the decoded commitments, the public inputs and the
 //                  key's committed lists (sha256_h2f.cuh); a proof that did not decode is skipped
 //   host      the decoded records come back and go through mi_verify_run, the body of mi_groth16_verify_batch, which assembles on the
-//             host as it always did; a proof that did not decode enters it as malformed and none of its words is read
+//             host as it always did; a proof that did not decode enters it as malformed and none of its words is read.
+//             mi_groth16_verify_bytes_combined enters mi_verify_combined_run (verify_combined.hip) with the same records and flags
 // Two decode kernels rather than one: a G2 lane does four times the work of a G1 lane, and in one wave the G1 lanes would wait for it.
 // Everything of a batch lives in ONE grow-only workspace (WS_VERIFY_BYTES): nothing is allocated in steady state.
 #include "verify_internal.h"
@@ -67,9 +68,12 @@ __global__ void __launch_bounds__(64, 1) k_hash_to_field(const uint8_t *msgs, si
     out[i] = hash_to_field(d, dst_len, msgs + i * msg_len, msg_len);
 }
 
-int32_t verify_bytes_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, uint8_t *verdicts) {
+// combined = null: verdicts[n], every proof on its own.  Otherwise ONE verdict by the combined check (verify_combined.hip) under
+// combined->seed, and *combined->first_malformed.
+struct CombinedArgs { const uint8_t *seed; uint64_t *first_malformed; };
+int32_t verify_bytes_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, uint8_t *verdicts, const CombinedArgs *combined = nullptr) {
     if (!ctx) return MI_EINVAL;
-    if (!vk || (!in && n) || (!verdicts && n)) MI_FAIL(ctx, MI_EINVAL, "verify bytes: null vk, input or verdict pointer");
+    if (!vk || (!in && n) || (!verdicts && (n || combined))) MI_FAIL(ctx, MI_EINVAL, "verify bytes: null vk, input or verdict pointer");
     if (n > ((size_t)1 << 24)) MI_FAIL(ctx, MI_EINVAL, "verify bytes: more than 2^24 proofs in one batch");
     const u32 nc = vk->n_commitments, n_pub = vk->nb_public - 1, slots = proof_g1_slots(nc);
     const size_t plen = proof_bytes_len(nc);
@@ -79,7 +83,7 @@ int32_t verify_bytes_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_inp
             MI_FAIL(ctx, MI_EINVAL, "verify bytes: proof_len is " + std::to_string(in[i].proof_len) + ", the key's proofs have " + std::to_string(plen) + " bytes");
         if (n_pub && !in[i].public_inputs) MI_FAIL(ctx, MI_EINVAL, "verify bytes: public_inputs is null");
     }
-    if (!n) return MI_OK;
+    if (!n) return combined ? mi_verify_combined_run(ctx, vk, nullptr, 0, combined->seed, verdicts, combined->first_malformed, nullptr) : MI_OK;
     // ---- workspace: bytes | public inputs | committed offsets | committed indices | G1 | G2 | bad G1 | bad G2 | bad | values | folds
     const size_t n_idx = vk->pc_idx.size();
     const size_t off_pub = up256(n * plen), off_po = off_pub + up256(n * n_pub * sizeof(Fr)), off_pi = off_po + up256((nc + 1) * sizeof(u32));
@@ -132,6 +136,7 @@ int32_t verify_bytes_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_inp
         dec[i].commitment_values = nc ? (const mi_fr *)&values[i * nc] : nullptr;
         dec[i].fold_challenge = (const mi_fr *)&folds[i];
     }
+    if (combined) return mi_verify_combined_run(ctx, vk, dec.data(), n, combined->seed, verdicts, combined->first_malformed, bad.data());
     return mi_verify_run(ctx, vk, dec.data(), n, verdicts, bad.data());
 }
 
@@ -164,6 +169,12 @@ int32_t mi_groth16_verify_bytes(mi_ctx *ctx, const mi_vk *vk, const uint8_t *pro
 }
 int32_t mi_groth16_verify_bytes_batch(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, uint8_t *verdicts) {
     return verify_bytes_run(ctx, vk, in, n, verdicts);
+}
+
+int32_t mi_groth16_verify_bytes_combined(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, const uint8_t *seed, uint8_t *verdict,
+                                         uint64_t *first_malformed) {
+    const CombinedArgs combined{seed, first_malformed};
+    return verify_bytes_run(ctx, vk, in, n, verdict, &combined);
 }
 
 // ---------------------------------------------------------------- debug surface (include/mi355x_groth16_debug.h)

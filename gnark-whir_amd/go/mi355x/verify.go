@@ -5,12 +5,14 @@
 // STATUS: SOURCE ONLY, like the rest of the shim (mi355x.go): never compiled here.  Verify computes what gnark's verify.go computes on
 // the host -- the hash-to-field of every commitment (with the public committed values) and the fold challenge -- and hands the rest to
 // mi_groth16_verify.  VerifyBytes takes Proof.WriteTo's bytes and leaves decoding and hashing to the device (mi_groth16_verify_bytes).
+// VerifyBytesCombined judges a whole batch of such proofs with ONE verdict (mi_groth16_verify_bytes_combined).
 package mi355x
 
 /*
 #include <stdlib.h>
 #include "mi355x_groth16_verify.h"
 #include "mi355x_groth16_verify_bytes.h"
+#include "mi355x_groth16_verify_combined.h"
 */
 import "C"
 
@@ -204,6 +206,60 @@ func VerifyBytes(vk *VerifyingKey, proof []byte, publicWitness fr.Vector) error 
 	}
 	if verdict != C.MI_VERIFY_OK {
 		return ErrRejected{Verdict: int(verdict)}
+	}
+	return nil
+}
+
+// ErrBatchRejected carries the ONE verdict of a rejected batch.  FirstMalformed is the lowest malformed index when Verdict is
+// MI_VERIFY_MALFORMED; verdicts MI_VERIFY_PAIRING and MI_VERIFY_PEDERSEN do not say which proof is at fault (VerifyBytes on each does).
+type ErrBatchRejected struct {
+	Verdict        int
+	FirstMalformed uint64
+}
+
+func (e ErrBatchRejected) Error() string {
+	return fmt.Sprintf("mi355x: batch rejected (verdict %d, first malformed %d)", e.Verdict, e.FirstMalformed)
+}
+
+// VerifyBytesCombined judges n proofs under one key by one pairing product: the random linear combination of their equations
+// (include/mi355x_groth16_verify_combined.h).  The library draws the seed of the coefficients from the operating system, so a batch
+// with a rejected proof passes with probability about 2^-128; a batch of accepted proofs always passes.  proofs[i] is Proof.WriteTo's
+// bytes, publicWitnesses[i] its public inputs without the ONE wire.
+func VerifyBytesCombined(vk *VerifyingKey, proofs [][]byte, publicWitnesses []fr.Vector) error {
+	if len(proofs) != len(publicWitnesses) {
+		return errors.New("mi355x: one public witness per proof")
+	}
+	if len(proofs) == 0 {
+		return nil
+	}
+	nc := len(vk.PublicAndCommitmentCommitted)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	in := (*[1 << 24]C.mi_verify_bytes_input)(C.calloc(C.size_t(len(proofs)), C.size_t(unsafe.Sizeof(C.mi_verify_bytes_input{}))))
+	defer C.free(unsafe.Pointer(in))
+	for i, p := range proofs {
+		if len(publicWitnesses[i]) != len(vk.G1.K)-nc-1 {
+			return errors.New("mi355x: wrong number of public inputs")
+		}
+		if len(p) == 0 {
+			return errors.New("mi355x: empty proof")
+		}
+		pin.Pin(&p[0])
+		in[i].proof = (*C.uint8_t)(unsafe.Pointer(&p[0]))
+		in[i].proof_len = C.size_t(len(p))
+		if len(publicWitnesses[i]) > 0 {
+			pin.Pin(&publicWitnesses[i][0])
+			in[i].public_inputs = (*C.mi_fr)(unsafe.Pointer(&publicWitnesses[i][0]))
+		}
+	}
+	var verdict C.uint8_t
+	var first C.uint64_t
+	rc := C.mi_groth16_verify_bytes_combined(vk.ctx, vk.dev, &in[0], C.size_t(len(proofs)), nil, &verdict, &first)
+	if err := status(vk.ctx, rc); err != nil {
+		return err
+	}
+	if verdict != C.MI_VERIFY_OK {
+		return ErrBatchRejected{Verdict: int(verdict), FirstMalformed: uint64(first)}
 	}
 	return nil
 }

@@ -22,6 +22,7 @@
 #include "../../include/mi355x_groth16_r1cs.h"
 #include "../../include/mi355x_groth16_verify.h"
 #include "../../include/mi355x_groth16_verify_bytes.h"
+#include "../../include/mi355x_groth16_verify_combined.h"
 #include "../../include/mi355x_groth16_debug.h"   // (this mirror is the TEST side: generators and knobs)
 
 namespace groth16 {
@@ -249,6 +250,31 @@ inline uint8_t Verify(const Context &ctx, const VerifyingKey &vk, const Proof &p
 inline uint8_t VerifyBytes(const Context &ctx, const VerifyingKey &vk, const std::vector<uint8_t> &bytes, const std::vector<mi_fr> &publicInputs) {
     uint8_t verdict = MI_VERIFY_MALFORMED;
     ctx.check(mi_groth16_verify_bytes(ctx.get(), vk.get(), bytes.data(), bytes.size(), publicInputs.empty() ? nullptr : publicInputs.data(), &verdict));
+    return verdict;
+}
+// ONE verdict for a batch of proofs under one key (include/mi355x_groth16_verify_combined.h): the random linear combination of their
+// equations -- n + 3 (+ commitments + 1) Miller loops, two final exponentiations and a constant number of MSMs for the whole batch.
+// seed = nullptr: the library draws it from the operating system, which is what judging proofs from someone else requires (a seed the
+// maker of the proofs can predict voids the soundness claim).  firstMalformed (may be null) = the lowest malformed index with
+// MI_VERIFY_MALFORMED, n otherwise.  Verdicts 1 and 2 do not say which proof is at fault.
+struct BatchProof {
+    std::vector<uint8_t> bytes;          // Proof::WriteTo
+    std::vector<mi_fr> publicInputs;     // without the ONE wire
+};
+inline uint8_t VerifyBytesCombined(const Context &ctx, const VerifyingKey &vk, const std::vector<BatchProof> &proofs, const uint8_t *seed = nullptr,
+                                   uint64_t *firstMalformed = nullptr) {
+    std::vector<mi_verify_bytes_input> in(proofs.size());
+    for (size_t i = 0; i < proofs.size(); i++)
+        in[i] = mi_verify_bytes_input{proofs[i].bytes.data(), proofs[i].bytes.size(), proofs[i].publicInputs.empty() ? nullptr : proofs[i].publicInputs.data()};
+    uint8_t verdict = MI_VERIFY_MALFORMED;
+    ctx.check(mi_groth16_verify_bytes_combined(ctx.get(), vk.get(), in.data(), in.size(), seed, &verdict, firstMalformed));
+    return verdict;
+}
+// the same over proofs already taken apart (mi_verify_input: the caller computed the BSB22 hashes)
+inline uint8_t VerifyCombined(const Context &ctx, const VerifyingKey &vk, const std::vector<mi_verify_input> &in, const uint8_t *seed = nullptr,
+                              uint64_t *firstMalformed = nullptr) {
+    uint8_t verdict = MI_VERIFY_MALFORMED;
+    ctx.check(mi_groth16_verify_combined(ctx.get(), vk.get(), in.data(), in.size(), seed, &verdict, firstMalformed));
     return verdict;
 }
 // The inverse of Proof::WriteTo (mi_proof_read): false when the bytes are not one well-formed proof with nCommitments commitments

@@ -70,6 +70,15 @@ int32_t mi_debug_fp12_op_dev(mi_ctx *ctx, int op, mi_fp *z_dev, const mi_fp *x_d
 int32_t mi_debug_decode_g1_dev(mi_ctx *ctx, const uint8_t *enc_dev, size_t n, mi_g1_affine *out_dev, uint8_t *bad_dev);
 int32_t mi_debug_decode_g2_dev(mi_ctx *ctx, const uint8_t *enc_dev, size_t n, mi_g2_affine *out_dev, uint8_t *bad_dev);
 int32_t mi_debug_hash_to_field_dev(mi_ctx *ctx, const uint8_t *dst_dev, uint32_t dst_len, const uint8_t *msgs_dev, size_t msg_len, size_t n, mi_fr *out_dev);
+
+/* the two kernels mi355x_groth16_verify_combined.h adds in front of and behind the Miller loops (csrc/verify_combined.hip), alone; the
+ * host build of the tests (tests/emu/emu_verify_combined.cpp) runs the same bodies.  Device pointers, enqueued on the context's stream.
+ * mi_debug_fp12_product_dev: out_dev[0] = x_dev[0] x_dev[1] ... x_dev[n - 1], Fp12 records of 12 x mi_fp, by the verifier's tree (fan-in
+ * 8, one launch per level; its scratch is the context's verifier workspace).  1 <= n <= 2^24 + 3, the most the verifier multiplies.
+ * mi_debug_g1_scale128_dev: out_dev[i] = k_i p_dev[i], affine, k_i = k_dev[2 i] + 2^64 k_dev[2 i + 1] (a plain integer below 2^128);
+ * (0, 0) = infinity in and out.  out_dev may be p_dev.  The points must lie on the curve. */
+int32_t mi_debug_fp12_product_dev(mi_ctx *ctx, const mi_fp *x_dev, size_t n, mi_fp *out_dev);
+int32_t mi_debug_g1_scale128_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, const uint64_t *k_dev, size_t n, mi_g1_affine *out_dev);
 /* random-gather throughput probe: n_threads lanes each chain `iters` dependent 64-byte gathers from a table of n_entries
  * (a power of two) 64-byte entries; scratch: 1 KiB.  The ceiling the level-1 bucket accumulation's point gathers run against. */
 int32_t mi_bench_gather_dev(mi_ctx *ctx, const void *table_dev, size_t n_entries, size_t n_threads, uint32_t iters,

@@ -86,8 +86,9 @@ typedef struct mi_verify_input {
                                    curve; Bs off the twist or outside its r-torsion */
 
 /* Both return MI_OK whenever a verdict was reached: a rejected proof is a verdict, not an error.  MI_EINVAL (null pointers, a missing
- * array the key's counts call for) is decided on the host before any device work.  A batch judges every proof on its own -- no random
- * linear combination: verdicts[i] is exactly what mi_groth16_verify says for in[i]. */
+ * array the key's counts call for) is decided on the host before any device work.  A batch judges every proof on its own: verdicts[i] is exactly
+ * what mi_groth16_verify says for in[i].  (ONE verdict for a whole batch, by a random linear combination of the proofs' equations and at
+ * a fraction of the cost: mi355x_groth16_verify_combined.h.) */
 int32_t mi_groth16_verify(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, uint8_t *verdict);
 int32_t mi_groth16_verify_batch(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts);
 

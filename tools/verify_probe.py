@@ -1,5 +1,7 @@
 """Times groth16.Verify on the device (mi_groth16_verify[_batch], csrc/verify.hip) and, beside each of its legs, the same proofs from
 their bytes (mi_groth16_verify_bytes[_batch], csrc/verify_bytes.hip): the difference of the two is the cost of decoding and hashing.
+Beside each batch leg, the same inputs through mi_groth16_verify_combined (csrc/verify_combined.hip: one verdict for the batch, under a
+fixed seed), in the same process: the two calls ALTERNATE, one pair per run, and each gets its median and its min .. max.
 
     python tools/verify_probe.py [--write profiles/verify.txt] [--batches 64,1024,16384] [--runs 5]
 
@@ -34,6 +36,7 @@ def main():
     ap.add_argument("--write")
     ap.add_argument("--batches", default="64,1024,16384")
     ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--combined-only", action="store_true", help="the batch legs time the combined call alone: for a kernel trace of it")
     args = ap.parse_args()
     B = load_binding()
     ctx = B.Context(0)
@@ -72,6 +75,12 @@ def main():
     lines = [f"groth16.Verify on the device: 1000 constraints (domain 2^10), {nb_public - 1} public inputs, 1 commitment (5 pairs per proof)",
              f"median wall time of {args.runs} calls after one warm-up call, host part included; no baseline exists, no rate is claimed"]
 
+    print("\n".join(lines), flush=True)
+
+    def emit(line):     # as it is measured: a long leg is not silent
+        lines.append(line)
+        print(line, flush=True)
+
     def timed(fn):
         fn()
         ts = []
@@ -79,14 +88,28 @@ def main():
             t = time.perf_counter(); fn(); ts.append((time.perf_counter() - t) * 1e3)
         return statistics.median(ts)
 
+    def timed_pair(fa, fb):
+        """one warm-up call of each, then `runs` pairs (a, b), alternating -> [median, min, max] of each, ms"""
+        fa(); fb()
+        ta, tb = [], []
+        for _ in range(args.runs):
+            for fn, ts in ((fa, ta), (fb, tb)):
+                t = time.perf_counter(); fn(); ts.append((time.perf_counter() - t) * 1e3)
+        return [(statistics.median(ts), min(ts), max(ts)) for ts in (ta, tb)]
+
     one, one_b = timed(lambda: vkh.verify(inp)), timed(lambda: vkh.verify_bytes(data, inp["public_inputs"]))
-    lines.append(f"one verification      {one:10.3f} ms   from bytes {one_b:10.3f} ms   decode + hash {one_b - one:9.3f} ms")
+    emit(f"one verification      {one:10.3f} ms   from bytes {one_b:10.3f} ms   decode + hash {one_b - one:9.3f} ms")
     for nb in [int(x) for x in args.batches.split(",") if x]:
         arr, keep = vkh._inputs([inp] * nb)
         out = np.zeros(nb, np.uint8)
         call = lambda: ctx._ck(ctx.lib.mi_groth16_verify_batch(ctx.h, vkh.h, arr, nb, out.ctypes.data_as(B.C.c_void_p)))
-        ms = timed(call)
-        assert not out.any()
+        seed = bytes(range(32)); one_v = B.C.c_uint8(255); first = B.C.c_uint64(0)
+        ccall = lambda: ctx._ck(ctx.lib.mi_groth16_verify_combined(ctx.h, vkh.h, arr, B.C.c_size_t(nb), seed, B.C.byref(one_v), B.C.byref(first)))
+        if args.combined_only:
+            emit(f"batch of {nb:6d}       combined alone {timed(ccall):10.3f} ms")
+            continue
+        (ms, lo, hi), (cms, clo, chi) = timed_pair(call, ccall)
+        assert not out.any() and (one_v.value, first.value) == (B.VERIFY_OK, nb)
         barr = (B.VerifyBytesInput * nb)()
         buf = B.C.create_string_buffer(data, len(data)); pub = np.ascontiguousarray(inp["public_inputs"], np.uint64)
         for i in range(nb):
@@ -94,8 +117,9 @@ def main():
         bcall = lambda: ctx._ck(ctx.lib.mi_groth16_verify_bytes_batch(ctx.h, vkh.h, barr, B.C.c_size_t(nb), out.ctypes.data_as(B.C.c_void_p)))
         bms = timed(bcall)
         assert not out.any()
-        lines.append(f"batch of {nb:6d}       {ms:10.3f} ms   {ms / nb:8.4f} ms per proof   from bytes {bms:10.3f} ms   decode + hash {(bms - ms) / nb:8.4f} ms per proof")
-    print("\n".join(lines))
+        emit(f"batch of {nb:6d}       {ms:10.3f} ms   {ms / nb:8.4f} ms per proof   from bytes {bms:10.3f} ms   decode + hash {(bms - ms) / nb:8.4f} ms per proof")
+        emit(f"  alternating pairs   per proof {ms:10.3f} ms ({lo:.3f} .. {hi:.3f})   combined {cms:10.3f} ms ({clo:.3f} .. {chi:.3f})   "
+                     f"{cms / nb:8.4f} ms per proof   per proof / combined {ms / cms:7.1f}")
     if args.write:
         with open(args.write, "w") as f:
             f.write("\n".join(lines) + "\n")
