@@ -1222,46 +1222,31 @@ static int32_t pk_load_sharded_impl(mi_group *g, const mi_pk_desc *descs, bool d
     //  leaves a zeroed bucket array of the agreed shape, msm.hip mi_msm_enqueue)
     const uint32_t share = lead_share_of(g);
     spk->lead_share = share;
-    u64 max_w = 0, max_b = 0, max_z = 0;
+    u64 largest[3] = {0, 0, 0};   // pairs of A+K, B, Z
     for (int r = 0; r < W; r++) {
         u64 lo, hi, zlo, zhi, nb = 0;
         wire_range_of(d->nb_wires, W, r, share, lo, hi); range_of(N - 1, W, r, zlo, zhi);
         for (u64 j = lo; j < hi; j++) nb += d->infinity_b[j] ? 0 : 1;
-        if (hi - lo > max_w) max_w = hi - lo;
-        if (nb > max_b) max_b = nb;
-        if (zhi - zlo > max_z) max_z = zhi - zlo;
+        const u64 part[3] = {hi - lo, nb, zhi - zlo};
+        for (int k = 0; k < 3; k++) largest[k] = std::max(largest[k], part[k]);
     }
-    // ONE fixed-base plan for all parts (mode 1 exchanges buckets, so the parts must cut their scalars alike; and a part just
-    // under the 2^20-point threshold next to one just over it would otherwise pick different paths): the rule of mi_pk_load
-    // (prove.hip: tables for an MSM of >= 2^20 points while they fit in a third of the free memory, smallest group first),
-    // applied to the LARGEST part and the tightest device OF THE WHOLE GROUP (one rank per process: the budgets are all-gathered),
-    // then forced on every context through its knobs.  Knobs the caller set (mi_debug_set_prove_fixed_base) are kept.
-    u32 plan[3] = {1, 1, 1};   // A+K, B, Z: 1 = no tables
+    // ONE fixed-base plan for all parts (mode 1 exchanges buckets, so the parts must cut their scalars alike; and a part just under the
+    // 2^20-point threshold next to one just over it would otherwise pick different paths): mi_pk_load's rule (fixed_base_plan) for the LARGEST part
+    // and the tightest device OF THE WHOLE GROUP (the budgets are all-gathered), handed to every part.  Knobs the caller set are kept.
     auto fail = [&](int32_t rc) { for (size_t i = 0; i < spk->part.size(); i++) if (spk->part[i]) { (void)hipSetDevice(g->dev[i]); mi_pk_free(g->ctx[i], spk->part[i]); } delete spk; return rc; };
-    {
-        std::vector<u64> budgets(nl, 0);
-        for (int i = 0; i < nl; i++) {
-            (void)hipSetDevice(g->dev[i]);
-            size_t fr = 0, tot = 0, sharers = 0;
-            if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
-            for (int j = 0; j < nl; j++) sharers += g->dev[j] == g->dev[i] ? 1 : 0;
-            budgets[i] = fr / 3 / sharers;
-        }
-        u64 bmin = 0, bmax = 0;
-        int32_t rc = group_min_max(g, budgets, &bmin, &bmax);
-        if (rc != MI_OK) return fail(rc);
-        size_t budget = (size_t)bmin;
-        auto nwin_of = [](u32 c) { return (size_t)((256 + c - 1) / c); };
-        auto choose = [&](u32 c_auto, u64 n_max, size_t bytes_per_point) -> u32 {
-            const size_t need = nwin_of(c_auto) * n_max * bytes_per_point;
-            if (n_max < ((u64)1 << 20) || need > budget) return 1;
-            budget -= need;
-            return c_auto;
-        };
-        plan[2] = choose(20, max_z, sizeof(G1Aff));
-        plan[1] = choose(17, max_b, sizeof(G1Aff) + sizeof(G2Aff));
-        plan[0] = choose(19, max_w, 2 * sizeof(G1Aff));
+    std::vector<u64> budgets(nl, 0);
+    for (int i = 0; i < nl; i++) {
+        (void)hipSetDevice(g->dev[i]);
+        size_t fr = 0, tot = 0, sharers = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
+        for (int j = 0; j < nl; j++) sharers += g->dev[j] == g->dev[i] ? 1 : 0;
+        budgets[i] = fr / 3 / sharers;
     }
+    u64 bmin = 0, bmax = 0, smin = 0, smax = 0;
+    int32_t rc = group_min_max(g, budgets, &bmin, &bmax);
+    if (rc != MI_OK) return fail(rc);
+    const u32 automatic[3] = {0, 0, 0};
+    const FixedBasePlan plan = fixed_base_plan(automatic, bmin, largest[KEY_AK], largest[KEY_B], largest[KEY_Z]);
     std::vector<int32_t> rcs(nl, MI_OK);
     std::vector<std::thread> th;
     for (int i = 0; i < nl; i++) th.emplace_back([&, i] {   // uploads (and table builds) of the parts run side by side, one host thread per device
@@ -1269,10 +1254,7 @@ static int32_t pk_load_sharded_impl(mi_group *g, const mi_pk_desc *descs, bool d
         mi_ctx *ctx = g->ctx[i];
         ShardRange sr;
         wire_range_of(d->nb_wires, W, g->rank0 + i, share, sr.w_lo, sr.w_hi); range_of(N - 1, W, g->rank0 + i, sr.z_lo, sr.z_hi);
-        u32 saved[3];
-        for (int k = 0; k < 3; k++) { saved[k] = ctx->fixed_knob[k]; if (!saved[k]) ctx->fixed_knob[k] = plan[k]; }
-        rcs[i] = mi_pk_load_range(ctx, device_points ? &descs[i] : d, &spk->part[i], device_points, &sr);
-        for (int k = 0; k < 3; k++) ctx->fixed_knob[k] = saved[k];
+        rcs[i] = mi_pk_load_range(ctx, device_points ? &descs[i] : d, &spk->part[i], device_points, &sr, &plan);
     });
     for (auto &t : th) t.join();
     // every process reaches the agreement below even when a local part failed (a collective that only some ranks enter would hang)
@@ -1282,11 +1264,10 @@ static int32_t pk_load_sharded_impl(mi_group *g, const mi_pk_desc *descs, bool d
     std::vector<u64> sig(nl, 0);
     for (int i = 0; i < nl; i++) {
         mi_pk *p = spk->part[i];
-        if (p) { p->gen_c_ak = mi_msm_auto_c(max_w); p->gen_c_b = mi_msm_auto_c(max_b); p->gen_c_z = mi_msm_auto_c(max_z); }
-        sig[i] = p ? ((u64)1 << 32 | (u64)p->c_ak << 16 | (u64)p->c_b << 8 | (u64)p->c_z) : 0;   // 0 = this part failed to load
+        for (int k = 0; p && k < 3; k++) p->group[k].gen_c = p->group[k].c ? 0 : mi_msm_auto_c(largest[k]);
+        sig[i] = p ? ((u64)1 << 32 | (u64)p->group[KEY_AK].c << 16 | (u64)p->group[KEY_B].c << 8 | (u64)p->group[KEY_Z].c) : 0;   // 0 = this part failed to load
     }
-    u64 smin = 0, smax = 0;
-    int32_t rc = group_min_max(g, sig, &smin, &smax);
+    rc = group_min_max(g, sig, &smin, &smax);
     if (first_bad != MI_OK) return fail(first_bad);
     if (rc != MI_OK) return fail(rc);
     if (smin == 0) { g->err = "pk: another rank of the group failed to load its part"; return fail(MI_EHIP); }

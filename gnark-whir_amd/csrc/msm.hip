@@ -17,6 +17,7 @@
 #include "msm2_core.cuh"
 #include "scan_u32.cuh"
 #include "msm_curve_ops.h"
+#include "key_plan.h"
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
@@ -603,7 +604,7 @@ static Msm2Shape msm2_plan_shape(const MsmKnobs *kn, u32 n, u32 c, bool wkeys) {
     const u32 chunk = kn->chunk ? kn->chunk : 8192;    // (gbits, chunk) sweep at 2^23 pairs, c = 20: tools/fixed_probe.py
     u32 gbits = kn->gbits ? kn->gbits : 11;
     if (gbits > 15) gbits = 15;
-    const u32 keys_total = (wkeys ? (256 + c - 1) / c : 1u) << (c - 1);
+    const u32 keys_total = (wkeys ? msm_nwin(c) : 1u) << (c - 1);
     while ((keys_total >> gbits) > MSM2_MAX_GROUPS) gbits++;
     return msm2_shape(n, c, G, chunk, gbits, wkeys ? 1u : 0u);
 }
@@ -855,8 +856,8 @@ int32_t mi_msm_precompute(mi_ctx *ctx, int curve, const void *base_dev, void *pr
     void *state = nullptr, *prefix = nullptr;
     const bool batched = !knobs_of(ctx)->precompute_unbatched && hipMalloc(&state, n * ops.xyzz_bytes) == hipSuccess && hipMalloc(&prefix, n * ops.coord_bytes) == hipSuccess;
     if (!batched) (void)hipGetLastError();
-    if (batched) ops.precompute_batched(ctx->stream, base_dev, pre_dev, (u32)n, c, (256 + c - 1) / c, state, prefix);
-    else ops.precompute(ctx->stream, base_dev, pre_dev, (u32)n, c, (256 + c - 1) / c);
+    if (batched) ops.precompute_batched(ctx->stream, base_dev, pre_dev, (u32)n, c, msm_nwin(c), state, prefix);
+    else ops.precompute(ctx->stream, base_dev, pre_dev, (u32)n, c, msm_nwin(c));
     hipError_t e = hipGetLastError();
     if (batched && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // the scratch goes away below
     if (state) (void)hipFree(state);
@@ -894,7 +895,7 @@ int32_t mi_msm_enqueue(mi_ctx *ctx, int slot, int sort_slot, int curve, const vo
             sl.c = srt.c; sl.nwin_digits = srt.nwin_digits; sl.nwin_keys = srt.nwin_keys;
         } else {
             sl.c = precomp_c ? precomp_c : (knobs_of(ctx)->c ? knobs_of(ctx)->c : (generic_c >= 2 && generic_c <= 16 ? generic_c : auto_c(1)));
-            sl.nwin_digits = (256 + sl.c - 1) / sl.c;
+            sl.nwin_digits = msm_nwin(sl.c);
             sl.nwin_keys = precomp_c ? 1 : sl.nwin_digits;
         }
         sl.entries_cap = 0;

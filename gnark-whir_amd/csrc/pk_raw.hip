@@ -136,7 +136,7 @@ int32_t mi_pk_load_raw(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nb_
         d.infinity_a = ia.data(); d.infinity_b = ib.data();
         d.committed_wires = committed_wires; d.n_committed = n_committed;
         bool took = false;
-        const int32_t lr = mi_pk_load_range(ctx, &d, out, true, nullptr, /*adopt=*/true, &took);
+        const int32_t lr = mi_pk_load_range(ctx, &d, out, true, nullptr, /*forced=*/nullptr, /*adopt=*/true, &took);
         if (took) for (void *&a : arrays) a = nullptr;   // the key owns them now (it has released them itself if it failed after taking them)
         MI_TRY(lr);
         // Pedersen commitment keys

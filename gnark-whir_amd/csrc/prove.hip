@@ -22,178 +22,149 @@ __global__ void k_gather_fr(Fr *out, const Fr *W, const u32 *idx, size_t n) {
     if (i < n) out[i] = W[idx[i]];
 }
 
+static size_t point_bytes(int curve) { return curve == 1 ? sizeof(G1Aff) : sizeof(G2Aff); }
 static int32_t upload(mi_ctx *ctx, void **dst, const void *src, size_t bytes) {
     MI_CHECK_HIP(ctx, hipMalloc(dst, bytes ? bytes : 32));
     if (bytes) MI_CHECK_HIP(ctx, hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return MI_OK;
 }
 
-int32_t mi_pk_load_range(mi_ctx *ctx, const mi_pk_desc *d, mi_pk **out, bool device_points, const ShardRange *sr, bool adopt, bool *took_arrays) {
-    if (took_arrays) *took_arrays = false;
-    if (!ctx || !d || !out) return MI_EINVAL;
-    *out = nullptr;
-    // device_points with a range (mi_pk_load_sharded_dev): the arrays ARE this part's slices (counts = points of the slice)
+// ---------------------------------------------------------------- mi_pk_load_range, step by step
+// 1: the header, and the range this load covers (the whole key without sr; slices, mi_pk_load_sharded_dev: the arrays ARE this part's slices,
+// counts = points of the slice).  Step 2 is wire_indices (key_plan.h).
+static int32_t check_header(mi_ctx *ctx, const mi_pk_desc *d, bool slices, const ShardRange *sr, ShardRange *r) {
     if (d->log_n > 28 || d->nb_public > d->nb_wires || !d->infinity_a || !d->infinity_b) MI_FAIL(ctx, MI_EINVAL, "pk: bad header");
     const u64 N = (u64)1 << d->log_n;
-    const bool slices = sr && device_points;
     if (!slices && d->n_g1_z + 1 < N) MI_FAIL(ctx, MI_EINVAL, "pk: G1.Z needs at least 2^log_n - 1 points");
     if (d->nb_wires >= ((u64)1 << 31)) MI_FAIL(ctx, MI_EINVAL, "pk: too many wires");
     if (d->n_g2_b != d->n_g1_b) MI_FAIL(ctx, MI_EINVAL, "pk: G1.B and G2.B differ in length");
-    // gather indices from the static masks (prove.go: wireValuesA/B filters; K drops public + committed)
-    // a part of a sharded key keeps the wires [w_lo, w_hi) (indices relative to w_lo) and the points those wires own:
-    // a0 / b0 / k0 = points of earlier wires = offset of this part's slice in the caller's arrays
-    const u64 w_lo = sr ? sr->w_lo : 0, w_hi = sr ? sr->w_hi : d->nb_wires;
-    const u64 z_lo = sr ? sr->z_lo : 0, z_hi = sr ? sr->z_hi : N - 1;
-    if (w_lo > w_hi || w_hi > d->nb_wires || z_lo > z_hi || z_hi > N - 1) MI_FAIL(ctx, MI_EINVAL, "pk: bad shard range");
+    *r = sr ? *sr : ShardRange{0, d->nb_wires, 0, N - 1};
+    if (r->w_lo > r->w_hi || r->w_hi > d->nb_wires || r->z_lo > r->z_hi || r->z_hi > N - 1) MI_FAIL(ctx, MI_EINVAL, "pk: bad shard range");
     // one device runs every MSM of its part, and a single-device MSM takes at most 2^27 pairs (mi_msm_enqueue): A and K run over the
     // part's wires, B over a subset of them, Z over its Z range.  Refused here, before anything is allocated or enqueued.
-    if (w_hi - w_lo > MI_MSM_MAX_PAIRS || z_hi - z_lo > MI_MSM_MAX_PAIRS)
+    if (r->w_hi - r->w_lo > MI_MSM_MAX_PAIRS || r->z_hi - r->z_lo > MI_MSM_MAX_PAIRS)
         MI_FAIL(ctx, MI_EINVAL, "pk: a per-device MSM would exceed 2^27 pairs (log_n = 28, or more than 2^27 wires on one device): "
                                 "load the key with mi_pk_load_sharded over enough devices");
-    std::vector<u32> ia, ib, ik;
-    u64 ci = 0, ca = 0, cb = 0, ck = 0, a0 = 0, b0 = 0, k0 = 0;
-    for (u64 j = 0; j < d->nb_wires; j++) {
-        const bool in = j >= w_lo && j < w_hi;
-        if (j == w_lo) { a0 = ca; b0 = cb; k0 = ck; }
-        if (!d->infinity_a[j]) { ca++; if (in) ia.push_back((u32)(j - w_lo)); }
-        if (!d->infinity_b[j]) { cb++; if (in) ib.push_back((u32)(j - w_lo)); }
-        if (j >= d->nb_public) {
-            while (ci < d->n_committed && d->committed_wires[ci] < j) ci++;
-            if (ci < d->n_committed && d->committed_wires[ci] == j) continue;
-            ck++;
-            if (in) ik.push_back((u32)(j - w_lo));
-        }
+    return MI_OK;
+}
+// 3: the point arrays in the order of their uploads -- this range's share of the host arrays, or the device arrays as they stand, the
+// key's own from here on when it adopts them -- and the index arrays of A, B, K
+enum { ARR_A, ARR_B1, ARR_K, ARR_Z, ARR_B2 };
+static int32_t take_arrays(mi_ctx *ctx, mi_pk *pk, const mi_pk_desc *d, const WireIndices &wi, u64 n_z, bool device_points, bool adopt, void *arr[5], u32 *idx[3]) {
+    const void *given[5] = {d->g1_a, d->g1_b, d->g1_k, d->g1_z, d->g2_b};
+    const u64 first[5] = {wi.a0, wi.b0, wi.k0, pk->z_lo, wi.b0}, n[5] = {wi.a.size(), wi.b.size(), wi.k.size(), n_z, wi.b.size()};
+    // an upload is the key's from its allocation on: a failing copy leaves it to mi_pk_free
+    auto key_upload = [&](void **dst, const void *src, size_t bytes, int kind) { const int32_t rc = upload(ctx, dst, src, bytes); if (*dst) pk->own(*dst, bytes, kind); return rc; };
+    for (int i = 0; i < 5; i++) {
+        const size_t size = point_bytes(i == ARR_B2 ? 2 : 1);
+        if (!device_points) MI_TRY(key_upload(&arr[i], (const char *)given[i] + first[i] * size, n[i] * size, KEY_MEM_BASES));
+        else { arr[i] = (void *)given[i]; if (adopt) pk->own(arr[i], n[i] * size, KEY_MEM_BASES); }
     }
-    if (w_lo >= d->nb_wires) { a0 = ca; b0 = cb; k0 = ck; }
-    if (slices) {
-        if (ia.size() != d->n_g1_a || ib.size() != d->n_g1_b || ik.size() != d->n_g1_k || d->n_g1_z < z_hi - z_lo)
-            MI_FAIL(ctx, MI_EINVAL, "pk: slice point counts do not match the infinity masks / public / committed wire sets of this rank's wire range");
-    } else if (ca != d->n_g1_a || cb != d->n_g1_b || ck != d->n_g1_k)
+    const std::vector<u32> *wires[3] = {&wi.a, &wi.b, &wi.k};
+    for (int i = 0; i < 3; i++) MI_TRY(key_upload((void **)&idx[i], wires[i]->data(), wires[i]->size() * 4, KEY_MEM_INDICES));
+    return MI_OK;
+}
+// 4: pk.G1.A / pk.G1.K with one slot per wire of the range
+static int32_t expand_per_wire(mi_ctx *ctx, mi_pk *pk, void **full, const void *compact, const u32 *idx, size_t n) {
+    const size_t bytes = (size_t)pk->nb_wires * sizeof(G1Aff);
+    MI_CHECK_HIP(ctx, hipMalloc(full, bytes ? bytes : 64));
+    pk->own(*full, bytes, KEY_MEM_BASES);
+    MI_CHECK_HIP(ctx, hipMemsetAsync(*full, 0, bytes, ctx->stream));
+    if (n) hipLaunchKernelGGL(k_expand_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (G1Aff *)*full, (const G1Aff *)compact, idx, n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+// 5: the table plan.  The key's own: fixed_base_plan over a third of the device memory that is free NOW, after the uploads and the
+// expansions (the rest stays for the contexts' workspaces).  forced: that plan, except for the groups whose knob the caller set.
+static void plan_tables(mi_ctx *ctx, mi_pk *pk, const FixedBasePlan *forced) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+    const FixedBasePlan own = fixed_base_plan(ctx->fixed_knob, free_b / 3, pk->group[KEY_AK].n, pk->group[KEY_B].n, pk->group[KEY_Z].n);
+    for (int g = 0; g < 3; g++) pk->group[g].c = forced && !ctx->fixed_knob[g] ? forced->c[g] : own.c[g];
+}
+// 6: the tables of one group from its plain bases; without room for them after all (the budget is an estimate) the group stays generic
+static int32_t build_table(mi_ctx *ctx, mi_pk *pk, void **table, const void *plain, size_t n, int curve, u32 c) {
+    const size_t bytes = msm_nwin(c) * n * point_bytes(curve);
+    MI_CHECK_HIP(ctx, hipMalloc(table, bytes ? bytes : 64));
+    pk->own(*table, bytes, KEY_MEM_TABLES);
+    return mi_msm_precompute(ctx, curve, plain, *table, n, c);
+}
+static int32_t build_tables(mi_ctx *ctx, mi_pk *pk, int g, void *const plain[2]) {
+    KeyGroup &G = pk->group[g];
+    void *t[2] = {nullptr, nullptr};
+    int32_t rc = MI_OK;
+    for (int i = 0; i < KEY_GROUP_MSMS[g] && G.c && rc == MI_OK; i++) rc = build_table(ctx, pk, &t[i], plain[i], G.n, KEY_GROUP_CURVE[g][i], G.c);
+    if (rc == MI_ENOMEM) { (void)hipGetLastError(); pk->drop(t[0]); pk->drop(t[1]); G.c = 0; rc = MI_OK; }
+    for (int i = 0; i < KEY_GROUP_MSMS[g]; i++) G.bases[i].pts = G.c ? t[i] : plain[i];
+    return rc;
+}
+// 8: what the level-1 accumulation gathers from goes into the R' packed form: in place where the array is the key's own (tables, the
+// per-wire copies, uploaded or adopted bases), into a converted copy of the key's where it is the caller's
+static int32_t to_rprime_form(mi_ctx *ctx, mi_pk *pk, bool arrays_mine) {
+    for (int g = 0; g < 3; g++) for (int i = 0; i < KEY_GROUP_MSMS[g]; i++) {
+        KeyGroup &G = pk->group[g];
+        const int curve = KEY_GROUP_CURVE[g][i];
+        const size_t n = (G.c ? msm_nwin(G.c) : 1) * G.n, bytes = n * point_bytes(curve);
+        const bool in_place = G.c || g == KEY_AK || arrays_mine;
+        void *src = G.bases[i].pts, *dst = in_place ? src : nullptr;
+        if (!src || !n) continue;
+        if (!in_place) {
+            if (curve == 1) MI_CHECK_HIP(ctx, hipMalloc(&dst, bytes));
+            else if (hipMalloc(&dst, bytes) != hipSuccess) { (void)hipGetLastError(); MI_FAIL(ctx, MI_ENOMEM, "pk: no room for the converted copy of pk.G2.B"); }
+            pk->own(dst, bytes, KEY_MEM_BASES);
+        }
+        mi_msm_ops(curve).to_rprime(ctx->stream, dst, src, n);
+        G.bases[i].pts = dst;
+    }
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) MI_FAIL(ctx, MI_EHIP, "pk: conversion of the G1 arrays failed");
+    pk->rprime = true;
+    return MI_OK;
+}
+// steps 3 to 8 on the key under construction: whatever fails, the caller frees the key and with it all it owns by then
+static int32_t fill_key(mi_ctx *ctx, mi_pk *pk, const mi_pk_desc *d, const WireIndices &wi, u64 n_z, bool device_points, const FixedBasePlan *forced, bool adopt) {
+    const bool mine = !device_points || adopt;   // the five arrays are the key's, not the caller's
+    void *arr[5] = {}, *a_full = nullptr, *k_full = nullptr;
+    u32 *idx[3] = {};
+    MI_TRY(take_arrays(ctx, pk, d, wi, n_z, device_points, adopt, arr, idx));
+    pk->idx_b = idx[1];
+    MI_TRY(expand_per_wire(ctx, pk, &a_full, arr[ARR_A], idx[0], wi.a.size()));
+    MI_TRY(expand_per_wire(ctx, pk, &k_full, arr[ARR_K], idx[2], wi.k.size()));
+    void *const plain[3][2] = {{a_full, k_full}, {arr[ARR_B1], arr[ARR_B2]}, {arr[ARR_Z], nullptr}};
+    plan_tables(ctx, pk, forced);
+    for (int g : {KEY_Z, KEY_B, KEY_AK}) MI_TRY(build_tables(ctx, pk, g, plain[g]));
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) MI_FAIL(ctx, MI_EHIP, "pk upload sync failed");
+    // 7: the compact A and K are not needed any more when they are the key's; nor are plain bases of the key's that have tables
+    if (mine) { pk->drop(arr[ARR_A]); pk->drop(arr[ARR_K]); }
+    for (int g = 0; g < 3; g++) for (int i = 0; i < KEY_GROUP_MSMS[g]; i++) if (pk->group[g].c && (g == KEY_AK || mine)) pk->drop(plain[g][i]);
+    return mi_msm_limb29_enabled(ctx) ? to_rprime_form(ctx, pk, mine) : MI_OK;
+}
+int32_t mi_pk_load_range(mi_ctx *ctx, const mi_pk_desc *d, mi_pk **out, bool device_points, const ShardRange *sr, const FixedBasePlan *forced,
+                         bool adopt, bool *took_arrays) {
+    if (took_arrays) *took_arrays = false;
+    if (!ctx || !d || !out) return MI_EINVAL;
+    *out = nullptr;
+    const bool slices = sr && device_points;
+    ShardRange r;
+    MI_TRY(check_header(ctx, d, slices, sr, &r));
+    const WireIndices wi = wire_indices(d->infinity_a, d->infinity_b, d->nb_wires, d->nb_public, d->committed_wires, d->n_committed, r.w_lo, r.w_hi);
+    if (slices && (wi.a.size() != d->n_g1_a || wi.b.size() != d->n_g1_b || wi.k.size() != d->n_g1_k || d->n_g1_z < r.z_hi - r.z_lo))
+        MI_FAIL(ctx, MI_EINVAL, "pk: slice point counts do not match the infinity masks / public / committed wire sets of this rank's wire range");
+    if (!slices && (wi.n_a != d->n_g1_a || wi.n_b != d->n_g1_b || wi.n_k != d->n_g1_k))
         MI_FAIL(ctx, MI_EINVAL, "pk: point counts do not match the infinity masks / public / committed wire sets");
     mi_pk *pk = new (std::nothrow) mi_pk();
     if (!pk) return MI_ENOMEM;
-    pk->log_n = d->log_n; pk->nb_wires = w_hi - w_lo;
-    pk->nb_public = (u32)(d->nb_public <= w_lo ? 0 : (d->nb_public >= w_hi ? w_hi - w_lo : d->nb_public - w_lo));
-    pk->n_a = ia.size(); pk->n_b = ib.size(); pk->n_k = ik.size(); pk->n_z = sr ? z_hi - z_lo : d->n_g1_z;
-    pk->wire_lo = w_lo; pk->z_lo = z_lo; pk->n_z_msm = z_hi - z_lo;
+    pk->log_n = d->log_n; pk->nb_wires = r.w_hi - r.w_lo;
+    pk->nb_public = (u32)(d->nb_public <= r.w_lo ? 0 : (d->nb_public >= r.w_hi ? r.w_hi - r.w_lo : d->nb_public - r.w_lo));
+    pk->wire_lo = r.w_lo; pk->z_lo = r.z_lo; pk->n_z_msm = r.z_hi - r.z_lo;
+    pk->group[KEY_AK].n = pk->nb_wires; pk->group[KEY_B].n = wi.b.size(); pk->group[KEY_Z].n = pk->n_z_msm;
+    pk->group[KEY_AK].bases[0].stat_pairs = wi.a.size(); pk->group[KEY_AK].bases[1].stat_pairs = wi.k.size();
     std::memcpy(&pk->alpha1, &d->alpha1, 64); std::memcpy(&pk->beta1, &d->beta1, 64); std::memcpy(&pk->delta1, &d->delta1, 64);
     std::memcpy(&pk->beta2, &d->beta2, 128); std::memcpy(&pk->delta2, &d->delta2, 128);
-    int32_t rc = MI_OK;
-    if (device_points) {
-        pk->g1_a = (void *)d->g1_a; pk->g1_b = (void *)d->g1_b; pk->g1_k = (void *)d->g1_k; pk->g1_z = (void *)d->g1_z; pk->g2_b = (void *)d->g2_b;
-        // mi_pk_load_raw hands its converted arrays over (adopt): from here on they are the key's, on success AND on every failure
-        // path below (mi_pk_free releases what is still there); *took_arrays tells the caller so
-        pk->owns_points = adopt;
-        if (adopt && took_arrays) *took_arrays = true;
-    } else {
-        pk->owns_points = true;
-        if (rc == MI_OK) rc = upload(ctx, &pk->g1_a, d->g1_a + a0, pk->n_a * 64);
-        if (rc == MI_OK) rc = upload(ctx, &pk->g1_b, d->g1_b + b0, pk->n_b * 64);
-        if (rc == MI_OK) rc = upload(ctx, &pk->g1_k, d->g1_k + k0, pk->n_k * 64);
-        if (rc == MI_OK) rc = upload(ctx, &pk->g1_z, d->g1_z + z_lo, pk->n_z * 64);
-        if (rc == MI_OK) rc = upload(ctx, &pk->g2_b, d->g2_b + b0, pk->n_b * 128);
-    }
-    if (rc == MI_OK) rc = upload(ctx, (void **)&pk->idx_a, ia.data(), ia.size() * 4);
-    if (rc == MI_OK) rc = upload(ctx, (void **)&pk->idx_b, ib.data(), ib.size() * 4);
-    if (rc == MI_OK) rc = upload(ctx, (void **)&pk->idx_k, ik.data(), ik.size() * 4);
-    // expanded per-wire copies of A and K
-    auto expand = [&](G1Aff **full, const void *compact, const u32 *idx, size_t n) -> int32_t {
-        const size_t bytes = (size_t)pk->nb_wires * sizeof(G1Aff);
-        MI_CHECK_HIP(ctx, hipMalloc((void **)full, bytes ? bytes : 64));
-        MI_CHECK_HIP(ctx, hipMemsetAsync(*full, 0, bytes, ctx->stream));
-        if (n) hipLaunchKernelGGL(k_expand_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, *full, (const G1Aff *)compact, idx, n);
-        MI_CHECK_HIP(ctx, hipGetLastError());
-        return MI_OK;
-    };
-    if (rc == MI_OK) rc = expand(&pk->a_full, pk->g1_a, pk->idx_a, pk->n_a);
-    if (rc == MI_OK) rc = expand(&pk->k_full, pk->g1_k, pk->idx_k, pk->n_k);
-    // Fixed-base tables.  Measured at N = 2^23 with proofs overlapping: c = 19 / 17 / 20 for A+K / B / Z (round 2: B went
-    // from 18 to 17 when the G2 additions got 18 % cheaper and the 2^17-bucket G2 reduce weighed more: 30.2 vs 29.9 proofs/s) gives
-    // +7 % proofs/s over the generic c = 16 path (13..15 windows instead of 16); wider windows lose it again to the bucket
-    // reduce (2^(c-1) buckets, G2 first).  Automatic: a group gets tables when its MSM has >= 2^20 points and the tables of
-    // the groups chosen so far fit in a third of the free device memory (smallest first: Z, B, A+K); the rest stays for the
-    // contexts' workspaces.  ctx->fixed_knob (mi_debug_set_prove_fixed_base): 0 = automatic, 1 = never, 17..22 = forced.
-    {
-        size_t free_b = 0, total_b = 0;
-        if (rc == MI_OK && hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-        size_t budget = free_b / 3;
-        auto nwin_of = [](u32 c) { return (size_t)((256 + c - 1) / c); };
-        auto choose = [&](u32 knob, u32 c_auto, size_t n_max, size_t bytes_per_point) -> u32 {
-            if (knob == 1) return 0;
-            if (knob >= 17 && knob <= 22) return knob;
-            const size_t need = nwin_of(c_auto) * bytes_per_point;
-            if (n_max < ((size_t)1 << 20) || need > budget) return 0;
-            budget -= need;
-            return c_auto;
-        };
-        pk->c_z = choose(ctx->fixed_knob[2], 20, pk->n_z_msm, pk->n_z_msm * sizeof(G1Aff));
-        pk->c_b = choose(ctx->fixed_knob[1], 17, pk->n_b, pk->n_b * (sizeof(G1Aff) + sizeof(G2Aff)));
-        pk->c_ak = choose(ctx->fixed_knob[0], 19, pk->nb_wires, pk->nb_wires * 2 * sizeof(G1Aff));
-        auto pre = [&](void **dst, const void *base, size_t n, int curve, u32 c) -> int32_t {
-            const size_t bytes = nwin_of(c) * n * (curve == 1 ? sizeof(G1Aff) : sizeof(G2Aff));
-            MI_CHECK_HIP(ctx, hipMalloc(dst, bytes ? bytes : 64));
-            return mi_msm_precompute(ctx, curve, base, *dst, n, c);
-        };
-        // a group whose tables cannot be allocated after all (the budget is an estimate) falls back to the generic path
-        auto group = [&](u32 &c, void **t0, const void *b0, int curve0, void **t1, const void *b1, int curve1, size_t n) -> int32_t {
-            if (!c) return MI_OK;
-            int32_t r = pre(t0, b0, n, curve0, c);
-            if (r == MI_OK && t1) r = pre(t1, b1, n, curve1, c);
-            if (r == MI_ENOMEM) {
-                (void)hipGetLastError();
-                if (*t0) { (void)hipFree(*t0); *t0 = nullptr; }
-                if (t1 && *t1) { (void)hipFree(*t1); *t1 = nullptr; }
-                c = 0;
-                r = MI_OK;
-            }
-            return r;
-        };
-        if (rc == MI_OK) rc = group(pk->c_z, &pk->pre_z, pk->g1_z, 1, nullptr, nullptr, 0, pk->n_z_msm);
-        if (rc == MI_OK) rc = group(pk->c_b, &pk->pre_b1, pk->g1_b, 1, &pk->pre_b2, pk->g2_b, 2, pk->n_b);
-        if (rc == MI_OK) rc = group(pk->c_ak, &pk->pre_a, pk->a_full, 1, &pk->pre_k, pk->k_full, 1, pk->nb_wires);
-    }
-    if (rc == MI_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { mi_set_err(ctx, "pk upload sync failed"); rc = MI_EHIP; }
-    if (rc != MI_OK) { if (device_points && !adopt) pk->owns_points = false; mi_pk_free(ctx, pk); return rc; }
-    // the compact A and K copies are not needed any more when the library owns them; nor are plain bases that have tables
-    if (pk->owns_points) { (void)hipFree(pk->g1_a); (void)hipFree(pk->g1_k); pk->g1_a = pk->g1_k = nullptr; }
-    if (pk->c_ak) { (void)hipFree(pk->a_full); (void)hipFree(pk->k_full); pk->a_full = pk->k_full = nullptr; }
-    if (pk->owns_points && pk->c_b) { (void)hipFree(pk->g1_b); (void)hipFree(pk->g2_b); pk->g1_b = pk->g2_b = nullptr; }
-    if (pk->owns_points && pk->c_z) { (void)hipFree(pk->g1_z); pk->g1_z = nullptr; }
-    // the G1 arrays of the level-1 accumulation go into the R' packed form, in place where the key owns them
-    if (mi_msm_limb29_enabled(ctx)) {
-        const MsmCurveOps &g1 = mi_msm_ops(1);
-        auto nwin_of = [](u32 c) { return (size_t)((256 + c - 1) / c); };
-        auto in_place = [&](void *arr, size_t n) { if (arr && n) g1.to_rprime(ctx->stream, arr, arr, n); };
-        auto own_or_copy = [&](void **arr, void **copy, size_t n) -> int32_t {
-            if (!*arr || !n) return MI_OK;
-            if (pk->owns_points) { g1.to_rprime(ctx->stream, *arr, *arr, n); return MI_OK; }
-            MI_CHECK_HIP(ctx, hipMalloc(copy, n * sizeof(G1Aff)));
-            g1.to_rprime(ctx->stream, *copy, *arr, n);
-            *arr = *copy;
-            return MI_OK;
-        };
-        int32_t r = MI_OK;
-        if (pk->c_ak) { in_place(pk->pre_a, nwin_of(pk->c_ak) * pk->nb_wires); in_place(pk->pre_k, nwin_of(pk->c_ak) * pk->nb_wires); }
-        else { in_place(pk->a_full, pk->nb_wires); in_place(pk->k_full, pk->nb_wires); }
-        if (pk->c_b) in_place(pk->pre_b1, nwin_of(pk->c_b) * pk->n_b);
-        else r = own_or_copy(&pk->g1_b, &pk->b1_copy, pk->n_b);
-        {   // pk.G2.B the same way with the G2 conversion
-            const MsmCurveOps &g2 = mi_msm_ops(2);
-            if (pk->c_b) { if (pk->pre_b2 && pk->n_b) g2.to_rprime(ctx->stream, pk->pre_b2, pk->pre_b2, nwin_of(pk->c_b) * pk->n_b); }
-            else if (r == MI_OK && pk->g2_b && pk->n_b) {
-                if (pk->owns_points) g2.to_rprime(ctx->stream, pk->g2_b, pk->g2_b, pk->n_b);
-                else if (hipMalloc(&pk->b2_copy, pk->n_b * sizeof(G2Aff)) != hipSuccess) { (void)hipGetLastError(); mi_set_err(ctx, "pk: no room for the converted copy of pk.G2.B"); r = MI_ENOMEM; }
-                else { g2.to_rprime(ctx->stream, pk->b2_copy, pk->g2_b, pk->n_b); pk->g2_b = pk->b2_copy; }
-            }
-        }
-        if (pk->c_z) in_place(pk->pre_z, nwin_of(pk->c_z) * pk->n_z_msm);
-        else if (r == MI_OK) r = own_or_copy(&pk->g1_z, &pk->z_copy, pk->n_z_msm);
-        if (r == MI_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)) { mi_set_err(ctx, "pk: conversion of the G1 arrays failed"); r = MI_EHIP; }
-        if (r != MI_OK) { if (device_points && !adopt) pk->owns_points = false; mi_pk_free(ctx, pk); return r; }
-        pk->rprime = true;
-    }
-    *out = pk;
-    return MI_OK;
+    // adopt: from here on the arrays are the key's, on success AND on every failure path (mi_pk_free releases what is still there)
+    if (device_points && adopt && took_arrays) *took_arrays = true;
+    const int32_t rc = fill_key(ctx, pk, d, wi, sr ? pk->n_z_msm : d->n_g1_z, device_points, forced, adopt);   // (Z of a whole key: every point given)
+    if (rc == MI_OK) *out = pk; else mi_pk_free(ctx, pk);
+    return rc;
 }
 
 // k * p on the host, k canonical 8 x u32
@@ -216,7 +187,7 @@ static constexpr u32 PEDERSEN_TABLE_C = 17;
 static void pedersen_build_tables(mi_ctx *ctx, mi_pedersen_pk *pk) {
     if (pk->n < ((size_t)1 << 15) || !mi_msm_limb29_enabled(ctx)) return;
     const u32 c = PEDERSEN_TABLE_C;
-    const size_t nwin = (256 + c - 1) / c, bytes = nwin * pk->n * sizeof(G1Aff);
+    const size_t nwin = msm_nwin(c), bytes = nwin * pk->n * sizeof(G1Aff);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || 2 * bytes > free_b / 4) { (void)hipGetLastError(); return; }
     void *t[2] = {nullptr, nullptr};
@@ -319,17 +290,7 @@ int32_t mi_pedersen_fold(const mi_g1_affine *points, size_t n, const mi_fr *chal
 int32_t mi_get_mem_ledger(mi_ctx *ctx, const mi_pk *pk, mi_mem_ledger *out) {
     if (!ctx || !out) return MI_EINVAL;
     std::memset(out, 0, sizeof(*out));
-    auto nwin_of = [](u32 c) { return (size_t)((256 + c - 1) / c); };
-    if (pk) {
-        const size_t g1 = sizeof(G1Aff), g2 = sizeof(G2Aff);
-        if (pk->owns_points) out->key_bases += (pk->g1_a ? pk->n_a * g1 : 0) + (pk->g1_k ? pk->n_k * g1 : 0) + (pk->g1_b ? pk->n_b * g1 : 0) + (pk->g2_b ? pk->n_b * g2 : 0) + (pk->g1_z ? pk->n_z * g1 : 0);
-        out->key_bases += (pk->a_full ? pk->nb_wires * g1 : 0) + (pk->k_full ? pk->nb_wires * g1 : 0);
-        out->key_bases += (pk->b1_copy ? pk->n_b * g1 : 0) + (pk->b2_copy ? pk->n_b * g2 : 0) + (pk->z_copy ? pk->n_z_msm * g1 : 0);
-        if (pk->c_ak) out->key_tables += 2 * nwin_of(pk->c_ak) * pk->nb_wires * g1;
-        if (pk->c_b) out->key_tables += nwin_of(pk->c_b) * pk->n_b * (g1 + g2);
-        if (pk->c_z) out->key_tables += nwin_of(pk->c_z) * pk->n_z_msm * g1;
-        out->key_indices = (pk->n_a + pk->n_b + pk->n_k) * 4;
-    }
+    if (pk) { out->key_bases = pk->mem[KEY_MEM_BASES]; out->key_tables = pk->mem[KEY_MEM_TABLES]; out->key_indices = pk->mem[KEY_MEM_INDICES]; }
     out->ctx_ntt_tables = mi_ntt_table_bytes(ctx);
     for (int i = 0; i < WS_COUNT; i++) {
         const size_t cap = ctx->ws[i].cap;
@@ -340,7 +301,7 @@ int32_t mi_get_mem_ledger(mi_ctx *ctx, const mi_pk *pk, mi_mem_ledger *out) {
 }
 int32_t mi_pk_table_plan(const mi_pk *pk, uint32_t c_out[3]) {
     if (!pk || !c_out) return MI_EINVAL;
-    c_out[0] = pk->c_ak; c_out[1] = pk->c_b; c_out[2] = pk->c_z;
+    for (int g = 0; g < 3; g++) c_out[g] = pk->group[g].c;
     return MI_OK;
 }
 int32_t mi_pk_load(mi_ctx *ctx, const mi_pk_desc *d, mi_pk **out) {
@@ -351,9 +312,7 @@ int32_t mi_pk_load_dev(mi_ctx *ctx, const mi_pk_desc *d, mi_pk **out) { return m
 int32_t mi_pk_free(mi_ctx *ctx, mi_pk *pk) {
     if (!ctx || !pk) return MI_EINVAL;
     (void)hipStreamSynchronize(ctx->stream);
-    if (pk->owns_points) for (void *p : {pk->g1_a, pk->g1_b, pk->g1_k, pk->g1_z, pk->g2_b}) if (p) (void)hipFree(p);
-    for (void *p : {(void *)pk->idx_a, (void *)pk->idx_b, (void *)pk->idx_k, (void *)pk->a_full, (void *)pk->k_full}) if (p) (void)hipFree(p);
-    for (void *p : {pk->pre_a, pk->pre_k, pk->pre_b1, pk->pre_b2, pk->pre_z, pk->b1_copy, pk->z_copy, pk->b2_copy}) if (p) (void)hipFree(p);
+    for (const mi_pk::Alloc &a : pk->owned) if (a.p) (void)hipFree(a.p);
     delete pk;
     return MI_OK;
 }
@@ -372,32 +331,30 @@ static int32_t enqueue_b_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, hipEvent_t
     // wire values are skewed (45 % of them 0 or 1): their sorts are sized by the counted entries, not by windows * n (msm.hip)
     const uint32_t fl = (defer ? MI_MSM_DEFER_REDUCE : 0) | MI_MSM_EXACT_SIZE | (pk->rprime ? MI_MSM_PTS_RPRIME : 0);
     // wireValuesB by the static gather indices, on its MSM's stream; B2 (G2) shares B1's sort (same scalars)
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_B_WIRES], (pk->n_b + 1) * sizeof(Fr)));
+    const KeyGroup &B = pk->group[KEY_B];
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_B_WIRES], (B.n + 1) * sizeof(Fr)));
     hipStream_t st = ctx->msm[MSM_SLOT_B1].stream;
     if (ev_w) MI_CHECK_HIP(ctx, hipStreamWaitEvent(st, ev_w, 0));
-    if (pk->n_b) hipLaunchKernelGGL(k_gather_fr, dim3((unsigned)((pk->n_b + 255) / 256)), dim3(256), 0, st, (Fr *)ctx->ws[WS_B_WIRES].p, (const Fr *)W, pk->idx_b, pk->n_b);
+    if (B.n) hipLaunchKernelGGL(k_gather_fr, dim3((unsigned)((B.n + 255) / 256)), dim3(256), 0, st, (Fr *)ctx->ws[WS_B_WIRES].p, (const Fr *)W, pk->idx_b, B.n);
     MI_CHECK_HIP(ctx, hipGetLastError());
-    // fixed-base tables, or the plain bases on the generic path (with the window bits the parts of a sharded key agree on)
-    const bool tables = pk->pre_b1 != nullptr;
-    const uint32_t precomp_c = tables ? pk->c_b : 0;
+    // the group's record says which: fixed-base tables, or the plain bases with the window bits the parts of a sharded key agree on
     arm_accum_gate(ctx, MSM_SLOT_B1, accum_gate);
     // (B1 and K are not timed: their chains interleave on one stream, so the event pair around one's level-1 launch may bracket kernels
     //  of the other; mi_stats.g1_accum_* then cover A and Z, the two launches with a stream of their own)
-    MI_TRY(mi_msm_enqueue(ctx, MSM_SLOT_B1, -1, 1, tables ? pk->pre_b1 : pk->g1_b, ctx->ws[WS_B_WIRES].p, pk->n_b, fl, nullptr, false, precomp_c, 0, tables ? 0 : pk->gen_c_b));
+    MI_TRY(mi_msm_enqueue(ctx, MSM_SLOT_B1, -1, 1, B.bases[0].pts, ctx->ws[WS_B_WIRES].p, B.n, fl, nullptr, false, B.c, B.bases[0].stat_pairs, B.gen_c));
     arm_accum_gate(ctx, MSM_SLOT_B2, accum_gate);
-    return mi_msm_enqueue(ctx, MSM_SLOT_B2, MSM_SLOT_B1, 2, tables ? pk->pre_b2 : pk->g2_b, nullptr, pk->n_b, fl, nullptr, false, precomp_c);
+    return mi_msm_enqueue(ctx, MSM_SLOT_B2, MSM_SLOT_B1, 2, B.bases[1].pts, nullptr, B.n, fl, nullptr, false, B.c, B.bases[1].stat_pairs);
 }
 static int32_t enqueue_ak_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, hipEvent_t ev_w, bool defer, const std::function<hipEvent_t()> *accum_gate) {
     (void)hipSetDevice(ctx->dev);
     const uint32_t fl = (defer ? MI_MSM_DEFER_REDUCE : 0) | MI_MSM_EXACT_SIZE | (pk->rprime ? MI_MSM_PTS_RPRIME : 0);
     // A and K are both multiplied by W itself: one sort of all wires (A's slot) serves both, against the per-wire expanded
     // point arrays (a wire without a point reads (0,0) = infinity and is skipped); no gather, one sort less
-    const bool tables = pk->pre_a != nullptr;
-    const uint32_t precomp_c = tables ? pk->c_ak : 0;
+    const KeyGroup &AK = pk->group[KEY_AK];
     arm_accum_gate(ctx, MSM_SLOT_A, accum_gate);
-    MI_TRY(mi_msm_enqueue(ctx, MSM_SLOT_A, -1, 1, tables ? pk->pre_a : (const void *)pk->a_full, W, pk->nb_wires, fl, ev_w, true, precomp_c, pk->n_a, tables ? 0 : pk->gen_c_ak));
+    MI_TRY(mi_msm_enqueue(ctx, MSM_SLOT_A, -1, 1, AK.bases[0].pts, W, AK.n, fl, ev_w, true, AK.c, AK.bases[0].stat_pairs, AK.gen_c));
     arm_accum_gate(ctx, MSM_SLOT_K, accum_gate);
-    return mi_msm_enqueue(ctx, MSM_SLOT_K, MSM_SLOT_A, 1, tables ? pk->pre_k : (const void *)pk->k_full, nullptr, pk->nb_wires, fl, nullptr, false, precomp_c, pk->n_k);   // (not timed: K and B1 share a stream, msm.hip)
+    return mi_msm_enqueue(ctx, MSM_SLOT_K, MSM_SLOT_A, 1, AK.bases[1].pts, nullptr, AK.n, fl, nullptr, false, AK.c, AK.bases[1].stat_pairs);   // (not timed: K and B1 share a stream, msm.hip)
 }
 void WireMsms::start(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, hipEvent_t ev_w, bool defer, const std::function<hipEvent_t()> *accum_gate) {
     auto group = [&](std::future<int32_t> &f, int32_t (*enqueue)(mi_ctx *, mi_pk *, const mi_fr *, hipEvent_t, bool, const std::function<hipEvent_t()> *)) {
@@ -426,8 +383,8 @@ int32_t mi_prove_enqueue_wire_msms(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, hipEv
 // the Z MSM over this key's h coefficients against the bit-reversed pk.G1.Z (ev_h = "h is ready")
 int32_t mi_prove_enqueue_z_msm(mi_ctx *ctx, mi_pk *pk, const mi_fr *h, hipEvent_t ev_h, bool defer) {
     const uint32_t fl = (defer ? MI_MSM_DEFER_REDUCE : 0) | (pk->rprime ? MI_MSM_PTS_RPRIME : 0);
-    const bool tables = pk->pre_z != nullptr;
-    return mi_msm_enqueue(ctx, MSM_SLOT_Z, -1, 1, tables ? pk->pre_z : pk->g1_z, h, pk->n_z_msm, fl, ev_h, true, tables ? pk->c_z : 0, 0, tables ? 0 : pk->gen_c_z);
+    const KeyGroup &Z = pk->group[KEY_Z];
+    return mi_msm_enqueue(ctx, MSM_SLOT_Z, -1, 1, Z.bases[0].pts, h, Z.n, fl, ev_h, true, Z.c, Z.bases[0].stat_pairs, Z.gen_c);
 }
 
 // a host helper thread for one independent scalar multiplication; without a thread to be had the work runs here (no exception may
@@ -597,7 +554,7 @@ static int32_t prove_common(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wir
         if (derive_c) MI_TRY(mi_compute_h_part(ctx, pk->log_n, 2, abc[0], n_constraints, h, abc[1]));   // c = a o b on the device: c is never asked for (a quarter of a host proof's PCIe bytes never crosses)
         else { MI_TRY(arrival.make_abc(2)); MI_TRY(mi_compute_h_part(ctx, pk->log_n, 2, abc[2], n_constraints, h)); }
         // the Z MSM's digit count rides in computeH's last launch (mi_ctx::zhook): armed for exactly that launch
-        if (pk->pre_z) MI_TRY(mi_msm_z_count_arm(ctx, MSM_SLOT_Z, pk->n_z_msm, pk->c_z));
+        if (pk->group[KEY_Z].c) MI_TRY(mi_msm_z_count_arm(ctx, MSM_SLOT_Z, pk->n_z_msm, pk->group[KEY_Z].c));
         const int32_t rc_h = mi_compute_h_part(ctx, pk->log_n, 3, nullptr, n_constraints, h);
         ctx->zhook.armed = false;
         MI_TRY(rc_h);
@@ -650,7 +607,7 @@ static int32_t prove_common(mi_ctx *ctx, mi_pk *pk, const mi_fr *W, size_t n_wir
     // per-phase spans overlap (five streams): they do not add up to total_ms
     MI_CHECK_HIP(ctx, hipEventElapsedTime(&st.compute_h_ms, ev[EV_PROVE_BEGIN], ev[EV_H_READY]));
     if (pk->nb_wires) MI_TRY(slot_ms(MSM_SLOT_A, &st.msm_a_ms));
-    if (pk->n_b) { MI_TRY(slot_ms(MSM_SLOT_B1, &st.msm_b1_ms)); MI_TRY(slot_ms(MSM_SLOT_B2, &st.msm_b2_ms)); }
+    if (pk->group[KEY_B].n) { MI_TRY(slot_ms(MSM_SLOT_B1, &st.msm_b1_ms)); MI_TRY(slot_ms(MSM_SLOT_B2, &st.msm_b2_ms)); }
     if (pk->nb_wires) MI_TRY(slot_ms(MSM_SLOT_K, &st.msm_k_ms));
     if (N > 1) MI_TRY(slot_ms(MSM_SLOT_Z, &st.msm_z_ms));
     st.assemble_ms = ms(t_gpu_done, t_end);     // host work left after the last MSM landed

@@ -3,44 +3,55 @@
 #include "ctx.h"
 #include "curve.cuh"
 #include "msm_curve_ops.h"
+#include "key_plan.h"
 #include <functional>
 #include <future>
+
+// The MSMs of a proof that share one sort of their scalars, as the key serves them.
+struct KeyGroup {
+    u32 c = 0;       // window width of the fixed-base tables; 0 = the generic path on the plain bases
+    u32 gen_c = 0;   // generic-path window bits the parts of a sharded key agree on (0 = from n); stays 0 where there are tables
+    u64 n = 0;       // pairs of each MSM of the group
+    // per MSM: the device array its level-1 accumulation gathers from (fixed-base window copies 2^(c*w) * P of the bases, msm2_core.cuh,
+    // or the plain bases) and the pair count it reports (mi_msm_enqueue's stat_pairs: 0 = n)
+    struct { void *pts = nullptr; u64 stat_pairs = 0; } bases[2];
+};
+// The groups, in the order of FixedBasePlan::c and ctx->fixed_knob: A + K over all wires (pk.G1.A and pk.G1.K re-expanded to one slot per
+// wire, zero = infinity where the wire has no point: both are multiplied by W itself, so ONE sort of W serves both and neither needs a
+// gather), B1 + B2 over the gathered B wires, Z over h.
+enum { KEY_AK, KEY_B, KEY_Z };
+static constexpr int KEY_GROUP_MSMS[3] = {2, 2, 1}, KEY_GROUP_CURVE[3][2] = {{1, 1}, {1, 2}, {1, 1}};
+enum { KEY_MEM_BASES, KEY_MEM_TABLES, KEY_MEM_INDICES };   // mi_mem_ledger's key_bases, key_tables, key_indices
 
 struct mi_pk {
     u32 log_n = 0, nb_public = 0;
     u64 nb_wires = 0;
-    void *g1_a = nullptr, *g1_b = nullptr, *g1_k = nullptr, *g1_z = nullptr, *g2_b = nullptr;
-    u64 n_a = 0, n_b = 0, n_k = 0, n_z = 0;
-    bool owns_points = false;
-    u32 *idx_a = nullptr, *idx_b = nullptr, *idx_k = nullptr;  // wire index of every A / B / K point
-    // pk.G1.A and pk.G1.K re-expanded to one slot per wire (zero = infinity where the wire has no point): both are multiplied
-    // by W itself, so ONE sort of W serves both MSMs and neither needs a gather (prove.hip, step 5)
-    G1Aff *a_full = nullptr, *k_full = nullptr;
-    // Fixed-base window copies 2^(c*w) * P (msm2_core.cuh) of the bases, per group of MSMs that share a sort: A+K, B1+B2, Z.
-    // c = 0: the group runs the generic path on the plain bases.  A group with tables no longer keeps its plain copy
-    // (pre[0] is the base array) unless the caller owns it.
-    u32 c_ak = 0, c_b = 0, c_z = 0;
-    void *pre_a = nullptr, *pre_k = nullptr, *pre_b1 = nullptr, *pre_b2 = nullptr, *pre_z = nullptr;
+    KeyGroup group[3];
+    const u32 *idx_b = nullptr;   // wire index of every B point (the gather of wireValuesB)
+    // The arrays of every group hold both coordinates times 2^5: the R' = 2^261 packed form of the 9 x 29-bit kernel
+    // (msm_curve_ops.h).  Arrays of the caller (mi_pk_load_dev) are never rewritten: the key points at converted copies of its own then.
+    bool rprime = false;
     G1Aff alpha1, beta1, delta1;
     G2Aff beta2, delta2;
     // A part of a point-sharded key (group.hip) covers wires [wire_lo, wire_lo + nb_wires) and the Z pairs
     // [z_lo, z_lo + n_z_msm) of the 2^log_n - 1; a whole key has wire_lo = z_lo = 0 and n_z_msm = 2^log_n - 1.
     u64 wire_lo = 0, z_lo = 0, n_z_msm = 0;
-    u32 gen_c_ak = 0, gen_c_b = 0, gen_c_z = 0;
-    // The G1 arrays the level-1 accumulation gathers from (tables, or the plain bases of a group without tables) hold both
-    // coordinates times 2^5: the R' = 2^261 packed form of the 9 x 29-bit kernel (msm_curve_ops.h).  Arrays of the caller
-    // (mi_pk_load_dev) are never rewritten: b1_copy / z_copy are the key's own converted copies of pk.G1.B / pk.G1.Z then.
-    bool rprime = false;
-    void *b1_copy = nullptr, *z_copy = nullptr, *b2_copy = nullptr;   // generic-path window bits the parts of a sharded key agree on (0 = from n)
+    // Every device allocation the key frees, and their bytes by KEY_MEM_* as they come and go.  Arrays of the caller are not among them.
+    struct Alloc { void *p; u64 bytes; int kind; };
+    std::vector<Alloc> owned;
+    u64 mem[3] = {0, 0, 0};
+    void own(void *p, u64 bytes, int kind) { owned.push_back({p, bytes, kind}); mem[kind] += bytes; }
+    void drop(void *p) { for (Alloc &a : owned) if (p && a.p == p) { (void)hipFree(p); mem[a.kind] -= a.bytes; a.p = nullptr; } }   // frees one of them now
 };
-
 
 struct ShardRange { u64 w_lo, w_hi, z_lo, z_hi; };   // wires [w_lo, w_hi), Z pairs [z_lo, z_hi)
 // mi_pk_load / mi_pk_load_dev (sr == nullptr) or one part of a sharded key (host arrays only)
 // sr with device_points: the arrays are this part's slices on ctx's device (mi_pk_load_sharded_dev).
+// forced (null: the key plans for itself): the table plan of a sharded key's parts; a knob the caller set on the context wins for its group
 // adopt (device_points only): the key takes ownership of the five arrays; *took_arrays = true once it has (then they are released by
 // the key on success and by this function on failure -- the caller must not free them again).
-int32_t mi_pk_load_range(mi_ctx *ctx, const mi_pk_desc *d, mi_pk **out, bool device_points, const ShardRange *sr, bool adopt = false, bool *took_arrays = nullptr);
+int32_t mi_pk_load_range(mi_ctx *ctx, const mi_pk_desc *d, mi_pk **out, bool device_points, const ShardRange *sr, const FixedBasePlan *forced = nullptr,
+                         bool adopt = false, bool *took_arrays = nullptr);
 // a Pedersen key over device arrays the key takes ownership of (mi_pk_load_raw)
 extern "C" int32_t mi_pedersen_pk_adopt(mi_ctx *ctx, void *basis_dev, void *basis_exp_sigma_dev, size_t n, mi_pedersen_pk **out);
 // ProveKnowledge of one BSB22 commitment in two halves on MSM_SLOT_POK of ctx (beside a proof's five MSMs): host values in, affine point out

@@ -578,7 +578,7 @@ int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
         d.infinity_a = ia.data(); d.infinity_b = ib.data();
         d.committed_wires = pl.removed.empty() ? nullptr : pl.removed.data(); d.n_committed = pl.removed.size();
         bool took = false;
-        const int32_t lr = mi_pk_load_range(ctx, &d, pk_out, true, nullptr, /*adopt=*/true, &took);
+        const int32_t lr = mi_pk_load_range(ctx, &d, pk_out, true, nullptr, /*forced=*/nullptr, /*adopt=*/true, &took);
         if (took) for (void *a : arrays) ar.disown(a);   // the key's now (it has released them itself if it failed after taking them)
         MI_TRY(lr);
         MI_TRY(tm.mark(ctx, Timer::DONE));

@@ -216,8 +216,8 @@ def test_group_argument_errors(B, grp):
 
 
 def test_sharded_prove_at_2p22_two_ranks_automatic_tables(B):
-    """N = 2^22: every part has >= 2^20 points per MSM, so mi_pk_load_sharded builds the fixed-base tables by itself (c = 19 / 18 /
-    20, as at the benchmark size).  2 ranks on device 0, both modes, against the oracle and the unsharded proof of the same inputs"""
+    """N = 2^22: every part has >= 2^20 points per MSM, so mi_pk_load_sharded builds the fixed-base tables by itself (c = 19 / 17 /
+    20 for A+K / B / Z, as at the benchmark size).  2 ranks on device 0, both modes, against the oracle and the unsharded proof of the same inputs"""
     g = B.Group([0, 0])
     try:
         log_n = 22
