@@ -1,8 +1,12 @@
 // What the verifier's kernels (verify.hip) and the host build of the tests (tests/emu/emu_pairing.cpp, overflow traps on) both run, one
 // record per lane / per call: the Fp12 operations of mi_debug_fp12_op_dev, the judgement of one proof from its Miller values, and the
-// host half of one proof (its range and curve checks, kSum, the folds, the layout of its pairs), which verify.hip's host code runs.
+// host half of one proof (its range and curve checks, kSum, the folds, the layout of its pairs) and of one batch (VerifyStage), which
+// the host code of verify.hip and verify_combined.hip runs.
 #pragma once
 #include "pairing.cuh"
+#include <cstring>
+#include <utility>
+#include <vector>
 
 // op numbers of mi_debug_fp12_op_dev (mirrored in include/mi355x_groth16_debug.h); x, y, z are Fp12 records of 12 x mi_fp
 enum {
@@ -114,6 +118,36 @@ inline void verify_assemble(const VerifyKeyRef &vk, const VerifyProofRef &in, bo
         }
     }
 }
+
+// The host's view of one batch before any device work: what mi_verify_run and mi_verify_combined_run (through mi_verify_open, verify.hip)
+// and the host build of the tests all start from.  A proof whose decode_malformed byte (the array may be null) is set has none of its
+// words read.  The references point into the caller's memory, which outlives the stage.
+struct VerifyStage {
+    VerifyKeyRef key{};
+    u32 n_pub = 0, nc = 0, ns = 0;         // ns = n_pub + nc: the scalars of one proof's kSum
+    std::vector<VerifyProofRef> proofs;
+    std::vector<uint8_t> flags;            // flags[i] = decode_malformed[i] || !verify_well_formed(proof i)
+    std::vector<Fr> scal;                  // n x ns, row-major: public_inputs | commitment_values; a flagged proof's row is zero, never read
+    size_t first_flagged = 0;              // the lowest i with flags[i], n() when there is none
+    VerifyStage() = default;
+    VerifyStage(const VerifyKeyRef &k, std::vector<VerifyProofRef> refs, const uint8_t *decode_malformed)
+        : key(k), n_pub(k.n_pub), nc(k.n_commitments), ns(n_pub + nc), proofs(std::move(refs)), flags(proofs.size(), 0),
+          scal(proofs.size() * ns, Fr::zero()), first_flagged(proofs.size()) {
+        for (size_t i = n(); i-- > 0;) {
+            const VerifyProofRef &in = proofs[i];
+            if ((decode_malformed && decode_malformed[i]) || !verify_well_formed(key, in)) { flags[i] = 1; first_flagged = i; continue; }
+            if (n_pub) std::memcpy(&scal[i * ns], in.public_inputs, (size_t)n_pub * sizeof(Fr));
+            if (nc) std::memcpy(&scal[i * ns + n_pub], in.commitment_values, (size_t)nc * sizeof(Fr));
+        }
+    }
+    size_t n() const { return proofs.size(); }
+    // The device's half (k_verify_g2_check, Bs in the r-torsion of the twist): dev[i] != 0 flags proof i.  dev may be flags.data()
+    // itself, after the kernel's bytes were copied back over it: the kernel only ever sets a byte.
+    void merge(const uint8_t *dev) {
+        for (size_t i = n(); i-- > 0;)
+            if (dev[i]) { flags[i] = 1; first_flagged = i < first_flagged ? i : first_flagged; }
+    }
+};
 
 MI_OOL uint8_t verify_judge(const Fp12 *ml, u32 n_ped, const Fp12 *e_alpha_beta, bool malformed) {
     Fp12 f;

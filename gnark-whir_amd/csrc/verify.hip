@@ -2,17 +2,18 @@
 // device-resident verifying key, and the two debug entry points over the same arithmetic (fp12.cuh, pairing.cuh, pairing_ops.cuh).
 //
 // One batch, every launch on ctx->stream:
-//   host      the range checks of every word and the curve checks of the G1 points (verify_well_formed: a proof that fails them is
-//             malformed and goes no further), the scalars of kSum; per proof one G1 MSM over the key's resident K[1..] (msm.hip), then
-//             kSum = K[0] + that + sum C_k, the folded commitments c^k C_k and the layout of the pairs (verify_assemble); both functions
-//             live in pairing_ops.cuh, where the host build of the tests runs them too
+//   host      mi_verify_open, the start of both bodies: the argument checks, then the VerifyStage (the range checks of every word and the
+//             curve checks of the G1 points, verify_well_formed: a proof that fails them is malformed and goes no further; the scalars
+//             of kSum); per proof one G1 MSM over the key's resident K[1..] (mi_verify_msm over msm.hip), then kSum = K[0] + that +
+//             sum C_k, the folded commitments c^k C_k and the layout of the pairs (verify_assemble).  Stage and functions live in
+//             pairing_ops.cuh, where the host build of the tests runs them too
 //   k_verify_g2_check   one lane per proof: Bs on the twist and in its r-torsion -> the malformed flag
 //   k_pairing_miller    one lane per (proof, pair): a Miller loop, 384 B out
 //   k_verify_judge      one lane per proof: the products of its Miller values, the final exponentiations, the comparisons -> a verdict byte
-// Everything of a batch lives in ONE grow-only workspace (WS_VERIFY): nothing is allocated in steady state.
-// mi_verify_run is that batch; verify_bytes.hip calls it too, with the proofs it decoded (verify_internal.h holds mi_vk for both).
-// verify_combined.hip judges a batch with ONE verdict instead and reuses k_verify_g2_check, k_pairing_miller and k_pairing_final_exp
-// through mi_verify_g2_check_enqueue / mi_pairing_enqueue.
+// Everything of a batch lives in ONE grow-only workspace (WS_VERIFY), laid out by a WsCut: nothing is allocated in steady state.
+// mi_verify_run is that batch; verify_bytes.hip calls it too, with the proofs it decoded.  verify_combined.hip judges a batch with ONE
+// verdict instead: it starts with mi_verify_open too and reuses k_verify_g2_check, k_pairing_miller and k_pairing_final_exp through
+// the three *_enqueue functions.  Every launch of the three files goes through mi_launch64 (verify_internal.h, which holds mi_vk too).
 #include "verify_internal.h"
 #include <cstring>
 #include <string>
@@ -67,82 +68,72 @@ static_assert(sizeof(mi_pedersen_vk) == 2 * sizeof(G2Aff) && sizeof(mi_g1_affine
 
 }   // namespace
 
-int32_t mi_final_exp_enqueue(mi_ctx *ctx, Fp12 *io_dev, size_t n) {
-    hipLaunchKernelGGL(k_pairing_final_exp, dim3(grid64(n)), dim3(64), 0, ctx->stream, io_dev, n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    return MI_OK;
-}
+int32_t mi_final_exp_enqueue(mi_ctx *ctx, Fp12 *io_dev, size_t n) { return mi_launch64(ctx, k_pairing_final_exp, n, io_dev, n); }
 // Miller values of n pairs already on the device, then (final) f^d' in place
 int32_t mi_pairing_enqueue(mi_ctx *ctx, const G1Aff *p_dev, const G2Aff *q_dev, size_t n, Fp12 *gt_dev, bool final_exp) {
-    hipLaunchKernelGGL(k_pairing_miller, dim3(grid64(n)), dim3(64), 0, ctx->stream, p_dev, q_dev, gt_dev, n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    if (final_exp) MI_TRY(mi_final_exp_enqueue(ctx, gt_dev, n));
-    return MI_OK;
+    MI_TRY(mi_launch64(ctx, k_pairing_miller, n, p_dev, q_dev, gt_dev, n));
+    return final_exp ? mi_final_exp_enqueue(ctx, gt_dev, n) : MI_OK;
 }
 int32_t mi_verify_g2_check_enqueue(mi_ctx *ctx, const G2Aff *q_dev, u32 stride, uint8_t *flags_dev, size_t n) {
-    hipLaunchKernelGGL(k_verify_g2_check, dim3(grid64(n)), dim3(64), 0, ctx->stream, q_dev, stride, flags_dev, n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
+    return mi_launch64(ctx, k_verify_g2_check, n, q_dev, stride, flags_dev, n);
+}
+int32_t mi_verify_msm(mi_ctx *ctx, const void *bases_dev, const void *scalars_dev, size_t count, uint32_t msm_flags, G1Aff *out) {
+    mi_g1_jac j;   // the MSM's result is normalised: Z = 1, or Z = 0 for infinity
+    MI_TRY(mi_msm_g1_dev(ctx, (const mi_g1_affine *)bases_dev, (const mi_fr *)scalars_dev, count, msm_flags, &j));
+    Fp z;
+    std::memcpy(&z, &j.z, sizeof(z));
+    *out = G1Aff{Fp::zero(), Fp::zero()};
+    if (!z.is_zero()) std::memcpy(out, &j, sizeof(*out));
+    return MI_OK;
+}
+
+int32_t mi_verify_open(mi_ctx *ctx, const char *who, const mi_vk *vk, const mi_verify_input *in, size_t n, bool has_verdict,
+                       const uint8_t *decode_malformed, VerifyStage *st) {
+    if (!ctx) return MI_EINVAL;
+    const std::string w = who;
+    if (!vk || (!in && n) || !has_verdict) MI_FAIL(ctx, MI_EINVAL, w + "null vk, input or verdict pointer");
+    if (n > ((size_t)1 << 24)) MI_FAIL(ctx, MI_EINVAL, w + "more than 2^24 proofs in one batch");
+    const u32 nc = vk->n_commitments, n_pub = vk->nb_public - 1;
+    std::vector<VerifyProofRef> refs(n);
+    for (size_t i = 0; i < n; i++) {
+        if (n_pub && !in[i].public_inputs) MI_FAIL(ctx, MI_EINVAL, w + "public_inputs is null");
+        if (nc && (!in[i].commitments || !in[i].pok || !in[i].commitment_values)) MI_FAIL(ctx, MI_EINVAL, w + "commitments, pok or commitment_values is null");
+        if (nc > 1 && !in[i].fold_challenge) MI_FAIL(ctx, MI_EINVAL, w + "fold_challenge is null with more than one commitment");
+        refs[i] = VerifyProofRef{(const G1Aff *)&in[i].proof.ar, (const G2Aff *)&in[i].proof.bs, (const G1Aff *)&in[i].proof.krs,
+                                 (const G1Aff *)in[i].commitments, (const G1Aff *)in[i].pok, (const Fr *)in[i].public_inputs,
+                                 (const Fr *)in[i].commitment_values, (const Fr *)in[i].fold_challenge};
+    }
+    *st = VerifyStage(VerifyKeyRef{&vk->k[0], &vk->gamma2, &vk->delta2, (const G2Aff *)vk->ped.data(), n_pub, nc}, std::move(refs), decode_malformed);
     return MI_OK;
 }
 
 int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts, const uint8_t *decode_malformed) {
-    if (!ctx) return MI_EINVAL;
-    if (!vk || (!in && n) || (!verdicts && n)) MI_FAIL(ctx, MI_EINVAL, "verify: null vk, input or verdict pointer");
-    if (n > ((size_t)1 << 24)) MI_FAIL(ctx, MI_EINVAL, "verify: more than 2^24 proofs in one batch");
-    const u32 nc = vk->n_commitments, n_pub = vk->nb_public - 1, ns = n_pub + nc;
-    const u32 np = verify_pairs_per_proof(nc);
-    for (size_t i = 0; i < n; i++) {
-        if (n_pub && !in[i].public_inputs) MI_FAIL(ctx, MI_EINVAL, "verify: public_inputs is null");
-        if (nc && (!in[i].commitments || !in[i].pok || !in[i].commitment_values)) MI_FAIL(ctx, MI_EINVAL, "verify: commitments, pok or commitment_values is null");
-        if (nc > 1 && !in[i].fold_challenge) MI_FAIL(ctx, MI_EINVAL, "verify: fold_challenge is null with more than one commitment");
-    }
+    VerifyStage st;   // host: flags (range and curve checks), scalars
+    MI_TRY(mi_verify_open(ctx, "verify: ", vk, in, n, verdicts || !n, decode_malformed, &st));
     if (!n) return MI_OK;
-
-    // ---- host: flags (range and curve checks, pairing_ops.cuh), scalars
-    const VerifyKeyRef kref{&vk->k[0], &vk->gamma2, &vk->delta2, (const G2Aff *)vk->ped.data(), n_pub, nc};
-    auto proof_ref = [&](size_t i) {
-        return VerifyProofRef{(const G1Aff *)&in[i].proof.ar, (const G2Aff *)&in[i].proof.bs, (const G1Aff *)&in[i].proof.krs,
-                              (const G1Aff *)in[i].commitments, (const G1Aff *)in[i].pok, (const Fr *)in[i].public_inputs,
-                              (const Fr *)in[i].commitment_values, (const Fr *)in[i].fold_challenge};
-    };
-    std::vector<uint8_t> flags(n, 0);
-    std::vector<mi_fr> scal((size_t)n * ns);
-    for (size_t i = 0; i < n; i++) {
-        flags[i] = (decode_malformed && decode_malformed[i]) || !verify_well_formed(kref, proof_ref(i)) ? 1 : 0;
-        if (flags[i]) continue;   // its scalars stay zero and are never read: no MSM runs for a malformed proof
-        if (n_pub) std::memcpy(&scal[i * ns], in[i].public_inputs, (size_t)n_pub * sizeof(mi_fr));
-        if (nc) std::memcpy(&scal[i * ns + n_pub], in[i].commitment_values, (size_t)nc * sizeof(mi_fr));
-    }
-    // ---- workspace: scalars | P | Q | Miller values | flags | verdicts
-    const size_t off_p = up256((size_t)n * ns * sizeof(mi_fr)), off_q = off_p + up256(n * np * sizeof(G1Aff));
-    const size_t off_ml = off_q + up256(n * np * sizeof(G2Aff)), off_fl = off_ml + up256(n * np * sizeof(Fp12));
-    const size_t off_vd = off_fl + up256(n), total = off_vd + up256(n);
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], total));
+    const u32 ns = st.ns, np = verify_pairs_per_proof(st.nc);
+    WsCut cut;
+    const size_t off_scal = cut.take(n * ns * sizeof(Fr)), off_p = cut.take(n * np * sizeof(G1Aff)), off_q = cut.take(n * np * sizeof(G2Aff));
+    const size_t off_ml = cut.take(n * np * sizeof(Fp12)), off_fl = cut.take(n), off_vd = cut.take(n);
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], cut.total));
     char *ws = (char *)ctx->ws[WS_VERIFY].p;
     // ---- kSum: the scalar part through the G1 MSM over the resident K[1..], the rest on the host
     std::vector<G1Aff> P(n * np);
     std::vector<G2Aff> Q(n * np);
-    if (ns) MI_CHECK_HIP(ctx, hipMemcpyAsync(ws, scal.data(), scal.size() * sizeof(mi_fr), hipMemcpyHostToDevice, ctx->stream));
+    if (ns) MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_scal, st.scal.data(), st.scal.size() * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
     for (size_t i = 0; i < n; i++) {
-        G1Aff msm{Fp::zero(), Fp::zero()};
-        if (ns && !flags[i]) {
-            mi_g1_jac j;
-            MI_TRY(mi_msm_g1_dev(ctx, (const mi_g1_affine *)vk->k_dev, (const mi_fr *)ws + i * ns, ns, 0, &j));
-            Fp jz;
-            std::memcpy(&jz, &j.z, sizeof(jz));
-            if (!jz.is_zero()) std::memcpy(&msm, &j, sizeof(msm));   // normalised: Z = 1
-        }
-        verify_assemble(kref, proof_ref(i), !flags[i], msm, &P[i * np], &Q[i * np]);
+        G1Aff msm{Fp::zero(), Fp::zero()};   // no MSM runs for a malformed proof
+        if (ns && !st.flags[i]) MI_TRY(mi_verify_msm(ctx, vk->k_dev, (const Fr *)(ws + off_scal) + i * ns, ns, 0, &msm));
+        verify_assemble(st.key, st.proofs[i], !st.flags[i], msm, &P[i * np], &Q[i * np]);
     }
-    // ---- device: Bs check, Miller loops, judgement
+    // ---- device: Bs check (its answer joins the flags there, for the judgement), Miller loops, judgement
     MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_p, P.data(), P.size() * sizeof(G1Aff), hipMemcpyHostToDevice, ctx->stream));
     MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_q, Q.data(), Q.size() * sizeof(G2Aff), hipMemcpyHostToDevice, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, st.flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
     MI_TRY(mi_verify_g2_check_enqueue(ctx, (const G2Aff *)(ws + off_q), np, (uint8_t *)(ws + off_fl), n));
     MI_TRY(mi_pairing_enqueue(ctx, (const G1Aff *)(ws + off_p), (const G2Aff *)(ws + off_q), n * np, (Fp12 *)(ws + off_ml), false));
-    hipLaunchKernelGGL(k_verify_judge, dim3(grid64(n)), dim3(64), 0, ctx->stream, (const Fp12 *)(ws + off_ml), np, vk->e_alpha_beta_dev,
-                       (const uint8_t *)(ws + off_fl), (uint8_t *)(ws + off_vd), n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
+    MI_TRY(mi_launch64(ctx, k_verify_judge, n, (const Fp12 *)(ws + off_ml), np, vk->e_alpha_beta_dev, (const uint8_t *)(ws + off_fl),
+                       (uint8_t *)(ws + off_vd), n));
     MI_CHECK_HIP(ctx, hipMemcpyAsync(verdicts, ws + off_vd, n, hipMemcpyDeviceToHost, ctx->stream));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MI_OK;
@@ -198,11 +189,13 @@ int32_t mi_vk_load(mi_ctx *ctx, const mi_vk_desc *d, mi_vk **out) {
         MI_CHECK_HIP(ctx, hipMalloc((void **)&vk->k_dev, nb + 64));
         MI_CHECK_HIP(ctx, hipMalloc((void **)&vk->e_alpha_beta_dev, sizeof(Fp12)));
         if (nb) MI_CHECK_HIP(ctx, hipMemcpyAsync(vk->k_dev, vk->k.data() + 1, nb, hipMemcpyHostToDevice, ctx->stream));
-        MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], 512));
+        WsCut cut;
+        const size_t off_alpha = cut.take(sizeof(alpha)), off_beta = cut.take(sizeof(beta));
+        MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], cut.total));
         char *ws = (char *)ctx->ws[WS_VERIFY].p;
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(ws, &alpha, sizeof(alpha), hipMemcpyHostToDevice, ctx->stream));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + 256, &beta, sizeof(beta), hipMemcpyHostToDevice, ctx->stream));
-        MI_TRY(mi_pairing_enqueue(ctx, (const G1Aff *)ws, (const G2Aff *)(ws + 256), 1, vk->e_alpha_beta_dev, true));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_alpha, &alpha, sizeof(alpha), hipMemcpyHostToDevice, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_beta, &beta, sizeof(beta), hipMemcpyHostToDevice, ctx->stream));
+        MI_TRY(mi_pairing_enqueue(ctx, (const G1Aff *)(ws + off_alpha), (const G2Aff *)(ws + off_beta), 1, vk->e_alpha_beta_dev, true));
         MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return MI_OK;
     };
@@ -258,14 +251,10 @@ int32_t mi_groth16_verify_batch(mi_ctx *ctx, const mi_vk *vk, const mi_verify_in
 // ---------------------------------------------------------------- debug surface (include/mi355x_groth16_debug.h)
 int32_t mi_debug_pairing_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, const mi_g2_affine *q_dev, size_t n, mi_fp *gt_dev, uint32_t flags) {
     if (!ctx || (flags & ~MI_PAIRING_FINAL_EXP) || ((!p_dev || !q_dev || !gt_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
-    if (!n) return MI_OK;
     return mi_pairing_enqueue(ctx, (const G1Aff *)p_dev, (const G2Aff *)q_dev, n, (Fp12 *)gt_dev, (flags & MI_PAIRING_FINAL_EXP) != 0);
 }
 int32_t mi_debug_fp12_op_dev(mi_ctx *ctx, int op, mi_fp *z_dev, const mi_fp *x_dev, const mi_fp *y_dev, size_t n) {
     if (!ctx || op < 0 || op >= F12_OP_END || ((!z_dev || !x_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
-    if (!n) return MI_OK;
-    hipLaunchKernelGGL(k_fp12_op, dim3(grid64(n)), dim3(64), 0, ctx->stream, op, (Fp12 *)z_dev, (const Fp12 *)x_dev, (const Fp12 *)y_dev, n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    return MI_OK;
+    return mi_launch64(ctx, k_fp12_op, n, op, (Fp12 *)z_dev, (const Fp12 *)x_dev, (const Fp12 *)y_dev, n);
 }
 }

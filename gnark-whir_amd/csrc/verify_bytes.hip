@@ -1,5 +1,5 @@
-// groth16.Verify from the bytes of a proof (include/mi355x_groth16_verify_bytes.h): decode and hash on the device, then the batch body
-// of verify.hip (mi_verify_run) over the decoded records, and the three debug entry points over the same arithmetic.
+// groth16.Verify from the bytes of a proof (include/mi355x_groth16_verify_bytes.h): decode and hash on the device, then one of the two
+// bodies of the verifier over the decoded records, and the three debug entry points over the same arithmetic.
 //
 // One batch, every launch on ctx->stream:
 //   host      the framing (proof_len, null pointers: MI_EINVAL), the count inside each proof against the key's (-> malformed)
@@ -7,9 +7,10 @@
 //   k_decode_g2    one lane per proof: Bs -> a G2Aff and a malformed byte (an Fp2 square root: four fixed exponentiations)
 //   k_verify_hash  one lane per proof: commitment_values and fold_challenge from the decoded commitments, the public inputs and the
 //                  key's committed lists (sha256_h2f.cuh); a proof that did not decode is skipped
-//   host      the decoded records come back and go through mi_verify_run, the body of mi_groth16_verify_batch, which assembles on the
-//             host as it always did; a proof that did not decode enters it as malformed and none of its words is read.
-//             mi_groth16_verify_bytes_combined enters mi_verify_combined_run (verify_combined.hip) with the same records and flags
+//   host      the decoded records come back as mi_verify_input (verify_bytes_decode, the one front of the entry points below) and go
+//             through mi_verify_run, the body of mi_groth16_verify_batch, or for mi_groth16_verify_bytes_combined through
+//             mi_verify_combined_run (verify_combined.hip); a proof that did not decode enters either as malformed and none of its
+//             words is read.
 // Two decode kernels rather than one: a G2 lane does four times the work of a G1 lane, and in one wave the G1 lanes would wait for it.
 // Everything of a batch lives in ONE grow-only workspace (WS_VERIFY_BYTES): nothing is allocated in steady state.
 #include "verify_internal.h"
@@ -68,12 +69,19 @@ __global__ void __launch_bounds__(64, 1) k_hash_to_field(const uint8_t *msgs, si
     out[i] = hash_to_field(d, dst_len, msgs + i * msg_len, msg_len);
 }
 
-// combined = null: verdicts[n], every proof on its own.  Otherwise ONE verdict by the combined check (verify_combined.hip) under
-// combined->seed, and *combined->first_malformed.
-struct CombinedArgs { const uint8_t *seed; uint64_t *first_malformed; };
-int32_t verify_bytes_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, uint8_t *verdicts, const CombinedArgs *combined = nullptr) {
+// A batch decoded: dec, the records as mi_verify_input for either body of the verifier, over the vectors that hold their words, and
+// bad[i] != 0 where proof i did not decode (the bodies' decode_malformed)
+struct Decoded {
+    std::vector<G1Aff> g1;
+    std::vector<G2Aff> g2;
+    std::vector<Fr> values, folds;
+    std::vector<uint8_t> bad;
+    std::vector<mi_verify_input> dec;
+};
+// has_verdict: the caller's verdict pointer passes its own rule.  n = 0 leaves *d empty.
+int32_t verify_bytes_decode(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, bool has_verdict, Decoded *d) {
     if (!ctx) return MI_EINVAL;
-    if (!vk || (!in && n) || (!verdicts && (n || combined))) MI_FAIL(ctx, MI_EINVAL, "verify bytes: null vk, input or verdict pointer");
+    if (!vk || (!in && n) || !has_verdict) MI_FAIL(ctx, MI_EINVAL, "verify bytes: null vk, input or verdict pointer");
     if (n > ((size_t)1 << 24)) MI_FAIL(ctx, MI_EINVAL, "verify bytes: more than 2^24 proofs in one batch");
     const u32 nc = vk->n_commitments, n_pub = vk->nb_public - 1, slots = proof_g1_slots(nc);
     const size_t plen = proof_bytes_len(nc);
@@ -83,61 +91,56 @@ int32_t verify_bytes_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_inp
             MI_FAIL(ctx, MI_EINVAL, "verify bytes: proof_len is " + std::to_string(in[i].proof_len) + ", the key's proofs have " + std::to_string(plen) + " bytes");
         if (n_pub && !in[i].public_inputs) MI_FAIL(ctx, MI_EINVAL, "verify bytes: public_inputs is null");
     }
-    if (!n) return combined ? mi_verify_combined_run(ctx, vk, nullptr, 0, combined->seed, verdicts, combined->first_malformed, nullptr) : MI_OK;
-    // ---- workspace: bytes | public inputs | committed offsets | committed indices | G1 | G2 | bad G1 | bad G2 | bad | values | folds
+    if (!n) return MI_OK;
+    // ---- workspace; the first four regions travel as one image
     const size_t n_idx = vk->pc_idx.size();
-    const size_t off_pub = up256(n * plen), off_po = off_pub + up256(n * n_pub * sizeof(Fr)), off_pi = off_po + up256((nc + 1) * sizeof(u32));
-    const size_t off_g1 = off_pi + up256(n_idx * sizeof(u32)), off_g2 = off_g1 + up256(n * slots * sizeof(G1Aff)), off_b1 = off_g2 + up256(n * sizeof(G2Aff));
-    const size_t off_b2 = off_b1 + up256(n * slots), off_bad = off_b2 + up256(n), off_val = off_bad + up256(n), off_fold = off_val + up256(n * nc * sizeof(Fr));
-    const size_t total = off_fold + up256(n * sizeof(Fr));
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY_BYTES], total));
+    WsCut cut;
+    const size_t off_bytes = cut.take(n * plen), off_pub = cut.take(n * n_pub * sizeof(Fr)), off_po = cut.take((nc + 1) * sizeof(u32));
+    const size_t off_pi = cut.take(n_idx * sizeof(u32)), image = cut.total;
+    const size_t off_g1 = cut.take(n * slots * sizeof(G1Aff)), off_g2 = cut.take(n * sizeof(G2Aff)), off_b1 = cut.take(n * slots);
+    const size_t off_b2 = cut.take(n), off_bad = cut.take(n), off_val = cut.take(n * nc * sizeof(Fr)), off_fold = cut.take(n * sizeof(Fr));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY_BYTES], cut.total));
     char *ws = (char *)ctx->ws[WS_VERIFY_BYTES].p;
     // ---- host: one staging image of the first four regions and the count check
-    std::vector<uint8_t> stage(off_g1, 0), bad(n, 0);
+    *d = Decoded{std::vector<G1Aff>(n * slots), std::vector<G2Aff>(n), std::vector<Fr>((size_t)n * nc), std::vector<Fr>(n),
+                 std::vector<uint8_t>(n, 0), std::vector<mi_verify_input>(n)};
+    std::vector<uint8_t> stage(image, 0);
     for (size_t i = 0; i < n; i++) {
-        std::memcpy(&stage[i * plen], in[i].proof, plen);
+        std::memcpy(&stage[off_bytes + i * plen], in[i].proof, plen);
         if (n_pub) std::memcpy(&stage[off_pub + i * n_pub * sizeof(Fr)], in[i].public_inputs, (size_t)n_pub * sizeof(Fr));
-        bad[i] = proof_bytes_count(in[i].proof) != nc;
+        d->bad[i] = proof_bytes_count(in[i].proof) != nc;
     }
     std::memcpy(&stage[off_po], vk->pc_off.data(), (nc + 1) * sizeof(u32));
     if (n_idx) std::memcpy(&stage[off_pi], vk->pc_idx.data(), n_idx * sizeof(u32));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws, stage.data(), off_g1, hipMemcpyHostToDevice, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_bad, bad.data(), n, hipMemcpyHostToDevice, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_bytes, stage.data(), image, hipMemcpyHostToDevice, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_bad, d->bad.data(), n, hipMemcpyHostToDevice, ctx->stream));
     // ---- device: decode, hash
-    hipLaunchKernelGGL(k_decode_g1, dim3(grid64(n * slots)), dim3(64), 0, ctx->stream, (const uint8_t *)ws, plen, slots, (G1Aff *)(ws + off_g1),
-                       (uint8_t *)(ws + off_b1), n * slots);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_decode_g2, dim3(grid64(n)), dim3(64), 0, ctx->stream, (const uint8_t *)ws + MI_PROOF_OFF_BS, plen, (G2Aff *)(ws + off_g2),
-                       (uint8_t *)(ws + off_b2), n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_verify_hash, dim3(grid64(n)), dim3(64), 0, ctx->stream, (const G1Aff *)(ws + off_g1), (const uint8_t *)(ws + off_b1),
-                       (const uint8_t *)(ws + off_b2), nc, (const Fr *)(ws + off_pub), n_pub, (const u32 *)(ws + off_po), (const u32 *)(ws + off_pi),
-                       (Fr *)(ws + off_val), (Fr *)(ws + off_fold), (uint8_t *)(ws + off_bad), n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    // ---- host: the decoded records as mi_verify_input, then the body of mi_groth16_verify_batch
-    std::vector<G1Aff> g1(n * slots);
-    std::vector<G2Aff> g2(n);
-    std::vector<Fr> values((size_t)n * nc), folds(n);
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(g1.data(), ws + off_g1, g1.size() * sizeof(G1Aff), hipMemcpyDeviceToHost, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(g2.data(), ws + off_g2, g2.size() * sizeof(G2Aff), hipMemcpyDeviceToHost, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(bad.data(), ws + off_bad, n, hipMemcpyDeviceToHost, ctx->stream));
-    if (nc) MI_CHECK_HIP(ctx, hipMemcpyAsync(values.data(), ws + off_val, values.size() * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(folds.data(), ws + off_fold, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    const uint8_t *bytes = (const uint8_t *)(ws + off_bytes);
+    MI_TRY(mi_launch64(ctx, k_decode_g1, n * slots, bytes, plen, slots, (G1Aff *)(ws + off_g1), (uint8_t *)(ws + off_b1), n * slots));
+    MI_TRY(mi_launch64(ctx, k_decode_g2, n, bytes + MI_PROOF_OFF_BS, plen, (G2Aff *)(ws + off_g2), (uint8_t *)(ws + off_b2), n));
+    MI_TRY(mi_launch64(ctx, k_verify_hash, n, (const G1Aff *)(ws + off_g1), (const uint8_t *)(ws + off_b1), (const uint8_t *)(ws + off_b2), nc,
+                       (const Fr *)(ws + off_pub), n_pub, (const u32 *)(ws + off_po), (const u32 *)(ws + off_pi), (Fr *)(ws + off_val),
+                       (Fr *)(ws + off_fold), (uint8_t *)(ws + off_bad), n));
+    // ---- host: the decoded records as mi_verify_input
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(d->g1.data(), ws + off_g1, d->g1.size() * sizeof(G1Aff), hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(d->g2.data(), ws + off_g2, d->g2.size() * sizeof(G2Aff), hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(d->bad.data(), ws + off_bad, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (nc) MI_CHECK_HIP(ctx, hipMemcpyAsync(d->values.data(), ws + off_val, d->values.size() * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(d->folds.data(), ws + off_fold, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<mi_verify_input> dec(n);
+    mi_verify_input *dec = d->dec.data();
     for (size_t i = 0; i < n; i++) {
-        const G1Aff *p = &g1[i * slots];
+        const G1Aff *p = &d->g1[i * slots];
         std::memcpy(&dec[i].proof.ar, &p[0], sizeof(G1Aff));
-        std::memcpy(&dec[i].proof.bs, &g2[i], sizeof(G2Aff));
+        std::memcpy(&dec[i].proof.bs, &d->g2[i], sizeof(G2Aff));
         std::memcpy(&dec[i].proof.krs, &p[1], sizeof(G1Aff));
         dec[i].commitments = (const mi_g1_affine *)(p + 2);
         dec[i].pok = (const mi_g1_affine *)(p + 2 + nc);
         dec[i].public_inputs = in[i].public_inputs;
-        dec[i].commitment_values = nc ? (const mi_fr *)&values[i * nc] : nullptr;
-        dec[i].fold_challenge = (const mi_fr *)&folds[i];
+        dec[i].commitment_values = nc ? (const mi_fr *)&d->values[i * nc] : nullptr;
+        dec[i].fold_challenge = (const mi_fr *)&d->folds[i];
     }
-    if (combined) return mi_verify_combined_run(ctx, vk, dec.data(), n, combined->seed, verdicts, combined->first_malformed, bad.data());
-    return mi_verify_run(ctx, vk, dec.data(), n, verdicts, bad.data());
+    return MI_OK;
 }
 
 }   // namespace
@@ -165,38 +168,32 @@ int32_t mi_vk_set_public_committed(mi_ctx *ctx, mi_vk *vk, const uint32_t *offse
 int32_t mi_groth16_verify_bytes(mi_ctx *ctx, const mi_vk *vk, const uint8_t *proof, size_t proof_len, const mi_fr *public_inputs, uint8_t *verdict) {
     if (ctx && !verdict) MI_FAIL(ctx, MI_EINVAL, "verify bytes: null verdict pointer");
     const mi_verify_bytes_input in{proof, proof_len, public_inputs};
-    return verify_bytes_run(ctx, vk, &in, 1, verdict);
+    return mi_groth16_verify_bytes_batch(ctx, vk, &in, 1, verdict);
 }
 int32_t mi_groth16_verify_bytes_batch(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, uint8_t *verdicts) {
-    return verify_bytes_run(ctx, vk, in, n, verdicts);
+    Decoded d;
+    MI_TRY(verify_bytes_decode(ctx, vk, in, n, verdicts || !n, &d));
+    return mi_verify_run(ctx, vk, d.dec.data(), n, verdicts, d.bad.data());
 }
 
 int32_t mi_groth16_verify_bytes_combined(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, const uint8_t *seed, uint8_t *verdict,
                                          uint64_t *first_malformed) {
-    const CombinedArgs combined{seed, first_malformed};
-    return verify_bytes_run(ctx, vk, in, n, verdict, &combined);
+    Decoded d;
+    MI_TRY(verify_bytes_decode(ctx, vk, in, n, verdict != nullptr, &d));
+    return mi_verify_combined_run(ctx, vk, d.dec.data(), n, seed, verdict, first_malformed, d.bad.data());
 }
 
 // ---------------------------------------------------------------- debug surface (include/mi355x_groth16_debug.h)
 int32_t mi_debug_decode_g1_dev(mi_ctx *ctx, const uint8_t *enc_dev, size_t n, mi_g1_affine *out_dev, uint8_t *bad_dev) {
     if (!ctx || ((!enc_dev || !out_dev || !bad_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
-    if (!n) return MI_OK;
-    hipLaunchKernelGGL(k_decode_g1, dim3(grid64(n)), dim3(64), 0, ctx->stream, enc_dev, (size_t)0, 0u, (G1Aff *)out_dev, bad_dev, n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    return MI_OK;
+    return mi_launch64(ctx, k_decode_g1, n, enc_dev, (size_t)0, 0u, (G1Aff *)out_dev, bad_dev, n);
 }
 int32_t mi_debug_decode_g2_dev(mi_ctx *ctx, const uint8_t *enc_dev, size_t n, mi_g2_affine *out_dev, uint8_t *bad_dev) {
     if (!ctx || ((!enc_dev || !out_dev || !bad_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
-    if (!n) return MI_OK;
-    hipLaunchKernelGGL(k_decode_g2, dim3(grid64(n)), dim3(64), 0, ctx->stream, enc_dev, (size_t)64, (G2Aff *)out_dev, bad_dev, n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    return MI_OK;
+    return mi_launch64(ctx, k_decode_g2, n, enc_dev, (size_t)64, (G2Aff *)out_dev, bad_dev, n);
 }
 int32_t mi_debug_hash_to_field_dev(mi_ctx *ctx, const uint8_t *dst_dev, uint32_t dst_len, const uint8_t *msgs_dev, size_t msg_len, size_t n, mi_fr *out_dev) {
     if (!ctx || !dst_dev || dst_len == 0 || dst_len > 255 || ((!out_dev || (!msgs_dev && msg_len)) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
-    if (!n) return MI_OK;
-    hipLaunchKernelGGL(k_hash_to_field, dim3(grid64(n)), dim3(64), 0, ctx->stream, msgs_dev, msg_len, dst_dev, dst_len, (Fr *)out_dev, n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    return MI_OK;
+    return mi_launch64(ctx, k_hash_to_field, n, msgs_dev, msg_len, dst_dev, dst_len, (Fr *)out_dev, n);
 }
 }

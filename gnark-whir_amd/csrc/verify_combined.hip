@@ -3,7 +3,8 @@
 // combine_coeff.cuh; the host build of the tests (tests/emu/emu_verify_combined.cpp) runs the same text.
 //
 // One batch, every launch on ctx->stream:
-//   host      the range and curve checks of every proof (verify_well_formed)
+//   host      mi_verify_open (verify.hip): the argument checks, then the VerifyStage of pairing_ops.cuh -- the range and curve checks of
+//             every proof (verify_well_formed) and the scalar matrix
 //   k_verify_g2_check (verify.hip)   Bs of every proof that passed them -> with the host's flags, the lowest malformed index.  If there
 //             is one the batch ends here with verdict 3: nothing below runs.
 //   host      the coefficients r_i (one SHA-256 each)
@@ -22,7 +23,8 @@
 // then share one Miller launch (the tail would otherwise be a second, nearly empty one), the debug entry point measures the kernel
 // the verifier runs, and the 64 bytes per proof that cross memory between the two are nothing beside a Miller loop.
 // Everything of a batch lives in ONE grow-only workspace (WS_VERIFY, which mi_groth16_verify_batch uses too: the calls of a context
-// are serial on its stream): nothing is allocated in steady state.
+// are serial on its stream), laid out by a WsCut: nothing is allocated in steady state.  Launches go through mi_launch64, the MSMs
+// through mi_verify_msm (verify_internal.h).
 #include "verify_internal.h"
 #include "combine_coeff.cuh"
 #include <sys/random.h>
@@ -106,39 +108,23 @@ int32_t fp12_product_enqueue(mi_ctx *ctx, const Fp12 *x, size_t m, Fp12 *t0, Fp1
     for (int level = 0;; level++) {
         const size_t m_out = product_level(m);
         Fp12 *dst = m_out == 1 ? out : (level & 1) ? t1 : t0;
-        hipLaunchKernelGGL(k_fp12_product, dim3(grid64(m_out)), dim3(64), 0, ctx->stream, x, m, dst, m_out);
-        MI_CHECK_HIP(ctx, hipGetLastError());
+        MI_TRY(mi_launch64(ctx, k_fp12_product, m_out, x, m, dst, m_out));
         if (m_out == 1) return MI_OK;
         x = dst;
         m = m_out;
     }
 }
 
-G1Aff affine_of(const mi_g1_jac &j) {   // the MSM's normalised result: Z = 1, or Z = 0 for infinity
-    G1Aff a{Fp::zero(), Fp::zero()};
-    Fp z;
-    std::memcpy(&z, &j.z, sizeof(z));
-    if (!z.is_zero()) std::memcpy(&a, &j, sizeof(a));
-    return a;
-}
-
 }   // namespace
 
 int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdict,
                                uint64_t *first_malformed, const uint8_t *decode_malformed) {
-    if (!ctx) return MI_EINVAL;
-    if (!vk || (!in && n) || !verdict) MI_FAIL(ctx, MI_EINVAL, "verify combined: null vk, input or verdict pointer");
-    if (n > ((size_t)1 << 24)) MI_FAIL(ctx, MI_EINVAL, "verify combined: more than 2^24 proofs in one batch");
-    if ((uint64_t)n * vk->n_commitments > MI_MSM_MAX_PAIRS)
+    // refused where it always was, between mi_verify_open's checks of ctx, vk, in, verdict and n and those of the proofs' pointers
+    if (ctx && vk && in && verdict && n <= ((size_t)1 << 24) && (uint64_t)n * vk->n_commitments > MI_MSM_MAX_PAIRS)
         MI_FAIL(ctx, MI_EINVAL, "verify combined: n * n_commitments above MI_MSM_MAX_PAIRS (one MSM runs over every commitment of the batch)");
-    const u32 nc = vk->n_commitments, n_pub = vk->nb_public - 1, ns = n_pub + nc;
-    const u32 np = verify_combined_tail_pairs(nc);
-    for (size_t i = 0; i < n; i++) {
-        if (n_pub && !in[i].public_inputs) MI_FAIL(ctx, MI_EINVAL, "verify combined: public_inputs is null");
-        if (nc && (!in[i].commitments || !in[i].pok || !in[i].commitment_values))
-            MI_FAIL(ctx, MI_EINVAL, "verify combined: commitments, pok or commitment_values is null");
-        if (nc > 1 && !in[i].fold_challenge) MI_FAIL(ctx, MI_EINVAL, "verify combined: fold_challenge is null with more than one commitment");
-    }
+    VerifyStage st;   // host: the range and curve checks of every proof, the scalar matrix
+    MI_TRY(mi_verify_open(ctx, "verify combined: ", vk, in, n, verdict != nullptr, decode_malformed, &st));
+    const u32 nc = st.nc, ns = st.ns, np = verify_combined_tail_pairs(nc);
     uint8_t own_seed[32];
     if (!seed && n) {
         for (size_t got = 0; got < sizeof(own_seed);) {
@@ -152,52 +138,40 @@ int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_inp
     if (!n) { *verdict = MI_VERIFY_OK; return MI_OK; }
 
     // ---- workspace
-    const u32 nb = (u32)(grid64(n) < MI_COMBINE_MAX_BLOCKS ? grid64(n) : MI_COMBINE_MAX_BLOCKS);
+    const u32 nb = mi_blocks_of(n, 64) < MI_COMBINE_MAX_BLOCKS ? mi_blocks_of(n, 64) : MI_COMBINE_MAX_BLOCKS;
     const size_t lvl0 = product_level(n + np), lvl1 = product_level(lvl0);
-    size_t total = 0;
-    auto take = [&total](size_t bytes) { const size_t at = total; total += up256(bytes); return at; };
-    const size_t off_scal = take(n * ns * sizeof(Fr)), off_r = take(n * sizeof(Fr)), off_fold = take(n * sizeof(Fr));
-    const size_t off_part = take((size_t)(ns + 1) * nb * sizeof(Fr)), off_sum = take((size_t)(ns + 1) * sizeof(Fr));
-    const size_t off_rc = take(n * nc * sizeof(Fr)), off_rrep = take(n * nc * sizeof(Fr));
-    const size_t off_krs = take(n * sizeof(G1Aff)), off_pok = take(n * sizeof(G1Aff)), off_cm = take(n * nc * sizeof(G1Aff));
-    const size_t off_p = take((n + np) * sizeof(G1Aff)), off_q = take((n + np) * sizeof(G2Aff)), off_ml = take((n + np) * sizeof(Fp12));
-    const size_t off_t0 = take(lvl0 * sizeof(Fp12)), off_t1 = take(lvl1 * sizeof(Fp12)), off_res = take(2 * sizeof(Fp12));
-    const size_t off_fl = take(n), off_vd = take(1);
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], total));
+    WsCut cut;
+    const size_t off_scal = cut.take(n * ns * sizeof(Fr)), off_r = cut.take(n * sizeof(Fr)), off_fold = cut.take(n * sizeof(Fr));
+    const size_t off_part = cut.take((size_t)(ns + 1) * nb * sizeof(Fr)), off_sum = cut.take((size_t)(ns + 1) * sizeof(Fr));
+    const size_t off_rc = cut.take(n * nc * sizeof(Fr)), off_rrep = cut.take(n * nc * sizeof(Fr));
+    const size_t off_krs = cut.take(n * sizeof(G1Aff)), off_pok = cut.take(n * sizeof(G1Aff)), off_cm = cut.take(n * nc * sizeof(G1Aff));
+    const size_t off_p = cut.take((n + np) * sizeof(G1Aff)), off_q = cut.take((n + np) * sizeof(G2Aff)), off_ml = cut.take((n + np) * sizeof(Fp12));
+    const size_t off_t0 = cut.take(lvl0 * sizeof(Fp12)), off_t1 = cut.take(lvl1 * sizeof(Fp12)), off_res = cut.take(2 * sizeof(Fp12));
+    const size_t off_fl = cut.take(n), off_vd = cut.take(1);
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], cut.total));
     char *ws = (char *)ctx->ws[WS_VERIFY].p;
 
-    // ---- malformed first: the host's checks, then Bs of the proofs that passed them (infinity stands in for the others)
-    const VerifyKeyRef kref{&vk->k[0], &vk->gamma2, &vk->delta2, (const G2Aff *)vk->ped.data(), n_pub, nc};
-    auto proof_ref = [&](size_t i) {
-        return VerifyProofRef{(const G1Aff *)&in[i].proof.ar, (const G2Aff *)&in[i].proof.bs, (const G1Aff *)&in[i].proof.krs,
-                              (const G1Aff *)in[i].commitments, (const G1Aff *)in[i].pok, (const Fr *)in[i].public_inputs,
-                              (const Fr *)in[i].commitment_values, (const Fr *)in[i].fold_challenge};
-    };
-    std::vector<uint8_t> flags(n, 0);
+    // ---- malformed first: Bs of the proofs that passed the host's checks (infinity stands in for the others)
     std::vector<G2Aff> Q(n + np, G2Aff{Fp2::zero(), Fp2::zero()});
-    for (size_t i = 0; i < n; i++) {
-        flags[i] = (decode_malformed && decode_malformed[i]) || !verify_well_formed(kref, proof_ref(i)) ? 1 : 0;
-        if (!flags[i]) std::memcpy(&Q[i], &in[i].proof.bs, sizeof(G2Aff));
-    }
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_q, Q.data(), n * sizeof(G2Aff), hipMemcpyHostToDevice, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
-    MI_TRY(mi_verify_g2_check_enqueue(ctx, (const G2Aff *)(ws + off_q), 1, (uint8_t *)(ws + off_fl), n));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(flags.data(), ws + off_fl, n, hipMemcpyDeviceToHost, ctx->stream));
-    MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < n; i++)
-        if (flags[i]) {
-            *verdict = MI_VERIFY_MALFORMED;
-            if (first_malformed) *first_malformed = i;
-            return MI_OK;
-        }
+        if (!st.flags[i]) Q[i] = *st.proofs[i].bs;
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_q, Q.data(), n * sizeof(G2Aff), hipMemcpyHostToDevice, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, st.flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
+    MI_TRY(mi_verify_g2_check_enqueue(ctx, (const G2Aff *)(ws + off_q), 1, (uint8_t *)(ws + off_fl), n));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(st.flags.data(), ws + off_fl, n, hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    st.merge(st.flags.data());
+    if (st.first_flagged < n) {
+        *verdict = MI_VERIFY_MALFORMED;
+        if (first_malformed) *first_malformed = st.first_flagged;
+        return MI_OK;
+    }
 
     // ---- host: the coefficients and the inputs of the combination, the points in the MSMs' order (commitments by column: [k][i])
-    std::vector<Fr> r(n, Fr::zero()), scal((size_t)n * ns), fold(nc > 1 ? n : 0);
+    std::vector<Fr> r(n, Fr::zero()), fold(nc > 1 ? n : 0);
     std::vector<G1Aff> krs(n), pok(nc ? n : 0), cm((size_t)n * nc), P(n + np);
     for (size_t i = 0; i < n; i++) {
         combine_coefficient(seed, n, i, r[i].l);
-        if (n_pub) std::memcpy(&scal[i * ns], in[i].public_inputs, (size_t)n_pub * sizeof(Fr));
-        if (nc) std::memcpy(&scal[i * ns + n_pub], in[i].commitment_values, (size_t)nc * sizeof(Fr));
         if (nc > 1) std::memcpy(&fold[i], in[i].fold_challenge, sizeof(Fr));
         std::memcpy(&P[i], &in[i].proof.ar, sizeof(G1Aff));
         std::memcpy(&krs[i], &in[i].proof.krs, sizeof(G1Aff));
@@ -208,7 +182,7 @@ int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_inp
         if (bytes) MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off, src, bytes, hipMemcpyHostToDevice, ctx->stream));
         return MI_OK;
     };
-    MI_TRY(up(off_scal, scal.data(), scal.size() * sizeof(Fr)));
+    MI_TRY(up(off_scal, st.scal.data(), st.scal.size() * sizeof(Fr)));
     MI_TRY(up(off_r, r.data(), n * sizeof(Fr)));
     MI_TRY(up(off_fold, fold.data(), fold.size() * sizeof(Fr)));
     MI_TRY(up(off_krs, krs.data(), n * sizeof(G1Aff)));
@@ -217,48 +191,37 @@ int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_inp
     MI_TRY(up(off_p, P.data(), n * sizeof(G1Aff)));
 
     // ---- device: the scalar combination; S comes back for S K[0] and S alpha
-    hipLaunchKernelGGL(k_verify_combine_scalars, dim3(nb * (ns + 1)), dim3(64), 0, ctx->stream, (const Fr *)(ws + off_scal), ns, (const Fr *)(ws + off_r),
-                       nc > 1 ? (const Fr *)(ws + off_fold) : nullptr, nc, n, nb, (Fr *)(ws + off_part), (Fr *)(ws + off_rc), (Fr *)(ws + off_rrep));
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_verify_combine_reduce, dim3(grid64(ns + 1)), dim3(64), 0, ctx->stream, (const Fr *)(ws + off_part), nb, (Fr *)(ws + off_sum), ns + 1);
-    MI_CHECK_HIP(ctx, hipGetLastError());
+    MI_TRY(mi_launch64(ctx, k_verify_combine_scalars, (size_t)nb * (ns + 1) * 64, (const Fr *)(ws + off_scal), ns, (const Fr *)(ws + off_r),
+                       nc > 1 ? (const Fr *)(ws + off_fold) : nullptr, nc, n, nb, (Fr *)(ws + off_part), (Fr *)(ws + off_rc), (Fr *)(ws + off_rrep)));
+    MI_TRY(mi_launch64(ctx, k_verify_combine_reduce, ns + 1, (const Fr *)(ws + off_part), nb, (Fr *)(ws + off_sum), ns + 1));
     VerifyCombinedSums sums{};
     MI_CHECK_HIP(ctx, hipMemcpyAsync(&sums.s, ws + off_sum + (size_t)ns * sizeof(Fr), sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
     // ---- the MSMs: their number does not depend on n
     const G1Aff inf{Fp::zero(), Fp::zero()};
-    auto msm = [&](const void *bases, size_t off_scalars, size_t count, uint32_t msm_flags, G1Aff *out) -> int32_t {
-        mi_g1_jac j;
-        MI_TRY(mi_msm_g1_dev(ctx, (const mi_g1_affine *)bases, (const mi_fr *)(ws + off_scalars), count, msm_flags, &j));
-        *out = affine_of(j);
-        return MI_OK;
-    };
     std::vector<G1Aff> ck(nc, inf);
     sums.k = sums.c = sums.pok = inf;
     sums.ck = ck.data();
-    if (ns) MI_TRY(msm(vk->k_dev, off_sum, ns, 0, &sums.k));
-    MI_TRY(msm(ws + off_krs, off_r, n, MI_MSM_SCALARS_CANONICAL, &sums.krs));
+    if (ns) MI_TRY(mi_verify_msm(ctx, vk->k_dev, ws + off_sum, ns, 0, &sums.k));
+    MI_TRY(mi_verify_msm(ctx, ws + off_krs, ws + off_r, n, MI_MSM_SCALARS_CANONICAL, &sums.krs));
     if (nc) {
-        MI_TRY(msm(ws + off_cm, off_rrep, n * nc, MI_MSM_SCALARS_CANONICAL, &sums.c));
-        MI_TRY(msm(ws + off_pok, off_r, n, MI_MSM_SCALARS_CANONICAL, &sums.pok));
-        for (u32 k = 0; k < nc; k++) MI_TRY(msm(ws + off_cm + (size_t)k * n * sizeof(G1Aff), off_rc + (size_t)k * n * sizeof(Fr), n, 0, &ck[k]));
+        MI_TRY(mi_verify_msm(ctx, ws + off_cm, ws + off_rrep, n * nc, MI_MSM_SCALARS_CANONICAL, &sums.c));
+        MI_TRY(mi_verify_msm(ctx, ws + off_pok, ws + off_r, n, MI_MSM_SCALARS_CANONICAL, &sums.pok));
+        for (u32 k = 0; k < nc; k++) MI_TRY(mi_verify_msm(ctx, (G1Aff *)(ws + off_cm) + (size_t)k * n, (Fr *)(ws + off_rc) + (size_t)k * n, n, 0, &ck[k]));
     }
 
     // ---- the tail pairs, r_i Ar_i, the Miller loops, the two products, their final exponentiations, the verdict
-    verify_combined_assemble(kref, vk->alpha1, vk->beta2, sums, &P[n], &Q[n]);
+    verify_combined_assemble(st.key, vk->alpha1, vk->beta2, sums, &P[n], &Q[n]);
     MI_TRY(up(off_p + n * sizeof(G1Aff), &P[n], np * sizeof(G1Aff)));
     MI_TRY(up(off_q + n * sizeof(G2Aff), &Q[n], np * sizeof(G2Aff)));
-    hipLaunchKernelGGL(k_g1_scale128, dim3(grid64(n)), dim3(64), 0, ctx->stream, (const G1Aff *)(ws + off_p), (const u32 *)(ws + off_r), 8u,
-                       (G1Aff *)(ws + off_p), n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
+    MI_TRY(mi_launch64(ctx, k_g1_scale128, n, (const G1Aff *)(ws + off_p), (const u32 *)(ws + off_r), 8u, (G1Aff *)(ws + off_p), n));
     Fp12 *ml = (Fp12 *)(ws + off_ml), *res = (Fp12 *)(ws + off_res);
     MI_TRY(mi_pairing_enqueue(ctx, (const G1Aff *)(ws + off_p), (const G2Aff *)(ws + off_q), n + np, ml, false));
     MI_TRY(fp12_product_enqueue(ctx, ml, n + MI_VERIFY_GROTH_PAIRS, (Fp12 *)(ws + off_t0), (Fp12 *)(ws + off_t1), &res[0]));
     if (nc) MI_TRY(fp12_product_enqueue(ctx, ml + n + MI_VERIFY_GROTH_PAIRS, nc + 1, (Fp12 *)(ws + off_t0), (Fp12 *)(ws + off_t1), &res[1]));
     MI_TRY(mi_final_exp_enqueue(ctx, res, nc ? 2 : 1));
-    hipLaunchKernelGGL(k_verify_combined_judge, dim3(1), dim3(64), 0, ctx->stream, (const Fp12 *)res, nc ? 1u : 0u, (uint8_t *)(ws + off_vd));
-    MI_CHECK_HIP(ctx, hipGetLastError());
+    MI_TRY(mi_launch64(ctx, k_verify_combined_judge, 64, (const Fp12 *)res, nc ? 1u : 0u, (uint8_t *)(ws + off_vd)));
     MI_CHECK_HIP(ctx, hipMemcpyAsync(verdict, ws + off_vd, 1, hipMemcpyDeviceToHost, ctx->stream));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MI_OK;
@@ -274,16 +237,14 @@ int32_t mi_groth16_verify_combined(mi_ctx *ctx, const mi_vk *vk, const mi_verify
 // ---------------------------------------------------------------- debug surface (include/mi355x_groth16_debug.h)
 int32_t mi_debug_fp12_product_dev(mi_ctx *ctx, const mi_fp *x_dev, size_t n, mi_fp *out_dev) {
     if (!ctx || !x_dev || !out_dev || n == 0 || n > ((size_t)1 << 24) + MI_VERIFY_GROTH_PAIRS) return MI_EINVAL;
-    const size_t lvl0 = product_level(n), off_t1 = up256(lvl0 * sizeof(Fp12));
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], off_t1 + up256(product_level(lvl0) * sizeof(Fp12))));
+    WsCut cut;
+    const size_t lvl0 = product_level(n), off_t0 = cut.take(lvl0 * sizeof(Fp12)), off_t1 = cut.take(product_level(lvl0) * sizeof(Fp12));
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], cut.total));
     char *ws = (char *)ctx->ws[WS_VERIFY].p;
-    return fp12_product_enqueue(ctx, (const Fp12 *)x_dev, n, (Fp12 *)ws, (Fp12 *)(ws + off_t1), (Fp12 *)out_dev);
+    return fp12_product_enqueue(ctx, (const Fp12 *)x_dev, n, (Fp12 *)(ws + off_t0), (Fp12 *)(ws + off_t1), (Fp12 *)out_dev);
 }
 int32_t mi_debug_g1_scale128_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, const uint64_t *k_dev, size_t n, mi_g1_affine *out_dev) {
     if (!ctx || ((!p_dev || !k_dev || !out_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
-    if (!n) return MI_OK;
-    hipLaunchKernelGGL(k_g1_scale128, dim3(grid64(n)), dim3(64), 0, ctx->stream, (const G1Aff *)p_dev, (const u32 *)k_dev, 4u, (G1Aff *)out_dev, n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    return MI_OK;
+    return mi_launch64(ctx, k_g1_scale128, n, (const G1Aff *)p_dev, (const u32 *)k_dev, 4u, (G1Aff *)out_dev, n);
 }
 }

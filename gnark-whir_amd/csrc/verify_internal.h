@@ -1,5 +1,6 @@
-// What verify.hip, verify_bytes.hip and verify_combined.hip share (not part of the C-ABI): the resident key, the body that judges a batch
-// proof by proof, the body that judges it with one verdict, and the launches of verify.hip's kernels that the latter reuses.
+// What verify.hip, verify_bytes.hip and verify_combined.hip share (not part of the C-ABI): the resident key, the opening of a batch
+// (mi_verify_open: argument checks, proof references, the VerifyStage of pairing_ops.cuh), the two bodies that judge it, the launches of
+// verify.hip's kernels that the combined body reuses, and three helpers: WsCut (a workspace's layout), mi_launch64, mi_verify_msm.
 #pragma once
 #include "ctx.h"
 #include "../../include/mi355x_groth16_verify.h"
@@ -20,11 +21,14 @@ struct mi_vk {
     std::vector<uint32_t> pc_off, pc_idx;
 };
 
-// mi_groth16_verify_batch's body (verify.hip).  decode_malformed (may be null): n bytes; a non-zero byte makes proof i malformed before
-// any of its words is read -- what mi_groth16_verify_bytes_batch knows from decoding.
+// How both bodies start: the checks of ctx, vk, in, n and the pointers of every proof (messages under `who`, "verify: " or
+// "verify combined: "; has_verdict = the caller's verdict pointer passes its own rule), then *st over the proofs' references.
+// decode_malformed (may be null): n bytes; a non-zero byte makes proof i malformed before any of its words is read (verify_bytes.hip).
+int32_t mi_verify_open(mi_ctx *ctx, const char *who, const mi_vk *vk, const mi_verify_input *in, size_t n, bool has_verdict,
+                       const uint8_t *decode_malformed, VerifyStage *st);
+// mi_groth16_verify_batch's body (verify.hip)
 int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts, const uint8_t *decode_malformed);
-
-// mi_groth16_verify_combined's body (verify_combined.hip): one verdict for the batch; decode_malformed as above.  seed may be null.
+// mi_groth16_verify_combined's body (verify_combined.hip): one verdict for the batch.  seed may be null.
 int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdict,
                                uint64_t *first_malformed, const uint8_t *decode_malformed);
 // verify.hip's kernels for the other translation units, enqueued on ctx->stream: Miller values of n pairs on the device (then, with
@@ -33,6 +37,18 @@ int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_inp
 int32_t mi_final_exp_enqueue(mi_ctx *ctx, Fp12 *io_dev, size_t n);
 int32_t mi_pairing_enqueue(mi_ctx *ctx, const G1Aff *p_dev, const G2Aff *q_dev, size_t n, Fp12 *gt_dev, bool final_exp);
 int32_t mi_verify_g2_check_enqueue(mi_ctx *ctx, const G2Aff *q_dev, u32 stride, uint8_t *flags_dev, size_t n);
+// mi_msm_g1_dev (msm.hip) over bases and scalars on the device; *out affine, (0, 0) for infinity
+int32_t mi_verify_msm(mi_ctx *ctx, const void *bases_dev, const void *scalars_dev, size_t count, uint32_t msm_flags, G1Aff *out);
 
-inline unsigned grid64(size_t n) { return (unsigned)((n + 63) / 64); }
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+// The layout of a workspace: regions in the order they are taken, each at a multiple of 256 bytes; total is what to reserve
+struct WsCut {
+    size_t total = 0;
+    size_t take(size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; }
+};
+// k over `lanes` lanes, 64 per workgroup, on ctx->stream, and the one checked hipGetLastError of a launch; no lane, no launch
+template <class K, class... A> int32_t mi_launch64(mi_ctx *ctx, K k, size_t lanes, A... args) {
+    if (!lanes) return MI_OK;
+    hipLaunchKernelGGL(k, dim3(mi_blocks_of(lanes, 64)), dim3(64), 0, ctx->stream, args...);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}

@@ -33,7 +33,7 @@ int emu_verify_pairs(const void *p, const void *q, unsigned n_ped, const void *e
     for (unsigned i = 0; i < MI_VERIFY_GROTH_PAIRS + n_ped; i++) pairing_miller_loop(&ml[i], (const G1Aff *)p + i, (const G2Aff *)q + i);
     return verify_judge(ml, n_ped, (const Fp12 *)e_alpha_beta, malformed != 0);
 }
-// One whole proof the way verify.hip's verify_run judges it, host half included: verify_well_formed, the MSM of kSum's scalar part
+// One whole proof the way verify.hip's mi_verify_run judges it, host half included: the VerifyStage, the MSM of kSum's scalar part
 // done naively here (the device's runs through msm.hip), verify_assemble, the Bs check of k_verify_g2_check, the Miller loops,
 // verify_judge.  k: nb_public + nc points; ped: 2 nc twist points (G, GSigmaNeg per commitment); proof: Ar | Bs | Krs; the other
 // pointers as mi_verify_input (null where the header allows it).  Returns the verdict, -1 for counts out of range.
@@ -42,26 +42,24 @@ int emu_verify_assemble(const void *k, const void *gamma2, const void *delta2, c
                         const void *commitment_values, const void *fold_challenge) {
     if (nb_public == 0 || nc > 16) return -1;
     const G1Aff *kk = (const G1Aff *)k;
-    const unsigned n_pub = nb_public - 1, np = verify_pairs_per_proof(nc);
-    const VerifyKeyRef vk{kk, (const G2Aff *)gamma2, (const G2Aff *)delta2, (const G2Aff *)ped, n_pub, nc};
+    const unsigned np = verify_pairs_per_proof(nc);
+    const VerifyKeyRef vk{kk, (const G2Aff *)gamma2, (const G2Aff *)delta2, (const G2Aff *)ped, nb_public - 1, nc};
     const char *raw = (const char *)proof;
     const VerifyProofRef in{(const G1Aff *)raw, (const G2Aff *)(raw + sizeof(G1Aff)), (const G1Aff *)(raw + sizeof(G1Aff) + sizeof(G2Aff)),
                             (const G1Aff *)commitments, (const G1Aff *)pok, (const Fr *)public_inputs, (const Fr *)commitment_values,
                             (const Fr *)fold_challenge};
-    bool malformed = !verify_well_formed(vk, in);
+    VerifyStage st(vk, {in}, nullptr);   // a batch of one, staged as mi_verify_run stages it: the flag and the row of scalars
     G1X msm = G1X::inf();
-    if (!malformed)
-        for (unsigned i = 0; i < n_pub + nc; i++) {
-            const Fr s = i < n_pub ? in.public_inputs[i] : in.commitment_values[i - n_pub];
-            xyzz_add(msm, xyzz_mul_256(G1X::from_affine(kk[1 + i]), fe_from_mont(s).l));
-        }
+    if (!st.flags[0])
+        for (unsigned i = 0; i < st.ns; i++) xyzz_add(msm, xyzz_mul_256(G1X::from_affine(kk[1 + i]), fe_from_mont(st.scal[i]).l));
     G1Aff p[MI_VERIFY_GROTH_PAIRS + 17];
     G2Aff q[MI_VERIFY_GROTH_PAIRS + 17];
-    verify_assemble(vk, in, !malformed, xyzz_to_affine(msm), p, q);
-    if (!g2_in_subgroup(&q[0])) malformed = true;
+    verify_assemble(vk, in, !st.flags[0], xyzz_to_affine(msm), p, q);
+    const uint8_t off_torsion = !g2_in_subgroup(&q[0]);
+    st.merge(&off_torsion);
     Fp12 ml[MI_VERIFY_GROTH_PAIRS + 17];
     for (unsigned i = 0; i < np; i++) pairing_miller_loop(&ml[i], &p[i], &q[i]);
-    return verify_judge(ml, np - MI_VERIFY_GROTH_PAIRS, (const Fp12 *)e_alpha_beta, malformed);
+    return verify_judge(ml, np - MI_VERIFY_GROTH_PAIRS, (const Fp12 *)e_alpha_beta, st.flags[0] != 0);
 }
 int emu_g1_reduced(const void *p) { return g1_reduced(*(const G1Aff *)p) ? 1 : 0; }
 int emu_g2_reduced(const void *q) { return g2_reduced(*(const G2Aff *)q) ? 1 : 0; }

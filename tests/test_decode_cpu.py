@@ -290,3 +290,16 @@ def test_mutated_and_truncated_bytes_never_trip_a_sanitizer():
     assert res.returncode == 0 and not res.stderr.strip(), f"rc {res.returncode}\n{res.stdout[-2000:]}\n{res.stderr[-6000:]}"
     accepted, refused = (int(x) for x in res.stdout.split()[-2:])
     assert accepted > 50 and refused > 1000
+
+
+def test_the_staged_batch_of_the_verifier_never_trips_a_sanitizer():
+    """tests/cpp/verify_stage_asan.cpp, its own main, -fsanitize=address,undefined -DMI_CHECK_NOWRAP on the host: VerifyStage
+    (csrc/pairing_ops.cuh) over exactly-sized heap arrays -- four keys, batches of 0, 1 and 3, four variants each: null optional
+    pointers, proofs flagged by decode_malformed with every pointer null, words that are not reduced -- with the flags, the first
+    flagged index and every scalar row checked inside the program"""
+    pkg = os.path.join(ROOT, "gnark-whir_amd")
+    subprocess.check_call(["make", "-C", pkg, "-s", "sanitize-stage"])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    res = subprocess.run([os.path.join(pkg, "build", "verify_stage_asan")], capture_output=True, text=True, env=env, timeout=300)
+    assert res.returncode == 0 and not res.stderr.strip(), f"rc {res.returncode}\n{res.stdout[-2000:]}\n{res.stderr[-6000:]}"
+    assert int(res.stdout.split()[-1]) == 4 * 3 * 4

@@ -4,6 +4,10 @@ import ctypes as C
 import numpy as np
 import pytest
 import cref
+import bytes_cases as BC
+import verify_cases as V
+import verify_combine_ref as CR
+import verify_forge as F
 from helpers import *
 from gpu_common import load_binding
 
@@ -51,6 +55,64 @@ def test_prove_reports_injected_failures_and_recovers():
         assert B.proof_write(c.prove(pkh, W, a, b, cc, r, s)[0]["raw"]) == want
     c.pk_free(pkh)
     c.close()
+
+
+# checked HIP calls that can fail in one call of n = 2, on a fresh context in this order, at the commit before the verifier's three
+# entry points got one staged batch: the sweep below must not find more
+VERIFY_STEPS_BEFORE = {"verify_batch": 57, "verify_combined": 145, "verify_bytes_batch": 68, "verify_bytes_combined": 156}
+
+
+def test_verify_reports_injected_failures_and_recovers():
+    """the four batch entry points of the verifier over two honest proofs of a forged key with one commitment (its values and challenge
+    are the hashes, so the same proof serves the struct and the bytes calls): the k-th checked HIP call is made to fail for k = 1, 2, ...
+    until the call succeeds.  Every failing call reports MI_EHIP or MI_ENOMEM and a message, the first call without an injection gives
+    the honest verdicts, and the same batch with proof 1's Krs off by one gets VERIFY_PAIRING at index 1 (as the ONE verdict of the
+    combined calls).  Failing steps per call at the commit before (VERIFY_STEPS_BEFORE): verify_batch 57, verify_combined 145,
+    verify_bytes_batch 68, verify_bytes_combined 156; the sweep stops a call at twice that many."""
+    B = load_binding()
+    c = B.Context(0)
+    key = F.forge_key(3, 1)
+    vkh = c.vk_load(*V.vk_arrays(key["vk"]))
+    good = BC.hashed_honest(key, 4100)
+    bad = CR.shift_groth(key, good, 1)
+    assert F.verdict_in_exponent(key, good) == B.VERIFY_OK and F.verdict_in_exponent(key, bad) == B.VERIFY_PAIRING
+    pub = F.verify_input(good)["public_inputs"]
+    structs = {id(x): F.verify_input(x) for x in (good, bad)}
+    encoded = {id(x): (BC.proof_bytes_of(x), pub) for x in (good, bad)}
+    calls = {"verify_batch": lambda cs: list(vkh.verify_batch([structs[id(x)] for x in cs])),
+             "verify_combined": lambda cs: vkh.verify_combined([structs[id(x)] for x in cs], CR.SEED_A),
+             "verify_bytes_batch": lambda cs: list(vkh.verify_bytes_batch([encoded[id(x)] for x in cs])),
+             "verify_bytes_combined": lambda cs: vkh.verify_bytes_combined([encoded[id(x)] for x in cs], CR.SEED_A)}
+    honest = {name: ([B.VERIFY_OK] * 2 if "combined" not in name else (B.VERIFY_OK, 2)) for name in calls}
+    tampered = {name: ([B.VERIFY_OK, B.VERIFY_PAIRING] if "combined" not in name else (B.VERIFY_PAIRING, 2)) for name in calls}
+    steps = {}
+    try:
+        for name, call in calls.items():
+            for nth in range(1, 2 * VERIFY_STEPS_BEFORE[name] + 2):
+                assert c.lib.mi_debug_inject_hip_failure(nth) == 0
+                try:
+                    got = call([good, good])
+                except B.MiError as e:
+                    got = None
+                    msg = str(e)
+                finally:
+                    c.lib.mi_debug_inject_hip_failure(0)
+                c.sync()
+                if got is not None:          # nth is past the last checked call
+                    assert got == honest[name], (name, nth)
+                    break
+                rc, _, text = msg.partition(": ")
+                assert rc in ("rc=-2", "rc=-3") and text.strip(), (name, nth, msg)
+            else:
+                pytest.fail(f"{name} still fails with the injection at step {nth}")
+            steps[name] = nth - 1
+            assert call([good, good]) == honest[name], name
+            assert call([good, bad]) == tampered[name], name
+        print("failing steps per call:", steps)
+        assert all(steps[name] <= VERIFY_STEPS_BEFORE[name] for name in calls), steps
+    finally:
+        vkh.free()
+        c.close()
 
 
 def test_pool_rejects_second_waiter_and_unknown_ticket():

@@ -294,6 +294,43 @@ def test_batch_of_distinct_forged_proofs(forged_vk, shape):
         assert list(vkh.verify_batch(inputs[70 - n:])) == want[70 - n:], n
 
 
+@pytest.mark.parametrize("entry", ["verify", "verify combined"])
+def test_refusal_messages_are_the_same_words_under_each_entry_point(ctx, forged_vk, entry):
+    """mi_groth16_verify_batch and mi_groth16_verify_combined over n = 2 proofs of a key with 1 public input and 2 commitments: a null
+    vk, input or verdict, n = 2^24 + 1 and each optional pointer left out of proof 1 are refused with MI_EINVAL and the exact message,
+    under the entry point's own prefix, and a refusal writes neither a verdict nor first_malformed"""
+    key = F.forge_key(2, 2)
+    vkh = forged_vk(key)
+    lib = ctx.lib
+    inp = F.verify_input(F.honest(key, 77))
+    assert set(inp) == {"raw", "public_inputs", "commitments", "pok", "commitment_values", "fold_challenge"}
+    arr, keep = vkh._inputs([inp, inp])
+    out = np.full(2, 255, np.uint8)
+    first = C.c_uint64(77)
+    vd = out.ctypes.data_as(C.c_void_p)
+    if entry == "verify":
+        call = lambda vk, a, n, v: lib.mi_groth16_verify_batch(ctx.h, vk, a, C.c_size_t(n), v)
+    else:
+        call = lambda vk, a, n, v: lib.mi_groth16_verify_combined(ctx.h, vk, a, C.c_size_t(n), bytes(32), v, C.byref(first))
+
+    def refused(message, vk, a, n, v):
+        assert call(vk, a, n, v) == -1, message
+        assert lib.mi_last_error(ctx.h).decode() == f"{entry}: {message}"
+        assert out.tolist() == [255, 255] and first.value == 77, message
+
+    refused("null vk, input or verdict pointer", None, arr, 2, vd)
+    refused("null vk, input or verdict pointer", vkh.h, None, 2, vd)
+    refused("more than 2^24 proofs in one batch", vkh.h, arr, (1 << 24) + 1, vd)
+    refused("null vk, input or verdict pointer", vkh.h, arr, 2, None)
+    cv_null = "commitments, pok or commitment_values is null"
+    for name, message in (("commitments", cv_null), ("public_inputs", "public_inputs is null"), ("pok", cv_null),
+                          ("fold_challenge", "fold_challenge is null with more than one commitment"), ("commitment_values", cv_null)):
+        one_out, keep1 = vkh._inputs([inp, {k: x for k, x in inp.items() if k != name}])
+        refused(message, vkh.h, one_out, 2, vd)
+    assert call(vkh.h, arr, 2, vd) == 0
+    assert (out.tolist() == [R.OK, R.OK]) if entry == "verify" else (out[0], first.value) == (R.OK, 2)
+
+
 def test_vk_load_asks_for_reduced_words_and_takes_infinite_k(ctx):
     B = load_binding()
     key = F.forge_key(3, 1)
