@@ -19,7 +19,7 @@ EXPORTS = [
     "mi_ntt", "mi_ntt_dev", "mi_compute_h", "mi_compute_h_dev", "mi_msm_g1", "mi_msm_g1_dev", "mi_msm_g2",
     "mi_msm_g2_dev", "mi_groth16_prove", "mi_groth16_prove_dev", "mi_get_stats", "mi_g1_compress",
     "mi_g2_compress", "mi_proof_write", "mi_g1_sum", "mi_g2_sum", "mi_gen_scalars_dev", "mi_gen_g1_dev",
-    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_debug_decode_g1_dev", "mi_debug_decode_g2_dev", "mi_debug_hash_to_field_dev", "mi_debug_fp12_product_dev", "mi_debug_g1_scale128_dev", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
+    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_debug_decode_g1_dev", "mi_debug_decode_g2_dev", "mi_debug_hash_to_field_dev", "mi_debug_fp12_product_dev", "mi_debug_g1_scale128_dev", "mi_debug_g1_sum_tree_dev", "mi_debug_locate_points_dev", "mi_debug_locate_colsums_dev", "mi_debug_set_locate_round_nodes", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
     "mi_dev_alloc", "mi_dev_free", "mi_dev_upload", "mi_dev_download", "mi_dev_sync",
     "mi_msm_precompute_g1_dev", "mi_msm_precompute_g2_dev", "mi_msm_g1_fixed_dev", "mi_msm_g2_fixed_dev", "mi_msm_table_to_rprime_g1_dev", "mi_msm_table_to_rprime_g2_dev", "mi_pk_table_plan",
     "mi_batch_scalar_mul_g1", "mi_batch_scalar_mul_g1_dev", "mi_batch_scalar_mul_g2", "mi_batch_scalar_mul_g2_dev",
@@ -53,6 +53,8 @@ PAIRING_FINAL_EXP = 1
 VERIFY_BYTES_EXPORTS = ["mi_vk_set_public_committed", "mi_groth16_verify_bytes", "mi_groth16_verify_bytes_batch", "mi_proof_read", "mi_hash_to_field"]
 # include/mi355x_groth16_verify_combined.h (one verdict for a batch: the random linear combination of the proofs' equations)
 VERIFY_COMBINED_EXPORTS = ["mi_groth16_verify_combined", "mi_groth16_verify_bytes_combined"]
+# include/mi355x_groth16_verify_locate.h (one verdict per proof: the combined test on a tree of subsets, descending into the ones that fail)
+VERIFY_LOCATE_EXPORTS = ["mi_groth16_verify_locate", "mi_groth16_verify_bytes_locate"]
 
 
 class PkDesc(C.Structure):
@@ -176,6 +178,13 @@ class VerifyInput(C.Structure):
 
 class VerifyBytesInput(C.Structure):
     _fields_ = [("proof", C.c_void_p), ("proof_len", C.c_size_t), ("public_inputs", C.c_void_p)]
+
+
+class VerifyLocateStats(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("nodes_tested", C.c_uint64), ("judged_alone", C.c_uint64), ("malformed", C.c_uint64), ("rejected", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class Bsb22Input(C.Structure):
@@ -645,6 +654,62 @@ class Context:
         finally:
             for b in (dp, dk, do): b.free()
 
+    def g1_sum_tree(self, pts):
+        """mi_debug_g1_sum_tree_dev: (n, 8) G1 points -> every level above them of the sum tree of fan-in 8, level 1 first"""
+        pts = _u64(pts).reshape(-1, 8); n = pts.shape[0]
+        m, total = n, 0
+        while True:
+            m = (m + 7) // 8; total += m
+            if m <= 1:
+                break
+        dp = self.to_dev(pts); do = self.alloc(64 * total)
+        try:
+            self._ck(self.lib.mi_debug_g1_sum_tree_dev(self.h, _p(dp.ptr), C.c_size_t(n), _p(do.ptr)))
+            self.sync()
+            return do.download((total, 8))
+        finally:
+            for b in (dp, do): b.free()
+
+    def locate_points(self, rs, krs, cm=None, pok=None, fold=None):
+        """mi_debug_locate_points_dev: n plain integers below 2^128, (n, 8) Krs, (n, nc, 8) commitments, (n, 8) pok, (n, 4) fold challenges
+        -> (arrays, n, 8): r Krs | r sum_k C_k | r pok | (r c^k) C_k per k (the last with nc > 1 only)"""
+        krs = _u64(krs).reshape(-1, 8); n = krs.shape[0]
+        nc = 0 if cm is None else _u64(cm).reshape(n, -1, 8).shape[1]
+        na = 1 + (2 if nc else 0) + (nc if nc > 1 else 0)
+        kk = np.array([[int(k) & (1 << 64) - 1, int(k) >> 64] for k in rs], np.uint64)
+        bufs = [self.to_dev(kk), self.to_dev(krs), self.to_dev(_u64(cm)) if nc else None, self.to_dev(_u64(pok)) if nc else None,
+                self.to_dev(_u64(fold)) if nc > 1 else None, self.alloc(64 * na * n)]
+        try:
+            ptr = [_p(b.ptr) if b else None for b in bufs]
+            self._ck(self.lib.mi_debug_locate_points_dev(self.h, ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], C.c_uint32(nc), C.c_size_t(n), ptr[5]))
+            self.sync()
+            return bufs[5].download((na, n, 8))
+        finally:
+            for b in bufs:
+                if b: b.free()
+
+    def locate_colsums(self, scal, rs, level, nodes):
+        """mi_debug_locate_colsums_dev: (n, ns, 4) Montgomery scalars, n plain integers below 2^128, the nodes of one level of the tree over
+        n proofs -> (m, ns + 1, 4): per node the sums of r_i scal[i, j] over its proofs, the last column the sum of the r_i"""
+        n = len(rs)
+        scal = _u64(scal).reshape(n, -1, 4); ns = scal.shape[1]
+        rr = np.zeros((n, 4), np.uint64)
+        rr[:, 0] = [int(k) & (1 << 64) - 1 for k in rs]; rr[:, 1] = [int(k) >> 64 for k in rs]
+        nd = np.ascontiguousarray(nodes, np.uint32); m = len(nd)
+        bufs = [self.to_dev(scal) if ns else None, self.to_dev(rr), self.to_dev(nd), self.alloc(32 * m * (ns + 1))]
+        try:
+            self._ck(self.lib.mi_debug_locate_colsums_dev(self.h, _p(bufs[0].ptr) if ns else None, C.c_uint32(ns), _p(bufs[1].ptr), C.c_size_t(n),
+                                                          C.c_uint32(level), _p(bufs[2].ptr), C.c_size_t(m), _p(bufs[3].ptr)))
+            self.sync()
+            return bufs[3].download((m, ns + 1, 4))
+        finally:
+            for b in bufs:
+                if b: b.free()
+
+    def set_locate_round_nodes(self, cap=0):
+        """mi_debug_set_locate_round_nodes: the node budget of a round of verify_locate's descent; 0 = the default"""
+        self._ck(self.lib.mi_debug_set_locate_round_nodes(self.h, C.c_uint32(cap)))
+
     def decode_points(self, enc: bytes, g2=False):
         """mi_debug_decode_g1_dev / _g2_dev over host bytes: n encodings of 32 (64) bytes -> ((n, 8) or (n, 16) uint64, (n,) uint8 malformed)"""
         w = 64 if g2 else 32
@@ -742,6 +807,21 @@ class VerifyingKey:
         arr, keep = self._bytes_inputs(proofs); v = C.c_uint8(255); first = C.c_uint64(1 << 63)
         self.ctx._ck(self.ctx.lib.mi_groth16_verify_bytes_combined(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), seed, C.byref(v), C.byref(first)))
         return int(v.value), int(first.value)
+
+    # ---- one verdict per proof at the combined test's price (include/mi355x_groth16_verify_locate.h)
+    def verify_locate(self, proofs, seed=None):
+        """mi_groth16_verify_locate: proofs as verify_batch takes them, seed as verify_combined -> (verdicts (n,) uint8, stats dict)"""
+        assert seed is None or len(seed) == 32
+        arr, keep = self._inputs(list(proofs)); out = np.full(len(arr), 255, np.uint8); st = VerifyLocateStats()
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_locate(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), seed, _p(out), C.byref(st)))
+        return out, st.as_dict()
+
+    def verify_bytes_locate(self, proofs, seed=None):
+        """mi_groth16_verify_bytes_locate: proofs as verify_bytes_batch takes them -> (verdicts, stats dict)"""
+        assert seed is None or len(seed) == 32
+        arr, keep = self._bytes_inputs(proofs); out = np.full(len(arr), 255, np.uint8); st = VerifyLocateStats()
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_bytes_locate(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), seed, _p(out), C.byref(st)))
+        return out, st.as_dict()
 
     # ---- from a proof's bytes (include/mi355x_groth16_verify_bytes.h)
     def set_public_committed(self, lists):

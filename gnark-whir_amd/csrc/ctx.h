@@ -40,12 +40,13 @@ enum {
     WS_VERIFY_BYTES = 15,  // verify_bytes.hip: proof bytes, lists, decoded points, flags, hashes of a batch           main
     WS_PROVE_IN = 16,      // prove.hip / group.hip: W (+ a, b, c) of a prove over host inputs           filled on copy_stream
     WS_B_WIRES = 17,       // prove.hip: W gathered to the wires that own a pk.G1.B point                msm[MSM_SLOT_B1].stream
+    WS_VERIFY_LOCATE = 18, // verify_locate.hip: the per-proof values, their trees and a round's nodes   main
     WS_POK_VALUES = 19,    // prove.hip ProveKnowledge: the committed values                             msm[MSM_SLOT_POK].stream
     WS_FB_TABLE = 20,      // fixed_base.hip: the window table of the base                               main
     WS_FB_SCALARS = 21,    // fixed_base.hip host entry point: the scalars                               main
     WS_FB_OUT = 22,        // fixed_base.hip host entry point: the points                                main
     WS_RPRIME = 23,        // msm.hip device entry point: the points in the R' packed form               main
-    WS_COUNT = 24          // 18 is free
+    WS_COUNT = 24
 };
 // mi_ctx::ev[]: every event of the context in use, what it marks and the stream that records it ("main" = ctx->stream).
 enum {
@@ -146,6 +147,7 @@ struct mi_ctx {
     std::atomic<uint64_t> dense_item_sorts{0};   // accumulations whose item size the dense-sort rule chose (msm.hip; helper threads enqueue too)
     uint64_t z_count_fused_launches = 0;   // computeH last launches that carried the count (mi_debug_get_counter: the tests' proof that the path ran)
     struct ZCountHook { bool armed = false, done = false; int slot = -1; uint32_t n = 0, c = 0; alignas(8) unsigned char shape[64]; uint32_t *C1 = nullptr; const void *h = nullptr; /* the vector whose digits were counted */ } zhook;
+    uint32_t locate_round_nodes = 0;     // mi_groth16_verify_locate's node budget per round: 0 = MI_LOCATE_ROUND_NODES (mi_debug_set_locate_round_nodes)
     uint32_t hold_accum = 0;             // prove: 1 = the wire MSMs' bucket accumulations wait for computeH (mi_debug_set_prove_schedule; measured: no gain)
 };
 

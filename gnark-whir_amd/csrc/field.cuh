@@ -350,6 +350,8 @@ MI_HD Fe<P> fe_dbl(const Fe<P> &x) { return x + x; }
 // Device: one v_mad_u64_u32 into an even-aligned 64-bit pair plus one v_addc for the carry word; the
 // operands never leave their registers (the compiler's own lowering of the row-wise CIOS spent ~350
 // v_mov per product re-aligning 64-bit pairs).  Host (tests): the same arithmetic in plain C++.
+// (No early-clobber mark is needed on acc and c HERE: both factors are read by the first instruction, before anything is written.  The
+// generated columns of mont_cols.inc chain many such pairs in one block and must mark them: tools/gen_mont_cols.py.)
 MI_HD void mac96(u64 &acc, u32 &c, u32 a, u32 b) {
 #if defined(__HIP_DEVICE_COMPILE__)
     u64 cy;

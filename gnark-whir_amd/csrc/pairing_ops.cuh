@@ -231,3 +231,142 @@ MI_HD uint8_t verify_combined_judge(const Fp12 *groth, const Fp12 *ped) {
     if (ped && !(*ped == Fp12::one())) return 2;
     return 0;
 }
+
+// ---------------------------------------------------------------- which proof (include/mi355x_groth16_verify_locate.h;
+// csrc/verify_locate.hip and tests/emu/emu_verify_locate.cpp both run this text).  The combined test is linear, so it judges any subset
+// of a batch; the subsets are the nodes of the tree k_fp12_product walks: node (l, j) covers the proofs [j 8^l, min(n, (j + 1) 8^l)),
+// level 0 is single proofs, the root is at level L = the number of product levels of n (at least 1).  What a node's test needs is
+// computed once per proof and summed up the tree: the Miller values ml_i (Fp12 product tree) and the points below (G1 sum trees).
+#define MI_LOCATE_ROUND_NODES 64   // node tests of one round, unless mi_debug_set_locate_round_nodes says otherwise
+
+// The point arrays of the G1 sum trees: 0: r Krs   then, with commitments, 1: r sum_k C_k   2: r pok   and with more than one
+// commitment 3 + k: (r c^k) C_k.  With one commitment array 1 IS (r c^0) C_0: it is not computed twice.
+MI_HD u32 verify_locate_arrays(u32 nc) { return 1 + (nc ? 2 : 0) + (nc > 1 ? nc : 0); }
+// One proof's points for the trees, out[a * stride] for array a; affine, (0, 0) = infinity in and out.  r: the coefficient, a plain
+// integer below 2^128 (0 for a malformed proof: everything comes out infinite).  cm: the proof's nc commitments; fold is read with
+// nc > 1 only.  (r c^k) is a full-width scalar: the canonical product goes through xyzz_mul_256.
+MI_OOL void verify_locate_points(const u32 r[4], const G1Aff &krs, const G1Aff *cm, const G1Aff *pok, const Fr *fold, u32 nc, G1Aff *out, size_t stride) {
+    out[0] = g1_scale128(krs, r);
+    if (!nc) return;
+    G1X sum = G1X::inf();
+    for (u32 k = 0; k < nc; k++) xyzz_madd(sum, cm[k], false);
+    out[stride] = g1_scale128(xyzz_to_affine(sum), r);
+    out[2 * stride] = g1_scale128(*pok, r);
+    if (nc == 1) return;
+    const Fr c = *fold;
+    Fr pw = fr_from_u128(r);
+    for (u32 k = 0; k < nc; k++) {
+        out[(3 + k) * stride] = xyzz_to_affine(xyzz_mul_256(G1X::from_affine(cm[k]), fe_from_mont(pw).l));
+        pw = pw * c;
+    }
+}
+// p[0] + ... + p[cnt - 1], cnt >= 1: XYZZ accumulation by the mixed addition (its doubling and cancelling branches included), one
+// inversion back to affine
+MI_OOL G1Aff g1_sum_run(const G1Aff *p, size_t cnt) {
+    G1X acc = G1X::inf();
+    for (size_t i = 0; i < cnt; i++) xyzz_madd(acc, p[i], false);
+    return xyzz_to_affine(acc);
+}
+// One equation of a node before its final exponentiation.  eq 0: the tree's value (prod ml_i over the node) times the Miller values of
+// tail pairs 0..2; eq 1 (with commitments): the product of the tail's values 3 .. np - 1.
+MI_OOL void verify_locate_node_product(Fp12 *z, const Fp12 *tree, const Fp12 *tail, u32 np, u32 eq) {
+    if (eq == 0) {
+        Fp12 f = *tree;
+        for (u32 t = 0; t < MI_VERIFY_GROTH_PAIRS; t++) { const Fp12 y = tail[t]; fp12_mul(&f, &f, &y); }
+        *z = f;
+    } else {
+        fp12_product_run(z, tail + MI_VERIFY_GROTH_PAIRS, np - MI_VERIFY_GROTH_PAIRS);
+    }
+}
+
+// The shape of the tree over n >= 1 proofs: cnt[l] nodes at level l = 0 .. L, off[l] = where level l starts in an array that keeps every level
+struct LocateTree {
+    size_t n = 0;
+    u32 L = 0;
+    std::vector<size_t> cnt, off;
+    size_t total = 0;
+    explicit LocateTree(size_t n_) : n(n_) {
+        cnt.push_back(n);
+        do cnt.push_back((cnt.back() + MI_FP12_PRODUCT_FAN_IN - 1) / MI_FP12_PRODUCT_FAN_IN); while (cnt.back() > 1);
+        L = (u32)cnt.size() - 1;
+        for (size_t c : cnt) { off.push_back(total); total += c; }
+    }
+    size_t first(u32 l, size_t j) const { return j << (3 * l); }                                  // the proofs of node (l, j): [first, end)
+    size_t end(u32 l, size_t j) const { const size_t e = (j + 1) << (3 * l); return e < n ? e : n; }
+};
+static_assert(MI_FP12_PRODUCT_FAN_IN == 8, "LocateTree shifts by 3 bits per level");
+
+struct LocateStats { uint32_t rounds = 0; uint64_t nodes_tested = 0, judged_alone = 0, malformed = 0, rejected = 0; };
+// The descent: which nodes to test next, from the answers to the last round.  flags[i] != 0: proof i is malformed (decided, 3) and
+// counts in no node.  Use: if (start()) do { pass[t] = the test of node (level, query[t]) } while (next(pass)); then suspects().
+// A round is `query`, all on `level`.  A node test only ever decides "accepted": whatever fails or cannot be told goes on as a suspect.
+struct LocatePlan {
+    LocateTree tree;
+    u32 cap;
+    std::vector<size_t> good;          // good[i] = well-formed proofs below index i (n + 1 entries)
+    u32 level = 0;                     // of `query`
+    std::vector<size_t> query;         // node indices of this round, ascending
+    std::vector<size_t> parent_end;    // query[parent_end[t - 1] .. parent_end[t]) are the children of the t-th failing node of the round before
+    std::vector<size_t> failing;       // after the last round: the failing nodes, on `level`
+    bool done_clean = false;           // the root passed, or there was nothing to test
+    LocateStats stats;
+    LocatePlan(size_t n, const uint8_t *flags, u32 cap_) : tree(n), cap(cap_ ? cap_ : MI_LOCATE_ROUND_NODES), good(n + 1, 0) {
+        for (size_t i = 0; i < n; i++) good[i + 1] = good[i] + (flags[i] ? 0 : 1);
+        stats.malformed = n - good[n];
+    }
+    size_t under(u32 l, size_t j) const { return good[tree.end(l, j)] - good[tree.first(l, j)]; }
+    bool start() {
+        if (!good[tree.n]) { done_clean = true; return false; }
+        level = tree.L;
+        query.assign(1, 0);
+        parent_end.assign(1, 1);
+        return round();
+    }
+    // pass[t] != 0: node query[t] passed
+    bool next(const uint8_t *pass) {
+        failing.clear();
+        size_t t = 0;
+        for (size_t e : parent_end) {
+            const size_t from = failing.size(), t0 = t;
+            for (; t < e; t++)
+                if (!pass[t]) failing.push_back(query[t]);
+            if (failing.size() == from && level != tree.L)     // every child of a failing node passed: all of them stay under suspicion
+                for (size_t s = t0; s < e; s++) failing.push_back(query[s]);
+        }
+        if (failing.empty()) { done_clean = true; return false; }   // the root passed
+        const u32 l = level;
+        if (l == 1) return false;
+        auto nodes_under = [&](u32 lo) {   // level-lo nodes under the failing ones
+            size_t m = 0;
+            for (size_t j : failing) m += children_end(l, j, lo) - (j << (3 * (l - lo)));
+            return m;
+        };
+        u32 lo = l - 1;
+        for (u32 c = 1; c < l; c++)
+            if (nodes_under(c) <= cap) { lo = c; break; }
+        size_t u = 0;
+        for (size_t j : failing) u += under(l, j);
+        if (u <= 2 * nodes_under(lo)) return false;   // a round that buys less than a halving
+        query.clear();
+        parent_end.clear();
+        for (size_t j : failing) {
+            for (size_t c = j << (3 * (l - lo)), e = children_end(l, j, lo); c < e; c++) query.push_back(c);
+            parent_end.push_back(query.size());
+        }
+        level = lo;
+        return round();
+    }
+    // the well-formed proofs under the failing nodes, ascending: what the per-proof body judges
+    std::vector<size_t> suspects() {
+        std::vector<size_t> out;
+        if (!done_clean)
+            for (size_t j : failing)
+                for (size_t i = tree.first(level, j); i < tree.end(level, j); i++)
+                    if (good[i + 1] != good[i]) out.push_back(i);
+        stats.judged_alone = out.size();
+        return out;
+    }
+private:
+    size_t children_end(u32 l, size_t j, u32 lo) const { const size_t e = (j + 1) << (3 * (l - lo)); return e < tree.cnt[lo] ? e : tree.cnt[lo]; }
+    bool round() { stats.rounds++; stats.nodes_tested += query.size(); return true; }
+};

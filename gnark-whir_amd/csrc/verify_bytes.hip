@@ -1,4 +1,4 @@
-// groth16.Verify from the bytes of a proof (include/mi355x_groth16_verify_bytes.h): decode and hash on the device, then one of the two
+// groth16.Verify from the bytes of a proof (include/mi355x_groth16_verify_bytes.h): decode and hash on the device, then one of the three
 // bodies of the verifier over the decoded records, and the three debug entry points over the same arithmetic.
 //
 // One batch, every launch on ctx->stream:
@@ -9,7 +9,7 @@
 //                  key's committed lists (sha256_h2f.cuh); a proof that did not decode is skipped
 //   host      the decoded records come back as mi_verify_input (verify_bytes_decode, the one front of the entry points below) and go
 //             through mi_verify_run, the body of mi_groth16_verify_batch, or for mi_groth16_verify_bytes_combined through
-//             mi_verify_combined_run (verify_combined.hip); a proof that did not decode enters either as malformed and none of its
+//             mi_verify_combined_run (verify_combined.hip), for mi_groth16_verify_bytes_locate through mi_verify_locate_run; a proof that did not decode enters either as malformed and none of its
 //             words is read.
 // Two decode kernels rather than one: a G2 lane does four times the work of a G1 lane, and in one wave the G1 lanes would wait for it.
 // Everything of a batch lives in ONE grow-only workspace (WS_VERIFY_BYTES): nothing is allocated in steady state.
@@ -181,6 +181,13 @@ int32_t mi_groth16_verify_bytes_combined(mi_ctx *ctx, const mi_vk *vk, const mi_
     Decoded d;
     MI_TRY(verify_bytes_decode(ctx, vk, in, n, verdict != nullptr, &d));
     return mi_verify_combined_run(ctx, vk, d.dec.data(), n, seed, verdict, first_malformed, d.bad.data());
+}
+
+int32_t mi_groth16_verify_bytes_locate(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, const uint8_t *seed, uint8_t *verdicts,
+                                       mi_verify_locate_stats *stats) {
+    Decoded d;
+    MI_TRY(verify_bytes_decode(ctx, vk, in, n, verdicts || !n, &d));
+    return mi_verify_locate_run(ctx, vk, d.dec.data(), n, seed, verdicts, stats, d.bad.data());
 }
 
 // ---------------------------------------------------------------- debug surface (include/mi355x_groth16_debug.h)

@@ -117,6 +117,14 @@ int32_t fp12_product_enqueue(mi_ctx *ctx, const Fp12 *x, size_t m, Fp12 *t0, Fp1
 
 }   // namespace
 
+// the two kernels for verify_locate.hip, which keeps every level of the product and scales into trees of its own
+int32_t mi_fp12_product_level_enqueue(mi_ctx *ctx, const Fp12 *x_dev, size_t m, Fp12 *out_dev, size_t m_out) {
+    return mi_launch64(ctx, k_fp12_product, m_out, x_dev, m, out_dev, m_out);
+}
+int32_t mi_g1_scale128_enqueue(mi_ctx *ctx, const G1Aff *p_dev, const u32 *k_dev, u32 stride, G1Aff *out_dev, size_t n) {
+    return mi_launch64(ctx, k_g1_scale128, n, p_dev, k_dev, stride, out_dev, n);
+}
+
 int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdict,
                                uint64_t *first_malformed, const uint8_t *decode_malformed) {
     // refused where it always was, between mi_verify_open's checks of ctx, vk, in, verdict and n and those of the proofs' pointers

@@ -1,10 +1,11 @@
-// What verify.hip, verify_bytes.hip and verify_combined.hip share (not part of the C-ABI): the resident key, the opening of a batch
-// (mi_verify_open: argument checks, proof references, the VerifyStage of pairing_ops.cuh), the two bodies that judge it, the launches of
+// What verify.hip, verify_bytes.hip, verify_combined.hip and verify_locate.hip share (not part of the C-ABI): the resident key, the opening of a batch
+// (mi_verify_open: argument checks, proof references, the VerifyStage of pairing_ops.cuh), the three bodies that judge it, the launches of
 // verify.hip's kernels that the combined body reuses, and three helpers: WsCut (a workspace's layout), mi_launch64, mi_verify_msm.
 #pragma once
 #include "ctx.h"
 #include "../../include/mi355x_groth16_verify.h"
 #include "../../include/mi355x_groth16_verify_combined.h"
+#include "../../include/mi355x_groth16_verify_locate.h"
 #include "pairing_ops.cuh"
 #include <vector>
 
@@ -31,12 +32,19 @@ int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, s
 // mi_groth16_verify_combined's body (verify_combined.hip): one verdict for the batch.  seed may be null.
 int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdict,
                                uint64_t *first_malformed, const uint8_t *decode_malformed);
+// mi_groth16_verify_locate's body (verify_locate.hip): one verdict per proof.  seed and stats may be null.
+int32_t mi_verify_locate_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdicts,
+                             mi_verify_locate_stats *stats, const uint8_t *decode_malformed);
 // verify.hip's kernels for the other translation units, enqueued on ctx->stream: Miller values of n pairs on the device (then, with
 // final_exp, f^d' in place), f^d' in place alone, and flags[i] = 1 where q[i * stride] is not a point of the r-torsion of the twist
 // (else flags[i] stays)
 int32_t mi_final_exp_enqueue(mi_ctx *ctx, Fp12 *io_dev, size_t n);
 int32_t mi_pairing_enqueue(mi_ctx *ctx, const G1Aff *p_dev, const G2Aff *q_dev, size_t n, Fp12 *gt_dev, bool final_exp);
 int32_t mi_verify_g2_check_enqueue(mi_ctx *ctx, const G2Aff *q_dev, u32 stride, uint8_t *flags_dev, size_t n);
+// verify_combined.hip's kernels the same way: one level of the Fp12 product tree (out[j] = x[8 j] x[8 j + 1] ..., m_out = ceil(m / 8)), and
+// out[i] = k_i p[i] with k_i the four words at k + i * stride
+int32_t mi_fp12_product_level_enqueue(mi_ctx *ctx, const Fp12 *x_dev, size_t m, Fp12 *out_dev, size_t m_out);
+int32_t mi_g1_scale128_enqueue(mi_ctx *ctx, const G1Aff *p_dev, const u32 *k_dev, u32 stride, G1Aff *out_dev, size_t n);
 // mi_msm_g1_dev (msm.hip) over bases and scalars on the device; *out affine, (0, 0) for infinity
 int32_t mi_verify_msm(mi_ctx *ctx, const void *bases_dev, const void *scalars_dev, size_t count, uint32_t msm_flags, G1Aff *out);
 

@@ -79,6 +79,24 @@ int32_t mi_debug_hash_to_field_dev(mi_ctx *ctx, const uint8_t *dst_dev, uint32_t
  * (0, 0) = infinity in and out.  out_dev may be p_dev.  The points must lie on the curve. */
 int32_t mi_debug_fp12_product_dev(mi_ctx *ctx, const mi_fp *x_dev, size_t n, mi_fp *out_dev);
 int32_t mi_debug_g1_scale128_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, const uint64_t *k_dev, size_t n, mi_g1_affine *out_dev);
+/* the kernels mi355x_groth16_verify_locate.h adds (csrc/verify_locate.hip), alone; the host build of the tests
+ * (tests/emu/emu_verify_locate.cpp) runs the same bodies.  Device pointers, enqueued on the context's stream, 1 <= n <= 2^24.
+ * mi_debug_g1_sum_tree_dev: levels_dev receives every level above p_dev's of the sum tree of fan-in 8 over the n affine points, level 1
+ * first: ceil(n / 8) points, then ceil of that / 8, ... down to one (n = 1: one level of one point); (0, 0) = infinity in and out.
+ * mi_debug_locate_points_dev: one lane per proof, out_dev[a * n + i] = array a of proof i: 0: r Krs; with nc > 0 1: r sum_k C_k, 2: r pok;
+ * with nc > 1 3 + k: (r c^k) C_k.  r_dev: n x 2 words as mi_debug_g1_scale128_dev's k_dev; cm_dev: n x nc points; fold_dev: n
+ * scalars, read with nc > 1 only; pok_dev and cm_dev are read with nc > 0 only.  nc <= 16.
+ * mi_debug_locate_colsums_dev: sums_dev[t * (ns + 1) + j] = sum of r_i scal_dev[i * ns + j] over the proofs i of node (level,
+ * nodes_dev[t]) of the tree over n proofs, column ns = sum of r_i; m nodes, every one below the level's count; r_dev: n canonical
+ * mi_fr records below 2^128.  Its partials live in the context's locate workspace.
+ * mi_debug_set_locate_round_nodes: the node budget of one round of mi_groth16_verify_locate's descent on this context; 0 restores the
+ * default (MI_LOCATE_ROUND_NODES).  Tests force deep descents at small n with it. */
+int32_t mi_debug_g1_sum_tree_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, size_t n, mi_g1_affine *levels_dev);
+int32_t mi_debug_locate_points_dev(mi_ctx *ctx, const uint64_t *r_dev, const mi_g1_affine *krs_dev, const mi_g1_affine *cm_dev, const mi_g1_affine *pok_dev,
+                                   const mi_fr *fold_dev, uint32_t nc, size_t n, mi_g1_affine *out_dev);
+int32_t mi_debug_locate_colsums_dev(mi_ctx *ctx, const mi_fr *scal_dev, uint32_t ns, const mi_fr *r_dev, size_t n, uint32_t level, const uint32_t *nodes_dev,
+                                    size_t m, mi_fr *sums_dev);
+int32_t mi_debug_set_locate_round_nodes(mi_ctx *ctx, uint32_t cap);
 /* random-gather throughput probe: n_threads lanes each chain `iters` dependent 64-byte gathers from a table of n_entries
  * (a power of two) 64-byte entries; scratch: 1 KiB.  The ceiling the level-1 bucket accumulation's point gathers run against. */
 int32_t mi_bench_gather_dev(mi_ctx *ctx, const void *table_dev, size_t n_entries, size_t n_threads, uint32_t iters,

@@ -25,7 +25,8 @@
  *   - A batch with at least one proof that mi_groth16_verify rejects with 1 or 2 is accepted with probability at most about 2^-128 over
  *     the seed: after the checks of verdict 3 every point lies in a group of prime order r, so each equation reads sum_i r_i d_i = 0
  *     mod r with d_i proof i's defect in the exponent, and a non-zero d_i leaves one value of r_i (of 2^128) that satisfies it.
- *   - Verdicts 1 and 2 do not say WHICH proof is at fault; mi_groth16_verify_batch does.
+ *   - Verdicts 1 and 2 do not say WHICH proof is at fault; mi_groth16_verify_batch does.  mi_groth16_verify_locate
+ *     (mi355x_groth16_verify_locate.h) names them by running this test on a tree of subsets of the batch.
  *
  * VERDICTS (MI_VERIFY_* of mi355x_groth16_verify.h), one for the whole batch, decided in the order 3, 1, 2:
  *   3  MI_VERIFY_MALFORMED  some proof is malformed by the rules of mi_groth16_verify (a word that is not reduced, a G1 point off the

@@ -2,6 +2,10 @@
 their bytes (mi_groth16_verify_bytes[_batch], csrc/verify_bytes.hip): the difference of the two is the cost of decoding and hashing.
 Beside each batch leg, the same inputs through mi_groth16_verify_combined (csrc/verify_combined.hip: one verdict for the batch, under a
 fixed seed), in the same process: the two calls ALTERNATE, one pair per run, and each gets its median and its min .. max.
+Beside each batch leg, a locate leg (mi_groth16_verify_locate, csrc/verify_locate.hip: one verdict per proof by descent): the batch with
+b = 0, 1 and 8 proofs tampered (another Krs) at seeded positions through the locate, the combined and the per-proof call, the three
+ALTERNATING, with the locate call's stats; then, for the larger batches with b = 1 and 8, the locate call under node budgets of 8, 64 and
+512 per round (mi_debug_set_locate_round_nodes): the column the default MI_LOCATE_ROUND_NODES is read from.
 
     python tools/verify_probe.py [--write profiles/verify.txt] [--batches 64,1024,16384] [--runs 5]
 
@@ -37,6 +41,8 @@ def main():
     ap.add_argument("--batches", default="64,1024,16384")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--combined-only", action="store_true", help="the batch legs time the combined call alone: for a kernel trace of it")
+    ap.add_argument("--locate-only", action="store_true", help="the batch legs time one locate call with one tampered proof alone: for a kernel trace of it")
+    ap.add_argument("--no-locate", action="store_true", help="skip the locate legs")
     args = ap.parse_args()
     B = load_binding()
     ctx = B.Context(0)
@@ -97,16 +103,69 @@ def main():
                 t = time.perf_counter(); fn(); ts.append((time.perf_counter() - t) * 1e3)
         return [(statistics.median(ts), min(ts), max(ts)) for ts in (ta, tb)]
 
+    def timed_group(fns):
+        """one warm-up call of each, then `runs` rounds through all of them, alternating -> (median, min, max) of each, ms"""
+        for fn in fns:
+            fn()
+        ts = [[] for _ in fns]
+        for _ in range(args.runs):
+            for fn, t_ in zip(fns, ts):
+                t = time.perf_counter(); fn(); t_.append((time.perf_counter() - t) * 1e3)
+        return [(statistics.median(t_), min(t_), max(t_)) for t_ in ts]
+
+    other_krs = inp["raw"].copy()
+    other_krs[24:32] = cref.gen_g1(1, 77)[0]
+    tampered = dict(inp, raw=other_krs)
+    assert vkh.verify(tampered) == B.VERIFY_PAIRING
+    seed = bytes(range(32))
+
+    def locate_leg(nb):
+        """the locate, combined and per-proof calls on the same inputs with b tampered proofs, then the node budgets"""
+        stats = B.VerifyLocateStats()
+        for b in (0, 1, 8):
+            pos = sorted(int(x) for x in np.random.default_rng(1000 + nb + b).choice(nb, b, replace=False))
+            proofs = [inp] * nb
+            for i in pos:
+                proofs[i] = tampered
+            arr, keep = vkh._inputs(proofs)
+            want = np.zeros(nb, np.uint8); want[pos] = B.VERIFY_PAIRING
+            out_l, out_b = np.full(nb, 255, np.uint8), np.full(nb, 255, np.uint8)
+            one_v = B.C.c_uint8(255)
+            lcall = lambda: ctx._ck(ctx.lib.mi_groth16_verify_locate(ctx.h, vkh.h, arr, B.C.c_size_t(nb), seed, out_l.ctypes.data_as(B.C.c_void_p), B.C.byref(stats)))
+            ccall = lambda: ctx._ck(ctx.lib.mi_groth16_verify_combined(ctx.h, vkh.h, arr, B.C.c_size_t(nb), seed, B.C.byref(one_v), None))
+            bcall = lambda: ctx._ck(ctx.lib.mi_groth16_verify_batch(ctx.h, vkh.h, arr, B.C.c_size_t(nb), out_b.ctypes.data_as(B.C.c_void_p)))
+            if args.locate_only:
+                if b == 1:
+                    emit(f"batch of {nb:6d}       locate alone, 1 tampered {timed(lcall):10.3f} ms   {stats.as_dict()}")
+                continue
+            (lms, llo, lhi), (cms, clo, chi), (bms, blo, bhi) = timed_group([lcall, ccall, bcall])
+            assert np.array_equal(out_l, want) and np.array_equal(out_b, want) and one_v.value == (B.VERIFY_PAIRING if b else B.VERIFY_OK)
+            emit(f"  locate, {b} tampered   locate {lms:10.3f} ms ({llo:.3f} .. {lhi:.3f})   combined {cms:10.3f} ms ({clo:.3f} .. {chi:.3f})   "
+                 f"per proof {bms:10.3f} ms ({blo:.3f} .. {bhi:.3f})   locate / combined {lms / cms:6.2f}   per proof / locate {bms / lms:7.1f}")
+            emit(f"                        {stats.as_dict()}")
+            if nb >= 1024 and b:
+                cols = []
+                for cap in (8, 64, 512):
+                    ctx.set_locate_round_nodes(cap)
+                    cols.append((cap, timed(lcall), stats.as_dict()))
+                    assert np.array_equal(out_l, want)
+                ctx.set_locate_round_nodes(0)
+                emit("    node budget per round: " + "   ".join(f"{cap}: {ms:9.3f} ms ({st['rounds']} rounds, {st['nodes_tested']} nodes, {st['judged_alone']} alone)"
+                                                               for cap, ms, st in cols))
+
     one, one_b = timed(lambda: vkh.verify(inp)), timed(lambda: vkh.verify_bytes(data, inp["public_inputs"]))
     emit(f"one verification      {one:10.3f} ms   from bytes {one_b:10.3f} ms   decode + hash {one_b - one:9.3f} ms")
     for nb in [int(x) for x in args.batches.split(",") if x]:
         arr, keep = vkh._inputs([inp] * nb)
         out = np.zeros(nb, np.uint8)
         call = lambda: ctx._ck(ctx.lib.mi_groth16_verify_batch(ctx.h, vkh.h, arr, nb, out.ctypes.data_as(B.C.c_void_p)))
-        seed = bytes(range(32)); one_v = B.C.c_uint8(255); first = B.C.c_uint64(0)
+        one_v = B.C.c_uint8(255); first = B.C.c_uint64(0)
         ccall = lambda: ctx._ck(ctx.lib.mi_groth16_verify_combined(ctx.h, vkh.h, arr, B.C.c_size_t(nb), seed, B.C.byref(one_v), B.C.byref(first)))
         if args.combined_only:
             emit(f"batch of {nb:6d}       combined alone {timed(ccall):10.3f} ms")
+            continue
+        if args.locate_only:
+            locate_leg(nb)
             continue
         (ms, lo, hi), (cms, clo, chi) = timed_pair(call, ccall)
         assert not out.any() and (one_v.value, first.value) == (B.VERIFY_OK, nb)
@@ -120,6 +179,8 @@ def main():
         emit(f"batch of {nb:6d}       {ms:10.3f} ms   {ms / nb:8.4f} ms per proof   from bytes {bms:10.3f} ms   decode + hash {(bms - ms) / nb:8.4f} ms per proof")
         emit(f"  alternating pairs   per proof {ms:10.3f} ms ({lo:.3f} .. {hi:.3f})   combined {cms:10.3f} ms ({clo:.3f} .. {chi:.3f})   "
                      f"{cms / nb:8.4f} ms per proof   per proof / combined {ms / cms:7.1f}")
+        if not args.no_locate:
+            locate_leg(nb)
     if args.write:
         with open(args.write, "w") as f:
             f.write("\n".join(lines) + "\n")
