@@ -46,6 +46,17 @@ int32_t mi_debug_limb29_op_dev(mi_ctx *ctx, int op, void *out_dev, const void *i
 #define MI_LAZY_IN_WORDS 24
 #define MI_LAZY_OUT_WORDS 16
 int32_t mi_debug_lazy_op_dev(mi_ctx *ctx, int op, void *out_dev, const void *in_dev, size_t n);
+/* the field arithmetic on operand shapes the compiler can see through -- literal factors, limbs that are provably zero, one value in two
+ * operand positions, results written over their inputs, chains that start at a literal (csrc/shape_ops.cuh) -- one record per lane: in_dev
+ * holds n records of MI_SHAPE_IN_WORDS u32 (x | y | u | v, eight limbs each; the curve, 29-bit and Fp12 shapes read the same words as
+ * csrc/shape_ops.cuh states), out_dev receives n of MI_SHAPE_OUT_WORDS (words a shape does not write are zero).  Every shape is a kernel of
+ * its own, so its body is compiled as its call site in the product is; the host build of the tests runs the same bodies.  shape: a
+ * generic shape g of csrc/shape_ops.cuh over Fr is g, over Fp SHG_END + g, a typed shape t is 2 SHG_END + t.  Inputs are raw Montgomery
+ * residues below the modulus (points on their curves, 29-bit limbs within the contract of csrc/field29.cuh).  No kernel has a
+ * data-dependent address or trip count.  MI_EINVAL for an unknown shape, null buffers or n > 2^24. */
+#define MI_SHAPE_IN_WORDS 32
+#define MI_SHAPE_OUT_WORDS 32
+int32_t mi_debug_field_shape_dev(mi_ctx *ctx, int shape, void *out_dev, const void *in_dev, size_t n);
 /* the pairing behind mi355x_groth16_verify.h (csrc/fp12.cuh, pairing.cuh), one record per lane; the host build of the tests
  * (tests/emu/emu_pairing.cpp) runs the same bodies.  An Fp12 / GT record is 12 x mi_fp in the tower order C0.B0.A0, C0.B0.A1, C0.B1.A0,
  * ... C1.B2.A1 (Fp2 = Fp[u]/(u^2+1), Fp6 = Fp2[v]/(v^3 - (9+u)), Fp12 = Fp6[w]/(w^2 - v)).

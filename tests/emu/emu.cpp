@@ -300,6 +300,30 @@ extern "C" int emu_lazy_op(int op, u32 *out, const u32 *in, size_t n) {
     return 0;
 }
 
+// records of shape_ops.cuh, n of them: the host twin of mi_debug_field_shape_dev (same shape numbers, same layout, one instantiation per
+// shape as on the device; every bound of the arithmetic traps)
+#include <utility>
+#include "../../gnark-whir_amd/csrc/shape_ops.cuh"
+typedef void (*emu_shape_fn)(const u32 *, u32 *);
+template <int... S>
+static emu_shape_fn emu_shape_pick(int shape, std::integer_sequence<int, S...>) {
+    static const emu_shape_fn table[] = {shape_op<S>...};
+    return table[shape];
+}
+extern "C" int emu_shape_op_end() { return SH_OP_END; }
+extern "C" int emu_shape_generic_end() { return SHG_END; }
+extern "C" int emu_field_shape(int shape, u32 *out, const u32 *in, size_t n) {
+    if (shape < 0 || shape >= SH_OP_END) return -1;
+    const emu_shape_fn f = emu_shape_pick(shape, std::make_integer_sequence<int, SH_OP_END>());
+    for (size_t i = 0; i < n; i++) {
+        u32 r[SH_IN_WORDS], o[SH_OUT_WORDS] = {};   // words a shape does not write stay zero (the device does the same)
+        memcpy(r, in + i * SH_IN_WORDS, sizeof(r));
+        f(r, o);
+        memcpy(out + i * SH_OUT_WORDS, o, sizeof(o));
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------- MSM pipeline emulation (msm_core.cuh on the host)
 #include "../../gnark-whir_amd/csrc/msm_core.cuh"
 static void excl_scan(const std::vector<u32> &in, std::vector<u32> &out) {

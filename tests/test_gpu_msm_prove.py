@@ -305,6 +305,75 @@ def test_batch_scalar_mul_vs_oracle(ctx):
     assert ctx.batch_scalar_mul(gen, sc[:0]).shape == (0, 8)
 
 
+def _bsm_scalar_pool():
+    """canonical scalars at the edges of the fixed-base walk (one table digit per byte): exactly one non-zero byte at each of the 32
+    positions (the top byte 0x30, so the value stays below r), every byte 0xFF below the top byte (top byte 0 and 0x2f), bytes that
+    alternate zero and non-zero in both phases, and 0, 1, r - 1"""
+    one_byte = [(0x30 if k == 31 else 0xFF - k) << (8 * k) for k in range(32)]
+    ff = [(1 << 248) - 1, (0x2F << 248) | ((1 << 248) - 1)]
+    alt = [sum((0x11 + 7 * k) << (8 * k) for k in range(0, 32, 2)), sum((0x2A if k == 31 else 0x13 + 5 * k) << (8 * k) for k in range(1, 32, 2))]
+    pool = one_byte + ff + alt + [0, 1, P.R_MOD - 1]
+    assert all(0 <= s < P.R_MOD for s in pool) and all(sum(1 for b in s.to_bytes(32, "little") if b) == 1 for s in one_byte)
+    assert all(b == 0xFF for s in ff for b in s.to_bytes(32, "little")[:31])
+    assert all((b != 0) == (k % 2 == ph) for ph, s in enumerate(alt) for k, b in enumerate(s.to_bytes(32, "little")))
+    return pool
+
+
+BSM_SIZES = (1, 15, 16, 17, 63, 64, 65, 1000)   # around k_xyzz_batch_to_affine's group of 16 and the wave of 64
+
+
+def _bsm_scalars(n, variant):
+    """canonical scalars of one run.  pool: the edge scalars in rotation.  zeros: the same with a whole aligned group of 16 zero
+    (rows 16 .. 31), zeros in the first and the last place of group 0, and a zero in the ragged last group where that is one lane
+    (n = 1, 17, 65).  all_zero: every scalar zero."""
+    pool = _bsm_scalar_pool()
+    if variant == "all_zero":
+        return [0] * n
+    sc = [pool[(i + n) % len(pool)] for i in range(n)]
+    if variant == "zeros":
+        for i in list(range(16, min(32, n))) + [0, min(15, n - 1)] + ([n - 1] if n % 16 == 1 else []):
+            sc[i] = 0
+    return sc
+
+
+@pytest.mark.parametrize("g2", [False, True], ids=["g1", "g2"])
+@pytest.mark.parametrize("n", BSM_SIZES)
+def test_batch_scalar_mul_at_its_edges(ctx, n, g2):
+    """the fixed-base batch scalar multiplication behind every point of a Setup key and of mi_pedersen_vk_make, at the sizes around its
+    conversion group and the wave, on scalars at the edges of its byte walk and zeros placed against the groups, for the base (0, 0), the
+    generator and a seeded point, through the host and the device entry points, against cref.batch_scalar_mul; the first and last dozen
+    rows against pyref's own scalar multiplication too.  The base (0, 0) is infinity: every multiple is (0, 0) by definition."""
+    width = 16 if g2 else 8
+    F, arr, gen = (P.F2, g2_arr, P.G2_GEN) if g2 else (P.F1, g1_arr, P.G1_GEN)
+    seeded = P.ec_mul(F, gen, 0x1D2C3B4A59687766554433221100FFEE)
+    memo = {}
+    for bname, bpt in (("infinity", None), ("generator", gen), ("seeded", seeded)):
+        base = arr([bpt])[0]
+        for variant in ("pool", "zeros", "all_zero"):
+            ints = _bsm_scalars(n, variant)
+            sc = fr_arr(ints)
+            tag = (n, "g2" if g2 else "g1", bname, variant)
+            want = cref.batch_scalar_mul(base, sc, g2=g2)
+            if bpt is None:   # the definition, whatever the oracle says
+                want = np.zeros((n, width), np.uint64)
+            rows = sorted(set(list(range(min(12, n))) + list(range(max(0, n - 12), n))))
+            for i in rows:
+                if (bname, ints[i]) not in memo:
+                    memo[(bname, ints[i])] = arr([P.ec_mul(F, bpt, ints[i])])[0]
+                assert np.array_equal(want[i], memo[(bname, ints[i])]), ("oracle differs from pyref", tag, i)
+            zero_rows = np.array([s == 0 for s in ints]) | (bpt is None)
+            assert not want[zero_rows].any() and want[~zero_rows].any(axis=1).all(), tag
+            got = ctx.batch_scalar_mul(base, sc, g2=g2)
+            assert np.array_equal(got, want), ("host entry point", tag, np.nonzero((got != want).any(axis=1))[0][:8])
+            ds = ctx.to_dev(sc); out = ctx.alloc(max(8 * width * n, 32))
+            try:
+                ctx.batch_scalar_mul_dev(base, ds.ptr, n, out.ptr, g2=g2)
+                got = out.download((n, width))
+            finally:
+                ds.free(); out.free()
+            assert np.array_equal(got, want), ("device entry point", tag, np.nonzero((got != want).any(axis=1))[0][:8])
+
+
 @pytest.mark.parametrize("log_n", [23, 25, 26])
 def test_full_size_prove_equals_composition_of_primitives(ctx, log_n):
     """BASELINE configs[1] size (N = 2^23, WHIR scalar mix), N = 2^25 and configs[2] size (2^26): the fused multi-stream
