@@ -55,6 +55,12 @@ VERIFY_BYTES_EXPORTS = ["mi_vk_set_public_committed", "mi_groth16_verify_bytes",
 VERIFY_COMBINED_EXPORTS = ["mi_groth16_verify_combined", "mi_groth16_verify_bytes_combined"]
 # include/mi355x_groth16_verify_locate.h (one verdict per proof: the combined test on a tree of subsets, descending into the ones that fail)
 VERIFY_LOCATE_EXPORTS = ["mi_groth16_verify_locate", "mi_groth16_verify_bytes_locate"]
+# include/mi355x_groth16_keyfile.h (proving keys as files: bulk point codecs, loading gnark's raw or compressed stream, writing both)
+KEYFILE_EXPORTS = ["mi_g1_decompress_dev", "mi_g2_decompress_dev", "mi_g1_compress_dev", "mi_g2_compress_dev", "mi_pk_stream_inspect", "mi_pk_load_stream",
+                   "mi_keyfile_get_stats", "mi_pk_stream_size", "mi_pk_write_dev", "mi_groth16_setup_to_stream"]
+KEYFILE_RAW, KEYFILE_COMPRESSED = 0, 1
+KEYFILE_NO_SUBGROUP_CHECK, KEYFILE_SUBGROUP_BY_R = 1, 2
+NO_BAD_INDEX = (1 << 64) - 1
 
 
 class PkDesc(C.Structure):
@@ -87,6 +93,41 @@ def pk_raw_inspect(blob: bytes):
     if load().mi_pk_raw_inspect(buf, C.c_size_t(len(blob)), C.byref(info)) != 0:
         raise MiError("mi_pk_raw_inspect: not a gnark v0.11.0 ProvingKey.WriteRawTo stream (as recalled)")
     return info
+
+
+class PedersenArrays(C.Structure):
+    _fields_ = [("basis_dev", C.c_void_p), ("basis_exp_sigma_dev", C.c_void_p), ("n", C.c_uint64)]
+
+
+class KeyfileStats(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("upload_ms", "decode_ms", "subgroup_ms", "build_ms", "total_ms")]
+
+
+def pk_stream_inspect(blob: bytes):
+    """(section offsets / counts, KEYFILE_RAW or KEYFILE_COMPRESSED) of a proving key's stream (host only); raises MiError if neither layout parses"""
+    info = PkRawInfo(); enc = C.c_uint32(); buf = (C.c_uint8 * len(blob)).from_buffer_copy(blob)
+    if load().mi_pk_stream_inspect(buf, C.c_size_t(len(blob)), C.byref(info), C.byref(enc)) != 0:
+        raise MiError("mi_pk_stream_inspect: neither a ProvingKey.WriteRawTo nor a ProvingKey.WriteTo stream (as recalled)")
+    return info, int(enc.value)
+
+
+def _pedersen_arrays(ped):
+    """[(basis device pointer, basis_exp_sigma device pointer, n)] -> the C array"""
+    arr = (PedersenArrays * max(len(ped), 1))()
+    for k, (b, s, n) in enumerate(ped):
+        arr[k].basis_dev, arr[k].basis_exp_sigma_dev, arr[k].n = (int(b) if b else None), (int(s) if s else None), int(n)
+    return arr
+
+
+def pk_stream_size(counts: dict, ped_ns=(), encoding=KEYFILE_COMPRESSED):
+    """mi_pk_stream_size: counts = nb_wires and n_g1_a, n_g1_b, n_g1_k, n_g1_z, n_g2_b"""
+    d = PkDesc()
+    for k, v in counts.items():
+        setattr(d, k, int(v))
+    n = C.c_size_t()
+    if load().mi_pk_stream_size(C.byref(d), _pedersen_arrays([(None, None, m) for m in ped_ns]), C.c_uint32(len(ped_ns)), C.c_uint32(encoding), C.byref(n)) != 0:
+        raise MiError("mi_pk_stream_size refused its arguments")
+    return int(n.value)
 
 
 class R1csMatrix(C.Structure):
@@ -543,6 +584,73 @@ class Context:
         vkd = {n: np.array(getattr(vk, n), dtype=np.uint64) for n in ("alpha1", "beta2", "gamma2", "delta2")}
         vkd["k"] = vk_k[:int(vk.n_k)].copy()
         return h, [C.c_void_p(ped[i]) for i in range(int(d.n_commitments))], vkd
+
+    # ---- proving keys as files (include/mi355x_groth16_keyfile.h)
+    def decompress_dev(self, bytes_ptr, n, out_ptr, g2=False, flags=0):
+        """mi_g1_decompress_dev / mi_g2_decompress_dev over device pointers -> (rc, lowest bad index or NO_BAD_INDEX)"""
+        first = C.c_uint64()
+        if g2:
+            rc = self.lib.mi_g2_decompress_dev(self.h, _p(bytes_ptr), C.c_size_t(n), C.c_uint32(flags), _p(out_ptr), C.byref(first))
+        else:
+            rc = self.lib.mi_g1_decompress_dev(self.h, _p(bytes_ptr), C.c_size_t(n), _p(out_ptr), C.byref(first))
+        return rc, int(first.value)
+
+    def compress_dev(self, pts_ptr, n, bytes_ptr, g2=False, encoding=KEYFILE_COMPRESSED):
+        f = self.lib.mi_g2_compress_dev if g2 else self.lib.mi_g1_compress_dev
+        self._ck(f(self.h, _p(pts_ptr), C.c_size_t(n), C.c_uint32(encoding), _p(bytes_ptr)))
+
+    def pk_load_stream(self, blob: bytes, nb_public, committed_wires=None, flags=0):
+        """a ProvingKey.WriteRawTo or ProvingKey.WriteTo stream -> (device-resident key, [Pedersen key handles]), every point checked"""
+        buf = (C.c_uint8 * len(blob)).from_buffer_copy(blob); h = C.c_void_p()
+        ped = (C.c_void_p * MAX_COMMITMENTS)(); nped = C.c_uint32()
+        cw = None if committed_wires is None or not len(committed_wires) else np.ascontiguousarray(committed_wires, dtype=np.uint32)
+        self._ck(self.lib.mi_pk_load_stream(self.h, buf, C.c_size_t(len(blob)), C.c_uint32(flags), C.c_uint32(nb_public), _p(cw),
+                                            C.c_size_t(0 if cw is None else cw.shape[0]), C.byref(h), ped, C.byref(nped)))
+        return h, [C.c_void_p(ped[i]) for i in range(nped.value)]
+
+    def pk_write_dev(self, pk: dict, ped=(), encoding=KEYFILE_COMPRESSED, cap=None):
+        """mi_pk_write_dev: pk as pk_load takes it with device_points (arrays = (device pointer, count)), ped = [(basis pointer,
+        basis_exp_sigma pointer, n)] -> the stream's bytes.  cap: the room offered (default: what mi_pk_stream_size asks for)"""
+        d = PkDesc(); d.log_n, d.nb_wires = pk["log_n"], pk["nb_wires"]
+        for name in ("g1_a", "g1_b", "g1_k", "g1_z", "g2_b"):
+            ptr, cnt = pk[name]
+            setattr(d, name, int(ptr)); setattr(d, "n_" + name, int(cnt))
+        for name, k in (("alpha1", 8), ("beta1", 8), ("delta1", 8), ("beta2", 16), ("delta2", 16)):
+            setattr(d, name, (C.c_uint64 * k)(*[int(v) for v in _u64(pk[name]).reshape(-1)]))
+        ia = np.ascontiguousarray(pk["infinity_a"], dtype=np.uint8); ib = np.ascontiguousarray(pk["infinity_b"], dtype=np.uint8)
+        d.infinity_a, d.infinity_b = ia.ctypes.data, ib.ctypes.data
+        pa = _pedersen_arrays(list(ped)); need = C.c_size_t()
+        if cap is None:
+            if self.lib.mi_pk_stream_size(C.byref(d), pa, C.c_uint32(len(ped)), C.c_uint32(encoding), C.byref(need)) != 0:
+                raise MiError("mi_pk_stream_size refused its arguments")
+            cap = need.value
+        out = (C.c_uint8 * max(cap, 1))()
+        self.keyfile_len = None
+        rc = self.lib.mi_pk_write_dev(self.h, C.byref(d), pa, C.c_uint32(len(ped)), C.c_uint32(encoding), out, C.c_size_t(cap), C.byref(need))
+        self.keyfile_len = int(need.value)   # the size asked for, also after a refusal for want of room
+        self._ck(rc)
+        return C.string_at(out, need.value)
+
+    def setup_to_stream(self, r1cs: dict, td: dict, encoding=KEYFILE_COMPRESSED, cap=1 << 24, build=True):
+        """mi_groth16_setup_to_stream -> (the key's stream, key handle or None, [Pedersen key handles], vk dict as setup())"""
+        d, keep = _r1cs_desc(r1cs); t = _trapdoor(td)
+        n_k = int(d.nb_public) + int(d.n_commitments)
+        vk_k = np.zeros((max(n_k, 1), 8), np.uint64)
+        vk = VkOut(); vk.k = vk_k.ctypes.data; vk.k_cap = n_k
+        h = C.c_void_p(); ped = (C.c_void_p * MAX_COMMITMENTS)(); need = C.c_size_t()
+        out = (C.c_uint8 * max(cap, 1))()
+        self.keyfile_len = None
+        rc = self.lib.mi_groth16_setup_to_stream(self.h, C.byref(d), C.byref(t), C.c_uint32(encoding), out, C.c_size_t(cap), C.byref(need),
+                                                 C.byref(h) if build else None, ped if build else None, C.byref(vk))
+        self.keyfile_len = int(need.value)
+        self._ck(rc)
+        vkd = {n: np.array(getattr(vk, n), dtype=np.uint64) for n in ("alpha1", "beta2", "gamma2", "delta2")}
+        vkd["k"] = vk_k[:int(vk.n_k)].copy()
+        return C.string_at(out, need.value), (h if build else None), ([C.c_void_p(ped[i]) for i in range(int(d.n_commitments))] if build else []), vkd
+
+    def keyfile_stats(self):
+        st = KeyfileStats(); self._ck(self.lib.mi_keyfile_get_stats(self.h, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in KeyfileStats._fields_}
 
     def setup_stats(self):
         st = SetupStats(); self._ck(self.lib.mi_groth16_setup_get_stats(self.h, C.byref(st)))

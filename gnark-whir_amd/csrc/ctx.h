@@ -13,6 +13,7 @@
 #include "../../include/mi355x_groth16_debug.h"
 #include "../../include/mi355x_groth16_setup.h"
 #include "../../include/mi355x_groth16_r1cs.h"
+#include "../../include/mi355x_groth16_keyfile.h"
 
 struct DevBuf {             // growable device scratch owned by the ctx (no hipMalloc in the hot path
     void *p = nullptr;      // after warm-up: buffers only ever grow)
@@ -126,6 +127,7 @@ struct mi_ctx {
     std::mutex err_m;          // a prove enqueues its MSM groups from helper threads (prove.hip): failures there report through mi_set_err
     mi_stats stats{};
     mi_setup_stats setup_stats{};   // last mi_groth16_setup[_exponents] call (setup.hip)
+    mi_keyfile_stats keyfile_stats{};   // last mi_pk_load_stream / mi_pk_write_dev call (keyfile.hip)
     mi_r1cs_stats r1cs_stats{};     // last evaluation of a resident R1CS on this context (r1cs.hip); eval_ms is read from ev[EV_R1CS_BEGIN], ev[EV_R1CS_END] on request
     bool r1cs_timed = false;
     hipEvent_t ev[EV_COUNT]{};

@@ -64,24 +64,33 @@ MI_HD bool fp_lex_largest(const Fp &mont) {
 // degenerate inputs take the same path as every other: a = 0 gives 0; a1 = 0 with a0 a residue gives s = a0, (x0, x1) = (sqrt a0, 0);
 // a1 = 0 with a0 a non-residue gives s = -a0, x0^2 = 0 and x1^2 = -a0, the purely imaginary root (where the "complex method" divides
 // by 2 x0 = 0); a norm that is a non-residue has no s and whatever comes out fails the final x^2 == a, which alone decides.
-MI_OOL bool fp2_sqrt(Fp2 *out, const Fp2 *a) {
+// Root: who raises to (p + 1) / 4 (FpRootBitwise below; the windowed chain of keyfile_ops.cuh) -- the same value whichever chain.
+template <class Root>
+MI_HD bool fp2_sqrt_by(Fp2 *out, const Fp2 *a) {
     const Fp half = fp12c_half();
     const Fp n = fe_sqr(a->a0) + fe_sqr(a->a1);
     Fp s, cp, cm, x1;
-    fp_sqrt_candidate(&s, &n);
+    Root::candidate(&s, &n);
     const Fp hp = (a->a0 + s) * half, hm = (a->a0 - s) * half;
-    fp_sqrt_candidate(&cp, &hp);
-    fp_sqrt_candidate(&cm, &hm);
+    Root::candidate(&cp, &hp);
+    Root::candidate(&cm, &hm);
     const bool plus = fe_sqr(cp) == hp;
     const Fp x0 = fp_select(plus, cp, cm);
     const Fp k = fp_select(plus, hp, hm) - a->a0;   // (s' - a0) / 2 = (a0 + s') / 2 - a0
-    fp_sqrt_candidate(&x1, &k);
+    Root::candidate(&x1, &k);
     const Fp t = x0 * x1;
     x1 = fp_select(t + t == a->a1, x1, fe_neg(x1));
     const Fp2 x{x0, x1};
     *out = x;
     return fe_sqr(x) == *a;
 }
+MI_OOL bool fp2_sqrt(Fp2 *out, const Fp2 *a);
+// the roots of a proof's handful of points: the bit-by-bit chain
+struct FpRootBitwise {
+    static MI_HD void candidate(Fp *y, const Fp *a) { fp_sqrt_candidate(y, a); }
+    static MI_HD bool sqrt2(Fp2 *y, const Fp2 *a) { return fp2_sqrt(y, a); }
+};
+MI_OOL bool fp2_sqrt(Fp2 *out, const Fp2 *a) { return fp2_sqrt_by<FpRootBitwise>(out, a); }
 
 // 32 bytes, big-endian, the two flag bits of byte 0 cleared -> Montgomery form; false when the integer is not below p
 MI_HD bool fp_from_be32(Fp *out, const uint8_t *in, bool mask_flags) {
@@ -116,7 +125,8 @@ MI_HD bool decode_is_clean_infinity(const uint8_t *in, int len) {
 }
 
 // false = malformed, and *out = (0, 0)
-MI_HD bool g1_decode(G1Aff *out, const uint8_t *in) {
+template <class Root>
+MI_HD bool g1_decode_by(G1Aff *out, const uint8_t *in) {
     *out = G1Aff{Fp::zero(), Fp::zero()};
     const u32 flag = in[0] >> 6;
     if (flag == 0) return false;
@@ -124,15 +134,18 @@ MI_HD bool g1_decode(G1Aff *out, const uint8_t *in) {
     Fp x, y;
     bool ok = fp_from_be32(&x, in, true);
     const Fp rhs = fe_sqr(x) * x + curve_b((const Fp *)0);
-    ok = fp_sqrt(&y, rhs) && ok;
+    Root::candidate(&y, &rhs);
+    ok = fe_sqr(y) == rhs && ok;
     const bool want_largest = flag == 3;
     y = fp_select(fp_lex_largest(y) == want_largest, y, fe_neg(y));
     ok = ok && fp_lex_largest(y) == want_largest;   // y = 0 has one encoding (no such point exists on this curve: its order is odd)
     if (ok) *out = G1Aff{x, y};
     return ok;
 }
+MI_HD bool g1_decode(G1Aff *out, const uint8_t *in) { return g1_decode_by<FpRootBitwise>(out, in); }
 MI_HD bool fp2_lex_largest(const Fp2 &y) { return y.a1.is_zero() ? fp_lex_largest(y.a0) : fp_lex_largest(y.a1); }
-MI_HD bool g2_decode(G2Aff *out, const uint8_t *in) {
+template <class Root>
+MI_HD bool g2_decode_by(G2Aff *out, const uint8_t *in) {
     *out = G2Aff{Fp2::zero(), Fp2::zero()};
     const u32 flag = in[0] >> 6;
     if (flag == 0) return false;
@@ -141,7 +154,7 @@ MI_HD bool g2_decode(G2Aff *out, const uint8_t *in) {
     bool ok = fp_from_be32(&x.a1, in, true);
     ok = fp_from_be32(&x.a0, in + 32, false) && ok;
     const Fp2 rhs = fe_sqr(x) * x + fp12c_twist_b();
-    ok = fp2_sqrt(&y, &rhs) && ok;
+    ok = Root::sqrt2(&y, &rhs) && ok;
     const bool want_largest = flag == 3;
     const bool keep = fp2_lex_largest(y) == want_largest;
     y = Fp2{fp_select(keep, y.a0, fe_neg(y.a0)), fp_select(keep, y.a1, fe_neg(y.a1))};
@@ -149,6 +162,7 @@ MI_HD bool g2_decode(G2Aff *out, const uint8_t *in) {
     if (ok) *out = G2Aff{x, y};
     return ok;
 }
+MI_HD bool g2_decode(G2Aff *out, const uint8_t *in) { return g2_decode_by<FpRootBitwise>(out, in); }
 
 // ---------------------------------------------------------------- Proof.WriteTo's layout
 //     Ar (32) | Bs (64) | Krs (32) | u32 big-endian count | count x 32 commitments | pok (32)          164 + 32 count bytes

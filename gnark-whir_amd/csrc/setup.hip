@@ -431,16 +431,23 @@ int32_t mi_groth16_setup_exponents(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const 
     return MI_OK;
 }
 
-int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, mi_pk **pk_out, mi_pedersen_pk **ped_out, mi_vk_out *vk_out) {
+// Where the stream of the key goes (mi_groth16_setup_to_stream); null for mi_groth16_setup.
+struct KeyStream { uint32_t encoding; uint8_t *out; size_t cap; size_t *len; };
+// groth16.Setup behind both entry points.  ks: the key's stream is written from the plain arrays, right before the key takes them.
+// pk_out null (with ks only): no key is built and ped_out is not written.
+static int32_t setup_run(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, const KeyStream *ks, mi_pk **pk_out, mi_pedersen_pk **ped_out,
+                         mi_vk_out *vk_out) {
     if (!ctx) return MI_EINVAL;
-    if (!pk_out) MI_FAIL(ctx, MI_EINVAL, "setup: pk_out is null");
-    *pk_out = nullptr;
+    if (!pk_out && !ks) MI_FAIL(ctx, MI_EINVAL, "setup: pk_out is null");
+    if (pk_out) *pk_out = nullptr;
     if (!vk_out) MI_FAIL(ctx, MI_EINVAL, "setup: vk_out is null");
+    const bool build = pk_out != nullptr;
     Plan pl;
     MI_TRY(make_plan(ctx, r1cs, trapdoor, pl));
-    if (pl.n_commitments && !ped_out) MI_FAIL(ctx, MI_EINVAL, "setup: ped_out is null");
+    if (pl.n_commitments && !ped_out && build) MI_FAIL(ctx, MI_EINVAL, "setup: ped_out is null");
     if (!vk_out->k || vk_out->k_cap < pl.vk_wires.size()) MI_FAIL(ctx, MI_EINVAL, "setup: vk_out.k / k_cap: room for nb_public + n_commitments points is needed");
-    for (u32 k = 0; k < pl.n_commitments; k++) ped_out[k] = nullptr;
+    for (u32 k = 0; k < pl.n_commitments && build; k++) ped_out[k] = nullptr;
+    std::vector<mi_pedersen_arrays> ped_arrays;   // the plain Pedersen arrays, for the stream
     const double t0 = now_ms();
     ctx->setup_stats = mi_setup_stats{};
     const mi_g1_affine g1 = g1_generator();
@@ -464,6 +471,17 @@ int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
         MI_CHECK_HIP(ctx, hipMemcpyAsync(&n_k, f.slot_k + nw, 4, hipMemcpyDeviceToHost, st));
         MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
         ar.release(f.inf_a); ar.release(f.inf_b);
+        if (ks) {   // the counts are known: a buffer that cannot hold the stream is refused before the points are computed
+            mi_pk_desc counts;
+            std::memset(&counts, 0, sizeof(counts));
+            counts.nb_wires = nw; counts.n_g1_a = n_a; counts.n_g1_b = counts.n_g2_b = n_b; counts.n_g1_k = n_k; counts.n_g1_z = pl.N;
+            std::vector<mi_pedersen_arrays> pc(pl.n_commitments);
+            for (u32 k = 0; k < pl.n_commitments; k++) pc[k] = mi_pedersen_arrays{nullptr, nullptr, r1cs->n_committed[k]};
+            size_t need = 0;
+            if (mi_pk_stream_size(&counts, pc.data(), pl.n_commitments, ks->encoding, &need) != MI_OK) MI_FAIL(ctx, MI_EINVAL, "setup: encoding is neither MI_KEYFILE_RAW nor MI_KEYFILE_COMPRESSED");
+            if (ks->len) *ks->len = need;
+            if (!ks->out || ks->cap < need) MI_FAIL(ctx, MI_EINVAL, "setup: the key's stream takes " + std::to_string(need) + " bytes, out_host has room for " + std::to_string(ks->out ? ks->cap : 0));
+        }
         // dense scalar arrays; each per-wire array goes as soon as it has been read
         Fr *sa = nullptr, *sb = nullptr, *sk = nullptr;
         auto compact = [&](Fr **dst, Fr *src, u32 *slot, u32 n) -> int32_t {
@@ -518,6 +536,8 @@ int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
             MI_TRY(mul_g1(&bes, s1, n));
             MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
             ar.release(s0); ar.release(s1);
+            ped_arrays.push_back(mi_pedersen_arrays{(const mi_g1_affine *)basis, (const mi_g1_affine *)bes, n});
+            if (!build) continue;   // write only: the arrays stay the arena's
             MI_TRY(mi_pedersen_pk_adopt(ctx, basis, bes, n, &ped_out[k]));
             ar.disown(basis); ar.disown(bes);
             n_ped = k + 1;
@@ -577,10 +597,13 @@ int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
         std::memcpy(&d.beta2, &small2[0], 128); std::memcpy(&d.delta2, &small2[1], 128);
         d.infinity_a = ia.data(); d.infinity_b = ib.data();
         d.committed_wires = pl.removed.empty() ? nullptr : pl.removed.data(); d.n_committed = pl.removed.size();
-        bool took = false;
-        const int32_t lr = mi_pk_load_range(ctx, &d, pk_out, true, nullptr, /*forced=*/nullptr, /*adopt=*/true, &took);
-        if (took) for (void *a : arrays) ar.disown(a);   // the key's now (it has released them itself if it failed after taking them)
-        MI_TRY(lr);
+        if (ks) MI_TRY(mi_pk_write_dev(ctx, &d, ped_arrays.data(), pl.n_commitments, ks->encoding, ks->out, ks->cap, ks->len));
+        if (build) {
+            bool took = false;
+            const int32_t lr = mi_pk_load_range(ctx, &d, pk_out, true, nullptr, /*forced=*/nullptr, /*adopt=*/true, &took);
+            if (took) for (void *a : arrays) ar.disown(a);   // the key's now (it has released them itself if it failed after taking them)
+            MI_TRY(lr);
+        }
         MI_TRY(tm.mark(ctx, Timer::DONE));
         MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
         fill_stats(ctx, pl, tm, f, now_ms() - t0);
@@ -589,10 +612,18 @@ int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
     const int32_t rc = body();
     if (rc != MI_OK) {
         (void)hipStreamSynchronize(st);
-        if (*pk_out) { mi_pk_free(ctx, *pk_out); *pk_out = nullptr; }
+        if (build && *pk_out) { mi_pk_free(ctx, *pk_out); *pk_out = nullptr; }
         for (u32 k = 0; k < n_ped; k++) { mi_pedersen_pk_free(ctx, ped_out[k]); ped_out[k] = nullptr; }
     }
     return rc;
+}
+int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, mi_pk **pk_out, mi_pedersen_pk **ped_out, mi_vk_out *vk_out) {
+    return setup_run(ctx, r1cs, trapdoor, nullptr, pk_out, ped_out, vk_out);
+}
+int32_t mi_groth16_setup_to_stream(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, uint32_t encoding, uint8_t *out_host, size_t cap,
+                                   size_t *len, mi_pk **pk_out, mi_pedersen_pk **ped_out, mi_vk_out *vk_out) {
+    const KeyStream ks{encoding, out_host, cap, len};
+    return setup_run(ctx, r1cs, trapdoor, &ks, pk_out, ped_out, vk_out);
 }
 
 }  // extern "C"
