@@ -19,7 +19,7 @@ EXPORTS = [
     "mi_ntt", "mi_ntt_dev", "mi_compute_h", "mi_compute_h_dev", "mi_msm_g1", "mi_msm_g1_dev", "mi_msm_g2",
     "mi_msm_g2_dev", "mi_groth16_prove", "mi_groth16_prove_dev", "mi_get_stats", "mi_g1_compress",
     "mi_g2_compress", "mi_proof_write", "mi_g1_sum", "mi_g2_sum", "mi_gen_scalars_dev", "mi_gen_g1_dev",
-    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_field_shape_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_debug_decode_g1_dev", "mi_debug_decode_g2_dev", "mi_debug_hash_to_field_dev", "mi_debug_fp12_product_dev", "mi_debug_g1_scale128_dev", "mi_debug_g1_sum_tree_dev", "mi_debug_locate_points_dev", "mi_debug_locate_colsums_dev", "mi_debug_set_locate_round_nodes", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
+    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_field_shape_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_debug_decode_g1_dev", "mi_debug_decode_g2_dev", "mi_debug_hash_to_field_dev", "mi_debug_witness_decode_dev", "mi_debug_fp12_product_dev", "mi_debug_g1_scale128_dev", "mi_debug_g1_sum_tree_dev", "mi_debug_locate_points_dev", "mi_debug_locate_colsums_dev", "mi_debug_set_locate_round_nodes", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
     "mi_dev_alloc", "mi_dev_free", "mi_dev_upload", "mi_dev_download", "mi_dev_sync",
     "mi_msm_precompute_g1_dev", "mi_msm_precompute_g2_dev", "mi_msm_g1_fixed_dev", "mi_msm_g2_fixed_dev", "mi_msm_table_to_rprime_g1_dev", "mi_msm_table_to_rprime_g2_dev", "mi_pk_table_plan",
     "mi_batch_scalar_mul_g1", "mi_batch_scalar_mul_g1_dev", "mi_batch_scalar_mul_g2", "mi_batch_scalar_mul_g2_dev",
@@ -61,6 +61,10 @@ KEYFILE_EXPORTS = ["mi_g1_decompress_dev", "mi_g2_decompress_dev", "mi_g1_compre
 KEYFILE_RAW, KEYFILE_COMPRESSED = 0, 1
 KEYFILE_NO_SUBGROUP_CHECK, KEYFILE_SUBGROUP_BY_R = 1, 2
 NO_BAD_INDEX = (1 << 64) - 1
+# include/mi355x_groth16_vkfile.h (verify from files: the verifying key's stream and the public witness's bytes, decoded on the device)
+VKFILE_EXPORTS = ["mi_vk_stream_inspect", "mi_vk_stream_size", "mi_vk_write", "mi_vk_load_stream", "mi_groth16_setup_to_streams",
+                  "mi_public_witness_write", "mi_public_witness_read", "mi_groth16_verify_files", "mi_groth16_verify_files_batch",
+                  "mi_groth16_verify_files_combined", "mi_groth16_verify_files_locate"]
 
 
 class PkDesc(C.Structure):
@@ -219,6 +223,82 @@ class VerifyInput(C.Structure):
 
 class VerifyBytesInput(C.Structure):
     _fields_ = [("proof", C.c_void_p), ("proof_len", C.c_size_t), ("public_inputs", C.c_void_p)]
+
+
+class VerifyFilesInput(C.Structure):
+    _fields_ = [("proof", C.c_void_p), ("proof_len", C.c_size_t), ("witness", C.c_void_p), ("witness_len", C.c_size_t)]
+
+
+class VkStreamInfo(C.Structure):
+    _fields_ = [("n_k", C.c_uint64), ("nb_public", C.c_uint32), ("n_commitment_keys", C.c_uint32)] + [(n, C.c_uint64) for n in (
+        "off_alpha1", "off_beta1", "off_beta2", "off_gamma2", "off_delta1", "off_delta2", "off_k", "off_lists")] + [
+        ("list_len", C.c_uint64 * 16), ("off_list", C.c_uint64 * 16), ("off_commitment_keys", C.c_uint64), ("off_ped", C.c_uint64 * 16),
+        ("refused", C.c_char * 96)]
+
+
+class VkFileDesc(C.Structure):
+    _fields_ = [("alpha1", C.c_uint64 * 8), ("beta1", C.c_uint64 * 8), ("delta1", C.c_uint64 * 8), ("beta2", C.c_uint64 * 16),
+                ("gamma2", C.c_uint64 * 16), ("delta2", C.c_uint64 * 16), ("k", C.c_void_p), ("n_k", C.c_uint64), ("nb_public", C.c_uint32),
+                ("n_commitments", C.c_uint32), ("ped", C.c_void_p), ("pc_offsets", C.c_void_p), ("pc_indices", C.c_void_p)]
+
+
+def vk_stream_inspect(blob: bytes):
+    """(field offsets / counts, KEYFILE_RAW or KEYFILE_COMPRESSED) of a verifying key's stream (host only); raises MiError naming the
+    field if neither layout parses"""
+    info = VkStreamInfo(); enc = C.c_uint32(); buf = (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(blob or b"\0")
+    if load().mi_vk_stream_inspect(buf, C.c_size_t(len(blob)), C.byref(info), C.byref(enc)) != 0:
+        raise MiError("mi_vk_stream_inspect: neither a VerifyingKey.WriteRawTo nor a VerifyingKey.WriteTo stream (as recalled): " + info.refused.decode())
+    return info, int(enc.value)
+
+
+def _vk_file_desc(vk: dict, nb_public, ped=None, lists=None):
+    """the vk dict of setup() plus beta1 and delta1, the Pedersen verifying keys and the committed lists -> (VkFileDesc, what it points to)"""
+    d = VkFileDesc()
+    for n, w in (("alpha1", 8), ("beta1", 8), ("delta1", 8), ("beta2", 16), ("gamma2", 16), ("delta2", 16)):
+        if vk.get(n) is not None:
+            setattr(d, n, (C.c_uint64 * w)(*[int(v) for v in _u64(vk[n]).reshape(w)]))
+    k = _u64(vk["k"]).reshape(-1, 8)
+    ped = None if ped is None else _u64(ped).reshape(-1, 2, 16)
+    d.k, d.n_k, d.nb_public = k.ctypes.data, int(k.shape[0]), int(nb_public)
+    d.n_commitments = 0 if ped is None else int(ped.shape[0])
+    d.ped = None if ped is None else ped.ctypes.data
+    off = idx = None
+    if lists is not None:
+        off = np.cumsum([0] + [len(l) for l in lists]).astype(np.uint32)
+        idx = np.array([j for l in lists for j in l], np.uint32)
+        d.pc_offsets = off.ctypes.data
+        d.pc_indices = idx.ctypes.data if len(idx) else None
+    return d, (k, ped, off, idx)
+
+
+def vk_stream_size(n_k, n_commitments=0, n_indices=0, encoding=KEYFILE_COMPRESSED):
+    d = VkFileDesc(); d.n_k, d.n_commitments = int(n_k), int(n_commitments)
+    off = np.array([0] * int(n_commitments) + [int(n_indices)], np.uint32); d.pc_offsets = off.ctypes.data
+    n = C.c_size_t()
+    if load().mi_vk_stream_size(C.byref(d), C.c_uint32(encoding), C.byref(n)) != 0:
+        raise MiError("mi_vk_stream_size refused its arguments")
+    return int(n.value)
+
+
+def public_witness_write(values, cap=None) -> bytes:
+    """mi_public_witness_write: (n, 4) Montgomery values -> witness.WriteTo's bytes of a public witness"""
+    v = _u64(values).reshape(-1, 4); n = v.shape[0]
+    cap = 12 + 32 * n if cap is None else cap
+    out = (C.c_uint8 * max(cap, 1))(); need = C.c_size_t()
+    if load().mi_public_witness_write(_p(v) if n else None, C.c_size_t(n), out, C.c_size_t(cap), C.byref(need)) != 0:
+        raise MiError(f"mi_public_witness_write: MI_EINVAL ({need.value} bytes needed)")
+    return C.string_at(out, need.value)
+
+
+def public_witness_read(data: bytes, cap=None):
+    """mi_public_witness_read: the public part of a witness's bytes -> (nbPublic, 4) uint64 Montgomery; MiError for a header that
+    disagrees with the length or a value not below r"""
+    buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
+    cap = max((len(data) - 12) // 32, 0) if cap is None else cap
+    out = np.zeros((max(cap, 1), 4), np.uint64); n = C.c_size_t()
+    if load().mi_public_witness_read(buf, C.c_size_t(len(data)), _p(out), C.c_size_t(cap), C.byref(n)) != 0:
+        raise MiError("mi_public_witness_read: MI_EINVAL")
+    return out[:int(n.value)].copy()
 
 
 class VerifyLocateStats(C.Structure):
@@ -648,6 +728,62 @@ class Context:
         vkd["k"] = vk_k[:int(vk.n_k)].copy()
         return C.string_at(out, need.value), (h if build else None), ([C.c_void_p(ped[i]) for i in range(int(d.n_commitments))] if build else []), vkd
 
+    # ---- verifying keys as files (include/mi355x_groth16_vkfile.h)
+    def vk_load_stream(self, blob: bytes, flags=0):
+        """a VerifyingKey.WriteRawTo or VerifyingKey.WriteTo stream -> VerifyingKey, every point checked, the committed lists installed"""
+        info, _ = vk_stream_inspect(blob) if len(blob) else (None, 0)
+        buf = (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(blob or b"\0"); h = C.c_void_p()
+        self._ck(self.lib.mi_vk_load_stream(self.h, buf, C.c_size_t(len(blob)), C.c_uint32(flags), C.byref(h)))
+        return VerifyingKey._adopt(self, h, int(info.nb_public), int(info.n_commitment_keys))
+
+    def vk_write(self, vk: dict, nb_public, ped=None, lists=None, encoding=KEYFILE_COMPRESSED, cap=None):
+        """mi_vk_write: the vk dict of setup() with beta1 and delta1 added -> the stream's bytes.  cap: the room offered (default: what
+        mi_vk_stream_size asks for)"""
+        d, keep = _vk_file_desc(vk, nb_public, ped, lists); need = C.c_size_t()
+        if cap is None:
+            if self.lib.mi_vk_stream_size(C.byref(d), C.c_uint32(encoding), C.byref(need)) != 0:
+                raise MiError("mi_vk_stream_size refused its arguments")
+            cap = need.value
+        out = (C.c_uint8 * max(cap, 1))()
+        self.keyfile_len = None
+        rc = self.lib.mi_vk_write(self.h, C.byref(d), C.c_uint32(encoding), out, C.c_size_t(cap), C.byref(need))
+        self.keyfile_len = int(need.value)   # the size asked for, also after a refusal for want of room
+        self.keyfile_out = bytes(out)        # what the call left in the buffer
+        self._ck(rc)
+        return C.string_at(out, need.value)
+
+    def setup_to_streams(self, r1cs: dict, td: dict, encoding=KEYFILE_COMPRESSED, cap=1 << 24, vk_cap=1 << 20, build=True):
+        """mi_groth16_setup_to_streams -> (the proving key's stream, the verifying key's stream, key handle or None, [Pedersen key
+        handles], vk dict as setup())"""
+        d, keep = _r1cs_desc(r1cs); t = _trapdoor(td)
+        n_k = int(d.nb_public) + int(d.n_commitments)
+        vk_k = np.zeros((max(n_k, 1), 8), np.uint64)
+        vk = VkOut(); vk.k = vk_k.ctypes.data; vk.k_cap = n_k
+        h = C.c_void_p(); ped = (C.c_void_p * MAX_COMMITMENTS)(); need = C.c_size_t(); vk_need = C.c_size_t()
+        out = (C.c_uint8 * max(cap, 1))(); vk_out = (C.c_uint8 * max(vk_cap, 1))()
+        self.keyfile_len = self.vkfile_len = None
+        rc = self.lib.mi_groth16_setup_to_streams(self.h, C.byref(d), C.byref(t), C.c_uint32(encoding), out, C.c_size_t(cap), C.byref(need),
+                                                  vk_out, C.c_size_t(vk_cap), C.byref(vk_need), C.byref(h) if build else None, ped if build else None, C.byref(vk))
+        self.keyfile_len, self.vkfile_len = int(need.value), int(vk_need.value)
+        self._ck(rc)
+        vkd = {n: np.array(getattr(vk, n), dtype=np.uint64) for n in ("alpha1", "beta2", "gamma2", "delta2")}
+        vkd["k"] = vk_k[:int(vk.n_k)].copy()
+        return (C.string_at(out, need.value), C.string_at(vk_out, vk_need.value), (h if build else None),
+                ([C.c_void_p(ped[i]) for i in range(int(d.n_commitments))] if build else []), vkd)
+
+    def witness_decode_dev(self, values: bytes, n, n_pub, odd=True):
+        """mi_debug_witness_decode_dev over host bytes (n * n_pub values of 32 bytes, placed at an odd device address) ->
+        ((n, n_pub, 4) uint64 Montgomery, (n,) uint8 bad)"""
+        assert len(values) == 32 * n * n_pub
+        shift = 1 if odd else 0
+        de = self.to_dev(np.frombuffer(b"\0" * shift + values + b"\0" * 32, np.uint8)); do = self.alloc(max(32 * n * n_pub, 32)); db = self.to_dev(np.zeros(max(n, 32), np.uint8))
+        try:
+            self._ck(self.lib.mi_debug_witness_decode_dev(self.h, C.c_void_p(int(de.ptr) + shift), C.c_size_t(n), C.c_uint32(n_pub), _p(do.ptr), _p(db.ptr)))
+            self.sync()
+            return do.download((n, n_pub, 4)) if n * n_pub else np.zeros((n, n_pub, 4), np.uint64), db.download((max(n, 32),), np.uint8)[:n]
+        finally:
+            for b in (de, do, db): b.free()
+
     def keyfile_stats(self):
         st = KeyfileStats(); self._ck(self.lib.mi_keyfile_get_stats(self.h, C.byref(st)))
         return {n: getattr(st, n) for n, _ in KeyfileStats._fields_}
@@ -888,6 +1024,13 @@ class VerifyingKey:
         ctx._ck(ctx.lib.mi_vk_load(ctx.h, C.byref(d), C.byref(h)))
         self.h = h
 
+    @classmethod
+    def _adopt(cls, ctx, h, nb_public, n_commitments):
+        """a handle mi_vk_load_stream made"""
+        self = cls.__new__(cls)
+        self.ctx, self.h, self.nb_public, self.n_commitments = ctx, h, int(nb_public), int(n_commitments)
+        return self
+
     def _inputs(self, proofs):
         arr = (VerifyInput * len(proofs))(); keep = []
         for i, pr in enumerate(proofs):
@@ -968,6 +1111,37 @@ class VerifyingKey:
             if pub is not None:
                 pub = _u64(pub); keep.append(pub); arr[i].public_inputs = pub.ctypes.data
         return arr, keep
+
+    # ---- from the bytes of proof and public witness (include/mi355x_groth16_vkfile.h); proofs: [(proof bytes, witness bytes)]
+    def _files_inputs(self, proofs):
+        proofs = list(proofs); arr = (VerifyFilesInput * len(proofs))(); keep = []
+        for i, (b, w) in enumerate(proofs):
+            pb = C.create_string_buffer(b, len(b)); wb = C.create_string_buffer(w, len(w)); keep += [pb, wb]
+            arr[i].proof, arr[i].proof_len, arr[i].witness, arr[i].witness_len = C.addressof(pb), len(b), C.addressof(wb), len(w)
+        return arr, keep
+
+    def verify_files(self, proof: bytes, witness: bytes) -> int:
+        v = C.c_uint8(255)
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_files(self.ctx.h, self.h, proof, C.c_size_t(len(proof)), witness, C.c_size_t(len(witness)), C.byref(v)))
+        return int(v.value)
+
+    def verify_files_batch(self, proofs, out=None):
+        arr, keep = self._files_inputs(proofs)
+        out = np.full(len(arr), 255, np.uint8) if out is None else out
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_files_batch(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), _p(out)))
+        return out
+
+    def verify_files_combined(self, proofs, seed=None):
+        assert seed is None or len(seed) == 32
+        arr, keep = self._files_inputs(proofs); v = C.c_uint8(255); first = C.c_uint64(1 << 63)
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_files_combined(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), seed, C.byref(v), C.byref(first)))
+        return int(v.value), int(first.value)
+
+    def verify_files_locate(self, proofs, seed=None):
+        assert seed is None or len(seed) == 32
+        arr, keep = self._files_inputs(proofs); out = np.full(len(arr), 255, np.uint8); st = VerifyLocateStats()
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_files_locate(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), seed, _p(out), C.byref(st)))
+        return out, st.as_dict()
 
     def free(self):
         if self.h:

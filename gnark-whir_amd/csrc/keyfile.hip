@@ -15,6 +15,7 @@
 // on the device and copied into place; the Domain block, the counts and the masks are host code and follow oracle/pk_raw.py.
 #include "prove_internal.h"
 #include "keyfile_ops.cuh"
+#include "keyfile_internal.h"
 #include <chrono>
 #include <cstring>
 #include <string>
@@ -165,6 +166,15 @@ void put_fr(uint8_t *&p, const Fr &mont) {
 }
 
 }  // namespace
+
+// keyfile_internal.h: the same launches for the verifying key's stream (vkfile.hip)
+int32_t mi_keyfile_decode_enqueue(mi_ctx *ctx, bool g2, void *dst_dev, const uint8_t *src_dev, size_t n, bool compressed, ull *first_bad_dev) {
+    return g2 ? decode_g2(ctx, dst_dev, src_dev, n, compressed, first_bad_dev) : decode_g1(ctx, dst_dev, src_dev, n, compressed, first_bad_dev);
+}
+int32_t mi_keyfile_subgroup_enqueue(mi_ctx *ctx, const void *g2_dev, size_t n, bool by_r, ull *first_bad_dev) { return subgroup_g2(ctx, g2_dev, n, by_r, first_bad_dev); }
+int32_t mi_keyfile_encode_enqueue(mi_ctx *ctx, bool g2, uint8_t *dst_dev, const void *src_dev, size_t n, bool compressed) {
+    return g2 ? encode_g2(ctx, dst_dev, src_dev, n, compressed) : encode_g1(ctx, dst_dev, src_dev, n, compressed);
+}
 
 extern "C" {
 

@@ -81,13 +81,13 @@ MI_HD G1Aff g1_aff_neg(const G1Aff &p) { return G1Aff{p.x, fe_neg(p.y)}; }
 // What the host can say about a proof before any arithmetic: every coordinate below p, every scalar below r (fe_is_reduced), every G1
 // point on the curve.  (Bs on the twist and in its r-torsion is the device's question, k_verify_g2_check.)  fold_challenge is read, and
 // therefore checked, with more than one commitment only.  A proof that fails here is MI_VERIFY_MALFORMED and none of its words reaches
-// the MSM, the group law or a Miller loop.
-inline bool verify_well_formed(const VerifyKeyRef &vk, const VerifyProofRef &in) {
+// the MSM, the group law or a Miller loop.  check_public = false: public_inputs is not read (the device decoded and checked them).
+inline bool verify_well_formed(const VerifyKeyRef &vk, const VerifyProofRef &in, bool check_public = true) {
     const u32 nc = vk.n_commitments;
     bool ok = g1_on_curve(*in.ar) && g1_on_curve(*in.krs) && g2_reduced(*in.bs);
     if (nc) ok = ok && g1_on_curve(*in.pok);
     for (u32 k = 0; k < nc; k++) ok = ok && g1_on_curve(in.commitments[k]) && fe_is_reduced(in.commitment_values[k]);
-    for (u32 i = 0; i < vk.n_pub; i++) ok = ok && fe_is_reduced(in.public_inputs[i]);
+    for (u32 i = 0; check_public && i < vk.n_pub; i++) ok = ok && fe_is_reduced(in.public_inputs[i]);
     if (nc > 1) ok = ok && fe_is_reduced(*in.fold_challenge);
     return ok;
 }
@@ -122,22 +122,28 @@ inline void verify_assemble(const VerifyKeyRef &vk, const VerifyProofRef &in, bo
 // The host's view of one batch before any device work: what mi_verify_run and mi_verify_combined_run (through mi_verify_open, verify.hip)
 // and the host build of the tests all start from.  A proof whose decode_malformed byte (the array may be null) is set has none of its
 // words read.  The references point into the caller's memory, which outlives the stage.
+// pub_dev (optional): the public inputs of the batch already on the DEVICE, n x n_pub Montgomery values, row i for proof i, decoded and
+// range-checked there (k_witness_decode, verify_bytes.hip: its answer arrives through decode_malformed).  With it the host neither reads
+// nor checks public_inputs, and scal holds the commitment values alone.
 struct VerifyStage {
     VerifyKeyRef key{};
     u32 n_pub = 0, nc = 0, ns = 0;         // ns = n_pub + nc: the scalars of one proof's kSum
     std::vector<VerifyProofRef> proofs;
     std::vector<uint8_t> flags;            // flags[i] = decode_malformed[i] || !verify_well_formed(proof i)
-    std::vector<Fr> scal;                  // n x ns, row-major: public_inputs | commitment_values; a flagged proof's row is zero, never read
+    const Fr *pub_dev = nullptr;
+    u32 scal_cols = 0;                     // ns, or nc with pub_dev
+    std::vector<Fr> scal;                  // n x scal_cols, row-major: public_inputs | commitment_values; a flagged proof's row is zero, never read
     size_t first_flagged = 0;              // the lowest i with flags[i], n() when there is none
     VerifyStage() = default;
-    VerifyStage(const VerifyKeyRef &k, std::vector<VerifyProofRef> refs, const uint8_t *decode_malformed)
-        : key(k), n_pub(k.n_pub), nc(k.n_commitments), ns(n_pub + nc), proofs(std::move(refs)), flags(proofs.size(), 0),
-          scal(proofs.size() * ns, Fr::zero()), first_flagged(proofs.size()) {
+    VerifyStage(const VerifyKeyRef &k, std::vector<VerifyProofRef> refs, const uint8_t *decode_malformed, const Fr *public_dev = nullptr)
+        : key(k), n_pub(k.n_pub), nc(k.n_commitments), ns(n_pub + nc), proofs(std::move(refs)), flags(proofs.size(), 0), pub_dev(public_dev),
+          scal_cols(public_dev ? nc : ns), scal(proofs.size() * scal_cols, Fr::zero()), first_flagged(proofs.size()) {
+        const u32 own = pub_dev ? 0 : n_pub;   // the public columns this stage holds itself
         for (size_t i = n(); i-- > 0;) {
             const VerifyProofRef &in = proofs[i];
-            if ((decode_malformed && decode_malformed[i]) || !verify_well_formed(key, in)) { flags[i] = 1; first_flagged = i; continue; }
-            if (n_pub) std::memcpy(&scal[i * ns], in.public_inputs, (size_t)n_pub * sizeof(Fr));
-            if (nc) std::memcpy(&scal[i * ns + n_pub], in.commitment_values, (size_t)nc * sizeof(Fr));
+            if ((decode_malformed && decode_malformed[i]) || !verify_well_formed(key, in, !pub_dev)) { flags[i] = 1; first_flagged = i; continue; }
+            if (own) std::memcpy(&scal[i * scal_cols], in.public_inputs, (size_t)own * sizeof(Fr));
+            if (nc) std::memcpy(&scal[i * scal_cols + own], in.commitment_values, (size_t)nc * sizeof(Fr));
         }
     }
     size_t n() const { return proofs.size(); }

@@ -21,6 +21,7 @@
 // Only the R1CS goes up; the infinity masks, the counts and the verifying key come down.
 #include "prove_internal.h"
 #include "r1cs_internal.h"
+#include "../../include/mi355x_groth16_vkfile.h"
 #include "scan_u32.cuh"
 #include "sparse_fr.cuh"
 #include <algorithm>
@@ -432,7 +433,8 @@ int32_t mi_groth16_setup_exponents(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const 
 }
 
 // Where the stream of the key goes (mi_groth16_setup_to_stream); null for mi_groth16_setup.
-struct KeyStream { uint32_t encoding; uint8_t *out; size_t cap; size_t *len; };
+// with_vk (mi_groth16_setup_to_streams): the verifying key's stream too, with a triple of its own.
+struct KeyStream { uint32_t encoding; uint8_t *out; size_t cap; size_t *len; bool with_vk = false; uint8_t *vk_out = nullptr; size_t vk_cap = 0; size_t *vk_len = nullptr; };
 // groth16.Setup behind both entry points.  ks: the key's stream is written from the plain arrays, right before the key takes them.
 // pk_out null (with ks only): no key is built and ped_out is not written.
 static int32_t setup_run(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, const KeyStream *ks, mi_pk **pk_out, mi_pedersen_pk **ped_out,
@@ -480,7 +482,17 @@ static int32_t setup_run(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
             size_t need = 0;
             if (mi_pk_stream_size(&counts, pc.data(), pl.n_commitments, ks->encoding, &need) != MI_OK) MI_FAIL(ctx, MI_EINVAL, "setup: encoding is neither MI_KEYFILE_RAW nor MI_KEYFILE_COMPRESSED");
             if (ks->len) *ks->len = need;
+            size_t vk_need = 0;
+            if (ks->with_vk) {
+                mi_vk_file_desc vc;
+                std::memset(&vc, 0, sizeof(vc));
+                vc.n_k = pl.vk_wires.size(); vc.nb_public = pl.nb_public; vc.n_commitments = pl.n_commitments;
+                (void)mi_vk_stream_size(&vc, ks->encoding, &vk_need);   // the encoding has passed above
+                if (ks->vk_len) *ks->vk_len = vk_need;
+            }
             if (!ks->out || ks->cap < need) MI_FAIL(ctx, MI_EINVAL, "setup: the key's stream takes " + std::to_string(need) + " bytes, out_host has room for " + std::to_string(ks->out ? ks->cap : 0));
+            if (ks->with_vk && (!ks->vk_out || ks->vk_cap < vk_need))
+                MI_FAIL(ctx, MI_EINVAL, "setup: the verifying key's stream takes " + std::to_string(vk_need) + " bytes, vk_out_host has room for " + std::to_string(ks->vk_out ? ks->vk_cap : 0));
         }
         // dense scalar arrays; each per-wire array goes as soon as it has been read
         Fr *sa = nullptr, *sb = nullptr, *sk = nullptr;
@@ -562,6 +574,17 @@ static int32_t setup_run(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
         }
         std::memcpy(&vk_out->alpha1, &small1[0], 64);
         std::memcpy(&vk_out->beta2, &small2[0], 128); std::memcpy(&vk_out->delta2, &small2[1], 128); std::memcpy(&vk_out->gamma2, &small2[2], 128);
+        if (ks && ks->with_vk) {   // the verifying key's stream: everything it holds is on the host here; its lists start empty
+            mi_vk_file_desc vd;
+            std::memset(&vd, 0, sizeof(vd));
+            vd.alpha1 = vk_out->alpha1; vd.beta2 = vk_out->beta2; vd.gamma2 = vk_out->gamma2; vd.delta2 = vk_out->delta2;
+            std::memcpy(&vd.beta1, &small1[1], 64); std::memcpy(&vd.delta1, &small1[2], 64);
+            vd.k = vk_out->k; vd.n_k = vk_out->n_k; vd.nb_public = pl.nb_public; vd.n_commitments = pl.n_commitments;
+            std::vector<mi_pedersen_vk> pvk(pl.n_commitments);
+            MI_TRY(mi_pedersen_vk_make(ctx, trapdoor->sigma, pl.n_commitments, pvk.data()));
+            vd.ped = pvk.data();
+            MI_TRY(mi_vk_write(ctx, &vd, ks->encoding, ks->vk_out, ks->vk_cap, ks->vk_len));
+        }
         // the five arrays of the key
         void *arrays[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
         MI_TRY(mul_g1(&arrays[0], sa, n_a));
@@ -623,6 +646,12 @@ int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
 int32_t mi_groth16_setup_to_stream(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, uint32_t encoding, uint8_t *out_host, size_t cap,
                                    size_t *len, mi_pk **pk_out, mi_pedersen_pk **ped_out, mi_vk_out *vk_out) {
     const KeyStream ks{encoding, out_host, cap, len};
+    return setup_run(ctx, r1cs, trapdoor, &ks, pk_out, ped_out, vk_out);
+}
+int32_t mi_groth16_setup_to_streams(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, uint32_t encoding, uint8_t *out_host, size_t cap,
+                                    size_t *len, uint8_t *vk_out_host, size_t vk_cap, size_t *vk_len, mi_pk **pk_out, mi_pedersen_pk **ped_out,
+                                    mi_vk_out *vk_out) {
+    const KeyStream ks{encoding, out_host, cap, len, true, vk_out_host, vk_cap, vk_len};
     return setup_run(ctx, r1cs, trapdoor, &ks, pk_out, ped_out, vk_out);
 }
 

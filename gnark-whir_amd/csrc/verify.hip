@@ -88,7 +88,7 @@ int32_t mi_verify_msm(mi_ctx *ctx, const void *bases_dev, const void *scalars_de
 }
 
 int32_t mi_verify_open(mi_ctx *ctx, const char *who, const mi_vk *vk, const mi_verify_input *in, size_t n, bool has_verdict,
-                       const uint8_t *decode_malformed, VerifyStage *st) {
+                       const uint8_t *decode_malformed, VerifyStage *st, const Fr *pub_dev) {
     if (!ctx) return MI_EINVAL;
     const std::string w = who;
     if (!vk || (!in && n) || !has_verdict) MI_FAIL(ctx, MI_EINVAL, w + "null vk, input or verdict pointer");
@@ -96,20 +96,21 @@ int32_t mi_verify_open(mi_ctx *ctx, const char *who, const mi_vk *vk, const mi_v
     const u32 nc = vk->n_commitments, n_pub = vk->nb_public - 1;
     std::vector<VerifyProofRef> refs(n);
     for (size_t i = 0; i < n; i++) {
-        if (n_pub && !in[i].public_inputs) MI_FAIL(ctx, MI_EINVAL, w + "public_inputs is null");
+        if (n_pub && !pub_dev && !in[i].public_inputs) MI_FAIL(ctx, MI_EINVAL, w + "public_inputs is null");
         if (nc && (!in[i].commitments || !in[i].pok || !in[i].commitment_values)) MI_FAIL(ctx, MI_EINVAL, w + "commitments, pok or commitment_values is null");
         if (nc > 1 && !in[i].fold_challenge) MI_FAIL(ctx, MI_EINVAL, w + "fold_challenge is null with more than one commitment");
         refs[i] = VerifyProofRef{(const G1Aff *)&in[i].proof.ar, (const G2Aff *)&in[i].proof.bs, (const G1Aff *)&in[i].proof.krs,
                                  (const G1Aff *)in[i].commitments, (const G1Aff *)in[i].pok, (const Fr *)in[i].public_inputs,
                                  (const Fr *)in[i].commitment_values, (const Fr *)in[i].fold_challenge};
     }
-    *st = VerifyStage(VerifyKeyRef{&vk->k[0], &vk->gamma2, &vk->delta2, (const G2Aff *)vk->ped.data(), n_pub, nc}, std::move(refs), decode_malformed);
+    *st = VerifyStage(VerifyKeyRef{&vk->k[0], &vk->gamma2, &vk->delta2, (const G2Aff *)vk->ped.data(), n_pub, nc}, std::move(refs), decode_malformed, n_pub ? pub_dev : nullptr);
     return MI_OK;
 }
 
-int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts, const uint8_t *decode_malformed) {
+int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts, const uint8_t *decode_malformed,
+                      const Fr *pub_dev) {
     VerifyStage st;   // host: flags (range and curve checks), scalars
-    MI_TRY(mi_verify_open(ctx, "verify: ", vk, in, n, verdicts || !n, decode_malformed, &st));
+    MI_TRY(mi_verify_open(ctx, "verify: ", vk, in, n, verdicts || !n, decode_malformed, &st, pub_dev));
     if (!n) return MI_OK;
     const u32 ns = st.ns, np = verify_pairs_per_proof(st.nc);
     WsCut cut;
@@ -120,7 +121,7 @@ int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, s
     // ---- kSum: the scalar part through the G1 MSM over the resident K[1..], the rest on the host
     std::vector<G1Aff> P(n * np);
     std::vector<G2Aff> Q(n * np);
-    if (ns) MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_scal, st.scal.data(), st.scal.size() * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+    MI_TRY(mi_verify_put_scalars(ctx, st, (Fr *)(ws + off_scal)));
     for (size_t i = 0; i < n; i++) {
         G1Aff msm{Fp::zero(), Fp::zero()};   // no MSM runs for a malformed proof
         if (ns && !st.flags[i]) MI_TRY(mi_verify_msm(ctx, vk->k_dev, (const Fr *)(ws + off_scal) + i * ns, ns, 0, &msm));
@@ -176,8 +177,20 @@ int32_t mi_vk_load(mi_ctx *ctx, const mi_vk_desc *d, mi_vk **out) {
         if (g.is_inf() || !g2_in_subgroup(&g) || !g2_in_subgroup(&gs))
             MI_FAIL(ctx, MI_EINVAL, "vk load: ped[" + std::to_string(k) + "] is not in the r-torsion of the twist");
     }
+    return mi_vk_build(ctx, d, nullptr, out);
+}
+
+}   // extern "C"
+
+int32_t mi_vk_build(mi_ctx *ctx, const mi_vk_desc *d, G1Aff *k_dev_adopt, mi_vk **out) {
+    const G1Aff alpha = g1_of(d->alpha1);
+    const G2Aff beta = g2_of(d->beta2), gamma = g2_of(d->gamma2), delta = g2_of(d->delta2);
     mi_vk *vk = new (std::nothrow) mi_vk;
-    if (!vk) MI_FAIL(ctx, MI_ENOMEM, "vk load: out of host memory");
+    if (!vk) {
+        if (k_dev_adopt) (void)hipFree(k_dev_adopt);
+        MI_FAIL(ctx, MI_ENOMEM, "vk load: out of host memory");
+    }
+    vk->k_dev = k_dev_adopt;
     vk->alpha1 = alpha; vk->beta2 = beta; vk->gamma2 = gamma; vk->delta2 = delta;
     vk->nb_public = d->nb_public; vk->n_commitments = d->n_commitments;
     vk->pc_off.assign((size_t)d->n_commitments + 1, 0);
@@ -186,9 +199,9 @@ int32_t mi_vk_load(mi_ctx *ctx, const mi_vk_desc *d, mi_vk **out) {
     if (d->n_commitments) vk->ped.assign(d->ped, d->ped + d->n_commitments);
     auto body = [&]() -> int32_t {
         const size_t nb = (d->n_k - 1) * sizeof(G1Aff);
-        MI_CHECK_HIP(ctx, hipMalloc((void **)&vk->k_dev, nb + 64));
+        if (!k_dev_adopt) MI_CHECK_HIP(ctx, hipMalloc((void **)&vk->k_dev, nb + 64));
         MI_CHECK_HIP(ctx, hipMalloc((void **)&vk->e_alpha_beta_dev, sizeof(Fp12)));
-        if (nb) MI_CHECK_HIP(ctx, hipMemcpyAsync(vk->k_dev, vk->k.data() + 1, nb, hipMemcpyHostToDevice, ctx->stream));
+        if (nb && !k_dev_adopt) MI_CHECK_HIP(ctx, hipMemcpyAsync(vk->k_dev, vk->k.data() + 1, nb, hipMemcpyHostToDevice, ctx->stream));
         WsCut cut;
         const size_t off_alpha = cut.take(sizeof(alpha)), off_beta = cut.take(sizeof(beta));
         MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], cut.total));
@@ -209,6 +222,8 @@ int32_t mi_vk_load(mi_ctx *ctx, const mi_vk_desc *d, mi_vk **out) {
     *out = vk;
     return MI_OK;
 }
+
+extern "C" {
 
 int32_t mi_vk_free(mi_ctx *ctx, mi_vk *vk) {
     if (!ctx) return MI_EINVAL;

@@ -126,12 +126,12 @@ int32_t mi_g1_scale128_enqueue(mi_ctx *ctx, const G1Aff *p_dev, const u32 *k_dev
 }
 
 int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdict,
-                               uint64_t *first_malformed, const uint8_t *decode_malformed) {
+                               uint64_t *first_malformed, const uint8_t *decode_malformed, const Fr *pub_dev) {
     // refused where it always was, between mi_verify_open's checks of ctx, vk, in, verdict and n and those of the proofs' pointers
     if (ctx && vk && in && verdict && n <= ((size_t)1 << 24) && (uint64_t)n * vk->n_commitments > MI_MSM_MAX_PAIRS)
         MI_FAIL(ctx, MI_EINVAL, "verify combined: n * n_commitments above MI_MSM_MAX_PAIRS (one MSM runs over every commitment of the batch)");
     VerifyStage st;   // host: the range and curve checks of every proof, the scalar matrix
-    MI_TRY(mi_verify_open(ctx, "verify combined: ", vk, in, n, verdict != nullptr, decode_malformed, &st));
+    MI_TRY(mi_verify_open(ctx, "verify combined: ", vk, in, n, verdict != nullptr, decode_malformed, &st, pub_dev));
     const u32 nc = st.nc, ns = st.ns, np = verify_combined_tail_pairs(nc);
     uint8_t own_seed[32];
     if (!seed && n) {
@@ -190,7 +190,7 @@ int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_inp
         if (bytes) MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off, src, bytes, hipMemcpyHostToDevice, ctx->stream));
         return MI_OK;
     };
-    MI_TRY(up(off_scal, st.scal.data(), st.scal.size() * sizeof(Fr)));
+    MI_TRY(mi_verify_put_scalars(ctx, st, (Fr *)(ws + off_scal)));
     MI_TRY(up(off_r, r.data(), n * sizeof(Fr)));
     MI_TRY(up(off_fold, fold.data(), fold.size() * sizeof(Fr)));
     MI_TRY(up(off_krs, krs.data(), n * sizeof(G1Aff)));

@@ -25,16 +25,22 @@ struct mi_vk {
 // How both bodies start: the checks of ctx, vk, in, n and the pointers of every proof (messages under `who`, "verify: " or
 // "verify combined: "; has_verdict = the caller's verdict pointer passes its own rule), then *st over the proofs' references.
 // decode_malformed (may be null): n bytes; a non-zero byte makes proof i malformed before any of its words is read (verify_bytes.hip).
+// pub_dev (may be null; the three bodies pass it on): VerifyStage's device-resident public block.  With it in[i].public_inputs is not read.
 int32_t mi_verify_open(mi_ctx *ctx, const char *who, const mi_vk *vk, const mi_verify_input *in, size_t n, bool has_verdict,
-                       const uint8_t *decode_malformed, VerifyStage *st);
+                       const uint8_t *decode_malformed, VerifyStage *st, const Fr *pub_dev = nullptr);
 // mi_groth16_verify_batch's body (verify.hip)
-int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts, const uint8_t *decode_malformed);
+int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts, const uint8_t *decode_malformed,
+                      const Fr *pub_dev = nullptr);
 // mi_groth16_verify_combined's body (verify_combined.hip): one verdict for the batch.  seed may be null.
 int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdict,
-                               uint64_t *first_malformed, const uint8_t *decode_malformed);
+                               uint64_t *first_malformed, const uint8_t *decode_malformed, const Fr *pub_dev = nullptr);
 // mi_groth16_verify_locate's body (verify_locate.hip): one verdict per proof.  seed and stats may be null.
 int32_t mi_verify_locate_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdicts,
-                             mi_verify_locate_stats *stats, const uint8_t *decode_malformed);
+                             mi_verify_locate_stats *stats, const uint8_t *decode_malformed, const Fr *pub_dev = nullptr);
+// What mi_vk_load and mi_vk_load_stream (vkfile.hip) share: the resident key over a descriptor whose conditions the caller has checked.
+// k_dev_adopt (may be null): K[1 .. n_k) already on the device in an allocation of (n_k - 1) * 64 + 64 bytes, which the key takes
+// (and has freed when the call fails); without it K is uploaded from d->k.
+int32_t mi_vk_build(mi_ctx *ctx, const mi_vk_desc *d, G1Aff *k_dev_adopt, mi_vk **out);
 // verify.hip's kernels for the other translation units, enqueued on ctx->stream: Miller values of n pairs on the device (then, with
 // final_exp, f^d' in place), f^d' in place alone, and flags[i] = 1 where q[i * stride] is not a point of the r-torsion of the twist
 // (else flags[i] stays)
@@ -58,5 +64,27 @@ template <class K, class... A> int32_t mi_launch64(mi_ctx *ctx, K k, size_t lane
     if (!lanes) return MI_OK;
     hipLaunchKernelGGL(k, dim3(mi_blocks_of(lanes, 64)), dim3(64), 0, ctx->stream, args...);
     MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+// A stage's scalar matrix (n x ns, row-major: public_inputs | commitment_values) at a device address, enqueued on ctx->stream.  Without
+// a device-resident public block it is one upload of st.scal.  With one, the public columns are a strided device-to-device copy of the
+// block, the commitment-value columns a strided upload of st.scal, and the row of every proof st.flags marks now is zeroed, as the
+// host's rows of such proofs are.
+inline int32_t mi_verify_put_scalars(mi_ctx *ctx, const VerifyStage &st, Fr *dst_dev) {
+    const size_t n = st.n(), row = (size_t)st.ns * sizeof(Fr);
+    if (!n || !st.ns) return MI_OK;
+    if (!st.pub_dev) {
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(dst_dev, st.scal.data(), st.scal.size() * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
+        return MI_OK;
+    }
+    const size_t pub = (size_t)st.n_pub * sizeof(Fr), cv = (size_t)st.nc * sizeof(Fr);
+    if (pub) MI_CHECK_HIP(ctx, hipMemcpy2DAsync(dst_dev, row, st.pub_dev, pub, pub, n, hipMemcpyDeviceToDevice, ctx->stream));
+    if (cv) MI_CHECK_HIP(ctx, hipMemcpy2DAsync(dst_dev + st.n_pub, row, st.scal.data(), cv, cv, n, hipMemcpyHostToDevice, ctx->stream));
+    for (size_t i = 0; i < n;) {   // one fill per RUN of flagged rows: a batch that is malformed throughout costs one enqueue
+        size_t e = i;
+        while (e < n && st.flags[e]) e++;
+        if (e > i) MI_CHECK_HIP(ctx, hipMemsetAsync(dst_dev + i * st.ns, 0, (e - i) * row, ctx->stream));
+        i = e + 1;
+    }
     return MI_OK;
 }

@@ -148,12 +148,12 @@ size_t max_round_partials(const LocateTree &t, u32 ns) {
 }   // namespace
 
 int32_t mi_verify_locate_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdicts,
-                             mi_verify_locate_stats *stats, const uint8_t *decode_malformed) {
+                             mi_verify_locate_stats *stats, const uint8_t *decode_malformed, const Fr *pub_dev) {
     // the combined call's refusals, in its order
     if (ctx && vk && in && verdicts && n <= ((size_t)1 << 24) && (uint64_t)n * vk->n_commitments > MI_MSM_MAX_PAIRS)
         MI_FAIL(ctx, MI_EINVAL, "verify locate: n * n_commitments above MI_MSM_MAX_PAIRS");
     VerifyStage st;
-    MI_TRY(mi_verify_open(ctx, "verify locate: ", vk, in, n, verdicts || !n, decode_malformed, &st));
+    MI_TRY(mi_verify_open(ctx, "verify locate: ", vk, in, n, verdicts || !n, decode_malformed, &st, pub_dev));
     const u32 nc = st.nc, ns = st.ns, np = verify_combined_tail_pairs(nc), na = verify_locate_arrays(nc), neq = nc ? 2 : 1;
     uint8_t own_seed[32];
     if (!seed && n) {
@@ -200,7 +200,7 @@ int32_t mi_verify_locate_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     st.merge(st.flags.data());
     for (size_t i = 0; i < n; i++)   // a proof the device's check flagged: its scalar row goes the way of its points
-        if (st.flags[i]) std::fill(st.scal.begin() + i * ns, st.scal.begin() + (i + 1) * ns, Fr::zero());
+        if (st.flags[i]) std::fill(st.scal.begin() + i * st.scal_cols, st.scal.begin() + (i + 1) * st.scal_cols, Fr::zero());
     LocatePlan plan(n, st.flags.data(), ctx->locate_round_nodes);
     std::vector<uint8_t> out(n, MI_VERIFY_OK);
     for (size_t i = 0; i < n; i++)
@@ -220,7 +220,7 @@ int32_t mi_verify_locate_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input
             if (nc) std::memcpy(&cm[i * nc], in[i].commitments, (size_t)nc * sizeof(G1Aff));
         }
         MI_TRY(up(off_q, Q.data(), n * sizeof(G2Aff)));   // again: a proof the device's check flagged becomes infinity
-        MI_TRY(up(off_scal, st.scal.data(), st.scal.size() * sizeof(Fr)));
+        MI_TRY(mi_verify_put_scalars(ctx, st, (Fr *)(ws + off_scal)));
         MI_TRY(up(off_r, r.data(), n * sizeof(Fr)));
         MI_TRY(up(off_fold, fold.data(), fold.size() * sizeof(Fr)));
         MI_TRY(up(off_krs, krs.data(), n * sizeof(G1Aff)));
@@ -295,7 +295,11 @@ int32_t mi_verify_locate_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input
         std::vector<mi_verify_input> alone(sus.size());
         std::vector<uint8_t> vd(sus.size(), 255);
         for (size_t t = 0; t < sus.size(); t++) alone[t] = in[sus[t]];
-        MI_TRY(mi_verify_run(ctx, vk, alone.data(), alone.size(), vd.data(), nullptr));
+        // a device-resident public block: the suspects' rows, gathered over the scalar matrix, which the rounds have finished with
+        Fr *sus_pub = st.pub_dev ? (Fr *)(ws + off_scal) : nullptr;
+        for (size_t t = 0; sus_pub && t < sus.size(); t++)
+            MI_CHECK_HIP(ctx, hipMemcpyAsync(sus_pub + t * st.n_pub, st.pub_dev + sus[t] * st.n_pub, (size_t)st.n_pub * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+        MI_TRY(mi_verify_run(ctx, vk, alone.data(), alone.size(), vd.data(), nullptr, sus_pub));
         for (size_t t = 0; t < sus.size(); t++) {
             out[sus[t]] = vd[t];
             if (vd[t] == MI_VERIFY_PAIRING || vd[t] == MI_VERIFY_PEDERSEN) plan.stats.rejected++;

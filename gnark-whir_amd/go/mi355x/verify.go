@@ -6,6 +6,8 @@
 // the host -- the hash-to-field of every commitment (with the public committed values) and the fold challenge -- and hands the rest to
 // mi_groth16_verify.  VerifyBytes takes Proof.WriteTo's bytes and leaves decoding and hashing to the device (mi_groth16_verify_bytes).
 // VerifyBytesCombined judges a whole batch of such proofs with ONE verdict (mi_groth16_verify_bytes_combined).
+// VerifyFiles and VerifyFilesCombined take the public witness as witness.WriteTo's bytes too (include/mi355x_groth16_vkfile.h): with a
+// key from LoadVerifyingKeyStream (keyfile.go) nothing of gnark is decoded on the host.
 package mi355x
 
 /*
@@ -13,6 +15,7 @@ package mi355x
 #include "mi355x_groth16_verify.h"
 #include "mi355x_groth16_verify_bytes.h"
 #include "mi355x_groth16_verify_combined.h"
+#include "mi355x_groth16_vkfile.h"
 */
 import "C"
 
@@ -255,6 +258,64 @@ func VerifyBytesCombined(vk *VerifyingKey, proofs [][]byte, publicWitnesses []fr
 	var verdict C.uint8_t
 	var first C.uint64_t
 	rc := C.mi_groth16_verify_bytes_combined(vk.ctx, vk.dev, &in[0], C.size_t(len(proofs)), nil, &verdict, &first)
+	if err := status(vk.ctx, rc); err != nil {
+		return err
+	}
+	if verdict != C.MI_VERIFY_OK {
+		return ErrBatchRejected{Verdict: int(verdict), FirstMalformed: uint64(first)}
+	}
+	return nil
+}
+
+// VerifyFiles replaces groth16.Verify for a verifier that holds files: proof is Proof.WriteTo's bytes, witness is witness.WriteTo's
+// (public, or full: the secret part is not read).  The public inputs go up as bytes and become Montgomery words on the device; a value
+// that is not below r, or a header whose count is not the key's, rejects the proof as malformed.
+func VerifyFiles(vk *VerifyingKey, proof []byte, witness []byte) error {
+	if len(proof) == 0 || len(witness) == 0 {
+		return errors.New("mi355x: empty proof or witness")
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&proof[0])
+	pin.Pin(&witness[0])
+	var verdict C.uint8_t
+	rc := C.mi_groth16_verify_files(vk.ctx, vk.dev, (*C.uint8_t)(unsafe.Pointer(&proof[0])), C.size_t(len(proof)),
+		(*C.uint8_t)(unsafe.Pointer(&witness[0])), C.size_t(len(witness)), &verdict)
+	if err := status(vk.ctx, rc); err != nil {
+		return err
+	}
+	if verdict != C.MI_VERIFY_OK {
+		return ErrRejected{Verdict: int(verdict)}
+	}
+	return nil
+}
+
+// VerifyFilesCombined is VerifyBytesCombined over (proof bytes, witness bytes) pairs.
+func VerifyFilesCombined(vk *VerifyingKey, proofs [][]byte, witnesses [][]byte) error {
+	if len(proofs) != len(witnesses) {
+		return errors.New("mi355x: one witness per proof")
+	}
+	if len(proofs) == 0 {
+		return nil
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	in := (*[1 << 24]C.mi_verify_files_input)(C.calloc(C.size_t(len(proofs)), C.size_t(unsafe.Sizeof(C.mi_verify_files_input{}))))
+	defer C.free(unsafe.Pointer(in))
+	for i, p := range proofs {
+		if len(p) == 0 || len(witnesses[i]) == 0 {
+			return errors.New("mi355x: empty proof or witness")
+		}
+		pin.Pin(&p[0])
+		pin.Pin(&witnesses[i][0])
+		in[i].proof = (*C.uint8_t)(unsafe.Pointer(&p[0]))
+		in[i].proof_len = C.size_t(len(p))
+		in[i].witness = (*C.uint8_t)(unsafe.Pointer(&witnesses[i][0]))
+		in[i].witness_len = C.size_t(len(witnesses[i]))
+	}
+	var verdict C.uint8_t
+	var first C.uint64_t
+	rc := C.mi_groth16_verify_files_combined(vk.ctx, vk.dev, &in[0], C.size_t(len(proofs)), nil, &verdict, &first)
 	if err := status(vk.ctx, rc); err != nil {
 		return err
 	}

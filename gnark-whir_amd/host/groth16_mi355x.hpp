@@ -22,6 +22,7 @@
 #include "../../include/mi355x_groth16_r1cs.h"
 #include "../../include/mi355x_groth16_verify.h"
 #include "../../include/mi355x_groth16_verify_bytes.h"
+#include "../../include/mi355x_groth16_vkfile.h"
 #include "../../include/mi355x_groth16_verify_combined.h"
 #include "../../include/mi355x_groth16_debug.h"   // (this mirror is the TEST side: generators and knobs)
 
@@ -213,6 +214,11 @@ inline Proof ProveW(const Context &ctx, const ProvingKey &pk, const ResidentR1CS
 class VerifyingKey {
   public:
     VerifyingKey(const Context &ctx, const mi_vk_desc &desc) : ctx_(ctx) { ctx_.check(mi_vk_load(ctx_.get(), &desc, &vk_)); }
+    // from VerifyingKey.WriteTo's or WriteRawTo's bytes (include/mi355x_groth16_vkfile.h): decoded and checked on the device, the committed
+    // lists installed.  flags: MI_KEYFILE_NO_SUBGROUP_CHECK, MI_KEYFILE_SUBGROUP_BY_R.  Throws MI_EINVAL naming the field that was refused.
+    VerifyingKey(const Context &ctx, const std::vector<uint8_t> &stream, uint32_t flags = 0) : ctx_(ctx) {
+        ctx_.check(mi_vk_load_stream(ctx_.get(), stream.data(), stream.size(), flags, &vk_));
+    }
     ~VerifyingKey() { if (vk_) mi_vk_free(ctx_.get(), vk_); }
     VerifyingKey(const VerifyingKey &) = delete;
     VerifyingKey &operator=(const VerifyingKey &) = delete;
@@ -276,6 +282,65 @@ inline uint8_t VerifyCombined(const Context &ctx, const VerifyingKey &vk, const 
     uint8_t verdict = MI_VERIFY_MALFORMED;
     ctx.check(mi_groth16_verify_combined(ctx.get(), vk.get(), in.data(), in.size(), seed, &verdict, firstMalformed));
     return verdict;
+}
+// groth16.Verify from the two files a verifier holds beside the key (include/mi355x_groth16_vkfile.h): Proof.WriteTo's bytes and
+// witness.WriteTo's.  The public inputs go up as bytes and are decoded on the device.  Throws MI_EINVAL for a framing error (a length
+// that is not the key's proof length, resp. 12 + 32 n of the witness's own header); anything else is a verdict.
+struct FileProof {
+    std::vector<uint8_t> proof;          // Proof::WriteTo
+    std::vector<uint8_t> witness;        // witness.WriteTo, public or full
+};
+inline uint8_t VerifyFiles(const Context &ctx, const VerifyingKey &vk, const std::vector<uint8_t> &proof, const std::vector<uint8_t> &witness) {
+    uint8_t verdict = MI_VERIFY_MALFORMED;
+    ctx.check(mi_groth16_verify_files(ctx.get(), vk.get(), proof.data(), proof.size(), witness.data(), witness.size(), &verdict));
+    return verdict;
+}
+inline std::vector<mi_verify_files_input> FilesInputs(const std::vector<FileProof> &proofs) {
+    std::vector<mi_verify_files_input> in(proofs.size());
+    for (size_t i = 0; i < proofs.size(); i++)
+        in[i] = mi_verify_files_input{proofs[i].proof.data(), proofs[i].proof.size(), proofs[i].witness.data(), proofs[i].witness.size()};
+    return in;
+}
+inline std::vector<uint8_t> VerifyFilesBatch(const Context &ctx, const VerifyingKey &vk, const std::vector<FileProof> &proofs) {
+    const auto in = FilesInputs(proofs);
+    std::vector<uint8_t> verdicts(proofs.size(), MI_VERIFY_MALFORMED);
+    ctx.check(mi_groth16_verify_files_batch(ctx.get(), vk.get(), in.data(), in.size(), verdicts.data()));
+    return verdicts;
+}
+inline uint8_t VerifyFilesCombined(const Context &ctx, const VerifyingKey &vk, const std::vector<FileProof> &proofs, const uint8_t *seed = nullptr,
+                                   uint64_t *firstMalformed = nullptr) {
+    const auto in = FilesInputs(proofs);
+    uint8_t verdict = MI_VERIFY_MALFORMED;
+    ctx.check(mi_groth16_verify_files_combined(ctx.get(), vk.get(), in.data(), in.size(), seed, &verdict, firstMalformed));
+    return verdict;
+}
+inline std::vector<uint8_t> VerifyFilesLocate(const Context &ctx, const VerifyingKey &vk, const std::vector<FileProof> &proofs, const uint8_t *seed = nullptr,
+                                              mi_verify_locate_stats *stats = nullptr) {
+    const auto in = FilesInputs(proofs);
+    std::vector<uint8_t> verdicts(proofs.size(), MI_VERIFY_MALFORMED);
+    ctx.check(mi_groth16_verify_files_locate(ctx.get(), vk.get(), in.data(), in.size(), seed, verdicts.data(), stats));
+    return verdicts;
+}
+// VerifyingKey.WriteTo (MI_KEYFILE_COMPRESSED) / WriteRawTo (MI_KEYFILE_RAW) for a key in host memory (mi_vk_write)
+inline std::vector<uint8_t> WriteVerifyingKey(const Context &ctx, const mi_vk_file_desc &desc, uint32_t encoding = MI_KEYFILE_COMPRESSED) {
+    size_t len = 0;
+    if (mi_vk_stream_size(&desc, encoding, &len) != MI_OK) throw Error(MI_EINVAL, "WriteVerifyingKey: more than MI_PK_RAW_MAX_COMMITMENTS commitments or an unknown encoding");
+    std::vector<uint8_t> out(len);
+    ctx.check(mi_vk_write(ctx.get(), &desc, encoding, out.data(), out.size(), &len));
+    return out;
+}
+// witness.WriteTo of a public witness, and its inverse: false for a header that disagrees with the length or a value not below r
+inline std::vector<uint8_t> WritePublicWitness(const std::vector<mi_fr> &values) {
+    std::vector<uint8_t> out(12 + 32 * values.size());
+    if (mi_public_witness_write(values.data(), values.size(), out.data(), out.size(), nullptr) != MI_OK) throw Error(MI_EINVAL, "WritePublicWitness: more than 2^32 - 1 values");
+    return out;
+}
+inline bool ReadPublicWitness(const std::vector<uint8_t> &bytes, std::vector<mi_fr> &out) {
+    out.resize(bytes.size() / 32);
+    size_t n = 0;
+    const bool ok = mi_public_witness_read(bytes.data(), bytes.size(), out.data(), out.size(), &n) == MI_OK;
+    out.resize(ok ? n : 0);
+    return ok;
 }
 // The inverse of Proof::WriteTo (mi_proof_read): false when the bytes are not one well-formed proof with nCommitments commitments
 inline bool ReadProof(const std::vector<uint8_t> &bytes, uint32_t nCommitments, Proof &out) {

@@ -81,6 +81,12 @@ int32_t mi_debug_fp12_op_dev(mi_ctx *ctx, int op, mi_fp *z_dev, const mi_fp *x_d
 int32_t mi_debug_decode_g1_dev(mi_ctx *ctx, const uint8_t *enc_dev, size_t n, mi_g1_affine *out_dev, uint8_t *bad_dev);
 int32_t mi_debug_decode_g2_dev(mi_ctx *ctx, const uint8_t *enc_dev, size_t n, mi_g2_affine *out_dev, uint8_t *bad_dev);
 int32_t mi_debug_hash_to_field_dev(mi_ctx *ctx, const uint8_t *dst_dev, uint32_t dst_len, const uint8_t *msgs_dev, size_t msg_len, size_t n, mi_fr *out_dev);
+/* the decoder of the public witness behind mi_groth16_verify_files* (mi355x_groth16_vkfile.h; csrc/witness_ops.cuh, one value per lane;
+ * the host build tests/emu/emu_witness.cpp runs the same body).  Device pointers of any alignment, enqueued on the context's stream.
+ * values_dev: n witnesses of n_pub values of 32 bytes, big-endian, back to back (no headers) -> out_dev, n x n_pub Montgomery mi_fr; a
+ * value not below r leaves zero and sets bad_dev[i] of its witness.  The kernel only ever sets a byte: clear bad_dev first.
+ * MI_EINVAL for null buffers, n > 2^24 or n * n_pub > 2^32. */
+int32_t mi_debug_witness_decode_dev(mi_ctx *ctx, const uint8_t *values_dev, size_t n, uint32_t n_pub, mi_fr *out_dev, uint8_t *bad_dev);
 
 /* the two kernels mi355x_groth16_verify_combined.h adds in front of and behind the Miller loops (csrc/verify_combined.hip), alone; the
  * host build of the tests (tests/emu/emu_verify_combined.cpp) runs the same bodies.  Device pointers, enqueued on the context's stream.

@@ -18,7 +18,7 @@
  * EXPERIMENTAL, as mi_pk_load_raw: THE LAYOUT IS RECALLED, NOT PINNED TO gnark (no gnark on the machines this was written on); the
  * caveat of oracle/pk_raw.py and csrc/pk_raw.hip about the bit order of the masks carries over unchanged.
  *
- * Decoding a VERIFYING key from bytes is not here (mi_vk_load takes points): the follow-up. */
+ * A VERIFYING key as bytes (and the public witness as bytes) is mi355x_groth16_vkfile.h: mi_vk_load_stream, mi_vk_write. */
 #ifndef MI355X_GROTH16_KEYFILE_H
 #define MI355X_GROTH16_KEYFILE_H
 #include "mi355x_groth16.h"

@@ -8,6 +8,7 @@ ALTERNATING, with the locate call's stats; then, for the larger batches with b =
 512 per round (mi_debug_set_locate_round_nodes): the column the default MI_LOCATE_ROUND_NODES is read from.
 
     python tools/verify_probe.py [--write profiles/verify.txt] [--batches 64,1024,16384] [--runs 5]
+    python tools/verify_probe.py --files [--write profiles/verify.txt]      the files leg alone (files_leg below); --write APPENDS
 
 A solvable circuit of 1000 constraints (domain 2^10, 4 public inputs, one BSB22 commitment; tests/r1cs_cases.py), its key from
 mi_groth16_setup, one proof through the prover pool.  After a warm-up call, the median wall time of `--runs` calls of one verification
@@ -35,8 +36,101 @@ from helpers import fr_arr, fr_vals, g1_pts  # noqa: E402
 from gpu_common import load_binding  # noqa: E402
 
 
+def files_leg(B, args):
+    """--files: the public inputs as witness bytes (mi_groth16_verify_files_combined, include/mi355x_groth16_vkfile.h) against Montgomery
+    words prepared on the host, on a key with 4096 public inputs (SURVEY 8d's count) and one commitment.  The key is made of seeded
+    points, not of a circuit, and the proof is five valid points: the verdict is 1 in every leg (asserted equal) and the work is that of
+    an accepted batch -- the arithmetic does not depend on the data.  Per batch, medians of `--runs` calls after one warm-up, the calls
+    ALTERNATING:
+      (a) verify_bytes_combined, the Montgomery inputs prepared beforehand     (b) (a) + the host time of mi_public_witness_read over the batch
+      (c) verify_files_combined on the same proofs and the witnesses' bytes
+    and, in a group of its own after them (back to back, so that no host-only leg sits in front of a launch), k_witness_decode alone
+    over the batch's values through mi_debug_witness_decode_dev, in launches of at most 1024 witnesses;
+    then mi_vk_load_stream (compressed, all checks) against mi_vk_load on the same key.  With --write the lines are APPENDED."""
+    import pyref as P
+    from helpers import g1_arr, g2_arr
+    from benchlib.clocks import ClockSampler
+    C = B.C
+    ctx = B.Context(0)
+    n_pub, nc = 4096, 1
+    rnd = np.random.default_rng(4096)
+    k = cref.gen_g1(n_pub + 1 + nc, 21)
+    g2 = lambda e: g2_arr([P.g2_mul(P.G2_GEN, e)])[0]
+    vk = {"alpha1": cref.gen_g1(1, 22)[0], "beta1": cref.gen_g1(1, 23)[0], "delta1": cref.gen_g1(1, 24)[0], "beta2": g2(2), "gamma2": g2(3), "delta2": g2(5), "k": k}
+    ped = np.stack([np.stack([g2(1), g2(7)])])
+    vkh = ctx.vk_load(vk, n_pub + 1, ped)
+    vkh.set_public_committed([[]])
+    pts = cref.gen_g1(4, 25)
+    data = B.proof_write(np.concatenate([pts[0], g2(11), pts[1]]), commitments=np.ascontiguousarray(pts[2]).reshape(1, 8), pok=np.ascontiguousarray(pts[3]))
+    pub_ints = [int.from_bytes(rnd.bytes(31), "big") for _ in range(n_pub)]
+    pub = fr_arr(pub_ints)
+    wit = B.public_witness_write(pub)
+    seed = bytes(range(32))
+    lines = [f"verify from files (tools/verify_probe.py --files): {n_pub} public inputs, {nc} commitment, a key of seeded points and a proof of valid points",
+             f"(verdict 1 in every leg; the work is an accepted batch's); median (min .. max) ms of {args.runs} calls after one warm-up, the legs (a), read, (c) alternating, the kernel timed apart; host clocks"]
+    print("\n".join(lines), flush=True)
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+
+    def timed_group(fns):
+        for fn in fns:
+            fn()
+        ts = [[] for _ in fns]
+        for _ in range(args.runs):
+            for fn, t_ in zip(fns, ts):
+                t = time.perf_counter(); fn(); t_.append((time.perf_counter() - t) * 1e3)
+        return [(statistics.median(t_), min(t_), max(t_)) for t_ in ts]
+
+    clocks = ClockSampler(0).start()
+    pbuf = C.create_string_buffer(data, len(data)); wbuf = C.create_string_buffer(wit, len(wit))
+    for nb in [int(x) for x in args.batches.split(",") if x]:
+        barr = (B.VerifyBytesInput * nb)(); farr = (B.VerifyFilesInput * nb)()
+        for i in range(nb):
+            barr[i].proof, barr[i].proof_len, barr[i].public_inputs = C.addressof(pbuf), len(data), pub.ctypes.data
+            farr[i].proof, farr[i].proof_len, farr[i].witness, farr[i].witness_len = C.addressof(pbuf), len(data), C.addressof(wbuf), len(wit)
+        va, vc = C.c_uint8(255), C.c_uint8(255)
+        out = np.zeros((n_pub, 4), np.uint64); got = C.c_size_t()
+        lib = ctx.lib
+        acall = lambda: ctx._ck(lib.mi_groth16_verify_bytes_combined(ctx.h, vkh.h, barr, C.c_size_t(nb), seed, C.byref(va), None))
+        ccall = lambda: ctx._ck(lib.mi_groth16_verify_files_combined(ctx.h, vkh.h, farr, C.c_size_t(nb), seed, C.byref(vc), None))
+
+        def hcall():   # what a caller of (a) does first: every witness of the batch through the host reader
+            for _ in range(nb):
+                assert lib.mi_public_witness_read(wbuf, C.c_size_t(len(wit)), out.ctypes.data_as(C.c_void_p), C.c_size_t(n_pub), C.byref(got)) == 0
+        din = ctx.to_dev(np.frombuffer(wit[12:] * min(nb, 1024), np.uint8)); dout = ctx.alloc(32 * n_pub * min(nb, 1024)); dbad = ctx.to_dev(np.zeros(max(nb, 32), np.uint8))
+        reps = (nb + 1023) // 1024   # the debug entry over at most 1024 witnesses at a time: the same lanes, in `reps` launches
+
+        def kcall():
+            for _ in range(reps):
+                ctx._ck(lib.mi_debug_witness_decode_dev(ctx.h, C.c_void_p(din.ptr), C.c_size_t(min(nb, 1024)), C.c_uint32(n_pub), C.c_void_p(dout.ptr), C.c_void_p(dbad.ptr)))
+            ctx.sync()
+        (a, alo, ahi), (h, hlo, hhi), (c, clo, chi) = timed_group([acall, hcall, ccall])
+        ((kms, klo, khi),) = timed_group([kcall])   # apart from the alternation: behind seconds of host-only work the device has idled
+        assert va.value == vc.value == B.VERIFY_PAIRING and np.array_equal(out, pub)
+        for b in (din, dout, dbad):
+            b.free()
+        emit(f"batch of {nb:6d}   (a) bytes_combined {a:10.3f} ({alo:.3f} .. {ahi:.3f})   host witness_read {h:10.3f} ({hlo:.3f} .. {hhi:.3f})   (b) = (a) + read {a + h:10.3f}")
+        emit(f"                  (c) files_combined {c:10.3f} ({clo:.3f} .. {chi:.3f})   (c) / (b) {c / (a + h):6.3f}   (c) / (a) {c / a:6.3f}   "
+             f"k_witness_decode alone {kms:8.3f} ({klo:.3f} .. {khi:.3f}), {100 * kms / c:5.2f} % of (c)")
+    # the key: from its compressed stream, every check on, against mi_vk_load over the same points
+    blob = ctx.vk_write(vk, n_pub + 1, ped, [[]], B.KEYFILE_COMPRESSED)
+    (ls, llo, lhi), (lp, plo, phi) = timed_group([lambda: ctx.vk_load_stream(blob).free(), lambda: ctx.vk_load(vk, n_pub + 1, ped).free()])
+    emit(f"key of {n_pub + 1 + nc} K points   mi_vk_load_stream (compressed, {len(blob)} bytes, all checks) {ls:9.3f} ({llo:.3f} .. {lhi:.3f})   "
+         f"mi_vk_load over the points {lp:9.3f} ({plo:.3f} .. {phi:.3f})")
+    emit(f"clocks {clocks.stop()}")
+    emit("NOT MEASURED: kernel times by a profiler (every figure is a host clock around a call that ends in a device synchronise), other public-input "
+         "counts, any figure from gnark")
+    if args.write:
+        with open(args.write, "a") as f:
+            f.write("\n" + "\n".join(lines) + "\n")
+    vkh.free(); ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--files", action="store_true", help="the files leg alone (see files_leg); --write appends")
     ap.add_argument("--write")
     ap.add_argument("--batches", default="64,1024,16384")
     ap.add_argument("--runs", type=int, default=5)
@@ -45,6 +139,8 @@ def main():
     ap.add_argument("--no-locate", action="store_true", help="skip the locate legs")
     args = ap.parse_args()
     B = load_binding()
+    if args.files:
+        return files_leg(B, args)
     ctx = B.Context(0)
     n, nab, nb_public = 1000, 400, 5
     r1cs = RC.skewed_r1cs(n, nab, nb_public, 11, long_lens=(16, 17, 64), commitments=1, n_committed=32)
