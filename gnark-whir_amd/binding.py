@@ -65,6 +65,10 @@ NO_BAD_INDEX = (1 << 64) - 1
 VKFILE_EXPORTS = ["mi_vk_stream_inspect", "mi_vk_stream_size", "mi_vk_write", "mi_vk_load_stream", "mi_groth16_setup_to_streams",
                   "mi_public_witness_write", "mi_public_witness_read", "mi_groth16_verify_files", "mi_groth16_verify_files_batch",
                   "mi_groth16_verify_files_combined", "mi_groth16_verify_files_locate"]
+# include/mi355x_groth16_phase2.h (the keys from a powers-of-tau SRS: gnark's mpcsetup phase 2 on the device)
+PHASE2_EXPORTS = ["mi_phase2_init", "mi_phase2_contribute", "mi_phase2_seal", "mi_phase2_to_streams", "mi_phase2_free", "mi_phase2_get_stats",
+                  "mi_phase2_get_array"]
+PHASE2_G1_A, PHASE2_G1_B, PHASE2_G2_B, PHASE2_G1_K, PHASE2_G1_Z, PHASE2_VK_K, PHASE2_BASIS = 0, 1, 2, 3, 4, 5, 6
 
 
 class PkDesc(C.Structure):
@@ -161,6 +165,30 @@ class SetupExponents(C.Structure):
 class SetupStats(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("upload_ms", "lagrange_ms", "sparse_ms", "elementwise_ms", "points_ms", "handover_ms", "total_ms",
                                          "sparse_sort_ms", "sparse_sum_ms")] + [(n, C.c_uint64) for n in ("entries", "long_columns", "chunks")]
+
+
+class SrsDesc(C.Structure):
+    _fields_ = [("tau_g1", C.c_void_p), ("alpha_tau_g1", C.c_void_p), ("beta_tau_g1", C.c_void_p), ("tau_g2", C.c_void_p), ("beta_g2", C.c_uint64 * 16)] + [
+        (n, C.c_uint64) for n in ("n_tau_g1", "n_alpha_tau_g1", "n_beta_tau_g1", "n_tau_g2")]
+
+
+class Phase2Stats(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("upload_ms", "check_ms", "point_ntt_g1_ms", "point_ntt_g2_ms", "sparse_g1_ms", "sparse_g2_ms", "z_ms",
+                                         "affine_ms", "total_ms")] + [("pad_", C.c_uint32)] + [(n, C.c_uint64) for n in ("entries", "long_columns", "chunks", "peak_bytes")]
+
+
+def _srs_desc(srs: dict):
+    """srs: tau_g1 (n, 8), alpha_tau_g1, beta_tau_g1 (n, 8), tau_g2 (n, 16), beta_g2 (16,) uint64 Montgomery; a row may be None, and
+    n_<row> overrides the count the array has -> (SrsDesc, the arrays it points into)"""
+    d = SrsDesc(); keep = []
+    for name in ("tau_g1", "alpha_tau_g1", "beta_tau_g1", "tau_g2"):
+        a = srs.get(name)
+        if a is not None:
+            a = _u64(a); keep.append(a)
+            setattr(d, name, a.ctypes.data)
+        setattr(d, "n_" + name, int(srs.get("n_" + name, 0 if a is None else a.shape[0])))
+    d.beta_g2 = (C.c_uint64 * 16)(*[int(v) for v in _u64(srs["beta_g2"]).reshape(16)])
+    return d, keep
 
 
 class R1csStats(C.Structure):
@@ -783,6 +811,53 @@ class Context:
             return do.download((n, n_pub, 4)) if n * n_pub else np.zeros((n, n_pub, 4), np.uint64), db.download((max(n, 32),), np.uint8)[:n]
         finally:
             for b in (de, do, db): b.free()
+
+    # ---- the keys from a powers-of-tau SRS (include/mi355x_groth16_phase2.h)
+    def phase2_init(self, r1cs: dict, srs: dict, sigma=(), flags=0):
+        """mi_phase2_init: the dict setup() takes, the SRS rows (_srs_desc), one sigma per commitment -> the ceremony state's handle"""
+        d, keep = _r1cs_desc(r1cs); sd, keep2 = _srs_desc(srs); h = C.c_void_p()
+        sg = _u64(np.array(sigma, np.uint64).reshape(-1, 4)) if len(sigma) else None
+        self._ck(self.lib.mi_phase2_init(self.h, C.byref(d), C.byref(sd), _p(sg), C.c_uint32(flags), C.byref(h)))
+        return h
+
+    def phase2_contribute(self, st, delta, sigma_factor=None):
+        sf = None if sigma_factor is None else _u64(np.array(sigma_factor, np.uint64).reshape(-1, 4))
+        self._ck(self.lib.mi_phase2_contribute(self.h, st, _p(_u64(delta)), _p(sf)))
+
+    def phase2_seal(self, st, n_k, n_commitments=0):
+        """mi_phase2_seal -> (key handle, [Pedersen key handles], vk dict as setup()); n_k = nb_public + n_commitments"""
+        vk_k = np.zeros((max(n_k, 1), 8), np.uint64)
+        vk = VkOut(); vk.k = vk_k.ctypes.data; vk.k_cap = n_k
+        h = C.c_void_p(); ped = (C.c_void_p * MAX_COMMITMENTS)()
+        self._ck(self.lib.mi_phase2_seal(self.h, st, C.byref(h), ped, C.byref(vk)))
+        vkd = {n: np.array(getattr(vk, n), dtype=np.uint64) for n in ("alpha1", "beta2", "gamma2", "delta2")}
+        vkd["k"] = vk_k[:int(vk.n_k)].copy()
+        return h, [C.c_void_p(ped[i]) for i in range(n_commitments)], vkd
+
+    def phase2_to_streams(self, st, encoding=KEYFILE_COMPRESSED, cap=1 << 24, vk_cap=1 << 20):
+        """mi_phase2_to_streams -> (the proving key's stream, the verifying key's stream)"""
+        need = C.c_size_t(); vk_need = C.c_size_t()
+        out = (C.c_uint8 * max(cap, 1))(); vk_out = (C.c_uint8 * max(vk_cap, 1))()
+        self.keyfile_len = self.vkfile_len = None
+        rc = self.lib.mi_phase2_to_streams(self.h, st, C.c_uint32(encoding), out, C.c_size_t(cap), C.byref(need), vk_out, C.c_size_t(vk_cap), C.byref(vk_need))
+        self.keyfile_len, self.vkfile_len = int(need.value), int(vk_need.value)
+        self._ck(rc)
+        return C.string_at(out, need.value), C.string_at(vk_out, vk_need.value)
+
+    def phase2_array(self, st, which):
+        """mi_phase2_get_array: one array of the state -> (n, 8) or (n, 16) uint64"""
+        n = C.c_uint64()
+        self._ck(self.lib.mi_phase2_get_array(self.h, st, C.c_uint32(which), None, C.c_uint64(0), C.byref(n)))
+        out = np.zeros((int(n.value), 16 if which == PHASE2_G2_B else 8), np.uint64)
+        self._ck(self.lib.mi_phase2_get_array(self.h, st, C.c_uint32(which), _p(out) if n.value else None, n, C.byref(n)))
+        return out
+
+    def phase2_free(self, st):
+        self._ck(self.lib.mi_phase2_free(self.h, st))
+
+    def phase2_stats(self):
+        st = Phase2Stats(); self._ck(self.lib.mi_phase2_get_stats(self.h, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in Phase2Stats._fields_ if n != "pad_"}
 
     def keyfile_stats(self):
         st = KeyfileStats(); self._ck(self.lib.mi_keyfile_get_stats(self.h, C.byref(st)))

@@ -14,6 +14,7 @@
 #include "../../include/mi355x_groth16_setup.h"
 #include "../../include/mi355x_groth16_r1cs.h"
 #include "../../include/mi355x_groth16_keyfile.h"
+#include "../../include/mi355x_groth16_phase2.h"
 
 struct DevBuf {             // growable device scratch owned by the ctx (no hipMalloc in the hot path
     void *p = nullptr;      // after warm-up: buffers only ever grow)
@@ -127,6 +128,7 @@ struct mi_ctx {
     std::mutex err_m;          // a prove enqueues its MSM groups from helper threads (prove.hip): failures there report through mi_set_err
     mi_stats stats{};
     mi_setup_stats setup_stats{};   // last mi_groth16_setup[_exponents] call (setup.hip)
+    mi_phase2_stats phase2_stats{};   // last mi_phase2_init call (phase2.hip)
     mi_keyfile_stats keyfile_stats{};   // last mi_pk_load_stream / mi_pk_write_dev call (keyfile.hip)
     mi_r1cs_stats r1cs_stats{};     // last evaluation of a resident R1CS on this context (r1cs.hip); eval_ms is read from ev[EV_R1CS_BEGIN], ev[EV_R1CS_END] on request
     bool r1cs_timed = false;

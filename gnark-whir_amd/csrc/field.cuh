@@ -579,6 +579,17 @@ MI_HD Fe<P> fe_pow(const Fe<P> &x, const u32 e[8]) {
     }
     return acc;
 }
+// x^e for a 64-bit exponent, by its bits from the bottom
+template <class P>
+MI_HD Fe<P> fe_pow_u64(Fe<P> x, u64 e) {
+    Fe<P> acc = Fe<P>::one();
+    while (e) {
+        if (e & 1) acc = acc * x;
+        x = fe_sqr(x);
+        e >>= 1;
+    }
+    return acc;
+}
 template <class P>
 MI_HD Fe<P> fe_inv(const Fe<P> &x) {  // Fermat, 0 -> 0
     u32 e[8];

@@ -24,6 +24,7 @@
 #include "../../include/mi355x_groth16_vkfile.h"
 #include "scan_u32.cuh"
 #include "sparse_fr.cuh"
+#include "dev_arena.h"
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -34,15 +35,6 @@ namespace {
 
 constexpr u32 LAG_RUN = 64;    // rows per thread of k_lagrange: one inversion per run
 
-MI_D Fr fr_pow_u64(Fr b, u64 e) {
-    Fr acc = Fr::one();
-    while (e) {
-        if (e & 1) acc = acc * b;
-        b = fe_sqr(b);
-        e >>= 1;
-    }
-    return acc;
-}
 // cnt[key] += 1 for every active lane; returns the value this lane's increment saw.  Lanes of one wave that share a key are served by
 // ONE atomic: each round takes the first active lane's key, its lanes count themselves with a ballot, the lowest adds the count.
 MI_D u32 wave_claim(u32 *cnt, u32 key) {
@@ -68,7 +60,7 @@ MI_D u32 wave_claim(u32 *cnt, u32 key) {
 __global__ void __launch_bounds__(64) k_lagrange(Fr *L, u64 nc, u32 T, Fr w, Fr wT, Fr wTinv, Fr tau, Fr lam) {
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T || t >= nc) return;
-    Fr x = fr_pow_u64(w, t), p = Fr::one();
+    Fr x = fe_pow_u64(w, t), p = Fr::one();
     u32 cnt = 0;
     for (u64 i = t; i < nc && cnt < LAG_RUN; i += T, cnt++) {   // L[i] <- product of the run's earlier denominators
         st_fr(L + i, p);
@@ -223,24 +215,6 @@ int32_t make_plan(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_trapdoor *td, Pla
     return MI_OK;
 }
 
-// device allocations of one call, freed when it returns (the key takes what it adopts out of the list)
-struct Arena {
-    std::vector<void *> live;
-    ~Arena() { for (void *p : live) if (p) (void)hipFree(p); }
-    int32_t alloc(mi_ctx *ctx, void **out, size_t bytes) {
-        *out = nullptr;
-        MI_CHECK_HIP(ctx, hipMalloc(out, bytes ? bytes : 64));
-        live.push_back(*out);
-        return MI_OK;
-    }
-    template <class T> int32_t alloc(mi_ctx *ctx, T **out, size_t count) { return alloc(ctx, (void **)out, count * sizeof(T)); }
-    void release(void *p) {   // free now
-        if (!p) return;
-        for (void *&q : live) if (q == p) { q = nullptr; (void)hipFree(p); return; }
-    }
-    void disown(void *p) { for (void *&q : live) if (q == p) q = nullptr; }
-};
-
 struct Timer {   // HIP events on the context's stream, one per phase boundary
     enum { UP0, UP1, LAG, SUM, ELEM, POINTS, DONE, COUNT };
     hipEvent_t ev[COUNT]{};
@@ -319,11 +293,7 @@ int32_t run_fr_half(mi_ctx *ctx, const mi_r1cs_desc *d, const Plan &pl, Arena &a
             MI_CHECK_HIP(ctx, hipMemcpyAsync(cf, mats[k]->coeff, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
         }
         MI_CHECK_HIP(ctx, hipEventRecord(e1, st));
-        MI_CHECK_HIP(ctx, hipMemsetAsync(cnt, 0, nw * 4, st));
-        if (nnz) hipLaunchKernelGGL(k_col_count, dim3(mi_blocks_of(nnz, 256)), dim3(256), 0, st, (const u32 *)col, nnz, cnt, rank);
-        MI_TRY(exclusive_scan(ctx, st, cnt, nw, off, ctx->ws[WS_SCAN]));   // off[nw] = the number of entries
-        if (nnz) hipLaunchKernelGGL(k_col_scatter, dim3(mi_blocks_of(((u64)nnz + 3) / 4, 256)), dim3(256), 0, st, (const u32 *)row_ptr, (u32)pl.nc,
-                                    (const u32 *)col, (const u32 *)cf, nnz, (const u32 *)off, (const u32 *)rank, sorted);
+        MI_TRY(mi_setup_col_sort_enqueue(ctx, st, row_ptr, (u32)pl.nc, col, cf, nnz, nw, cnt, off, rank, sorted));
         MI_CHECK_HIP(ctx, hipEventRecord(e2, st));
         MI_CHECK_HIP(ctx, hipMemsetAsync(ctr, 0, 8, st));
         const ColTerm term{L, coeffs};
@@ -392,6 +362,17 @@ void fill_stats(mi_ctx *ctx, const Plan &pl, Timer &tm, const FrHalf &f, double 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace
+
+// r1cs_internal.h: the counting sort by column of one matrix, for phase2.hip too
+int32_t mi_setup_col_sort_enqueue(mi_ctx *ctx, hipStream_t st, const uint32_t *row_ptr, uint32_t n_rows, const uint32_t *col, const uint32_t *coeff, uint32_t nnz,
+                                  uint64_t nb_wires, uint32_t *cnt, uint32_t *off, uint32_t *rank, uint2 *sorted) {
+    MI_CHECK_HIP(ctx, hipMemsetAsync(cnt, 0, nb_wires * 4, st));
+    if (nnz) hipLaunchKernelGGL(k_col_count, dim3(mi_blocks_of(nnz, 256)), dim3(256), 0, st, col, nnz, cnt, rank);
+    MI_TRY(exclusive_scan(ctx, st, cnt, nb_wires, off, ctx->ws[WS_SCAN]));   // off[nb_wires] = the number of entries
+    if (nnz) hipLaunchKernelGGL(k_col_scatter, dim3(mi_blocks_of(((u64)nnz + 3) / 4, 256)), dim3(256), 0, st, row_ptr, n_rows, col, coeff, nnz, (const u32 *)off,
+                                (const u32 *)rank, sorted);
+    return MI_OK;
+}
 
 extern "C" {
 

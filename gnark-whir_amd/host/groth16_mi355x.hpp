@@ -24,6 +24,7 @@
 #include "../../include/mi355x_groth16_verify_bytes.h"
 #include "../../include/mi355x_groth16_vkfile.h"
 #include "../../include/mi355x_groth16_verify_combined.h"
+#include "../../include/mi355x_groth16_phase2.h"
 #include "../../include/mi355x_groth16_debug.h"   // (this mirror is the TEST side: generators and knobs)
 
 namespace groth16 {
@@ -75,6 +76,7 @@ struct Proof {
 class ProvingKey {
   public:
     ProvingKey(const Context &ctx, const mi_pk_desc &desc) : ctx_(ctx) { ctx_.check(mi_pk_load(ctx_.get(), &desc, &pk_)); }
+    ProvingKey(const Context &ctx, mi_pk *adopted) : ctx_(ctx), pk_(adopted) {}   // a key the library has built (Phase2::Seal)
     ~ProvingKey() { if (pk_) mi_pk_free(ctx_.get(), pk_); }
     ProvingKey(const ProvingKey &) = delete;
     ProvingKey &operator=(const ProvingKey &) = delete;
@@ -356,6 +358,41 @@ inline mi_fr HashToField(const std::string &dst, const std::vector<uint8_t> &msg
     if (mi_hash_to_field((const uint8_t *)dst.data(), dst.size(), msg.data(), msg.size(), &out) != MI_OK) throw Error(MI_EINVAL, "HashToField: dst must have 1 .. 255 bytes");
     return out;
 }
+// mpcsetup's phase 2 (include/mi355x_groth16_phase2.h): the circuit's keys derived on the device from a powers-of-tau SRS, delta
+// re-randomised by contributors.  NOT here: the pairing check of the SRS, the contributions' proofs, gnark's mpcsetup file formats.
+//   p2 := mpcsetup.InitPhase2(r1cs, &srs)      groth16::Phase2 p2(ctx, r1cs, srs, sigma)
+//   p2.Contribute()                            p2.Contribute(delta)            // the caller samples delta (and must forget it)
+//   pk, vk := mpcsetup.ExtractKeys(...)        p2.Seal(vk) / p2.Streams(...)   // as often as wanted: sealing does not end the ceremony
+class Phase2 {
+  public:
+    Phase2(const Context &ctx, const mi_r1cs_desc &r1cs, const mi_srs_desc &srs, const std::vector<mi_fr> &sigma = {}, uint32_t flags = 0) : ctx_(ctx) {
+        ctx_.check(mi_phase2_init(ctx_.get(), &r1cs, &srs, sigma.empty() ? nullptr : sigma.data(), flags, &st_));
+    }
+    ~Phase2() { if (st_) mi_phase2_free(ctx_.get(), st_); }
+    Phase2(const Phase2 &) = delete;
+    Phase2 &operator=(const Phase2 &) = delete;
+    mi_phase2 *get() const { return st_; }
+    void Contribute(const mi_fr &delta, const std::vector<mi_fr> &sigmaFactor = {}) {
+        ctx_.check(mi_phase2_contribute(ctx_.get(), st_, &delta, sigmaFactor.empty() ? nullptr : sigmaFactor.data()));
+    }
+    // the proving key as an ordinary device-resident key; vk (k / k_cap set by the caller) and ped (room for the commitments) as mi_groth16_setup
+    std::unique_ptr<ProvingKey> Seal(mi_vk_out &vk, mi_pedersen_pk **ped = nullptr) const {
+        mi_pk *pk = nullptr;
+        ctx_.check(mi_phase2_seal(ctx_.get(), st_, &pk, ped, &vk));
+        return std::unique_ptr<ProvingKey>(new ProvingKey(ctx_, pk));
+    }
+    // ProvingKey.WriteTo / VerifyingKey.WriteTo (MI_KEYFILE_COMPRESSED) or the raw forms (MI_KEYFILE_RAW)
+    void Streams(std::vector<uint8_t> &pk, std::vector<uint8_t> &vk, uint32_t encoding = MI_KEYFILE_COMPRESSED) const {
+        size_t len = 0, vkLen = 0;
+        (void)mi_phase2_to_streams(ctx_.get(), st_, encoding, nullptr, 0, &len, nullptr, 0, &vkLen);   // the sizes
+        pk.resize(len); vk.resize(vkLen);
+        ctx_.check(mi_phase2_to_streams(ctx_.get(), st_, encoding, pk.data(), pk.size(), &len, vk.data(), vk.size(), &vkLen));
+    }
+
+  private:
+    const Context &ctx_;
+    mi_phase2 *st_ = nullptr;
+};
 // fft.Domain: FFT / FFTInverse with fft.DIF / fft.DIT and fft.OnCoset()
 enum Decimation { DIF = 0, DIT = 1 };
 inline void FFT(const Context &ctx, std::vector<mi_fr> &a, uint32_t logN, Decimation d, bool onCoset = false) {

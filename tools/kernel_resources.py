@@ -94,7 +94,7 @@ def main():
         rows = [r for rs in ex.map(kernels_of, srcs) for r in rs]
     dm = demangle([r["symbol"] for r in rows])
     for r in rows:
-        r["name"] = re.sub(r"\(.*", "", dm.get(r["symbol"], r["symbol"]))
+        r["name"] = re.sub(r"\(.*", "", dm.get(r["symbol"], r["symbol"]).replace("(anonymous namespace)::", ""))   # (a kernel in an unnamed namespace keeps its name)
         tot = r["vgpr"] + r["agpr"] if r["agpr"] else r["vgpr"]
         gran = (tot + 7) // 8 * 8
         r["vgpr_alloc"] = gran
