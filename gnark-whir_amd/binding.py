@@ -69,6 +69,12 @@ VKFILE_EXPORTS = ["mi_vk_stream_inspect", "mi_vk_stream_size", "mi_vk_write", "m
 PHASE2_EXPORTS = ["mi_phase2_init", "mi_phase2_contribute", "mi_phase2_seal", "mi_phase2_to_streams", "mi_phase2_free", "mi_phase2_get_stats",
                   "mi_phase2_get_array"]
 PHASE2_G1_A, PHASE2_G1_B, PHASE2_G2_B, PHASE2_G1_K, PHASE2_G1_Z, PHASE2_VK_K, PHASE2_BASIS = 0, 1, 2, 3, 4, 5, 6
+# include/mi355x_groth16_phase2_check.h (the SRS rows are consistent powers, contributions with a proof of knowledge, a claimed state verified)
+PHASE2_CHECK_EXPORTS = ["mi_srs_check_powers", "mi_srs_check_get_stats", "mi_phase2_set_transcript_id", "mi_phase2_contribute_proved",
+                        "mi_phase2_records_verify", "mi_phase2_verify_adopt", "mi_phase2_verify_get_stats"]
+SRS_BAD_GENERATORS, SRS_BAD_TAU_G1, SRS_BAD_ALPHA_G1, SRS_BAD_BETA_G1, SRS_BAD_TAU_G2, SRS_BAD_BETA_G2 = 1, 2, 4, 8, 16, 32
+PHASE2_BAD_RECORD, PHASE2_BAD_DELTA, PHASE2_BAD_Z, PHASE2_BAD_K = 1, 2, 4, 8
+PHASE2_RECORD_WORDS = 24   # a mi_phase2_record as uint64 words: delta1 (8), commit (8), response (4), hash (4 words = 32 bytes)
 
 
 class PkDesc(C.Structure):
@@ -175,6 +181,15 @@ class SrsDesc(C.Structure):
 class Phase2Stats(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("upload_ms", "check_ms", "point_ntt_g1_ms", "point_ntt_g2_ms", "sparse_g1_ms", "sparse_g2_ms", "z_ms",
                                          "affine_ms", "total_ms")] + [("pad_", C.c_uint32)] + [(n, C.c_uint64) for n in ("entries", "long_columns", "chunks", "peak_bytes")]
+
+
+class SrsCheckStats(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("upload_ms", "point_check_ms", "coeff_ms", "msm_g1_ms", "msm_g2_ms", "pairing_ms", "total_ms")] + [
+        ("pad_", C.c_uint32), ("peak_bytes", C.c_uint64)]
+
+
+class Phase2Claim(C.Structure):
+    _fields_ = [("g1_z", C.c_void_p), ("n_z", C.c_uint64), ("g1_k", C.c_void_p), ("n_k", C.c_uint64), ("delta1", C.c_uint64 * 8), ("delta2", C.c_uint64 * 16)]
 
 
 def _srs_desc(srs: dict):
@@ -858,6 +873,45 @@ class Context:
     def phase2_stats(self):
         st = Phase2Stats(); self._ck(self.lib.mi_phase2_get_stats(self.h, C.byref(st)))
         return {n: getattr(st, n) for n, _ in Phase2Stats._fields_ if n != "pad_"}
+
+    # ---- the checks of a ceremony (include/mi355x_groth16_phase2_check.h)
+    def srs_check_powers(self, srs: dict, n_domain, seed=None, flags=0):
+        """mi_srs_check_powers -> the mask of relations that do not hold; seed: 32 bytes, or None for the operating system's"""
+        sd, keep = _srs_desc(srs); failed = C.c_uint32(0xFFFFFFFF)
+        self._ck(self.lib.mi_srs_check_powers(self.h, C.byref(sd), C.c_uint64(n_domain), seed, C.c_uint32(flags), C.byref(failed)))
+        return int(failed.value)
+
+    def srs_check_stats(self, verify=False):
+        """mi_srs_check_get_stats, or with verify mi_phase2_verify_get_stats"""
+        st = SrsCheckStats(); self._ck((self.lib.mi_phase2_verify_get_stats if verify else self.lib.mi_srs_check_get_stats)(self.h, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in SrsCheckStats._fields_ if n != "pad_"}
+
+    def ceremony_coeffs(self, seed, n):
+        """mi_debug_ceremony_coeffs_dev -> (n, 4) uint64, Montgomery"""
+        out = self.alloc(max(n, 1) * 32)
+        try:
+            self._ck(self.lib.mi_debug_ceremony_coeffs_dev(self.h, seed, C.c_size_t(n), C.c_void_p(out.ptr)))
+            return out.download((n, 4), np.uint64)
+        finally:
+            out.free()
+
+    def phase2_set_transcript_id(self, st, ident):
+        self._ck(self.lib.mi_phase2_set_transcript_id(self.h, st, ident))
+
+    def phase2_contribute_proved(self, st, delta, nonce=None):
+        """mi_phase2_contribute_proved -> the record, PHASE2_RECORD_WORDS uint64"""
+        rec = np.zeros(PHASE2_RECORD_WORDS, np.uint64)
+        self._ck(self.lib.mi_phase2_contribute_proved(self.h, st, _p(_u64(delta)), None if nonce is None else _p(_u64(nonce)), _p(rec)))
+        return rec
+
+    def phase2_verify_adopt(self, st, g1_z, g1_k, delta1, delta2, records, seed=None):
+        """mi_phase2_verify_adopt -> (mask, first_bad_record); records: (m, PHASE2_RECORD_WORDS) uint64"""
+        z, k, rec = _u64(g1_z), _u64(g1_k), _u64(records).reshape(-1, PHASE2_RECORD_WORDS)
+        cl = Phase2Claim(z.ctypes.data, z.shape[0], k.ctypes.data if k.shape[0] else None, k.shape[0], (C.c_uint64 * 8)(*[int(v) for v in _u64(delta1).reshape(8)]),
+                         (C.c_uint64 * 16)(*[int(v) for v in _u64(delta2).reshape(16)]))
+        failed = C.c_uint32(0xFFFFFFFF); fb = C.c_uint64(0)
+        self._ck(self.lib.mi_phase2_verify_adopt(self.h, st, C.byref(cl), _p(rec), C.c_size_t(rec.shape[0]), seed, C.byref(failed), C.byref(fb)))
+        return int(failed.value), int(fb.value)
 
     def keyfile_stats(self):
         st = KeyfileStats(); self._ck(self.lib.mi_keyfile_get_stats(self.h, C.byref(st)))
@@ -1561,6 +1615,15 @@ def g1_compress(p):
 
 def g2_compress(p):
     buf = np.zeros(64, np.uint8); load().mi_g2_compress(_p(_u64(p)), _p(buf)); return bytes(buf)
+
+
+def phase2_records_verify(delta1_start, start_hash, first_index, records):
+    """mi_phase2_records_verify (host only) -> the index of the first record that does not hold, len(records) when all hold"""
+    rec = _u64(records).reshape(-1, PHASE2_RECORD_WORDS); fb = C.c_uint64()
+    rc = load().mi_phase2_records_verify(_p(_u64(delta1_start)), start_hash, C.c_uint64(first_index), _p(rec), C.c_size_t(rec.shape[0]), C.byref(fb))
+    if rc != 0:
+        raise MiError(f"rc={rc}: mi_phase2_records_verify")
+    return int(fb.value)
 
 
 def pedersen_fold(points, challenge):

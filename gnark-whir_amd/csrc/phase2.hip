@@ -15,31 +15,16 @@
 #include "r1cs_internal.h"
 #include "keyfile_internal.h"
 #include "keyfile_ops.cuh"
-#include "../../include/mi355x_groth16_phase2.h"
+#include "phase2_internal.h"
 #include "../../include/mi355x_groth16_vkfile.h"
 #include "scan_u32.cuh"
 #include "batch_affine.cuh"
-#include "dev_arena.h"
 #include "point_ntt.cuh"
 #include "sparse_points.cuh"
 #include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <vector>
-
-struct mi_phase2 {
-    u32 log_n = 0, nb_public = 0, n_commitments = 0;
-    u64 N = 0, nb_wires = 0;
-    std::vector<u32> removed;             // committed + commitment wires: the private wires without a pk.G1.K point
-    std::vector<uint8_t> inf_a, inf_b;
-    // device arrays, affine
-    void *g1_a = nullptr, *g1_b = nullptr, *g2_b = nullptr, *g1_k = nullptr, *g1_z = nullptr, *vk_k = nullptr;
-    u64 n_a = 0, n_b = 0, n_k = 0, n_vk = 0;
-    struct Ped { void *basis = nullptr, *bes = nullptr; u64 n = 0; Fr sigma; };
-    std::vector<Ped> ped;
-    G1Aff alpha1, beta1, delta1;
-    G2Aff beta2, gamma2, delta2;
-};
 
 namespace {
 
@@ -261,18 +246,6 @@ int32_t sum_points(mi_ctx *ctx, XYZZ<F> *out, u64 nw, const PointSources<F, NS> 
     return MI_OK;
 }
 
-int32_t check_srs_host(mi_ctx *ctx, const mi_srs_desc *srs, u64 N) {
-    if (!srs) MI_FAIL(ctx, MI_EINVAL, "phase2: srs is null");
-    const struct { const char *name; const void *p; u64 n, need; } rows[4] = {
-        {"tau_g1", srs->tau_g1, srs->n_tau_g1, 2 * N}, {"alpha_tau_g1", srs->alpha_tau_g1, srs->n_alpha_tau_g1, N},
-        {"beta_tau_g1", srs->beta_tau_g1, srs->n_beta_tau_g1, N}, {"tau_g2", srs->tau_g2, srs->n_tau_g2, N}};
-    for (const auto &r : rows) {
-        if (!r.p) MI_FAIL(ctx, MI_EINVAL, std::string("phase2: srs.") + r.name + " is null");
-        if (r.n < r.need) MI_FAIL(ctx, MI_EINVAL, std::string("phase2: srs.n_") + r.name + " is " + std::to_string(r.n) + ", the circuit needs " + std::to_string(r.need) + " points");
-    }
-    return MI_OK;
-}
-
 void free_state(mi_phase2 *s) {
     for (void *p : {s->g1_a, s->g1_b, s->g2_b, s->g1_k, s->g1_z, s->vk_k}) if (p) (void)hipFree(p);
     for (auto &pd : s->ped) { if (pd.basis) (void)hipFree(pd.basis); if (pd.bes) (void)hipFree(pd.bes); }
@@ -302,31 +275,9 @@ int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, con
     MI_CHECK_HIP(ctx, hipMemcpyAsync(b2, &srs->beta_g2, 128, hipMemcpyHostToDevice, st));
     MI_TRY(laps.lap(ctx, stats.upload_ms));
     {
-        enum { TAU1, ALPHA, BETA, TAU2, TAU2_SUB, BETA2, BETA2_SUB, WORDS };
-        ull *bad = nullptr, bad_h[WORDS];
-        MI_TRY(ar.alloc(ctx, &bad, (size_t)WORDS));
-        MI_CHECK_HIP(ctx, hipMemsetAsync(bad, 0xff, WORDS * sizeof(ull), st));
-        hipLaunchKernelGGL(k_phase2_check_g1, dim3(mi_blocks_of(2 * N, 256)), dim3(256), 0, st, (const G1Aff *)T1, 2 * N, bad + TAU1);
-        hipLaunchKernelGGL(k_phase2_check_g1, dim3(mi_blocks_of(N, 256)), dim3(256), 0, st, (const G1Aff *)Al, N, bad + ALPHA);
-        hipLaunchKernelGGL(k_phase2_check_g1, dim3(mi_blocks_of(N, 256)), dim3(256), 0, st, (const G1Aff *)Be, N, bad + BETA);
-        hipLaunchKernelGGL(k_phase2_check_g2, dim3(mi_blocks_of(N, 256)), dim3(256), 0, st, (const G2Aff *)T2, N, bad + TAU2);
-        hipLaunchKernelGGL(k_phase2_check_g2, dim3(1), dim3(256), 0, st, (const G2Aff *)b2, (u64)1, bad + BETA2);
-        MI_CHECK_HIP(ctx, hipGetLastError());
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(bad_h, bad, sizeof(bad_h), hipMemcpyDeviceToHost, st));
-        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
-        const struct { int word; const char *row; } curve_rows[5] = {{TAU1, "tau_g1"}, {ALPHA, "alpha_tau_g1"}, {BETA, "beta_tau_g1"}, {TAU2, "tau_g2"}, {BETA2, "beta_g2"}};
-        for (const auto &r : curve_rows)
-            if (bad_h[r.word] != ~0ull)
-                MI_FAIL(ctx, MI_EINVAL, std::string("phase2: srs.") + r.row + "[" + std::to_string(bad_h[r.word]) + "] is at infinity or not on its curve");
-        if (!(flags & MI_KEYFILE_NO_SUBGROUP_CHECK)) {   // of points of the twist only: the curve checks have passed
-            MI_TRY(mi_keyfile_subgroup_enqueue(ctx, T2, (size_t)N, false, bad + TAU2_SUB));
-            MI_TRY(mi_keyfile_subgroup_enqueue(ctx, b2, 1, false, bad + BETA2_SUB));
-            MI_CHECK_HIP(ctx, hipMemcpyAsync(bad_h, bad, sizeof(bad_h), hipMemcpyDeviceToHost, st));
-            MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
-            if (bad_h[TAU2_SUB] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "phase2: srs.tau_g2[" + std::to_string(bad_h[TAU2_SUB]) + "] is not in the r-torsion");
-            if (bad_h[BETA2_SUB] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "phase2: srs.beta_g2[0] is not in the r-torsion");
-        }
-        ar.release(bad); ar.release(b2);
+        const Phase2Row rows[5] = {{"tau_g1", false, T1, 2 * N}, {"alpha_tau_g1", false, Al, N}, {"beta_tau_g1", false, Be, N}, {"tau_g2", true, T2, N}, {"beta_g2", true, b2, 1}};
+        MI_TRY(mi_phase2_check_points(ctx, ar, rows, 5, flags));
+        ar.release(b2);
     }
     MI_TRY(laps.lap(ctx, stats.check_ms));
     // one scratch for every batched conversion: a field element per point (Fp2-sized, the longest array)
@@ -530,6 +481,51 @@ void fill_pk_desc(const mi_phase2 *S, mi_pk_desc &d) {
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------- shared with phase2_check.hip
+int32_t mi_phase2_srs_host_check(mi_ctx *ctx, const mi_srs_desc *srs, u64 N) {
+    if (!srs) MI_FAIL(ctx, MI_EINVAL, "phase2: srs is null");
+    const struct { const char *name; const void *p; u64 n, need; } rows[4] = {
+        {"tau_g1", srs->tau_g1, srs->n_tau_g1, 2 * N}, {"alpha_tau_g1", srs->alpha_tau_g1, srs->n_alpha_tau_g1, N},
+        {"beta_tau_g1", srs->beta_tau_g1, srs->n_beta_tau_g1, N}, {"tau_g2", srs->tau_g2, srs->n_tau_g2, N}};
+    for (const auto &r : rows) {
+        if (!r.p) MI_FAIL(ctx, MI_EINVAL, std::string("phase2: srs.") + r.name + " is null");
+        if (r.n < r.need) MI_FAIL(ctx, MI_EINVAL, std::string("phase2: srs.n_") + r.name + " is " + std::to_string(r.n) + ", the circuit needs " + std::to_string(r.need) + " points");
+    }
+    return MI_OK;
+}
+int32_t mi_phase2_check_points(mi_ctx *ctx, Arena &ar, const Phase2Row *rows, int n_rows, uint32_t flags) {
+    hipStream_t st = ctx->stream;
+    ull *bad = nullptr, bad_h[16];   // word 2 i: row i's curve check; 2 i + 1: its r-torsion check
+    if (n_rows > 8) return MI_EINVAL;
+    MI_TRY(ar.alloc(ctx, &bad, (size_t)16));
+    MI_CHECK_HIP(ctx, hipMemsetAsync(bad, 0xff, sizeof(bad_h), st));
+    for (int i = 0; i < n_rows; i++) {
+        const Phase2Row &r = rows[i];
+        if (r.g2) hipLaunchKernelGGL(k_phase2_check_g2, dim3(mi_blocks_of(r.n, 256)), dim3(256), 0, st, (const G2Aff *)r.pts, r.n, bad + 2 * i);
+        else hipLaunchKernelGGL(k_phase2_check_g1, dim3(mi_blocks_of(r.n, 256)), dim3(256), 0, st, (const G1Aff *)r.pts, r.n, bad + 2 * i);
+    }
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(bad_h, bad, sizeof(bad_h), hipMemcpyDeviceToHost, st));
+    MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+    for (int i = 0; i < n_rows; i++)
+        if (bad_h[2 * i] != ~0ull)
+            MI_FAIL(ctx, MI_EINVAL, std::string("phase2: srs.") + rows[i].name + "[" + std::to_string(bad_h[2 * i]) + "] is at infinity or not on its curve");
+    if (!(flags & MI_KEYFILE_NO_SUBGROUP_CHECK)) {   // of points of the twist only: the curve checks have passed
+        bool any = false;
+        for (int i = 0; i < n_rows; i++)
+            if (rows[i].g2) { MI_TRY(mi_keyfile_subgroup_enqueue(ctx, rows[i].pts, (size_t)rows[i].n, false, bad + 2 * i + 1)); any = true; }
+        if (any) {
+            MI_CHECK_HIP(ctx, hipMemcpyAsync(bad_h, bad, sizeof(bad_h), hipMemcpyDeviceToHost, st));
+            MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+        }
+        for (int i = 0; i < n_rows; i++)
+            if (bad_h[2 * i + 1] != ~0ull)
+                MI_FAIL(ctx, MI_EINVAL, std::string("phase2: srs.") + rows[i].name + "[" + std::to_string(bad_h[2 * i + 1]) + "] is not in the r-torsion");
+    }
+    ar.release(bad);
+    return MI_OK;
+}
+
 extern "C" {
 
 int32_t mi_phase2_get_stats(mi_ctx *ctx, mi_phase2_stats *out) {
@@ -546,7 +542,7 @@ int32_t mi_phase2_init(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_srs_desc 
     if (flags & ~MI_KEYFILE_NO_SUBGROUP_CHECK) MI_FAIL(ctx, MI_EINVAL, "phase2: unknown flag");
     R1csShape sh;
     MI_TRY(mi_r1cs_validate(ctx, "phase2", r1cs, sh));
-    MI_TRY(check_srs_host(ctx, srs, sh.N));
+    MI_TRY(mi_phase2_srs_host_check(ctx, srs, sh.N));
     if (sh.n_commitments && !sigma) MI_FAIL(ctx, MI_EINVAL, "phase2: sigma is null");
     std::vector<Fr> sg(sh.n_commitments);
     for (u32 k = 0; k < sh.n_commitments; k++) {

@@ -1,0 +1,35 @@
+// What phase2.hip shares with phase2_check.hip (not part of the C-ABI): the ceremony state, the host checks of an SRS descriptor and
+// the point checks of its rows on the device.
+#pragma once
+#include "ctx.h"
+#include "fp12.cuh"
+#include "dev_arena.h"
+#include "../../include/mi355x_groth16_phase2.h"
+#include <vector>
+
+struct mi_phase2 {
+    u32 log_n = 0, nb_public = 0, n_commitments = 0;
+    u64 N = 0, nb_wires = 0;
+    std::vector<u32> removed;             // committed + commitment wires: the private wires without a pk.G1.K point
+    std::vector<uint8_t> inf_a, inf_b;
+    // device arrays, affine
+    void *g1_a = nullptr, *g1_b = nullptr, *g2_b = nullptr, *g1_k = nullptr, *g1_z = nullptr, *vk_k = nullptr;
+    u64 n_a = 0, n_b = 0, n_k = 0, n_vk = 0;
+    struct Ped { void *basis = nullptr, *bes = nullptr; u64 n = 0; Fr sigma; };
+    std::vector<Ped> ped;
+    G1Aff alpha1, beta1, delta1;
+    G2Aff beta2, gamma2, delta2;
+    // the chain of proved contributions (include/mi355x_groth16_phase2_check.h): records so far, and the hash the next one continues
+    // (the transcript id until there is one)
+    u64 n_records = 0;
+    uint8_t chain[32] = {0};
+};
+
+// null rows and rows shorter than the circuit needs (tau_g1: 2 N, the others: N)
+int32_t mi_phase2_srs_host_check(mi_ctx *ctx, const mi_srs_desc *srs, u64 N);
+// One row of an SRS on the device.  mi_phase2_check_points over n_rows of them: every point on its curve and not at infinity -- the rows
+// in the order given, the lowest bad index of the first bad row named -- then, unless flags holds MI_KEYFILE_NO_SUBGROUP_CHECK, every
+// point of the G2 rows in the r-torsion, the same way.  MI_EINVAL with "phase2: srs.<name>[<index>] ..." in mi_last_error.  The stream
+// is idle on return.  At most 8 rows.
+struct Phase2Row { const char *name; bool g2; const void *pts; u64 n; };
+int32_t mi_phase2_check_points(mi_ctx *ctx, Arena &ar, const Phase2Row *rows, int n_rows, uint32_t flags);

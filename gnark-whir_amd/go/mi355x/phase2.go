@@ -9,15 +9,18 @@
 //	pk, vk := mpcsetup.ExtractKeys(...)        pkBytes, vkBytes, err := p2.Streams(mi355x.KeyCompressed)
 //
 // The keys leave as the streams of keyfile.go (LoadKeyStream / LoadVerifyingKeyStream read them back in any later process).
-// NOT here, and not in the library yet: the pairing check that the SRS rows are consistent powers, the contributions' proofs of
-// knowledge and the verification of a transcript, and gnark's mpcsetup file formats (their layout is not available to this project:
-// the SRS crosses this interface as slices of points).  The walk over gnark's constraints below (GetR1Cs, Term.CoeffID / WireID)
-// is written from memory of gnark v0.11 and has never been compiled.
+// What makes the result checkable (include/mi355x_groth16_phase2_check.h) is at the end of this file: CheckSRS (the pairing check
+// that the rows are consistent powers; call it before InitPhase2), ContributeProved (a contribution with its Schnorr record),
+// VerifyRecords and VerifyAdopt (a contributor's claimed state checked against one's own, then taken over).  NOT here, and not in the
+// library: gnark's mpcsetup file formats (their layout is not available to this project: the SRS and the records cross this interface
+// as slices, in this project's own layout), a record for sigma, a phase-1 transcript.  The walk over gnark's constraints below
+// (GetR1Cs, Term.CoeffID / WireID) is written from memory of gnark v0.11 and has never been compiled.
 package mi355x
 
 /*
 #include <stdlib.h>
 #include "mi355x_groth16_phase2.h"
+#include "mi355x_groth16_phase2_check.h"
 */
 import "C"
 
@@ -177,6 +180,107 @@ func (p *Phase2) Streams(encoding int) (pk []byte, vk []byte, err error) {
 		return nil, nil, err
 	}
 	return pk, vk, nil
+}
+
+// The relations of CheckSRS's mask (MI_SRS_BAD_*) and of VerifyAdopt's (MI_PHASE2_BAD_*).
+const (
+	SRSBadGenerators = 1 << iota
+	SRSBadTauG1
+	SRSBadAlphaG1
+	SRSBadBetaG1
+	SRSBadTauG2
+	SRSBadBetaG2
+)
+const (
+	Phase2BadRecord = 1 << iota
+	Phase2BadDelta
+	Phase2BadZ
+	Phase2BadK
+)
+
+// Record is one contribution's proof of knowledge: mi_phase2_record, word for word.
+type Record struct {
+	Delta1, Commit bn254.G1Affine
+	Response       fr.Element
+	Hash           [32]byte
+}
+
+// Claim is what a contributor hands over: the arrays of mi_phase2_get_array (MI_PHASE2_G1_Z, MI_PHASE2_G1_K) and the two delta points.
+type Claim struct {
+	Z, K   []bn254.G1Affine
+	Delta1 bn254.G1Affine
+	Delta2 bn254.G2Affine
+}
+
+func srsDesc(pin *runtime.Pinner, srs *SRS) (s C.mi_srs_desc) {
+	s.tau_g1, s.n_tau_g1 = g1(pin, srs.TauG1), C.uint64_t(len(srs.TauG1))
+	s.alpha_tau_g1, s.n_alpha_tau_g1 = g1(pin, srs.AlphaTauG1), C.uint64_t(len(srs.AlphaTauG1))
+	s.beta_tau_g1, s.n_beta_tau_g1 = g1(pin, srs.BetaTauG1), C.uint64_t(len(srs.BetaTauG1))
+	s.tau_g2, s.n_tau_g2 = g2(pin, srs.TauG2), C.uint64_t(len(srs.TauG2))
+	s.beta_g2 = *(*C.mi_g2_affine)(unsafe.Pointer(&srs.BetaG2))
+	return
+}
+
+// CheckSRS decides by pairings whether the rows are [tau^k]1, [alpha tau^k]1, [beta tau^k]1, [tau^k]2, [beta]2 for one (tau, alpha,
+// beta), for a circuit of domain size n (a power of two).  failed == 0: they are.  The seed of the test's coefficients is the
+// operating system's: never pass one the maker of the SRS could have known.
+func CheckSRS(srs *SRS, n uint64, device int) (failed uint32, err error) {
+	var ctx *C.mi_ctx
+	if rc := C.mi_init(C.int(device), &ctx); rc != C.MI_OK {
+		return 0, fmt.Errorf("mi355x: mi_init rc=%d (no gfx950 device?)", int(rc))
+	}
+	defer C.mi_shutdown(ctx)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	s := srsDesc(&pin, srs)
+	var mask C.uint32_t
+	err = status(ctx, C.mi_srs_check_powers(ctx, &s, C.uint64_t(n), nil, 0, &mask))
+	return uint32(mask), err
+}
+
+// SetTranscriptID names the ceremony: the value the first record's hash continues.  Only before the first record.
+func (p *Phase2) SetTranscriptID(id [32]byte) error {
+	return status(p.ctx, C.mi_phase2_set_transcript_id(p.ctx, p.st, (*C.uint8_t)(unsafe.Pointer(&id[0]))))
+}
+
+// ContributeProved re-randomises delta as Contribute(delta, nil) does and returns the record of the step (the nonce is the library's).
+func (p *Phase2) ContributeProved(delta fr.Element) (Record, error) {
+	var r Record
+	err := status(p.ctx, C.mi_phase2_contribute_proved(p.ctx, p.st, (*C.mi_fr)(unsafe.Pointer(&delta)), nil, (*C.mi_phase2_record)(unsafe.Pointer(&r))))
+	return r, err
+}
+
+// VerifyRecords checks the chain of records continuing (delta1Start, startHash, firstIndex) on the host; firstBad == len(recs): all hold.
+func VerifyRecords(delta1Start bn254.G1Affine, startHash [32]byte, firstIndex uint64, recs []Record) (firstBad uint64, err error) {
+	var rp *C.mi_phase2_record
+	if len(recs) > 0 {
+		rp = (*C.mi_phase2_record)(unsafe.Pointer(&recs[0]))
+	}
+	var fb C.uint64_t
+	if rc := C.mi_phase2_records_verify((*C.mi_g1_affine)(unsafe.Pointer(&delta1Start)), (*C.uint8_t)(unsafe.Pointer(&startHash[0])), C.uint64_t(firstIndex),
+		rp, C.size_t(len(recs)), &fb); rc != C.MI_OK {
+		return 0, fmt.Errorf("mi355x: mi_phase2_records_verify rc=%d", int(rc))
+	}
+	return uint64(fb), nil
+}
+
+// VerifyAdopt checks a contributor's claim and records against this state and, when failed == 0 and only then, takes the claimed
+// arrays over and advances the chain by the records.
+func (p *Phase2) VerifyAdopt(c *Claim, recs []Record) (failed uint32, firstBadRecord uint64, err error) {
+	if c == nil || len(recs) == 0 {
+		return 0, 0, errors.New("mi355x: nil claim or no record")
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	var cl C.mi_phase2_claim
+	cl.g1_z, cl.n_z = g1(&pin, c.Z), C.uint64_t(len(c.Z))
+	cl.g1_k, cl.n_k = g1(&pin, c.K), C.uint64_t(len(c.K))
+	cl.delta1 = *(*C.mi_g1_affine)(unsafe.Pointer(&c.Delta1))
+	cl.delta2 = *(*C.mi_g2_affine)(unsafe.Pointer(&c.Delta2))
+	var mask C.uint32_t
+	var fb C.uint64_t
+	err = status(p.ctx, C.mi_phase2_verify_adopt(p.ctx, p.st, &cl, (*C.mi_phase2_record)(unsafe.Pointer(&recs[0])), C.size_t(len(recs)), nil, &mask, &fb))
+	return uint32(mask), uint64(fb), err
 }
 
 // Close frees the state and its context.

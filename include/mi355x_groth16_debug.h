@@ -216,6 +216,9 @@ int32_t mi_debug_set_trace_ranges(int32_t on);
 /* error-path tests: the nth MI-checked HIP call from now (library-wide, any thread) fails with hipErrorUnknown instead of
  * running; 0 disarms.  Used to prove that init / load / prove unwind without leaks or crashes. */
 int32_t mi_debug_inject_hip_failure(int32_t nth);
+/* The coefficients of the ceremony checks (mi355x_groth16_phase2_check.h) by the kernel those checks run, enqueued on the context's
+ * stream: out_dev[k] = r_k as a Montgomery mi_fr, k < n <= 2^27; seed: 32 HOST bytes. */
+int32_t mi_debug_ceremony_coeffs_dev(mi_ctx *ctx, const uint8_t seed[32], size_t n, mi_fr *out_dev);
 
 #ifdef __cplusplus
 }

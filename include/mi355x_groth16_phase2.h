@@ -26,13 +26,18 @@
  * So an SRS built from known (tau, alpha, beta) gives, byte for byte, the key mi_groth16_setup gives for (tau, alpha, beta, 1, 1, sigma),
  * and after contributions d_1 .. d_m the key for delta = d_1 ... d_m (an affine point has one encoding).
  *
- * NOT DONE HERE (each of them is needed before a ceremony can be trusted, none of them is in this library yet):
+ * NOT DONE HERE (each of them is needed before a ceremony can be trusted).  The first two are in mi355x_groth16_phase2_check.h, which a
+ * ceremony runs beside the entry points below; the third is in this library nowhere:
  *   - the pairing check that the SRS rows are consistent powers (e([tau^(k+1)]1, g2) = e([tau^k]1, [tau]2), and the same for the alpha
- *     and beta rows): the rows are checked point by point only -- on the curve, in the r-torsion, not at infinity;
- *   - the contributions' proofs of knowledge of delta and the verification of a transcript of contributions;
+ *     and beta rows): mi_phase2_init checks the rows point by point only -- on the curve, in the r-torsion, not at infinity -- and
+ *     derives a key from whatever passes that.  mi_srs_check_powers makes the pairing check over the same rows: call it first;
+ *   - the contributions' proofs of knowledge of delta and the verification of a transcript of contributions: mi_phase2_contribute
+ *     below moves delta and leaves no record.  mi_phase2_contribute_proved writes a Schnorr record per contribution, and
+ *     mi_phase2_verify_adopt checks a contributor's claimed Z, K and delta points against one's own state and takes them over
+ *     (mi_phase2_get_array exports what it takes back).  The commitment keys' sigma has no such record (that header says what is left);
  *   - gnark's mpcsetup file formats (Phase1 / Phase2 WriteTo): their layout is NOT AVAILABLE to this project (no gnark on the machines
- *     this was written on), so the SRS and the state cross this interface as plain arrays.  The keys leave as the streams of
- *     mi355x_groth16_keyfile.h and mi355x_groth16_vkfile.h, with those headers' caveats.
+ *     this was written on), so the SRS, the state and the records cross this interface as plain arrays in this project's own layout.
+ *     The keys leave as the streams of mi355x_groth16_keyfile.h and mi355x_groth16_vkfile.h, with those headers' caveats.
  */
 #ifndef MI355X_GROTH16_PHASE2_H
 #define MI355X_GROTH16_PHASE2_H

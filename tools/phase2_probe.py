@@ -15,6 +15,14 @@ matrix, one BSB22 commitment over N / 32 wires; tests/setup_cases.py, the circui
   setup       mi_groth16_setup for the trapdoor (tau, alpha, beta, 1, 1, sigma) on the same circuit, second run, as tools/setup_probe.py
               times it: what the same key costs when the trapdoor is known
   --check     the compressed streams of the state equal mi_groth16_setup_to_streams's, before and after the contribution
+
+The checks of a ceremony (include/mi355x_groth16_phase2_check.h); with either flag the legs above from init on are left out:
+  --check-srs mi_srs_check_powers over the probe's SRS with the operating system's seed, ONE run: wall time, the time of every phase
+              (mi_srs_check_get_stats: the host's clock around work that is waited for), the peak of the call's device allocations
+              and the mask (0: the SRS is honest)
+  --verify    two states from the same SRS (their mi_phase2_init times are this run's yardstick), one mi_phase2_contribute_proved on
+              the first, its Z, K and delta points handed to mi_phase2_verify_adopt on the second, ONE run: wall time, phases
+              (mi_phase2_verify_get_stats), peak, the mask (0: adopted) and whether the adopter's Z then equals the contributor's
 """
 import argparse
 import os
@@ -44,11 +52,56 @@ def build_srs(ctx, N, td):
             "beta_g2": ctx.batch_scalar_mul(D.G2, td["beta"].reshape(1, 4), g2=True)[0]}
 
 
+def phases(s):
+    return " ".join(f"{k}={s[k]:.1f}" for k in ("total_ms", "upload_ms", "point_check_ms", "coeff_ms", "msm_g1_ms", "msm_g2_ms", "pairing_ms")) + \
+        f" peak_device_bytes={s['peak_bytes']} ({s['peak_bytes'] / 2**30:.2f} GiB)"
+
+
+def check_legs(ctx, B, a, N, r1cs, srs, td, say):
+    if a.check_srs:
+        t0 = time.perf_counter()
+        mask = ctx.srs_check_powers(srs, N)
+        wall = time.perf_counter() - t0
+        say(f"check_srs log_n={a.log_n} mask={mask} wall_ms={wall * 1e3:.1f} {phases(ctx.srs_check_stats())} ctx_ledger={ctx.mem_ledger()}")
+        ctx.trim()
+    if a.verify:
+        states = []
+        try:
+            for who in ("contributor", "verifier"):
+                t0 = time.perf_counter()
+                states.append(ctx.phase2_init(r1cs, srs, [td["sigma"][0]]))
+                say(f"init log_n={a.log_n} state={who} wall_ms={(time.perf_counter() - t0) * 1e3:.1f} total_ms={ctx.phase2_stats()['total_ms']:.1f}")
+            st, v = states
+            delta = cref.gen_scalars(1, 99, 0)[0]
+            t0 = time.perf_counter()
+            rec = ctx.phase2_contribute_proved(st, delta)
+            say(f"contribute_proved log_n={a.log_n} wall_ms={(time.perf_counter() - t0) * 1e3:.1f}")
+            z, k = ctx.phase2_array(st, B.PHASE2_G1_Z), ctx.phase2_array(st, B.PHASE2_G1_K)
+            d2 = ctx.batch_scalar_mul(D.G2, delta.reshape(1, 4), g2=True)[0]
+            ctx.trim()
+            t0 = time.perf_counter()
+            mask, first_bad = ctx.phase2_verify_adopt(v, z, k, rec[:8], d2, rec.reshape(1, -1))
+            wall = time.perf_counter() - t0
+            say(f"verify_adopt log_n={a.log_n} points_z={len(z)} points_k={len(k)} mask={mask} first_bad_record={first_bad} wall_ms={wall * 1e3:.1f} "
+                f"{phases(ctx.srs_check_stats(verify=True))} adopted_z_equals_contributors={np.array_equal(ctx.phase2_array(v, B.PHASE2_G1_Z), z)}")
+        finally:
+            for s in states:
+                ctx.phase2_free(s)
+
+
+def write_lines(a, lines):
+    if a.write:
+        with open(a.write, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("log_n", type=int)
     ap.add_argument("--check", action="store_true", help="compare the state's compressed streams with Setup's")
     ap.add_argument("--write", default=None, help="append the result lines to this file")
+    ap.add_argument("--check-srs", action="store_true", help="time mi_srs_check_powers over the SRS")
+    ap.add_argument("--verify", action="store_true", help="time mi_phase2_verify_adopt of one proved contribution")
     a = ap.parse_args()
     B = load_binding()
     ctx = B.Context(0)
@@ -69,6 +122,10 @@ def main():
         srs = build_srs(ctx, N, td)
         ctx.trim()
         say(f"srs log_n={a.log_n} points_g1={4 * N} points_g2={N} build_s={time.perf_counter() - t0:.1f} (the probe's preparation)")
+        if a.check_srs or a.verify:
+            check_legs(ctx, B, a, N, r1cs, srs, td, say)
+            write_lines(a, lines)
+            return
         t0 = time.perf_counter()
         st = ctx.phase2_init(r1cs, srs, [td["sigma"][0]])
         wall = time.perf_counter() - t0
@@ -109,9 +166,7 @@ def main():
             f"handover_ms={ss['handover_ms']:.1f} (the same key from the trapdoor in the clear)")
     finally:
         ctx.close()
-    if a.write:
-        with open(a.write, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    write_lines(a, lines)
 
 
 if __name__ == "__main__":
