@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <chrono>
 #include <functional>
 #include <mutex>
 #include <string>
@@ -235,6 +236,8 @@ static inline bool mi_try_reserve(DevBuf &b, size_t bytes) {
     return true;
 }
 
+// the host's steady clock in milliseconds
+static inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static inline unsigned mi_blocks_of(uint64_t n, uint32_t per) { return (unsigned)((n + per - 1) / per); }   // workgroups of `per` items over n
 
 // ctx->copy_stream, created on first use (api.hip)

@@ -3,8 +3,7 @@
 #include "ctx.h"
 #include <vector>
 
-// device allocations of one call, freed when it returns (the key takes what it adopts out of the list)
-struct Arena {
+struct Arena {   // (the key takes what it adopts out of the list: key_handover.h)
     struct Block { void *p; size_t bytes; };
     std::vector<Block> live;
     size_t held = 0, peak = 0;   // bytes the arena holds now, and the most it has held

@@ -14,6 +14,10 @@
 #include "curve.cuh"
 #include "fp12_consts.inc"   // generated: tools/gen_fp12_consts.py
 
+// the generators gnark-crypto's bn254 package fixes: g1 = (1, 2), g2 as in EIP-197
+MI_HD G1Aff g1_generator() { return G1Aff{Fp::one(), fe_from_u32<FpParams>(2)}; }
+MI_HD G2Aff g2_generator() { return G2Aff{fp12c_g2gen_x(), fp12c_g2gen_y()}; }
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #define MI_OOL __host__ __device__ __attribute__((noinline))   // (__host__: the host functions of a .hip file are parsed in the device pass too)
 #else

@@ -11,12 +11,12 @@
 // extended coordinates where the decoder holds its table of fifteen powers, and apart each is timed (mi_keyfile_stats).
 //
 // mi_pk_load_stream: inspect on the host, upload once, decode every section straight into the array the key will own, ONE wait for all
-// verdicts, then the adopt path of pk_raw.hip (mi_pk_load_range / mi_pedersen_pk_adopt).  mi_pk_write_dev: the sections are encoded
+// verdicts, then the handover of key_handover.h (mi_pk_load_range / mi_pedersen_pk_adopt).  mi_pk_write_dev: the sections are encoded
 // on the device and copied into place; the Domain block, the counts and the masks are host code and follow oracle/pk_raw.py.
 #include "prove_internal.h"
 #include "keyfile_ops.cuh"
 #include "keyfile_internal.h"
-#include <chrono>
+#include "key_handover.h"
 #include <cstring>
 #include <string>
 #include <vector>
@@ -126,7 +126,6 @@ struct BadSlots {
     }
     ~BadSlots() { if (dev) (void)hipFree(dev); }
 };
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // n strings of one group -> points, and the lowest refused index
 int32_t decompress(mi_ctx *ctx, bool g2, const uint8_t *bytes_dev, size_t n, uint32_t flags, void *out_dev, uint64_t *first_bad) {
@@ -208,26 +207,19 @@ int32_t mi_pk_load_stream(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t 
         MI_FAIL(ctx, MI_EINVAL, "keyfile: the stream has neither the layout of ProvingKey.WriteRawTo nor of ProvingKey.WriteTo (include/mi355x_groth16_keyfile.h)");
     const bool compressed = encoding == MI_KEYFILE_COMPRESSED;
     // the domain's generator must be the one fft.NewDomain derives for this size (a cheap canary for a shifted layout)
-    {
-        Fr c;
-        const uint8_t *g = buf + 8 + 32;
-        for (int i = 0; i < 8; i++) { const uint8_t *q = g + 28 - 4 * i; c.l[i] = ((u32)q[0] << 24) | ((u32)q[1] << 16) | ((u32)q[2] << 8) | q[3]; }
-        if (fe_to_mont(c) != fr_domain_generator(in.log_n)) MI_FAIL(ctx, MI_EINVAL, "keyfile: Domain.Generator is not fft.NewDomain's for this cardinality");
-    }
+    if (mi_pk_stream_generator(buf) != fr_domain_generator(in.log_n)) MI_FAIL(ctx, MI_EINVAL, "keyfile: Domain.Generator is not fft.NewDomain's for this cardinality");
     ctx->keyfile_stats = mi_keyfile_stats{};
     const double t0 = now_ms();
-    std::vector<uint8_t> ia(in.nb_wires), ib(in.nb_wires);
-    for (uint64_t j = 0; j < in.nb_wires; j++) {
-        ia[j] = (buf[in.off_infinity_a + j / 8] >> (7 - j % 8)) & 1;
-        ib[j] = (buf[in.off_infinity_b + j / 8] >> (7 - j % 8)) & 1;
-    }
+    const std::vector<uint8_t> ia = mi_pk_stream_mask(buf, in.off_infinity_a, in.nb_wires), ib = mi_pk_stream_mask(buf, in.off_infinity_b, in.nb_wires);
     const uint32_t n_ped = ped_out ? in.n_commitment_keys : 0;
     // every section, in stream order: where it lies, where it goes
     struct Section { std::string name; bool g2; uint64_t off, n; void *dst; };
-    void *arrays[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *d_small1 = nullptr, *d_small2 = nullptr;
+    KeyArrays ka(in.log_n, nb_public, in.nb_wires, ia.data(), ib.data(), committed_wires, n_committed);   // the arrays are this call's own until the key takes them
+    ka.n[KEY_G1_A] = in.n_g1_a; ka.n[KEY_G1_B] = in.n_g1_b; ka.n[KEY_G1_K] = in.n_g1_k; ka.n[KEY_G1_Z] = in.n_g1_z; ka.n[KEY_G2_B] = in.n_g2_b;
+    void *d_small1 = nullptr, *d_small2 = nullptr;
     std::vector<void *> ped_arrays(2 * (size_t)n_ped, nullptr);
     void *raw = nullptr;
-    uint32_t peds_made = 0;
+    KeyHandover hand(ctx, out, ped_out);
     auto body = [&]() -> int32_t {
         std::vector<Section> sec = {{"G1.AlphaBetaDelta", false, in.off_alpha1, 3, nullptr}, {"G1.A", false, in.off_g1_a, in.n_g1_a, nullptr},
                                     {"G1.B", false, in.off_g1_b, in.n_g1_b, nullptr},        {"G1.Z", false, in.off_g1_z, in.n_g1_z, nullptr},
@@ -237,7 +229,7 @@ int32_t mi_pk_load_stream(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t 
             sec.push_back({"Basis[" + std::to_string(k) + "]", false, in.off_basis[k], in.n_basis[k], nullptr});
             sec.push_back({"BasisExpSigma[" + std::to_string(k) + "]", false, in.off_basis_exp_sigma[k], in.n_basis[k], nullptr});
         }
-        void **const home[7] = {&d_small1, &arrays[0], &arrays[1], &arrays[3], &arrays[2], &d_small2, &arrays[4]};   // (mi_pk_desc order: a, b, k, z, g2_b)
+        void **const home[7] = {&d_small1, &ka.arr[KEY_G1_A], &ka.arr[KEY_G1_B], &ka.arr[KEY_G1_Z], &ka.arr[KEY_G1_K], &d_small2, &ka.arr[KEY_G2_B]};
         for (size_t s = 0; s < sec.size(); s++) {
             void **h = s < 7 ? home[s] : &ped_arrays[s - 7];
             const size_t bytes = (size_t)sec[s].n * (sec[s].g2 ? 128 : 64);
@@ -258,10 +250,8 @@ int32_t mi_pk_load_stream(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t 
         const double t_dec = now_ms();
         if (!(flags & MI_KEYFILE_NO_SUBGROUP_CHECK))
             for (int k = 0; k < 2; k++) MI_TRY(subgroup_g2(ctx, sec[5 + k].dst, (size_t)sec[5 + k].n, (flags & MI_KEYFILE_SUBGROUP_BY_R) != 0, bad.dev + sec.size() + k));
-        G1Aff small1[3];
-        G2Aff small2[2];
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(small1, d_small1, sizeof(small1), hipMemcpyDeviceToHost, ctx->stream));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(small2, d_small2, sizeof(small2), hipMemcpyDeviceToHost, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ka.small1, d_small1, 3 * sizeof(G1Aff), hipMemcpyDeviceToHost, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ka.small2, d_small2, 2 * sizeof(G2Aff), hipMemcpyDeviceToHost, ctx->stream));
         MI_TRY(bad.fetch(ctx));
         const double t_sub = now_ms();
         (void)hipFree(raw); raw = nullptr;   // the stream has been read
@@ -269,27 +259,8 @@ int32_t mi_pk_load_stream(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t 
             if (bad.host[s] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "keyfile: " + sec[s].name + "[" + std::to_string(bad.host[s]) + "] is malformed: no point of the curve has this " + (compressed ? "compressed" : "raw") + " encoding");
         for (int k = 0; k < 2; k++)
             if (bad.host[sec.size() + k] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "keyfile: " + sec[5 + k].name + "[" + std::to_string(bad.host[sec.size() + k]) + "] is on the twist but not in the r-torsion");
-        mi_pk_desc d;
-        std::memset(&d, 0, sizeof(d));
-        d.log_n = in.log_n; d.nb_public = nb_public; d.nb_wires = in.nb_wires;
-        d.g1_a = (const mi_g1_affine *)arrays[0]; d.n_g1_a = in.n_g1_a;
-        d.g1_b = (const mi_g1_affine *)arrays[1]; d.n_g1_b = in.n_g1_b;
-        d.g1_k = (const mi_g1_affine *)arrays[2]; d.n_g1_k = in.n_g1_k;
-        d.g1_z = (const mi_g1_affine *)arrays[3]; d.n_g1_z = in.n_g1_z;
-        d.g2_b = (const mi_g2_affine *)arrays[4]; d.n_g2_b = in.n_g2_b;
-        std::memcpy(&d.alpha1, &small1[0], 64); std::memcpy(&d.beta1, &small1[1], 64); std::memcpy(&d.delta1, &small1[2], 64);
-        std::memcpy(&d.beta2, &small2[0], 128); std::memcpy(&d.delta2, &small2[1], 128);
-        d.infinity_a = ia.data(); d.infinity_b = ib.data();
-        d.committed_wires = committed_wires; d.n_committed = n_committed;
-        bool took = false;
-        const int32_t lr = mi_pk_load_range(ctx, &d, out, true, nullptr, /*forced=*/nullptr, /*adopt=*/true, &took);
-        if (took) for (void *&a : arrays) a = nullptr;   // the key owns them now (it has released them itself if it failed after taking them)
-        MI_TRY(lr);
-        for (uint32_t k = 0; k < n_ped; k++) {
-            MI_TRY(mi_pedersen_pk_adopt(ctx, ped_arrays[2 * k], ped_arrays[2 * k + 1], (size_t)in.n_basis[k], &ped_out[k]));
-            ped_arrays[2 * k] = ped_arrays[2 * k + 1] = nullptr;
-            peds_made = k + 1;
-        }
+        MI_TRY(hand.adopt_key(ka, nullptr));
+        for (uint32_t k = 0; k < n_ped; k++) MI_TRY(hand.adopt_pedersen(&ped_arrays[2 * k], &ped_arrays[2 * k + 1], (size_t)in.n_basis[k], nullptr));
         MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const double t_end = now_ms();
         ctx->keyfile_stats = mi_keyfile_stats{(float)(t_up - t0), (float)(t_dec - t_up), (float)(t_sub - t_dec), (float)(t_end - t_sub), (float)(t_end - t0)};
@@ -297,13 +268,13 @@ int32_t mi_pk_load_stream(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t 
     };
     const int32_t rc = body();
     (void)hipStreamSynchronize(ctx->stream);
-    for (void *a : arrays) if (a) (void)hipFree(a);
+    for (void *a : ka.arr) if (a) (void)hipFree(a);
     for (void *a : ped_arrays) if (a) (void)hipFree(a);
     for (void *a : {raw, d_small1, d_small2}) if (a) (void)hipFree(a);
-    if (rc != MI_OK) {
-        if (*out) { mi_pk_free(ctx, *out); *out = nullptr; }
-        for (uint32_t k = 0; k < peds_made; k++) { mi_pedersen_pk_free(ctx, ped_out[k]); ped_out[k] = nullptr; }
-    } else if (n_ped_out) *n_ped_out = n_ped;
+    if (rc == MI_OK) {
+        hand.dismiss();
+        if (n_ped_out) *n_ped_out = n_ped;
+    }
     return rc;
 }
 

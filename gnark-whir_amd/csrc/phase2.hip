@@ -6,23 +6,21 @@
 //   2  Z_i = [tau^(i + N)]1 - [tau^i]1, stored bit-reversed
 //   3  the Lagrange bases [L_i]1, [alpha L_i]1, [beta L_i]1, [L_i]2: the inverse NTT over points of point_ntt.cuh, a launch per stage, a
 //      lane per butterfly, then batch_affine.cuh's conversion in place over the SRS row (bit-reversed order)
-//   4  the three matrices sorted by column by setup.hip's sort, then the sums of points of sparse_points.cuh:
+//   4  the three matrices sorted by column by setup.hip's MatrixSorter, then the sums of points of sparse_points.cuh:
 //      [A_j]1, [B_j]1, [B_j]2 and [t_j]1 = one accumulator over (A, [beta L]), (B, [alpha L]), (C, [L])
-//   5  masks from the points at infinity, setup.hip's compaction by scanned flags, the gathers for vk.K and the Pedersen bases
+//   5  masks from the points at infinity, Setup's wire selection (key_handover.h), the gathers for vk.K and the Pedersen bases
 // The state keeps the plain affine arrays; contribute multiplies Z, K, BasisExpSigma and the two delta points by scalars; seal copies
-// the arrays into an ordinary key (mi_pk_load_range's adopt path); the streams are written from the state's arrays directly.
+// the arrays into an ordinary key and the streams are written from the state's arrays directly, both through key_handover.h.
 #include "prove_internal.h"
 #include "r1cs_internal.h"
 #include "keyfile_internal.h"
 #include "keyfile_ops.cuh"
 #include "phase2_internal.h"
-#include "../../include/mi355x_groth16_vkfile.h"
-#include "scan_u32.cuh"
+#include "key_handover.h"
 #include "batch_affine.cuh"
 #include "point_ntt.cuh"
 #include "sparse_points.cuh"
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <vector>
 
@@ -102,7 +100,7 @@ __global__ void __launch_bounds__(64) k_phase2_sum_pieces_g2(G2X *partial, Point
 __global__ void __launch_bounds__(64) k_phase2_sum_combine_g1(G1X *out, PointSource<Fp> ps, const G1X *partial) { sparse_points_combine(out, ps, partial); }
 __global__ void __launch_bounds__(64) k_phase2_sum_combine_g2(G2X *out, PointSource<Fp2> ps, const G2X *partial) { sparse_points_combine(out, ps, partial); }
 
-// masks and the compaction's flags from the per-wire points (setup.hip's k_elementwise, from points): keep_k = private wire, the
+// masks and the wire selection's flags from the per-wire points (setup.hip's k_elementwise, from points): keep_k = private wire, the
 // committed and commitment wires are cleared afterwards
 __global__ void __launch_bounds__(256) k_phase2_masks(const G1Aff *A, const G1Aff *B, uint8_t *inf_a, uint8_t *inf_b, u32 *keep_a, u32 *keep_b, u32 *keep_k,
                                                       u64 nb_wires, u32 nb_public) {
@@ -112,29 +110,12 @@ __global__ void __launch_bounds__(256) k_phase2_masks(const G1Aff *A, const G1Af
     inf_a[j] = za; inf_b[j] = zb;
     keep_a[j] = !za; keep_b[j] = !zb; keep_k[j] = j >= nb_public;
 }
-__global__ void k_phase2_clear_flags(u32 *flags, const u32 *idx, u32 n) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) flags[idx[i]] = 0;
-}
-// slot[j] = scanned flags (slot[j + 1] != slot[j] where the wire is kept)
-template <class A>
-MI_D void lane_compact(A *dst, const A *src, const u32 *slot, u64 n) {
-    const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const u32 s = slot[j];
-    if (slot[j + 1] != s) dst[s] = src[j];
-}
-__global__ void __launch_bounds__(256) k_phase2_compact_g1(G1Aff *dst, const G1Aff *src, const u32 *slot, u64 n) { lane_compact(dst, src, slot, n); }
-__global__ void __launch_bounds__(256) k_phase2_compact_g2(G2Aff *dst, const G2Aff *src, const u32 *slot, u64 n) { lane_compact(dst, src, slot, n); }
 __global__ void __launch_bounds__(256) k_phase2_gather_g1(G1Aff *dst, const G1Aff *src, const u32 *idx, u64 n) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[idx[i]];
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-Fr fr_of(const mi_fr &x) { Fr r; std::memcpy(&r, &x, 32); return r; }
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 // the time of the stream's work since the last lap (each lap waits for the stream: the phases are long and run one after the other)
 struct Laps {
     hipEvent_t ev[2]{};
@@ -162,7 +143,6 @@ template <> struct Curve<Fp> {
     static void scale(hipStream_t st, G1X *o, const G1Aff *i, u64 n, const Fr &s) { hipLaunchKernelGGL(k_phase2_scale_g1, dim3(mi_blocks_of(n, 64)), dim3(64), 0, st, o, i, n, s); }
     static void pieces(hipStream_t st, unsigned grid, G1X *partial, const PointSource<Fp> &ps) { hipLaunchKernelGGL(k_phase2_sum_pieces_g1, dim3(grid), dim3(64), 0, st, partial, ps); }
     static void combine(hipStream_t st, unsigned grid, G1X *out, const PointSource<Fp> &ps, const G1X *partial) { hipLaunchKernelGGL(k_phase2_sum_combine_g1, dim3(grid), dim3(64), 0, st, out, ps, partial); }
-    static void compact(hipStream_t st, G1Aff *d, const G1Aff *s, const u32 *slot, u64 n) { hipLaunchKernelGGL(k_phase2_compact_g1, dim3(mi_blocks_of(n, 256)), dim3(256), 0, st, d, s, slot, n); }
 };
 template <> struct Curve<Fp2> {
     static void from_affine(hipStream_t st, G2X *o, const G2Aff *i, u64 n) { hipLaunchKernelGGL(k_phase2_from_affine_g2, dim3(mi_blocks_of(n, 256)), dim3(256), 0, st, o, i, n); }
@@ -170,7 +150,6 @@ template <> struct Curve<Fp2> {
     static void scale(hipStream_t st, G2X *o, const G2Aff *i, u64 n, const Fr &s) { hipLaunchKernelGGL(k_phase2_scale_g2, dim3(mi_blocks_of(n, 64)), dim3(64), 0, st, o, i, n, s); }
     static void pieces(hipStream_t st, unsigned grid, G2X *partial, const PointSource<Fp2> &ps) { hipLaunchKernelGGL(k_phase2_sum_pieces_g2, dim3(grid), dim3(64), 0, st, partial, ps); }
     static void combine(hipStream_t st, unsigned grid, G2X *out, const PointSource<Fp2> &ps, const G2X *partial) { hipLaunchKernelGGL(k_phase2_sum_combine_g2, dim3(grid), dim3(64), 0, st, out, ps, partial); }
-    static void compact(hipStream_t st, G2Aff *d, const G2Aff *s, const u32 *slot, u64 n) { hipLaunchKernelGGL(k_phase2_compact_g2, dim3(mi_blocks_of(n, 256)), dim3(256), 0, st, d, s, slot, n); }
 };
 void short_pass(hipStream_t st, G1X *out, u64 nw, const PointSources<Fp, 1> &s) { hipLaunchKernelGGL(k_phase2_sum_short_g1, dim3(mi_blocks_of(nw, 64)), dim3(64), 0, st, out, nw, s); }
 void short_pass(hipStream_t st, G1X *out, u64 nw, const PointSources<Fp, 3> &s) { hipLaunchKernelGGL(k_phase2_sum_short_g1x3, dim3(mi_blocks_of(nw, 64)), dim3(64), 0, st, out, nw, s); }
@@ -312,31 +291,25 @@ int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, con
     Fr *coeffs = nullptr;
     SortedMatrix mat[3];
     {
-        u32 *row_ptr = nullptr, *col = nullptr, *cf = nullptr, *cnt = nullptr, *rank = nullptr;
+        MatrixSorter ms{d, &sh};
         MI_TRY(ar.alloc(ctx, &coeffs, (size_t)d->n_coeffs));
         if (d->n_coeffs) MI_CHECK_HIP(ctx, hipMemcpyAsync(coeffs, d->coeffs, d->n_coeffs * 32, hipMemcpyHostToDevice, st));
-        MI_TRY(ar.alloc(ctx, &row_ptr, (size_t)sh.nc + 1));
-        MI_TRY(ar.alloc(ctx, &col, (size_t)max_nnz));
-        MI_TRY(ar.alloc(ctx, &cf, (size_t)max_nnz));
-        MI_TRY(ar.alloc(ctx, &cnt, (size_t)nw));
-        MI_TRY(ar.alloc(ctx, &rank, (size_t)max_nnz));
-        const mi_r1cs_matrix *mats[3] = {&d->A, &d->B, &d->C};
+        MI_TRY(ar.alloc(ctx, &ms.row_ptr, (size_t)sh.nc + 1));
+        MI_TRY(ar.alloc(ctx, &ms.col, (size_t)max_nnz));
+        MI_TRY(ar.alloc(ctx, &ms.cf, (size_t)max_nnz));
+        MI_TRY(ar.alloc(ctx, &ms.cnt, (size_t)nw));
+        MI_TRY(ar.alloc(ctx, &ms.rank, (size_t)max_nnz));
         for (int k = 0; k < 3; k++) {
-            const u32 nnz = sh.nnz[k];
-            mat[k].nnz = nnz;
+            mat[k].nnz = sh.nnz[k];
             MI_TRY(ar.alloc(ctx, &mat[k].off, (size_t)nw + 1));
-            MI_TRY(ar.alloc(ctx, &mat[k].sorted, (size_t)nnz));
-            MI_CHECK_HIP(ctx, hipMemcpyAsync(row_ptr, sh.row_ptr[k].data(), (sh.nc + 1) * 4, hipMemcpyHostToDevice, st));
-            if (nnz) {
-                MI_CHECK_HIP(ctx, hipMemcpyAsync(col, mats[k]->col, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-                MI_CHECK_HIP(ctx, hipMemcpyAsync(cf, mats[k]->coeff, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-            }
+            MI_TRY(ar.alloc(ctx, &mat[k].sorted, (size_t)sh.nnz[k]));
+            MI_TRY(ms.upload(ctx, st, k));
             MI_TRY(laps.lap(ctx, stats.upload_ms));
-            MI_TRY(mi_setup_col_sort_enqueue(ctx, st, row_ptr, (u32)sh.nc, col, cf, nnz, nw, cnt, mat[k].off, rank, mat[k].sorted));
+            MI_TRY(ms.sort(ctx, st, k, mat[k].off, mat[k].sorted));
             MI_CHECK_HIP(ctx, hipGetLastError());
             MI_TRY(laps.lap(ctx, stats.sparse_g1_ms));   // the host arrays of this matrix are not read after this point
         }
-        for (void *p : {(void *)row_ptr, (void *)col, (void *)cf, (void *)cnt, (void *)rank}) ar.release(p);
+        for (void *p : {(void *)ms.row_ptr, (void *)ms.col, (void *)ms.cf, (void *)ms.cnt, (void *)ms.rank}) ar.release(p);
     }
     // a long column has more than SPARSE_SHORT entries and at most len / SPARSE_SHORT pieces
     LongPlan lp[3];
@@ -392,50 +365,33 @@ int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, con
     for (void *p : {(void *)T1, (void *)Al, (void *)Be, (void *)T2, (void *)coeffs, (void *)ctr, (void *)prefix}) ar.release(p);
     // ---- 5: masks, compaction, gathers
     uint8_t *inf_a = nullptr, *inf_b = nullptr;
-    u32 *slot_a = nullptr, *slot_b = nullptr, *slot_k = nullptr;
+    WireSelection sel; sel.nb_wires = nw;
     MI_TRY(ar.alloc(ctx, &inf_a, (size_t)nw));
     MI_TRY(ar.alloc(ctx, &inf_b, (size_t)nw));
-    MI_TRY(ar.alloc(ctx, &slot_a, (size_t)nw + 1));
-    MI_TRY(ar.alloc(ctx, &slot_b, (size_t)nw + 1));
-    MI_TRY(ar.alloc(ctx, &slot_k, (size_t)nw + 1));
-    hipLaunchKernelGGL(k_phase2_masks, dim3(mi_blocks_of(nw, 256)), dim3(256), 0, st, (const G1Aff *)pA, (const G1Aff *)pB1, inf_a, inf_b, slot_a, slot_b, slot_k, nw, sh.nb_public);
+    MI_TRY(ar.alloc(ctx, &sel.slot_a, (size_t)nw + 1));
+    MI_TRY(ar.alloc(ctx, &sel.slot_b, (size_t)nw + 1));
+    MI_TRY(ar.alloc(ctx, &sel.slot_k, (size_t)nw + 1));
+    hipLaunchKernelGGL(k_phase2_masks, dim3(mi_blocks_of(nw, 256)), dim3(256), 0, st, (const G1Aff *)pA, (const G1Aff *)pB1, inf_a, inf_b, sel.slot_a, sel.slot_b, sel.slot_k, nw, sh.nb_public);
     MI_CHECK_HIP(ctx, hipGetLastError());
-    auto upload_idx = [&](u32 **dst, const u32 *src, size_t n) -> int32_t {
-        MI_TRY(ar.alloc(ctx, dst, n));
-        if (n) MI_CHECK_HIP(ctx, hipMemcpyAsync(*dst, src, n * 4, hipMemcpyHostToDevice, st));
-        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));   // src may be the caller's
-        return MI_OK;
-    };
-    if (!sh.removed.empty()) {
-        u32 *rem = nullptr;
-        MI_TRY(upload_idx(&rem, sh.removed.data(), sh.removed.size()));
-        hipLaunchKernelGGL(k_phase2_clear_flags, dim3(mi_blocks_of(sh.removed.size(), 256)), dim3(256), 0, st, slot_k, (const u32 *)rem, (u32)sh.removed.size());
-        MI_CHECK_HIP(ctx, hipGetLastError());
-    }
-    // in == out, as in setup.hip: k_scan_final holds a block's values in registers before it stores the first of them
-    for (u32 *s : {slot_a, slot_b, slot_k}) MI_TRY(exclusive_scan(ctx, st, s, nw, s, ctx->ws[WS_SCAN]));
+    MI_TRY(sel.scan(ctx, ar, sh.removed));
     S->inf_a.resize(nw); S->inf_b.resize(nw);
-    u32 n_a = 0, n_b = 0, n_k = 0;
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(S->inf_a.data(), inf_a, nw, hipMemcpyDeviceToHost, st));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(S->inf_b.data(), inf_b, nw, hipMemcpyDeviceToHost, st));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(&n_a, slot_a + nw, 4, hipMemcpyDeviceToHost, st));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(&n_b, slot_b + nw, 4, hipMemcpyDeviceToHost, st));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(&n_k, slot_k + nw, 4, hipMemcpyDeviceToHost, st));
-    MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
-    S->n_a = n_a; S->n_b = n_b; S->n_k = n_k; S->n_vk = sh.vk_wires.size();
-    MI_TRY(ar.alloc(ctx, (G1Aff **)&S->g1_a, (size_t)n_a));
-    MI_TRY(ar.alloc(ctx, (G1Aff **)&S->g1_b, (size_t)n_b));
-    MI_TRY(ar.alloc(ctx, (G2Aff **)&S->g2_b, (size_t)n_b));
-    MI_TRY(ar.alloc(ctx, (G1Aff **)&S->g1_k, (size_t)n_k));
+    MI_TRY(sel.fetch(ctx, inf_a, inf_b, S->inf_a.data(), S->inf_b.data()));
+    S->n_a = sel.n_a; S->n_b = sel.n_b; S->n_k = sel.n_k; S->n_vk = sh.vk_wires.size();
+    MI_TRY(ar.alloc(ctx, (G1Aff **)&S->g1_a, (size_t)S->n_a));
+    MI_TRY(ar.alloc(ctx, (G1Aff **)&S->g1_b, (size_t)S->n_b));
+    MI_TRY(ar.alloc(ctx, (G2Aff **)&S->g2_b, (size_t)S->n_b));
+    MI_TRY(ar.alloc(ctx, (G1Aff **)&S->g1_k, (size_t)S->n_k));
     MI_TRY(ar.alloc(ctx, (G1Aff **)&S->vk_k, (size_t)S->n_vk));
-    Curve<Fp>::compact(st, (G1Aff *)S->g1_a, pA, slot_a, nw);
-    Curve<Fp>::compact(st, (G1Aff *)S->g1_b, pB1, slot_b, nw);
-    Curve<Fp2>::compact(st, (G2Aff *)S->g2_b, pB2, slot_b, nw);
-    Curve<Fp>::compact(st, (G1Aff *)S->g1_k, pT, slot_k, nw);
+    MI_TRY(sel.compact(ctx, S->g1_a, pA, sel.slot_a, sizeof(G1Aff)));
+    MI_TRY(sel.compact(ctx, S->g1_b, pB1, sel.slot_b, sizeof(G1Aff)));
+    MI_TRY(sel.compact(ctx, S->g2_b, pB2, sel.slot_b, sizeof(G2Aff)));
+    MI_TRY(sel.compact(ctx, S->g1_k, pT, sel.slot_k, sizeof(G1Aff)));
     MI_CHECK_HIP(ctx, hipGetLastError());
     auto gather = [&](void **dst, const u32 *wires, size_t n) -> int32_t {
         u32 *idx = nullptr;
-        MI_TRY(upload_idx(&idx, wires, n));
+        MI_TRY(ar.alloc(ctx, &idx, n));
+        if (n) MI_CHECK_HIP(ctx, hipMemcpyAsync(idx, wires, n * 4, hipMemcpyHostToDevice, st));
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));   // wires may be the caller's
         if (n) hipLaunchKernelGGL(k_phase2_gather_g1, dim3(mi_blocks_of(n, 256)), dim3(256), 0, st, (G1Aff *)*dst, (const G1Aff *)pT, (const u32 *)idx, (u64)n);
         MI_CHECK_HIP(ctx, hipGetLastError());
         return MI_OK;
@@ -456,8 +412,8 @@ int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, con
     std::memcpy(&S->alpha1, &srs->alpha_tau_g1[0], 64);
     std::memcpy(&S->beta1, &srs->beta_tau_g1[0], 64);
     std::memcpy(&S->beta2, &srs->beta_g2, 128);
-    S->delta1 = G1Aff{Fp::one(), fe_from_u32<FpParams>(2)};
-    S->gamma2 = S->delta2 = G2Aff{fp12c_g2gen_x(), fp12c_g2gen_y()};
+    S->delta1 = g1_generator();
+    S->gamma2 = S->delta2 = g2_generator();
     stats.peak_bytes = ar.peak;
     // the state takes its arrays
     for (void *p : {S->g1_a, S->g1_b, S->g2_b, S->g1_k, S->g1_z, S->vk_k}) ar.disown(p);
@@ -465,18 +421,13 @@ int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, con
     return MI_OK;
 }
 
-void fill_pk_desc(const mi_phase2 *S, mi_pk_desc &d) {
-    std::memset(&d, 0, sizeof(d));
-    d.log_n = S->log_n; d.nb_public = S->nb_public; d.nb_wires = S->nb_wires;
-    d.g1_a = (const mi_g1_affine *)S->g1_a; d.n_g1_a = S->n_a;
-    d.g1_b = (const mi_g1_affine *)S->g1_b; d.n_g1_b = S->n_b;
-    d.g1_k = (const mi_g1_affine *)S->g1_k; d.n_g1_k = S->n_k;
-    d.g1_z = (const mi_g1_affine *)S->g1_z; d.n_g1_z = S->N;
-    d.g2_b = (const mi_g2_affine *)S->g2_b; d.n_g2_b = S->n_b;
-    std::memcpy(&d.alpha1, &S->alpha1, 64); std::memcpy(&d.beta1, &S->beta1, 64); std::memcpy(&d.delta1, &S->delta1, 64);
-    std::memcpy(&d.beta2, &S->beta2, 128); std::memcpy(&d.delta2, &S->delta2, 128);
-    d.infinity_a = S->inf_a.data(); d.infinity_b = S->inf_b.data();
-    d.committed_wires = S->removed.empty() ? nullptr : S->removed.data(); d.n_committed = S->removed.size();
+// the state's own arrays as a key's (seal hands copies of them over, the streams read them where they are)
+KeyArrays key_arrays_of(const mi_phase2 *S) {
+    KeyArrays ka(S->log_n, S->nb_public, S->nb_wires, S->inf_a.data(), S->inf_b.data(), S->removed.data(), S->removed.size());
+    ka.arr[KEY_G1_A] = S->g1_a; ka.arr[KEY_G1_B] = S->g1_b; ka.arr[KEY_G1_K] = S->g1_k; ka.arr[KEY_G1_Z] = S->g1_z; ka.arr[KEY_G2_B] = S->g2_b;
+    ka.n[KEY_G1_A] = S->n_a; ka.n[KEY_G1_B] = ka.n[KEY_G2_B] = S->n_b; ka.n[KEY_G1_K] = S->n_k; ka.n[KEY_G1_Z] = S->N;
+    ka.small1[0] = S->alpha1; ka.small1[1] = S->beta1; ka.small1[2] = S->delta1; ka.small2[0] = S->beta2; ka.small2[1] = S->delta2; ka.small2[2] = S->gamma2;
+    return ka;
 }
 
 }  // namespace
@@ -614,7 +565,7 @@ int32_t mi_phase2_seal(mi_ctx *ctx, const mi_phase2 *S, mi_pk **pk_out, mi_peder
     if (!vk_out->k || vk_out->k_cap < S->n_vk) MI_FAIL(ctx, MI_EINVAL, "phase2: vk_out.k / k_cap: room for nb_public + n_commitments points is needed");
     for (u32 k = 0; k < S->n_commitments; k++) ped_out[k] = nullptr;
     hipStream_t st = ctx->stream;
-    u32 n_ped = 0;
+    KeyHandover hand(ctx, pk_out, ped_out);
     auto body = [&]() -> int32_t {
         Arena ar;
         auto copy = [&](void **dst, const void *src, size_t bytes) -> int32_t {
@@ -628,33 +579,19 @@ int32_t mi_phase2_seal(mi_ctx *ctx, const mi_phase2 *S, mi_pk **pk_out, mi_peder
             MI_TRY(copy(&basis, S->ped[k].basis, S->ped[k].n * 64));
             MI_TRY(copy(&bes, S->ped[k].bes, S->ped[k].n * 64));
             MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
-            MI_TRY(mi_pedersen_pk_adopt(ctx, basis, bes, (size_t)S->ped[k].n, &ped_out[k]));
-            ar.disown(basis); ar.disown(bes);
-            n_ped = k + 1;
+            MI_TRY(hand.adopt_pedersen(&basis, &bes, (size_t)S->ped[k].n, &ar));
         }
-        mi_pk_desc d;
-        fill_pk_desc(S, d);
-        void *arrays[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        MI_TRY(copy(&arrays[0], S->g1_a, S->n_a * 64));
-        MI_TRY(copy(&arrays[1], S->g1_b, S->n_b * 64));
-        MI_TRY(copy(&arrays[2], S->g1_k, S->n_k * 64));
-        MI_TRY(copy(&arrays[3], S->g1_z, S->N * 64));
-        MI_TRY(copy(&arrays[4], S->g2_b, S->n_b * 128));
+        KeyArrays ka = key_arrays_of(S);   // the key takes copies
+        for (int i = 0; i < KEY_ARRAYS; i++) {
+            const void *src = ka.arr[i];
+            MI_TRY(copy(&ka.arr[i], src, ka.n[i] * (i == KEY_G2_B ? 128 : 64)));
+        }
         MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
-        d.g1_a = (const mi_g1_affine *)arrays[0]; d.g1_b = (const mi_g1_affine *)arrays[1]; d.g1_k = (const mi_g1_affine *)arrays[2];
-        d.g1_z = (const mi_g1_affine *)arrays[3]; d.g2_b = (const mi_g2_affine *)arrays[4];
-        bool took = false;
-        const int32_t lr = mi_pk_load_range(ctx, &d, pk_out, true, nullptr, /*forced=*/nullptr, /*adopt=*/true, &took);
-        if (took) for (void *a : arrays) ar.disown(a);   // the key's now (it has released them itself if it failed after taking them)
-        return lr;
+        return hand.adopt_key(ka, &ar);
     };
     const int32_t rc = body();
-    if (rc != MI_OK) {
-        (void)hipStreamSynchronize(st);
-        if (*pk_out) { mi_pk_free(ctx, *pk_out); *pk_out = nullptr; }
-        for (u32 k = 0; k < n_ped; k++) { mi_pedersen_pk_free(ctx, ped_out[k]); ped_out[k] = nullptr; }
-        return rc;
-    }
+    if (rc != MI_OK) { (void)hipStreamSynchronize(st); return rc; }
+    hand.dismiss();
     std::memcpy(&vk_out->alpha1, &S->alpha1, 64);
     std::memcpy(&vk_out->beta2, &S->beta2, 128); std::memcpy(&vk_out->gamma2, &S->gamma2, 128); std::memcpy(&vk_out->delta2, &S->delta2, 128);
     vk_out->n_k = S->n_vk;
@@ -665,8 +602,8 @@ int32_t mi_phase2_to_streams(mi_ctx *ctx, const mi_phase2 *S, uint32_t encoding,
                              size_t vk_cap, size_t *vk_len) {
     if (!ctx) return MI_EINVAL;
     if (!S) MI_FAIL(ctx, MI_EINVAL, "phase2: the state is null");
-    mi_pk_desc d;
-    fill_pk_desc(S, d);
+    const KeyArrays ka = key_arrays_of(S);
+    const mi_pk_desc d = ka.desc();
     std::vector<mi_pedersen_arrays> pa(S->n_commitments);
     std::vector<mi_fr> sigma(S->n_commitments);
     for (u32 k = 0; k < S->n_commitments; k++) {
@@ -674,26 +611,11 @@ int32_t mi_phase2_to_streams(mi_ctx *ctx, const mi_phase2 *S, uint32_t encoding,
         std::memcpy(&sigma[k], &S->ped[k].sigma, 32);
     }
     std::vector<mi_g1_affine> k_host(S->n_vk);
-    mi_vk_file_desc vd;
-    std::memset(&vd, 0, sizeof(vd));
-    vd.n_k = S->n_vk; vd.nb_public = S->nb_public; vd.n_commitments = S->n_commitments;
-    size_t need = 0, vk_need = 0;
-    if (mi_pk_stream_size(&d, pa.data(), S->n_commitments, encoding, &need) != MI_OK) MI_FAIL(ctx, MI_EINVAL, "phase2: encoding is neither MI_KEYFILE_RAW nor MI_KEYFILE_COMPRESSED");
-    (void)mi_vk_stream_size(&vd, encoding, &vk_need);   // the encoding has passed above
-    if (len) *len = need;
-    if (vk_len) *vk_len = vk_need;
-    if (!out_host || cap < need) MI_FAIL(ctx, MI_EINVAL, "phase2: the key's stream takes " + std::to_string(need) + " bytes, out_host has room for " + std::to_string(out_host ? cap : 0));
-    if (!vk_out_host || vk_cap < vk_need)
-        MI_FAIL(ctx, MI_EINVAL, "phase2: the verifying key's stream takes " + std::to_string(vk_need) + " bytes, vk_out_host has room for " + std::to_string(vk_out_host ? vk_cap : 0));
+    const KeyStreams ks{encoding, out_host, cap, len, true, vk_out_host, vk_cap, vk_len};
+    MI_TRY(ks.check(ctx, "phase2", d, pa.data(), S->n_commitments, S->n_vk));
     if (S->n_vk) MI_CHECK_HIP(ctx, hipMemcpyAsync(k_host.data(), S->vk_k, S->n_vk * 64, hipMemcpyDeviceToHost, ctx->stream));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(&vd.alpha1, &S->alpha1, 64); std::memcpy(&vd.beta1, &S->beta1, 64); std::memcpy(&vd.delta1, &S->delta1, 64);
-    std::memcpy(&vd.beta2, &S->beta2, 128); std::memcpy(&vd.gamma2, &S->gamma2, 128); std::memcpy(&vd.delta2, &S->delta2, 128);
-    vd.k = k_host.data();
-    std::vector<mi_pedersen_vk> pvk(S->n_commitments);
-    MI_TRY(mi_pedersen_vk_make(ctx, sigma.data(), S->n_commitments, pvk.data()));
-    vd.ped = pvk.data();
-    MI_TRY(mi_vk_write(ctx, &vd, encoding, vk_out_host, vk_cap, vk_len));
+    MI_TRY(ks.write_vk(ctx, ka, k_host.data(), S->n_vk, sigma.data(), S->n_commitments));
     return mi_pk_write_dev(ctx, &d, pa.data(), S->n_commitments, encoding, out_host, cap, len);
 }
 

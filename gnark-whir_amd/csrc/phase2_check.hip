@@ -20,7 +20,6 @@
 #include "phase2_internal.h"
 #include "ceremony_ops.cuh"
 #include <sys/random.h>
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -53,7 +52,6 @@ __global__ void __launch_bounds__(64, 1) k_ceremony_judge(const Fp12 *res, u32 n
     bad[i] = ceremony_relation_holds(&f) ? 0 : 1;
 }
 
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // the host's clock around work that has been waited for
 struct Clock {
     double t = now_ms();
@@ -67,8 +65,6 @@ int32_t sync_lap(mi_ctx *ctx, Clock &ck, float &into) {
 
 G1Aff g1_of(const mi_g1_affine &p) { G1Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
 G2Aff g2_of(const mi_g2_affine &p) { G2Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
-G1Aff g1_generator() { return G1Aff{Fp::one(), fe_from_u32<FpParams>(2)}; }
-G2Aff g2_generator() { return G2Aff{fp12c_g2gen_x(), fp12c_g2gen_y()}; }
 
 // seed, or 32 bytes of the operating system's into own
 int32_t seed_or_random(mi_ctx *ctx, const char *who, const uint8_t *&seed, uint8_t own[32]) {

@@ -15,7 +15,8 @@
 // Raw points are big-endian CANONICAL coordinates; the device wants little-endian Montgomery limbs.  The conversion is the one
 // data-parallel piece (one point per thread: byte swap, flag bits, fe_to_mont) and runs on the GPU over the uploaded bytes;
 // the variable-length header walk is host code (csrc/pk_raw_inspect.hip: no HIP in it, so that the CPU build with sanitizers covers it).
-#include "prove_internal.h"
+#include "keyfile_internal.h"
+#include "key_handover.h"
 #include <cstring>
 #include <vector>
 
@@ -72,30 +73,24 @@ int32_t mi_pk_load_raw(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nb_
     if (mi_pk_raw_inspect(buf, len, &in) != MI_OK) MI_FAIL(ctx, MI_EINVAL, "pk raw: the stream does not have the layout of gnark v0.11.0 ProvingKey.WriteRawTo (see csrc/pk_raw.hip)");
     // the domain's constants must be the ones fft.NewDomain derives for this size (a cheap canary for a shifted layout)
     {
-        Fr want_gen = Fr::zero();
-        const uint8_t *g = buf + 8 + 32;   // Generator
-        for (int i = 0; i < 8; i++) { const uint8_t *q = g + 28 - 4 * i; want_gen.l[i] = ((u32)q[0] << 24) | ((u32)q[1] << 16) | ((u32)q[2] << 8) | q[3]; }
-        Fr gen = fe_to_mont(want_gen), acc = gen;
+        const Fr gen = mi_pk_stream_generator(buf);
+        Fr acc = gen;
         for (u32 k = 0; k < in.log_n; k++) acc = fe_sqr(acc);
         Fr half = gen;
         for (u32 k = 0; k + 1 < in.log_n; k++) half = fe_sqr(half);
         if (acc != Fr::one() || (in.log_n && half == Fr::one())) MI_FAIL(ctx, MI_EINVAL, "pk raw: Domain.Generator is not a primitive 2^log_n-th root of unity");
     }
     // infinity masks: bit-packed -> one byte per wire
-    std::vector<uint8_t> ia(in.nb_wires), ib(in.nb_wires);
-    for (uint64_t j = 0; j < in.nb_wires; j++) {
-        ia[j] = (buf[in.off_infinity_a + j / 8] >> (7 - j % 8)) & 1;
-        ib[j] = (buf[in.off_infinity_b + j / 8] >> (7 - j % 8)) & 1;
-    }
+    const std::vector<uint8_t> ia = mi_pk_stream_mask(buf, in.off_infinity_a, in.nb_wires), ib = mi_pk_stream_mask(buf, in.off_infinity_b, in.nb_wires);
     // upload the stream once; convert section by section on the device
     void *raw = nullptr;
     u32 *bad = nullptr;
     MI_CHECK_HIP(ctx, hipMalloc(&raw, len + 64));
-    void *arrays[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    G1Aff small1[3];
-    G2Aff small2[2];
+    KeyArrays ka(in.log_n, nb_public, in.nb_wires, ia.data(), ib.data(), committed_wires, n_committed);   // the arrays are this call's own until the key takes them
+    ka.n[KEY_G1_A] = in.n_g1_a; ka.n[KEY_G1_B] = in.n_g1_b; ka.n[KEY_G1_K] = in.n_g1_k; ka.n[KEY_G1_Z] = in.n_g1_z; ka.n[KEY_G2_B] = in.n_g2_b;
+    // the key alone: the Pedersen keys made before a later failure stay with the caller, who is told how many (n_ped_out)
+    KeyHandover hand(ctx, out, nullptr);
     void *d_small = nullptr;
-    int32_t rc = MI_OK;
     auto body = [&]() -> int32_t {
         MI_CHECK_HIP(ctx, hipMalloc((void **)&bad, 4));
         MI_CHECK_HIP(ctx, hipMemsetAsync(bad, 0, 4, ctx->stream));
@@ -107,38 +102,23 @@ int32_t mi_pk_load_raw(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nb_
             MI_CHECK_HIP(ctx, hipGetLastError());
             return MI_OK;
         };
-        MI_TRY(conv1(&arrays[0], in.off_g1_a, in.n_g1_a));
-        MI_TRY(conv1(&arrays[1], in.off_g1_b, in.n_g1_b));
-        MI_TRY(conv1(&arrays[2], in.off_g1_k, in.n_g1_k));
-        MI_TRY(conv1(&arrays[3], in.off_g1_z, in.n_g1_z));
-        MI_CHECK_HIP(ctx, hipMalloc(&arrays[4], in.n_g2_b ? in.n_g2_b * 128 : 128));
-        if (in.n_g2_b) hipLaunchKernelGGL(k_raw_to_g2, dim3((unsigned)((in.n_g2_b + 127) / 128)), dim3(128), 0, ctx->stream, (G2Aff *)arrays[4], (const uint8_t *)raw + in.off_g2_b, (size_t)in.n_g2_b, bad);
+        MI_TRY(conv1(&ka.arr[KEY_G1_A], in.off_g1_a, in.n_g1_a));
+        MI_TRY(conv1(&ka.arr[KEY_G1_B], in.off_g1_b, in.n_g1_b));
+        MI_TRY(conv1(&ka.arr[KEY_G1_K], in.off_g1_k, in.n_g1_k));
+        MI_TRY(conv1(&ka.arr[KEY_G1_Z], in.off_g1_z, in.n_g1_z));
+        MI_CHECK_HIP(ctx, hipMalloc(&ka.arr[KEY_G2_B], in.n_g2_b ? in.n_g2_b * 128 : 128));
+        if (in.n_g2_b) hipLaunchKernelGGL(k_raw_to_g2, dim3((unsigned)((in.n_g2_b + 127) / 128)), dim3(128), 0, ctx->stream, (G2Aff *)ka.arr[KEY_G2_B], (const uint8_t *)raw + in.off_g2_b, (size_t)in.n_g2_b, bad);
         void *ds1 = d_small;
         MI_TRY(conv1(&ds1, in.off_alpha1, 3));
         hipLaunchKernelGGL(k_raw_to_g2, dim3(1), dim3(128), 0, ctx->stream, (G2Aff *)((char *)d_small + 192), (const uint8_t *)raw + in.off_beta2, (size_t)2, bad);
         MI_CHECK_HIP(ctx, hipGetLastError());
         u32 bad_h = 0;
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(small1, d_small, 192, hipMemcpyDeviceToHost, ctx->stream));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(small2, (char *)d_small + 192, 256, hipMemcpyDeviceToHost, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ka.small1, d_small, 192, hipMemcpyDeviceToHost, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ka.small2, (char *)d_small + 192, 256, hipMemcpyDeviceToHost, ctx->stream));
         MI_CHECK_HIP(ctx, hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, ctx->stream));
         MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (bad_h) MI_FAIL(ctx, MI_EINVAL, "pk raw: a point carries compressed-encoding flag bits (this is a WriteTo stream, not WriteRawTo?)");
-        mi_pk_desc d;
-        std::memset(&d, 0, sizeof(d));
-        d.log_n = in.log_n; d.nb_public = nb_public; d.nb_wires = in.nb_wires;
-        d.g1_a = (const mi_g1_affine *)arrays[0]; d.n_g1_a = in.n_g1_a;
-        d.g1_b = (const mi_g1_affine *)arrays[1]; d.n_g1_b = in.n_g1_b;
-        d.g1_k = (const mi_g1_affine *)arrays[2]; d.n_g1_k = in.n_g1_k;
-        d.g1_z = (const mi_g1_affine *)arrays[3]; d.n_g1_z = in.n_g1_z;
-        d.g2_b = (const mi_g2_affine *)arrays[4]; d.n_g2_b = in.n_g2_b;
-        std::memcpy(&d.alpha1, &small1[0], 64); std::memcpy(&d.beta1, &small1[1], 64); std::memcpy(&d.delta1, &small1[2], 64);
-        std::memcpy(&d.beta2, &small2[0], 128); std::memcpy(&d.delta2, &small2[1], 128);
-        d.infinity_a = ia.data(); d.infinity_b = ib.data();
-        d.committed_wires = committed_wires; d.n_committed = n_committed;
-        bool took = false;
-        const int32_t lr = mi_pk_load_range(ctx, &d, out, true, nullptr, /*forced=*/nullptr, /*adopt=*/true, &took);
-        if (took) for (void *&a : arrays) a = nullptr;   // the key owns them now (it has released them itself if it failed after taking them)
-        MI_TRY(lr);
+        MI_TRY(hand.adopt_key(ka, nullptr));
         // Pedersen commitment keys
         if (ped_out) {
             for (uint32_t k = 0; k < in.n_commitment_keys; k++) {
@@ -153,13 +133,13 @@ int32_t mi_pk_load_raw(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t nb_
         }
         return MI_OK;
     };
-    rc = body();
+    const int32_t rc = body();
     (void)hipStreamSynchronize(ctx->stream);
-    for (void *a : arrays) if (a) (void)hipFree(a);
+    for (void *a : ka.arr) if (a) (void)hipFree(a);
     if (raw) (void)hipFree(raw);
     if (bad) (void)hipFree(bad);
     if (d_small) (void)hipFree(d_small);
-    if (rc != MI_OK && *out) { mi_pk_free(ctx, *out); *out = nullptr; }
+    if (rc == MI_OK) hand.dismiss();
     return rc;
 }
 

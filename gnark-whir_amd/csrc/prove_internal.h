@@ -6,6 +6,8 @@
 #include "key_plan.h"
 #include <functional>
 #include <future>
+#include <cstring>
+inline Fr fr_of(const mi_fr &x) { Fr r; std::memcpy(&r, &x, 32); return r; }   // a scalar of the C-ABI (Montgomery words) as the library's Fr
 
 // The MSMs of a proof that share one sort of their scalars, as the key serves them.
 struct KeyGroup {

@@ -18,11 +18,17 @@ struct R1csShape {
 // mi_last_error = "<who>: <field> ...".  d itself is checked by the caller (Setup reports a null trapdoor before the first field).
 int32_t mi_r1cs_validate(mi_ctx *ctx, const char *who, const mi_r1cs_desc *d, R1csShape &sh);
 
-// setup.hip's counting sort of one matrix's entries by column, enqueued on st (all pointers on the device): cnt[nb_wires] ends as the
-// histogram, off[nb_wires + 1] as its exclusive scan (through ctx->ws[WS_SCAN]), sorted[off[j] ..] holds (row, coefficient index) of
-// column j's entries in the order the atomics gave; rank[nnz] is scratch
-int32_t mi_setup_col_sort_enqueue(mi_ctx *ctx, hipStream_t st, const uint32_t *row_ptr, uint32_t n_rows, const uint32_t *col, const uint32_t *coeff, uint32_t nnz,
-                                  uint64_t nb_wires, uint32_t *cnt, uint32_t *off, uint32_t *rank, uint2 *sorted);
+// The matrices of a descriptor on the device one at a time, sorted by column (setup.hip; for phase2.hip too).  The five arrays are the
+// caller's device scratch for all three: row_ptr[nc + 1], col / cf / rank[the largest nnz], cnt[nb_wires].  upload(k) enqueues matrix k's
+// row starts, columns and coefficient indices on st; sort(k) its counting sort: cnt ends as the histogram, off[nb_wires + 1] as its
+// exclusive scan (through ctx->ws[WS_SCAN]), sorted[off[j] ..] holds (row, coefficient index) of column j's entries in the atomics' order
+struct MatrixSorter {
+    const mi_r1cs_desc *d;
+    const R1csShape *sh;   // (both outlive the sorter)
+    uint32_t *row_ptr = nullptr, *col = nullptr, *cf = nullptr, *cnt = nullptr, *rank = nullptr;
+    int32_t upload(mi_ctx *ctx, hipStream_t st, int k);
+    int32_t sort(mi_ctx *ctx, hipStream_t st, int k, uint32_t *off, uint2 *sorted);
+};
 
 struct SparseLong;   // sparse_fr.cuh
 struct R1csMatrixDev {

@@ -16,19 +16,17 @@
 //      one address.
 //   3  element-wise: t_j = beta A_j + alpha B_j + C_j, t_j / delta, t_j / gamma, the zero tests; prefix sums compact the A_j / B_j / K_j
 //      that own a key point into dense arrays; the Z exponents directly in the stored bit-reversed order
-//   4  points: mi_batch_scalar_mul_g1/g2_dev (csrc/fixed_base.hip), then the arrays go to the key through the adopt path of
-//      mi_pk_load_range / mi_pedersen_pk_adopt.  Every exponent array is freed as soon as its points exist.
+//   4  points: mi_batch_scalar_mul_g1/g2_dev (csrc/fixed_base.hip), then the arrays go to the key through key_handover.h (the adopt
+//      path of mi_pk_load_range / mi_pedersen_pk_adopt).  Every exponent array is freed as soon as its points exist.
 // Only the R1CS goes up; the infinity masks, the counts and the verifying key come down.
 #include "prove_internal.h"
 #include "r1cs_internal.h"
-#include "../../include/mi355x_groth16_vkfile.h"
+#include "key_handover.h"
+#include "fp12.cuh"
 #include "scan_u32.cuh"
 #include "sparse_fr.cuh"
-#include "dev_arena.h"
 #include <algorithm>
-#include <chrono>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 namespace {
@@ -128,7 +126,7 @@ __global__ void __launch_bounds__(256) k_col_sum_combine(Fr *out, const u32 *ctr
 
 // ---------------------------------------------------------------------------------------------------- 3: element-wise
 // keep_* = 1 where the wire owns a point of pk.G1.A / pk.G1.B (+ pk.G2.B) / pk.G1.K (private; the committed and commitment wires are
-// cleared afterwards by k_clear_flags); all three are scanned into the compaction's slots
+// cleared afterwards); WireSelection::scan turns all three into the compaction's slots
 __global__ void __launch_bounds__(256) k_elementwise(const Fr *A, const Fr *B, const Fr *C, Fr *Kd, Fr *Kg, uint8_t *inf_a, uint8_t *inf_b,
                                                      u32 *keep_a, u32 *keep_b, u32 *keep_k, u64 nb_wires, u32 nb_public, Fr alpha, Fr beta,
                                                      Fr delta_inv, Fr gamma_inv) {
@@ -141,17 +139,6 @@ __global__ void __launch_bounds__(256) k_elementwise(const Fr *A, const Fr *B, c
     const bool za = a.is_zero(), zb = b.is_zero();
     inf_a[j] = za; inf_b[j] = zb;
     keep_a[j] = !za; keep_b[j] = !zb; keep_k[j] = j >= nb_public;
-}
-__global__ void k_clear_flags(u32 *flags, const u32 *idx, u32 n) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) flags[idx[i]] = 0;
-}
-// slot[j] = scanned flags (slot[j + 1] != slot[j] where the wire is kept)
-__global__ void __launch_bounds__(256) k_compact(Fr *dst, const Fr *src, const u32 *slot, u64 n) {
-    const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const u32 s = slot[j];
-    if (slot[j + 1] != s) st_fr(dst + s, ld_fr(src + j));
 }
 __global__ void __launch_bounds__(256) k_gather_scale(Fr *dst, const Fr *src, const u32 *idx, u64 n, Fr factor) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -170,21 +157,6 @@ __global__ void __launch_bounds__(256) k_z_exps(Fr *Z, u32 log_n, Fr zt, TauPowe
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-Fr fr_of(const mi_fr &x) { Fr r; std::memcpy(&r, &x, 32); return r; }
-// the generators gnark-crypto's bn254 package fixes (g1 = (1, 2); g2 as in EIP-197)
-mi_g1_affine g1_generator() {
-    G1Aff g{Fp::one(), fe_from_u32<FpParams>(2)};
-    mi_g1_affine o; std::memcpy(&o, &g, 64); return o;
-}
-mi_g2_affine g2_generator() {
-    G2Aff g;
-    g.x.a0 = fe_from_u64x4<FpParams>(0x46debd5cd992f6edull, 0x674322d4f75edaddull, 0x426a00665e5c4479ull, 0x1800deef121f1e76ull);
-    g.x.a1 = fe_from_u64x4<FpParams>(0x97e485b7aef312c2ull, 0xf1aa493335a9e712ull, 0x7260bfb731fb5d25ull, 0x198e9393920d483aull);
-    g.y.a0 = fe_from_u64x4<FpParams>(0x4ce6cc0166fa7daaull, 0xe3d1e7690c43d37bull, 0x4aab71808dcb408full, 0x12c85ea5db8c6debull);
-    g.y.a1 = fe_from_u64x4<FpParams>(0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull);
-    mi_g2_affine o; std::memcpy(&o, &g, 128); return o;
-}
-
 // what the host derives from the inputs before any device work: the R1CS's shape (r1cs_internal.h, shared with the resident handle
 // of r1cs.hip) and the trapdoor's part
 struct Plan : R1csShape {
@@ -229,7 +201,7 @@ struct Timer {   // HIP events on the context's stream, one per phase boundary
 struct FrHalf {
     Fr *A = nullptr, *B = nullptr, *C = nullptr, *Kd = nullptr, *Kg = nullptr;
     uint8_t *inf_a = nullptr, *inf_b = nullptr;
-    u32 *slot_a = nullptr, *slot_b = nullptr, *slot_k = nullptr;   // nb_wires + 1 each: compaction slots, [nb_wires] = the count
+    WireSelection sel;   // the compaction slots
     float sort_ms = 0, sum_ms = 0;
     u64 long_columns = 0, chunks = 0;
 };
@@ -241,12 +213,12 @@ int32_t run_fr_half(mi_ctx *ctx, const mi_r1cs_desc *d, const Plan &pl, Arena &a
     // ---- upload
     MI_TRY(tm.mark(ctx, Timer::UP0));
     Fr *coeffs = nullptr, *L = nullptr;
-    u32 *row_ptr = nullptr, *col = nullptr, *cf = nullptr;
+    MatrixSorter ms{d, &pl};
     MI_TRY(ar.alloc(ctx, &coeffs, (size_t)d->n_coeffs));
     if (d->n_coeffs) MI_CHECK_HIP(ctx, hipMemcpyAsync(coeffs, d->coeffs, d->n_coeffs * 32, hipMemcpyHostToDevice, st));
-    MI_TRY(ar.alloc(ctx, &row_ptr, (size_t)pl.nc + 1));
-    MI_TRY(ar.alloc(ctx, &col, (size_t)max_nnz));
-    MI_TRY(ar.alloc(ctx, &cf, (size_t)max_nnz));
+    MI_TRY(ar.alloc(ctx, &ms.row_ptr, (size_t)pl.nc + 1));
+    MI_TRY(ar.alloc(ctx, &ms.col, (size_t)max_nnz));
+    MI_TRY(ar.alloc(ctx, &ms.cf, (size_t)max_nnz));
     MI_TRY(tm.mark(ctx, Timer::UP1));
     // ---- 1: Lagrange
     MI_TRY(ar.alloc(ctx, &L, (size_t)pl.nc));
@@ -260,14 +232,14 @@ int32_t run_fr_half(mi_ctx *ctx, const mi_r1cs_desc *d, const Plan &pl, Arena &a
     }
     MI_TRY(tm.mark(ctx, Timer::LAG));
     // ---- 2: the three transposed products, one after the other over the same scratch
-    u32 *cnt = nullptr, *off = nullptr, *ctr = nullptr, *rank = nullptr;
+    u32 *off = nullptr, *ctr = nullptr;
     uint2 *sorted = nullptr, *pieces = nullptr;
     SparseLong *long_cols = nullptr;
     Fr *partial = nullptr;
     const size_t cap_long = (size_t)max_nnz / SPARSE_SHORT + 1;   // a long column has more than SPARSE_SHORT entries and at most len / SPARSE_SHORT pieces
-    MI_TRY(ar.alloc(ctx, &cnt, (size_t)nw));
+    MI_TRY(ar.alloc(ctx, &ms.cnt, (size_t)nw));
     MI_TRY(ar.alloc(ctx, &off, (size_t)nw + 1));
-    MI_TRY(ar.alloc(ctx, &rank, (size_t)max_nnz));
+    MI_TRY(ar.alloc(ctx, &ms.rank, (size_t)max_nnz));
     MI_TRY(ar.alloc(ctx, &sorted, (size_t)max_nnz));
     MI_TRY(ar.alloc(ctx, &pieces, cap_long));
     MI_TRY(ar.alloc(ctx, &long_cols, cap_long));
@@ -277,7 +249,6 @@ int32_t run_fr_half(mi_ctx *ctx, const mi_r1cs_desc *d, const Plan &pl, Arena &a
     MI_TRY(ar.alloc(ctx, &f.B, (size_t)nw));
     MI_TRY(ar.alloc(ctx, &f.C, (size_t)nw));
     MI_CHECK_HIP(ctx, hipMemsetAsync(ctr, 0, 32, st));
-    const mi_r1cs_matrix *mats[3] = {&d->A, &d->B, &d->C};
     Fr *outs[3] = {f.A, f.B, f.C};
     // per matrix: e[0] upload e[1] sort e[2] sum e[3]
     struct Events { hipEvent_t e[4]{}; ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } evs;
@@ -285,15 +256,10 @@ int32_t run_fr_half(mi_ctx *ctx, const mi_r1cs_desc *d, const Plan &pl, Arena &a
     hipEvent_t e0 = evs.e[0], e1 = evs.e[1], e2 = evs.e[2], e3 = evs.e[3];
     const unsigned wave_grid = (unsigned)ctx->cu_count * 8;   // blocks of 4 waves for the grid-stride passes
     for (int k = 0; k < 3; k++) {
-        const u32 nnz = pl.nnz[k];
         MI_CHECK_HIP(ctx, hipEventRecord(e0, st));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(row_ptr, pl.row_ptr[k].data(), (pl.nc + 1) * 4, hipMemcpyHostToDevice, st));
-        if (nnz) {
-            MI_CHECK_HIP(ctx, hipMemcpyAsync(col, mats[k]->col, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-            MI_CHECK_HIP(ctx, hipMemcpyAsync(cf, mats[k]->coeff, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-        }
+        MI_TRY(ms.upload(ctx, st, k));
         MI_CHECK_HIP(ctx, hipEventRecord(e1, st));
-        MI_TRY(mi_setup_col_sort_enqueue(ctx, st, row_ptr, (u32)pl.nc, col, cf, nnz, nw, cnt, off, rank, sorted));
+        MI_TRY(ms.sort(ctx, st, k, off, sorted));
         MI_CHECK_HIP(ctx, hipEventRecord(e2, st));
         MI_CHECK_HIP(ctx, hipMemsetAsync(ctr, 0, 8, st));
         const ColTerm term{L, coeffs};
@@ -312,31 +278,21 @@ int32_t run_fr_half(mi_ctx *ctx, const mi_r1cs_desc *d, const Plan &pl, Arena &a
         f.chunks += ctr_h[0]; f.long_columns += ctr_h[1];
     }
     MI_TRY(tm.mark(ctx, Timer::SUM));
-    for (void *p : {(void *)row_ptr, (void *)col, (void *)cf, (void *)cnt, (void *)off, (void *)rank, (void *)sorted, (void *)pieces, (void *)long_cols, (void *)partial, (void *)L, (void *)coeffs, (void *)ctr})
+    for (void *p : {(void *)ms.row_ptr, (void *)ms.col, (void *)ms.cf, (void *)ms.cnt, (void *)off, (void *)ms.rank, (void *)sorted, (void *)pieces, (void *)long_cols, (void *)partial, (void *)L, (void *)coeffs, (void *)ctr})
         ar.release(p);
     // ---- 3: element-wise and the compaction slots
     MI_TRY(ar.alloc(ctx, &f.Kd, (size_t)nw));
     MI_TRY(ar.alloc(ctx, &f.Kg, (size_t)nw));
     MI_TRY(ar.alloc(ctx, &f.inf_a, (size_t)nw));
     MI_TRY(ar.alloc(ctx, &f.inf_b, (size_t)nw));
-    MI_TRY(ar.alloc(ctx, &f.slot_a, (size_t)nw + 1));
-    MI_TRY(ar.alloc(ctx, &f.slot_b, (size_t)nw + 1));
-    MI_TRY(ar.alloc(ctx, &f.slot_k, (size_t)nw + 1));
+    f.sel.nb_wires = nw;
+    MI_TRY(ar.alloc(ctx, &f.sel.slot_a, (size_t)nw + 1));
+    MI_TRY(ar.alloc(ctx, &f.sel.slot_b, (size_t)nw + 1));
+    MI_TRY(ar.alloc(ctx, &f.sel.slot_k, (size_t)nw + 1));
     hipLaunchKernelGGL(k_elementwise, dim3(mi_blocks_of(nw, 256)), dim3(256), 0, st, (const Fr *)f.A, (const Fr *)f.B, (const Fr *)f.C, f.Kd, f.Kg, f.inf_a, f.inf_b,
-                       f.slot_a, f.slot_b, f.slot_k, nw, pl.nb_public, pl.alpha, pl.beta, pl.delta_inv, pl.gamma_inv);
+                       f.sel.slot_a, f.sel.slot_b, f.sel.slot_k, nw, pl.nb_public, pl.alpha, pl.beta, pl.delta_inv, pl.gamma_inv);
     MI_CHECK_HIP(ctx, hipGetLastError());
-    if (!pl.removed.empty()) {
-        u32 *rem = nullptr;
-        MI_TRY(ar.alloc(ctx, &rem, pl.removed.size()));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(rem, pl.removed.data(), pl.removed.size() * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_clear_flags, dim3(mi_blocks_of(pl.removed.size(), 256)), dim3(256), 0, st, f.slot_k, (const u32 *)rem, (u32)pl.removed.size());
-        MI_CHECK_HIP(ctx, hipGetLastError());
-        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
-        ar.release(rem);
-    }
-    // in == out: k_scan_final holds a block's values in registers before it stores the first of them, no block reads another's, and
-    // the block sums come from an earlier launch.  The count of kept wires arrives in slot[nw].
-    for (u32 *s : {f.slot_a, f.slot_b, f.slot_k}) MI_TRY(exclusive_scan(ctx, st, s, nw, s, ctx->ws[WS_SCAN]));
+    MI_TRY(f.sel.scan(ctx, ar, pl.removed));
     MI_TRY(tm.mark(ctx, Timer::ELEM));
     return MI_OK;
 }
@@ -359,18 +315,28 @@ void fill_stats(mi_ctx *ctx, const Plan &pl, Timer &tm, const FrHalf &f, double 
     s.entries = (u64)pl.nnz[0] + pl.nnz[1] + pl.nnz[2];
     s.long_columns = f.long_columns; s.chunks = f.chunks;
 }
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace
 
-// r1cs_internal.h: the counting sort by column of one matrix, for phase2.hip too
-int32_t mi_setup_col_sort_enqueue(mi_ctx *ctx, hipStream_t st, const uint32_t *row_ptr, uint32_t n_rows, const uint32_t *col, const uint32_t *coeff, uint32_t nnz,
-                                  uint64_t nb_wires, uint32_t *cnt, uint32_t *off, uint32_t *rank, uint2 *sorted) {
+// r1cs_internal.h: one matrix up, then its counting sort by column; for phase2.hip too
+int32_t MatrixSorter::upload(mi_ctx *ctx, hipStream_t st, int k) {
+    const mi_r1cs_matrix *mats[3] = {&d->A, &d->B, &d->C};
+    const u32 nnz = sh->nnz[k];
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(row_ptr, sh->row_ptr[k].data(), (sh->nc + 1) * 4, hipMemcpyHostToDevice, st));
+    if (nnz) {
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(col, mats[k]->col, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(cf, mats[k]->coeff, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+    }
+    return MI_OK;
+}
+int32_t MatrixSorter::sort(mi_ctx *ctx, hipStream_t st, int k, uint32_t *off, uint2 *sorted) {
+    const u32 nnz = sh->nnz[k];
+    const u64 nb_wires = sh->nb_wires;
     MI_CHECK_HIP(ctx, hipMemsetAsync(cnt, 0, nb_wires * 4, st));
-    if (nnz) hipLaunchKernelGGL(k_col_count, dim3(mi_blocks_of(nnz, 256)), dim3(256), 0, st, col, nnz, cnt, rank);
+    if (nnz) hipLaunchKernelGGL(k_col_count, dim3(mi_blocks_of(nnz, 256)), dim3(256), 0, st, (const u32 *)col, nnz, cnt, rank);
     MI_TRY(exclusive_scan(ctx, st, cnt, nb_wires, off, ctx->ws[WS_SCAN]));   // off[nb_wires] = the number of entries
-    if (nnz) hipLaunchKernelGGL(k_col_scatter, dim3(mi_blocks_of(((u64)nnz + 3) / 4, 256)), dim3(256), 0, st, row_ptr, n_rows, col, coeff, nnz, (const u32 *)off,
-                                (const u32 *)rank, sorted);
+    if (nnz) hipLaunchKernelGGL(k_col_scatter, dim3(mi_blocks_of(((u64)nnz + 3) / 4, 256)), dim3(256), 0, st, (const u32 *)row_ptr, (u32)sh->nc, (const u32 *)col,
+                                (const u32 *)cf, nnz, (const u32 *)off, (const u32 *)rank, sorted);
     return MI_OK;
 }
 
@@ -413,12 +379,9 @@ int32_t mi_groth16_setup_exponents(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const 
     return MI_OK;
 }
 
-// Where the stream of the key goes (mi_groth16_setup_to_stream); null for mi_groth16_setup.
-// with_vk (mi_groth16_setup_to_streams): the verifying key's stream too, with a triple of its own.
-struct KeyStream { uint32_t encoding; uint8_t *out; size_t cap; size_t *len; bool with_vk = false; uint8_t *vk_out = nullptr; size_t vk_cap = 0; size_t *vk_len = nullptr; };
-// groth16.Setup behind both entry points.  ks: the key's stream is written from the plain arrays, right before the key takes them.
-// pk_out null (with ks only): no key is built and ped_out is not written.
-static int32_t setup_run(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, const KeyStream *ks, mi_pk **pk_out, mi_pedersen_pk **ped_out,
+// groth16.Setup behind the three entry points.  ks (mi_groth16_setup_to_stream[s]; null for mi_groth16_setup): the key's stream is written
+// from the plain arrays, right before the key takes them.  pk_out null (with ks only): no key is built and ped_out is not written.
+static int32_t setup_run(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, const KeyStreams *ks, mi_pk **pk_out, mi_pedersen_pk **ped_out,
                          mi_vk_out *vk_out) {
     if (!ctx) return MI_EINVAL;
     if (!pk_out && !ks) MI_FAIL(ctx, MI_EINVAL, "setup: pk_out is null");
@@ -433,11 +396,11 @@ static int32_t setup_run(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
     std::vector<mi_pedersen_arrays> ped_arrays;   // the plain Pedersen arrays, for the stream
     const double t0 = now_ms();
     ctx->setup_stats = mi_setup_stats{};
-    const mi_g1_affine g1 = g1_generator();
-    const mi_g2_affine g2 = g2_generator();
+    const G1Aff g1 = g1_generator();
+    const G2Aff g2 = g2_generator();
     hipStream_t st = ctx->stream;
     const u64 nw = pl.nb_wires;
-    u32 n_ped = 0;
+    KeyHandover hand(ctx, pk_out, ped_out);
     auto body = [&]() -> int32_t {
         Arena ar;
         Timer tm;
@@ -446,53 +409,34 @@ static int32_t setup_run(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
         MI_TRY(run_fr_half(ctx, r1cs, pl, ar, tm, f));
         // masks and counts to the host
         std::vector<uint8_t> ia(nw), ib(nw);
-        u32 n_a = 0, n_b = 0, n_k = 0;
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(ia.data(), f.inf_a, nw, hipMemcpyDeviceToHost, st));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(ib.data(), f.inf_b, nw, hipMemcpyDeviceToHost, st));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(&n_a, f.slot_a + nw, 4, hipMemcpyDeviceToHost, st));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(&n_b, f.slot_b + nw, 4, hipMemcpyDeviceToHost, st));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(&n_k, f.slot_k + nw, 4, hipMemcpyDeviceToHost, st));
-        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+        WireSelection &sel = f.sel;
+        MI_TRY(sel.fetch(ctx, f.inf_a, f.inf_b, ia.data(), ib.data()));
         ar.release(f.inf_a); ar.release(f.inf_b);
+        KeyArrays ka(pl.log_n, pl.nb_public, nw, ia.data(), ib.data(), pl.removed.data(), pl.removed.size());
+        ka.n[KEY_G1_A] = sel.n_a; ka.n[KEY_G1_B] = ka.n[KEY_G2_B] = sel.n_b; ka.n[KEY_G1_K] = sel.n_k; ka.n[KEY_G1_Z] = pl.N;
         if (ks) {   // the counts are known: a buffer that cannot hold the stream is refused before the points are computed
-            mi_pk_desc counts;
-            std::memset(&counts, 0, sizeof(counts));
-            counts.nb_wires = nw; counts.n_g1_a = n_a; counts.n_g1_b = counts.n_g2_b = n_b; counts.n_g1_k = n_k; counts.n_g1_z = pl.N;
             std::vector<mi_pedersen_arrays> pc(pl.n_commitments);
             for (u32 k = 0; k < pl.n_commitments; k++) pc[k] = mi_pedersen_arrays{nullptr, nullptr, r1cs->n_committed[k]};
-            size_t need = 0;
-            if (mi_pk_stream_size(&counts, pc.data(), pl.n_commitments, ks->encoding, &need) != MI_OK) MI_FAIL(ctx, MI_EINVAL, "setup: encoding is neither MI_KEYFILE_RAW nor MI_KEYFILE_COMPRESSED");
-            if (ks->len) *ks->len = need;
-            size_t vk_need = 0;
-            if (ks->with_vk) {
-                mi_vk_file_desc vc;
-                std::memset(&vc, 0, sizeof(vc));
-                vc.n_k = pl.vk_wires.size(); vc.nb_public = pl.nb_public; vc.n_commitments = pl.n_commitments;
-                (void)mi_vk_stream_size(&vc, ks->encoding, &vk_need);   // the encoding has passed above
-                if (ks->vk_len) *ks->vk_len = vk_need;
-            }
-            if (!ks->out || ks->cap < need) MI_FAIL(ctx, MI_EINVAL, "setup: the key's stream takes " + std::to_string(need) + " bytes, out_host has room for " + std::to_string(ks->out ? ks->cap : 0));
-            if (ks->with_vk && (!ks->vk_out || ks->vk_cap < vk_need))
-                MI_FAIL(ctx, MI_EINVAL, "setup: the verifying key's stream takes " + std::to_string(vk_need) + " bytes, vk_out_host has room for " + std::to_string(ks->vk_out ? ks->vk_cap : 0));
+            MI_TRY(ks->check(ctx, "setup", ka.desc(), pc.data(), pl.n_commitments, pl.vk_wires.size()));
         }
         // dense scalar arrays; each per-wire array goes as soon as it has been read
         Fr *sa = nullptr, *sb = nullptr, *sk = nullptr;
         auto compact = [&](Fr **dst, Fr *src, u32 *slot, u32 n) -> int32_t {
             MI_TRY(ar.alloc(ctx, dst, (size_t)n));
-            hipLaunchKernelGGL(k_compact, dim3(mi_blocks_of(nw, 256)), dim3(256), 0, st, *dst, (const Fr *)src, (const u32 *)slot, nw);
+            MI_TRY(sel.compact(ctx, *dst, src, slot, sizeof(Fr)));
             MI_CHECK_HIP(ctx, hipGetLastError());
             MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
             ar.release(src); ar.release(slot);
             return MI_OK;
         };
-        MI_TRY(compact(&sa, f.A, f.slot_a, n_a));
-        MI_TRY(compact(&sb, f.B, f.slot_b, n_b));
+        MI_TRY(compact(&sa, f.A, sel.slot_a, sel.n_a));
+        MI_TRY(compact(&sb, f.B, sel.slot_b, sel.n_b));
         ar.release(f.C);
-        MI_TRY(compact(&sk, f.Kd, f.slot_k, n_k));
+        MI_TRY(compact(&sk, f.Kd, sel.slot_k, sel.n_k));
         // a batch of points from device scalars into a fresh array
         auto mul_g1 = [&](void **dst, const Fr *sc, size_t n) -> int32_t {
             MI_TRY(ar.alloc(ctx, dst, n * 64));
-            return mi_batch_scalar_mul_g1_dev(ctx, &g1, (const mi_fr *)sc, n, (mi_g1_affine *)*dst);
+            return mi_batch_scalar_mul_g1_dev(ctx, (const mi_g1_affine *)&g1, (const mi_fr *)sc, n, (mi_g1_affine *)*dst);
         };
         auto gather = [&](Fr **dst, const u32 *wires, size_t n, const Fr &factor) -> int32_t {
             u32 *idx = nullptr;
@@ -531,14 +475,10 @@ static int32_t setup_run(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
             ar.release(s0); ar.release(s1);
             ped_arrays.push_back(mi_pedersen_arrays{(const mi_g1_affine *)basis, (const mi_g1_affine *)bes, n});
             if (!build) continue;   // write only: the arrays stay the arena's
-            MI_TRY(mi_pedersen_pk_adopt(ctx, basis, bes, n, &ped_out[k]));
-            ar.disown(basis); ar.disown(bes);
-            n_ped = k + 1;
+            MI_TRY(hand.adopt_pedersen(&basis, &bes, n, &ar));
         }
         ar.release(f.Kg);
         // alpha, beta, delta on G1; beta, delta, gamma on G2
-        G1Aff small1[3];
-        G2Aff small2[3];
         {
             const Fr sc[4] = {pl.alpha, pl.beta, fr_of(trapdoor->delta), fr_of(trapdoor->gamma)};
             Fr *ds = nullptr;
@@ -547,78 +487,51 @@ static int32_t setup_run(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
             MI_CHECK_HIP(ctx, hipMemcpyAsync(ds, sc, sizeof(sc), hipMemcpyHostToDevice, st));
             MI_TRY(mul_g1(&p1, ds, 3));
             MI_TRY(ar.alloc(ctx, &p2, (size_t)3 * 128));
-            MI_TRY(mi_batch_scalar_mul_g2_dev(ctx, &g2, (const mi_fr *)(ds + 1), 3, (mi_g2_affine *)p2));
-            MI_CHECK_HIP(ctx, hipMemcpyAsync(small1, p1, sizeof(small1), hipMemcpyDeviceToHost, st));
-            MI_CHECK_HIP(ctx, hipMemcpyAsync(small2, p2, sizeof(small2), hipMemcpyDeviceToHost, st));
+            MI_TRY(mi_batch_scalar_mul_g2_dev(ctx, (const mi_g2_affine *)&g2, (const mi_fr *)(ds + 1), 3, (mi_g2_affine *)p2));
+            MI_CHECK_HIP(ctx, hipMemcpyAsync(ka.small1, p1, sizeof(ka.small1), hipMemcpyDeviceToHost, st));
+            MI_CHECK_HIP(ctx, hipMemcpyAsync(ka.small2, p2, sizeof(ka.small2), hipMemcpyDeviceToHost, st));
             MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
             ar.release(ds); ar.release(p1); ar.release(p2);
         }
-        std::memcpy(&vk_out->alpha1, &small1[0], 64);
-        std::memcpy(&vk_out->beta2, &small2[0], 128); std::memcpy(&vk_out->delta2, &small2[1], 128); std::memcpy(&vk_out->gamma2, &small2[2], 128);
-        if (ks && ks->with_vk) {   // the verifying key's stream: everything it holds is on the host here; its lists start empty
-            mi_vk_file_desc vd;
-            std::memset(&vd, 0, sizeof(vd));
-            vd.alpha1 = vk_out->alpha1; vd.beta2 = vk_out->beta2; vd.gamma2 = vk_out->gamma2; vd.delta2 = vk_out->delta2;
-            std::memcpy(&vd.beta1, &small1[1], 64); std::memcpy(&vd.delta1, &small1[2], 64);
-            vd.k = vk_out->k; vd.n_k = vk_out->n_k; vd.nb_public = pl.nb_public; vd.n_commitments = pl.n_commitments;
-            std::vector<mi_pedersen_vk> pvk(pl.n_commitments);
-            MI_TRY(mi_pedersen_vk_make(ctx, trapdoor->sigma, pl.n_commitments, pvk.data()));
-            vd.ped = pvk.data();
-            MI_TRY(mi_vk_write(ctx, &vd, ks->encoding, ks->vk_out, ks->vk_cap, ks->vk_len));
-        }
+        std::memcpy(&vk_out->alpha1, &ka.small1[0], 64);
+        std::memcpy(&vk_out->beta2, &ka.small2[0], 128); std::memcpy(&vk_out->delta2, &ka.small2[1], 128); std::memcpy(&vk_out->gamma2, &ka.small2[2], 128);
+        // the verifying key's stream: everything it holds is on the host here
+        if (ks && ks->with_vk) MI_TRY(ks->write_vk(ctx, ka, vk_out->k, vk_out->n_k, trapdoor->sigma, pl.n_commitments));
         // the five arrays of the key
-        void *arrays[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        MI_TRY(mul_g1(&arrays[0], sa, n_a));
+        MI_TRY(mul_g1(&ka.arr[KEY_G1_A], sa, sel.n_a));
         MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
         ar.release(sa);
-        MI_TRY(mul_g1(&arrays[1], sb, n_b));
-        MI_TRY(ar.alloc(ctx, &arrays[4], (size_t)n_b * 128));
-        MI_TRY(mi_batch_scalar_mul_g2_dev(ctx, &g2, (const mi_fr *)sb, n_b, (mi_g2_affine *)arrays[4]));
+        MI_TRY(mul_g1(&ka.arr[KEY_G1_B], sb, sel.n_b));
+        MI_TRY(ar.alloc(ctx, &ka.arr[KEY_G2_B], (size_t)sel.n_b * 128));
+        MI_TRY(mi_batch_scalar_mul_g2_dev(ctx, (const mi_g2_affine *)&g2, (const mi_fr *)sb, sel.n_b, (mi_g2_affine *)ka.arr[KEY_G2_B]));
         MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
         ar.release(sb);
-        MI_TRY(mul_g1(&arrays[2], sk, n_k));
+        MI_TRY(mul_g1(&ka.arr[KEY_G1_K], sk, sel.n_k));
         MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
         ar.release(sk);
         {
             Fr *Z = nullptr;
             MI_TRY(ar.alloc(ctx, &Z, (size_t)pl.N));
             MI_TRY(z_exps_dev(ctx, pl, Z));
-            MI_TRY(mul_g1(&arrays[3], Z, pl.N));
+            MI_TRY(mul_g1(&ka.arr[KEY_G1_Z], Z, pl.N));
             MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
             ar.release(Z);
         }
         MI_TRY(tm.mark(ctx, Timer::POINTS));
         // ---- the key takes the arrays
-        mi_pk_desc d;
-        std::memset(&d, 0, sizeof(d));
-        d.log_n = pl.log_n; d.nb_public = pl.nb_public; d.nb_wires = nw;
-        d.g1_a = (const mi_g1_affine *)arrays[0]; d.n_g1_a = n_a;
-        d.g1_b = (const mi_g1_affine *)arrays[1]; d.n_g1_b = n_b;
-        d.g1_k = (const mi_g1_affine *)arrays[2]; d.n_g1_k = n_k;
-        d.g1_z = (const mi_g1_affine *)arrays[3]; d.n_g1_z = pl.N;
-        d.g2_b = (const mi_g2_affine *)arrays[4]; d.n_g2_b = n_b;
-        std::memcpy(&d.alpha1, &small1[0], 64); std::memcpy(&d.beta1, &small1[1], 64); std::memcpy(&d.delta1, &small1[2], 64);
-        std::memcpy(&d.beta2, &small2[0], 128); std::memcpy(&d.delta2, &small2[1], 128);
-        d.infinity_a = ia.data(); d.infinity_b = ib.data();
-        d.committed_wires = pl.removed.empty() ? nullptr : pl.removed.data(); d.n_committed = pl.removed.size();
-        if (ks) MI_TRY(mi_pk_write_dev(ctx, &d, ped_arrays.data(), pl.n_commitments, ks->encoding, ks->out, ks->cap, ks->len));
-        if (build) {
-            bool took = false;
-            const int32_t lr = mi_pk_load_range(ctx, &d, pk_out, true, nullptr, /*forced=*/nullptr, /*adopt=*/true, &took);
-            if (took) for (void *a : arrays) ar.disown(a);   // the key's now (it has released them itself if it failed after taking them)
-            MI_TRY(lr);
+        if (ks) {
+            const mi_pk_desc d = ka.desc();
+            MI_TRY(mi_pk_write_dev(ctx, &d, ped_arrays.data(), pl.n_commitments, ks->encoding, ks->out, ks->cap, ks->len));
         }
+        if (build) MI_TRY(hand.adopt_key(ka, &ar));
         MI_TRY(tm.mark(ctx, Timer::DONE));
         MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
         fill_stats(ctx, pl, tm, f, now_ms() - t0);
         return MI_OK;
     };
     const int32_t rc = body();
-    if (rc != MI_OK) {
-        (void)hipStreamSynchronize(st);
-        if (build && *pk_out) { mi_pk_free(ctx, *pk_out); *pk_out = nullptr; }
-        for (u32 k = 0; k < n_ped; k++) { mi_pedersen_pk_free(ctx, ped_out[k]); ped_out[k] = nullptr; }
-    }
+    if (rc == MI_OK) hand.dismiss();
+    else (void)hipStreamSynchronize(st);
     return rc;
 }
 int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, mi_pk **pk_out, mi_pedersen_pk **ped_out, mi_vk_out *vk_out) {
@@ -626,13 +539,13 @@ int32_t mi_groth16_setup(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoo
 }
 int32_t mi_groth16_setup_to_stream(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, uint32_t encoding, uint8_t *out_host, size_t cap,
                                    size_t *len, mi_pk **pk_out, mi_pedersen_pk **ped_out, mi_vk_out *vk_out) {
-    const KeyStream ks{encoding, out_host, cap, len};
+    const KeyStreams ks{encoding, out_host, cap, len};
     return setup_run(ctx, r1cs, trapdoor, &ks, pk_out, ped_out, vk_out);
 }
 int32_t mi_groth16_setup_to_streams(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_trapdoor *trapdoor, uint32_t encoding, uint8_t *out_host, size_t cap,
                                     size_t *len, uint8_t *vk_out_host, size_t vk_cap, size_t *vk_len, mi_pk **pk_out, mi_pedersen_pk **ped_out,
                                     mi_vk_out *vk_out) {
-    const KeyStream ks{encoding, out_host, cap, len, true, vk_out_host, vk_cap, vk_len};
+    const KeyStreams ks{encoding, out_host, cap, len, true, vk_out_host, vk_cap, vk_len};
     return setup_run(ctx, r1cs, trapdoor, &ks, pk_out, ped_out, vk_out);
 }
 

@@ -239,7 +239,7 @@ int32_t mi_pedersen_vk_make(mi_ctx *ctx, const mi_fr *sigma, uint32_t n, mi_pede
     if (!ctx) return MI_EINVAL;
     if ((!sigma || !out) && n) MI_FAIL(ctx, MI_EINVAL, "pedersen vk: null sigma or output pointer");
     if (!n) return MI_OK;
-    const G2Aff gen{fp12c_g2gen_x(), fp12c_g2gen_y()};
+    const G2Aff gen = g2_generator();
     mi_g2_affine g;
     std::memcpy(&g, &gen, sizeof(g));
     std::vector<mi_fr> neg(n);
