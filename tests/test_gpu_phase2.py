@@ -208,27 +208,12 @@ def test_phase2_cancelling_entries_and_columns(ctx, root_of_unity):
 EDGE_LENS = (16, 17, 512, 513, 2 * 512 + 1)
 
 
-def transposed(r1cs):
-    """the R1CS whose matrices are the transposes of r1cs's: rows become columns, by a stable argsort of col"""
-    nc, nw = r1cs["n_constraints"], r1cs["nb_wires"]
-    out = {"n_constraints": nw, "nb_wires": nc, "nb_public": r1cs["nb_public"], "coeffs": r1cs["coeffs"], "commitments": []}
-    for name in "ABC":
-        rp, col, cf = r1cs[name]
-        rp = np.asarray(rp, np.uint64).astype(np.int64)
-        row_of = np.repeat(np.arange(nc, dtype=np.uint32), rp[1:] - rp[:-1])
-        order = np.argsort(col, kind="stable")
-        trp = np.zeros(nw + 1, np.uint64)
-        trp[1:] = np.cumsum(np.bincount(col, minlength=nw)).astype(np.uint64)
-        out[name] = (trp, np.ascontiguousarray(row_of[order]), np.ascontiguousarray(cf[order]))
-    return out
-
-
 def test_phase2_columns_at_the_split_edges(ctx):
     """columns of exactly 0..4, 16, 17, 512, 513 and 2 * 512 + 1 entries in each matrix (the transposes of r1cs_cases.skewed_r1cs's
     planted rows), for the G1 sums and the G2 sum: a lane's list, the first list cut, one full piece, one piece and one entry, two
     pieces and one entry.  The plan's counts are those of the untransposed rows."""
     src = RC.skewed_r1cs(n_constraints=200, nb_wires=1024, nb_public=9, seed=1408, long_lens=EDGE_LENS, n_coeffs=64)
-    r1cs = transposed(src)
+    r1cs = RC.transposed(src)
     assert r1cs["n_constraints"] == 1024 and r1cs["nb_wires"] == 200
     for name in "ABC":
         lens = np.bincount(r1cs[name][1], minlength=200)

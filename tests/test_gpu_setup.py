@@ -118,27 +118,12 @@ def test_setup_exponents_skew_and_size(ctx, log_n, n_coeffs):
     print(f"host reference 2^{log_n}: {time.perf_counter() - t0:.1f} s on {cref.num_threads()} threads")
 
 
-def _transposed(r1cs):
-    """the R1CS whose matrices are the transposes of r1cs's: rows become columns, by a stable argsort of col"""
-    nc, nw = r1cs["n_constraints"], r1cs["nb_wires"]
-    out = {"n_constraints": nw, "nb_wires": nc, "nb_public": r1cs["nb_public"], "coeffs": r1cs["coeffs"], "commitments": []}
-    for name in "ABC":
-        rp, col, cf = r1cs[name]
-        rp = np.asarray(rp, np.uint64).astype(np.int64)
-        row_of = np.repeat(np.arange(nc, dtype=np.uint32), rp[1:] - rp[:-1])
-        order = np.argsort(col, kind="stable")
-        trp = np.zeros(nw + 1, np.uint64)
-        trp[1:] = np.cumsum(np.bincount(col, minlength=nw)).astype(np.uint64)
-        out[name] = (trp, np.ascontiguousarray(row_of[order]), np.ascontiguousarray(cf[order]))
-    return out
-
-
 def test_setup_columns_at_the_split_edges(ctx):
     """Columns of exactly 0..4, 16, 17, 64, 511, 512, 513, 5000 and 100 003 entries (r1cs_cases.LONG_LENS: the last is 196 pieces, so the
     combine pass's lane stride loops): the transposes of r1cs_cases.skewed_r1cs's matrices, whose planted ROWS those are.  4096
     constraints (log_n = 12) over 3000 wires.  The plan's counts are those of the untransposed rows (r1cs_cases.split_counts)."""
     src = RC.skewed_r1cs(n_constraints=3000, nb_wires=4096, nb_public=33, seed=1208)
-    r1cs = _transposed(src)
+    r1cs = RC.transposed(src)
     nw = r1cs["nb_wires"]
     assert r1cs["n_constraints"] == 4096 and nw == 3000
     td = S.synth_trapdoor(1209)
@@ -147,18 +132,21 @@ def test_setup_columns_at_the_split_edges(ctx):
     print(f"setup_exponents at the split edges: {st}")
     assert (st["long_columns"], st["chunks"]) == RC.split_counts(src)
     assert st["entries"] == sum(len(r1cs[name][1]) for name in "ABC")
-    L, _ = S.lagrange_rows(r1cs["n_constraints"], td["tau"])
-    rho = cref.gen_scalars(nw, 1210, 0)
+    RC.check_columns(r1cs, td, got, split_edge_wires(src, r1cs), seed=1210)
+    S.check_z(td, 12, got["z"])
+
+
+def split_edge_wires(src, r1cs):
+    """name -> the columns test_setup_columns_at_the_split_edges recomputes in integers: the planted ones, the ends, an empty one, 32 random"""
+    nw = r1cs["nb_wires"]
     wires = {0, 1, nw - 2, nw - 1} | {int(x) for x in np.random.default_rng(1211).integers(0, nw, 32)}
-    for name, key in (("A", "a"), ("B", "b"), ("C", "c")):
+    out = {}
+    for name in "ABC":
         lens = np.bincount(r1cs[name][1], minlength=nw)
         planted = src["long_at"][name]
         assert [int(lens[planted[n]]) for n in RC.LONG_LENS] == list(RC.LONG_LENS) and set(range(5)) <= set(lens.tolist())
-        for j in sorted(wires | set(planted.values()) | {int(np.nonzero(lens == 0)[0][0])}):
-            assert S._int(got[key][j]) == S.column_by_integers(r1cs, name, L, j), f"{name}_{j} ({lens[j]} entries)"
-        lhs, rhs = D.fr_dot(rho, got[key]), D.fr_dot(RC.eval_rows(r1cs, name, rho), L)
-        assert S._int(lhs) == S._int(rhs), f"matrix {name}: sum_j rho_j M_j differs from sum_i L_i (M rho)_i"
-    S.check_z(td, 12, got["z"])
+        out[name] = wires | set(planted.values()) | {int(np.nonzero(lens == 0)[0][0])}
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------- 3: whole key
