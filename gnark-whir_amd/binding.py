@@ -25,7 +25,7 @@ EXPORTS = [
     "mi_batch_scalar_mul_g1", "mi_batch_scalar_mul_g1_dev", "mi_batch_scalar_mul_g2", "mi_batch_scalar_mul_g2_dev",
     "mi_pedersen_pk_load", "mi_pedersen_pk_free", "mi_pedersen_commit", "mi_pedersen_prove_knowledge", "mi_pedersen_fold",
     "mi_debug_set_prove_fixed_base", "mi_debug_set_prove_schedule", "mi_debug_set_msm_batch_affine", "mi_debug_set_msm_group_bits", "mi_debug_inject_hip_failure", "mi_debug_set_ntt_plan", "mi_debug_set_ntt_threads", "mi_debug_set_ntt_wave_stages",
-    "mi_debug_set_msm_plan", "mi_debug_set_msm_chunk", "mi_debug_set_msm_one_pass_sort", "mi_debug_set_msm_bound_levels", "mi_debug_set_msm_limb29", "mi_debug_set_msm_l1_waves", "mi_debug_set_msm_precompute_batched", "mi_debug_set_ntt_fuse_pair", "mi_debug_set_knob", "mi_debug_get_counter", "mi_debug_set_stream_plan", "mi_debug_set_trace_ranges", "mi_set_trace_ranges",
+    "mi_debug_set_msm_plan", "mi_debug_set_msm_chunk", "mi_debug_set_msm_one_pass_sort", "mi_debug_set_msm_bound_levels", "mi_debug_set_msm_limb29", "mi_debug_set_msm_l1_waves", "mi_debug_set_msm_precompute_batched", "mi_debug_set_ntt_fuse_pair", "mi_debug_set_knob", "mi_debug_get_counter", "mi_debug_scale_powers_dev", "mi_debug_set_stream_plan", "mi_debug_set_trace_ranges", "mi_set_trace_ranges",
     "mi_prover_create", "mi_prover_destroy", "mi_prover_in_flight", "mi_prover_ctx", "mi_prover_last_error",
     "mi_prover_submit", "mi_prover_submit_dev", "mi_prover_wait", "mi_prover_commit", "mi_prover_submit_bsb22", "mi_prover_trim", "mi_ctx_trim",
     "mi_group_create", "mi_group_unique_id", "mi_group_create_rank", "mi_group_create_rank_ex", "mi_group_rank", "mi_group_destroy", "mi_group_world", "mi_group_local", "mi_group_ctx",
@@ -74,6 +74,12 @@ PHASE2_CHECK_EXPORTS = ["mi_srs_check_powers", "mi_srs_check_get_stats", "mi_pha
                         "mi_phase2_records_verify", "mi_phase2_verify_adopt", "mi_phase2_verify_get_stats"]
 SRS_BAD_GENERATORS, SRS_BAD_TAU_G1, SRS_BAD_ALPHA_G1, SRS_BAD_BETA_G1, SRS_BAD_TAU_G2, SRS_BAD_BETA_G2 = 1, 2, 4, 8, 16, 32
 PHASE2_BAD_RECORD, PHASE2_BAD_DELTA, PHASE2_BAD_Z, PHASE2_BAD_K = 1, 2, 4, 8
+# include/mi355x_groth16_phase1.h (the powers-of-tau SRS itself: a phase-1 ceremony on the device and its handover to phase 2)
+PHASE1_EXPORTS = ["mi_phase1_init", "mi_phase1_from_srs", "mi_phase1_set_transcript_id", "mi_phase1_contribute", "mi_phase1_contribute_proved",
+                  "mi_phase1_records_verify", "mi_phase1_verify_adopt", "mi_phase1_check", "mi_phase1_get_info", "mi_phase1_export", "mi_phase1_free",
+                  "mi_phase1_get_stats", "mi_phase2_init_from_phase1"]
+PHASE1_BAD_RECORD, PHASE1_BAD_LINK = 64, 128
+PHASE1_RECORD_WORDS = 64   # a mi_phase1_record as uint64 words: tau1, alpha1, beta1 (8 each), commit[3] (24), response[3] (12), hash (4)
 PHASE2_RECORD_WORDS = 24   # a mi_phase2_record as uint64 words: delta1 (8), commit (8), response (4), hash (4 words = 32 bytes)
 
 
@@ -186,6 +192,16 @@ class Phase2Stats(C.Structure):
 class SrsCheckStats(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("upload_ms", "point_check_ms", "coeff_ms", "msm_g1_ms", "msm_g2_ms", "pairing_ms", "total_ms")] + [
         ("pad_", C.c_uint32), ("peak_bytes", C.c_uint64)]
+
+
+class Phase1Stats(C.Structure):
+    _fields_ = [("scalar_mul_ms", C.c_float * 4), ("affine_ms", C.c_float * 4), ("total_ms", C.c_float), ("window", C.c_uint32), ("chunk", C.c_uint32),
+                ("pad_", C.c_uint32), ("peak_bytes", C.c_uint64)]
+
+
+class Phase1Info(C.Structure):
+    _fields_ = [("log_n", C.c_uint32), ("pad_", C.c_uint32), ("n_records", C.c_uint64), ("chain", C.c_uint8 * 32), ("tau1", C.c_uint64 * 8),
+                ("alpha1", C.c_uint64 * 8), ("beta1", C.c_uint64 * 8)]
 
 
 class Phase2Claim(C.Structure):
@@ -913,6 +929,84 @@ class Context:
         self._ck(self.lib.mi_phase2_verify_adopt(self.h, st, C.byref(cl), _p(rec), C.c_size_t(rec.shape[0]), seed, C.byref(failed), C.byref(fb)))
         return int(failed.value), int(fb.value)
 
+    # ---- phase 1: the SRS itself (include/mi355x_groth16_phase1.h)
+    def phase1_init(self, log_n):
+        """mi_phase1_init -> the state's handle: every row the generator"""
+        h = C.c_void_p()
+        self._ck(self.lib.mi_phase1_init(self.h, C.c_uint32(log_n), C.byref(h)))
+        return h
+
+    def phase1_from_srs(self, srs: dict, n_domain, flags=0):
+        """mi_phase1_from_srs: the SRS rows (_srs_desc) taken in -> the state's handle"""
+        sd, keep = _srs_desc(srs); h = C.c_void_p()
+        self._ck(self.lib.mi_phase1_from_srs(self.h, C.byref(sd), C.c_uint64(n_domain), C.c_uint32(flags), C.byref(h)))
+        return h
+
+    def phase1_set_transcript_id(self, st, ident):
+        self._ck(self.lib.mi_phase1_set_transcript_id(self.h, st, ident))
+
+    def phase1_contribute(self, st, tau, alpha, beta):
+        """mi_phase1_contribute: tau, alpha, beta (4,) uint64 Montgomery (None passes a null pointer)"""
+        self._ck(self.lib.mi_phase1_contribute(self.h, st, *(None if v is None else _p(_u64(v)) for v in (tau, alpha, beta))))
+
+    def phase1_contribute_proved(self, st, tau, alpha, beta, nonce=None):
+        """mi_phase1_contribute_proved -> the record, PHASE1_RECORD_WORDS uint64; nonce: (3, 4) uint64 Montgomery, or None for the operating system's"""
+        rec = np.zeros(PHASE1_RECORD_WORDS, np.uint64)
+        nn = None if nonce is None else _u64(np.array(nonce, np.uint64).reshape(3, 4))
+        self._ck(self.lib.mi_phase1_contribute_proved(self.h, st, *(None if v is None else _p(_u64(v)) for v in (tau, alpha, beta)), _p(nn), _p(rec)))
+        return rec
+
+    def phase1_verify_adopt(self, st, claim: dict, records, seed=None):
+        """mi_phase1_verify_adopt: claim as _srs_desc takes it -> (mask, first_bad_record); records: (m, PHASE1_RECORD_WORDS) uint64"""
+        sd, keep = _srs_desc(claim); rec = _u64(records).reshape(-1, PHASE1_RECORD_WORDS)
+        failed = C.c_uint32(0xFFFFFFFF); fb = C.c_uint64(0)
+        self._ck(self.lib.mi_phase1_verify_adopt(self.h, st, C.byref(sd), _p(rec) if rec.shape[0] else None, C.c_size_t(rec.shape[0]), seed, C.byref(failed), C.byref(fb)))
+        return int(failed.value), int(fb.value)
+
+    def phase1_check(self, st, seed=None):
+        """mi_phase1_check -> the SRS_BAD_* mask of the state's own rows"""
+        failed = C.c_uint32(0xFFFFFFFF)
+        self._ck(self.lib.mi_phase1_check(self.h, st, seed, C.byref(failed)))
+        return int(failed.value)
+
+    def phase1_info(self, st):
+        """mi_phase1_get_info -> log_n, n_records, chain (32 bytes), tau1 / alpha1 / beta1 (8,) uint64"""
+        i = Phase1Info(); self._ck(self.lib.mi_phase1_get_info(self.h, st, C.byref(i)))
+        return {"log_n": int(i.log_n), "n_records": int(i.n_records), "chain": bytes(i.chain),
+                **{n: np.array(getattr(i, n), dtype=np.uint64) for n in ("tau1", "alpha1", "beta1")}}
+
+    def phase1_export(self, st, caps=None):
+        """mi_phase1_export -> the rows as the dict _srs_desc takes; caps: four capacities in place of the rows' own sizes (for the refusals)"""
+        n = (C.c_uint64 * 4)()
+        self._ck(self.lib.mi_phase1_export(self.h, st, None, None, None, None, None, *(C.c_uint64(0),) * 4, n))
+        cnt = [int(v) for v in n]
+        rows = [np.zeros((c, w), np.uint64) for c, w in zip(cnt, (8, 8, 8, 16))]
+        b2 = np.zeros(16, np.uint64)
+        self._ck(self.lib.mi_phase1_export(self.h, st, *(_p(r) for r in rows), _p(b2), *(C.c_uint64(c) for c in (caps or cnt)), n))
+        return {"tau_g1": rows[0], "alpha_tau_g1": rows[1], "beta_tau_g1": rows[2], "tau_g2": rows[3], "beta_g2": b2}
+
+    def phase1_free(self, st):
+        self._ck(self.lib.mi_phase1_free(self.h, st))
+
+    def phase1_stats(self):
+        st = Phase1Stats(); self._ck(self.lib.mi_phase1_get_stats(self.h, C.byref(st)))
+        return {"scalar_mul_ms": list(st.scalar_mul_ms), "affine_ms": list(st.affine_ms), "total_ms": st.total_ms, "window": st.window, "chunk": st.chunk,
+                "peak_bytes": st.peak_bytes}
+
+    def phase2_init_from_phase1(self, r1cs: dict, p1, sigma=(), flags=0):
+        """mi_phase2_init_from_phase1: phase2_init with the SRS rows read from a phase-1 state's device arrays"""
+        d, keep = _r1cs_desc(r1cs); h = C.c_void_p()
+        sg = _u64(np.array(sigma, np.uint64).reshape(-1, 4)) if len(sigma) else None
+        self._ck(self.lib.mi_phase2_init_from_phase1(self.h, C.byref(d), p1, _p(sg), C.c_uint32(flags), C.byref(h)))
+        return h
+
+    def debug_scale_powers(self, pts, t, c, k0=0, g2=False):
+        """mi_debug_scale_powers_dev: out[i] = [c t^(k0 + i)] pts[i] by the driver a phase-1 contribution runs -> (n, 8) or (n, 16) uint64"""
+        p = _u64(pts).reshape(-1, 16 if g2 else 8); out = np.zeros_like(p)
+        self._ck(self.lib.mi_debug_scale_powers_dev(self.h, C.c_int32(1 if g2 else 0), _p(p) if p.shape[0] else None, C.c_size_t(p.shape[0]), _p(_u64(t)), _p(_u64(c)),
+                                                    C.c_uint64(k0), _p(out) if p.shape[0] else None))
+        return out
+
     def keyfile_stats(self):
         st = KeyfileStats(); self._ck(self.lib.mi_keyfile_get_stats(self.h, C.byref(st)))
         return {n: getattr(st, n) for n, _ in KeyfileStats._fields_}
@@ -1615,6 +1709,17 @@ def g1_compress(p):
 
 def g2_compress(p):
     buf = np.zeros(64, np.uint8); load().mi_g2_compress(_p(_u64(p)), _p(buf)); return bytes(buf)
+
+
+def phase1_records_verify(start, start_hash, first_index, records):
+    """mi_phase1_records_verify (host only) -> the index of the first record that does not hold, len(records) when all hold; start: (3, 8)
+    uint64 = tau_g1[1], alpha_tau_g1[0], beta_tau_g1[0] before the first record"""
+    rec = _u64(records).reshape(-1, PHASE1_RECORD_WORDS); fb = C.c_uint64()
+    rc = load().mi_phase1_records_verify(_p(_u64(np.array(start, np.uint64).reshape(3, 8))), start_hash, C.c_uint64(first_index), _p(rec) if rec.shape[0] else None,
+                                         C.c_size_t(rec.shape[0]), C.byref(fb))
+    if rc != 0:
+        raise MiError(f"rc={rc}: mi_phase1_records_verify")
+    return int(fb.value)
 
 
 def phase2_records_verify(delta1_start, start_hash, first_index, records):

@@ -1075,6 +1075,8 @@ int32_t mi_debug_set_knob(mi_ctx *ctx, const char *name, int64_t value) {
     else if (is("reduce_seg") && value >= 0 && value <= 256) k->seg = (u32)value;                    // buckets per bucket-reduce thread (0 = 8)
     else if (is("hold_accum") && (value == 0 || value == 1)) ctx->hold_accum = (uint32_t)value;   // = mi_debug_set_prove_schedule
     else if (is("finisher_min_level") && value >= 0 && value <= 16) k->finisher_min_level = (u32)value;
+    else if (is("scale_powers_window") && (value == 0 || (value >= 2 && value <= 5))) ctx->scale_powers_window = (uint32_t)value;   // phase1.hip
+    else if (is("scale_powers_chunk") && (value == 0 || (value >= 64 && value <= (1 << 24)))) ctx->scale_powers_chunk = (uint32_t)value;
     else if (mi_ntt_set_knob(ctx, name, value)) return MI_OK;
     else MI_FAIL(ctx, MI_EINVAL, std::string("mi_debug_set_knob: unknown knob or value out of range: ") + name);
     return MI_OK;

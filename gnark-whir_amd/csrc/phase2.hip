@@ -231,7 +231,7 @@ void free_state(mi_phase2 *s) {
     delete s;
 }
 
-int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, const R1csShape &sh, const std::vector<Fr> &sigma, uint32_t flags, mi_phase2 *S) {
+int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, bool on_device, const R1csShape &sh, const std::vector<Fr> &sigma, uint32_t flags, mi_phase2 *S) {
     hipStream_t st = ctx->stream;
     mi_phase2_stats &stats = ctx->phase2_stats;
     const u64 N = sh.N, nw = sh.nb_wires;
@@ -247,11 +247,15 @@ int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, con
     MI_TRY(ar.alloc(ctx, &Be, (size_t)N));
     MI_TRY(ar.alloc(ctx, &T2, (size_t)N));
     MI_TRY(ar.alloc(ctx, &b2, (size_t)1));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(T1, srs->tau_g1, 2 * N * 64, hipMemcpyHostToDevice, st));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(Al, srs->alpha_tau_g1, N * 64, hipMemcpyHostToDevice, st));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(Be, srs->beta_tau_g1, N * 64, hipMemcpyHostToDevice, st));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(T2, srs->tau_g2, N * 128, hipMemcpyHostToDevice, st));
+    const hipMemcpyKind up = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;   // the rows are transformed in place: copies either way
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(T1, srs->tau_g1, 2 * N * 64, up, st));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(Al, srs->alpha_tau_g1, N * 64, up, st));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(Be, srs->beta_tau_g1, N * 64, up, st));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(T2, srs->tau_g2, N * 128, up, st));
     MI_CHECK_HIP(ctx, hipMemcpyAsync(b2, &srs->beta_g2, 128, hipMemcpyHostToDevice, st));
+    // the points the SRS hands over as they are
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(&S->alpha1, Al, 64, hipMemcpyDeviceToHost, st));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(&S->beta1, Be, 64, hipMemcpyDeviceToHost, st));
     MI_TRY(laps.lap(ctx, stats.upload_ms));
     {
         const Phase2Row rows[5] = {{"tau_g1", false, T1, 2 * N}, {"alpha_tau_g1", false, Al, N}, {"beta_tau_g1", false, Be, N}, {"tau_g2", true, T2, N}, {"beta_g2", true, b2, 1}};
@@ -408,9 +412,7 @@ int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, con
         MI_TRY(scale_array<Fp>(ctx, (G1Aff *)pd.bes, pd.n, pd.sigma));
     }
     MI_TRY(laps.lap(ctx, stats.affine_ms));
-    // the points the SRS hands over as they are, and the generators where gamma = delta = 1
-    std::memcpy(&S->alpha1, &srs->alpha_tau_g1[0], 64);
-    std::memcpy(&S->beta1, &srs->beta_tau_g1[0], 64);
+    // beta_g2 as it is, and the generators where gamma = delta = 1
     std::memcpy(&S->beta2, &srs->beta_g2, 128);
     S->delta1 = g1_generator();
     S->gamma2 = S->delta2 = g2_generator();
@@ -486,6 +488,12 @@ int32_t mi_phase2_get_stats(mi_ctx *ctx, mi_phase2_stats *out) {
 }
 
 int32_t mi_phase2_init(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_srs_desc *srs, const mi_fr *sigma, uint32_t flags, mi_phase2 **out) {
+    return mi_phase2_init_rows(ctx, r1cs, srs, false, sigma, flags, out);
+}
+
+}  // extern "C"
+
+int32_t mi_phase2_init_rows(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_srs_desc *srs, bool on_device, const mi_fr *sigma, uint32_t flags, mi_phase2 **out) {
     if (!ctx) return MI_EINVAL;
     if (!out) MI_FAIL(ctx, MI_EINVAL, "phase2: out is null");
     *out = nullptr;
@@ -507,7 +515,7 @@ int32_t mi_phase2_init(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_srs_desc 
     if (!S) return MI_ENOMEM;
     S->log_n = sh.log_n; S->N = sh.N; S->nb_public = sh.nb_public; S->nb_wires = sh.nb_wires; S->n_commitments = sh.n_commitments;
     S->removed = sh.removed;
-    const int32_t rc = init_run(ctx, r1cs, srs, sh, sg, flags, S);
+    const int32_t rc = init_run(ctx, r1cs, srs, on_device, sh, sg, flags, S);
     if (rc != MI_OK) {   // the arena has freed everything, the state's arrays included (they are disowned last)
         (void)hipStreamSynchronize(ctx->stream);
         delete S;
@@ -517,6 +525,8 @@ int32_t mi_phase2_init(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_srs_desc 
     *out = S;
     return MI_OK;
 }
+
+extern "C" {
 
 int32_t mi_phase2_contribute(mi_ctx *ctx, mi_phase2 *S, const mi_fr *delta, const mi_fr *sigma_factor) {
     if (!ctx) return MI_EINVAL;

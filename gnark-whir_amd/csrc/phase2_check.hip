@@ -133,9 +133,10 @@ int32_t judge(mi_ctx *ctx, Arena &ar, const Relations &rel, std::vector<uint8_t>
 }
 
 // ---------------------------------------------------------------------------------------------------- the SRS
-int32_t srs_check_run(mi_ctx *ctx, const mi_srs_desc *srs, u64 N, const uint8_t *seed, uint32_t flags, uint32_t *failed) {
+// srs: HOST rows, which go up and are checked point by point here, or (on_device) rows that are on the device and have passed those
+// checks already -- beta_g2 then still sits in the descriptor, on the host
+int32_t srs_check_run(mi_ctx *ctx, const mi_srs_desc *srs, bool on_device, u64 N, const uint8_t *seed, uint32_t flags, mi_srs_check_stats &stats, uint32_t *failed) {
     hipStream_t st = ctx->stream;
-    mi_srs_check_stats &stats = ctx->srs_check_stats;
     Arena ar;
     Clock ck;
     Fr *r = nullptr;
@@ -144,18 +145,20 @@ int32_t srs_check_run(mi_ctx *ctx, const mi_srs_desc *srs, u64 N, const uint8_t 
     MI_TRY(sync_lap(ctx, ck, stats.coeff_ms));
     // one G1 row: up, checked, summed over [1, 1 + n_rel) and [0, n_rel) with the same scalars, (for tau_g1) over [0, N) too, released
     auto g1_row = [&](const char *name, const mi_g1_affine *host, u64 n, u64 n_rel, G1Aff *hi, G1Aff *lo, G1Aff *first_n) -> int32_t {
-        G1Aff *row = nullptr;
-        MI_TRY(ar.alloc(ctx, &row, (size_t)n));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(row, host, n * sizeof(G1Aff), hipMemcpyHostToDevice, st));
-        MI_TRY(sync_lap(ctx, ck, stats.upload_ms));
-        const Phase2Row pr{name, false, row, n};
-        MI_TRY(mi_phase2_check_points(ctx, ar, &pr, 1, flags));
-        ck.lap(stats.point_check_ms);
+        G1Aff *row = (G1Aff *)host;
+        if (!on_device) {
+            MI_TRY(ar.alloc(ctx, &row, (size_t)n));
+            MI_CHECK_HIP(ctx, hipMemcpyAsync(row, host, n * sizeof(G1Aff), hipMemcpyHostToDevice, st));
+            MI_TRY(sync_lap(ctx, ck, stats.upload_ms));
+            const Phase2Row pr{name, false, row, n};
+            MI_TRY(mi_phase2_check_points(ctx, ar, &pr, 1, flags));
+            ck.lap(stats.point_check_ms);
+        }
         MI_TRY(msm_g1(ctx, row + 1, r, n_rel, hi));
         MI_TRY(msm_g1(ctx, row, r, n_rel, lo));
         if (first_n) MI_TRY(msm_g1(ctx, row, r, N, first_n));
         ck.lap(stats.msm_g1_ms);
-        ar.release(row);
+        if (!on_device) ar.release(row);
         return MI_OK;
     };
     G1Aff t_hi, t_lo, t_n, a_hi, a_lo, b_hi, b_lo;
@@ -163,7 +166,10 @@ int32_t srs_check_run(mi_ctx *ctx, const mi_srs_desc *srs, u64 N, const uint8_t 
     MI_TRY(g1_row("alpha_tau_g1", srs->alpha_tau_g1, N, N - 1, &a_hi, &a_lo, nullptr));
     MI_TRY(g1_row("beta_tau_g1", srs->beta_tau_g1, N, N - 1, &b_hi, &b_lo, nullptr));
     G2Aff t2_sum;
-    {
+    if (on_device) {
+        MI_TRY(msm_g2(ctx, (const G2Aff *)srs->tau_g2, r, N, &t2_sum));
+        ck.lap(stats.msm_g2_ms);
+    } else {
         G2Aff *row = nullptr, *b2 = nullptr;
         MI_TRY(ar.alloc(ctx, &row, (size_t)N));
         MI_TRY(ar.alloc(ctx, &b2, (size_t)1));
@@ -179,8 +185,18 @@ int32_t srs_check_run(mi_ctx *ctx, const mi_srs_desc *srs, u64 N, const uint8_t 
     }
     ar.release(r);
     // every point below has passed its checks
-    const G1Aff g1 = g1_generator(), tau1_0 = g1_of(srs->tau_g1[0]), beta1 = g1_of(srs->beta_tau_g1[0]);
-    const G2Aff g2 = g2_generator(), tau2_0 = g2_of(srs->tau_g2[0]), tau2 = g2_of(srs->tau_g2[1]), beta2 = g2_of(srs->beta_g2);
+    mi_g1_affine first1[2];   // tau_g1[0], beta_tau_g1[0]
+    mi_g2_affine first2[2];   // tau_g2[0], tau_g2[1]
+    if (on_device) {
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(&first1[0], srs->tau_g1, sizeof(G1Aff), hipMemcpyDeviceToHost, st));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(&first1[1], srs->beta_tau_g1, sizeof(G1Aff), hipMemcpyDeviceToHost, st));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(first2, srs->tau_g2, 2 * sizeof(G2Aff), hipMemcpyDeviceToHost, st));
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+    } else {
+        first1[0] = srs->tau_g1[0]; first1[1] = srs->beta_tau_g1[0]; first2[0] = srs->tau_g2[0]; first2[1] = srs->tau_g2[1];
+    }
+    const G1Aff g1 = g1_generator(), tau1_0 = g1_of(first1[0]), beta1 = g1_of(first1[1]);
+    const G2Aff g2 = g2_generator(), tau2_0 = g2_of(first2[0]), tau2 = g2_of(first2[1]), beta2 = g2_of(srs->beta_g2);
     Relations rel;
     rel.add(t_hi, g2, t_lo, tau2);     // MI_SRS_BAD_TAU_G1
     rel.add(a_hi, g2, a_lo, tau2);     // MI_SRS_BAD_ALPHA_G1
@@ -252,6 +268,18 @@ int32_t verify_run(mi_ctx *ctx, mi_phase2 *S, const mi_phase2_claim *claim, cons
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------- shared with phase1.hip
+int32_t mi_srs_check_rows_dev(mi_ctx *ctx, const char *who, const mi_srs_desc *rows_dev, u64 N, const uint8_t *seed, mi_srs_check_stats &stats, uint32_t *failed) {
+    uint8_t own_seed[32];
+    MI_TRY(seed_or_random(ctx, who, seed, own_seed));
+    const double t0 = now_ms();
+    stats = mi_srs_check_stats{};
+    const int32_t rc = srs_check_run(ctx, rows_dev, true, N, seed, 0, stats, failed);
+    if (rc != MI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    stats.total_ms = (float)(now_ms() - t0);
+    return MI_OK;
+}
+
 extern "C" {
 
 int32_t mi_debug_ceremony_coeffs_dev(mi_ctx *ctx, const uint8_t seed[32], size_t n, mi_fr *out_dev) {
@@ -281,7 +309,7 @@ int32_t mi_srs_check_powers(mi_ctx *ctx, const mi_srs_desc *srs, uint64_t n_doma
     MI_TRY(seed_or_random(ctx, "srs check", seed, own_seed));
     const double t0 = now_ms();
     ctx->srs_check_stats = mi_srs_check_stats{};
-    const int32_t rc = srs_check_run(ctx, srs, n_domain, seed, flags, failed);
+    const int32_t rc = srs_check_run(ctx, srs, false, n_domain, seed, flags, ctx->srs_check_stats, failed);
     if (rc != MI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }   // the arena has freed everything
     ctx->srs_check_stats.total_ms = (float)(now_ms() - t0);
     return MI_OK;

@@ -33,3 +33,10 @@ int32_t mi_phase2_srs_host_check(mi_ctx *ctx, const mi_srs_desc *srs, u64 N);
 // is idle on return.  At most 8 rows.
 struct Phase2Row { const char *name; bool g2; const void *pts; u64 n; };
 int32_t mi_phase2_check_points(mi_ctx *ctx, Arena &ar, const Phase2Row *rows, int n_rows, uint32_t flags);
+// mi_srs_check_powers' relations (phase2_check.hip) over rows that are ON THE DEVICE and have passed mi_phase2_check_points: the four row
+// pointers of rows_dev are device pointers to 2 N / N points, beta_g2 sits in the descriptor.  seed may be null (getrandom; MI_ENODEV
+// names `who`).  No row is copied; stats takes the times.
+int32_t mi_srs_check_rows_dev(mi_ctx *ctx, const char *who, const mi_srs_desc *rows_dev, u64 N, const uint8_t *seed, mi_srs_check_stats &stats, uint32_t *failed);
+// mi_phase2_init, or with on_device the same reading the SRS rows from device arrays (phase1.hip's handover: rows as above, the counts
+// the arrays' own, so that a circuit they are too short for is refused as a short row is)
+int32_t mi_phase2_init_rows(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_srs_desc *rows, bool on_device, const mi_fr *sigma, uint32_t flags, mi_phase2 **out);

@@ -13,7 +13,8 @@
 // that the rows are consistent powers; call it before InitPhase2), ContributeProved (a contribution with its Schnorr record),
 // VerifyRecords and VerifyAdopt (a contributor's claimed state checked against one's own, then taken over).  NOT here, and not in the
 // library: gnark's mpcsetup file formats (their layout is not available to this project: the SRS and the records cross this interface
-// as slices, in this project's own layout), a record for sigma, a phase-1 transcript.  The walk over gnark's constraints below
+// as slices, in this project's own layout), a record for sigma.  The SRS itself comes from a ceremony of its own: phase1.go.  The walk
+// over gnark's constraints below
 // (GetR1Cs, Term.CoeffID / WireID) is written from memory of gnark v0.11 and has never been compiled.
 package mi355x
 
@@ -46,8 +47,9 @@ type SRS struct {
 
 // Phase2 is the device-resident state of a ceremony for one circuit.
 type Phase2 struct {
-	ctx *C.mi_ctx
-	st  *C.mi_phase2
+	ctx      *C.mi_ctx
+	st       *C.mi_phase2
+	borrowed bool // the context is a Phase1's (Phase1.InitPhase2): Close leaves it alone
 }
 
 // csr is one matrix of the R1CS by rows: mi_r1cs_matrix.
@@ -85,6 +87,19 @@ func InitPhase2(r1cs *cs.R1CS, srs *SRS, sigma []fr.Element, device int) (*Phase
 	if rc := C.mi_init(C.int(device), &p.ctx); rc != C.MI_OK {
 		return nil, fmt.Errorf("mi355x: mi_init rc=%d (no gfx950 device?)", int(rc))
 	}
+	err := initPhase2(p, r1cs, sigma, func(pin *runtime.Pinner, d *C.mi_r1cs_desc, sg *C.mi_fr) C.int32_t {
+		s := srsDesc(pin, srs)
+		return C.mi_phase2_init(p.ctx, d, &s, sg, 0, &p.st)
+	})
+	if err != nil {
+		C.mi_shutdown(p.ctx)
+		return nil, err
+	}
+	return p, nil
+}
+
+// initPhase2 lays the constraint system out as mi_r1cs_desc and hands it to call, which runs mi_phase2_init or its phase-1 form on p.ctx.
+func initPhase2(p *Phase2, r1cs *cs.R1CS, sigma []fr.Element, call func(pin *runtime.Pinner, d *C.mi_r1cs_desc, sg *C.mi_fr) C.int32_t) error {
 	var pin runtime.Pinner
 	defer pin.Unpin()
 	a, b, c := csrOf(r1cs)
@@ -110,8 +125,7 @@ func InitPhase2(r1cs *cs.R1CS, srs *SRS, sigma []fr.Element, device int) (*Phase
 	committed := info.GetPrivateCommitted()
 	wires := info.CommitmentIndexes()
 	if len(sigma) != len(committed) {
-		C.mi_shutdown(p.ctx)
-		return nil, fmt.Errorf("mi355x: %d sigma values for %d commitments", len(sigma), len(committed))
+		return fmt.Errorf("mi355x: %d sigma values for %d commitments", len(sigma), len(committed))
 	}
 	if n := len(committed); n > 0 {
 		lists := make([][]uint32, n)
@@ -138,22 +152,12 @@ func InitPhase2(r1cs *cs.R1CS, srs *SRS, sigma []fr.Element, device int) (*Phase
 		d.n_committed = (*C.uint64_t)(unsafe.Pointer(&counts[0]))
 		d.commitment_wire = (*C.uint32_t)(unsafe.Pointer(&cw[0]))
 	}
-	var s C.mi_srs_desc
-	s.tau_g1, s.n_tau_g1 = g1(&pin, srs.TauG1), C.uint64_t(len(srs.TauG1))
-	s.alpha_tau_g1, s.n_alpha_tau_g1 = g1(&pin, srs.AlphaTauG1), C.uint64_t(len(srs.AlphaTauG1))
-	s.beta_tau_g1, s.n_beta_tau_g1 = g1(&pin, srs.BetaTauG1), C.uint64_t(len(srs.BetaTauG1))
-	s.tau_g2, s.n_tau_g2 = g2(&pin, srs.TauG2), C.uint64_t(len(srs.TauG2))
-	s.beta_g2 = *(*C.mi_g2_affine)(unsafe.Pointer(&srs.BetaG2))
 	var sg *C.mi_fr
 	if len(sigma) > 0 {
 		pin.Pin(&sigma[0])
 		sg = (*C.mi_fr)(unsafe.Pointer(&sigma[0]))
 	}
-	if err := status(p.ctx, C.mi_phase2_init(p.ctx, &d, &s, sg, 0, &p.st)); err != nil {
-		C.mi_shutdown(p.ctx)
-		return nil, err
-	}
-	return p, nil
+	return status(p.ctx, call(&pin, &d, sg))
 }
 
 // Contribute re-randomises delta (and, per commitment, sigma: nil leaves every sigma as it is).  Zero is refused.
@@ -289,8 +293,8 @@ func (p *Phase2) Close() {
 		C.mi_phase2_free(p.ctx, p.st)
 		p.st = nil
 	}
-	if p.ctx != nil {
+	if p.ctx != nil && !p.borrowed {
 		C.mi_shutdown(p.ctx)
-		p.ctx = nil
 	}
+	p.ctx = nil
 }

@@ -199,7 +199,10 @@ int32_t mi_debug_set_msm_precompute_batched(mi_ctx *ctx, uint32_t on);
  *                            are where every ordinary bucket ends; a finisher over 2^19 buckets of 13 partial sums each measured -5 %)
  *   "item_l1", "item_l2", "reduce_seg"   = the L1, L2, seg of mi_debug_set_msm_plan, one at a time (a flat sort keeps its own item size: "flat_item_l1")
  *   "hold_accum" 0 | 1       = mi_debug_set_prove_schedule
- *   "ntt_lds_floor_kb" 0..160   LDS every NTT pass workgroup requests at least (caps the workgroups per CU) */
+ *   "ntt_lds_floor_kb" 0..160   LDS every NTT pass workgroup requests at least (caps the workgroups per CU)
+ *   "scale_powers_window" 0 | 2..5   phase 1's scalar multiplications (csrc/scale_powers.cuh): 2..5 = the fixed-window ladder of that width
+ *                            (default 5, measured fastest: profiles/phase1.txt); 0 = the bit-by-bit xyzz_scale of the point NTT on the same scalars, the yardstick.  Same points
+ *   "scale_powers_chunk" 0 | 64..2^24   lanes per chunk of that driver, which sizes its table workspace (0 = the default, 2^18) */
 int32_t mi_debug_set_knob(mi_ctx *ctx, const char *name, int64_t value);
 /* Counters the tests read to prove that an optional path really ran: "z_count_fused_launches" = computeH last launches of this context that
  * carried the Z MSM's digit count (knob "z_count_fused"); "dense_item_sorts" = bucket accumulations whose level-1 item size the dense-sort rule
@@ -219,6 +222,10 @@ int32_t mi_debug_inject_hip_failure(int32_t nth);
 /* The coefficients of the ceremony checks (mi355x_groth16_phase2_check.h) by the kernel those checks run, enqueued on the context's
  * stream: out_dev[k] = r_k as a Montgomery mi_fr, k < n <= 2^27; seed: 32 HOST bytes. */
 int32_t mi_debug_ceremony_coeffs_dev(mi_ctx *ctx, const uint8_t seed[32], size_t n, mi_fr *out_dev);
+/* The scalar multiplication of a phase-1 contribution (mi355x_groth16_phase1.h) by exactly the driver a contribution runs, for any n up to
+ * 2^28, not only powers of two: out_host[i] = [c t^(k0 + i)] pts_host[i], affine points of G1 (g2 = 0) or G2 (g2 != 0), (0, 0) = infinity in
+ * and out; t, c Montgomery and below r.  The knobs of mi_debug_set_knob choose what runs; mi_phase1_get_stats then tells row 0's times. */
+int32_t mi_debug_scale_powers_dev(mi_ctx *ctx, int32_t g2, const void *pts_host, size_t n, const mi_fr *t, const mi_fr *c, uint64_t k0, void *out_host);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 /* mi355x_groth16_phase2.h -- the circuit's keys from a powers-of-tau SRS, on the device (BN254): gnark's mpcsetup phase 2.
  *
  * mi_groth16_setup needs tau, alpha, beta, gamma, delta in the clear: whoever ran it can forge proofs.  This header is the other way a
- * key comes to be: nobody knows tau, alpha, beta (a public SRS holds their powers as points), the circuit's key is DERIVED from the SRS
+ * key comes to be: nobody knows tau, alpha, beta (a public SRS holds their powers as points; mi355x_groth16_phase1.h makes one by a
+ * ceremony of its own and hands its rows over on the device: mi_phase2_init_from_phase1), the circuit's key is DERIVED from the SRS
  * with gamma = 1 and delta = 1, and contributors then re-randomise delta one after the other.  It replaces
  *     mpcsetup.InitPhase2(r1cs, &srs) / (*Phase2).Contribute() / ExtractKeys
  * All of it is Setup's arithmetic "in the exponent" (csrc/phase2.hip): the Lagrange basis is an inverse NTT over curve points

@@ -29,8 +29,10 @@
  * NOT COVERED:
  *   - sigma / BasisExpSigma: mi_phase2_contribute_proved leaves them alone and mi_phase2_verify_adopt takes none from outside (the
  *     adopting state's stay its own), so the re-randomisation of the commitment keys has no proof of knowledge and no chain;
- *   - gnark's Phase1 / Phase2 file formats;
- *   - a phase-1 transcript: mi_srs_check_powers says that the rows ARE powers of one (tau, alpha, beta), not who contributed to them.
+ *   - gnark's Phase1 / Phase2 file formats.
+ * mi_srs_check_powers says that the rows ARE powers of one (tau, alpha, beta), not who contributed to them: that is what a phase-1 transcript
+ * says, and mi355x_groth16_phase1.h makes and verifies one (its mi_phase1_verify_adopt and mi_phase1_check run the relations below over
+ * rows that are on the device already).
  */
 #ifndef MI355X_GROTH16_PHASE2_CHECK_H
 #define MI355X_GROTH16_PHASE2_CHECK_H
