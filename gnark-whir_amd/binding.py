@@ -79,6 +79,11 @@ PHASE1_EXPORTS = ["mi_phase1_init", "mi_phase1_from_srs", "mi_phase1_set_transcr
                   "mi_phase1_records_verify", "mi_phase1_verify_adopt", "mi_phase1_check", "mi_phase1_get_info", "mi_phase1_export", "mi_phase1_free",
                   "mi_phase1_get_stats", "mi_phase2_init_from_phase1"]
 PHASE1_BAD_RECORD, PHASE1_BAD_LINK = 64, 128
+# include/mi355x_groth16_keyaudit.h (a key audited against its circuit and an SRS without deriving it again)
+KEYAUDIT_EXPORTS = ["mi_key_claim_from_streams", "mi_key_claim_from_phase2", "mi_key_claim_from_arrays", "mi_key_claim_free", "mi_key_audit",
+                    "mi_key_audit_get_stats"]
+(KEY_BAD_SMALL, KEY_BAD_A, KEY_BAD_B1, KEY_BAD_B2, KEY_BAD_K_PRIVATE, KEY_BAD_K_PUBLIC, KEY_BAD_BASIS, KEY_BAD_SIGMA,
+ KEY_BAD_Z) = 1, 2, 4, 8, 16, 32, 64, 128, 256
 PHASE1_RECORD_WORDS = 64   # a mi_phase1_record as uint64 words: tau1, alpha1, beta1 (8 each), commit[3] (24), response[3] (12), hash (4)
 PHASE2_RECORD_WORDS = 24   # a mi_phase2_record as uint64 words: delta1 (8), commit (8), response (4), hash (4 words = 32 bytes)
 
@@ -192,6 +197,16 @@ class Phase2Stats(C.Structure):
 class SrsCheckStats(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("upload_ms", "point_check_ms", "coeff_ms", "msm_g1_ms", "msm_g2_ms", "pairing_ms", "total_ms")] + [
         ("pad_", C.c_uint32), ("peak_bytes", C.c_uint64)]
+
+
+class KeyAuditStats(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("upload_ms", "point_check_ms", "coeff_ms", "sparse_ms", "transform_ms", "srs_msm_g1_ms", "srs_msm_g2_ms",
+                                         "key_msm_g1_ms", "key_msm_g2_ms", "pairing_ms", "total_ms")] + [("relations", C.c_uint32), ("peak_bytes", C.c_uint64)]
+
+
+class KeyAuditSums(C.Structure):
+    _fields_ = [(n, (C.c_uint64 * 8) * 2) for n in ("a", "b1", "k_private", "k_public", "basis", "z")] + [
+        ("b2", (C.c_uint64 * 16) * 2), ("sigma", ((C.c_uint64 * 8) * 2) * 16), ("n_sigma", C.c_uint32), ("valid", C.c_uint32)]
 
 
 class Phase1Stats(C.Structure):
@@ -930,6 +945,66 @@ class Context:
         return int(failed.value), int(fb.value)
 
     # ---- phase 1: the SRS itself (include/mi355x_groth16_phase1.h)
+    # ---- a key audited against its circuit and an SRS (include/mi355x_groth16_keyaudit.h)
+    def key_claim_from_streams(self, pk_blob: bytes, vk_blob: bytes, flags=0):
+        """mi_key_claim_from_streams: both of a key's streams, either encoding -> the claim's handle"""
+        pb = (C.c_uint8 * max(len(pk_blob), 1)).from_buffer_copy(pk_blob or b"\0"); vb = (C.c_uint8 * max(len(vk_blob), 1)).from_buffer_copy(vk_blob or b"\0")
+        h = C.c_void_p()
+        self._ck(self.lib.mi_key_claim_from_streams(self.h, pb, C.c_size_t(len(pk_blob)), vb, C.c_size_t(len(vk_blob)), C.c_uint32(flags), C.byref(h)))
+        return h
+
+    def key_claim_from_phase2(self, st):
+        """mi_key_claim_from_phase2: the claim borrows the state's arrays; free it before the state"""
+        h = C.c_void_p()
+        self._ck(self.lib.mi_key_claim_from_phase2(self.h, st, C.byref(h)))
+        return h
+
+    def key_claim_from_arrays(self, pk: dict, ped, vk: dict, vk_ped=None, n_vk=None):
+        """mi_key_claim_from_arrays: pk as pk_write_dev takes it (arrays = (device pointer, count)), ped = [(basis pointer, basis_exp_sigma
+        pointer, n)], vk = the dict setup() returns, vk_ped = (n_commitments, 2, 16) as pedersen_vk_make -> the claim's handle"""
+        d = PkDesc(); d.log_n, d.nb_wires, d.nb_public = int(pk.get("log_n", 0)), int(pk["nb_wires"]), int(pk.get("nb_public", 0))
+        for name in ("g1_a", "g1_b", "g1_k", "g1_z", "g2_b"):
+            ptr, cnt = pk[name]
+            setattr(d, name, int(ptr) if ptr else None); setattr(d, "n_" + name, int(cnt))
+        for name, k in (("alpha1", 8), ("beta1", 8), ("delta1", 8), ("beta2", 16), ("delta2", 16)):
+            setattr(d, name, (C.c_uint64 * k)(*[int(v) for v in _u64(pk[name]).reshape(-1)]))
+        ia = np.ascontiguousarray(pk["infinity_a"], dtype=np.uint8); ib = np.ascontiguousarray(pk["infinity_b"], dtype=np.uint8)
+        d.infinity_a, d.infinity_b = ia.ctypes.data, ib.ctypes.data
+        vd = VkDesc()
+        for n, w in (("alpha1", 8), ("beta2", 16), ("gamma2", 16), ("delta2", 16)):
+            setattr(vd, n, (C.c_uint64 * w)(*[int(v) for v in _u64(vk[n]).reshape(w)]))
+        k = _u64(vk["k"]).reshape(-1, 8)
+        vp = None if vk_ped is None or not len(vk_ped) else _u64(vk_ped).reshape(-1, 2, 16)
+        vd.k, vd.n_k = k.ctypes.data, int(k.shape[0] if n_vk is None else n_vk)
+        vd.n_commitments = 0 if vp is None else int(vp.shape[0])
+        vd.nb_public = max(int(vd.n_k) - int(vd.n_commitments), 0)
+        vd.ped = None if vp is None else vp.ctypes.data
+        h = C.c_void_p()
+        self._ck(self.lib.mi_key_claim_from_arrays(self.h, C.byref(d), _pedersen_arrays(list(ped)), C.c_uint32(len(ped)), C.byref(vd), C.byref(h)))
+        return h
+
+    def key_claim_free(self, claim):
+        self._ck(self.lib.mi_key_claim_free(self.h, claim))
+
+    def key_audit(self, r1cs: dict, claim, srs=None, p1=None, seed=None, flags=0):
+        """mi_key_audit -> the mask of relations that do not hold.  srs: the rows as a dict (_srs_desc), or p1: a phase-1 state's handle;
+        seed: 32 bytes, or None for the operating system's"""
+        d, keep = _r1cs_desc(r1cs); failed = C.c_uint32()
+        sd, keep2 = _srs_desc(srs) if srs is not None else (None, None)
+        self._ck(self.lib.mi_key_audit(self.h, C.byref(d), None if sd is None else C.byref(sd), p1, claim, seed, C.c_uint32(flags), C.byref(failed)))
+        return int(failed.value)
+
+    def key_audit_stats(self):
+        st = KeyAuditStats(); self._ck(self.lib.mi_key_audit_get_stats(self.h, C.byref(st)))
+        return {n: getattr(st, n) for n, _ in KeyAuditStats._fields_}
+
+    def key_audit_sums(self):
+        """mi_debug_key_audit_sums -> {relation: (2, 8) or (2, 16) uint64: the key's side, the SRS's side; "sigma": (n, 2, 8)}"""
+        s = KeyAuditSums(); self._ck(self.lib.mi_debug_key_audit_sums(self.h, C.byref(s)))
+        out = {n: np.array(getattr(s, n), dtype=np.uint64) for n in ("a", "b1", "k_private", "k_public", "basis", "z", "b2")}
+        out["sigma"] = np.array(s.sigma, dtype=np.uint64)[:int(s.n_sigma)]
+        return out
+
     def phase1_init(self, log_n):
         """mi_phase1_init -> the state's handle: every row the generator"""
         h = C.c_void_p()

@@ -18,6 +18,7 @@
 #include "../../include/mi355x_groth16_phase2.h"
 #include "../../include/mi355x_groth16_phase2_check.h"
 #include "../../include/mi355x_groth16_phase1.h"
+#include "../../include/mi355x_groth16_keyaudit.h"
 
 struct DevBuf {             // growable device scratch owned by the ctx (no hipMalloc in the hot path
     void *p = nullptr;      // after warm-up: buffers only ever grow)
@@ -133,6 +134,8 @@ struct mi_ctx {
     mi_setup_stats setup_stats{};   // last mi_groth16_setup[_exponents] call (setup.hip)
     mi_phase2_stats phase2_stats{};   // last mi_phase2_init call (phase2.hip)
     mi_srs_check_stats srs_check_stats{}, phase2_verify_stats{};   // last mi_srs_check_powers / mi_phase2_verify_adopt call (phase2_check.hip)
+    mi_key_audit_stats key_audit_stats{};   // last mi_key_audit call (keyaudit.hip)
+    mi_key_audit_sums key_audit_sums{};     // and the two sides of its relations (mi_debug_key_audit_sums)
     mi_phase1_stats phase1_stats{};   // last contribution of a phase-1 state / mi_debug_scale_powers_dev (phase1.hip)
     uint32_t scale_powers_window = 5, scale_powers_chunk = 0;   // knobs "scale_powers_window" (0 = the bit-by-bit yardstick, 2..5) and "scale_powers_chunk" (0 = the default)
     mi_keyfile_stats keyfile_stats{};   // last mi_pk_load_stream / mi_pk_write_dev call (keyfile.hip)

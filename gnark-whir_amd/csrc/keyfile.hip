@@ -10,8 +10,9 @@
 // The membership test is a kernel of its own rather than the tail of the G2 decoder: its 63-step scalar multiple holds a G2 point in
 // extended coordinates where the decoder holds its table of fifteen powers, and apart each is timed (mi_keyfile_stats).
 //
-// mi_pk_load_stream: inspect on the host, upload once, decode every section straight into the array the key will own, ONE wait for all
-// verdicts, then the handover of key_handover.h (mi_pk_load_range / mi_pedersen_pk_adopt).  mi_pk_write_dev: the sections are encoded
+// mi_pk_stream_decode (keyfile_internal.h): inspect on the host, upload once, decode every section straight into the array the key will
+// own, ONE wait for all verdicts.  mi_pk_load_stream: that, then the handover of key_handover.h (mi_pk_load_range / mi_pedersen_pk_adopt);
+// the key audit's claim (keyaudit.hip) stops before the handover.  mi_pk_write_dev: the sections are encoded
 // on the device and copied into place; the Domain block, the counts and the masks are host code and follow oracle/pk_raw.py.
 #include "prove_internal.h"
 #include "keyfile_ops.cuh"
@@ -175,6 +176,72 @@ int32_t mi_keyfile_encode_enqueue(mi_ctx *ctx, bool g2, uint8_t *dst_dev, const 
     return g2 ? encode_g2(ctx, dst_dev, src_dev, n, compressed) : encode_g1(ctx, dst_dev, src_dev, n, compressed);
 }
 
+int32_t mi_pk_stream_decode(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t flags, bool with_ped, PkStreamDecoded &out) {
+    if (flags & ~(MI_KEYFILE_NO_SUBGROUP_CHECK | MI_KEYFILE_SUBGROUP_BY_R)) MI_FAIL(ctx, MI_EINVAL, "keyfile: unknown flag");
+    mi_pk_raw_info &in = out.in;
+    uint32_t encoding = 0;
+    if (mi_pk_stream_inspect(buf, len, &in, &encoding) != MI_OK)
+        MI_FAIL(ctx, MI_EINVAL, "keyfile: the stream has neither the layout of ProvingKey.WriteRawTo nor of ProvingKey.WriteTo (include/mi355x_groth16_keyfile.h)");
+    const bool compressed = out.compressed = encoding == MI_KEYFILE_COMPRESSED;
+    // the domain's generator must be the one fft.NewDomain derives for this size (a cheap canary for a shifted layout)
+    if (mi_pk_stream_generator(buf) != fr_domain_generator(in.log_n)) MI_FAIL(ctx, MI_EINVAL, "keyfile: Domain.Generator is not fft.NewDomain's for this cardinality");
+    ctx->keyfile_stats = mi_keyfile_stats{};
+    out.t0 = now_ms();
+    out.inf_a = mi_pk_stream_mask(buf, in.off_infinity_a, in.nb_wires);
+    out.inf_b = mi_pk_stream_mask(buf, in.off_infinity_b, in.nb_wires);
+    const uint32_t n_ped = with_ped ? in.n_commitment_keys : 0;
+    out.ped.assign(2 * (size_t)n_ped, nullptr);
+    // every section, in stream order: where it lies, where it goes
+    struct Section { std::string name; bool g2; uint64_t off, n; void *dst; };
+    void *d_small1 = nullptr, *d_small2 = nullptr, *raw = nullptr;
+    auto body = [&]() -> int32_t {
+        std::vector<Section> sec = {{"G1.AlphaBetaDelta", false, in.off_alpha1, 3, nullptr}, {"G1.A", false, in.off_g1_a, in.n_g1_a, nullptr},
+                                    {"G1.B", false, in.off_g1_b, in.n_g1_b, nullptr},        {"G1.Z", false, in.off_g1_z, in.n_g1_z, nullptr},
+                                    {"G1.K", false, in.off_g1_k, in.n_g1_k, nullptr},        {"G2.BetaDelta", true, in.off_beta2, 2, nullptr},
+                                    {"G2.B", true, in.off_g2_b, in.n_g2_b, nullptr}};
+        for (uint32_t k = 0; k < n_ped; k++) {
+            sec.push_back({"Basis[" + std::to_string(k) + "]", false, in.off_basis[k], in.n_basis[k], nullptr});
+            sec.push_back({"BasisExpSigma[" + std::to_string(k) + "]", false, in.off_basis_exp_sigma[k], in.n_basis[k], nullptr});
+        }
+        void **const home[7] = {&d_small1, &out.arr[0], &out.arr[1], &out.arr[3], &out.arr[2], &d_small2, &out.arr[4]};
+        for (size_t s = 0; s < sec.size(); s++) {
+            void **h = s < 7 ? home[s] : &out.ped[s - 7];
+            const size_t bytes = (size_t)sec[s].n * (sec[s].g2 ? 128 : 64);
+            MI_CHECK_HIP(ctx, hipMalloc(h, bytes ? bytes : 64));
+            sec[s].dst = *h;
+        }
+        BadSlots bad;   // one word per section, then the membership tests of the two G2 sections
+        MI_TRY(bad.init(ctx, sec.size() + 2));
+        MI_CHECK_HIP(ctx, hipMalloc(&raw, len));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(raw, buf, len, hipMemcpyHostToDevice, ctx->stream));
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        out.t_up = now_ms();
+        for (size_t s = 0; s < sec.size(); s++) {
+            const uint8_t *src = (const uint8_t *)raw + sec[s].off;
+            MI_TRY(sec[s].g2 ? decode_g2(ctx, sec[s].dst, src, (size_t)sec[s].n, compressed, bad.dev + s) : decode_g1(ctx, sec[s].dst, src, (size_t)sec[s].n, compressed, bad.dev + s));
+        }
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        out.t_dec = now_ms();
+        if (!(flags & MI_KEYFILE_NO_SUBGROUP_CHECK))
+            for (int k = 0; k < 2; k++) MI_TRY(subgroup_g2(ctx, sec[5 + k].dst, (size_t)sec[5 + k].n, (flags & MI_KEYFILE_SUBGROUP_BY_R) != 0, bad.dev + sec.size() + k));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(out.small1, d_small1, 3 * sizeof(G1Aff), hipMemcpyDeviceToHost, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(out.small2, d_small2, 2 * sizeof(G2Aff), hipMemcpyDeviceToHost, ctx->stream));
+        MI_TRY(bad.fetch(ctx));
+        out.t_sub = now_ms();
+        (void)hipFree(raw); raw = nullptr;   // the stream has been read
+        for (size_t s = 0; s < sec.size(); s++)
+            if (bad.host[s] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "keyfile: " + sec[s].name + "[" + std::to_string(bad.host[s]) + "] is malformed: no point of the curve has this " + (compressed ? "compressed" : "raw") + " encoding");
+        for (int k = 0; k < 2; k++)
+            if (bad.host[sec.size() + k] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "keyfile: " + sec[5 + k].name + "[" + std::to_string(bad.host[sec.size() + k]) + "] is on the twist but not in the r-torsion");
+        ctx->keyfile_stats = mi_keyfile_stats{(float)(out.t_up - out.t0), (float)(out.t_dec - out.t_up), (float)(out.t_sub - out.t_dec), 0.f, (float)(out.t_sub - out.t0)};   // a loader adds its build
+        return MI_OK;
+    };
+    const int32_t rc = body();
+    (void)hipStreamSynchronize(ctx->stream);
+    for (void *a : {raw, d_small1, d_small2}) if (a) (void)hipFree(a);
+    return rc;
+}
+
 extern "C" {
 
 int32_t mi_g1_decompress_dev(mi_ctx *ctx, const uint8_t *bytes_dev, size_t n, mi_g1_affine *out_dev, uint64_t *first_bad) {
@@ -200,77 +267,29 @@ int32_t mi_pk_load_stream(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t 
     if (!ctx || !buf || !out) return MI_EINVAL;
     *out = nullptr;
     if (n_ped_out) *n_ped_out = 0;
-    if (flags & ~(MI_KEYFILE_NO_SUBGROUP_CHECK | MI_KEYFILE_SUBGROUP_BY_R)) MI_FAIL(ctx, MI_EINVAL, "keyfile: unknown flag");
-    mi_pk_raw_info in;
-    uint32_t encoding = 0;
-    if (mi_pk_stream_inspect(buf, len, &in, &encoding) != MI_OK)
-        MI_FAIL(ctx, MI_EINVAL, "keyfile: the stream has neither the layout of ProvingKey.WriteRawTo nor of ProvingKey.WriteTo (include/mi355x_groth16_keyfile.h)");
-    const bool compressed = encoding == MI_KEYFILE_COMPRESSED;
-    // the domain's generator must be the one fft.NewDomain derives for this size (a cheap canary for a shifted layout)
-    if (mi_pk_stream_generator(buf) != fr_domain_generator(in.log_n)) MI_FAIL(ctx, MI_EINVAL, "keyfile: Domain.Generator is not fft.NewDomain's for this cardinality");
-    ctx->keyfile_stats = mi_keyfile_stats{};
-    const double t0 = now_ms();
-    const std::vector<uint8_t> ia = mi_pk_stream_mask(buf, in.off_infinity_a, in.nb_wires), ib = mi_pk_stream_mask(buf, in.off_infinity_b, in.nb_wires);
-    const uint32_t n_ped = ped_out ? in.n_commitment_keys : 0;
-    // every section, in stream order: where it lies, where it goes
-    struct Section { std::string name; bool g2; uint64_t off, n; void *dst; };
-    KeyArrays ka(in.log_n, nb_public, in.nb_wires, ia.data(), ib.data(), committed_wires, n_committed);   // the arrays are this call's own until the key takes them
-    ka.n[KEY_G1_A] = in.n_g1_a; ka.n[KEY_G1_B] = in.n_g1_b; ka.n[KEY_G1_K] = in.n_g1_k; ka.n[KEY_G1_Z] = in.n_g1_z; ka.n[KEY_G2_B] = in.n_g2_b;
-    void *d_small1 = nullptr, *d_small2 = nullptr;
-    std::vector<void *> ped_arrays(2 * (size_t)n_ped, nullptr);
-    void *raw = nullptr;
+    PkStreamDecoded dec;
     KeyHandover hand(ctx, out, ped_out);
+    uint32_t n_ped = 0;
     auto body = [&]() -> int32_t {
-        std::vector<Section> sec = {{"G1.AlphaBetaDelta", false, in.off_alpha1, 3, nullptr}, {"G1.A", false, in.off_g1_a, in.n_g1_a, nullptr},
-                                    {"G1.B", false, in.off_g1_b, in.n_g1_b, nullptr},        {"G1.Z", false, in.off_g1_z, in.n_g1_z, nullptr},
-                                    {"G1.K", false, in.off_g1_k, in.n_g1_k, nullptr},        {"G2.BetaDelta", true, in.off_beta2, 2, nullptr},
-                                    {"G2.B", true, in.off_g2_b, in.n_g2_b, nullptr}};
-        for (uint32_t k = 0; k < n_ped; k++) {
-            sec.push_back({"Basis[" + std::to_string(k) + "]", false, in.off_basis[k], in.n_basis[k], nullptr});
-            sec.push_back({"BasisExpSigma[" + std::to_string(k) + "]", false, in.off_basis_exp_sigma[k], in.n_basis[k], nullptr});
-        }
-        void **const home[7] = {&d_small1, &ka.arr[KEY_G1_A], &ka.arr[KEY_G1_B], &ka.arr[KEY_G1_Z], &ka.arr[KEY_G1_K], &d_small2, &ka.arr[KEY_G2_B]};
-        for (size_t s = 0; s < sec.size(); s++) {
-            void **h = s < 7 ? home[s] : &ped_arrays[s - 7];
-            const size_t bytes = (size_t)sec[s].n * (sec[s].g2 ? 128 : 64);
-            MI_CHECK_HIP(ctx, hipMalloc(h, bytes ? bytes : 64));
-            sec[s].dst = *h;
-        }
-        BadSlots bad;   // one word per section, then the membership tests of the two G2 sections
-        MI_TRY(bad.init(ctx, sec.size() + 2));
-        MI_CHECK_HIP(ctx, hipMalloc(&raw, len));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(raw, buf, len, hipMemcpyHostToDevice, ctx->stream));
-        MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const double t_up = now_ms();
-        for (size_t s = 0; s < sec.size(); s++) {
-            const uint8_t *src = (const uint8_t *)raw + sec[s].off;
-            MI_TRY(sec[s].g2 ? decode_g2(ctx, sec[s].dst, src, (size_t)sec[s].n, compressed, bad.dev + s) : decode_g1(ctx, sec[s].dst, src, (size_t)sec[s].n, compressed, bad.dev + s));
-        }
-        MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const double t_dec = now_ms();
-        if (!(flags & MI_KEYFILE_NO_SUBGROUP_CHECK))
-            for (int k = 0; k < 2; k++) MI_TRY(subgroup_g2(ctx, sec[5 + k].dst, (size_t)sec[5 + k].n, (flags & MI_KEYFILE_SUBGROUP_BY_R) != 0, bad.dev + sec.size() + k));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(ka.small1, d_small1, 3 * sizeof(G1Aff), hipMemcpyDeviceToHost, ctx->stream));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(ka.small2, d_small2, 2 * sizeof(G2Aff), hipMemcpyDeviceToHost, ctx->stream));
-        MI_TRY(bad.fetch(ctx));
-        const double t_sub = now_ms();
-        (void)hipFree(raw); raw = nullptr;   // the stream has been read
-        for (size_t s = 0; s < sec.size(); s++)
-            if (bad.host[s] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "keyfile: " + sec[s].name + "[" + std::to_string(bad.host[s]) + "] is malformed: no point of the curve has this " + (compressed ? "compressed" : "raw") + " encoding");
-        for (int k = 0; k < 2; k++)
-            if (bad.host[sec.size() + k] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "keyfile: " + sec[5 + k].name + "[" + std::to_string(bad.host[sec.size() + k]) + "] is on the twist but not in the r-torsion");
-        MI_TRY(hand.adopt_key(ka, nullptr));
-        for (uint32_t k = 0; k < n_ped; k++) MI_TRY(hand.adopt_pedersen(&ped_arrays[2 * k], &ped_arrays[2 * k + 1], (size_t)in.n_basis[k], nullptr));
+        MI_TRY(mi_pk_stream_decode(ctx, buf, len, flags, ped_out != nullptr, dec));
+        const mi_pk_raw_info &in = dec.in;
+        n_ped = (uint32_t)(dec.ped.size() / 2);
+        KeyArrays ka(in.log_n, nb_public, in.nb_wires, dec.inf_a.data(), dec.inf_b.data(), committed_wires, n_committed);   // the arrays are this call's own until the key takes them
+        ka.n[KEY_G1_A] = in.n_g1_a; ka.n[KEY_G1_B] = in.n_g1_b; ka.n[KEY_G1_K] = in.n_g1_k; ka.n[KEY_G1_Z] = in.n_g1_z; ka.n[KEY_G2_B] = in.n_g2_b;
+        for (int i = 0; i < KEY_ARRAYS; i++) ka.arr[i] = dec.arr[i];
+        std::memcpy(ka.small1, dec.small1, sizeof(dec.small1));
+        std::memcpy(ka.small2, dec.small2, sizeof(dec.small2));
+        const int32_t rc = hand.adopt_key(ka, nullptr);
+        for (int i = 0; i < KEY_ARRAYS; i++) dec.arr[i] = ka.arr[i];   // what the key took is no longer this call's
+        MI_TRY(rc);
+        for (uint32_t k = 0; k < n_ped; k++) MI_TRY(hand.adopt_pedersen(&dec.ped[2 * k], &dec.ped[2 * k + 1], (size_t)in.n_basis[k], nullptr));
         MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const double t_end = now_ms();
-        ctx->keyfile_stats = mi_keyfile_stats{(float)(t_up - t0), (float)(t_dec - t_up), (float)(t_sub - t_dec), (float)(t_end - t_sub), (float)(t_end - t0)};
+        ctx->keyfile_stats = mi_keyfile_stats{(float)(dec.t_up - dec.t0), (float)(dec.t_dec - dec.t_up), (float)(dec.t_sub - dec.t_dec), (float)(t_end - dec.t_sub), (float)(t_end - dec.t0)};
         return MI_OK;
     };
     const int32_t rc = body();
     (void)hipStreamSynchronize(ctx->stream);
-    for (void *a : ka.arr) if (a) (void)hipFree(a);
-    for (void *a : ped_arrays) if (a) (void)hipFree(a);
-    for (void *a : {raw, d_small1, d_small2}) if (a) (void)hipFree(a);
     if (rc == MI_OK) {
         hand.dismiss();
         if (n_ped_out) *n_ped_out = n_ped;

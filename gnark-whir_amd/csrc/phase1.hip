@@ -281,6 +281,9 @@ int32_t check_domain(mi_ctx *ctx, uint64_t n_domain, u32 *log_n) {
 
 }  // namespace
 
+// phase2_internal.h: for the audit of a key against a phase-1 state's rows (keyaudit.hip)
+mi_srs_desc mi_phase1_rows_desc(const mi_phase1 *p1) { return rows_desc(p1->tau_g1, p1->alpha_tau_g1, p1->beta_tau_g1, p1->tau_g2, p1->beta_g2, p1->N); }
+
 extern "C" {
 
 int32_t mi_phase1_get_stats(mi_ctx *ctx, mi_phase1_stats *out) {

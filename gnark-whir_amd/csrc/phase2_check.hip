@@ -97,16 +97,7 @@ int32_t msm_g2(mi_ctx *ctx, const G2Aff *bases, const Fr *scalars, u64 n, G2Aff 
     return MI_OK;
 }
 
-// The relations of one call: relation i is e(p[2 i], q[2 i]) = e(pb, q[2 i + 1]), with p[2 i + 1] = -pb
-struct Relations {
-    std::vector<G1Aff> p;
-    std::vector<G2Aff> q;
-    void add(const G1Aff &pa, const G2Aff &qa, const G1Aff &pb, const G2Aff &qb) {
-        p.push_back(pa); q.push_back(qa);
-        p.push_back(g1_aff_neg(pb)); q.push_back(qb);
-    }
-    u32 count() const { return (u32)(p.size() / 2); }
-};
+typedef CeremonyRelations Relations;   // phase2_internal.h
 // bad[i] = relation i does not hold
 int32_t judge(mi_ctx *ctx, Arena &ar, const Relations &rel, std::vector<uint8_t> &bad) {
     const u32 n = rel.count();
@@ -267,6 +258,17 @@ int32_t verify_run(mi_ctx *ctx, mi_phase2 *S, const mi_phase2_claim *claim, cons
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------------- shared with keyaudit.hip
+void CeremonyRelations::add(const G1Aff &pa, const G2Aff &qa, const G1Aff &pb, const G2Aff &qb) {
+    p.push_back(pa); q.push_back(qa);
+    p.push_back(g1_aff_neg(pb)); q.push_back(qb);
+}
+int32_t mi_ceremony_seed_or_random(mi_ctx *ctx, const char *who, const uint8_t *&seed, uint8_t own[32]) { return seed_or_random(ctx, who, seed, own); }
+int32_t mi_ceremony_coeffs_enqueue(mi_ctx *ctx, const uint8_t seed[32], u64 n, Fr *out_dev) { return coeffs_enqueue(ctx, seed, n, out_dev); }
+int32_t mi_ceremony_msm_g1(mi_ctx *ctx, const G1Aff *bases, const Fr *scalars, u64 n, G1Aff *out) { return msm_g1(ctx, bases, scalars, n, out); }
+int32_t mi_ceremony_msm_g2(mi_ctx *ctx, const G2Aff *bases, const Fr *scalars, u64 n, G2Aff *out) { return msm_g2(ctx, bases, scalars, n, out); }
+int32_t mi_ceremony_judge(mi_ctx *ctx, Arena &ar, const CeremonyRelations &rel, std::vector<uint8_t> &bad) { return judge(ctx, ar, rel, bad); }
 
 // ---------------------------------------------------------------------------------------------------- shared with phase1.hip
 int32_t mi_srs_check_rows_dev(mi_ctx *ctx, const char *who, const mi_srs_desc *rows_dev, u64 N, const uint8_t *seed, mi_srs_check_stats &stats, uint32_t *failed) {

@@ -40,3 +40,26 @@ int32_t mi_srs_check_rows_dev(mi_ctx *ctx, const char *who, const mi_srs_desc *r
 // mi_phase2_init, or with on_device the same reading the SRS rows from device arrays (phase1.hip's handover: rows as above, the counts
 // the arrays' own, so that a circuit they are too short for is refused as a short row is)
 int32_t mi_phase2_init_rows(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_srs_desc *rows, bool on_device, const mi_fr *sigma, uint32_t flags, mi_phase2 **out);
+
+// ---------------------------------------------------------------------------------------------------- shared with keyaudit.hip
+// The steps of a same-ratio test as phase2_check.hip runs them, for the audit of a key (include/mi355x_groth16_keyaudit.h).
+// seed, or 32 bytes of the operating system's into own (MI_ENODEV names `who`)
+int32_t mi_ceremony_seed_or_random(mi_ctx *ctx, const char *who, const uint8_t *&seed, uint8_t own[32]);
+// out_dev[k] = r_k for k < n (k_ceremony_coeffs), Montgomery, enqueued on ctx->stream
+int32_t mi_ceremony_coeffs_enqueue(mi_ctx *ctx, const uint8_t seed[32], u64 n, Fr *out_dev);
+// sum_k scalars[k] bases[k] over device arrays, affine, (0, 0) = infinity; Montgomery scalars.  The result is on the host on return
+int32_t mi_ceremony_msm_g1(mi_ctx *ctx, const G1Aff *bases, const Fr *scalars, u64 n, G1Aff *out);
+int32_t mi_ceremony_msm_g2(mi_ctx *ctx, const G2Aff *bases, const Fr *scalars, u64 n, G2Aff *out);
+// The relations of one call: relation i is e(p[2 i], q[2 i]) = e(pb, q[2 i + 1]), with p[2 i + 1] = -pb
+struct CeremonyRelations {
+    std::vector<G1Aff> p;
+    std::vector<G2Aff> q;
+    void add(const G1Aff &pa, const G2Aff &qa, const G1Aff &pb, const G2Aff &qb);
+    u32 count() const { return (u32)(p.size() / 2); }
+};
+// bad[i] = relation i does not hold: every pair through ONE launch of the Miller loop, a product and a final exponentiation per
+// relation, k_ceremony_judge.  The stream is idle on return
+int32_t mi_ceremony_judge(mi_ctx *ctx, Arena &ar, const CeremonyRelations &rel, std::vector<uint8_t> &bad);
+// the four rows of a phase-1 state where they lie on the device, as a descriptor with the rows' own counts (phase1.hip)
+struct mi_phase1;
+mi_srs_desc mi_phase1_rows_desc(const mi_phase1 *p1);

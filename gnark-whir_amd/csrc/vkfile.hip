@@ -2,7 +2,7 @@
 // host-only half (which encoding, where the fields lie, the witness's bytes) is vkfile_inspect.hip; the verifier's entry points over
 // witness bytes are in verify_bytes.hip, beside the decode step they extend.
 //
-// mi_vk_load_stream: inspect on the host, upload once, every point through the bulk decoders of keyfile.hip (keyfile_internal.h; one
+// mi_vk_stream_decode + mi_vk_load_stream: inspect on the host, upload once, every point through the bulk decoders of keyfile.hip (keyfile_internal.h; one
 // launch per run of points the stream holds back to back), every G2 point through its membership test, ONE wait for all verdicts; then
 // the conditions mi_vk_load puts on a key and its own build of the resident key (mi_vk_build, verify.hip), which adopts K[1..] where the
 // decoder left it.  mi_vk_write: K through the bulk encoders, the single points and the lists on the host.
@@ -24,22 +24,18 @@ std::string ped_name(size_t j) { return "CommitmentKeys[" + std::to_string(j / 2
 
 }  // namespace
 
-extern "C" {
-
-int32_t mi_vk_load_stream(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t flags, mi_vk **out) {
-    if (!ctx) return MI_EINVAL;
-    if (!buf || !out) MI_FAIL(ctx, MI_EINVAL, "vkfile: null stream or output pointer");
-    *out = nullptr;
+// keyfile_internal.h: what mi_vk_load_stream and the key audit's claim (keyaudit.hip) share
+int32_t mi_vk_stream_decode(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t flags, VkStreamDecoded &out) {
     if (flags & ~(MI_KEYFILE_NO_SUBGROUP_CHECK | MI_KEYFILE_SUBGROUP_BY_R)) MI_FAIL(ctx, MI_EINVAL, "vkfile: unknown flag");
-    mi_vk_stream_info in;
+    mi_vk_stream_info &in = out.in;
     uint32_t encoding = 0;
     if (mi_vk_stream_inspect(buf, len, &in, &encoding) != MI_OK)
         MI_FAIL(ctx, MI_EINVAL, std::string("vkfile: the stream has neither the layout of VerifyingKey.WriteRawTo nor of VerifyingKey.WriteTo: ") + in.refused);
-    const bool compressed = encoding == MI_KEYFILE_COMPRESSED;
+    const bool compressed = out.compressed = encoding == MI_KEYFILE_COMPRESSED;
     const uint32_t nck = in.n_commitment_keys;
     const size_t n_k = (size_t)in.n_k, n_g2 = 3 + 2 * (size_t)nck;
     // where the decoded points go: g1 = Alpha, Beta, Delta, K[0]; g2 = Beta, Gamma, Delta, then G, GSigmaNeg of every key; k = K[1..]
-    G1Aff *d_g1 = nullptr, *d_k = nullptr;
+    G1Aff *d_g1 = nullptr;
     G2Aff *d_g2 = nullptr;
     uint8_t *raw = nullptr;
     ull *d_bad = nullptr;
@@ -47,12 +43,13 @@ int32_t mi_vk_load_stream(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t 
     auto body = [&]() -> int32_t {
         MI_CHECK_HIP(ctx, hipMalloc((void **)&d_g1, 4 * sizeof(G1Aff)));
         MI_CHECK_HIP(ctx, hipMalloc((void **)&d_g2, n_g2 * sizeof(G2Aff)));
-        MI_CHECK_HIP(ctx, hipMalloc((void **)&d_k, (n_k - 1) * sizeof(G1Aff) + 64));
+        MI_CHECK_HIP(ctx, hipMalloc(&out.k_dev, (n_k - 1) * sizeof(G1Aff) + 64));
         MI_CHECK_HIP(ctx, hipMalloc((void **)&d_bad, S_END * sizeof(ull)));
         MI_CHECK_HIP(ctx, hipMalloc((void **)&raw, len));
         MI_CHECK_HIP(ctx, hipMemsetAsync(d_bad, 0xff, S_END * sizeof(ull), ctx->stream));
         MI_CHECK_HIP(ctx, hipMemcpyAsync(raw, buf, len, hipMemcpyHostToDevice, ctx->stream));
         const size_t g1b = MI_KEYFILE_G1_BYTES(compressed);
+        G1Aff *const d_k = (G1Aff *)out.k_dev;
         MI_TRY(mi_keyfile_decode_enqueue(ctx, false, d_g1, raw + in.off_alpha1, 2, compressed, d_bad + S_ALPHA_BETA1));
         MI_TRY(mi_keyfile_decode_enqueue(ctx, true, d_g2, raw + in.off_beta2, 2, compressed, d_bad + S_BETA_GAMMA2));
         MI_TRY(mi_keyfile_decode_enqueue(ctx, false, d_g1 + 2, raw + in.off_delta1, 1, compressed, d_bad + S_DELTA1));
@@ -62,16 +59,17 @@ int32_t mi_vk_load_stream(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t 
         if (nck) MI_TRY(mi_keyfile_decode_enqueue(ctx, true, d_g2 + 3, raw + in.off_ped[0], 2 * (size_t)nck, compressed, d_bad + S_PED));
         if (!(flags & MI_KEYFILE_NO_SUBGROUP_CHECK))
             MI_TRY(mi_keyfile_subgroup_enqueue(ctx, d_g2, n_g2, (flags & MI_KEYFILE_SUBGROUP_BY_R) != 0, d_bad + S_SUBGROUP));
-        G1Aff g1[4];
+        out.g2.resize(n_g2);
+        out.k.resize(n_k);
         std::vector<G2Aff> g2(n_g2);
-        std::vector<G1Aff> k(n_k);
         ull bad[S_END];
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(g1, d_g1, sizeof(g1), hipMemcpyDeviceToHost, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(out.g1, d_g1, sizeof(out.g1), hipMemcpyDeviceToHost, ctx->stream));
         MI_CHECK_HIP(ctx, hipMemcpyAsync(g2.data(), d_g2, n_g2 * sizeof(G2Aff), hipMemcpyDeviceToHost, ctx->stream));
-        if (n_k > 1) MI_CHECK_HIP(ctx, hipMemcpyAsync(k.data() + 1, d_k, (n_k - 1) * sizeof(G1Aff), hipMemcpyDeviceToHost, ctx->stream));
+        if (n_k > 1) MI_CHECK_HIP(ctx, hipMemcpyAsync(out.k.data() + 1, d_k, (n_k - 1) * sizeof(G1Aff), hipMemcpyDeviceToHost, ctx->stream));
         MI_CHECK_HIP(ctx, hipMemcpyAsync(bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
         MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the one wait
-        k[0] = g1[3];
+        out.k[0] = out.g1[3];
+        std::memcpy(out.g2.data(), g2.data(), n_g2 * sizeof(G2Aff));
         // ---- the decoders' verdicts, in stream order
         const std::string no_point = std::string(" is malformed: no point of the curve has this ") + (compressed ? "compressed" : "raw") + " encoding";
         const char *const g2_names[3] = {"G2.Beta", "G2.Gamma", "G2.Delta"};
@@ -92,15 +90,35 @@ int32_t mi_vk_load_stream(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t 
             if (std::memcmp(&g2[3 + 2 * c], &g2[3], sizeof(G2Aff)) != 0) MI_FAIL(ctx, MI_EINVAL, "vkfile: the Pedersen keys do not share one G (" + ped_name(2 * c) + ")");
             if (g2[3 + 2 * c].is_inf()) MI_FAIL(ctx, MI_EINVAL, "vkfile: " + ped_name(2 * c) + " is infinity");
         }
+        return MI_OK;
+    };
+    const int32_t rc = body();
+    (void)hipStreamSynchronize(ctx->stream);
+    for (void *a : {(void *)d_g1, (void *)d_g2, (void *)d_bad, (void *)raw})
+        if (a) (void)hipFree(a);
+    return rc;
+}
+
+extern "C" {
+
+int32_t mi_vk_load_stream(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t flags, mi_vk **out) {
+    if (!ctx) return MI_EINVAL;
+    if (!buf || !out) MI_FAIL(ctx, MI_EINVAL, "vkfile: null stream or output pointer");
+    *out = nullptr;
+    VkStreamDecoded dec;
+    auto body = [&]() -> int32_t {
+        MI_TRY(mi_vk_stream_decode(ctx, buf, len, flags, dec));
+        const mi_vk_stream_info &in = dec.in;
+        const uint32_t nck = in.n_commitment_keys;
         // ---- the resident key, as mi_vk_load builds it, and the lists
         mi_vk_desc d;
         std::memset(&d, 0, sizeof(d));
-        std::memcpy(&d.alpha1, &g1[0], sizeof(G1Aff));
-        std::memcpy(&d.beta2, &g2[0], sizeof(G2Aff)); std::memcpy(&d.gamma2, &g2[1], sizeof(G2Aff)); std::memcpy(&d.delta2, &g2[2], sizeof(G2Aff));
-        d.k = (const mi_g1_affine *)k.data(); d.n_k = n_k; d.nb_public = in.nb_public; d.n_commitments = nck;
-        d.ped = nck ? (const mi_pedersen_vk *)&g2[3] : nullptr;
-        G1Aff *adopt = d_k;
-        d_k = nullptr;   // the key owns it from here, whatever mi_vk_build returns
+        d.alpha1 = dec.g1[0];
+        d.beta2 = dec.g2[0]; d.gamma2 = dec.g2[1]; d.delta2 = dec.g2[2];
+        d.k = dec.k.data(); d.n_k = in.n_k; d.nb_public = in.nb_public; d.n_commitments = nck;
+        d.ped = nck ? (const mi_pedersen_vk *)&dec.g2[3] : nullptr;
+        G1Aff *adopt = (G1Aff *)dec.k_dev;
+        dec.k_dev = nullptr;   // the key owns it from here, whatever mi_vk_build returns
         MI_TRY(mi_vk_build(ctx, &d, adopt, out));
         std::vector<uint32_t> off(nck + 1, 0), idx;
         for (uint32_t c = 0; c < nck; c++) {
@@ -114,8 +132,6 @@ int32_t mi_vk_load_stream(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_t 
     };
     const int32_t rc = body();
     (void)hipStreamSynchronize(ctx->stream);
-    for (void *a : {(void *)d_g1, (void *)d_g2, (void *)d_k, (void *)d_bad, (void *)raw})
-        if (a) (void)hipFree(a);
     if (rc != MI_OK && *out) { (void)mi_vk_free(ctx, *out); *out = nullptr; }
     return rc;
 }

@@ -226,6 +226,17 @@ int32_t mi_debug_ceremony_coeffs_dev(mi_ctx *ctx, const uint8_t seed[32], size_t
  * 2^28, not only powers of two: out_host[i] = [c t^(k0 + i)] pts_host[i], affine points of G1 (g2 = 0) or G2 (g2 != 0), (0, 0) = infinity in
  * and out; t, c Montgomery and below r.  The knobs of mi_debug_set_knob choose what runs; mi_phase1_get_stats then tells row 0's times. */
 int32_t mi_debug_scale_powers_dev(mi_ctx *ctx, int32_t g2, const void *pts_host, size_t n, const mi_fr *t, const mi_fr *c, uint64_t k0, void *out_host);
+/* The two sides of every relation of the last mi_key_audit on ctx (mi355x_groth16_keyaudit.h) that got as far as its sums, as affine
+ * points before any pairing: [0] = the side summed over the claimed key, [1] = the side summed over the SRS.  k_private, k_public, basis:
+ * [0] is paired with delta2 / gamma2, [1] = T(r^P), T(r^V), T(r^C) with g2; z[1] is the difference of the two MSMs; sigma[k] = the sums
+ * over Basis_k and BasisExpSigma_k for k < n_sigma.  MI_EINVAL when the context has run no such audit. */
+typedef struct mi_key_audit_sums {
+    mi_g1_affine a[2], b1[2], k_private[2], k_public[2], basis[2], z[2];
+    mi_g2_affine b2[2];
+    mi_g1_affine sigma[16][2];
+    uint32_t n_sigma, valid;
+} mi_key_audit_sums;
+int32_t mi_debug_key_audit_sums(mi_ctx *ctx, mi_key_audit_sums *out);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,8 @@
  *   - gnark's mpcsetup file formats (Phase1 / Phase2 WriteTo): their layout is NOT AVAILABLE to this project (no gnark on the machines
  *     this was written on), so the SRS, the state and the records cross this interface as plain arrays in this project's own layout.
  *     The keys leave as the streams of mi355x_groth16_keyfile.h and mi355x_groth16_vkfile.h, with those headers' caveats.
+ * Whether a key -- a sealed state's or a file's -- IS the key of this circuit under this SRS can be checked without deriving it again:
+ * mi355x_groth16_keyaudit.h.
  */
 #ifndef MI355X_GROTH16_PHASE2_H
 #define MI355X_GROTH16_PHASE2_H

@@ -30,6 +30,8 @@
  *   - sigma / BasisExpSigma: mi_phase2_contribute_proved leaves them alone and mi_phase2_verify_adopt takes none from outside (the
  *     adopting state's stay its own), so the re-randomisation of the commitment keys has no proof of knowledge and no chain;
  *   - gnark's Phase1 / Phase2 file formats.
+ * That BasisExpSigma IS sigma Basis for the sigma of the verifying key, and every other array the key of its circuit under its SRS, is
+ * what mi355x_groth16_keyaudit.h checks without the derivation; who knows sigma it cannot say either.
  * mi_srs_check_powers says that the rows ARE powers of one (tau, alpha, beta), not who contributed to them: that is what a phase-1 transcript
  * says, and mi355x_groth16_phase1.h makes and verifies one (its mi_phase1_verify_adopt and mi_phase1_check run the relations below over
  * rows that are on the device already).
