@@ -19,7 +19,7 @@ EXPORTS = [
     "mi_ntt", "mi_ntt_dev", "mi_compute_h", "mi_compute_h_dev", "mi_msm_g1", "mi_msm_g1_dev", "mi_msm_g2",
     "mi_msm_g2_dev", "mi_groth16_prove", "mi_groth16_prove_dev", "mi_get_stats", "mi_g1_compress",
     "mi_g2_compress", "mi_proof_write", "mi_g1_sum", "mi_g2_sum", "mi_gen_scalars_dev", "mi_gen_g1_dev",
-    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_field_shape_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_debug_decode_g1_dev", "mi_debug_decode_g2_dev", "mi_debug_hash_to_field_dev", "mi_debug_witness_decode_dev", "mi_debug_fp12_product_dev", "mi_debug_g1_scale128_dev", "mi_debug_g1_sum_tree_dev", "mi_debug_locate_points_dev", "mi_debug_locate_colsums_dev", "mi_debug_set_locate_round_nodes", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
+    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_field_shape_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_debug_pairing_wave_dev", "mi_debug_fp12_op_wave_dev", "mi_debug_verify_wave_split", "mi_debug_decode_g1_dev", "mi_debug_decode_g2_dev", "mi_debug_hash_to_field_dev", "mi_debug_witness_decode_dev", "mi_debug_fp12_product_dev", "mi_debug_g1_scale128_dev", "mi_debug_g1_sum_tree_dev", "mi_debug_locate_points_dev", "mi_debug_locate_colsums_dev", "mi_debug_set_locate_round_nodes", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
     "mi_dev_alloc", "mi_dev_free", "mi_dev_upload", "mi_dev_download", "mi_dev_sync",
     "mi_msm_precompute_g1_dev", "mi_msm_precompute_g2_dev", "mi_msm_g1_fixed_dev", "mi_msm_g2_fixed_dev", "mi_msm_table_to_rprime_g1_dev", "mi_msm_table_to_rprime_g2_dev", "mi_pk_table_plan",
     "mi_batch_scalar_mul_g1", "mi_batch_scalar_mul_g1_dev", "mi_batch_scalar_mul_g2", "mi_batch_scalar_mul_g2_dev",
@@ -55,6 +55,9 @@ VERIFY_BYTES_EXPORTS = ["mi_vk_set_public_committed", "mi_groth16_verify_bytes",
 VERIFY_COMBINED_EXPORTS = ["mi_groth16_verify_combined", "mi_groth16_verify_bytes_combined"]
 # include/mi355x_groth16_verify_locate.h (one verdict per proof: the combined test on a tree of subsets, descending into the ones that fail)
 VERIFY_LOCATE_EXPORTS = ["mi_groth16_verify_locate", "mi_groth16_verify_bytes_locate"]
+# include/mi355x_groth16_verify_wave.h (one proof, or a few: one wave per pairing, the verdicts of the batch calls)
+VERIFY_WAVE_EXPORTS = ["mi_groth16_verify_wave", "mi_groth16_verify_bytes_wave"]
+VERIFY_WAVE_SPLIT_PHASES = ("host", "bs_check", "miller", "judge", "copy_back")   # mi_debug_verify_wave_split, ms
 # include/mi355x_groth16_keyfile.h (proving keys as files: bulk point codecs, loading gnark's raw or compressed stream, writing both)
 KEYFILE_EXPORTS = ["mi_g1_decompress_dev", "mi_g2_decompress_dev", "mi_g1_compress_dev", "mi_g2_compress_dev", "mi_pk_stream_inspect", "mi_pk_load_stream",
                    "mi_keyfile_get_stats", "mi_pk_stream_size", "mi_pk_write_dev", "mi_groth16_setup_to_stream"]
@@ -1181,6 +1184,29 @@ class Context:
             for b in (dx, dy, dz):
                 if b: b.free()
 
+    def pairing_wave(self, p, q, final_exp=True):
+        """mi_debug_pairing_wave_dev: pairing() with one wave per pair"""
+        p, q = _u64(p).reshape(-1, 8), _u64(q).reshape(-1, 16); n = p.shape[0]
+        dp, dq = self.to_dev(p), self.to_dev(q); do = self.alloc(max(384 * n, 32))
+        try:
+            self._ck(self.lib.mi_debug_pairing_wave_dev(self.h, _p(dp.ptr), _p(dq.ptr), C.c_size_t(n), _p(do.ptr), C.c_uint32(PAIRING_FINAL_EXP if final_exp else 0)))
+            self.sync()
+            return do.download((n, 48)) if n else np.zeros((0, 48), np.uint64)
+        finally:
+            for b in (dp, dq, do): b.free()
+
+    def fp12_op_wave(self, op, x, y=None):
+        """mi_debug_fp12_op_wave_dev: fp12_op() with one wave per record"""
+        x = _u64(x).reshape(-1, 48); n = x.shape[0]
+        dx = self.to_dev(x); dy = self.to_dev(_u64(y).reshape(-1, 48)) if y is not None else None; dz = self.alloc(max(384 * n, 32))
+        try:
+            self._ck(self.lib.mi_debug_fp12_op_wave_dev(self.h, C.c_int(op), _p(dz.ptr), _p(dx.ptr), _p(dy.ptr if dy else None), C.c_size_t(n)))
+            self.sync()
+            return dz.download((n, 48)) if n else np.zeros((0, 48), np.uint64)
+        finally:
+            for b in (dx, dy, dz):
+                if b: b.free()
+
     def fp12_product(self, x):
         """mi_debug_fp12_product_dev over a host array of (n, 48) uint64 records -> (48,): their product"""
         x = _u64(x).reshape(-1, 48); n = x.shape[0]
@@ -1349,6 +1375,25 @@ class VerifyingKey:
         arr, keep = self._inputs(list(proofs)); out = np.full(len(arr), 255, np.uint8)
         self.ctx._ck(self.ctx.lib.mi_groth16_verify_batch(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), _p(out)))
         return out
+
+    # ---- one wave per pairing: one proof, or a few (include/mi355x_groth16_verify_wave.h)
+    def verify_wave(self, proofs):
+        """mi_groth16_verify_wave: proofs as verify_batch takes them -> verdicts (n,) uint8"""
+        arr, keep = self._inputs(list(proofs)); out = np.full(len(arr), 255, np.uint8)
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_wave(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), _p(out)))
+        return out
+
+    def verify_bytes_wave(self, proofs):
+        """mi_groth16_verify_bytes_wave: proofs as verify_bytes_batch takes them -> verdicts (n,) uint8"""
+        arr, keep = self._bytes_inputs(proofs); out = np.full(len(arr), 255, np.uint8)
+        self.ctx._ck(self.ctx.lib.mi_groth16_verify_bytes_wave(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), _p(out)))
+        return out
+
+    def verify_wave_split(self, proofs):
+        """mi_debug_verify_wave_split -> (verdicts, {phase: ms} over VERIFY_WAVE_SPLIT_PHASES)"""
+        arr, keep = self._inputs(list(proofs)); out = np.full(len(arr), 255, np.uint8); ms = (C.c_float * len(VERIFY_WAVE_SPLIT_PHASES))()
+        self.ctx._ck(self.ctx.lib.mi_debug_verify_wave_split(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), _p(out), ms))
+        return out, dict(zip(VERIFY_WAVE_SPLIT_PHASES, (float(v) for v in ms)))
 
     # ---- one verdict for the batch (include/mi355x_groth16_verify_combined.h)
     def verify_combined(self, proofs, seed=None):

@@ -224,6 +224,12 @@ int32_t mi_groth16_verify_bytes_batch(mi_ctx *ctx, const mi_vk *vk, const mi_ver
     return mi_verify_run(ctx, vk, d.dec.data(), n, verdicts, d.bad.data());
 }
 
+int32_t mi_groth16_verify_bytes_wave(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, uint8_t *verdicts) {
+    Decoded d;
+    MI_TRY(verify_bytes_decode(ctx, vk, in, nullptr, n, verdicts || !n, &d));
+    return mi_verify_run_wave(ctx, vk, d.dec.data(), n, verdicts, d.bad.data());
+}
+
 int32_t mi_groth16_verify_bytes_combined(mi_ctx *ctx, const mi_vk *vk, const mi_verify_bytes_input *in, size_t n, const uint8_t *seed, uint8_t *verdict,
                                          uint64_t *first_malformed) {
     Decoded d;

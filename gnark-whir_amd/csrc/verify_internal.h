@@ -1,11 +1,12 @@
-// What verify.hip, verify_bytes.hip, verify_combined.hip and verify_locate.hip share (not part of the C-ABI): the resident key, the opening of a batch
-// (mi_verify_open: argument checks, proof references, the VerifyStage of pairing_ops.cuh), the three bodies that judge it, the launches of
+// What verify.hip, verify_bytes.hip, verify_combined.hip, verify_locate.hip and verify_wave.hip share (not part of the C-ABI): the resident key, the opening of a batch
+// (mi_verify_open: argument checks, proof references, the VerifyStage of pairing_ops.cuh), the four bodies that judge it, the launches of
 // verify.hip's kernels that the combined body reuses, and three helpers: WsCut (a workspace's layout), mi_launch64, mi_verify_msm.
 #pragma once
 #include "ctx.h"
 #include "../../include/mi355x_groth16_verify.h"
 #include "../../include/mi355x_groth16_verify_combined.h"
 #include "../../include/mi355x_groth16_verify_locate.h"
+#include "../../include/mi355x_groth16_verify_wave.h"
 #include "pairing_ops.cuh"
 #include <vector>
 
@@ -31,6 +32,10 @@ int32_t mi_verify_open(mi_ctx *ctx, const char *who, const mi_vk *vk, const mi_v
 // mi_groth16_verify_batch's body (verify.hip)
 int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts, const uint8_t *decode_malformed,
                       const Fr *pub_dev = nullptr);
+// mi_groth16_verify_wave's body (verify_wave.hip): mi_verify_run's inputs and verdict bytes, one wave per pairing.  split_ms (may be
+// null): MI_VERIFY_WAVE_SPLIT_PHASES times of the call, which then sends the Bs checks and the Miller loops as two launches
+int32_t mi_verify_run_wave(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts, const uint8_t *decode_malformed,
+                           const Fr *pub_dev = nullptr, float *split_ms = nullptr);
 // mi_groth16_verify_combined's body (verify_combined.hip): one verdict for the batch.  seed may be null.
 int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdict,
                                uint64_t *first_malformed, const uint8_t *decode_malformed, const Fr *pub_dev = nullptr);

@@ -6,6 +6,8 @@
 // the host -- the hash-to-field of every commitment (with the public committed values) and the fold challenge -- and hands the rest to
 // mi_groth16_verify.  VerifyBytes takes Proof.WriteTo's bytes and leaves decoding and hashing to the device (mi_groth16_verify_bytes).
 // VerifyBytesCombined judges a whole batch of such proofs with ONE verdict (mi_groth16_verify_bytes_combined).
+// VerifyWave and VerifyBytesWave are Verify and VerifyBytes through the low-latency body (include/mi355x_groth16_verify_wave.h: one
+// wave per pairing, the same verdicts): the calls for the single proof mt.go:497 verifies.
 // VerifyFiles and VerifyFilesCombined take the public witness as witness.WriteTo's bytes too (include/mi355x_groth16_vkfile.h): with a
 // key from LoadVerifyingKeyStream (keyfile.go) nothing of gnark is decoded on the host.
 package mi355x
@@ -15,6 +17,7 @@ package mi355x
 #include "mi355x_groth16_verify.h"
 #include "mi355x_groth16_verify_bytes.h"
 #include "mi355x_groth16_verify_combined.h"
+#include "mi355x_groth16_verify_wave.h"
 #include "mi355x_groth16_vkfile.h"
 */
 import "C"
@@ -113,6 +116,16 @@ func (vk *VerifyingKey) Close() {
 // Verify replaces groth16.Verify(proof, vk, publicWitness).  publicWitness holds the public inputs without the ONE wire, as
 // witness.Vector() of the public witness does.
 func Verify(vk *VerifyingKey, proof *groth16_bn254.Proof, publicWitness fr.Vector) error {
+	return verify(vk, proof, publicWitness, false)
+}
+
+// VerifyWave is Verify through mi_groth16_verify_wave: one wave per pairing instead of one lane, the same verdict, a fraction of the
+// latency for one proof (the measured range is in the header).
+func VerifyWave(vk *VerifyingKey, proof *groth16_bn254.Proof, publicWitness fr.Vector) error {
+	return verify(vk, proof, publicWitness, true)
+}
+
+func verify(vk *VerifyingKey, proof *groth16_bn254.Proof, publicWitness fr.Vector, wave bool) error {
 	nc := len(vk.PublicAndCommitmentCommitted)
 	if len(proof.Commitments) != nc {
 		return errors.New("mi355x: the proof's commitments do not match the key")
@@ -175,7 +188,13 @@ func Verify(vk *VerifyingKey, proof *groth16_bn254.Proof, publicWitness fr.Vecto
 		in.fold_challenge = (*C.mi_fr)(unsafe.Pointer(&challenge))
 	}
 	var verdict C.uint8_t
-	if err := status(vk.ctx, C.mi_groth16_verify(vk.ctx, vk.dev, &in, &verdict)); err != nil {
+	var rc C.int32_t
+	if wave {
+		rc = C.mi_groth16_verify_wave(vk.ctx, vk.dev, &in, 1, &verdict)
+	} else {
+		rc = C.mi_groth16_verify(vk.ctx, vk.dev, &in, &verdict)
+	}
+	if err := status(vk.ctx, rc); err != nil {
 		return err
 	}
 	if verdict != C.MI_VERIFY_OK {
@@ -187,6 +206,15 @@ func Verify(vk *VerifyingKey, proof *groth16_bn254.Proof, publicWitness fr.Vecto
 // VerifyBytes replaces groth16.Verify for a proof that arrives as Proof.WriteTo's bytes (164 + 32 * commitments): the points are
 // decompressed and the BSB22 hashes computed on the device.  No host hashing, no gnark-crypto decoding.
 func VerifyBytes(vk *VerifyingKey, proof []byte, publicWitness fr.Vector) error {
+	return verifyBytes(vk, proof, publicWitness, false)
+}
+
+// VerifyBytesWave is VerifyBytes through mi_groth16_verify_bytes_wave (see VerifyWave).
+func VerifyBytesWave(vk *VerifyingKey, proof []byte, publicWitness fr.Vector) error {
+	return verifyBytes(vk, proof, publicWitness, true)
+}
+
+func verifyBytes(vk *VerifyingKey, proof []byte, publicWitness fr.Vector, wave bool) error {
 	nc := len(vk.PublicAndCommitmentCommitted)
 	if len(publicWitness) != len(vk.G1.K)-nc-1 {
 		return errors.New("mi355x: wrong number of public inputs")
@@ -203,7 +231,13 @@ func VerifyBytes(vk *VerifyingKey, proof []byte, publicWitness fr.Vector) error 
 		pub = (*C.mi_fr)(unsafe.Pointer(&publicWitness[0]))
 	}
 	var verdict C.uint8_t
-	rc := C.mi_groth16_verify_bytes(vk.ctx, vk.dev, (*C.uint8_t)(unsafe.Pointer(&proof[0])), C.size_t(len(proof)), pub, &verdict)
+	var rc C.int32_t
+	if wave {
+		in := C.mi_verify_bytes_input{proof: (*C.uint8_t)(unsafe.Pointer(&proof[0])), proof_len: C.size_t(len(proof)), public_inputs: pub}
+		rc = C.mi_groth16_verify_bytes_wave(vk.ctx, vk.dev, &in, 1, &verdict)
+	} else {
+		rc = C.mi_groth16_verify_bytes(vk.ctx, vk.dev, (*C.uint8_t)(unsafe.Pointer(&proof[0])), C.size_t(len(proof)), pub, &verdict)
+	}
 	if err := status(vk.ctx, rc); err != nil {
 		return err
 	}

@@ -24,6 +24,7 @@
 #include "../../include/mi355x_groth16_verify_bytes.h"
 #include "../../include/mi355x_groth16_vkfile.h"
 #include "../../include/mi355x_groth16_verify_combined.h"
+#include "../../include/mi355x_groth16_verify_wave.h"
 #include "../../include/mi355x_groth16_phase2.h"
 #include "../../include/mi355x_groth16_debug.h"   // (this mirror is the TEST side: generators and knobs)
 
@@ -259,6 +260,19 @@ inline uint8_t VerifyBytes(const Context &ctx, const VerifyingKey &vk, const std
     uint8_t verdict = MI_VERIFY_MALFORMED;
     ctx.check(mi_groth16_verify_bytes(ctx.get(), vk.get(), bytes.data(), bytes.size(), publicInputs.empty() ? nullptr : publicInputs.data(), &verdict));
     return verdict;
+}
+// One proof, or a few, at low latency (include/mi355x_groth16_verify_wave.h): one wave per pairing instead of one lane, the verdicts of
+// mi_groth16_verify_batch / mi_groth16_verify_bytes_batch byte for byte.  The header quotes the measured range; above it the batch,
+// combined and locate calls remain the tools.
+inline std::vector<uint8_t> VerifyWave(const Context &ctx, const VerifyingKey &vk, const std::vector<mi_verify_input> &in) {
+    std::vector<uint8_t> verdicts(in.size(), MI_VERIFY_MALFORMED);
+    ctx.check(mi_groth16_verify_wave(ctx.get(), vk.get(), in.data(), in.size(), verdicts.data()));
+    return verdicts;
+}
+inline std::vector<uint8_t> VerifyBytesWave(const Context &ctx, const VerifyingKey &vk, const std::vector<mi_verify_bytes_input> &in) {
+    std::vector<uint8_t> verdicts(in.size(), MI_VERIFY_MALFORMED);
+    ctx.check(mi_groth16_verify_bytes_wave(ctx.get(), vk.get(), in.data(), in.size(), verdicts.data()));
+    return verdicts;
 }
 // ONE verdict for a batch of proofs under one key (include/mi355x_groth16_verify_combined.h): the random linear combination of their
 // equations -- n + 3 (+ commitments + 1) Miller loops, two final exponentiations and a constant number of MSMs for the whole batch.

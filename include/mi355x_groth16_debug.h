@@ -71,6 +71,18 @@ int32_t mi_debug_field_shape_dev(mi_ctx *ctx, int shape, void *out_dev, const vo
 #define MI_FP12_WORDS 96
 int32_t mi_debug_pairing_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, const mi_g2_affine *q_dev, size_t n, mi_fp *gt_dev, uint32_t flags);
 int32_t mi_debug_fp12_op_dev(mi_ctx *ctx, int op, mi_fp *z_dev, const mi_fp *x_dev, const mi_fp *y_dev, size_t n);
+/* The same two with ONE WAVE per record (csrc/fp12_wave.cuh, pairing_wave.cuh; the host build of the tests: tests/emu/
+ * emu_pairing_wave.cpp): the arguments, op numbers, flags and refusals of mi_debug_pairing_dev / mi_debug_fp12_op_dev, and word for word
+ * their results -- the grid is n single-wave workgroups.  Inversion and the Fp6 ops run in one lane of the wave.
+ * mi_debug_verify_wave_split: mi_groth16_verify_wave (mi355x_groth16_verify_wave.h) with its time split into MI_VERIFY_WAVE_SPLIT_PHASES
+ * phases, in ms: [0] the host stage with the MSM calls (wall clock), then by events on the context's stream [1] the Bs checks, [2] the
+ * Miller loops, [3] the judgement with the verdict bytes, [4] the copy back.  To be timed apart the checks and the Miller loops go as two
+ * launches here; the product call sends them as one.  MI_EINVAL also for a null split pointer. */
+#define MI_VERIFY_WAVE_SPLIT_PHASES 5
+int32_t mi_debug_pairing_wave_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, const mi_g2_affine *q_dev, size_t n, mi_fp *gt_dev, uint32_t flags);
+int32_t mi_debug_fp12_op_wave_dev(mi_ctx *ctx, int op, mi_fp *z_dev, const mi_fp *x_dev, const mi_fp *y_dev, size_t n);
+struct mi_vk; struct mi_verify_input;
+int32_t mi_debug_verify_wave_split(mi_ctx *ctx, const struct mi_vk *vk, const struct mi_verify_input *in, size_t n, uint8_t *verdicts, float *split_ms);
 /* the decoders and the hash behind mi355x_groth16_verify_bytes.h (csrc/decode_ops.cuh, sha256_h2f.cuh), one record per lane; the host
  * build of the tests (tests/emu/emu_decode.cpp) runs the same bodies.  All pointers are DEVICE pointers; the launches go to the context's
  * stream (mi_dev_sync before reading).

@@ -9,6 +9,7 @@ ALTERNATING, with the locate call's stats; then, for the larger batches with b =
 
     python tools/verify_probe.py [--write profiles/verify.txt] [--batches 64,1024,16384] [--runs 5]
     python tools/verify_probe.py --files [--write profiles/verify.txt]      the files leg alone (files_leg below); --write APPENDS
+    python tools/verify_probe.py --wave [--write profiles/verify.txt]       the wave leg alone (wave_leg below); --write APPENDS
 
 A solvable circuit of 1000 constraints (domain 2^10, 4 public inputs, one BSB22 commitment; tests/r1cs_cases.py), its key from
 mi_groth16_setup, one proof through the prover pool.  After a warm-up call, the median wall time of `--runs` calls of one verification
@@ -128,8 +129,63 @@ def files_leg(B, args):
     vkh.free(); ctx.close()
 
 
+def wave_leg(B, ctx, vkh, inp, args, header):
+    """--wave: mi_groth16_verify_wave (csrc/verify_wave.hip: one wave per pairing) against the parent's mi_groth16_verify_batch on the
+    probe's key and proof, n = 1, 8, 64, 512, 4096 (--wave-batches): the two calls ALTERNATE in this process on this context, one
+    warm-up pair and then max(--runs, 5) pairs, whole calls with their host part.  Per leg the median and the spread (max - min).  The
+    yardstick is the parent's call in the same run: the wave call counts as faster at an n only where its median is below the
+    parent's by more than the larger of the two spreads.  At n = 1 also the phase split of the wave call
+    (mi_debug_verify_wave_split), the median of each phase over the same number of calls.  With --write the lines are APPENDED."""
+    C = B.C
+    runs = max(args.runs, 5)
+    lines = [f"verify, one wave per pairing (tools/verify_probe.py --wave): {header}",
+             f"mi_groth16_verify_batch (the parent's call) and mi_groth16_verify_wave alternating on one context, {runs} pairs after one warm-up pair, whole calls, host clocks;",
+             "median ms (spread = max - min); 'faster' only where the wave median is below the batch median by more than the larger spread"]
+    print("\n".join(lines), flush=True)
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+
+    lead = None
+    for nb in [int(x) for x in args.wave_batches.split(",") if x]:
+        arr, keep = vkh._inputs([inp] * nb)
+        out_b, out_w = np.full(nb, 255, np.uint8), np.full(nb, 255, np.uint8)
+        bcall = lambda: ctx._ck(ctx.lib.mi_groth16_verify_batch(ctx.h, vkh.h, arr, C.c_size_t(nb), out_b.ctypes.data_as(C.c_void_p)))
+        wcall = lambda: ctx._ck(ctx.lib.mi_groth16_verify_wave(ctx.h, vkh.h, arr, C.c_size_t(nb), out_w.ctypes.data_as(C.c_void_p)))
+        bcall(); wcall()
+        tb, tw = [], []
+        for _ in range(runs):
+            for fn, ts in ((bcall, tb), (wcall, tw)):
+                t = time.perf_counter(); fn(); ts.append((time.perf_counter() - t) * 1e3)
+        assert not out_b.any() and not out_w.any()
+        mb, mw, sb, sw = statistics.median(tb), statistics.median(tw), max(tb) - min(tb), max(tw) - min(tw)
+        verdict = "wave faster" if mb - mw > max(sb, sw) else ("batch faster" if mw - mb > max(sb, sw) else "no difference beyond the spread")
+        if verdict == "batch faster" and lead is None:
+            lead = nb
+        emit(f"n = {nb:5d}   batch {mb:10.3f} ms (spread {sb:.3f}, {100 * sb / mb:.1f} %)   wave {mw:10.3f} ms (spread {sw:.3f}, {100 * sw / mw:.1f} %)   "
+             f"batch / wave {mb / mw:6.2f}   {verdict}")
+        if nb == 1:
+            splits = []
+            for _ in range(runs + 1):
+                v, ms = vkh.verify_wave_split([inp])
+                assert not v.any()
+                splits.append(ms)
+            med = {k: statistics.median(x[k] for x in splits[1:]) for k in B.VERIFY_WAVE_SPLIT_PHASES}
+            emit("            phase split of the wave call at n = 1, ms (host stage with the MSM call by the wall clock, the rest by events on the stream; "
+                 "the Bs check and the Miller loops as two launches here, one launch in the product call):")
+            emit("            " + "   ".join(f"{k} {med[k]:.3f}" for k in B.VERIFY_WAVE_SPLIT_PHASES) + f"   sum {sum(med.values()):.3f}")
+    emit(f"the batch call takes the lead at n = {lead}" if lead else "the batch call takes the lead at none of these n")
+    emit("NOT MEASURED: kernel times by a profiler, sizes between these, other keys (more pairs per proof), any CPU verifier (none exists here)")
+    if args.write:
+        with open(args.write, "a") as f:
+            f.write("\n" + "\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--wave", action="store_true", help="the wave leg alone (see wave_leg); --write appends")
+    ap.add_argument("--wave-batches", default="1,8,64,512,4096")
     ap.add_argument("--files", action="store_true", help="the files leg alone (see files_leg); --write appends")
     ap.add_argument("--write")
     ap.add_argument("--batches", default="64,1024,16384")
@@ -174,6 +230,10 @@ def main():
     assert vkh.verify(inp) == B.VERIFY_OK
     data = B.proof_write(inp["raw"], commitments=cm, pok=inp["pok"])
     assert vkh.verify_bytes(data, inp["public_inputs"]) == B.VERIFY_OK
+    if args.wave:
+        wave_leg(B, ctx, vkh, inp, args, f"1000 constraints (domain 2^10), {nb_public - 1} public inputs, 1 commitment (5 pairs per proof)")
+        vkh.free(); ctx.pedersen_pk_free(peds[0]); ctx.pk_free(pkh); ctx.close()
+        return
     lines = [f"groth16.Verify on the device: 1000 constraints (domain 2^10), {nb_public - 1} public inputs, 1 commitment (5 pairs per proof)",
              f"median wall time of {args.runs} calls after one warm-up call, host part included; no baseline exists, no rate is claimed"]
 
