@@ -2,18 +2,19 @@
 // device-resident verifying key, and the two debug entry points over the same arithmetic (fp12.cuh, pairing.cuh, pairing_ops.cuh).
 //
 // One batch, every launch on ctx->stream:
-//   host      mi_verify_open, the start of both bodies: the argument checks, then the VerifyStage (the range checks of every word and the
+//   host      mi_verify_open, the start of every body: the argument checks, then the VerifyStage (the range checks of every word and the
 //             curve checks of the G1 points, verify_well_formed: a proof that fails them is malformed and goes no further; the scalars
-//             of kSum); per proof one G1 MSM over the key's resident K[1..] (mi_verify_msm over msm.hip), then kSum = K[0] + that +
-//             sum C_k, the folded commitments c^k C_k and the layout of the pairs (verify_assemble).  Stage and functions live in
-//             pairing_ops.cuh, where the host build of the tests runs them too
+//             of kSum); then mi_verify_stage_pairs, the host half this body shares with the wave body: per proof one G1 MSM over the
+//             key's resident K[1..] (mi_verify_msm over msm.hip), then kSum = K[0] + that + sum C_k, the folded commitments c^k C_k and
+//             the layout of the pairs (verify_assemble), and the pairs and flags up.  Stage and functions live in pairing_ops.cuh,
+//             where the host build of the tests runs them too
 //   k_verify_g2_check   one lane per proof: Bs on the twist and in its r-torsion -> the malformed flag
 //   k_pairing_miller    one lane per (proof, pair): a Miller loop, 384 B out
 //   k_verify_judge      one lane per proof: the products of its Miller values, the final exponentiations, the comparisons -> a verdict byte
 // Everything of a batch lives in ONE grow-only workspace (WS_VERIFY), laid out by a WsCut: nothing is allocated in steady state.
-// mi_verify_run is that batch; verify_bytes.hip calls it too, with the proofs it decoded.  verify_combined.hip judges a batch with ONE
-// verdict instead: it starts with mi_verify_open too and reuses k_verify_g2_check, k_pairing_miller and k_pairing_final_exp through
-// the three *_enqueue functions.  Every launch of the three files goes through mi_launch64 (verify_internal.h, which holds mi_vk too).
+// mi_verify_run is that batch; verify_bytes.hip calls it too, with the proofs it decoded, and verify_locate.hip with its suspects.  The
+// other three bodies (verify_internal.h names all four) reuse k_verify_g2_check, k_pairing_miller and k_pairing_final_exp through the
+// three *_enqueue functions.  Every launch of one lane per item goes through mi_launch64 (verify_internal.h, which holds mi_vk too).
 #include "verify_internal.h"
 #include <cstring>
 #include <string>
@@ -107,35 +108,43 @@ int32_t mi_verify_open(mi_ctx *ctx, const char *who, const mi_vk *vk, const mi_v
     return MI_OK;
 }
 
+int32_t mi_verify_stage_pairs(mi_ctx *ctx, const mi_vk *vk, const VerifyStage &st, size_t extra_bytes, VerifyPairs *out) {
+    const size_t n = st.n();
+    const u32 ns = st.ns, np = verify_pairs_per_proof(st.nc);
+    WsCut cut;
+    const size_t off_scal = cut.take(n * ns * sizeof(Fr)), off_p = cut.take(n * np * sizeof(G1Aff)), off_q = cut.take(n * np * sizeof(G2Aff));
+    const size_t off_ml = cut.take(n * np * sizeof(Fp12)), off_fl = cut.take(n), off_vd = cut.take(n), off_extra = cut.take(extra_bytes);
+    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], cut.total));
+    char *ws = (char *)ctx->ws[WS_VERIFY].p;
+    // ---- kSum: the scalar part through the G1 MSM over the resident K[1..], the rest on the host
+    out->P.resize(n * np), out->Q.resize(n * np);
+    MI_TRY(mi_verify_put_scalars(ctx, st, (Fr *)(ws + off_scal)));
+    for (size_t i = 0; i < n; i++) {
+        G1Aff msm{Fp::zero(), Fp::zero()};   // no MSM runs for a malformed proof
+        if (ns && !st.flags[i]) MI_TRY(mi_verify_msm(ctx, vk->k_dev, (const Fr *)(ws + off_scal) + i * ns, ns, 0, &msm));
+        verify_assemble(st.key, st.proofs[i], !st.flags[i], msm, &out->P[i * np], &out->Q[i * np]);
+    }
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_p, out->P.data(), n * np * sizeof(G1Aff), hipMemcpyHostToDevice, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_q, out->Q.data(), n * np * sizeof(G2Aff), hipMemcpyHostToDevice, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, st.flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
+    out->np = np;
+    out->p = (G1Aff *)(ws + off_p); out->q = (G2Aff *)(ws + off_q); out->ml = (Fp12 *)(ws + off_ml);
+    out->flags = (uint8_t *)(ws + off_fl); out->verdicts = (uint8_t *)(ws + off_vd); out->extra = extra_bytes ? (uint8_t *)(ws + off_extra) : nullptr;
+    return MI_OK;
+}
+
 int32_t mi_verify_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, uint8_t *verdicts, const uint8_t *decode_malformed,
                       const Fr *pub_dev) {
     VerifyStage st;   // host: flags (range and curve checks), scalars
     MI_TRY(mi_verify_open(ctx, "verify: ", vk, in, n, verdicts || !n, decode_malformed, &st, pub_dev));
     if (!n) return MI_OK;
-    const u32 ns = st.ns, np = verify_pairs_per_proof(st.nc);
-    WsCut cut;
-    const size_t off_scal = cut.take(n * ns * sizeof(Fr)), off_p = cut.take(n * np * sizeof(G1Aff)), off_q = cut.take(n * np * sizeof(G2Aff));
-    const size_t off_ml = cut.take(n * np * sizeof(Fp12)), off_fl = cut.take(n), off_vd = cut.take(n);
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], cut.total));
-    char *ws = (char *)ctx->ws[WS_VERIFY].p;
-    // ---- kSum: the scalar part through the G1 MSM over the resident K[1..], the rest on the host
-    std::vector<G1Aff> P(n * np);
-    std::vector<G2Aff> Q(n * np);
-    MI_TRY(mi_verify_put_scalars(ctx, st, (Fr *)(ws + off_scal)));
-    for (size_t i = 0; i < n; i++) {
-        G1Aff msm{Fp::zero(), Fp::zero()};   // no MSM runs for a malformed proof
-        if (ns && !st.flags[i]) MI_TRY(mi_verify_msm(ctx, vk->k_dev, (const Fr *)(ws + off_scal) + i * ns, ns, 0, &msm));
-        verify_assemble(st.key, st.proofs[i], !st.flags[i], msm, &P[i * np], &Q[i * np]);
-    }
+    VerifyPairs d;
+    MI_TRY(mi_verify_stage_pairs(ctx, vk, st, 0, &d));
     // ---- device: Bs check (its answer joins the flags there, for the judgement), Miller loops, judgement
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_p, P.data(), P.size() * sizeof(G1Aff), hipMemcpyHostToDevice, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_q, Q.data(), Q.size() * sizeof(G2Aff), hipMemcpyHostToDevice, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, st.flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
-    MI_TRY(mi_verify_g2_check_enqueue(ctx, (const G2Aff *)(ws + off_q), np, (uint8_t *)(ws + off_fl), n));
-    MI_TRY(mi_pairing_enqueue(ctx, (const G1Aff *)(ws + off_p), (const G2Aff *)(ws + off_q), n * np, (Fp12 *)(ws + off_ml), false));
-    MI_TRY(mi_launch64(ctx, k_verify_judge, n, (const Fp12 *)(ws + off_ml), np, vk->e_alpha_beta_dev, (const uint8_t *)(ws + off_fl),
-                       (uint8_t *)(ws + off_vd), n));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(verdicts, ws + off_vd, n, hipMemcpyDeviceToHost, ctx->stream));
+    MI_TRY(mi_verify_g2_check_enqueue(ctx, d.q, d.np, d.flags, n));
+    MI_TRY(mi_pairing_enqueue(ctx, d.p, d.q, n * d.np, d.ml, false));
+    MI_TRY(mi_launch64(ctx, k_verify_judge, n, (const Fp12 *)d.ml, d.np, (const Fp12 *)vk->e_alpha_beta_dev, (const uint8_t *)d.flags, d.verdicts, n));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(verdicts, d.verdicts, n, hipMemcpyDeviceToHost, ctx->stream));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MI_OK;
 }

@@ -1,5 +1,5 @@
-// groth16.Verify from the bytes of a proof (include/mi355x_groth16_verify_bytes.h): decode and hash on the device, then one of the three
-// bodies of the verifier over the decoded records, and the three debug entry points over the same arithmetic.
+// groth16.Verify from the bytes of a proof (include/mi355x_groth16_verify_bytes.h): decode and hash on the device, then one of the four
+// bodies of the verifier (verify_internal.h) over the decoded records, and the three debug entry points over the same arithmetic.
 //
 // One batch, every launch on ctx->stream:
 //   host      the framing (proof_len, null pointers: MI_EINVAL), the count inside each proof against the key's (-> malformed)
@@ -8,9 +8,9 @@
 //   k_verify_hash  one lane per proof: commitment_values and fold_challenge from the decoded commitments, the public inputs and the
 //                  key's committed lists (sha256_h2f.cuh); a proof that did not decode is skipped
 //   host      the decoded records come back as mi_verify_input (verify_bytes_decode, the one front of the entry points below) and go
-//             through mi_verify_run, the body of mi_groth16_verify_batch, or for mi_groth16_verify_bytes_combined through
-//             mi_verify_combined_run (verify_combined.hip), for mi_groth16_verify_bytes_locate through mi_verify_locate_run; a proof that did not decode enters either as malformed and none of its
-//             words is read.
+//             through the body of their entry point: mi_verify_run (verify.hip), mi_verify_run_wave (verify_wave.hip),
+//             mi_verify_combined_run (verify_combined.hip) or mi_verify_locate_run (verify_locate.hip); a proof that did not decode
+//             enters any of them as malformed and none of its words is read.
 // Two decode kernels rather than one: a G2 lane does four times the work of a G1 lane, and in one wave the G1 lanes would wait for it.
 // Everything of a batch lives in ONE grow-only workspace (WS_VERIFY_BYTES): nothing is allocated in steady state.
 #include "verify_internal.h"
@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(64, 1) k_hash_to_field(const uint8_t *msgs, si
     out[i] = hash_to_field(d, dst_len, msgs + i * msg_len, msg_len);
 }
 
-// A batch decoded: dec, the records as mi_verify_input for either body of the verifier, over the vectors that hold their words, and
+// A batch decoded: dec, the records as mi_verify_input for any body of the verifier, over the vectors that hold their words, and
 // bad[i] != 0 where proof i did not decode (the bodies' decode_malformed)
 struct Decoded {
     std::vector<G1Aff> g1;

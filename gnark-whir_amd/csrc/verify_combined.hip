@@ -5,11 +5,12 @@
 // One batch, every launch on ctx->stream:
 //   host      mi_verify_open (verify.hip): the argument checks, then the VerifyStage of pairing_ops.cuh -- the range and curve checks of
 //             every proof (verify_well_formed) and the scalar matrix
-//   k_verify_g2_check (verify.hip)   Bs of every proof that passed them -> with the host's flags, the lowest malformed index.  If there
-//             is one the batch ends here with verdict 3: nothing below runs.
-//   host      the coefficients r_i (one SHA-256 each)
-//   k_verify_combine_scalars / k_verify_combine_reduce   sum_i r_i s_ij for every column j of the scalar matrix, S = sum_i r_i, and
-//             r_i c_i^k for the Pedersen equation: blocks over the proofs, one partial per (block, column), then one sum per column
+//   k_verify_g2_check (verify.hip)   Bs of every proof that passed them -> with the host's flags, the lowest malformed index
+//             (mi_verify_flag_bs).  If there is one the batch ends here with verdict 3: nothing below runs.
+//   host      the coefficients r_i (one SHA-256 each) and the inputs of the combination, up (mi_verify_put_coeffs)
+//   k_verify_locate_colsums / _reduce (verify_locate.hip)   the batch as the root of that file's tree: sum_i r_i s_ij for every column j
+//             of the scalar matrix, S = sum_i r_i, and r_i c_i^k for the Pedersen equation: blocks over the proofs, one partial per
+//             (block, column), then one sum per column
 //   MSMs      2 without commitments (1 for a key without a scalar column), 4 + n_commitments with: over the resident K[1..] with the
 //             column sums, over Krs_i, over all C_ik, over pok_i with r_i, and per k over C_.k with r_i c_i^k (msm.hip; a base at infinity, (0, 0), contributes nothing there:
 //             both of its level-1 additions skip it).  Their results come back to the host, which forms the tail pairs
@@ -24,7 +25,7 @@
 // the verifier runs, and the 64 bytes per proof that cross memory between the two are nothing beside a Miller loop.
 // Everything of a batch lives in ONE grow-only workspace (WS_VERIFY, which mi_groth16_verify_batch uses too: the calls of a context
 // are serial on its stream), laid out by a WsCut: nothing is allocated in steady state.  Launches go through mi_launch64, the MSMs
-// through mi_verify_msm (verify_internal.h).
+// through mi_verify_msm (verify_internal.h).  The front of this body is the locating body's too and is defined here, once.
 #include "verify_internal.h"
 #include "combine_coeff.cuh"
 #include <sys/random.h>
@@ -34,49 +35,6 @@
 
 namespace {
 
-#define MI_COMBINE_MAX_BLOCKS 256   // blocks over the proofs in k_verify_combine_scalars: 2^24 proofs are 1024 per lane
-
-// scal: n x ns Montgomery scalars, row-major.  r: n coefficients as canonical Fr records (below 2^128).  fold: n challenges, or null when
-// the key has at most one commitment (c_i = 1).  nb * (ns + 1) blocks: block j * nb + b adds up column j over the proofs b * 64 + lane,
-// + nb * 64, ...; column ns is S, and its blocks also write r_i c_i^k (Montgomery) and r_i again (canonical) at [k * n + i] for the
-// MSMs over the commitments.  partial[j * nb + b].  Exact field arithmetic: the order of the additions does not reach the result.
-__global__ void __launch_bounds__(64, 1) k_verify_combine_scalars(const Fr *scal, u32 ns, const Fr *r, const Fr *fold, u32 nc, size_t n, u32 nb,
-                                                                  Fr *partial, Fr *rc, Fr *rrep) {
-    __shared__ Fr sh[64];
-    const u32 j = blockIdx.x / nb, b = blockIdx.x % nb, lane = threadIdx.x;
-    Fr acc = Fr::zero();
-    for (size_t i = (size_t)b * 64 + lane; i < n; i += (size_t)nb * 64) {
-        const Fr plain = r[i];
-        const Fr ri = fe_to_mont(plain);
-        if (j < ns) {
-            acc = acc + ri * scal[i * ns + j];
-        } else {
-            acc = acc + ri;
-            const Fr c = fold ? fold[i] : Fr::one();
-            Fr pw = ri;
-            for (u32 k = 0; k < nc; k++) {
-                rc[(size_t)k * n + i] = pw;
-                rrep[(size_t)k * n + i] = plain;
-                pw = pw * c;
-            }
-        }
-    }
-    sh[lane] = acc;
-    __syncthreads();
-    for (u32 s = 32; s > 0; s >>= 1) {
-        if (lane < s) sh[lane] = sh[lane] + sh[lane + s];
-        __syncthreads();
-    }
-    if (lane == 0) partial[(size_t)j * nb + b] = sh[0];
-}
-// sums[j] = the sum of column j's nb partials
-__global__ void __launch_bounds__(64, 1) k_verify_combine_reduce(const Fr *partial, u32 nb, Fr *sums, u32 n_cols) {
-    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_cols) return;
-    Fr acc = Fr::zero();
-    for (u32 b = 0; b < nb; b++) acc = acc + partial[(size_t)j * nb + b];
-    sums[j] = acc;
-}
 // out[i] = k_i p[i]; k_i = the four words at k + i * stride (stride 8: canonical Fr records below 2^128).  out may be p.
 __global__ void __launch_bounds__(64, 1) k_g1_scale128(const G1Aff *p, const u32 *k, u32 stride, G1Aff *out, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -125,28 +83,71 @@ int32_t mi_g1_scale128_enqueue(mi_ctx *ctx, const G1Aff *p_dev, const u32 *k_dev
     return mi_launch64(ctx, k_g1_scale128, n, p_dev, k_dev, stride, out_dev, n);
 }
 
+// ---------------------------------------------------------------- the front of the two coefficient bodies (verify_internal.h)
+int32_t mi_verify_refuse_msm_pairs(mi_ctx *ctx, const mi_vk *vk, bool args_ok, size_t n, const char *msg) {
+    if (ctx && vk && args_ok && n <= ((size_t)1 << 24) && (uint64_t)n * vk->n_commitments > MI_MSM_MAX_PAIRS) MI_FAIL(ctx, MI_EINVAL, msg);
+    return MI_OK;
+}
+int32_t mi_verify_seed(mi_ctx *ctx, const char *who, const uint8_t *&seed, uint8_t own[32]) {
+    if (seed) return MI_OK;
+    for (size_t got = 0; got < 32;) {
+        const ssize_t k = getrandom(own + got, 32 - got, 0);
+        if (k <= 0) MI_FAIL(ctx, MI_ENODEV, std::string(who) + "the operating system gave no randomness for the seed (getrandom)");
+        got += (size_t)k;
+    }
+    seed = own;
+    return MI_OK;
+}
+int32_t mi_verify_flag_bs(mi_ctx *ctx, VerifyStage &st, G2Aff *Q, G2Aff *q_dev, uint8_t *flags_dev) {
+    const size_t n = st.n();
+    for (size_t i = 0; i < n; i++) Q[i] = st.flags[i] ? G2Aff{Fp2::zero(), Fp2::zero()} : *st.proofs[i].bs;
+    MI_TRY(mi_verify_upload(ctx, q_dev, Q, n * sizeof(G2Aff)));
+    MI_TRY(mi_verify_upload(ctx, flags_dev, st.flags.data(), n));
+    MI_TRY(mi_verify_g2_check_enqueue(ctx, q_dev, 1, flags_dev, n));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(st.flags.data(), flags_dev, n, hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    st.merge(st.flags.data());
+    return MI_OK;
+}
+int32_t mi_verify_put_coeffs(mi_ctx *ctx, const VerifyStage &st, const mi_verify_input *in, const uint8_t *seed, bool cm_by_column, VerifyCoeffs *h,
+                             char *ws, const VerifyCoeffsAt &at) {
+    const size_t n = st.n();
+    const u32 nc = st.nc;
+    const G1Aff inf{Fp::zero(), Fp::zero()};
+    h->r.assign(n, Fr::zero()), h->fold.assign(nc > 1 ? n : 0, Fr::zero());
+    h->p.assign(n, inf), h->krs.assign(n, inf), h->pok.assign(nc ? n : 0, inf), h->cm.assign(n * nc, inf);
+    for (size_t i = 0; i < n; i++) {
+        if (st.flags[i]) continue;
+        combine_coefficient(seed, n, i, h->r[i].l);
+        if (nc > 1) std::memcpy(&h->fold[i], in[i].fold_challenge, sizeof(Fr));
+        std::memcpy(&h->p[i], &in[i].proof.ar, sizeof(G1Aff));
+        std::memcpy(&h->krs[i], &in[i].proof.krs, sizeof(G1Aff));
+        if (nc) std::memcpy(&h->pok[i], in[i].pok, sizeof(G1Aff));
+        for (u32 k = 0; k < nc; k++) std::memcpy(&h->cm[cm_by_column ? k * n + i : i * nc + k], &in[i].commitments[k], sizeof(G1Aff));
+    }
+    MI_TRY(mi_verify_put_scalars(ctx, st, (Fr *)(ws + at.scal)));
+    MI_TRY(mi_verify_upload(ctx, ws + at.r, h->r.data(), n * sizeof(Fr)));
+    MI_TRY(mi_verify_upload(ctx, ws + at.fold, h->fold.data(), h->fold.size() * sizeof(Fr)));
+    MI_TRY(mi_verify_upload(ctx, ws + at.krs, h->krs.data(), n * sizeof(G1Aff)));
+    MI_TRY(mi_verify_upload(ctx, ws + at.pok, h->pok.data(), h->pok.size() * sizeof(G1Aff)));
+    MI_TRY(mi_verify_upload(ctx, ws + at.cm, h->cm.data(), h->cm.size() * sizeof(G1Aff)));
+    return mi_verify_upload(ctx, ws + at.p, h->p.data(), n * sizeof(G1Aff));
+}
+
 int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdict,
                                uint64_t *first_malformed, const uint8_t *decode_malformed, const Fr *pub_dev) {
-    // refused where it always was, between mi_verify_open's checks of ctx, vk, in, verdict and n and those of the proofs' pointers
-    if (ctx && vk && in && verdict && n <= ((size_t)1 << 24) && (uint64_t)n * vk->n_commitments > MI_MSM_MAX_PAIRS)
-        MI_FAIL(ctx, MI_EINVAL, "verify combined: n * n_commitments above MI_MSM_MAX_PAIRS (one MSM runs over every commitment of the batch)");
+    MI_TRY(mi_verify_refuse_msm_pairs(ctx, vk, in && verdict, n,
+                                      "verify combined: n * n_commitments above MI_MSM_MAX_PAIRS (one MSM runs over every commitment of the batch)"));
     VerifyStage st;   // host: the range and curve checks of every proof, the scalar matrix
     MI_TRY(mi_verify_open(ctx, "verify combined: ", vk, in, n, verdict != nullptr, decode_malformed, &st, pub_dev));
     const u32 nc = st.nc, ns = st.ns, np = verify_combined_tail_pairs(nc);
     uint8_t own_seed[32];
-    if (!seed && n) {
-        for (size_t got = 0; got < sizeof(own_seed);) {
-            const ssize_t k = getrandom(own_seed + got, sizeof(own_seed) - got, 0);
-            if (k <= 0) MI_FAIL(ctx, MI_ENODEV, "verify combined: the operating system gave no randomness for the seed (getrandom)");
-            got += (size_t)k;
-        }
-        seed = own_seed;
-    }
+    if (n) MI_TRY(mi_verify_seed(ctx, "verify combined: ", seed, own_seed));
     if (first_malformed) *first_malformed = n;
     if (!n) { *verdict = MI_VERIFY_OK; return MI_OK; }
 
-    // ---- workspace
-    const u32 nb = mi_blocks_of(n, 64) < MI_COMBINE_MAX_BLOCKS ? mi_blocks_of(n, 64) : MI_COMBINE_MAX_BLOCKS;
+    // ---- workspace.  The batch is the root of the locating verifier's tree: its column sums are that node's
+    const u32 root = LocateTree(n).L, nb = mi_verify_node_blocks(root, n);
     const size_t lvl0 = product_level(n + np), lvl1 = product_level(lvl0);
     WsCut cut;
     const size_t off_scal = cut.take(n * ns * sizeof(Fr)), off_r = cut.take(n * sizeof(Fr)), off_fold = cut.take(n * sizeof(Fr));
@@ -160,15 +161,8 @@ int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_inp
     char *ws = (char *)ctx->ws[WS_VERIFY].p;
 
     // ---- malformed first: Bs of the proofs that passed the host's checks (infinity stands in for the others)
-    std::vector<G2Aff> Q(n + np, G2Aff{Fp2::zero(), Fp2::zero()});
-    for (size_t i = 0; i < n; i++)
-        if (!st.flags[i]) Q[i] = *st.proofs[i].bs;
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_q, Q.data(), n * sizeof(G2Aff), hipMemcpyHostToDevice, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, st.flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
-    MI_TRY(mi_verify_g2_check_enqueue(ctx, (const G2Aff *)(ws + off_q), 1, (uint8_t *)(ws + off_fl), n));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(st.flags.data(), ws + off_fl, n, hipMemcpyDeviceToHost, ctx->stream));
-    MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    st.merge(st.flags.data());
+    std::vector<G2Aff> Q(n);
+    MI_TRY(mi_verify_flag_bs(ctx, st, Q.data(), (G2Aff *)(ws + off_q), (uint8_t *)(ws + off_fl)));
     if (st.first_flagged < n) {
         *verdict = MI_VERIFY_MALFORMED;
         if (first_malformed) *first_malformed = st.first_flagged;
@@ -176,32 +170,12 @@ int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_inp
     }
 
     // ---- host: the coefficients and the inputs of the combination, the points in the MSMs' order (commitments by column: [k][i])
-    std::vector<Fr> r(n, Fr::zero()), fold(nc > 1 ? n : 0);
-    std::vector<G1Aff> krs(n), pok(nc ? n : 0), cm((size_t)n * nc), P(n + np);
-    for (size_t i = 0; i < n; i++) {
-        combine_coefficient(seed, n, i, r[i].l);
-        if (nc > 1) std::memcpy(&fold[i], in[i].fold_challenge, sizeof(Fr));
-        std::memcpy(&P[i], &in[i].proof.ar, sizeof(G1Aff));
-        std::memcpy(&krs[i], &in[i].proof.krs, sizeof(G1Aff));
-        if (nc) std::memcpy(&pok[i], in[i].pok, sizeof(G1Aff));
-        for (u32 k = 0; k < nc; k++) std::memcpy(&cm[(size_t)k * n + i], &in[i].commitments[k], sizeof(G1Aff));
-    }
-    auto up = [&](size_t off, const void *src, size_t bytes) -> int32_t {
-        if (bytes) MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return MI_OK;
-    };
-    MI_TRY(mi_verify_put_scalars(ctx, st, (Fr *)(ws + off_scal)));
-    MI_TRY(up(off_r, r.data(), n * sizeof(Fr)));
-    MI_TRY(up(off_fold, fold.data(), fold.size() * sizeof(Fr)));
-    MI_TRY(up(off_krs, krs.data(), n * sizeof(G1Aff)));
-    MI_TRY(up(off_pok, pok.data(), pok.size() * sizeof(G1Aff)));
-    MI_TRY(up(off_cm, cm.data(), cm.size() * sizeof(G1Aff)));
-    MI_TRY(up(off_p, P.data(), n * sizeof(G1Aff)));
+    VerifyCoeffs h;
+    MI_TRY(mi_verify_put_coeffs(ctx, st, in, seed, true, &h, ws, VerifyCoeffsAt{off_scal, off_r, off_fold, off_krs, off_pok, off_cm, off_p}));
 
-    // ---- device: the scalar combination; S comes back for S K[0] and S alpha
-    MI_TRY(mi_launch64(ctx, k_verify_combine_scalars, (size_t)nb * (ns + 1) * 64, (const Fr *)(ws + off_scal), ns, (const Fr *)(ws + off_r),
-                       nc > 1 ? (const Fr *)(ws + off_fold) : nullptr, nc, n, nb, (Fr *)(ws + off_part), (Fr *)(ws + off_rc), (Fr *)(ws + off_rrep)));
-    MI_TRY(mi_launch64(ctx, k_verify_combine_reduce, ns + 1, (const Fr *)(ws + off_part), nb, (Fr *)(ws + off_sum), ns + 1));
+    // ---- device: the scalar combination (the root's column sums, with r_i c_i^k written beside S); S comes back for S K[0] and S alpha
+    MI_TRY(mi_verify_colsums_enqueue(ctx, (const Fr *)(ws + off_scal), ns, (const Fr *)(ws + off_r), n, root, nullptr, 1, (Fr *)(ws + off_part), (Fr *)(ws + off_sum),
+                                     nc > 1 ? (const Fr *)(ws + off_fold) : nullptr, nc, (Fr *)(ws + off_rc), (Fr *)(ws + off_rrep)));
     VerifyCombinedSums sums{};
     MI_CHECK_HIP(ctx, hipMemcpyAsync(&sums.s, ws + off_sum + (size_t)ns * sizeof(Fr), sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -220,9 +194,11 @@ int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_inp
     }
 
     // ---- the tail pairs, r_i Ar_i, the Miller loops, the two products, their final exponentiations, the verdict
-    verify_combined_assemble(st.key, vk->alpha1, vk->beta2, sums, &P[n], &Q[n]);
-    MI_TRY(up(off_p + n * sizeof(G1Aff), &P[n], np * sizeof(G1Aff)));
-    MI_TRY(up(off_q + n * sizeof(G2Aff), &Q[n], np * sizeof(G2Aff)));
+    std::vector<G1Aff> tp(np);
+    std::vector<G2Aff> tq(np);
+    verify_combined_assemble(st.key, vk->alpha1, vk->beta2, sums, tp.data(), tq.data());
+    MI_TRY(mi_verify_upload(ctx, ws + off_p + n * sizeof(G1Aff), tp.data(), np * sizeof(G1Aff)));
+    MI_TRY(mi_verify_upload(ctx, ws + off_q + n * sizeof(G2Aff), tq.data(), np * sizeof(G2Aff)));
     MI_TRY(mi_launch64(ctx, k_g1_scale128, n, (const G1Aff *)(ws + off_p), (const u32 *)(ws + off_r), 8u, (G1Aff *)(ws + off_p), n));
     Fp12 *ml = (Fp12 *)(ws + off_ml), *res = (Fp12 *)(ws + off_res);
     MI_TRY(mi_pairing_enqueue(ctx, (const G1Aff *)(ws + off_p), (const G2Aff *)(ws + off_q), n + np, ml, false));

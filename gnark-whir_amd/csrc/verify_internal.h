@@ -1,6 +1,9 @@
-// What verify.hip, verify_bytes.hip, verify_combined.hip, verify_locate.hip and verify_wave.hip share (not part of the C-ABI): the resident key, the opening of a batch
-// (mi_verify_open: argument checks, proof references, the VerifyStage of pairing_ops.cuh), the four bodies that judge it, the launches of
-// verify.hip's kernels that the combined body reuses, and three helpers: WsCut (a workspace's layout), mi_launch64, mi_verify_msm.
+// What the verifier's files share (not part of the C-ABI): the resident key and the one structure of a batch.  mi_verify_open (argument
+// checks under the body's message prefix, proof references, the VerifyStage of pairing_ops.cuh) opens it for one of FOUR bodies:
+//   a verdict per proof    mi_verify_run ("verify: ") and mi_verify_run_wave ("verify wave: ") start from mi_verify_stage_pairs
+//   the coefficients r_i   mi_verify_combined_run ("verify combined: ") and mi_verify_locate_run ("verify locate: ") start from
+//                          mi_verify_refuse_msm_pairs, mi_verify_seed, mi_verify_flag_bs and mi_verify_put_coeffs, and share the column sums
+// verify_bytes.hip decodes a batch and calls the same bodies.  Then the launches other files reuse, WsCut, mi_launch64 and small helpers.
 #pragma once
 #include "ctx.h"
 #include "../../include/mi355x_groth16_verify.h"
@@ -23,10 +26,10 @@ struct mi_vk {
     std::vector<uint32_t> pc_off, pc_idx;
 };
 
-// How both bodies start: the checks of ctx, vk, in, n and the pointers of every proof (messages under `who`, "verify: " or
-// "verify combined: "; has_verdict = the caller's verdict pointer passes its own rule), then *st over the proofs' references.
+// How every body starts: the checks of ctx, vk, in, n and the pointers of every proof (messages under `who`, the body's prefix;
+// has_verdict = the caller's verdict pointer passes its own rule), then *st over the proofs' references.
 // decode_malformed (may be null): n bytes; a non-zero byte makes proof i malformed before any of its words is read (verify_bytes.hip).
-// pub_dev (may be null; the three bodies pass it on): VerifyStage's device-resident public block.  With it in[i].public_inputs is not read.
+// pub_dev (may be null; the bodies pass it on): VerifyStage's device-resident public block.  With it in[i].public_inputs is not read.
 int32_t mi_verify_open(mi_ctx *ctx, const char *who, const mi_vk *vk, const mi_verify_input *in, size_t n, bool has_verdict,
                        const uint8_t *decode_malformed, VerifyStage *st, const Fr *pub_dev = nullptr);
 // mi_groth16_verify_batch's body (verify.hip)
@@ -42,6 +45,44 @@ int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_inp
 // mi_groth16_verify_locate's body (verify_locate.hip): one verdict per proof.  seed and stats may be null.
 int32_t mi_verify_locate_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdicts,
                              mi_verify_locate_stats *stats, const uint8_t *decode_malformed, const Fr *pub_dev = nullptr);
+// ---- the host half of the two per-proof bodies (verify.hip), all on ctx->stream: WS_VERIFY cut as scal | p | q | ml | flags | verdicts |
+// extra, the scalars up, one mi_verify_msm per well-formed proof and verify_assemble, then P, Q and the stage's flags up.  P and Q are
+// the host copies the uploads read: they live until the body's last synchronise.  extra: extra_bytes of the body's own, null without.
+struct VerifyPairs {
+    u32 np = 0;   // pairs per proof
+    std::vector<G1Aff> P;
+    std::vector<G2Aff> Q;
+    G1Aff *p = nullptr;
+    G2Aff *q = nullptr;
+    Fp12 *ml = nullptr;
+    uint8_t *flags = nullptr, *verdicts = nullptr, *extra = nullptr;
+};
+int32_t mi_verify_stage_pairs(mi_ctx *ctx, const mi_vk *vk, const VerifyStage &st, size_t extra_bytes, VerifyPairs *out);
+// ---- the front of the two coefficient bodies (verify_combined.hip), in the order they call it.  The refusal of n * n_commitments above
+// MI_MSM_MAX_PAIRS under msg, the body's own text, before mi_verify_open and under its first checks (args_ok: in and the verdict pointer)
+int32_t mi_verify_refuse_msm_pairs(mi_ctx *ctx, const mi_vk *vk, bool args_ok, size_t n, const char *msg);
+// seed stays, or becomes own filled with 32 bytes of the operating system's (MI_ENODEV under `who`)
+int32_t mi_verify_seed(mi_ctx *ctx, const char *who, const uint8_t *&seed, uint8_t own[32]);
+// Malformed first: Q[i] = Bs of proof i where the host's checks passed, else infinity (Q: n host entries); Q and the flags up to the
+// body's regions, k_verify_g2_check, the flags back, synchronise, st.merge: st.flags and st.first_flagged are final on return
+int32_t mi_verify_flag_bs(mi_ctx *ctx, VerifyStage &st, G2Aff *Q, G2Aff *q_dev, uint8_t *flags_dev);
+// The inputs of the combination: r_i = combine_coefficient(seed, n, i), the fold challenges (more than one commitment), Ar (p), Krs, pok
+// and the commitments, [k][i] (cm_by_column) or [i][k]; a proof st flags keeps coefficient 0 and infinities.  Then the uploads, the
+// scalar matrix first, to the offsets `at` in the body's workspace ws.  *h: the host copies, alive until the body's last synchronise.
+struct VerifyCoeffs {
+    std::vector<Fr> r, fold;
+    std::vector<G1Aff> p, krs, pok, cm;
+};
+struct VerifyCoeffsAt { size_t scal, r, fold, krs, pok, cm, p; };
+int32_t mi_verify_put_coeffs(mi_ctx *ctx, const VerifyStage &st, const mi_verify_input *in, const uint8_t *seed, bool cm_by_column, VerifyCoeffs *h,
+                             char *ws, const VerifyCoeffsAt &at);
+// ---- the column sums of both (verify_locate.hip): sums[t (ns + 1) + j] = sum of r_i scal[i ns + j] over the proofs i of node (level,
+// nodes_dev[t]) of the tree over n proofs, column ns = sum of r_i; nodes_dev == null: node t is t.  One launch over (node, column,
+// block) into partial (m (ns + 1) mi_verify_node_blocks(level, n) records), one reduce.  rc (may be null) with rrep, fold (null: c_i =
+// 1) and nc: the column-ns blocks also write rc[k n + i] = r_i c_i^k (Montgomery) and rrep[k n + i] = r_i, k < nc.
+u32 mi_verify_node_blocks(u32 level, size_t n);
+int32_t mi_verify_colsums_enqueue(mi_ctx *ctx, const Fr *scal, u32 ns, const Fr *r, size_t n, u32 level, const u32 *nodes_dev, size_t m, Fr *partial, Fr *sums,
+                                  const Fr *fold = nullptr, u32 nc = 0, Fr *rc = nullptr, Fr *rrep = nullptr);
 // What mi_vk_load and mi_vk_load_stream (vkfile.hip) share: the resident key over a descriptor whose conditions the caller has checked.
 // k_dev_adopt (may be null): K[1 .. n_k) already on the device in an allocation of (n_k - 1) * 64 + 64 bytes, which the key takes
 // (and has freed when the call fails); without it K is uploaded from d->k.
@@ -91,5 +132,10 @@ inline int32_t mi_verify_put_scalars(mi_ctx *ctx, const VerifyStage &st, Fr *dst
         if (e > i) MI_CHECK_HIP(ctx, hipMemsetAsync(dst_dev + i * st.ns, 0, (e - i) * row, ctx->stream));
         i = e + 1;
     }
+    return MI_OK;
+}
+// bytes from the host to a device address on ctx->stream; no byte, no call
+inline int32_t mi_verify_upload(mi_ctx *ctx, void *dst_dev, const void *src, size_t bytes) {
+    if (bytes) MI_CHECK_HIP(ctx, hipMemcpyAsync(dst_dev, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return MI_OK;
 }

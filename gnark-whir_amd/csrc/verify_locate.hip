@@ -4,9 +4,10 @@
 // (tests/emu/emu_verify_locate.cpp) runs the same text.
 //
 // Once per batch, every launch on ctx->stream:
-//   host      mi_verify_open (verify.hip): the argument checks and the VerifyStage, as the other two bodies
-//   k_verify_g2_check (verify.hip)   Bs of every proof that passed the host's checks -> the malformed flags.  A malformed proof gets 3,
-//             coefficient 0 and infinities for all of its points from here on: none of its words reaches any arithmetic
+//   host      mi_verify_open (verify.hip): the argument checks and the VerifyStage, as the other three bodies.  The front from here to
+//             mi_verify_put_coeffs' uploads is the combined body's, the same functions (verify_combined.hip)
+//   k_verify_g2_check (verify.hip)   Bs of every proof that passed the host's checks -> the malformed flags (mi_verify_flag_bs).  A
+//             malformed proof gets 3, coefficient 0 and infinities for all of its points from here on: none of its words reaches any arithmetic
 //   host      the coefficients r_i of the combined verifier: combine_coefficient(seed, n, i), the full n and the original index
 //   k_g1_scale128, k_pairing_miller   r_i Ar_i, then ONE Miller launch over the n pairs -> ml[i] (one for a malformed proof)
 //   k_verify_locate_points   one lane per proof: r_i Krs_i, r_i sum_k C_ik, r_i pok_i and with more than one commitment (r_i c_i^k) C_ik
@@ -14,7 +15,8 @@
 //   k_fp12_product (verify_combined.hip)   per level over ml: EVERY level is kept, and no tail is inside the tree
 // Per round (m nodes of one level, LocatePlan::query):
 //   k_verify_locate_colsums / _reduce   sum_{i in node} r_i s_ij per (node, column), column ns = S: (node, column, block) -> partials
-//             -> one sum each.  The scalar matrix stays level 0 only; the cost is the rows the queried nodes cover
+//             -> one sum each.  The scalar matrix stays level 0 only; the cost is the rows the queried nodes cover.  The combined
+//             body runs the same pair over the root (mi_verify_colsums_enqueue)
 //   k_verify_locate_gather   the m nodes' values of every G1 tree, side by side for one copy
 //   host      per node one mi_verify_msm over the resident K[1..] with the node's column sums (host-synchronous: the known cost of a
 //             node); the other sums are those gathered out of the G1 trees; verify_combined_assemble, unchanged, gives the node's tail pairs
@@ -28,8 +30,6 @@
 // and the MSM's slots out their own way while the trees must live across rounds.  Everything of a batch, the rounds' regions sized for
 // the largest round the tree allows, is reserved in ONE mi_reserve before the first launch: a later growth would drop the trees.
 #include "verify_internal.h"
-#include "combine_coeff.cuh"
-#include <sys/random.h>
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -64,21 +64,34 @@ __global__ void __launch_bounds__(64, 1) k_g1_sum_level(const G1Aff *in, size_t 
     for (size_t s = 0; s < cnt; s++) p[s] = in[a * in_stride + at + s];
     out[a * out_stride + j] = g1_sum_run(p, cnt);
 }
-// k_verify_combine_scalars over the rows of nodes: block ((t (ns + 1) + j) bpn + b) adds up column j (column ns: the coefficients
-// themselves) over the proofs first + b * 64 + lane, + bpn * 64, ... of node (level, nodes[t]).  r: canonical records below 2^128, 0
-// for a malformed proof.  partial[blockIdx.x].  Exact field arithmetic: the order of the additions does not reach the result.
-__global__ void __launch_bounds__(64, 1) k_verify_locate_colsums(const Fr *scal, u32 ns, const Fr *r, size_t n, u32 level, const u32 *nodes, u32 bpn, Fr *partial) {
+// The column sums of both coefficient bodies (mi_verify_colsums_enqueue, verify_internal.h).  scal: n x ns Montgomery scalars,
+// row-major.  Block ((t (ns + 1) + j) bpn + b) adds up column j (column ns: the coefficients themselves, S) over the proofs first +
+// b * 64 + lane, + bpn * 64, ... of node (level, nodes[t]); nodes == null: node t.  r: canonical records below 2^128, 0 for a malformed
+// proof.  partial[blockIdx.x].  With rc (the combined body, one node: the root) the blocks of column ns also write r_i c_i^k
+// (Montgomery; c_i = fold[i], or 1 without fold) and r_i again (canonical) at [k * n + i], k < nc, for the MSMs over the commitments.
+// Exact field arithmetic: the order of the additions does not reach the result.
+__global__ void __launch_bounds__(64, 1) k_verify_locate_colsums(const Fr *scal, u32 ns, const Fr *r, size_t n, u32 level, const u32 *nodes, u32 bpn, Fr *partial,
+                                                                 const Fr *fold, u32 nc, Fr *rc, Fr *rrep) {
     __shared__ Fr sh[64];
     const u32 b = blockIdx.x % bpn, lane = threadIdx.x;
     const size_t tj = blockIdx.x / bpn, t = tj / (ns + 1);
     const u32 j = (u32)(tj % (ns + 1));
-    const size_t first = (size_t)nodes[t] << (3 * level);
+    const size_t first = (nodes ? (size_t)nodes[t] : t) << (3 * level);
     size_t end = first + ((size_t)1 << (3 * level));
     if (end > n) end = n;
     Fr acc = Fr::zero();
     for (size_t i = first + (size_t)b * 64 + lane; i < end; i += (size_t)bpn * 64) {
-        const Fr ri = fe_to_mont(r[i]);
+        const Fr plain = r[i];
+        const Fr ri = fe_to_mont(plain);
         acc = j < ns ? acc + ri * scal[i * ns + j] : acc + ri;
+        if (j < ns || !rc) continue;
+        const Fr c = fold ? fold[i] : Fr::one();
+        Fr pw = ri;
+        for (u32 k = 0; k < nc; k++) {
+            rc[(size_t)k * n + i] = pw;
+            rrep[(size_t)k * n + i] = plain;
+            pw = pw * c;
+        }
     }
     sh[lane] = acc;
     __syncthreads();
@@ -120,26 +133,12 @@ __global__ void __launch_bounds__(64, 1) k_verify_locate_judge(const Fp12 *res, 
     pass[t] = verify_combined_judge(&res[t * neq], neq > 1 ? &res[t * neq + 1] : nullptr) == 0 ? 1 : 0;
 }
 
-// blocks over the rows of one node of `level` in a tree over n proofs
-u32 node_blocks(u32 level, size_t n) {
-    size_t rows = (size_t)1 << (3 * level);
-    if (rows > n) rows = n;
-    const size_t b = mi_blocks_of(rows, 64);
-    return (u32)(b < MI_LOCATE_MAX_NODE_BLOCKS ? b : MI_LOCATE_MAX_NODE_BLOCKS);
-}
-int32_t colsums_enqueue(mi_ctx *ctx, const Fr *scal, u32 ns, const Fr *r, size_t n, u32 level, const u32 *nodes_dev, size_t m, Fr *partial, Fr *sums) {
-    const u32 bpn = node_blocks(level, n);
-    const size_t blocks = m * (ns + 1) * bpn;
-    if (blocks > 0x7fffffffu) MI_FAIL(ctx, MI_EINVAL, "verify locate: a round of " + std::to_string(m) + " nodes times the key's scalar columns exceeds one launch");
-    MI_TRY(mi_launch64(ctx, k_verify_locate_colsums, blocks * 64, scal, ns, r, n, level, nodes_dev, bpn, partial));
-    return mi_launch64(ctx, k_verify_locate_colsums_reduce, m * (ns + 1), (const Fr *)partial, bpn, sums, m * (ns + 1));
-}
 // the most nodes a round over this tree can have: the root alone, or every node of level 1
 size_t max_round_nodes(const LocateTree &t) { return t.L >= 2 ? t.cnt[1] : 1; }
 size_t max_round_partials(const LocateTree &t, u32 ns) {
     size_t most = 0;
     for (u32 l = 1; l <= t.L; l++) {
-        const size_t m = t.cnt[l] < max_round_nodes(t) ? t.cnt[l] : max_round_nodes(t), p = m * (ns + 1) * node_blocks(l, t.n);
+        const size_t m = t.cnt[l] < max_round_nodes(t) ? t.cnt[l] : max_round_nodes(t), p = m * (ns + 1) * mi_verify_node_blocks(l, t.n);
         most = p > most ? p : most;
     }
     return most;
@@ -147,23 +146,31 @@ size_t max_round_partials(const LocateTree &t, u32 ns) {
 
 }   // namespace
 
+// blocks over the rows of one node of `level` in a tree over n proofs
+u32 mi_verify_node_blocks(u32 level, size_t n) {
+    size_t rows = (size_t)1 << (3 * level);
+    if (rows > n) rows = n;
+    const size_t b = mi_blocks_of(rows, 64);
+    return (u32)(b < MI_LOCATE_MAX_NODE_BLOCKS ? b : MI_LOCATE_MAX_NODE_BLOCKS);
+}
+int32_t mi_verify_colsums_enqueue(mi_ctx *ctx, const Fr *scal, u32 ns, const Fr *r, size_t n, u32 level, const u32 *nodes_dev, size_t m, Fr *partial, Fr *sums,
+                                  const Fr *fold, u32 nc, Fr *rc, Fr *rrep) {
+    const u32 bpn = mi_verify_node_blocks(level, n);
+    const size_t blocks = m * (ns + 1) * bpn;
+    if (blocks > 0x7fffffffu) MI_FAIL(ctx, MI_EINVAL, "verify locate: a round of " + std::to_string(m) + " nodes times the key's scalar columns exceeds one launch");
+    MI_TRY(mi_launch64(ctx, k_verify_locate_colsums, blocks * 64, scal, ns, r, n, level, nodes_dev, bpn, partial, fold, nc, rc, rrep));
+    return mi_launch64(ctx, k_verify_locate_colsums_reduce, m * (ns + 1), (const Fr *)partial, bpn, sums, m * (ns + 1));
+}
+
 int32_t mi_verify_locate_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdicts,
                              mi_verify_locate_stats *stats, const uint8_t *decode_malformed, const Fr *pub_dev) {
     // the combined call's refusals, in its order
-    if (ctx && vk && in && verdicts && n <= ((size_t)1 << 24) && (uint64_t)n * vk->n_commitments > MI_MSM_MAX_PAIRS)
-        MI_FAIL(ctx, MI_EINVAL, "verify locate: n * n_commitments above MI_MSM_MAX_PAIRS");
+    MI_TRY(mi_verify_refuse_msm_pairs(ctx, vk, in && verdicts, n, "verify locate: n * n_commitments above MI_MSM_MAX_PAIRS"));
     VerifyStage st;
     MI_TRY(mi_verify_open(ctx, "verify locate: ", vk, in, n, verdicts || !n, decode_malformed, &st, pub_dev));
     const u32 nc = st.nc, ns = st.ns, np = verify_combined_tail_pairs(nc), na = verify_locate_arrays(nc), neq = nc ? 2 : 1;
     uint8_t own_seed[32];
-    if (!seed && n) {
-        for (size_t got = 0; got < sizeof(own_seed);) {
-            const ssize_t k = getrandom(own_seed + got, sizeof(own_seed) - got, 0);
-            if (k <= 0) MI_FAIL(ctx, MI_ENODEV, "verify locate: the operating system gave no randomness for the seed (getrandom)");
-            got += (size_t)k;
-        }
-        seed = own_seed;
-    }
+    if (n) MI_TRY(mi_verify_seed(ctx, "verify locate: ", seed, own_seed));
     auto report = [&](const LocateStats &s) {
         if (stats) *stats = mi_verify_locate_stats{s.rounds, s.nodes_tested, s.judged_alone, s.malformed, s.rejected};
     };
@@ -183,50 +190,25 @@ int32_t mi_verify_locate_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input
     const size_t off_gather = cut.take(m_max * na * sizeof(G1Aff));
     MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY_LOCATE], cut.total));
     char *ws = (char *)ctx->ws[WS_VERIFY_LOCATE].p;
-    auto up = [&](size_t off, const void *src, size_t bytes) -> int32_t {
-        if (bytes) MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return MI_OK;
-    };
 
     // ---- malformed first, per proof: Bs of the proofs that passed the host's checks (infinity stands in for the others)
     const G1Aff inf{Fp::zero(), Fp::zero()};
-    std::vector<G2Aff> Q(n, G2Aff{Fp2::zero(), Fp2::zero()});
-    for (size_t i = 0; i < n; i++)
-        if (!st.flags[i]) Q[i] = *st.proofs[i].bs;
-    MI_TRY(up(off_q, Q.data(), n * sizeof(G2Aff)));
-    MI_TRY(up(off_fl, st.flags.data(), n));
-    MI_TRY(mi_verify_g2_check_enqueue(ctx, (const G2Aff *)(ws + off_q), 1, (uint8_t *)(ws + off_fl), n));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(st.flags.data(), ws + off_fl, n, hipMemcpyDeviceToHost, ctx->stream));
-    MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    st.merge(st.flags.data());
-    for (size_t i = 0; i < n; i++)   // a proof the device's check flagged: its scalar row goes the way of its points
-        if (st.flags[i]) std::fill(st.scal.begin() + i * st.scal_cols, st.scal.begin() + (i + 1) * st.scal_cols, Fr::zero());
+    std::vector<G2Aff> Q(n);
+    MI_TRY(mi_verify_flag_bs(ctx, st, Q.data(), (G2Aff *)(ws + off_q), (uint8_t *)(ws + off_fl)));
     LocatePlan plan(n, st.flags.data(), ctx->locate_round_nodes);
     std::vector<uint8_t> out(n, MI_VERIFY_OK);
-    for (size_t i = 0; i < n; i++)
-        if (st.flags[i]) out[i] = MI_VERIFY_MALFORMED;
+    for (size_t i = 0; i < n; i++) {   // a proof the device's check flagged too: its scalar row and its Bs go the way of its points
+        if (!st.flags[i]) continue;
+        out[i] = MI_VERIFY_MALFORMED;
+        std::fill(st.scal.begin() + i * st.scal_cols, st.scal.begin() + (i + 1) * st.scal_cols, Fr::zero());
+        Q[i] = G2Aff{Fp2::zero(), Fp2::zero()};
+    }
 
     if (plan.start()) {
-        // ---- host: the coefficients and the points; a malformed proof has coefficient 0, infinities and a zero scalar row
-        std::vector<Fr> r(n, Fr::zero()), fold(nc > 1 ? n : 0, Fr::zero());
-        std::vector<G1Aff> P(n, inf), krs(n, inf), pok(nc ? n : 0, inf), cm((size_t)n * nc, inf);
-        for (size_t i = 0; i < n; i++) {
-            if (st.flags[i]) { Q[i] = G2Aff{Fp2::zero(), Fp2::zero()}; continue; }
-            combine_coefficient(seed, n, i, r[i].l);
-            if (nc > 1) std::memcpy(&fold[i], in[i].fold_challenge, sizeof(Fr));
-            std::memcpy(&P[i], &in[i].proof.ar, sizeof(G1Aff));
-            std::memcpy(&krs[i], &in[i].proof.krs, sizeof(G1Aff));
-            if (nc) std::memcpy(&pok[i], in[i].pok, sizeof(G1Aff));
-            if (nc) std::memcpy(&cm[i * nc], in[i].commitments, (size_t)nc * sizeof(G1Aff));
-        }
-        MI_TRY(up(off_q, Q.data(), n * sizeof(G2Aff)));   // again: a proof the device's check flagged becomes infinity
-        MI_TRY(mi_verify_put_scalars(ctx, st, (Fr *)(ws + off_scal)));
-        MI_TRY(up(off_r, r.data(), n * sizeof(Fr)));
-        MI_TRY(up(off_fold, fold.data(), fold.size() * sizeof(Fr)));
-        MI_TRY(up(off_krs, krs.data(), n * sizeof(G1Aff)));
-        MI_TRY(up(off_pok, pok.data(), pok.size() * sizeof(G1Aff)));
-        MI_TRY(up(off_cm, cm.data(), cm.size() * sizeof(G1Aff)));
-        MI_TRY(up(off_p, P.data(), n * sizeof(G1Aff)));
+        // ---- host: the coefficients and the points ([i][k]); a malformed proof has coefficient 0, infinities and a zero scalar row
+        VerifyCoeffs h;
+        MI_TRY(mi_verify_upload(ctx, ws + off_q, Q.data(), n * sizeof(G2Aff)));   // again: a proof the device's check flagged becomes infinity
+        MI_TRY(mi_verify_put_coeffs(ctx, st, in, seed, false, &h, ws, VerifyCoeffsAt{off_scal, off_r, off_fold, off_krs, off_pok, off_cm, off_p}));
 
         // ---- device, once per batch: the Miller values, the per-proof points, both kinds of tree
         Fp12 *ml = (Fp12 *)(ws + off_ml);
@@ -253,9 +235,9 @@ int32_t mi_verify_locate_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input
             const size_t m = plan.query.size();
             if (m > m_max) MI_FAIL(ctx, MI_EINVAL, "verify locate: a round larger than the tree allows");
             nodes.assign(plan.query.begin(), plan.query.end());
-            MI_TRY(up(off_nodes, nodes.data(), m * sizeof(u32)));
+            MI_TRY(mi_verify_upload(ctx, ws + off_nodes, nodes.data(), m * sizeof(u32)));
             const u32 *nodes_dev = (const u32 *)(ws + off_nodes);
-            MI_TRY(colsums_enqueue(ctx, (const Fr *)(ws + off_scal), ns, r_dev, n, l, nodes_dev, m, (Fr *)(ws + off_part), (Fr *)(ws + off_sum)));
+            MI_TRY(mi_verify_colsums_enqueue(ctx, (const Fr *)(ws + off_scal), ns, r_dev, n, l, nodes_dev, m, (Fr *)(ws + off_part), (Fr *)(ws + off_sum)));
             hsum.resize(m * (ns + 1));
             hpts.resize(na * m);
             MI_TRY(mi_launch64(ctx, k_verify_locate_gather, m * na, (const G1Aff *)(g1 + tree.off[l]), tree.total, nodes_dev, m, na, (G1Aff *)(ws + off_gather)));
@@ -276,8 +258,8 @@ int32_t mi_verify_locate_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input
                 sums.ck = ck.data();
                 verify_combined_assemble(st.key, vk->alpha1, vk->beta2, sums, &tp[t * np], &tq[t * np]);
             }
-            MI_TRY(up(off_tp, tp.data(), m * np * sizeof(G1Aff)));
-            MI_TRY(up(off_tq, tq.data(), m * np * sizeof(G2Aff)));
+            MI_TRY(mi_verify_upload(ctx, ws + off_tp, tp.data(), m * np * sizeof(G1Aff)));
+            MI_TRY(mi_verify_upload(ctx, ws + off_tq, tq.data(), m * np * sizeof(G2Aff)));
             Fp12 *tml = (Fp12 *)(ws + off_tml), *res = (Fp12 *)(ws + off_res);
             MI_TRY(mi_pairing_enqueue(ctx, (const G1Aff *)(ws + off_tp), (const G2Aff *)(ws + off_tq), m * np, tml, false));
             MI_TRY(mi_launch64(ctx, k_verify_locate_node_products, m * neq, (const Fp12 *)(ml + tree.off[l]), nodes_dev, (const Fp12 *)tml, np, neq, res, m));
@@ -339,9 +321,9 @@ int32_t mi_debug_locate_colsums_dev(mi_ctx *ctx, const mi_fr *scal_dev, uint32_t
                                     size_t m, mi_fr *sums_dev) {
     if (!ctx || (!scal_dev && ns) || !r_dev || !nodes_dev || !sums_dev || n == 0 || n > ((size_t)1 << 24) || m == 0 || m > n) return MI_EINVAL;
     if (level > LocateTree(n).L) return MI_EINVAL;
-    const size_t partials = m * (ns + 1) * node_blocks(level, n);
+    const size_t partials = m * (ns + 1) * mi_verify_node_blocks(level, n);
     MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY_LOCATE], partials * sizeof(Fr)));
-    return colsums_enqueue(ctx, (const Fr *)scal_dev, ns, (const Fr *)r_dev, n, level, nodes_dev, m, (Fr *)ctx->ws[WS_VERIFY_LOCATE].p, (Fr *)sums_dev);
+    return mi_verify_colsums_enqueue(ctx, (const Fr *)scal_dev, ns, (const Fr *)r_dev, n, level, nodes_dev, m, (Fr *)ctx->ws[WS_VERIFY_LOCATE].p, (Fr *)sums_dev);
 }
 int32_t mi_debug_set_locate_round_nodes(mi_ctx *ctx, uint32_t cap) {
     if (!ctx) return MI_EINVAL;

@@ -2,9 +2,9 @@
 // (verify.hip) -- same inputs, same verdict bytes, built for the latency of one proof.  The arithmetic is the phase text of
 // fp12_wave.cuh / pairing_wave.cuh; the image of a wave is MI_WAVE_IMAGE_BYTES of LDS, and every workgroup is ONE wave of 64 lanes.
 //
-// One batch, every launch on ctx->stream.  The host half is mi_verify_run's, call for call: mi_verify_open (argument checks, the
-// VerifyStage), mi_verify_put_scalars, one mi_verify_msm per well-formed proof, verify_assemble -- so a malformed proof is decided
-// exactly as there and its words stay out of the arithmetic.  Then
+// One batch, every launch on ctx->stream.  The host half is mi_verify_run's, the same function: mi_verify_open (argument checks, the
+// VerifyStage) under this body's prefix, then mi_verify_stage_pairs (verify.hip: the scalars, one mi_verify_msm per well-formed proof,
+// verify_assemble, the uploads) -- so a malformed proof is decided exactly as there and its words stay out of the arithmetic.  Then
 //   k_pairing_miller_wave   one workgroup per (proof, pair): a Miller loop, 384 B out.  The SAME launch carries the Bs checks, 64 proofs
 //                           per workgroup and one lane each (wave_bs_in_subgroup: the 63-bit endomorphism test), in front of the pairs:
 //                           the longest one-lane chain of the call starts first and runs beside the Miller waves, not before them
@@ -124,44 +124,26 @@ int32_t mi_verify_run_wave(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *
     MI_TRY(mi_verify_open(ctx, "verify wave: ", vk, in, n, verdicts || !n, decode_malformed, &st, pub_dev));
     if (split_ms) std::memset(split_ms, 0, MI_VERIFY_WAVE_SPLIT_PHASES * sizeof(float));
     if (!n) return MI_OK;
-    const u32 ns = st.ns, np = verify_pairs_per_proof(st.nc), n_eq = wave_equations(np);
-    WsCut cut;
-    const size_t off_scal = cut.take(n * ns * sizeof(Fr)), off_p = cut.take(n * np * sizeof(G1Aff)), off_q = cut.take(n * np * sizeof(G2Aff));
-    const size_t off_ml = cut.take(n * np * sizeof(Fp12)), off_fl = cut.take(n), off_vd = cut.take(n), off_pass = cut.take(n * n_eq);
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], cut.total));
-    char *ws = (char *)ctx->ws[WS_VERIFY].p;
+    const u32 np = verify_pairs_per_proof(st.nc), n_eq = wave_equations(np);
     SplitClock clk;
     MI_TRY(clk.open(ctx, split_ms != nullptr));
-    // ---- kSum: the scalar part through the G1 MSM over the resident K[1..], the rest on the host (as mi_verify_run)
-    std::vector<G1Aff> P(n * np);
-    std::vector<G2Aff> Q(n * np);
-    MI_TRY(mi_verify_put_scalars(ctx, st, (Fr *)(ws + off_scal)));
-    for (size_t i = 0; i < n; i++) {
-        G1Aff msm{Fp::zero(), Fp::zero()};   // no MSM runs for a malformed proof
-        if (ns && !st.flags[i]) MI_TRY(mi_verify_msm(ctx, vk->k_dev, (const Fr *)(ws + off_scal) + i * ns, ns, 0, &msm));
-        verify_assemble(st.key, st.proofs[i], !st.flags[i], msm, &P[i * np], &Q[i * np]);
-    }
+    VerifyPairs d;   // the host half, mi_verify_run's: a malformed proof is decided exactly as there; extra: the pass bytes
+    MI_TRY(mi_verify_stage_pairs(ctx, vk, st, n * n_eq, &d));
     const auto t1 = std::chrono::steady_clock::now();
     // ---- device: Bs checks and Miller loops in one launch, one judgement per equation, the verdict bytes
-    const G1Aff *p_dev = (const G1Aff *)(ws + off_p);
-    const G2Aff *q_dev = (const G2Aff *)(ws + off_q);
-    uint8_t *fl_dev = (uint8_t *)(ws + off_fl), *pass_dev = (uint8_t *)(ws + off_pass);
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_p, P.data(), P.size() * sizeof(G1Aff), hipMemcpyHostToDevice, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_q, Q.data(), Q.size() * sizeof(G2Aff), hipMemcpyHostToDevice, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, st.flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
     MI_TRY(clk.mark(ctx, 0));
     if (split_ms) {   // the split times the two halves of the first launch apart: two launches, the checks first
-        MI_TRY(miller_wave_enqueue(ctx, p_dev, q_dev, 0, (Fp12 *)(ws + off_ml), np, fl_dev, n));
+        MI_TRY(miller_wave_enqueue(ctx, d.p, d.q, 0, d.ml, np, d.flags, n));
         MI_TRY(clk.mark(ctx, 1));
-        MI_TRY(miller_wave_enqueue(ctx, p_dev, q_dev, n * np, (Fp12 *)(ws + off_ml), np, fl_dev, 0));
+        MI_TRY(miller_wave_enqueue(ctx, d.p, d.q, n * np, d.ml, np, d.flags, 0));
     } else {
-        MI_TRY(miller_wave_enqueue(ctx, p_dev, q_dev, n * np, (Fp12 *)(ws + off_ml), np, fl_dev, n));
+        MI_TRY(miller_wave_enqueue(ctx, d.p, d.q, n * np, d.ml, np, d.flags, n));
     }
     MI_TRY(clk.mark(ctx, 2));
-    MI_TRY(mi_launch_waves(ctx, k_verify_judge_wave, n * n_eq, (const Fp12 *)(ws + off_ml), np, vk->e_alpha_beta_dev, (const uint8_t *)fl_dev, pass_dev, n));
-    MI_TRY(mi_launch64(ctx, k_verify_verdict_wave, n, (const uint8_t *)fl_dev, (const uint8_t *)pass_dev, n_eq, (uint8_t *)(ws + off_vd), n));
+    MI_TRY(mi_launch_waves(ctx, k_verify_judge_wave, n * n_eq, (const Fp12 *)d.ml, np, (const Fp12 *)vk->e_alpha_beta_dev, (const uint8_t *)d.flags, d.extra, n));
+    MI_TRY(mi_launch64(ctx, k_verify_verdict_wave, n, (const uint8_t *)d.flags, (const uint8_t *)d.extra, n_eq, d.verdicts, n));
     MI_TRY(clk.mark(ctx, 3));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(verdicts, ws + off_vd, n, hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(verdicts, d.verdicts, n, hipMemcpyDeviceToHost, ctx->stream));
     MI_TRY(clk.mark(ctx, 4));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (split_ms) {

@@ -67,7 +67,7 @@ int emu_verify_combined(const void *k, const void *alpha1, const void *beta2, co
     verdict_and_index[0] = st.first_flagged < n ? 3 : 0;
     verdict_and_index[1] = st.first_flagged;
     if (!n || st.first_flagged < n) return 0;
-    // ---- the coefficients and the scalar combination (k_verify_combine_scalars' arithmetic)
+    // ---- the coefficients and the scalar combination (k_verify_locate_colsums' arithmetic over the root)
     std::vector<Fr> r(n), col(ns + 1, Fr::zero()), rc((size_t)n * nc);
     std::vector<u32> plain(4 * n);
     for (size_t i = 0; i < n; i++) {

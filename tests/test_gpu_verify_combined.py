@@ -121,6 +121,18 @@ def test_a_batch_of_130_then_small_ones_in_its_workspace(emu, forged_vk):
     _check(emu, vkh, {"name": "the first 3", "key": key, "cases": bad[:3], "seed": CR.SEED_A, "want": (R.OK, 3), "crafted_for_seed": False})
 
 
+def test_a_batch_of_130_with_three_commitments(emu, forged_vk):
+    """three blocks per column of the column-sum kernel, the last one partial, with fold challenges: the blocks of column S write
+    r_i c_i^k for k = 0, 1, 2 across all three (the larger batches above have one commitment, where that product is r_i alone); a
+    Pedersen defect of the last proof, in the partial block, is seen"""
+    key = F.forge_key(3, 3)
+    vkh = forged_vk(key)
+    cases = [dict(F.honest(key, 1300 + i), name=f"entry {i}") for i in range(130)]
+    _check(emu, vkh, {"name": "130 honest, 3 commitments", "key": key, "cases": cases, "seed": CR.SEED_B, "want": (R.OK, 130), "crafted_for_seed": False})
+    bad = list(cases); bad[129] = CR.shift_pedersen(cases[129], 1)
+    _check(emu, vkh, {"name": "130, pok of the last off by one", "key": key, "cases": bad, "seed": CR.SEED_A, "want": (R.PEDERSEN, 130), "crafted_for_seed": False})
+
+
 # ---------------------------------------------------------------------------------------------------- real proofs
 @pytest.fixture(scope="module", params=[0, 2])
 def made(ctx, request):
