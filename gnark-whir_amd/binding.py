@@ -74,9 +74,11 @@ PHASE2_EXPORTS = ["mi_phase2_init", "mi_phase2_contribute", "mi_phase2_seal", "m
 PHASE2_G1_A, PHASE2_G1_B, PHASE2_G2_B, PHASE2_G1_K, PHASE2_G1_Z, PHASE2_VK_K, PHASE2_BASIS = 0, 1, 2, 3, 4, 5, 6
 # include/mi355x_groth16_phase2_check.h (the SRS rows are consistent powers, contributions with a proof of knowledge, a claimed state verified)
 PHASE2_CHECK_EXPORTS = ["mi_srs_check_powers", "mi_srs_check_get_stats", "mi_phase2_set_transcript_id", "mi_phase2_contribute_proved",
-                        "mi_phase2_records_verify", "mi_phase2_verify_adopt", "mi_phase2_verify_get_stats"]
+                        "mi_phase2_records_verify", "mi_phase2_verify_adopt", "mi_phase2_verify_get_stats", "mi_phase2_get_pedersen_vk",
+                        "mi_phase2_contribute_sigma_proved", "mi_phase2_sigma_records_verify", "mi_phase2_get_chain_info", "mi_phase2_verify_adopt_sigma"]
 SRS_BAD_GENERATORS, SRS_BAD_TAU_G1, SRS_BAD_ALPHA_G1, SRS_BAD_BETA_G1, SRS_BAD_TAU_G2, SRS_BAD_BETA_G2 = 1, 2, 4, 8, 16, 32
 PHASE2_BAD_RECORD, PHASE2_BAD_DELTA, PHASE2_BAD_Z, PHASE2_BAD_K = 1, 2, 4, 8
+PHASE2_BAD_SIGMA_RECORD, PHASE2_BAD_SIGMA_LINK, PHASE2_BAD_BES = 16, 32, 64
 # include/mi355x_groth16_phase1.h (the powers-of-tau SRS itself: a phase-1 ceremony on the device and its handover to phase 2)
 PHASE1_EXPORTS = ["mi_phase1_init", "mi_phase1_from_srs", "mi_phase1_set_transcript_id", "mi_phase1_contribute", "mi_phase1_contribute_proved",
                   "mi_phase1_records_verify", "mi_phase1_verify_adopt", "mi_phase1_check", "mi_phase1_get_info", "mi_phase1_export", "mi_phase1_free",
@@ -88,6 +90,7 @@ KEYAUDIT_EXPORTS = ["mi_key_claim_from_streams", "mi_key_claim_from_phase2", "mi
 (KEY_BAD_SMALL, KEY_BAD_A, KEY_BAD_B1, KEY_BAD_B2, KEY_BAD_K_PRIVATE, KEY_BAD_K_PUBLIC, KEY_BAD_BASIS, KEY_BAD_SIGMA,
  KEY_BAD_Z) = 1, 2, 4, 8, 16, 32, 64, 128, 256
 PHASE1_RECORD_WORDS = 64   # a mi_phase1_record as uint64 words: tau1, alpha1, beta1 (8 each), commit[3] (24), response[3] (12), hash (4)
+PHASE2_SIGMA_PROOF_WORDS = 36   # a mi_phase2_sigma_proof as uint64 words: g_sigma_neg (16), commit (16), response (4)
 PHASE2_RECORD_WORDS = 24   # a mi_phase2_record as uint64 words: delta1 (8), commit (8), response (4), hash (4 words = 32 bytes)
 
 
@@ -224,6 +227,24 @@ class Phase1Info(C.Structure):
 
 class Phase2Claim(C.Structure):
     _fields_ = [("g1_z", C.c_void_p), ("n_z", C.c_uint64), ("g1_k", C.c_void_p), ("n_k", C.c_uint64), ("delta1", C.c_uint64 * 8), ("delta2", C.c_uint64 * 16)]
+
+
+class Phase2SigmaClaim(C.Structure):
+    _fields_ = [("basis_exp_sigma", C.c_void_p), ("n", C.c_void_p), ("g_sigma_neg", C.c_void_p)]
+
+
+class Phase2ChainInfo(C.Structure):
+    _fields_ = [("n_commitments", C.c_uint32), ("pad_", C.c_uint32), ("n_records", C.c_uint64), ("chain", C.c_uint8 * 32), ("n_sigma_records", C.c_uint64),
+                ("sigma_chain", C.c_uint8 * 32)]
+
+
+def _sigma_steps(proofs, hashes, nc):
+    """proofs: (m, nc, PHASE2_SIGMA_PROOF_WORDS) uint64; hashes: m values of 32 bytes -> (the array, the hashes as one buffer, m)"""
+    pr = _u64(proofs).reshape(-1, nc, PHASE2_SIGMA_PROOF_WORDS)
+    hs = b"".join(bytes(h) for h in hashes)
+    if len(hs) != 32 * pr.shape[0]:
+        raise ValueError("one 32-byte chain value per step")
+    return pr, (C.c_uint8 * max(len(hs), 1)).from_buffer_copy(hs or b"\0"), pr.shape[0]
 
 
 def _srs_desc(srs: dict):
@@ -946,6 +967,37 @@ class Context:
         failed = C.c_uint32(0xFFFFFFFF); fb = C.c_uint64(0)
         self._ck(self.lib.mi_phase2_verify_adopt(self.h, st, C.byref(cl), _p(rec), C.c_size_t(rec.shape[0]), seed, C.byref(failed), C.byref(fb)))
         return int(failed.value), int(fb.value)
+
+    def phase2_get_pedersen_vk(self, st, n_commitments):
+        """mi_phase2_get_pedersen_vk -> (n_commitments, 2, 16) uint64 as pedersen_vk_make: {g2, [-sigma_k]2} of the state's points"""
+        out = np.zeros((n_commitments, 2, 16), np.uint64)
+        self._ck(self.lib.mi_phase2_get_pedersen_vk(self.h, st, _p(out) if n_commitments else None))
+        return out
+
+    def phase2_contribute_sigma_proved(self, st, sigma_factor, nonce=None):
+        """mi_phase2_contribute_sigma_proved -> (the step: (n_commitments, PHASE2_SIGMA_PROOF_WORDS) uint64, the chain value after it)"""
+        sf = _u64(sigma_factor).reshape(-1, 4); out = np.zeros((sf.shape[0], PHASE2_SIGMA_PROOF_WORDS), np.uint64); h = (C.c_uint8 * 32)()
+        self._ck(self.lib.mi_phase2_contribute_sigma_proved(self.h, st, _p(sf), None if nonce is None else _p(_u64(nonce).reshape(-1, 4)), _p(out), h))
+        return out, bytes(h)
+
+    def phase2_chain_info(self, st):
+        """mi_phase2_get_chain_info -> {n_commitments, n_records, chain, n_sigma_records, sigma_chain}: where the delta and the sigma chain stand"""
+        info = Phase2ChainInfo(); self._ck(self.lib.mi_phase2_get_chain_info(self.h, st, C.byref(info)))
+        return {"n_commitments": int(info.n_commitments), "n_records": int(info.n_records), "chain": bytes(info.chain),
+                "n_sigma_records": int(info.n_sigma_records), "sigma_chain": bytes(info.sigma_chain)}
+
+    def phase2_verify_adopt_sigma(self, st, basis_exp_sigma, g_sigma_neg, proofs, hashes, seed=None):
+        """mi_phase2_verify_adopt_sigma -> (mask, bad_commitments, first_bad_record); basis_exp_sigma: one (n_k, 8) array per commitment,
+        g_sigma_neg: (n_commitments, 16), proofs: (m, n_commitments, PHASE2_SIGMA_PROOF_WORDS), hashes: m chain values"""
+        bes = [_u64(a) for a in basis_exp_sigma]; nc = len(bes)
+        ptrs = (C.c_void_p * max(nc, 1))(*[a.ctypes.data if a.shape[0] else None for a in bes])
+        counts = (C.c_uint64 * max(nc, 1))(*[a.shape[0] for a in bes])
+        gs = _u64(g_sigma_neg).reshape(-1, 16)
+        pr, hs, m = _sigma_steps(proofs, hashes, max(nc, 1))
+        cl = Phase2SigmaClaim(C.cast(ptrs, C.c_void_p), C.cast(counts, C.c_void_p), gs.ctypes.data)
+        failed = C.c_uint32(0xFFFFFFFF); bad = C.c_uint64(0); fb = C.c_uint64(0)
+        self._ck(self.lib.mi_phase2_verify_adopt_sigma(self.h, st, C.byref(cl), _p(pr), hs, C.c_size_t(m), seed, C.byref(failed), C.byref(bad), C.byref(fb)))
+        return int(failed.value), int(bad.value), int(fb.value)
 
     # ---- phase 1: the SRS itself (include/mi355x_groth16_phase1.h)
     # ---- a key audited against its circuit and an SRS (include/mi355x_groth16_keyaudit.h)
@@ -1839,6 +1891,18 @@ def phase1_records_verify(start, start_hash, first_index, records):
                                          C.c_size_t(rec.shape[0]), C.byref(fb))
     if rc != 0:
         raise MiError(f"rc={rc}: mi_phase1_records_verify")
+    return int(fb.value)
+
+
+def phase2_sigma_records_verify(start, start_hash, first_index, proofs, hashes):
+    """mi_phase2_sigma_records_verify (host only); start: (nc, 16) uint64, proofs: (m, nc, PHASE2_SIGMA_PROOF_WORDS), hashes: m chain values
+    -> the index of the first step that does not hold, m when all hold"""
+    st = _u64(start).reshape(-1, 16); nc = st.shape[0]
+    pr, hs, m = _sigma_steps(proofs, hashes, max(nc, 1)); fb = C.c_uint64()
+    rc = load().mi_phase2_sigma_records_verify(_p(st) if nc else None, C.c_uint32(nc), start_hash, C.c_uint64(first_index), _p(pr) if m else None,
+                                               hs if m else None, C.c_size_t(m), C.byref(fb))
+    if rc:
+        raise MiError(f"rc={rc}: mi_phase2_sigma_records_verify")
     return int(fb.value)
 
 

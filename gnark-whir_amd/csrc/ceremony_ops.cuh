@@ -1,5 +1,5 @@
 // What the checks of a ceremony (include/mi355x_groth16_phase2_check.h) hash and judge, one record per lane / per call, MI_HD: the kernels
-// of phase2_check.hip, the host code of phase2_records.hip and the host build of the tests (tests/cpp/phase2_check_host.cpp) run this text.
+// of phase2_check.hip, the host code of phase2_records.hip and the host build of the tests (tests/cpp/phase2_check_host.cpp, phase2_sigma_host.cpp) run this text.
 //
 // Coefficients of the same-ratio tests:
 //     r_k = the little-endian integer of the first 16 bytes of SHA-256("mi355x-ceremony-coeff" | seed (32 bytes) | le64(k))
@@ -13,6 +13,7 @@
 #include "pairing_ops.cuh"
 #include "keyfile_ops.cuh"
 #include "point_ntt.cuh"
+#include <vector>
 
 #define MI_CEREMONY_COEFF_TAG_LEN 21
 #define MI_CEREMONY_RECORD_TAG_LEN 20
@@ -134,6 +135,96 @@ inline u64 ceremony_records_first_bad(const G1Aff &start, const uint8_t start_ha
         if (!ceremony_record_holds(prev, first_index + i, before, rec[i])) return i;
         before = rec[i].delta1;
         prev = rec[i].hash;
+    }
+    return m;
+}
+
+// ---------------------------------------------------------------- the steps of the sigma chain (host callers)
+// One step re-randomises the nc points [-sigma_k]2 of a state under ONE challenge, over the twist:
+//     hash_i = SHA-256("mi355x-phase2-sigma-record" | hash_(i-1) | le64(i) | le32(nc) | for k: compress2(before_k) | compress2(after_k) | compress2(T_k))
+//     c_i    = the little-endian integer of the first 16 bytes of SHA-256("mi355x-phase2-sigma-challenge" | hash_i)
+//     step i holds iff   hash = hash_i   and for every k   [z_k] before_k = T_k + [c_i] after_k
+// compress2 = mi_g2_compress (keyfile_ops.cuh's g2_encode_stream gives the same 64 bytes).
+#define MI_CEREMONY_SIGMA_RECORD_TAG_LEN 26
+#define MI_CEREMONY_SIGMA_CHALLENGE_TAG_LEN 29
+MI_HD uint8_t ceremony_sigma_record_tag(int i) { constexpr char d[MI_CEREMONY_SIGMA_RECORD_TAG_LEN + 1] = "mi355x-phase2-sigma-record"; return (uint8_t)d[i]; }
+MI_HD uint8_t ceremony_sigma_challenge_tag(int i) { constexpr char d[MI_CEREMONY_SIGMA_CHALLENGE_TAG_LEN + 1] = "mi355x-phase2-sigma-challenge"; return (uint8_t)d[i]; }
+// the layout of mi_phase2_sigma_proof: one commitment's part of a step
+struct CeremonySigmaProof {
+    G2Aff g_sigma_neg, commit;
+    Fr response;
+};
+// before: the nc points the step starts from; step: its nc parts
+inline void ceremony_sigma_hash(const uint8_t prev[32], u64 index, u32 nc, const G2Aff *before, const CeremonySigmaProof *step, uint8_t out[32]) {
+    Sha256 s;
+    uint8_t b[64];
+    sha256_init(&s);
+    for (int i = 0; i < MI_CEREMONY_SIGMA_RECORD_TAG_LEN; i++) sha256_byte(&s, ceremony_sigma_record_tag(i));
+    sha256_update(&s, prev, 32);
+    for (int i = 0; i < 8; i++) sha256_byte(&s, (uint8_t)(index >> (8 * i)));
+    for (int i = 0; i < 4; i++) sha256_byte(&s, (uint8_t)(nc >> (8 * i)));
+    for (u32 k = 0; k < nc; k++) {
+        g2_encode_stream(b, before[k], true); sha256_update(&s, b, 64);
+        g2_encode_stream(b, step[k].g_sigma_neg, true); sha256_update(&s, b, 64);
+        g2_encode_stream(b, step[k].commit, true); sha256_update(&s, b, 64);
+    }
+    sha256_final(&s, out);
+}
+inline void ceremony_sigma_challenge(const uint8_t hash[32], u32 c[4]) {
+    Sha256 s;
+    uint8_t d[32];
+    sha256_init(&s);
+    for (int i = 0; i < MI_CEREMONY_SIGMA_CHALLENGE_TAG_LEN; i++) sha256_byte(&s, ceremony_sigma_challenge_tag(i));
+    sha256_update(&s, hash, 32);
+    sha256_final(&s, d);
+    ceremony_low128(d, c);
+}
+// The step after_k = [s_k] before_k with the nonces n_k (Montgomery, none 0): T_k = [n_k] before_k, z_k = n_k + c s_k.  after is given: the
+// caller has computed it (the state's points after the contribution).
+inline void ceremony_sigma_step_make(const uint8_t prev[32], u64 index, u32 nc, const G2Aff *before, const G2Aff *after, const Fr *s, const Fr *n,
+                                     CeremonySigmaProof *out, uint8_t hash_out[32]) {
+    for (u32 k = 0; k < nc; k++) {
+        out[k].g_sigma_neg = after[k];
+        out[k].commit = xyzz_to_affine(xyzz_scale(G2X::from_affine(before[k]), n[k]));
+    }
+    ceremony_sigma_hash(prev, index, nc, before, out, hash_out);
+    u32 c[4];
+    ceremony_sigma_challenge(hash_out, c);
+    const Fr cc = fr_from_u128(c);
+    for (u32 k = 0; k < nc; k++) out[k].response = n[k] + cc * s[k];
+}
+// words that are a point of the twist other than infinity: decided before any arithmetic touches them
+inline bool ceremony_sigma_point_ok(const G2Aff &q) { return g2_reduced(q) && !q.is_inf() && g2_on_twist(q); }
+// Step `index` of a chain after `prev`, over the nc points before
+inline bool ceremony_sigma_step_holds(const uint8_t prev[32], u64 index, u32 nc, const G2Aff *before, const CeremonySigmaProof *step, const uint8_t hash[32]) {
+    for (u32 k = 0; k < nc; k++)
+        if (!ceremony_sigma_point_ok(step[k].g_sigma_neg) || !ceremony_sigma_point_ok(step[k].commit) || !fe_is_reduced(step[k].response)) return false;
+    uint8_t h[32];
+    ceremony_sigma_hash(prev, index, nc, before, step, h);
+    for (int i = 0; i < 32; i++) if (h[i] != hash[i]) return false;
+    u32 c[4];
+    ceremony_sigma_challenge(h, c);
+    const Fr cc = fr_from_u128(c);
+    for (u32 k = 0; k < nc; k++) {
+        const G2Aff lhs = xyzz_to_affine(xyzz_scale(G2X::from_affine(before[k]), step[k].response));
+        G2X rhs = xyzz_scale(G2X::from_affine(step[k].g_sigma_neg), cc);
+        xyzz_madd(rhs, step[k].commit, false);
+        const G2Aff r = xyzz_to_affine(rhs);
+        if (!(lhs.x == r.x && lhs.y == r.y)) return false;
+    }
+    return true;
+}
+// The chain of m steps (proofs: m * nc parts, hashes: m) that continues (start, start_hash, first_index): the index of the first step that
+// does not hold, m when all do
+inline u64 ceremony_sigma_first_bad(const G2Aff *start, u32 nc, const uint8_t start_hash[32], u64 first_index, const CeremonySigmaProof *proofs,
+                                    const uint8_t (*hashes)[32], size_t m) {
+    std::vector<G2Aff> before(start, start + nc);
+    const uint8_t *prev = start_hash;
+    for (size_t i = 0; i < m; i++) {
+        const CeremonySigmaProof *step = proofs + i * nc;
+        if (!ceremony_sigma_step_holds(prev, first_index + i, nc, before.data(), step, hashes[i])) return i;
+        for (u32 k = 0; k < nc; k++) before[k] = step[k].g_sigma_neg;
+        prev = hashes[i];
     }
     return m;
 }

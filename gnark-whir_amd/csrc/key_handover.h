@@ -55,6 +55,8 @@ struct KeyStreams {
     int32_t check(mi_ctx *ctx, const char *who, const mi_pk_desc &counts, const mi_pedersen_arrays *ped, u32 n_commitments, u64 n_vk_k) const;
     // the verifying key's stream from ka's small points and vk.G1.K on the host; its Pedersen keys are made from sigma, its lists start empty
     int32_t write_vk(mi_ctx *ctx, const KeyArrays &ka, const mi_g1_affine *k, u64 n_k, const mi_fr *sigma, u32 n_commitments) const;
+    // the same with the Pedersen keys handed over as pairs {g2, [-sigma]2}: for a maker that holds the points and no scalar (phase2.hip)
+    int32_t write_vk_points(mi_ctx *ctx, const KeyArrays &ka, const mi_g1_affine *k, u64 n_k, const mi_pedersen_vk *ped, u32 n_commitments) const;
 };
 
 // Which wires own a point of pk.G1.A / pk.G1.B (+ pk.G2.B) / pk.G1.K.  slot_*: nb_wires + 1 words each on the device; the maker's own

@@ -71,14 +71,17 @@ int32_t KeyStreams::check(mi_ctx *ctx, const char *who_c, const mi_pk_desc &coun
     return MI_OK;
 }
 int32_t KeyStreams::write_vk(mi_ctx *ctx, const KeyArrays &ka, const mi_g1_affine *k, u64 n_k, const mi_fr *sigma, u32 n_commitments) const {
+    std::vector<mi_pedersen_vk> pvk(n_commitments);
+    MI_TRY(mi_pedersen_vk_make(ctx, sigma, n_commitments, pvk.data()));
+    return write_vk_points(ctx, ka, k, n_k, pvk.data(), n_commitments);
+}
+int32_t KeyStreams::write_vk_points(mi_ctx *ctx, const KeyArrays &ka, const mi_g1_affine *k, u64 n_k, const mi_pedersen_vk *ped, u32 n_commitments) const {
     mi_vk_file_desc vd;
     std::memset(&vd, 0, sizeof(vd));
     std::memcpy(&vd.alpha1, &ka.small1[0], 64); std::memcpy(&vd.beta1, &ka.small1[1], 64); std::memcpy(&vd.delta1, &ka.small1[2], 64);
     std::memcpy(&vd.beta2, &ka.small2[0], 128); std::memcpy(&vd.delta2, &ka.small2[1], 128); std::memcpy(&vd.gamma2, &ka.small2[2], 128);
     vd.k = k; vd.n_k = n_k; vd.nb_public = ka.nb_public; vd.n_commitments = n_commitments;
-    std::vector<mi_pedersen_vk> pvk(n_commitments);
-    MI_TRY(mi_pedersen_vk_make(ctx, sigma, n_commitments, pvk.data()));
-    vd.ped = pvk.data();
+    vd.ped = ped;
     return mi_vk_write(ctx, &vd, encoding, vk_out, vk_cap, vk_len);
 }
 

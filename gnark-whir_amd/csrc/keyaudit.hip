@@ -114,7 +114,7 @@ void free_claim(mi_key_claim *c) {
     }
     delete c;
 }
-// the state's arrays where they are now, its small points and the Pedersen pairs of its sigma
+// the state's arrays where they are now, its small points and the Pedersen pairs of its [-sigma]2 points
 int32_t view_state(mi_ctx *ctx, const mi_phase2 *S, mi_key_claim &c) {
     c.borrowed = S;
     c.nb_wires = S->nb_wires;
@@ -122,18 +122,16 @@ int32_t view_state(mi_ctx *ctx, const mi_phase2 *S, mi_key_claim &c) {
     c.arr[ARR_A] = S->g1_a; c.arr[ARR_B] = S->g1_b; c.arr[ARR_K] = S->g1_k; c.arr[ARR_Z] = S->g1_z; c.arr[ARR_G2B] = S->g2_b;
     c.n[ARR_A] = S->n_a; c.n[ARR_B] = c.n[ARR_G2B] = S->n_b; c.n[ARR_K] = S->n_k; c.n[ARR_Z] = S->N;
     c.ped.clear();
-    std::vector<mi_fr> sigma(S->ped.size());
     for (size_t k = 0; k < S->ped.size(); k++) {
         mi_key_claim::Ped p;
         p.basis = S->ped[k].basis; p.bes = S->ped[k].bes; p.n = S->ped[k].n;
         c.ped.push_back(p);
-        std::memcpy(&sigma[k], &S->ped[k].sigma, 32);
     }
     c.alpha1 = c.vk_alpha1 = S->alpha1; c.beta1 = S->beta1; c.delta1 = S->delta1;
     c.beta2 = c.vk_beta2 = S->beta2; c.delta2 = c.vk_delta2 = S->delta2; c.vk_gamma2 = S->gamma2;
     c.vk_k = S->vk_k; c.n_vk = S->n_vk;
     c.vk_ped.assign(S->ped.size(), mi_pedersen_vk{});
-    if (!S->ped.empty()) MI_TRY(mi_pedersen_vk_make(ctx, sigma.data(), (uint32_t)S->ped.size(), c.vk_ped.data()));
+    mi_phase2_pedersen_vk_of(S, c.vk_ped.data());
     return MI_OK;
 }
 

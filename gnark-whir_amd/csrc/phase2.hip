@@ -9,7 +9,8 @@
 //   4  the three matrices sorted by column by setup.hip's MatrixSorter, then the sums of points of sparse_points.cuh:
 //      [A_j]1, [B_j]1, [B_j]2 and [t_j]1 = one accumulator over (A, [beta L]), (B, [alpha L]), (C, [L])
 //   5  masks from the points at infinity, Setup's wire selection (key_handover.h), the gathers for vk.K and the Pedersen bases
-// The state keeps the plain affine arrays; contribute multiplies Z, K, BasisExpSigma and the two delta points by scalars; seal copies
+// The state keeps the plain affine arrays and, per commitment, the point [-sigma]2; contribute multiplies Z, K, BasisExpSigma, that
+// point and the two delta points by scalars; seal copies
 // the arrays into an ordinary key and the streams are written from the state's arrays directly, both through key_handover.h.
 #include "prove_internal.h"
 #include "r1cs_internal.h"
@@ -411,6 +412,13 @@ int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, boo
         MI_CHECK_HIP(ctx, hipMemcpyAsync(pd.bes, pd.basis, pd.n * 64, hipMemcpyDeviceToDevice, st));
         MI_TRY(scale_array<Fp>(ctx, (G1Aff *)pd.bes, pd.n, pd.sigma));
     }
+    if (sh.n_commitments) {   // [-sigma_k]2 as mi_pedersen_vk_make makes it
+        std::vector<mi_fr> sg(sh.n_commitments);
+        std::vector<mi_pedersen_vk> pvk(sh.n_commitments);
+        for (u32 k = 0; k < sh.n_commitments; k++) std::memcpy(&sg[k], &sigma[k], 32);
+        MI_TRY(mi_pedersen_vk_make(ctx, sg.data(), sh.n_commitments, pvk.data()));
+        for (u32 k = 0; k < sh.n_commitments; k++) std::memcpy(&S->ped[k].g_sigma_neg, &pvk[k].g_sigma_neg, sizeof(G2Aff));
+    }
     MI_TRY(laps.lap(ctx, stats.affine_ms));
     // beta_g2 as it is, and the generators where gamma = delta = 1
     std::memcpy(&S->beta2, &srs->beta_g2, 128);
@@ -445,6 +453,32 @@ int32_t mi_phase2_srs_host_check(mi_ctx *ctx, const mi_srs_desc *srs, u64 N) {
         if (r.n < r.need) MI_FAIL(ctx, MI_EINVAL, std::string("phase2: srs.n_") + r.name + " is " + std::to_string(r.n) + ", the circuit needs " + std::to_string(r.need) + " points");
     }
     return MI_OK;
+}
+int32_t mi_phase2_scale_sigma(mi_ctx *ctx, mi_phase2 *S, const Fr *sf) {
+    for (u32 k = 0; k < S->n_commitments; k++) {
+        MI_TRY(scale_array<Fp>(ctx, (G1Aff *)S->ped[k].bes, S->ped[k].n, sf[k]));
+        S->ped[k].sigma = S->ped[k].sigma * sf[k];
+    }
+    if (!S->n_commitments) return MI_OK;
+    // the points [-sigma_k]2: one array of n_commitments points, one factor each -- a launch per point of the kernel delta2 goes through
+    Arena ar;
+    G2Aff *g = nullptr;
+    std::vector<G2Aff> h(S->n_commitments);
+    for (u32 k = 0; k < S->n_commitments; k++) h[k] = S->ped[k].g_sigma_neg;
+    MI_TRY(ar.alloc(ctx, &g, (size_t)S->n_commitments));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(g, h.data(), h.size() * sizeof(G2Aff), hipMemcpyHostToDevice, ctx->stream));
+    for (u32 k = 0; k < S->n_commitments; k++) MI_TRY(scale_array<Fp2>(ctx, g + k, 1, sf[k]));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(h.data(), g, h.size() * sizeof(G2Aff), hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (u32 k = 0; k < S->n_commitments; k++) S->ped[k].g_sigma_neg = h[k];
+    return MI_OK;
+}
+void mi_phase2_pedersen_vk_of(const mi_phase2 *S, mi_pedersen_vk *out) {
+    const G2Aff gen = g2_generator();
+    for (u32 k = 0; k < S->n_commitments; k++) {
+        std::memcpy(&out[k].g, &gen, sizeof(gen));
+        std::memcpy(&out[k].g_sigma_neg, &S->ped[k].g_sigma_neg, sizeof(gen));
+    }
 }
 int32_t mi_phase2_check_points(mi_ctx *ctx, Arena &ar, const Phase2Row *rows, int n_rows, uint32_t flags) {
     hipStream_t st = ctx->stream;
@@ -542,10 +576,7 @@ int32_t mi_phase2_contribute(mi_ctx *ctx, mi_phase2 *S, const mi_fr *delta, cons
     const Fr d_inv = fe_inv(d);
     MI_TRY(scale_array<Fp>(ctx, (G1Aff *)S->g1_z, S->N, d_inv));
     MI_TRY(scale_array<Fp>(ctx, (G1Aff *)S->g1_k, S->n_k, d_inv));
-    for (u32 k = 0; k < S->n_commitments; k++) {
-        MI_TRY(scale_array<Fp>(ctx, (G1Aff *)S->ped[k].bes, S->ped[k].n, sf[k]));
-        S->ped[k].sigma = S->ped[k].sigma * sf[k];
-    }
+    if (sigma_factor) MI_TRY(mi_phase2_scale_sigma(ctx, S, sf.data()));
     // the two delta points: one-point arrays through the same kernel
     Arena ar;
     G1Aff *d1 = nullptr;
@@ -615,17 +646,15 @@ int32_t mi_phase2_to_streams(mi_ctx *ctx, const mi_phase2 *S, uint32_t encoding,
     const KeyArrays ka = key_arrays_of(S);
     const mi_pk_desc d = ka.desc();
     std::vector<mi_pedersen_arrays> pa(S->n_commitments);
-    std::vector<mi_fr> sigma(S->n_commitments);
-    for (u32 k = 0; k < S->n_commitments; k++) {
-        pa[k] = mi_pedersen_arrays{(const mi_g1_affine *)S->ped[k].basis, (const mi_g1_affine *)S->ped[k].bes, S->ped[k].n};
-        std::memcpy(&sigma[k], &S->ped[k].sigma, 32);
-    }
+    std::vector<mi_pedersen_vk> pvk(S->n_commitments);
+    for (u32 k = 0; k < S->n_commitments; k++) pa[k] = mi_pedersen_arrays{(const mi_g1_affine *)S->ped[k].basis, (const mi_g1_affine *)S->ped[k].bes, S->ped[k].n};
+    mi_phase2_pedersen_vk_of(S, pvk.data());
     std::vector<mi_g1_affine> k_host(S->n_vk);
     const KeyStreams ks{encoding, out_host, cap, len, true, vk_out_host, vk_cap, vk_len};
     MI_TRY(ks.check(ctx, "phase2", d, pa.data(), S->n_commitments, S->n_vk));
     if (S->n_vk) MI_CHECK_HIP(ctx, hipMemcpyAsync(k_host.data(), S->vk_k, S->n_vk * 64, hipMemcpyDeviceToHost, ctx->stream));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    MI_TRY(ks.write_vk(ctx, ka, k_host.data(), S->n_vk, sigma.data(), S->n_commitments));
+    MI_TRY(ks.write_vk_points(ctx, ka, k_host.data(), S->n_vk, pvk.data(), S->n_commitments));
     return mi_pk_write_dev(ctx, &d, pa.data(), S->n_commitments, encoding, out_host, cap, len);
 }
 
@@ -652,6 +681,14 @@ int32_t mi_phase2_get_array(mi_ctx *ctx, const mi_phase2 *S, uint32_t which, voi
     if (cap < cnt) MI_FAIL(ctx, MI_EINVAL, "phase2: the array holds " + std::to_string(cnt) + " points, out_host has room for " + std::to_string(cap));
     if (cnt) MI_CHECK_HIP(ctx, hipMemcpyAsync(out_host, src, cnt * bytes, hipMemcpyDeviceToHost, ctx->stream));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MI_OK;
+}
+
+int32_t mi_phase2_get_pedersen_vk(mi_ctx *ctx, const mi_phase2 *S, mi_pedersen_vk *out) {
+    if (!ctx) return MI_EINVAL;
+    if (!S) MI_FAIL(ctx, MI_EINVAL, "phase2: the state is null");
+    if (!out && S->n_commitments) MI_FAIL(ctx, MI_EINVAL, "phase2: out is null");
+    mi_phase2_pedersen_vk_of(S, out);
     return MI_OK;
 }
 

@@ -1,6 +1,8 @@
 // The checks of a ceremony (include/mi355x_groth16_phase2_check.h): the SRS rows are consistent powers, contributions carry a proof of
-// knowledge, a claimed state is verified before it is taken over.  The hashes, the records and the judgement of a relation are
-// ceremony_ops.cuh's text; the chain of records is verified on the host (phase2_records.hip).
+// knowledge, a claimed state is verified before it is taken over -- for delta (Z, K, the delta points) and for the commitment keys'
+// sigma (BasisExpSigma, the points [-sigma_k]2), each with a chain of its own.  The hashes, the records and the judgement of a relation
+// are ceremony_ops.cuh's text; the chains of records are verified on the host (phase2_records.hip).  The sigma calls at the end of this
+// file add no kernel: they run the ones below and phase2.hip's scale kernels.
 //
 // Every pairing check here is a SAME-RATIO TEST  e(sum r_k P_k, s) = e(sum r_k Q_k, t):
 //   k_ceremony_coeffs   one lane per k: r_k = 128 bits of SHA-256(tag | seed | k), stored as a Montgomery Fr -- ONE array per call, every
@@ -94,6 +96,25 @@ int32_t msm_g2(mi_ctx *ctx, const G2Aff *bases, const Fr *scalars, u64 n, G2Aff 
     std::memcpy(&z, &j.z, sizeof(z));
     *out = G2Aff{Fp2::zero(), Fp2::zero()};
     if (!z.is_zero()) std::memcpy(out, &j, sizeof(*out));
+    return MI_OK;
+}
+
+// a Schnorr nonce: the caller's (not 0, below r), or 48 bytes of the operating system's reduced mod r: uniform to within 2^-128
+int32_t nonce_or_random(mi_ctx *ctx, const mi_fr *nonce, Fr &k) {
+    if (nonce) {
+        std::memcpy(&k, nonce, 32);
+        if (k.is_zero()) MI_FAIL(ctx, MI_EINVAL, "phase2: nonce is 0");
+        if (!fe_is_reduced(k)) MI_FAIL(ctx, MI_EINVAL, "phase2: nonce is not below r");
+        return MI_OK;
+    }
+    uint8_t b[MI_H2F_BYTES];
+    for (size_t got = 0; got < sizeof(b);) {
+        const ssize_t n = getrandom(b + got, sizeof(b) - got, 0);
+        if (n <= 0) MI_FAIL(ctx, MI_ENODEV, "phase2: the operating system gave no randomness for the nonce (getrandom)");
+        got += (size_t)n;
+    }
+    k = fr_from_be48(b);
+    if (k.is_zero()) MI_FAIL(ctx, MI_ENODEV, "phase2: the drawn nonce is 0");
     return MI_OK;
 }
 
@@ -257,6 +278,58 @@ int32_t verify_run(mi_ctx *ctx, mi_phase2 *S, const mi_phase2_claim *claim, cons
     return MI_OK;
 }
 
+// the claimed BasisExpSigma arrays on the device, and per commitment whether its relation fails.  No kernel here is new: the claim is
+// checked by k_ceremony_claim_check, summed by the context's MSM and judged by judge() as Z and K are above
+int32_t sigma_verify_run(mi_ctx *ctx, mi_phase2 *S, const mi_phase2_sigma_claim *claim, const uint8_t *seed, Arena &ar, std::vector<G1Aff *> &bes,
+                         std::vector<uint8_t> &bad) {
+    hipStream_t st = ctx->stream;
+    mi_srs_check_stats &stats = ctx->phase2_verify_stats;
+    Clock ck;
+    const u32 nc = S->n_commitments;
+    u64 nr = 0;
+    for (u32 k = 0; k < nc; k++) {
+        const u64 n = S->ped[k].n;
+        MI_TRY(ar.alloc(ctx, &bes[k], (size_t)n));
+        if (n) MI_CHECK_HIP(ctx, hipMemcpyAsync(bes[k], claim->basis_exp_sigma[k], n * sizeof(G1Aff), hipMemcpyHostToDevice, st));
+        if (n > nr) nr = n;
+    }
+    MI_TRY(sync_lap(ctx, ck, stats.upload_ms));
+    {
+        ull *first_bad = nullptr;
+        std::vector<ull> first_bad_h(nc);
+        MI_TRY(ar.alloc(ctx, &first_bad, (size_t)nc));
+        MI_CHECK_HIP(ctx, hipMemsetAsync(first_bad, 0xff, nc * sizeof(ull), st));
+        for (u32 k = 0; k < nc; k++)
+            if (S->ped[k].n) hipLaunchKernelGGL(k_ceremony_claim_check, dim3(mi_blocks_of(S->ped[k].n, 256)), dim3(256), 0, st, (const G1Aff *)bes[k], S->ped[k].n, first_bad + k);
+        MI_CHECK_HIP(ctx, hipGetLastError());
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(first_bad_h.data(), first_bad, nc * sizeof(ull), hipMemcpyDeviceToHost, st));
+        MI_TRY(sync_lap(ctx, ck, stats.point_check_ms));
+        ar.release(first_bad);
+        for (u32 k = 0; k < nc; k++)
+            if (first_bad_h[k] != ~0ull)
+                MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: claim.basis_exp_sigma[" + std::to_string(k) + "][" + std::to_string(first_bad_h[k]) + "] is not a point of the curve");
+    }
+    Fr *r = nullptr;
+    MI_TRY(ar.alloc(ctx, &r, (size_t)nr));
+    MI_TRY(coeffs_enqueue(ctx, seed, nr, r));
+    MI_TRY(sync_lap(ctx, ck, stats.coeff_ms));
+    const G1Aff inf1{Fp::zero(), Fp::zero()};
+    std::vector<G1Aff> sum_basis(nc, inf1), sum_bes(nc, inf1);
+    for (u32 k = 0; k < nc; k++) {
+        if (!S->ped[k].n) continue;
+        MI_TRY(msm_g1(ctx, (const G1Aff *)S->ped[k].basis, r, S->ped[k].n, &sum_basis[k]));
+        MI_TRY(msm_g1(ctx, bes[k], r, S->ped[k].n, &sum_bes[k]));
+    }
+    ck.lap(stats.msm_g1_ms);
+    ar.release(r);
+    Relations rel;   // e(sum r_i Basis_k[i], g_sigma_neg'_k) e(sum r_i BES'_k[i], g2) = 1
+    for (u32 k = 0; k < nc; k++) rel.add(sum_basis[k], g2_of(claim->g_sigma_neg[k]), g1_aff_neg(sum_bes[k]), g2_generator());
+    MI_TRY(judge(ctx, ar, rel, bad));
+    ck.lap(stats.pairing_ms);
+    stats.peak_bytes = ar.peak;
+    return MI_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------- shared with keyaudit.hip
@@ -321,7 +394,10 @@ int32_t mi_phase2_set_transcript_id(mi_ctx *ctx, mi_phase2 *S, const uint8_t id[
     if (!ctx) return MI_EINVAL;
     if (!S || !id) MI_FAIL(ctx, MI_EINVAL, "phase2: the state or the transcript id is null");
     if (S->n_records) MI_FAIL(ctx, MI_EINVAL, "phase2: the transcript id is set before the first record only; the state holds " + std::to_string(S->n_records));
+    if (S->n_sigma_records)
+        MI_FAIL(ctx, MI_EINVAL, "phase2: the transcript id is set before the first record only; the state's sigma chain holds " + std::to_string(S->n_sigma_records));
     std::memcpy(S->chain, id, 32);
+    std::memcpy(S->sigma_chain, id, 32);
     return MI_OK;
 }
 
@@ -334,20 +410,7 @@ int32_t mi_phase2_contribute_proved(mi_ctx *ctx, mi_phase2 *S, const mi_fr *delt
     std::memcpy(&d, delta, 32);
     if (d.is_zero()) MI_FAIL(ctx, MI_EINVAL, "phase2: delta is 0");
     if (!fe_is_reduced(d)) MI_FAIL(ctx, MI_EINVAL, "phase2: delta is not below r");
-    if (nonce) {
-        std::memcpy(&k, nonce, 32);
-        if (k.is_zero()) MI_FAIL(ctx, MI_EINVAL, "phase2: nonce is 0");
-        if (!fe_is_reduced(k)) MI_FAIL(ctx, MI_EINVAL, "phase2: nonce is not below r");
-    } else {   // 48 bytes reduced mod r: uniform to within 2^-128
-        uint8_t b[MI_H2F_BYTES];
-        for (size_t got = 0; got < sizeof(b);) {
-            const ssize_t n = getrandom(b + got, sizeof(b) - got, 0);
-            if (n <= 0) MI_FAIL(ctx, MI_ENODEV, "phase2: the operating system gave no randomness for the nonce (getrandom)");
-            got += (size_t)n;
-        }
-        k = fr_from_be48(b);
-        if (k.is_zero()) MI_FAIL(ctx, MI_ENODEV, "phase2: the drawn nonce is 0");
-    }
+    MI_TRY(nonce_or_random(ctx, nonce, k));
     const G1Aff before = S->delta1;
     MI_TRY(mi_phase2_contribute(ctx, S, delta, nullptr));
     CeremonyRecord rec;
@@ -398,6 +461,104 @@ int32_t mi_phase2_verify_adopt(mi_ctx *ctx, mi_phase2 *S, const mi_phase2_claim 
         S->delta1 = d1; S->delta2 = d2;
         std::memcpy(S->chain, rec[m - 1].hash, 32);
         S->n_records += m;
+    }
+    ctx->phase2_verify_stats.total_ms = (float)(now_ms() - t0);
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- sigma
+int32_t mi_phase2_get_chain_info(mi_ctx *ctx, const mi_phase2 *S, mi_phase2_chain_info *out) {
+    if (!ctx) return MI_EINVAL;
+    if (!S || !out) MI_FAIL(ctx, MI_EINVAL, "phase2: the state or out is null");
+    std::memset(out, 0, sizeof(*out));
+    out->n_commitments = S->n_commitments;
+    out->n_records = S->n_records;
+    std::memcpy(out->chain, S->chain, 32);
+    out->n_sigma_records = S->n_sigma_records;
+    std::memcpy(out->sigma_chain, S->sigma_chain, 32);
+    return MI_OK;
+}
+
+int32_t mi_phase2_contribute_sigma_proved(mi_ctx *ctx, mi_phase2 *S, const mi_fr *sigma_factor, const mi_fr *nonce, mi_phase2_sigma_proof *out, uint8_t hash_out[32]) {
+    if (!ctx) return MI_EINVAL;
+    if (!S) MI_FAIL(ctx, MI_EINVAL, "phase2: the state is null");
+    if (!sigma_factor) MI_FAIL(ctx, MI_EINVAL, "phase2: sigma_factor is null");
+    if (!out || !hash_out) MI_FAIL(ctx, MI_EINVAL, "phase2: the step's out or hash_out is null");
+    const u32 nc = S->n_commitments;
+    if (!nc) MI_FAIL(ctx, MI_EINVAL, "phase2: the state has no commitments, so no sigma to contribute to");
+    std::vector<Fr> s(nc), n(nc);
+    for (u32 k = 0; k < nc; k++) {
+        std::memcpy(&s[k], &sigma_factor[k], 32);
+        if (s[k].is_zero()) MI_FAIL(ctx, MI_EINVAL, "phase2: sigma_factor[" + std::to_string(k) + "] is 0");
+        if (!fe_is_reduced(s[k])) MI_FAIL(ctx, MI_EINVAL, "phase2: sigma_factor[" + std::to_string(k) + "] is not below r");
+    }
+    for (u32 k = 0; k < nc; k++) MI_TRY(nonce_or_random(ctx, nonce ? nonce + k : nullptr, n[k]));
+    std::vector<G2Aff> before(nc), after(nc);
+    for (u32 k = 0; k < nc; k++) before[k] = S->ped[k].g_sigma_neg;
+    MI_TRY(mi_phase2_scale_sigma(ctx, S, s.data()));
+    for (u32 k = 0; k < nc; k++) after[k] = S->ped[k].g_sigma_neg;
+    std::vector<CeremonySigmaProof> step(nc);
+    uint8_t h[32];
+    ceremony_sigma_step_make(S->sigma_chain, S->n_sigma_records, nc, before.data(), after.data(), s.data(), n.data(), step.data(), h);
+    std::memcpy(out, step.data(), (size_t)nc * sizeof(CeremonySigmaProof));
+    std::memcpy(hash_out, h, 32);
+    std::memcpy(S->sigma_chain, h, 32);
+    S->n_sigma_records++;
+    return MI_OK;
+}
+
+int32_t mi_phase2_verify_adopt_sigma(mi_ctx *ctx, mi_phase2 *S, const mi_phase2_sigma_claim *claim, const mi_phase2_sigma_proof *proofs, const uint8_t (*hashes)[32],
+                                     size_t m, const uint8_t *seed, uint32_t *failed, uint64_t *bad_commitments, uint64_t *first_bad_record) {
+    if (!ctx) return MI_EINVAL;
+    if (!S) MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: the state is null");
+    if (!m) MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: m is 0: a claimed state comes with the steps of its contributions");
+    if (!claim || !proofs || !hashes || !failed || !bad_commitments) MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: claim, proofs, hashes, failed or bad_commitments is null");
+    const u32 nc = S->n_commitments;
+    if (!nc) MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: the state has no commitments");
+    if (nc > 64) MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: bad_commitments has a bit for 64 commitments, the state has " + std::to_string(nc));
+    if (!claim->basis_exp_sigma || !claim->n || !claim->g_sigma_neg) MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: claim.basis_exp_sigma, claim.n or claim.g_sigma_neg is null");
+    for (u32 k = 0; k < nc; k++) {
+        const std::string name = "claim.g_sigma_neg[" + std::to_string(k) + "]";
+        if (claim->n[k] != S->ped[k].n)
+            MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: claim.n[" + std::to_string(k) + "] is " + std::to_string(claim->n[k]) + ", the state's commitment holds " + std::to_string(S->ped[k].n) + " points");
+        if (!claim->basis_exp_sigma[k] && claim->n[k]) MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: claim.basis_exp_sigma[" + std::to_string(k) + "] is null");
+        const G2Aff gs = g2_of(claim->g_sigma_neg[k]);
+        if (gs.is_inf() || !g2_reduced(gs) || !g2_on_twist(gs)) MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: " + name + " is at infinity or not on its curve");
+        if (!g2_in_subgroup_psi(&gs)) MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: " + name + " is not in the r-torsion");
+    }
+    uint8_t own_seed[32];
+    MI_TRY(seed_or_random(ctx, "phase2 verify sigma", seed, own_seed));
+    const double t0 = now_ms();
+    ctx->phase2_verify_stats = mi_srs_check_stats{};
+    Arena ar;
+    std::vector<G1Aff *> bes(nc, nullptr);
+    std::vector<uint8_t> bad;
+    const int32_t rc = sigma_verify_run(ctx, S, claim, seed, ar, bes, bad);
+    if (rc != MI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    // the chain, on the host: from where this state stands
+    std::vector<G2Aff> start(nc);
+    for (u32 k = 0; k < nc; k++) start[k] = S->ped[k].g_sigma_neg;
+    const uint64_t fb = ceremony_sigma_first_bad(start.data(), nc, S->sigma_chain, S->n_sigma_records, (const CeremonySigmaProof *)proofs, hashes, m);
+    uint32_t mask = 0;
+    uint64_t bad_k = 0;
+    if (fb != m) mask |= MI_PHASE2_BAD_SIGMA_RECORD;
+    for (u32 k = 0; k < nc; k++) {
+        if (std::memcmp(&proofs[(m - 1) * nc + k].g_sigma_neg, &claim->g_sigma_neg[k], sizeof(mi_g2_affine)) != 0) mask |= MI_PHASE2_BAD_SIGMA_LINK;
+        if (bad[k]) { mask |= MI_PHASE2_BAD_BES; bad_k |= (uint64_t)1 << k; }
+    }
+    *failed = mask;
+    *bad_commitments = bad_k;
+    if (first_bad_record) *first_bad_record = fb;
+    if (!mask) {   // the state takes the claimed arrays as they stand on the device; nothing below can fail
+        for (u32 k = 0; k < nc; k++) {
+            (void)hipFree(S->ped[k].bes);
+            S->ped[k].bes = bes[k];
+            ar.disown(bes[k]);
+            S->ped[k].g_sigma_neg = g2_of(claim->g_sigma_neg[k]);
+            S->ped[k].sigma_known = false;   // points from outside: the scalar the state once had says nothing about them
+        }
+        std::memcpy(S->sigma_chain, hashes[m - 1], 32);
+        S->n_sigma_records += m;
     }
     ctx->phase2_verify_stats.total_ms = (float)(now_ms() - t0);
     return MI_OK;

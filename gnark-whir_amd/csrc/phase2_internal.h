@@ -4,7 +4,7 @@
 #include "ctx.h"
 #include "fp12.cuh"
 #include "dev_arena.h"
-#include "../../include/mi355x_groth16_phase2.h"
+#include "../../include/mi355x_groth16_phase2_check.h"
 #include <vector>
 
 struct mi_phase2 {
@@ -15,7 +15,9 @@ struct mi_phase2 {
     // device arrays, affine
     void *g1_a = nullptr, *g1_b = nullptr, *g2_b = nullptr, *g1_k = nullptr, *g1_z = nullptr, *vk_k = nullptr;
     u64 n_a = 0, n_b = 0, n_k = 0, n_vk = 0;
-    struct Ped { void *basis = nullptr, *bes = nullptr; u64 n = 0; Fr sigma; };
+    // g_sigma_neg = [-sigma]2 is what the library's outputs are made from; the scalar is a convenience that holds only while sigma_known
+    // (until the state adopts points from outside), and nothing is computed from it after mi_phase2_init
+    struct Ped { void *basis = nullptr, *bes = nullptr; u64 n = 0; Fr sigma; bool sigma_known = true; G2Aff g_sigma_neg; };
     std::vector<Ped> ped;
     G1Aff alpha1, beta1, delta1;
     G2Aff beta2, gamma2, delta2;
@@ -23,6 +25,9 @@ struct mi_phase2 {
     // (the transcript id until there is one)
     u64 n_records = 0;
     uint8_t chain[32] = {0};
+    // the chain of proved contributions to sigma: a second one, which starts from the same transcript id
+    u64 n_sigma_records = 0;
+    uint8_t sigma_chain[32] = {0};
 };
 
 // null rows and rows shorter than the circuit needs (tau_g1: 2 N, the others: N)
@@ -40,6 +45,11 @@ int32_t mi_srs_check_rows_dev(mi_ctx *ctx, const char *who, const mi_srs_desc *r
 // mi_phase2_init, or with on_device the same reading the SRS rows from device arrays (phase1.hip's handover: rows as above, the counts
 // the arrays' own, so that a circuit they are too short for is refused as a short row is)
 int32_t mi_phase2_init_rows(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_srs_desc *rows, bool on_device, const mi_fr *sigma, uint32_t flags, mi_phase2 **out);
+// BasisExpSigma_k and g_sigma_neg_k times sf[k] for every commitment (k_phase2_scale_g1 / _g2): the sigma half of mi_phase2_contribute, and
+// all of mi_phase2_contribute_sigma_proved's device work.  The stream is idle on return
+int32_t mi_phase2_scale_sigma(mi_ctx *ctx, mi_phase2 *S, const Fr *sf);
+// the Pedersen verifying pairs {g2, g_sigma_neg_k} of the state's points
+void mi_phase2_pedersen_vk_of(const mi_phase2 *S, mi_pedersen_vk *out);
 
 // ---------------------------------------------------------------------------------------------------- shared with keyaudit.hip
 // The steps of a same-ratio test as phase2_check.hip runs them, for the audit of a key (include/mi355x_groth16_keyaudit.h).

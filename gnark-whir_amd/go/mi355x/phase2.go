@@ -11,9 +11,11 @@
 // The keys leave as the streams of keyfile.go (LoadKeyStream / LoadVerifyingKeyStream read them back in any later process).
 // What makes the result checkable (include/mi355x_groth16_phase2_check.h) is at the end of this file: CheckSRS (the pairing check
 // that the rows are consistent powers; call it before InitPhase2), ContributeProved (a contribution with its Schnorr record),
-// VerifyRecords and VerifyAdopt (a contributor's claimed state checked against one's own, then taken over).  NOT here, and not in the
+// VerifyRecords and VerifyAdopt (a contributor's claimed state checked against one's own, then taken over), and the same for the
+// commitment keys' sigma: ContributeSigmaProved, VerifySigmaRecords, VerifyAdoptSigma, ChainInfo, and PedersenVK for the verifying half
+// of a sealed key -- a ceremony starts from sigma = 1 and nobody holds the scalar.  NOT here, and not in the
 // library: gnark's mpcsetup file formats (their layout is not available to this project: the SRS and the records cross this interface
-// as slices, in this project's own layout), a record for sigma.  The SRS itself comes from a ceremony of its own: phase1.go.  The walk
+// as slices, in this project's own layout).  The SRS itself comes from a ceremony of its own: phase1.go.  The walk
 // over gnark's constraints below
 // (GetR1Cs, Term.CoeffID / WireID) is written from memory of gnark v0.11 and has never been compiled.
 package mi355x
@@ -200,6 +202,9 @@ const (
 	Phase2BadDelta
 	Phase2BadZ
 	Phase2BadK
+	Phase2BadSigmaRecord // VerifyAdoptSigma's bits from here on (MI_PHASE2_BAD_SIGMA_RECORD, _SIGMA_LINK, _BES)
+	Phase2BadSigmaLink
+	Phase2BadBES
 )
 
 // Record is one contribution's proof of knowledge: mi_phase2_record, word for word.
@@ -285,6 +290,118 @@ func (p *Phase2) VerifyAdopt(c *Claim, recs []Record) (failed uint32, firstBadRe
 	var fb C.uint64_t
 	err = status(p.ctx, C.mi_phase2_verify_adopt(p.ctx, p.st, &cl, (*C.mi_phase2_record)(unsafe.Pointer(&recs[0])), C.size_t(len(recs)), nil, &mask, &fb))
 	return uint32(mask), uint64(fb), err
+}
+
+// PedersenVK is one commitment's verifying pair: mi_pedersen_vk, word for word.
+type PedersenVK struct {
+	G, GSigmaNeg bn254.G2Affine
+}
+
+// SigmaProof is one commitment's part of a step of the sigma chain: mi_phase2_sigma_proof, word for word.
+type SigmaProof struct {
+	GSigmaNeg, Commit bn254.G2Affine
+	Response          fr.Element
+}
+
+// SigmaClaim is what a contributor to sigma hands over: per commitment the array of mi_phase2_get_array (MI_PHASE2_BASIS + 2k + 1)
+// and the point [-sigma_k]2.
+type SigmaClaim struct {
+	BasisExpSigma [][]bn254.G1Affine
+	GSigmaNeg     []bn254.G2Affine
+}
+
+// ChainInfo says where the two chains of a state stand: mi_phase2_chain_info.
+type ChainInfo struct {
+	NCommitments  uint32
+	NRecords      uint64
+	Chain         [32]byte
+	NSigmaRecords uint64
+	SigmaChain    [32]byte
+}
+
+// PedersenVK returns the pairs {g2, [-sigma_k]2} of the state's points: what goes into the verifying key of a sealed state.
+func (p *Phase2) PedersenVK() ([]PedersenVK, error) {
+	info, err := p.ChainInfo()
+	if err != nil || info.NCommitments == 0 {
+		return nil, err
+	}
+	out := make([]PedersenVK, info.NCommitments)
+	err = status(p.ctx, C.mi_phase2_get_pedersen_vk(p.ctx, p.st, (*C.mi_pedersen_vk)(unsafe.Pointer(&out[0]))))
+	return out, err
+}
+
+// ChainInfo reads the record counts and chain values of the delta chain and of the sigma chain.
+func (p *Phase2) ChainInfo() (ChainInfo, error) {
+	var ci C.mi_phase2_chain_info
+	if err := status(p.ctx, C.mi_phase2_get_chain_info(p.ctx, p.st, &ci)); err != nil {
+		return ChainInfo{}, err
+	}
+	out := ChainInfo{NCommitments: uint32(ci.n_commitments), NRecords: uint64(ci.n_records), NSigmaRecords: uint64(ci.n_sigma_records)}
+	copy(out.Chain[:], C.GoBytes(unsafe.Pointer(&ci.chain[0]), 32))
+	copy(out.SigmaChain[:], C.GoBytes(unsafe.Pointer(&ci.sigma_chain[0]), 32))
+	return out, nil
+}
+
+// ContributeSigmaProved re-randomises every commitment's sigma as Contribute(1, sigmaFactor) does and returns the step: one proof per
+// commitment and the chain value after it (the nonces are the library's).  One factor per commitment.
+func (p *Phase2) ContributeSigmaProved(sigmaFactor []fr.Element) ([]SigmaProof, [32]byte, error) {
+	var h [32]byte
+	if len(sigmaFactor) == 0 {
+		return nil, h, errors.New("mi355x: no sigma factor")
+	}
+	out := make([]SigmaProof, len(sigmaFactor))
+	err := status(p.ctx, C.mi_phase2_contribute_sigma_proved(p.ctx, p.st, (*C.mi_fr)(unsafe.Pointer(&sigmaFactor[0])), nil,
+		(*C.mi_phase2_sigma_proof)(unsafe.Pointer(&out[0])), (*C.uint8_t)(unsafe.Pointer(&h[0]))))
+	return out, h, err
+}
+
+// VerifySigmaRecords checks the chain of len(hashes) steps (proofs: len(start) per step) continuing (start, startHash, firstIndex) on
+// the host; firstBad == len(hashes): all hold.
+func VerifySigmaRecords(start []bn254.G2Affine, startHash [32]byte, firstIndex uint64, proofs []SigmaProof, hashes [][32]byte) (firstBad uint64, err error) {
+	if len(start) == 0 || len(proofs) != len(start)*len(hashes) {
+		return 0, errors.New("mi355x: no start point, or proofs that are not one per commitment and step")
+	}
+	var pp *C.mi_phase2_sigma_proof
+	var hp *[32]C.uint8_t
+	if len(hashes) > 0 {
+		pp = (*C.mi_phase2_sigma_proof)(unsafe.Pointer(&proofs[0]))
+		hp = (*[32]C.uint8_t)(unsafe.Pointer(&hashes[0]))
+	}
+	var fb C.uint64_t
+	if rc := C.mi_phase2_sigma_records_verify((*C.mi_g2_affine)(unsafe.Pointer(&start[0])), C.uint32_t(len(start)), (*C.uint8_t)(unsafe.Pointer(&startHash[0])),
+		C.uint64_t(firstIndex), pp, hp, C.size_t(len(hashes)), &fb); rc != C.MI_OK {
+		return 0, fmt.Errorf("mi355x: mi_phase2_sigma_records_verify rc=%d", int(rc))
+	}
+	return uint64(fb), nil
+}
+
+// VerifyAdoptSigma checks a contributor's claimed BasisExpSigma arrays and [-sigma]2 points and the steps against this state and, when
+// failed == 0 and only then, takes them over and advances the sigma chain.  badCommitments has bit k set where commitment k's
+// relation fails.  The seed of the test's coefficients is the operating system's.
+func (p *Phase2) VerifyAdoptSigma(c *SigmaClaim, proofs []SigmaProof, hashes [][32]byte) (failed uint32, badCommitments, firstBadRecord uint64, err error) {
+	if c == nil || len(hashes) == 0 || len(c.BasisExpSigma) == 0 || len(c.BasisExpSigma) != len(c.GSigmaNeg) || len(proofs) != len(hashes)*len(c.GSigmaNeg) {
+		return 0, 0, 0, errors.New("mi355x: nil claim, no step, or counts that do not agree")
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	nc := len(c.BasisExpSigma)
+	// the two per-commitment arrays live in C memory: a Go array of Go pointers may not cross
+	ptrs := (*[1 << 20]*C.mi_g1_affine)(C.malloc(C.size_t(nc) * C.size_t(unsafe.Sizeof(uintptr(0)))))
+	counts := (*[1 << 20]C.uint64_t)(C.malloc(C.size_t(nc) * 8))
+	defer C.free(unsafe.Pointer(ptrs))
+	defer C.free(unsafe.Pointer(counts))
+	for k, a := range c.BasisExpSigma {
+		ptrs[k], counts[k] = g1(&pin, a), C.uint64_t(len(a))
+	}
+	var cl C.mi_phase2_sigma_claim
+	cl.basis_exp_sigma = (**C.mi_g1_affine)(unsafe.Pointer(ptrs))
+	cl.n = (*C.uint64_t)(unsafe.Pointer(counts))
+	cl.g_sigma_neg = g2(&pin, c.GSigmaNeg)
+	var mask C.uint32_t
+	var bad, fb C.uint64_t
+	err = status(p.ctx, C.mi_phase2_verify_adopt_sigma(p.ctx, p.st, &cl, (*C.mi_phase2_sigma_proof)(unsafe.Pointer(&proofs[0])),
+		(*[32]C.uint8_t)(unsafe.Pointer(&hashes[0])), C.size_t(len(hashes)), nil, &mask, &bad, &fb))
+	return uint32(mask), uint64(bad), uint64(fb), err
 }
 
 // Close frees the state and its context.

@@ -26,6 +26,7 @@
 #include "../../include/mi355x_groth16_verify_combined.h"
 #include "../../include/mi355x_groth16_verify_wave.h"
 #include "../../include/mi355x_groth16_phase2.h"
+#include "../../include/mi355x_groth16_phase2_check.h"
 #include "../../include/mi355x_groth16_debug.h"   // (this mirror is the TEST side: generators and knobs)
 
 namespace groth16 {
@@ -373,7 +374,9 @@ inline mi_fr HashToField(const std::string &dst, const std::vector<uint8_t> &msg
     return out;
 }
 // mpcsetup's phase 2 (include/mi355x_groth16_phase2.h): the circuit's keys derived on the device from a powers-of-tau SRS, delta
-// re-randomised by contributors.  NOT here: the pairing check of the SRS, the contributions' proofs, gnark's mpcsetup file formats.
+// re-randomised by contributors.  The commitment keys' sigma is re-randomised with a proof per step and adopted by the next party
+// (include/mi355x_groth16_phase2_check.h): ContributeSigmaProved / VerifyAdoptSigma / PedersenVk / ChainInfo below and
+// VerifySigmaRecords beside the class.  NOT here: the pairing check of the SRS, delta's proofs, gnark's mpcsetup file formats.
 //   p2 := mpcsetup.InitPhase2(r1cs, &srs)      groth16::Phase2 p2(ctx, r1cs, srs, sigma)
 //   p2.Contribute()                            p2.Contribute(delta)            // the caller samples delta (and must forget it)
 //   pk, vk := mpcsetup.ExtractKeys(...)        p2.Seal(vk) / p2.Streams(...)   // as often as wanted: sealing does not end the ceremony
@@ -402,11 +405,44 @@ class Phase2 {
         pk.resize(len); vk.resize(vkLen);
         ctx_.check(mi_phase2_to_streams(ctx_.get(), st_, encoding, pk.data(), pk.size(), &len, vk.data(), vk.size(), &vkLen));
     }
+    // ---- sigma (include/mi355x_groth16_phase2_check.h): the state's points, a proved step, a claimed state checked and taken
+    // {g2, [-sigma_k]2} per commitment: what goes into mi_vk_desc.ped for the key Seal hands out
+    std::vector<mi_pedersen_vk> PedersenVk() const {
+        std::vector<mi_pedersen_vk> out(ChainInfo().n_commitments);
+        ctx_.check(mi_phase2_get_pedersen_vk(ctx_.get(), st_, out.empty() ? nullptr : out.data()));
+        return out;
+    }
+    mi_phase2_chain_info ChainInfo() const {
+        mi_phase2_chain_info info;
+        ctx_.check(mi_phase2_get_chain_info(ctx_.get(), st_, &info));
+        return info;
+    }
+    // one factor per commitment; the nonces are the library's.  Returns the step's proofs, hash takes the chain value after it
+    std::vector<mi_phase2_sigma_proof> ContributeSigmaProved(const std::vector<mi_fr> &sigmaFactor, uint8_t hash[32]) {
+        std::vector<mi_phase2_sigma_proof> out(sigmaFactor.size());
+        ctx_.check(mi_phase2_contribute_sigma_proved(ctx_.get(), st_, sigmaFactor.data(), nullptr, out.data(), hash));
+        return out;
+    }
+    // failed == 0, and only then: the claimed BasisExpSigma arrays and [-sigma]2 points are the state's and the sigma chain has advanced
+    uint32_t VerifyAdoptSigma(const mi_phase2_sigma_claim &claim, const std::vector<mi_phase2_sigma_proof> &proofs, const uint8_t (*hashes)[32], size_t steps,
+                              uint64_t *badCommitments, uint64_t *firstBadRecord = nullptr) {
+        uint32_t failed = 0;
+        ctx_.check(mi_phase2_verify_adopt_sigma(ctx_.get(), st_, &claim, proofs.data(), hashes, steps, nullptr, &failed, badCommitments, firstBadRecord));
+        return failed;
+    }
 
   private:
     const Context &ctx_;
     mi_phase2 *st_ = nullptr;
 };
+// the sigma chain of `steps` steps continuing (start, startHash, firstIndex), on the host: the index of the first step that does not hold
+inline uint64_t VerifySigmaRecords(const std::vector<mi_g2_affine> &start, const uint8_t startHash[32], uint64_t firstIndex,
+                                   const std::vector<mi_phase2_sigma_proof> &proofs, const uint8_t (*hashes)[32], size_t steps) {
+    uint64_t firstBad = 0;
+    if (mi_phase2_sigma_records_verify(start.data(), (uint32_t)start.size(), startHash, firstIndex, proofs.data(), hashes, steps, &firstBad) != MI_OK)
+        throw Error(MI_EINVAL, "VerifySigmaRecords: a null argument, no commitment, or a start point off the twist or at infinity");
+    return firstBad;
+}
 // fft.Domain: FFT / FFTInverse with fft.DIF / fft.DIT and fft.OnCoset()
 enum Decimation { DIF = 0, DIT = 1 };
 inline void FFT(const Context &ctx, std::vector<mi_fr> &a, uint32_t logN, Decimation d, bool onCoset = false) {

@@ -30,8 +30,8 @@
  * a mask of 0 says nothing.
  *
  * NOT COVERED:
- *   - who knows delta or sigma: that is what the records of contributions say (mi355x_groth16_phase2_check.h), and sigma still has
- *     none.  The audit says that BasisExpSigma is sigma Basis for the sigma of g_sigma_neg, not that nobody kept sigma;
+ *   - who knows delta or sigma: that is what the records of contributions say (mi355x_groth16_phase2_check.h: the delta chain and the
+ *     sigma chain).  The audit says that BasisExpSigma is sigma Basis for the sigma of g_sigma_neg, not that nobody kept sigma;
  *   - encodings and mask canonicity: the audit judges group elements.  A wire flagged finite whose point is (0, 0) in the arrays, or
  *     two encodings of one stream, are the loaders' business (a stream is decoded by exactly their code, refusals included);
  *   - gnark's formats: the stream layouts carry the "recalled, not pinned to gnark" caveat of the loaders this header shares them

@@ -35,7 +35,9 @@
  *   - the contributions' proofs of knowledge of delta and the verification of a transcript of contributions: mi_phase2_contribute
  *     below moves delta and leaves no record.  mi_phase2_contribute_proved writes a Schnorr record per contribution, and
  *     mi_phase2_verify_adopt checks a contributor's claimed Z, K and delta points against one's own state and takes them over
- *     (mi_phase2_get_array exports what it takes back).  The commitment keys' sigma has no such record (that header says what is left);
+ *     (mi_phase2_get_array exports what it takes back).  The commitment keys' sigma has the same there, over the state's points
+ *     [-sigma_k]2: mi_phase2_contribute_sigma_proved, mi_phase2_verify_adopt_sigma, and mi_phase2_get_pedersen_vk for the sealed key's
+ *     verifying half, so that a ceremony starts from sigma = 1 and nobody holds the scalar;
  *   - gnark's mpcsetup file formats (Phase1 / Phase2 WriteTo): their layout is NOT AVAILABLE to this project (no gnark on the machines
  *     this was written on), so the SRS, the state and the records cross this interface as plain arrays in this project's own layout.
  *     The keys leave as the streams of mi355x_groth16_keyfile.h and mi355x_groth16_vkfile.h, with those headers' caveats.
@@ -83,12 +85,15 @@ typedef struct mi_phase2_stats {
  * the lowest bad index in it.  Only the first 2 N / N points of a row are read and checked. */
 int32_t mi_phase2_init(mi_ctx *ctx, const mi_r1cs_desc *r1cs, const mi_srs_desc *srs, const mi_fr *sigma, uint32_t flags, mi_phase2 **out);
 /* Contribute: Z and the private wires' K are multiplied by 1 / delta, delta1 and delta2 by delta, BasisExpSigma[k] by sigma_factor[k]
- * (NULL = all 1), and the state's sigma[k] becomes sigma[k] sigma_factor[k].  Nothing else changes.  delta = 0 or a sigma_factor of 0:
+ * (NULL = all 1), and the state's point [-sigma_k]2 -- which the verifying key's stream and mi_phase2_get_pedersen_vk are written
+ * from -- by sigma_factor[k] as well.  Nothing else changes.  delta = 0 or a sigma_factor of 0:
  * MI_EINVAL and the state is as it was. */
 int32_t mi_phase2_contribute(mi_ctx *ctx, mi_phase2 *st, const mi_fr *delta, const mi_fr *sigma_factor);
 /* ExtractKeys: the state's arrays are COPIED into an ordinary mi_pk (fixed-base tables and all, as any adopted key), the commitments'
  * Pedersen keys (ped_out: room for n_commitments handles; may be NULL when there are none) and the verifying key's points (vk_out as
- * for mi_groth16_setup).  Sealing does not end the ceremony: one state can be sealed after every contribution. */
+ * for mi_groth16_setup).  The Pedersen pairs for mi_vk_desc.ped come from the state's points: mi_phase2_get_pedersen_vk
+ * (mi355x_groth16_phase2_check.h), so no caller needs sigma.  Sealing does not end the ceremony: one state can be sealed after every
+ * contribution. */
 int32_t mi_phase2_seal(mi_ctx *ctx, const mi_phase2 *st, mi_pk **pk_out, mi_pedersen_pk **ped_out, mi_vk_out *vk_out);
 /* Both keys as gnark's streams, written from the state's arrays: the out / cap / len triples of mi_groth16_setup_to_streams (cap too
  * small: MI_EINVAL with both *len and *vk_len set). */

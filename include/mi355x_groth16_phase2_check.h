@@ -26,12 +26,15 @@
  * THE RECORDS OF CONTRIBUTIONS ARE THIS PROJECT'S OWN FORMAT.  gnark's mpcsetup layouts are not available to this project (see
  * mi355x_groth16_phase2.h); a transcript written here is read here.
  *
+ * SIGMA HAS A CHAIN OF ITS OWN.  mi_phase2_contribute_proved leaves sigma / BasisExpSigma alone and mi_phase2_verify_adopt takes none from
+ * outside; the re-randomisation of the commitment keys is proved, chained and adopted by the calls of the last section below
+ * (mi_phase2_contribute_sigma_proved, mi_phase2_sigma_records_verify, mi_phase2_verify_adopt_sigma).  The state holds [-sigma_k]2 as a
+ * point, so no party -- this library included -- needs the scalar after mi_phase2_init, which a ceremony calls with sigma = 1.
+ *
  * NOT COVERED:
- *   - sigma / BasisExpSigma: mi_phase2_contribute_proved leaves them alone and mi_phase2_verify_adopt takes none from outside (the
- *     adopting state's stay its own), so the re-randomisation of the commitment keys has no proof of knowledge and no chain;
  *   - gnark's Phase1 / Phase2 file formats.
  * That BasisExpSigma IS sigma Basis for the sigma of the verifying key, and every other array the key of its circuit under its SRS, is
- * what mi355x_groth16_keyaudit.h checks without the derivation; who knows sigma it cannot say either.
+ * what mi355x_groth16_keyaudit.h checks without the derivation; who contributed to sigma is what the sigma chain says.
  * mi_srs_check_powers says that the rows ARE powers of one (tau, alpha, beta), not who contributed to them: that is what a phase-1 transcript
  * says, and mi355x_groth16_phase1.h makes and verifies one (its mi_phase1_verify_adopt and mi_phase1_check run the relations below over
  * rows that are on the device already).
@@ -39,6 +42,7 @@
 #ifndef MI355X_GROTH16_PHASE2_CHECK_H
 #define MI355X_GROTH16_PHASE2_CHECK_H
 #include "mi355x_groth16_phase2.h"
+#include "mi355x_groth16_verify.h"   /* mi_pedersen_vk */
 
 #ifdef __cplusplus
 extern "C" {
@@ -86,7 +90,8 @@ typedef struct mi_phase2_record {
  * c_i    = le integer of the first 16 bytes of SHA-256("mi355x-phase2-challenge" | hash_i);   accept iff [z] delta1_before = T + [c] delta1
  * compress = mi_g1_compress; hash_(-1) = the state's transcript id (32 zero bytes unless set) */
 
-/* The id the first record's hash continues.  Only before the first record of the state: else MI_EINVAL. */
+/* The id the first record's hash continues, of the delta chain and of the sigma chain alike.  Only before the first record of either
+ * chain of the state: else MI_EINVAL. */
 int32_t mi_phase2_set_transcript_id(mi_ctx *ctx, mi_phase2 *st, const uint8_t id[32]);
 /* Does to the arrays exactly what mi_phase2_contribute(st, delta, NULL) does, then writes the record of that step and advances the
  * state's chain (its record count and chain hash).  nonce: the Schnorr nonce k, which must be secret, fresh and uniform -- NULL: drawn
@@ -125,6 +130,72 @@ int32_t mi_phase2_verify_adopt(mi_ctx *ctx, mi_phase2 *st, const mi_phase2_claim
 /* Times of the last mi_phase2_verify_adopt on ctx, as mi_srs_check_stats (msm_g1: four MSMs; msm_g2_ms stays 0; pairing: six Miller loops
  * and three final exponentiations; point_check: the claimed arrays on the curve). */
 int32_t mi_phase2_verify_get_stats(mi_ctx *ctx, mi_srs_check_stats *out);
+
+/* ---------------------------------------------------------------- sigma: the state's points, proved contributions, a claimed state
+ * Per commitment k the state holds g_sigma_neg_k = [-sigma_k]2 beside Basis_k and BasisExpSigma_k = sigma_k Basis_k: mi_phase2_init makes
+ * the point as mi_pedersen_vk_make does, mi_phase2_contribute with a sigma_factor multiplies it, and everything that writes the verifying
+ * half of the commitment keys (mi_phase2_to_streams, mi_key_claim_from_phase2) reads the state's points.  out[k] = {g2, g_sigma_neg_k}:
+ * what a caller of mi_phase2_seal puts into mi_vk_desc.ped.  MI_EINVAL: a null argument (out may be null for a state without commitments). */
+int32_t mi_phase2_get_pedersen_vk(mi_ctx *ctx, const mi_phase2 *st, mi_pedersen_vk *out /* n_commitments */);
+
+/* One contribution step re-randomises ALL commitments of the state under one challenge (a Schnorr proof per commitment over the twist) */
+typedef struct mi_phase2_sigma_proof {   /* one per commitment */
+    mi_g2_affine g_sigma_neg;            /* AFTER this step: [s_k] before_k */
+    mi_g2_affine commit;                 /* T_k = [n_k] before_k */
+    mi_fr        response;               /* z_k = n_k + c s_k mod r (Montgomery) */
+} mi_phase2_sigma_proof;
+/* hash_i = SHA-256("mi355x-phase2-sigma-record" | hash_(i-1) | le64(i) | le32(n_commitments) |
+ *                  for k: compress2(before_k) | compress2(after_k) | compress2(T_k))
+ * c_i    = le integer of the first 16 bytes of SHA-256("mi355x-phase2-sigma-challenge" | hash_i)
+ * accept iff the hash matches and [z_k] before_k = T_k + [c_i] after_k for every k
+ * compress2 = mi_g2_compress.  The chain is the state's SECOND one: its own record count and its own 32-byte chain value, which starts
+ * from the same transcript id as the delta chain.  The delta chain above does not change by a byte. */
+
+/* Does to BasisExpSigma_k and g_sigma_neg_k exactly what mi_phase2_contribute(st, 1, sigma_factor) does and touches nothing that depends
+ * on delta, then writes the step (n_commitments proofs and the chain value after it) and advances the sigma chain.  nonce: as
+ * mi_phase2_contribute_proved's, one per commitment.  MI_EINVAL, the state bit for bit as it was: a null argument, a state without
+ * commitments, a factor or nonce that is 0 or not below r.  MI_ENODEV: nonce == NULL and no randomness. */
+int32_t mi_phase2_contribute_sigma_proved(mi_ctx *ctx, mi_phase2 *st, const mi_fr *sigma_factor /* [n_commitments] */,
+                                          const mi_fr *nonce /* [n_commitments] or NULL: getrandom */,
+                                          mi_phase2_sigma_proof *out /* [n_commitments] */, uint8_t hash_out[32]);
+/* Host only, no context: the chain of m steps of nc commitments continuing (start, start_hash, first_index).  MI_OK with *first_bad = the
+ * index of the first step that does not hold, m when all hold.  A step one of whose points is off the twist or at infinity, or one of whose
+ * responses is not below r, does not hold.  MI_EINVAL: a null pointer (proofs and hashes may be null with m = 0), nc = 0, a start point
+ * off the twist or at infinity. */
+int32_t mi_phase2_sigma_records_verify(const mi_g2_affine *start /* [nc] */, uint32_t nc, const uint8_t start_hash[32], uint64_t first_index,
+                                       const mi_phase2_sigma_proof *proofs /* [m * nc] */, const uint8_t (*hashes)[32] /* [m] */, size_t m,
+                                       uint64_t *first_bad /* = m when all hold */);
+/* Where the two chains of a state stand: what a verifier keeps books with (the points of sigma: mi_phase2_get_pedersen_vk) */
+typedef struct mi_phase2_chain_info {
+    uint32_t n_commitments, pad_;
+    uint64_t n_records;        /* records of the delta chain so far */
+    uint8_t  chain[32];        /* the value its next record continues: the transcript id until there is a record */
+    uint64_t n_sigma_records;  /* steps of the sigma chain so far */
+    uint8_t  sigma_chain[32];  /* the value its next step continues: the transcript id until there is a step */
+} mi_phase2_chain_info;
+int32_t mi_phase2_get_chain_info(mi_ctx *ctx, const mi_phase2 *st, mi_phase2_chain_info *out);
+
+/* Check a claimed sigma state, then take it.  Basis_k and the generator are the verifier's own; only BasisExpSigma_k and g_sigma_neg_k
+ * come from outside.  The coefficients r_i are those of the top of this file with i the index within the commitment. */
+typedef struct mi_phase2_sigma_claim {          /* HOST pointers */
+    const mi_g1_affine *const *basis_exp_sigma; /* [nc] arrays, layout of mi_phase2_get_array(MI_PHASE2_BASIS + 2k + 1) */
+    const uint64_t *n;                          /* [nc] */
+    const mi_g2_affine *g_sigma_neg;            /* [nc] */
+} mi_phase2_sigma_claim;
+#define MI_PHASE2_BAD_SIGMA_RECORD 16u  /* the sigma chain from the state's (g_sigma_neg, chain, count) fails; *first_bad_record says where */
+#define MI_PHASE2_BAD_SIGMA_LINK   32u  /* some claim.g_sigma_neg[k] is not the last step's */
+#define MI_PHASE2_BAD_BES          64u  /* some k: e(sum_i r_i Basis_k[i], g_sigma_neg'_k) . e(sum_i r_i BES'_k[i], g2) != 1; *bad_commitments bit k */
+/* MI_EINVAL, the state untouched: a null argument, m = 0, a state without commitments (or with more than 64), a count that differs from
+ * the state's, a claimed BasisExpSigma point off its curve ((0, 0) is allowed, where a basis point may be infinity), a claimed g_sigma_neg
+ * off the twist, outside the r-torsion or at infinity.  MI_ENODEV: seed == NULL and no randomness (the rule of the seed is the one at the
+ * top of this file).  Otherwise MI_OK, *failed = the mask and *bad_commitments = the commitments whose MI_PHASE2_BAD_BES relation fails;
+ * every relation is evaluated whatever the others say.  *first_bad_record = m unless MI_PHASE2_BAD_SIGMA_RECORD is set.  With mask 0, and
+ * only then, BasisExpSigma_k and g_sigma_neg_k are replaced and the sigma chain advances by the m steps; otherwise the state is bit for bit
+ * as it was.  The delta chain and everything that depends on delta are not touched either way.  mi_phase2_verify_get_stats reports this
+ * call's times too (msm_g1: two MSMs per commitment; pairing: two Miller loops and one final exponentiation per commitment). */
+int32_t mi_phase2_verify_adopt_sigma(mi_ctx *ctx, mi_phase2 *st, const mi_phase2_sigma_claim *claim, const mi_phase2_sigma_proof *proofs,
+                                     const uint8_t (*hashes)[32], size_t m /* >= 1 */, const uint8_t seed[32] /* may be NULL */, uint32_t *failed,
+                                     uint64_t *bad_commitments, uint64_t *first_bad_record /* may be NULL */);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,9 @@ The checks of a ceremony (include/mi355x_groth16_phase2_check.h); with either fl
               and the mask (0: the SRS is honest)
   --verify    two states from the same SRS (their mi_phase2_init times are this run's yardstick), one mi_phase2_contribute_proved on
               the first, its Z, K and delta points handed to mi_phase2_verify_adopt on the second, ONE run: wall time, phases
-              (mi_phase2_verify_get_stats), peak, the mask (0: adopted) and whether the adopter's Z then equals the contributor's
+              (mi_phase2_verify_get_stats), peak, the mask (0: adopted) and whether the adopter's Z then equals the contributor's;
+              then one mi_phase2_contribute_sigma_proved on the first and its BasisExpSigma and [-sigma]2 handed to
+              mi_phase2_verify_adopt_sigma on the second, timed the same way (one commitment over N / 32 wires)
 """
 import argparse
 import os
@@ -84,6 +86,18 @@ def check_legs(ctx, B, a, N, r1cs, srs, td, say):
             wall = time.perf_counter() - t0
             say(f"verify_adopt log_n={a.log_n} points_z={len(z)} points_k={len(k)} mask={mask} first_bad_record={first_bad} wall_ms={wall * 1e3:.1f} "
                 f"{phases(ctx.srs_check_stats(verify=True))} adopted_z_equals_contributors={np.array_equal(ctx.phase2_array(v, B.PHASE2_G1_Z), z)}")
+            sf = cref.gen_scalars(1, 98, 0)
+            t0 = time.perf_counter()
+            step, h = ctx.phase2_contribute_sigma_proved(st, sf)
+            say(f"contribute_sigma_proved log_n={a.log_n} commitments=1 wall_ms={(time.perf_counter() - t0) * 1e3:.1f}")
+            bes, gs = ctx.phase2_array(st, B.PHASE2_BASIS + 1), ctx.phase2_get_pedersen_vk(st, 1)[:, 1].copy()
+            ctx.trim()
+            t0 = time.perf_counter()
+            mask, bad, first_bad = ctx.phase2_verify_adopt_sigma(v, [bes], gs, step[None], [h])
+            wall = time.perf_counter() - t0
+            say(f"verify_adopt_sigma log_n={a.log_n} commitments=1 points_committed={len(bes)} mask={mask} bad_commitments={bad} first_bad_record={first_bad} "
+                f"wall_ms={wall * 1e3:.1f} {phases(ctx.srs_check_stats(verify=True))} "
+                f"adopted_bes_equals_contributors={np.array_equal(ctx.phase2_array(v, B.PHASE2_BASIS + 1), bes)}")
         finally:
             for s in states:
                 ctx.phase2_free(s)
@@ -101,7 +115,7 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare the state's compressed streams with Setup's")
     ap.add_argument("--write", default=None, help="append the result lines to this file")
     ap.add_argument("--check-srs", action="store_true", help="time mi_srs_check_powers over the SRS")
-    ap.add_argument("--verify", action="store_true", help="time mi_phase2_verify_adopt of one proved contribution")
+    ap.add_argument("--verify", action="store_true", help="time mi_phase2_verify_adopt of one proved contribution, then the same for sigma")
     a = ap.parse_args()
     B = load_binding()
     ctx = B.Context(0)
