@@ -19,7 +19,7 @@ EXPORTS = [
     "mi_ntt", "mi_ntt_dev", "mi_compute_h", "mi_compute_h_dev", "mi_msm_g1", "mi_msm_g1_dev", "mi_msm_g2",
     "mi_msm_g2_dev", "mi_groth16_prove", "mi_groth16_prove_dev", "mi_get_stats", "mi_g1_compress",
     "mi_g2_compress", "mi_proof_write", "mi_g1_sum", "mi_g2_sum", "mi_gen_scalars_dev", "mi_gen_g1_dev",
-    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_field_shape_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_debug_pairing_wave_dev", "mi_debug_fp12_op_wave_dev", "mi_debug_verify_wave_split", "mi_debug_decode_g1_dev", "mi_debug_decode_g2_dev", "mi_debug_hash_to_field_dev", "mi_debug_witness_decode_dev", "mi_debug_fp12_product_dev", "mi_debug_g1_scale128_dev", "mi_debug_g1_sum_tree_dev", "mi_debug_locate_points_dev", "mi_debug_locate_colsums_dev", "mi_debug_set_locate_round_nodes", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
+    "mi_gen_g2_dev", "mi_field_op_dev", "mi_debug_limb29_op_dev", "mi_debug_lazy_op_dev", "mi_debug_field_shape_dev", "mi_debug_pairing_dev", "mi_debug_fp12_op_dev", "mi_debug_pairing_wave_dev", "mi_debug_fp12_op_wave_dev", "mi_debug_verify_wave_split", "mi_debug_verify_pairs_dev", "mi_debug_decode_g1_dev", "mi_debug_decode_g2_dev", "mi_debug_hash_to_field_dev", "mi_debug_witness_decode_dev", "mi_debug_fp12_product_dev", "mi_debug_g1_scale128_dev", "mi_debug_g1_sum_tree_dev", "mi_debug_locate_points_dev", "mi_debug_locate_colsums_dev", "mi_debug_set_locate_round_nodes", "mi_g1_add_dev", "mi_g2_add_dev", "mi_bench_modmul_dev", "mi_bench_valu_dev", "mi_bench_gather_dev",
     "mi_dev_alloc", "mi_dev_free", "mi_dev_upload", "mi_dev_download", "mi_dev_sync",
     "mi_msm_precompute_g1_dev", "mi_msm_precompute_g2_dev", "mi_msm_g1_fixed_dev", "mi_msm_g2_fixed_dev", "mi_msm_table_to_rprime_g1_dev", "mi_msm_table_to_rprime_g2_dev", "mi_pk_table_plan",
     "mi_batch_scalar_mul_g1", "mi_batch_scalar_mul_g1_dev", "mi_batch_scalar_mul_g2", "mi_batch_scalar_mul_g2_dev",
@@ -57,6 +57,10 @@ VERIFY_COMBINED_EXPORTS = ["mi_groth16_verify_combined", "mi_groth16_verify_byte
 VERIFY_LOCATE_EXPORTS = ["mi_groth16_verify_locate", "mi_groth16_verify_bytes_locate"]
 # include/mi355x_groth16_verify_wave.h (one proof, or a few: one wave per pairing, the verdicts of the batch calls)
 VERIFY_WAVE_EXPORTS = ["mi_groth16_verify_wave", "mi_groth16_verify_bytes_wave"]
+# include/mi355x_groth16_verify_ksum.h (the public-input sums of a whole batch over a window table of the key's bases)
+VERIFY_KSUM_EXPORTS = ["mi_vk_ksum_prepare", "mi_vk_ksum_get_info", "mi_vk_ksum_batch_dev", "mi_vk_ksum_batch"]
+KSUM_NOT_BUILT, KSUM_READY, KSUM_OVER_BUDGET, KSUM_NO_MEMORY, KSUM_NO_BASES = 0, 1, 2, 3, 4
+KSUM_DEFAULT_TABLE_BYTES = 64 << 20
 VERIFY_WAVE_SPLIT_PHASES = ("host", "bs_check", "miller", "judge", "copy_back")   # mi_debug_verify_wave_split, ms
 # include/mi355x_groth16_keyfile.h (proving keys as files: bulk point codecs, loading gnark's raw or compressed stream, writing both)
 KEYFILE_EXPORTS = ["mi_g1_decompress_dev", "mi_g2_decompress_dev", "mi_g1_compress_dev", "mi_g2_compress_dev", "mi_pk_stream_inspect", "mi_pk_load_stream",
@@ -404,6 +408,14 @@ class VerifyLocateStats(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class VkKsumInfo(C.Structure):
+    _fields_ = [("window_bits", C.c_uint32), ("windows", C.c_uint32), ("table_bytes", C.c_uint64), ("bases", C.c_uint64), ("budget_bytes", C.c_uint64),
+                ("state", C.c_uint32), ("build_ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: (float if n == "build_ms" else int)(getattr(self, n)) for n, _ in self._fields_}
 
 
 class Bsb22Input(C.Structure):
@@ -1446,6 +1458,38 @@ class VerifyingKey:
         arr, keep = self._inputs(list(proofs)); out = np.full(len(arr), 255, np.uint8); ms = (C.c_float * len(VERIFY_WAVE_SPLIT_PHASES))()
         self.ctx._ck(self.ctx.lib.mi_debug_verify_wave_split(self.ctx.h, self.h, arr, C.c_size_t(len(arr)), _p(out), ms))
         return out, dict(zip(VERIFY_WAVE_SPLIT_PHASES, (float(v) for v in ms)))
+
+    # ---- the sums of a whole batch over the key's window table (include/mi355x_groth16_verify_ksum.h)
+    def ksum_prepare(self, max_table_bytes=0):
+        """mi_vk_ksum_prepare: build (or build again) the table under a byte budget, 0 = the default -> ksum_info()"""
+        self.ctx._ck(self.ctx.lib.mi_vk_ksum_prepare(self.ctx.h, self.h, C.c_uint64(int(max_table_bytes))))
+        return self.ksum_info()
+
+    def ksum_info(self):
+        """mi_vk_ksum_get_info -> dict: window_bits (0 = no table), windows, table_bytes, bases, budget_bytes, state (KSUM_*), build_ms"""
+        info = VkKsumInfo()
+        self.ctx._ck(self.ctx.lib.mi_vk_ksum_get_info(self.ctx.h, self.h, C.byref(info)))
+        return info.as_dict()
+
+    def ksum_batch_dev(self, scalars_ptr, skip_ptr, n, out_ptr):
+        """mi_vk_ksum_batch_dev over raw device pointers (skip_ptr may be None); mi_dev_sync before reading"""
+        self.ctx._ck(self.ctx.lib.mi_vk_ksum_batch_dev(self.ctx.h, self.h, _p(scalars_ptr), _p(skip_ptr), C.c_size_t(n), _p(out_ptr)))
+
+    def ksum_batch(self, scalars, skip=None):
+        """mi_vk_ksum_batch: scalars (n, bases, 4) Montgomery, skip (n,) uint8 or None -> (n, 8) affine points, zeros = infinity"""
+        scalars = _u64(scalars); n = int(scalars.shape[0])
+        skip = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        out = np.zeros((n, 8), np.uint64)
+        self.ctx._ck(self.ctx.lib.mi_vk_ksum_batch(self.ctx.h, self.h, _p(scalars) if n else None, _p(skip), C.c_size_t(n), _p(out) if n else None))
+        return out
+
+    def verify_pairs(self, proofs):
+        """mi_debug_verify_pairs_dev: the pairs the per-proof bodies hand to their Miller loops -> (P (n, np, 8), Q (n, np, 16))"""
+        arr, keep = self._inputs(list(proofs)); n = len(arr)
+        np_ = 3 + (self.n_commitments + 1 if self.n_commitments else 0)
+        P_, Q_ = np.zeros((n, np_, 8), np.uint64), np.zeros((n, np_, 16), np.uint64)
+        self.ctx._ck(self.ctx.lib.mi_debug_verify_pairs_dev(self.ctx.h, self.h, arr, C.c_size_t(n), _p(P_), _p(Q_)))
+        return P_, Q_
 
     # ---- one verdict for the batch (include/mi355x_groth16_verify_combined.h)
     def verify_combined(self, proofs, seed=None):

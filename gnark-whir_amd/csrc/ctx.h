@@ -161,6 +161,9 @@ struct mi_ctx {
     uint64_t z_count_fused_launches = 0;   // computeH last launches that carried the count (mi_debug_get_counter: the tests' proof that the path ran)
     struct ZCountHook { bool armed = false, done = false; int slot = -1; uint32_t n = 0, c = 0; alignas(8) unsigned char shape[64]; uint32_t *C1 = nullptr; const void *h = nullptr; /* the vector whose digits were counted */ } zhook;
     uint32_t locate_round_nodes = 0;     // mi_groth16_verify_locate's node budget per round: 0 = MI_LOCATE_ROUND_NODES (mi_debug_set_locate_round_nodes)
+    uint32_t verify_ksum = 1;            // knob "verify_ksum": 1 = the per-proof bodies stage a batch through the key's window table (ksum.hip), 0 = one MSM per proof
+    uint32_t verify_ksum_min_batch = 8;  // knob "verify_ksum_min_batch": the proofs from which they do (MI_VERIFY_KSUM_MIN_BATCH, verify_internal.h: not faster at n = 1)
+    uint64_t verify_ksum_batches = 0, verify_ksum_launches = 0;   // batches staged that way and the kernel launches of their stages (mi_debug_get_counter)
     uint32_t hold_accum = 0;             // prove: 1 = the wire MSMs' bucket accumulations wait for computeH (mi_debug_set_prove_schedule; measured: no gain)
 };
 

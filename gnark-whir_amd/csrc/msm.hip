@@ -355,6 +355,8 @@ extern "C" int32_t mi_debug_get_counter(mi_ctx *ctx, const char *name, uint64_t 
     if (!std::strcmp(name, "dense_item_sorts")) { *out = ctx->dense_item_sorts.load(); return MI_OK; }
     if (!std::strcmp(name, "generic_sorts_two_pass")) { *out = ctx->generic_sorts_two_pass.load(); return MI_OK; }
     if (!std::strcmp(name, "generic_sorts_one_pass")) { *out = ctx->generic_sorts_one_pass.load(); return MI_OK; }
+    if (!std::strcmp(name, "verify_ksum_batches")) { *out = ctx->verify_ksum_batches; return MI_OK; }
+    if (!std::strcmp(name, "verify_ksum_launches")) { *out = ctx->verify_ksum_launches; return MI_OK; }
     if (!std::strcmp(name, "hip_failure_countdown")) { const int v = mi_fault_countdown.load(); *out = v > 0 ? (uint64_t)v : 0; return MI_OK; }
     MI_FAIL(ctx, MI_EINVAL, std::string("unknown counter: ") + name);
 }
@@ -1077,6 +1079,8 @@ int32_t mi_debug_set_knob(mi_ctx *ctx, const char *name, int64_t value) {
     else if (is("finisher_min_level") && value >= 0 && value <= 16) k->finisher_min_level = (u32)value;
     else if (is("scale_powers_window") && (value == 0 || (value >= 2 && value <= 5))) ctx->scale_powers_window = (uint32_t)value;   // phase1.hip
     else if (is("scale_powers_chunk") && (value == 0 || (value >= 64 && value <= (1 << 24)))) ctx->scale_powers_chunk = (uint32_t)value;
+    else if (is("verify_ksum") && (value == 0 || value == 1)) ctx->verify_ksum = (uint32_t)value;   // verify.hip: the stage of the per-proof bodies
+    else if (is("verify_ksum_min_batch") && value >= 1 && value <= (1 << 24)) ctx->verify_ksum_min_batch = (uint32_t)value;
     else if (mi_ntt_set_knob(ctx, name, value)) return MI_OK;
     else MI_FAIL(ctx, MI_EINVAL, std::string("mi_debug_set_knob: unknown knob or value out of range: ") + name);
     return MI_OK;

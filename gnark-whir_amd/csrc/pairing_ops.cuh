@@ -94,7 +94,7 @@ inline bool verify_well_formed(const VerifyKeyRef &vk, const VerifyProofRef &in,
 // The pairs of one proof, p[] and q[] of verify_pairs_per_proof entries in the order below.  msm = sum_i public_inputs[i] K[1 + i] +
 // sum_k commitment_values[k] K[nb_public + k], affine ((0, 0) = infinity, also when there is no scalar at all).  A proof that is not
 // well formed gets pairs of infinities: its verdict is decided, and its words stay out of the arithmetic.
-inline void verify_assemble(const VerifyKeyRef &vk, const VerifyProofRef &in, bool well_formed, const G1Aff &msm, G1Aff *p, G2Aff *q) {
+MI_HD void verify_assemble(const VerifyKeyRef &vk, const VerifyProofRef &in, bool well_formed, const G1Aff &msm, G1Aff *p, G2Aff *q) {
     const u32 nc = vk.n_commitments, np = verify_pairs_per_proof(nc);
     if (!well_formed) {
         for (u32 j = 0; j < np; j++) { p[j] = G1Aff{Fp::zero(), Fp::zero()}; q[j] = G2Aff{Fp2::zero(), Fp2::zero()}; }
@@ -117,6 +117,25 @@ inline void verify_assemble(const VerifyKeyRef &vk, const VerifyProofRef &in, bo
             pw = pw * ch;
         }
     }
+}
+
+// The same for proof i of a staged batch whose arrays lie side by side: what one lane of k_verify_assemble (verify.hip) runs over device
+// arrays and the host build of the tests over host ones.  ar, bs, krs, pok: one record per proof; cm: nc per proof; fold: one per proof,
+// read with nc > 1 only; flags[i] != 0: not well formed; msm[i]: the scalar part of kSum.  p, q: verify_pairs_per_proof entries per proof.
+struct VerifyAssembleArrays {
+    VerifyKeyRef key;
+    const G1Aff *ar;
+    const G2Aff *bs;
+    const G1Aff *krs, *cm, *pok;
+    const Fr *fold;
+    const uint8_t *flags;
+    const G1Aff *msm;
+};
+MI_HD void verify_assemble_lane(const VerifyAssembleArrays &a, size_t i, G1Aff *p, G2Aff *q) {
+    const u32 nc = a.key.n_commitments, np = verify_pairs_per_proof(nc);
+    const VerifyProofRef in{a.ar + i, a.bs + i, a.krs + i, a.cm + i * nc, a.pok + i, nullptr, nullptr, a.fold + i};
+    const G1Aff msm = a.msm[i];
+    verify_assemble(a.key, in, a.flags[i] == 0, msm, p + i * np, q + i * np);
 }
 
 // The host's view of one batch before any device work: what mi_verify_run and mi_verify_combined_run (through mi_verify_open, verify.hip)

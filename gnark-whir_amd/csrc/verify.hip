@@ -4,10 +4,14 @@
 // One batch, every launch on ctx->stream:
 //   host      mi_verify_open, the start of every body: the argument checks, then the VerifyStage (the range checks of every word and the
 //             curve checks of the G1 points, verify_well_formed: a proof that fails them is malformed and goes no further; the scalars
-//             of kSum); then mi_verify_stage_pairs, the host half this body shares with the wave body: per proof one G1 MSM over the
-//             key's resident K[1..] (mi_verify_msm over msm.hip), then kSum = K[0] + that + sum C_k, the folded commitments c^k C_k and
-//             the layout of the pairs (verify_assemble), and the pairs and flags up.  Stage and functions live in pairing_ops.cuh,
-//             where the host build of the tests runs them too
+//             of kSum); then mi_verify_stage_pairs, the stage this body shares with the wave body.  With a window table on the key
+//             (ksum.hip) the host gathers the proofs' points with copies and uploads them once, the sums of every row over K[1..]
+//             take three launches whatever the batch's size, and k_verify_assemble, one lane per proof, forms kSum = K[0] + that +
+//             sum C_k, the folded commitments c^k C_k and the layout of the pairs (verify_assemble).  Without one (the knob
+//             "verify_ksum" at 0, or a key whose table does not fit) the older loop: per proof one G1 MSM over the resident K[1..]
+//             (mi_verify_msm over msm.hip) and verify_assemble on the host, then the pairs up.  Stage and functions live in
+//             pairing_ops.cuh, where the host build of the tests runs them too
+//   k_verify_assemble   one lane per proof: its pairs into the stage's regions
 //   k_verify_g2_check   one lane per proof: Bs on the twist and in its r-torsion -> the malformed flag
 //   k_pairing_miller    one lane per (proof, pair): a Miller loop, 384 B out
 //   k_verify_judge      one lane per proof: the products of its Miller values, the final exponentiations, the comparisons -> a verdict byte
@@ -62,6 +66,13 @@ __global__ void __launch_bounds__(64, 1) k_verify_judge(const Fp12 *ml, u32 pair
     verdicts[i] = verify_judge(ml + i * pairs_per_proof, pairs_per_proof - MI_VERIFY_GROTH_PAIRS, &eab, flags[i] != 0);
 }
 
+// one lane per proof: its pairs from the gathered arrays of the stage and its row's sum (verify_assemble, the text the host ran before)
+__global__ void __launch_bounds__(64, 1) k_verify_assemble(const VerifyAssembleArrays a, G1Aff *p, G2Aff *q, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    verify_assemble_lane(a, i, p, q);
+}
+
 G1Aff g1_of(const mi_g1_affine &p) { G1Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
 G2Aff g2_of(const mi_g2_affine &p) { G2Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
 static_assert(sizeof(mi_pedersen_vk) == 2 * sizeof(G2Aff) && sizeof(mi_g1_affine) == sizeof(G1Aff) && sizeof(mi_fr) == sizeof(Fr),
@@ -114,19 +125,65 @@ int32_t mi_verify_stage_pairs(mi_ctx *ctx, const mi_vk *vk, const VerifyStage &s
     WsCut cut;
     const size_t off_scal = cut.take(n * ns * sizeof(Fr)), off_p = cut.take(n * np * sizeof(G1Aff)), off_q = cut.take(n * np * sizeof(G2Aff));
     const size_t off_ml = cut.take(n * np * sizeof(Fp12)), off_fl = cut.take(n), off_vd = cut.take(n), off_extra = cut.take(extra_bytes);
-    MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], cut.total));
-    char *ws = (char *)ctx->ws[WS_VERIFY].p;
-    // ---- kSum: the scalar part through the G1 MSM over the resident K[1..], the rest on the host
-    out->P.resize(n * np), out->Q.resize(n * np);
-    MI_TRY(mi_verify_put_scalars(ctx, st, (Fr *)(ws + off_scal)));
-    for (size_t i = 0; i < n; i++) {
-        G1Aff msm{Fp::zero(), Fp::zero()};   // no MSM runs for a malformed proof
-        if (ns && !st.flags[i]) MI_TRY(mi_verify_msm(ctx, vk->k_dev, (const Fr *)(ws + off_scal) + i * ns, ns, 0, &msm));
-        verify_assemble(st.key, st.proofs[i], !st.flags[i], msm, &out->P[i * np], &out->Q[i * np]);
+    bool table = false;   // the key's window table carries the stage (ksum.hip); built here when no call has asked for one yet
+    if (ctx->verify_ksum && n >= ctx->verify_ksum_min_batch) MI_TRY(mi_ksum_ready(ctx, vk, &table));
+    if (!table) {
+        MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], cut.total));
+        char *ws = (char *)ctx->ws[WS_VERIFY].p;
+        // ---- kSum: the scalar part through the G1 MSM over the resident K[1..], the rest on the host
+        out->host.resize(n * np * (sizeof(G1Aff) + sizeof(G2Aff)));
+        G1Aff *P = (G1Aff *)out->host.data();
+        G2Aff *Q = (G2Aff *)(out->host.data() + n * np * sizeof(G1Aff));
+        MI_TRY(mi_verify_put_scalars(ctx, st, (Fr *)(ws + off_scal)));
+        for (size_t i = 0; i < n; i++) {
+            G1Aff msm{Fp::zero(), Fp::zero()};   // no MSM runs for a malformed proof
+            if (ns && !st.flags[i]) MI_TRY(mi_verify_msm(ctx, vk->k_dev, (const Fr *)(ws + off_scal) + i * ns, ns, 0, &msm));
+            verify_assemble(st.key, st.proofs[i], !st.flags[i], msm, &P[i * np], &Q[i * np]);
+        }
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_p, P, n * np * sizeof(G1Aff), hipMemcpyHostToDevice, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_q, Q, n * np * sizeof(G2Aff), hipMemcpyHostToDevice, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, st.flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        // ---- the host gathers (copies only), one upload; the sums of every row and the pairs of every proof on the device
+        const u32 nc = st.nc;
+        WsCut in;   // the gathered block, laid out as it lies on the device
+        const size_t in_k0 = in.take(sizeof(G1Aff)), in_gamma = in.take(sizeof(G2Aff)), in_delta = in.take(sizeof(G2Aff)), in_ped = in.take(2 * (size_t)nc * sizeof(G2Aff));
+        const size_t in_ar = in.take(n * sizeof(G1Aff)), in_bs = in.take(n * sizeof(G2Aff)), in_krs = in.take(n * sizeof(G1Aff));
+        const size_t in_cm = in.take(n * nc * sizeof(G1Aff)), in_pok = in.take(n * sizeof(G1Aff)), in_fold = in.take(n * sizeof(Fr));
+        const size_t off_in = cut.take(in.total), off_msm = cut.take(n * sizeof(G1Aff)), off_ksum = cut.take(mi_ksum_scratch_bytes(vk, n));
+        MI_TRY(mi_reserve(ctx, ctx->ws[WS_VERIFY], cut.total));
+        char *ws = (char *)ctx->ws[WS_VERIFY].p;
+        out->host.assign(in.total, 0);   // a flagged proof's records stay zero: none of its words is read, here or there
+        char *h = out->host.data();
+        std::memcpy(h + in_k0, st.key.k0, sizeof(G1Aff));
+        std::memcpy(h + in_gamma, st.key.gamma2, sizeof(G2Aff));
+        std::memcpy(h + in_delta, st.key.delta2, sizeof(G2Aff));
+        if (nc) std::memcpy(h + in_ped, st.key.ped, 2 * (size_t)nc * sizeof(G2Aff));
+        for (size_t i = 0; i < n; i++) {
+            if (st.flags[i]) continue;
+            const VerifyProofRef &pr = st.proofs[i];
+            std::memcpy(h + in_ar + i * sizeof(G1Aff), pr.ar, sizeof(G1Aff));
+            std::memcpy(h + in_bs + i * sizeof(G2Aff), pr.bs, sizeof(G2Aff));
+            std::memcpy(h + in_krs + i * sizeof(G1Aff), pr.krs, sizeof(G1Aff));
+            if (nc) std::memcpy(h + in_cm + i * nc * sizeof(G1Aff), pr.commitments, nc * sizeof(G1Aff));
+            if (nc) std::memcpy(h + in_pok + i * sizeof(G1Aff), pr.pok, sizeof(G1Aff));
+            if (nc > 1) std::memcpy(h + in_fold + i * sizeof(Fr), pr.fold_challenge, sizeof(Fr));
+        }
+        MI_TRY(mi_verify_put_scalars(ctx, st, (Fr *)(ws + off_scal)));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, st.flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
+        MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_in, h, in.total, hipMemcpyHostToDevice, ctx->stream));
+        uint64_t launches = 0;
+        MI_TRY(mi_ksum_enqueue(ctx, vk, (const Fr *)(ws + off_scal), (const uint8_t *)(ws + off_fl), n, (G1Aff *)(ws + off_msm), ws + off_ksum, &launches));
+        const char *d = ws + off_in;
+        const VerifyAssembleArrays arrays{VerifyKeyRef{(const G1Aff *)(d + in_k0), (const G2Aff *)(d + in_gamma), (const G2Aff *)(d + in_delta),
+                                                       (const G2Aff *)(d + in_ped), st.n_pub, nc},
+                                          (const G1Aff *)(d + in_ar), (const G2Aff *)(d + in_bs), (const G1Aff *)(d + in_krs), (const G1Aff *)(d + in_cm),
+                                          (const G1Aff *)(d + in_pok), (const Fr *)(d + in_fold), (const uint8_t *)(ws + off_fl), (const G1Aff *)(ws + off_msm)};
+        MI_TRY(mi_launch64(ctx, k_verify_assemble, n, arrays, (G1Aff *)(ws + off_p), (G2Aff *)(ws + off_q), n));
+        ctx->verify_ksum_batches++;
+        ctx->verify_ksum_launches += launches + 1;
     }
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_p, out->P.data(), n * np * sizeof(G1Aff), hipMemcpyHostToDevice, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_q, out->Q.data(), n * np * sizeof(G2Aff), hipMemcpyHostToDevice, ctx->stream));
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(ws + off_fl, st.flags.data(), n, hipMemcpyHostToDevice, ctx->stream));
+    char *ws = (char *)ctx->ws[WS_VERIFY].p;
     out->np = np;
     out->p = (G1Aff *)(ws + off_p); out->q = (G2Aff *)(ws + off_q); out->ml = (Fp12 *)(ws + off_ml);
     out->flags = (uint8_t *)(ws + off_fl); out->verdicts = (uint8_t *)(ws + off_vd); out->extra = extra_bytes ? (uint8_t *)(ws + off_extra) : nullptr;
@@ -238,9 +295,11 @@ int32_t mi_vk_free(mi_ctx *ctx, mi_vk *vk) {
     if (!ctx) return MI_EINVAL;
     if (!vk) return MI_OK;
     hipError_t e1 = vk->k_dev ? hipFree(vk->k_dev) : hipSuccess, e2 = vk->e_alpha_beta_dev ? hipFree(vk->e_alpha_beta_dev) : hipSuccess;
+    hipError_t e3 = vk->ksum.table ? hipFree(vk->ksum.table) : hipSuccess;   // the window table of K[1..] (ksum.hip)
     delete vk;
     MI_CHECK_HIP(ctx, e1);
     MI_CHECK_HIP(ctx, e2);
+    MI_CHECK_HIP(ctx, e3);
     return MI_OK;
 }
 
@@ -276,6 +335,18 @@ int32_t mi_groth16_verify_batch(mi_ctx *ctx, const mi_vk *vk, const mi_verify_in
 int32_t mi_debug_pairing_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, const mi_g2_affine *q_dev, size_t n, mi_fp *gt_dev, uint32_t flags) {
     if (!ctx || (flags & ~MI_PAIRING_FINAL_EXP) || ((!p_dev || !q_dev || !gt_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;
     return mi_pairing_enqueue(ctx, (const G1Aff *)p_dev, (const G2Aff *)q_dev, n, (Fp12 *)gt_dev, (flags & MI_PAIRING_FINAL_EXP) != 0);
+}
+int32_t mi_debug_verify_pairs_dev(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, mi_g1_affine *p_out, mi_g2_affine *q_out) {
+    if (ctx && n && (!p_out || !q_out)) MI_FAIL(ctx, MI_EINVAL, "verify pairs: null output pointer");
+    VerifyStage st;
+    MI_TRY(mi_verify_open(ctx, "verify pairs: ", vk, in, n, true, nullptr, &st));
+    if (!n) return MI_OK;
+    VerifyPairs d;
+    MI_TRY(mi_verify_stage_pairs(ctx, vk, st, 0, &d));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(p_out, d.p, n * d.np * sizeof(G1Aff), hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipMemcpyAsync(q_out, d.q, n * d.np * sizeof(G2Aff), hipMemcpyDeviceToHost, ctx->stream));
+    MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MI_OK;
 }
 int32_t mi_debug_fp12_op_dev(mi_ctx *ctx, int op, mi_fp *z_dev, const mi_fp *x_dev, const mi_fp *y_dev, size_t n) {
     if (!ctx || op < 0 || op >= F12_OP_END || ((!z_dev || !x_dev) && n) || n > ((size_t)1 << 24)) return MI_EINVAL;

@@ -10,6 +10,7 @@
 #include "../../include/mi355x_groth16_verify_combined.h"
 #include "../../include/mi355x_groth16_verify_locate.h"
 #include "../../include/mi355x_groth16_verify_wave.h"
+#include "../../include/mi355x_groth16_verify_ksum.h"
 #include "pairing_ops.cuh"
 #include <vector>
 
@@ -24,6 +25,17 @@ struct mi_vk {
     // gnark's PublicAndCommitmentCommitted in CSR form (mi_vk_set_public_committed, verify_bytes.hip): offsets of n_commitments + 1
     // entries (all 0 until set: empty lists) and the indices; host memory only, a batch carries them to the device in its workspace
     std::vector<uint32_t> pc_off, pc_idx;
+    // The window table of K[1..] (ksum.hip, include/mi355x_groth16_verify_ksum.h): T[j][w][d - 1] = d 2^(c w) K[1 + j], built on the first
+    // verdict-per-proof call or by mi_vk_ksum_prepare, freed with the key.  c == 0: no table, and `state` (MI_KSUM_*) says why.  The stage
+    // of a batch builds it through a const key: it is a cache of what the key's bases already say.
+    struct Ksum {
+        G1Aff *table = nullptr;
+        uint32_t c = 0, state = MI_KSUM_NOT_BUILT;
+        uint64_t bytes = 0, budget = MI_KSUM_DEFAULT_TABLE_BYTES;
+        float build_ms = 0;
+    };
+    mutable Ksum ksum;
+    uint32_t ksum_bases() const { return nb_public - 1 + n_commitments; }
 };
 
 // How every body starts: the checks of ctx, vk, in, n and the pointers of every proof (messages under `who`, the body's prefix;
@@ -45,19 +57,33 @@ int32_t mi_verify_combined_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_inp
 // mi_groth16_verify_locate's body (verify_locate.hip): one verdict per proof.  seed and stats may be null.
 int32_t mi_verify_locate_run(mi_ctx *ctx, const mi_vk *vk, const mi_verify_input *in, size_t n, const uint8_t *seed, uint8_t *verdicts,
                              mi_verify_locate_stats *stats, const uint8_t *decode_malformed, const Fr *pub_dev = nullptr);
-// ---- the host half of the two per-proof bodies (verify.hip), all on ctx->stream: WS_VERIFY cut as scal | p | q | ml | flags | verdicts |
-// extra, the scalars up, one mi_verify_msm per well-formed proof and verify_assemble, then P, Q and the stage's flags up.  P and Q are
-// the host copies the uploads read: they live until the body's last synchronise.  extra: extra_bytes of the body's own, null without.
+// ---- the stage of the two per-proof bodies (verify.hip), all on ctx->stream: WS_VERIFY cut as scal | p | q | ml | flags | verdicts |
+// extra | the stage's own regions, the scalars and the flags up, then the pairs of every proof into p, q.  With a window table on the
+// key (mi_vk::ksum; the knob "verify_ksum" is 1) the host only gathers: Ar, Bs, Krs, the commitments, pok and the fold challenges of
+// the batch go up in ONE copy behind the key's own points, mi_ksum_enqueue sums every row, and k_verify_assemble lays the pairs out, one
+// lane per proof.  Without one it is the older loop: one mi_verify_msm per well-formed proof and verify_assemble on the host, then the
+// pairs up.  `host` is the copy the upload reads: it lives until the body's last synchronise.  extra: extra_bytes of the body's own.
 struct VerifyPairs {
     u32 np = 0;   // pairs per proof
-    std::vector<G1Aff> P;
-    std::vector<G2Aff> Q;
+    std::vector<char> host;
     G1Aff *p = nullptr;
     G2Aff *q = nullptr;
     Fp12 *ml = nullptr;
     uint8_t *flags = nullptr, *verdicts = nullptr, *extra = nullptr;
 };
 int32_t mi_verify_stage_pairs(mi_ctx *ctx, const mi_vk *vk, const VerifyStage &st, size_t extra_bytes, VerifyPairs *out);
+// ---- kSum of a whole batch over the key's window table (ksum.hip).  mi_ksum_ready: the key has a table, building it first when no call
+// has asked for one yet (under the key's budget; a key that ends without one is no error).  mi_ksum_scratch_bytes: what mi_ksum_enqueue
+// needs at `scratch` for n rows (partials | sums | running products).  mi_ksum_enqueue: out_dev[i] = sum_j scal_dev[i ns + j] K[1 + j],
+// affine, infinity where skip_dev[i] != 0 (skip_dev may be null); three launches whatever n is, counted into *launches (may be null).
+// Proofs from which the stage of a batch takes the table; below, the older loop.  profiles/verify.txt, both stages alternating: at n = 1
+// the table is not faster on either body (wave body 5.20 ms against 4.96, 5.90 against 5.57 with 4096 inputs: three launches and a
+// gather against one MSM), at n = 8 it is on the wave body (5.76 against 8.20) and no slower on the one-lane body; not measured in between
+#define MI_VERIFY_KSUM_MIN_BATCH 8
+static_assert(MI_VERIFY_KSUM_MIN_BATCH == 8, "mi_ctx::verify_ksum_min_batch starts from this value (ctx.h)");
+int32_t mi_ksum_ready(mi_ctx *ctx, const mi_vk *vk, bool *ready);
+size_t mi_ksum_scratch_bytes(const mi_vk *vk, size_t n);
+int32_t mi_ksum_enqueue(mi_ctx *ctx, const mi_vk *vk, const Fr *scal_dev, const uint8_t *skip_dev, size_t n, G1Aff *out_dev, char *scratch, uint64_t *launches);
 // ---- the front of the two coefficient bodies (verify_combined.hip), in the order they call it.  The refusal of n * n_commitments above
 // MI_MSM_MAX_PAIRS under msg, the body's own text, before mi_verify_open and under its first checks (args_ok: in and the verdict pointer)
 int32_t mi_verify_refuse_msm_pairs(mi_ctx *ctx, const mi_vk *vk, bool args_ok, size_t n, const char *msg);

@@ -3,8 +3,9 @@
 // fp12_wave.cuh / pairing_wave.cuh; the image of a wave is MI_WAVE_IMAGE_BYTES of LDS, and every workgroup is ONE wave of 64 lanes.
 //
 // One batch, every launch on ctx->stream.  The host half is mi_verify_run's, the same function: mi_verify_open (argument checks, the
-// VerifyStage) under this body's prefix, then mi_verify_stage_pairs (verify.hip: the scalars, one mi_verify_msm per well-formed proof,
-// verify_assemble, the uploads) -- so a malformed proof is decided exactly as there and its words stay out of the arithmetic.  Then
+// VerifyStage) under this body's prefix, then mi_verify_stage_pairs (verify.hip: the scalars up, the sums of every row over the key's
+// window table and verify_assemble one lane per proof -- or, without a table, one mi_verify_msm per well-formed proof and verify_assemble
+// on the host) -- so a malformed proof is decided exactly as there and its words stay out of the arithmetic.  Then
 //   k_pairing_miller_wave   one workgroup per (proof, pair): a Miller loop, 384 B out.  The SAME launch carries the Bs checks, 64 proofs
 //                           per workgroup and one lane each (wave_bs_in_subgroup: the 63-bit endomorphism test), in front of the pairs:
 //                           the longest one-lane chain of the call starts first and runs beside the Miller waves, not before them

@@ -18,6 +18,7 @@ package mi355x
 #include "mi355x_groth16_verify_bytes.h"
 #include "mi355x_groth16_verify_combined.h"
 #include "mi355x_groth16_verify_wave.h"
+#include "mi355x_groth16_verify_ksum.h"
 #include "mi355x_groth16_vkfile.h"
 */
 import "C"
@@ -111,6 +112,58 @@ func (vk *VerifyingKey) Close() {
 		C.mi_shutdown(vk.ctx)
 		vk.ctx = nil
 	}
+}
+
+// KsumInfo is mi_vk_ksum_info: the window table of the key's K[1..] (include/mi355x_groth16_verify_ksum.h).  WindowBits == 0: the key
+// has no table, State (MI_KSUM_*) says why, and the verifiers keep one MSM per proof for it.
+type KsumInfo struct {
+	WindowBits, Windows      uint32
+	TableBytes, Bases, Budget uint64
+	State                    uint32
+	BuildMs                  float32
+}
+
+// PrepareKsum builds the key's window table now under a byte budget (0 = MI_KSUM_DEFAULT_TABLE_BYTES, 64 MiB), or again under another
+// one (mi_vk_ksum_prepare).  Without it the first Verify on the key builds the table under the default budget.
+func (vk *VerifyingKey) PrepareKsum(maxTableBytes uint64) (KsumInfo, error) {
+	if err := status(vk.ctx, C.mi_vk_ksum_prepare(vk.ctx, vk.dev, C.uint64_t(maxTableBytes))); err != nil {
+		return KsumInfo{}, err
+	}
+	return vk.KsumInfo()
+}
+
+// KsumInfo reads mi_vk_ksum_get_info.
+func (vk *VerifyingKey) KsumInfo() (KsumInfo, error) {
+	var i C.mi_vk_ksum_info
+	if err := status(vk.ctx, C.mi_vk_ksum_get_info(vk.ctx, vk.dev, &i)); err != nil {
+		return KsumInfo{}, err
+	}
+	return KsumInfo{uint32(i.window_bits), uint32(i.windows), uint64(i.table_bytes), uint64(i.bases), uint64(i.budget_bytes), uint32(i.state),
+		float32(i.build_ms)}, nil
+}
+
+// PublicInputSums is mi_vk_ksum_batch: rows[i] holds the scalars of statement i (public inputs, then commitment values: len(vk.G1.K) - 1
+// of them); the result is sum_j rows[i][j] K[1 + j] for every i, with no pairing attached.  The key must have a table (PrepareKsum).
+// mi_vk_ksum_batch_dev is the same over device pointers, for callers that keep their scalars on the device.
+func (vk *VerifyingKey) PublicInputSums(rows []fr.Vector) ([]bn254.G1Affine, error) {
+	ns := len(vk.G1.K) - 1
+	flat := make(fr.Vector, 0, len(rows)*ns)
+	for _, row := range rows {
+		if len(row) != ns {
+			return nil, errors.New("mi355x: a row has not one scalar per base of the key")
+		}
+		flat = append(flat, row...)
+	}
+	out := make([]bn254.G1Affine, len(rows))
+	if len(rows) == 0 {
+		return out, nil
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pin.Pin(&flat[0])
+	pin.Pin(&out[0])
+	rc := C.mi_vk_ksum_batch(vk.ctx, vk.dev, (*C.mi_fr)(unsafe.Pointer(&flat[0])), nil, C.size_t(len(rows)), (*C.mi_g1_affine)(unsafe.Pointer(&out[0])))
+	return out, status(vk.ctx, rc)
 }
 
 // Verify replaces groth16.Verify(proof, vk, publicWitness).  publicWitness holds the public inputs without the ONE wire, as

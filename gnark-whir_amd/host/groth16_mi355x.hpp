@@ -25,6 +25,7 @@
 #include "../../include/mi355x_groth16_vkfile.h"
 #include "../../include/mi355x_groth16_verify_combined.h"
 #include "../../include/mi355x_groth16_verify_wave.h"
+#include "../../include/mi355x_groth16_verify_ksum.h"
 #include "../../include/mi355x_groth16_phase2.h"
 #include "../../include/mi355x_groth16_phase2_check.h"
 #include "../../include/mi355x_groth16_debug.h"   // (this mirror is the TEST side: generators and knobs)
@@ -232,6 +233,27 @@ class VerifyingKey {
         std::vector<uint32_t> off{0}, idx;
         for (const auto &l : lists) { idx.insert(idx.end(), l.begin(), l.end()); off.push_back((uint32_t)idx.size()); }
         ctx_.check(mi_vk_set_public_committed(ctx_.get(), vk_, off.data(), idx.empty() ? nullptr : idx.data()));
+    }
+    // The window table of K[1..] (include/mi355x_groth16_verify_ksum.h): built now under a byte budget (0 = 64 MiB), or again under
+    // another one; without this call the first verdict-per-proof Verify on the key builds it.  window_bits == 0 in the info: no table.
+    mi_vk_ksum_info PrepareKsum(uint64_t maxTableBytes = 0) {
+        ctx_.check(mi_vk_ksum_prepare(ctx_.get(), vk_, maxTableBytes));
+        return KsumInfo();
+    }
+    mi_vk_ksum_info KsumInfo() const {
+        mi_vk_ksum_info info{};
+        ctx_.check(mi_vk_ksum_get_info(ctx_.get(), vk_, &info));
+        return info;
+    }
+    // sum_j scalars[i * bases + j] K[1 + j] for every row i, with no pairing attached (mi_vk_ksum_batch); skip: empty, or one byte per row
+    std::vector<mi_g1_affine> PublicInputSums(const std::vector<mi_fr> &scalars, size_t n, const std::vector<uint8_t> &skip = {}) const {
+        std::vector<mi_g1_affine> out(n);
+        ctx_.check(mi_vk_ksum_batch(ctx_.get(), vk_, scalars.data(), skip.empty() ? nullptr : skip.data(), n, out.data()));
+        return out;
+    }
+    // the same over device pointers, enqueued on the context's stream (mi_vk_ksum_batch_dev)
+    void PublicInputSumsDev(const mi_fr *scalarsDev, const uint8_t *skipDev, size_t n, mi_g1_affine *outDev) const {
+        ctx_.check(mi_vk_ksum_batch_dev(ctx_.get(), vk_, scalarsDev, skipDev, n, outDev));
     }
 
   private:

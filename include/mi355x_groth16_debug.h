@@ -83,6 +83,11 @@ int32_t mi_debug_pairing_wave_dev(mi_ctx *ctx, const mi_g1_affine *p_dev, const 
 int32_t mi_debug_fp12_op_wave_dev(mi_ctx *ctx, int op, mi_fp *z_dev, const mi_fp *x_dev, const mi_fp *y_dev, size_t n);
 struct mi_vk; struct mi_verify_input;
 int32_t mi_debug_verify_wave_split(mi_ctx *ctx, const struct mi_vk *vk, const struct mi_verify_input *in, size_t n, uint8_t *verdicts, float *split_ms);
+/* The pairs of a staged batch: what mi_groth16_verify_batch and mi_groth16_verify_wave hand to their Miller loops for these inputs, before
+ * the check of Bs.  p_out, q_out: HOST arrays of n x (3, or 4 + n_commitments with commitments) points in the order of
+ * csrc/pairing_ops.cuh (verify_assemble); a proof that is not well formed has infinities.  The stage is the one the knob "verify_ksum"
+ * selects, so the two stages can be compared word for word.  The refusals of mi_groth16_verify_batch under the prefix "verify pairs: ". */
+int32_t mi_debug_verify_pairs_dev(mi_ctx *ctx, const struct mi_vk *vk, const struct mi_verify_input *in, size_t n, mi_g1_affine *p_out, mi_g2_affine *q_out);
 /* the decoders and the hash behind mi355x_groth16_verify_bytes.h (csrc/decode_ops.cuh, sha256_h2f.cuh), one record per lane; the host
  * build of the tests (tests/emu/emu_decode.cpp) runs the same bodies.  All pointers are DEVICE pointers; the launches go to the context's
  * stream (mi_dev_sync before reading).
@@ -214,12 +219,19 @@ int32_t mi_debug_set_msm_precompute_batched(mi_ctx *ctx, uint32_t on);
  *   "ntt_lds_floor_kb" 0..160   LDS every NTT pass workgroup requests at least (caps the workgroups per CU)
  *   "scale_powers_window" 0 | 2..5   phase 1's scalar multiplications (csrc/scale_powers.cuh): 2..5 = the fixed-window ladder of that width
  *                            (default 5, measured fastest: profiles/phase1.txt); 0 = the bit-by-bit xyzz_scale of the point NTT on the same scalars, the yardstick.  Same points
- *   "scale_powers_chunk" 0 | 64..2^24   lanes per chunk of that driver, which sizes its table workspace (0 = the default, 2^18) */
+ *   "scale_powers_chunk" 0 | 64..2^24   lanes per chunk of that driver, which sizes its table workspace (0 = the default, 2^18)
+ *   "verify_ksum" 0 | 1      the stage of the verdict-per-proof verifiers (mi355x_groth16_verify_ksum.h): 1 (default) = the sums of a whole
+ *                            batch over the key's window table and the pairs laid out on the device; 0 = one MSM per proof and the group
+ *                            law on the host, the yardstick.  Same pairs word for word, same verdicts
+ *   "verify_ksum_min_batch" 1..2^24   the proofs from which knob 1 takes the table (default 8: at n = 1 three launches and a gather are not
+ *                            faster than one MSM, profiles/verify.txt); smaller batches keep the older stage */
 int32_t mi_debug_set_knob(mi_ctx *ctx, const char *name, int64_t value);
 /* Counters the tests read to prove that an optional path really ran: "z_count_fused_launches" = computeH last launches of this context that
  * carried the Z MSM's digit count (knob "z_count_fused"); "dense_item_sorts" = bucket accumulations whose level-1 item size the dense-sort rule
  * chose (knob "dense_item_l1"); "generic_sorts_two_pass" / "generic_sorts_one_pass" = generic (no-table) MSM sorts that took the LDS-staged
- * two-pass sort (c = 16, 2^18 <= n, 16 n < 2^31) / the one-pass counting sort; "hip_failure_countdown" = checked calls still to pass before
+ * two-pass sort (c = 16, 2^18 <= n, 16 n < 2^31) / the one-pass counting sort; "verify_ksum_batches" = batches the verdict-per-proof
+ * verifiers staged through the key's window table (knob "verify_ksum"), "verify_ksum_launches" = the kernel launches of those stages (the
+ * same number for every batch size); "hip_failure_countdown" = checked calls still to pass before
  * the failure armed by mi_debug_inject_hip_failure (process-wide; 0 = disarmed or spent).  MI_EINVAL for an unknown name. */
 int32_t mi_debug_get_counter(mi_ctx *ctx, const char *name, uint64_t *out);
 /* Process-wide, for contexts created afterwards: how the MSM slots of a context share streams (0: K's stream created, destroyed and

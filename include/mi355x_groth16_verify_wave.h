@@ -18,7 +18,9 @@
  * against 39.0; n = 64: 30.0 against 59.7; n = 512: 209.5 against 235.5; n = 4096: 1644.6 against 1620.1 -- the batch call takes the
  * lead somewhere between n = 512 and n = 4096 (not measured in between).  Both calls run one synchronous MSM per proof from the host;
  * at n = 1 that host stage is 0.39 ms of the 5.2, so by that figure it is most of either call from n = 64 on.  So: these calls for one
- * proof up to a few hundred.
+ * proof up to a few hundred.  (Those figures are from before mi355x_groth16_verify_ksum.h, which took that MSM out of both calls for
+ * batches of 8 proofs and more; in the later block of profiles/verify.txt, same key: n = 64: 5.9 ms against 35.4; n = 512: 10.3
+ * against 36.1; n = 4096: 64.5 against 40.4 -- the same advice, at other prices.)
  * Above that, mi_groth16_verify_batch names every rejected proof at a lower price per proof, mi_groth16_verify_combined
  * (mi355x_groth16_verify_combined.h) gives one verdict for the batch at a fraction of it, and mi_groth16_verify_locate
  * (mi355x_groth16_verify_locate.h) one verdict per proof at the combined test's price when the batch is good: they remain the tools for

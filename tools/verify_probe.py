@@ -10,6 +10,7 @@ ALTERNATING, with the locate call's stats; then, for the larger batches with b =
     python tools/verify_probe.py [--write profiles/verify.txt] [--batches 64,1024,16384] [--runs 5]
     python tools/verify_probe.py --files [--write profiles/verify.txt]      the files leg alone (files_leg below); --write APPENDS
     python tools/verify_probe.py --wave [--write profiles/verify.txt]       the wave leg alone (wave_leg below); --write APPENDS
+    python tools/verify_probe.py --ksum [--write profiles/verify.txt]       the ksum leg alone (ksum_leg below); --write APPENDS
 
 A solvable circuit of 1000 constraints (domain 2^10, 4 public inputs, one BSB22 commitment; tests/r1cs_cases.py), its key from
 mi_groth16_setup, one proof through the prover pool.  After a warm-up call, the median wall time of `--runs` calls of one verification
@@ -182,8 +183,85 @@ def wave_leg(B, ctx, vkh, inp, args, header):
             f.write("\n" + "\n".join(lines) + "\n")
 
 
+def ksum_key_4096(B, ctx):
+    """the key of the --files leg: 4096 public inputs and one commitment, seeded points; byte-valued public inputs and a proof of valid
+    points (verdict 1 under either stage: the work is an accepted batch's)"""
+    import pyref as P
+    from helpers import g2_arr
+    n_pub = 4096
+    g2 = lambda e: g2_arr([P.g2_mul(P.G2_GEN, e)])[0]
+    vk = {"alpha1": cref.gen_g1(1, 22)[0], "beta2": g2(2), "gamma2": g2(3), "delta2": g2(5), "k": cref.gen_g1(n_pub + 2, 21)}
+    vkh = ctx.vk_load(vk, n_pub + 1, np.stack([np.stack([g2(1), g2(7)])]))
+    pts = cref.gen_g1(4, 25)
+    rnd = np.random.default_rng(4096)
+    inp = {"raw": np.concatenate([pts[0], g2(11), pts[1]]), "public_inputs": fr_arr([int(x) for x in rnd.integers(0, 256, n_pub)]),
+           "commitments": np.ascontiguousarray(pts[2]).reshape(1, 8), "pok": np.ascontiguousarray(pts[3]), "commitment_values": cref.gen_scalars(1, 26, 0)}
+    return vkh, inp
+
+
+def ksum_leg(B, ctx, legs, args):
+    """--ksum: the stage of the verdict-per-proof bodies through the key's window table (knob "verify_ksum" = 1; csrc/ksum.hip) against
+    the older stage, one MSM per proof from the host (knob 0), on the SAME context: mi_groth16_verify_batch and mi_groth16_verify_wave at
+    n = 1, 8, 64, 512, 4096, 16384 (--ksum-batches), for each body one warm-up pair (knob 1, knob 0) and then max(--runs, 5) pairs,
+    whole calls with their host part.  legs: (header, key, proof, table budget, expected verdict).  Per leg the table's build time and
+    bytes, then per size and body the medians and spreads (max - min).  The yardstick is knob 0 in the same run: knob 1 counts as
+    faster only where its median is below knob 0's by more than the larger of the two spreads.  With --write the lines are APPENDED."""
+    C = B.C
+    runs = max(args.runs, 5)
+    lines = ["kSum of a whole batch over the key's window table (tools/verify_probe.py --ksum): the knob \"verify_ksum\" at 1 (table) and 0 (one MSM per proof,",
+             f"the yardstick) alternating on one context, {runs} pairs after one warm-up pair, whole calls, host clocks; median ms (spread = max - min);",
+             "'faster' only where the knob-1 median is below the knob-0 median by more than the larger spread; the knob \"verify_ksum_min_batch\" is at 1 here,",
+             "so knob 1 is the table at EVERY size (the library's default keeps the older stage below 8 proofs: the pairs at n = 1 and n = 8 are why)"]
+    print("\n".join(lines), flush=True)
+    ctx.set_knob("verify_ksum_min_batch", 1)
+
+    def emit(line):
+        lines.append(line)
+        print(line, flush=True)
+
+    bodies = (("batch", ctx.lib.mi_groth16_verify_batch), ("wave ", ctx.lib.mi_groth16_verify_wave))
+    for header, vkh, inp, budget, verdict in legs:
+        info = vkh.ksum_prepare(budget)
+        emit(f"--- {header}")
+        emit(f"    table: budget {info['budget_bytes']} bytes -> c = {info['window_bits']}, {info['windows']} windows, {info['bases']} bases, "
+             f"{info['table_bytes']} bytes ({info['table_bytes'] / 2**20:.1f} MiB), built in {info['build_ms']:.3f} ms (wall clock, with its synchronisation)")
+        assert info["state"] == B.KSUM_READY
+        not_faster = []
+        for nb in [int(x) for x in args.ksum_batches.split(",") if x]:
+            arr, keep = vkh._inputs([inp] * nb)
+            for name, f in bodies:
+                outs = {1: np.full(nb, 255, np.uint8), 0: np.full(nb, 255, np.uint8)}
+
+                def call(knob):
+                    ctx.set_knob("verify_ksum", knob)
+                    t = time.perf_counter()
+                    ctx._ck(f(ctx.h, vkh.h, arr, C.c_size_t(nb), outs[knob].ctypes.data_as(C.c_void_p)))
+                    return (time.perf_counter() - t) * 1e3
+                call(1); call(0)
+                ts = {1: [], 0: []}
+                for _ in range(runs):
+                    for knob in (1, 0):
+                        ts[knob].append(call(knob))
+                ctx.set_knob("verify_ksum", 1)
+                assert (outs[1] == verdict).all() and (outs[0] == verdict).all()
+                m1, m0, s1, s0 = statistics.median(ts[1]), statistics.median(ts[0]), max(ts[1]) - min(ts[1]), max(ts[0]) - min(ts[0])
+                word = "knob 1 faster" if m0 - m1 > max(s0, s1) else ("knob 0 faster" if m1 - m0 > max(s0, s1) else "no difference beyond the spread")
+                if word != "knob 1 faster":
+                    not_faster.append((name.strip(), nb))
+                emit(f"    n = {nb:5d}  {name}  knob 1 {m1:10.3f} ms (spread {s1:.3f})   knob 0 {m0:10.3f} ms (spread {s0:.3f})   knob 0 / knob 1 {m0 / m1:7.2f}   "
+                     f"{m1 / nb:8.4f} against {m0 / nb:8.4f} ms per proof   {word}")
+        emit("    knob 1 faster at every size, both bodies" if not not_faster else f"    knob 1 NOT faster at: {not_faster}")
+    emit("NOT MEASURED: kernel times by a profiler, sizes between these, other public-input counts and widths than the ones stated, the bytes and files calls "
+         "(they run the batch body's stage), any figure from gnark")
+    if args.write:
+        with open(args.write, "a") as f:
+            f.write("\n" + "\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ksum", action="store_true", help="the ksum leg alone (see ksum_leg); --write appends")
+    ap.add_argument("--ksum-batches", default="1,8,64,512,4096,16384")
     ap.add_argument("--wave", action="store_true", help="the wave leg alone (see wave_leg); --write appends")
     ap.add_argument("--wave-batches", default="1,8,64,512,4096")
     ap.add_argument("--files", action="store_true", help="the files leg alone (see files_leg); --write appends")
@@ -230,6 +308,14 @@ def main():
     assert vkh.verify(inp) == B.VERIFY_OK
     data = B.proof_write(inp["raw"], commitments=cm, pok=inp["pok"])
     assert vkh.verify_bytes(data, inp["public_inputs"]) == B.VERIFY_OK
+    if args.ksum:
+        vkh_files, inp_files = ksum_key_4096(B, ctx)
+        ksum_leg(B, ctx, [(f"1000 constraints (domain 2^10), {nb_public - 1} public inputs with full-width values, 1 commitment (5 pairs per proof); the default budget",
+                           vkh, inp, 0, B.VERIFY_OK),
+                          ("4096 byte-valued public inputs, 1 commitment (5 pairs per proof), a key of seeded points and a proof of valid points "
+                           "(verdict 1 under either knob); a budget of 256 MiB", vkh_files, inp_files, 256 << 20, B.VERIFY_PAIRING)], args)
+        vkh_files.free(); vkh.free(); ctx.pedersen_pk_free(peds[0]); ctx.pk_free(pkh); ctx.close()
+        return
     if args.wave:
         wave_leg(B, ctx, vkh, inp, args, f"1000 constraints (domain 2^10), {nb_public - 1} public inputs, 1 commitment (5 pairs per proof)")
         vkh.free(); ctx.pedersen_pk_free(peds[0]); ctx.pk_free(pkh); ctx.close()
