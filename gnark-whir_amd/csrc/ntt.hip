@@ -44,36 +44,19 @@ struct NttState {
 // Tile / radix knobs for a transform of 2^log_n: the caller's (mi_debug_set_ntt_plan) or, untouched, the measured best per size
 // (tools/ntt_probe.py sweep, profiles/r02_tune_ntt_sweep.json): 2^9 tiles and radices 2^7 2^7 2^9 up to 2^23; 2^10 tiles and
 // 2^8 2^8 2^8 at 2^24 (16.2 vs 17.4 ms per computeH); 2^10 tiles and 2^8 2^8(2^7) 2^10 from 2^25 on (71.9 vs 74.0 ms at 2^26).
-struct NttKnobs { u32 log_e, max_contig, max_strided; };
 static NttKnobs knobs_for(const struct NttState *st, u32 log_n);
 static NttState *state_of(mi_ctx *ctx) {
     static_assert(sizeof(NttState) <= 384, "NttState lives in ctx->ntt_state");
     return reinterpret_cast<NttState *>(ctx->ntt_state);
 }
 
-__global__ void k_ntt_pass(Fr *dst, const Fr *src, NttPass p, NttTables t);
-__global__ void k_ntt_pass_wave(Fr *dst, const Fr *src, NttPass p, NttTables t);
-__global__ void k_ntt_contig_pair(Fr *data, NttPass pi, NttTables ti, NttPass pf, NttTables tf);
-__global__ void k_ntt_strided_triple(Fr *a, const Fr *b, NttPass pc, NttTables tc, NttPass pl, NttTables tl);
-__global__ void k_ntt_strided_triple8(Fr *a, const Fr *b, NttPass pc, NttTables tc, NttPass pl, NttTables tl);
-__global__ void k_ntt_contig_last_sub(Fr *A, const Fr *Cin, NttPass pa, NttTables ta, NttPass pc, NttTables tc);
+// k_ntt_contig_last_sub with the Z MSM's digit count riding along, one instantiation per window width.  Named HERE, ahead of every
+// kernel: naming them after the definitions changed their code (119 VGPRs for 117, profiles/ntt_schedule.txt)
 template <int CC> __global__ void k_ntt_contig_last_sub_count(Fr *A, const Fr *Cin, NttPass pa, NttTables ta, NttPass pc, NttTables tc, Msm2Shape zs, u32 *C1);
-void mi_ntt_state_init(mi_ctx *ctx) {
-    static_assert(sizeof(NttState) <= sizeof(ctx->ntt_state), "NttState lives in ctx->ntt_state");
-    new (ctx->ntt_state) NttState();
-    (void)hipFuncSetAttribute((const void *)k_ntt_pass, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void *)k_ntt_pass_wave, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void *)k_ntt_contig_pair, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void *)k_ntt_strided_triple, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void *)k_ntt_strided_triple8, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void *)k_ntt_contig_last_sub, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void *)k_ntt_contig_last_sub_count<17>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void *)k_ntt_contig_last_sub_count<18>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void *)k_ntt_contig_last_sub_count<19>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void *)k_ntt_contig_last_sub_count<20>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void *)k_ntt_contig_last_sub_count<21>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void *)k_ntt_contig_last_sub_count<22>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
+typedef void (*LastSubCountKernel)(Fr *, const Fr *, NttPass, NttTables, NttPass, NttTables, Msm2Shape, u32 *);
+static const LastSubCountKernel k_last_sub_count[6] = {   // by window width c - 17
+    k_ntt_contig_last_sub_count<17>, k_ntt_contig_last_sub_count<18>, k_ntt_contig_last_sub_count<19>,
+    k_ntt_contig_last_sub_count<20>, k_ntt_contig_last_sub_count<21>, k_ntt_contig_last_sub_count<22>};
 bool mi_ntt_set_knob(mi_ctx *ctx, const char *name, int64_t value) {
     if (!std::strcmp(name, "ntt_lds_floor_kb") && value >= 0 && value <= 160) { state_of(ctx)->lds_floor = (u32)value * 1024u; return true; }
     return false;
@@ -179,7 +162,7 @@ __global__ void __launch_bounds__(256, MI_NTT_WAVES_PER_EU) k_ntt_pass_wave(Fr *
 // follows (DIT, the same contiguous tiles, coset shift on the way in) as one launch -- the tile is loaded once, runs the inverse
 // stages, is multiplied by the shift, runs the forward stages and is stored once; in the register stages the two transforms meet
 // without an LDS round trip (a lane ends the DIF stages holding positions 2L, 2L + 1 -- what the DIT stages start from).  One store
-// and one load of the vector (0.54 GB at N = 2^23) and one launch less per vector.  pi / ti: the inverse pass as ntt_run would have
+// and one load of the vector (0.54 GB at N = 2^23) and one launch less per vector.  pi / ti: the inverse pass as launch_pass would have
 // launched it, pf / tf: the forward one.  Radix >= 2^7, equal tile shapes.
 __global__ void __launch_bounds__(256) k_ntt_contig_pair(Fr *data, NttPass pi, NttTables ti, NttPass pf, NttTables tf) {
     extern __shared__ U4 lds[];
@@ -221,7 +204,7 @@ __global__ void __launch_bounds__(256) k_ntt_contig_pair(Fr *data, NttPass pi, N
 // (DIT pre-twiddle on the way in), runs the seven register stages and keeps the result in registers (a lane ends DIT holding rows L,
 // L + 64 -- exactly what the DIF stages start from), loads b's tile into the same LDS, does the same, multiplies, runs the DIF stages
 // and stores through LDS with the DIF post-twiddle.  Per element: the same products; four passes of a vector through HBM (store a,
-// store b, load a, load b: 1.07 GB at N = 2^23) and two launches less.  pc / tc: the coset FFT's last pass as ntt_run would have
+// store b, load a, load b: 1.07 GB at N = 2^23) and two launches less.  pc / tc: the coset FFT's last pass as launch_pass would have
 // launched it (for a and for b alike), pl / tl: the last transform's first pass (without load_mul).  Radix 2^7 exactly (no stage
 // through LDS) and one 128-row sub-block per wave (blockDim = 64 x sub-blocks of the tile).
 __global__ void __launch_bounds__(512) k_ntt_strided_triple(Fr *a, const Fr *b, NttPass pc, NttTables tc, NttPass pl, NttTables tl) {
@@ -314,7 +297,7 @@ __global__ void __launch_bounds__(256) k_ntt_strided_triple8(Fr *a, const Fr *b,
 // contiguous tiles, and the second subtracts the first's output element by element.  One launch: c's tile goes through its stages and its
 // den / N scaling and stays in REGISTERS (a thread keeps the elements it would have stored), the main tile follows through the same LDS,
 // and the store subtracts, canonicalises and writes h.  c's last store and the store_sub read (0.54 GB at N = 2^23) and one launch go.
-// pa / ta: the last transform's last pass as ntt_run would have launched it (store_sub unset), pc / tc: c's.  Equal tile shapes, radix >= 2^7,
+// pa / ta: the last transform's last pass as launch_pass would have launched it (store_sub unset), pc / tc: c's.  Equal tile shapes, radix >= 2^7,
 // at most four elements per thread.
 __device__ __forceinline__ void ntt_wave_pass_to_lds(const NttPass &p, const NttTables &t, const Fr *src, u64 tile, U4 *lds) {
     const u32 PL = ntt_plane_slots(p);
@@ -392,6 +375,14 @@ template <int CC>
 __global__ void __launch_bounds__(256) k_ntt_contig_last_sub_count(Fr *A, const Fr *Cin, NttPass pa, NttTables ta, NttPass pc, NttTables tc, Msm2Shape zs, u32 *C1) {
     ntt_contig_last_sub_body<CC>(A, Cin, pa, ta, pc, tc, zs, C1);
 }
+void mi_ntt_state_init(mi_ctx *ctx) {
+    static_assert(sizeof(NttState) <= sizeof(ctx->ntt_state), "NttState lives in ctx->ntt_state");
+    new (ctx->ntt_state) NttState();
+    const void *const dynamic_lds[] = {(const void *)k_ntt_pass, (const void *)k_ntt_pass_wave, (const void *)k_ntt_contig_pair,
+                                       (const void *)k_ntt_strided_triple, (const void *)k_ntt_strided_triple8, (const void *)k_ntt_contig_last_sub};
+    for (const void *k : dynamic_lds) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (LastSubCountKernel k : k_last_sub_count) (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
 
 // direct factor tables (NttPass::tw_direct / sc_direct), one thread per entry, square-and-multiply
 __global__ void k_tw_layout(Fr *out, u32 log_n, u32 log_r, Fr w) {   // the M = N pass: element g = (rho << log_s) | lo
@@ -420,6 +411,21 @@ static int32_t build_table(mi_ctx *ctx, Fr **slot, u32 count, const Fr &base, co
     return MI_OK;
 }
 
+// the constants of the domain of size 2^log_n: its root, the coset generator, 1/N and den = 1 / (g^N - 1)
+struct NttRoots { Fr w, wi, g, gi, ninv, den; };
+static NttRoots ntt_roots(u32 log_n) {
+    NttRoots r;
+    r.w = fr_domain_generator(log_n); r.wi = fe_inv(r.w);
+    r.g = fe_from_u32<FrParams>(5); r.gi = fe_inv(r.g);
+    Fr nn = Fr::zero();
+    nn.l[0] = (u32)(1u << log_n);  // log_n <= 28
+    r.ninv = fe_inv(fe_to_mont(nn));
+    Fr gn = r.g;
+    for (u32 k = 0; k < log_n; k++) gn = fe_sqr(gn);
+    r.den = fe_inv(gn - Fr::one());
+    return r;
+}
+
 static int32_t ensure_tables(mi_ctx *ctx, u32 log_n) {
     NttState *st = state_of(ctx);
     if (!st->small_f) {
@@ -431,31 +437,24 @@ static int32_t ensure_tables(mi_ctx *ctx, u32 log_n) {
         MI_TRY(build_table(ctx, &st->tw64k_i, 65536, fe_inv(w64k), Fr::one(), 0));
     }
     if (st->log_n == log_n) return MI_OK;
-    Fr w = fr_domain_generator(log_n), wi = fe_inv(w);
-    Fr g = fe_from_u32<FrParams>(5), gi = fe_inv(g);
-    Fr nn = Fr::zero();
-    nn.l[0] = (u32)(1u << log_n);  // log_n <= 28
-    Fr ninv = fe_inv(fe_to_mont(nn));
+    const NttRoots r = ntt_roots(log_n);
     u32 h = (log_n + 1) / 2;
     u32 nlo = 1u << h, nhi = 1u << (log_n - h);
     st->tw_h = h;
-    MI_TRY(build_table(ctx, &st->tw_lo_f, nlo, w, Fr::one(), 0));
-    MI_TRY(build_table(ctx, &st->tw_hi_f, nhi, w, Fr::one(), h));
-    MI_TRY(build_table(ctx, &st->tw_lo_i, nlo, wi, Fr::one(), 0));
-    MI_TRY(build_table(ctx, &st->tw_hi_i, nhi, wi, Fr::one(), h));
-    MI_TRY(build_table(ctx, &st->g_lo, nlo, g, Fr::one(), 0));
-    MI_TRY(build_table(ctx, &st->g_hi, nhi, g, Fr::one(), h));
-    MI_TRY(build_table(ctx, &st->gi_lo, nlo, gi, Fr::one(), 0));
-    MI_TRY(build_table(ctx, &st->gi_hi, nhi, gi, ninv, h));
-    MI_TRY(build_table(ctx, &st->ninv, 1, Fr::one(), ninv, 0));
+    MI_TRY(build_table(ctx, &st->tw_lo_f, nlo, r.w, Fr::one(), 0));
+    MI_TRY(build_table(ctx, &st->tw_hi_f, nhi, r.w, Fr::one(), h));
+    MI_TRY(build_table(ctx, &st->tw_lo_i, nlo, r.wi, Fr::one(), 0));
+    MI_TRY(build_table(ctx, &st->tw_hi_i, nhi, r.wi, Fr::one(), h));
+    MI_TRY(build_table(ctx, &st->g_lo, nlo, r.g, Fr::one(), 0));
+    MI_TRY(build_table(ctx, &st->g_hi, nhi, r.g, Fr::one(), h));
+    MI_TRY(build_table(ctx, &st->gi_lo, nlo, r.gi, Fr::one(), 0));
+    MI_TRY(build_table(ctx, &st->gi_hi, nhi, r.gi, r.ninv, h));
+    MI_TRY(build_table(ctx, &st->ninv, 1, Fr::one(), r.ninv, 0));
     // computeH folds the 1/N of FFTInverse(a|b|c) into the coset shift of the next transform and den = 1/(g^N - 1) into the
     // last inverse transform's scaling (both are linear): 4 of its 121 products per element disappear
-    Fr gn = g;
-    for (u32 k = 0; k < log_n; k++) gn = fe_sqr(gn);
-    Fr den = fe_inv(gn - Fr::one());
-    MI_TRY(build_table(ctx, &st->g_hi_n, nhi, g, ninv, h));
-    MI_TRY(build_table(ctx, &st->gi_hi_nd, nhi, gi, ninv * den, h));
-    MI_TRY(build_table(ctx, &st->ninv_den, 1, Fr::one(), ninv * den, 0));
+    MI_TRY(build_table(ctx, &st->g_hi_n, nhi, r.g, r.ninv, h));
+    MI_TRY(build_table(ctx, &st->gi_hi_nd, nhi, r.gi, r.ninv * r.den, h));
+    MI_TRY(build_table(ctx, &st->ninv_den, 1, Fr::one(), r.ninv * r.den, 0));
     st->log_n = log_n;
     return MI_OK;
 }
@@ -470,7 +469,6 @@ static int32_t ensure_direct(mi_ctx *ctx, u32 log_n) {
     for (Fr **p : four) if (*p) { (void)hipFree(*p); *p = nullptr; }
     st->d_log_n = 0xffffffffu;
     if (log_n < st->direct_min_log_n) return MI_OK;
-    MI_TRY(ensure_tables(ctx, log_n));
     const size_t bytes = sizeof(Fr) << log_n;
     for (Fr **p : four)
         if (hipMalloc((void **)p, bytes) != hipSuccess) {   // no room: stay on the composed tables
@@ -478,108 +476,128 @@ static int32_t ensure_direct(mi_ctx *ctx, u32 log_n) {
             for (Fr **q : four) if (*q) { (void)hipFree(*q); *q = nullptr; }
             return MI_OK;
         }
-    const Fr w = fr_domain_generator(log_n), wi = fe_inv(w), g = fe_from_u32<FrParams>(5), gi = fe_inv(g);
-    Fr nn = Fr::zero();
-    nn.l[0] = (u32)(1u << log_n);
-    const Fr ninv = fe_inv(fe_to_mont(nn));
-    Fr gn = g;
-    for (u32 k = 0; k < log_n; k++) gn = fe_sqr(gn);
-    const Fr den = fe_inv(gn - Fr::one());
+    const NttRoots r = ntt_roots(log_n);
     const unsigned blocks = (unsigned)(((size_t)1 << log_n) + 255) / 256;
     if (pl.n_pass > 1) {
-        hipLaunchKernelGGL(k_tw_layout, dim3(blocks), dim3(256), 0, ctx->stream, st->d_tw_inv, log_n, pl.log_r[0], wi);
-        hipLaunchKernelGGL(k_tw_layout, dim3(blocks), dim3(256), 0, ctx->stream, st->d_tw_fwd, log_n, pl.log_r[0], w);
+        hipLaunchKernelGGL(k_tw_layout, dim3(blocks), dim3(256), 0, ctx->stream, st->d_tw_inv, log_n, pl.log_r[0], r.wi);
+        hipLaunchKernelGGL(k_tw_layout, dim3(blocks), dim3(256), 0, ctx->stream, st->d_tw_fwd, log_n, pl.log_r[0], r.w);
     }
-    hipLaunchKernelGGL(k_sc_layout, dim3(blocks), dim3(256), 0, ctx->stream, st->d_sc_fwd, log_n, g, ninv);          // variant 2
-    hipLaunchKernelGGL(k_sc_layout, dim3(blocks), dim3(256), 0, ctx->stream, st->d_sc_inv, log_n, gi, ninv * den);   // variant 3
+    hipLaunchKernelGGL(k_sc_layout, dim3(blocks), dim3(256), 0, ctx->stream, st->d_sc_fwd, log_n, r.g, r.ninv);            // NTT_COSET_FWD_NINV
+    hipLaunchKernelGGL(k_sc_layout, dim3(blocks), dim3(256), 0, ctx->stream, st->d_sc_inv, log_n, r.gi, r.ninv * r.den);   // NTT_COSET_INV_DEN
     MI_CHECK_HIP(ctx, hipGetLastError());
     st->d_log_n = log_n; st->d_log_r0 = pl.log_r[0]; st->d_npass = pl.n_pass;
     return MI_OK;
 }
 
-// One transform of size 2^log_n: dst <- NTT(src[0..n_valid) zero padded).  dst == src allowed.
-// variant (computeH only): 1 = inverse without the 1/N scaling; 2 = forward coset with 1/N folded into the shift tables;
-// 3 = inverse coset with den folded into its scaling; 4 = inverse scaled by den / N.  0 = exactly fft.Domain's FFT / FFTInverse.
-// load_mul / store_sub (computeH only, see NttPass): pointwise factor on the way into the first pass / pointwise subtrahend on the
-// way out of the last.
-// skip (computeH's fused contiguous pair, k_ntt_contig_pair): bit 0 = the first pass, bit 1 = the last pass is not launched but
-// returned in *cap / *cap_t for the fused kernel; bit 2 = nothing is launched at all (capture only).
-static int32_t ntt_run(mi_ctx *ctx, Fr *dst, const Fr *src, u32 n_valid, u32 log_n, u32 flags, u32 variant = 0,
-                       const Fr *load_mul = nullptr, const Fr *store_sub = nullptr, u32 skip = 0, NttPass *cap = nullptr, NttTables *cap_t = nullptr) {
-    NttState *st = state_of(ctx);
-    MI_TRY(ensure_tables(ctx, log_n));
-    const bool inverse = flags & MI_NTT_INVERSE, coset = flags & MI_NTT_COSET, dit = flags & MI_NTT_DIT;
-    NttTables t{};
+// ---------------------------------------------------------------- a transform: build, bind, launch
+static_assert(NTT_INVERSE == MI_NTT_INVERSE && NTT_COSET == MI_NTT_COSET && NTT_DIT == MI_NTT_DIT, "ntt_tile.cuh names the public flags");
+// build: the passes of one transform under the context's current knobs (ntt_tile.cuh; nothing bound yet)
+static NttTransform ntt_build(const NttState *st, u32 log_n, u32 flags, NttVariant variant, u32 n_valid) {
+    return ntt_build_transform(log_n, flags, variant, knobs_for(st, log_n), st->wave_stages != 0, n_valid);
+}
+// bind: the context's tables (ensure_tables / ensure_direct have run) and the optional pointers of the passes.  load_mul / store_sub
+// (computeH only, see NttPass): pointwise factor on the way into the first pass / pointwise subtrahend on the way out of the last.
+static int32_t ntt_bind(mi_ctx *ctx, NttTransform &tr, const Fr *load_mul = nullptr, const Fr *store_sub = nullptr) {
+    const NttState *st = state_of(ctx);
+    const bool inverse = tr.flags & NTT_INVERSE, coset = tr.flags & NTT_COSET;
+    NttTables &t = tr.t;
     t.small = inverse ? st->small_i : st->small_f;
     t.tw_lo = inverse ? st->tw_lo_i : st->tw_lo_f;
     t.tw_hi = inverse ? st->tw_hi_i : st->tw_hi_f;
     t.tw_h = st->tw_h;
     t.tw_64k = inverse ? st->tw64k_i : st->tw64k_f;
-    u32 load_scale = 0, store_scale = 0;
-    if (coset && !inverse) { t.sc_lo = st->g_lo; t.sc_hi = variant == 2 ? st->g_hi_n : st->g_hi; load_scale = dit ? 1 : 2; }
-    else if (coset && inverse) { t.sc_lo = st->gi_lo; t.sc_hi = variant == 3 ? st->gi_hi_nd : st->gi_hi; store_scale = dit ? 4 : 3; }
-    else if (inverse && variant != 1) { t.sc_lo = t.sc_hi = variant == 4 ? st->ninv_den : st->ninv; store_scale = 5; }
-    if (load_mul && (load_scale || dit)) MI_FAIL(ctx, MI_EINVAL, "internal: load_mul on a pass whose load side already has a factor");
-
-    const NttKnobs kn = knobs_for(st, log_n);
-    NttPlan pl = ntt_make_plan(log_n, kn.max_contig, kn.max_strided);
-    // log_s of pass i (DIF order): product of later radices
-    u32 log_s[8];
-    for (u32 i = 0, acc = log_n; i < pl.n_pass; i++) { acc -= pl.log_r[i]; log_s[i] = acc; }
-    const Fr *cur_src = src;
-    for (u32 step = 0; step < pl.n_pass; step++) {
-        u32 i = dit ? pl.n_pass - 1 - step : step;
-        NttPass p{};
-        p.log_n = log_n; p.log_r = pl.log_r[i]; p.log_s = log_s[i];
-        u32 room = kn.log_e > p.log_r ? kn.log_e - p.log_r : 0;
-        u32 avail = p.log_s == 0 ? log_n - p.log_r : p.log_s;
-        p.log_c = room < avail ? room : avail;
-        p.dit = dit ? 1 : 0;
-        p.twiddle = p.log_s != 0;
-        p.scale = 0;
-        if (step == 0 && load_scale) p.scale = load_scale;
-        if (step == pl.n_pass - 1 && store_scale) {
-            if (p.scale) MI_FAIL(ctx, MI_EINVAL, "internal: load and store scale on one pass");
-            p.scale = store_scale;
-        }
-        p.n_valid = step == 0 ? n_valid : (1u << log_n);
-        if (step == 0) p.load_mul = load_mul;
-        if (step == pl.n_pass - 1) p.store_sub = store_sub;
-        // the elements travel lazily reduced (below 4p) between the stages and the passes (ntt_tile.cuh); the last pass of a transform
-        // whose output is final -- fft.Domain's own transforms (variant 0) and computeH's last one (variant 3: h) -- stores canonical values
-        if (step == pl.n_pass - 1 && (variant == 0 || variant == 3)) p.canon = 1;
-        // computeH's direct tables (variant != 0 only): the twiddle of the M = N pass, the coset shift of the contiguous pass
-        const bool direct = variant != 0 && st->d_log_n == log_n && st->d_sc_fwd;
-        if (direct && p.twiddle && i == 0 && pl.n_pass > 1) p.tw_direct = inverse ? st->d_tw_inv : st->d_tw_fwd;
-        if (direct && variant == 2 && p.scale == 1) p.sc_direct = st->d_sc_fwd;
-        if (direct && variant == 3 && p.scale == 3) p.sc_direct = st->d_sc_inv;
-        const bool wave = p.log_r >= 7 && st->wave_stages;
-        p.lds_pad = wave && p.log_s != 0 ? 1 : 0;
-        if (((skip & 1) && step == 0) || ((skip & 2) && step == pl.n_pass - 1)) {
-            if (cap) { *cap = p; *cap_t = t; }
-            cur_src = dst;
-            continue;
-        }
-        if (skip & 4) continue;
-        u32 tiles = 1u << (log_n - p.log_r - p.log_c);
-        size_t lds_bytes = (size_t)32 * ntt_plane_slots(p);
-        if (st->lds_floor > lds_bytes) lds_bytes = st->lds_floor;   // occupancy cap of the pass kernels (mi_debug_set_knob "ntt_lds_floor_kb")
-        u32 E = 1u << (p.log_r + p.log_c);
-        // one butterfly per thread per stage when the tile allows: 64 KiB of LDS admits two workgroups per CU,
-        // so 1024-thread workgroups are what fills the SIMDs (8 waves each) and hides the mad->addc chains
-        u32 threads = E / 2 >= st->threads ? st->threads : (E / 2 >= 64 ? E / 2 : 64);
-        if (wave) hipLaunchKernelGGL(k_ntt_pass_wave, dim3(tiles), dim3(threads > 256 ? 256 : threads), lds_bytes, ctx->stream, dst, cur_src, p, t);
-        else hipLaunchKernelGGL(k_ntt_pass, dim3(tiles), dim3(threads), lds_bytes, ctx->stream, dst, cur_src, p, t);
-        MI_CHECK_HIP(ctx, hipGetLastError());
-        cur_src = dst;
-        ctx->stats.ntt_launches++;
+    if (coset && !inverse) { t.sc_lo = st->g_lo; t.sc_hi = tr.variant == NTT_COSET_FWD_NINV ? st->g_hi_n : st->g_hi; }
+    else if (coset && inverse) { t.sc_lo = st->gi_lo; t.sc_hi = tr.variant == NTT_COSET_INV_DEN ? st->gi_hi_nd : st->gi_hi; }
+    else if (inverse && tr.variant != NTT_INV_UNSCALED) t.sc_lo = t.sc_hi = tr.variant == NTT_INV_DEN_NINV ? st->ninv_den : st->ninv;
+    NttPass &first = tr.pass[0];
+    if (load_mul && (first.scale == 1 || first.scale == 2 || first.dit)) MI_FAIL(ctx, MI_EINVAL, "internal: load_mul on a pass whose load side already has a factor");
+    first.load_mul = load_mul;
+    tr.pass[tr.n_pass - 1].store_sub = store_sub;
+    // computeH's direct tables: the twiddle of the M = N pass, the coset shift of the contiguous pass
+    if (tr.variant == NTT_PLAIN || st->d_log_n != tr.log_n || !st->d_sc_fwd) return MI_OK;
+    for (u32 i = 0; i < tr.n_pass; i++) {
+        NttPass &p = tr.pass[i];
+        if (p.twiddle && p.log_r + p.log_s == tr.log_n) p.tw_direct = inverse ? st->d_tw_inv : st->d_tw_fwd;
+        if (tr.variant == NTT_COSET_FWD_NINV && p.scale == 1) p.sc_direct = st->d_sc_fwd;
+        if (tr.variant == NTT_COSET_INV_DEN && p.scale == 3) p.sc_direct = st->d_sc_inv;
     }
-    if (!(skip & 4)) ctx->stats.ntt_elems += (u64)1 << log_n;
     return MI_OK;
 }
 
+// launch: one function per kernel family; each owns its grid, block, LDS size, error check and launch count
+static u32 ntt_tiles(const NttPass &p) { return 1u << (p.log_n - p.log_r - p.log_c); }
+static size_t ntt_lds_bytes(const NttPass &p) { return (size_t)32 * ntt_plane_slots(p); }
+static int32_t ntt_launched(mi_ctx *ctx) {
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    ctx->stats.ntt_launches++;
+    return MI_OK;
+}
+static int32_t launch_pass(mi_ctx *ctx, Fr *dst, const Fr *src, const NttPass &p, const NttTables &t) {
+    const NttState *st = state_of(ctx);
+    const bool wave = p.log_r >= 7 && st->wave_stages;
+    size_t lds_bytes = ntt_lds_bytes(p);
+    if (st->lds_floor > lds_bytes) lds_bytes = st->lds_floor;   // occupancy cap of the pass kernels (mi_debug_set_knob "ntt_lds_floor_kb")
+    const u32 E = 1u << (p.log_r + p.log_c);
+    // one butterfly per thread per stage when the tile allows: 64 KiB of LDS admits two workgroups per CU,
+    // so 1024-thread workgroups are what fills the SIMDs (8 waves each) and hides the mad->addc chains
+    u32 threads = E / 2 >= st->threads ? st->threads : (E / 2 >= 64 ? E / 2 : 64);
+    if (wave && threads > 256) threads = 256;
+    void (*const kernel)(Fr *, const Fr *, NttPass, NttTables) = wave ? k_ntt_pass_wave : k_ntt_pass;
+    hipLaunchKernelGGL(kernel, dim3(ntt_tiles(p)), dim3(threads), lds_bytes, ctx->stream, dst, src, p, t);
+    return ntt_launched(ctx);
+}
+// computeH's a and b: the inverse transform's last pass pi and the coset transform's first pass pf (the same contiguous tiles)
+static int32_t launch_contig_pair(mi_ctx *ctx, Fr *v, const NttPass &pi, const NttTables &ti, const NttPass &pf, const NttTables &tf) {
+    hipLaunchKernelGGL(k_ntt_contig_pair, dim3(ntt_tiles(pi)), dim3(256), ntt_lds_bytes(pi), ctx->stream, v, pi, ti, pf, tf);
+    return ntt_launched(ctx);
+}
+// the coset transform's last pass pc of a and of b, the product, the last transform's first pass pl (the same strided tiles).
+// radix 2^7: one wave per 128-row sub-block of the tile, 64 * 2^log_c threads (256 at the default 2^9-element tiles); radix 2^8: 256 threads
+static int32_t launch_strided_triple(mi_ctx *ctx, Fr *a, const Fr *b, const NttPass &pc, const NttTables &tc, const NttPass &pl, const NttTables &tl) {
+    const bool r7 = pc.log_r == 7;
+    void (*const kernel)(Fr *, const Fr *, NttPass, NttTables, NttPass, NttTables) = r7 ? k_ntt_strided_triple : k_ntt_strided_triple8;
+    hipLaunchKernelGGL(kernel, dim3(ntt_tiles(pc)), dim3(r7 ? 64u << pc.log_c : 256u), ntt_lds_bytes(pc), ctx->stream, a, b, pc, tc, pl, tl);
+    return ntt_launched(ctx);
+}
+// the last transform's last pass pa and c's last pass pc (the same contiguous tiles): h = A - C.  The Z MSM's digit count rides along when
+// prove.hip armed the hook and this launch's tiles are whole slices of that sort
+static int32_t launch_contig_last_sub(mi_ctx *ctx, Fr *A, const Fr *C, const NttPass &pa, const NttTables &ta, const NttPass &pc, const NttTables &tc) {
+    const size_t n = (size_t)1 << pa.log_n;
+    const u32 E = 1u << (pa.log_r + pa.log_c);
+    size_t lds_bytes = ntt_lds_bytes(pa);
+    Msm2Shape zs{};
+    bool count = ctx->zhook.armed && ctx->zhook.C1;
+    if (count) {
+        std::memcpy(&zs, ctx->zhook.shape, sizeof(zs));
+        const size_t with_counters = lds_bytes + (size_t)(E / MSM2_SLICE) * zs.ngroups * 4;
+        count = E % MSM2_SLICE == 0 && E / MSM2_SLICE <= 4 && zs.n <= n && (u64)zs.nslices * MSM2_SLICE == n && zs.c >= 17 && zs.c <= 22 && !zs.wkeys &&
+                with_counters <= 160 * 1024;
+        if (count) lds_bytes = with_counters;
+    }
+    ctx->zhook.armed = false;
+    if (count) {
+        hipLaunchKernelGGL(k_last_sub_count[zs.c - 17], dim3(ntt_tiles(pa)), dim3(256), lds_bytes, ctx->stream, A, C, pa, ta, pc, tc, zs, ctx->zhook.C1);
+        ctx->zhook.done = true; ctx->zhook.h = A;
+        ctx->z_count_fused_launches++;
+    } else {
+        hipLaunchKernelGGL(k_ntt_contig_last_sub, dim3(ntt_tiles(pa)), dim3(256), lds_bytes, ctx->stream, A, C, pa, ta, pc, tc);
+    }
+    return ntt_launched(ctx);
+}
+// passes [from, to) of a bound transform, one launch each: pass 0 reads src, every later one works on dst in place
+static int32_t launch_passes(mi_ctx *ctx, const NttTransform &tr, Fr *dst, const Fr *src, u32 from, u32 to) {
+    for (u32 i = from; i < to; i++) MI_TRY(launch_pass(ctx, dst, i == 0 ? src : dst, tr.pass[i], tr.t));
+    return MI_OK;
+}
+
+// One fft.Domain transform of size 2^log_n, in place: build, bind, launch
 int32_t mi_ntt_dev_impl(mi_ctx *ctx, mi_fr *inout_dev, uint32_t log_n, uint32_t flags) {
-    return ntt_run(ctx, (Fr *)inout_dev, (const Fr *)inout_dev, 1u << log_n, log_n, flags);
+    MI_TRY(ensure_tables(ctx, log_n));
+    NttTransform tr = ntt_build(state_of(ctx), log_n, flags, NTT_PLAIN, 1u << log_n);
+    MI_TRY(ntt_bind(ctx, tr));
+    MI_TRY(launch_passes(ctx, tr, (Fr *)inout_dev, (const Fr *)inout_dev, 0, tr.n_pass));
+    ctx->stats.ntt_elems += (u64)1 << log_n;
+    return MI_OK;
 }
 
 // computeH in four parts on ctx->stream, so that a caller whose inputs arrive one vector at a time (the host-pointer prove: a, b, c cross
@@ -590,137 +608,81 @@ int32_t mi_ntt_dev_impl(mi_ctx *ctx, mi_fr *inout_dev, uint32_t log_n, uint32_t 
 //                                        row by row) on the way into the first pass -- what c is for every witness gnark's solver accepts
 //   part 3                               the strided triple (or the coset FFTs' last passes) and the last transform -> h_out
 // The same launches as the one-call form, in an order that differs only between independent vectors: identical h.
+//
+// The schedule: the four distinct transforms, each built once and bound, and which of the three seams between them run as one launch.
+// A part launches its slice of these lists by index.  (Built per part, not kept: the knobs may change between calls.)
 struct ComputeHPlan {
-    bool pair, triple, last;   // last: c's last pass and the last transform's last pass run fused (decided from the plan alone: both are the
-                               // contiguous pass of a plain DIF transform, equal shapes by construction)
-    NttPass pc, plast;
-    NttTables tc, tlast;
+    NttTransform inv, cos, cinv, last;   // N FFTInverse of a / b; their coset FFT; den FFTInverse of c; den FFTInverse on the coset (-> h)
+    u32 pair, triple, last_sub;          // 1: that seam is fused
 };
-static int32_t compute_h_plan(mi_ctx *ctx, uint32_t log_n, Fr *A, ComputeHPlan &cp) {
-    const size_t n = (size_t)1 << log_n;
-    NttState *st = state_of(ctx);
-    const NttKnobs kn = knobs_for(st, log_n);
-    const NttPlan pl = ntt_make_plan(log_n, kn.max_contig, kn.max_strided);
+// what a fused kernel needs of the two passes it joins: the same tile, in LDS too
+static bool same_tile(const NttPass &p, const NttPass &q) {
+    return p.log_r == q.log_r && p.log_s == q.log_s && p.log_c == q.log_c && p.lds_pad == q.lds_pad;
+}
+// n_valid: the rows of a, b, c that are given; c_mul: the part's src2.  B, C: where b and c live by part 3
+static int32_t compute_h_plan(mi_ctx *ctx, u32 log_n, u32 n_valid, const Fr *c_mul, const Fr *B, const Fr *C, ComputeHPlan &cp) {
+    const NttState *st = state_of(ctx);
+    cp.inv = ntt_build(st, log_n, NTT_INVERSE, NTT_INV_UNSCALED, n_valid);
+    cp.cos = ntt_build(st, log_n, NTT_DIT | NTT_COSET, NTT_COSET_FWD_NINV, 1u << log_n);
+    cp.cinv = ntt_build(st, log_n, NTT_INVERSE, NTT_INV_DEN_NINV, n_valid);   // (part 3 takes only its last pass, which reads whole tiles whatever n_valid)
+    cp.last = ntt_build(st, log_n, NTT_INVERSE | NTT_COSET, NTT_COSET_INV_DEN, 1u << log_n);
+    const u32 m = cp.last.n_pass;
+    const bool seams = st->wave_stages && m >= 2;   // every fused kernel runs the register stages and joins two different passes
+    const NttPass &strided = cp.last.pass[0], &contig = cp.last.pass[m - 1];
     // a and b: the contiguous last pass of the inverse transform and the contiguous first pass of the coset transform run as ONE
     // launch on the same tiles (k_ntt_contig_pair) when the plan has such a pair of radix >= 2^7
-    cp.pair = st->fuse_pair && st->wave_stages && pl.n_pass >= 2 && pl.log_r[pl.n_pass - 1] >= 7;
+    cp.pair = seams && st->fuse_pair && same_tile(cp.inv.pass[m - 1], cp.cos.pass[0]) && contig.log_r >= 7;
     // The coset FFT's LAST pass (of a and of b), the product and the last transform's FIRST pass share their strided tiles: one
-    // launch (k_ntt_strided_triple / k_ntt_strided_triple8) when that pass has radix 2^7 or 2^8 and the tile shape fits
-    cp.triple = st->fuse_triple && st->wave_stages && pl.n_pass >= 2 && (pl.log_r[0] == 7 || pl.log_r[0] == 8);
-    {
-        const u32 lr = pl.log_r[pl.n_pass - 1];
-        const u32 room = kn.log_e > lr ? kn.log_e - lr : 0, avail = log_n - lr, lc = room < avail ? room : avail;
-        cp.last = st->fuse_last && st->wave_stages && pl.n_pass >= 2 && lr >= 7 && (1u << (lr + lc)) <= 4 * 256;
-    }
-    cp.pc = NttPass{}; cp.plast = NttPass{}; cp.tc = NttTables{}; cp.tlast = NttTables{};
-    if (cp.triple) {   // capture the two passes without launching anything, and check the tile shape before committing to the fused form
-        MI_TRY(ntt_run(ctx, A, A, (u32)n, log_n, MI_NTT_DIT | MI_NTT_COSET, 2, nullptr, nullptr, 2 | 4, &cp.pc, &cp.tc));
-        MI_TRY(ntt_run(ctx, A, A, (u32)n, log_n, MI_NTT_INVERSE | MI_NTT_COSET, 3, nullptr, nullptr, 1 | 4, &cp.plast, &cp.tlast));
-        const NttPass &pc = cp.pc, &plast = cp.plast;
-        cp.triple = pc.log_r == plast.log_r && pc.log_s == plast.log_s && pc.log_c == plast.log_c && pc.log_s != 0 && pc.lds_pad == plast.lds_pad && !pc.scale && !plast.scale &&
-                    ((pc.log_r == 7 && pc.log_c <= 3) ||                      // one wave per 128-row sub-block, up to 512 threads
-                     (pc.log_r == 8 && pc.log_c >= 1 && pc.log_c <= 2));      // k_ntt_strided_triple8: 256 threads, 1 or 2 pairs at distance 128 each
-    }
-    return MI_OK;
+    // launch when that pass has radix 2^7 (one wave per 128-row sub-block, up to 512 threads) or 2^8 (k_ntt_strided_triple8: 256 threads,
+    // 1 or 2 pairs at distance 128 each)
+    cp.triple = seams && st->fuse_triple && same_tile(cp.cos.pass[m - 1], strided) &&
+                ((strided.log_r == 7 && strided.log_c <= 3) || (strided.log_r == 8 && strided.log_c >= 1 && strided.log_c <= 2));
+    // c's last pass and the last transform's last pass, which subtracts it: one launch (k_ntt_contig_last_sub) at radix >= 2^7 and at
+    // most four elements per thread
+    cp.last_sub = seams && st->fuse_last && same_tile(cp.cinv.pass[m - 1], contig) && contig.log_r >= 7 && (1u << (contig.log_r + contig.log_c)) <= 4 * 256;
+    // the product a b is taken on the way into the last transform's first pass and c subtracted on the way out of its last (no pointwise
+    // kernel, no extra round trip through HBM), unless the fused kernel at that end does it
+    MI_TRY(ntt_bind(ctx, cp.inv));
+    MI_TRY(ntt_bind(ctx, cp.cos));
+    MI_TRY(ntt_bind(ctx, cp.cinv, c_mul));
+    return ntt_bind(ctx, cp.last, cp.triple ? nullptr : B, cp.last_sub ? nullptr : C);
 }
 int32_t mi_compute_h_part(mi_ctx *ctx, uint32_t log_n, int part, const mi_fr *src, size_t n_constraints, mi_fr *h_out, const mi_fr *src2) {
     static const char *const range_names[4] = {"mi.computeH.a.enqueue", "mi.computeH.b.enqueue", "mi.computeH.c.enqueue", "mi.computeH.last.enqueue"};
     const MiRange range(range_names[part & 3]);
-    const size_t n = (size_t)1 << log_n;
+    const u64 n = (u64)1 << log_n;
     // gnark's computeH (7 transforms): a, b, c <- FFTInverse; a, b, c <- FFT on the coset; a <- (a b - c) den; h <- FFTInverse on
     // the coset.  The last transform is linear and undoes the coset FFT of c exactly:
     //     h = cosetFFTInverse((ca cb - cc) den) = den cosetFFTInverse(ca cb) - den FFTInverse(c),
     // so the coset FFT of c is never computed -- SIX transforms, the same field elements (exact arithmetic), for ANY a, b, c.
+    MI_TRY(ensure_tables(ctx, log_n));
     MI_TRY(ensure_direct(ctx, log_n));
     MI_TRY(mi_reserve(ctx, ctx->ws[WS_H_B], n * sizeof(Fr)));
     MI_TRY(mi_reserve(ctx, ctx->ws[WS_H_C], n * sizeof(Fr)));
     Fr *A = (Fr *)h_out, *B = (Fr *)ctx->ws[WS_H_B].p, *C = (Fr *)ctx->ws[WS_H_C].p;
     ComputeHPlan cp;
-    MI_TRY(compute_h_plan(ctx, log_n, A, cp));
-    const u32 first_skip = cp.pair ? 1u : 0u;
+    MI_TRY(compute_h_plan(ctx, log_n, (u32)n_constraints, (const Fr *)src2, B, C, cp));
+    const u32 m = cp.last.n_pass;
     if (part == 0 || part == 1) {
-        // 1. v <- N FFTInverse(v, DIF) (zero padding fused into the first pass's load; the 1/N rides in the coset shift)
+        // v <- N FFTInverse(v, DIF) (zero padding fused into the first pass's load; the 1/N rides in the coset shift), then
+        // v <- FFT(v, DIT, OnCoset) without its last pass when that one runs in the triple
         Fr *v = part == 0 ? A : B;
-        if (!cp.pair) {
-            MI_TRY(ntt_run(ctx, v, (const Fr *)src, (u32)n_constraints, log_n, MI_NTT_INVERSE, 1));
-        } else {
-            NttPass pi{}, pf{};
-            NttTables ti{}, tf{};
-            MI_TRY(ntt_run(ctx, v, (const Fr *)src, (u32)n_constraints, log_n, MI_NTT_INVERSE, 1, nullptr, nullptr, 2, &pi, &ti));
-            MI_TRY(ntt_run(ctx, v, v, (u32)n, log_n, MI_NTT_DIT | MI_NTT_COSET, 2, nullptr, nullptr, 1 | 4, &pf, &tf));
-            if (pi.log_r != pf.log_r || pi.log_c != pf.log_c || pi.log_s || pf.log_s) MI_FAIL(ctx, MI_EINVAL, "internal: contiguous pass pair does not match");
-            hipLaunchKernelGGL(k_ntt_contig_pair, dim3(1u << (log_n - pi.log_r - pi.log_c)), dim3(256), (size_t)32 * ntt_plane_slots(pi), ctx->stream, v, pi, ti, pf, tf);
-            MI_CHECK_HIP(ctx, hipGetLastError());
-            ctx->stats.ntt_launches++;
-        }
-        // 2. v <- FFT(v, DIT, OnCoset): the rest of it after the pair, without its last pass when that one runs in the triple
-        NttPass px{};
-        NttTables tx{};
-        return ntt_run(ctx, v, v, (u32)n, log_n, MI_NTT_DIT | MI_NTT_COSET, 2, nullptr, nullptr, first_skip | (cp.triple ? 2u : 0u), &px, &tx);
+        MI_TRY(launch_passes(ctx, cp.inv, v, (const Fr *)src, 0, m - cp.pair));
+        if (cp.pair) MI_TRY(launch_contig_pair(ctx, v, cp.inv.pass[m - 1], cp.inv.t, cp.cos.pass[0], cp.cos.t));
+        MI_TRY(launch_passes(ctx, cp.cos, v, v, cp.pair, m - cp.triple));
+        ctx->stats.ntt_elems += 2 * n;
+    } else if (part == 2) {
+        // c <- den FFTInverse(c, DIF) (one constant den / N on the way out), bit-reversed like h; its last pass waits for part 3 when fused
+        MI_TRY(launch_passes(ctx, cp.cinv, C, (const Fr *)src, 0, m - cp.last_sub));
+        ctx->stats.ntt_elems += n;
+    } else {
+        // h <- den FFTInverse(a b, DIF, OnCoset) - c, left bit-reversed like gnark
+        if (cp.triple) MI_TRY(launch_strided_triple(ctx, A, B, cp.cos.pass[m - 1], cp.cos.t, cp.last.pass[0], cp.last.t));
+        MI_TRY(launch_passes(ctx, cp.last, A, A, cp.triple, m - cp.last_sub));
+        if (cp.last_sub) MI_TRY(launch_contig_last_sub(ctx, A, C, cp.last.pass[m - 1], cp.last.t, cp.cinv.pass[m - 1], cp.cinv.t));
+        ctx->stats.ntt_elems += n;
     }
-    if (part == 2) {   // c <- den FFTInverse(c, DIF) (one constant den / N on the way out), bit-reversed like h; its last pass waits for part 3 when fused
-        NttPass px{};
-        NttTables tx{};
-        return ntt_run(ctx, C, (const Fr *)src, (u32)n_constraints, log_n, MI_NTT_INVERSE, 4, (const Fr *)src2, nullptr, cp.last ? 2u : 0u, &px, &tx);
-    }
-    // 3. h <- den FFTInverse(a b, DIF, OnCoset) - c, left bit-reversed like gnark: the product a b is taken on the way into the
-    //    first pass, the subtraction on the way out of the last (no pointwise kernel, no extra round trip through HBM)
-    // the last launch when fused: both last passes captured (nothing launched), one kernel does them and the subtraction
-    auto last_fused = [&]() -> int32_t {
-        NttPass pa{}, pcl{};
-        NttTables ta{}, tcl{};
-        MI_TRY(ntt_run(ctx, C, C, (u32)n, log_n, MI_NTT_INVERSE, 4, nullptr, nullptr, 2 | 4, &pcl, &tcl));
-        MI_TRY(ntt_run(ctx, A, A, (u32)n, log_n, MI_NTT_INVERSE | MI_NTT_COSET, 3, nullptr, nullptr, 2 | 4, &pa, &ta));
-        if (pa.log_r != pcl.log_r || pa.log_c != pcl.log_c || pa.log_s || pcl.log_s || pa.dit || pcl.dit || pa.lds_pad != pcl.lds_pad)
-            MI_FAIL(ctx, MI_EINVAL, "internal: the two last passes of computeH do not match");
-        // the Z MSM's digit count rides along when prove.hip armed the hook and this launch's tiles are whole slices of that sort
-        const u32 E = 1u << (pa.log_r + pa.log_c);
-        Msm2Shape zs{};
-        bool count = ctx->zhook.armed && ctx->zhook.C1;
-        if (count) {
-            std::memcpy(&zs, ctx->zhook.shape, sizeof(zs));
-            count = E % MSM2_SLICE == 0 && E / MSM2_SLICE <= 4 && zs.n <= n && (u64)zs.nslices * MSM2_SLICE == n && zs.c >= 17 && zs.c <= 22 && !zs.wkeys &&
-                    (size_t)32 * ntt_plane_slots(pa) + (size_t)(E / MSM2_SLICE) * zs.ngroups * 4 <= 160 * 1024;
-        }
-        ctx->zhook.armed = false;
-        if (count) {
-            const size_t lds_bytes = (size_t)32 * ntt_plane_slots(pa) + (size_t)(E / MSM2_SLICE) * zs.ngroups * 4;
-#define MI_LAST_COUNT(CW) do { \
-            hipLaunchKernelGGL(k_ntt_contig_last_sub_count<CW>, dim3(1u << (log_n - pa.log_r - pa.log_c)), dim3(256), lds_bytes, ctx->stream, A, (const Fr *)C, pa, ta, pcl, tcl, zs, ctx->zhook.C1); } while (0)
-            switch (zs.c) { case 17: MI_LAST_COUNT(17); break; case 18: MI_LAST_COUNT(18); break; case 19: MI_LAST_COUNT(19); break; case 20: MI_LAST_COUNT(20); break;
-                            case 21: MI_LAST_COUNT(21); break; default: MI_LAST_COUNT(22); break; }
-#undef MI_LAST_COUNT
-            ctx->zhook.done = true; ctx->zhook.h = A;
-            ctx->z_count_fused_launches++;
-        } else {
-            hipLaunchKernelGGL(k_ntt_contig_last_sub, dim3(1u << (log_n - pa.log_r - pa.log_c)), dim3(256), (size_t)32 * ntt_plane_slots(pa), ctx->stream, A, (const Fr *)C, pa, ta, pcl, tcl);
-        }
-        MI_CHECK_HIP(ctx, hipGetLastError());
-        ctx->stats.ntt_launches++;
-        return MI_OK;
-    };
-    if (!cp.triple) {
-        if (!cp.last) return ntt_run(ctx, A, A, (u32)n, log_n, MI_NTT_INVERSE | MI_NTT_COSET, 3, B, C);
-        NttPass px{};
-        NttTables tx{};
-        MI_TRY(ntt_run(ctx, A, A, (u32)n, log_n, MI_NTT_INVERSE | MI_NTT_COSET, 3, B, nullptr, 2, &px, &tx));
-        return last_fused();
-    }
-    // radix 2^7: one wave per 128-row sub-block of the tile, 64 * 2^log_c threads (256 at the default 2^9-element tiles); radix 2^8: 256 threads
-    const NttPass &pc = cp.pc;
-    if (pc.log_r == 7)
-        hipLaunchKernelGGL(k_ntt_strided_triple, dim3(1u << (log_n - pc.log_r - pc.log_c)), dim3(64u << pc.log_c), (size_t)32 * ntt_plane_slots(pc), ctx->stream,
-                           A, (const Fr *)B, pc, cp.tc, cp.plast, cp.tlast);
-    else
-        hipLaunchKernelGGL(k_ntt_strided_triple8, dim3(1u << (log_n - pc.log_r - pc.log_c)), dim3(256), (size_t)32 * ntt_plane_slots(pc), ctx->stream,
-                           A, (const Fr *)B, pc, cp.tc, cp.plast, cp.tlast);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    ctx->stats.ntt_launches++;
-    if (!cp.last) return ntt_run(ctx, A, A, (u32)n, log_n, MI_NTT_INVERSE | MI_NTT_COSET, 3, nullptr, C, 1);
-    NttPass px{};
-    NttTables tx{};
-    MI_TRY(ntt_run(ctx, A, A, (u32)n, log_n, MI_NTT_INVERSE | MI_NTT_COSET, 3, nullptr, nullptr, 1 | 2, &px, &tx));
-    return last_fused();
+    return MI_OK;
 }
 int32_t mi_compute_h_dev_impl(mi_ctx *ctx, uint32_t log_n, const mi_fr *a, const mi_fr *b, const mi_fr *c,
                               size_t n_constraints, mi_fr *h_out) {

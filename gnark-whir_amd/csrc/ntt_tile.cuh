@@ -230,3 +230,56 @@ MI_HD NttPlan ntt_make_plan(u32 log_n, u32 max_contig, u32 max_strided) {
     pl.log_r[pl.n_pass++] = max_contig;
     return pl;
 }
+
+// ---------------------------------------------------------------- transform: the passes of one NTT, in execution order
+// Pure host arithmetic (no device call, no table): ntt.hip binds pointers to what this returns and launches it, the host emulation of
+// the CPU tests runs the very same records through ntt_tile_load / stage / store.
+enum : u32 { NTT_INVERSE = 1, NTT_COSET = 2, NTT_DIT = 4 };   // the transform's flags (the public MI_NTT_* values)
+enum NttVariant : u32 {
+    NTT_PLAIN = 0,           // exactly fft.Domain's FFT / FFTInverse
+    // computeH only:
+    NTT_INV_UNSCALED = 1,    // inverse without the 1/N scaling
+    NTT_COSET_FWD_NINV = 2,  // forward coset with 1/N folded into the shift tables
+    NTT_COSET_INV_DEN = 3,   // inverse coset with den folded into its scaling
+    NTT_INV_DEN_NINV = 4,    // inverse scaled by den / N
+};
+struct NttKnobs { u32 log_e, max_contig, max_strided; };   // tile of <= 2^log_e elements; radix limits of ntt_make_plan
+struct NttTransform {
+    u32 log_n, flags;
+    NttVariant variant;
+    u32 n_pass;
+    NttPass pass[8];
+    NttTables t;       // this and the passes' pointers: null as built, filled by whoever owns the tables
+};
+// wave_stages: passes of radix >= 2^7 run seven stages in registers (their strided tiles are padded in LDS).
+// n_valid: the first pass reads elements at or past n_valid as zero.
+inline NttTransform ntt_build_transform(u32 log_n, u32 flags, NttVariant variant, NttKnobs kn, bool wave_stages, u32 n_valid) {
+    const bool inverse = flags & NTT_INVERSE, coset = flags & NTT_COSET, dit = flags & NTT_DIT;
+    u32 load_scale = 0, store_scale = 0;   // at most one of them: a forward transform scales on the way in, an inverse one on the way out
+    if (coset && !inverse) load_scale = dit ? 1 : 2;
+    else if (coset && inverse) store_scale = dit ? 4 : 3;
+    else if (inverse && variant != NTT_INV_UNSCALED) store_scale = 5;
+    const NttPlan pl = ntt_make_plan(log_n, kn.max_contig, kn.max_strided);
+    u32 log_s[8];   // of pass i in DIF order: the product of the later radices
+    for (u32 i = 0, acc = log_n; i < pl.n_pass; i++) { acc -= pl.log_r[i]; log_s[i] = acc; }
+    NttTransform tr{};
+    tr.log_n = log_n; tr.flags = flags; tr.variant = variant; tr.n_pass = pl.n_pass;
+    for (u32 step = 0; step < pl.n_pass; step++) {
+        const u32 i = dit ? pl.n_pass - 1 - step : step;
+        const bool first = step == 0, last = step == pl.n_pass - 1;
+        NttPass &p = tr.pass[step];
+        p.log_n = log_n; p.log_r = pl.log_r[i]; p.log_s = log_s[i];
+        const u32 room = kn.log_e > p.log_r ? kn.log_e - p.log_r : 0;
+        const u32 avail = p.log_s == 0 ? log_n - p.log_r : p.log_s;
+        p.log_c = room < avail ? room : avail;
+        p.dit = dit ? 1 : 0;
+        p.twiddle = p.log_s != 0;
+        p.scale = first && load_scale ? load_scale : last ? store_scale : 0;
+        p.n_valid = first ? n_valid : (1u << log_n);
+        p.lds_pad = wave_stages && p.log_r >= 7 && p.log_s != 0 ? 1 : 0;
+        // the elements travel lazily reduced (below 4p) between the stages and the passes; the last pass of a transform whose output
+        // is final -- fft.Domain's own transforms and computeH's last one (h) -- stores canonical values
+        p.canon = last && (variant == NTT_PLAIN || variant == NTT_COSET_INV_DEN);
+    }
+    return tr;
+}

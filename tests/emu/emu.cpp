@@ -230,7 +230,7 @@ static Fr fr_from_u64x4(u64 a, u64 b, u64 c, u64 d) {
 extern "C" int emu_ntt_fused(void *data_v, uint32_t log_n, uint32_t flags, uint32_t log_e, uint32_t max_contig, uint32_t max_strided,
                              uint32_t nthr, uint32_t n_valid, const void *load_mul, const void *store_sub) {
     Fr *data = (Fr *)data_v;
-    const bool inverse = flags & 1, coset = flags & 2, dit = flags & 4;
+    const bool inverse = flags & NTT_INVERSE, coset = flags & NTT_COSET;
     Fr root = fr_from_u64x4(0x9bd61b6e725b19f0ull, 0x402d111e41112ed4ull, 0x00e0a7eb8ef62abcull, 0x2a3c09f0a58a7e85ull);
     Fr w2048 = root; for (int k = 12; k < 28; k++) w2048 = fe_sqr(w2048);   // w_4096 (name kept)
     Fr w = root; for (u32 k = log_n; k < 28; k++) w = fe_sqr(w);
@@ -252,28 +252,15 @@ extern "C" int emu_ntt_fused(void *data_v, uint32_t log_n, uint32_t flags, uint3
         t.tw_64k = tw64k.data();
     }
     std::vector<Fr> nv(1, ninv);
-    u32 load_scale = 0, store_scale = 0;
-    if (coset && !inverse) load_scale = dit ? 1 : 2;
-    else if (coset && inverse) store_scale = dit ? 4 : 3;
-    else if (inverse) { t.sc_lo = nv.data(); t.sc_hi = nv.data(); store_scale = 5; }
-    NttPlan pl = ntt_make_plan(log_n, max_contig, max_strided);
-    u32 log_s[8];
-    for (u32 i = 0, acc = log_n; i < pl.n_pass; i++) { acc -= pl.log_r[i]; log_s[i] = acc; }
-    for (u32 step = 0; step < pl.n_pass; step++) {
-        u32 i = dit ? pl.n_pass - 1 - step : step;
-        NttPass p{};
-        p.log_n = log_n; p.log_r = pl.log_r[i]; p.log_s = log_s[i];
-        u32 room = log_e > p.log_r ? log_e - p.log_r : 0;
-        u32 avail = p.log_s == 0 ? log_n - p.log_r : p.log_s;
-        p.log_c = room < avail ? room : avail;
-        p.dit = dit; p.twiddle = p.log_s != 0; p.scale = 0;
-        if (step == 0 && load_scale) p.scale = load_scale;
-        if (step == pl.n_pass - 1 && store_scale) { if (p.scale) return -1; p.scale = store_scale; }
-        p.n_valid = step == 0 ? n_valid : (1u << log_n);
-        if (step == 0) p.load_mul = (const Fr *)load_mul;
-        if (step == pl.n_pass - 1) { p.store_sub = (const Fr *)store_sub; p.canon = 1; }   // (the elements are lazily reduced until the last store: ntt_tile.cuh)
+    if (inverse && !coset) { t.sc_lo = nv.data(); t.sc_hi = nv.data(); }
+    // the passes the library itself would launch for this transform (every stage through LDS here)
+    NttTransform tr = ntt_build_transform(log_n, flags, NTT_PLAIN, NttKnobs{log_e, max_contig, max_strided}, false, n_valid);
+    tr.pass[0].load_mul = (const Fr *)load_mul;
+    tr.pass[tr.n_pass - 1].store_sub = (const Fr *)store_sub;
+    for (u32 step = 0; step < tr.n_pass; step++) {
+        const NttPass &p = tr.pass[step];
         u32 tiles = 1u << (log_n - p.log_r - p.log_c);
-        std::vector<U4> lds((size_t)2 << (p.log_r + p.log_c));
+        std::vector<U4> lds((size_t)2 * ntt_plane_slots(p));
         for (u32 tile = 0; tile < tiles; tile++) {
             for (u32 tid = 0; tid < nthr; tid++) ntt_tile_load(p, t, data, tile, tid, nthr, lds.data());
             for (u32 s = 0; s < p.log_r; s++)
@@ -281,7 +268,7 @@ extern "C" int emu_ntt_fused(void *data_v, uint32_t log_n, uint32_t flags, uint3
             for (u32 tid = 0; tid < nthr; tid++) ntt_tile_store(p, t, data, tile, tid, nthr, lds.data());
         }
     }
-    return (int)pl.n_pass;
+    return (int)tr.n_pass;
 }
 extern "C" int emu_ntt(void *data_v, uint32_t log_n, uint32_t flags, uint32_t log_e, uint32_t max_contig, uint32_t max_strided,
                        uint32_t nthr, uint32_t n_valid) {

@@ -198,8 +198,49 @@ def test_ntt_register_and_lds_stage_paths_agree_with_oracle(ctx, log_n):
         assert ctx.lib.mi_debug_set_ntt_wave_stages(ctx.h, 1, 12) == 0
 
 
-@pytest.mark.parametrize("log_n,plan", [(10, None), (14, (8, 7, 7)), (16, None), (17, (10, 10, 7)), (20, None), (21, (9, 7, 7)), (16, (10, 8, 8)),
-                                         (17, (9, 9, 8)), (19, (10, 3, 8))])
+FUSE_CASES = [(10, None), (14, (8, 7, 7)), (16, None), (17, (10, 10, 7)), (20, None), (21, (9, 7, 7)), (16, (10, 8, 8)),
+              (17, (9, 9, 8)), (19, (10, 3, 8)), (9, None)]   # (new cases go at the end: the position names the case)
+
+
+def _compute_h_launches(log_n, plan, on):
+    """(n_pass, pair, triple, last) of one computeH under mi_debug_set_ntt_plan(*plan) (None: the default 2^9 tiles, contiguous radix <= 2^9,
+    strided radices <= 2^7, which holds below 2^24) and mi_debug_set_ntt_fuse_pair(on), from the documented rules alone: the contiguous
+    pass takes max_contig bits, the rest is spread evenly over the fewest strided passes, first pass first; a tile has
+    2^log_c columns, log_c = min(log_e - log_r, what is left of the row)."""
+    log_e, max_contig, max_strided = plan or (9, 9, 7)
+    if log_n <= max_contig:
+        radices = [log_n]
+    else:
+        rest = log_n - max_contig
+        ns = -(-rest // max_strided)
+        radices = []
+        for i in range(ns):
+            radices.append(rest // (ns - i)); rest -= radices[-1]
+        radices.append(max_contig)
+    n_pass, first, contig = len(radices), radices[0], radices[-1]
+    log_c_first = min(max(log_e - first, 0), log_n - first)      # strided first pass: log_s = log_n - log_r
+    log_c_contig = min(max(log_e - contig, 0), log_n - contig)
+    pair = bool(on & 1) and n_pass >= 2 and contig >= 7
+    triple = bool(on & 2) and n_pass >= 2 and ((first == 7 and log_c_first <= 3) or (first == 8 and 1 <= log_c_first <= 2))
+    last = bool(on & 4) and n_pass >= 2 and contig >= 7 and (1 << (contig + log_c_contig)) <= 1024
+    return n_pass, int(pair), int(triple), int(last)
+
+
+def test_compute_h_fuse_cases_reach_both_sides_of_every_fusion():
+    """the parameters below have each of the three fused launches applicable at least once and inapplicable at least once; the default
+    plan at N = 2^23 has all three: the 13 launches DESIGN.md states"""
+    got = [_compute_h_launches(log_n, plan, 7)[1:] for log_n, plan in FUSE_CASES]
+    for k in range(3):
+        assert {g[k] for g in got} == {0, 1}, k
+    assert _compute_h_launches(19, (10, 3, 8), 7)[1:] == (0, 1, 0)
+    assert _compute_h_launches(10, None, 7)[1:] == (1, 0, 1)
+    assert _compute_h_launches(14, (8, 7, 7), 7)[1:] == (1, 1, 1)
+    assert _compute_h_launches(9, None, 7) == (1, 0, 0, 0)
+    n_pass, pair, triple, last = _compute_h_launches(23, None, 7)
+    assert 6 * n_pass - 2 * pair - 2 * triple - last == 13
+
+
+@pytest.mark.parametrize("log_n,plan", FUSE_CASES)
 def test_compute_h_with_and_without_the_fused_launches(ctx, log_n, plan):
     """computeH with its two fused launches -- the inverse transform's last pass + the coset transform's first pass of a and b
     (bit 0; wherever the plan's contiguous radix is >= 2^7), and the coset transform's last pass of a and of b + the product + the last
@@ -214,9 +255,14 @@ def test_compute_h_with_and_without_the_fused_launches(ctx, log_n, plan):
             assert ctx.lib.mi_debug_set_ntt_plan(ctx.h, *plan) == 0
         for on in (7, 0, 1, 2, 3, 4, 5, 6, 7):   # bit 2 (r4): c's last pass + the last transform's last pass, which subtracts it, as one launch
             assert ctx.lib.mi_debug_set_ntt_fuse_pair(ctx.h, on) == 0
+            n_pass, pair, triple, last = _compute_h_launches(log_n, plan, on)
             assert np.array_equal(ctx.compute_h(log_n, a, b, c), want), (on, log_n)
+            st = ctx.stats()
+            assert st["ntt_elems"] == 6 << log_n and st["ntt_launches"] == 6 * n_pass - 2 * pair - 2 * triple - last, (on, log_n, st)
             if on in (7, 4):   # c = NULL: formed on the device as a o b, against the oracle given that c
                 assert np.array_equal(ctx.compute_h(log_n, a, b, None), cref.compute_h(log_n, a, b, cref.field_op(0, 2, a, b))), (on, log_n, "derived c")
+                st = ctx.stats()
+                assert st["ntt_elems"] == 6 << log_n and st["ntt_launches"] == 6 * n_pass - 2 * pair - 2 * triple - last, (on, log_n, st, "derived c")
     finally:
         assert ctx.lib.mi_debug_set_ntt_fuse_pair(ctx.h, 7) == 0
         if plan:
