@@ -2,6 +2,8 @@
 // partial-sum combine).  See include/mi355x_groth16.h for the contract of each entry point.
 #include "ctx.h"
 #include "curve.cuh"
+#include "abi_glue.h"
+#include <sys/random.h>
 #include <cstring>
 #include <dlfcn.h>
 
@@ -33,6 +35,16 @@ static bool ranges_load() {
 int32_t mi_copy_stream(mi_ctx *ctx, hipStream_t *out) {
     if (!ctx->copy_stream) MI_CHECK_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     *out = ctx->copy_stream;
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------- the operating system's randomness (abi_glue.h)
+int32_t mi_os_random(mi_ctx *ctx, const std::string &msg, uint8_t *buf, size_t n) {
+    for (size_t got = 0; got < n;) {
+        const ssize_t k = getrandom(buf + got, n - got, 0);
+        if (k <= 0) MI_FAIL(ctx, MI_ENODEV, msg);
+        got += (size_t)k;
+    }
     return MI_OK;
 }
 

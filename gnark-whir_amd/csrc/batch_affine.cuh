@@ -7,6 +7,7 @@
 // Used by the fixed-base batch scalar multiplication (fixed_base.hip) and by mi_msm_precompute (the window tables of
 // mi_pk_load: one conversion per point per window).
 #pragma once
+#include "ctx.h"
 #include "curve.cuh"
 
 template <class F, int K>
@@ -30,6 +31,17 @@ __global__ void __launch_bounds__(64) k_xyzz_batch_to_affine(const XYZZ<F> *in, 
         out[b + j] = Affine<F>{p.x * izz, p.y * izzz};
     }
 }
+// AFFINE_K points per inversion and the grid that goes with it: the one width every launch of the conversion uses
+constexpr int AFFINE_K = 16;
+inline unsigned xyzz_to_affine_blocks(size_t n) { return (unsigned)(((n + AFFINE_K - 1) / AFFINE_K + 63) / 64); }
+// the conversion of n points on ctx->stream: what fixed_base.hip, ksum.hip, phase1.hip and phase2.hip launch.  prefix: scratch of n
+// field elements.  No point, no launch
+template <class F>
+int32_t mi_xyzz_to_affine_enqueue(mi_ctx *ctx, const XYZZ<F> *in, Affine<F> *out, F *prefix, size_t n) {
+    if (n) hipLaunchKernelGGL((k_xyzz_batch_to_affine<F, AFFINE_K>), dim3(xyzz_to_affine_blocks(n)), dim3(64), 0, ctx->stream, in, out, prefix, n);
+    MI_CHECK_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
 template <class F>
 __global__ void __launch_bounds__(64) k_xyzz_from_affine(XYZZ<F> *state, Affine<F> *first_window, const Affine<F> *base, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -51,11 +63,10 @@ __global__ void __launch_bounds__(64) k_xyzz_dbl_c(XYZZ<F> *state, size_t n, u32
 // state (n XYZZ) and prefix (n field elements) are scratch
 template <class F>
 static void launch_precompute_batched(hipStream_t st, const void *base, void *pre, uint32_t n, uint32_t c, uint32_t nwin, void *state, void *prefix) {
-    constexpr int K = 16;
-    const unsigned blocks = (n + 63) / 64, cblocks = (unsigned)(((size_t)n + K - 1) / K + 63) / 64;
+    const unsigned blocks = (n + 63) / 64, cblocks = xyzz_to_affine_blocks(n);
     hipLaunchKernelGGL(k_xyzz_from_affine<F>, dim3(blocks), dim3(64), 0, st, (XYZZ<F> *)state, (Affine<F> *)pre, (const Affine<F> *)base, (size_t)n);
     for (uint32_t w = 1; w < nwin; w++) {
         hipLaunchKernelGGL(k_xyzz_dbl_c<F>, dim3(blocks), dim3(64), 0, st, (XYZZ<F> *)state, (size_t)n, c);
-        hipLaunchKernelGGL((k_xyzz_batch_to_affine<F, K>), dim3(cblocks), dim3(64), 0, st, (const XYZZ<F> *)state, (Affine<F> *)pre + (size_t)w * n, (F *)prefix, (size_t)n);
+        hipLaunchKernelGGL((k_xyzz_batch_to_affine<F, AFFINE_K>), dim3(cblocks), dim3(64), 0, st, (const XYZZ<F> *)state, (Affine<F> *)pre + (size_t)w * n, (F *)prefix, (size_t)n);
     }
 }

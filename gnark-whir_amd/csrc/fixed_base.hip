@@ -79,11 +79,7 @@ static int32_t fb_run_dev(mi_ctx *ctx, const AffT *base, const mi_fr *scalars_de
     } else {
         hipLaunchKernelGGL(k_fb_mul<F>, dim3(blocks), dim3(64), 0, ctx->stream, sums, table, (const Fr *)scalars_dev, n);
     }
-    constexpr int K = 16;
-    hipLaunchKernelGGL((k_xyzz_batch_to_affine<F, K>), dim3((unsigned)(((n + K - 1) / K + 63) / 64)), dim3(64), 0, ctx->stream, (const XYZZ<F> *)sums,
-                       (Affine<F> *)out_dev, (F *)ctx->ws[WS_FB_INV].p, n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    return MI_OK;
+    return mi_xyzz_to_affine_enqueue<F>(ctx, (const XYZZ<F> *)sums, (Affine<F> *)out_dev, (F *)ctx->ws[WS_FB_INV].p, n);
 }
 template <class F, class AffT>
 static int32_t fb_run_host(mi_ctx *ctx, const AffT *base, const mi_fr *scalars, size_t n, AffT *out) {

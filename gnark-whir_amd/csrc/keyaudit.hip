@@ -8,7 +8,7 @@
 //   k_keyaudit_gather      out[s] = r[wire[s]]: the coefficients in the order of pk.A / B / K, vk.K, a basis
 //   k_keyaudit_bitrev      out[i] = in[bitrev(i)]: the Z coefficients in stored order
 //   k_keyaudit_unreverse   a DIF transform's output to natural order, and (acc != null) its sum into the unmasked vector
-//   k_keyaudit_check_g1 / _g2   the points of mi_key_claim_from_arrays
+// The points of mi_key_claim_from_arrays go through point_check.cuh's k_points_check_g1 / _g2 under POINT_RULE_AUDIT.
 // Coefficients, MSMs and the judgement of the pairing relations are phase2_check.hip's (phase2_internal.h); a stream is decoded by the
 // loaders' own code (keyfile_internal.h).  The wire classes, the slot lists and the shape refusals are host code in keyaudit_ops.cuh.
 // A = sum of the three class vectors, so nine masked products and nine transforms give every relation.  A host SRS goes up one row at a
@@ -19,6 +19,8 @@
 #include "r1cs_internal.h"
 #include "keyaudit_ops.cuh"
 #include "keyfile_ops.cuh"
+#include "point_check.cuh"
+#include "stream_clock.h"
 #include <cstring>
 #include <string>
 #include <vector>
@@ -42,7 +44,6 @@ struct mi_key_claim {
 
 namespace {
 
-typedef unsigned long long ull;
 enum { ARR_A, ARR_B, ARR_K, ARR_Z, ARR_G2B };
 
 __global__ void __launch_bounds__(64) k_keyaudit_mask(const Fr *r, const uint8_t *cls, uint8_t want, u64 n, Fr *out) {
@@ -64,45 +65,13 @@ __global__ void __launch_bounds__(64) k_keyaudit_unreverse(const Fr *in, u32 log
     out[i] = v;
     if (acc) acc[i] = acc[i] + v;
 }
-__global__ void __launch_bounds__(64) k_keyaudit_check_g1(const G1Aff *pts, u64 n, bool allow_inf, ull *first_bad) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const G1Aff p = pts[i];
-    if (!keyaudit_g1_ok(p, allow_inf)) atomicMin(first_bad, (ull)i);
-}
-__global__ void __launch_bounds__(64) k_keyaudit_check_g2(const G2Aff *pts, u64 n, bool allow_inf, ull *first_bad) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const G2Aff q = pts[i];
-    if (!keyaudit_g2_ok(q, allow_inf)) atomicMin(first_bad, (ull)i);
-}
 
-struct Clock {
-    double t = now_ms();
-    void lap(float &into) { const double n = now_ms(); into += (float)(n - t); t = n; }
-};
-int32_t sync_lap(mi_ctx *ctx, Clock &ck, float &into) {
-    MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ck.lap(into);
-    return MI_OK;
-}
-G1Aff g1_of(const mi_g1_affine &p) { G1Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
-G2Aff g2_of(const mi_g2_affine &p) { G2Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
 bool same(const G1Aff &a, const G1Aff &b) { return std::memcmp(&a, &b, sizeof(a)) == 0; }
 bool same(const G2Aff &a, const G2Aff &b) { return std::memcmp(&a, &b, sizeof(a)) == 0; }
 G1Aff g1_sum(const G1Aff &a, const G1Aff &b, bool negate_b = false) {
     G1X acc = G1X::from_affine(a);
     xyzz_madd(acc, b, negate_b);
     return xyzz_to_affine(acc);
-}
-// an MSM over no pair is the point at infinity, whatever the pointers
-int32_t msm1(mi_ctx *ctx, const void *bases, const Fr *scalars, u64 n, G1Aff *out) {
-    *out = G1Aff{Fp::zero(), Fp::zero()};
-    return n ? mi_ceremony_msm_g1(ctx, (const G1Aff *)bases, scalars, n, out) : MI_OK;
-}
-int32_t msm2(mi_ctx *ctx, const void *bases, const Fr *scalars, u64 n, G2Aff *out) {
-    *out = G2Aff{Fp2::zero(), Fp2::zero()};
-    return n ? mi_ceremony_msm_g2(ctx, (const G2Aff *)bases, scalars, n, out) : MI_OK;
 }
 
 void free_claim(mi_key_claim *c) {
@@ -138,29 +107,22 @@ int32_t view_state(mi_ctx *ctx, const mi_phase2 *S, mi_key_claim &c) {
 // ---------------------------------------------------------------------------------------------------- the points of plain arrays
 struct ClaimArray { std::string name; bool g2, allow_inf; const void *pts; u64 n; };
 int32_t check_arrays(mi_ctx *ctx, const std::vector<ClaimArray> &arrs) {
-    Arena ar;
-    ull *bad = nullptr;
-    std::vector<ull> bad_h(2 * arrs.size(), ~0ull);   // word 2 i: array i on its curve; 2 i + 1: a G2 array in the r-torsion
-    MI_TRY(ar.alloc(ctx, &bad, bad_h.size()));
+    BadSlots bad;   // word 2 i: array i on its curve; 2 i + 1: a G2 array in the r-torsion
     auto body = [&]() -> int32_t {
-        MI_CHECK_HIP(ctx, hipMemsetAsync(bad, 0xff, bad_h.size() * sizeof(ull), ctx->stream));
+        MI_TRY(bad.init(ctx, 2 * arrs.size()));
         for (size_t i = 0; i < arrs.size(); i++) {
             const ClaimArray &a = arrs[i];
-            if (a.g2) {
-                MI_TRY(mi_launch64(ctx, k_keyaudit_check_g2, (size_t)a.n, (const G2Aff *)a.pts, a.n, a.allow_inf, bad + 2 * i));
-                MI_TRY(mi_keyfile_subgroup_enqueue(ctx, a.pts, (size_t)a.n, false, bad + 2 * i + 1));   // a word that is no point fails the curve check, which is reported first
-            } else MI_TRY(mi_launch64(ctx, k_keyaudit_check_g1, (size_t)a.n, (const G1Aff *)a.pts, a.n, a.allow_inf, bad + 2 * i));
+            MI_TRY(mi_points_check_enqueue(ctx, a.g2, a.pts, a.n, point_rule_audit(a.allow_inf), bad.dev + 2 * i));
+            if (a.g2) MI_TRY(mi_keyfile_subgroup_enqueue(ctx, a.pts, (size_t)a.n, false, bad.dev + 2 * i + 1));   // a word that is no point fails the curve check, which is reported first
         }
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(bad_h.data(), bad, bad_h.size() * sizeof(ull), hipMemcpyDeviceToHost, ctx->stream));
-        MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return MI_OK;
+        return bad.fetch(ctx);
     };
     const int32_t rc = body();
     if (rc != MI_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     for (size_t i = 0; i < arrs.size(); i++) {
-        if (bad_h[2 * i] != ~0ull)
-            MI_FAIL(ctx, MI_EINVAL, "key claim: " + arrs[i].name + "[" + std::to_string(bad_h[2 * i]) + "] is not a point of its curve" + (arrs[i].allow_inf ? "" : " or is at infinity"));
-        if (bad_h[2 * i + 1] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "key claim: " + arrs[i].name + "[" + std::to_string(bad_h[2 * i + 1]) + "] is not in the r-torsion");
+        if (bad.bad(2 * i))
+            MI_FAIL(ctx, MI_EINVAL, "key claim: " + arrs[i].name + "[" + std::to_string(bad.host[2 * i]) + "] is not a point of its curve" + (arrs[i].allow_inf ? "" : " or is at infinity"));
+        if (bad.bad(2 * i + 1)) MI_FAIL(ctx, MI_EINVAL, "key claim: " + arrs[i].name + "[" + std::to_string(bad.host[2 * i + 1]) + "] is not in the r-torsion");
     }
     return MI_OK;
 }
@@ -192,7 +154,7 @@ int32_t audit_run(mi_ctx *ctx, const AuditIn &in, const mi_r1cs *R, Arena &ar, m
     const KeyAuditWires &w = *in.w;
     const u64 N = sh.N, nw = sh.nb_wires, nc = sh.nc;
     const u32 n_ped = sh.n_commitments;
-    Clock ck;
+    HostClock ck;
     // ---- the wire classes and the slot lists go up
     uint8_t *cls = nullptr;
     MI_TRY(ar.alloc(ctx, &cls, (size_t)nw));
@@ -274,25 +236,25 @@ int32_t audit_run(mi_ctx *ctx, const AuditIn &in, const mi_r1cs *R, Arena &ar, m
     G2Aff srs_b2;
     G1Aff *row = nullptr;
     MI_TRY(g1_row("tau_g1", srs->tau_g1, 2 * N, &row));
-    MI_TRY(msm1(ctx, row, p_a, N, &srs_a));
-    MI_TRY(msm1(ctx, row, p_b, N, &srs_b1));
-    for (int x = 0; x < KEYAUDIT_CLASSES; x++) MI_TRY(msm1(ctx, row, nat[x][2], N, &t_part[2][x]));
-    MI_TRY(msm1(ctx, row, r + nw, N, &z_lo));
-    MI_TRY(msm1(ctx, row + N, r + nw, N, &z_hi));
+    MI_TRY(mi_ceremony_msm_g1(ctx, row, p_a, N, &srs_a));
+    MI_TRY(mi_ceremony_msm_g1(ctx, row, p_b, N, &srs_b1));
+    for (int x = 0; x < KEYAUDIT_CLASSES; x++) MI_TRY(mi_ceremony_msm_g1(ctx, row, nat[x][2], N, &t_part[2][x]));
+    MI_TRY(mi_ceremony_msm_g1(ctx, row, r + nw, N, &z_lo));
+    MI_TRY(mi_ceremony_msm_g1(ctx, row + N, r + nw, N, &z_hi));
     ck.lap(stats.srs_msm_g1_ms);
     if (!in.on_device) ar.release(row);
     MI_TRY(g1_row("alpha_tau_g1", srs->alpha_tau_g1, N, &row));
     MI_TRY(first_of(row, srs->alpha_tau_g1, &alpha0));
-    for (int x = 0; x < KEYAUDIT_CLASSES; x++) MI_TRY(msm1(ctx, row, nat[x][1], N, &t_part[1][x]));
+    for (int x = 0; x < KEYAUDIT_CLASSES; x++) MI_TRY(mi_ceremony_msm_g1(ctx, row, nat[x][1], N, &t_part[1][x]));
     ck.lap(stats.srs_msm_g1_ms);
     if (!in.on_device) ar.release(row);
     MI_TRY(g1_row("beta_tau_g1", srs->beta_tau_g1, N, &row));
     MI_TRY(first_of(row, srs->beta_tau_g1, &beta0));
-    for (int x = 0; x < KEYAUDIT_CLASSES; x++) MI_TRY(msm1(ctx, row, nat[x][0], N, &t_part[0][x]));
+    for (int x = 0; x < KEYAUDIT_CLASSES; x++) MI_TRY(mi_ceremony_msm_g1(ctx, row, nat[x][0], N, &t_part[0][x]));
     ck.lap(stats.srs_msm_g1_ms);
     if (!in.on_device) ar.release(row);
     if (in.on_device) {
-        MI_TRY(msm2(ctx, srs->tau_g2, p_b, N, &srs_b2));
+        MI_TRY(mi_ceremony_msm_g2(ctx, srs->tau_g2, p_b, N, &srs_b2));
         ck.lap(stats.srs_msm_g2_ms);
     } else {
         G2Aff *row2 = nullptr, *b2 = nullptr;
@@ -304,7 +266,7 @@ int32_t audit_run(mi_ctx *ctx, const AuditIn &in, const mi_r1cs *R, Arena &ar, m
         const Phase2Row pr[2] = {{"tau_g2", true, row2, N}, {"beta_g2", true, b2, 1}};
         MI_TRY(mi_phase2_check_points(ctx, ar, pr, 2, in.flags));
         ck.lap(stats.point_check_ms);
-        MI_TRY(msm2(ctx, row2, p_b, N, &srs_b2));
+        MI_TRY(mi_ceremony_msm_g2(ctx, row2, p_b, N, &srs_b2));
         ck.lap(stats.srs_msm_g2_ms);
         ar.release(row2); ar.release(b2);
     }
@@ -314,18 +276,18 @@ int32_t audit_run(mi_ctx *ctx, const AuditIn &in, const mi_r1cs *R, Arena &ar, m
     G1Aff key_a, key_b1, key_k, key_v, key_z, key_basis = G1Aff{Fp::zero(), Fp::zero()};
     G2Aff key_b2;
     std::vector<G1Aff> sum_basis(n_ped), sum_bes(n_ped);
-    MI_TRY(msm1(ctx, c.arr[ARR_A], s_a, c.n[ARR_A], &key_a));
-    MI_TRY(msm1(ctx, c.arr[ARR_B], s_b, c.n[ARR_B], &key_b1));
-    MI_TRY(msm1(ctx, c.arr[ARR_K], s_k, c.n[ARR_K], &key_k));
-    MI_TRY(msm1(ctx, c.vk_k, s_v, c.n_vk, &key_v));
-    MI_TRY(msm1(ctx, c.arr[ARR_Z], s_z, N, &key_z));
+    MI_TRY(mi_ceremony_msm_g1(ctx, c.arr[ARR_A], s_a, c.n[ARR_A], &key_a));
+    MI_TRY(mi_ceremony_msm_g1(ctx, c.arr[ARR_B], s_b, c.n[ARR_B], &key_b1));
+    MI_TRY(mi_ceremony_msm_g1(ctx, c.arr[ARR_K], s_k, c.n[ARR_K], &key_k));
+    MI_TRY(mi_ceremony_msm_g1(ctx, c.vk_k, s_v, c.n_vk, &key_v));
+    MI_TRY(mi_ceremony_msm_g1(ctx, c.arr[ARR_Z], s_z, N, &key_z));
     for (u32 k = 0; k < n_ped; k++) {
-        MI_TRY(msm1(ctx, c.ped[k].basis, s_c[k], c.ped[k].n, &sum_basis[k]));
-        MI_TRY(msm1(ctx, c.ped[k].bes, s_c[k], c.ped[k].n, &sum_bes[k]));
+        MI_TRY(mi_ceremony_msm_g1(ctx, c.ped[k].basis, s_c[k], c.ped[k].n, &sum_basis[k]));
+        MI_TRY(mi_ceremony_msm_g1(ctx, c.ped[k].bes, s_c[k], c.ped[k].n, &sum_bes[k]));
         key_basis = g1_sum(key_basis, sum_basis[k]);
     }
     ck.lap(stats.key_msm_g1_ms);
-    MI_TRY(msm2(ctx, c.arr[ARR_G2B], s_b, c.n[ARR_G2B], &key_b2));
+    MI_TRY(mi_ceremony_msm_g2(ctx, c.arr[ARR_G2B], s_b, c.n[ARR_G2B], &key_b2));
     ck.lap(stats.key_msm_g2_ms);
     // ---- the relations
     G1Aff T[KEYAUDIT_CLASSES];

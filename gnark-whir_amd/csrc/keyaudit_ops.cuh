@@ -4,25 +4,27 @@
 // Per lane:
 //   keyaudit_masked        r^X[j]: the coefficient of a wire of class X, 0 for the others
 //   keyaudit_bitrev        the index permutation of pk.G1.Z and of a DIF transform's output
-//   keyaudit_g1_ok / _g2_ok   a claimed point: reduced words, on its curve; (0, 0) passes where the array may hold it
+//   keyaudit_g1_ok / _g2_ok   a claimed point: reduced words, on its curve; (0, 0) passes where the array may hold it -- the audit's
+//                          name for point_check.cuh's point_ok under POINT_RULE_AUDIT, which is what the kernels run
 // Host only:
 //   keyaudit_wire_lists    the wire classes and, per compacted array of the key, the wires of its slots in order
 //   keyaudit_shape_refusal a claim whose counts are not the circuit's: the text that names the count
 #pragma once
 #include "pairing_ops.cuh"
+#include "point_check.cuh"
 #include <string>
 #include <vector>
 
 enum { KEYAUDIT_P = 0, KEYAUDIT_V = 1, KEYAUDIT_C = 2, KEYAUDIT_CLASSES = 3 };   // private / public + commitment wires / committed
 
 MI_HD Fr keyaudit_masked(const Fr &r, uint8_t cls, uint8_t want) { return cls == want ? r : Fr::zero(); }
+MI_HD bool keyaudit_g1_ok(const G1Aff &p, bool allow_inf) { return point_ok(p, point_rule_audit(allow_inf)); }
+MI_HD bool keyaudit_g2_ok(const G2Aff &q, bool allow_inf) { return point_ok(q, point_rule_audit(allow_inf)); }
 MI_HD u64 keyaudit_bitrev(u64 i, u32 log_n) {
     u64 r = 0;
     for (u32 b = 0; b < log_n; b++) { r = (r << 1) | (i & 1); i >>= 1; }
     return r;
 }
-MI_HD bool keyaudit_g1_ok(const G1Aff &p, bool allow_inf) { return g1_on_curve(p) && (allow_inf || !p.is_inf()); }
-MI_HD bool keyaudit_g2_ok(const G2Aff &q, bool allow_inf) { return g2_reduced(q) && g2_on_twist(q) && (allow_inf || !q.is_inf()); }
 
 // ---------------------------------------------------------------------------------------------------- host only
 // what the audit reads of a circuit once mi_r1cs_validate has passed it: every list holds private wires, no wire twice

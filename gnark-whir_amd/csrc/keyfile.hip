@@ -17,7 +17,7 @@
 #include "prove_internal.h"
 #include "keyfile_ops.cuh"
 #include "keyfile_internal.h"
-#include "key_handover.h"
+#include "key_handover.h"   // dev_arena.h: BadSlots
 #include <cstring>
 #include <string>
 #include <vector>
@@ -109,24 +109,6 @@ int32_t encode_g2(mi_ctx *ctx, uint8_t *dst, const void *src, size_t n, bool com
     else KF_LAUNCH(ctx, k_keyfile_encode_g2_raw, n, dst, (const G2Aff *)src, n);
     return MI_OK;
 }
-
-// device words that collect the lowest refused index of a launch each; all UINT64_MAX to begin with
-struct BadSlots {
-    ull *dev = nullptr;
-    std::vector<ull> host;
-    int32_t init(mi_ctx *ctx, size_t n) {
-        host.assign(n, ~0ull);
-        MI_CHECK_HIP(ctx, hipMalloc((void **)&dev, n * sizeof(ull)));
-        MI_CHECK_HIP(ctx, hipMemsetAsync(dev, 0xff, n * sizeof(ull), ctx->stream));
-        return MI_OK;
-    }
-    int32_t fetch(mi_ctx *ctx) {   // returns with the stream idle
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(host.data(), dev, host.size() * sizeof(ull), hipMemcpyDeviceToHost, ctx->stream));
-        MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return MI_OK;
-    }
-    ~BadSlots() { if (dev) (void)hipFree(dev); }
-};
 
 // n strings of one group -> points, and the lowest refused index
 int32_t decompress(mi_ctx *ctx, bool g2, const uint8_t *bytes_dev, size_t n, uint32_t flags, void *out_dev, uint64_t *first_bad) {

@@ -5,7 +5,7 @@
 // The table (mi_vk::ksum), built once per key:
 //   k_ksum_rows        one lane per base: 2^(c w) K_j for every window, by doublings down the lane -> XYZZ rows
 //   k_ksum_multiples   one lane per (j, w) of a chunk: d row for 1 <= d < 2^c by repeated addition -> XYZZ entries
-//   k_xyzz_batch_to_affine   the chunk's entries to affine, one inversion per 16 (batch_affine.cuh)
+//   k_xyzz_batch_to_affine   the chunk's entries to affine, one inversion per 16 (batch_affine.cuh's mi_xyzz_to_affine_enqueue)
 // in chunks of MI_KSUM_BUILD_CHUNK entries, so the scratch of a build is bounded whatever the table's size.  Rows, entries and running
 // products are allocations of the build alone, freed when it ends; when they or the table are not to be had the key stays without a
 // table (MI_KSUM_NO_MEMORY), which is no error.
@@ -70,8 +70,6 @@ unsigned capped_blocks(uint64_t lanes) {
     const uint64_t b = (lanes + 63) / 64;
     return (unsigned)(b < MI_KSUM_GRID_CAP ? b : MI_KSUM_GRID_CAP);
 }
-constexpr int AFFINE_K = 16;   // results per inversion
-unsigned affine_blocks(size_t n) { return (unsigned)(((n + AFFINE_K - 1) / AFFINE_K + 63) / 64); }
 
 struct KsumScratch { size_t part, sums, prefix, total; };
 KsumScratch scratch_of(u32 ns, u32 c, size_t n) {
@@ -119,9 +117,7 @@ int32_t build_table(mi_ctx *ctx, const mi_vk *vk, uint64_t budget) {
         for (size_t r0 = 0; r0 < n_rows; r0 += chunk_rows) {
             const size_t m = n_rows - r0 < chunk_rows ? n_rows - r0 : chunk_rows, cnt = m * entries;
             MI_TRY(mi_launch64(ctx, k_ksum_multiples, m, (const G1X *)rows + r0, m, entries, (G1X *)xyzz));
-            hipLaunchKernelGGL((k_xyzz_batch_to_affine<Fp, AFFINE_K>), dim3(affine_blocks(cnt)), dim3(64), 0, ctx->stream, (const G1X *)xyzz,
-                               (G1Aff *)table + r0 * entries, (Fp *)prefix, cnt);
-            MI_CHECK_HIP(ctx, hipGetLastError());
+            MI_TRY(mi_xyzz_to_affine_enqueue<Fp>(ctx, (const G1X *)xyzz, (G1Aff *)table + r0 * entries, (Fp *)prefix, cnt));
         }
         MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         k.table = (G1Aff *)table; table = nullptr;
@@ -168,9 +164,7 @@ int32_t mi_ksum_enqueue(mi_ctx *ctx, const mi_vk *vk, const Fr *scal_dev, const 
     hipLaunchKernelGGL(k_ksum_reduce, dim3((unsigned)(items < MI_KSUM_GRID_CAP ? items : MI_KSUM_GRID_CAP)), dim3(64), 0, ctx->stream, (const G1X *)part, skip_dev,
                        slices, lanes_per_row, n, sums);
     MI_CHECK_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL((k_xyzz_batch_to_affine<Fp, AFFINE_K>), dim3(affine_blocks(n)), dim3(64), 0, ctx->stream, (const G1X *)sums, out_dev,
-                       (Fp *)(scratch + at.prefix), n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
+    MI_TRY(mi_xyzz_to_affine_enqueue<Fp>(ctx, (const G1X *)sums, out_dev, (Fp *)(scratch + at.prefix), n));
     if (launches) *launches += 3;
     return MI_OK;
 }

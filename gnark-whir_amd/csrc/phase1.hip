@@ -5,7 +5,7 @@
 //   k_phase1_table_*    one lane per point of a chunk: the table (m + 1) P, m < 2^(W-1), into the call's workspace, lane-interleaved
 //   k_phase1_ladder_*   one lane per point: the scalar made in the lane, recoded, the fixed-window ladder over that table -> XYZZ
 //   k_phase1_bits_*     the yardstick (knob "scale_powers_window" = 0): point_ntt.cuh's xyzz_scale, bit by bit, on the same scalars
-//   k_xyzz_batch_to_affine   batch_affine.cuh: the chunk's XYZZ results to affine
+//   k_xyzz_batch_to_affine   batch_affine.cuh's mi_xyzz_to_affine_enqueue: the chunk's XYZZ results to affine
 // The driver (scale_row) walks a row chunk by chunk, so the table is sized for a chunk of lanes and not for the row.
 // The records are phase1_ops.cuh's, verified on the host; the same-ratio tests are phase2_check.hip's over the rows where they are.
 #include "verify_internal.h"
@@ -15,7 +15,7 @@
 #include "point_ntt.cuh"
 #include "scale_powers.cuh"
 #include "phase1_ops.cuh"
-#include <sys/random.h>
+#include "stream_clock.h"
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -33,7 +33,6 @@ struct mi_phase1 {
 
 namespace {
 
-constexpr int AFFINE_K = 16;               // points per inversion of the batched conversion (phase2.hip's)
 constexpr u32 DEFAULT_CHUNK = 1u << 18;    // lanes per chunk: four waves on every SIMD of 256 CUs; the width and the chunk measured fastest (profiles/phase1.txt)
 constexpr u64 MAX_DEBUG_POINTS = (u64)1 << 28;
 
@@ -84,26 +83,6 @@ template <> struct Launch<Fp2> {
 };
 
 // ---------------------------------------------------------------------------------------------------- the chunk driver
-// the time of the stream's work since the last lap (each lap waits for the stream)
-struct Laps {
-    hipEvent_t ev[2]{};
-    ~Laps() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
-    int32_t init(mi_ctx *ctx) {
-        for (auto &e : ev) MI_CHECK_HIP(ctx, hipEventCreate(&e));
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
-        return MI_OK;
-    }
-    int32_t lap(mi_ctx *ctx, float &into) {
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
-        MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) { (void)hipGetLastError(); ms = 0; }
-        into += ms;
-        std::swap(ev[0], ev[1]);
-        return MI_OK;
-    }
-};
-
 // what the knobs say for this call
 struct Plan { u32 window, chunk; };
 Plan plan_of(const mi_ctx *ctx) { return Plan{ctx->scale_powers_window, ctx->scale_powers_chunk ? ctx->scale_powers_chunk : DEFAULT_CHUNK}; }
@@ -125,7 +104,7 @@ template <class F> struct Workspace {
 
 // out[i] = [c t^(k0 + i)] in[i], i < n, device arrays of affine points (out may be in).  mul_ms / aff_ms take the device times.
 template <class F>
-int32_t scale_row(mi_ctx *ctx, Laps &laps, const Plan &pl, const Workspace<F> &ws, const Affine<F> *in, Affine<F> *out, u64 n, const Fr &t, const Fr &c, u64 k0,
+int32_t scale_row(mi_ctx *ctx, StreamLaps &laps, const Plan &pl, const Workspace<F> &ws, const Affine<F> *in, Affine<F> *out, u64 n, const Fr &t, const Fr &c, u64 k0,
                   float &mul_ms, float &aff_ms) {
     hipStream_t st = ctx->stream;
     float skip = 0;
@@ -144,15 +123,11 @@ int32_t scale_row(mi_ctx *ctx, Laps &laps, const Plan &pl, const Workspace<F> &w
         }
         MI_CHECK_HIP(ctx, hipGetLastError());
         MI_TRY(laps.lap(ctx, mul_ms));
-        hipLaunchKernelGGL((k_xyzz_batch_to_affine<F, AFFINE_K>), dim3((unsigned)(((m + AFFINE_K - 1) / AFFINE_K + 63) / 64)), dim3(64), 0, st, (const XYZZ<F> *)ws.x, out + off, ws.prefix, (size_t)m);
-        MI_CHECK_HIP(ctx, hipGetLastError());
+        MI_TRY(mi_xyzz_to_affine_enqueue<F>(ctx, (const XYZZ<F> *)ws.x, out + off, ws.prefix, (size_t)m));
         MI_TRY(laps.lap(ctx, aff_ms));
     }
     return MI_OK;
 }
-
-Fr fr_in(const mi_fr *x) { Fr r; std::memcpy(&r, x, 32); return r; }
-G1Aff g1_of(const mi_g1_affine &p) { G1Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
 
 void free_rows(mi_phase1 *S) {
     for (void *p : {(void *)S->tau_g1, (void *)S->alpha_tau_g1, (void *)S->beta_tau_g1, (void *)S->tau_g2}) if (p) (void)hipFree(p);
@@ -182,7 +157,7 @@ int32_t contribute_run(mi_ctx *ctx, const mi_phase1 *S, const Fr &t, const Fr &a
     const Plan pl = plan_of(ctx);
     const u64 N = S->N;
     stats.window = pl.window; stats.chunk = pl.chunk;
-    Laps laps;
+    StreamLaps laps;
     MI_TRY(laps.init(ctx));
     MI_TRY(ar.alloc(ctx, &nr.t1, (size_t)(2 * N)));
     MI_TRY(ar.alloc(ctx, &nr.al, (size_t)N));
@@ -220,7 +195,7 @@ int32_t read_factors(mi_ctx *ctx, const mi_phase1 *S, const mi_fr *tau, const mi
     const struct { const char *name; const mi_fr *p; } in[3] = {{"tau", tau}, {"alpha", alpha}, {"beta", beta}};
     for (int x = 0; x < 3; x++) {
         if (!in[x].p) MI_FAIL(ctx, MI_EINVAL, std::string("phase1: ") + in[x].name + " is null");
-        d[x] = fr_in(in[x].p);
+        d[x] = fr_of(*in[x].p);
         if (d[x].is_zero()) MI_FAIL(ctx, MI_EINVAL, std::string("phase1: ") + in[x].name + " is 0");
         if (!fe_is_reduced(d[x])) MI_FAIL(ctx, MI_EINVAL, std::string("phase1: ") + in[x].name + " is not below r");
     }
@@ -370,19 +345,10 @@ int32_t mi_phase1_contribute_proved(mi_ctx *ctx, mi_phase1 *S, const mi_fr *tau,
     if (!out) MI_FAIL(ctx, MI_EINVAL, "phase1: the record's out is null");
     for (int x = 0; x < 3; x++) {
         if (nonce) {
-            k[x] = fr_in(&nonce[x]);
+            k[x] = fr_of(nonce[x]);
             if (k[x].is_zero()) MI_FAIL(ctx, MI_EINVAL, "phase1: nonce[" + std::to_string(x) + "] is 0");
             if (!fe_is_reduced(k[x])) MI_FAIL(ctx, MI_EINVAL, "phase1: nonce[" + std::to_string(x) + "] is not below r");
-        } else {   // 48 bytes reduced mod r: uniform to within 2^-128
-            uint8_t b[MI_H2F_BYTES];
-            for (size_t got = 0; got < sizeof(b);) {
-                const ssize_t n = getrandom(b + got, sizeof(b) - got, 0);
-                if (n <= 0) MI_FAIL(ctx, MI_ENODEV, "phase1: the operating system gave no randomness for the nonces (getrandom)");
-                got += (size_t)n;
-            }
-            k[x] = fr_from_be48(b);
-            if (k[x].is_zero()) MI_FAIL(ctx, MI_ENODEV, "phase1: a drawn nonce is 0");
-        }
+        } else MI_TRY(mi_draw_nonce(ctx, "phase1: the operating system gave no randomness for the nonces (getrandom)", "phase1: a drawn nonce is 0", k[x]));
     }
     G1Aff before[3];
     MI_TRY(contribute(ctx, S, d, before));
@@ -488,7 +454,7 @@ int32_t mi_debug_scale_powers_dev(mi_ctx *ctx, int32_t g2, const void *pts_host,
     if (!ctx) return MI_EINVAL;
     if (!t || !c || ((!pts_host || !out_host) && n)) MI_FAIL(ctx, MI_EINVAL, "scale powers: a null argument");
     if (n > MAX_DEBUG_POINTS || k0 > ~(uint64_t)0 - n) MI_FAIL(ctx, MI_EINVAL, "scale powers: n or k0 out of range");
-    const Fr tt = fr_in(t), cc = fr_in(c);
+    const Fr tt = fr_of(*t), cc = fr_of(*c);
     if (!fe_is_reduced(tt) || !fe_is_reduced(cc)) MI_FAIL(ctx, MI_EINVAL, "scale powers: t or c is not below r");
     ctx->phase1_stats = mi_phase1_stats{};
     if (!n) return MI_OK;
@@ -498,7 +464,7 @@ int32_t mi_debug_scale_powers_dev(mi_ctx *ctx, int32_t g2, const void *pts_host,
     const double t0 = now_ms();
     auto body = [&]() -> int32_t {
         Arena ar;
-        Laps laps;
+        StreamLaps laps;
         MI_TRY(laps.init(ctx));
         void *pts = nullptr;
         const size_t bytes = n * (g2 ? sizeof(G2Aff) : sizeof(G1Aff));

@@ -1,8 +1,8 @@
 // Phase-2 key generation from a powers-of-tau SRS (include/mi355x_groth16_phase2.h): Setup's arithmetic "in the exponent".
 // Replaces gnark's mpcsetup.InitPhase2 / Contribute / ExtractKeys for the key the reference makes with groth16.Setup (mt.go:448).
 //
-//   1  the SRS rows go up and are checked point by point: on the curve and not at infinity (the equation of keyfile_ops.cuh's raw
-//      decoders), the G2 points in the r-torsion (keyfile.hip's endomorphism test)
+//   1  the SRS rows go up and are checked point by point: on the curve and not at infinity (point_check.cuh's POINT_RULE_SRS_ROW through
+//      k_points_check_g1 / _g2), the G2 points in the r-torsion (keyfile.hip's endomorphism test)
 //   2  Z_i = [tau^(i + N)]1 - [tau^i]1, stored bit-reversed
 //   3  the Lagrange bases [L_i]1, [alpha L_i]1, [beta L_i]1, [L_i]2: the inverse NTT over points of point_ntt.cuh, a launch per stage, a
 //      lane per butterfly, then batch_affine.cuh's conversion in place over the SRS row (bit-reversed order)
@@ -21,30 +21,15 @@
 #include "batch_affine.cuh"
 #include "point_ntt.cuh"
 #include "sparse_points.cuh"
+#include "point_check.cuh"
+#include "stream_clock.h"
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
 namespace {
 
-typedef unsigned long long ull;
-constexpr int AFFINE_K = 16;   // points per inversion of the batched conversion (fixed_base.hip's)
-
-MI_HD bool on_curve(const G1Aff &p) { return fe_sqr(p.y) == fe_sqr(p.x) * p.x + curve_b((const Fp *)0); }
-MI_HD bool on_curve(const G2Aff &p) { return fe_sqr(p.y) == fe_sqr(p.x) * p.x + fp12c_twist_b(); }
-
 // ---------------------------------------------------------------------------------------------------- kernels
-// an SRS point is on its curve and not at infinity; *first_bad takes the lowest index that is not
-template <class F>
-MI_D void lane_check(const Affine<F> *pts, u64 n, ull *first_bad) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Affine<F> p = pts[i];
-    if (p.is_inf() || !on_curve(p)) atomicMin(first_bad, (ull)i);
-}
-__global__ void __launch_bounds__(256) k_phase2_check_g1(const G1Aff *pts, u64 n, ull *first_bad) { lane_check(pts, n, first_bad); }
-__global__ void __launch_bounds__(256) k_phase2_check_g2(const G2Aff *pts, u64 n, ull *first_bad) { lane_check(pts, n, first_bad); }
-
 // Z_i = tau_g1[i + N] - tau_g1[i] into slot bitrev(i)
 __global__ void __launch_bounds__(256) k_phase2_z(G1X *Z, const G1Aff *tau, u32 log_n) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -117,26 +102,6 @@ __global__ void __launch_bounds__(256) k_phase2_gather_g1(G1Aff *dst, const G1Af
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-// the time of the stream's work since the last lap (each lap waits for the stream: the phases are long and run one after the other)
-struct Laps {
-    hipEvent_t ev[2]{};
-    ~Laps() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
-    int32_t init(mi_ctx *ctx) {
-        for (auto &e : ev) MI_CHECK_HIP(ctx, hipEventCreate(&e));
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
-        return MI_OK;
-    }
-    int32_t lap(mi_ctx *ctx, float &into) {
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
-        MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) { (void)hipGetLastError(); ms = 0; }
-        into += ms;
-        std::swap(ev[0], ev[1]);
-        return MI_OK;
-    }
-};
-
 template <class F> struct Curve;
 template <> struct Curve<Fp> {
     static void from_affine(hipStream_t st, G1X *o, const G1Aff *i, u64 n) { hipLaunchKernelGGL(k_phase2_from_affine_g1, dim3(mi_blocks_of(n, 256)), dim3(256), 0, st, o, i, n); }
@@ -156,13 +121,6 @@ void short_pass(hipStream_t st, G1X *out, u64 nw, const PointSources<Fp, 1> &s) 
 void short_pass(hipStream_t st, G1X *out, u64 nw, const PointSources<Fp, 3> &s) { hipLaunchKernelGGL(k_phase2_sum_short_g1x3, dim3(mi_blocks_of(nw, 64)), dim3(64), 0, st, out, nw, s); }
 void short_pass(hipStream_t st, G2X *out, u64 nw, const PointSources<Fp2, 1> &s) { hipLaunchKernelGGL(k_phase2_sum_short_g2, dim3(mi_blocks_of(nw, 64)), dim3(64), 0, st, out, nw, s); }
 
-// batch_affine.cuh's conversion of n points, in and out two arrays; prefix is its scratch of n field elements
-template <class F>
-int32_t to_affine(mi_ctx *ctx, const XYZZ<F> *in, Affine<F> *out, F *prefix, u64 n) {
-    if (n) hipLaunchKernelGGL((k_xyzz_batch_to_affine<F, AFFINE_K>), dim3((unsigned)(((n + AFFINE_K - 1) / AFFINE_K + 63) / 64)), dim3(64), 0, ctx->stream, in, out, prefix, (size_t)n);
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    return MI_OK;
-}
 // every point of an affine array times s, in place
 template <class F>
 int32_t scale_array(mi_ctx *ctx, Affine<F> *pts, u64 n, const Fr &s) {
@@ -173,13 +131,13 @@ int32_t scale_array(mi_ctx *ctx, Affine<F> *pts, u64 n, const Fr &s) {
     MI_TRY(ar.alloc(ctx, &x, (size_t)n));
     MI_TRY(ar.alloc(ctx, &prefix, (size_t)n));
     Curve<F>::scale(ctx->stream, x, pts, n, s);
-    MI_TRY(to_affine(ctx, x, pts, prefix, n));
+    MI_TRY(mi_xyzz_to_affine_enqueue<F>(ctx, x, pts, prefix, (size_t)n));
     MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return MI_OK;
 }
 // the inverse point NTT of one SRS row, in place: row[bitrev(i)] <- [L_i] (affine)
 template <class F>
-int32_t lagrange_row(mi_ctx *ctx, Arena &ar, Laps &laps, float &ntt_ms, Affine<F> *row, u32 log_n, const Fr *tw, F *prefix) {
+int32_t lagrange_row(mi_ctx *ctx, Arena &ar, StreamLaps &laps, float &ntt_ms, Affine<F> *row, u32 log_n, const Fr *tw, F *prefix) {
     const u64 N = (u64)1 << log_n;
     XYZZ<F> *x = nullptr;
     MI_TRY(ar.alloc(ctx, &x, (size_t)N));
@@ -188,7 +146,7 @@ int32_t lagrange_row(mi_ctx *ctx, Arena &ar, Laps &laps, float &ntt_ms, Affine<F
     for (u32 s = 0; s < log_n; s++) Curve<F>::stage(ctx->stream, x, log_n, s, tw, s == 0 ? n_inv : Fr::one());
     MI_CHECK_HIP(ctx, hipGetLastError());
     MI_TRY(laps.lap(ctx, ntt_ms));
-    MI_TRY(to_affine(ctx, x, row, prefix, N));
+    MI_TRY(mi_xyzz_to_affine_enqueue<F>(ctx, x, row, prefix, (size_t)N));
     MI_TRY(laps.lap(ctx, ctx->phase2_stats.affine_ms));
     ar.release(x);
     return MI_OK;
@@ -238,7 +196,7 @@ int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, boo
     const u64 N = sh.N, nw = sh.nb_wires;
     const u32 log_n = sh.log_n;
     Arena ar;
-    Laps laps;
+    StreamLaps laps;
     MI_TRY(laps.init(ctx));
     // ---- 1: the SRS goes up and is checked
     G1Aff *T1 = nullptr, *Al = nullptr, *Be = nullptr;
@@ -275,7 +233,7 @@ int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, boo
         hipLaunchKernelGGL(k_phase2_z, dim3(mi_blocks_of(N, 256)), dim3(256), 0, st, zx, (const G1Aff *)T1, log_n);
         MI_CHECK_HIP(ctx, hipGetLastError());
         MI_TRY(laps.lap(ctx, stats.z_ms));
-        MI_TRY(to_affine(ctx, (const G1X *)zx, (G1Aff *)S->g1_z, (Fp *)prefix, N));
+        MI_TRY(mi_xyzz_to_affine_enqueue<Fp>(ctx, zx, (G1Aff *)S->g1_z, (Fp *)prefix, (size_t)N));
         MI_TRY(laps.lap(ctx, stats.affine_ms));
         ar.release(zx);
     }
@@ -342,15 +300,15 @@ int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, boo
                                        source_of<Fp>(mat[2], lp[2], T1, coeffs, log_n, ctr, 2)}};
         MI_TRY((sum_points<Fp, 1>(ctx, x1, nw, sa, ctr, part1, nullptr, nullptr)));
         MI_TRY(laps.lap(ctx, stats.sparse_g1_ms));
-        MI_TRY(to_affine(ctx, (const G1X *)x1, pA, (Fp *)prefix, nw));
+        MI_TRY(mi_xyzz_to_affine_enqueue<Fp>(ctx, x1, pA, (Fp *)prefix, (size_t)nw));
         MI_TRY(laps.lap(ctx, stats.affine_ms));
         MI_TRY((sum_points<Fp, 1>(ctx, x1, nw, sb, ctr, part1, nullptr, nullptr)));
         MI_TRY(laps.lap(ctx, stats.sparse_g1_ms));
-        MI_TRY(to_affine(ctx, (const G1X *)x1, pB1, (Fp *)prefix, nw));
+        MI_TRY(mi_xyzz_to_affine_enqueue<Fp>(ctx, x1, pB1, (Fp *)prefix, (size_t)nw));
         MI_TRY(laps.lap(ctx, stats.affine_ms));
         MI_TRY((sum_points<Fp, 3>(ctx, x1, nw, stt, ctr, part1, &stats.long_columns, &stats.chunks)));
         MI_TRY(laps.lap(ctx, stats.sparse_g1_ms));
-        MI_TRY(to_affine(ctx, (const G1X *)x1, pT, (Fp *)prefix, nw));
+        MI_TRY(mi_xyzz_to_affine_enqueue<Fp>(ctx, x1, pT, (Fp *)prefix, (size_t)nw));
         MI_TRY(laps.lap(ctx, stats.affine_ms));
         ar.release(x1); ar.release(part1);
     }
@@ -362,7 +320,7 @@ int32_t init_run(mi_ctx *ctx, const mi_r1cs_desc *d, const mi_srs_desc *srs, boo
         const PointSources<Fp2, 1> sb2{{source_of<Fp2>(mat[1], lp[1], T2, coeffs, log_n, ctr, 0)}};
         MI_TRY((sum_points<Fp2, 1>(ctx, x2, nw, sb2, ctr, part2, nullptr, nullptr)));
         MI_TRY(laps.lap(ctx, stats.sparse_g2_ms));
-        MI_TRY(to_affine(ctx, (const G2X *)x2, pB2, prefix, nw));
+        MI_TRY(mi_xyzz_to_affine_enqueue<Fp2>(ctx, x2, pB2, prefix, (size_t)nw));
         MI_TRY(laps.lap(ctx, stats.affine_ms));
         ar.release(x2); ar.release(part2);
     }
@@ -481,35 +439,23 @@ void mi_phase2_pedersen_vk_of(const mi_phase2 *S, mi_pedersen_vk *out) {
     }
 }
 int32_t mi_phase2_check_points(mi_ctx *ctx, Arena &ar, const Phase2Row *rows, int n_rows, uint32_t flags) {
-    hipStream_t st = ctx->stream;
-    ull *bad = nullptr, bad_h[16];   // word 2 i: row i's curve check; 2 i + 1: its r-torsion check
     if (n_rows > 8) return MI_EINVAL;
-    MI_TRY(ar.alloc(ctx, &bad, (size_t)16));
-    MI_CHECK_HIP(ctx, hipMemsetAsync(bad, 0xff, sizeof(bad_h), st));
-    for (int i = 0; i < n_rows; i++) {
-        const Phase2Row &r = rows[i];
-        if (r.g2) hipLaunchKernelGGL(k_phase2_check_g2, dim3(mi_blocks_of(r.n, 256)), dim3(256), 0, st, (const G2Aff *)r.pts, r.n, bad + 2 * i);
-        else hipLaunchKernelGGL(k_phase2_check_g1, dim3(mi_blocks_of(r.n, 256)), dim3(256), 0, st, (const G1Aff *)r.pts, r.n, bad + 2 * i);
-    }
-    MI_CHECK_HIP(ctx, hipGetLastError());
-    MI_CHECK_HIP(ctx, hipMemcpyAsync(bad_h, bad, sizeof(bad_h), hipMemcpyDeviceToHost, st));
-    MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
+    BadSlots bad;   // word 2 i: row i's curve check; 2 i + 1: its r-torsion check
+    MI_TRY(bad.init(ctx, 16, &ar));
+    for (int i = 0; i < n_rows; i++) MI_TRY(mi_points_check_enqueue(ctx, rows[i].g2, rows[i].pts, rows[i].n, POINT_RULE_SRS_ROW, bad.dev + 2 * i));
+    MI_TRY(bad.fetch(ctx));
     for (int i = 0; i < n_rows; i++)
-        if (bad_h[2 * i] != ~0ull)
-            MI_FAIL(ctx, MI_EINVAL, std::string("phase2: srs.") + rows[i].name + "[" + std::to_string(bad_h[2 * i]) + "] is at infinity or not on its curve");
+        if (bad.bad(2 * i))
+            MI_FAIL(ctx, MI_EINVAL, std::string("phase2: srs.") + rows[i].name + "[" + std::to_string(bad.host[2 * i]) + "] is at infinity or not on its curve");
     if (!(flags & MI_KEYFILE_NO_SUBGROUP_CHECK)) {   // of points of the twist only: the curve checks have passed
         bool any = false;
         for (int i = 0; i < n_rows; i++)
-            if (rows[i].g2) { MI_TRY(mi_keyfile_subgroup_enqueue(ctx, rows[i].pts, (size_t)rows[i].n, false, bad + 2 * i + 1)); any = true; }
-        if (any) {
-            MI_CHECK_HIP(ctx, hipMemcpyAsync(bad_h, bad, sizeof(bad_h), hipMemcpyDeviceToHost, st));
-            MI_CHECK_HIP(ctx, hipStreamSynchronize(st));
-        }
+            if (rows[i].g2) { MI_TRY(mi_keyfile_subgroup_enqueue(ctx, rows[i].pts, (size_t)rows[i].n, false, bad.dev + 2 * i + 1)); any = true; }
+        if (any) MI_TRY(bad.fetch(ctx));
         for (int i = 0; i < n_rows; i++)
-            if (bad_h[2 * i + 1] != ~0ull)
-                MI_FAIL(ctx, MI_EINVAL, std::string("phase2: srs.") + rows[i].name + "[" + std::to_string(bad_h[2 * i + 1]) + "] is not in the r-torsion");
+            if (bad.bad(2 * i + 1))
+                MI_FAIL(ctx, MI_EINVAL, std::string("phase2: srs.") + rows[i].name + "[" + std::to_string(bad.host[2 * i + 1]) + "] is not in the r-torsion");
     }
-    ar.release(bad);
     return MI_OK;
 }
 

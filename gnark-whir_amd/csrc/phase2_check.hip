@@ -21,14 +21,14 @@
 #include "verify_internal.h"
 #include "phase2_internal.h"
 #include "ceremony_ops.cuh"
-#include <sys/random.h>
+#include "point_check.cuh"
+#include "stream_clock.h"
 #include <cstring>
 #include <string>
 #include <vector>
 
 namespace {
 
-typedef unsigned long long ull;
 struct CeremonySeed { uint8_t b[32]; };
 
 // out[k] = r_k, Montgomery
@@ -39,13 +39,6 @@ __global__ void __launch_bounds__(256) k_ceremony_coeffs(CeremonySeed seed, u64 
     ceremony_coefficient(seed.b, k, w);
     out[k] = fr_from_u128(w);
 }
-// a claimed array: reduced words, on the curve; (0, 0) passes.  *first_bad takes the lowest index that is not
-__global__ void __launch_bounds__(256) k_ceremony_claim_check(const G1Aff *pts, u64 n, ull *first_bad) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const G1Aff p = pts[i];
-    if (!g1_on_curve(p)) atomicMin(first_bad, (ull)i);
-}
 // bad[i] = relation i does not hold (res: the products after their final exponentiations)
 __global__ void __launch_bounds__(64, 1) k_ceremony_judge(const Fp12 *res, u32 n_rel, uint8_t *bad) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -54,28 +47,10 @@ __global__ void __launch_bounds__(64, 1) k_ceremony_judge(const Fp12 *res, u32 n
     bad[i] = ceremony_relation_holds(&f) ? 0 : 1;
 }
 
-// the host's clock around work that has been waited for
-struct Clock {
-    double t = now_ms();
-    void lap(float &into) { const double n = now_ms(); into += (float)(n - t); t = n; }
-};
-int32_t sync_lap(mi_ctx *ctx, Clock &ck, float &into) {
-    MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ck.lap(into);
-    return MI_OK;
-}
-
-G1Aff g1_of(const mi_g1_affine &p) { G1Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
-G2Aff g2_of(const mi_g2_affine &p) { G2Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
-
 // seed, or 32 bytes of the operating system's into own
 int32_t seed_or_random(mi_ctx *ctx, const char *who, const uint8_t *&seed, uint8_t own[32]) {
     if (seed) return MI_OK;
-    for (size_t got = 0; got < 32;) {
-        const ssize_t k = getrandom(own + got, 32 - got, 0);
-        if (k <= 0) MI_FAIL(ctx, MI_ENODEV, std::string(who) + ": the operating system gave no randomness for the seed (getrandom)");
-        got += (size_t)k;
-    }
+    MI_TRY(mi_os_random(ctx, std::string(who) + ": the operating system gave no randomness for the seed (getrandom)", own, 32));
     seed = own;
     return MI_OK;
 }
@@ -87,14 +62,19 @@ int32_t coeffs_enqueue(mi_ctx *ctx, const uint8_t seed[32], u64 n, Fr *out_dev) 
     MI_CHECK_HIP(ctx, hipGetLastError());
     return MI_OK;
 }
-// sum_k scalars[k] bases[k] over device arrays, affine, (0, 0) = infinity; Montgomery scalars
-int32_t msm_g1(mi_ctx *ctx, const G1Aff *bases, const Fr *scalars, u64 n, G1Aff *out) { return mi_verify_msm(ctx, bases, scalars, (size_t)n, 0, out); }
+// sum_k scalars[k] bases[k] over device arrays, affine, (0, 0) = infinity; Montgomery scalars.  A sum over no pair is infinity, whatever
+// the pointers: nothing is launched for it
+int32_t msm_g1(mi_ctx *ctx, const G1Aff *bases, const Fr *scalars, u64 n, G1Aff *out) {
+    *out = G1Aff{Fp::zero(), Fp::zero()};
+    return n ? mi_verify_msm(ctx, bases, scalars, (size_t)n, 0, out) : MI_OK;
+}
 int32_t msm_g2(mi_ctx *ctx, const G2Aff *bases, const Fr *scalars, u64 n, G2Aff *out) {
+    *out = G2Aff{Fp2::zero(), Fp2::zero()};
+    if (!n) return MI_OK;
     mi_g2_jac j;   // normalised as the G1 result is: Z = 1, or Z = 0 for infinity
     MI_TRY(mi_msm_g2_dev(ctx, (const mi_g2_affine *)bases, (const mi_fr *)scalars, (size_t)n, 0, &j));
     Fp2 z;
     std::memcpy(&z, &j.z, sizeof(z));
-    *out = G2Aff{Fp2::zero(), Fp2::zero()};
     if (!z.is_zero()) std::memcpy(out, &j, sizeof(*out));
     return MI_OK;
 }
@@ -107,15 +87,7 @@ int32_t nonce_or_random(mi_ctx *ctx, const mi_fr *nonce, Fr &k) {
         if (!fe_is_reduced(k)) MI_FAIL(ctx, MI_EINVAL, "phase2: nonce is not below r");
         return MI_OK;
     }
-    uint8_t b[MI_H2F_BYTES];
-    for (size_t got = 0; got < sizeof(b);) {
-        const ssize_t n = getrandom(b + got, sizeof(b) - got, 0);
-        if (n <= 0) MI_FAIL(ctx, MI_ENODEV, "phase2: the operating system gave no randomness for the nonce (getrandom)");
-        got += (size_t)n;
-    }
-    k = fr_from_be48(b);
-    if (k.is_zero()) MI_FAIL(ctx, MI_ENODEV, "phase2: the drawn nonce is 0");
-    return MI_OK;
+    return mi_draw_nonce(ctx, "phase2: the operating system gave no randomness for the nonce (getrandom)", "phase2: the drawn nonce is 0", k);
 }
 
 typedef CeremonyRelations Relations;   // phase2_internal.h
@@ -150,7 +122,7 @@ int32_t judge(mi_ctx *ctx, Arena &ar, const Relations &rel, std::vector<uint8_t>
 int32_t srs_check_run(mi_ctx *ctx, const mi_srs_desc *srs, bool on_device, u64 N, const uint8_t *seed, uint32_t flags, mi_srs_check_stats &stats, uint32_t *failed) {
     hipStream_t st = ctx->stream;
     Arena ar;
-    Clock ck;
+    HostClock ck;
     Fr *r = nullptr;
     MI_TRY(ar.alloc(ctx, &r, (size_t)(2 * N - 1)));
     MI_TRY(coeffs_enqueue(ctx, seed, 2 * N - 1, r));
@@ -234,7 +206,7 @@ int32_t verify_run(mi_ctx *ctx, mi_phase2 *S, const mi_phase2_claim *claim, cons
                    bool *z_bad, bool *k_bad, bool *delta_bad) {
     hipStream_t st = ctx->stream;
     mi_srs_check_stats &stats = ctx->phase2_verify_stats;
-    Clock ck;
+    HostClock ck;
     const u64 N = S->N, nk = S->n_k;
     MI_TRY(ar.alloc(ctx, &c.z, (size_t)N));
     MI_TRY(ar.alloc(ctx, &c.k, (size_t)nk));
@@ -242,17 +214,14 @@ int32_t verify_run(mi_ctx *ctx, mi_phase2 *S, const mi_phase2_claim *claim, cons
     if (nk) MI_CHECK_HIP(ctx, hipMemcpyAsync(c.k, claim->g1_k, nk * sizeof(G1Aff), hipMemcpyHostToDevice, st));
     MI_TRY(sync_lap(ctx, ck, stats.upload_ms));
     {
-        ull *bad = nullptr, bad_h[2];
-        MI_TRY(ar.alloc(ctx, &bad, (size_t)2));
-        MI_CHECK_HIP(ctx, hipMemsetAsync(bad, 0xff, sizeof(bad_h), st));
-        hipLaunchKernelGGL(k_ceremony_claim_check, dim3(mi_blocks_of(N, 256)), dim3(256), 0, st, (const G1Aff *)c.z, N, bad);
-        if (nk) hipLaunchKernelGGL(k_ceremony_claim_check, dim3(mi_blocks_of(nk, 256)), dim3(256), 0, st, (const G1Aff *)c.k, nk, bad + 1);
-        MI_CHECK_HIP(ctx, hipGetLastError());
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(bad_h, bad, sizeof(bad_h), hipMemcpyDeviceToHost, st));
-        MI_TRY(sync_lap(ctx, ck, stats.point_check_ms));
-        ar.release(bad);
-        if (bad_h[0] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "phase2 verify: claim.g1_z[" + std::to_string(bad_h[0]) + "] is not a point of the curve");
-        if (bad_h[1] != ~0ull) MI_FAIL(ctx, MI_EINVAL, "phase2 verify: claim.g1_k[" + std::to_string(bad_h[1]) + "] is not a point of the curve");
+        BadSlots bad;
+        MI_TRY(bad.init(ctx, 2, &ar));
+        MI_TRY(mi_points_check_enqueue(ctx, false, c.z, N, POINT_RULE_CLAIM, bad.dev));
+        MI_TRY(mi_points_check_enqueue(ctx, false, c.k, nk, POINT_RULE_CLAIM, bad.dev + 1));
+        MI_TRY(bad.fetch(ctx));
+        ck.lap(stats.point_check_ms);
+        if (bad.bad(0)) MI_FAIL(ctx, MI_EINVAL, "phase2 verify: claim.g1_z[" + std::to_string(bad.host[0]) + "] is not a point of the curve");
+        if (bad.bad(1)) MI_FAIL(ctx, MI_EINVAL, "phase2 verify: claim.g1_k[" + std::to_string(bad.host[1]) + "] is not a point of the curve");
     }
     Fr *r = nullptr;
     const u64 nr = N > nk ? N : nk;
@@ -279,12 +248,12 @@ int32_t verify_run(mi_ctx *ctx, mi_phase2 *S, const mi_phase2_claim *claim, cons
 }
 
 // the claimed BasisExpSigma arrays on the device, and per commitment whether its relation fails.  No kernel here is new: the claim is
-// checked by k_ceremony_claim_check, summed by the context's MSM and judged by judge() as Z and K are above
+// checked by point_check.cuh's POINT_RULE_CLAIM, summed by the context's MSM and judged by judge() as Z and K are above
 int32_t sigma_verify_run(mi_ctx *ctx, mi_phase2 *S, const mi_phase2_sigma_claim *claim, const uint8_t *seed, Arena &ar, std::vector<G1Aff *> &bes,
                          std::vector<uint8_t> &bad) {
     hipStream_t st = ctx->stream;
     mi_srs_check_stats &stats = ctx->phase2_verify_stats;
-    Clock ck;
+    HostClock ck;
     const u32 nc = S->n_commitments;
     u64 nr = 0;
     for (u32 k = 0; k < nc; k++) {
@@ -295,28 +264,21 @@ int32_t sigma_verify_run(mi_ctx *ctx, mi_phase2 *S, const mi_phase2_sigma_claim 
     }
     MI_TRY(sync_lap(ctx, ck, stats.upload_ms));
     {
-        ull *first_bad = nullptr;
-        std::vector<ull> first_bad_h(nc);
-        MI_TRY(ar.alloc(ctx, &first_bad, (size_t)nc));
-        MI_CHECK_HIP(ctx, hipMemsetAsync(first_bad, 0xff, nc * sizeof(ull), st));
+        BadSlots bad;
+        MI_TRY(bad.init(ctx, nc, &ar));
+        for (u32 k = 0; k < nc; k++) MI_TRY(mi_points_check_enqueue(ctx, false, bes[k], S->ped[k].n, POINT_RULE_CLAIM, bad.dev + k));
+        MI_TRY(bad.fetch(ctx));
+        ck.lap(stats.point_check_ms);
         for (u32 k = 0; k < nc; k++)
-            if (S->ped[k].n) hipLaunchKernelGGL(k_ceremony_claim_check, dim3(mi_blocks_of(S->ped[k].n, 256)), dim3(256), 0, st, (const G1Aff *)bes[k], S->ped[k].n, first_bad + k);
-        MI_CHECK_HIP(ctx, hipGetLastError());
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(first_bad_h.data(), first_bad, nc * sizeof(ull), hipMemcpyDeviceToHost, st));
-        MI_TRY(sync_lap(ctx, ck, stats.point_check_ms));
-        ar.release(first_bad);
-        for (u32 k = 0; k < nc; k++)
-            if (first_bad_h[k] != ~0ull)
-                MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: claim.basis_exp_sigma[" + std::to_string(k) + "][" + std::to_string(first_bad_h[k]) + "] is not a point of the curve");
+            if (bad.bad(k))
+                MI_FAIL(ctx, MI_EINVAL, "phase2 verify sigma: claim.basis_exp_sigma[" + std::to_string(k) + "][" + std::to_string(bad.host[k]) + "] is not a point of the curve");
     }
     Fr *r = nullptr;
     MI_TRY(ar.alloc(ctx, &r, (size_t)nr));
     MI_TRY(coeffs_enqueue(ctx, seed, nr, r));
     MI_TRY(sync_lap(ctx, ck, stats.coeff_ms));
-    const G1Aff inf1{Fp::zero(), Fp::zero()};
-    std::vector<G1Aff> sum_basis(nc, inf1), sum_bes(nc, inf1);
+    std::vector<G1Aff> sum_basis(nc), sum_bes(nc);
     for (u32 k = 0; k < nc; k++) {
-        if (!S->ped[k].n) continue;
         MI_TRY(msm_g1(ctx, (const G1Aff *)S->ped[k].basis, r, S->ped[k].n, &sum_basis[k]));
         MI_TRY(msm_g1(ctx, bes[k], r, S->ped[k].n, &sum_bes[k]));
     }
@@ -339,11 +301,19 @@ void CeremonyRelations::add(const G1Aff &pa, const G2Aff &qa, const G1Aff &pb, c
 }
 int32_t mi_ceremony_seed_or_random(mi_ctx *ctx, const char *who, const uint8_t *&seed, uint8_t own[32]) { return seed_or_random(ctx, who, seed, own); }
 int32_t mi_ceremony_coeffs_enqueue(mi_ctx *ctx, const uint8_t seed[32], u64 n, Fr *out_dev) { return coeffs_enqueue(ctx, seed, n, out_dev); }
-int32_t mi_ceremony_msm_g1(mi_ctx *ctx, const G1Aff *bases, const Fr *scalars, u64 n, G1Aff *out) { return msm_g1(ctx, bases, scalars, n, out); }
-int32_t mi_ceremony_msm_g2(mi_ctx *ctx, const G2Aff *bases, const Fr *scalars, u64 n, G2Aff *out) { return msm_g2(ctx, bases, scalars, n, out); }
+int32_t mi_ceremony_msm_g1(mi_ctx *ctx, const void *bases, const Fr *scalars, u64 n, G1Aff *out) { return msm_g1(ctx, (const G1Aff *)bases, scalars, n, out); }
+int32_t mi_ceremony_msm_g2(mi_ctx *ctx, const void *bases, const Fr *scalars, u64 n, G2Aff *out) { return msm_g2(ctx, (const G2Aff *)bases, scalars, n, out); }
 int32_t mi_ceremony_judge(mi_ctx *ctx, Arena &ar, const CeremonyRelations &rel, std::vector<uint8_t> &bad) { return judge(ctx, ar, rel, bad); }
 
 // ---------------------------------------------------------------------------------------------------- shared with phase1.hip
+// abi_glue.h: the drawn nonce of a proved contribution, phase 1's and phase 2's
+int32_t mi_draw_nonce(mi_ctx *ctx, const char *msg_no_random, const char *msg_zero, Fr &k) {
+    uint8_t b[MI_H2F_BYTES];
+    MI_TRY(mi_os_random(ctx, msg_no_random, b, sizeof(b)));
+    k = fr_from_be48(b);
+    if (k.is_zero()) MI_FAIL(ctx, MI_ENODEV, msg_zero);
+    return MI_OK;
+}
 int32_t mi_srs_check_rows_dev(mi_ctx *ctx, const char *who, const mi_srs_desc *rows_dev, u64 N, const uint8_t *seed, mi_srs_check_stats &stats, uint32_t *failed) {
     uint8_t own_seed[32];
     MI_TRY(seed_or_random(ctx, who, seed, own_seed));

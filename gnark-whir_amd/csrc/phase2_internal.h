@@ -4,6 +4,7 @@
 #include "ctx.h"
 #include "fp12.cuh"
 #include "dev_arena.h"
+#include "abi_glue.h"
 #include "../../include/mi355x_groth16_phase2_check.h"
 #include <vector>
 
@@ -32,8 +33,8 @@ struct mi_phase2 {
 
 // null rows and rows shorter than the circuit needs (tau_g1: 2 N, the others: N)
 int32_t mi_phase2_srs_host_check(mi_ctx *ctx, const mi_srs_desc *srs, u64 N);
-// One row of an SRS on the device.  mi_phase2_check_points over n_rows of them: every point on its curve and not at infinity -- the rows
-// in the order given, the lowest bad index of the first bad row named -- then, unless flags holds MI_KEYFILE_NO_SUBGROUP_CHECK, every
+// One row of an SRS on the device.  mi_phase2_check_points over n_rows of them: every point on its curve and not at infinity
+// (point_check.cuh's POINT_RULE_SRS_ROW) -- the rows in the order given, the lowest bad index of the first bad row named -- then, unless flags holds MI_KEYFILE_NO_SUBGROUP_CHECK, every
 // point of the G2 rows in the r-torsion, the same way.  MI_EINVAL with "phase2: srs.<name>[<index>] ..." in mi_last_error.  The stream
 // is idle on return.  At most 8 rows.
 struct Phase2Row { const char *name; bool g2; const void *pts; u64 n; };
@@ -57,9 +58,10 @@ void mi_phase2_pedersen_vk_of(const mi_phase2 *S, mi_pedersen_vk *out);
 int32_t mi_ceremony_seed_or_random(mi_ctx *ctx, const char *who, const uint8_t *&seed, uint8_t own[32]);
 // out_dev[k] = r_k for k < n (k_ceremony_coeffs), Montgomery, enqueued on ctx->stream
 int32_t mi_ceremony_coeffs_enqueue(mi_ctx *ctx, const uint8_t seed[32], u64 n, Fr *out_dev);
-// sum_k scalars[k] bases[k] over device arrays, affine, (0, 0) = infinity; Montgomery scalars.  The result is on the host on return
-int32_t mi_ceremony_msm_g1(mi_ctx *ctx, const G1Aff *bases, const Fr *scalars, u64 n, G1Aff *out);
-int32_t mi_ceremony_msm_g2(mi_ctx *ctx, const G2Aff *bases, const Fr *scalars, u64 n, G2Aff *out);
+// sum_k scalars[k] bases[k] over device arrays of affine points (G1Aff / G2Aff), (0, 0) = infinity; Montgomery scalars.  The result is on
+// the host on return.  A sum over no pair is infinity, whatever the pointers, and launches nothing
+int32_t mi_ceremony_msm_g1(mi_ctx *ctx, const void *bases, const Fr *scalars, u64 n, G1Aff *out);
+int32_t mi_ceremony_msm_g2(mi_ctx *ctx, const void *bases, const Fr *scalars, u64 n, G2Aff *out);
 // The relations of one call: relation i is e(p[2 i], q[2 i]) = e(pb, q[2 i + 1]), with p[2 i + 1] = -pb
 struct CeremonyRelations {
     std::vector<G1Aff> p;

@@ -4,10 +4,10 @@
 #include "curve.cuh"
 #include "msm_curve_ops.h"
 #include "key_plan.h"
+#include "abi_glue.h"   // fr_of: a scalar of the C-ABI (Montgomery words) as the library's Fr
 #include <functional>
 #include <future>
 #include <cstring>
-inline Fr fr_of(const mi_fr &x) { Fr r; std::memcpy(&r, &x, 32); return r; }   // a scalar of the C-ABI (Montgomery words) as the library's Fr
 
 // The MSMs of a proof that share one sort of their scalars, as the key serves them.
 struct KeyGroup {

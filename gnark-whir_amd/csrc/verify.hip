@@ -73,8 +73,6 @@ __global__ void __launch_bounds__(64, 1) k_verify_assemble(const VerifyAssembleA
     verify_assemble_lane(a, i, p, q);
 }
 
-G1Aff g1_of(const mi_g1_affine &p) { G1Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
-G2Aff g2_of(const mi_g2_affine &p) { G2Aff a; std::memcpy(&a, &p, sizeof(a)); return a; }
 static_assert(sizeof(mi_pedersen_vk) == 2 * sizeof(G2Aff) && sizeof(mi_g1_affine) == sizeof(G1Aff) && sizeof(mi_fr) == sizeof(Fr),
               "pairing_ops.cuh reads the header's records as G1Aff / G2Aff / Fr");
 

@@ -28,7 +28,6 @@
 // through mi_verify_msm (verify_internal.h).  The front of this body is the locating body's too and is defined here, once.
 #include "verify_internal.h"
 #include "combine_coeff.cuh"
-#include <sys/random.h>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -90,11 +89,7 @@ int32_t mi_verify_refuse_msm_pairs(mi_ctx *ctx, const mi_vk *vk, bool args_ok, s
 }
 int32_t mi_verify_seed(mi_ctx *ctx, const char *who, const uint8_t *&seed, uint8_t own[32]) {
     if (seed) return MI_OK;
-    for (size_t got = 0; got < 32;) {
-        const ssize_t k = getrandom(own + got, 32 - got, 0);
-        if (k <= 0) MI_FAIL(ctx, MI_ENODEV, std::string(who) + "the operating system gave no randomness for the seed (getrandom)");
-        got += (size_t)k;
-    }
+    MI_TRY(mi_os_random(ctx, std::string(who) + "the operating system gave no randomness for the seed (getrandom)", own, 32));
     seed = own;
     return MI_OK;
 }

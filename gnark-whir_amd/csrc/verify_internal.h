@@ -12,6 +12,7 @@
 #include "../../include/mi355x_groth16_verify_wave.h"
 #include "../../include/mi355x_groth16_verify_ksum.h"
 #include "pairing_ops.cuh"
+#include "abi_glue.h"
 #include <vector>
 
 struct mi_vk {

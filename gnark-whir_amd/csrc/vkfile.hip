@@ -10,13 +10,13 @@
 #include "../../include/mi355x_groth16_vkfile.h"
 #include "keyfile_ops.cuh"
 #include "keyfile_internal.h"
+#include "dev_arena.h"
 #include <cstring>
 #include <string>
 #include <vector>
 
 namespace {
 
-typedef unsigned long long ull;
 void put_be(uint8_t *&p, uint64_t v, int bytes) {
     for (int i = bytes - 1; i >= 0; i--) *p++ = (uint8_t)(v >> (8 * i));
 }
@@ -38,15 +38,16 @@ int32_t mi_vk_stream_decode(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_
     G1Aff *d_g1 = nullptr;
     G2Aff *d_g2 = nullptr;
     uint8_t *raw = nullptr;
-    ull *d_bad = nullptr;
     enum { S_ALPHA_BETA1, S_BETA_GAMMA2, S_DELTA1, S_DELTA2, S_K0, S_K, S_PED, S_SUBGROUP, S_END };
     auto body = [&]() -> int32_t {
         MI_CHECK_HIP(ctx, hipMalloc((void **)&d_g1, 4 * sizeof(G1Aff)));
         MI_CHECK_HIP(ctx, hipMalloc((void **)&d_g2, n_g2 * sizeof(G2Aff)));
         MI_CHECK_HIP(ctx, hipMalloc(&out.k_dev, (n_k - 1) * sizeof(G1Aff) + 64));
-        MI_CHECK_HIP(ctx, hipMalloc((void **)&d_bad, S_END * sizeof(ull)));
+        BadSlots slots;   // one word per run of points the stream holds back to back, then the membership test
+        MI_TRY(slots.init(ctx, S_END));
+        unsigned long long *const d_bad = slots.dev;
+        const std::vector<unsigned long long> &bad = slots.host;
         MI_CHECK_HIP(ctx, hipMalloc((void **)&raw, len));
-        MI_CHECK_HIP(ctx, hipMemsetAsync(d_bad, 0xff, S_END * sizeof(ull), ctx->stream));
         MI_CHECK_HIP(ctx, hipMemcpyAsync(raw, buf, len, hipMemcpyHostToDevice, ctx->stream));
         const size_t g1b = MI_KEYFILE_G1_BYTES(compressed);
         G1Aff *const d_k = (G1Aff *)out.k_dev;
@@ -62,12 +63,10 @@ int32_t mi_vk_stream_decode(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_
         out.g2.resize(n_g2);
         out.k.resize(n_k);
         std::vector<G2Aff> g2(n_g2);
-        ull bad[S_END];
         MI_CHECK_HIP(ctx, hipMemcpyAsync(out.g1, d_g1, sizeof(out.g1), hipMemcpyDeviceToHost, ctx->stream));
         MI_CHECK_HIP(ctx, hipMemcpyAsync(g2.data(), d_g2, n_g2 * sizeof(G2Aff), hipMemcpyDeviceToHost, ctx->stream));
         if (n_k > 1) MI_CHECK_HIP(ctx, hipMemcpyAsync(out.k.data() + 1, d_k, (n_k - 1) * sizeof(G1Aff), hipMemcpyDeviceToHost, ctx->stream));
-        MI_CHECK_HIP(ctx, hipMemcpyAsync(bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
-        MI_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the one wait
+        MI_TRY(slots.fetch(ctx));   // the one wait
         out.k[0] = out.g1[3];
         std::memcpy(out.g2.data(), g2.data(), n_g2 * sizeof(G2Aff));
         // ---- the decoders' verdicts, in stream order
@@ -94,7 +93,7 @@ int32_t mi_vk_stream_decode(mi_ctx *ctx, const uint8_t *buf, size_t len, uint32_
     };
     const int32_t rc = body();
     (void)hipStreamSynchronize(ctx->stream);
-    for (void *a : {(void *)d_g1, (void *)d_g2, (void *)d_bad, (void *)raw})
+    for (void *a : {(void *)d_g1, (void *)d_g2, (void *)raw})
         if (a) (void)hipFree(a);
     return rc;
 }
