@@ -35,67 +35,57 @@
 #include "msm_curve_ops.h"
 #include "ntt_cross.h"
 #include <rccl/rccl.h>
-#include <atomic>
-#include <chrono>
+#include "group_link.h"   // transport 3: the shared-memory segment, its rings and its all-gather area (host code only)
 #include <cstdlib>
-#include <cstring>
 #include <future>
-#include <thread>
-#include <vector>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
-// ---------------------------------------------------------------- transport 3: the shared-memory segment
-static constexpr uint32_t SHM_MAGIC = 0x6d693335u, SHM_MAX_WORLD = 64, SHM_AG_MAX = 1024;
-struct alignas(64) ShmRing { std::atomic<uint64_t> head; char pad0[56]; std::atomic<uint64_t> tail; char pad1[56]; };   // chunks produced (by the source) / consumed (by the destination)
-struct alignas(64) ShmAg { std::atomic<uint64_t> seq; char pad[56]; unsigned char data[2][SHM_AG_MAX]; };              // collective k writes data[k & 1], then seq = k
-struct ShmHeader {
-    std::atomic<uint32_t> magic;      // set by rank 0 when the header is initialised
-    uint32_t world, nslot;
-    uint64_t chunk;                   // bytes per ring slot
-    std::atomic<uint32_t> attached;   // ranks that have mapped the segment
-    std::atomic<uint32_t> poisoned;   // a rank hit a transport error: everyone waiting gives up at once
-    std::atomic<uint64_t> beat;       // rank 0 counts here while it waits for the others to attach: a segment whose count stands still has no creator any more
-    ShmAg ag[SHM_MAX_WORLD];
-    ShmRing ring[SHM_MAX_WORLD * SHM_MAX_WORLD];   // ring[src * world + dst]
+// Everything one LOCAL rank owns.  The events, one enum: seven "ready" events of computeH over the ranks -- a transfer waits for the ONE
+// kernel that produced what it moves, not for whatever else has been enqueued on the context's stream since: that is what lets the
+// next vector's arithmetic run under this vector's transfer -- and the six hand-over events of the exchanges.
+enum { E_IN, E_DA, E_DB, E_DC, E_FA, E_FB, E_MID,          // computeH: inputs, cross-rank steps of a / b / c, coset transforms of a / b, middle kernel
+       E_C0, E_C1,                                         // computeH: the context's stream -> the exchange stream (last coefficient) and back
+       E_PEER_IN, E_PEER_OUT,                              // transport 2: the stream-level barriers on entry to and exit from a batch
+       E_DONE, E_H, E_COUNT };                             // slice sums -> an MSM's stream; the h slice has arrived (recorded by its receiver)
+enum { H_A, H_B, H_C, H_Y0, H_Y1, H_COUNT };               // computeH over the ranks: the slice vectors of a, b, c and the two exchange vectors
+struct GroupRank {
+    int dev = 0; mi_ctx *ctx = nullptr;
+    ncclComm_t comm = nullptr;     // transport 1: this rank's RCCL communicator
+    hipStream_t xs = nullptr;      // the exchange stream (sends, receives, slice sums)
+    hipEvent_t ev[E_COUNT] = {};
+    DevBuf recv;                   // bucket slices received from the other ranks
+    DevBuf stage;                  // small staging area for the all-gathers (transport 1)
+    // computeH over the ranks (compute_h_sharded): the vectors of H_*, the h slice with one slot in front (the previous rank's last
+    // coefficient: the Z cut of a sharded key starts one element early) and the cross-rank tables
+    DevBuf hv[H_COUNT], hh;
+    CrossNttTables xt;
 };
-struct ShmLink {
-    ShmHeader *h = nullptr;
-    unsigned char *data = nullptr;    // ring r, slot k: data + ((size_t)r * nslot + k) * chunk
-    size_t map_bytes = 0;
-    uint64_t ag_seq = 0;              // collectives of the all-gather area this rank has entered (all ranks in lockstep)
-    int timeout_ms = 60000;
-    std::vector<void *> registered;   // the ring regions pinned for the device (hipHostRegister): this rank's row and column
-};
-
 struct mi_group {
     int world = 0;                 // ranks in the group
-    int rank0 = 0;                 // global rank of the first local context
+    int rank0 = 0;                 // global rank of the first local rank
     int transport = 0;             // 1 = RCCL, 2 = same-process copies, 3 = host-staged (shared memory)
-    std::vector<int> dev;          // device of every LOCAL rank
-    std::vector<mi_ctx *> ctx;     // one context per local rank
-    std::vector<ncclComm_t> comm;  // transport 1: RCCL communicator per local rank
+    std::vector<GroupRank> rk;     // the LOCAL ranks, complete at creation (threads of a call hold references into it)
     ShmLink shm;                   // transport 3
-    std::vector<hipStream_t> xs;   // per local rank: the exchange stream (sends, receives, slice sums)
-    std::vector<hipEvent_t> ev_x, ev_in, ev_done, ev_h;
-    std::vector<DevBuf> recv;      // per local rank: bucket slices received from the other ranks
-    std::vector<DevBuf> stage;     // per local rank: small staging area for the all-gathers (transport 1)
-    // computeH over the ranks (compute_h_sharded): per local rank the cross-rank tables, three slice vectors + the exchange area + the h
-    // slice with one slot in front (the previous rank's last coefficient: the Z cut of a sharded key starts one element early), two events
+    std::vector<void *> pinned;    // transport 3: the ring regions pinned for the device (hipHostRegister): this rank's row and column
     bool sharded_h = false;        // mi_group_set_sharded_compute_h: mi_groth16_prove_sharded runs computeH over all ranks
-    std::vector<CrossNttTables> xt;
-    std::vector<DevBuf> hx[3], hy, hy2, hh;
-    std::vector<hipEvent_t> ev_c0, ev_c1, ev_r;
     uint32_t lead_share = 0xffffffffu;   // permille of an even wire share that rank 0 -- which also runs computeH -- takes (mi_group_set_lead_share; all ones = automatic)
     int timeout_ms = 60000;        // how long a rank waits for its peers without anything completing (MI_GROUP_TIMEOUT_MS; both transports)
     bool nonblocking = false;      // transport 1, one rank per process: the communicator is non-blocking and every wait on it is a deadline poll
     std::string err;
     bool broken = false;           // a transport call failed half-way: rings / communicator are in an unknown state, every later call is refused
     std::atomic<bool> busy{false};   // calls on one group must not overlap: an entry point that finds it set returns MI_EINVAL (GroupCall)
-    int n_local() const { return (int)ctx.size(); }
+    int n_local() const { return (int)rk.size(); }
     bool local(int r) const { return r >= rank0 && r < rank0 + n_local(); }
+    u32 log_w() const { u32 lw = 0; while ((1 << lw) < world) lw++; return lw; }
+    // computeH over the ranks at N = 2^log_n: a rank's slice has M = 2^log_m elements, a block of an all-to-all cnt = M / world of them
+    struct HCut { u32 log_w, log_m; size_t M, cnt; };
+    HCut h_cut(u32 log_n) const { const u32 lw = log_w(), lm = log_n - lw; return {lw, lm, (size_t)1 << lm, ((size_t)1 << lm) >> lw}; }
+};
+// The first LOCAL failure of a call: noted, carried through every exchange the peers are already in, returned afterwards.
+struct Carried {
+    int32_t rc = MI_OK; std::string text;
+    void note(int32_t r, const std::string &msg) { if (r != MI_OK && rc == MI_OK) { rc = r; text = msg; } }
+    bool ok() const { return rc == MI_OK; }
+    int32_t leave(mi_group *g) const { if (!ok()) g->err = text; return rc; }   // the call's return: the failure with its text, or MI_OK
 };
 struct mi_pk_sharded {
     std::vector<mi_pk *> part;     // one per local rank
@@ -108,10 +98,10 @@ struct mi_pk_sharded {
 #define G_FAIL(g, code, msg) do { (g)->err = (msg); return (code); } while (0)
 #define G_HIP(g, call) do { hipError_t e__ = mi_fault_hit() ? hipErrorUnknown : (call); if (e__ != hipSuccess) { (g)->err = std::string(#call) + ": " + hipGetErrorString(e__); \
                             return e__ == hipErrorOutOfMemory ? MI_ENOMEM : MI_EHIP; } } while (0)
-#define G_CTX(g, i, expr) do { int32_t rc__ = (expr); if (rc__ != MI_OK) { (g)->err = mi_last_error((g)->ctx[i]); return rc__; } } while (0)
+#define G_CTX(g, i, expr) do { int32_t rc__ = (expr); if (rc__ != MI_OK) { (g)->err = mi_last_error((g)->rk[i].ctx); return rc__; } } while (0)
 
 // Entry-point guard: the group's exchange streams, receive buffers and per-rank contexts serve ONE call at a time.  A second call that
-// arrives while one is running is refused (MI_EINVAL, the running call's error text is left alone) instead of corrupting g->recv.
+// arrives while one is running is refused (MI_EINVAL, the running call's error text is left alone) instead of corrupting the ranks' receive buffers.
 struct GroupCall {
     mi_group *g; bool ok;
     explicit GroupCall(mi_group *g_) : g(g_), ok(g_ && !g_->busy.exchange(true, std::memory_order_acquire)) {}
@@ -142,146 +132,34 @@ static void wire_range_of(u64 nb_wires, int world, int r, uint32_t share, u64 &l
     lo = lead_n + a; hi = lead_n + b;
 }
 
-// ---------------------------------------------------------------- transport 3: shared-memory link
-static std::string shm_name_of(const uint8_t id[128]) {
-    uint64_t h = 1469598103934665603ull;   // FNV-1a over the 128 id bytes
-    for (int i = 0; i < 128; i++) { h ^= id[i]; h *= 1099511628211ull; }
-    char buf[64];
-    snprintf(buf, sizeof buf, "/mi355x_grp_%016llx", (unsigned long long)h);
-    return buf;
+// ---------------------------------------------------------------- transport 3: the link (group_link.h) on this group
+static int32_t link_status(mi_group *g, const LinkStatus &s) {   // what the link reports becomes the group's text and flag
+    if (!s.text.empty()) g->err = s.text;
+    if (s.broken) g->broken = true;
+    return s.code;
 }
-struct Deadline {
-    std::chrono::steady_clock::time_point t;
-    explicit Deadline(int ms) : t(std::chrono::steady_clock::now() + std::chrono::milliseconds(ms)) {}
-    bool passed() const { return std::chrono::steady_clock::now() > t; }
-};
-static void shm_pause(unsigned &spins) {
-    if (++spins < 200) std::this_thread::yield();
-    else std::this_thread::sleep_for(std::chrono::microseconds(50));
-}
-// Rank 0 creates and initialises the segment, the others map it as soon as it shows its magic; once every rank is attached rank 0
-// unlinks the name, so that nothing outlives the processes whatever way they end.
 static int32_t shm_attach(mi_group *g, const uint8_t id[128]) {
-    ShmLink &L = g->shm;
-    L.timeout_ms = g->timeout_ms;
     uint64_t chunk = (uint64_t)1 << 20;
-    uint32_t nslot = 4;
     if (const char *e = getenv("MI_GROUP_SHM_CHUNK_KB")) { const long v = atol(e); if (v >= 4 && v <= (1 << 16)) chunk = (uint64_t)v << 10; }
-    const int W = g->world, rank = g->rank0;
-    if (W > (int)SHM_MAX_WORLD) G_FAIL(g, MI_EINVAL, "group: the host-staged transport serves at most 64 ranks");
-    const size_t hdr = (sizeof(ShmHeader) + 4095) & ~(size_t)4095;
-    const std::string name = shm_name_of(id);
-    const Deadline dl(L.timeout_ms);
-    if (rank == 0) {
-        (void)shm_unlink(name.c_str());   // a leftover of a run that died before everyone had attached
-        const int fd = shm_open(name.c_str(), O_CREAT | O_EXCL | O_RDWR, 0600);
-        if (fd < 0) G_FAIL(g, MI_EHIP, "group: shm_open (create) failed");
-        L.map_bytes = hdr + (size_t)W * W * nslot * chunk;   // tmpfs allocates a page when it is first touched: rings nobody uses cost nothing
-        if (ftruncate(fd, (off_t)L.map_bytes) != 0) { close(fd); (void)shm_unlink(name.c_str()); G_FAIL(g, MI_ENOMEM, "group: ftruncate of the shared segment failed"); }
-        void *m = mmap(nullptr, L.map_bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-        close(fd);
-        if (m == MAP_FAILED) { (void)shm_unlink(name.c_str()); G_FAIL(g, MI_ENOMEM, "group: mmap of the shared segment failed"); }
-        L.h = (ShmHeader *)m;
-        L.data = (unsigned char *)m + hdr;
-        // (a fresh tmpfs file reads as zeros: rings, sequence numbers and flags start at 0)
-        L.h->world = (uint32_t)W; L.h->nslot = nslot; L.h->chunk = chunk;
-        L.h->magic.store(SHM_MAGIC, std::memory_order_release);
-    } else {
-        // The name may still point at the segment of an EARLIER group with the same id (a run that died before rank 0 unlinked it, or rank
-        // 0 of this run has not replaced it yet): its magic and shape look right.  A segment is this group's only if, once its magic shows,
-        // the NAME still leads to the same file -- rank 0 unlinks a leftover before it creates, and unlinks its own only after every rank
-        // (this one included) has attached.  Anything else is unmapped and the name is tried again until the deadline.
-        unsigned spins = 0;
-        for (;;) {
-            if (dl.passed()) G_FAIL(g, MI_EHIP, "group: rank 0 never created (or initialised) the shared segment (timeout)");
-            const int fd = shm_open(name.c_str(), O_RDWR, 0600);
-            struct stat sb;
-            if (fd < 0 || fstat(fd, &sb) != 0 || (size_t)sb.st_size < hdr) { if (fd >= 0) close(fd); shm_pause(spins); continue; }   // not there / not sized yet
-            const size_t bytes = (size_t)sb.st_size;
-            void *m = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-            close(fd);
-            if (m == MAP_FAILED) G_FAIL(g, MI_ENOMEM, "group: mmap of the shared segment failed");
-            ShmHeader *h = (ShmHeader *)m;
-            bool mine = false;
-            while (!dl.passed()) {
-                if (h->magic.load(std::memory_order_acquire) == SHM_MAGIC) {
-                    const int fd2 = shm_open(name.c_str(), O_RDWR, 0600);
-                    struct stat sb2;
-                    mine = fd2 >= 0 && fstat(fd2, &sb2) == 0 && sb2.st_ino == sb.st_ino && sb2.st_dev == sb.st_dev;
-                    if (fd2 >= 0) close(fd2);
-                    if (mine) {   // ... and its creator is alive: rank 0 counts h->beat while it waits for us (a leftover's stands still)
-                        const uint64_t b0 = h->beat.load(std::memory_order_acquire);
-                        const Deadline alive(L.timeout_ms < 1000 ? L.timeout_ms : 1000);
-                        while (h->beat.load(std::memory_order_acquire) == b0 && !alive.passed()) shm_pause(spins);
-                        mine = h->beat.load(std::memory_order_acquire) != b0;
-                    }
-                    break;
-                }
-                shm_pause(spins);
-            }
-            if (mine && (int)h->world == W && hdr + (size_t)W * W * h->nslot * h->chunk <= bytes) { L.h = h; L.data = (unsigned char *)m + hdr; L.map_bytes = bytes; break; }
-            (void)munmap(m, bytes);
-            if (mine) G_FAIL(g, MI_EINVAL, "group: the shared segment belongs to a group of another shape");
-            shm_pause(spins);   // a leftover: try the name again
-        }
-    }
-    L.h->attached.fetch_add(1, std::memory_order_acq_rel);
-    unsigned spins = 0;
-    while ((int)L.h->attached.load(std::memory_order_acquire) < W) {
-        if (dl.passed()) { if (rank == 0) (void)shm_unlink(name.c_str()); G_FAIL(g, MI_EHIP, "group: not every rank attached to the shared segment (timeout)"); }
-        if (rank == 0) L.h->beat.fetch_add(1, std::memory_order_release);
-        shm_pause(spins);
-    }
-    if (rank == 0) (void)shm_unlink(name.c_str());
+    ShmLink &L = g->shm;
+    MI_TRY(link_status(g, L.attach(shm_name_of(id), g->rank0, g->world, g->timeout_ms, chunk, 4)));
     // The rings THIS rank sources (row `rank`, contiguous) or sinks (column `rank`) as pinned memory: copies to and from them run at the
     // bus rate and do not stage a second time (best effort).  Registering pins -- and therefore allocates -- every page it covers: the
     // whole area would be W * W rings for every rank (256 MB at W = 8, 16 GB at 64), these are 2 W - 1.
-    {
-        const size_t ring_bytes = (size_t)L.h->nslot * L.h->chunk;
-        auto reg = [&](size_t first_ring, size_t n_rings) {
-            void *p = L.data + first_ring * ring_bytes;
-            if (hipHostRegister(p, n_rings * ring_bytes, hipHostRegisterDefault) == hipSuccess) L.registered.push_back(p);
-            else (void)hipGetLastError();
-        };
-        reg((size_t)rank * W, (size_t)W);
-        for (int s = 0; s < W; s++) if (s != rank) reg((size_t)s * W + rank, 1);
-    }
+    const size_t W = (size_t)g->world, rank = (size_t)g->rank0;
+    auto reg = [&](size_t first_ring, size_t n_rings) {
+        void *p = L.data + first_ring * L.ring_bytes();
+        if (hipHostRegister(p, n_rings * L.ring_bytes(), hipHostRegisterDefault) == hipSuccess) g->pinned.push_back(p);
+        else (void)hipGetLastError();
+    };
+    reg(rank * W, W);
+    for (size_t s = 0; s < W; s++) if (s != rank) reg(s * W + rank, 1);
     return MI_OK;
 }
 static void shm_detach(mi_group *g) {
-    ShmLink &L = g->shm;
-    if (!L.h) return;
-    for (void *p : L.registered) (void)hipHostUnregister(p);
-    L.registered.clear();
-    (void)munmap((void *)L.h, L.map_bytes);
-    L.h = nullptr; L.data = nullptr;
-}
-static int32_t shm_fail(mi_group *g, const char *msg) {
-    g->shm.h->poisoned.store(1, std::memory_order_release);
-    g->broken = true;
-    G_FAIL(g, MI_EHIP, msg);
-}
-// all-gather of `bytes` (<= SHM_AG_MAX) per rank through the segment's all-gather area
-static int32_t shm_allgather(mi_group *g, const void *local, size_t bytes, void *all) {
-    ShmLink &L = g->shm;
-    if (bytes > SHM_AG_MAX) G_FAIL(g, MI_EINVAL, "group: all-gather payload too large");
-    const uint64_t k = ++L.ag_seq;
-    ShmAg &mine = L.h->ag[g->rank0];
-    std::memcpy(mine.data[k & 1], local, bytes);
-    mine.seq.store(k, std::memory_order_release);
-    const Deadline dl(L.timeout_ms);
-    for (int r = 0; r < g->world; r++) {
-        unsigned spins = 0;
-        // (a rank may be one collective ahead -- it then wrote the OTHER buffer -- never two: collective k + 1 completes only once
-        //  every rank has entered it, i.e. has finished reading k)
-        while (L.h->ag[r].seq.load(std::memory_order_acquire) < k) {
-            if (L.h->poisoned.load(std::memory_order_acquire)) { g->broken = true; G_FAIL(g, MI_EHIP, "group: another rank reported a transport failure"); }
-            if (dl.passed()) return shm_fail(g, "group: a rank did not reach the all-gather (timeout; did its process end?)");
-            shm_pause(spins);
-        }
-        std::memcpy((char *)all + (size_t)r * bytes, L.h->ag[r].data[k & 1], bytes);
-    }
-    return MI_OK;
+    for (void *p : g->pinned) (void)hipHostUnregister(p);
+    g->pinned.clear();
+    g->shm.detach();
 }
 
 // ---------------------------------------------------------------- transport 1 with one rank per process: deadlines
@@ -293,7 +171,7 @@ static int32_t shm_allgather(mi_group *g, const void *local, size_t bytes, void 
 // Single-process groups (ncclCommInitAll) keep blocking communicators: all their ranks live and die with this process.
 static inline bool nccl_ok(ncclResult_t r) { return r == ncclSuccess || r == ncclInProgress; }
 static int32_t nccl_abort_all(mi_group *g, const std::string &msg) {
-    for (auto &c : g->comm) if (c) { (void)ncclCommAbort(c); c = nullptr; }
+    for (GroupRank &k : g->rk) if (k.comm) { (void)ncclCommAbort(k.comm); k.comm = nullptr; }
     g->broken = true;
     G_FAIL(g, MI_EHIP, msg);
 }
@@ -304,7 +182,7 @@ static int32_t nccl_settle(mi_group *g, int i, const char *what) {
     unsigned spins = 0;
     for (;;) {
         ncclResult_t st = ncclSuccess;
-        const ncclResult_t r = ncclCommGetAsyncError(g->comm[i], &st);
+        const ncclResult_t r = ncclCommGetAsyncError(g->rk[i].comm, &st);
         if (r != ncclSuccess) return nccl_abort_all(g, std::string("group: ncclCommGetAsyncError failed ") + what + ": " + ncclGetErrorString(r));
         if (st == ncclSuccess) return MI_OK;
         if (st != ncclInProgress) return nccl_abort_all(g, std::string("group: RCCL reported an asynchronous error ") + what + ": " + ncclGetErrorString(st));
@@ -323,7 +201,7 @@ static int32_t nccl_wait_stream(mi_group *g, int i, hipStream_t s, const char *w
         if (q == hipSuccess) return MI_OK;
         if (q != hipErrorNotReady) { (void)hipGetLastError(); return nccl_abort_all(g, std::string("group: the exchange stream failed ") + what + ": " + hipGetErrorString(q)); }
         ncclResult_t st = ncclSuccess;
-        if (ncclCommGetAsyncError(g->comm[i], &st) != ncclSuccess || (st != ncclSuccess && st != ncclInProgress))
+        if (ncclCommGetAsyncError(g->rk[i].comm, &st) != ncclSuccess || (st != ncclSuccess && st != ncclInProgress))
             return nccl_abort_all(g, std::string("group: RCCL reported an asynchronous error ") + what + ": " + ncclGetErrorString(st));
         if (dl.passed()) return nccl_abort_all(g, std::string("group: the exchange did not complete ") + what + " (timeout; did a peer's process end?)");
         shm_pause(spins);
@@ -331,75 +209,24 @@ static int32_t nccl_wait_stream(mi_group *g, int i, hipStream_t s, const char *w
 }
 
 // ---------------------------------------------------------------- point-to-point batches
-struct Xfer { int src, dst; const void *sp; void *dp; size_t bytes; };   // global ranks; a pointer is meaningful in its owner's process only
-// transport 3: every transfer this process takes part in advances chunk by chunk through ring[src][dst] -- the source copies a chunk
-// device -> slot and publishes it (head), the destination copies slot -> device and releases it (tail).  A process both sends and
-// receives in one batch and the rings are finite, so the two directions are interleaved in ONE progress loop (two ranks that each
-// first sent everything would wait for each other's free slots forever).  Transfers of one (src, dst) pair complete in list order
-// (the ring is a FIFO and both sides build the same list).
-static int32_t run_xfers_shm(mi_group *g, const std::vector<Xfer> &list, const std::vector<hipStream_t> &xs) {
-    ShmLink &L = g->shm;
-    const int W = g->world, me = g->rank0;
-    const size_t chunk = (size_t)L.h->chunk;
-    const uint32_t nslot = L.h->nslot;
-    (void)hipSetDevice(g->dev[0]);
-    G_HIP(g, hipStreamSynchronize(xs[0]));   // what this rank sends is complete; what it receives into is no longer read
-    struct St { size_t sent = 0, rcvd = 0; };
-    std::vector<St> st(list.size());
-    Deadline dl(L.timeout_ms);   // the time this rank may WAIT for its peers without any chunk moving (renewed by every chunk)
-    unsigned spins = 0;
-    for (;;) {
-        bool all_done = true, progress = false;
-        std::vector<char> pair_send_busy((size_t)W * W, 0), pair_recv_busy((size_t)W * W, 0);
-        for (size_t k = 0; k < list.size(); k++) {
-            const Xfer &x = list[k];
-            if (!x.bytes) continue;
-            const size_t pr = (size_t)x.src * W + x.dst;
-            ShmRing &ring = L.h->ring[pr];
-            unsigned char *slots = L.data + pr * nslot * chunk;
-            if (x.src == me && st[k].sent < x.bytes) {
-                all_done = false;
-                if (!pair_send_busy[pr]) {
-                    pair_send_busy[pr] = 1;   // later transfers of this pair wait for this one
-                    uint64_t head = ring.head.load(std::memory_order_relaxed);
-                    while (st[k].sent < x.bytes && head - ring.tail.load(std::memory_order_acquire) < nslot) {
-                        const size_t nb = x.bytes - st[k].sent < chunk ? x.bytes - st[k].sent : chunk;
-                        G_HIP(g, hipMemcpyAsync(slots + (head % nslot) * chunk, (const char *)x.sp + st[k].sent, nb, hipMemcpyDeviceToHost, xs[0]));
-                        G_HIP(g, hipStreamSynchronize(xs[0]));
-                        st[k].sent += nb;
-                        ring.head.store(++head, std::memory_order_release);
-                        progress = true;
-                    }
-                }
-            }
-            if (x.dst == me && st[k].rcvd < x.bytes) {
-                all_done = false;
-                if (!pair_recv_busy[pr]) {
-                    pair_recv_busy[pr] = 1;
-                    uint64_t tail = ring.tail.load(std::memory_order_relaxed);
-                    while (st[k].rcvd < x.bytes && tail < ring.head.load(std::memory_order_acquire)) {
-                        const size_t nb = x.bytes - st[k].rcvd < chunk ? x.bytes - st[k].rcvd : chunk;
-                        G_HIP(g, hipMemcpyAsync((char *)x.dp + st[k].rcvd, slots + (tail % nslot) * chunk, nb, hipMemcpyHostToDevice, xs[0]));
-                        G_HIP(g, hipStreamSynchronize(xs[0]));
-                        st[k].rcvd += nb;
-                        ring.tail.store(++tail, std::memory_order_release);
-                        progress = true;
-                    }
-                }
-            }
-        }
-        if (all_done) return MI_OK;
-        if (progress) { spins = 0; dl = Deadline(L.timeout_ms); continue; }
-        if (L.h->poisoned.load(std::memory_order_acquire)) { g->broken = true; G_FAIL(g, MI_EHIP, "group: another rank reported a transport failure"); }
-        if (dl.passed()) return shm_fail(g, "group: a peer did not take part in the exchange (timeout; did its process end?)");
-        shm_pause(spins);
-    }
+// transport 3: the link's progress loop over this rank's exchange stream; a chunk is complete in its slot / on the device when its copy returns
+static int32_t run_xfers_shm(mi_group *g, const std::vector<Xfer> &list) {
+    hipStream_t xs = g->rk[0].xs;
+    (void)hipSetDevice(g->rk[0].dev);
+    G_HIP(g, hipStreamSynchronize(xs));   // what this rank sends is complete; what it receives into is no longer read
+    auto copy = [&](void *dst, const void *src, size_t nb, hipMemcpyKind kind) -> int32_t {
+        G_HIP(g, hipMemcpyAsync(dst, src, nb, kind, xs));
+        G_HIP(g, hipStreamSynchronize(xs));
+        return MI_OK;
+    };
+    return link_status(g, g->shm.run_xfers(list, [&](void *slot, const void *src, size_t nb) { return copy(slot, src, nb, hipMemcpyDeviceToHost); },
+                                           [&](void *dst, const void *slot, size_t nb) { return copy(dst, slot, nb, hipMemcpyHostToDevice); }));
 }
-// Runs the batch on the exchange streams xs[local rank].  Afterwards xs[i] is ordered after every transfer rank i sends or receives.
+// Runs the batch on the ranks' exchange streams.  Afterwards rk[i].xs is ordered after every transfer rank i sends or receives.
 // A failure inside a batch leaves the transport in an unknown state (some ranks may be waiting in it): the group is marked broken.
-static int32_t run_xfers_impl(mi_group *g, const std::vector<Xfer> &xs_list, const std::vector<hipStream_t> &xs) {
+static int32_t run_xfers_impl(mi_group *g, const std::vector<Xfer> &xs_list) {
     const MiRange range_fn("mi.group.exchange");
-    if (g->transport == 3) return run_xfers_shm(g, xs_list, xs);
+    if (g->transport == 3) return run_xfers_shm(g, xs_list);
     if (g->transport == 1) {
         // every ncclGroupStart is closed by its ncclGroupEnd whatever happens in between (an open group would swallow this thread's next
         // RCCL calls); the first failure is reported after the group has been closed
@@ -410,13 +237,15 @@ static int32_t run_xfers_impl(mi_group *g, const std::vector<Xfer> &xs_list, con
         for (const Xfer &x : xs_list) {
             if (!x.bytes || bad != ncclSuccess) continue;
             if (g->local(x.src)) {
-                (void)hipSetDevice(g->dev[x.src - g->rank0]);
-                r = mi_fault_hit() ? ncclInternalError : ncclSend(x.sp, x.bytes, ncclUint8, x.dst, g->comm[x.src - g->rank0], xs[x.src - g->rank0]);
+                const GroupRank &k = g->rk[x.src - g->rank0];
+                (void)hipSetDevice(k.dev);
+                r = mi_fault_hit() ? ncclInternalError : ncclSend(x.sp, x.bytes, ncclUint8, x.dst, k.comm, k.xs);
                 if (!nccl_ok(r)) { bad = r; where = "ncclSend"; continue; }
             }
             if (g->local(x.dst)) {
-                (void)hipSetDevice(g->dev[x.dst - g->rank0]);
-                r = ncclRecv(x.dp, x.bytes, ncclUint8, x.src, g->comm[x.dst - g->rank0], xs[x.dst - g->rank0]);
+                const GroupRank &k = g->rk[x.dst - g->rank0];
+                (void)hipSetDevice(k.dev);
+                r = ncclRecv(x.dp, x.bytes, ncclUint8, x.src, k.comm, k.xs);
                 if (!nccl_ok(r)) { bad = r; where = "ncclRecv"; }
             }
         }
@@ -431,38 +260,37 @@ static int32_t run_xfers_impl(mi_group *g, const std::vector<Xfer> &xs_list, con
             // one rank per process: the batch is issued AND complete (or the group is broken) before anything else is built on it -- a peer
             // that ended mid-exchange surfaces here, within the deadline, not in some later synchronisation without one
             MI_TRY(nccl_settle(g, 0, "while issuing an exchange"));
-            MI_TRY(nccl_wait_stream(g, 0, xs[0], "in an exchange"));
+            MI_TRY(nccl_wait_stream(g, 0, g->rk[0].xs, "in an exchange"));
         }
         return MI_OK;
     }
     // same process, no communicator (a device named twice): peer copies on the source's stream, then every stream waits for all.
     // A copy is issued by its SOURCE into the destination's buffer, so the sources must first wait for whatever the destinations
     // still do with those buffers (the slice sums of the previous exchange): a stream-level barrier on entry as well.
-    for (int i = 0; i < g->n_local(); i++) { (void)hipSetDevice(g->dev[i]); G_HIP(g, hipEventRecord(g->ev_in[i], xs[i])); }
-    for (int i = 0; i < g->n_local(); i++) {
-        (void)hipSetDevice(g->dev[i]);
-        for (int j = 0; j < g->n_local(); j++) if (j != i) G_HIP(g, hipStreamWaitEvent(xs[i], g->ev_in[j], 0));
-    }
+    auto barrier = [&](int ev) -> int32_t {   // every exchange stream waits for what every other one has been given so far
+        for (GroupRank &k : g->rk) { (void)hipSetDevice(k.dev); G_HIP(g, hipEventRecord(k.ev[ev], k.xs)); }
+        for (GroupRank &k : g->rk) {
+            (void)hipSetDevice(k.dev);
+            for (GroupRank &o : g->rk) if (&o != &k) G_HIP(g, hipStreamWaitEvent(k.xs, o.ev[ev], 0));
+        }
+        return MI_OK;
+    };
+    MI_TRY(barrier(E_PEER_IN));
     for (const Xfer &x : xs_list) {
         if (!x.bytes) continue;
         if (!g->local(x.src) || !g->local(x.dst)) G_FAIL(g, MI_EINVAL, "group: peer-copy transport reached a remote rank");
-        const int s = x.src - g->rank0, d = x.dst - g->rank0;
-        (void)hipSetDevice(g->dev[s]);
-        if (g->dev[s] == g->dev[d]) G_HIP(g, hipMemcpyAsync(x.dp, x.sp, x.bytes, hipMemcpyDeviceToDevice, xs[s]));
-        else G_HIP(g, hipMemcpyPeerAsync(x.dp, g->dev[d], x.sp, g->dev[s], x.bytes, xs[s]));
+        const GroupRank &s = g->rk[x.src - g->rank0], &d = g->rk[x.dst - g->rank0];
+        (void)hipSetDevice(s.dev);
+        if (s.dev == d.dev) G_HIP(g, hipMemcpyAsync(x.dp, x.sp, x.bytes, hipMemcpyDeviceToDevice, s.xs));
+        else G_HIP(g, hipMemcpyPeerAsync(x.dp, d.dev, x.sp, s.dev, x.bytes, s.xs));
     }
-    for (int i = 0; i < g->n_local(); i++) { (void)hipSetDevice(g->dev[i]); G_HIP(g, hipEventRecord(g->ev_x[i], xs[i])); }
-    for (int i = 0; i < g->n_local(); i++) {
-        (void)hipSetDevice(g->dev[i]);
-        for (int j = 0; j < g->n_local(); j++) if (j != i) G_HIP(g, hipStreamWaitEvent(xs[i], g->ev_x[j], 0));
-    }
-    return MI_OK;
+    return barrier(E_PEER_OUT);
 }
-static int32_t run_xfers(mi_group *g, const std::vector<Xfer> &xs_list, const std::vector<hipStream_t> &xs) {
-    const int32_t rc = run_xfers_impl(g, xs_list, xs);
+static int32_t run_xfers(mi_group *g, const std::vector<Xfer> &xs_list) {
+    const int32_t rc = run_xfers_impl(g, xs_list);
     if (rc != MI_OK && g->n_local() != g->world) {   // the peers may be inside the exchange this rank just left
         g->broken = true;
-        if (g->transport == 3) g->shm.h->poisoned.store(1, std::memory_order_release);
+        if (g->transport == 3) g->shm.poison();
     }
     return rc;
 }
@@ -476,15 +304,16 @@ static int32_t group_allgather(mi_group *g, const void *local, size_t bytes, voi
     if (g->n_local() == g->world && !g->nonblocking) { std::memcpy(all, local, bytes * (size_t)g->world); return MI_OK; }
     if (g->n_local() != 1) G_FAIL(g, MI_EINVAL, "group: a process holds either all ranks or exactly one");
     int32_t rc;
-    if (g->transport == 3) rc = shm_allgather(g, local, bytes, all);
-    else if (g->transport != 1 || g->comm.size() != 1) G_FAIL(g, MI_EINVAL, "group: no transport between the processes of this group");
+    if (g->transport == 3) rc = link_status(g, g->shm.allgather(local, bytes, all));
+    else if (g->transport != 1 || !g->rk[0].comm) G_FAIL(g, MI_EINVAL, "group: no transport between the processes of this group");
     else rc = [&]() -> int32_t {
-        (void)hipSetDevice(g->dev[0]);
-        G_CTX(g, 0, mi_reserve(g->ctx[0], g->stage[0], bytes * (size_t)(g->world + 1)));
-        char *st = (char *)g->stage[0].p;
-        hipStream_t s = g->xs[0];
+        GroupRank &k = g->rk[0];
+        (void)hipSetDevice(k.dev);
+        G_CTX(g, 0, mi_reserve(k.ctx, k.stage, bytes * (size_t)(g->world + 1)));
+        char *st = (char *)k.stage.p;
+        hipStream_t s = k.xs;
         G_HIP(g, hipMemcpyAsync(st, local, bytes, hipMemcpyHostToDevice, s));
-        const ncclResult_t r = mi_fault_hit() ? ncclInternalError : ncclAllGather(st, st + bytes, bytes, ncclUint8, g->comm[0], s);
+        const ncclResult_t r = mi_fault_hit() ? ncclInternalError : ncclAllGather(st, st + bytes, bytes, ncclUint8, k.comm, s);
         if (!nccl_ok(r)) {
             const std::string msg = std::string("group: ncclAllGather: ") + ncclGetErrorString(r);
             if (g->nonblocking) return nccl_abort_all(g, msg);
@@ -498,27 +327,39 @@ static int32_t group_allgather(mi_group *g, const void *local, size_t bytes, voi
     if (rc != MI_OK) g->broken = true;   // some ranks may have got through, others not: nothing collective can follow
     return rc;
 }
-// What every rank says before the group enters an exchange: its status and up to ten values all ranks must agree on.
-struct Agree { int32_t rc; uint32_t check_n; uint64_t check[10]; };
-// local_rc / local_err: the first failure among this process's ranks (MI_OK: none).  Every rank of the group returns MI_OK or every
-// rank returns an error: the failing rank its own, the others "another rank failed".  check[0..check_n): values that must be EQUAL on
-// all ranks (bucket layouts of an exchange).
-static int32_t group_agree(mi_group *g, int32_t local_rc, const std::string &local_err, const char *phase, const uint64_t *check = nullptr, uint32_t check_n = 0) {
-    std::vector<Agree> mine((size_t)g->n_local()), all((size_t)g->world);
-    for (auto &a : mine) {
-        std::memset(&a, 0, sizeof a);
-        a.rc = local_rc; a.check_n = check_n;
-        for (uint32_t k = 0; k < check_n && k < 10; k++) a.check[k] = check[k];
-    }
-    MI_TRY(group_allgather(g, mine.data(), sizeof(Agree), all.data()));
-    for (int r = 0; r < g->world; r++)
-        if (all[r].rc != MI_OK) {
-            if (local_rc != MI_OK) { g->err = local_err; return local_rc; }
-            g->err = std::string("group: rank ") + std::to_string(r) + " failed " + phase + " (status " + std::to_string(all[r].rc) + "); nothing was exchanged";
-            return all[r].rc;
+// Every local rank contributes the call's carried status and a payload (mine[local rank]) in ONE all-gather: either every rank of the
+// group returns MI_OK with all `world` payloads, or every rank returns an error -- a rank that failed its own, the others
+// "group: rank r failed <phase> (status n)<tail>".
+template <class P>
+static int32_t group_gather(mi_group *g, const Carried &st, const std::vector<P> &mine, const char *phase, const char *tail, std::vector<P> &all) {
+    struct Slot { int32_t rc; uint32_t pad[3]; P p; };
+    static_assert(sizeof(Slot) <= SHM_AG_MAX, "a gathered payload must fit the link's all-gather area");
+    std::vector<Slot> in(mine.size()), out((size_t)g->world);
+    for (size_t i = 0; i < in.size(); i++) { std::memset((void *)&in[i], 0, sizeof(Slot)); in[i].rc = st.rc; std::memcpy((void *)&in[i].p, (const void *)&mine[i], sizeof(P)); }
+    MI_TRY(group_allgather(g, in.data(), sizeof(Slot), out.data()));
+    all.resize(out.size());
+    for (int r = 0; r < g->world; r++) {
+        if (out[r].rc != MI_OK) {
+            if (!st.ok()) return st.leave(g);
+            g->err = std::string("group: rank ") + std::to_string(r) + " failed " + phase + " (status " + std::to_string(out[r].rc) + ")" + tail;
+            return out[r].rc;
         }
+        std::memcpy((void *)&all[r], (const void *)&out[r].p, sizeof(P));
+    }
+    return MI_OK;
+}
+// What every rank says before the group enters an exchange: its status (st: the first failure among this process's ranks) and up to ten
+// values that must be EQUAL on all ranks (bucket layouts of an exchange).  Every rank of the group returns MI_OK or every rank returns an
+// error: the failing rank its own, the others "another rank failed".
+static int32_t group_agree(mi_group *g, const Carried &st, const char *phase, const uint64_t *check = nullptr, uint32_t check_n = 0) {
+    struct Checks { uint32_t n; uint64_t v[10]; } c;
+    std::memset(&c, 0, sizeof c);
+    c.n = check_n;
+    for (uint32_t k = 0; k < check_n && k < 10; k++) c.v[k] = check[k];
+    std::vector<Checks> all;
+    MI_TRY(group_gather(g, st, std::vector<Checks>((size_t)g->n_local(), c), phase, "; nothing was exchanged", all));
     for (int r = 1; r < g->world; r++)
-        if (all[r].check_n != all[0].check_n || std::memcmp(all[r].check, all[0].check, sizeof all[0].check) != 0)
+        if (all[r].n != all[0].n || std::memcmp(all[r].v, all[0].v, sizeof c.v) != 0)
             G_FAIL(g, MI_EINVAL, std::string("group: the ranks disagree on the shape of the exchange ") + phase);
     return MI_OK;
 }
@@ -532,47 +373,42 @@ static int32_t group_min_max(mi_group *g, const std::vector<u64> &local, u64 *mn
 }
 
 // ---------------------------------------------------------------- lifecycle
-static int32_t group_finish_init(mi_group *g) {
-    const int n = g->n_local();
-    g->xs.assign(n, nullptr); g->ev_x.assign(n, nullptr); g->ev_in.assign(n, nullptr); g->ev_done.assign(n, nullptr); g->ev_h.assign(n, nullptr);
-    g->recv.assign(n, DevBuf{}); g->stage.assign(n, DevBuf{});
-    g->xt.assign(n, CrossNttTables{}); g->hy.assign(n, DevBuf{}); g->hy2.assign(n, DevBuf{}); g->hh.assign(n, DevBuf{}); g->ev_c0.assign(n, nullptr); g->ev_c1.assign(n, nullptr);
-    g->ev_r.assign((size_t)n * 7, nullptr);   // computeH over the ranks: seven "ready" events a local rank, created by compute_h_sharded_prepare
-    for (auto &v : g->hx) v.assign(n, DevBuf{});
+// The local ranks on devices devs[0..n): every rank's context first, then every rank's exchange stream and all the events it will ever
+// record (the order matters: context, stream, context, stream moved a sharded proof at 2^22 by half a millisecond, up in mode 0 and
+// down in mode 1, profiles/group_ranks.txt).  A rank is in g->rk from the moment it has a context, so that
+// mi_group_destroy releases whatever a failure half-way left.
+static int32_t ranks_open(mi_group *g, const int *devs, int n) {
     for (int i = 0; i < n; i++) {
-        (void)hipSetDevice(g->dev[i]);
-        G_HIP(g, hipEventCreateWithFlags(&g->ev_c0[i], hipEventDisableTiming));
-        G_HIP(g, hipEventCreateWithFlags(&g->ev_c1[i], hipEventDisableTiming));
-        G_HIP(g, hipStreamCreateWithFlags(&g->xs[i], hipStreamNonBlocking));
-        G_HIP(g, hipEventCreateWithFlags(&g->ev_x[i], hipEventDisableTiming));
-        G_HIP(g, hipEventCreateWithFlags(&g->ev_in[i], hipEventDisableTiming));
-        G_HIP(g, hipEventCreateWithFlags(&g->ev_done[i], hipEventDisableTiming));
-        G_HIP(g, hipEventCreateWithFlags(&g->ev_h[i], hipEventDisableTiming));
+        GroupRank k;
+        MI_TRY(mi_init(k.dev = devs[i], &k.ctx));
+        g->rk.push_back(k);
+    }
+    for (GroupRank &k : g->rk) {
+        (void)hipSetDevice(k.dev);
+        G_HIP(g, hipStreamCreateWithFlags(&k.xs, hipStreamNonBlocking));
+        for (hipEvent_t &e : k.ev) G_HIP(g, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     return MI_OK;
+}
+static void rank_release(GroupRank &k, bool broken) {   // everything but the context
+    (void)hipSetDevice(k.dev);
+    (void)hipStreamSynchronize(k.ctx->stream);
+    if (k.xs) { (void)hipStreamSynchronize(k.xs); (void)hipStreamDestroy(k.xs); }
+    // (a broken group's communicator was aborted where it broke; one that is merely unused is destroyed -- on a non-blocking
+    //  communicator neither call holds this thread)
+    if (k.comm) (void)(broken ? ncclCommAbort(k.comm) : ncclCommDestroy(k.comm));
+    for (hipEvent_t e : k.ev) if (e) (void)hipEventDestroy(e);
+    for (DevBuf *b : {&k.hv[H_A], &k.hv[H_B], &k.hv[H_C], &k.hv[H_Y0], &k.hv[H_Y1], &k.hh, &k.recv, &k.stage}) if (b->p) (void)hipFree(b->p);
+    mi_cross_tables_free(&k.xt);
 }
 
 extern "C" {
 
 int32_t mi_group_destroy(mi_group *g) {
     if (!g) return MI_EINVAL;
-    for (int i = 0; i < g->n_local(); i++) {
-        (void)hipSetDevice(g->dev[i]);
-        if (g->ctx[i]) (void)hipStreamSynchronize(g->ctx[i]->stream);
-        if (i < (int)g->xs.size() && g->xs[i]) { (void)hipStreamSynchronize(g->xs[i]); (void)hipStreamDestroy(g->xs[i]); }
-        // (a broken group's communicator was aborted where it broke; one that is merely unused is destroyed -- on a non-blocking
-        //  communicator neither call holds this thread)
-        if (i < (int)g->comm.size() && g->comm[i]) (void)(g->broken ? ncclCommAbort(g->comm[i]) : ncclCommDestroy(g->comm[i]));
-        for (auto *v : {&g->ev_x, &g->ev_in, &g->ev_done, &g->ev_h}) if (i < (int)v->size() && (*v)[i]) (void)hipEventDestroy((*v)[i]);
-        for (auto *v : {&g->ev_c0, &g->ev_c1}) if (i < (int)v->size() && (*v)[i]) (void)hipEventDestroy((*v)[i]);
-        for (size_t k = (size_t)i * 7; k < (size_t)(i + 1) * 7 && k < g->ev_r.size(); k++) if (g->ev_r[k]) (void)hipEventDestroy(g->ev_r[k]);
-        for (auto *v : {&g->hx[0], &g->hx[1], &g->hx[2], &g->hy, &g->hy2, &g->hh}) if (i < (int)v->size() && (*v)[i].p) (void)hipFree((*v)[i].p);
-        if (i < (int)g->xt.size()) mi_cross_tables_free(&g->xt[i]);
-        if (i < (int)g->recv.size() && g->recv[i].p) (void)hipFree(g->recv[i].p);
-        if (i < (int)g->stage.size() && g->stage[i].p) (void)hipFree(g->stage[i].p);
-    }
+    for (GroupRank &k : g->rk) rank_release(k, g->broken);
     shm_detach(g);
-    for (int i = 0; i < g->n_local(); i++) if (g->ctx[i]) { (void)hipSetDevice(g->dev[i]); mi_shutdown(g->ctx[i]); }
+    for (GroupRank &k : g->rk) { (void)hipSetDevice(k.dev); mi_shutdown(k.ctx); }
     delete g;
     return MI_OK;
 }
@@ -586,14 +422,8 @@ int32_t mi_group_create(const int *dev_ids, int n_dev, mi_group **out) {
     g->world = n_dev; g->rank0 = 0;
     bool distinct = true;
     for (int i = 0; i < n_dev; i++) for (int j = 0; j < i; j++) if (dev_ids[i] == dev_ids[j]) distinct = false;
-    for (int i = 0; i < n_dev; i++) {
-        mi_ctx *c = nullptr;
-        int32_t rc = mi_init(dev_ids[i], &c);
-        if (rc != MI_OK) { mi_group_destroy(g); return rc; }
-        g->dev.push_back(dev_ids[i]); g->ctx.push_back(c);
-    }
-    int32_t rc = group_finish_init(g);
     g->transport = distinct ? 1 : 2;
+    int32_t rc = ranks_open(g, dev_ids, n_dev);
     if (rc == MI_OK && distinct) {
         // full-mesh xGMI: let every device map every other one (peer copies of the h slices; RCCL does its own set-up)
         for (int i = 0; i < n_dev; i++) for (int j = 0; j < n_dev; j++) if (i != j) {
@@ -601,9 +431,9 @@ int32_t mi_group_create(const int *dev_ids, int n_dev, mi_group **out) {
             hipError_t e = hipDeviceEnablePeerAccess(dev_ids[j], 0);
             if (e != hipSuccess) (void)hipGetLastError();   // already enabled, or no direct link: hipMemcpyPeerAsync still works (staged)
         }
-        g->comm.assign(n_dev, nullptr);
-        ncclResult_t r = ncclCommInitAll(g->comm.data(), n_dev, dev_ids);
-        if (r != ncclSuccess) { g->comm.clear(); mi_group_destroy(g); return MI_EHIP; }
+        std::vector<ncclComm_t> comms((size_t)n_dev, nullptr);
+        if (ncclCommInitAll(comms.data(), n_dev, dev_ids) != ncclSuccess) rc = MI_EHIP;
+        else for (int i = 0; i < n_dev; i++) g->rk[i].comm = comms[i];
     }
     if (rc != MI_OK) { mi_group_destroy(g); return rc; }
     *out = g;
@@ -626,21 +456,16 @@ int32_t mi_group_create_rank_ex(int device_id, int rank, int world, const uint8_
     if (!g) return MI_ENOMEM;
     g->world = world; g->rank0 = rank; g->transport = transport;
     if (const char *e = getenv("MI_GROUP_TIMEOUT_MS")) { const int v = atoi(e); if (v > 0) g->timeout_ms = v; }
-    mi_ctx *c = nullptr;
-    int32_t rc = mi_init(device_id, &c);
-    if (rc != MI_OK) { delete g; return rc; }
-    g->dev.push_back(device_id); g->ctx.push_back(c);
-    rc = group_finish_init(g);
+    int32_t rc = ranks_open(g, &device_id, 1);
     if (rc == MI_OK && transport == MI_GROUP_TRANSPORT_RCCL) {
         ncclUniqueId u;
         std::memcpy(&u, id, 128);
         (void)hipSetDevice(device_id);
-        g->comm.assign(1, nullptr);
         ncclConfig_t cfg = NCCL_CONFIG_INITIALIZER;
         cfg.blocking = 0;   // (see "transport 1 with one rank per process: deadlines")
         g->nonblocking = true;
-        const ncclResult_t r = ncclCommInitRankConfig(&g->comm[0], world, u, rank, &cfg);
-        if (!nccl_ok(r) || !g->comm[0]) { g->comm.clear(); g->err = std::string("ncclCommInitRankConfig: ") + ncclGetErrorString(r); rc = MI_EHIP; }
+        const ncclResult_t r = ncclCommInitRankConfig(&g->rk[0].comm, world, u, rank, &cfg);
+        if (!nccl_ok(r) || !g->rk[0].comm) { g->rk[0].comm = nullptr; g->err = std::string("ncclCommInitRankConfig: ") + ncclGetErrorString(r); rc = MI_EHIP; }
         else rc = nccl_settle(g, 0, "while the communicator was coming up (every rank of the group must call mi_group_create_rank)");
     }
     if (rc == MI_OK && transport == MI_GROUP_TRANSPORT_HOST) { (void)hipSetDevice(device_id); rc = shm_attach(g, id); }
@@ -667,7 +492,7 @@ int32_t mi_group_wire_range(const mi_group *g, uint64_t nb_wires, int rank, uint
 int32_t mi_group_world(const mi_group *g) { return g ? g->world : 0; }
 int32_t mi_group_rank(const mi_group *g) { return g ? g->rank0 : -1; }
 int32_t mi_group_local(const mi_group *g) { return g ? g->n_local() : 0; }
-mi_ctx *mi_group_ctx(mi_group *g, int local_rank) { return g && local_rank >= 0 && local_rank < g->n_local() ? g->ctx[local_rank] : nullptr; }
+mi_ctx *mi_group_ctx(mi_group *g, int local_rank) { return g && local_rank >= 0 && local_rank < g->n_local() ? g->rk[local_rank].ctx : nullptr; }
 const char *mi_group_last_error(mi_group *g) { return g ? g->err.c_str() : "null group"; }
 // 1 = RCCL communicator, 2 = copies inside this process (a device named twice), 3 = host-staged through shared memory
 int32_t mi_group_transport(const mi_group *g) { return !g ? 0 : g->transport; }
@@ -675,16 +500,16 @@ int32_t mi_group_transport(const mi_group *g) { return !g ? 0 : g->transport; }
 // ranks RCCL joined (ncclCommCount of this process's first communicator), 0 when the transport is not RCCL, negative on an RCCL error.
 int32_t mi_group_comm_ranks(const mi_group *g) {
     if (!g) return MI_EINVAL;
-    if (g->transport != MI_GROUP_TRANSPORT_RCCL || g->comm.empty() || !g->comm[0]) return 0;
+    if (g->transport != MI_GROUP_TRANSPORT_RCCL || g->rk.empty() || !g->rk[0].comm) return 0;
     int n = 0;
-    return ncclCommCount(g->comm[0], &n) == ncclSuccess ? n : MI_EHIP;
+    return ncclCommCount(g->rk[0].comm, &n) == ncclSuccess ? n : MI_EHIP;
 }
 // PCI bus id ("0000:c1:00.0") of the device local rank `local_rank` runs on, as the HIP runtime reports it: what tells two ranks on two
 // GPUs from two ranks on one.
 int32_t mi_group_device_pci(const mi_group *g, int local_rank, char out[32]) {
     if (!g || !out || local_rank < 0 || local_rank >= g->n_local()) return MI_EINVAL;
     out[0] = 0;
-    return hipDeviceGetPCIBusId(out, 32, g->dev[local_rank]) == hipSuccess ? MI_OK : MI_EHIP;
+    return hipDeviceGetPCIBusId(out, 32, g->rk[local_rank].dev) == hipSuccess ? MI_OK : MI_EHIP;
 }
 
 // Every local rank sends a distinct pattern of `bytes` bytes to every rank of the group (itself included) and checks what it
@@ -695,55 +520,54 @@ int32_t mi_group_exchange_selftest(mi_group *g, size_t bytes) {
     G_ENTER(g);
     const int nl = g->n_local(), W = g->world;
     std::vector<void *> sbuf(nl, nullptr), rbuf(nl, nullptr);
-    std::vector<hipStream_t> xs(nl);
     std::vector<Xfer> list;
     auto pat = [](int src, int dst, size_t k) { return (unsigned char)(17 * src + 101 * dst + 3 * k + (k >> 8)); };
-    int32_t rc = MI_OK;
     auto prepare = [&]() -> int32_t {
         for (int i = 0; i < nl; i++) {
-            (void)hipSetDevice(g->dev[i]);
+            hipStream_t xs = g->rk[i].xs;
+            (void)hipSetDevice(g->rk[i].dev);
             G_HIP(g, hipMalloc(&sbuf[i], bytes * W)); G_HIP(g, hipMalloc(&rbuf[i], bytes * W));
             std::vector<unsigned char> h(bytes * W);
             for (int d = 0; d < W; d++) for (size_t k = 0; k < bytes; k++) h[d * bytes + k] = pat(g->rank0 + i, d, k);
-            xs[i] = g->xs[i];
-            G_HIP(g, hipMemcpyAsync(sbuf[i], h.data(), h.size(), hipMemcpyHostToDevice, xs[i]));
-            G_HIP(g, hipMemsetAsync(rbuf[i], 0, bytes * W, xs[i]));
-            G_HIP(g, hipStreamSynchronize(xs[i]));
+            G_HIP(g, hipMemcpyAsync(sbuf[i], h.data(), h.size(), hipMemcpyHostToDevice, xs));
+            G_HIP(g, hipMemsetAsync(rbuf[i], 0, bytes * W, xs));
+            G_HIP(g, hipStreamSynchronize(xs));
         }
         return MI_OK;
     };
     auto verify = [&]() -> int32_t {
         for (int i = 0; i < nl; i++) {
-            (void)hipSetDevice(g->dev[i]);
+            (void)hipSetDevice(g->rk[i].dev);
             std::vector<unsigned char> h(bytes * W);
-            G_HIP(g, hipMemcpyAsync(h.data(), rbuf[i], h.size(), hipMemcpyDeviceToHost, xs[i]));
-            G_HIP(g, hipStreamSynchronize(xs[i]));
+            G_HIP(g, hipMemcpyAsync(h.data(), rbuf[i], h.size(), hipMemcpyDeviceToHost, g->rk[i].xs));
+            G_HIP(g, hipStreamSynchronize(g->rk[i].xs));
             for (int s = 0; s < W; s++) for (size_t k = 0; k < bytes; k++)
                 if (h[s * bytes + k] != pat(s, g->rank0 + i, k)) G_FAIL(g, MI_EHIP, "group: exchange self-test received wrong bytes");
         }
         return MI_OK;
     };
     auto body = [&]() -> int32_t {
-        int32_t lrc = prepare();
-        MI_TRY(group_agree(g, lrc, g->err, "while preparing the self-test"));   // a rank without buffers must not leave the others in the exchange
+        Carried st, seen;
+        st.note(prepare(), g->err);
+        MI_TRY(group_agree(g, st, "while preparing the self-test"));   // a rank without buffers must not leave the others in the exchange
         for (int s = 0; s < W; s++) for (int d = 0; d < W; d++) {
             Xfer x{s, d, nullptr, nullptr, bytes};
             if (g->local(s)) x.sp = (char *)sbuf[s - g->rank0] + (size_t)d * bytes;
             if (g->local(d)) x.dp = (char *)rbuf[d - g->rank0] + (size_t)s * bytes;
             list.push_back(x);
         }
-        MI_TRY(run_xfers(g, list, xs));
-        lrc = verify();
+        MI_TRY(run_xfers(g, list));
+        seen.note(verify(), g->err);
         // the all-gather of host values: every rank contributes (rank, 3 rank + 1) and must read that back from everyone
         std::vector<u64> mine(2 * (size_t)nl), all(2 * (size_t)W);
         for (int i = 0; i < nl; i++) { mine[2 * i] = (u64)(g->rank0 + i); mine[2 * i + 1] = 3 * (u64)(g->rank0 + i) + 1; }
         MI_TRY(group_allgather(g, mine.data(), 16, all.data()));
-        for (int r = 0; r < W && lrc == MI_OK; r++)
-            if (all[2 * r] != (u64)r || all[2 * r + 1] != 3 * (u64)r + 1) { g->err = "group: all-gather self-test received wrong values"; lrc = MI_EHIP; }
-        return group_agree(g, lrc, g->err, "in the transport self-test");
+        for (int r = 0; r < W; r++)
+            if (all[2 * r] != (u64)r || all[2 * r + 1] != 3 * (u64)r + 1) seen.note(MI_EHIP, "group: all-gather self-test received wrong values");
+        return group_agree(g, seen, "in the transport self-test");
     };
-    rc = body();
-    for (int i = 0; i < nl; i++) { (void)hipSetDevice(g->dev[i]); if (sbuf[i]) (void)hipFree(sbuf[i]); if (rbuf[i]) (void)hipFree(rbuf[i]); }
+    const int32_t rc = body();
+    for (int i = 0; i < nl; i++) { (void)hipSetDevice(g->rk[i].dev); if (sbuf[i]) (void)hipFree(sbuf[i]); if (rbuf[i]) (void)hipFree(rbuf[i]); }
     return rc;
 }
 
@@ -767,7 +591,7 @@ static int32_t exchange_prepare(mi_group *g, BucketExchange &bx, const int *slot
     for (int k = 0; k < n_slots; k++) {
         const MsmCurveOps &ops = mi_msm_ops(curves[k]);
         for (int i = 0; i < nl; i++) {
-            G_CTX(g, i, mi_msm_bucket_view(g->ctx[i], slots[k], curves[k], &bx.v[k][i]));
+            G_CTX(g, i, mi_msm_bucket_view(g->rk[i].ctx, slots[k], curves[k], &bx.v[k][i]));
             if (!bx.v[k][i].bucket) G_FAIL(g, MI_EINVAL, "group: mode 1 (bucket exchange): a rank has no bucket array for one of the MSMs");
             if (bx.v[k][i].nkeys != bx.v[k][0].nkeys || bx.v[k][i].c != bx.v[k][0].c) G_FAIL(g, MI_EINVAL, "group: the ranks disagree on the bucket layout of an MSM");
         }
@@ -776,22 +600,20 @@ static int32_t exchange_prepare(mi_group *g, BucketExchange &bx, const int *slot
         check.push_back(((uint64_t)K << 8) | bx.v[k][0].c);
     }
     for (int i = 0; i < nl; i++) {
-        (void)hipSetDevice(g->dev[i]);
-        // the previous batch's slice sums still read the buffer on xs[i]: growing it (hipFree) synchronises the device, reusing it is ordered by xs[i]
-        G_CTX(g, i, mi_reserve(g->ctx[i], g->recv[i], bx.off[n_slots] + 256));
+        (void)hipSetDevice(g->rk[i].dev);
+        // the previous batch's slice sums still read the buffer on the exchange stream: growing it (hipFree) synchronises the device, reusing it is ordered by that stream
+        G_CTX(g, i, mi_reserve(g->rk[i].ctx, g->rk[i].recv, bx.off[n_slots] + 256));
     }
     return MI_OK;
 }
 static int32_t exchange_run(mi_group *g, const BucketExchange &bx, int first, int count) {
     const int nl = g->n_local(), W = g->world;
-    int32_t local_rc = MI_OK;
-    std::string local_err;
-    auto note = [&](int32_t rc, const std::string &msg) { if (rc != MI_OK && local_rc == MI_OK) { local_rc = rc; local_err = msg; } };
+    Carried st;
     for (int i = 0; i < nl; i++) {
-        (void)hipSetDevice(g->dev[i]);
+        (void)hipSetDevice(g->rk[i].dev);
         for (int k = first; k < first + count; k++) {
-            const hipError_t e = hipStreamWaitEvent(g->xs[i], bx.v[k][i].ready, 0);
-            if (e != hipSuccess) note(MI_EHIP, std::string("hipStreamWaitEvent (bucket sums ready): ") + hipGetErrorString(e));
+            const hipError_t e = hipStreamWaitEvent(g->rk[i].xs, bx.v[k][i].ready, 0);
+            if (e != hipSuccess) st.note(MI_EHIP, std::string("hipStreamWaitEvent (bucket sums ready): ") + hipGetErrorString(e));
         }
     }
     std::vector<Xfer> list;
@@ -803,13 +625,14 @@ static int32_t exchange_run(mi_group *g, const BucketExchange &bx, int first, in
             range_of(K, W, d, lo, hi);
             Xfer x{s, d, nullptr, nullptr, (size_t)(hi - lo) * B};
             if (g->local(s)) x.sp = (const char *)bx.v[k][s - g->rank0].bucket + lo * B;
-            if (g->local(d)) x.dp = (char *)g->recv[d - g->rank0].p + bx.off[k] + (size_t)(s < d ? s : s - 1) * (hi - lo) * B;
+            if (g->local(d)) x.dp = (char *)g->rk[d - g->rank0].recv.p + bx.off[k] + (size_t)(s < d ? s : s - 1) * (hi - lo) * B;
             list.push_back(x);
         }
     }
-    MI_TRY(run_xfers(g, list, g->xs));   // a transport failure: the group is broken, nothing below matters
+    MI_TRY(run_xfers(g, list));   // a transport failure: the group is broken, nothing below matters
     for (int i = 0; i < nl; i++) {
-        (void)hipSetDevice(g->dev[i]);
+        GroupRank &rk = g->rk[i];
+        (void)hipSetDevice(rk.dev);
         for (int k = first; k < first + count; k++) {
             const MsmCurveOps &ops = mi_msm_ops(bx.curves[k]);
             const size_t K = bx.v[k][0].nkeys, B = ops.xyzz_bytes;
@@ -817,36 +640,34 @@ static int32_t exchange_run(mi_group *g, const BucketExchange &bx, int first, in
                 u64 lo, hi;
                 range_of(K, W, g->rank0 + i, lo, hi);
                 char *bk = (char *)bx.v[k][i].bucket;
-                ops.sum_slices(g->xs[i], bk + lo * B, (const char *)g->recv[i].p + bx.off[k], (u32)(W - 1), (u32)(hi - lo));
+                ops.sum_slices(rk.xs, bk + lo * B, (const char *)rk.recv.p + bx.off[k], (u32)(W - 1), (u32)(hi - lo));
                 G_HIP(g, hipGetLastError());
                 // keys of other owners: their sums live there now; here they read as infinity for the reduce
-                if (lo) G_HIP(g, hipMemsetAsync(bk, 0, lo * B, g->xs[i]));
-                if (hi < K) G_HIP(g, hipMemsetAsync(bk + hi * B, 0, (K - hi) * B, g->xs[i]));
-                G_HIP(g, hipEventRecord(g->ev_done[i], g->xs[i]));
-                G_HIP(g, hipStreamWaitEvent(bx.v[k][i].stream, g->ev_done[i], 0));
-                G_CTX(g, i, mi_msm_reduce_enqueue(g->ctx[i], bx.slots[k], bx.curves[k]));
+                if (lo) G_HIP(g, hipMemsetAsync(bk, 0, lo * B, rk.xs));
+                if (hi < K) G_HIP(g, hipMemsetAsync(bk + hi * B, 0, (K - hi) * B, rk.xs));
+                G_HIP(g, hipEventRecord(rk.ev[E_DONE], rk.xs));
+                G_HIP(g, hipStreamWaitEvent(bx.v[k][i].stream, rk.ev[E_DONE], 0));
+                G_CTX(g, i, mi_msm_reduce_enqueue(rk.ctx, bx.slots[k], bx.curves[k]));
                 return MI_OK;
             };
-            const int32_t rc = post();
-            note(rc, g->err);
+            st.note(post(), g->err);
         }
     }
-    if (local_rc != MI_OK) g->err = local_err;
-    return local_rc;
+    return st.leave(g);
 }
 
 // Whatever a failed call left on a context's MSM slots is collected (a deferred slot runs its reduce over its local buckets first), so
 // that the next call finds every slot idle.  Errors here change nothing any more.
 static void drain_slots(mi_group *g, const int *slots, const int *curves, int n) {
-    for (int i = 0; i < g->n_local(); i++) {
-        (void)hipSetDevice(g->dev[i]);
+    for (GroupRank &rk : g->rk) {
+        (void)hipSetDevice(rk.dev);
         G1X t1; G2X t2;
         for (int k = 0; k < n; k++) {
-            (void)mi_msm_reduce_enqueue(g->ctx[i], slots[k], curves[k]);
-            (void)mi_msm_finish(g->ctx[i], slots[k], curves[k], curves[k] == 1 ? (void *)&t1 : (void *)&t2);
+            (void)mi_msm_reduce_enqueue(rk.ctx, slots[k], curves[k]);
+            (void)mi_msm_finish(rk.ctx, slots[k], curves[k], curves[k] == 1 ? (void *)&t1 : (void *)&t2);
         }
-        (void)hipStreamSynchronize(g->ctx[i]->stream);
-        (void)hipStreamSynchronize(g->xs[i]);
+        (void)hipStreamSynchronize(rk.ctx->stream);
+        (void)hipStreamSynchronize(rk.xs);
     }
 }
 
@@ -859,21 +680,20 @@ static void write_jac(const XYZZ<F> &r, JacT *out) {
 }
 // runs fn(i) for every local rank, rank 0 on this thread and the others on threads of their own (an MSM enqueue waits once on the
 // host for its sort's largest bucket, msm.hip: one after the other, rank i + 1 would not even start its sort before rank i's has
-// counted); returns the first failure in rank order with its text in *err
+// counted); notes the first failure in rank order with its context's text
 template <class Fn>
-static int32_t for_each_local_rank(mi_group *g, std::string *err, Fn fn) {
+static void for_each_local_rank(mi_group *g, Carried &st, Fn fn) {
     const int nl = g->n_local();
     std::vector<int32_t> rcs((size_t)nl, MI_OK);
-    auto guarded = [&](int i) { try { (void)hipSetDevice(g->dev[i]); rcs[i] = fn(i); } catch (...) { rcs[i] = MI_ENOMEM; } };
+    auto guarded = [&](int i) { try { (void)hipSetDevice(g->rk[i].dev); rcs[i] = fn(i); } catch (...) { rcs[i] = MI_ENOMEM; } };
     std::vector<std::thread> th;
     for (int i = 1; i < nl; i++) {
         try { th.emplace_back(guarded, i); } catch (...) { guarded(i); }   // no thread to be had: in line
     }
     guarded(0);
     for (auto &t : th) t.join();
-    (void)hipSetDevice(g->dev[0]);
-    for (int i = 0; i < nl; i++) if (rcs[i] != MI_OK) { *err = mi_last_error(g->ctx[i]); return rcs[i]; }
-    return MI_OK;
+    (void)hipSetDevice(g->rk[0].dev);
+    for (int i = 0; i < nl; i++) st.note(rcs[i], mi_last_error(g->rk[i].ctx));
 }
 
 // One MSM whose (point, scalar) pairs are already spread over the local ranks' devices.
@@ -887,43 +707,33 @@ static int32_t msm_sharded_dev(mi_group *g, int curve, const void *const *pts_de
     const uint32_t df = mode == 1 ? MI_MSM_DEFER_REDUCE : 0;
     const auto t0 = std::chrono::steady_clock::now();
     const int slots[1] = {MSM_SLOT_A}, curves[1] = {curve};
-    std::string lerr;
-    int32_t lrc = for_each_local_rank(g, &lerr, [&](int i) -> int32_t {
-        mi_ctx *ctx = g->ctx[i];
+    Carried st;
+    for_each_local_rank(g, st, [&](int i) -> int32_t {
+        mi_ctx *ctx = g->rk[i].ctx;
         std::memset(&ctx->stats, 0, sizeof(ctx->stats));
         MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_T0], ctx->stream));
         return mi_msm_enqueue(ctx, MSM_SLOT_A, -1, curve, pts_dev[i], sc_dev[i], n_local[i], flags | df, ctx->ev[EV_T0], curve == 1, 0, 0, c);
     });
     BucketExchange bx;
     std::vector<uint64_t> check{(uint64_t)n_total, (uint64_t)mode, (uint64_t)flags};
-    if (mode == 1 && lrc == MI_OK) { lrc = exchange_prepare(g, bx, slots, curves, 1, check); lerr = g->err; }
-    int32_t rc = group_agree(g, lrc, lerr, "while enqueueing its share of the MSM", check.data(), (uint32_t)check.size());
-    if (rc == MI_OK && mode == 1) { lrc = exchange_run(g, bx, 0, 1); lerr = g->err; if (g->broken) rc = lrc; }
+    if (mode == 1 && st.ok()) st.note(exchange_prepare(g, bx, slots, curves, 1, check), g->err);
+    int32_t rc = group_agree(g, st, "while enqueueing its share of the MSM", check.data(), (uint32_t)check.size());
+    if (rc == MI_OK && mode == 1) { const int32_t r = exchange_run(g, bx, 0, 1); if (g->broken) rc = r; else st.note(r, g->err); }
     // the partial sums and the status of every rank in ONE all-gather: all ranks return the sum, or all return an error
-    struct Part { int32_t rc; uint32_t pad[3]; XYZZ<F> p; };
-    std::vector<Part> mine((size_t)nl), all((size_t)g->world);
+    std::vector<XYZZ<F>> mine((size_t)nl), all;
     if (rc == MI_OK) {
         for (int i = 0; i < nl; i++) {
-            (void)hipSetDevice(g->dev[i]);
-            std::memset(&mine[i], 0, sizeof(Part));
-            const int32_t r = lrc != MI_OK ? lrc : mi_msm_finish(g->ctx[i], MSM_SLOT_A, curve, &mine[i].p);
-            if (r != MI_OK && lrc == MI_OK) { lrc = r; lerr = mi_last_error(g->ctx[i]); }
-            mine[i].rc = lrc;
+            (void)hipSetDevice(g->rk[i].dev);
+            std::memset((void *)&mine[i], 0, sizeof mine[i]);
+            if (st.ok()) st.note(mi_msm_finish(g->rk[i].ctx, MSM_SLOT_A, curve, &mine[i]), mi_last_error(g->rk[i].ctx));
         }
-        rc = group_allgather(g, mine.data(), sizeof(Part), all.data());
-        if (rc == MI_OK)
-            for (int r = 0; r < g->world && rc == MI_OK; r++)
-                if (all[r].rc != MI_OK) {
-                    rc = all[r].rc;
-                    g->err = lrc != MI_OK ? lerr : std::string("group: rank ") + std::to_string(r) + " failed in its share of the MSM (status " + std::to_string(rc) + ")";
-                    if (lrc != MI_OK) rc = lrc;
-                }
+        rc = group_gather(g, st, mine, "in its share of the MSM", "", all);
     }
     if (rc != MI_OK) { const std::string keep = g->err; drain_slots(g, slots, curves, 1); g->err = keep; return rc; }
     XYZZ<F> total = XYZZ<F>::inf();
-    for (const Part &p : all) xyzz_add(total, p.p);
+    for (const XYZZ<F> &p : all) xyzz_add(total, p);
     write_jac<F>(total, out);
-    g->ctx[0]->stats.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    g->rk[0].ctx->stats.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return MI_OK;
 }
 
@@ -938,8 +748,8 @@ static int32_t msm_sharded_host(mi_group *g, int curve, const AffT *pts, const m
     for (int i = 0; i < nl; i++) {
         u64 lo, hi;
         range_of(n, g->world, i, lo, hi);
-        (void)hipSetDevice(g->dev[i]);
-        mi_ctx *ctx = g->ctx[i];
+        (void)hipSetDevice(g->rk[i].dev);
+        mi_ctx *ctx = g->rk[i].ctx;
         G_CTX(g, i, mi_reserve(ctx, ctx->ws[WS_HOST_IO0], (hi - lo) * sizeof(AffT) + 64));
         G_CTX(g, i, mi_reserve(ctx, ctx->ws[WS_HOST_IO1], (hi - lo) * sizeof(mi_fr) + 64));
         if (hi > lo) {
@@ -973,8 +783,8 @@ int32_t mi_msm_g2_sharded(mi_group *g, const mi_g2_affine *pts, const mi_fr *sca
 }
 
 // ---------------------------------------------------------------- computeH over the ranks of the group (csrc/ntt_cross.hip has the maths)
-// Data: rank r holds the natural-order slice [r M, (r + 1) M) of a, b (and c) in g->hx[0..2][local], M = N / world.  Result: the
-// coefficients of h in gnark's bit-reversed order, slice r on rank r, in g->hh[local] + 1 (slot 0 = the previous rank's last coefficient,
+// Data: rank r holds the natural-order slice [r M, (r + 1) M) of a, b (and c) in its hv[H_A], [H_B], [H_C], M = N / world.  Result: the
+// coefficients of h in gnark's bit-reversed order, slice r on rank r, in its hh + 1 (slot 0 = the previous rank's last coefficient,
 // fetched by one more batch: the Z pairs of a sharded key are cut over N - 1, so every slice but the first starts one element early).
 // Six transforms as on one device (h = den FFT^-1_coset(ca cb) - den FFT^-1(c)); each is a local size-M transform and one cross-rank
 // step between two all-to-alls over the group's transport -- 9 batches of (world - 1) / world of a slice per rank: the pair between
@@ -983,150 +793,120 @@ int32_t mi_msm_g2_sharded(mi_group *g, const mi_g2_affine *pts, const mi_fr *sca
 static bool sharded_h_possible(const mi_group *g, u32 log_n) {
     const int W = g->world;
     if (W < 2 || W > 16 || (W & (W - 1))) return false;
-    u32 lw = 0;
-    while ((1 << lw) < W) lw++;
-    return log_n >= 2 * lw && log_n <= 28;
+    return log_n >= 2 * g->log_w() && log_n <= 28;
 }
-// Seven "ready" events per local rank: a transfer waits for the ONE kernel that produced what it moves, not for whatever else has
-// been enqueued on the context's stream since -- that is what lets the next vector's arithmetic run under this vector's transfer.
-enum { E_IN, E_DA, E_DB, E_DC, E_FA, E_FB, E_MID, E_COUNT };
-// Everything compute_h_sharded allocates -- the cross-rank tables, the two exchange vectors, the h slice, the events -- for ONE local rank.
+// Everything compute_h_sharded allocates -- the cross-rank tables, the two exchange vectors, the h slice -- for ONE local rank.
 // Called in the LOCAL phase of the callers, before the group agrees to proceed: an allocation that fails here is an MI_ENOMEM
 // every rank returns with the group intact, not a null pointer under kernels and transfers the peers are already waiting for.
 static int32_t compute_h_sharded_prepare(mi_group *g, int i, u32 log_n) {
-    const int nl = g->n_local();
-    u32 log_w = 0;
-    while ((1 << log_w) < g->world) log_w++;
-    const size_t M = (size_t)1 << (log_n - log_w);
-    mi_ctx *c = g->ctx[i];
-    MI_TRY(mi_cross_tables_build(c, log_n, log_w, (u32)(g->rank0 + i), &g->xt[i]));
-    MI_TRY(mi_reserve(c, g->hy[i], M * sizeof(Fr)));
-    MI_TRY(mi_reserve(c, g->hy2[i], M * sizeof(Fr)));
-    MI_TRY(mi_reserve(c, g->hh[i], (M + 1) * sizeof(Fr)));
-    if (g->ev_r.size() != (size_t)nl * E_COUNT) MI_FAIL(c, MI_EINVAL, "sharded computeH: the group's event table was not sized at creation");
-    for (int k = 0; k < E_COUNT; k++) {   // (slots of local rank i only: local ranks prepare from their own threads)
-        hipEvent_t &e = g->ev_r[(size_t)i * E_COUNT + k];
-        if (!e) MI_CHECK_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const mi_group::HCut cut = g->h_cut(log_n);
+    GroupRank &k = g->rk[i];
+    MI_TRY(mi_cross_tables_build(k.ctx, log_n, cut.log_w, (u32)(g->rank0 + i), &k.xt));
+    MI_TRY(mi_reserve(k.ctx, k.hv[H_Y0], cut.M * sizeof(Fr)));
+    MI_TRY(mi_reserve(k.ctx, k.hv[H_Y1], cut.M * sizeof(Fr)));
+    return mi_reserve(k.ctx, k.hh, (cut.M + 1) * sizeof(Fr));
+}
+static bool compute_h_sharded_prepared(const GroupRank &k) { return k.hv[H_Y0].p && k.hv[H_Y1].p && k.hh.p && k.xt.s_fwd && k.xt.s_inv; }
+// One batch between two stream hand-overs: the exchange stream of every local rank picks up behind event `after` of its context's
+// stream, the batch runs, and with `back` the context's stream picks up behind the batch.  A hand-over that fails is a LOCAL failure:
+// noted, and the rank still takes part in the batch.  Returns the transport's status.
+static int32_t run_batch_behind(mi_group *g, const std::vector<Xfer> &list, int after, bool back, Carried &st) {
+    for (GroupRank &k : g->rk) {
+        (void)hipSetDevice(k.dev);
+        if (hipStreamWaitEvent(k.xs, k.ev[after], 0) != hipSuccess) st.note(MI_EHIP, "sharded computeH: stream hand-over failed");
+    }
+    MI_TRY(run_xfers(g, list));
+    for (GroupRank &k : g->rk) {
+        if (!back) break;
+        (void)hipSetDevice(k.dev);
+        if (hipEventRecord(k.ev[E_C1], k.xs) != hipSuccess || hipStreamWaitEvent(k.ctx->stream, k.ev[E_C1], 0) != hipSuccess) st.note(MI_EHIP, "sharded computeH: stream hand-over failed");
     }
     return MI_OK;
 }
-static bool compute_h_sharded_prepared(const mi_group *g, int i) {
-    if (g->ev_r.size() != (size_t)g->n_local() * E_COUNT || !g->hy[i].p || !g->hy2[i].p || !g->hh[i].p || !g->xt[i].s_fwd || !g->xt[i].s_inv) return false;
-    for (int k = 0; k < E_COUNT; k++) if (!g->ev_r[(size_t)i * E_COUNT + k]) return false;
-    return true;
-}
 static int32_t compute_h_sharded(mi_group *g, u32 log_n, bool derive_c) {
     const MiRange range_fn("mi.group.computeH.enqueue");
-    const int nl = g->n_local(), W = g->world;
-    u32 log_w = 0;
-    while ((1 << log_w) < W) log_w++;
-    const u32 log_m = log_n - log_w;
-    const size_t M = (size_t)1 << log_m, cnt = M >> log_w, row = cnt * sizeof(Fr);
-    int32_t lrc = MI_OK;
-    std::string lerr;
-    auto note = [&](int32_t rc, const std::string &msg) { if (rc != MI_OK && lrc == MI_OK) { lrc = rc; lerr = msg; } };
-    auto each = [&](const std::function<int32_t(int, mi_ctx *)> &fn) {
-        for (int i = 0; i < nl; i++) { (void)hipSetDevice(g->dev[i]); const int32_t rc = fn(i, g->ctx[i]); note(rc, mi_last_error(g->ctx[i])); }
+    const int W = g->world;
+    const mi_group::HCut cut = g->h_cut(log_n);
+    const u32 log_m = cut.log_m;
+    const size_t M = cut.M, row = cut.cnt * sizeof(Fr);
+    Carried st;
+    auto each = [&](const std::function<int32_t(GroupRank &, mi_ctx *)> &fn) {
+        for (GroupRank &k : g->rk) { (void)hipSetDevice(k.dev); st.note(fn(k, k.ctx), mi_last_error(k.ctx)); }
     };
     // the callers prepared every local rank and the GROUP agreed on the outcome: nothing is allocated from here on.  (A caller that skipped
     // that would have kernels and transfers run on null buffers: refused before anything is enqueued.)
-    for (int i = 0; i < nl; i++) if (!compute_h_sharded_prepared(g, i)) { g->err = "sharded computeH: buffers were not prepared before the agreement"; return MI_EINVAL; }
-    auto mark = [&](int k) {
-        for (int i = 0; i < nl; i++) {
-            (void)hipSetDevice(g->dev[i]);
-            hipEvent_t e = g->ev_r[(size_t)i * E_COUNT + k];
-            if (!e || hipEventRecord(e, g->ctx[i]->stream) != hipSuccess) note(MI_EHIP, "sharded computeH: hipEventRecord failed");
-        }
+    for (const GroupRank &k : g->rk) if (!compute_h_sharded_prepared(k)) { g->err = "sharded computeH: buffers were not prepared before the agreement"; return MI_EINVAL; }
+    auto mark = [&](int ev, const char *what = "sharded computeH: hipEventRecord failed") {
+        for (GroupRank &k : g->rk) { (void)hipSetDevice(k.dev); if (hipEventRecord(k.ev[ev], k.ctx->stream) != hipSuccess) st.note(MI_EHIP, what); }
     };
     // all-to-all: block d of the source rank's buffer -> block s of rank d's buffer (the same rule in both directions); the exchange
     // streams pick up behind event `after` of their context's stream and hand back to it when the batch is done
-    auto a2a = [&](std::vector<DevBuf> &from, std::vector<DevBuf> &to, int after) -> int32_t {
+    auto a2a = [&](int from, int to, int after) -> int32_t {
         std::vector<Xfer> list;
         for (int s = 0; s < W; s++) for (int d = 0; d < W; d++) {
             Xfer x{s, d, nullptr, nullptr, row};
-            if (g->local(s)) x.sp = (const char *)from[s - g->rank0].p + (size_t)d * row;
-            if (g->local(d)) x.dp = (char *)to[d - g->rank0].p + (size_t)s * row;
+            if (g->local(s)) x.sp = (const char *)g->rk[s - g->rank0].hv[from].p + (size_t)d * row;
+            if (g->local(d)) x.dp = (char *)g->rk[d - g->rank0].hv[to].p + (size_t)s * row;
             list.push_back(x);
         }
-        for (int i = 0; i < nl; i++) {
-            (void)hipSetDevice(g->dev[i]);
-            hipEvent_t e = g->ev_r[(size_t)i * E_COUNT + after];
-            if (!e || hipStreamWaitEvent(g->xs[i], e, 0) != hipSuccess) note(MI_EHIP, "sharded computeH: stream hand-over failed");
-        }
-        MI_TRY(run_xfers(g, list, g->xs));
-        for (int i = 0; i < nl; i++) {
-            (void)hipSetDevice(g->dev[i]);
-            if (hipEventRecord(g->ev_c1[i], g->xs[i]) != hipSuccess || hipStreamWaitEvent(g->ctx[i]->stream, g->ev_c1[i], 0) != hipSuccess) note(MI_EHIP, "sharded computeH: stream hand-over failed");
-        }
-        return MI_OK;
+        return run_batch_behind(g, list, after, true, st);
     };
     // the pieces of a transform (csrc/ntt_cross.hip header): cross-rank step of FFTInverse on the columns in Y; local size-M FFTInverse;
     // coset factor + local size-M FFT (DIT) of a coefficient slice
-    auto cross_inv = [&](std::vector<DevBuf> &Y, bool den_scale) { each([&](int i, mi_ctx *c) { return mi_cross_dft(c, c->stream, Y[i].p, g->xt[i], 0, den_scale); }); };
-    auto local_inv = [&](std::vector<DevBuf> &X) { each([&](int i, mi_ctx *c) { return mi_ntt_dev_impl(c, (mi_fr *)X[i].p, log_m, MI_NTT_INVERSE); }); };
-    auto local_fwd = [&](std::vector<DevBuf> &X) {
-        each([&](int i, mi_ctx *c) -> int32_t {
-            MI_TRY(mi_cross_mul(c, c->stream, X[i].p, X[i].p, g->xt[i].s_fwd, nullptr, M));
-            return mi_ntt_dev_impl(c, (mi_fr *)X[i].p, log_m, MI_NTT_DIT);
+    auto cross_inv = [&](int Y, bool den_scale) { each([&](GroupRank &k, mi_ctx *c) { return mi_cross_dft(c, c->stream, k.hv[Y].p, k.xt, 0, den_scale); }); };
+    auto local_inv = [&](int X) { each([&](GroupRank &k, mi_ctx *c) { return mi_ntt_dev_impl(c, (mi_fr *)k.hv[X].p, log_m, MI_NTT_INVERSE); }); };
+    auto local_fwd = [&](int X) {
+        each([&](GroupRank &k, mi_ctx *c) -> int32_t {
+            MI_TRY(mi_cross_mul(c, c->stream, k.hv[X].p, k.hv[X].p, k.xt.s_fwd, nullptr, M));
+            return mi_ntt_dev_impl(c, (mi_fr *)k.hv[X].p, log_m, MI_NTT_DIT);
         });
     };
-    std::vector<DevBuf> &Xa = g->hx[0], &Xb = g->hx[1], &Xc = g->hx[2], &Y0 = g->hy, &Y1 = g->hy2;
     // The six transforms, interleaved so that a batch of the transport moves one vector while the kernels of another run (a batch
     // blocks this thread until it is complete -- the transports' deadline rule -- so what should overlap it is enqueued BEFORE it):
     //   FFTInverse(a), (b), (c) = [rows -> columns] cross-rank step [columns -> rows] local transform;  FFT_coset(a), (b) = factor, local
     //   transform [rows -> columns];  then the middle kernel (cross-rank steps of a and b, product, cross-rank step of the last
     //   FFTInverse: the all-to-all pair in between cancels)  [columns -> rows]  local transform.   9 batches.
-    if (derive_c) each([&](int i, mi_ctx *c) { return mi_cross_mul(c, c->stream, Xc[i].p, Xa[i].p, Xb[i].p, nullptr, M); });
+    if (derive_c) each([&](GroupRank &k, mi_ctx *c) { return mi_cross_mul(c, c->stream, k.hv[H_C].p, k.hv[H_A].p, k.hv[H_B].p, nullptr, M); });
     mark(E_IN);
-    MI_TRY(a2a(Xa, Y0, E_IN));
-    cross_inv(Y0, false); mark(E_DA);
-    MI_TRY(a2a(Xb, Y1, E_IN));                 // under a's cross-rank step
-    cross_inv(Y1, false); mark(E_DB);
-    MI_TRY(a2a(Y0, Xa, E_DA));                 // under b's cross-rank step
-    local_inv(Xa); local_fwd(Xa); mark(E_FA);
-    MI_TRY(a2a(Xc, Y0, E_IN));                 // under a's two local transforms
-    cross_inv(Y0, true); mark(E_DC);           // den * coefficients of c
-    MI_TRY(a2a(Y1, Xb, E_DB));
-    local_inv(Xb); local_fwd(Xb); mark(E_FB);
-    MI_TRY(a2a(Y0, Xc, E_DC));                 // under b's two local transforms
-    local_inv(Xc);
-    MI_TRY(a2a(Xa, Y0, E_FA));                 // under c's local transform
-    MI_TRY(a2a(Xb, Y1, E_FB));
-    each([&](int i, mi_ctx *c) { return mi_cross_mid(c, c->stream, Y0[i].p, Y1[i].p, g->xt[i]); });
+    MI_TRY(a2a(H_A, H_Y0, E_IN));
+    cross_inv(H_Y0, false); mark(E_DA);
+    MI_TRY(a2a(H_B, H_Y1, E_IN));               // under a's cross-rank step
+    cross_inv(H_Y1, false); mark(E_DB);
+    MI_TRY(a2a(H_Y0, H_A, E_DA));               // under b's cross-rank step
+    local_inv(H_A); local_fwd(H_A); mark(E_FA);
+    MI_TRY(a2a(H_C, H_Y0, E_IN));               // under a's two local transforms
+    cross_inv(H_Y0, true); mark(E_DC);          // den * coefficients of c
+    MI_TRY(a2a(H_Y1, H_B, E_DB));
+    local_inv(H_B); local_fwd(H_B); mark(E_FB);
+    MI_TRY(a2a(H_Y0, H_C, E_DC));               // under b's two local transforms
+    local_inv(H_C);
+    MI_TRY(a2a(H_A, H_Y0, E_FA));               // under c's local transform
+    MI_TRY(a2a(H_B, H_Y1, E_FB));
+    each([&](GroupRank &k, mi_ctx *c) { return mi_cross_mid(c, c->stream, k.hv[H_Y0].p, k.hv[H_Y1].p, k.xt); });
     mark(E_MID);
-    MI_TRY(a2a(Y0, Xa, E_MID));
-    local_inv(Xa);
+    MI_TRY(a2a(H_Y0, H_A, E_MID));
+    local_inv(H_A);
     // h = den g^-k (.) - den c_k, into the h slice behind its front slot
-    each([&](int i, mi_ctx *c) { return mi_cross_mul(c, c->stream, (char *)g->hh[i].p + sizeof(Fr), g->hx[0][i].p, g->xt[i].s_inv, g->hx[2][i].p, M); });
-    {   // every rank's last coefficient -> the front slot of the next rank
-        std::vector<Xfer> list;
-        for (int r = 0; r + 1 < W; r++) {
-            Xfer x{r, r + 1, nullptr, nullptr, sizeof(Fr)};
-            if (g->local(r)) x.sp = (const char *)g->hh[r - g->rank0].p + M * sizeof(Fr);
-            if (g->local(r + 1)) x.dp = g->hh[r + 1 - g->rank0].p;
-            list.push_back(x);
-        }
-        for (int i = 0; i < nl; i++) {
-            (void)hipSetDevice(g->dev[i]);
-            if (hipEventRecord(g->ev_c0[i], g->ctx[i]->stream) != hipSuccess || hipStreamWaitEvent(g->xs[i], g->ev_c0[i], 0) != hipSuccess) note(MI_EHIP, "sharded computeH: stream hand-over failed");
-        }
-        MI_TRY(run_xfers(g, list, g->xs));
-        for (int i = 0; i < nl; i++) {
-            (void)hipSetDevice(g->dev[i]);
-            if (hipEventRecord(g->ev_c1[i], g->xs[i]) != hipSuccess || hipStreamWaitEvent(g->ctx[i]->stream, g->ev_c1[i], 0) != hipSuccess) note(MI_EHIP, "sharded computeH: stream hand-over failed");
-        }
+    each([&](GroupRank &k, mi_ctx *c) { return mi_cross_mul(c, c->stream, (char *)k.hh.p + sizeof(Fr), k.hv[H_A].p, k.xt.s_inv, k.hv[H_C].p, M); });
+    std::vector<Xfer> last;   // every rank's last coefficient -> the front slot of the next rank
+    for (int r = 0; r + 1 < W; r++) {
+        Xfer x{r, r + 1, nullptr, nullptr, sizeof(Fr)};
+        if (g->local(r)) x.sp = (const char *)g->rk[r - g->rank0].hh.p + M * sizeof(Fr);
+        if (g->local(r + 1)) x.dp = g->rk[r + 1 - g->rank0].hh.p;
+        last.push_back(x);
     }
-    if (lrc != MI_OK) g->err = lerr;
-    return lrc;
+    mark(E_C0, "sharded computeH: stream hand-over failed");
+    MI_TRY(run_batch_behind(g, last, E_C0, true, st));
+    return st.leave(g);
 }
-// fills g->hx[which][i] with local rank i's slice of a vector of n_valid elements: rows [r M, (r + 1) M), zero beyond n_valid.
+// fills hv[which] of local rank i with its slice of a vector of n_valid elements: rows [r M, (r + 1) M), zero beyond n_valid.
 // src: host (whole vector) or device (THIS rank's slice, i.e. the elements [r M, min((r + 1) M, n_valid)))
 static int32_t load_h_slice(mi_group *g, int i, int which, u32 log_m, const mi_fr *src, bool host_whole, size_t n_valid, hipStream_t st) {
-    mi_ctx *c = g->ctx[i];
+    mi_ctx *c = g->rk[i].ctx;
     const size_t M = (size_t)1 << log_m, lo = (size_t)(g->rank0 + i) * M;
     const size_t have = n_valid > lo ? (n_valid - lo < M ? n_valid - lo : M) : 0;
-    MI_TRY(mi_reserve(c, g->hx[which][i], M * sizeof(Fr)));
-    char *dst = (char *)g->hx[which][i].p;
+    MI_TRY(mi_reserve(c, g->rk[i].hv[which], M * sizeof(Fr)));
+    char *dst = (char *)g->rk[i].hv[which].p;
     if (have) {
         if (!src) MI_FAIL(c, MI_EINVAL, "sharded computeH: null input vector");
         if (host_whole) MI_CHECK_HIP(c, hipMemcpyAsync(dst, src + lo, have * sizeof(Fr), hipMemcpyHostToDevice, st));
@@ -1149,45 +929,44 @@ int32_t mi_compute_h_sharded_dev(mi_group *g, uint32_t log_n, const mi_fr *const
                                  size_t n_constraints, mi_fr *const *h_sl) {
     if (!g || !a_sl || !b_sl || !h_sl) return MI_EINVAL;
     G_ENTER(g);
-    int32_t lrc = MI_OK;
-    std::string lerr;
-    const bool ok_shape = sharded_h_possible(g, log_n) && n_constraints <= ((size_t)1 << log_n);
-    if (!ok_shape) { lrc = MI_EINVAL; lerr = "sharded computeH: needs 2, 4, 8 or 16 ranks, N >= ranks^2 and n_constraints <= N"; }
-    u32 log_w = 0;
-    while ((1 << log_w) < g->world) log_w++;
-    const u32 log_m = log_n - log_w;
-    for (int i = 0; i < g->n_local() && lrc == MI_OK; i++) {
-        (void)hipSetDevice(g->dev[i]);
-        mi_ctx *c = g->ctx[i];
-        int32_t rc = load_h_slice(g, i, 0, log_m, a_sl[i], false, n_constraints, c->stream);
-        if (rc == MI_OK) rc = load_h_slice(g, i, 1, log_m, b_sl[i], false, n_constraints, c->stream);
-        if (rc == MI_OK) rc = c_sl ? load_h_slice(g, i, 2, log_m, c_sl[i], false, n_constraints, c->stream) : mi_reserve(c, g->hx[2][i], sizeof(Fr) << log_m);
+    Carried st;
+    if (!sharded_h_possible(g, log_n) || n_constraints > ((size_t)1 << log_n)) st.note(MI_EINVAL, "sharded computeH: needs 2, 4, 8 or 16 ranks, N >= ranks^2 and n_constraints <= N");
+    const u32 log_m = log_n - g->log_w();   // (meaningless where the shape was refused: nothing below uses it then)
+    for (int i = 0; i < g->n_local() && st.ok(); i++) {
+        (void)hipSetDevice(g->rk[i].dev);
+        mi_ctx *c = g->rk[i].ctx;
+        int32_t rc = load_h_slice(g, i, H_A, log_m, a_sl[i], false, n_constraints, c->stream);
+        if (rc == MI_OK) rc = load_h_slice(g, i, H_B, log_m, b_sl[i], false, n_constraints, c->stream);
+        if (rc == MI_OK) rc = c_sl ? load_h_slice(g, i, H_C, log_m, c_sl[i], false, n_constraints, c->stream) : mi_reserve(c, g->rk[i].hv[H_C], sizeof(Fr) << log_m);
         if (rc == MI_OK) rc = compute_h_sharded_prepare(g, i, log_n);   // every buffer of the collective exists BEFORE the ranks agree to enter it
-        if (rc != MI_OK) { lrc = rc; lerr = mi_last_error(c); }
+        st.note(rc, mi_last_error(c));
     }
     const uint64_t check[3] = {log_n, (uint64_t)n_constraints, c_sl ? 1u : 0u};
-    MI_TRY(group_agree(g, lrc, lerr, "while loading its slices for computeH", check, 3));
-    lrc = compute_h_sharded(g, log_n, c_sl == nullptr);
-    if (g->broken) return lrc;
-    lerr = g->err;
-    for (int i = 0; i < g->n_local() && lrc == MI_OK; i++) {
-        (void)hipSetDevice(g->dev[i]);
-        mi_ctx *c = g->ctx[i];
-        hipError_t e = hipMemcpyAsync(h_sl[i], (const char *)g->hh[i].p + sizeof(Fr), sizeof(Fr) << log_m, hipMemcpyDeviceToDevice, c->stream);
+    MI_TRY(group_agree(g, st, "while loading its slices for computeH", check, 3));
+    const int32_t rc = compute_h_sharded(g, log_n, c_sl == nullptr);
+    if (g->broken) return rc;
+    st.note(rc, g->err);
+    for (int i = 0; i < g->n_local() && st.ok(); i++) {
+        (void)hipSetDevice(g->rk[i].dev);
+        mi_ctx *c = g->rk[i].ctx;
+        hipError_t e = hipMemcpyAsync(h_sl[i], (const char *)g->rk[i].hh.p + sizeof(Fr), sizeof(Fr) << log_m, hipMemcpyDeviceToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { lrc = MI_EHIP; lerr = std::string("sharded computeH: copying h out failed: ") + hipGetErrorString(e); }
+        if (e != hipSuccess) st.note(MI_EHIP, std::string("sharded computeH: copying h out failed: ") + hipGetErrorString(e));
     }
-    return group_agree(g, lrc, lerr, "in the sharded computeH");
+    return group_agree(g, st, "in the sharded computeH");
 }
 }  // extern "C"
 
 // ---------------------------------------------------------------- sharded proving key
+static void pk_sharded_release(mi_group *g, mi_pk_sharded *spk) {
+    for (size_t i = 0; i < spk->part.size(); i++) if (spk->part[i]) { (void)hipSetDevice(g->rk[i].dev); mi_pk_free(g->rk[i].ctx, spk->part[i]); }
+    delete spk;
+}
 int32_t mi_pk_sharded_free(mi_group *g, mi_pk_sharded *spk) {
     if (!g || !spk) return MI_EINVAL;
     GroupCall call__(g);
     if (!call__.ok) return MI_EINVAL;   // (a broken group still frees its keys)
-    for (size_t i = 0; i < spk->part.size(); i++) if (spk->part[i]) { (void)hipSetDevice(g->dev[i]); mi_pk_free(g->ctx[i], spk->part[i]); }
-    delete spk;
+    pk_sharded_release(g, spk);
     return MI_OK;
 }
 
@@ -1203,15 +982,13 @@ static int32_t pk_load_sharded_impl(mi_group *g, const mi_pk_desc *descs, bool d
     const mi_pk_desc *d = descs;
     const int nl = g->n_local(), W = g->world;
     {   // the header every process passes must be acceptable AND the same everywhere before anything collective starts
-        int32_t lrc = MI_OK;
-        std::string lerr;
-        if (d->log_n > 28 || !d->infinity_a || !d->infinity_b || d->nb_public > d->nb_wires) { lrc = MI_EINVAL; lerr = "pk: bad header"; }
-        if (lrc == MI_OK && device_points) for (int i = 1; i < nl; i++)
-            if (descs[i].log_n != d->log_n || descs[i].nb_wires != d->nb_wires || descs[i].nb_public != d->nb_public || !descs[i].infinity_a || !descs[i].infinity_b) {
-                lrc = MI_EINVAL; lerr = "pk: the per-rank descriptors disagree on the key's header";
-            }
+        Carried st;
+        if (d->log_n > 28 || !d->infinity_a || !d->infinity_b || d->nb_public > d->nb_wires) st.note(MI_EINVAL, "pk: bad header");
+        if (st.ok() && device_points) for (int i = 1; i < nl; i++)
+            if (descs[i].log_n != d->log_n || descs[i].nb_wires != d->nb_wires || descs[i].nb_public != d->nb_public || !descs[i].infinity_a || !descs[i].infinity_b)
+                st.note(MI_EINVAL, "pk: the per-rank descriptors disagree on the key's header");
         const uint64_t check[4] = {d->log_n, d->nb_wires, d->nb_public, lead_share_of(g)};   // (the lead's wire share must be the same on every rank)
-        MI_TRY(group_agree(g, lrc, lerr, "while checking the key's header", check, 4));
+        MI_TRY(group_agree(g, st, "while checking the key's header", check, 4));
     }
     const u64 N = (u64)1 << d->log_n;
     mi_pk_sharded *spk = new (std::nothrow) mi_pk_sharded();
@@ -1233,13 +1010,13 @@ static int32_t pk_load_sharded_impl(mi_group *g, const mi_pk_desc *descs, bool d
     // ONE fixed-base plan for all parts (mode 1 exchanges buckets, so the parts must cut their scalars alike; and a part just under the
     // 2^20-point threshold next to one just over it would otherwise pick different paths): mi_pk_load's rule (fixed_base_plan) for the LARGEST part
     // and the tightest device OF THE WHOLE GROUP (the budgets are all-gathered), handed to every part.  Knobs the caller set are kept.
-    auto fail = [&](int32_t rc) { for (size_t i = 0; i < spk->part.size(); i++) if (spk->part[i]) { (void)hipSetDevice(g->dev[i]); mi_pk_free(g->ctx[i], spk->part[i]); } delete spk; return rc; };
+    auto fail = [&](int32_t rc) { pk_sharded_release(g, spk); return rc; };
     std::vector<u64> budgets(nl, 0);
     for (int i = 0; i < nl; i++) {
-        (void)hipSetDevice(g->dev[i]);
+        (void)hipSetDevice(g->rk[i].dev);
         size_t fr = 0, tot = 0, sharers = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = 0;
-        for (int j = 0; j < nl; j++) sharers += g->dev[j] == g->dev[i] ? 1 : 0;
+        for (const GroupRank &o : g->rk) sharers += o.dev == g->rk[i].dev ? 1 : 0;
         budgets[i] = fr / 3 / sharers;
     }
     u64 bmin = 0, bmax = 0, smin = 0, smax = 0;
@@ -1247,19 +1024,14 @@ static int32_t pk_load_sharded_impl(mi_group *g, const mi_pk_desc *descs, bool d
     if (rc != MI_OK) return fail(rc);
     const u32 automatic[3] = {0, 0, 0};
     const FixedBasePlan plan = fixed_base_plan(automatic, bmin, largest[KEY_AK], largest[KEY_B], largest[KEY_Z]);
-    std::vector<int32_t> rcs(nl, MI_OK);
-    std::vector<std::thread> th;
-    for (int i = 0; i < nl; i++) th.emplace_back([&, i] {   // uploads (and table builds) of the parts run side by side, one host thread per device
-        (void)hipSetDevice(g->dev[i]);
-        mi_ctx *ctx = g->ctx[i];
+    Carried loaded;
+    for_each_local_rank(g, loaded, [&](int i) {   // uploads (and table builds) of the parts run side by side, one host thread per device
         ShardRange sr;
         wire_range_of(d->nb_wires, W, g->rank0 + i, share, sr.w_lo, sr.w_hi); range_of(N - 1, W, g->rank0 + i, sr.z_lo, sr.z_hi);
-        rcs[i] = mi_pk_load_range(ctx, device_points ? &descs[i] : d, &spk->part[i], device_points, &sr, &plan);
+        return mi_pk_load_range(g->rk[i].ctx, device_points ? &descs[i] : d, &spk->part[i], device_points, &sr, &plan);
     });
-    for (auto &t : th) t.join();
     // every process reaches the agreement below even when a local part failed (a collective that only some ranks enter would hang)
-    int32_t first_bad = MI_OK;
-    for (int i = 0; i < nl; i++) if (rcs[i] != MI_OK && first_bad == MI_OK) { g->err = mi_last_error(g->ctx[i]); first_bad = rcs[i]; }
+    const int32_t first_bad = loaded.leave(g);
     // all parts on the same plan?  (a part whose tables could not be allocated after all fell back to the generic path by itself)
     std::vector<u64> sig(nl, 0);
     for (int i = 0; i < nl; i++) {
@@ -1286,217 +1058,220 @@ static int32_t pk_load_sharded_impl(mi_group *g, const mi_pk_desc *descs, bool d
 // of every rank's status and five partial sums.
 // abc_sl (may be null): per LOCAL rank device pointers to its rows of a, b, c (abc_sl[2] == null: c = a o b): computeH runs over the ranks
 // (compute_h_sharded); so it does for host arrays when the group asks for it (mi_group_set_sharded_compute_h) and the shape allows.
-static int32_t prove_sharded_impl(mi_group *g, mi_pk_sharded *spk, bool host, const mi_fr *W_host, const mi_fr *const *W_dev, size_t n_wires,
-                                  const mi_fr *a, const mi_fr *b, const mi_fr *c, size_t n_constraints, const mi_fr *r_m, const mi_fr *s_m,
-                                  uint32_t mode, mi_proof_out *out, mi_stats *stats, const mi_fr *const *const *abc_sl = nullptr) {
-    const MiRange range_fn("mi.group.prove");
-    if (!g || !spk || !out) return MI_EINVAL;
-    const int nl = g->n_local(), W = g->world;
-    if ((nl != W && nl != 1) || (int)spk->part.size() != nl) G_FAIL(g, MI_EINVAL, "group: a process holds either all ranks or exactly one");
-    static const int slots[5] = {MSM_SLOT_A, MSM_SLOT_B1, MSM_SLOT_B2, MSM_SLOT_K, MSM_SLOT_Z}, curves[5] = {1, 1, 2, 1, 1};   // the same order on every rank
-    const bool lead_here = g->rank0 == 0;   // global rank 0 runs computeH and owns a, b, c
-    const size_t N = (size_t)1 << spk->log_n;
-    const auto t_begin = std::chrono::steady_clock::now();
-    const size_t cb = n_constraints * sizeof(mi_fr);
-    const bool defer = mode == 1;
-    const bool use_sh = (abc_sl != nullptr || (host && g->sharded_h)) && sharded_h_possible(g, spk->log_n);
-    u32 log_w = 0;
-    while ((1 << log_w) < W) log_w++;
-    // ---- local phase 1.  Nothing returns from here on without the group having agreed on it (a process that left alone would leave
-    //      the others waiting in the next exchange): failures are noted and carried to the agreement.
-    int32_t lrc = MI_OK;
-    std::string lerr;
-    auto note = [&](int32_t rc, const std::string &msg) { if (rc != MI_OK && lrc == MI_OK) { lrc = rc; lerr = msg; } };
-    if (!r_m || !s_m || mode > 1 || (host ? (!W_host && n_wires) : !W_dev)) note(MI_EINVAL, "prove: null argument or unknown mode");
-    if (abc_sl && !use_sh) note(MI_EINVAL, "prove: row slices of a, b, c need computeH over the ranks: 2, 4, 8 or 16 ranks and N >= ranks^2");
-    if (abc_sl && (!abc_sl[0] || !abc_sl[1])) note(MI_EINVAL, "prove: null slice arrays");
-    if (!abc_sl && (lead_here || use_sh) && (!a || !b) && n_constraints)
-        note(MI_EINVAL, use_sh ? "prove: with computeH over the ranks every process passes a and b" : "prove: the process that holds rank 0 must pass a and b");
-    if (use_sh && n_constraints > N) note(MI_EINVAL, "prove: witness size does not match the proving key");
-    if (n_wires != spk->nb_wires || (lead_here && n_constraints > N)) note(MI_EINVAL, "prove: witness size does not match the proving key");
-    if (mode == 1 && !spk->uniform) note(MI_EINVAL, "group: mode 1 needs every part of the key to use the same MSM plan");
+struct ShardedProve {   // the arguments of one call, what follows from them, and the call's carried status
+    mi_group *g; mi_pk_sharded *spk; bool host; const mi_fr *W_host; const mi_fr *const *W_dev; size_t n_wires;
+    const mi_fr *a, *b, *c; size_t n_constraints; const mi_fr *r_m, *s_m; uint32_t mode; const mi_fr *const *const *abc_sl;
+    bool lead_here = false, use_sh = false, defer = false;   // global rank 0 (it runs computeH and owns a, b, c) is here; computeH runs over the ranks; mode 1
+    size_t N = 0, cb = 0;
+    std::chrono::steady_clock::time_point t_begin;
+    Carried st;
+};
+static const int PROVE_SLOTS[5] = {MSM_SLOT_A, MSM_SLOT_B1, MSM_SLOT_B2, MSM_SLOT_K, MSM_SLOT_Z}, PROVE_CURVES[5] = {1, 1, 2, 1, 1};   // the same order on every rank
+
+// ---- local phase 1.  Nothing returns from here on without the group having agreed on it (a process that left alone would leave
+//      the others waiting in the next exchange): failures are noted and carried to the agreement.
+static void prove_check_and_reserve(ShardedProve &p) {
+    mi_group *g = p.g; Carried &st = p.st;
+    const bool use_sh = p.use_sh, lead_here = p.lead_here;
+    if (!p.r_m || !p.s_m || p.mode > 1 || (p.host ? (!p.W_host && p.n_wires) : !p.W_dev)) st.note(MI_EINVAL, "prove: null argument or unknown mode");
+    if (p.abc_sl && !use_sh) st.note(MI_EINVAL, "prove: row slices of a, b, c need computeH over the ranks: 2, 4, 8 or 16 ranks and N >= ranks^2");
+    if (p.abc_sl && (!p.abc_sl[0] || !p.abc_sl[1])) st.note(MI_EINVAL, "prove: null slice arrays");
+    if (!p.abc_sl && (lead_here || use_sh) && (!p.a || !p.b) && p.n_constraints)
+        st.note(MI_EINVAL, use_sh ? "prove: with computeH over the ranks every process passes a and b" : "prove: the process that holds rank 0 must pass a and b");
+    if (use_sh && p.n_constraints > p.N) st.note(MI_EINVAL, "prove: witness size does not match the proving key");
+    if (p.n_wires != p.spk->nb_wires || (lead_here && p.n_constraints > p.N)) st.note(MI_EINVAL, "prove: witness size does not match the proving key");
+    if (p.mode == 1 && !p.spk->uniform) st.note(MI_EINVAL, "group: mode 1 needs every part of the key to use the same MSM plan");
     // (mi_group_wire_range answers with the group's CURRENT share: a caller of the _dev entry points would cut W unlike the key's parts)
-    if (lead_share_of(g) != spk->lead_share) note(MI_EINVAL, "group: the lead's wire share (mi_group_set_lead_share) changed since this key was loaded: reload the key");
+    if (lead_share_of(g) != p.spk->lead_share) st.note(MI_EINVAL, "group: the lead's wire share (mi_group_set_lead_share) changed since this key was loaded: reload the key");
     // workspaces, each on its own device: W slice (+ a, b, c on the lead) for host inputs; h (whole on the lead, a slice elsewhere)
-    for (int i = 0; i < nl && lrc == MI_OK; i++) {
-        (void)hipSetDevice(g->dev[i]);
-        mi_ctx *ctx = g->ctx[i];
-        mi_pk *pk = spk->part[i];
+    for (int i = 0; i < g->n_local() && st.ok(); i++) {
+        (void)hipSetDevice(g->rk[i].dev);
+        mi_ctx *ctx = g->rk[i].ctx;
+        mi_pk *pk = p.spk->part[i];
         const bool lead = g->rank0 + i == 0;
         std::memset(&ctx->stats, 0, sizeof(ctx->stats));
         int32_t rc = MI_OK;
-        if (host) rc = mi_reserve(ctx, ctx->ws[WS_PROVE_IN], pk->nb_wires * sizeof(mi_fr) + (lead && !use_sh ? 3 * cb : 0) + 128);
-        if (rc == MI_OK && !use_sh) rc = mi_reserve(ctx, ctx->ws[WS_H], (lead ? N : pk->n_z_msm + 1) * sizeof(Fr));
-        note(rc, mi_last_error(ctx));
+        if (p.host) rc = mi_reserve(ctx, ctx->ws[WS_PROVE_IN], pk->nb_wires * sizeof(mi_fr) + (lead && !use_sh ? 3 * p.cb : 0) + 128);
+        if (rc == MI_OK && !use_sh) rc = mi_reserve(ctx, ctx->ws[WS_H], (lead ? p.N : pk->n_z_msm + 1) * sizeof(Fr));
+        st.note(rc, mi_last_error(ctx));
     }
-    // every local rank: its slice of W, its wire MSMs; the lead also a, b, c, computeH and its own Z MSM.  One host thread per rank:
-    // enqueueing the wire MSMs waits once for the count pass of their sorts (msm.hip, MI_MSM_EXACT_SIZE)
-    auto rank_main = [&](int i) -> int32_t {
-        mi_ctx *ctx = g->ctx[i];
-        mi_pk *pk = spk->part[i];
-        hipEvent_t *ev = ctx->ev;
-        const bool lead = g->rank0 + i == 0;
-        const size_t wb = pk->nb_wires * sizeof(mi_fr);
-        const mi_fr *Wd = host ? (const mi_fr *)ctx->ws[WS_PROVE_IN].p : W_dev[i];
-        if (!Wd && wb) MI_FAIL(ctx, MI_EINVAL, "prove: null wire slice");
-        // host inputs: pageable copies on the context's copy stream (which carries nothing else), ordered by synchronising it on this
-        // thread -- no event between two of them (prove.hip, pool.hip: a marker slows every copy behind it)
-        const auto t_up = std::chrono::steady_clock::now();
-        hipStream_t cps = nullptr;
-        if (host) MI_TRY(mi_copy_stream(ctx, &cps));
-        if (host && wb) {
-            MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)Wd, W_host + pk->wire_lo, wb, hipMemcpyHostToDevice, cps));
+}
+// Local rank i: its slice of W, its wire MSMs; the lead also a, b, c, computeH and its own Z MSM.  One host thread per rank:
+// enqueueing the wire MSMs waits once for the count pass of their sorts (msm.hip, MI_MSM_EXACT_SIZE)
+static int32_t prove_rank_local(const ShardedProve &p, int i) {
+    mi_group *g = p.g;
+    mi_ctx *ctx = g->rk[i].ctx; mi_pk *pk = p.spk->part[i];
+    hipEvent_t *ev = ctx->ev;
+    const bool lead = g->rank0 + i == 0, host = p.host;
+    const size_t wb = pk->nb_wires * sizeof(mi_fr), cb = p.cb;
+    const mi_fr *Wd = host ? (const mi_fr *)ctx->ws[WS_PROVE_IN].p : p.W_dev[i];
+    if (!Wd && wb) MI_FAIL(ctx, MI_EINVAL, "prove: null wire slice");
+    // host inputs: pageable copies on the context's copy stream (which carries nothing else), ordered by synchronising it on this
+    // thread -- no event between two of them (prove.hip, pool.hip: a marker slows every copy behind it)
+    const auto t_up = std::chrono::steady_clock::now();
+    hipStream_t cps = nullptr;
+    if (host) MI_TRY(mi_copy_stream(ctx, &cps));
+    if (host && wb) {
+        MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)Wd, p.W_host + pk->wire_lo, wb, hipMemcpyHostToDevice, cps));
+        MI_CHECK_HIP(ctx, hipStreamSynchronize(cps));
+    }
+    MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_W_READY], ctx->stream));
+    MI_TRY(mi_prove_enqueue_wire_msms(ctx, pk, Wd, ev[EV_W_READY], p.defer));
+    if (p.use_sh) {   // this rank's rows of a, b (, c) into the group's slice vectors; computeH itself is a collective and follows the agreement
+        const mi_fr *const *const *abc_sl = p.abc_sl;
+        const u32 log_m = pk->log_n - g->log_w();
+        MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_PROVE_BEGIN], ctx->stream));
+        for (int which = 0; which < 3; which++) {
+            const mi_fr *src = abc_sl ? (abc_sl[which] ? abc_sl[which][i] : nullptr) : (which == 0 ? p.a : which == 1 ? p.b : p.c);
+            const bool given = abc_sl ? abc_sl[which] != nullptr : src != nullptr;
+            if (which == H_C && !given) { MI_TRY(mi_reserve(ctx, g->rk[i].hv[H_C], sizeof(Fr) << log_m)); continue; }
+            MI_TRY(load_h_slice(g, i, which, log_m, src, !abc_sl, p.n_constraints, abc_sl ? ctx->stream : cps));
+        }
+        if (!abc_sl) MI_CHECK_HIP(ctx, hipStreamSynchronize(cps));   // (grown buffers: hipFree inside mi_reserve has synchronised already)
+        return compute_h_sharded_prepare(g, i, pk->log_n);   // the collective's own buffers too: a failure is agreed on below, before any rank enters it
+    }
+    if (!lead) return MI_OK;
+    // lead: a, b, c arrive while the wire MSMs run; computeH; its own slice of h feeds its Z MSM straight away
+    const mi_fr *da = p.a, *db = p.b, *dc = p.c;
+    if (host) {
+        char *base = (char *)ctx->ws[WS_PROVE_IN].p;
+        da = (mi_fr *)(base + wb); db = (mi_fr *)(base + wb + cb); dc = p.c ? (mi_fr *)(base + wb + 2 * cb) : nullptr;
+        if (cb) {
+            MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)da, p.a, cb, hipMemcpyHostToDevice, cps));
+            MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)db, p.b, cb, hipMemcpyHostToDevice, cps));
+            if (p.c) MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)dc, p.c, cb, hipMemcpyHostToDevice, cps));
             MI_CHECK_HIP(ctx, hipStreamSynchronize(cps));
         }
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_W_READY], ctx->stream));
-        MI_TRY(mi_prove_enqueue_wire_msms(ctx, pk, Wd, ev[EV_W_READY], defer));
-        if (use_sh) {   // this rank's rows of a, b (, c) into the group's slice vectors; computeH itself is a collective and follows the agreement
-            const u32 log_m = pk->log_n - log_w;
-            MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_PROVE_BEGIN], ctx->stream));
-            for (int which = 0; which < 3; which++) {
-                const mi_fr *src = abc_sl ? (abc_sl[which] ? abc_sl[which][i] : nullptr) : (which == 0 ? a : which == 1 ? b : c);
-                const bool given = abc_sl ? abc_sl[which] != nullptr : src != nullptr;
-                if (which == 2 && !given) { MI_TRY(mi_reserve(ctx, g->hx[2][i], sizeof(Fr) << log_m)); continue; }
-                MI_TRY(load_h_slice(g, i, which, log_m, src, !abc_sl, n_constraints, abc_sl ? ctx->stream : cps));
-            }
-            if (!abc_sl) MI_CHECK_HIP(ctx, hipStreamSynchronize(cps));   // (grown buffers: hipFree inside mi_reserve has synchronised already)
-            return compute_h_sharded_prepare(g, i, pk->log_n);   // the collective's own buffers too: a failure is agreed on below, before any rank enters it
-        }
-        if (!lead) return MI_OK;
-        // lead: a, b, c arrive while the wire MSMs run; computeH; its own slice of h feeds its Z MSM straight away
-        const mi_fr *da = a, *db = b, *dc = c;
-        if (host) {
-            char *base = (char *)ctx->ws[WS_PROVE_IN].p;
-            da = (mi_fr *)(base + wb); db = (mi_fr *)(base + wb + cb); dc = c ? (mi_fr *)(base + wb + 2 * cb) : nullptr;
-            if (cb) {
-                MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)da, a, cb, hipMemcpyHostToDevice, cps));
-                MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)db, b, cb, hipMemcpyHostToDevice, cps));
-                if (c) MI_CHECK_HIP(ctx, hipMemcpyAsync((void *)dc, c, cb, hipMemcpyHostToDevice, cps));
-                MI_CHECK_HIP(ctx, hipStreamSynchronize(cps));
-            }
-            ctx->stats.h2d_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
-        }
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_PROVE_BEGIN], ctx->stream));
-        Fr *h = (Fr *)ctx->ws[WS_H].p;
-        MI_TRY(mi_compute_h_dev_impl(ctx, pk->log_n, da, db, dc, n_constraints, (mi_fr *)h));
-        MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_H_READY], ctx->stream));
-        return mi_prove_enqueue_z_msm(ctx, pk, (const mi_fr *)(h + pk->z_lo), ev[EV_H_READY], defer);
-    };
-    if (lrc == MI_OK) { std::string e; note(for_each_local_rank(g, &e, rank_main), e); }
-    auto fail = [&](int32_t rc) { const std::string keep = g->err; drain_slots(g, slots, curves, 5); g->err = keep; return rc; };
-    {
-        const uint64_t check[5] = {(uint64_t)n_wires, (uint64_t)mode, (uint64_t)spk->log_n, use_sh ? 1u : 0u, use_sh ? (uint64_t)n_constraints : 0u};   // (without computeH over the ranks n_constraints is the lead's alone)
-        const int32_t rc = group_agree(g, lrc, lerr, "before computeH / the exchange of the h slices", check, 5);
-        if (rc != MI_OK) return fail(rc);
+        ctx->stats.h2d_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_up).count();
     }
-    // ---- h: rank 0 hands every other rank its slice device to device, as one batch of the group's transport (grouped ncclSend / ncclRecv,
-    // same-process copies or the shared-memory rings) on the exchange streams; the events that order the Z MSMs behind it are recorded by
-    // each RECEIVER on its own stream (an event is recorded only on a stream of the device it was created on)
-    if (use_sh) {
-        // computeH over all ranks; every rank's h slice is born where its Z pairs live (front slot = the previous rank's last coefficient)
-        const bool derive_c = abc_sl ? abc_sl[2] == nullptr : c == nullptr;
-        const int32_t rc = compute_h_sharded(g, spk->log_n, derive_c);
-        if (g->broken) return fail(rc);
-        note(rc, g->err);
-        if (lrc == MI_OK) {
-            std::string e;
-            note(for_each_local_rank(g, &e, [&](int i) -> int32_t {
-                mi_ctx *ctx = g->ctx[i];
-                MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_H_READY], ctx->stream));
-                const Fr *hz = (const Fr *)g->hh[i].p + (g->rank0 + i == 0 ? 1 : 0);
-                return mi_prove_enqueue_z_msm(ctx, spk->part[i], (const mi_fr *)hz, ctx->ev[EV_H_READY], defer);
-            }), e);
-        }
-    } else if (W > 1) {
-        std::vector<Xfer> list;
-        for (int j = 1; j < W; j++) {
-            u64 zlo, zhi;
-            range_of(N - 1, W, j, zlo, zhi);
-            Xfer x{0, j, nullptr, nullptr, (size_t)(zhi - zlo) * sizeof(Fr)};
-            if (g->local(0)) x.sp = (const char *)g->ctx[0 - g->rank0]->ws[WS_H].p + zlo * sizeof(Fr);
-            if (g->local(j)) x.dp = g->ctx[j - g->rank0]->ws[WS_H].p;
-            list.push_back(x);
-        }
-        if (lead_here) {
-            (void)hipSetDevice(g->dev[0]);
-            const hipError_t e = hipStreamWaitEvent(g->xs[0], g->ctx[0]->ev[EV_H_READY], 0);
-            if (e != hipSuccess) note(MI_EHIP, std::string("hipStreamWaitEvent (h ready): ") + hipGetErrorString(e));   // (still takes part in the batch)
-        }
-        const int32_t rc = run_xfers(g, list, g->xs);
-        if (rc != MI_OK) return fail(rc);   // transport failure: the group is broken
-        if (lrc == MI_OK) {
-            std::string e;
-            note(for_each_local_rank(g, &e, [&](int i) -> int32_t {
-                if (g->rank0 + i == 0) return MI_OK;
-                mi_ctx *ctx = g->ctx[i];
-                MI_CHECK_HIP(ctx, hipEventRecord(g->ev_h[i], g->xs[i]));
-                return mi_prove_enqueue_z_msm(ctx, spk->part[i], (const mi_fr *)ctx->ws[WS_H].p, g->ev_h[i], defer);
-            }), e);
-        }
+    MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_PROVE_BEGIN], ctx->stream));
+    Fr *h = (Fr *)ctx->ws[WS_H].p;
+    MI_TRY(mi_compute_h_dev_impl(ctx, pk->log_n, da, db, dc, p.n_constraints, (mi_fr *)h));
+    MI_CHECK_HIP(ctx, hipEventRecord(ev[EV_H_READY], ctx->stream));
+    return mi_prove_enqueue_z_msm(ctx, pk, (const mi_fr *)(h + pk->z_lo), ev[EV_H_READY], p.defer);
+}
+// ---- h, first form: computeH over all ranks; every rank's h slice is born where its Z pairs live (front slot = the previous rank's
+// last coefficient).  This and the two phases below return MI_OK or what ends the call: a transport failure, a failed agreement.
+static int32_t prove_h_over_ranks(ShardedProve &p) {
+    mi_group *g = p.g;
+    const bool derive_c = p.abc_sl ? p.abc_sl[2] == nullptr : p.c == nullptr;
+    const int32_t rc = compute_h_sharded(g, p.spk->log_n, derive_c);
+    if (g->broken) return rc;
+    p.st.note(rc, g->err);
+    if (p.st.ok()) for_each_local_rank(g, p.st, [&](int i) -> int32_t {
+        mi_ctx *ctx = g->rk[i].ctx;
+        MI_CHECK_HIP(ctx, hipEventRecord(ctx->ev[EV_H_READY], ctx->stream));
+        const Fr *hz = (const Fr *)g->rk[i].hh.p + (g->rank0 + i == 0 ? 1 : 0);
+        return mi_prove_enqueue_z_msm(ctx, p.spk->part[i], (const mi_fr *)hz, ctx->ev[EV_H_READY], p.defer);
+    });
+    return MI_OK;
+}
+// ---- h, second form: rank 0 hands every other rank its slice device to device, as one batch of the group's transport (grouped ncclSend /
+// ncclRecv, same-process copies or the shared-memory rings) on the exchange streams; the events that order the Z MSMs behind it are recorded
+// by each RECEIVER on its own stream (an event is recorded only on a stream of the device it was created on)
+static int32_t prove_h_from_lead(ShardedProve &p) {
+    mi_group *g = p.g;
+    std::vector<Xfer> list;
+    for (int j = 1; j < g->world; j++) {
+        u64 zlo, zhi;
+        range_of(p.N - 1, g->world, j, zlo, zhi);
+        Xfer x{0, j, nullptr, nullptr, (size_t)(zhi - zlo) * sizeof(Fr)};
+        if (g->local(0)) x.sp = (const char *)g->rk[0 - g->rank0].ctx->ws[WS_H].p + zlo * sizeof(Fr);
+        if (g->local(j)) x.dp = g->rk[j - g->rank0].ctx->ws[WS_H].p;
+        list.push_back(x);
     }
-    if (defer) {
-        // the wire MSMs' slices go first (one batch), Z's -- the last to have its bucket sums -- second: their reduces then run under
-        // Z's accumulation.  No local failure point lies between the agreement and the end of the second batch that a rank does not carry
-        // THROUGH both batches.
-        BucketExchange bx;
-        std::vector<uint64_t> check;
-        if (lrc == MI_OK) { const int32_t rc = exchange_prepare(g, bx, slots, curves, 5, check); note(rc, g->err); }
-        const int32_t rc = group_agree(g, lrc, lerr, "before the exchange of the bucket sums", check.data(), (uint32_t)check.size());
-        if (rc != MI_OK) return fail(rc);
-        int32_t r1 = exchange_run(g, bx, 0, 4);
-        if (g->broken) return fail(r1);
-        note(r1, g->err);
-        r1 = exchange_run(g, bx, 4, 1);
-        if (g->broken) return fail(r1);
-        note(r1, g->err);
+    if (p.lead_here) {
+        (void)hipSetDevice(g->rk[0].dev);
+        const hipError_t e = hipStreamWaitEvent(g->rk[0].xs, g->rk[0].ctx->ev[EV_H_READY], 0);
+        if (e != hipSuccess) p.st.note(MI_EHIP, std::string("hipStreamWaitEvent (h ready): ") + hipGetErrorString(e));   // (still takes part in the batch)
     }
+    MI_TRY(run_xfers(g, list));   // transport failure: the group is broken
+    if (p.st.ok()) for_each_local_rank(g, p.st, [&](int i) -> int32_t {
+        if (g->rank0 + i == 0) return MI_OK;
+        GroupRank &k = g->rk[i];
+        MI_CHECK_HIP(k.ctx, hipEventRecord(k.ev[E_H], k.xs));
+        return mi_prove_enqueue_z_msm(k.ctx, p.spk->part[i], (const mi_fr *)k.ctx->ws[WS_H].p, k.ev[E_H], p.defer);
+    });
+    return MI_OK;
+}
+// ---- mode 1: the wire MSMs' slices go first (one batch), Z's -- the last to have its bucket sums -- second: their reduces then run under
+// Z's accumulation.  No local failure point lies between the agreement and the end of the second batch that a rank does not carry
+// THROUGH both batches.
+static int32_t prove_bucket_exchange(ShardedProve &p) {
+    mi_group *g = p.g;
+    BucketExchange bx;
+    std::vector<uint64_t> check;
+    if (p.st.ok()) p.st.note(exchange_prepare(g, bx, PROVE_SLOTS, PROVE_CURVES, 5, check), g->err);
+    MI_TRY(group_agree(g, p.st, "before the exchange of the bucket sums", check.data(), (uint32_t)check.size()));
+    static const int batches[2][2] = {{0, 4}, {4, 1}};   // {first slot, count}
+    for (const auto &b : batches) {
+        const int32_t rc = exchange_run(g, bx, b[0], b[1]);
+        if (g->broken) return rc;
+        p.st.note(rc, g->err);
+    }
+    return MI_OK;
+}
+// ---- collect: this process's partial results of the five MSMs, then ONE all-gather of (status, five partial sums) per rank: every
+// process ends with the same five sums, or every process returns an error.  Then the assembly of the proof and the call's statistics.
+static int32_t prove_collect(ShardedProve &p, mi_proof_out *out, mi_stats *stats) {
+    mi_group *g = p.g;
     ProofAssembler as;
-    if (lrc == MI_OK) as.start(spk->part[0], r_m, s_m);
-    // ---- collect: this process's partial results of the five MSMs, then ONE all-gather of (status, five partial sums) per rank: every
-    // process ends with the same five sums, or every process returns an error
-    struct Part { int32_t rc; uint32_t pad[3]; G1X a, b1, k, z; G2X b2; };
-    std::vector<Part> mine((size_t)nl), all((size_t)W);
-    for (int i = 0; i < nl; i++) {
-        (void)hipSetDevice(g->dev[i]);
-        std::memset(&mine[i], 0, sizeof(Part));
-        if (lrc == MI_OK) {
-            mi_ctx *ctx = g->ctx[i];
-            int32_t rc = mi_msm_finish(ctx, MSM_SLOT_A, 1, &mine[i].a);
-            if (rc == MI_OK) rc = mi_msm_finish(ctx, MSM_SLOT_B1, 1, &mine[i].b1);
-            if (rc == MI_OK) rc = mi_msm_finish(ctx, MSM_SLOT_K, 1, &mine[i].k);
-            if (rc == MI_OK) rc = mi_msm_finish(ctx, MSM_SLOT_B2, 2, &mine[i].b2);
-            if (rc == MI_OK) rc = mi_msm_finish(ctx, MSM_SLOT_Z, 1, &mine[i].z);
-            if (rc == MI_OK && (hipStreamSynchronize(ctx->stream) != hipSuccess || hipStreamSynchronize(g->xs[i]) != hipSuccess)) { mi_set_err(ctx, "prove: stream synchronisation failed"); rc = MI_EHIP; }
-            note(rc, mi_last_error(ctx));
-        }
+    if (p.st.ok()) as.start(p.spk->part[0], p.r_m, p.s_m);
+    struct Sums { G1X a, b1, k, z; G2X b2; };
+    std::vector<Sums> mine((size_t)g->n_local()), all;
+    for (int i = 0; i < g->n_local(); i++) {
+        GroupRank &rk = g->rk[i];
+        (void)hipSetDevice(rk.dev);
+        std::memset((void *)&mine[i], 0, sizeof(Sums));
+        if (!p.st.ok()) continue;
+        mi_ctx *ctx = rk.ctx;
+        int32_t rc = mi_msm_finish(ctx, MSM_SLOT_A, 1, &mine[i].a);
+        if (rc == MI_OK) rc = mi_msm_finish(ctx, MSM_SLOT_B1, 1, &mine[i].b1);
+        if (rc == MI_OK) rc = mi_msm_finish(ctx, MSM_SLOT_K, 1, &mine[i].k);
+        if (rc == MI_OK) rc = mi_msm_finish(ctx, MSM_SLOT_B2, 2, &mine[i].b2);
+        if (rc == MI_OK) rc = mi_msm_finish(ctx, MSM_SLOT_Z, 1, &mine[i].z);
+        if (rc == MI_OK && (hipStreamSynchronize(ctx->stream) != hipSuccess || hipStreamSynchronize(rk.xs) != hipSuccess)) { mi_set_err(ctx, "prove: stream synchronisation failed"); rc = MI_EHIP; }
+        p.st.note(rc, mi_last_error(ctx));
     }
-    for (int i = 0; i < nl; i++) mine[i].rc = lrc;
-    {
-        const int32_t rc = group_allgather(g, mine.data(), sizeof(Part), all.data());
-        if (rc != MI_OK) return fail(rc);
-        for (int r = 0; r < W; r++)
-            if (all[r].rc != MI_OK) {
-                if (lrc != MI_OK) { g->err = lerr; return fail(lrc); }
-                g->err = std::string("group: rank ") + std::to_string(r) + " failed in its part of the proof (status " + std::to_string(all[r].rc) + ")";
-                return fail(all[r].rc);
-            }
-    }
+    MI_TRY(group_gather(g, p.st, mine, "in its part of the proof", "", all));
     G1X sum_a = G1X::inf(), sum_b1 = G1X::inf(), sum_k = G1X::inf(), sum_z = G1X::inf();
     G2X sum_b2 = G2X::inf();
-    for (const Part &p : all) { xyzz_add(sum_a, p.a); xyzz_add(sum_b1, p.b1); xyzz_add(sum_k, p.k); xyzz_add(sum_z, p.z); xyzz_add(sum_b2, p.b2); }
+    for (const Sums &s : all) { xyzz_add(sum_a, s.a); xyzz_add(sum_b1, s.b1); xyzz_add(sum_k, s.k); xyzz_add(sum_z, s.z); xyzz_add(sum_b2, s.b2); }
     const auto t_gpu_done = std::chrono::steady_clock::now();
     as.have_a_b1(sum_a, sum_b1);
     as.finish(sum_k, sum_b2, sum_z, out);
     const auto t_end = std::chrono::steady_clock::now();
-    (void)hipSetDevice(g->dev[0]);
-    mi_stats &st = g->ctx[0]->stats;
+    (void)hipSetDevice(g->rk[0].dev);
+    mi_ctx *c0 = g->rk[0].ctx;
+    mi_stats &st = c0->stats;
     auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<float, std::milli>(y - x).count(); };
     // (statistics are best effort: past the last all-gather nothing may fail on one rank alone)
-    if ((lead_here || use_sh) && hipEventElapsedTime(&st.compute_h_ms, g->ctx[0]->ev[EV_PROVE_BEGIN], g->ctx[0]->ev[EV_H_READY]) != hipSuccess) { (void)hipGetLastError(); st.compute_h_ms = 0; }
+    if ((p.lead_here || p.use_sh) && hipEventElapsedTime(&st.compute_h_ms, c0->ev[EV_PROVE_BEGIN], c0->ev[EV_H_READY]) != hipSuccess) { (void)hipGetLastError(); st.compute_h_ms = 0; }
     st.assemble_ms = ms(t_gpu_done, t_end);
-    st.total_ms = ms(t_begin, t_end);
+    st.total_ms = ms(p.t_begin, t_end);
     if (stats) *stats = st;
     return MI_OK;
+}
+static int32_t prove_sharded(ShardedProve p, mi_proof_out *out, mi_stats *stats) {
+    const MiRange range_fn("mi.group.prove");
+    mi_group *g = p.g;
+    if (!p.spk || !out) return MI_EINVAL;
+    const int nl = g->n_local(), W = g->world;
+    if ((nl != W && nl != 1) || (int)p.spk->part.size() != nl) G_FAIL(g, MI_EINVAL, "group: a process holds either all ranks or exactly one");
+    p.t_begin = std::chrono::steady_clock::now();
+    p.lead_here = g->rank0 == 0; p.defer = p.mode == 1;
+    p.N = (size_t)1 << p.spk->log_n; p.cb = p.n_constraints * sizeof(mi_fr);
+    p.use_sh = (p.abc_sl != nullptr || (p.host && g->sharded_h)) && sharded_h_possible(g, p.spk->log_n);
+    prove_check_and_reserve(p);
+    if (p.st.ok()) for_each_local_rank(g, p.st, [&](int i) { return prove_rank_local(p, i); });
+    // (without computeH over the ranks n_constraints is the lead's alone)
+    const uint64_t check[5] = {(uint64_t)p.n_wires, (uint64_t)p.mode, (uint64_t)p.spk->log_n, p.use_sh ? 1u : 0u, p.use_sh ? (uint64_t)p.n_constraints : 0u};
+    int32_t rc = group_agree(g, p.st, "before computeH / the exchange of the h slices", check, 5);
+    if (rc == MI_OK) rc = p.use_sh ? prove_h_over_ranks(p) : W > 1 ? prove_h_from_lead(p) : MI_OK;
+    if (rc == MI_OK && p.defer) rc = prove_bucket_exchange(p);
+    if (rc == MI_OK) rc = prove_collect(p, out, stats);
+    if (rc != MI_OK) { const std::string keep = g->err; drain_slots(g, PROVE_SLOTS, PROVE_CURVES, 5); g->err = keep; }
+    return rc;
 }
 
 extern "C" {
@@ -1512,20 +1287,20 @@ int32_t mi_pk_load_sharded_dev(mi_group *g, const mi_pk_desc *slice_descs, mi_pk
 int32_t mi_groth16_prove_sharded(mi_group *g, mi_pk_sharded *spk, const mi_fr *W, size_t n_wires, const mi_fr *a, const mi_fr *b, const mi_fr *c,
                                  size_t n_constraints, const mi_fr *r_m, const mi_fr *s_m, uint32_t mode, mi_proof_out *out, mi_stats *stats) {
     G_ENTER(g);
-    return prove_sharded_impl(g, spk, true, W, nullptr, n_wires, a, b, c, n_constraints, r_m, s_m, mode, out, stats);
+    return prove_sharded({g, spk, true, W, nullptr, n_wires, a, b, c, n_constraints, r_m, s_m, mode, nullptr}, out, stats);
 }
 int32_t mi_groth16_prove_sharded_slices_dev(mi_group *g, mi_pk_sharded *spk, const mi_fr *const *W_dev, size_t n_wires, const mi_fr *const *a_sl,
                                             const mi_fr *const *b_sl, const mi_fr *const *c_sl, size_t n_constraints, const mi_fr *r_m, const mi_fr *s_m,
                                             uint32_t mode, mi_proof_out *out, mi_stats *stats) {
     G_ENTER(g);
     const mi_fr *const *abc[3] = {a_sl, b_sl, c_sl};
-    return prove_sharded_impl(g, spk, false, nullptr, W_dev, n_wires, nullptr, nullptr, nullptr, n_constraints, r_m, s_m, mode, out, stats, abc);
+    return prove_sharded({g, spk, false, nullptr, W_dev, n_wires, nullptr, nullptr, nullptr, n_constraints, r_m, s_m, mode, abc}, out, stats);
 }
 int32_t mi_groth16_prove_sharded_dev(mi_group *g, mi_pk_sharded *spk, const mi_fr *const *W_dev, size_t n_wires, const mi_fr *a_dev, const mi_fr *b_dev,
                                      const mi_fr *c_dev, size_t n_constraints, const mi_fr *r_m, const mi_fr *s_m, uint32_t mode, mi_proof_out *out,
                                      mi_stats *stats) {
     G_ENTER(g);
-    return prove_sharded_impl(g, spk, false, nullptr, W_dev, n_wires, a_dev, b_dev, c_dev, n_constraints, r_m, s_m, mode, out, stats);
+    return prove_sharded({g, spk, false, nullptr, W_dev, n_wires, a_dev, b_dev, c_dev, n_constraints, r_m, s_m, mode, nullptr}, out, stats);
 }
 
 }  // extern "C"
