@@ -6,8 +6,10 @@
 // HBM layout: the caller's array of 32-byte Montgomery elements, transformed in place.  Each pass
 // is one launch; a workgroup owns one LDS tile (<= 2^log_e elements, two 16-byte planes), loads
 // it with >= 256-byte contiguous runs, runs log2(R) butterfly stages out of LDS and stores it
-// back.  Root tables: one 1024-entry table serves every in-tile stage; inter-pass twiddles and
-// coset powers come from two sqrt(N)-sized tables and one product (no N-sized table is ever read).
+// back.  Root tables of a generic transform (mi_ntt): one 2048-entry table serves every in-tile stage; inter-pass
+// twiddles and coset powers come from two sqrt(N)-sized tables and one product (no N-sized table is read).
+// computeH trades HBM for products: its strided passes read their stage twiddles by global index from
+// M-entry tables (NttPass::tw_stage: no inter-pass product at all) and its coset shifts from N-entry ones.
 // Bound: HBM for the load/store (64 B per element per pass), VALU (one 256-bit Montgomery product
 // per butterfly) for the stages -- see DESIGN.md for the measured split.
 #include "ctx.h"
@@ -26,9 +28,17 @@ struct NttState {
     u32 tw_h = 0;
     // computeH's direct factor tables in the data's layout (NttPass::tw_direct / sc_direct), N entries each, built for one
     // (log_n, first radix): twiddles of the M = N pass for the inverse and the forward root, coset shifts g^bitrev(i) / N and
-    // g^-bitrev(i) * den / N.  4 x 32 B x N of HBM (1 GiB at N = 2^23) buy 11 of computeH's ~107 products per element.
+    // g^-bitrev(i) * den / N.  4 x 32 B x N of HBM (1 GiB at N = 2^23) bought 11 of the ~107 products per element computeH had
+    // when they came (77 since; 71 with the stage twiddles below).
+    // d_tw_* stay null while the stage-twiddle tables below are bound (they serve the same pass).
     Fr *d_tw_inv = nullptr, *d_tw_fwd = nullptr, *d_sc_fwd = nullptr, *d_sc_inv = nullptr;
     u32 d_log_n = 0xffffffffu, d_log_r0 = 0, d_npass = 0;
+    // computeH's stage twiddles by global index (NttPass::tw_stage): one table of M = R S entries per strided pass of the plan and
+    // root, instead of d_tw_* (the M = N pass) and tw64k_* (the inner ones).  Another ~6 products per element go: 71 of 77.
+    Fr *s_tw_inv[3] = {nullptr, nullptr, nullptr}, *s_tw_fwd[3] = {nullptr, nullptr, nullptr};
+    u32 s_log_r[3] = {0, 0, 0}, s_log_s[3] = {0, 0, 0}, s_n = 0;   // the passes they serve; s_n = 0: none built
+    u32 stage_tw = 1;      // knob "ntt_stage_twiddles": build and bind them at the next table build (0: d_tw_* and the edge products)
+    u32 d_radices = 0, d_stage_tw = 0;   // what the direct and stage tables were built for: the plan's radices (4 bits each) and the knob
     u32 direct_min_log_n = 12;   // below this the tables are not worth a launch
     // plan knobs (mi_debug_set_ntt_plan)
     // defaults from the tools/tune.py sweep at N = 2^23: 2^9-element tiles (16 KiB of LDS, 8 workgroups of 256
@@ -59,13 +69,20 @@ static const LastSubCountKernel k_last_sub_count[6] = {   // by window width c -
     k_ntt_contig_last_sub_count<20>, k_ntt_contig_last_sub_count<21>, k_ntt_contig_last_sub_count<22>};
 bool mi_ntt_set_knob(mi_ctx *ctx, const char *name, int64_t value) {
     if (!std::strcmp(name, "ntt_lds_floor_kb") && value >= 0 && value <= 160) { state_of(ctx)->lds_floor = (u32)value * 1024u; return true; }
+    if (!std::strcmp(name, "ntt_stage_twiddles") && (value == 0 || value == 1)) { state_of(ctx)->stage_tw = (u32)value; return true; }   // (ensure_direct rebuilds)
     return false;
+}
+static void free_stage_tables(NttState *st) {
+    for (u32 k = 0; k < 3; k++)
+        for (Fr **p : {&st->s_tw_inv[k], &st->s_tw_fwd[k]}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    st->s_n = 0;
 }
 void mi_ntt_state_free(mi_ctx *ctx) {
     NttState *st = state_of(ctx);
     Fr **all[] = {&st->small_f, &st->small_i, &st->tw64k_f, &st->tw64k_i, &st->g_hi_n, &st->gi_hi_nd, &st->tw_lo_f, &st->tw_hi_f, &st->tw_lo_i, &st->tw_hi_i,
                   &st->g_lo, &st->g_hi, &st->gi_lo, &st->gi_hi, &st->ninv, &st->ninv_den, &st->d_tw_inv, &st->d_tw_fwd, &st->d_sc_fwd, &st->d_sc_inv};
     for (Fr **p : all) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    free_stage_tables(st);
 }
 
 // mi_ctx_trim: every table goes; the markers say "nothing built", the plan knobs stay
@@ -84,6 +101,7 @@ size_t mi_ntt_table_bytes(mi_ctx *ctx) {
         b += (4 * nlo + 6 * nhi + 2) * sizeof(Fr);
     }
     for (const Fr *p : {st->d_tw_inv, st->d_tw_fwd, st->d_sc_fwd, st->d_sc_inv}) if (p) b += sizeof(Fr) << st->d_log_n;
+    for (u32 k = 0; k < st->s_n; k++) b += 2 * (sizeof(Fr) << (st->s_log_r[k] + st->s_log_s[k]));
     return b;
 }
 
@@ -114,7 +132,7 @@ __global__ void __launch_bounds__(1024) k_ntt_pass(Fr *dst, const Fr *src, NttPa
     ntt_tile_load(p, t, src, tile, threadIdx.x, blockDim.x, lds);
     __syncthreads();
     for (u32 s = 0; s < p.log_r; s++) {
-        ntt_tile_stage(p, t, s, threadIdx.x, blockDim.x, lds);
+        ntt_tile_stage(p, t, s, threadIdx.x, blockDim.x, lds, tile);
         __syncthreads();
     }
     ntt_tile_store(p, t, dst, tile, threadIdx.x, blockDim.x, lds);
@@ -134,7 +152,7 @@ __global__ void __launch_bounds__(256, MI_NTT_WAVES_PER_EU) k_ntt_pass_wave(Fr *
     __syncthreads();
     if (!p.dit)   // DIF: distances R/2 ... 128 first
         for (u32 s = 0; s + 7 < p.log_r; s++) {
-            ntt_tile_stage(p, t, s, threadIdx.x, blockDim.x, lds);
+            ntt_tile_stage(p, t, s, threadIdx.x, blockDim.x, lds, tile);
             __syncthreads();
         }
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
@@ -145,14 +163,14 @@ __global__ void __launch_bounds__(256, MI_NTT_WAVES_PER_EU) k_ntt_pass_wave(Fr *
         if (!p.dit) { ra = base + lane; rb = ra + 64; wa = base + 2 * lane; wb = wa + 1; }
         else { ra = base + 2 * lane; rb = ra + 1; wa = base + lane; wb = wa + 64; }
         Fr x0 = lds_get(lds, PL, ntt_lds_slot(p, ra, col)), x1 = lds_get(lds, PL, ntt_lds_slot(p, rb, col));
-        wave_ntt128(x0, x1, lane, p.dit != 0, t.small);
+        wave_ntt128(x0, x1, lane, p.dit != 0, t.small, ntt_stage_run(p, tile, col));
         lds_put(lds, PL, ntt_lds_slot(p, wa, col), x0);
         lds_put(lds, PL, ntt_lds_slot(p, wb, col), x1);
     }
     __syncthreads();
     if (p.dit)    // DIT: distances 128 ... R/2 last
         for (u32 s = 7; s < p.log_r; s++) {
-            ntt_tile_stage(p, t, s, threadIdx.x, blockDim.x, lds);
+            ntt_tile_stage(p, t, s, threadIdx.x, blockDim.x, lds, tile);
             __syncthreads();
         }
     ntt_tile_store(p, t, dst, tile, threadIdx.x, blockDim.x, lds);
@@ -214,17 +232,18 @@ __global__ void __launch_bounds__(512) k_ntt_strided_triple(Fr *a, const Fr *b, 
     const u32 lane = threadIdx.x & 63, sb = threadIdx.x >> 6;
     const u32 col = sb & ((1u << pc.log_c) - 1), base = (sb >> pc.log_c) << 7;
     const u32 s0 = ntt_lds_slot(pc, base + 2 * lane, col), s1 = ntt_lds_slot(pc, base + 2 * lane + 1, col);
+    const Fr *const run_c = ntt_stage_run(pc, tile, col), *const run_l = ntt_stage_run(pl, tile, col);   // stage twiddles by global index, or null
     ntt_tile_load(pc, tc, a, tile, threadIdx.x, blockDim.x, lds);
     __syncthreads();
     Fr a0 = lds_get(lds, PL, s0), a1 = lds_get(lds, PL, s1);
-    wave_ntt128(a0, a1, lane, true, tc.small);     // -> rows L, L + 64
+    wave_ntt128(a0, a1, lane, true, tc.small, run_c);     // -> rows L, L + 64
     __syncthreads();                               // every wave has read a's tile
     ntt_tile_load(pc, tc, b, tile, threadIdx.x, blockDim.x, lds);
     __syncthreads();
     Fr x0 = lds_get(lds, PL, s0), x1 = lds_get(lds, PL, s1);
-    wave_ntt128(x0, x1, lane, true, tc.small);
+    wave_ntt128(x0, x1, lane, true, tc.small, run_c);
     x0 = ntt_mul_lazy2(x0, a0); x1 = ntt_mul_lazy2(x1, a1);   // DIT left both factors below 4p; the DIF stages want [0, 2p)
-    wave_ntt128(x0, x1, lane, false, tl.small);    // rows L, L + 64 -> positions 2L, 2L + 1
+    wave_ntt128(x0, x1, lane, false, tl.small, run_l);    // rows L, L + 64 -> positions 2L, 2L + 1
     __syncthreads();                               // every wave has read b's tile
     lds_put(lds, PL, ntt_lds_slot(pl, base + 2 * lane, col), x0);
     lds_put(lds, PL, ntt_lds_slot(pl, base + 2 * lane + 1, col), x1);
@@ -251,7 +270,7 @@ __global__ void __launch_bounds__(256) k_ntt_strided_triple8(Fr *a, const Fr *b,
             if (!dit) { ra = base + lane; rb = ra + 64; wa = base + 2 * lane; wb = wa + 1; }
             else { ra = base + 2 * lane; rb = ra + 1; wa = base + lane; wb = wa + 64; }
             Fr x0 = lds_get(lds, PL, ntt_lds_slot(p, ra, col)), x1 = lds_get(lds, PL, ntt_lds_slot(p, rb, col));
-            wave_ntt128(x0, x1, lane, dit, small);
+            wave_ntt128(x0, x1, lane, dit, small, ntt_stage_run(p, tile, col));
             lds_put(lds, PL, ntt_lds_slot(p, wa, col), x0);
             lds_put(lds, PL, ntt_lds_slot(p, wb, col), x1);
         }
@@ -267,7 +286,8 @@ __global__ void __launch_bounds__(256) k_ntt_strided_triple8(Fr *a, const Fr *b,
         const u32 bf = threadIdx.x + 256 * k, col = bf & (C - 1), j = bf >> pc.log_c;
         Fr x = lds_get(lds, PL, ntt_lds_slot(pc, j, col));
         Fr y = lds_get(lds, PL, ntt_lds_slot(pc, j + 128, col));
-        ntt_bfly_dit(x, y, j ? &tc.small[j << 4] : nullptr);           // w_256^j = w_4096^(16 j)
+        const Fr *run = ntt_stage_run(pc, tile, col);
+        ntt_bfly_dit(x, y, run ? &run[128 + j] : j ? &tc.small[j << 4] : nullptr);           // w_256^j = w_4096^(16 j), or the global stage's
         keep[2 * k] = x; keep[2 * k + 1] = y;
     }
     __syncthreads();
@@ -281,9 +301,10 @@ __global__ void __launch_bounds__(256) k_ntt_strided_triple8(Fr *a, const Fr *b,
         const u32 bf = threadIdx.x + 256 * k, col = bf & (C - 1), j = bf >> pc.log_c;
         Fr x = lds_get(lds, PL, ntt_lds_slot(pc, j, col));
         Fr y = lds_get(lds, PL, ntt_lds_slot(pc, j + 128, col));
-        ntt_bfly_dit(x, y, j ? &tc.small[j << 4] : nullptr);
+        const Fr *run_c = ntt_stage_run(pc, tile, col), *run_l = ntt_stage_run(pl, tile, col);
+        ntt_bfly_dit(x, y, run_c ? &run_c[128 + j] : j ? &tc.small[j << 4] : nullptr);
         Fr p0 = ntt_mul_lazy2(x, keep[2 * k]), p1 = ntt_mul_lazy2(y, keep[2 * k + 1]);   // the products at rows j, j + 128, below 2p
-        ntt_bfly_dif(p0, p1, j ? &tl.small[j << 4] : nullptr);                           // DIF butterfly at distance 128
+        ntt_bfly_dif(p0, p1, run_l ? &run_l[128 + j] : j ? &tl.small[j << 4] : nullptr);                           // DIF butterfly at distance 128
         lds_put(lds, PL, ntt_lds_slot(pl, j, col), p0);
         lds_put(lds, PL, ntt_lds_slot(pl, j + 128, col), p1);
     }
@@ -394,6 +415,15 @@ __global__ void k_tw_layout(Fr *out, u32 log_n, u32 log_r, Fr w) {   // the M = 
     while (e) { if (e & 1) acc = acc * b; b = fe_sqr(b); e >>= 1; }
     out[g] = acc;
 }
+// stage twiddles by global index of the pass (log_r, log_s), NttPass::tw_stage: 2^(log_r + log_s) entries
+__global__ void k_tw_stage_layout(Fr *out, u32 log_n, u32 log_r, u32 log_s, Fr w) {
+    const u32 idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (1u << (log_r + log_s))) return;
+    u32 e = ntt_stage_tw_exponent(log_n, log_r, log_s, idx);   // < N / 2
+    Fr acc = Fr::one(), b = w;
+    while (e) { if (e & 1) acc = acc * b; b = fe_sqr(b); e >>= 1; }
+    out[idx] = acc;
+}
 __global__ void k_sc_layout(Fr *out, u32 log_n, Fr base, Fr c) {     // out[i] = c * base^bitrev_N(i)
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (1u << log_n)) return;
@@ -459,33 +489,58 @@ static int32_t ensure_tables(mi_ctx *ctx, u32 log_n) {
     return MI_OK;
 }
 
-// computeH's direct tables for (log_n, current plan); a failure to allocate them only means the composed-table path runs
+// computeH's direct and stage-twiddle tables for (log_n, current plan, knob "ntt_stage_twiddles"); a failure to allocate the stage
+// twiddles only means the direct tables serve, a failure to allocate those that the composed-table path runs
 static int32_t ensure_direct(mi_ctx *ctx, u32 log_n) {
     NttState *st = state_of(ctx);
     const NttKnobs kn = knobs_for(st, log_n);
     const NttPlan pl = ntt_make_plan(log_n, kn.max_contig, kn.max_strided);
-    if (st->d_log_n == log_n && st->d_log_r0 == pl.log_r[0] && st->d_npass == pl.n_pass) return MI_OK;
+    u32 radices = 0;
+    for (u32 i = 0; i < pl.n_pass; i++) radices |= pl.log_r[i] << (4 * i);
+    if (st->d_log_n == log_n && st->d_log_r0 == pl.log_r[0] && st->d_npass == pl.n_pass && st->d_radices == radices && st->d_stage_tw == st->stage_tw) return MI_OK;
     Fr **four[] = {&st->d_tw_inv, &st->d_tw_fwd, &st->d_sc_fwd, &st->d_sc_inv};
     for (Fr **p : four) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    free_stage_tables(st);
     st->d_log_n = 0xffffffffu;
     if (log_n < st->direct_min_log_n) return MI_OK;
+    // one stage-twiddle table per strided pass and root (plans of up to three strided passes: every default plan)
+    const u32 n_strided = pl.n_pass - 1;
+    bool stage = st->stage_tw && n_strided >= 1 && n_strided <= 3;
+    for (u32 k = 0, log_s = log_n; stage && k < n_strided; k++) {
+        log_s -= pl.log_r[k];
+        st->s_log_r[k] = pl.log_r[k]; st->s_log_s[k] = log_s;
+        for (Fr **p : {&st->s_tw_inv[k], &st->s_tw_fwd[k]})
+            if (stage && hipMalloc((void **)p, sizeof(Fr) << (pl.log_r[k] + log_s)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; stage = false; }
+    }
+    if (!stage) free_stage_tables(st);
     const size_t bytes = sizeof(Fr) << log_n;
-    for (Fr **p : four)
+    for (Fr **p : four) {
+        if (stage && (p == &st->d_tw_inv || p == &st->d_tw_fwd)) continue;   // the stage twiddles serve the M = N pass
         if (hipMalloc((void **)p, bytes) != hipSuccess) {   // no room: stay on the composed tables
             (void)hipGetLastError();
+            *p = nullptr;
             for (Fr **q : four) if (*q) { (void)hipFree(*q); *q = nullptr; }
+            free_stage_tables(st);
             return MI_OK;
         }
+    }
     const NttRoots r = ntt_roots(log_n);
     const unsigned blocks = (unsigned)(((size_t)1 << log_n) + 255) / 256;
-    if (pl.n_pass > 1) {
+    if (stage) {
+        st->s_n = n_strided;
+        for (u32 k = 0; k < n_strided; k++) {
+            const unsigned sb = (unsigned)((((size_t)1 << (st->s_log_r[k] + st->s_log_s[k])) + 255) / 256);
+            hipLaunchKernelGGL(k_tw_stage_layout, dim3(sb), dim3(256), 0, ctx->stream, st->s_tw_inv[k], log_n, st->s_log_r[k], st->s_log_s[k], r.wi);
+            hipLaunchKernelGGL(k_tw_stage_layout, dim3(sb), dim3(256), 0, ctx->stream, st->s_tw_fwd[k], log_n, st->s_log_r[k], st->s_log_s[k], r.w);
+        }
+    } else if (pl.n_pass > 1) {
         hipLaunchKernelGGL(k_tw_layout, dim3(blocks), dim3(256), 0, ctx->stream, st->d_tw_inv, log_n, pl.log_r[0], r.wi);
         hipLaunchKernelGGL(k_tw_layout, dim3(blocks), dim3(256), 0, ctx->stream, st->d_tw_fwd, log_n, pl.log_r[0], r.w);
     }
     hipLaunchKernelGGL(k_sc_layout, dim3(blocks), dim3(256), 0, ctx->stream, st->d_sc_fwd, log_n, r.g, r.ninv);            // NTT_COSET_FWD_NINV
     hipLaunchKernelGGL(k_sc_layout, dim3(blocks), dim3(256), 0, ctx->stream, st->d_sc_inv, log_n, r.gi, r.ninv * r.den);   // NTT_COSET_INV_DEN
     MI_CHECK_HIP(ctx, hipGetLastError());
-    st->d_log_n = log_n; st->d_log_r0 = pl.log_r[0]; st->d_npass = pl.n_pass;
+    st->d_log_n = log_n; st->d_log_r0 = pl.log_r[0]; st->d_npass = pl.n_pass; st->d_radices = radices; st->d_stage_tw = st->stage_tw;
     return MI_OK;
 }
 
@@ -513,11 +568,13 @@ static int32_t ntt_bind(mi_ctx *ctx, NttTransform &tr, const Fr *load_mul = null
     if (load_mul && (first.scale == 1 || first.scale == 2 || first.dit)) MI_FAIL(ctx, MI_EINVAL, "internal: load_mul on a pass whose load side already has a factor");
     first.load_mul = load_mul;
     tr.pass[tr.n_pass - 1].store_sub = store_sub;
-    // computeH's direct tables: the twiddle of the M = N pass, the coset shift of the contiguous pass
+    // computeH's stage twiddles of every strided pass, else the direct twiddle of the M = N pass; the coset shift of the contiguous pass
     if (tr.variant == NTT_PLAIN || st->d_log_n != tr.log_n || !st->d_sc_fwd) return MI_OK;
     for (u32 i = 0; i < tr.n_pass; i++) {
         NttPass &p = tr.pass[i];
-        if (p.twiddle && p.log_r + p.log_s == tr.log_n) p.tw_direct = inverse ? st->d_tw_inv : st->d_tw_fwd;
+        for (u32 k = 0; p.twiddle && k < st->s_n; k++)
+            if (st->s_log_r[k] == p.log_r && st->s_log_s[k] == p.log_s) p.tw_stage = inverse ? st->s_tw_inv[k] : st->s_tw_fwd[k];
+        if (p.twiddle && !p.tw_stage && p.log_r + p.log_s == tr.log_n) p.tw_direct = inverse ? st->d_tw_inv : st->d_tw_fwd;
         if (tr.variant == NTT_COSET_FWD_NINV && p.scale == 1) p.sc_direct = st->d_sc_fwd;
         if (tr.variant == NTT_COSET_INV_DEN && p.scale == 3) p.sc_direct = st->d_sc_inv;
     }

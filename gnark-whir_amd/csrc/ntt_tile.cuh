@@ -17,6 +17,15 @@
 //   output equals gnark's stage-by-stage result bit for bit.  Coset shifts and 1/N are folded
 //   into the first pass's load or the last pass's store.
 //
+//   A strided pass that carries NttPass::tw_stage undoes the regrouping: its stage at row half-distance d
+//   is the stage at GLOBAL half-distance D = d*S of the size-M sub-transform, whose twiddle for the pair
+//   at (j = rho mod d, lo) is w_(2D)^(i mod D) = w_(2dS)^(j*S + lo) = w_2d^j * w_(2dS)^lo, and there is no
+//   product at the pass's edge (the extra factors w_(2dS)^lo along an element's path multiply to exactly
+//   w_M^(lo * bitrev_R(rho))).  One product per butterfly in every stage (d = 1 included) and none per
+//   element: R/2 * log2(R) products per column instead of R/2 * (log2(R) - 1) + R.  Lazy contract without
+//   the edge product: a DIF pass hands on what its last butterfly leaves, [0, 2p); a DIT pass takes what
+//   the previous pass stored, [0, 4p), straight into ntt_bfly_dit and stores [0, 4p).
+//
 // LDS image: two planes of 16-byte halves (lo / hi 128 bits of each element) so that a wave's
 // ds_read_b128 / ds_write_b128 walk consecutive 16-byte slots (conflict-free at unit stride).
 #pragma once
@@ -59,7 +68,21 @@ struct NttPass {
     const Fr *load_mul;
     const Fr *store_sub;
     u32 canon;      // 1 on the last pass of a transform whose output leaves the library (or is h): every element is brought back to [0, p)
+    // Stage twiddles by global index (strided passes only), or null = tile-local stage twiddles from NttTables::small plus the
+    // inter-pass twiddle at the edge.  One run of R entries per column lo of the block (S runs, the same for every block):
+    //     tw_stage[lo * R + d + j] = w_(2dS)^(j*S + lo) = w_N^(ntt_stage_tw_exponent)     d = 1, 2, ..., R/2;  j < d
+    // (slot 0 of a run is unused).  A wave that runs a column's butterflies reads one contiguous run; R*S = M entries in all.
+    const Fr *tw_stage;
 };
+// exponent of w_N in entry idx of the stage-twiddle table of a pass (log_r, log_s) of a transform of size 2^log_n (< N/2)
+MI_HD u32 ntt_stage_tw_exponent(u32 log_n, u32 log_r, u32 log_s, u32 idx) {
+    const u32 k = idx & ((1u << log_r) - 1), lo = idx >> log_r;
+    if (!k) return 0;
+    u32 log_d = 0;
+    while ((2u << log_d) <= k) log_d++;
+    const u32 j = k - (1u << log_d);
+    return ((j << log_s) + lo) << (log_n - 1 - log_d - log_s);
+}
 
 // ---------------------------------------------------------------- lazy butterflies (Harvey)
 // Between the stages of a transform the elements are 256-bit representatives that are NOT reduced below p (field.cuh, "lazy
@@ -122,6 +145,12 @@ MI_HD Fr lds_get(const U4 *lds, u32 plane_elems, u32 slot) {
     v.l[4] = b.x; v.l[5] = b.y; v.l[6] = b.z; v.l[7] = b.w;
     return v;
 }
+// the stage-twiddle run of column col of a tile (NttPass::tw_stage), or null
+MI_HD const Fr *ntt_stage_run(const NttPass &p, u64 tile, u32 col) {
+    if (!p.tw_stage) return nullptr;
+    const u64 lo = ((tile & (((u64)1 << (p.log_s - p.log_c)) - 1)) << p.log_c) + col;
+    return p.tw_stage + (lo << p.log_r);
+}
 // (inter-pass twiddle of (rho, lo): w_M^(lo * bitrev_R(rho)) = w_N^((lo * bitrev_R(rho)) << (log_n - log_m)), see ntt_edge_factor)
 // The ONE factor (if any) an element is multiplied by on its way into the tile (phase 0: coset / constant pre-scale, DIT
 // pre-twiddle) or out of it (phase 1: DIF post-twiddle, inverse / coset post-scale).  A pass never has a scale and a twiddle on
@@ -129,7 +158,7 @@ MI_HD Fr lds_get(const U4 *lds, u32 plane_elems, u32 slot) {
 // has one composing product site and one applying product site -- the product is ~330 instructions and is inlined.
 MI_HD bool ntt_edge_factor(const NttPass &p, const NttTables &t, u32 rho, u64 g, u32 phase, Fr &f) {
     const bool sc = phase == 0 ? (p.scale == 1 || p.scale == 2) : p.scale >= 3;
-    const bool tw = p.twiddle && (phase == 0) == (p.dit != 0);
+    const bool tw = p.twiddle && !p.tw_stage && (phase == 0) == (p.dit != 0);   // (tw_stage: the stages carry it)
     const Fr *lo, *hi;
     u32 e;
     if (sc) {
@@ -169,8 +198,9 @@ MI_HD void ntt_tile_load(const NttPass &p, const NttTables &t, const Fr *data, u
         lds_put(lds, ntt_plane_slots(p), ntt_lds_slot(p, rho, col), v);
     }
 }
-// phase 2: one radix-2 stage over the rows.  stage = 0 .. log_r-1 in execution order.
-MI_HD void ntt_tile_stage(const NttPass &p, const NttTables &t, u32 stage, u32 tid, u32 nthr, U4 *lds) {
+// phase 2: one radix-2 stage over the rows.  stage = 0 .. log_r-1 in execution order.  tile: which tile this is -- read only by
+// a pass that carries tw_stage (its twiddles depend on the tile's columns)
+MI_HD void ntt_tile_stage(const NttPass &p, const NttTables &t, u32 stage, u32 tid, u32 nthr, U4 *lds, u64 tile = 0) {
     const u32 E = 1u << (p.log_r + p.log_c);
     // DIF: half-distance d = R/2, R/4, ..., 1 ; DIT: d = 1, 2, ..., R/2
     const u32 log_d = p.dit ? stage : (p.log_r - 1 - stage);
@@ -186,8 +216,9 @@ MI_HD void ntt_tile_stage(const NttPass &p, const NttTables &t, u32 stage, u32 t
         u32 s0 = ntt_lds_slot(p, r0, col), s1 = ntt_lds_slot(p, r1, col);
         const u32 PL = ntt_plane_slots(p);
         Fr x = lds_get(lds, PL, s0), y = lds_get(lds, PL, s1);
-        // twiddle w_(2d)^j = w_4096^(j * 2048/d)
-        const Fr *w = j ? &t.small[j << (11 - log_d)] : nullptr;
+        // twiddle w_(2d)^j = w_4096^(j * 2048/d), or the global stage's w_(2dS)^(j*S + lo)
+        const Fr *run = ntt_stage_run(p, tile, col);
+        const Fr *w = run ? &run[d + j] : j ? &t.small[j << (11 - log_d)] : nullptr;
         if (p.dit) ntt_bfly_dit(x, y, w); else ntt_bfly_dif(x, y, w);
         lds_put(lds, PL, s0, x);
         lds_put(lds, PL, s1, y);

@@ -34,8 +34,37 @@ MI_D void wave_select_trade(Fr &x0, Fr &x1, u32 lane, u32 m) {
 #pragma unroll
     for (int i = 0; i < 8; i++) { x0.l[i] = hi ? recv.l[i] : x0.l[i]; x1.l[i] = hi ? x1.l[i] : recv.l[i]; }
 }
-// small[j] = w_4096^j (forward or inverse root): w_(2d)^j = small[j << (11 - log2 d)]
-MI_D void wave_ntt128(Fr &x0, Fr &x1, u32 lane, bool dit, const Fr *small) {
+// The same seven stages with the twiddles of the global stages (NttPass::tw_stage): run = the column's run (ntt_stage_run), the
+// butterfly at half-distance d takes run[d + (L & (d-1))] -- 32 d contiguous bytes per wave -- and the stage at d = 1 has a product
+// like every other.  The next stage's twiddle is read before this stage's trade and butterfly: the first runs come from HBM.
+MI_D void wave_ntt128_tw(Fr &x0, Fr &x1, u32 lane, bool dit, const Fr *run) {
+    if (!dit) {
+        Fr w = run[64 + lane];
+#pragma unroll 1
+        for (int log_d = 6; log_d >= 0; log_d--) {
+            const u32 d = 1u << log_d;
+            Fr wn = w;
+            if (log_d) wn = run[(d >> 1) + (lane & ((d >> 1) - 1))];
+            if (log_d < 6) wave_select_trade(x0, x1, lane, d);
+            ntt_bfly_dif(x0, x1, &w);
+            w = wn;
+        }
+    } else {
+        Fr w = run[1];
+#pragma unroll 1
+        for (int log_d = 0; log_d <= 6; log_d++) {
+            const u32 d = 1u << log_d;
+            Fr wn = w;
+            if (log_d < 6) wn = run[2 * d + (lane & (2 * d - 1))];
+            if (log_d) wave_select_trade(x0, x1, lane, d >> 1);
+            ntt_bfly_dit(x0, x1, &w);
+            w = wn;
+        }
+    }
+}
+// small[j] = w_4096^j (forward or inverse root): w_(2d)^j = small[j << (11 - log2 d)].  run != null: wave_ntt128_tw
+MI_D void wave_ntt128(Fr &x0, Fr &x1, u32 lane, bool dit, const Fr *small, const Fr *run = nullptr) {
+    if (run) { wave_ntt128_tw(x0, x1, lane, dit, run); return; }
     if (!dit) {
 #pragma unroll 1
         for (int log_d = 6; log_d >= 0; log_d--) {

@@ -217,6 +217,9 @@ int32_t mi_debug_set_msm_precompute_batched(mi_ctx *ctx, uint32_t on);
  *   "item_l1", "item_l2", "reduce_seg"   = the L1, L2, seg of mi_debug_set_msm_plan, one at a time (a flat sort keeps its own item size: "flat_item_l1")
  *   "hold_accum" 0 | 1       = mi_debug_set_prove_schedule
  *   "ntt_lds_floor_kb" 0..160   LDS every NTT pass workgroup requests at least (caps the workgroups per CU)
+ *   "ntt_stage_twiddles" 0 | 1   computeH's strided passes: 1 (default) = stage twiddles by global index from one M-entry table per pass and
+ *                            root, no inter-pass product; 0 = tile-local stage twiddles and one product per element at the pass's edge (the
+ *                            N-entry direct table), the yardstick.  Takes effect when computeH next builds its tables.  Same h, word for word
  *   "scale_powers_window" 0 | 2..5   phase 1's scalar multiplications (csrc/scale_powers.cuh): 2..5 = the fixed-window ladder of that width
  *                            (default 5, measured fastest: profiles/phase1.txt); 0 = the bit-by-bit xyzz_scale of the point NTT on the same scalars, the yardstick.  Same points
  *   "scale_powers_chunk" 0 | 64..2^24   lanes per chunk of that driver, which sizes its table workspace (0 = the default, 2^18)

@@ -7,7 +7,7 @@ import sys
 import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SETUP = ("k_gen_", "k_xyzz_dbl_c", "k_xyzz_batch_to_affine", "k_xyzz_from_affine", "k_g1_to_rprime", "k_g2_to_rprime", "k_expand_points", "k_field_op", "k_pow_table",
-         "k_tw_layout", "k_sc_layout", "k_msm2_precompute", "__amd_rocclr_fillBuffer")
+         "k_tw_layout", "k_tw_stage_layout", "k_sc_layout", "k_msm2_precompute", "__amd_rocclr_fillBuffer")
 
 
 def summary(db, proofs):
